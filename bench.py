@@ -14,8 +14,16 @@ metric = APD-GICP linearisations per second (one unit = one linearize(): corresp
 reduction for one pair at one pose); GP windows/s is reported beside it.  Multi-GPU: every rank owns its own batch (weak
 scaling, no data-path collective), value = all units / max-over-ranks time.
 
-After the timed region rank 0 CHECKS the results of the timed path against the CPU oracle (one pair, one window) and fails the
-run on a mismatch: a throughput line is only printed for results that are right.
+A plain run sets up, warms up, times --steps steps, writes the last step's results if --dump-outputs DIR is given, and prints
+the JSON line (metric, value, unit, higher_is_better, dtype, ms_per_step, ...).  Everything else is behind --full: per-stage
+device times, rooflines and the untimed exhaustive-search step, the RCCL co-registration of N > 1, the CPU baseline, and the
+post-run CHECK of the timed path's results against the CPU oracle (one pair, one window), which fails the run on a mismatch:
+with --full a throughput line is only printed for results that are right.
+
+--dump-outputs DIR writes what the last timed step returned to its caller, rank 0's batch, as DIR/<name>.npy (float32 /
+float64): apd_T [pairs, 4, 4], apd_H [pairs, 6, 6], apd_converged, apd_nr_iterations, apd_n_linearize [pairs], and for c4
+ugpm_records [windows, 83] (the raw record of gorio_ugpm_preint_batch).  Inputs are seeded: the same arguments give the same
+inputs on every run.
 """
 import argparse
 import importlib
@@ -55,15 +63,20 @@ def parse():
                     help="gn (default): the metric's fixed Gauss-Newton iterations, convergence test disabled; lm: the optimiser and tolerances the reference "
                          "ships (Levenberg-Marquardt, trans-eps 0.1, rot-eps 2e-3, <= 64 iterations) -- a secondary line, aligns/s is its natural unit")
     ap.add_argument("--search", default="pruned", choices=["brute", "pruned"], help="correspondence / k-NN search: both are exact and return identical indices")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-check", action="store_true", help="skip the post-run comparison with the CPU oracle (profiling runs)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check everything beyond the headline: per-stage device times and rooflines, the exhaustive-search step, "
+                         "the N > 1 co-registration, the CPU baseline and the comparison with the CPU oracle")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed (rank 0) as DIR/<name>.npy, for comparing two builds output for output")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-check", action="store_true", help="with --full: skip the post-run comparison with the CPU oracle (profiling runs)")
     ap.add_argument("--no-overlap", action="store_true", help="run the GP windows after the scan matching instead of beside it")
     ap.add_argument("--ugpm-four-launch", action="store_true", help="experiment: the rotation fit as four launches per iteration (gorio_ugpm_debug_set_schedule(0))")
-    ap.add_argument("--no-exhaustive", action="store_true", help="skip the extra untimed step that times the exhaustive search kernel")
+    ap.add_argument("--no-exhaustive", action="store_true", help="with --full: skip the extra untimed step that times the exhaustive search kernel")
     ap.add_argument("--dist-backend", default="nccl", choices=["nccl", "gloo"], help="nccl (= RCCL) in production; gloo only to rehearse the N > 1 path on one GPU")
     ap.add_argument("--all-ranks-on-device", type=int, default=-1, help="rehearsal only: put every rank on this device instead of LOCAL_RANK")
     ap.add_argument("--cpu-sample-pairs", type=int, default=1)
-    ap.add_argument("--coreg-points", type=int, default=262144, help="N > 1 only: source points of the sharded-source co-registration that follows the timed batch")
+    ap.add_argument("--coreg-points", type=int, default=262144, help="N > 1 with --full: source points of the sharded-source co-registration that follows the timed batch")
     ap.add_argument("--coreg-map-points", type=int, default=1000000)
     ap.add_argument("--coreg-only", action="store_true", help="N > 1: skip the batch workload and run only the RCCL co-registration (tests)")
     ap.add_argument("--latency", action="store_true",
@@ -204,7 +217,7 @@ def main():
             t=None if shared_map else [to_dev(tx[:, 0]), to_dev(tx[:, 1]), to_dev(tx[:, 2]), to_dev(tl)], n=sx.shape[0], m=tx.shape[0]))
     torch.cuda.synchronize()
     objs = [gorio.ApdGicp(device=local_rank, **params) for _ in range(n_pairs)]
-    objs[0].setProfiling(True)
+    objs[0].setProfiling(args.full)  # HIP events per stage on the launch stream: only --full reports them
     map_setup_s = None
     if shared_map:  # ONE upload, index and k-NN of the map per GPU; every other handle references it (gorio_apd_set_target_shared)
         t0 = time.perf_counter()
@@ -275,7 +288,7 @@ def main():
 
     for _ in range(args.warmup):
         step()
-    objs[0].setProfiling(True)  # reset the stage clocks: they now cover exactly the timed region
+    objs[0].setProfiling(args.full)  # reset the stage clocks: they now cover exactly the timed region
     for k in phase:
         phase[k] = 0.0
     ugpm_stage.clear()
@@ -307,10 +320,12 @@ def main():
     resident_shape = [dict(n=r["n"], m=r["m"]) for r in resident]
     timed_T = [r["T"].copy() for r in last["apd"]]
     timed_rec = None if windows is None else last["ugpm"].copy()
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, last["apd"], timed_rec)
 
     # the exhaustive kernel on the same resident data, one untimed step, for the roofline of the north star's brute-force search
     brute = None
-    if args.search == "pruned" and not args.no_exhaustive:
+    if args.full and args.search == "pruned" and not args.no_exhaustive:
         for o in objs:
             o.set_params(search=0)
         objs[0].setProfiling(True)
@@ -323,9 +338,9 @@ def main():
 
     coreg = None
     coreg_hung = False
-    if dist is not None and args.workload == "c4" and args.all_ranks_on_device >= 0 and not os.environ.get("GORIO_BENCH_FORCE_COREG"):
+    if args.full and dist is not None and args.workload == "c4" and args.all_ranks_on_device >= 0 and not os.environ.get("GORIO_BENCH_FORCE_COREG"):
         coreg = {"skipped": "rehearsal with every rank on one device: RCCL cannot place two ranks of a communicator on one GPU", "ok": True}
-    elif dist is not None and args.workload == "c4":
+    elif args.full and dist is not None and args.workload == "c4":
         # BASELINE configs[4] / SURVEY 8(e) row 2: ONE large co-registration, source sharded over the ranks, one ncclAllReduce of the 28
         # normal-equation sums per linearisation -- after (and outside) the timed weak-scaling batch.  Every rank runs it in a CHILD
         # process (`bench.py --coreg-only`, its own rendezvous): a collective that never completes, or a crash inside it, must not take
@@ -343,12 +358,12 @@ def main():
             out["map_setup_ms"] = 1e3 * map_setup_s  # upload + search index + k-NN covariances of the shared map, once per GPU
         check = None
         oracle_sample = None
-        if not args.no_check:
+        if args.full and not args.no_check:
             check, oracle_sample = check_against_oracle(args, pairs, windows, timed_T, timed_rec)
             out["check"] = check
             if not check["ok"]:
                 rc = 3
-        if not args.no_cpu_baseline:
+        if args.full and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(pairs[: args.cpu_sample_pairs], args, windows)
         if rc == 0:
             print(json.dumps(out), flush=True)
@@ -424,6 +439,23 @@ def guarded(fn, torch, local_rank, timeout_s):
     if th.is_alive():
         return {"ok": False, "timed_out": True, "error": f"no result after {timeout_s:.0f} s"}
     return box["out"]
+
+
+def dump_outputs(path, apd_results, ugpm_records):
+    """--dump-outputs: what the last timed step handed its caller (align_batch's result dicts, UgpmBatch.run()'s record array), one
+    .npy per array in float32 / float64.  C4 writes about 60 kB."""
+    os.makedirs(path, exist_ok=True)
+    arrays = {
+        "apd_T": np.stack([r["T"] for r in apd_results]).astype(np.float32),
+        "apd_H": np.stack([r["H"] for r in apd_results]).astype(np.float64),
+        "apd_converged": np.array([r["converged"] for r in apd_results], np.float64),
+        "apd_nr_iterations": np.array([r["nr_iterations"] for r in apd_results], np.float64),
+        "apd_n_linearize": np.array([r["n_linearize"] for r in apd_results], np.float64),
+    }
+    if ugpm_records is not None:
+        arrays["ugpm_records"] = np.asarray(ugpm_records, np.float64)
+    for name, a in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), a)
 
 
 # ------------------------------------------------------------------------------------------- RCCL co-registration (N > 1)
@@ -645,6 +677,33 @@ def valu_roofline(kernel, entry, avg_s, extra_note=""):
 
 def report(args, world, n_pairs, n, m, resident, units, wins, dt, stage_s, stage_n, ugpm_stage, ugpm_count, phase, brute):
     wl = args.workload
+    out = {
+        "metric": "APD-GICP GN iters/sec on 16k-pt scans + GP-preint windows/sec",
+        "value": units / dt,
+        "unit": "linearisations/s",
+        "n_gpus": world,
+        "steps": args.steps,
+        "warmup": args.warmup,
+        "ms_per_step": 1e3 * dt / args.steps,
+        "higher_is_better": True,
+        "scaling": "weak",
+        "vs_baseline": None,
+        "dtype": "f32 search / f64 accumulate",
+        "data": "synthetic",
+        "config": {
+            "workload": {"c4": "C4: 64 scan pairs 16384x16384 + 64 GP windows 1 s @ 200 Hz per GPU, k-NN covariances + 20 fixed GN iterations per pair",
+                         "c3": "C3: 16384-pt scan vs 100000-pt local map, 20 fixed GN iterations",
+                         "c5": f"C5, one rank's share: {n_pairs} scans of {n} points against ONE shared {m}-point map resident on the GPU "
+                               "(source k-NN covariances + 20 fixed GN iterations per scan; map index and covariances are setup)"}[wl],
+            "pairs_per_gpu": n_pairs, "source_points": n, "target_points": m, "iterations": args.iters if args.optimizer == "gn" else "until converged (<= 64)",
+            "optimizer": "GN (convergence test disabled)" if args.optimizer == "gn" else "LM, shipped tolerances (trans-eps 0.1, rot-eps 2e-3)",
+            "search": args.search, "parallelism": f"batch shard x{world} (no collective)"},
+        "gp_windows_per_s": (wins / dt) if wins else None,
+        "aligns_per_s": n_pairs * world * args.steps / dt,
+        "host_phase_seconds": phase,
+    }
+    if not args.full:
+        return out
     counters = load_counters()
     steps = args.steps
     knn_name = "knn_kth_kernel<20> + knn_collect_kernel<20>" if args.search == "pruned" else "knn_partial_kernel<20> + cov_finalize_kernel<20>"
@@ -684,35 +743,12 @@ def report(args, world, n_pairs, n, m, resident, units, wins, dt, stage_s, stage
         kernels[k]["ms_per_step"] = 1e3 * s / steps
     if counters.get("_stale"):
         roof["note"] = "STALE: profiles/kernel_counters.json was collected from other kernel sources; " + roof.get("note", "")
-    out = {
-        "metric": "APD-GICP GN iters/sec on 16k-pt scans + GP-preint windows/sec",
-        "value": units / dt,
-        "unit": "linearisations/s",
-        "n_gpus": world,
-        "steps": args.steps,
-        "warmup": args.warmup,
-        "ms_per_step": 1e3 * dt / args.steps,
-        "higher_is_better": True,
-        "scaling": "weak",
-        "vs_baseline": None,
-        "dtype": "f32 search / f64 accumulate",
-        "data": "synthetic",
-        "config": {
-            "workload": {"c4": "C4: 64 scan pairs 16384x16384 + 64 GP windows 1 s @ 200 Hz per GPU, k-NN covariances + 20 fixed GN iterations per pair",
-                         "c3": "C3: 16384-pt scan vs 100000-pt local map, 20 fixed GN iterations",
-                         "c5": f"C5, one rank's share: {n_pairs} scans of {n} points against ONE shared {m}-point map resident on the GPU "
-                               "(source k-NN covariances + 20 fixed GN iterations per scan; map index and covariances are setup)"}[wl],
-            "pairs_per_gpu": n_pairs, "source_points": n, "target_points": m, "iterations": args.iters if args.optimizer == "gn" else "until converged (<= 64)",
-            "optimizer": "GN (convergence test disabled)" if args.optimizer == "gn" else "LM, shipped tolerances (trans-eps 0.1, rot-eps 2e-3)",
-            "search": args.search, "parallelism": f"batch shard x{world} (no collective)"},
-        "gp_windows_per_s": (wins / dt) if wins else None,
-        "aligns_per_s": n_pairs * world * args.steps / dt,
-        "host_phase_seconds": phase,
+    out.update({
         "device_ms_per_step": {k: 1e3 * v for k, v in per_step.items()},
         "stage_launches": {"knn_cov": stage_n[0], "index_build": stage_n[4], "nn_search": stage_n[1], "linearize": stage_n[2], "solve": stage_n[3]},
         "roofline": roof,
         "kernels": kernels,
-    }
+    })
     # what the exact pruning saves against the exhaustive search it replaces: a ratio of algorithmic work rates, NOT a roofline
     if args.search == "pruned" and stage_n[1]:
         nn_avg = avg(stage_s[1], stage_n[1])

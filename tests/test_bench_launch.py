@@ -6,6 +6,7 @@ import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -48,7 +49,7 @@ def test_two_ranks_rehearsal_on_one_gpu(gpu):
     """`bench.py --gpus 2` with no launcher: the script itself starts two ranks (here both on device 0, reduction tensors over gloo);
     rank 0 prints ONE line with n_gpus = 2 and the work of both ranks."""
     r = _run(["--gpus", "2", "--all-ranks-on-device", "0", "--dist-backend", "gloo", "--pairs", "4", "--steps", "2", "--warmup", "1",
-              "--no-cpu-baseline", "--no-exhaustive"])
+              "--full", "--no-cpu-baseline", "--no-exhaustive"])
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
     assert len(lines) == 1
@@ -56,6 +57,32 @@ def test_two_ranks_rehearsal_on_one_gpu(gpu):
     assert out["n_gpus"] == 2 and out["scaling"] == "weak" and out["config"]["pairs_per_gpu"] == 4
     assert out["value"] == pytest.approx(2 * 4 * 20 * 2 / (out["ms_per_step"] * 1e-3 * 2), rel=1e-6)  # both ranks' linearisations / max time
     assert out["check"]["ok"]
+
+
+@pytest.mark.gpu
+def test_plain_run_times_the_steps_and_dumps_the_last_one(gpu, tmp_path):
+    """A plain run prints the headline only (no oracle check, CPU baseline or roofline: those are --full), its value counts exactly
+    --steps steps, and --dump-outputs writes what the last timed step returned, in float32 / float64."""
+    r = _run(["--gpus", "1", "--pairs", "4", "--steps", "3", "--warmup", "1", "--dump-outputs", str(tmp_path)])
+    assert r.returncode == 0, r.stderr[-2000:]
+    lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
+    assert len(lines) == 1
+    out = json.loads(lines[0])
+    for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+        assert k in out
+    assert out["steps"] == 3 and out["higher_is_better"] is True and out["unit"] == "linearisations/s"
+    assert out["value"] == pytest.approx(4 * 20 * 3 / (out["ms_per_step"] * 1e-3 * 3), rel=1e-6)
+    assert not {"check", "cpu_baseline", "roofline", "kernels", "device_ms_per_step"} & set(out)
+    T = np.load(os.path.join(tmp_path, "apd_T.npy"))
+    H = np.load(os.path.join(tmp_path, "apd_H.npy"))
+    nlin = np.load(os.path.join(tmp_path, "apd_n_linearize.npy"))
+    rec = np.load(os.path.join(tmp_path, "ugpm_records.npy"))
+    assert T.shape == (4, 4, 4) and T.dtype == np.float32 and np.all(np.isfinite(T))
+    assert H.shape == (4, 6, 6) and H.dtype == np.float64
+    assert nlin.dtype == np.float64 and np.all(nlin == 20)
+    assert rec.shape[0] == 4 and rec.dtype == np.float64 and np.all(np.isfinite(rec))
+    total = sum(os.path.getsize(os.path.join(tmp_path, f)) for f in os.listdir(tmp_path))
+    assert total < 64 << 20
 
 
 @pytest.mark.gpu

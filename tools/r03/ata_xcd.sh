@@ -6,7 +6,7 @@ timeout -k 10 600 python -m pytest tests/test_ugpm_gpu.py tests/test_golden.py -
 rc=$?
 tail -3 gpurun_out/r03/ata_tests.log
 [ $rc -eq 0 ] || exit $rc
-B="--steps 40 --warmup 5 --no-cpu-baseline --no-exhaustive --no-check"
+B="--full --steps 40 --warmup 5 --no-cpu-baseline --no-exhaustive --no-check"
 for rep in 1 2; do
 for v in default ata_noxcd; do
   if [ $v = default ]; then unset GORIO_AMD_LIB; else export GORIO_AMD_LIB=$PWD/tools/variants/$v.so; fi

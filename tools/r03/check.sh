@@ -4,7 +4,7 @@ timeout -k 10 1000 python -m pytest tests -m gpu -x -q > gpurun_out/r03/gpu_test
 rc=$?
 tail -3 gpurun_out/r03/gpu_tests_21.log
 [ $rc -eq 0 ] || exit $rc
-B="--steps 20 --warmup 3 --no-cpu-baseline --no-exhaustive --no-check"
+B="--full --steps 20 --warmup 3 --no-cpu-baseline --no-exhaustive --no-check"
 timeout -k 10 300 python bench.py $B --no-overlap > gpurun_out/r03/ab21_no.json 2> gpurun_out/r03/ab21_no.err || exit 1
 timeout -k 10 300 python bench.py $B > gpurun_out/r03/ab21_ov.json 2> gpurun_out/r03/ab21_ov.err || exit 1
 timeout -k 10 300 python bench.py --latency --latency-reps 50 > gpurun_out/r03/lat21.json 2> gpurun_out/r03/lat21.err || exit 1

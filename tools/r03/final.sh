@@ -7,12 +7,12 @@ done
 for wl in c3 c4 c5; do
   GORIO_AMD_LIB=$PWD/tools/variants/stats.so timeout -k 10 400 python tools/search_work.py $wl 20 --merge > profiles/r03/search_work_$wl.txt 2>&1 || { tail -20 profiles/r03/search_work_$wl.txt; exit 1; }
 done
-timeout -k 10 400 python bench.py --steps 40 --warmup 3 > profiles/r03/bench_c4.json 2> gpurun_out/r03/bench_c4.err || { tail -5 gpurun_out/r03/bench_c4.err; exit 1; }
+timeout -k 10 400 python bench.py --full --steps 40 --warmup 3 > profiles/r03/bench_c4.json || exit 1
 for k in 1 2 3; do timeout -k 10 400 python bench.py --steps 20 --warmup 3 --no-cpu-baseline --no-check --no-exhaustive 2>/dev/null | python -c "import sys,json; d=json.loads(sys.stdin.read()); print(round(d['ms_per_step'],3), round(d['value']), round(d['gp_windows_per_s']))" >> profiles/r03/bench_c4_repeats.txt; done
-timeout -k 10 400 python bench.py --steps 20 --warmup 3 --no-overlap --no-cpu-baseline > profiles/r03/bench_c4_no_overlap.json 2> gpurun_out/r03/bench_c4no.err || exit 1
-timeout -k 10 400 python bench.py --steps 20 --warmup 3 --optimizer lm > profiles/r03/bench_c4_lm.json 2> gpurun_out/r03/bench_c4lm.err || exit 1
-timeout -k 10 400 python bench.py --workload c3 --steps 40 --warmup 3 > profiles/r03/bench_c3.json 2> gpurun_out/r03/bench_c3.err || { tail -5 gpurun_out/r03/bench_c3.err; exit 1; }
-timeout -k 10 600 python bench.py --workload c5 --steps 10 --warmup 2 > profiles/r03/bench_c5.json 2> gpurun_out/r03/bench_c5.err || { tail -5 gpurun_out/r03/bench_c5.err; exit 1; }
+timeout -k 10 400 python bench.py --full --steps 20 --warmup 3 --no-overlap --no-cpu-baseline > profiles/r03/bench_c4_no_overlap.json || exit 1
+timeout -k 10 400 python bench.py --full --steps 20 --warmup 3 --optimizer lm > profiles/r03/bench_c4_lm.json || exit 1
+timeout -k 10 400 python bench.py --full --workload c3 --steps 40 --warmup 3 > profiles/r03/bench_c3.json || exit 1
+timeout -k 10 600 python bench.py --full --workload c5 --steps 10 --warmup 2 > profiles/r03/bench_c5.json || exit 1
 timeout -k 10 900 python bench.py --latency > profiles/r03/latency.json 2> gpurun_out/r03/latency.err || { tail -5 gpurun_out/r03/latency.err; exit 1; }
 timeout -k 10 1000 python -m pytest tests -m gpu -q > profiles/r03/gpu_tests_r03.txt 2>&1; tail -3 profiles/r03/gpu_tests_r03.txt
 cp profiles/kernel_counters.json gpurun_out/r03/kernel_counters_final.json

@@ -6,7 +6,7 @@ timeout -k 10 600 python -m pytest tests/test_ugpm_gpu.py -m gpu -x -q > gpurun_
 rc=$?
 tail -15 gpurun_out/r03/ugpm_tests_ab.log
 [ $rc -eq 0 ] || exit $rc
-B="--steps 40 --warmup 5 --no-cpu-baseline --no-exhaustive --no-check"
+B="--full --steps 40 --warmup 5 --no-cpu-baseline --no-exhaustive --no-check"
 for rep in 1 2; do
   timeout -k 10 300 python bench.py $B --no-overlap > gpurun_out/r03/uab_no3_$rep.json 2> gpurun_out/r03/uab.err || exit 1
   timeout -k 10 300 python bench.py $B --no-overlap --ugpm-four-launch > gpurun_out/r03/uab_no4_$rep.json 2> gpurun_out/r03/uab.err || exit 1
