@@ -50,7 +50,7 @@ APD_SYMBOLS = [
     "gorio_apd_set_source_covariances", "gorio_apd_set_target_covariances", "gorio_apd_get_source_covariances",
     "gorio_apd_get_target_covariances", "gorio_apd_calculate_covariances", "gorio_apd_get_knn_indices", "gorio_apd_align",
     "gorio_apd_align_batch", "gorio_apd_linearize", "gorio_apd_compute_error", "gorio_apd_get_correspondences",
-    "gorio_apd_get_mahalanobis", "gorio_apd_transform_source", "gorio_apd_fitness_score", "gorio_apd_set_profiling",
+    "gorio_apd_get_mahalanobis", "gorio_apd_transform_source", "gorio_apd_fitness_score", "gorio_apd_fitness_score_batch", "gorio_apd_set_profiling",
     "gorio_apd_get_stage_times", "gorio_apd_set_target_shared", "gorio_comm_get_unique_id", "gorio_apd_comm_init", "gorio_apd_comm_destroy", "gorio_apd_comm_info", "gorio_apd_debug_set_shard", "gorio_apd_debug_set_schedule", "gorio_apd_set_target_submap", "gorio_apd_get_target_points",
 ]
 
@@ -426,3 +426,20 @@ def align_batch(objs, guesses=None):
         o._converged = bool(conv[q])
         out.append(dict(T=T[q], H=H[q], converged=bool(conv[q]), nr_iterations=int(nit[q]), n_linearize=int(nlin[q])))
     return out
+
+
+def fitness_score_batch(regs, Ts=None, max_range=np.finfo(np.float64).max, inlier_dist=0.0):
+    """gorio_apd_fitness_score_batch over a list of ApdGicp objects (all on one device): the getFitnessScore / inlier fraction of every
+    object at its pose in one pass.  Ts: n poses (4x4), or None for every object's last final transformation.  inlier_dist <= 0 means the
+    nodelet's 0.5 m.  Returns (scores, inlier_fractions), float64 arrays equal bit for bit to the single getFitnessScore calls."""
+    lib = load_library()
+    n = len(regs)
+    scores = np.zeros(n, np.float64)
+    inl = np.zeros(n, np.float64)
+    if n == 0:
+        return scores, inl
+    T = np.ascontiguousarray(np.stack([o._final for o in regs]) if Ts is None else Ts, np.float32).reshape(n, 16)
+    arr = (C.c_void_p * n)(*[o._h for o in regs])
+    rc = lib.gorio_apd_fitness_score_batch(arr, n, _p(T, C.c_float), C.c_double(max_range), C.c_double(inlier_dist), _p(scores, C.c_double), _p(inl, C.c_double))
+    _check(regs[0]._h, rc)
+    return scores, inl

@@ -972,6 +972,24 @@ int align_impl(gorio_apd** hs, int count, const float* guesses, float* T_out, do
   return GORIO_OK;
 }
 
+// Search bound of a fitness score: nothing farther than max(max_range, inlier_dist^2) is counted by either statistic (rounded up to a float).
+float fitness_bound(double max_range, double inlier_sq) {
+  const double lim = std::max(max_range, inlier_sq);
+  float bf = FLT_MAX;
+  if (lim < (double)FLT_MAX) {
+    bf = (float)lim;
+    if ((double)bf < lim) bf = std::nextafterf(bf, FLT_MAX);
+  }
+  return bf;
+}
+
+// workgroups per query wave of a fitness score's pruned search (a power of two in [1, 16]); any value returns the same keys
+int fitness_splits(long waves) {
+  int splits = (int)std::min<long>(16, std::max<long>(1, 4096 / (waves > 0 ? waves : 1)));
+  while (splits & (splits - 1)) splits &= splits - 1;
+  return splits;
+}
+
 int single_desc(gorio_apd* h) {
   int rc = ensure_batch(h, 1);
   if (rc) return rc;
@@ -1587,18 +1605,8 @@ int gorio_apd_fitness_score(gorio_apd_t* h, const float T[16], double max_range,
   if (!(inlier_dist > 0.0)) inlier_dist = 0.5;  // const double max_correspondence_dist = 0.5, SMO:677
   const double inlier_sq = inlier_dist * inlier_dist;
   if (pruned) {
-    // nothing farther than max(max_range, inlier_dist^2) is counted by either statistic: that is the search bound (rounded up to a float)
-    const double lim = std::max(max_range, inlier_sq);
-    float bf = FLT_MAX;
-    if (lim < (double)FLT_MAX) {
-      bf = (float)lim;
-      if ((double)bf < lim) bf = std::nextafterf(bf, FLT_MAX);
-    }
     const int waves = (h->src->n + 63) / 64;
-    int splits = 4096 / (waves > 0 ? waves : 1);
-    splits = std::min(16, std::max(1, splits));
-    while (splits & (splits - 1)) splits &= splits - 1;
-    launch_pruned(dim3((roundup(h->src->n, 512) + 255) / 256, splits, 1), h->stream, h->d_desc, bf, 0);
+    launch_pruned(dim3((roundup(h->src->n, 512) + 255) / 256, fitness_splits(waves), 1), h->stream, h->d_desc, fitness_bound(max_range, inlier_sq), 0);
   } else {
     nn_search_kernel<<<dim3(nbx, d.nn_splits, 1), 256, 0, h->stream>>>(h->d_desc);
   }
@@ -1613,6 +1621,110 @@ int gorio_apd_fitness_score(gorio_apd_t* h, const float T[16], double max_range,
     for (int q = 0; q < 3; ++q) out[q] += part[(size_t)bk * 3 + q];
   *score = out[1] > 0 ? out[0] / out[1] : DBL_MAX;  // pcl: returns max double when no correspondence is in range
   if (inlier_fraction) *inlier_fraction = out[2] / (double)h->src->n;
+  return GORIO_OK;
+}
+
+int gorio_apd_fitness_score_batch(gorio_apd_t** handles, int count, const float* T, double max_range, double inlier_dist, double* score, double* inlier_fraction) {
+  if (count == 0) return GORIO_OK;
+  if (!handles || count < 0 || !T || !score) return GORIO_ERR_INVALID;
+  gorio_apd* lead = handles[0];
+  if (!lead) return GORIO_ERR_INVALID;
+  // every check comes before the first change to any handle: an error leaves them all as they were
+  {
+    std::unordered_set<gorio_apd*> distinct;
+    for (int q = 0; q < count; ++q) {
+      gorio_apd* h = handles[q];
+      const std::string at = "fitness_score_batch: handles[" + std::to_string(q) + "]: ";
+      if (!h) return fail(lead, GORIO_ERR_INVALID, at + "null handle");
+      if (h->device != lead->device) return fail(lead, GORIO_ERR_INVALID, at + "all handles of a batch must live on one device");
+      if (!distinct.insert(h).second) return fail(lead, GORIO_ERR_INVALID, at + "the same handle appears twice in a batch (its buffers would be raced on)");
+      if (!h->src->present || !h->tgt->present) return fail(lead, GORIO_ERR_STATE, at + "clouds not set");
+      if ((h->comm || h->shard_only) && h->comm_world > 1)
+        return fail(lead, GORIO_ERR_STATE, at + "this handle searches only its rank's share of the source (gorio_apd_comm_init); score the pose on an unsharded handle");
+    }
+  }
+  HIP_TRY(lead, hipSetDevice(lead->device));
+  // pairs in descriptor order: the pruned-search ones first, then the brute-force ones (each handle searches as its single call would)
+  std::vector<int> order;
+  for (int pass = 0; pass < 2; ++pass)
+    for (int q = 0; q < count; ++q)
+      if ((handles[q]->params.search == GORIO_SEARCH_PRUNED) == (pass == 0)) order.push_back(q);
+  int n_pruned = 0;
+  long total_src_waves = 0, pruned_waves = 0;
+  int max_n = 1, max_nbx = 1, max_spad_pruned = 512, max_nbx_brute = 1, max_splits_brute = 1;
+  std::vector<std::pair<gorio_apd*, DevCloud*>> all;
+  for (int q = 0; q < count; ++q) {
+    gorio_apd* h = handles[q];
+    int rc = ensure_points(h, h->src->n);
+    if (rc) {
+      if (h != lead) lead->err = "fitness_score_batch: handles[" + std::to_string(q) + "]: " + h->err;
+      return rc;
+    }
+    const int waves = (h->src->n + 63) / 64;
+    total_src_waves += waves;
+    max_n = std::max(max_n, h->src->n);
+    max_nbx = std::max(max_nbx, (h->src->n + 255) / 256);
+    if (h->params.search == GORIO_SEARCH_PRUNED) {
+      ++n_pruned;
+      pruned_waves += waves;
+      max_spad_pruned = std::max(max_spad_pruned, roundup(h->src->n, 512));
+      all.emplace_back(h, h->src.get());
+      all.emplace_back(h, h->tgt.get());
+    }
+  }
+  if (!all.empty()) {  // ONE index build for every cloud that lacks one; a target shared by several handles is one cloud
+    int rc = run_index_build(lead, all);
+    if (rc) return rc;
+  }
+  if (int rc = ensure_batch(lead, count)) return rc;
+  std::vector<PairDesc> descs(count);
+  std::vector<PairState> states(count);
+  for (int k = 0; k < count; ++k) {
+    const int q = order[k];
+    gorio_apd* h = handles[q];
+    double Td[16];
+    for (int i = 0; i < 16; ++i) Td[i] = (double)T[(size_t)q * 16 + i];
+    init_state(states[k], Td);
+    for (int i = 0; i < 12; ++i) states[k].Tf[i] = T[(size_t)q * 16 + i];
+    fill_desc(h, descs[k], h->d_state, total_src_waves);
+    if (k >= n_pruned) {
+      max_nbx_brute = std::max(max_nbx_brute, descs[k].nblk);
+      max_splits_brute = std::max(max_splits_brute, descs[k].nn_splits);
+    }
+  }
+  const size_t n_part = (size_t)count * max_nbx * 3;
+  if (n_part > lead->fit_cap) {
+    hipFree(lead->d_fit);
+    lead->d_fit = nullptr;
+    lead->fit_cap = 0;
+    HIP_TRY(lead, hipMalloc(&lead->d_fit, sizeof(double) * n_part));
+    lead->fit_cap = n_part;
+  }
+  if (int rc = upload_staged(lead, lead->pin_desc, lead->d_desc, descs.data(), sizeof(PairDesc) * count)) return rc;
+  if (int rc = upload_staged(lead, lead->pin_states, lead->d_states_batch, states.data(), sizeof(PairState) * count)) return rc;
+  scatter_states_kernel<<<count, 64, 0, lead->stream>>>(lead->d_desc, lead->d_states_batch);
+  arm_keys_kernel<<<dim3(std::min(64, (max_n + 255) / 256), count), 256, 0, lead->stream>>>(lead->d_desc);
+  if (!(inlier_dist > 0.0)) inlier_dist = 0.5;  // const double max_correspondence_dist = 0.5, SMO:677
+  const double inlier_sq = inlier_dist * inlier_dist;
+  if (n_pruned > 0)
+    launch_pruned(dim3(max_spad_pruned / 256, fitness_splits(pruned_waves), n_pruned), lead->stream, lead->d_desc, fitness_bound(max_range, inlier_sq), 0);
+  if (n_pruned < count) nn_search_kernel<<<dim3(max_nbx_brute, max_splits_brute, count - n_pruned), 256, 0, lead->stream>>>(lead->d_desc + n_pruned);
+  fitness_batch_kernel<<<dim3(max_nbx, count), 256, 0, lead->stream>>>(lead->d_desc, max_range, inlier_sq, lead->d_fit);
+  HIP_TRY(lead, hipGetLastError());
+  std::vector<double> part(n_part);
+  HIP_TRY(lead, hipMemcpyAsync(part.data(), lead->d_fit, sizeof(double) * n_part, hipMemcpyDeviceToHost, lead->stream));
+  HIP_TRY(lead, hipStreamSynchronize(lead->stream));
+  for (int k = 0; k < count; ++k) {
+    const int q = order[k];
+    gorio_apd* h = handles[q];
+    h->corr_valid = false;
+    double out[3] = {0.0, 0.0, 0.0};
+    const double* p = part.data() + (size_t)k * max_nbx * 3;
+    for (int bk = 0; bk < descs[k].nblk; ++bk)  // block order, as gorio_apd_fitness_score adds them
+      for (int c = 0; c < 3; ++c) out[c] += p[(size_t)bk * 3 + c];
+    score[q] = out[1] > 0 ? out[0] / out[1] : DBL_MAX;
+    if (inlier_fraction) inlier_fraction[q] = out[2] / (double)h->src->n;
+  }
   return GORIO_OK;
 }
 

@@ -1210,4 +1210,40 @@ __global__ __launch_bounds__(256) void fitness_kernel(unsigned long long* __rest
     out[(size_t)blockIdx.x * 3 + threadIdx.x] = (sw[0][threadIdx.x] + sw[1][threadIdx.x]) + (sw[2][threadIdx.x] + sw[3][threadIdx.x]);
 }
 
+// fitness_kernel for many pairs in one launch (gorio_apd_fitness_score_batch).  grid: (max over pairs of ceil(src.n / 256), pairs).  Block
+// (bx, q) covers source points [256 bx, 256 bx + 256) of pair q -- the block partition of fitness_kernel -- with the same wave_sum tree and
+// the same combination of the four wave sums, and writes its partial to out[q][bx] (row stride gridDim.x); blocks past a pair's last one
+// write nothing.  The host adds a pair's partials in block order, so every pair's score is bit-identical to a single fitness_kernel launch.
+__global__ __launch_bounds__(256) void fitness_batch_kernel(const PairDesc* __restrict__ descs, double max_range_sq, double inlier_sq, double* __restrict__ out /* [pairs][gridDim.x][3] */) {
+  const PairDesc& pd = descs[blockIdx.y];
+  const int n = pd.src.n;
+  if ((int)blockIdx.x * 256 >= n) return;  // uniform over the block: no __syncthreads below is skipped by a part of it
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  double s = 0.0, c = 0.0, inl = 0.0;
+  if (i < n) {
+    const unsigned long long key = pd.best_key[i];
+    pd.best_key[i] = ~0ull;
+    if (key != ~0ull) {
+      const double d = (double)__uint_as_float((unsigned int)(key >> 32));
+      if (d <= max_range_sq) {
+        s = d;
+        c = 1.0;
+      }
+      if (d < inlier_sq) inl = 1.0;
+    }
+  }
+  s = wave_sum(s);
+  c = wave_sum(c);
+  inl = wave_sum(inl);
+  __shared__ double sw[4][3];
+  if ((threadIdx.x & 63) == 0) {
+    sw[threadIdx.x >> 6][0] = s;
+    sw[threadIdx.x >> 6][1] = c;
+    sw[threadIdx.x >> 6][2] = inl;
+  }
+  __syncthreads();
+  if (threadIdx.x < 3)
+    out[((size_t)blockIdx.y * gridDim.x + blockIdx.x) * 3 + threadIdx.x] = (sw[0][threadIdx.x] + sw[1][threadIdx.x]) + (sw[2][threadIdx.x] + sw[3][threadIdx.x]);
+}
+
 }  // namespace gorio

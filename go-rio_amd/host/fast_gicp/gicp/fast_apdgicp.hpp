@@ -171,6 +171,59 @@ public:
     const std::size_t n = input_ ? input_->size() : 0;
     return n ? static_cast<float>(std::llround(frac * static_cast<double>(n))) / n : 0.0f;
   }
+
+  // ---- batch surface (extra; no counterpart in the reference).  Loop-closure verification (loop_detector.cpp:386-422) aligns N
+  // candidate sources against one target and scores each result: N x (align, getFitnessScore).  These members do the same for N objects
+  // -- typically sharing the target through setInputTargetShared -- with one device pass per step.
+
+  // regs[i]->align(outputs[i], guesses[i]) for every i through ONE gorio_apd_align_batch: afterwards every object is in the state the
+  // single align leaves (getFinalTransformation, hasConverged, nr_iterations_, getFinalHessian, the "lm not converged!!" message);
+  // outputs (may be null) receives the moved sources.  Objects must live on one device and carry the same settings; otherwise
+  // std::runtime_error with the library's message, and no object is modified.
+  static void alignBatch(const std::vector<FastAPDGICP*>& regs, const std::vector<Matrix4>& guesses, std::vector<PointCloudSource>* outputs = nullptr) {
+    if (regs.size() != guesses.size()) throw std::invalid_argument("FastAPDGICP::alignBatch: one guess per object");
+    if (outputs) outputs->resize(regs.size());
+    if (regs.empty()) return;
+    const std::size_t count = regs.size();
+    std::vector<gorio_apd_t*> hs(count);
+    std::vector<float> g(count * 16), T(count * 16);
+    std::vector<double> H(count * 36);
+    std::vector<int> conv(count), nit(count);
+    for (std::size_t i = 0; i < count; ++i) {
+      if (!regs[i]) throw std::invalid_argument("FastAPDGICP::alignBatch: null object");
+      regs[i]->push_params();  // as computeTransformation does
+      hs[i] = regs[i]->handle_;
+      to_row_major(guesses[i], &g[i * 16]);
+    }
+    regs[0]->check(gorio_apd_align_batch(hs.data(), static_cast<int>(count), g.data(), T.data(), H.data(), conv.data(), nit.data(), nullptr));
+    for (std::size_t i = 0; i < count; ++i) {
+      FastAPDGICP& o = *regs[i];
+      PointCloudSource* out = nullptr;
+      if (outputs) {  // what pcl::Registration::align does to output before computeTransformation
+        out = &(*outputs)[i];
+        out->points = o.input_->points;
+        for (auto& p : out->points) p.data[3] = 1.0f;
+      }
+      o.finish_align(&T[i * 16], &H[i * 36], conv[i], nit[i], out);
+    }
+  }
+  // regs[i]->getFitnessScore(max_range) for every i through ONE gorio_apd_fitness_score_batch: the same values, bit for bit
+  static std::vector<double> getFitnessScoreBatch(const std::vector<FastAPDGICP*>& regs, double max_range = std::numeric_limits<double>::max()) {
+    std::vector<double> score(regs.size());
+    score_batch(regs, max_range, 0.0, score, nullptr);
+    return score;
+  }
+  // regs[i]->getInlierFraction(max_correspondence_dist) for every i through ONE gorio_apd_fitness_score_batch
+  static std::vector<float> getInlierFractionBatch(const std::vector<FastAPDGICP*>& regs, double max_correspondence_dist = 0.5) {
+    std::vector<double> score(regs.size()), frac(regs.size());
+    score_batch(regs, 0.0, max_correspondence_dist, score, &frac);
+    std::vector<float> out(regs.size());
+    for (std::size_t i = 0; i < regs.size(); ++i) {
+      const std::size_t n = regs[i]->input_ ? regs[i]->input_->size() : 0;
+      out[i] = n ? static_cast<float>(std::llround(frac[i] * static_cast<double>(n))) / n : 0.0f;
+    }
+    return out;
+  }
   // Scan-to-submap target assembly on the GPU (extra; replaces the CPU loop of scan_matching_odometry_nodelet.cpp:602-612): keyframe
   // clouds moved by their relative poses, concatenated, downsampled (voxel_leaf <= 0: the launch files' NONE), set as the target.  The
   // assembled cloud is also returned as a pcl cloud and kept as target_, because pcl::Registration::align() insists on one.
@@ -227,6 +280,12 @@ protected:
     double H[36];
     int conv = 0, nit = 0;
     check(gorio_apd_align(handle_, g, T, H, &conv, &nit, nullptr));
+    finish_align(T, H, conv, nit, &output);
+  }
+
+  // What the members of an object are after gorio_apd_align / _align_batch returned T, H, converged and nr_iterations for it; output
+  // (may be null) receives pcl::transformPointCloud(*input_, output, final_transformation_), LSQ:79 (xyz only, labels untouched).
+  void finish_align(const float* T, const double* H, int conv, int nit, PointCloudSource* output) {
     for (int r = 0; r < 4; ++r)
       for (int c = 0; c < 4; ++c) final_transformation_(r, c) = T[r * 4 + c];
     for (int r = 0; r < 6; ++r)
@@ -237,10 +296,10 @@ protected:
     source_covs_fresh_ = target_covs_fresh_ = false;  // device now holds (possibly newly computed) covariances
     source_covs_.clear();
     target_covs_.clear();
-    // pcl::transformPointCloud(*input_, output, final_transformation_), LSQ:79 (xyz only, labels untouched)
+    if (!output) return;
     const int n = static_cast<int>(input_->size());
-    if (static_cast<int>(output.size()) != n) output.points = input_->points;
-    if (n > 0) check(gorio_apd_transform_source(handle_, T, output.points[0].data, n, sizeof(PointSource)));
+    if (static_cast<int>(output->size()) != n) output->points = input_->points;
+    if (n > 0) check(gorio_apd_transform_source(handle_, T, output->points[0].data, n, sizeof(PointSource)));
   }
 
   virtual void update_correspondences(const Eigen::Isometry3d& trans) { linearize(trans, nullptr, nullptr); }  // APD:160-220
@@ -278,6 +337,18 @@ private:
       for (int r = 0; r < 4; ++r)
         for (int c = 0; c < 4; ++c) rm[i * 16 + r * 4 + c] = covs[i](r, c);
     return rm;
+  }
+  // every object at its final_transformation_ through gorio_apd_fitness_score_batch
+  static void score_batch(const std::vector<FastAPDGICP*>& regs, double max_range, double inlier_dist, std::vector<double>& score, std::vector<double>* frac) {
+    if (regs.empty()) return;
+    std::vector<gorio_apd_t*> hs(regs.size());
+    std::vector<float> T(regs.size() * 16);
+    for (std::size_t i = 0; i < regs.size(); ++i) {
+      if (!regs[i]) throw std::invalid_argument("FastAPDGICP: null object in a batch");
+      hs[i] = regs[i]->handle_;
+      to_row_major(regs[i]->final_transformation_, &T[i * 16]);
+    }
+    regs[0]->check(gorio_apd_fitness_score_batch(hs.data(), static_cast<int>(regs.size()), T.data(), max_range, inlier_dist, score.data(), frac ? frac->data() : nullptr));
   }
   void check(int rc) const {
     if (rc < 0) throw std::runtime_error(std::string("FastAPDGICP (gorio_amd): ") + gorio_apd_last_error(handle_) + " [code " + std::to_string(rc) + "]");

@@ -195,6 +195,18 @@ int gorio_apd_transform_source(gorio_apd_t* h, const float T[16], float* xyz_out
  * the pose on an unsharded handle. */
 int gorio_apd_fitness_score(gorio_apd_t* h, const float T[16], double max_range, double inlier_dist, double* score, double* inlier_fraction);
 
+/* gorio_apd_fitness_score for `count` handles in one pass: N x getFitnessScore (SMO:675, loop_detector.cpp:411) -- the scoring of the loop
+ * candidates of loop_detector.cpp:386-422, one target and N aligned sources -- without N round trips.  T: count * 16 floats (row-major, pose
+ * of handle i at T + 16 i); score: count entries; inlier_fraction: count entries or NULL.  score[i] / inlier_fraction[i] are BIT FOR BIT
+ * those of gorio_apd_fitness_score(handles[i], T + 16 i, max_range, inlier_dist, ...): DBL_MAX when no point qualifies, inlier_dist <= 0
+ * means 0.5 m, every handle searches in its own search mode with the same rounded-up bound.  One index build for the clouds that lack one
+ * (a target shared through gorio_apd_set_target_shared is built once), one 1-NN search launch per search mode, one reduction launch, one
+ * device-to-host copy and one synchronisation for the whole batch.  Handles must be distinct, live on one device and have both clouds set;
+ * their parameters may differ.  A sharded handle (gorio_apd_comm_init / gorio_apd_debug_set_shard with more than one rank) gives
+ * GORIO_ERR_STATE.  count == 0 returns GORIO_OK.  On a validation error no handle is changed and handles[0]'s last error names the index
+ * of the offending handle.  Afterwards, as after the single call, no handle holds correspondences (gorio_apd_get_correspondences fails). */
+int gorio_apd_fitness_score_batch(gorio_apd_t** handles, int count, const float* T, double max_range, double inlier_dist, double* score, double* inlier_fraction);
+
 /*
  * Sharded-source mode -- "one large co-registration" (no counterpart in the reference, whose parallelism is one OpenMP
  * team): several processes, one per GPU, each with a handle holding the SAME source and target clouds, form an RCCL communicator
