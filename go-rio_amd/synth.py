@@ -173,3 +173,69 @@ def imu_window(seed, start_t=10.0, duration=1.0, gyr_hz=200.0, vel_hz=200.0, noi
         vel = vel + rng.normal(0.0, np.sqrt(vel_var), vel.shape)
     return dict(gyr_t=gyr_t, gyr=np.ascontiguousarray(gyr), vel_t=vel_t, vel=np.ascontiguousarray(vel), gyr_var=gyr_var, vel_var=vel_var,
                 start_t=start_t, end_t=end_t)
+
+
+# --------------------------------------------------------------------------- window shapes for the GP pre-integration tests
+
+def ugpm_state_count(win, infer_t=None, state_freq=50.0, overlap=8):
+    """(S, state frequency) that a UGPM request over `win` uses: preint.h:766-775 as gorio_ugpm_preint_batch computes it -- the state
+    rate max(state_freq, 5 / duration) clamped by the mean rates (n - 1) / span of the two input streams, S = ceil(duration f) + 2 overlap."""
+    q = np.asarray([win["end_t"]] if infer_t is None else infer_t, np.float64)
+    gt, vt = np.asarray(win["gyr_t"], np.float64), np.asarray(win["vel_t"], np.float64)
+    duration = float(q.max()) - float(win["start_t"])
+    vel_freq = (len(vt) - 1) / (vt[-1] - vt[0])
+    gyr_freq = (len(gt) - 1) / (gt[-1] - gt[0])
+    f = min(max(state_freq, 5.0 / duration), min(vel_freq, gyr_freq))
+    return int(np.ceil(duration * f)) + 2 * overlap, f
+
+
+def perturb_stream(win, stream, seed, jitter=0.0, drop=(), fn=None, var=None, noise=True):
+    """A copy of `win` whose `stream` ('gyr' or 'vel') has irregular stamps, as a real driver delivers them: every stamp moves by a
+    uniform offset of up to +-`jitter` of its nominal period (jitter < 0.5 keeps the order), the samples at the indices `drop` are
+    lost, and the values are those of `fn` (default: omega_true / vel_true) at the new stamps plus fresh noise of variance `var`."""
+    assert stream in ("gyr", "vel") and 0.0 <= jitter < 0.5
+    rng = np.random.default_rng(seed)
+    t = np.asarray(win[stream + "_t"], np.float64)
+    period = (t[-1] - t[0]) / (len(t) - 1)
+    t = t + rng.uniform(-jitter, jitter, t.shape) * period
+    t = np.delete(t, np.asarray(drop, dtype=np.int64))
+    fn = fn if fn is not None else (omega_true if stream == "gyr" else vel_true)
+    var = var if var is not None else win[stream + "_var"]
+    x = fn(t)
+    if noise:
+        x = x + rng.normal(0.0, np.sqrt(var), x.shape)
+    out = dict(win)
+    out[stream + "_t"], out[stream] = t, np.ascontiguousarray(x)
+    return out
+
+
+def shift_window(win, offset):
+    """The same window with every time (both streams' stamps, start_t, end_t) moved by `offset` seconds; the samples are unchanged.
+    offset = 1.6e9 gives ROS epoch stamps (header.stamp.toSec(), radar_graph_slam_nodelet.cpp:466-512)."""
+    out = dict(win)
+    for k in ("gyr_t", "vel_t"):
+        out[k] = np.asarray(win[k], np.float64) + offset
+    out["start_t"], out["end_t"] = win["start_t"] + offset, win["end_t"] + offset
+    return out
+
+
+def window_for_states(S, seed, overlap=8, state_freq=50.0, gyr_hz=200.0, vel_hz=200.0, start_t=10.0, gyr_jitter=0.0, gyr_drop=(),
+                      vel_jitter=0.0, vel_drop=(), **kw):
+    """A window (imu_window, then perturb_stream on either stream) whose UGPM request to its end_t has exactly `S` GP states at this
+    `overlap` and `state_freq`.  The duration sits in the middle of its ceil interval, (S - 2 overlap - 0.5) / f with f the clamped
+    state rate, so rounding cannot move S.  Below 6 core states the rate is 5 / duration and duration f = 5 exactly; such windows are
+    checked, not centred.  Raises ValueError when no window of these rates has S states."""
+    n = S - 2 * overlap
+    f = min(state_freq, gyr_hz, vel_hz)
+    for _ in range(6):
+        duration = (n - 0.5) / f
+        win = imu_window(seed, start_t=start_t, duration=duration, gyr_hz=gyr_hz, vel_hz=vel_hz, **kw)
+        if gyr_jitter or len(gyr_drop):
+            win = perturb_stream(win, "gyr", seed + 1, jitter=gyr_jitter, drop=gyr_drop)
+        if vel_jitter or len(vel_drop):
+            win = perturb_stream(win, "vel", seed + 2, jitter=vel_jitter, drop=vel_drop)
+        got, f_eff = ugpm_state_count(win, state_freq=state_freq, overlap=overlap)
+        if got == S:
+            return win
+        f = f_eff
+    raise ValueError(f"no window with S = {S} (overlap {overlap}, state_freq {state_freq}, gyro {gyr_hz} Hz, velocity {vel_hz} Hz): got {got}")
