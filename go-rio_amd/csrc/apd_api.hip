@@ -25,6 +25,7 @@
 #include "apd_submap.hip"
 #include "apd_prep.hip"
 #include "../../include/gorio_prep.h"
+#include "apd_ground.hip"
 
 using namespace gorio;
 
