@@ -32,4 +32,6 @@ from . import synth  # noqa: E402  (pure-numpy synthetic inputs, no GPU)
 from .apd import ApdGicp, ApdParams, DeviceInputs, GorioError, align_batch, fitness_score_batch, load_library  # noqa: E402
 from . import prep  # noqa: E402
 from . import ground  # noqa: E402
+from . import scan_context  # noqa: E402
+from .scan_context import SC_SYMBOLS, ScanContext  # noqa: E402
 from .ugpm import PreintOption, PreintPrior, UgpmBatch, VelPreintegration, ugpm_combine_preints, ugpm_preint_batch, ugpm_stage_times  # noqa: E402

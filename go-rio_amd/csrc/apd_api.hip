@@ -26,6 +26,8 @@
 #include "apd_prep.hip"
 #include "../../include/gorio_prep.h"
 #include "apd_ground.hip"
+#include "../../include/gorio_sc.h"
+#include "apd_sc.hip"
 
 using namespace gorio;
 

@@ -1,0 +1,232 @@
+// Drop-in for include/scan_context/Scancontext.h of the Go-RIO sources (SCH, with SC = src/radar_graph_slam/Scancontext.cpp):
+// SCManager with the reference's surface, on top of the C ABI of include/gorio_sc.h.  makeAndSaveScancontextAndKeys and
+// detectLoopClosureID run on the GPU against the library's keyframe database; the storage members mirror it on the host for
+// callers that read them.  makeScancontext(cloud) goes through a second, private database.  The helpers that take caller-given
+// matrices (make*Key, fastAlignUsingVkey, distDirectSC, distanceBtnScanContext) are O(800) and run here in the library's index
+// order.  Without nanoflann there is no InvKeyTree: the snapshot lives in the library, polarcontext_invkeys_to_search_ mirrors it.
+#pragma once
+#include <algorithm>
+#include <cmath>
+#include <memory>
+#include <stdexcept>
+#include <string>
+#include <utility>
+#include <vector>
+
+#include <Eigen/Dense>
+#include <pcl/point_cloud.h>
+#include <pcl/point_types.h>
+#include <radar_graph_slam/keyframe.hpp>
+
+#include "gorio_sc.h"
+
+using Eigen::MatrixXd;
+using SCPointType = pcl::PointXYZINormal;
+using KeyMat = std::vector<std::vector<float>>;
+
+inline MatrixXd circshift(MatrixXd& _mat, int _num_shift) {  // SC:42-62
+  MatrixXd out(_mat.rows(), _mat.cols());
+  for (int c = 0; c < _mat.cols(); ++c)
+    for (int r = 0; r < _mat.rows(); ++r) out(r, (c + _num_shift) % _mat.cols()) = _mat(r, c);
+  return out;
+}
+
+inline std::vector<float> eig2stdvec(MatrixXd _eigmat) { return std::vector<float>(_eigmat.data(), _eigmat.data() + _eigmat.size()); }  // SC:73-77
+
+class SCManager {
+ public:
+  SCManager() { open(h_, params_); }
+  ~SCManager() {
+    if (h_) gorio_sc_destroy(h_);
+    if (scratch_) gorio_sc_destroy(scratch_);
+  }
+  SCManager(const SCManager&) = delete;
+  SCManager& operator=(const SCManager&) = delete;
+
+  // The library holds the settings from creation, so a setter re-creates the (still empty) handle; changing a setting after
+  // keyframes were added is refused, as LoopDetector sets both in its constructor (LD:88-89).
+  void setScDistThresh(double thresh) {
+    SC_DIST_THRES = thresh;
+    params_.sc_dist_thresh = thresh;
+    reopen();
+  }
+  void setAzimuthRange(double range) {
+    PC_AZIMUTH_ANGLE_MAX = range;
+    PC_AZIMUTH_ANGLE_MIN = -range;
+    PC_UNIT_SECTOR_ANGLE = (PC_AZIMUTH_ANGLE_MAX - PC_AZIMUTH_ANGLE_MIN) / double(PC_NUM_SECTOR);
+    params_.azimuth_range = range;
+    reopen();
+  }
+
+  MatrixXd makeScancontext(pcl::PointCloud<SCPointType>& _scan_down) {
+    if (!scratch_) open(scratch_, params_);
+    const int idx = add(scratch_, _scan_down);
+    MatrixXd desc(PC_NUM_RING, PC_NUM_SECTOR);
+    fetch(scratch_, idx, &desc, nullptr, nullptr);
+    return desc;
+  }
+  MatrixXd makeRingkeyFromScancontext(MatrixXd& _desc) {  // SC:219-229, index order
+    MatrixXd k(_desc.rows(), 1);
+    for (int r = 0; r < _desc.rows(); ++r) {
+      double s = 0.0;
+      for (int c = 0; c < _desc.cols(); ++c) s += _desc(r, c);
+      k(r, 0) = s / (double)_desc.cols();
+    }
+    return k;
+  }
+  MatrixXd makeSectorkeyFromScancontext(MatrixXd& _desc) {  // SC:235-245, index order
+    MatrixXd k(1, _desc.cols());
+    for (int c = 0; c < _desc.cols(); ++c) {
+      double s = 0.0;
+      for (int r = 0; r < _desc.rows(); ++r) s += _desc(r, c);
+      k(0, c) = s / (double)_desc.rows();
+    }
+    return k;
+  }
+  int fastAlignUsingVkey(MatrixXd& _vkey1, MatrixXd& _vkey2) {  // SC:104-122
+    int arg = 0;
+    double best = 10000000;
+    for (int s = 0; s < _vkey1.cols(); ++s) {
+      MatrixXd sh = circshift(_vkey2, s);
+      double sq = 0.0;
+      for (int j = 0; j < _vkey1.cols(); ++j) {
+        const double d = _vkey1(0, j) - sh(0, j);
+        sq += d * d;
+      }
+      const double n = std::sqrt(sq);
+      if (n < best) {
+        arg = s;
+        best = n;
+      }
+    }
+    return arg;
+  }
+  double distDirectSC(MatrixXd& _sc1, MatrixXd& _sc2) {  // SC:80-101
+    int n_eff = 0;
+    double sum = 0;
+    for (int c = 0; c < _sc1.cols(); ++c) {
+      double n1 = 0, n2 = 0, dot = 0;
+      for (int r = 0; r < _sc1.rows(); ++r) {
+        n1 += _sc1(r, c) * _sc1(r, c);
+        n2 += _sc2(r, c) * _sc2(r, c);
+        dot += _sc1(r, c) * _sc2(r, c);
+      }
+      n1 = std::sqrt(n1);
+      n2 = std::sqrt(n2);
+      if ((n1 == 0) | (n2 == 0)) continue;
+      sum = sum + dot / (n1 * n2);
+      n_eff = n_eff + 1;
+    }
+    return 1.0 - sum / n_eff;
+  }
+  std::pair<double, int> distanceBtnScanContext(MatrixXd& _sc1, MatrixXd& _sc2) {  // SC:127-160
+    MatrixXd v1 = makeSectorkeyFromScancontext(_sc1), v2 = makeSectorkeyFromScancontext(_sc2);
+    const int a = fastAlignUsingVkey(v1, v2);
+    const int n = _sc1.cols();
+    std::vector<int> space{a, (a + 1 + n) % n, (a - 1 + n) % n};
+    std::sort(space.begin(), space.end());
+    int arg = 0;
+    double best = 10000000;
+    for (int s : space) {
+      MatrixXd sh = circshift(_sc2, s);
+      const double d = distDirectSC(_sc1, sh);
+      if (d < best) {
+        arg = s;
+        best = d;
+      }
+    }
+    return std::make_pair(best, arg);
+  }
+
+  // User-side API
+  void makeAndSaveScancontextAndKeys(pcl::PointCloud<SCPointType>& _scan_down) {  // SC:255-269, the descriptor made on the GPU
+    const int idx = add(h_, _scan_down);
+    MatrixXd sc(PC_NUM_RING, PC_NUM_SECTOR), ring(PC_NUM_RING, 1), sector(1, PC_NUM_SECTOR);
+    fetch(h_, idx, &sc, &ring, &sector);
+    polarcontexts_.push_back(sc);
+    polarcontext_invkeys_.push_back(ring);
+    polarcontext_vkeys_.push_back(sector);
+    polarcontext_invkeys_mat_.push_back(eig2stdvec(ring));
+  }
+  std::pair<int, float> detectLoopClosureID(const std::vector<radar_graph_slam::KeyFrame::Ptr>& candidate_keyframes, const radar_graph_slam::KeyFrame::Ptr& new_keyframe) {
+    std::vector<int> cand;
+    for (auto& k : candidate_keyframes) cand.push_back((int)k->index);
+    int loop_id = -1;
+    float yaw = 0.0f;
+    double min_dist = 0.0;
+    check(gorio_sc_detect(h_, (int)new_keyframe->index, cand.data(), (int)cand.size(), &loop_id, &yaw, &min_dist, nullptr), "detectLoopClosureID");
+    int n = 0, m = 0;
+    check(gorio_sc_get_state(h_, &n, &tree_making_period_conter, &m, nullptr, 0), "detectLoopClosureID");
+    std::vector<int> snap(m);
+    check(gorio_sc_get_state(h_, nullptr, nullptr, nullptr, snap.data(), m), "detectLoopClosureID");
+    polarcontext_invkeys_to_search_.clear();
+    for (int i : snap) polarcontext_invkeys_to_search_.push_back(polarcontext_invkeys_mat_.at(i));
+    return {loop_id, yaw};
+  }
+
+  const Eigen::MatrixXd& getConstRefRecentSCD(void) { return polarcontexts_.back(); }
+
+ public:
+  const double LIDAR_HEIGHT = 1.2;
+  double PC_AZIMUTH_ANGLE_MAX = 56.5;
+  double PC_AZIMUTH_ANGLE_MIN = -56.6;
+  const int PC_NUM_RING = GORIO_SC_RINGS;
+  const int PC_NUM_SECTOR = GORIO_SC_SECTORS;
+  const double PC_MAX_RADIUS = GORIO_SC_MAX_RADIUS;
+  double PC_UNIT_SECTOR_ANGLE = (PC_AZIMUTH_ANGLE_MAX - PC_AZIMUTH_ANGLE_MIN) / double(PC_NUM_SECTOR);
+  const double PC_UNIT_RINGGAP = PC_MAX_RADIUS / double(PC_NUM_RING);
+  const int NUM_EXCLUDE_RECENT = GORIO_SC_EXCLUDE_RECENT;
+  const int NUM_CANDIDATES_FROM_TREE = GORIO_SC_CANDIDATES;
+  const double SEARCH_RATIO = 0.1;
+  double SC_DIST_THRES = 0.5;
+  const int TREE_MAKING_PERIOD_ = GORIO_SC_TREE_PERIOD;
+  int tree_making_period_conter = 0;
+
+  std::vector<double> polarcontexts_timestamp_;
+  std::vector<Eigen::MatrixXd> polarcontexts_;
+  std::vector<Eigen::MatrixXd> polarcontext_invkeys_;
+  std::vector<Eigen::MatrixXd> polarcontext_vkeys_;
+  KeyMat polarcontext_invkeys_mat_;
+  KeyMat polarcontext_invkeys_to_search_;
+
+ private:
+  gorio_sc_t* h_ = nullptr;
+  gorio_sc_t* scratch_ = nullptr;
+  gorio_sc_params params_ = {0.5, 56.5};  // SC_DIST_THRES (SCH:125); the in-class -56.6 is asymmetric, so until setAzimuthRange the
+                                          // library holds the symmetric 56.5 every launch file sets
+
+  static void check(int rc, const char* what) {
+    if (rc < 0) throw std::runtime_error(std::string("SCManager::") + what + ": " + gorio_sc_last_error());
+  }
+  static void open(gorio_sc_t*& h, const gorio_sc_params& p) { check(gorio_sc_create(&h, 0, &p), "SCManager"); }
+  void reopen() {
+    int n = 0;
+    check(gorio_sc_get_state(h_, &n, nullptr, nullptr, nullptr, 0), "set");
+    if (n) throw std::logic_error("SCManager: settings change after keyframes were added");
+    gorio_sc_destroy(h_);
+    h_ = nullptr;
+    open(h_, params_);
+    if (scratch_) gorio_sc_destroy(scratch_);
+    scratch_ = nullptr;
+  }
+  static int add(gorio_sc_t* h, pcl::PointCloud<SCPointType>& c) {
+    const int n = (int)c.size();
+    const float* x = n ? &c.points[0].x : nullptr;
+    const float* in = n ? &c.points[0].intensity : nullptr;
+    const int stride = (int)sizeof(SCPointType);
+    int first = -1;
+    check(gorio_sc_add_scans(h, 1, &x, &in, &n, &stride, &first), "makeAndSaveScancontextAndKeys");
+    return first;
+  }
+  static void fetch(gorio_sc_t* h, int idx, MatrixXd* desc, MatrixXd* ring, MatrixXd* sector) {
+    std::vector<double> d(GORIO_SC_RINGS * GORIO_SC_SECTORS), r(GORIO_SC_RINGS), s(GORIO_SC_SECTORS);
+    check(gorio_sc_get_descriptor(h, idx, d.data(), r.data(), s.data()), "getDescriptor");
+    for (int i = 0; i < GORIO_SC_RINGS; ++i) {
+      for (int j = 0; j < GORIO_SC_SECTORS; ++j)
+        if (desc) (*desc)(i, j) = d[i * GORIO_SC_SECTORS + j];
+      if (ring) (*ring)(i, 0) = r[i];
+    }
+    for (int j = 0; j < GORIO_SC_SECTORS; ++j)
+      if (sector) (*sector)(0, j) = s[j];
+  }
+};

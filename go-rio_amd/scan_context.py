@@ -1,0 +1,136 @@
+"""ctypes binding of include/gorio_sc.h: the Intensity Scan Context loop-candidate search on the GPU (no numerics here, no CPU
+fallback)."""
+import ctypes as C
+
+import numpy as np
+
+from .apd import GorioError, load_library
+
+SC_SYMBOLS = ["gorio_sc_add_scans", "gorio_sc_create", "gorio_sc_default_params", "gorio_sc_destroy", "gorio_sc_detect", "gorio_sc_detect_batch",
+              "gorio_sc_distance", "gorio_sc_get_descriptor", "gorio_sc_get_state", "gorio_sc_last_error"]
+RINGS, SECTORS = 40, 20
+
+
+class ScParams(C.Structure):
+    _fields_ = [("sc_dist_thresh", C.c_double), ("azimuth_range", C.c_double)]
+
+
+class ScDiag(C.Structure):
+    _fields_ = [("early_return", C.c_int), ("rebuilt", C.c_int), ("counter", C.c_int), ("snapshot_size", C.c_int), ("n_found", C.c_int),
+                ("position", C.c_int * 3), ("key_dist", C.c_float * 3), ("keyframe", C.c_int * 3), ("sc_dist", C.c_double * 3), ("sc_shift", C.c_int * 3)]
+
+
+def _ptr(a):
+    return C.c_void_p(a.__array_interface__["data"][0])
+
+
+def diag_dict(d):
+    out = {}
+    for name, _ in d._fields_:
+        v = getattr(d, name)
+        out[name] = np.array(v[:]) if hasattr(v, "_length_") else v
+    out["key_dist"] = out["key_dist"].astype(np.float32)
+    return out
+
+
+def default_params():
+    lib = load_library()
+    p = ScParams()
+    lib.gorio_sc_default_params(C.byref(p))
+    return p
+
+
+def _points(xyz, intensity):
+    xyz = np.asarray(xyz, np.float32).reshape(-1, 3)
+    pts = np.zeros((max(xyz.shape[0], 1), 4), np.float32)
+    pts[:xyz.shape[0], :3] = xyz
+    pts[:xyz.shape[0], 3] = np.asarray(intensity, np.float32).reshape(-1)
+    return pts, xyz.shape[0]
+
+
+class ScanContext:
+    """SCManager (include/scan_context/Scancontext.h) on the GPU: a keyframe database of descriptors plus the loop-candidate
+    search with its tree-making counter and snapshot."""
+
+    def __init__(self, params=None, device=0, **overrides):
+        self.lib = load_library()
+        self.lib.gorio_sc_last_error.restype = C.c_char_p
+        p = default_params() if params is None else params
+        for k, v in overrides.items():
+            setattr(p, k, v)
+        self.params = p
+        self.h = C.c_void_p()
+        self._check(self.lib.gorio_sc_create(C.byref(self.h), int(device), C.byref(p)))
+
+    def _check(self, rc):
+        if rc < 0:
+            msg = self.lib.gorio_sc_last_error()
+            raise GorioError(rc, msg.decode() if msg else "")
+
+    def close(self):
+        if self.h:
+            self.lib.gorio_sc_destroy(self.h)
+            self.h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def add_scans(self, clouds):
+        """makeAndSaveScancontextAndKeys for every (xyz [n, 3], intensity [n]) in order, one launch; returns the first index."""
+        k = len(clouds)
+        pts = [_points(x, i) for x, i in clouds]
+        X = (C.c_void_p * k)(*[p.__array_interface__["data"][0] for p, _ in pts])
+        I = (C.c_void_p * k)(*[p.__array_interface__["data"][0] + 12 for p, _ in pts])
+        N = (C.c_int * k)(*[n for _, n in pts])
+        S = (C.c_int * k)(*([16] * k))
+        first = C.c_int(-1)
+        self._check(self.lib.gorio_sc_add_scans(self.h, k, X, I, N, S, C.byref(first)))
+        return first.value
+
+    def add_scan(self, xyz, intensity):
+        return self.add_scans([(xyz, intensity)])
+
+    def state(self):
+        n, c, m = C.c_int(), C.c_int(), C.c_int()
+        self._check(self.lib.gorio_sc_get_state(self.h, C.byref(n), C.byref(c), C.byref(m), None, 0))
+        snap = np.zeros(max(m.value, 1), np.int32)
+        self._check(self.lib.gorio_sc_get_state(self.h, None, None, None, _ptr(snap), snap.shape[0]))
+        return {"n_scans": n.value, "counter": c.value, "snapshot": snap[:m.value].copy()}
+
+    def descriptor(self, index):
+        """(desc [40, 20], ring_key [40], sector_key [20]) of a stored keyframe, float64."""
+        d = np.zeros((RINGS, SECTORS), np.float64)
+        r = np.zeros(RINGS, np.float64)
+        s = np.zeros(SECTORS, np.float64)
+        self._check(self.lib.gorio_sc_get_descriptor(self.h, int(index), _ptr(d), _ptr(r), _ptr(s)))
+        return d, r, s
+
+    def distance(self, i, j):
+        """distanceBtnScanContext(desc[i], desc[j]) -> (dist, shift)."""
+        dist, shift = C.c_double(), C.c_int()
+        self._check(self.lib.gorio_sc_distance(self.h, int(i), int(j), C.byref(dist), C.byref(shift)))
+        return dist.value, shift.value
+
+    def detect(self, query_index, candidates):
+        """detectLoopClosureID -> (loop_id, yaw_rad (float32), min_dist, diag dict)."""
+        cand = np.ascontiguousarray(candidates, np.int32).reshape(-1)
+        lid, yaw, md = C.c_int(), C.c_float(), C.c_double()
+        d = ScDiag()
+        self._check(self.lib.gorio_sc_detect(self.h, int(query_index), _ptr(cand) if cand.size else None, int(cand.size), C.byref(lid), C.byref(yaw), C.byref(md),
+                                             C.byref(d)))
+        return lid.value, np.float32(yaw.value), md.value, diag_dict(d)
+
+    def detect_batch(self, query_indices, candidate_lists):
+        """`count` detect calls in order in one device pass -> list of (loop_id, yaw_rad, min_dist, diag dict)."""
+        k = len(query_indices)
+        cands = [np.ascontiguousarray(c, np.int32).reshape(-1) for c in candidate_lists]
+        Q = (C.c_int * k)(*[int(q) for q in query_indices])
+        P = (C.c_void_p * k)(*[c.__array_interface__["data"][0] if c.size else None for c in cands])
+        N = (C.c_int * k)(*[c.size for c in cands])
+        lid, yaw, md = (C.c_int * k)(), (C.c_float * k)(), (C.c_double * k)()
+        d = (ScDiag * k)()
+        self._check(self.lib.gorio_sc_detect_batch(self.h, k, Q, P, N, lid, yaw, md, d))
+        return [(lid[i], np.float32(yaw[i]), md[i], diag_dict(d[i])) for i in range(k)]
