@@ -52,7 +52,14 @@ APD_SYMBOLS = [
     "gorio_apd_align_batch", "gorio_apd_linearize", "gorio_apd_compute_error", "gorio_apd_get_correspondences",
     "gorio_apd_get_mahalanobis", "gorio_apd_transform_source", "gorio_apd_fitness_score", "gorio_apd_fitness_score_batch", "gorio_apd_set_profiling",
     "gorio_apd_get_stage_times", "gorio_apd_set_target_shared", "gorio_comm_get_unique_id", "gorio_apd_comm_init", "gorio_apd_comm_destroy", "gorio_apd_comm_info", "gorio_apd_debug_set_shard", "gorio_apd_debug_set_schedule", "gorio_apd_set_target_submap", "gorio_apd_get_target_points",
+    "gorio_apd_set_method", "gorio_apd_get_method", "gorio_apd_get_voxelmap", "gorio_apd_get_voxel_correspondences",
 ]
+
+# gorio_method / gorio_voxel_search / gorio_voxel_mode of gorio_apd.h (the latter two in the order of gicp_settings.hpp)
+METHOD_APDGICP, METHOD_GICP, METHOD_VGICP = 0, 1, 2
+VOXEL_DIRECT27, VOXEL_DIRECT7, VOXEL_DIRECT1, VOXEL_DIRECT_RADIUS = 0, 1, 2, 3
+VOXEL_ADDITIVE, VOXEL_ADDITIVE_WEIGHTED, VOXEL_MULTIPLICATIVE = 0, 1, 2
+VOXEL_OFFSETS = {VOXEL_DIRECT27: 27, VOXEL_DIRECT7: 7, VOXEL_DIRECT1: 1}
 
 _lib = None
 
@@ -110,6 +117,33 @@ class ApdGicp:
                 raise AttributeError(k)
             setattr(self.params, k, v)
         _check(self._h, self._lib.gorio_apd_set_params(self._h, C.byref(self.params)))
+
+    # ---- which fast_gicp class the object stands for (gorio_apd_set_method): FastAPDGICP, FastGICP or FastVGICP with its
+    # setResolution / setNeighborSearchMethod / setVoxelAccumulationMode (fast_vgicp.hpp:55-62)
+    def set_method(self, method, voxel_resolution=1.0, voxel_search=VOXEL_DIRECT1, voxel_mode=VOXEL_ADDITIVE):
+        _check(self._h, self._lib.gorio_apd_set_method(self._h, int(method), C.c_double(voxel_resolution), int(voxel_search), int(voxel_mode)))
+
+    def get_method(self):
+        m, s, a, r = C.c_int(0), C.c_int(0), C.c_int(0), C.c_double(0.0)
+        _check(self._h, self._lib.gorio_apd_get_method(self._h, C.byref(m), C.byref(r), C.byref(s), C.byref(a)))
+        return dict(method=m.value, voxel_resolution=r.value, voxel_search=s.value, voxel_mode=a.value)
+
+    def getVoxelMap(self):  # noqa: N802 -- parity hook: voxelmap_ (fast_vgicp.hpp:85), voxels in ascending (x, y, z) coordinate order
+        nv = C.c_int(0)
+        _check(self._h, self._lib.gorio_apd_get_voxelmap(self._h, None, None, None, None, 0, C.byref(nv)))
+        n = nv.value
+        coord = np.empty((n, 3), np.int32)
+        num = np.empty(n, np.int32)
+        mean = np.empty((n, 4), np.float64)
+        cov = np.empty((n, 4, 4), np.float64)
+        _check(self._h, self._lib.gorio_apd_get_voxelmap(self._h, _p(coord, C.c_int), _p(num, C.c_int), _p(mean, C.c_double), _p(cov, C.c_double), n, C.byref(nv)))
+        return dict(coord=coord, num_points=num, mean=mean, cov=cov)
+
+    def getVoxelCorrespondences(self):  # noqa: N802 -- parity hook: voxel_correspondences_ as the table [n_source][n_offsets], -1 = no voxel
+        n_off = VOXEL_OFFSETS[self.get_method()["voxel_search"]]
+        idx = np.empty((self._n_src, n_off), np.int32)
+        _check(self._h, self._lib.gorio_apd_get_voxel_correspondences(self._h, _p(idx, C.c_int), self._n_src * n_off))
+        return idx
 
     def setNumThreads(self, n):  # noqa: N802 -- no-op on the GPU (APD:34-42)
         pass

@@ -23,6 +23,7 @@
 #include "apd_kernels.hip"
 #include "apd_index.hip"
 #include "apd_submap.hip"
+#include "apd_voxel.hip"
 #include "apd_prep.hip"
 #include "../../include/gorio_prep.h"
 #include "apd_ground.hip"
@@ -59,6 +60,24 @@ struct DevCloud {
   unsigned int* bb = nullptr;
   int idx_cap = 0, keys_cap = 0;
   bool idx_valid = false;
+  // Gaussian voxel map of this cloud as a FastVGICP target (voxelmap_, fast_vgicp.hpp:85): lives with the cloud, so the handles that share a
+  // target share its map.  Valid for (vm_res, vm_mult) until the points or the covariances change.
+  unsigned long long* vm_keys = nullptr;  // [vm_keys_cap] sort scratch: linear voxel id << 31 | point index
+  int vm_keys_cap = 0;
+  int* vm_counts = nullptr;               // [vm_counts_cap] voxel starts per 256 keys, scanned
+  int vm_counts_cap = 0;
+  int* vm_bb = nullptr;                   // [8] bounding box of the occupied coordinates + range flag
+  IndexJob* vm_job = nullptr;             // descriptor the bitonic sort kernels read
+  unsigned long long* vm_vkey = nullptr;  // the map itself (VoxelMapView), [vm_cap] voxels
+  double* vm_mean = nullptr;
+  double* vm_cov6 = nullptr;
+  int* vm_num = nullptr;
+  int vm_cap = 0, vm_nv = 0;
+  int vm_min[3] = {0, 0, 0}, vm_dim[3] = {0, 0, 0};
+  double vm_res = 0.0;
+  bool vm_mult = false;                   // MultiplicativeGaussianVoxel (ADDITIVE and ADDITIVE_WEIGHTED build the same voxels, VOX:138-141)
+  bool vm_valid = false;
+  VoxelMapView voxel_view() const { return VoxelMapView{vm_vkey, vm_mean, vm_cov6, vm_num, vm_nv, {vm_min[0], vm_min[1], vm_min[2]}, {vm_dim[0], vm_dim[1], vm_dim[2]}, vm_res}; }
   int device = 0;
   CloudView view() const { return CloudView{x, y, z, label, p4, cov6, geo_w, n, n_pad, idx}; }
   DevCloud() = default;
@@ -87,6 +106,20 @@ struct gorio_apd {
   double* partials = nullptr;
   int pt_cap = 0;
   bool corr_valid = false;
+  // registration method (gorio_apd_set_method): which fast_gicp class this handle stands for, and the FastVGICP members
+  // voxel_resolution_ / search_method_ / voxel_mode_ (fast_vgicp.hpp:79-81)
+  int method = GORIO_METHOD_APDGICP;
+  double voxel_resolution = 1.0;
+  int voxel_search = GORIO_VOXEL_DIRECT1;
+  int voxel_mode = GORIO_VOXEL_ADDITIVE;
+  // FastVGICP pair state: slot table, weighted Mahalanobis blocks, block partials (VoxPair); corr_valid / omega_valid describe them in that mode
+  int* v_slots = nullptr;
+  double* v_omega6 = nullptr;
+  double* v_partials = nullptr;
+  size_t v_cap = 0;          // slots
+  int v_n_off = 0;           // offsets per source point of the slot table held
+  VoxPair* d_vox = nullptr;  // batch array (owned by the handle that leads a batch)
+  int vox_cap = 0;
   bool omega_valid = false;  // omega6 holds the Mahalanobis matrices of the last linearisation (not after a Gauss-Newton align)
   PairState* d_state = nullptr;
   PairDesc* d_desc = nullptr;   // batch descriptor array (owned by the handle that leads a batch)
@@ -128,7 +161,7 @@ struct gorio_apd {
     hipEvent_t ev = nullptr;  // recorded behind the last upload from this buffer: the next writer waits for it
     bool pending = false;
   };
-  Pinned pin_ijobs, pin_jobs, pin_desc, pin_states, pin_copy;
+  Pinned pin_ijobs, pin_jobs, pin_desc, pin_states, pin_copy, pin_vox;
   std::string err;
   // profiling
   bool profiling = false;
@@ -235,6 +268,7 @@ DevCloud::~DevCloud() {
   hipSetDevice(c.device);
   hipFree(c.idx.sx); hipFree(c.idx.sy); hipFree(c.idx.sz); hipFree(c.idx.orig); hipFree(c.idx.s4); hipFree(c.idx.tbox); hipFree(c.idx.sbox); hipFree(c.idx.bbox); hipFree(c.keys); hipFree(c.bb);
   hipFree(c.x); hipFree(c.y); hipFree(c.z); hipFree(c.label); hipFree(c.p4); hipFree(c.cov6); hipFree(c.geo_w); hipFree(c.knn); hipFree(c.part_d); hipFree(c.part_i); hipFree(c.redo); hipFree(c.kth);
+  hipFree(c.vm_keys); hipFree(c.vm_counts); hipFree(c.vm_bb); hipFree(c.vm_job); hipFree(c.vm_vkey); hipFree(c.vm_mean); hipFree(c.vm_cov6); hipFree(c.vm_num);
 }
 namespace {
 
@@ -311,7 +345,7 @@ int upload_cloud(gorio_apd* h, DevCloud& c, const float* xyz, const float* label
   HIP_TRY(h, hipMemcpyAsync(c.p4, b4, sizeof(float4) * np, hipMemcpyHostToDevice, h->stream));
   HIP_TRY(h, hipStreamSynchronize(h->stream));
   c.present = true;
-  c.cov_count = 0;
+  c.cov_count = 0; c.vm_valid = false;
   c.idx_valid = false;
   return GORIO_OK;
 }
@@ -338,7 +372,7 @@ int upload_cloud_device(gorio_apd* h, DevCloud& c, const float* dx, const float*
   copy_cloud_kernel<<<(c.n_pad + 255) / 256, 256, 0, h->stream>>>(dx, dy, dz, dl, c.x, c.y, c.z, c.label, c.p4, n, c.n_pad);
   HIP_TRY(h, hipGetLastError());
   c.present = true;
-  c.cov_count = 0;
+  c.cov_count = 0; c.vm_valid = false;
   c.idx_valid = false;
   return GORIO_OK;
 }
@@ -646,7 +680,7 @@ int run_covariances(gorio_apd* lead, std::vector<std::pair<gorio_apd*, DevCloud*
   }
   HIP_TRY(lead, hipGetLastError());
   for (auto& t : todo) {
-    t.second->cov_count = t.second->n;
+    t.second->cov_count = t.second->n; t.second->vm_valid = false;
     t.second->cov_k = k;
     t.second->cov_reg = lead->params.regularization;
   }
@@ -710,11 +744,165 @@ bool shared_cov_mismatch(const gorio_apd* h) {
   return h->tgt.use_count() > 1 && t.cov_count == t.n && t.cov_k >= 0 && (t.cov_k != h->params.k_correspondences || t.cov_reg != h->params.regularization);
 }
 
+// ---- FastVGICP plumbing
+
+int voxel_offsets(int search) { return search == GORIO_VOXEL_DIRECT1 ? 1 : search == GORIO_VOXEL_DIRECT7 ? 7 : 27; }  // neighbor_offsets, VOX:16-43
+
+// sharers of a target share ONE voxel map: a sharer whose resolution / accumulation differ from the ones it was built with would register
+// against another object's map (or rebuild it under the other sharers)
+bool shared_voxel_mismatch(const gorio_apd* h) {
+  const DevCloud& t = *h->tgt;
+  return h->method == GORIO_METHOD_VGICP && h->tgt.use_count() > 1 && t.vm_valid &&
+         (t.vm_res != h->voxel_resolution || t.vm_mult != (h->voxel_mode == GORIO_VOXEL_MULTIPLICATIVE));
+}
+
+// create_voxelmap (VOX:129-156) of target cloud t, whose covariances are valid: coordinates + bounding box, keys, sort, voxel starts, one
+// accumulation pass.  Two small read-backs (the box, the voxel count); nothing to do when the map held matches.
+int build_voxelmap(gorio_apd* h, DevCloud& t, double res, int mode) {
+  const bool mult = mode == GORIO_VOXEL_MULTIPLICATIVE;
+  if (t.vm_valid && t.vm_res == res && t.vm_mult == mult) return GORIO_OK;
+  t.vm_valid = false;
+  const int n = t.n;
+  if (!t.vm_bb) HIP_TRY(h, hipMalloc(&t.vm_bb, sizeof(int) * 8));
+  if (!t.vm_job) HIP_TRY(h, hipMalloc(&t.vm_job, sizeof(IndexJob)));
+  vg_bbox_init_kernel<<<1, 64, 0, h->stream>>>(t.vm_bb);
+  vg_coord_bbox_kernel<<<std::min(256, (n + 255) / 256), 256, 0, h->stream>>>(t.p4, n, res, t.vm_bb);
+  int bb[8];
+  HIP_TRY(h, hipMemcpyAsync(bb, t.vm_bb, sizeof(int) * 7, hipMemcpyDeviceToHost, h->stream));
+  HIP_TRY(h, hipStreamSynchronize(h->stream));
+  if (bb[6]) return fail(h, GORIO_ERR_UNSUPPORTED, "voxel map: a target coordinate is not finite or its voxel coordinate does not fit 31 bits");
+  VoxBox g;
+  double cells = 1.0;
+  for (int a = 0; a < 3; ++a) {
+    g.min_c[a] = bb[a];
+    const long long d = (long long)bb[3 + a] - (long long)bb[a] + 1;
+    g.dim[a] = (int)d;
+    cells *= (double)d;
+  }
+  g.res = res;
+  if (cells >= 8589934592.0) return fail(h, GORIO_ERR_UNSUPPORTED, "voxel map: the bounding box of the occupied voxels has 2^33 cells or more (the voxel id is packed into 33 bits of the sort key)");
+  int npow2 = kSortTile;
+  while (npow2 < n) npow2 <<= 1;
+  const int nblocks = (n + 255) / 256;
+  if (npow2 > t.vm_keys_cap) {
+    hipFree(t.vm_keys);
+    t.vm_keys = nullptr;
+    t.vm_keys_cap = 0;
+    HIP_TRY(h, hipMalloc(&t.vm_keys, sizeof(unsigned long long) * (size_t)npow2));
+    t.vm_keys_cap = npow2;
+  }
+  if (nblocks + 1 > t.vm_counts_cap) {
+    hipFree(t.vm_counts);
+    t.vm_counts = nullptr;
+    t.vm_counts_cap = 0;
+    HIP_TRY(h, hipMalloc(&t.vm_counts, sizeof(int) * (size_t)(nblocks + 1)));
+    t.vm_counts_cap = nblocks + 1;
+  }
+  vg_key_kernel<<<(npow2 + 255) / 256, 256, 0, h->stream>>>(t.p4, n, npow2, g, t.vm_keys);
+  IndexJob job;
+  std::memset(&job, 0, sizeof(job));
+  job.n = n;
+  job.npow2 = npow2;
+  job.keys = t.vm_keys;
+  HIP_TRY(h, hipMemcpyAsync(t.vm_job, &job, sizeof(job), hipMemcpyHostToDevice, h->stream));
+  HIP_TRY(h, hipStreamSynchronize(h->stream));  // `job` lives on this stack frame
+  bitonic_tile_sort_kernel<<<dim3(npow2 / kSortTile, 1), 1024, 0, h->stream>>>(t.vm_job);
+  for (int k = 2 * kSortTile; k <= npow2; k <<= 1) {
+    for (int j = k >> 1; j >= kSortTile; j >>= 1) bitonic_global_kernel<<<dim3((npow2 / 2 + 255) / 256, 1), 256, 0, h->stream>>>(t.vm_job, k, j);
+    bitonic_tile_merge_kernel<<<dim3(npow2 / kSortTile, 1), 1024, 0, h->stream>>>(t.vm_job, k);
+  }
+  vox_count_kernel<<<nblocks, 256, 0, h->stream>>>(t.vm_keys, n, t.vm_counts);
+  vox_scan_kernel<<<1, 1024, 0, h->stream>>>(t.vm_counts, nblocks);
+  int nv = 0;
+  HIP_TRY(h, hipMemcpyAsync(&nv, t.vm_counts + nblocks, sizeof(int), hipMemcpyDeviceToHost, h->stream));
+  HIP_TRY(h, hipStreamSynchronize(h->stream));
+  if (nv <= 0 || nv > n) return fail(h, GORIO_ERR_NO_DEVICE, "voxel map: inconsistent voxel count");
+  if (nv > t.vm_cap) {
+    hipFree(t.vm_vkey); hipFree(t.vm_mean); hipFree(t.vm_cov6); hipFree(t.vm_num);
+    t.vm_vkey = nullptr; t.vm_mean = nullptr; t.vm_cov6 = nullptr; t.vm_num = nullptr;
+    t.vm_cap = 0;
+    const int cap = nv + nv / 8 + 64;
+    HIP_TRY(h, hipMalloc(&t.vm_vkey, sizeof(unsigned long long) * (size_t)cap));
+    HIP_TRY(h, hipMalloc(&t.vm_mean, sizeof(double) * 3 * (size_t)cap));
+    HIP_TRY(h, hipMalloc(&t.vm_cov6, sizeof(double) * 6 * (size_t)cap));
+    HIP_TRY(h, hipMalloc(&t.vm_num, sizeof(int) * (size_t)cap));
+    t.vm_cap = cap;
+  }
+  vg_accum_kernel<<<nblocks, 256, 0, h->stream>>>(t.vm_keys, t.p4, t.cov6, n, t.vm_counts, mult ? 2 : 0, t.vm_vkey, t.vm_mean, t.vm_cov6, t.vm_num);
+  HIP_TRY(h, hipGetLastError());
+  t.vm_nv = nv;
+  for (int a = 0; a < 3; ++a) {
+    t.vm_min[a] = g.min_c[a];
+    t.vm_dim[a] = g.dim[a];
+  }
+  t.vm_res = res;
+  t.vm_mult = mult;
+  t.vm_valid = true;
+  return GORIO_OK;
+}
+
+// slot table, Mahalanobis blocks and block partials of this handle's (source point, offset) slots
+int ensure_voxel_pair(gorio_apd* h) {
+  const int n_off = voxel_offsets(h->voxel_search);
+  const size_t total = (size_t)h->src->n * n_off;
+  if (total > h->v_cap) {
+    hipFree(h->v_slots); hipFree(h->v_omega6); hipFree(h->v_partials);
+    h->v_slots = nullptr; h->v_omega6 = nullptr; h->v_partials = nullptr;
+    h->v_cap = 0;
+    const size_t cap = total + total / 8 + 256;
+    HIP_TRY(h, hipMalloc(&h->v_slots, sizeof(int) * cap));
+    HIP_TRY(h, hipMalloc(&h->v_omega6, sizeof(double) * 6 * cap));
+    HIP_TRY(h, hipMalloc(&h->v_partials, sizeof(double) * 28 * (cap / 256 + 2)));
+    h->v_cap = cap;
+  }
+  h->v_n_off = n_off;
+  return GORIO_OK;
+}
+
+VoxPair make_vox_pair(const gorio_apd* h, int write_omega) {
+  VoxPair v;
+  v.map = h->tgt->voxel_view();
+  v.slots = h->v_slots;
+  v.omega6 = h->v_omega6;
+  v.n_off = h->v_n_off;
+  v.write_omega = write_omega;
+  return v;
+}
+
+int ensure_vox_batch(gorio_apd* lead, int count) {
+  if (count > lead->vox_cap) {
+    hipFree(lead->d_vox);
+    lead->d_vox = nullptr;
+    lead->vox_cap = 0;
+    HIP_TRY(lead, hipMalloc(&lead->d_vox, sizeof(VoxPair) * count));
+    lead->vox_cap = count;
+  }
+  return GORIO_OK;
+}
+
+// the compile-time variants behind one call (kMethodApd stays the instantiation every APD-GICP caller runs)
+void launch_linearize(int method, dim3 grid, hipStream_t stream, const PairDesc* d_desc, const ApdConsts& cst, int fuse) {
+  if (method == GORIO_METHOD_GICP) linearize_kernel<kMethodGicp><<<grid, 256, 0, stream>>>(d_desc, cst, fuse);
+  else linearize_kernel<kMethodApd><<<grid, 256, 0, stream>>>(d_desc, cst, fuse);
+}
+void launch_lm_solve(int method, dim3 grid, hipStream_t stream, const PairDesc* d_desc, const VoxPair* d_vox, const ApdConsts& cst, int mode) {
+  if (method == GORIO_METHOD_VGICP) lm_solve_vgicp_kernel<<<grid, 1024, 0, stream>>>(d_desc, d_vox, cst, mode);
+  else if (method == GORIO_METHOD_GICP) lm_solve_kernel<kMethodGicp><<<grid, 1024, 0, stream>>>(d_desc, cst, mode);
+  else lm_solve_kernel<kMethodApd><<<grid, 1024, 0, stream>>>(d_desc, cst, mode);
+}
+void launch_shard_trial_error(int method, hipStream_t stream, const PairDesc* d_desc, double* ered, const ApdConsts& cst, int mode) {
+  if (method == GORIO_METHOD_GICP) shard_trial_error_kernel<kMethodGicp><<<1, 1024, 0, stream>>>(d_desc, ered, cst, mode);
+  else shard_trial_error_kernel<kMethodApd><<<1, 1024, 0, stream>>>(d_desc, ered, cst, mode);
+}
+
 int check_ready(gorio_apd* h) {
   if (!h->src->present) return fail(h, GORIO_ERR_STATE, "no input source set (setInputSource)");
   if (!h->tgt->present) return fail(h, GORIO_ERR_STATE, "no input target set (setInputTarget)");
   const gorio_apd_params& p = h->params;
   if (shared_cov_mismatch(h)) return fail(h, GORIO_ERR_INVALID, "the shared target's covariances were estimated with another k_correspondences / regularization: give this handle a target of its own (setInputTarget)");
+  if (shared_voxel_mismatch(h)) return fail(h, GORIO_ERR_INVALID, "the shared target's voxel map was built with another voxel_resolution / voxel_mode: give this handle a target of its own (setInputTarget)");
+  if (h->method == GORIO_METHOD_VGICP && (h->comm || (h->shard_only && h->comm_world > 1)))
+    return fail(h, GORIO_ERR_STATE, "FastVGICP has no sharded-source mode (gorio_apd_comm_init / gorio_apd_debug_set_shard): use an unsharded handle");
   if (p.k_correspondences < 1 || p.k_correspondences > 32) return fail(h, GORIO_ERR_UNSUPPORTED, "k_correspondences must be in [1, 32]");
   if (p.regularization < 0 || p.regularization > 4) return fail(h, GORIO_ERR_UNSUPPORTED, "unknown regularization method (the reference aborts here, APD:389-391)");
   if (h->src->cov_count != h->src->n && h->src->n < p.k_correspondences) return fail(h, GORIO_ERR_INVALID, "source cloud has fewer points than k_correspondences (undefined in the reference, APD:366-369)");
@@ -757,6 +945,12 @@ void fill_desc(gorio_apd* h, PairDesc& d, PairState* state, long total_src_waves
     d.shard_lo = (int)(nb * h->comm_rank / h->comm_world) * 256;
     d.shard_hi = h->comm_rank == h->comm_world - 1 ? INT_MAX : (int)(nb * (h->comm_rank + 1) / h->comm_world) * 256;
   }
+}
+
+// FastVGICP linearisations reduce one partial per 256 (point, offset) slots (vgicp_linearize_kernel), not per 256 points
+void vgicp_desc(const gorio_apd* h, PairDesc& d) {
+  d.partials = h->v_partials;
+  d.nblk = (int)(((size_t)h->src->n * h->v_n_off + 255) / 256);
 }
 
 void init_state(PairState& s, const double* T16) {
@@ -819,6 +1013,9 @@ int align_impl(gorio_apd** hs, int count, const float* guesses, float* T_out, do
       gorio_apd_params a = h->params, b = lead->params;
       a.cl_weight_points = b.cl_weight_points = 0;
       if (std::memcmp(&a, &b, sizeof(a)) != 0) return fail(lead, GORIO_ERR_INVALID, "all handles of a batch must carry the same parameters (cl_weight_points excepted)");
+      if (h->method != lead->method) return fail(lead, GORIO_ERR_INVALID, "all handles of a batch must use the same registration method (gorio_apd_set_method)");
+      if (h->method == GORIO_METHOD_VGICP && (h->voxel_resolution != lead->voxel_resolution || h->voxel_search != lead->voxel_search || h->voxel_mode != lead->voxel_mode))
+        return fail(lead, GORIO_ERR_INVALID, "all FastVGICP handles of a batch must carry the same voxel_resolution / voxel_search / voxel_mode");
     }
     int rc = check_ready(h);
     if (rc) {
@@ -845,11 +1042,26 @@ int align_impl(gorio_apd** hs, int count, const float* guesses, float* T_out, do
       all.emplace_back(hs[q], hs[q]->src.get());
       all.emplace_back(hs[q], hs[q]->tgt.get());
     }
+    if (lead->method == GORIO_METHOD_VGICP) all = todo;  // no nearest-neighbour search in this mode: only the k-NN covariance stage of the stale clouds reads an index
     rc = run_index_build(lead, all);
     if (rc) return rc;
   }
   rc = run_covariances(lead, todo);
   if (rc) return rc;
+  const int method = lead->method;
+  const bool vgicp = method == GORIO_METHOD_VGICP;
+  if (vgicp) {  // VG:120-123: the voxel map of every target (a shared target's once: the second sharer finds it valid)
+    for (int q = 0; q < count; ++q) {
+      rc = build_voxelmap(hs[q], *hs[q]->tgt, hs[q]->voxel_resolution, hs[q]->voxel_mode);
+      if (!rc) rc = ensure_voxel_pair(hs[q]);
+      if (rc) {
+        if (hs[q] != lead) lead->err = hs[q]->err;
+        return rc;
+      }
+    }
+    rc = ensure_vox_batch(lead, count);
+    if (rc) return rc;
+  }
 
   rc = ensure_batch(lead, count);
   if (rc) return rc;
@@ -868,6 +1080,7 @@ int align_impl(gorio_apd** hs, int count, const float* guesses, float* T_out, do
     for (int i = 0; i < 16; ++i) T[i] = (double)guesses[(size_t)q * 16 + i];  // LSQ:56
     init_state(states[q], T);
     fill_desc(hs[q], descs[q], hs[q]->d_state, total_src_waves);
+    if (vgicp) vgicp_desc(hs[q], descs[q]);
     // Gauss-Newton never reads the Mahalanobis matrices back (only LM error trials and the parity hooks do): do not store them
     descs[q].write_omega = lead->params.optimizer == GORIO_OPT_LEVENBERG_MARQUARDT ? 1 : 0;
     hs[q]->omega_valid = descs[q].write_omega != 0;
@@ -876,8 +1089,15 @@ int align_impl(gorio_apd** hs, int count, const float* guesses, float* T_out, do
   }
   if (int rc2 = upload_staged(lead, lead->pin_desc, lead->d_desc, descs.data(), sizeof(PairDesc) * count)) return rc2;
   if (int rc2 = upload_staged(lead, lead->pin_states, lead->d_states_batch, states.data(), sizeof(PairState) * count)) return rc2;
+  int max_off = 1;
+  if (vgicp) {
+    std::vector<VoxPair> voxs(count);
+    for (int q = 0; q < count; ++q) voxs[q] = make_vox_pair(hs[q], descs[q].write_omega);
+    max_off = lead->v_n_off;
+    if (int rc2 = upload_staged(lead, lead->pin_vox, lead->d_vox, voxs.data(), sizeof(VoxPair) * count)) return rc2;
+  }
   scatter_states_kernel<<<count, 64, 0, lead->stream>>>(lead->d_desc, lead->d_states_batch);
-  arm_keys_kernel<<<dim3(std::min(64, (max_n + 255) / 256), count), 256, 0, lead->stream>>>(lead->d_desc);
+  if (!vgicp) arm_keys_kernel<<<dim3(std::min(64, (max_n + 255) / 256), count), 256, 0, lead->stream>>>(lead->d_desc);  // the search's key buffers
 
   const ApdConsts cst = make_consts(lead->params);
   const dim3 g_nn((max_n + 255) / 256, max_splits, count), g_lin((max_n + 255) / 256, 1, count), g_lm(count);
@@ -887,7 +1107,7 @@ int align_impl(gorio_apd** hs, int count, const float* guesses, float* T_out, do
     const bool lm = lead->params.optimizer == GORIO_OPT_LEVENBERG_MARQUARDT;
     for (int it = 0; it < max_it; ++it) {
       launch_nn(lead, lead->d_desc, g_nn, roundup(max_n, 512), 1, max_m);
-      linearize_kernel<<<g_lin, 256, 0, lead->stream>>>(lead->d_desc, cst, 0);
+      launch_linearize(method, g_lin, lead->stream, lead->d_desc, cst, 0);
       shard_reduce_partials_kernel<<<1, 64, 0, lead->stream>>>(lead->d_desc, lead->d_red);
       NCCL_TRY(lead, R.AllReduce(lead->d_red, lead->d_red, 28, ncclDouble, ncclSum, lead->comm, lead->stream));  // THE collective: H, b, error
       ++lead->allreduce_count;
@@ -898,7 +1118,7 @@ int align_impl(gorio_apd** hs, int count, const float* guesses, float* T_out, do
         // two trial slots per round trip: a Levenberg-Marquardt step is almost always decided by the first or second trial; every rank
         // reads the same flags, so every rank enqueues the same sequence of collectives
         for (int t = 0; t < 2 && trials < lead->params.lm_max_iterations; ++t, ++trials) {
-          shard_trial_error_kernel<<<1, 1024, 0, lead->stream>>>(lead->d_desc, lead->d_red + 28, cst, 0);
+          launch_shard_trial_error(method, lead->stream, lead->d_desc, lead->d_red + 28, cst, 0);
           NCCL_TRY(lead, R.AllReduce(lead->d_red + 28, lead->d_red + 28, 1, ncclDouble, ncclSum, lead->comm, lead->stream));
           ++lead->allreduce_count;
           shard_trial_decide_kernel<<<1, 64, 0, lead->stream>>>(lead->d_desc, lead->d_red + 28, cst, 0);
@@ -929,20 +1149,28 @@ int align_impl(gorio_apd** hs, int count, const float* guesses, float* T_out, do
   // batches first enqueue as many iterations as the previous batch needed -- on like data that look is the only one.  A finished pair's
   // kernels return at once, so the schedule of the looks never changes a result.
   int chunk_iters = lead->align_budget > 0 ? lead->align_budget : 4;
-  const bool fuse_gn = lead->params.optimizer != GORIO_OPT_LEVENBERG_MARQUARDT && lead->fuse_step;
+  const bool fuse_gn = lead->params.optimizer != GORIO_OPT_LEVENBERG_MARQUARDT && lead->fuse_step && !vgicp;
+  const dim3 g_vlin((unsigned int)(((size_t)max_n * max_off + 255) / 256), 1, count);
   const int max_it = lead->params.max_iterations;
   while (launched < max_it) {
     const int todo_it = std::min(chunk_iters, max_it - launched);
     StageChain chain(lead);
     for (int it = 0; it < todo_it; ++it) {
+      if (vgicp) {  // no nearest-neighbour search: the lookups are part of the linearisation (VG:73-116)
+        vgicp_linearize_kernel<<<g_vlin, 256, 0, lead->stream>>>(lead->d_desc, lead->d_vox);
+        chain.mark(2);
+        launch_lm_solve(method, g_lm, lead->stream, lead->d_desc, lead->d_vox, cst, 0);
+        chain.mark(3);
+        continue;
+      }
       launch_nn(lead, lead->d_desc, g_nn, roundup(max_n, 512), count, max_m, launched + it);
       chain.mark(1);
       // Gauss-Newton needs no error trials: the optimiser step rides on the linearisation launch (its last workgroup per pair).
       // Levenberg-Marquardt keeps its own launch: an error trial wants the 1024 threads of lm_solve_kernel.
-      linearize_kernel<<<g_lin, 256, 0, lead->stream>>>(lead->d_desc, cst, fuse_gn ? 1 : 0);
+      launch_linearize(method, g_lin, lead->stream, lead->d_desc, cst, fuse_gn ? 1 : 0);
       chain.mark(2);
       if (!fuse_gn) {
-        lm_solve_kernel<<<g_lm, 1024, 0, lead->stream>>>(lead->d_desc, cst, 0);
+        launch_lm_solve(method, g_lm, lead->stream, lead->d_desc, nullptr, cst, 0);
         chain.mark(3);
       }
     }
@@ -993,12 +1221,22 @@ int fitness_splits(long waves) {
   return splits;
 }
 
-int single_desc(gorio_apd* h) {
+// solver: the descriptor feeds linearize / compute_error (in FastVGICP mode with the slot table behind it), not a fitness search
+int single_desc(gorio_apd* h, bool solver = false) {
   int rc = ensure_batch(h, 1);
   if (rc) return rc;
   PairDesc d;
   fill_desc(h, d, h->d_state, (h->src->n + 63) / 64);
+  if (solver && h->method == GORIO_METHOD_VGICP) vgicp_desc(h, d);
   HIP_TRY(h, hipMemcpyAsync(h->d_desc, &d, sizeof(PairDesc), hipMemcpyHostToDevice, h->stream));
+  if (solver && h->method == GORIO_METHOD_VGICP) {
+    rc = ensure_vox_batch(h, 1);
+    if (rc) return rc;
+    const VoxPair v = make_vox_pair(h, 1);
+    HIP_TRY(h, hipMemcpyAsync(h->d_vox, &v, sizeof(VoxPair), hipMemcpyHostToDevice, h->stream));
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    return GORIO_OK;
+  }
   HIP_TRY(h, hipStreamSynchronize(h->stream));
   return GORIO_OK;
 }
@@ -1068,9 +1306,10 @@ void gorio_apd_destroy(gorio_apd_t* h) {
   h->src.reset();
   h->tgt.reset();
   hipFree(h->best_key); hipFree(h->seed); hipFree(h->nn_work); hipFree(h->nn_plan); hipFree(h->corr); hipFree(h->sqd); hipFree(h->omega6); hipFree(h->partials);
+  hipFree(h->v_slots); hipFree(h->v_omega6); hipFree(h->v_partials); hipFree(h->d_vox);
   hipFree(h->d_state); hipFree(h->d_desc); hipFree(h->d_states_batch); hipFree(h->d_jobs); hipFree(h->d_ijobs); hipFree(h->d_fit); hipFree(h->d_copy_jobs);
   for (auto& e : h->ev_pool) { hipEventDestroy(e.start); hipEventDestroy(e.stop); }
-  for (gorio_apd::Pinned* b : {&h->pin_ijobs, &h->pin_jobs, &h->pin_desc, &h->pin_states, &h->pin_copy}) {
+  for (gorio_apd::Pinned* b : {&h->pin_ijobs, &h->pin_jobs, &h->pin_desc, &h->pin_states, &h->pin_copy, &h->pin_vox}) {
     if (b->p) hipHostFree(b->p);
     if (b->ev) hipEventDestroy(b->ev);
   }
@@ -1097,6 +1336,100 @@ int gorio_apd_set_params(gorio_apd_t* h, const gorio_apd_params* p) {
 int gorio_apd_get_params(const gorio_apd_t* h, gorio_apd_params* p) {
   if (!h || !p) return GORIO_ERR_INVALID;
   *p = h->params;
+  return GORIO_OK;
+}
+
+int gorio_apd_set_method(gorio_apd_t* h, int method, double voxel_resolution, int voxel_search, int voxel_mode) {
+  if (!h) return GORIO_ERR_INVALID;
+  if (method != GORIO_METHOD_APDGICP && method != GORIO_METHOD_GICP && method != GORIO_METHOD_VGICP) return fail(h, GORIO_ERR_UNSUPPORTED, "set_method: unknown registration method");
+  if (voxel_search == GORIO_VOXEL_DIRECT_RADIUS) return fail(h, GORIO_ERR_UNSUPPORTED, "set_method: DIRECT_RADIUS is not supported (the reference aborts there, VOX:13-15)");
+  if (voxel_search != GORIO_VOXEL_DIRECT27 && voxel_search != GORIO_VOXEL_DIRECT7 && voxel_search != GORIO_VOXEL_DIRECT1) return fail(h, GORIO_ERR_UNSUPPORTED, "set_method: unknown neighbour search method");
+  if (voxel_mode != GORIO_VOXEL_ADDITIVE && voxel_mode != GORIO_VOXEL_ADDITIVE_WEIGHTED && voxel_mode != GORIO_VOXEL_MULTIPLICATIVE) return fail(h, GORIO_ERR_UNSUPPORTED, "set_method: unknown voxel accumulation mode");
+  if (!(voxel_resolution > 0.0) || !std::isfinite(voxel_resolution)) return fail(h, GORIO_ERR_UNSUPPORTED, "set_method: voxel_resolution must be positive");
+  if (method == GORIO_METHOD_VGICP && h->comm) return fail(h, GORIO_ERR_STATE, "set_method: FastVGICP has no sharded-source mode (the handle has a communicator)");
+  h->method = method;
+  h->voxel_resolution = voxel_resolution;
+  h->voxel_search = voxel_search;
+  h->voxel_mode = voxel_mode;
+  h->corr_valid = false;  // correspondences of another method (or another neighbourhood) mean nothing to this one
+  h->omega_valid = false;
+  return GORIO_OK;
+}
+
+int gorio_apd_get_method(const gorio_apd_t* h, int* method, double* voxel_resolution, int* voxel_search, int* voxel_mode) {
+  if (!h) return GORIO_ERR_INVALID;
+  if (method) *method = h->method;
+  if (voxel_resolution) *voxel_resolution = h->voxel_resolution;
+  if (voxel_search) *voxel_search = h->voxel_search;
+  if (voxel_mode) *voxel_mode = h->voxel_mode;
+  return GORIO_OK;
+}
+
+int gorio_apd_get_voxelmap(gorio_apd_t* h, int* coord3, int* num_points, double* mean4, double* cov16, int capacity, int* n_voxels) {
+  if (!h || !n_voxels) return GORIO_ERR_INVALID;
+  if (h->method != GORIO_METHOD_VGICP) return fail(h, GORIO_ERR_STATE, "get_voxelmap: the handle is not in FastVGICP mode (gorio_apd_set_method)");
+  HIP_TRY(h, hipSetDevice(h->device));
+  DevCloud& t = *h->tgt;  // the map depends on the target alone: no source is asked for, none is processed
+  if (!t.present) return fail(h, GORIO_ERR_STATE, "get_voxelmap: no input target set (setInputTarget)");
+  if (shared_cov_mismatch(h)) return fail(h, GORIO_ERR_INVALID, "the shared target's covariances were estimated with another k_correspondences / regularization");
+  if (shared_voxel_mismatch(h)) return fail(h, GORIO_ERR_INVALID, "the shared target's voxel map was built with another voxel_resolution / voxel_mode");
+  int rc = GORIO_OK;
+  if (t.cov_count != t.n) {  // calculate_covariances (GICP:262-330) of the target only
+    const gorio_apd_params& p = h->params;
+    if (p.k_correspondences < 1 || p.k_correspondences > 32) return fail(h, GORIO_ERR_UNSUPPORTED, "k_correspondences must be in [1, 32]");
+    if (t.n < p.k_correspondences) return fail(h, GORIO_ERR_INVALID, "target cloud has fewer points than k_correspondences (undefined in the reference, APD:366-369)");
+    std::vector<std::pair<gorio_apd*, DevCloud*>> todo = {{h, &t}};
+    if (p.search == GORIO_SEARCH_PRUNED) rc = run_index_build(h, todo);
+    if (!rc) rc = run_covariances(h, todo);
+    if (rc) return rc;
+  }
+  rc = build_voxelmap(h, t, h->voxel_resolution, h->voxel_mode);
+  if (rc) return rc;
+  const int nv = t.vm_nv;
+  *n_voxels = nv;
+  if (capacity < nv || (!coord3 && !num_points && !mean4 && !cov16)) return GORIO_OK;
+  std::vector<unsigned long long> vkey(nv);
+  std::vector<double> mean((size_t)nv * 3), c6((size_t)nv * 6);
+  std::vector<int> num(nv);
+  HIP_TRY(h, hipMemcpyAsync(vkey.data(), t.vm_vkey, sizeof(unsigned long long) * nv, hipMemcpyDeviceToHost, h->stream));
+  HIP_TRY(h, hipMemcpyAsync(mean.data(), t.vm_mean, sizeof(double) * 3 * nv, hipMemcpyDeviceToHost, h->stream));
+  HIP_TRY(h, hipMemcpyAsync(c6.data(), t.vm_cov6, sizeof(double) * 6 * nv, hipMemcpyDeviceToHost, h->stream));
+  HIP_TRY(h, hipMemcpyAsync(num.data(), t.vm_num, sizeof(int) * nv, hipMemcpyDeviceToHost, h->stream));
+  HIP_TRY(h, hipStreamSynchronize(h->stream));
+  const double c33 = t.vm_mult ? 1.0 : 0.0;  // finalize(): the multiplicative voxel inverts a matrix whose (3,3) is 1 (VOX:97-100), the additive one divides a 0
+  for (int v = 0; v < nv; ++v) {
+    if (coord3) {
+      const unsigned long long id = vkey[v];
+      const unsigned long long d1 = (unsigned long long)t.vm_dim[1], d2 = (unsigned long long)t.vm_dim[2];
+      coord3[3 * (size_t)v + 2] = (int)(id % d2) + t.vm_min[2];
+      coord3[3 * (size_t)v + 1] = (int)((id / d2) % d1) + t.vm_min[1];
+      coord3[3 * (size_t)v] = (int)(id / (d2 * d1)) + t.vm_min[0];
+    }
+    if (num_points) num_points[v] = num[v];
+    if (mean4) {
+      double* o = mean4 + 4 * (size_t)v;
+      o[0] = mean[3 * (size_t)v]; o[1] = mean[3 * (size_t)v + 1]; o[2] = mean[3 * (size_t)v + 2]; o[3] = 1.0;
+    }
+    if (cov16) {
+      const double* q = c6.data() + 6 * (size_t)v;
+      double* o = cov16 + 16 * (size_t)v;
+      o[0] = q[0]; o[1] = q[1]; o[2] = q[2]; o[3] = 0;
+      o[4] = q[1]; o[5] = q[3]; o[6] = q[4]; o[7] = 0;
+      o[8] = q[2]; o[9] = q[4]; o[10] = q[5]; o[11] = 0;
+      o[12] = 0; o[13] = 0; o[14] = 0; o[15] = c33;
+    }
+  }
+  return GORIO_OK;
+}
+
+int gorio_apd_get_voxel_correspondences(gorio_apd_t* h, int* voxel_idx, int n_source_times_offsets) {
+  if (!h || !voxel_idx) return GORIO_ERR_INVALID;
+  if (h->method != GORIO_METHOD_VGICP) return fail(h, GORIO_ERR_STATE, "get_voxel_correspondences: the handle is not in FastVGICP mode (gorio_apd_set_method)");
+  if (!h->corr_valid || !h->v_slots) return fail(h, GORIO_ERR_STATE, "no voxel correspondences held");
+  if ((size_t)n_source_times_offsets != (size_t)h->src->n * h->v_n_off) return fail(h, GORIO_ERR_INVALID, "get_voxel_correspondences: size mismatch");
+  HIP_TRY(h, hipSetDevice(h->device));
+  HIP_TRY(h, hipMemcpyAsync(voxel_idx, h->v_slots, sizeof(int) * (size_t)n_source_times_offsets, hipMemcpyDeviceToHost, h->stream));
+  HIP_TRY(h, hipStreamSynchronize(h->stream));
   return GORIO_OK;
 }
 
@@ -1152,7 +1485,7 @@ int gorio_apd_set_clouds_device_batch(gorio_apd_t** handles, int count, const go
       jobs.push_back(CopyJob{in.x, in.y, in.z, in.label, c.x, c.y, c.z, c.label, c.p4, in.n, c.n_pad});
       max_pad = std::max(max_pad, c.n_pad);
       c.present = true;
-      c.cov_count = 0;
+      c.cov_count = 0; c.vm_valid = false;
       c.idx_valid = false;
       h->corr_valid = false;
     }
@@ -1174,13 +1507,13 @@ int gorio_apd_set_clouds_device_batch(gorio_apd_t** handles, int count, const go
 int gorio_apd_clear_source(gorio_apd_t* h) {
   if (!h) return GORIO_ERR_INVALID;
   make_private(h, h->src);
-  h->src->present = false; h->src->n = 0; h->src->cov_count = 0; h->corr_valid = false;  // APD:101-105
+  h->src->present = false; h->src->n = 0; h->src->cov_count = 0; h->src->vm_valid = false; h->corr_valid = false;  // APD:101-105
   return GORIO_OK;
 }
 int gorio_apd_clear_target(gorio_apd_t* h) {
   if (!h) return GORIO_ERR_INVALID;
   make_private(h, h->tgt);
-  h->tgt->present = false; h->tgt->n = 0; h->tgt->cov_count = 0; h->corr_valid = false;  // APD:107-112
+  h->tgt->present = false; h->tgt->n = 0; h->tgt->cov_count = 0; h->tgt->vm_valid = false; h->corr_valid = false;  // APD:107-112
   return GORIO_OK;
 }
 int gorio_apd_set_target_shared(gorio_apd_t* h, gorio_apd_t* owner) {
@@ -1192,7 +1525,12 @@ int gorio_apd_set_target_shared(gorio_apd_t* h, gorio_apd_t* owner) {
     if (t.cov_count == t.n && t.cov_k >= 0 && (t.cov_k != h->params.k_correspondences || t.cov_reg != h->params.regularization))
       return fail(h, GORIO_ERR_INVALID, "set_target_shared: the owner's covariances were estimated with another k_correspondences / regularization than this handle's");
   }
-  h->tgt = owner->tgt;  // points, covariances, search index: one copy on the device, alive until the last handle lets go of it
+  {
+    const DevCloud& t = *owner->tgt;
+    if (h->method == GORIO_METHOD_VGICP && t.vm_valid && (t.vm_res != h->voxel_resolution || t.vm_mult != (h->voxel_mode == GORIO_VOXEL_MULTIPLICATIVE)))
+      return fail(h, GORIO_ERR_INVALID, "set_target_shared: the owner's voxel map was built with another voxel_resolution / voxel_mode than this handle's");
+  }
+  h->tgt = owner->tgt;  // points, covariances, search index, voxel map: one copy on the device, alive until the last handle lets go of it
   h->corr_valid = false;
   return GORIO_OK;
 }
@@ -1317,7 +1655,7 @@ int gorio_apd_set_target_submap(gorio_apd_t* h, const gorio_apd_keyframe* frames
   HIP_TRY(h, hipGetLastError());
   HIP_TRY(h, hipStreamSynchronize(h->stream));  // the staging vectors die with this call
   c.present = true;
-  c.cov_count = 0;
+  c.cov_count = 0; c.vm_valid = false;
   c.idx_valid = false;
   c.knn_valid = false;
   h->corr_valid = false;
@@ -1354,7 +1692,7 @@ static int set_covs(gorio_apd* h, DevCloud& c, const double* cov, int n) {
   if (!c.present || n != c.n) {
     // the reference stores the vector whatever its size (APD:138-145) and recomputes the covariances in computeTransformation when the
     // size does not match the cloud (APD:149-154): a mismatching set is therefore the same as none
-    c.cov_count = 0;
+    c.cov_count = 0; c.vm_valid = false;
     c.knn_valid = false;
     return GORIO_OK;
   }
@@ -1370,6 +1708,7 @@ static int set_covs(gorio_apd* h, DevCloud& c, const double* cov, int n) {
   HIP_TRY(h, hipGetLastError());
   HIP_TRY(h, hipStreamSynchronize(h->stream));
   c.cov_count = n;
+  c.vm_valid = false;
   c.cov_k = c.cov_reg = -1;
   c.knn_valid = false;  // these covariances did not come from a k-NN search of this library
   return GORIO_OK;
@@ -1460,7 +1799,13 @@ int gorio_apd_linearize(gorio_apd_t* h, const double T[16], double* H, double* b
     rc = run_index_build(h, all);
     if (rc) return rc;
   }
-  rc = single_desc(h);
+  const bool vgicp = h->method == GORIO_METHOD_VGICP;
+  if (vgicp) {  // VG:120-123
+    rc = build_voxelmap(h, *h->tgt, h->voxel_resolution, h->voxel_mode);
+    if (!rc) rc = ensure_voxel_pair(h);
+    if (rc) return rc;
+  }
+  rc = single_desc(h, true);
   if (rc) return rc;
   PairState s;
   init_state(s, T);
@@ -1469,15 +1814,20 @@ int gorio_apd_linearize(gorio_apd_t* h, const double T[16], double* H, double* b
   const ApdConsts cst = make_consts(h->params);
   PairDesc d;
   fill_desc(h, d, h->d_state, (h->src->n + 63) / 64);
+  if (vgicp) vgicp_desc(h, d);
   const int nbx = (h->src->n + 255) / 256;
-  launch_nn(h, h->d_desc, dim3(nbx, d.nn_splits, 1), roundup(h->src->n, 512), 1, h->tgt->n);
-  linearize_kernel<<<dim3(nbx, 1, 1), 256, 0, h->stream>>>(h->d_desc, cst, 0);
+  if (vgicp) {
+    vgicp_linearize_kernel<<<dim3(d.nblk, 1, 1), 256, 0, h->stream>>>(h->d_desc, h->d_vox);
+  } else {
+    launch_nn(h, h->d_desc, dim3(nbx, d.nn_splits, 1), roundup(h->src->n, 512), 1, h->tgt->n);
+    launch_linearize(h->method, dim3(nbx, 1, 1), h->stream, h->d_desc, cst, 0);
+  }
   if (h->comm) {  // every rank of the communicator makes this call; H, b and the error come back summed over all of them
     shard_reduce_partials_kernel<<<1, 64, 0, h->stream>>>(h->d_desc, h->d_red);
     NCCL_TRY(h, rccl().AllReduce(h->d_red, h->d_red, 28, ncclDouble, ncclSum, h->comm, h->stream));
     shard_begin_kernel<<<1, 64, 0, h->stream>>>(h->d_desc, h->d_red, cst, 1);
   } else {
-    lm_solve_kernel<<<1, 1024, 0, h->stream>>>(h->d_desc, cst, 1);
+    launch_lm_solve(h->method, dim3(1), h->stream, h->d_desc, h->d_vox, cst, 1);
   }
   HIP_TRY(h, hipGetLastError());
   HIP_TRY(h, hipMemcpyAsync(&s, h->d_state, sizeof(s), hipMemcpyDeviceToHost, h->stream));
@@ -1496,7 +1846,7 @@ int gorio_apd_compute_error(gorio_apd_t* h, const double T[16], double* error) {
   if (!h || !T || !error) return GORIO_ERR_INVALID;
   HIP_TRY(h, hipSetDevice(h->device));
   if (!h->corr_valid || !h->omega_valid) return fail(h, GORIO_ERR_STATE, "compute_error needs the correspondences and Mahalanobis matrices of a previous linearize (or LM align)");
-  int rc = single_desc(h);
+  int rc = single_desc(h, true);
   if (rc) return rc;
   double xi[16];
   for (int i = 0; i < 16; ++i) xi[i] = T[i];
@@ -1504,14 +1854,14 @@ int gorio_apd_compute_error(gorio_apd_t* h, const double T[16], double* error) {
   const ApdConsts cst = make_consts(h->params);
   double yi = 0.0;
   if (h->comm) {
-    shard_trial_error_kernel<<<1, 1024, 0, h->stream>>>(h->d_desc, h->d_red + 28, cst, 2);
+    launch_shard_trial_error(h->method, h->stream, h->d_desc, h->d_red + 28, cst, 2);
     NCCL_TRY(h, rccl().AllReduce(h->d_red + 28, h->d_red + 28, 1, ncclDouble, ncclSum, h->comm, h->stream));
     HIP_TRY(h, hipMemcpyAsync(&yi, h->d_red + 28, sizeof(double), hipMemcpyDeviceToHost, h->stream));
     HIP_TRY(h, hipStreamSynchronize(h->stream));
     *error = yi;
     return GORIO_OK;
   }
-  lm_solve_kernel<<<1, 1024, 0, h->stream>>>(h->d_desc, cst, 2);
+  launch_lm_solve(h->method, dim3(1), h->stream, h->d_desc, h->d_vox, cst, 2);
   HIP_TRY(h, hipGetLastError());
   HIP_TRY(h, hipMemcpyAsync(&yi, reinterpret_cast<char*>(h->d_state) + offsetof(PairState, yi), sizeof(double), hipMemcpyDeviceToHost, h->stream));
   HIP_TRY(h, hipStreamSynchronize(h->stream));
@@ -1521,6 +1871,7 @@ int gorio_apd_compute_error(gorio_apd_t* h, const double T[16], double* error) {
 
 int gorio_apd_get_correspondences(gorio_apd_t* h, int* corr, float* sq_dist, int n) {
   if (!h) return GORIO_ERR_INVALID;
+  if (h->method == GORIO_METHOD_VGICP) return fail(h, GORIO_ERR_STATE, "get_correspondences: FastVGICP pairs points with voxels, not with target points (gorio_apd_get_voxel_correspondences)");
   if (!h->corr_valid) return fail(h, GORIO_ERR_STATE, "no correspondences held");
   if (n != h->src->n) return fail(h, GORIO_ERR_INVALID, "get_correspondences: size mismatch");
   HIP_TRY(h, hipSetDevice(h->device));
@@ -1532,6 +1883,7 @@ int gorio_apd_get_correspondences(gorio_apd_t* h, int* corr, float* sq_dist, int
 
 int gorio_apd_get_mahalanobis(gorio_apd_t* h, double* maha, int n) {
   if (!h || !maha) return GORIO_ERR_INVALID;
+  if (h->method == GORIO_METHOD_VGICP) return fail(h, GORIO_ERR_STATE, "get_mahalanobis: FastVGICP holds one matrix per (point, voxel) pair, not per point");
   if (!h->corr_valid || !h->omega_valid) return fail(h, GORIO_ERR_STATE, "no Mahalanobis matrices held (a Gauss-Newton align does not materialise them: call gorio_apd_linearize)");
   if (n != h->src->n) return fail(h, GORIO_ERR_INVALID, "get_mahalanobis: size mismatch");
   HIP_TRY(h, hipSetDevice(h->device));
@@ -1744,6 +2096,7 @@ int gorio_comm_get_unique_id(char id[128]) {
 
 int gorio_apd_comm_init(gorio_apd_t* h, int world_size, int rank, const char id[128]) {
   if (!h || !id || world_size < 1 || rank < 0 || rank >= world_size) return GORIO_ERR_INVALID;
+  if (h->method == GORIO_METHOD_VGICP) return fail(h, GORIO_ERR_STATE, "comm_init: FastVGICP has no sharded-source mode");
   Rccl& R = rccl();
   if (!R.ok) return fail(h, GORIO_ERR_NO_DEVICE, "librccl could not be loaded");
   HIP_TRY(h, hipSetDevice(h->device));

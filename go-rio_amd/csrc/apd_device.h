@@ -104,6 +104,35 @@ struct PairDesc {
   int pad_;
 };
 
+// registration method of a handle (gorio_method, gorio_apd.h): the compile-time variants of linearize_kernel / lm_solve_kernel
+constexpr int kMethodApd = 0;    // fast_gicp::FastAPDGICP
+constexpr int kMethodGicp = 1;   // fast_gicp::FastGICP
+constexpr int kMethodVgicp = 2;  // fast_gicp::FastVGICP
+
+// Gaussian voxel map of a target cloud (GaussianVoxelMap, fast_vgicp_voxel.hpp:124-182): the occupied voxels in ASCENDING order of their
+// linear id ((cx - min.x) * dim.y + (cy - min.y)) * dim.z + (cz - min.z) inside the bounding box of the occupied coordinates, i.e. in
+// lexicographic (cx, cy, cz) order.  lookup_voxel (VOX:167-174) is a binary search over vkey.
+struct VoxelMapView {
+  const unsigned long long* vkey;  // [nv] linear voxel id
+  const double* mean;              // [nv][3]  GaussianVoxel::mean (component 3 is 1)
+  const double* cov6;              // [nv][6]  upper triangle of the 3x3 block of GaussianVoxel::cov
+  const int* num;                  // [nv]     GaussianVoxel::num_points
+  int nv;
+  int min_c[3];
+  int dim[3];
+  double res;                      // voxel_resolution_
+};
+
+// per scan pair of a FastVGICP linearisation: voxel_correspondences_ / voxel_mahalanobis_ (fast_vgicp.hpp:86-87) in a FIXED layout, one
+// slot per (source point, neighbour offset) in the offset order of VOX:16-43
+struct VoxPair {
+  VoxelMapView map;
+  int* slots;      // [n_source][n_off] voxel index (position in the ascending order) or -1
+  double* omega6;  // [n_source][n_off][6] sqrt(num_points) * Mahalanobis 3x3 block of the pair (the weight of VG:149 folded in)
+  int n_off;       // 1, 7 or 27
+  int write_omega;
+};
+
 // XCD-aware placement of a (x, y, units) launch whose third grid dimension counts independent units (scan pairs, clouds): the hardware
 // deals consecutive workgroups round-robin to the 8 XCDs, each with an L2 of its own, so with the plain (blockIdx.x, blockIdx.z) numbering
 // every XCD sees every unit's clouds.  Here unit u runs entirely on XCD u mod 8 -- its source, target, boxes and covariances stay in ONE

@@ -479,6 +479,8 @@ __device__ __forceinline__ double residual_terms(const double* __restrict__ T, f
 }
 
 __device__ void gn_step_tail(const PairDesc& pd, const ApdConsts& cst);
+// this thread's part of FastVGICP::compute_error over the pairs of the last linearise (apd_voxel.hip)
+__device__ double vgicp_error_part(const PairDesc& pd, const VoxPair& vp, const double* __restrict__ T);
 
 __device__ __forceinline__ float sumsq2_f(float a, float b) {  // x^2 + y^2 in float, un-fused (APD:198 squares floats)
   float r = a * a;
@@ -490,6 +492,9 @@ __device__ __forceinline__ float sumsq2_f(float a, float b) {  // x^2 + y^2 in f
 // partial per block: [0..20] upper triangle of H row-major, [21..26] b, [27] weighted error.
 // fuse != 0 (Gauss-Newton aligns): the workgroup that stores the LAST partial of its pair goes on to run the optimiser step
 // (gn_step_tail) -- the partials are summed in block order whoever sums them, so the result is the one lm_solve_kernel gives, one launch earlier.
+// METHOD (compile time, apd_device.h): kMethodApd = FastAPDGICP as above; kMethodGicp = plain FastGICP (GICP:126-257), i.e. no sensor
+// covariance in RCR (GICP:159) and no (1 + geo + cl) error weight (GICP:199).  H and b carry no weight in either (APD:289-293).
+template <int METHOD>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(6, 6))) void linearize_kernel(const PairDesc* __restrict__ descs, ApdConsts cst, int fuse) {
   const GridPos gp = xcd_grid_pos();  // pair -> XCD (apd_device.h)
   const PairDesc& pd = descs[gp.z];
@@ -550,6 +555,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(6, 6))) voi
         T[t] = sst->x0[t];
         Tf[t] = sst->Tf[t];
       }
+      double r00 = 0.0, r01 = 0.0, r02 = 0.0, r11 = 0.0, r12 = 0.0, r22 = 0.0;
+      if constexpr (METHOD == kMethodApd) {
       float qx, qy, qz;
       transform_f(Tf, ax, ay, az, qx, qy, qz);
       // sensor covariance at the transformed point, APD:194-210
@@ -584,25 +591,32 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(6, 6))) voi
       const double A00 = ca * ce * s_x, A01 = -sa * s_y, A02 = ca * se * s_z;
       const double A10 = sa * ce * s_x, A11 = ca * s_y, A12 = sa * se * s_z;
       const double A20 = -se * s_x, A22 = ce * s_z;  // A21 = 0
-      const double r00 = A00 * A00 + A01 * A01 + A02 * A02;
-      const double r01 = A00 * A10 + A01 * A11 + A02 * A12;
-      const double r02 = A00 * A20 + A02 * A22;
-      const double r11 = A10 * A10 + A11 * A11 + A12 * A12;
-      const double r12 = A10 * A20 + A12 * A22;
-      const double r22 = A20 * A20 + A22 * A22;
+      r00 = A00 * A00 + A01 * A01 + A02 * A02;
+      r01 = A00 * A10 + A01 * A11 + A02 * A12;
+      r02 = A00 * A20 + A02 * A22;
+      r11 = A10 * A10 + A11 * A11 + A12 * A12;
+      r12 = A10 * A20 + A12 * A22;
+      r22 = A20 * A20 + A22 * A22;
+      }
       // RCR = (C_B + cov_r) + R (C_A + cov_r) R^T, APD:213-214 (3x3 block; row/col 3 of the 4x4 decouple, APD:215-218)
-      const double a00 = cA[0] + r00, a01 = cA[1] + r01, a02 = cA[2] + r02, a11 = cA[3] + r11, a12 = cA[4] + r12, a22 = cA[5] + r22;
+      double a00 = cA[0], a01 = cA[1], a02 = cA[2], a11 = cA[3], a12 = cA[4], a22 = cA[5];
+      if constexpr (METHOD == kMethodApd) {
+        a00 = cA[0] + r00; a01 = cA[1] + r01; a02 = cA[2] + r02; a11 = cA[3] + r11; a12 = cA[4] + r12; a22 = cA[5] + r22;
+      }  // kMethodGicp: RCR = C_B + T C_A T^T, GICP:159 (r** stay zero and drop out below)
       // M = R * Asym
       const double R00 = T[0], R01 = T[1], R02 = T[2], R10 = T[4], R11 = T[5], R12 = T[6], R20 = T[8], R21 = T[9], R22 = T[10];
       const double M00 = R00 * a00 + R01 * a01 + R02 * a02, M01 = R00 * a01 + R01 * a11 + R02 * a12, M02 = R00 * a02 + R01 * a12 + R02 * a22;
       const double M10 = R10 * a00 + R11 * a01 + R12 * a02, M11 = R10 * a01 + R11 * a11 + R12 * a12, M12 = R10 * a02 + R11 * a12 + R12 * a22;
       const double M20 = R20 * a00 + R21 * a01 + R22 * a02, M21 = R20 * a01 + R21 * a11 + R22 * a12, M22 = R20 * a02 + R21 * a12 + R22 * a22;
-      const double q00 = (cB[0] + r00) + (M00 * R00 + M01 * R01 + M02 * R02);
-      const double q01 = (cB[1] + r01) + (M00 * R10 + M01 * R11 + M02 * R12);
-      const double q02 = (cB[2] + r02) + (M00 * R20 + M01 * R21 + M02 * R22);
-      const double q11 = (cB[3] + r11) + (M10 * R10 + M11 * R11 + M12 * R12);
-      const double q12 = (cB[4] + r12) + (M10 * R20 + M11 * R21 + M12 * R22);
-      const double q22 = (cB[5] + r22) + (M20 * R20 + M21 * R21 + M22 * R22);
+      if constexpr (METHOD == kMethodApd) {
+        cB[0] += r00; cB[1] += r01; cB[2] += r02; cB[3] += r11; cB[4] += r12; cB[5] += r22;
+      }
+      const double q00 = cB[0] + (M00 * R00 + M01 * R01 + M02 * R02);
+      const double q01 = cB[1] + (M00 * R10 + M01 * R11 + M02 * R12);
+      const double q02 = cB[2] + (M00 * R20 + M01 * R21 + M02 * R22);
+      const double q11 = cB[3] + (M10 * R10 + M11 * R11 + M12 * R12);
+      const double q12 = cB[4] + (M10 * R20 + M11 * R21 + M12 * R22);
+      const double q22 = cB[5] + (M20 * R20 + M21 * R21 + M22 * R22);
       PointTerms p;
       inv_sym3(q00, q01, q02, q11, q12, q22, p.o00, p.o01, p.o02, p.o11, p.o12, p.o22);  // APD:217
       if (pd.write_omega) {
@@ -610,8 +624,12 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(6, 6))) voi
       }
 
       const double quad = residual_terms(T, ax, ay, az, tb.x, tb.y, tb.z, p);  // APD:255-263
-      const double w = 1.0 + src_geo_w + ((tb.w == src_label) ? 1.0 / (double)(pd.cl_points > 0 ? pd.cl_points : n) : 0.0);  // APD:266-276
-      acc[27] = w * quad;
+      if constexpr (METHOD == kMethodApd) {
+        const double w = 1.0 + src_geo_w + ((tb.w == src_label) ? 1.0 / (double)(pd.cl_points > 0 ? pd.cl_points : n) : 0.0);  // APD:266-276
+        acc[27] = w * quad;
+      } else {
+        acc[27] = quad;  // GICP:199
+      }
 
       // J = [skew(Ta) | -I], APD:284-287.  With S = skew(Ta): H_rr = S^T O S, H_rt = -S^T O, H_tt = O, b_r = S^T O e, b_t = -O e.
       // G = S^T O (3x3): rows of S^T are (0, a2, -a1), (-a2, 0, a0), (a1, -a0, 0)
@@ -784,19 +802,29 @@ __device__ bool is_converged(const double* __restrict__ delta, double inv_rot_ep
 }
 
 // compute_error (APD:310-346) over all source points of one pair by one workgroup; result valid on every thread
-__device__ double block_error(const PairDesc& pd, const double* __restrict__ T, const ApdConsts& cst, double* __restrict__ sred) {
+// (kMethodGicp: GICP:234-257, no weight; kMethodVgicp: VG:183-204 over the slot table of the last linearise, apd_voxel.hip)
+template <int METHOD>
+__device__ double block_error(const PairDesc& pd, const VoxPair* __restrict__ vp, const double* __restrict__ T, const ApdConsts& cst, double* __restrict__ sred) {
   const int n = pd.src.n;
   double sum = 0.0;
-  for (int i = threadIdx.x; i < n; i += blockDim.x) {
-    const int j = pd.corr[i];
-    if (j < 0) continue;
-    const double* om = pd.omega6 + (size_t)i * 6;
-    PointTerms p;
-    p.o00 = om[0]; p.o01 = om[1]; p.o02 = om[2]; p.o11 = om[3]; p.o12 = om[4]; p.o22 = om[5];
-    const float4 tb = pd.tgt.p4[j];
-    const double quad = residual_terms(T, pd.src.x[i], pd.src.y[i], pd.src.z[i], tb.x, tb.y, tb.z, p);
-    const double w = 1.0 + pd.src.geo_w[i] + ((tb.w == pd.src.label[i]) ? 1.0 / (double)(pd.cl_points > 0 ? pd.cl_points : n) : 0.0);
-    sum += w * quad;
+  if constexpr (METHOD == kMethodVgicp) {
+    sum = vgicp_error_part(pd, *vp, T);
+  } else {
+    for (int i = threadIdx.x; i < n; i += blockDim.x) {
+      const int j = pd.corr[i];
+      if (j < 0) continue;
+      const double* om = pd.omega6 + (size_t)i * 6;
+      PointTerms p;
+      p.o00 = om[0]; p.o01 = om[1]; p.o02 = om[2]; p.o11 = om[3]; p.o12 = om[4]; p.o22 = om[5];
+      const float4 tb = pd.tgt.p4[j];
+      const double quad = residual_terms(T, pd.src.x[i], pd.src.y[i], pd.src.z[i], tb.x, tb.y, tb.z, p);
+      if constexpr (METHOD == kMethodApd) {
+        const double w = 1.0 + pd.src.geo_w[i] + ((tb.w == pd.src.label[i]) ? 1.0 / (double)(pd.cl_points > 0 ? pd.cl_points : n) : 0.0);
+        sum += w * quad;
+      } else {
+        sum += quad;  // GICP:253
+      }
+    }
   }
   sum = wave_sum(sum);
   const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
@@ -811,13 +839,14 @@ __device__ double block_error(const PairDesc& pd, const double* __restrict__ T, 
 
 // grid: (pairs), block 1024.  mode 0: full optimiser step (LSQ:67-76 body).  mode 1: only publish H, b, y0 (linearize API).
 // mode 2: only evaluate the error at st->xi with the stored correspondences (compute_error API).
-__device__ void lm_solve_body(const PairDesc& pd, const ApdConsts& cst, int mode) {
+template <int METHOD>
+__device__ void lm_solve_body(const PairDesc& pd, const VoxPair* __restrict__ vp, const ApdConsts& cst, int mode) {
   PairState* __restrict__ st = pd.state;
   __shared__ double sH[36], sb[6], sxi[16], sdelta[16], sd[6], sws[56], sHl[36], snb[6];
   __shared__ double sy0, sred[16];
   __shared__ int sflag;
   if (mode == 2) {
-    const double yi = block_error(pd, st->xi, cst, sred);
+    const double yi = block_error<METHOD>(pd, vp, st->xi, cst, sred);
     if (threadIdx.x == 0) st->yi = yi;
     return;
   }
@@ -892,7 +921,7 @@ __device__ void lm_solve_body(const PairDesc& pd, const ApdConsts& cst, int mode
         isom_mul(sdelta, st->x0, sxi);      // LSQ:144
       }
       __syncthreads();
-      const double yi = block_error(pd, sxi, cst, sred);  // LSQ:145
+      const double yi = block_error<METHOD>(pd, vp, sxi, cst, sred);  // LSQ:145
       if (threadIdx.x == 0) {
         st->n_error += 1;
         double den = 0.0;
@@ -945,8 +974,13 @@ __device__ void lm_solve_body(const PairDesc& pd, const ApdConsts& cst, int mode
   }
 }
 
+template <int METHOD>
 __global__ __launch_bounds__(1024) void lm_solve_kernel(const PairDesc* __restrict__ descs, ApdConsts cst, int mode) {
-  lm_solve_body(descs[blockIdx.x], cst, mode);
+  lm_solve_body<METHOD>(descs[blockIdx.x], nullptr, cst, mode);
+}
+// FastVGICP: the same shell over the (point, voxel) pairs; vox[pair] carries the voxel map and the slot table (apd_voxel.hip)
+__global__ __launch_bounds__(1024) void lm_solve_vgicp_kernel(const PairDesc* __restrict__ descs, const VoxPair* __restrict__ vox, ApdConsts cst, int mode) {
+  lm_solve_body<kMethodVgicp>(descs[blockIdx.x], vox + blockIdx.x, cst, mode);
 }
 
 // The Gauss-Newton case of lm_solve_body (mode 0, optimizer 0) for the last workgroup of linearize_kernel: the same sums in the same
@@ -1116,6 +1150,7 @@ __global__ __launch_bounds__(64) void shard_begin_kernel(const PairDesc* __restr
 
 // this rank's part of compute_error at the trial pose (APD:310-346) -> ered[0] (then all-reduced in place).  mode 2: the
 // compute_error API (always evaluates at st->xi).  grid 1, block 1024
+template <int METHOD>
 __global__ __launch_bounds__(1024) void shard_trial_error_kernel(const PairDesc* __restrict__ descs, double* __restrict__ ered, ApdConsts cst, int mode) {
   const PairDesc& pd = descs[0];
   PairState* __restrict__ st = pd.state;
@@ -1127,7 +1162,7 @@ __global__ __launch_bounds__(1024) void shard_trial_error_kernel(const PairDesc*
   }
   if (threadIdx.x < 16) sxi[threadIdx.x] = st->xi[threadIdx.x];
   __syncthreads();
-  const double yi = block_error(pd, sxi, cst, sred);
+  const double yi = block_error<METHOD>(pd, nullptr, sxi, cst, sred);
   if (threadIdx.x == 0) ered[0] = yi;
 }
 

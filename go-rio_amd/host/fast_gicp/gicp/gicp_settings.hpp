@@ -14,7 +14,8 @@ enum class RegularizationMethod {
   FROBENIUS            // lambda I added, then normalised by the Frobenius norm of the inverse
 };
 
-// only used by the voxelised registrations of fast_gicp (not part of this back end); kept so that headers including this file compile
+// FastVGICP's setNeighborSearchMethod / setVoxelAccumulationMode (fast_vgicp.hpp:59-61); they travel through the C ABI as gorio_voxel_search /
+// gorio_voxel_mode (gorio_apd_set_method)
 enum class NeighborSearchMethod { DIRECT27, DIRECT7, DIRECT1, DIRECT_RADIUS };
 enum class VoxelAccumulationMode { ADDITIVE, ADDITIVE_WEIGHTED, MULTIPLICATIVE };
 

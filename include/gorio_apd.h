@@ -43,6 +43,14 @@ typedef enum { GORIO_OPT_GAUSS_NEWTON = 0, GORIO_OPT_LEVENBERG_MARQUARDT = 1 } g
 /* correspondence search strategy; every mode returns the SAME indices (exact search, ties -> lowest index) */
 typedef enum { GORIO_SEARCH_BRUTE_FORCE = 0, GORIO_SEARCH_PRUNED = 1 } gorio_search;
 
+/* which fast_gicp registration a handle stands for: the three classes select_registration_method hands out through one pcl::Registration
+ * pointer (REG:28-37 FAST_APDGICP, REG:63-67 FAST_GICP, REG:68-71 FAST_VGICP) */
+typedef enum { GORIO_METHOD_APDGICP = 0, GORIO_METHOD_GICP = 1, GORIO_METHOD_VGICP = 2 } gorio_method;
+/* fast_gicp::NeighborSearchMethod, gicp_settings.hpp:8 (same order) */
+typedef enum { GORIO_VOXEL_DIRECT27 = 0, GORIO_VOXEL_DIRECT7 = 1, GORIO_VOXEL_DIRECT1 = 2, GORIO_VOXEL_DIRECT_RADIUS = 3 } gorio_voxel_search;
+/* fast_gicp::VoxelAccumulationMode, gicp_settings.hpp:10 (same order) */
+typedef enum { GORIO_VOXEL_ADDITIVE = 0, GORIO_VOXEL_ADDITIVE_WEIGHTED = 1, GORIO_VOXEL_MULTIPLICATIVE = 2 } gorio_voxel_mode;
+
 typedef struct {
   int k_correspondences;         /* setCorrespondenceRandomness, APD:45; default 20 (APD:21); <= 32 */
   int regularization;            /* setRegularizationMethod, APD:50; default PLANE (APD:25) */
@@ -75,6 +83,38 @@ void gorio_apd_default_params(gorio_apd_params* p);
 /* all setters of APD:34-65, LSQ:30-42 and the pcl::Registration setters used at REG:42-44, in one call */
 int gorio_apd_set_params(gorio_apd_t* h, const gorio_apd_params* p);
 int gorio_apd_get_params(const gorio_apd_t* h, gorio_apd_params* p);
+
+/*
+ * Method selection.  GICPH / VGH = fast_gicp/gicp/fast_gicp.hpp / fast_vgicp.hpp, GICP / VG = their impl/ files, VOX = fast_vgicp_voxel.hpp.
+ * A fresh handle is GORIO_METHOD_APDGICP and a caller that never calls the setter sees no change.
+ *   GORIO_METHOD_GICP   FastGICP (GICP:126-257): FastAPDGICP without the sensor covariance in RCR (GICP:159) and without the (1 + geo + cl)
+ *                       error weight (GICP:199, 253); dist_var / azimuth_var / elevation_var / cl_weight_points are not read.  Every entry
+ *                       point of this header works as in APD-GICP mode, the sharded-source collective included.
+ *   GORIO_METHOD_VGICP  FastVGICP (VG:66-204): the target becomes a Gaussian voxel map (GaussianVoxelMap, VOX:124-182; built on the device
+ *                       from the target's covariances at the first linearise / align, reused while target, covariances, voxel_resolution and
+ *                       voxel_mode stay as they are -- the reference rebuilds an equal map at every computeTransformation, VG:66-70), every
+ *                       source point is paired with the occupied voxels among the 1 / 7 / 27 neighbours of voxel_coord(T * point)
+ *                       (VG:83-94) and every pair enters H, b and the error with weight sqrt(num_points) (VG:149).  corr_dist_threshold is
+ *                       not read (the reference has no gate there).  gorio_apd_get_correspondences / _get_mahalanobis (per-point
+ *                       semantics) and the sharded-source calls return GORIO_ERR_STATE in this mode; fitness scores, transform_source,
+ *                       align_batch and shared targets (sharers share the voxel map; a sharer whose voxel_resolution / voxel_mode differ
+ *                       from the ones the shared map was built with gets GORIO_ERR_INVALID, like a differing k_correspondences) keep working.
+ * voxel_resolution = setResolution VG:31, voxel_search = setNeighborSearchMethod VG:36 (gorio_voxel_search), voxel_mode =
+ * setVoxelAccumulationMode VG:41 (gorio_voxel_mode); stored in every mode, read in VGICP mode (constructor defaults 1.0, DIRECT1, ADDITIVE,
+ * VG:22-24).  GORIO_ERR_UNSUPPORTED for DIRECT_RADIUS (neighbor_offsets aborts there, VOX:13-15), voxel_resolution <= 0 and unknown values.
+ * Target coordinates whose voxel grid does not fit the 33-bit voxel id of the map (bounding box of the occupied voxels >= 2^33 cells, or a
+ * non-finite point) make the VGICP linearise / align return GORIO_ERR_UNSUPPORTED.  All handles of a gorio_apd_align_batch must carry the
+ * same method and voxel settings (GORIO_ERR_INVALID otherwise).  Changing the method drops the correspondences held.
+ */
+int gorio_apd_set_method(gorio_apd_t* h, int method, double voxel_resolution, int voxel_search, int voxel_mode);
+int gorio_apd_get_method(const gorio_apd_t* h, int* method, double* voxel_resolution, int* voxel_search, int* voxel_mode);
+/* parity hooks (VGICP mode; they build the map when it is stale): voxelmap_ (VGH:85) as arrays over the occupied voxels in ascending
+ * lexicographic (x, y, z) coordinate order -- coord3: 3 ints, num_points, mean4: GaussianVoxel::mean, cov16: GaussianVoxel::cov row-major
+ * (VOX:74-76).  n_voxels always receives the voxel count; the arrays (any may be NULL) are filled when capacity >= that count.
+ * gorio_apd_get_voxel_correspondences: voxel_correspondences_ (VGH:86) of the last linearise as the fixed table [n_source][n_offsets],
+ * offsets in the order of VOX:16-43, entries = voxel position in the order above or -1. */
+int gorio_apd_get_voxelmap(gorio_apd_t* h, int* coord3, int* num_points, double* mean4, double* cov16, int capacity, int* n_voxels);
+int gorio_apd_get_voxel_correspondences(gorio_apd_t* h, int* voxel_idx, int n_source_times_offsets);
 
 /*
  * setInputSource APD:115-124 / setInputTarget APD:127-135.  xyz points at the first x; consecutive points are
