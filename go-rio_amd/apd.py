@@ -51,7 +51,7 @@ APD_SYMBOLS = [
     "gorio_apd_get_target_covariances", "gorio_apd_calculate_covariances", "gorio_apd_get_knn_indices", "gorio_apd_align",
     "gorio_apd_align_batch", "gorio_apd_linearize", "gorio_apd_compute_error", "gorio_apd_get_correspondences",
     "gorio_apd_get_mahalanobis", "gorio_apd_transform_source", "gorio_apd_fitness_score", "gorio_apd_fitness_score_batch", "gorio_apd_set_profiling",
-    "gorio_apd_get_stage_times", "gorio_apd_set_target_shared", "gorio_comm_get_unique_id", "gorio_apd_comm_init", "gorio_apd_comm_destroy", "gorio_apd_comm_info", "gorio_apd_debug_set_shard", "gorio_apd_debug_set_schedule", "gorio_apd_set_target_submap", "gorio_apd_get_target_points",
+    "gorio_apd_get_stage_times", "gorio_apd_set_target_shared", "gorio_comm_get_unique_id", "gorio_apd_comm_init", "gorio_apd_comm_destroy", "gorio_apd_comm_info", "gorio_apd_debug_set_shard", "gorio_apd_debug_set_schedule", "gorio_apd_debug_get_index", "gorio_apd_set_target_submap", "gorio_apd_get_target_points",
     "gorio_apd_set_method", "gorio_apd_get_method", "gorio_apd_get_voxelmap", "gorio_apd_get_voxel_correspondences",
 ]
 
@@ -320,6 +320,17 @@ class ApdGicp:
 
     def calculateCovariances(self):  # noqa: N802
         _check(self._h, self._lib.gorio_apd_calculate_covariances(self._h))
+
+    def debugGetIndex(self, which):  # noqa: N802 -- test hook: the search index of the source (0) / target (1) as the pruned searches see it
+        sizes = (C.c_int * 6)()
+        _check(self._h, self._lib.gorio_apd_debug_get_index(self._h, int(which), sizes, None, None, None, None, None))
+        n, n_spad, n_tiles, n_super, n_blk, chunk = list(sizes)
+        sxyz = np.empty(7 * n_spad, np.float32)
+        orig = np.empty(n_spad, np.int32)
+        tbox, sbox, bbox = (np.empty((m, 8), np.float32) for m in (n_tiles, n_super, n_blk))
+        _check(self._h, self._lib.gorio_apd_debug_get_index(self._h, int(which), sizes, _p(sxyz, C.c_float), _p(orig, C.c_int), _p(tbox, C.c_float), _p(sbox, C.c_float), _p(bbox, C.c_float)))
+        return dict(n=n, n_spad=n_spad, kd_chunk=chunk, sx=sxyz[:n_spad], sy=sxyz[n_spad : 2 * n_spad], sz=sxyz[2 * n_spad : 3 * n_spad],
+                    s4=sxyz[3 * n_spad :].reshape(n_spad, 4), orig=orig, tbox=tbox, sbox=sbox, bbox=bbox)
 
     def getKnnIndices(self, which):  # noqa: N802
         n = self._n_src if which == 0 else self._n_tgt

@@ -60,6 +60,7 @@ struct DevCloud {
   unsigned int* bb = nullptr;
   int idx_cap = 0, keys_cap = 0;
   bool idx_valid = false;
+  int idx_chunk = 0;       // kd chunk size the index was built with (gorio_apd_debug_get_index)
   // Gaussian voxel map of this cloud as a FastVGICP target (voxelmap_, fast_vgicp.hpp:85): lives with the cloud, so the handles that share a
   // target share its map.  Valid for (vm_res, vm_mult) until the points or the covariances change.
   unsigned long long* vm_keys = nullptr;  // [vm_keys_cap] sort scratch: linear voxel id << 31 | point index
@@ -484,7 +485,12 @@ void resolve_stage_events(gorio_apd* h) {
   h->ev_used = 0;
 }
 
-// Build the search accelerator of every listed cloud that lacks one (batched: one launch per sort stage for all clouds).
+// Build the search accelerator of every listed cloud that lacks one (batched: every launch covers all clouds).  The launches, in order:
+//   bbox_morton_kernel                        bounding box + Morton keys (bbox_init / bbox / morton_kernel when a cloud exceeds kBboxFusedMax)
+//   bitonic_tile_sort_kernel, then per merge size above the sort tile bitonic_global_kernel per stride + bitonic_tile_merge_kernel
+//   kd_refine_kernel                          gather in Morton order, median splits, sx / sy / sz / orig / s4, tile and super-tile boxes
+//   box_block_kernel                          block boxes
+// 9 launches for 16 384-point scans (14 before the gather and the two lower box levels moved into kd_refine_kernel).
 int run_index_build(gorio_apd* lead, std::vector<std::pair<gorio_apd*, DevCloud*>>& clouds) {
   std::vector<std::pair<gorio_apd*, DevCloud*>> todo;
   bool small_call = true;  // every cloud named in the call (built now or not) is a scan-sized one: kd chunks of 2048 points (kd_refine_kernel)
@@ -546,23 +552,27 @@ int run_index_build(gorio_apd* lead, std::vector<std::pair<gorio_apd*, DevCloud*
   {
     StageTimer t(lead, 4);
     const IndexJob* dj = lead->d_ijobs;
-    bbox_init_kernel<<<(nj + 63) / 64, 64, 0, lead->stream>>>(dj, nj);
-    bbox_kernel<<<dim3(std::min(64, (max_n + 255) / 256), nj), 256, 0, lead->stream>>>(dj);
-    morton_kernel<<<dim3((max_pow2 + 255) / 256, nj), 256, 0, lead->stream>>>(dj);
+    if (max_n <= kBboxFusedMax) {
+      bbox_morton_kernel<<<nj, 1024, 0, lead->stream>>>(dj);
+    } else {
+      bbox_init_kernel<<<(nj + 63) / 64, 64, 0, lead->stream>>>(dj, nj);
+      bbox_kernel<<<dim3(std::min(64, (max_n + 255) / 256), nj), 256, 0, lead->stream>>>(dj);
+      morton_kernel<<<dim3((max_pow2 + 255) / 256, nj), 256, 0, lead->stream>>>(dj);
+    }
     bitonic_tile_sort_kernel<<<dim3(max_pow2 / kSortTile, nj), 1024, 0, lead->stream>>>(dj);
     for (int k = 2 * kSortTile; k <= max_pow2; k <<= 1) {
       for (int j = k >> 1; j >= kSortTile; j >>= 1) bitonic_global_kernel<<<dim3((max_pow2 / 2 + 255) / 256, nj), 256, 0, lead->stream>>>(dj, k, j);
       bitonic_tile_merge_kernel<<<dim3(max_pow2 / kSortTile, nj), 1024, 0, lead->stream>>>(dj, k);
     }
-    gather_sorted_kernel<<<dim3((max_spad + 255) / 256, nj), 256, 0, lead->stream>>>(dj);
     if (small_call) kd_refine_kernel<2048><<<dim3((max_spad + 2047) / 2048, nj), 512, 0, lead->stream>>>(dj);
     else kd_refine_kernel<4096><<<dim3((max_spad + 4095) / 4096, nj), 1024, 0, lead->stream>>>(dj);
-    box_tile_kernel<<<dim3((max_spad / 32 + 255) / 256, nj), 256, 0, lead->stream>>>(dj);
-    box_super_kernel<<<dim3((max_spad / 512 + 255) / 256, nj), 256, 0, lead->stream>>>(dj);
     box_block_kernel<<<dim3((max_spad / 32768 + 64) / 64, nj), 64, 0, lead->stream>>>(dj);
   }
   HIP_TRY(lead, hipGetLastError());
-  for (auto& t : todo) t.second->idx_valid = true;
+  for (auto& t : todo) {
+    t.second->idx_valid = true;
+    t.second->idx_chunk = small_call ? 2048 : 4096;
+  }
   return GORIO_OK;
 }
 
@@ -2143,6 +2153,28 @@ int gorio_apd_debug_set_schedule(gorio_apd_t* h, int fuse_step, int plan_search)
   if (!h) return GORIO_ERR_INVALID;
   h->fuse_step = fuse_step != 0;
   h->plan_search = plan_search != 0;
+  return GORIO_OK;
+}
+
+int gorio_apd_debug_get_index(gorio_apd_t* h, int which, int sizes[6], float* sxyz, int* orig, float* tbox, float* sbox, float* bbox) {
+  if (!h || !sizes) return GORIO_ERR_INVALID;
+  DevCloud& c = which == 0 ? *h->src : *h->tgt;
+  if (!c.present || !c.idx_valid) return fail(h, GORIO_ERR_STATE, "debug_get_index: no search index held for this cloud (pruned search, after the covariances or a linearisation)");
+  const SearchIndex& ix = c.idx;
+  const int n_blk = (ix.n_super + 63) / 64;
+  sizes[0] = ix.n; sizes[1] = ix.n_spad; sizes[2] = ix.n_tiles; sizes[3] = ix.n_super; sizes[4] = n_blk; sizes[5] = c.idx_chunk;
+  HIP_TRY(h, hipSetDevice(h->device));
+  HIP_TRY(h, hipStreamSynchronize(h->stream));
+  if (sxyz) {
+    HIP_TRY(h, hipMemcpy(sxyz, ix.sx, sizeof(float) * ix.n_spad, hipMemcpyDeviceToHost));
+    HIP_TRY(h, hipMemcpy(sxyz + ix.n_spad, ix.sy, sizeof(float) * ix.n_spad, hipMemcpyDeviceToHost));
+    HIP_TRY(h, hipMemcpy(sxyz + 2 * (size_t)ix.n_spad, ix.sz, sizeof(float) * ix.n_spad, hipMemcpyDeviceToHost));
+    HIP_TRY(h, hipMemcpy(sxyz + 3 * (size_t)ix.n_spad, ix.s4, sizeof(float4) * ix.n_spad, hipMemcpyDeviceToHost));
+  }
+  if (orig) HIP_TRY(h, hipMemcpy(orig, ix.orig, sizeof(int) * ix.n_spad, hipMemcpyDeviceToHost));
+  if (tbox) HIP_TRY(h, hipMemcpy(tbox, ix.tbox, sizeof(float) * 8 * ix.n_tiles, hipMemcpyDeviceToHost));
+  if (sbox) HIP_TRY(h, hipMemcpy(sbox, ix.sbox, sizeof(float) * 8 * ix.n_super, hipMemcpyDeviceToHost));
+  if (bbox) HIP_TRY(h, hipMemcpy(bbox, ix.bbox, sizeof(float) * 8 * n_blk, hipMemcpyDeviceToHost));
   return GORIO_OK;
 }
 

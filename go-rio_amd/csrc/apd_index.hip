@@ -1,9 +1,11 @@
 // apd_index.hip -- building the exact search accelerator (SearchIndex, apd_device.h) and the two branch-and-bound searches that
 // use it.  Included by apd_api.hip after apd_kernels.hip.
 //
-//   bbox_kernel / morton_kernel      bounding box, 3 x 11-bit Morton code per point
+//   bbox_morton_kernel               bounding box + 3 x 11-bit Morton code per point in one launch (clouds up to kBboxFusedMax points);
+//   bbox_kernel / morton_kernel      the same as three launches for bigger clouds
 //   bitonic_*_kernel                 LDS-tiled bitonic sort of (code << 31 | index) keys
-//   gather_sorted_kernel / box_kernel   Morton-ordered copy + tile / super-tile boxes
+//   kd_refine_kernel                 gathers the points in Morton order, median splits inside every chunk, tile / super-tile boxes
+//   box_block_kernel                 block boxes
 //   nn_search_pruned_kernel          1-NN correspondences (APD:164-180), same packed-key output as nn_search_kernel
 //   knn_pruned_kernel                self k-NN (APD:364), same list layout as knn_partial_kernel with splits = 1
 //
@@ -70,30 +72,88 @@ __device__ __forceinline__ unsigned long long spread11(unsigned int v) {  // 11 
   return x;
 }
 
+// Morton key of point i (padding keys ~0 sort to the tail); lo[] / ext from the cloud's bounding box
+__device__ __forceinline__ unsigned long long morton_key(const IndexJob& jb, int i, const float (&lo)[3], float ext) {
+  if (i >= jb.n) return ~0ull;
+  unsigned int q[3];
+  const float v[3] = {jb.x[i], jb.y[i], jb.z[i]};
+#pragma unroll
+  for (int a = 0; a < 3; ++a) {
+    float t = (v[a] - lo[a]) / ext * 2047.0f;
+    t = fminf(fmaxf(t, 0.0f), 2047.0f);
+    q[a] = (unsigned int)t;
+  }
+  const unsigned long long code = spread11(q[0]) | (spread11(q[1]) << 1) | (spread11(q[2]) << 2);
+  return (code << 31) | (unsigned long long)i;
+}
+
 // grid: (blocks over npow2, jobs)
 __global__ __launch_bounds__(256) void morton_kernel(const IndexJob* __restrict__ jobs) {
   const IndexJob& jb = jobs[blockIdx.y];
   const int i = blockIdx.x * 256 + threadIdx.x;
   if (i >= jb.npow2) return;
-  unsigned long long key = ~0ull;
-  if (i < jb.n) {
-    unsigned int q[3];
-    const float v[3] = {jb.x[i], jb.y[i], jb.z[i]};
-    // ONE cell size for the three axes (cubic cells): tiles of consecutive codes are then compact in metres, not in bbox fractions
-    float ext = 1e-6f;
+  // ONE cell size for the three axes (cubic cells): tiles of consecutive codes are then compact in metres, not in bbox fractions
+  float ext = 1e-6f, lo[3];
 #pragma unroll
-    for (int a = 0; a < 3; ++a) ext = fmaxf(ext, ord2f(jb.bb[3 + a]) - ord2f(jb.bb[a]));
+  for (int a = 0; a < 3; ++a) {
+    lo[a] = ord2f(jb.bb[a]);
+    ext = fmaxf(ext, ord2f(jb.bb[3 + a]) - lo[a]);
+  }
+  jb.keys[i] = morton_key(jb, i, lo, ext);
+}
+
+// bbox_init_kernel + bbox_kernel + morton_kernel as ONE launch for clouds of at most kBboxFusedMax points: one workgroup per cloud reduces
+// the bounding box (waves by shuffles, the 16 waves through LDS: no atomics, nothing to initialise) and then writes the keys of the same
+// points, which it reads a second time from L2.  The three launches cost 72 + 2 x ~10 us per C4 batch, 196 k contended atomics among them.
+// grid: (jobs), block 1024
+constexpr int kBboxFusedMax = 32768;
+__global__ __launch_bounds__(1024) void bbox_morton_kernel(const IndexJob* __restrict__ jobs) {
+  const IndexJob& jb = jobs[blockIdx.x];
+  __shared__ unsigned int s_bb[16][6];
+  const int tid = threadIdx.x;
+  float flo[3] = {INFINITY, INFINITY, INFINITY}, fhi[3] = {-INFINITY, -INFINITY, -INFINITY};
+  for (int i = tid; i < jb.n; i += 1024) {
+    const float v[3] = {jb.x[i], jb.y[i], jb.z[i]};
 #pragma unroll
     for (int a = 0; a < 3; ++a) {
-      const float lo = ord2f(jb.bb[a]);
-      float t = (v[a] - lo) / ext * 2047.0f;
-      t = fminf(fmaxf(t, 0.0f), 2047.0f);
-      q[a] = (unsigned int)t;
+      flo[a] = fminf(flo[a], v[a]);
+      fhi[a] = fmaxf(fhi[a], v[a]);
     }
-    const unsigned long long code = spread11(q[0]) | (spread11(q[1]) << 1) | (spread11(q[2]) << 2);
-    key = (code << 31) | (unsigned long long)i;
   }
-  jb.keys[i] = key;
+#pragma unroll
+  for (int a = 0; a < 3; ++a) {
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) {
+      flo[a] = fminf(flo[a], __shfl_xor(flo[a], off, 64));
+      fhi[a] = fmaxf(fhi[a], __shfl_xor(fhi[a], off, 64));
+    }
+    if ((tid & 63) == 0) {  // across waves on the order-preserving encoding, as the atomics of bbox_kernel
+      s_bb[tid >> 6][a] = f2ord(flo[a]);
+      s_bb[tid >> 6][3 + a] = f2ord(fhi[a]);
+    }
+  }
+  __syncthreads();
+  unsigned int bb[6];
+#pragma unroll
+  for (int a = 0; a < 3; ++a) {
+    bb[a] = 0xffffffffu;
+    bb[3 + a] = 0u;
+    for (int w = 0; w < 16; ++w) {
+      bb[a] = min(bb[a], s_bb[w][a]);
+      bb[3 + a] = max(bb[3 + a], s_bb[w][3 + a]);
+    }
+  }
+  if (tid == 0) {
+#pragma unroll
+    for (int a = 0; a < 6; ++a) jb.bb[a] = bb[a];
+  }
+  float ext = 1e-6f, lo[3];
+#pragma unroll
+  for (int a = 0; a < 3; ++a) {
+    lo[a] = ord2f(bb[a]);
+    ext = fmaxf(ext, ord2f(bb[3 + a]) - lo[a]);
+  }
+  for (int i = tid; i < jb.npow2; i += 1024) jb.keys[i] = morton_key(jb, i, lo, ext);
 }
 
 constexpr int kSortTile = 4096;  // u64 keys per LDS tile (32 KB), 1024 threads
@@ -169,45 +229,40 @@ __global__ __launch_bounds__(1024) void bitonic_tile_merge_kernel(const IndexJob
   for (int q = threadIdx.x; q < kSortTile; q += 1024) jb.keys[base + q] = s[q];
 }
 
-// grid: (blocks over n_spad, jobs)
-__global__ __launch_bounds__(256) void gather_sorted_kernel(const IndexJob* __restrict__ jobs) {
-  const IndexJob& jb = jobs[blockIdx.y];
-  const int p = blockIdx.x * 256 + threadIdx.x;
-  if (p >= jb.idx.n_spad) return;
-  if (p < jb.n) {
-    const int i = (int)(jb.keys[p] & 0x7fffffffull);
-    jb.idx.sx[p] = jb.x[i];
-    jb.idx.sy[p] = jb.y[i];
-    jb.idx.sz[p] = jb.z[i];
-    jb.idx.orig[p] = i;
-    jb.idx.s4[p] = make_float4(jb.x[i], jb.y[i], jb.z[i], __int_as_float(i));
-  } else {
-    jb.idx.sx[p] = 1e30f;
-    jb.idx.sy[p] = 1e30f;
-    jb.idx.sz[p] = 1e30f;
-    jb.idx.orig[p] = 0x7fffffff;
-    jb.idx.s4[p] = make_float4(1e30f, 1e30f, 1e30f, __int_as_float(0x7fffffff));
-  }
-}
-
 // kd refinement of the Morton order: inside every chunk of 4096 sorted points (a compact region of space after the Morton sort)
 // the points are re-ordered by recursive MEDIAN SPLITS along the widest axis down to 32-point leaves, entirely in LDS.  Leaves of
 // a median-split tree tile space without the long, overlapping boxes that runs of a space-filling curve produce: on the C4
 // clouds a query needs 2.2 tiles instead of 6.0 and a wave of 64 queries 11 instead of 17.  Any permutation is a valid index
 // (the searches are exact for every ordering), so this changes the work of the searches, never their results.
-// Per level (segment sizes 4096 .. 64): segment bounding boxes (wave reductions + LDS atomics), widest axis, bitonic sort of
-// every segment by that coordinate, payload permutation.  Padding points (1e30) are the largest on every axis and therefore stay
-// at the tail of the chunk.  grid: (chunks over max n_spad, jobs), block 1024.
+// The kernel is the whole second half of the index build:
+//   * GATHER: the chunk is loaded through the sorted Morton keys straight from the cloud's x / y / z (no Morton-ordered copy is ever
+//     written); positions past n are padding (1e30, original index 0x7fffffff).
+//   * Per level (segment sizes 4096 .. 64): segment bounding boxes (wave reductions + LDS atomics), widest axis, bitonic sort of
+//     every segment by that coordinate, payload permutation.  Padding points are the largest on every axis and therefore stay
+//     at the tail of the chunk.
+//   * A segment whose widest axis is the axis its PARENT was sorted on is not sorted again: its keys (coordinate << 12 | position) are
+//     already strictly ascending -- the parent's sort left the coordinates ascending with equal ones in position order, and the key's
+//     low bits ARE the position -- so the sort would be the identity, bit for bit.  Its pairs sit out the workgroup-wide stages, a wave
+//     whose 256-key window holds only such segments skips its wave-local stages, and a level at which every segment of the chunk is
+//     one costs only the boxes (GORIO_KD_SKIP_SORTED=0 builds the kernel without this, for A/B runs).
+//   * STORE + BOXES: sx / sy / sz / orig / s4 are written once, and the boxes of the chunk's 32-point tiles and 512-point super tiles
+//     are reduced from LDS (a tile and a super tile never straddle a chunk) with the arithmetic of the former box kernels: min / max
+//     over the positions below n, empty = (+inf, -inf).
+// grid: (chunks over max n_spad, jobs), block kKdChunk / 4.
 // Chunk size (a multiple of 1024, at most 4096: the index inside a chunk takes 12 key bits) by the clouds of the call: 2048 points when
 // every cloud named in the call has at most kKdSmallCloud points (scans, and local maps of the C3 size), 4096 otherwise.  Measured in round 3: 16 k-point scans against each other
 // build faster with the smaller chunk (0.71 -> 0.60 ms per C4 batch: 512-thread workgroups, one sort level less) AND search faster (20
 // searches 1.99 -> 1.90 ms, k-NN 1.66 -> 1.59 ms, a lone 5 k x 5 k align 0.95 -> 0.79 ms); scans that meet a big map search it faster
 // when THEY are ordered with 4096-point chunks too (64 scans x 1 M-point map: 20 searches 10.2 vs 10.9 ms), and the map's own tiles are
 // worse with small chunks (11.2 ms with 1024).
+#ifndef GORIO_KD_SKIP_SORTED
+#define GORIO_KD_SKIP_SORTED 1
+#endif
 constexpr int kKdSmallCloud = 131072;  // (65536 until the end of round 3: a 100 k-point local map is better off with 2048-point chunks too -- C3 step 2.72 -> 2.55 ms)
 template <int kKdChunk>
 __global__ __launch_bounds__(kKdChunk / 4) void kd_refine_kernel(const IndexJob* __restrict__ jobs) {
   constexpr int kKdThreads = kKdChunk / 4;  // four points, two compare-exchange pairs per thread and stage
+  constexpr int kTiles = kKdChunk / 32, kSupers = kKdChunk / 512;
   const IndexJob& jb = jobs[blockIdx.y];
   const int base = blockIdx.x * kKdChunk;
   if (base >= jb.idx.n_spad) return;
@@ -215,19 +270,26 @@ __global__ __launch_bounds__(kKdChunk / 4) void kd_refine_kernel(const IndexJob*
   __shared__ int po[kKdChunk];
   __shared__ unsigned long long keys[kKdChunk];
   __shared__ unsigned int sb[64][6];  // per segment: ordered-uint min x,y,z / max x,y,z
+  __shared__ int sax[2][64];          // per segment: its widest axis = the axis it is sorted on after the level (this level's, the parent level's)
+  __shared__ int sskip[64];           // per segment: already sorted on its widest axis
+  __shared__ int s_nsort;             // != 0: some segment of the level needs its sort
+  __shared__ float tb[kTiles][6];     // tile boxes of the chunk, for the super-tile boxes
   const int tid = threadIdx.x, lane = tid & 63;
   for (int e = tid; e < kKdChunk; e += kKdThreads) {
     const int p = base + e;
-    const bool in = p < jb.idx.n_spad;
-    px[e] = in ? jb.idx.sx[p] : 1e30f;
-    py[e] = in ? jb.idx.sy[p] : 1e30f;
-    pz[e] = in ? jb.idx.sz[p] : 1e30f;
-    po[e] = in ? jb.idx.orig[p] : 0x7fffffff;
+    const bool in = p < jb.n;
+    const int i = in ? (int)(jb.keys[p] & 0x7fffffffull) : 0;
+    px[e] = in ? jb.x[i] : 1e30f;
+    py[e] = in ? jb.y[i] : 1e30f;
+    pz[e] = in ? jb.z[i] : 1e30f;
+    po[e] = in ? i : 0x7fffffff;
   }
   __syncthreads();
-  for (int seg = kKdChunk; seg >= 64; seg >>= 1) {
+  int lseg = __builtin_ctz(kKdChunk), cur = 0;
+  for (int seg = kKdChunk; seg >= 64; seg >>= 1, --lseg, cur ^= 1) {
     const int nseg = kKdChunk / seg;
     for (int q = tid; q < nseg * 6; q += kKdThreads) sb[q / 6][q % 6] = (q % 6) < 3 ? 0xffffffffu : 0u;
+    if (tid == 0) s_nsort = 0;
     __syncthreads();
     for (int r = 0; r < 4; ++r) {
       const int e = tid + kKdThreads * r;
@@ -248,9 +310,8 @@ __global__ __launch_bounds__(kKdChunk / 4) void kd_refine_kernel(const IndexJob*
       }
     }
     __syncthreads();
-    for (int r = 0; r < 4; ++r) {
-      const int e = tid + kKdThreads * r;
-      const unsigned int* b = sb[e / seg];
+    if (tid < nseg) {  // widest axis of the segment (the lowest among equals), and whether the parent's sort already ordered it
+      const unsigned int* b = sb[tid];
       int axis = 0;
       float best = -1.0f;
 #pragma unroll
@@ -261,12 +322,25 @@ __global__ __launch_bounds__(kKdChunk / 4) void kd_refine_kernel(const IndexJob*
           axis = a;
         }
       }
+      const bool skip = GORIO_KD_SKIP_SORTED && seg != kKdChunk && sax[cur ^ 1][tid >> 1] == axis;
+      sax[cur][tid] = axis;
+      sskip[tid] = skip ? 1 : 0;
+      if (!skip) s_nsort = 1;
+    }
+    __syncthreads();
+    if (s_nsort == 0) continue;  // every segment is in order already (workgroup-uniform; s_nsort is next written behind the next barrier)
+    for (int r = 0; r < 4; ++r) {
+      const int e = tid + kKdThreads * r;
+      const int axis = sax[cur][e >> lseg];
       const float c = axis == 0 ? px[e] : (axis == 1 ? py[e] : pz[e]);
       keys[e] = ((unsigned long long)f2ord(c) << 12) | (unsigned long long)e;
     }
     __syncthreads();
     // bitonic sort of every segment.  Strides >= 256 need the whole workgroup (barrier per stage); smaller strides stay inside
     // the 256-key window of one wave, where the in-order LDS pipe of the wave is the only synchronisation needed.
+    const int wbase = (tid >> 6) * 256;
+    bool wskip = true;  // every segment that meets this wave's window is in order already
+    for (int q = wbase >> lseg; q <= (wbase + 255) >> lseg; ++q) wskip = wskip && sskip[q] != 0;
     for (int lk = 1; (1 << lk) <= seg; ++lk) {
       const int k = 1 << lk;
       int lj = lk - 1;  // stride j = 1 << lj; pair t -> lo = (t / j) * 2j + t % j, by shifts
@@ -275,6 +349,7 @@ __global__ __launch_bounds__(kKdChunk / 4) void kd_refine_kernel(const IndexJob*
         for (int r = 0; r < 2; ++r) {
           const int t = tid + kKdThreads * r;
           const int lo = ((t >> lj) << (lj + 1)) | (t & (j - 1)), hi = lo + j;
+          if (sskip[lo >> lseg]) continue;
           const bool up = (k == seg) || ((lo & k) == 0);
           unsigned long long a = keys[lo], b = keys[hi];
           if ((a > b) == up) {
@@ -284,22 +359,23 @@ __global__ __launch_bounds__(kKdChunk / 4) void kd_refine_kernel(const IndexJob*
         }
         __syncthreads();
       }
-      const int wbase = (tid >> 6) * 256;
-      for (; lj >= 0; --lj) {
-        const int j = 1 << lj;
-        for (int r = 0; r < 2; ++r) {
-          const int t = lane + 64 * r;
-          const int lo = wbase + (((t >> lj) << (lj + 1)) | (t & (j - 1))), hi = lo + j;
-          const bool up = (k == seg) || ((lo & k) == 0);
-          unsigned long long a = keys[lo], b = keys[hi];
-          if ((a > b) == up) {
-            keys[lo] = b;
-            keys[hi] = a;
+      if (!wskip) {
+        for (; lj >= 0; --lj) {
+          const int j = 1 << lj;
+          for (int r = 0; r < 2; ++r) {
+            const int t = lane + 64 * r;
+            const int lo = wbase + (((t >> lj) << (lj + 1)) | (t & (j - 1))), hi = lo + j;
+            const bool up = (k == seg) || ((lo & k) == 0);
+            unsigned long long a = keys[lo], b = keys[hi];
+            if ((a > b) == up) {
+              keys[lo] = b;
+              keys[hi] = a;
+            }
           }
+          __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+          __builtin_amdgcn_wave_barrier();
+          __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
         }
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
       }
       if (k >= 256 && 2 * k <= seg) __syncthreads();  // the next merge starts with a workgroup-wide stride
     }
@@ -327,48 +403,65 @@ __global__ __launch_bounds__(kKdChunk / 4) void kd_refine_kernel(const IndexJob*
       jb.idx.s4[p] = make_float4(px[e], py[e], pz[e], __int_as_float(po[e]));
     }
   }
-}
-
-// boxes of 32-point tiles (one thread per tile) -- grid: (blocks over n_tiles, jobs); then super tiles in box_super_kernel
-__global__ __launch_bounds__(256) void box_tile_kernel(const IndexJob* __restrict__ jobs) {
-  const IndexJob& jb = jobs[blockIdx.y];
-  const int t = blockIdx.x * 256 + threadIdx.x;
-  if (t >= jb.idx.n_tiles) return;
-  float lo[3] = {INFINITY, INFINITY, INFINITY}, hi[3] = {-INFINITY, -INFINITY, -INFINITY};
-  for (int q = 0; q < 32; ++q) {
-    const int p = t * 32 + q;
-    if (p < jb.n) {
-      const float v[3] = {jb.idx.sx[p], jb.idx.sy[p], jb.idx.sz[p]};
+  // tile boxes: eight lanes per 32-point tile, four points each
+  {
+    const int t = tid >> 3, sub = tid & 7;
+    float lo[3] = {INFINITY, INFINITY, INFINITY}, hi[3] = {-INFINITY, -INFINITY, -INFINITY};
+    for (int r = 0; r < 4; ++r) {
+      const int e = t * 32 + sub + 8 * r;
+      if (base + e < jb.n) {
+        const float v[3] = {px[e], py[e], pz[e]};
+#pragma unroll
+        for (int a = 0; a < 3; ++a) {
+          lo[a] = fminf(lo[a], v[a]);
+          hi[a] = fmaxf(hi[a], v[a]);
+        }
+      }
+    }
+#pragma unroll
+    for (int a = 0; a < 3; ++a) {
+#pragma unroll
+      for (int off = 4; off > 0; off >>= 1) {
+        lo[a] = fminf(lo[a], __shfl_xor(lo[a], off, 64));
+        hi[a] = fmaxf(hi[a], __shfl_xor(hi[a], off, 64));
+      }
+    }
+    if (sub == 0) {
 #pragma unroll
       for (int a = 0; a < 3; ++a) {
-        lo[a] = fminf(lo[a], v[a]);
-        hi[a] = fmaxf(hi[a], v[a]);
+        tb[t][a] = lo[a];
+        tb[t][3 + a] = hi[a];
+      }
+      const int gt = base / 32 + t;
+      if (gt < jb.idx.n_tiles) {
+        float4* b = reinterpret_cast<float4*>(jb.idx.tbox + (size_t)gt * 8);
+        b[0] = make_float4(lo[0], lo[1], lo[2], 0.f);
+        b[1] = make_float4(hi[0], hi[1], hi[2], 0.f);
       }
     }
   }
-  float* b = jb.idx.tbox + (size_t)t * 8;
-  b[0] = lo[0]; b[1] = lo[1]; b[2] = lo[2]; b[3] = 0.f;
-  b[4] = hi[0]; b[5] = hi[1]; b[6] = hi[2]; b[7] = 0.f;
-}
-__global__ __launch_bounds__(256) void box_super_kernel(const IndexJob* __restrict__ jobs) {
-  const IndexJob& jb = jobs[blockIdx.y];
-  const int s = blockIdx.x * 256 + threadIdx.x;
-  if (s >= jb.idx.n_super) return;
-  float lo[3] = {INFINITY, INFINITY, INFINITY}, hi[3] = {-INFINITY, -INFINITY, -INFINITY};
-  for (int q = 0; q < 16; ++q) {
-    const int t = s * 16 + q;
-    if (t < jb.idx.n_tiles) {
-      const float* b = jb.idx.tbox + (size_t)t * 8;
+  __syncthreads();
+  // super-tile boxes: sixteen lanes per super tile, one tile box each
+  if (tid < kSupers * 16) {
+    const int sp = tid >> 4, q = tid & 15;
+    float lo[3], hi[3];
 #pragma unroll
-      for (int a = 0; a < 3; ++a) {
-        lo[a] = fminf(lo[a], b[a]);
-        hi[a] = fmaxf(hi[a], b[4 + a]);
+    for (int a = 0; a < 3; ++a) {
+      lo[a] = tb[sp * 16 + q][a];
+      hi[a] = tb[sp * 16 + q][3 + a];
+#pragma unroll
+      for (int off = 8; off > 0; off >>= 1) {
+        lo[a] = fminf(lo[a], __shfl_xor(lo[a], off, 64));
+        hi[a] = fmaxf(hi[a], __shfl_xor(hi[a], off, 64));
       }
     }
+    const int gs = base / 512 + sp;
+    if (q == 0 && gs < jb.idx.n_super) {
+      float4* b = reinterpret_cast<float4*>(jb.idx.sbox + (size_t)gs * 8);
+      b[0] = make_float4(lo[0], lo[1], lo[2], 0.f);
+      b[1] = make_float4(hi[0], hi[1], hi[2], 0.f);
+    }
   }
-  float* b = jb.idx.sbox + (size_t)s * 8;
-  b[0] = lo[0]; b[1] = lo[1]; b[2] = lo[2]; b[3] = 0.f;
-  b[4] = hi[0]; b[5] = hi[1]; b[6] = hi[2]; b[7] = 0.f;
 }
 
 // boxes of blocks (64 super tiles), one thread per block -- grid: (blocks over n_blk, jobs)

@@ -279,6 +279,13 @@ int gorio_apd_debug_set_shard(gorio_apd_t* h, int world_size, int rank);
  *   plan_search != 0: from the third correspondence search of an align on, query waves that were slow in the second one are cut into
  *                     parts and dispatched heaviest first; 0: every search uses the natural schedule. */
 int gorio_apd_debug_set_schedule(gorio_apd_t* h, int fuse_step, int plan_search);
+/* Test hook: read back the search index of the source (which = 0) or the target (1) as the pruned searches see it.  sizes receives
+ * { n, n_spad, n_tiles, n_super, n_blocks, kd chunk size }; every other pointer may be NULL (call once for the sizes, then again):
+ *   sxyz [7 * n_spad]   sx, sy, sz (n_spad floats each), then s4 as n_spad x (x, y, z, original index bits)
+ *   orig [n_spad]       original index per sorted position, 0x7fffffff for padding
+ *   tbox [n_tiles * 8], sbox [n_super * 8], bbox [n_blocks * 8]   lo.x lo.y lo.z 0 hi.x hi.y hi.z 0
+ * GORIO_ERR_STATE when the handle holds no valid index for that cloud. */
+int gorio_apd_debug_get_index(gorio_apd_t* h, int which, int sizes[6], float* sxyz, int* orig, float* tbox, float* sbox, float* bbox);
 
 /* seconds spent inside device kernels of the last align / align_batch, by stage (HIP events on the launch stream):
  * [0] k-NN + covariance estimation, [1] correspondence search, [2] linearize, [3] LM/GN solve + error trials, [4] search-index build
