@@ -20,12 +20,20 @@
 #include <vector>
 
 #include "../../include/gorio_apd.h"
+#include "dev_buffer.h"
+
+// THE check of a HIP call in every host module of this translation unit: on an error, return through the module's fail function
+// (`fail_fn` is anything callable as fail_fn(code, message)) with "<expression>: <hipGetErrorString>".
+#define GORIO_HIP_CHECK(fail_fn, expr)                                                                             \
+  do {                                                                                                           \
+    hipError_t e_ = (expr);                                                                                      \
+    if (e_ != hipSuccess) return fail_fn(GORIO_ERR_NO_DEVICE, std::string(#expr) + ": " + hipGetErrorString(e_)); \
+  } while (0)
+
 #include "apd_kernels.hip"
 #include "apd_index.hip"
 #include "apd_submap.hip"
 #include "apd_voxel.hip"
-#include "apd_prep.hip"
-#include "../../include/gorio_prep.h"
 #include "apd_ground.hip"
 #include "../../include/gorio_sc.h"
 #include "apd_sc.hip"
@@ -38,16 +46,17 @@ constexpr int kPad = 16;
 constexpr float kFar = 1e30f;
 
 struct DevCloud {
-  float *x = nullptr, *y = nullptr, *z = nullptr, *label = nullptr;
-  float4* p4 = nullptr;
-  double *cov6 = nullptr, *geo_w = nullptr;
-  int* knn = nullptr;      // [n][k] neighbour indices of the last covariance computation (parity hook, params.keep_knn_indices)
-  int* redo = nullptr;     // per query wave: redo flags of knn_collect_kernel
-  float* kth = nullptr;    // per sorted position: k-th distance (knn_kth_kernel)
-  int redo_cap = 0;
-  float* part_d = nullptr; // k-NN partial lists
-  int* part_i = nullptr;
-  size_t part_cap = 0;     // elements
+  int device = 0;          // first member: ~DevCloud selects it before the buffers below free themselves
+  DevBuf<float> x, y, z, label;  // the point group: these, p4, cov6 and geo_w share `cap`
+  DevBuf<float4> p4;
+  DevBuf<double> cov6, geo_w;
+  DevBuf<int> knn;         // [cap][knn_k] neighbour indices of the last covariance computation (parity hook, params.keep_knn_indices)
+  DevBuf<int> redo;        // per query wave: redo flags of knn_collect_kernel
+  DevBuf<float> kth;       // per sorted position: k-th distance (knn_kth_kernel)
+  int redo_cap = 0;        // query waves redo / kth hold
+  DevBuf<float> part_d;    // k-NN partial lists
+  DevBuf<int> part_i;
+  size_t part_cap = 0;     // elements of part_d / part_i
   int knn_k = 0;
   bool knn_valid = false;  // knn holds the lists of the current covariances
   int n = 0, n_pad = 0, cap = 0;
@@ -55,36 +64,40 @@ struct DevCloud {
   int cov_count = 0;       // == source_covs_.size(): n when valid, 0 when stale
   int cov_k = -1, cov_reg = -1;  // k_correspondences / regularization the covariances were ESTIMATED with; -1: supplied by set_*_covariances
   // exact search accelerator (GORIO_SEARCH_PRUNED)
-  SearchIndex idx = SearchIndex{nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 0, 0, 0, 0};
-  unsigned long long* keys = nullptr;
-  unsigned int* bb = nullptr;
-  int idx_cap = 0, keys_cap = 0;
+  DevBuf<float> idx_sx, idx_sy, idx_sz, idx_tbox, idx_sbox, idx_bbox;  // the arrays behind index_view(): one group of capacity idx_cap
+  DevBuf<int> idx_orig;
+  DevBuf<float4> idx_s4;
+  int idx_cap = 0;
+  int idx_n = 0, idx_spad = 0;  // sizes of the index held (SearchIndex::n / n_spad)
+  DevBuf<unsigned long long> keys;
+  DevBuf<unsigned int> bb;
   bool idx_valid = false;
   int idx_chunk = 0;       // kd chunk size the index was built with (gorio_apd_debug_get_index)
   // Gaussian voxel map of this cloud as a FastVGICP target (voxelmap_, fast_vgicp.hpp:85): lives with the cloud, so the handles that share a
   // target share its map.  Valid for (vm_res, vm_mult) until the points or the covariances change.
-  unsigned long long* vm_keys = nullptr;  // [vm_keys_cap] sort scratch: linear voxel id << 31 | point index
-  int vm_keys_cap = 0;
-  int* vm_counts = nullptr;               // [vm_counts_cap] voxel starts per 256 keys, scanned
-  int vm_counts_cap = 0;
-  int* vm_bb = nullptr;                   // [8] bounding box of the occupied coordinates + range flag
-  IndexJob* vm_job = nullptr;             // descriptor the bitonic sort kernels read
-  unsigned long long* vm_vkey = nullptr;  // the map itself (VoxelMapView), [vm_cap] voxels
-  double* vm_mean = nullptr;
-  double* vm_cov6 = nullptr;
-  int* vm_num = nullptr;
+  DevBuf<unsigned long long> vm_keys;  // sort scratch: linear voxel id << 31 | point index
+  DevBuf<int> vm_counts;               // voxel starts per 256 keys, scanned
+  DevBuf<int> vm_bb;                   // [8] bounding box of the occupied coordinates + range flag
+  DevBuf<IndexJob> vm_job;             // descriptor the bitonic sort kernels read
+  DevBuf<unsigned long long> vm_vkey;  // the map itself (VoxelMapView): these four hold vm_cap voxels
+  DevBuf<double> vm_mean;
+  DevBuf<double> vm_cov6;
+  DevBuf<int> vm_num;
   int vm_cap = 0, vm_nv = 0;
   int vm_min[3] = {0, 0, 0}, vm_dim[3] = {0, 0, 0};
   double vm_res = 0.0;
   bool vm_mult = false;                   // MultiplicativeGaussianVoxel (ADDITIVE and ADDITIVE_WEIGHTED build the same voxels, VOX:138-141)
   bool vm_valid = false;
   VoxelMapView voxel_view() const { return VoxelMapView{vm_vkey, vm_mean, vm_cov6, vm_num, vm_nv, {vm_min[0], vm_min[1], vm_min[2]}, {vm_dim[0], vm_dim[1], vm_dim[2]}, vm_res}; }
-  int device = 0;
-  CloudView view() const { return CloudView{x, y, z, label, p4, cov6, geo_w, n, n_pad, idx}; }
+  // the kernel-visible view of the search index (the buffers above own the memory)
+  SearchIndex index_view() const { return SearchIndex{idx_sx, idx_sy, idx_sz, idx_orig, idx_s4, idx_tbox, idx_sbox, idx_bbox, idx_n, idx_spad, idx_spad / 32, idx_spad / 512}; }
+  CloudView view() const { return CloudView{x, y, z, label, p4, cov6, geo_w, n, n_pad, index_view()}; }
   DevCloud() = default;
   DevCloud(const DevCloud&) = delete;
   DevCloud& operator=(const DevCloud&) = delete;
-  ~DevCloud();  // frees the device buffers: a cloud may be shared by several handles (gorio_apd_set_target_shared) and lives until the last one lets go
+  // A cloud may be shared by several handles (gorio_apd_set_target_shared) and lives until the last one lets go.  The buffers free
+  // themselves as members, AFTER this body: the device has to be current by then.
+  ~DevCloud() { hipSetDevice(device); }
 };
 
 }  // namespace
@@ -94,17 +107,15 @@ struct gorio_apd {
   hipStream_t stream = nullptr;
   gorio_apd_params params;
   std::shared_ptr<DevCloud> src, tgt;  // never null; tgt may be shared with other handles of the device
-  // per-source-point state
-  unsigned long long* best_key = nullptr;
-  int* seed = nullptr;     // warm start of the pruned search, by sorted source position (PairDesc::seed)
-  unsigned int* nn_work = nullptr;  // PairDesc::nn_work / nn_plan (measured work of the query waves, plan of the next searches)
-  unsigned int* nn_plan = nullptr;
+  // per-source-point state: one group of capacity pt_cap (ensure_points)
+  DevBuf<unsigned long long> best_key;
+  DevBuf<int> seed;        // warm start of the pruned search, by sorted source position (PairDesc::seed)
+  DevBuf<unsigned int> nn_work, nn_plan;  // PairDesc::nn_work / nn_plan (measured work of the query waves, plan of the next searches)
   int nn_wcap = 0;
   int align_budget = 0;    // loop iterations the previous batch led by this handle needed (0 = none yet): enqueued before the first look at the done flags
-  int* corr = nullptr;
-  float* sqd = nullptr;
-  double* omega6 = nullptr;
-  double* partials = nullptr;
+  DevBuf<int> corr;
+  DevBuf<float> sqd;
+  DevBuf<double> omega6, partials;
   int pt_cap = 0;
   bool corr_valid = false;
   // registration method (gorio_apd_set_method): which fast_gicp class this handle stands for, and the FastVGICP members
@@ -114,53 +125,44 @@ struct gorio_apd {
   int voxel_search = GORIO_VOXEL_DIRECT1;
   int voxel_mode = GORIO_VOXEL_ADDITIVE;
   // FastVGICP pair state: slot table, weighted Mahalanobis blocks, block partials (VoxPair); corr_valid / omega_valid describe them in that mode
-  int* v_slots = nullptr;
-  double* v_omega6 = nullptr;
-  double* v_partials = nullptr;
+  DevBuf<int> v_slots;       // these three: one group of capacity v_cap
+  DevBuf<double> v_omega6, v_partials;
   size_t v_cap = 0;          // slots
   int v_n_off = 0;           // offsets per source point of the slot table held
-  VoxPair* d_vox = nullptr;  // batch array (owned by the handle that leads a batch)
-  int vox_cap = 0;
+  DevBuf<VoxPair> d_vox;     // batch array (owned by the handle that leads a batch)
   bool omega_valid = false;  // omega6 holds the Mahalanobis matrices of the last linearisation (not after a Gauss-Newton align)
-  PairState* d_state = nullptr;
-  PairDesc* d_desc = nullptr;   // batch descriptor array (owned by the handle that leads a batch)
+  DevBuf<PairState> d_state;
+  DevBuf<PairDesc> d_desc;   // batch descriptor array and states (owned by the handle that leads a batch): one group of capacity desc_cap
+  DevBuf<PairState> d_states_batch;
   int desc_cap = 0;
-  PairState* d_states_batch = nullptr;
-  KnnJob* d_jobs = nullptr;
-  size_t fit_cap = 0;           // doubles in d_fit
-  void* d_copy_jobs = nullptr;  // gorio_apd_set_clouds_device_batch
-  size_t copy_jobs_cap = 0;
-  int jobs_cap = 0;
-  IndexJob* d_ijobs = nullptr;
-  int ijobs_cap = 0;
-  double* d_fit = nullptr;
+  DevBuf<KnnJob> d_jobs;
+  DevBuf<void> d_copy_jobs;  // gorio_apd_set_clouds_device_batch
+  DevBuf<IndexJob> d_ijobs;
+  DevBuf<double> d_fit;      // block partials of a fitness score
   // scan-to-submap assembly scratch (gorio_apd_set_target_submap)
-  float4* d_sub_in = nullptr;
-  float4* d_sub_out = nullptr;
-  float4* d_sub_vox = nullptr;
+  DevBuf<float4> d_sub_in, d_sub_out, d_sub_vox;  // one group of capacity sub_cap
   size_t sub_cap = 0;
-  unsigned long long* d_sub_keys = nullptr;
-  size_t sub_keys_cap = 0;
-  int* d_sub_counts = nullptr;
-  size_t sub_counts_cap = 0;
-  SubmapFrame* d_sub_frames = nullptr;
-  int sub_frames_cap = 0;
-  unsigned int* d_sub_bb = nullptr;
-  IndexJob* d_sub_job = nullptr;
+  DevBuf<unsigned long long> d_sub_keys;
+  DevBuf<int> d_sub_counts;
+  DevBuf<SubmapFrame> d_sub_frames;
+  DevBuf<unsigned int> d_sub_bb;
+  DevBuf<IndexJob> d_sub_job;
   // sharded-source mode (gorio_apd_comm_init): RCCL communicator over the ranks that share one source cloud
   ncclComm_t comm = nullptr;
   int comm_world = 1, comm_rank = 0;
   bool shard_only = false;  // gorio_apd_debug_set_shard: the source partition of a rank without the collectives (test hook)
   bool fuse_step = true, plan_search = true;  // gorio_apd_debug_set_schedule
-  double* d_red = nullptr;  // [32] all-reduce buffer: 28 sums of a linearisation, [28] trial error, [29] scratch
+  DevBuf<double> d_red;     // [32] all-reduce buffer: 28 sums of a linearisation, [28] trial error, [29] scratch
   long long allreduce_count = 0;  // ncclAllReduce calls enqueued through this handle's communicator (gorio_apd_comm_info)
   // pinned host staging of the small descriptor arrays a call uploads (index jobs, k-NN jobs, pair descriptors / states, copy jobs): a
   // copy from pageable memory needs a stream drain before the vector it came from may die; a pinned buffer of the handle's own needs none
   struct Pinned {
-    void* p = nullptr;
-    size_t cap = 0;
+    PinnedBuf buf;
     hipEvent_t ev = nullptr;  // recorded behind the last upload from this buffer: the next writer waits for it
     bool pending = false;
+    ~Pinned() {
+      if (ev) hipEventDestroy(ev);
+    }
   };
   Pinned pin_ijobs, pin_jobs, pin_desc, pin_states, pin_copy, pin_vox;
   std::string err;
@@ -171,6 +173,10 @@ struct gorio_apd {
   struct EvPair { hipEvent_t start, stop; int stage; int prev; };  // prev >= 0: the span starts at ev_pool[prev].stop (StageChain)
   std::vector<EvPair> ev_pool;
   size_t ev_used = 0;
+  // gorio_apd_destroy makes the device current and drains the stream first; the buffers then free themselves as members
+  ~gorio_apd() {
+    for (auto& e : ev_pool) { hipEventDestroy(e.start); hipEventDestroy(e.stop); }
+  }
 };
 
 namespace {
@@ -193,11 +199,11 @@ int fail(gorio_apd* h, int code, const std::string& msg) {
   return code;
 }
 
-#define HIP_TRY(h, expr)                                                                                        \
-  do {                                                                                                          \
-    hipError_t e_ = (expr);                                                                                     \
-    if (e_ != hipSuccess) return fail(h, GORIO_ERR_NO_DEVICE, std::string(#expr) + ": " + hipGetErrorString(e_)); \
-  } while (0)
+struct HandleFail {  // fail() bound to a handle, for GORIO_HIP_CHECK
+  gorio_apd* h;
+  int operator()(int code, const std::string& msg) const { return fail(h, code, msg); }
+};
+#define HIP_TRY(h, expr) GORIO_HIP_CHECK(HandleFail{h}, expr)
 
 int roundup(int v, int m) { return (v + m - 1) / m * m; }
 
@@ -208,16 +214,10 @@ int upload_staged(gorio_apd* h, gorio_apd::Pinned& b, void* dst, const void* src
     HIP_TRY(h, hipEventSynchronize(b.ev));
     b.pending = false;
   }
-  if (bytes > b.cap) {
-    if (b.p) hipHostFree(b.p);
-    b.p = nullptr;
-    b.cap = 0;
-    HIP_TRY(h, hipHostMalloc(&b.p, bytes + bytes / 2 + 256, hipHostMallocDefault));
-    b.cap = bytes + bytes / 2 + 256;
-  }
+  HIP_TRY(h, b.buf.reserve(bytes, bytes + bytes / 2 + 256));
   if (!b.ev) HIP_TRY(h, hipEventCreateWithFlags(&b.ev, hipEventDisableTiming));
-  std::memcpy(b.p, src, bytes);
-  HIP_TRY(h, hipMemcpyAsync(dst, b.p, bytes, hipMemcpyHostToDevice, h->stream));
+  std::memcpy(b.buf, src, bytes);
+  HIP_TRY(h, hipMemcpyAsync(dst, b.buf, bytes, hipMemcpyHostToDevice, h->stream));
   HIP_TRY(h, hipEventRecord(b.ev, h->stream));
   b.pending = true;
   return GORIO_OK;
@@ -263,15 +263,6 @@ Rccl& rccl() {
     if (e_ != ncclSuccess) return fail(h, GORIO_ERR_NO_DEVICE, std::string(#expr) + ": " + rccl().GetErrorString(e_)); \
   } while (0)
 
-}  // namespace
-DevCloud::~DevCloud() {
-  DevCloud& c = *this;
-  hipSetDevice(c.device);
-  hipFree(c.idx.sx); hipFree(c.idx.sy); hipFree(c.idx.sz); hipFree(c.idx.orig); hipFree(c.idx.s4); hipFree(c.idx.tbox); hipFree(c.idx.sbox); hipFree(c.idx.bbox); hipFree(c.keys); hipFree(c.bb);
-  hipFree(c.x); hipFree(c.y); hipFree(c.z); hipFree(c.label); hipFree(c.p4); hipFree(c.cov6); hipFree(c.geo_w); hipFree(c.knn); hipFree(c.part_d); hipFree(c.part_i); hipFree(c.redo); hipFree(c.kth);
-  hipFree(c.vm_keys); hipFree(c.vm_counts); hipFree(c.vm_bb); hipFree(c.vm_job); hipFree(c.vm_vkey); hipFree(c.vm_mean); hipFree(c.vm_cov6); hipFree(c.vm_num);
-}
-namespace {
 
 // a cloud about to be overwritten must not be one other handles still look at (gorio_apd_set_target_shared): detach first
 void make_private(gorio_apd* h, std::shared_ptr<DevCloud>& c) {
@@ -284,17 +275,10 @@ void make_private(gorio_apd* h, std::shared_ptr<DevCloud>& c) {
 int ensure_cloud(gorio_apd* h, DevCloud& c, int n) {
   const int n_pad = roundup(n, kPad) + kPad;
   if (n_pad > c.cap) {
-    hipFree(c.x); hipFree(c.y); hipFree(c.z); hipFree(c.label); hipFree(c.p4); hipFree(c.cov6); hipFree(c.geo_w); hipFree(c.knn);
-    c.x = c.y = c.z = c.label = nullptr; c.p4 = nullptr; c.cov6 = c.geo_w = nullptr; c.knn = nullptr; c.knn_k = 0;
-    const int cap = n_pad + n_pad / 8;
-    HIP_TRY(h, hipMalloc(&c.x, sizeof(float) * cap));
-    HIP_TRY(h, hipMalloc(&c.y, sizeof(float) * cap));
-    HIP_TRY(h, hipMalloc(&c.z, sizeof(float) * cap));
-    HIP_TRY(h, hipMalloc(&c.label, sizeof(float) * cap));
-    HIP_TRY(h, hipMalloc(&c.p4, sizeof(float4) * cap));
-    HIP_TRY(h, hipMalloc(&c.cov6, sizeof(double) * 6 * cap));
-    HIP_TRY(h, hipMalloc(&c.geo_w, sizeof(double) * cap));
-    c.cap = cap;
+    c.knn.reset();  // sized by cap * k: reallocated by the next covariance computation that keeps the lists
+    c.knn_k = 0;
+    const size_t cap = n_pad + n_pad / 8;
+    HIP_TRY(h, reserve_group(c.cap, n_pad, cap, c.x, cap, c.y, cap, c.z, cap, c.label, cap, c.p4, cap, c.cov6, 6 * cap, c.geo_w, cap));
   }
   c.n = n;
   c.n_pad = n_pad;
@@ -303,21 +287,13 @@ int ensure_cloud(gorio_apd* h, DevCloud& c, int n) {
 
 int ensure_points(gorio_apd* h, int n) {
   if (n > h->pt_cap) {
-    hipFree(h->best_key); hipFree(h->seed); hipFree(h->nn_work); hipFree(h->nn_plan); hipFree(h->corr); hipFree(h->sqd); hipFree(h->omega6); hipFree(h->partials);
-    h->best_key = nullptr; h->seed = nullptr; h->nn_work = nullptr; h->nn_plan = nullptr; h->corr = nullptr; h->sqd = nullptr; h->omega6 = nullptr; h->partials = nullptr;
-    const int cap = n + n / 8 + 256;
-    HIP_TRY(h, hipMalloc(&h->best_key, sizeof(unsigned long long) * cap));
-    HIP_TRY(h, hipMalloc(&h->seed, sizeof(int) * (cap + 512)));  // indexed by sorted position < roundup(n, 512)
-    h->nn_wcap = (cap + 512) / 64 + 1;
-    HIP_TRY(h, hipMalloc(&h->nn_work, sizeof(unsigned int) * 2 * h->nn_wcap));
-    HIP_TRY(h, hipMalloc(&h->nn_plan, sizeof(unsigned int) * (1 + 16 * (size_t)h->nn_wcap)));
-    HIP_TRY(h, hipMemsetAsync(h->nn_work, 0, sizeof(unsigned int) * 2 * h->nn_wcap, h->stream));
-    HIP_TRY(h, hipMemsetAsync(h->nn_plan, 0, sizeof(unsigned int) * (1 + 16 * (size_t)h->nn_wcap), h->stream));
-    HIP_TRY(h, hipMalloc(&h->corr, sizeof(int) * cap));
-    HIP_TRY(h, hipMalloc(&h->sqd, sizeof(float) * cap));
-    HIP_TRY(h, hipMalloc(&h->omega6, sizeof(double) * 6 * cap));
-    HIP_TRY(h, hipMalloc(&h->partials, sizeof(double) * 28 * (cap / 256 + 2)));
-    h->pt_cap = cap;
+    const size_t cap = n + n / 8 + 256;
+    const size_t wcap = (cap + 512) / 64 + 1;
+    HIP_TRY(h, reserve_group(h->pt_cap, n, cap, h->best_key, cap, h->seed, cap + 512 /* indexed by sorted position < roundup(n, 512) */, h->nn_work, 2 * wcap,
+                             h->nn_plan, 1 + 16 * wcap, h->corr, cap, h->sqd, cap, h->omega6, 6 * cap, h->partials, 28 * (cap / 256 + 2)));
+    h->nn_wcap = (int)wcap;
+    HIP_TRY(h, hipMemsetAsync(h->nn_work, 0, sizeof(unsigned int) * 2 * wcap, h->stream));
+    HIP_TRY(h, hipMemsetAsync(h->nn_plan, 0, sizeof(unsigned int) * (1 + 16 * wcap), h->stream));
   }
   return GORIO_OK;
 }
@@ -511,43 +487,20 @@ int run_index_build(gorio_apd* lead, std::vector<std::pair<gorio_apd*, DevCloud*
     const int n_spad = roundup(c.n, 512);
     int npow2 = kSortTile;
     while (npow2 < c.n) npow2 <<= 1;
-    if (n_spad > c.idx_cap) {
-      hipFree(c.idx.sx); hipFree(c.idx.sy); hipFree(c.idx.sz); hipFree(c.idx.orig); hipFree(c.idx.s4); hipFree(c.idx.tbox); hipFree(c.idx.sbox); hipFree(c.idx.bbox);
-      c.idx.sx = c.idx.sy = c.idx.sz = nullptr; c.idx.orig = nullptr; c.idx.s4 = nullptr; c.idx.tbox = c.idx.sbox = c.idx.bbox = nullptr;
-      const int cap = n_spad + roundup(n_spad / 8, 512);
-      HIP_TRY(h, hipMalloc(&c.idx.sx, sizeof(float) * cap));
-      HIP_TRY(h, hipMalloc(&c.idx.sy, sizeof(float) * cap));
-      HIP_TRY(h, hipMalloc(&c.idx.sz, sizeof(float) * cap));
-      HIP_TRY(h, hipMalloc(&c.idx.orig, sizeof(int) * cap));
-      HIP_TRY(h, hipMalloc(&c.idx.s4, sizeof(float4) * cap));
-      HIP_TRY(h, hipMalloc(&c.idx.tbox, sizeof(float) * 8 * (cap / 32)));
-      HIP_TRY(h, hipMalloc(&c.idx.sbox, sizeof(float) * 8 * (cap / 512)));
-      HIP_TRY(h, hipMalloc(&c.idx.bbox, sizeof(float) * 8 * (cap / 32768 + 1)));
-      c.idx_cap = cap;
-    }
-    if (npow2 > c.keys_cap) {
-      hipFree(c.keys);
-      c.keys = nullptr;
-      HIP_TRY(h, hipMalloc(&c.keys, sizeof(unsigned long long) * npow2));
-      c.keys_cap = npow2;
-    }
-    if (!c.bb) HIP_TRY(h, hipMalloc(&c.bb, sizeof(unsigned int) * 6));
-    c.idx.n = c.n;
-    c.idx.n_spad = n_spad;
-    c.idx.n_tiles = n_spad / 32;
-    c.idx.n_super = n_spad / 512;
+    const size_t cap = n_spad + roundup(n_spad / 8, 512);
+    HIP_TRY(h, reserve_group(c.idx_cap, n_spad, cap, c.idx_sx, cap, c.idx_sy, cap, c.idx_sz, cap, c.idx_orig, cap, c.idx_s4, cap, c.idx_tbox, 8 * (cap / 32),
+                             c.idx_sbox, 8 * (cap / 512), c.idx_bbox, 8 * (cap / 32768 + 1)));
+    HIP_TRY(h, c.keys.reserve(npow2));
+    HIP_TRY(h, c.bb.reserve(6));
+    c.idx_n = c.n;
+    c.idx_spad = n_spad;
     IndexJob& j = jobs[q];
-    j.x = c.x; j.y = c.y; j.z = c.z; j.n = c.n; j.npow2 = npow2; j.keys = c.keys; j.bb = c.bb; j.idx = c.idx;
+    j.x = c.x; j.y = c.y; j.z = c.z; j.n = c.n; j.npow2 = npow2; j.keys = c.keys; j.bb = c.bb; j.idx = c.index_view();
     max_pow2 = std::max(max_pow2, npow2);
     max_spad = std::max(max_spad, n_spad);
     max_n = std::max(max_n, c.n);
   }
-  if (nj > lead->ijobs_cap) {
-    hipFree(lead->d_ijobs);
-    lead->d_ijobs = nullptr;
-    HIP_TRY(lead, hipMalloc(&lead->d_ijobs, sizeof(IndexJob) * nj));
-    lead->ijobs_cap = nj;
-  }
+  HIP_TRY(lead, lead->d_ijobs.reserve(nj));
   if (int rc = upload_staged(lead, lead->pin_ijobs, lead->d_ijobs, jobs.data(), sizeof(IndexJob) * nj)) return rc;
   {
     StageTimer t(lead, 4);
@@ -608,38 +561,25 @@ int run_covariances(gorio_apd* lead, std::vector<std::pair<gorio_apd*, DevCloud*
     const int s = pruned ? 1 : (c.n_pad + chunk - 1) / chunk;
     if (s > max_splits) max_splits = s;
     const size_t need = pruned ? 0 : (size_t)s * K * c.n;
-    if (need > c.part_cap) {
-      hipFree(c.part_d); hipFree(c.part_i);
-      c.part_d = nullptr; c.part_i = nullptr;
-      HIP_TRY(h, hipMalloc(&c.part_d, sizeof(float) * need));
-      HIP_TRY(h, hipMalloc(&c.part_i, sizeof(int) * need));
-      c.part_cap = need;
-    }
+    HIP_TRY(h, reserve_group(c.part_cap, need, need, c.part_d, need, c.part_i, need));
     const bool keep = h->params.keep_knn_indices != 0;
     if (keep && (c.knn_k != k || !c.knn)) {
-      hipFree(c.knn);
-      c.knn = nullptr;
-      HIP_TRY(h, hipMalloc(&c.knn, sizeof(int) * (size_t)c.cap * k));
+      c.knn_k = 0;
+      HIP_TRY(h, c.knn.realloc((size_t)c.cap * k));
       c.knn_k = k;
     }
     c.knn_valid = keep;
     if (select) {
-      const int nw = roundup(c.n, 512) / 64;
-      if (nw > c.redo_cap) {
-        hipFree(c.redo); hipFree(c.kth);
-        c.redo = nullptr; c.kth = nullptr;
-        HIP_TRY(h, hipMalloc(&c.redo, sizeof(int) * (nw + nw / 8)));
-        HIP_TRY(h, hipMalloc(&c.kth, sizeof(float) * 64 * (nw + nw / 8)));
-        c.redo_cap = nw + nw / 8;
-      }
+      const size_t nw = roundup(c.n, 512) / 64, cap = nw + nw / 8;
+      HIP_TRY(h, reserve_group(c.redo_cap, nw, cap, c.redo, cap, c.kth, 64 * cap));
     }
     KnnJob& j = jobs[q];
     j.cloud = c.view();
     j.part_d = c.part_d;
     j.part_i = c.part_i;
-    j.knn_out = keep ? c.knn : nullptr;
-    j.redo = select ? c.redo : nullptr;
-    j.kth = select ? c.kth : nullptr;
+    j.knn_out = keep ? c.knn.get() : nullptr;
+    j.redo = select ? c.redo.get() : nullptr;
+    j.kth = select ? c.kth.get() : nullptr;
     j.k = k;
     j.regularization = h->params.regularization;
     j.splits = s;
@@ -659,12 +599,7 @@ int run_covariances(gorio_apd* lead, std::vector<std::pair<gorio_apd*, DevCloud*
     }
     for (int q = 0; q < njobs; ++q) jobs[q].qpw = qpw;
   }
-  if (njobs > lead->jobs_cap) {
-    hipFree(lead->d_jobs);
-    lead->d_jobs = nullptr;
-    HIP_TRY(lead, hipMalloc(&lead->d_jobs, sizeof(KnnJob) * njobs));
-    lead->jobs_cap = njobs;
-  }
+  HIP_TRY(lead, lead->d_jobs.reserve(njobs));
   if (int rc = upload_staged(lead, lead->pin_jobs, lead->d_jobs, jobs.data(), sizeof(KnnJob) * njobs)) return rc;
   {
     StageTimer t(lead, 0);
@@ -773,8 +708,8 @@ int build_voxelmap(gorio_apd* h, DevCloud& t, double res, int mode) {
   if (t.vm_valid && t.vm_res == res && t.vm_mult == mult) return GORIO_OK;
   t.vm_valid = false;
   const int n = t.n;
-  if (!t.vm_bb) HIP_TRY(h, hipMalloc(&t.vm_bb, sizeof(int) * 8));
-  if (!t.vm_job) HIP_TRY(h, hipMalloc(&t.vm_job, sizeof(IndexJob)));
+  HIP_TRY(h, t.vm_bb.reserve(8));
+  HIP_TRY(h, t.vm_job.reserve(1));
   vg_bbox_init_kernel<<<1, 64, 0, h->stream>>>(t.vm_bb);
   vg_coord_bbox_kernel<<<std::min(256, (n + 255) / 256), 256, 0, h->stream>>>(t.p4, n, res, t.vm_bb);
   int bb[8];
@@ -794,20 +729,8 @@ int build_voxelmap(gorio_apd* h, DevCloud& t, double res, int mode) {
   int npow2 = kSortTile;
   while (npow2 < n) npow2 <<= 1;
   const int nblocks = (n + 255) / 256;
-  if (npow2 > t.vm_keys_cap) {
-    hipFree(t.vm_keys);
-    t.vm_keys = nullptr;
-    t.vm_keys_cap = 0;
-    HIP_TRY(h, hipMalloc(&t.vm_keys, sizeof(unsigned long long) * (size_t)npow2));
-    t.vm_keys_cap = npow2;
-  }
-  if (nblocks + 1 > t.vm_counts_cap) {
-    hipFree(t.vm_counts);
-    t.vm_counts = nullptr;
-    t.vm_counts_cap = 0;
-    HIP_TRY(h, hipMalloc(&t.vm_counts, sizeof(int) * (size_t)(nblocks + 1)));
-    t.vm_counts_cap = nblocks + 1;
-  }
+  HIP_TRY(h, t.vm_keys.reserve(npow2));
+  HIP_TRY(h, t.vm_counts.reserve(nblocks + 1));
   vg_key_kernel<<<(npow2 + 255) / 256, 256, 0, h->stream>>>(t.p4, n, npow2, g, t.vm_keys);
   IndexJob job;
   std::memset(&job, 0, sizeof(job));
@@ -827,16 +750,9 @@ int build_voxelmap(gorio_apd* h, DevCloud& t, double res, int mode) {
   HIP_TRY(h, hipMemcpyAsync(&nv, t.vm_counts + nblocks, sizeof(int), hipMemcpyDeviceToHost, h->stream));
   HIP_TRY(h, hipStreamSynchronize(h->stream));
   if (nv <= 0 || nv > n) return fail(h, GORIO_ERR_NO_DEVICE, "voxel map: inconsistent voxel count");
-  if (nv > t.vm_cap) {
-    hipFree(t.vm_vkey); hipFree(t.vm_mean); hipFree(t.vm_cov6); hipFree(t.vm_num);
-    t.vm_vkey = nullptr; t.vm_mean = nullptr; t.vm_cov6 = nullptr; t.vm_num = nullptr;
-    t.vm_cap = 0;
-    const int cap = nv + nv / 8 + 64;
-    HIP_TRY(h, hipMalloc(&t.vm_vkey, sizeof(unsigned long long) * (size_t)cap));
-    HIP_TRY(h, hipMalloc(&t.vm_mean, sizeof(double) * 3 * (size_t)cap));
-    HIP_TRY(h, hipMalloc(&t.vm_cov6, sizeof(double) * 6 * (size_t)cap));
-    HIP_TRY(h, hipMalloc(&t.vm_num, sizeof(int) * (size_t)cap));
-    t.vm_cap = cap;
+  {
+    const size_t cap = nv + nv / 8 + 64;
+    HIP_TRY(h, reserve_group(t.vm_cap, nv, cap, t.vm_vkey, cap, t.vm_mean, 3 * cap, t.vm_cov6, 6 * cap, t.vm_num, cap));
   }
   vg_accum_kernel<<<nblocks, 256, 0, h->stream>>>(t.vm_keys, t.p4, t.cov6, n, t.vm_counts, mult ? 2 : 0, t.vm_vkey, t.vm_mean, t.vm_cov6, t.vm_num);
   HIP_TRY(h, hipGetLastError());
@@ -855,16 +771,8 @@ int build_voxelmap(gorio_apd* h, DevCloud& t, double res, int mode) {
 int ensure_voxel_pair(gorio_apd* h) {
   const int n_off = voxel_offsets(h->voxel_search);
   const size_t total = (size_t)h->src->n * n_off;
-  if (total > h->v_cap) {
-    hipFree(h->v_slots); hipFree(h->v_omega6); hipFree(h->v_partials);
-    h->v_slots = nullptr; h->v_omega6 = nullptr; h->v_partials = nullptr;
-    h->v_cap = 0;
-    const size_t cap = total + total / 8 + 256;
-    HIP_TRY(h, hipMalloc(&h->v_slots, sizeof(int) * cap));
-    HIP_TRY(h, hipMalloc(&h->v_omega6, sizeof(double) * 6 * cap));
-    HIP_TRY(h, hipMalloc(&h->v_partials, sizeof(double) * 28 * (cap / 256 + 2)));
-    h->v_cap = cap;
-  }
+  const size_t cap = total + total / 8 + 256;
+  HIP_TRY(h, reserve_group(h->v_cap, total, cap, h->v_slots, cap, h->v_omega6, 6 * cap, h->v_partials, 28 * (cap / 256 + 2)));
   h->v_n_off = n_off;
   return GORIO_OK;
 }
@@ -880,13 +788,7 @@ VoxPair make_vox_pair(const gorio_apd* h, int write_omega) {
 }
 
 int ensure_vox_batch(gorio_apd* lead, int count) {
-  if (count > lead->vox_cap) {
-    hipFree(lead->d_vox);
-    lead->d_vox = nullptr;
-    lead->vox_cap = 0;
-    HIP_TRY(lead, hipMalloc(&lead->d_vox, sizeof(VoxPair) * count));
-    lead->vox_cap = count;
-  }
+  HIP_TRY(lead, lead->d_vox.reserve(count));
   return GORIO_OK;
 }
 
@@ -995,13 +897,7 @@ __global__ __launch_bounds__(64) void scatter_states_kernel(const PairDesc* __re
 }
 
 int ensure_batch(gorio_apd* lead, int count) {
-  if (count > lead->desc_cap) {
-    hipFree(lead->d_desc); hipFree(lead->d_states_batch);
-    lead->d_desc = nullptr; lead->d_states_batch = nullptr;
-    HIP_TRY(lead, hipMalloc(&lead->d_desc, sizeof(PairDesc) * count));
-    HIP_TRY(lead, hipMalloc(&lead->d_states_batch, sizeof(PairState) * count));
-    lead->desc_cap = count;
-  }
+  HIP_TRY(lead, reserve_group(lead->desc_cap, count, count, lead->d_desc, count, lead->d_states_batch, count));
   return GORIO_OK;
 }
 
@@ -1297,8 +1193,7 @@ int gorio_apd_create(gorio_apd_t** out, int device) {
     hipDeviceProp_t prop;
     h->fuse_step = hipGetDeviceProperties(&prop, device) == hipSuccess && std::strncmp(prop.gcnArchName, "gfx950", 6) == 0;
   }
-  if (!h->stream || hipMalloc(&h->d_state, sizeof(PairState)) != hipSuccess ||
-      hipMalloc(&h->d_fit, sizeof(double) * 4) != hipSuccess || hipMalloc(&h->d_red, sizeof(double) * 32) != hipSuccess) {
+  if (!h->stream || h->d_state.reserve(1) != hipSuccess || h->d_red.reserve(32) != hipSuccess) {  // d_fit grows with its first fitness score
     delete h;
     return GORIO_ERR_NO_DEVICE;
   }
@@ -1311,19 +1206,7 @@ void gorio_apd_destroy(gorio_apd_t* h) {
   hipSetDevice(h->device);
   if (h->stream) hipStreamSynchronize(h->stream);
   if (h->comm && rccl().ok) rccl().CommDestroy(h->comm);
-  hipFree(h->d_red);
-  hipFree(h->d_sub_in); hipFree(h->d_sub_out); hipFree(h->d_sub_vox); hipFree(h->d_sub_keys); hipFree(h->d_sub_counts); hipFree(h->d_sub_frames); hipFree(h->d_sub_bb); hipFree(h->d_sub_job);
-  h->src.reset();
-  h->tgt.reset();
-  hipFree(h->best_key); hipFree(h->seed); hipFree(h->nn_work); hipFree(h->nn_plan); hipFree(h->corr); hipFree(h->sqd); hipFree(h->omega6); hipFree(h->partials);
-  hipFree(h->v_slots); hipFree(h->v_omega6); hipFree(h->v_partials); hipFree(h->d_vox);
-  hipFree(h->d_state); hipFree(h->d_desc); hipFree(h->d_states_batch); hipFree(h->d_jobs); hipFree(h->d_ijobs); hipFree(h->d_fit); hipFree(h->d_copy_jobs);
-  for (auto& e : h->ev_pool) { hipEventDestroy(e.start); hipEventDestroy(e.stop); }
-  for (gorio_apd::Pinned* b : {&h->pin_ijobs, &h->pin_jobs, &h->pin_desc, &h->pin_states, &h->pin_copy, &h->pin_vox}) {
-    if (b->p) hipHostFree(b->p);
-    if (b->ev) hipEventDestroy(b->ev);
-  }
-  delete h;
+  delete h;  // events, clouds and buffers: ~gorio_apd and its members
 }
 
 const char* gorio_apd_last_error(const gorio_apd_t* h) { return h ? h->err.c_str() : "null handle"; }
@@ -1501,15 +1384,9 @@ int gorio_apd_set_clouds_device_batch(gorio_apd_t** handles, int count, const go
     }
   }
   const size_t bytes = sizeof(CopyJob) * jobs.size();
-  if (bytes > lead->copy_jobs_cap) {
-    hipFree(lead->d_copy_jobs);
-    lead->d_copy_jobs = nullptr;
-    lead->copy_jobs_cap = 0;
-    HIP_TRY(lead, hipMalloc(&lead->d_copy_jobs, bytes));
-    lead->copy_jobs_cap = bytes;
-  }
+  HIP_TRY(lead, lead->d_copy_jobs.reserve(bytes));
   if (int rc = upload_staged(lead, lead->pin_copy, lead->d_copy_jobs, jobs.data(), bytes)) return rc;
-  copy_clouds_kernel<<<dim3(std::min(16, (max_pad + 255) / 256), (unsigned)jobs.size()), 256, 0, lead->stream>>>(static_cast<const CopyJob*>(lead->d_copy_jobs));
+  copy_clouds_kernel<<<dim3(std::min(16, (max_pad + 255) / 256), (unsigned)jobs.size()), 256, 0, lead->stream>>>(static_cast<const CopyJob*>(lead->d_copy_jobs.get()));
   HIP_TRY(lead, hipGetLastError());
   return GORIO_OK;
 }
@@ -1568,24 +1445,13 @@ int gorio_apd_set_target_submap(gorio_apd_t* h, const gorio_apd_keyframe* frames
   }
   const int m = (int)stage.size();
   if (m <= 0) return fail(h, GORIO_ERR_INVALID, "set_target_submap: no finite point in any keyframe");
-  if ((size_t)m > h->sub_cap) {
-    hipFree(h->d_sub_in); hipFree(h->d_sub_out); hipFree(h->d_sub_vox);
-    h->d_sub_in = h->d_sub_out = h->d_sub_vox = nullptr;
-    h->sub_cap = 0;
+  {
     const size_t cap = (size_t)m + (size_t)m / 8;
-    HIP_TRY(h, hipMalloc(&h->d_sub_in, sizeof(float4) * cap));
-    HIP_TRY(h, hipMalloc(&h->d_sub_out, sizeof(float4) * cap));
-    HIP_TRY(h, hipMalloc(&h->d_sub_vox, sizeof(float4) * cap));
-    h->sub_cap = cap;
+    HIP_TRY(h, reserve_group(h->sub_cap, m, cap, h->d_sub_in, cap, h->d_sub_out, cap, h->d_sub_vox, cap));
   }
-  if (count > h->sub_frames_cap) {
-    hipFree(h->d_sub_frames);
-    h->d_sub_frames = nullptr;
-    HIP_TRY(h, hipMalloc(&h->d_sub_frames, sizeof(SubmapFrame) * count));
-    h->sub_frames_cap = count;
-  }
-  if (!h->d_sub_bb) HIP_TRY(h, hipMalloc(&h->d_sub_bb, sizeof(unsigned int) * 8));
-  if (!h->d_sub_job) HIP_TRY(h, hipMalloc(&h->d_sub_job, sizeof(IndexJob)));
+  HIP_TRY(h, h->d_sub_frames.reserve(count));
+  HIP_TRY(h, h->d_sub_bb.reserve(8));
+  HIP_TRY(h, h->d_sub_job.reserve(1));
   HIP_TRY(h, hipMemcpyAsync(h->d_sub_in, stage.data(), sizeof(float4) * m, hipMemcpyHostToDevice, h->stream));
   HIP_TRY(h, hipMemcpyAsync(h->d_sub_frames, fr.data(), sizeof(SubmapFrame) * count, hipMemcpyHostToDevice, h->stream));
   submap_transform_kernel<<<dim3((max_frame + 255) / 256, count), 256, 0, h->stream>>>(h->d_sub_in, h->d_sub_frames, h->d_sub_out);
@@ -1619,21 +1485,9 @@ int gorio_apd_set_target_submap(gorio_apd_t* h, const gorio_apd_keyframe* frames
       g.div01 = div_b[0] * div_b[1];
       int npow2 = kSortTile;
       while (npow2 < m) npow2 <<= 1;
-      if ((size_t)npow2 > h->sub_keys_cap) {
-        hipFree(h->d_sub_keys);
-        h->d_sub_keys = nullptr;
-        h->sub_keys_cap = 0;
-        HIP_TRY(h, hipMalloc(&h->d_sub_keys, sizeof(unsigned long long) * npow2));
-        h->sub_keys_cap = npow2;
-      }
+      HIP_TRY(h, h->d_sub_keys.reserve(npow2));
       const int nblocks = (m + 255) / 256;
-      if ((size_t)nblocks + 1 > h->sub_counts_cap) {
-        hipFree(h->d_sub_counts);
-        h->d_sub_counts = nullptr;
-        h->sub_counts_cap = 0;
-        HIP_TRY(h, hipMalloc(&h->d_sub_counts, sizeof(int) * (nblocks + 1 + nblocks / 8)));
-        h->sub_counts_cap = nblocks + 1 + nblocks / 8;
-      }
+      HIP_TRY(h, h->d_sub_counts.reserve(nblocks + 1, nblocks + 1 + nblocks / 8));
       IndexJob job;
       std::memset(&job, 0, sizeof(job));
       job.n = m;
@@ -1860,7 +1714,7 @@ int gorio_apd_compute_error(gorio_apd_t* h, const double T[16], double* error) {
   if (rc) return rc;
   double xi[16];
   for (int i = 0; i < 16; ++i) xi[i] = T[i];
-  HIP_TRY(h, hipMemcpyAsync(reinterpret_cast<char*>(h->d_state) + offsetof(PairState, xi), xi, sizeof(xi), hipMemcpyHostToDevice, h->stream));
+  HIP_TRY(h, hipMemcpyAsync(reinterpret_cast<char*>(h->d_state.get()) + offsetof(PairState, xi), xi, sizeof(xi), hipMemcpyHostToDevice, h->stream));
   const ApdConsts cst = make_consts(h->params);
   double yi = 0.0;
   if (h->comm) {
@@ -1873,7 +1727,7 @@ int gorio_apd_compute_error(gorio_apd_t* h, const double T[16], double* error) {
   }
   launch_lm_solve(h->method, dim3(1), h->stream, h->d_desc, h->d_vox, cst, 2);
   HIP_TRY(h, hipGetLastError());
-  HIP_TRY(h, hipMemcpyAsync(&yi, reinterpret_cast<char*>(h->d_state) + offsetof(PairState, yi), sizeof(double), hipMemcpyDeviceToHost, h->stream));
+  HIP_TRY(h, hipMemcpyAsync(&yi, reinterpret_cast<char*>(h->d_state.get()) + offsetof(PairState, yi), sizeof(double), hipMemcpyDeviceToHost, h->stream));
   HIP_TRY(h, hipStreamSynchronize(h->stream));
   *error = yi;
   return GORIO_OK;
@@ -1916,15 +1770,14 @@ int gorio_apd_transform_source(gorio_apd_t* h, const float T[16], float* xyz_out
   if (!h->src->present || n != h->src->n) return fail(h, GORIO_ERR_STATE, "transform_source: no matching source cloud");
   if (stride < 12 || stride % 4) return fail(h, GORIO_ERR_INVALID, "transform_source: bad stride");
   HIP_TRY(h, hipSetDevice(h->device));
-  float* d_out = nullptr;
-  HIP_TRY(h, hipMalloc(&d_out, sizeof(float) * 3 * (size_t)n));
+  DevBuf<float> d_out;  // freed on every way out
+  HIP_TRY(h, d_out.reserve(3 * (size_t)n));
   TfArg tf;
   for (int i = 0; i < 12; ++i) tf.m[i] = T[i];
   transform_cloud_kernel<<<(n + 255) / 256, 256, 0, h->stream>>>(h->src->x, h->src->y, h->src->z, n, tf, d_out);
   std::vector<float> tmp((size_t)n * 3);
   hipError_t e = hipMemcpyAsync(tmp.data(), d_out, sizeof(float) * 3 * (size_t)n, hipMemcpyDeviceToHost, h->stream);
   if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
-  hipFree(d_out);
   if (e != hipSuccess) return fail(h, GORIO_ERR_NO_DEVICE, hipGetErrorString(e));
   const int st = stride / 4;
   for (int i = 0; i < n; ++i) {
@@ -1956,13 +1809,7 @@ int gorio_apd_fitness_score(gorio_apd_t* h, const float T[16], double max_range,
   init_state(s, Td);
   for (int i = 0; i < 12; ++i) s.Tf[i] = T[i];
   const int nbx = (h->src->n + 255) / 256;
-  if ((size_t)nbx * 3 > h->fit_cap) {
-    hipFree(h->d_fit);
-    h->d_fit = nullptr;
-    h->fit_cap = 0;
-    HIP_TRY(h, hipMalloc(&h->d_fit, sizeof(double) * 3 * nbx));
-    h->fit_cap = (size_t)nbx * 3;
-  }
+  HIP_TRY(h, h->d_fit.reserve((size_t)nbx * 3));
   HIP_TRY(h, hipMemcpyAsync(h->d_state, &s, sizeof(s), hipMemcpyHostToDevice, h->stream));
   HIP_TRY(h, hipMemsetAsync(h->best_key, 0xff, sizeof(unsigned long long) * h->src->n, h->stream));
   PairDesc d;
@@ -2058,13 +1905,7 @@ int gorio_apd_fitness_score_batch(gorio_apd_t** handles, int count, const float*
     }
   }
   const size_t n_part = (size_t)count * max_nbx * 3;
-  if (n_part > lead->fit_cap) {
-    hipFree(lead->d_fit);
-    lead->d_fit = nullptr;
-    lead->fit_cap = 0;
-    HIP_TRY(lead, hipMalloc(&lead->d_fit, sizeof(double) * n_part));
-    lead->fit_cap = n_part;
-  }
+  HIP_TRY(lead, lead->d_fit.reserve(n_part));
   if (int rc = upload_staged(lead, lead->pin_desc, lead->d_desc, descs.data(), sizeof(PairDesc) * count)) return rc;
   if (int rc = upload_staged(lead, lead->pin_states, lead->d_states_batch, states.data(), sizeof(PairState) * count)) return rc;
   scatter_states_kernel<<<count, 64, 0, lead->stream>>>(lead->d_desc, lead->d_states_batch);
@@ -2160,7 +2001,7 @@ int gorio_apd_debug_get_index(gorio_apd_t* h, int which, int sizes[6], float* sx
   if (!h || !sizes) return GORIO_ERR_INVALID;
   DevCloud& c = which == 0 ? *h->src : *h->tgt;
   if (!c.present || !c.idx_valid) return fail(h, GORIO_ERR_STATE, "debug_get_index: no search index held for this cloud (pruned search, after the covariances or a linearisation)");
-  const SearchIndex& ix = c.idx;
+  const SearchIndex ix = c.index_view();
   const int n_blk = (ix.n_super + 63) / 64;
   sizes[0] = ix.n; sizes[1] = ix.n_spad; sizes[2] = ix.n_tiles; sizes[3] = ix.n_super; sizes[4] = n_blk; sizes[5] = c.idx_chunk;
   HIP_TRY(h, hipSetDevice(h->device));
@@ -2211,592 +2052,6 @@ int gorio_apd_get_stage_times(gorio_apd_t* h, double seconds[8], int counts[8]) 
 
 }  // extern "C"
 
-// =============================================================================================== preprocessing (include/gorio_prep.h)
-
-namespace {
-thread_local std::string g_prep_err;
-int prep_fail(int code, const std::string& m) {
-  g_prep_err = m;
-  return code;
-}
-struct PrepCtx {  // per thread: a private registration handle serves as the device-side cloud + search-index holder
-  gorio_apd* h = nullptr;
-  int device = -1;
-  int* d_cnt = nullptr;
-  long long* d_offs = nullptr;
-  int* d_adj = nullptr;
-  size_t pts_cap = 0, adj_cap = 0;
-  ~PrepCtx() {
-    if (h) {
-      hipSetDevice(device);
-      hipFree(d_cnt); hipFree(d_offs); hipFree(d_adj);
-      gorio_apd_destroy(h);
-    }
-  }
-};
-thread_local PrepCtx g_prep;
-}  // namespace
-
-extern "C" {
-
-const char* gorio_prep_last_error(void) { return g_prep_err.c_str(); }
-
-int gorio_prep_dbscan_labels(int device, const float* xyz, int n, int point_stride_bytes, double eps, int core_min_pts, int min_cluster_size, int max_cluster_size,
-                             float* label_out, int label_stride_bytes, int* n_clusters) {
-  if (!xyz || !label_out || n <= 0 || point_stride_bytes < 12 || (point_stride_bytes % 4) || label_stride_bytes < 4 || (label_stride_bytes % 4))
-    return prep_fail(GORIO_ERR_INVALID, "dbscan_labels: bad arguments");
-  PrepCtx& c = g_prep;
-  if (!c.h || c.device != device) {
-    if (c.h) {
-      hipSetDevice(c.device);
-      hipFree(c.d_cnt); hipFree(c.d_offs); hipFree(c.d_adj);
-      gorio_apd_destroy(c.h);
-      c = PrepCtx();
-    }
-    const int rc = gorio_apd_create(&c.h, device);
-    if (rc) return prep_fail(rc, "dbscan_labels: no usable HIP device (there is no CPU fallback)");
-    c.device = device;
-  }
-  gorio_apd* h = c.h;
-  h->params.search = GORIO_SEARCH_PRUNED;
-  int rc = gorio_apd_set_source(h, xyz, nullptr, n, point_stride_bytes);
-  if (rc) return prep_fail(rc, h->err);
-#define PREP_HIP(expr)                                                                                   \
-  do {                                                                                                   \
-    hipError_t e_ = (expr);                                                                              \
-    if (e_ != hipSuccess) return prep_fail(GORIO_ERR_NO_DEVICE, std::string(#expr) + ": " + hipGetErrorString(e_)); \
-  } while (0)
-  {
-    std::vector<std::pair<gorio_apd*, DevCloud*>> one = {{h, h->src.get()}};
-    rc = run_index_build(h, one);
-    if (rc) return prep_fail(rc, h->err);
-  }
-  if ((size_t)n > c.pts_cap) {
-    hipFree(c.d_cnt); hipFree(c.d_offs);
-    c.d_cnt = nullptr; c.d_offs = nullptr;
-    c.pts_cap = 0;
-    PREP_HIP(hipMalloc(&c.d_cnt, sizeof(int) * ((size_t)n + n / 8)));
-    PREP_HIP(hipMalloc(&c.d_offs, sizeof(long long) * ((size_t)n + n / 8)));
-    c.pts_cap = (size_t)n + n / 8;
-  }
-  const CloudView cv = h->src->view();
-  const int grid = (roundup(n, 512) + 255) / 256;
-  RadiusArgs ra{eps, c.d_cnt, c.d_offs, nullptr};
-  radius_neighbours_kernel<0><<<grid, 256, 0, h->stream>>>(cv, ra);
-  PREP_HIP(hipGetLastError());
-  std::vector<int> cnt((size_t)n);
-  PREP_HIP(hipMemcpyAsync(cnt.data(), c.d_cnt, sizeof(int) * (size_t)n, hipMemcpyDeviceToHost, h->stream));
-  PREP_HIP(hipStreamSynchronize(h->stream));
-  std::vector<long long> offs((size_t)n + 1);
-  offs[0] = 0;
-  for (int i = 0; i < n; ++i) offs[i + 1] = offs[i] + cnt[i];
-  const long long E = offs[n];
-  if ((size_t)E > c.adj_cap) {
-    hipFree(c.d_adj);
-    c.d_adj = nullptr;
-    c.adj_cap = 0;
-    PREP_HIP(hipMalloc(&c.d_adj, sizeof(int) * ((size_t)E + (size_t)E / 8 + 16)));
-    c.adj_cap = (size_t)E + (size_t)E / 8 + 16;
-  }
-  PREP_HIP(hipMemcpyAsync(c.d_offs, offs.data(), sizeof(long long) * (size_t)n, hipMemcpyHostToDevice, h->stream));
-  ra.adj = c.d_adj;
-  radius_neighbours_kernel<1><<<grid, 256, 0, h->stream>>>(cv, ra);
-  PREP_HIP(hipGetLastError());
-  std::vector<int> adj((size_t)E);
-  if (E > 0) PREP_HIP(hipMemcpyAsync(adj.data(), c.d_adj, sizeof(int) * (size_t)E, hipMemcpyDeviceToHost, h->stream));
-  PREP_HIP(hipStreamSynchronize(h->stream));
-#undef PREP_HIP
-
-  // ---- the queue of DBSCAN_simple.h:28-100, statement for statement, over the adjacency (the radius searches are done)
-  enum : unsigned char { UN = 0, PROCESSING = 1, PROCESSED = 2 };
-  std::vector<unsigned char> types((size_t)n, UN), noise((size_t)n, 0);
-  std::vector<int> queue;
-  std::vector<std::vector<int>> clusters;
-  auto seed_count = [&](int i) { return cnt[i]; };  // |N(i, seed radius)|, the point itself included
-  auto exp_count = [&](int i) {
-    int k = 0;
-    for (long long e = offs[i]; e < offs[i + 1]; ++e) k += (adj[(size_t)e] < 0);
-    return k;
-  };
-  for (int i = 0; i < n; ++i) {
-    if (types[i] == PROCESSED) continue;
-    if (seed_count(i) < core_min_pts) {
-      noise[i] = 1;
-      continue;
-    }
-    queue.clear();
-    queue.push_back(i);
-    types[i] = PROCESSED;
-    for (long long e = offs[i]; e < offs[i + 1]; ++e) {
-      const int j = adj[(size_t)e] & 0x7fffffff;
-      if (j != i) {
-        queue.push_back(j);  // DBS:50-54: whatever its state
-        types[j] = PROCESSING;
-      }
-    }
-    size_t sq = 1;
-    while (sq < queue.size()) {
-      const int q = queue[sq];
-      if (noise[q] || types[q] == PROCESSED) {
-        types[q] = PROCESSED;
-        sq++;
-        continue;
-      }
-      if (exp_count(q) >= core_min_pts) {
-        for (long long e = offs[q]; e < offs[q + 1]; ++e) {
-          if (adj[(size_t)e] >= 0) continue;  // outside the expansion radius
-          const int j = adj[(size_t)e] & 0x7fffffff;
-          if (types[j] == UN) {
-            queue.push_back(j);
-            types[j] = PROCESSING;
-          }
-        }
-      }
-      types[q] = PROCESSED;
-      sq++;
-    }
-    if ((int)queue.size() >= min_cluster_size && (int)queue.size() <= max_cluster_size) clusters.push_back(queue);  // DBS:83-95
-  }
-  // ---- preprocessing_nodelet_ntu.cpp:533-568: rank the clusters by the distance of their centroid, write rank + 1
-  const int st = point_stride_bytes / 4, lst = label_stride_bytes / 4;
-  for (int i = 0; i < n; ++i) label_out[(size_t)i * lst] = 0.0f;
-  const int nc = (int)clusters.size();
-  std::vector<float> dist((size_t)nc);
-  std::vector<int> order((size_t)nc);
-  for (int cidx = 0; cidx < nc; ++cidx) {
-    std::vector<int>& m = clusters[cidx];
-    std::sort(m.begin(), m.end());  // DBS:91
-    float sx = 0.f, sy = 0.f, sz = 0.f;
-    for (int idx : m) {
-      const float* p = xyz + (size_t)idx * st;
-      sx += p[0]; sy += p[1]; sz += p[2];
-    }
-    const int num = (int)m.size();
-    const float cx = sx / num, cy = sy / num, cz = sz / num;
-    dist[cidx] = (float)std::sqrt((double)cx * cx + (double)cy * cy + (double)cz * cz);  // std::hypot(float, float, float)
-    order[cidx] = cidx;
-  }
-  std::stable_sort(order.begin(), order.end(), [&](int a, int b) { return dist[a] < dist[b]; });
-  for (int r = 0; r < nc; ++r)
-    for (int idx : clusters[order[r]]) label_out[(size_t)idx * lst] = (float)(r + 1);
-  if (n_clusters) *n_clusters = nc;
-  return GORIO_OK;
-}
-
-int gorio_prep_radius_outlier_mask(int device, const float* xyz, int n, int point_stride_bytes, double radius, int min_neighbors, unsigned char* keep, int* n_kept) {
-  if (!xyz || !keep || n <= 0 || point_stride_bytes < 12 || (point_stride_bytes % 4) || !(radius > 0.0) || min_neighbors < 0)
-    return prep_fail(GORIO_ERR_INVALID, "radius_outlier_mask: bad arguments");
-  PrepCtx& c = g_prep;
-  if (!c.h || c.device != device) {
-    if (c.h) {
-      hipSetDevice(c.device);
-      hipFree(c.d_cnt); hipFree(c.d_offs); hipFree(c.d_adj);
-      gorio_apd_destroy(c.h);
-      c = PrepCtx();
-    }
-    const int rc = gorio_apd_create(&c.h, device);
-    if (rc) return prep_fail(rc, "radius_outlier_mask: no usable HIP device (there is no CPU fallback)");
-    c.device = device;
-  }
-  gorio_apd* h = c.h;
-  h->params.search = GORIO_SEARCH_PRUNED;
-  int rc = gorio_apd_set_source(h, xyz, nullptr, n, point_stride_bytes);
-  if (rc) return prep_fail(rc, h->err);
-  {
-    std::vector<std::pair<gorio_apd*, DevCloud*>> one = {{h, h->src.get()}};
-    rc = run_index_build(h, one);
-    if (rc) return prep_fail(rc, h->err);
-  }
-  auto hip_fail = [&](const char* what, hipError_t e) { return prep_fail(GORIO_ERR_NO_DEVICE, std::string(what) + ": " + hipGetErrorString(e)); };
-  if ((size_t)n > c.pts_cap) {
-    hipFree(c.d_cnt); hipFree(c.d_offs);
-    c.d_cnt = nullptr; c.d_offs = nullptr;
-    c.pts_cap = 0;
-    hipError_t e = hipMalloc(&c.d_cnt, sizeof(int) * ((size_t)n + n / 8));
-    if (e == hipSuccess) e = hipMalloc(&c.d_offs, sizeof(long long) * ((size_t)n + n / 8));
-    if (e != hipSuccess) return hip_fail("hipMalloc", e);
-    c.pts_cap = (size_t)n + n / 8;
-  }
-  const double r2d = radius * radius;
-  float r2 = FLT_MAX;
-  if (r2d < (double)FLT_MAX) {  // largest float whose double value is <= r^2: (double)d <= r^2  <=>  d <= r2 for every float d
-    r2 = (float)r2d;
-    while ((double)r2 > r2d) r2 = std::nextafterf(r2, 0.0f);
-  }
-  radius_count_kernel<<<(roundup(n, 512) + 255) / 256, 256, 0, h->stream>>>(h->src->view(), r2, c.d_cnt);
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return hip_fail("radius_count_kernel", e);
-  std::vector<int> cnt((size_t)n);
-  e = hipMemcpyAsync(cnt.data(), c.d_cnt, sizeof(int) * (size_t)n, hipMemcpyDeviceToHost, h->stream);
-  if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
-  if (e != hipSuccess) return hip_fail("download", e);
-  int kept = 0;
-  for (int i = 0; i < n; ++i) {
-    keep[i] = cnt[i] > min_neighbors ? 1 : 0;  // the query itself is one of the counted points
-    kept += keep[i];
-  }
-  if (n_kept) *n_kept = kept;
-  return GORIO_OK;
-}
-
-int gorio_prep_statistical_outlier_mask(int device, const float* xyz, int n, int point_stride_bytes, int mean_k, double stddev_mul, unsigned char* keep, int* n_kept,
-                                        float* mean_dist_out) {
-  if (!xyz || !keep || n <= 0 || point_stride_bytes < 12 || (point_stride_bytes % 4) || mean_k < 1 || mean_k > 31)
-    return prep_fail(GORIO_ERR_INVALID, "statistical_outlier_mask: bad arguments (mean_k must lie in [1, 31])");
-  if (n < mean_k + 1) return prep_fail(GORIO_ERR_INVALID, "statistical_outlier_mask: fewer points than mean_k + 1 (PCL then sums distances nearestKSearch never set)");
-  PrepCtx& c = g_prep;
-  if (!c.h || c.device != device) {
-    if (c.h) {
-      hipSetDevice(c.device);
-      hipFree(c.d_cnt); hipFree(c.d_offs); hipFree(c.d_adj);
-      gorio_apd_destroy(c.h);
-      c = PrepCtx();
-    }
-    const int rc = gorio_apd_create(&c.h, device);
-    if (rc) return prep_fail(rc, "statistical_outlier_mask: no usable HIP device (there is no CPU fallback)");
-    c.device = device;
-  }
-  gorio_apd* h = c.h;
-  h->params.search = GORIO_SEARCH_PRUNED;
-  int rc = gorio_apd_set_source(h, xyz, nullptr, n, point_stride_bytes);
-  if (rc) return prep_fail(rc, h->err);
-  {
-    std::vector<std::pair<gorio_apd*, DevCloud*>> one = {{h, h->src.get()}};
-    rc = run_index_build(h, one);
-    if (rc) return prep_fail(rc, h->err);
-  }
-  auto hip_fail = [&](const char* what, hipError_t e) { return prep_fail(GORIO_ERR_NO_DEVICE, std::string(what) + ": " + hipGetErrorString(e)); };
-  if ((size_t)n > c.pts_cap) {
-    hipFree(c.d_cnt); hipFree(c.d_offs);
-    c.d_cnt = nullptr; c.d_offs = nullptr;
-    c.pts_cap = 0;
-    hipError_t e = hipMalloc(&c.d_cnt, sizeof(int) * ((size_t)n + n / 8));
-    if (e == hipSuccess) e = hipMalloc(&c.d_offs, sizeof(long long) * ((size_t)n + n / 8));
-    if (e != hipSuccess) return hip_fail("hipMalloc", e);
-    c.pts_cap = (size_t)n + n / 8;
-  }
-  float* d_mean = reinterpret_cast<float*>(c.d_cnt);  // one 4-byte word per point, like the neighbour counts
-  sor_mean_distance_kernel<<<(roundup(n, 512) + 255) / 256, 256, 0, h->stream>>>(h->src->view(), mean_k + 1, d_mean);
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return hip_fail("sor_mean_distance_kernel", e);
-  std::vector<float> dist((size_t)n);
-  e = hipMemcpyAsync(dist.data(), d_mean, sizeof(float) * (size_t)n, hipMemcpyDeviceToHost, h->stream);
-  if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
-  if (e != hipSuccess) return hip_fail("download", e);
-  // mean and standard deviation of the per-point values and the threshold, in PCL's order and types (statistical_outlier_removal.hpp:
-  // double sums over the float distances in point order, the n - 1 form of the variance); N numbers: done on the host
-  double sum = 0.0, sq_sum = 0.0;
-  for (int i = 0; i < n; ++i) {
-    sum += dist[i];
-    sq_sum += dist[i] * dist[i];
-  }
-  const double mean = sum / static_cast<double>(n);
-  const double variance = (sq_sum - sum * sum / static_cast<double>(n)) / (static_cast<double>(n) - 1);
-  const double stddev = std::sqrt(variance);
-  const double threshold = mean + stddev_mul * stddev;
-  int kept = 0;
-  for (int i = 0; i < n; ++i) {
-    keep[i] = dist[i] <= threshold ? 1 : 0;  // negative_ = false: the inliers stay
-    kept += keep[i];
-    if (mean_dist_out) mean_dist_out[i] = dist[i];
-  }
-  if (n_kept) *n_kept = kept;
-  return GORIO_OK;
-}
-
-int gorio_prep_voxel_downsample(int device, const float* xyz, int n, int point_stride_bytes, double leaf, float* xyz_out, int out_stride_bytes, int out_capacity, int* n_out) {
-  if (!xyz || !xyz_out || !n_out || n <= 0 || point_stride_bytes < 12 || (point_stride_bytes % 4) || out_stride_bytes < 12 || (out_stride_bytes % 4) || !(leaf > 0.0))
-    return prep_fail(GORIO_ERR_INVALID, "voxel_downsample: bad arguments");
-  PrepCtx& c = g_prep;
-  if (!c.h || c.device != device) {
-    if (c.h) {
-      hipSetDevice(c.device);
-      hipFree(c.d_cnt); hipFree(c.d_offs); hipFree(c.d_adj);
-      gorio_apd_destroy(c.h);
-      c = PrepCtx();
-    }
-    const int rc = gorio_apd_create(&c.h, device);
-    if (rc) return prep_fail(rc, "voxel_downsample: no usable HIP device (there is no CPU fallback)");
-    c.device = device;
-  }
-  // the scan-to-submap assembly with ONE frame and the identity pose is exactly pcl::VoxelGrid on that cloud (the float transform by
-  // the identity returns every coordinate unchanged)
-  const double eye[16] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1};
-  gorio_apd_keyframe fr;
-  fr.xyz = xyz;
-  fr.label = nullptr;
-  fr.n = n;
-  fr.point_stride_bytes = point_stride_bytes;
-  fr.rel_pose = eye;
-  int m = 0;
-  int rc = gorio_apd_set_target_submap(c.h, &fr, 1, leaf, &m);
-  if (rc) return prep_fail(rc, c.h->err);
-  *n_out = m;
-  if (m > out_capacity) return prep_fail(GORIO_ERR_INVALID, "voxel_downsample: output capacity too small (n_out holds the size needed)");
-  rc = gorio_apd_get_target_points(c.h, xyz_out, nullptr, m, out_stride_bytes);
-  if (rc) return prep_fail(rc, c.h->err);
-  return GORIO_OK;
-}
-
-}  // extern "C"
-
-// ----------------------------------------------------------------------------------------------- REVE (include/gorio_prep.h)
-namespace {
-
-void host_ldlt3_solve(const double* A_in, const double* rhs, double* x) {  // Eigen::LDLT<3x3>: the 6 x 6 routine of the kernels, n = 3
-  double A[9];
-  int perm[3] = {0, 1, 2};
-  std::memcpy(A, A_in, sizeof(A));
-  for (int k = 0; k < 3; ++k) {
-    int piv = k;
-    double best = std::fabs(A[k * 3 + k]);
-    for (int i = k + 1; i < 3; ++i)
-      if (std::fabs(A[i * 3 + i]) > best) {
-        best = std::fabs(A[i * 3 + i]);
-        piv = i;
-      }
-    if (piv != k) {
-      for (int c = 0; c < 3; ++c) std::swap(A[k * 3 + c], A[piv * 3 + c]);
-      for (int r = 0; r < 3; ++r) std::swap(A[r * 3 + k], A[r * 3 + piv]);
-      std::swap(perm[k], perm[piv]);
-    }
-    const double d = A[k * 3 + k];
-    if (d == 0.0) continue;
-    double col[3];
-    for (int i = k + 1; i < 3; ++i) col[i] = A[i * 3 + k];
-    for (int i = k + 1; i < 3; ++i) {
-      const double l = col[i] / d;
-      for (int j = k + 1; j <= i; ++j) A[i * 3 + j] -= l * col[j];
-      A[i * 3 + k] = l;
-    }
-    for (int i = k + 1; i < 3; ++i)
-      for (int j = i + 1; j < 3; ++j) A[i * 3 + j] = A[j * 3 + i];
-  }
-  double y[3];
-  for (int i = 0; i < 3; ++i) y[i] = rhs[perm[i]];
-  for (int i = 0; i < 3; ++i)
-    for (int j = 0; j < i; ++j) y[i] -= A[i * 3 + j] * y[j];
-  for (int i = 0; i < 3; ++i) y[i] = (A[i * 3 + i] != 0.0) ? y[i] / A[i * 3 + i] : 0.0;
-  for (int i = 2; i >= 0; --i)
-    for (int j = i + 1; j < 3; ++j) y[i] -= A[j * 3 + i] * y[j];
-  for (int i = 0; i < 3; ++i) x[perm[i]] = y[i];
-}
-
-struct ReveCtx {
-  int device = -1;
-  hipStream_t stream = nullptr;
-  float* d_in = nullptr;
-  double* d_f = nullptr;
-  double* d_fv = nullptr;
-  unsigned char* d_valid = nullptr;
-  unsigned char* d_flags = nullptr;
-  double* d_v = nullptr;
-  double* d_out = nullptr;
-  size_t cap = 0, flags_cap = 0;
-};
-thread_local ReveCtx g_reve;
-
-}  // namespace
-
-extern "C" {
-
-void gorio_prep_reve_default_config(gorio_reve_config* c) {  // radar_ego_velocity_estimator.h:30-60
-  if (!c) return;
-  std::memset(c, 0, sizeof(*c));
-  c->min_dist = 1; c->max_dist = 400; c->min_db = 0; c->elevation_thresh_deg = 22.5f; c->azimuth_thresh_deg = 56.5f; c->doppler_velocity_correction_factor = 1;
-  c->thresh_zero_velocity = 0.05f; c->allowed_outlier_percentage = 0.30f; c->sigma_zero_velocity_x = 1.0e-03f; c->sigma_zero_velocity_y = 3.2e-03f; c->sigma_zero_velocity_z = 1.0e-02f;
-  c->max_sigma_x = 0.2f; c->max_sigma_y = 0.2f; c->max_sigma_z = 0.2f; c->inlier_thresh = 0.5f; c->use_ransac = 1; c->n_ransac_points = 5;
-  c->outlier_prob = 0.05f; c->success_prob = 0.995f;
-}
-
-int gorio_prep_reve_ransac_iterations(const gorio_reve_config* c) {  // setRansacIter, radar_ego_velocity_estimator.h:138-141
-  if (!c) return 0;
-  return (int)(unsigned int)((std::log(1.0 - c->success_prob)) / std::log(1.0 - std::pow(1.0 - c->outlier_prob, (float)c->n_ransac_points)));
-}
-
-int gorio_prep_ego_velocity(int device, const float* xyz, const float* intensity, const float* doppler, int n, int stride_bytes, const gorio_reve_config* cfg,
-                            const unsigned int* sample_idx, int n_iter, double v_r[3], double sigma_v_r[3], unsigned char* inlier_mask, unsigned char* outlier_mask,
-                            int* n_valid, int* zero_velocity, int* success) {
-  if (!xyz || !intensity || !doppler || !cfg || !v_r || !sigma_v_r || n <= 0 || stride_bytes < 4 || (stride_bytes % 4) || n_iter < 0 || (n_iter > 0 && !sample_idx) || cfg->n_ransac_points < 3 || cfg->n_ransac_points > 64)
-    return prep_fail(GORIO_ERR_INVALID, "ego_velocity: bad arguments");
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return prep_fail(GORIO_ERR_NO_DEVICE, "ego_velocity: no usable HIP device (there is no CPU fallback)");
-  if (device < 0 || device >= ndev) return prep_fail(GORIO_ERR_INVALID, "ego_velocity: bad device ordinal");
-#define REVE_HIP(expr)                                                                                   \
-  do {                                                                                                   \
-    hipError_t e_ = (expr);                                                                              \
-    if (e_ != hipSuccess) return prep_fail(GORIO_ERR_NO_DEVICE, std::string(#expr) + ": " + hipGetErrorString(e_)); \
-  } while (0)
-  REVE_HIP(hipSetDevice(device));
-  ReveCtx& c = g_reve;
-  if (c.device != device) {
-    c = ReveCtx();
-    c.device = device;
-    c.stream = device_stream(device);
-    if (!c.stream) return prep_fail(GORIO_ERR_NO_DEVICE, "ego_velocity: no stream");
-    REVE_HIP(hipMalloc(&c.d_v, sizeof(double) * 3 * 64));
-  }
-  if ((size_t)n > c.cap) {
-    hipFree(c.d_in); hipFree(c.d_f); hipFree(c.d_fv); hipFree(c.d_valid); hipFree(c.d_out);
-    const size_t cap = (size_t)n + n / 8;
-    REVE_HIP(hipMalloc(&c.d_in, sizeof(float) * 5 * cap));
-    REVE_HIP(hipMalloc(&c.d_f, sizeof(double) * 4 * cap));
-    REVE_HIP(hipMalloc(&c.d_fv, sizeof(double) * 4 * cap));
-    REVE_HIP(hipMalloc(&c.d_valid, cap));
-    REVE_HIP(hipMalloc(&c.d_out, sizeof(double) * 10 * (cap / 256 + 2)));
-    c.cap = cap;
-  }
-  // ---- per-target features on the device
-  const int st = stride_bytes / 4;
-  std::vector<float> in((size_t)n * 5);
-  for (int i = 0; i < n; ++i) {
-    in[5 * (size_t)i] = xyz[(size_t)i * st]; in[5 * (size_t)i + 1] = xyz[(size_t)i * st + 1]; in[5 * (size_t)i + 2] = xyz[(size_t)i * st + 2];
-    in[5 * (size_t)i + 3] = intensity[(size_t)i * st]; in[5 * (size_t)i + 4] = doppler[(size_t)i * st];
-  }
-  REVE_HIP(hipMemcpyAsync(c.d_in, in.data(), sizeof(float) * in.size(), hipMemcpyHostToDevice, c.stream));
-  ReveCfg rc;
-  rc.min_dist = cfg->min_dist; rc.max_dist = cfg->max_dist; rc.min_db = cfg->min_db;
-  rc.az_lim = (double)cfg->azimuth_thresh_deg * M_PI / 180.0; rc.el_lim = (double)cfg->elevation_thresh_deg * M_PI / 180.0;  // angles::from_degrees
-  rc.doppler_factor_unused = 0; rc.doppler_factor = cfg->doppler_velocity_correction_factor; rc.pad_ = 0;
-  reve_features_kernel<<<(n + 255) / 256, 256, 0, c.stream>>>(c.d_in, c.d_in + 3, c.d_in + 4, 5, n, rc, c.d_f, c.d_valid);
-  REVE_HIP(hipGetLastError());
-  std::vector<double> f((size_t)n * 4);
-  std::vector<unsigned char> valid((size_t)n);
-  REVE_HIP(hipMemcpyAsync(f.data(), c.d_f, sizeof(double) * f.size(), hipMemcpyDeviceToHost, c.stream));
-  REVE_HIP(hipMemcpyAsync(valid.data(), c.d_valid, (size_t)n, hipMemcpyDeviceToHost, c.stream));
-  REVE_HIP(hipStreamSynchronize(c.stream));
-  std::vector<int> vidx;
-  std::vector<double> fv;
-  for (int i = 0; i < n; ++i)
-    if (valid[i]) {
-      vidx.push_back(i);
-      fv.insert(fv.end(), f.begin() + 4 * (size_t)i, f.begin() + 4 * (size_t)i + 4);
-    }
-  const int m = (int)vidx.size();
-  if (inlier_mask) std::memset(inlier_mask, 0, (size_t)n);
-  if (outlier_mask) std::memset(outlier_mask, 0, (size_t)n);
-  v_r[0] = v_r[1] = v_r[2] = 0.0;
-  sigma_v_r[0] = sigma_v_r[1] = sigma_v_r[2] = 0.0;
-  if (n_valid) *n_valid = m;
-  if (zero_velocity) *zero_velocity = 0;
-  int ok = 0;
-  // solve3DFull (REVE:252-303) over the valid rows selected by `sel`: sums on the device, 3 x 3 algebra here
-  auto solve = [&](const std::vector<unsigned char>& sel, int rows, bool estimate_sigma, double* v, double* sigma) -> int {
-    const int nb = (m + 255) / 256;
-    if (hipMemcpyAsync(c.d_valid, sel.data(), (size_t)m, hipMemcpyHostToDevice, c.stream) != hipSuccess) return -1;
-    std::vector<double> part((size_t)nb * 10);
-    double s[10];
-    for (int pass = 0; pass < (estimate_sigma ? 2 : 1); ++pass) {
-      if (pass == 1 && hipMemcpyAsync(c.d_v, v, sizeof(double) * 3, hipMemcpyHostToDevice, c.stream) != hipSuccess) return -1;
-      reve_sums_kernel<<<nb, 256, 0, c.stream>>>(c.d_fv, m, c.d_valid, pass == 1 ? c.d_v : nullptr, c.d_out);
-      if (hipMemcpyAsync(part.data(), c.d_out, sizeof(double) * part.size(), hipMemcpyDeviceToHost, c.stream) != hipSuccess || hipStreamSynchronize(c.stream) != hipSuccess) return -1;
-      for (int q = 0; q < 10; ++q) s[q] = 0.0;
-      for (int b = 0; b < nb; ++b)
-        for (int q = 0; q < 10; ++q) s[q] += part[(size_t)b * 10 + q];
-      if (pass == 0) {
-        const double HTH[9] = {s[0], s[1], s[2], s[1], s[3], s[4], s[2], s[4], s[5]}, HTy[3] = {s[6], s[7], s[8]};
-        host_ldlt3_solve(HTH, HTy, v);  // use_cholesky_instead_of_bdcsvd = true: (HTH).ldlt().solve(H^T y), REVE:272
-      }
-    }
-    if (estimate_sigma) {  // REVE:278-290
-      const double H0 = s[0], H1 = s[1], H2 = s[2], H4 = s[3], H5 = s[4], H8 = s[5];
-      const double c00 = H4 * H8 - H5 * H5, c01 = H5 * H2 - H1 * H8, c02 = H1 * H5 - H4 * H2;
-      const double det = H0 * c00 + H1 * c01 + H2 * c02;
-      const double sc = s[9] / (double)(rows - 3);
-      double sg[3] = {sc * (c00 / det), sc * ((H0 * H8 - H2 * H2) / det), sc * ((H0 * H4 - H1 * H1) / det)};
-      sigma[0] = sg[0]; sigma[1] = sg[1]; sigma[2] = sg[2];
-      if (sg[0] >= 0.0 && sg[1] >= 0.0 && sg[2] >= 0.0) {
-        sigma[0] = std::sqrt(sg[0]) + cfg->sigma_offset_radar_x;
-        sigma[1] = std::sqrt(sg[1]) + cfg->sigma_offset_radar_y;
-        sigma[2] = std::sqrt(sg[2]) + cfg->sigma_offset_radar_z;
-      }
-    }
-    return 0;
-  };
-  if (m > 2) {
-    REVE_HIP(hipMemcpyAsync(c.d_fv, fv.data(), sizeof(double) * fv.size(), hipMemcpyHostToDevice, c.stream));
-    std::vector<double> vd((size_t)m);
-    for (int k = 0; k < m; ++k) vd[k] = std::fabs(fv[4 * (size_t)k + 3]);
-    const size_t nth = std::min((size_t)((double)m * (1.0 - (double)cfg->allowed_outlier_percentage)), (size_t)m - 1);
-    std::nth_element(vd.begin(), vd.begin() + nth, vd.end());  // REVE:105-108
-    if (vd[nth] < cfg->thresh_zero_velocity) {                 // REVE:110-121
-      if (zero_velocity) *zero_velocity = 1;
-      sigma_v_r[0] = cfg->sigma_zero_velocity_x; sigma_v_r[1] = cfg->sigma_zero_velocity_y; sigma_v_r[2] = cfg->sigma_zero_velocity_z;
-      if (inlier_mask)
-        for (int k = 0; k < m; ++k)
-          if (std::fabs(fv[4 * (size_t)k + 3]) < cfg->thresh_zero_velocity) inlier_mask[vidx[k]] = 1;
-      ok = 1;
-    } else if (!cfg->use_ransac) {
-      std::vector<unsigned char> all((size_t)m, 1);
-      if (solve(all, m, true, v_r, sigma_v_r)) return prep_fail(GORIO_ERR_NO_DEVICE, "ego_velocity: device error");
-      if (inlier_mask) for (int k = 0; k < m; ++k) inlier_mask[vidx[k]] = 1;
-      ok = 1;
-    } else {  // solve3DFullRansac, REVE:172-250
-      std::vector<unsigned char> best_in, best_out;
-      size_t nbi = 0, nbo = 0;
-      const int K = m >= cfg->n_ransac_points ? n_iter : 0;
-      if (K > 0) {
-        if (K > 64) return prep_fail(GORIO_ERR_INVALID, "ego_velocity: more than 64 RANSAC iterations");
-        std::vector<double> vs((size_t)K * 3);
-        for (int k = 0; k < K; ++k) {  // the sample systems are N_ransac_points rows: solved here (3 x 3)
-          double HTH[9] = {0}, HTy[3] = {0};
-          for (int q = 0; q < cfg->n_ransac_points; ++q) {
-            const unsigned int row = sample_idx[(size_t)k * cfg->n_ransac_points + q];
-            if (row >= (unsigned int)m) return prep_fail(GORIO_ERR_INVALID, "ego_velocity: sample index outside the valid targets");
-            const double* r = fv.data() + 4 * (size_t)row;
-            for (int a = 0; a < 3; ++a) {
-              for (int b = 0; b < 3; ++b) HTH[a * 3 + b] += r[a] * r[b];
-              HTy[a] += r[a] * r[3];
-            }
-          }
-          host_ldlt3_solve(HTH, HTy, vs.data() + 3 * (size_t)k);
-        }
-        if ((size_t)K * m > c.flags_cap) {
-          hipFree(c.d_flags);
-          c.d_flags = nullptr;
-          c.flags_cap = 0;
-          REVE_HIP(hipMalloc(&c.d_flags, (size_t)K * m + 1024));
-          c.flags_cap = (size_t)K * m + 1024;
-        }
-        REVE_HIP(hipMemcpyAsync(c.d_v, vs.data(), sizeof(double) * vs.size(), hipMemcpyHostToDevice, c.stream));
-        reve_eval_kernel<<<dim3((m + 255) / 256, K), 256, 0, c.stream>>>(c.d_fv, m, c.d_v, (double)cfg->inlier_thresh, c.d_flags);
-        REVE_HIP(hipGetLastError());
-        std::vector<unsigned char> flags((size_t)K * m);
-        REVE_HIP(hipMemcpyAsync(flags.data(), c.d_flags, flags.size(), hipMemcpyDeviceToHost, c.stream));
-        REVE_HIP(hipStreamSynchronize(c.stream));
-        for (int k = 0; k < K; ++k) {
-          const unsigned char* fl = flags.data() + (size_t)k * m;
-          size_t ni = 0;
-          for (int j = 0; j < m; ++j) ni += fl[j];
-          size_t no = (size_t)m - ni;
-          std::vector<unsigned char> cur_in(fl, fl + m), cur_out((size_t)m);
-          for (int j = 0; j < m; ++j) cur_out[j] = !fl[j];
-          if ((float)no / (float)(ni + no) > 0.05) {  // REVE:215-220
-            std::fill(cur_in.begin(), cur_in.end(), 1);
-            std::fill(cur_out.begin(), cur_out.end(), 0);
-            ni = (size_t)m;
-            no = 0;
-          }
-          if (ni > nbi) { best_in = cur_in; nbi = ni; }
-          if (no > nbo) { best_out = cur_out; nbo = no; }
-          v_r[0] = vs[3 * (size_t)k]; v_r[1] = vs[3 * (size_t)k + 1]; v_r[2] = vs[3 * (size_t)k + 2];
-        }
-      }
-      if (nbi > 0) {
-        if (solve(best_in, (int)nbi, true, v_r, sigma_v_r)) return prep_fail(GORIO_ERR_NO_DEVICE, "ego_velocity: device error");
-        ok = 1;  // REVE:301: true whatever the sigma test said
-        if (inlier_mask) for (int j = 0; j < m; ++j) if (best_in[j]) inlier_mask[vidx[j]] = 1;
-      }
-      if (outlier_mask && nbo > 0) for (int j = 0; j < m; ++j) if (best_out[j]) outlier_mask[vidx[j]] = 1;
-    }
-  }
-#undef REVE_HIP
-  if (success) *success = ok;
-  return GORIO_OK;
-}
-
-}  // extern "C"
-
 #ifdef GORIO_STATS
 extern "C" int gorio_debug_search_stats(unsigned long long out[24], int reset) {
   static std::vector<unsigned long long> all(1024 * 24);
@@ -2812,3 +2067,8 @@ extern "C" int gorio_debug_search_stats(unsigned long long out[24], int reset) {
   return 0;
 }
 #endif
+
+// the preprocessing ABI (include/gorio_prep.h) keeps kernels and host side together, like apd_sc.hip and apd_ground.hip; its host side
+// works through a private registration handle, hence down here
+#include "../../include/gorio_prep.h"
+#include "apd_prep.hip"

@@ -703,18 +703,18 @@ struct gorio_ground {
   std::vector<double> upd_elev[4], upd_flat[4];
   float last_mean[3] = {0, 0, 0}, last_cov[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};  // pc_mean_ / cov_ of the last estimate in sequential order
   // device buffers (a batch uses the first handle's)
-  float4* d_pts = nullptr;
-  int *d_pid = nullptr, *d_seg = nullptr, *d_glist = nullptr;
-  unsigned char* d_mask = nullptr;
-  double* d_C6 = nullptr;
-  unsigned long long* d_keys = nullptr;
+  gorio::DevBuf<float4> d_pts;  // per point: one group of capacity pt_cap
+  gorio::DevBuf<int> d_pid, d_seg, d_glist;
+  gorio::DevBuf<unsigned char> d_mask;
+  gorio::DevBuf<double> d_C6;
+  gorio::DevBuf<unsigned long long> d_keys;
   size_t pt_cap = 0;
-  gorio::GroundPatch* d_rec = nullptr;
-  int2* d_blk = nullptr;
+  gorio::DevBuf<gorio::GroundPatch> d_rec;  // per patch: one group of capacity rec_cap
+  gorio::DevBuf<int2> d_blk;
   size_t rec_cap = 0;
-  gorio::GroundFrame* d_frames = nullptr;
-  gorio::GroundFinal* d_final = nullptr;
-  gorio::GroundFit* d_fit = nullptr;
+  gorio::DevBuf<gorio::GroundFrame> d_frames;  // per frame of a batch: one group of capacity frame_cap
+  gorio::DevBuf<gorio::GroundFinal> d_final;
+  gorio::DevBuf<gorio::GroundFit> d_fit;
   size_t frame_cap = 0;
   // diagnostics of the last estimate
   gorio_ground_frame_diag fdiag;
@@ -728,11 +728,6 @@ int ground_fail(int code, const std::string& m) {
   g_ground_err = m;
   return code;
 }
-#define GROUND_HIP(expr)                                                                                                  \
-  do {                                                                                                                    \
-    hipError_t e_ = (expr);                                                                                               \
-    if (e_ != hipSuccess) return ground_fail(GORIO_ERR_NO_DEVICE, std::string(#expr) + ": " + hipGetErrorString(e_)); \
-  } while (0)
 
 int ground_check_params(const gorio_ground_params& p) {
   if (p.enable_RVPF) return ground_fail(GORIO_ERR_INVALID, "enable_RVPF is not supported (off in the reference and in every caller)");
@@ -934,14 +929,6 @@ void ground_decide(gorio_ground* h, const gorio::GroundPatch* rec, const int* pi
   h->fdiag.n_ground = (int)ground.size();
 }
 
-template <typename T>
-int ground_grow(T*& ptr, size_t need) {
-  hipFree(ptr);
-  ptr = nullptr;
-  GROUND_HIP(hipMalloc(&ptr, sizeof(T) * need));
-  return GORIO_OK;
-}
-
 int ground_run(gorio_ground* const* hs, int count, const float* const* xyz, const float* const* inten, const int* n, const int* stride, int id, int* const* order_out,
                int* n_ground, int* n_out) {
   if (!hs || count <= 0 || !xyz || !inten || !n || !stride || !order_out || !n_ground || !n_out) return ground_fail(GORIO_ERR_INVALID, "estimate: null argument");
@@ -965,25 +952,14 @@ int ground_run(gorio_ground* const* hs, int count, const float* const* xyz, cons
     ptot += hs[q]->n_patches;
   }
   if (ntot > (size_t)INT_MAX / 2) return ground_fail(GORIO_ERR_INVALID, "estimate: too many points");
-  GROUND_HIP(hipSetDevice(lead->device));
-  if (ntot > lead->pt_cap) {
+  GORIO_HIP_CHECK(ground_fail, hipSetDevice(lead->device));
+  {
     const size_t cap = ntot + ntot / 4;
-    lead->pt_cap = 0;
-    if (ground_grow(lead->d_pts, cap) || ground_grow(lead->d_pid, cap) || ground_grow(lead->d_seg, cap) || ground_grow(lead->d_glist, cap) || ground_grow(lead->d_mask, cap) ||
-        ground_grow(lead->d_C6, 6 * cap) || ground_grow(lead->d_keys, 2 * cap))
-      return GORIO_ERR_NO_DEVICE;
-    lead->pt_cap = cap;
+    GORIO_HIP_CHECK(ground_fail, gorio::reserve_group(lead->pt_cap, ntot, cap, lead->d_pts, cap, lead->d_pid, cap, lead->d_seg, cap, lead->d_glist, cap, lead->d_mask, cap, lead->d_C6, 6 * cap,
+                                    lead->d_keys, 2 * cap));
   }
-  if (ptot > lead->rec_cap) {
-    lead->rec_cap = 0;
-    if (ground_grow(lead->d_rec, ptot) || ground_grow(lead->d_blk, ptot)) return GORIO_ERR_NO_DEVICE;
-    lead->rec_cap = ptot;
-  }
-  if ((size_t)count > lead->frame_cap) {
-    lead->frame_cap = 0;
-    if (ground_grow(lead->d_frames, count) || ground_grow(lead->d_final, count) || ground_grow(lead->d_fit, count)) return GORIO_ERR_NO_DEVICE;
-    lead->frame_cap = count;
-  }
+  GORIO_HIP_CHECK(ground_fail, gorio::reserve_group(lead->rec_cap, ptot, ptot, lead->d_rec, ptot, lead->d_blk, ptot));
+  GORIO_HIP_CHECK(ground_fail, gorio::reserve_group(lead->frame_cap, count, count, lead->d_frames, count, lead->d_final, count, lead->d_fit, count));
   std::vector<float4> pts(ntot);
   std::vector<gorio::GroundFrame> fr(count);
   std::vector<int2> blk;
@@ -1029,23 +1005,23 @@ int ground_run(gorio_ground* const* hs, int count, const float* const* xyz, cons
     max_n = std::max(max_n, n[q]);
   }
   hipStream_t st = lead->stream;
-  GROUND_HIP(hipMemcpyAsync(lead->d_pts, pts.data(), sizeof(float4) * ntot, hipMemcpyHostToDevice, st));
-  GROUND_HIP(hipMemcpyAsync(lead->d_frames, fr.data(), sizeof(gorio::GroundFrame) * count, hipMemcpyHostToDevice, st));
-  GROUND_HIP(hipMemcpyAsync(lead->d_blk, blk.data(), sizeof(int2) * ptot, hipMemcpyHostToDevice, st));
+  GORIO_HIP_CHECK(ground_fail, hipMemcpyAsync(lead->d_pts, pts.data(), sizeof(float4) * ntot, hipMemcpyHostToDevice, st));
+  GORIO_HIP_CHECK(ground_fail, hipMemcpyAsync(lead->d_frames, fr.data(), sizeof(gorio::GroundFrame) * count, hipMemcpyHostToDevice, st));
+  GORIO_HIP_CHECK(ground_fail, hipMemcpyAsync(lead->d_blk, blk.data(), sizeof(int2) * ptot, hipMemcpyHostToDevice, st));
   gorio::ground_classify_kernel<<<dim3((max_n + 255) / 256, count), 256, 0, st>>>(lead->d_frames, lead->d_pts, lead->d_pid, lead->d_C6);
-  GROUND_HIP(hipGetLastError());
+  GORIO_HIP_CHECK(ground_fail, hipGetLastError());
   gorio::ground_segment_kernel<<<count, 1024, 0, st>>>(lead->d_frames, lead->d_pid, lead->d_seg, lead->d_rec);
-  GROUND_HIP(hipGetLastError());
+  GORIO_HIP_CHECK(ground_fail, hipGetLastError());
   gorio::ground_patch_kernel<<<(unsigned)ptot, 256, 0, st>>>(lead->d_frames, lead->d_blk, lead->d_pts, lead->d_C6, lead->d_seg, lead->d_mask, lead->d_keys, lead->d_rec);
-  GROUND_HIP(hipGetLastError());
+  GORIO_HIP_CHECK(ground_fail, hipGetLastError());
   std::vector<int> pid(ntot), seg(ntot);
   std::vector<unsigned char> mask(ntot);
   std::vector<gorio::GroundPatch> rec(ptot);
-  GROUND_HIP(hipMemcpyAsync(pid.data(), lead->d_pid, sizeof(int) * ntot, hipMemcpyDeviceToHost, st));
-  GROUND_HIP(hipMemcpyAsync(seg.data(), lead->d_seg, sizeof(int) * ntot, hipMemcpyDeviceToHost, st));
-  GROUND_HIP(hipMemcpyAsync(mask.data(), lead->d_mask, ntot, hipMemcpyDeviceToHost, st));
-  GROUND_HIP(hipMemcpyAsync(rec.data(), lead->d_rec, sizeof(gorio::GroundPatch) * ptot, hipMemcpyDeviceToHost, st));
-  GROUND_HIP(hipStreamSynchronize(st));
+  GORIO_HIP_CHECK(ground_fail, hipMemcpyAsync(pid.data(), lead->d_pid, sizeof(int) * ntot, hipMemcpyDeviceToHost, st));
+  GORIO_HIP_CHECK(ground_fail, hipMemcpyAsync(seg.data(), lead->d_seg, sizeof(int) * ntot, hipMemcpyDeviceToHost, st));
+  GORIO_HIP_CHECK(ground_fail, hipMemcpyAsync(mask.data(), lead->d_mask, ntot, hipMemcpyDeviceToHost, st));
+  GORIO_HIP_CHECK(ground_fail, hipMemcpyAsync(rec.data(), lead->d_rec, sizeof(gorio::GroundPatch) * ptot, hipMemcpyDeviceToHost, st));
+  GORIO_HIP_CHECK(ground_fail, hipStreamSynchronize(st));
   std::vector<std::vector<int>> grounds(count), nongrounds(count);
   std::vector<gorio::GroundFinal> fin(count);
   std::vector<int> glist;
@@ -1066,13 +1042,13 @@ int ground_run(gorio_ground* const* hs, int count, const float* const* xyz, cons
     std::memcpy(fin[q].stale_cov, h->last_cov, sizeof(h->last_cov));
     glist.insert(glist.end(), grounds[q].begin(), grounds[q].end());
   }
-  if (!glist.empty()) GROUND_HIP(hipMemcpyAsync(lead->d_glist, glist.data(), sizeof(int) * glist.size(), hipMemcpyHostToDevice, st));
-  GROUND_HIP(hipMemcpyAsync(lead->d_final, fin.data(), sizeof(gorio::GroundFinal) * count, hipMemcpyHostToDevice, st));
+  if (!glist.empty()) GORIO_HIP_CHECK(ground_fail, hipMemcpyAsync(lead->d_glist, glist.data(), sizeof(int) * glist.size(), hipMemcpyHostToDevice, st));
+  GORIO_HIP_CHECK(ground_fail, hipMemcpyAsync(lead->d_final, fin.data(), sizeof(gorio::GroundFinal) * count, hipMemcpyHostToDevice, st));
   gorio::ground_final_fit_kernel<<<count, 256, 0, st>>>(lead->d_frames, lead->d_final, lead->d_glist, lead->d_pts, lead->d_C6, lead->d_fit);
-  GROUND_HIP(hipGetLastError());
+  GORIO_HIP_CHECK(ground_fail, hipGetLastError());
   std::vector<gorio::GroundFit> fits(count);
-  GROUND_HIP(hipMemcpyAsync(fits.data(), lead->d_fit, sizeof(gorio::GroundFit) * count, hipMemcpyDeviceToHost, st));
-  GROUND_HIP(hipStreamSynchronize(st));
+  GORIO_HIP_CHECK(ground_fail, hipMemcpyAsync(fits.data(), lead->d_fit, sizeof(gorio::GroundFit) * count, hipMemcpyDeviceToHost, st));
+  GORIO_HIP_CHECK(ground_fail, hipStreamSynchronize(st));
   for (int q = 0; q < count; ++q) {
     gorio_ground* h = hs[q];
     const gorio::GroundFit& F = fits[q];
@@ -1152,7 +1128,7 @@ int gorio_ground_create(gorio_ground_t** out, int device, const gorio_ground_par
   int ndev = 0;
   if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return ground_fail(GORIO_ERR_NO_DEVICE, "create: no usable HIP device (there is no CPU fallback)");
   if (device < 0 || device >= ndev) return ground_fail(GORIO_ERR_INVALID, "create: bad device ordinal");
-  GROUND_HIP(hipSetDevice(device));
+  GORIO_HIP_CHECK(ground_fail, hipSetDevice(device));
   gorio_ground* h = new (std::nothrow) gorio_ground();
   if (!h) return ground_fail(GORIO_ERR_ALLOC, "create: out of memory");
   h->device = device;
@@ -1174,8 +1150,6 @@ int gorio_ground_create(gorio_ground_t** out, int device, const gorio_ground_par
 void gorio_ground_destroy(gorio_ground_t* h) {
   if (!h) return;
   hipSetDevice(h->device);
-  hipFree(h->d_pts); hipFree(h->d_pid); hipFree(h->d_seg); hipFree(h->d_glist); hipFree(h->d_mask); hipFree(h->d_C6); hipFree(h->d_keys);
-  hipFree(h->d_rec); hipFree(h->d_blk); hipFree(h->d_frames); hipFree(h->d_final); hipFree(h->d_fit);
   if (h->stream) hipStreamDestroy(h->stream);
   delete h;
 }

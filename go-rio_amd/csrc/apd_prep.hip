@@ -1,5 +1,6 @@
 // apd_prep.hip -- preprocessing that feeds the hot path: the radius searches of the DBSCAN cluster labelling
-// (preprocessing_nodelet_ntu.cpp:518-568, DBSCAN_simple.h:28-100).  Included by apd_api.hip after apd_index.hip.
+// (preprocessing_nodelet_ntu.cpp:518-568, DBSCAN_simple.h:28-100).  Kernels first, the host side of include/gorio_prep.h below them.  Included at the end of
+// apd_api.hip.
 //
 // DBSCAN_simple.h is an order-dependent queue (points visited in index order, first cluster to reach a point keeps it as a member,
 // seed neighbours re-queued whatever their state) whose cost is entirely in its radius searches -- one per visited point, each a
@@ -190,7 +191,7 @@ __global__ __launch_bounds__(256) void sor_mean_distance_kernel(CloudView cloud,
 }  // namespace gorio
 
 // ----------------------------------------------------------------------------------------------- REVE Doppler ego-velocity
-// REVE = /root/reference/4DRadarSLAM/src/radar_ego_velocity_estimator.cpp.  The per-target work of estimate() (REVE:75-90: range,
+// REVE = the reference's src/radar_ego_velocity_estimator.cpp.  The per-target work of estimate() (REVE:75-90: range,
 // azimuth / elevation gates, unit direction, corrected Doppler), of every RANSAC hypothesis (REVE:203-214: |y - H v| against the
 // inlier threshold for ALL targets) and of the final least squares (REVE:252-290: H^T H, H^T y, e^T e) are data parallel and run
 // here; the 3 x 3 solves, the order statistic and the bookkeeping of the best hypothesis are a few hundred flops on the host.
@@ -259,3 +260,513 @@ __global__ __launch_bounds__(256) void reve_sums_kernel(const double* __restrict
 }
 
 }  // namespace gorio
+
+// ================================================================================================= host (include/gorio_prep.h)
+// Included at the end of apd_api.hip: the filters work through a private registration handle (gorio_apd, DevCloud, run_index_build).
+
+namespace {
+thread_local std::string g_prep_err;
+int prep_fail(int code, const std::string& m) {
+  g_prep_err = m;
+  return code;
+}
+
+struct PrepCtx {  // per thread: a private registration handle serves as the device-side cloud + search-index holder
+  gorio_apd* h = nullptr;
+  int device = -1;
+  DevBuf<int> d_cnt;  // d_cnt and d_offs: one group of capacity pts_cap (points)
+  DevBuf<long long> d_offs;
+  size_t pts_cap = 0;
+  DevBuf<int> d_adj;
+  void reset() {  // back to the empty context; the buffers free on the device they live on
+    if (!h) return;
+    hipSetDevice(device);
+    d_cnt.reset(), d_offs.reset(), d_adj.reset();
+    pts_cap = 0;
+    gorio_apd_destroy(h);
+    h = nullptr;
+    device = -1;
+  }
+  ~PrepCtx() { reset(); }
+};
+thread_local PrepCtx g_prep;
+
+// the thread's context, ready for `device`; nullptr (and `rc`, the error recorded) when the device is not usable
+PrepCtx* prep_context(int device, const char* who, int& rc) {
+  PrepCtx& c = g_prep;
+  rc = GORIO_OK;
+  if (!c.h || c.device != device) {
+    c.reset();
+    rc = gorio_apd_create(&c.h, device);
+    if (rc) {
+      prep_fail(rc, std::string(who) + ": no usable HIP device (there is no CPU fallback)");
+      return nullptr;
+    }
+    c.device = device;
+  }
+  return &c;
+}
+
+// the cloud becomes the source of the context's handle, with its search index built and one d_cnt / d_offs slot per point
+int prep_index_cloud(PrepCtx& c, const float* xyz, int n, int point_stride_bytes) {
+  gorio_apd* h = c.h;
+  h->params.search = GORIO_SEARCH_PRUNED;
+  int rc = gorio_apd_set_source(h, xyz, nullptr, n, point_stride_bytes);
+  if (rc) return prep_fail(rc, h->err);
+  std::vector<std::pair<gorio_apd*, DevCloud*>> one = {{h, h->src.get()}};
+  rc = run_index_build(h, one);
+  if (rc) return prep_fail(rc, h->err);
+  const size_t cap = (size_t)n + n / 8;
+  GORIO_HIP_CHECK(prep_fail, reserve_group(c.pts_cap, n, cap, c.d_cnt, cap, c.d_offs, cap));
+  return GORIO_OK;
+}
+}  // namespace
+
+extern "C" {
+
+const char* gorio_prep_last_error(void) { return g_prep_err.c_str(); }
+
+int gorio_prep_dbscan_labels(int device, const float* xyz, int n, int point_stride_bytes, double eps, int core_min_pts, int min_cluster_size, int max_cluster_size,
+                             float* label_out, int label_stride_bytes, int* n_clusters) {
+  if (!xyz || !label_out || n <= 0 || point_stride_bytes < 12 || (point_stride_bytes % 4) || label_stride_bytes < 4 || (label_stride_bytes % 4))
+    return prep_fail(GORIO_ERR_INVALID, "dbscan_labels: bad arguments");
+  int rc = GORIO_OK;
+  PrepCtx* ctx = prep_context(device, "dbscan_labels", rc);
+  if (!ctx) return rc;
+  PrepCtx& c = *ctx;
+  rc = prep_index_cloud(c, xyz, n, point_stride_bytes);
+  if (rc) return rc;
+  gorio_apd* h = c.h;
+  const CloudView cv = h->src->view();
+  const int grid = (roundup(n, 512) + 255) / 256;
+  RadiusArgs ra{eps, c.d_cnt, c.d_offs, nullptr};
+  radius_neighbours_kernel<0><<<grid, 256, 0, h->stream>>>(cv, ra);
+  GORIO_HIP_CHECK(prep_fail, hipGetLastError());
+  std::vector<int> cnt((size_t)n);
+  GORIO_HIP_CHECK(prep_fail, hipMemcpyAsync(cnt.data(), c.d_cnt, sizeof(int) * (size_t)n, hipMemcpyDeviceToHost, h->stream));
+  GORIO_HIP_CHECK(prep_fail, hipStreamSynchronize(h->stream));
+  std::vector<long long> offs((size_t)n + 1);
+  offs[0] = 0;
+  for (int i = 0; i < n; ++i) offs[i + 1] = offs[i] + cnt[i];
+  const long long E = offs[n];
+  GORIO_HIP_CHECK(prep_fail, c.d_adj.reserve((size_t)E, (size_t)E + (size_t)E / 8 + 16));
+  GORIO_HIP_CHECK(prep_fail, hipMemcpyAsync(c.d_offs, offs.data(), sizeof(long long) * (size_t)n, hipMemcpyHostToDevice, h->stream));
+  ra.adj = c.d_adj;
+  radius_neighbours_kernel<1><<<grid, 256, 0, h->stream>>>(cv, ra);
+  GORIO_HIP_CHECK(prep_fail, hipGetLastError());
+  std::vector<int> adj((size_t)E);
+  if (E > 0) GORIO_HIP_CHECK(prep_fail, hipMemcpyAsync(adj.data(), c.d_adj, sizeof(int) * (size_t)E, hipMemcpyDeviceToHost, h->stream));
+  GORIO_HIP_CHECK(prep_fail, hipStreamSynchronize(h->stream));
+
+  // ---- the queue of DBSCAN_simple.h:28-100, statement for statement, over the adjacency (the radius searches are done)
+  enum : unsigned char { UN = 0, PROCESSING = 1, PROCESSED = 2 };
+  std::vector<unsigned char> types((size_t)n, UN), noise((size_t)n, 0);
+  std::vector<int> queue;
+  std::vector<std::vector<int>> clusters;
+  auto seed_count = [&](int i) { return cnt[i]; };  // |N(i, seed radius)|, the point itself included
+  auto exp_count = [&](int i) {
+    int k = 0;
+    for (long long e = offs[i]; e < offs[i + 1]; ++e) k += (adj[(size_t)e] < 0);
+    return k;
+  };
+  for (int i = 0; i < n; ++i) {
+    if (types[i] == PROCESSED) continue;
+    if (seed_count(i) < core_min_pts) {
+      noise[i] = 1;
+      continue;
+    }
+    queue.clear();
+    queue.push_back(i);
+    types[i] = PROCESSED;
+    for (long long e = offs[i]; e < offs[i + 1]; ++e) {
+      const int j = adj[(size_t)e] & 0x7fffffff;
+      if (j != i) {
+        queue.push_back(j);  // DBS:50-54: whatever its state
+        types[j] = PROCESSING;
+      }
+    }
+    size_t sq = 1;
+    while (sq < queue.size()) {
+      const int q = queue[sq];
+      if (noise[q] || types[q] == PROCESSED) {
+        types[q] = PROCESSED;
+        sq++;
+        continue;
+      }
+      if (exp_count(q) >= core_min_pts) {
+        for (long long e = offs[q]; e < offs[q + 1]; ++e) {
+          if (adj[(size_t)e] >= 0) continue;  // outside the expansion radius
+          const int j = adj[(size_t)e] & 0x7fffffff;
+          if (types[j] == UN) {
+            queue.push_back(j);
+            types[j] = PROCESSING;
+          }
+        }
+      }
+      types[q] = PROCESSED;
+      sq++;
+    }
+    if ((int)queue.size() >= min_cluster_size && (int)queue.size() <= max_cluster_size) clusters.push_back(queue);  // DBS:83-95
+  }
+  // ---- preprocessing_nodelet_ntu.cpp:533-568: rank the clusters by the distance of their centroid, write rank + 1
+  const int st = point_stride_bytes / 4, lst = label_stride_bytes / 4;
+  for (int i = 0; i < n; ++i) label_out[(size_t)i * lst] = 0.0f;
+  const int nc = (int)clusters.size();
+  std::vector<float> dist((size_t)nc);
+  std::vector<int> order((size_t)nc);
+  for (int cidx = 0; cidx < nc; ++cidx) {
+    std::vector<int>& m = clusters[cidx];
+    std::sort(m.begin(), m.end());  // DBS:91
+    float sx = 0.f, sy = 0.f, sz = 0.f;
+    for (int idx : m) {
+      const float* p = xyz + (size_t)idx * st;
+      sx += p[0]; sy += p[1]; sz += p[2];
+    }
+    const int num = (int)m.size();
+    const float cx = sx / num, cy = sy / num, cz = sz / num;
+    dist[cidx] = (float)std::sqrt((double)cx * cx + (double)cy * cy + (double)cz * cz);  // std::hypot(float, float, float)
+    order[cidx] = cidx;
+  }
+  std::stable_sort(order.begin(), order.end(), [&](int a, int b) { return dist[a] < dist[b]; });
+  for (int r = 0; r < nc; ++r)
+    for (int idx : clusters[order[r]]) label_out[(size_t)idx * lst] = (float)(r + 1);
+  if (n_clusters) *n_clusters = nc;
+  return GORIO_OK;
+}
+
+int gorio_prep_radius_outlier_mask(int device, const float* xyz, int n, int point_stride_bytes, double radius, int min_neighbors, unsigned char* keep, int* n_kept) {
+  if (!xyz || !keep || n <= 0 || point_stride_bytes < 12 || (point_stride_bytes % 4) || !(radius > 0.0) || min_neighbors < 0)
+    return prep_fail(GORIO_ERR_INVALID, "radius_outlier_mask: bad arguments");
+  int rc = GORIO_OK;
+  PrepCtx* ctx = prep_context(device, "radius_outlier_mask", rc);
+  if (!ctx) return rc;
+  PrepCtx& c = *ctx;
+  rc = prep_index_cloud(c, xyz, n, point_stride_bytes);
+  if (rc) return rc;
+  gorio_apd* h = c.h;
+  const double r2d = radius * radius;
+  float r2 = FLT_MAX;
+  if (r2d < (double)FLT_MAX) {  // largest float whose double value is <= r^2: (double)d <= r^2  <=>  d <= r2 for every float d
+    r2 = (float)r2d;
+    while ((double)r2 > r2d) r2 = std::nextafterf(r2, 0.0f);
+  }
+  radius_count_kernel<<<(roundup(n, 512) + 255) / 256, 256, 0, h->stream>>>(h->src->view(), r2, c.d_cnt);
+  GORIO_HIP_CHECK(prep_fail, hipGetLastError());
+  std::vector<int> cnt((size_t)n);
+  GORIO_HIP_CHECK(prep_fail, hipMemcpyAsync(cnt.data(), c.d_cnt, sizeof(int) * (size_t)n, hipMemcpyDeviceToHost, h->stream));
+  GORIO_HIP_CHECK(prep_fail, hipStreamSynchronize(h->stream));
+  int kept = 0;
+  for (int i = 0; i < n; ++i) {
+    keep[i] = cnt[i] > min_neighbors ? 1 : 0;  // the query itself is one of the counted points
+    kept += keep[i];
+  }
+  if (n_kept) *n_kept = kept;
+  return GORIO_OK;
+}
+
+int gorio_prep_statistical_outlier_mask(int device, const float* xyz, int n, int point_stride_bytes, int mean_k, double stddev_mul, unsigned char* keep, int* n_kept,
+                                        float* mean_dist_out) {
+  if (!xyz || !keep || n <= 0 || point_stride_bytes < 12 || (point_stride_bytes % 4) || mean_k < 1 || mean_k > 31)
+    return prep_fail(GORIO_ERR_INVALID, "statistical_outlier_mask: bad arguments (mean_k must lie in [1, 31])");
+  if (n < mean_k + 1) return prep_fail(GORIO_ERR_INVALID, "statistical_outlier_mask: fewer points than mean_k + 1 (PCL then sums distances nearestKSearch never set)");
+  int rc = GORIO_OK;
+  PrepCtx* ctx = prep_context(device, "statistical_outlier_mask", rc);
+  if (!ctx) return rc;
+  PrepCtx& c = *ctx;
+  rc = prep_index_cloud(c, xyz, n, point_stride_bytes);
+  if (rc) return rc;
+  gorio_apd* h = c.h;
+  float* d_mean = reinterpret_cast<float*>(c.d_cnt.get());  // one 4-byte word per point, like the neighbour counts
+  sor_mean_distance_kernel<<<(roundup(n, 512) + 255) / 256, 256, 0, h->stream>>>(h->src->view(), mean_k + 1, d_mean);
+  GORIO_HIP_CHECK(prep_fail, hipGetLastError());
+  std::vector<float> dist((size_t)n);
+  GORIO_HIP_CHECK(prep_fail, hipMemcpyAsync(dist.data(), d_mean, sizeof(float) * (size_t)n, hipMemcpyDeviceToHost, h->stream));
+  GORIO_HIP_CHECK(prep_fail, hipStreamSynchronize(h->stream));
+  // mean and standard deviation of the per-point values and the threshold, in PCL's order and types (statistical_outlier_removal.hpp:
+  // double sums over the float distances in point order, the n - 1 form of the variance); N numbers: done on the host
+  double sum = 0.0, sq_sum = 0.0;
+  for (int i = 0; i < n; ++i) {
+    sum += dist[i];
+    sq_sum += dist[i] * dist[i];
+  }
+  const double mean = sum / static_cast<double>(n);
+  const double variance = (sq_sum - sum * sum / static_cast<double>(n)) / (static_cast<double>(n) - 1);
+  const double stddev = std::sqrt(variance);
+  const double threshold = mean + stddev_mul * stddev;
+  int kept = 0;
+  for (int i = 0; i < n; ++i) {
+    keep[i] = dist[i] <= threshold ? 1 : 0;  // negative_ = false: the inliers stay
+    kept += keep[i];
+    if (mean_dist_out) mean_dist_out[i] = dist[i];
+  }
+  if (n_kept) *n_kept = kept;
+  return GORIO_OK;
+}
+
+int gorio_prep_voxel_downsample(int device, const float* xyz, int n, int point_stride_bytes, double leaf, float* xyz_out, int out_stride_bytes, int out_capacity, int* n_out) {
+  if (!xyz || !xyz_out || !n_out || n <= 0 || point_stride_bytes < 12 || (point_stride_bytes % 4) || out_stride_bytes < 12 || (out_stride_bytes % 4) || !(leaf > 0.0))
+    return prep_fail(GORIO_ERR_INVALID, "voxel_downsample: bad arguments");
+  int rc = GORIO_OK;
+  PrepCtx* ctx = prep_context(device, "voxel_downsample", rc);
+  if (!ctx) return rc;
+  PrepCtx& c = *ctx;
+  // the scan-to-submap assembly with ONE frame and the identity pose is exactly pcl::VoxelGrid on that cloud (the float transform by
+  // the identity returns every coordinate unchanged)
+  const double eye[16] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1};
+  gorio_apd_keyframe fr;
+  fr.xyz = xyz;
+  fr.label = nullptr;
+  fr.n = n;
+  fr.point_stride_bytes = point_stride_bytes;
+  fr.rel_pose = eye;
+  int m = 0;
+  rc = gorio_apd_set_target_submap(c.h, &fr, 1, leaf, &m);
+  if (rc) return prep_fail(rc, c.h->err);
+  *n_out = m;
+  if (m > out_capacity) return prep_fail(GORIO_ERR_INVALID, "voxel_downsample: output capacity too small (n_out holds the size needed)");
+  rc = gorio_apd_get_target_points(c.h, xyz_out, nullptr, m, out_stride_bytes);
+  if (rc) return prep_fail(rc, c.h->err);
+  return GORIO_OK;
+}
+
+}  // extern "C"
+
+// ----------------------------------------------------------------------------------------------- REVE (include/gorio_prep.h)
+namespace {
+
+void host_ldlt3_solve(const double* A_in, const double* rhs, double* x) {  // Eigen::LDLT<3x3>: the 6 x 6 routine of the kernels, n = 3
+  double A[9];
+  int perm[3] = {0, 1, 2};
+  std::memcpy(A, A_in, sizeof(A));
+  for (int k = 0; k < 3; ++k) {
+    int piv = k;
+    double best = std::fabs(A[k * 3 + k]);
+    for (int i = k + 1; i < 3; ++i)
+      if (std::fabs(A[i * 3 + i]) > best) {
+        best = std::fabs(A[i * 3 + i]);
+        piv = i;
+      }
+    if (piv != k) {
+      for (int c = 0; c < 3; ++c) std::swap(A[k * 3 + c], A[piv * 3 + c]);
+      for (int r = 0; r < 3; ++r) std::swap(A[r * 3 + k], A[r * 3 + piv]);
+      std::swap(perm[k], perm[piv]);
+    }
+    const double d = A[k * 3 + k];
+    if (d == 0.0) continue;
+    double col[3];
+    for (int i = k + 1; i < 3; ++i) col[i] = A[i * 3 + k];
+    for (int i = k + 1; i < 3; ++i) {
+      const double l = col[i] / d;
+      for (int j = k + 1; j <= i; ++j) A[i * 3 + j] -= l * col[j];
+      A[i * 3 + k] = l;
+    }
+    for (int i = k + 1; i < 3; ++i)
+      for (int j = i + 1; j < 3; ++j) A[i * 3 + j] = A[j * 3 + i];
+  }
+  double y[3];
+  for (int i = 0; i < 3; ++i) y[i] = rhs[perm[i]];
+  for (int i = 0; i < 3; ++i)
+    for (int j = 0; j < i; ++j) y[i] -= A[i * 3 + j] * y[j];
+  for (int i = 0; i < 3; ++i) y[i] = (A[i * 3 + i] != 0.0) ? y[i] / A[i * 3 + i] : 0.0;
+  for (int i = 2; i >= 0; --i)
+    for (int j = i + 1; j < 3; ++j) y[i] -= A[j * 3 + i] * y[j];
+  for (int i = 0; i < 3; ++i) x[perm[i]] = y[i];
+}
+
+struct ReveCtx {  // per thread; move-assigning a new one frees what the old one held
+  int device = -1;
+  hipStream_t stream = nullptr;
+  DevBuf<float> d_in;  // d_in, d_f, d_fv, d_valid and d_out: one group of capacity `cap` (targets)
+  DevBuf<double> d_f, d_fv, d_out;
+  DevBuf<unsigned char> d_valid;
+  size_t cap = 0;
+  DevBuf<unsigned char> d_flags;
+  DevBuf<double> d_v;
+};
+thread_local ReveCtx g_reve;
+
+}  // namespace
+
+extern "C" {
+
+void gorio_prep_reve_default_config(gorio_reve_config* c) {  // radar_ego_velocity_estimator.h:30-60
+  if (!c) return;
+  std::memset(c, 0, sizeof(*c));
+  c->min_dist = 1; c->max_dist = 400; c->min_db = 0; c->elevation_thresh_deg = 22.5f; c->azimuth_thresh_deg = 56.5f; c->doppler_velocity_correction_factor = 1;
+  c->thresh_zero_velocity = 0.05f; c->allowed_outlier_percentage = 0.30f; c->sigma_zero_velocity_x = 1.0e-03f; c->sigma_zero_velocity_y = 3.2e-03f; c->sigma_zero_velocity_z = 1.0e-02f;
+  c->max_sigma_x = 0.2f; c->max_sigma_y = 0.2f; c->max_sigma_z = 0.2f; c->inlier_thresh = 0.5f; c->use_ransac = 1; c->n_ransac_points = 5;
+  c->outlier_prob = 0.05f; c->success_prob = 0.995f;
+}
+
+int gorio_prep_reve_ransac_iterations(const gorio_reve_config* c) {  // setRansacIter, radar_ego_velocity_estimator.h:138-141
+  if (!c) return 0;
+  return (int)(unsigned int)((std::log(1.0 - c->success_prob)) / std::log(1.0 - std::pow(1.0 - c->outlier_prob, (float)c->n_ransac_points)));
+}
+
+int gorio_prep_ego_velocity(int device, const float* xyz, const float* intensity, const float* doppler, int n, int stride_bytes, const gorio_reve_config* cfg,
+                            const unsigned int* sample_idx, int n_iter, double v_r[3], double sigma_v_r[3], unsigned char* inlier_mask, unsigned char* outlier_mask,
+                            int* n_valid, int* zero_velocity, int* success) {
+  if (!xyz || !intensity || !doppler || !cfg || !v_r || !sigma_v_r || n <= 0 || stride_bytes < 4 || (stride_bytes % 4) || n_iter < 0 || (n_iter > 0 && !sample_idx) || cfg->n_ransac_points < 3 || cfg->n_ransac_points > 64)
+    return prep_fail(GORIO_ERR_INVALID, "ego_velocity: bad arguments");
+  int ndev = 0;
+  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return prep_fail(GORIO_ERR_NO_DEVICE, "ego_velocity: no usable HIP device (there is no CPU fallback)");
+  if (device < 0 || device >= ndev) return prep_fail(GORIO_ERR_INVALID, "ego_velocity: bad device ordinal");
+  ReveCtx& c = g_reve;
+  if (c.device >= 0 && c.device != device) {  // a context of another device: a plain reset, its buffers free on their own device
+    hipSetDevice(c.device);
+    c = ReveCtx();
+  }
+  GORIO_HIP_CHECK(prep_fail, hipSetDevice(device));
+  if (c.device < 0) {  // a context becomes this device's only once it is complete
+    c.stream = device_stream(device);
+    if (!c.stream) return prep_fail(GORIO_ERR_NO_DEVICE, "ego_velocity: no stream");
+    GORIO_HIP_CHECK(prep_fail, c.d_v.reserve(3 * 64));
+    c.device = device;
+  }
+  {
+    const size_t cap = (size_t)n + n / 8;
+    GORIO_HIP_CHECK(prep_fail, reserve_group(c.cap, n, cap, c.d_in, 5 * cap, c.d_f, 4 * cap, c.d_fv, 4 * cap, c.d_valid, cap, c.d_out, 10 * (cap / 256 + 2)));
+  }
+  // ---- per-target features on the device
+  const int st = stride_bytes / 4;
+  std::vector<float> in((size_t)n * 5);
+  for (int i = 0; i < n; ++i) {
+    in[5 * (size_t)i] = xyz[(size_t)i * st]; in[5 * (size_t)i + 1] = xyz[(size_t)i * st + 1]; in[5 * (size_t)i + 2] = xyz[(size_t)i * st + 2];
+    in[5 * (size_t)i + 3] = intensity[(size_t)i * st]; in[5 * (size_t)i + 4] = doppler[(size_t)i * st];
+  }
+  GORIO_HIP_CHECK(prep_fail, hipMemcpyAsync(c.d_in, in.data(), sizeof(float) * in.size(), hipMemcpyHostToDevice, c.stream));
+  ReveCfg rc;
+  rc.min_dist = cfg->min_dist; rc.max_dist = cfg->max_dist; rc.min_db = cfg->min_db;
+  rc.az_lim = (double)cfg->azimuth_thresh_deg * M_PI / 180.0; rc.el_lim = (double)cfg->elevation_thresh_deg * M_PI / 180.0;  // angles::from_degrees
+  rc.doppler_factor_unused = 0; rc.doppler_factor = cfg->doppler_velocity_correction_factor; rc.pad_ = 0;
+  reve_features_kernel<<<(n + 255) / 256, 256, 0, c.stream>>>(c.d_in, c.d_in + 3, c.d_in + 4, 5, n, rc, c.d_f, c.d_valid);
+  GORIO_HIP_CHECK(prep_fail, hipGetLastError());
+  std::vector<double> f((size_t)n * 4);
+  std::vector<unsigned char> valid((size_t)n);
+  GORIO_HIP_CHECK(prep_fail, hipMemcpyAsync(f.data(), c.d_f, sizeof(double) * f.size(), hipMemcpyDeviceToHost, c.stream));
+  GORIO_HIP_CHECK(prep_fail, hipMemcpyAsync(valid.data(), c.d_valid, (size_t)n, hipMemcpyDeviceToHost, c.stream));
+  GORIO_HIP_CHECK(prep_fail, hipStreamSynchronize(c.stream));
+  std::vector<int> vidx;
+  std::vector<double> fv;
+  for (int i = 0; i < n; ++i)
+    if (valid[i]) {
+      vidx.push_back(i);
+      fv.insert(fv.end(), f.begin() + 4 * (size_t)i, f.begin() + 4 * (size_t)i + 4);
+    }
+  const int m = (int)vidx.size();
+  if (inlier_mask) std::memset(inlier_mask, 0, (size_t)n);
+  if (outlier_mask) std::memset(outlier_mask, 0, (size_t)n);
+  v_r[0] = v_r[1] = v_r[2] = 0.0;
+  sigma_v_r[0] = sigma_v_r[1] = sigma_v_r[2] = 0.0;
+  if (n_valid) *n_valid = m;
+  if (zero_velocity) *zero_velocity = 0;
+  int ok = 0;
+  // solve3DFull (REVE:252-303) over the valid rows selected by `sel`: sums on the device, 3 x 3 algebra here
+  auto solve = [&](const std::vector<unsigned char>& sel, int rows, bool estimate_sigma, double* v, double* sigma) -> int {
+    const int nb = (m + 255) / 256;
+    if (hipMemcpyAsync(c.d_valid, sel.data(), (size_t)m, hipMemcpyHostToDevice, c.stream) != hipSuccess) return -1;
+    std::vector<double> part((size_t)nb * 10);
+    double s[10];
+    for (int pass = 0; pass < (estimate_sigma ? 2 : 1); ++pass) {
+      if (pass == 1 && hipMemcpyAsync(c.d_v, v, sizeof(double) * 3, hipMemcpyHostToDevice, c.stream) != hipSuccess) return -1;
+      reve_sums_kernel<<<nb, 256, 0, c.stream>>>(c.d_fv, m, c.d_valid, pass == 1 ? c.d_v.get() : nullptr, c.d_out);
+      if (hipMemcpyAsync(part.data(), c.d_out, sizeof(double) * part.size(), hipMemcpyDeviceToHost, c.stream) != hipSuccess || hipStreamSynchronize(c.stream) != hipSuccess) return -1;
+      for (int q = 0; q < 10; ++q) s[q] = 0.0;
+      for (int b = 0; b < nb; ++b)
+        for (int q = 0; q < 10; ++q) s[q] += part[(size_t)b * 10 + q];
+      if (pass == 0) {
+        const double HTH[9] = {s[0], s[1], s[2], s[1], s[3], s[4], s[2], s[4], s[5]}, HTy[3] = {s[6], s[7], s[8]};
+        host_ldlt3_solve(HTH, HTy, v);  // use_cholesky_instead_of_bdcsvd = true: (HTH).ldlt().solve(H^T y), REVE:272
+      }
+    }
+    if (estimate_sigma) {  // REVE:278-290
+      const double H0 = s[0], H1 = s[1], H2 = s[2], H4 = s[3], H5 = s[4], H8 = s[5];
+      const double c00 = H4 * H8 - H5 * H5, c01 = H5 * H2 - H1 * H8, c02 = H1 * H5 - H4 * H2;
+      const double det = H0 * c00 + H1 * c01 + H2 * c02;
+      const double sc = s[9] / (double)(rows - 3);
+      double sg[3] = {sc * (c00 / det), sc * ((H0 * H8 - H2 * H2) / det), sc * ((H0 * H4 - H1 * H1) / det)};
+      sigma[0] = sg[0]; sigma[1] = sg[1]; sigma[2] = sg[2];
+      if (sg[0] >= 0.0 && sg[1] >= 0.0 && sg[2] >= 0.0) {
+        sigma[0] = std::sqrt(sg[0]) + cfg->sigma_offset_radar_x;
+        sigma[1] = std::sqrt(sg[1]) + cfg->sigma_offset_radar_y;
+        sigma[2] = std::sqrt(sg[2]) + cfg->sigma_offset_radar_z;
+      }
+    }
+    return 0;
+  };
+  if (m > 2) {
+    GORIO_HIP_CHECK(prep_fail, hipMemcpyAsync(c.d_fv, fv.data(), sizeof(double) * fv.size(), hipMemcpyHostToDevice, c.stream));
+    std::vector<double> vd((size_t)m);
+    for (int k = 0; k < m; ++k) vd[k] = std::fabs(fv[4 * (size_t)k + 3]);
+    const size_t nth = std::min((size_t)((double)m * (1.0 - (double)cfg->allowed_outlier_percentage)), (size_t)m - 1);
+    std::nth_element(vd.begin(), vd.begin() + nth, vd.end());  // REVE:105-108
+    if (vd[nth] < cfg->thresh_zero_velocity) {                 // REVE:110-121
+      if (zero_velocity) *zero_velocity = 1;
+      sigma_v_r[0] = cfg->sigma_zero_velocity_x; sigma_v_r[1] = cfg->sigma_zero_velocity_y; sigma_v_r[2] = cfg->sigma_zero_velocity_z;
+      if (inlier_mask)
+        for (int k = 0; k < m; ++k)
+          if (std::fabs(fv[4 * (size_t)k + 3]) < cfg->thresh_zero_velocity) inlier_mask[vidx[k]] = 1;
+      ok = 1;
+    } else if (!cfg->use_ransac) {
+      std::vector<unsigned char> all((size_t)m, 1);
+      if (solve(all, m, true, v_r, sigma_v_r)) return prep_fail(GORIO_ERR_NO_DEVICE, "ego_velocity: device error");
+      if (inlier_mask) for (int k = 0; k < m; ++k) inlier_mask[vidx[k]] = 1;
+      ok = 1;
+    } else {  // solve3DFullRansac, REVE:172-250
+      std::vector<unsigned char> best_in, best_out;
+      size_t nbi = 0, nbo = 0;
+      const int K = m >= cfg->n_ransac_points ? n_iter : 0;
+      if (K > 0) {
+        if (K > 64) return prep_fail(GORIO_ERR_INVALID, "ego_velocity: more than 64 RANSAC iterations");
+        std::vector<double> vs((size_t)K * 3);
+        for (int k = 0; k < K; ++k) {  // the sample systems are N_ransac_points rows: solved here (3 x 3)
+          double HTH[9] = {0}, HTy[3] = {0};
+          for (int q = 0; q < cfg->n_ransac_points; ++q) {
+            const unsigned int row = sample_idx[(size_t)k * cfg->n_ransac_points + q];
+            if (row >= (unsigned int)m) return prep_fail(GORIO_ERR_INVALID, "ego_velocity: sample index outside the valid targets");
+            const double* r = fv.data() + 4 * (size_t)row;
+            for (int a = 0; a < 3; ++a) {
+              for (int b = 0; b < 3; ++b) HTH[a * 3 + b] += r[a] * r[b];
+              HTy[a] += r[a] * r[3];
+            }
+          }
+          host_ldlt3_solve(HTH, HTy, vs.data() + 3 * (size_t)k);
+        }
+        GORIO_HIP_CHECK(prep_fail, c.d_flags.reserve((size_t)K * m, (size_t)K * m + 1024));
+        GORIO_HIP_CHECK(prep_fail, hipMemcpyAsync(c.d_v, vs.data(), sizeof(double) * vs.size(), hipMemcpyHostToDevice, c.stream));
+        reve_eval_kernel<<<dim3((m + 255) / 256, K), 256, 0, c.stream>>>(c.d_fv, m, c.d_v, (double)cfg->inlier_thresh, c.d_flags);
+        GORIO_HIP_CHECK(prep_fail, hipGetLastError());
+        std::vector<unsigned char> flags((size_t)K * m);
+        GORIO_HIP_CHECK(prep_fail, hipMemcpyAsync(flags.data(), c.d_flags, flags.size(), hipMemcpyDeviceToHost, c.stream));
+        GORIO_HIP_CHECK(prep_fail, hipStreamSynchronize(c.stream));
+        for (int k = 0; k < K; ++k) {
+          const unsigned char* fl = flags.data() + (size_t)k * m;
+          size_t ni = 0;
+          for (int j = 0; j < m; ++j) ni += fl[j];
+          size_t no = (size_t)m - ni;
+          std::vector<unsigned char> cur_in(fl, fl + m), cur_out((size_t)m);
+          for (int j = 0; j < m; ++j) cur_out[j] = !fl[j];
+          if ((float)no / (float)(ni + no) > 0.05) {  // REVE:215-220
+            std::fill(cur_in.begin(), cur_in.end(), 1);
+            std::fill(cur_out.begin(), cur_out.end(), 0);
+            ni = (size_t)m;
+            no = 0;
+          }
+          if (ni > nbi) { best_in = cur_in; nbi = ni; }
+          if (no > nbo) { best_out = cur_out; nbo = no; }
+          v_r[0] = vs[3 * (size_t)k]; v_r[1] = vs[3 * (size_t)k + 1]; v_r[2] = vs[3 * (size_t)k + 2];
+        }
+      }
+      if (nbi > 0) {
+        if (solve(best_in, (int)nbi, true, v_r, sigma_v_r)) return prep_fail(GORIO_ERR_NO_DEVICE, "ego_velocity: device error");
+        ok = 1;  // REVE:301: true whatever the sigma test said
+        if (inlier_mask) for (int j = 0; j < m; ++j) if (best_in[j]) inlier_mask[vidx[j]] = 1;
+      }
+      if (outlier_mask && nbo > 0) for (int j = 0; j < m; ++j) if (best_out[j]) outlier_mask[vidx[j]] = 1;
+    }
+  }
+  if (success) *success = ok;
+  return GORIO_OK;
+}
+
+}  // extern "C"

@@ -329,16 +329,15 @@ struct gorio_sc {
   int n = 0;                  // scans added
   int counter = 0;            // tree_making_period_conter
   std::vector<int> snapshot;  // polarcontext_invkeys_to_search_ as database indices
-  // database
-  gorio::ScDb db{};
+  // database: five arrays of one capacity db_cap (scans); db() is the view the kernels take
+  gorio::DevBuf<double> db_desc, db_ring, db_sector, db_colnorm;
+  gorio::DevBuf<float> db_ringf;
   size_t db_cap = 0;
+  gorio::ScDb db() const { return gorio::ScDb{db_desc, db_ring, db_sector, db_colnorm, db_ringf}; }
   // scratch
-  void* d_in = nullptr;
-  size_t in_cap = 0;
-  gorio::ScHit* d_partial = nullptr;
-  size_t partial_cap = 0;
-  gorio::ScOut* d_out = nullptr;
-  size_t out_cap = 0;
+  gorio::DevBuf<void> d_in;
+  gorio::DevBuf<gorio::ScHit> d_partial;
+  gorio::DevBuf<gorio::ScOut> d_out;
 };
 
 namespace {
@@ -347,54 +346,28 @@ int sc_fail(int code, const std::string& m) {
   g_sc_err = m;
   return code;
 }
-#define SC_HIP(expr)                                                                                                  \
-  do {                                                                                                                \
-    hipError_t e_ = (expr);                                                                                           \
-    if (e_ != hipSuccess) return sc_fail(GORIO_ERR_NO_DEVICE, std::string(#expr) + ": " + hipGetErrorString(e_)); \
-  } while (0)
-
-template <typename T>
-int sc_reserve(T*& ptr, size_t& cap, size_t need) {
-  if (need <= cap) return GORIO_OK;
-  const size_t c = need + need / 2;
-  hipFree(ptr);
-  ptr = nullptr;
-  cap = 0;
-  SC_HIP(hipMalloc(&ptr, sizeof(T) * c));
-  cap = c;
-  return GORIO_OK;
-}
-
-int sc_reserve_bytes(gorio_sc* h, size_t bytes) {
-  if (bytes <= h->in_cap) return GORIO_OK;
-  const size_t c = bytes + bytes / 2;
-  hipFree(h->d_in);
-  h->d_in = nullptr;
-  h->in_cap = 0;
-  SC_HIP(hipMalloc(&h->d_in, c));
-  h->in_cap = c;
-  return GORIO_OK;
-}
 
 // Grows the database to hold `need` scans, keeping what is there.
 int sc_grow_db(gorio_sc* h, size_t need) {
   if (need <= h->db_cap) return GORIO_OK;
   const size_t cap = std::max(need + need / 2, (size_t)64);
-  gorio::ScDb nd{};
-  const size_t widths[5] = {gorio::kScBins, gorio::kScRings, gorio::kScSectors, gorio::kScSectors, gorio::kScRings};
-  void** dst[5] = {(void**)&nd.desc, (void**)&nd.ring, (void**)&nd.sector, (void**)&nd.colnorm, (void**)&nd.ringf};
-  void* src[5] = {h->db.desc, h->db.ring, h->db.sector, h->db.colnorm, h->db.ringf};
-  for (int a = 0; a < 5; ++a) {
-    const size_t el = a == 4 ? sizeof(float) : sizeof(double);
-    if (hipMalloc(dst[a], el * widths[a] * cap) != hipSuccess) {
-      for (int b = 0; b < a; ++b) hipFree(*dst[b]);
-      return sc_fail(GORIO_ERR_NO_DEVICE, "add_scans: device allocation failed");
-    }
-    if (h->n) SC_HIP(hipMemcpyAsync(*dst[a], src[a], el * widths[a] * h->n, hipMemcpyDeviceToDevice, h->stream));
+  // new buffers, copy, then move-assign: the old database stays whole until the new one is (an early return frees the new buffers)
+  gorio::DevBuf<double> desc, ring, sector, colnorm;
+  gorio::DevBuf<float> ringf;
+  size_t new_cap = 0;
+  if (gorio::reserve_group(new_cap, cap, cap, desc, gorio::kScBins * cap, ring, gorio::kScRings * cap, sector, gorio::kScSectors * cap, colnorm, gorio::kScSectors * cap,
+                           ringf, gorio::kScRings * cap) != hipSuccess)
+    return sc_fail(GORIO_ERR_NO_DEVICE, "add_scans: device allocation failed");
+  if (h->n) {
+    const size_t n = h->n;
+    GORIO_HIP_CHECK(sc_fail, hipMemcpyAsync(desc, h->db_desc, sizeof(double) * gorio::kScBins * n, hipMemcpyDeviceToDevice, h->stream));
+    GORIO_HIP_CHECK(sc_fail, hipMemcpyAsync(ring, h->db_ring, sizeof(double) * gorio::kScRings * n, hipMemcpyDeviceToDevice, h->stream));
+    GORIO_HIP_CHECK(sc_fail, hipMemcpyAsync(sector, h->db_sector, sizeof(double) * gorio::kScSectors * n, hipMemcpyDeviceToDevice, h->stream));
+    GORIO_HIP_CHECK(sc_fail, hipMemcpyAsync(colnorm, h->db_colnorm, sizeof(double) * gorio::kScSectors * n, hipMemcpyDeviceToDevice, h->stream));
+    GORIO_HIP_CHECK(sc_fail, hipMemcpyAsync(ringf, h->db_ringf, sizeof(float) * gorio::kScRings * n, hipMemcpyDeviceToDevice, h->stream));
   }
-  SC_HIP(hipStreamSynchronize(h->stream));
-  for (int a = 0; a < 5; ++a) hipFree(src[a]);
-  h->db = nd;
+  GORIO_HIP_CHECK(sc_fail, hipStreamSynchronize(h->stream));
+  h->db_desc = std::move(desc), h->db_ring = std::move(ring), h->db_sector = std::move(sector), h->db_colnorm = std::move(colnorm), h->db_ringf = std::move(ringf);
   h->db_cap = cap;
   return GORIO_OK;
 }
@@ -479,21 +452,23 @@ int sc_detect_run(gorio_sc* h, int count, const int* qidx, const int* const* can
     if (b_chunks) std::memcpy(blob.data(), chunks.data(), b_chunks);
     std::memcpy(blob.data() + b_chunks, queries.data(), b_queries);
     if (b_pool) std::memcpy(blob.data() + b_chunks + b_queries, pool.data(), b_pool);
-    SC_HIP(hipSetDevice(h->device));
-    if (sc_reserve_bytes(h, blob.size()) || sc_reserve(h->d_partial, h->partial_cap, std::max<size_t>(3 * chunks.size(), 3)) || sc_reserve(h->d_out, h->out_cap, nq))
-      return GORIO_ERR_NO_DEVICE;
-    char* base = (char*)h->d_in;
+    GORIO_HIP_CHECK(sc_fail, hipSetDevice(h->device));
+    const size_t n_partial = std::max<size_t>(3 * chunks.size(), 3);  // the scratch buffers grow by half beyond the need
+    GORIO_HIP_CHECK(sc_fail, h->d_in.reserve(blob.size(), blob.size() + blob.size() / 2));
+    GORIO_HIP_CHECK(sc_fail, h->d_partial.reserve(n_partial, n_partial + n_partial / 2));
+    GORIO_HIP_CHECK(sc_fail, h->d_out.reserve(nq, nq + nq / 2));
+    char* base = (char*)h->d_in.get();
     const gorio::ScChunk* d_chunks = (const gorio::ScChunk*)base;
     const gorio::ScQuery* d_queries = (const gorio::ScQuery*)(base + b_chunks);
     const int* d_pool = (const int*)(base + b_chunks + b_queries);
-    SC_HIP(hipMemcpyAsync(h->d_in, blob.data(), blob.size(), hipMemcpyHostToDevice, h->stream));
-    if (!chunks.empty()) hipLaunchKernelGGL(gorio::sc_knn_kernel, dim3((unsigned)chunks.size()), dim3(gorio::kScThreads), 0, h->stream, d_chunks, d_pool, h->db.ringf, h->d_partial);
+    GORIO_HIP_CHECK(sc_fail, hipMemcpyAsync(h->d_in, blob.data(), blob.size(), hipMemcpyHostToDevice, h->stream));
+    if (!chunks.empty()) hipLaunchKernelGGL(gorio::sc_knn_kernel, dim3((unsigned)chunks.size()), dim3(gorio::kScThreads), 0, h->stream, d_chunks, d_pool, h->db_ringf, h->d_partial);
     hipLaunchKernelGGL(gorio::sc_knn_merge_kernel, dim3(nq), dim3(64), 0, h->stream, d_queries, h->d_partial, d_pool, h->d_out);
     const int n_pairs = 3 * nq;
-    hipLaunchKernelGGL(gorio::sc_pair_kernel, dim3((n_pairs + 3) / 4), dim3(gorio::kScThreads), 0, h->stream, h->d_out, n_pairs, h->db);
-    SC_HIP(hipGetLastError());
-    SC_HIP(hipMemcpyAsync(res.data(), h->d_out, sizeof(gorio::ScOut) * nq, hipMemcpyDeviceToHost, h->stream));
-    SC_HIP(hipStreamSynchronize(h->stream));
+    hipLaunchKernelGGL(gorio::sc_pair_kernel, dim3((n_pairs + 3) / 4), dim3(gorio::kScThreads), 0, h->stream, h->d_out, n_pairs, h->db());
+    GORIO_HIP_CHECK(sc_fail, hipGetLastError());
+    GORIO_HIP_CHECK(sc_fail, hipMemcpyAsync(res.data(), h->d_out, sizeof(gorio::ScOut) * nq, hipMemcpyDeviceToHost, h->stream));
+    GORIO_HIP_CHECK(sc_fail, hipStreamSynchronize(h->stream));
   }
   const double unit = (h->p.azimuth_range - (-h->p.azimuth_range)) / double(GORIO_SC_SECTORS);  // PC_UNIT_SECTOR_ANGLE (SC:72)
   for (int i = 0; i < count; ++i) {
@@ -559,7 +534,7 @@ int gorio_sc_create(gorio_sc_t** out, int device, const gorio_sc_params* p) {
   int ndev = 0;
   if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return sc_fail(GORIO_ERR_NO_DEVICE, "create: no usable HIP device (there is no CPU fallback)");
   if (device < 0 || device >= ndev) return sc_fail(GORIO_ERR_INVALID, "create: bad device ordinal");
-  SC_HIP(hipSetDevice(device));
+  GORIO_HIP_CHECK(sc_fail, hipSetDevice(device));
   gorio_sc* h = new (std::nothrow) gorio_sc();
   if (!h) return sc_fail(GORIO_ERR_ALLOC, "create: out of memory");
   h->device = device;
@@ -575,8 +550,6 @@ int gorio_sc_create(gorio_sc_t** out, int device, const gorio_sc_params* p) {
 void gorio_sc_destroy(gorio_sc_t* h) {
   if (!h) return;
   hipSetDevice(h->device);
-  hipFree(h->db.desc); hipFree(h->db.ring); hipFree(h->db.sector); hipFree(h->db.colnorm); hipFree(h->db.ringf);
-  hipFree(h->d_in); hipFree(h->d_partial); hipFree(h->d_out);
   if (h->stream) hipStreamDestroy(h->stream);
   delete h;
 }
@@ -607,13 +580,14 @@ int gorio_sc_add_scans(gorio_sc_t* h, int count, const float* const* xyz, const 
     }
   }
   off[count] = (int)o;
-  SC_HIP(hipSetDevice(h->device));
-  if (sc_grow_db(h, (size_t)h->n + count) || sc_reserve_bytes(h, blob.size())) return GORIO_ERR_NO_DEVICE;
-  SC_HIP(hipMemcpyAsync(h->d_in, blob.data(), blob.size(), hipMemcpyHostToDevice, h->stream));
-  hipLaunchKernelGGL(gorio::sc_descriptor_kernel, dim3(count), dim3(gorio::kScThreads), 0, h->stream, (const float4*)h->d_in, (const int*)((char*)h->d_in + b_pts), h->n,
-                     h->p.azimuth_range, h->db);
-  SC_HIP(hipGetLastError());
-  SC_HIP(hipStreamSynchronize(h->stream));
+  GORIO_HIP_CHECK(sc_fail, hipSetDevice(h->device));
+  if (sc_grow_db(h, (size_t)h->n + count)) return GORIO_ERR_NO_DEVICE;
+  GORIO_HIP_CHECK(sc_fail, h->d_in.reserve(blob.size(), blob.size() + blob.size() / 2));
+  GORIO_HIP_CHECK(sc_fail, hipMemcpyAsync(h->d_in, blob.data(), blob.size(), hipMemcpyHostToDevice, h->stream));
+  hipLaunchKernelGGL(gorio::sc_descriptor_kernel, dim3(count), dim3(gorio::kScThreads), 0, h->stream, (const float4*)h->d_in.get(), (const int*)((char*)h->d_in.get() + b_pts), h->n,
+                     h->p.azimuth_range, h->db());
+  GORIO_HIP_CHECK(sc_fail, hipGetLastError());
+  GORIO_HIP_CHECK(sc_fail, hipStreamSynchronize(h->stream));
   if (first_index_out) *first_index_out = h->n;
   h->n += count;
   return GORIO_OK;
@@ -634,12 +608,12 @@ int gorio_sc_get_state(const gorio_sc_t* h, int* n_scans, int* counter, int* sna
 int gorio_sc_get_descriptor(const gorio_sc_t* h, int index, double* desc, double* ring_key, double* sector_key) {
   if (!h) return sc_fail(GORIO_ERR_INVALID, "get_descriptor: null handle");
   if (index < 0 || index >= h->n) return sc_fail(GORIO_ERR_INVALID, "get_descriptor: index " + std::to_string(index) + " has not been added");
-  SC_HIP(hipSetDevice(h->device));
+  GORIO_HIP_CHECK(sc_fail, hipSetDevice(h->device));
   const size_t i = index;
-  if (desc) SC_HIP(hipMemcpyAsync(desc, h->db.desc + i * gorio::kScBins, sizeof(double) * gorio::kScBins, hipMemcpyDeviceToHost, h->stream));
-  if (ring_key) SC_HIP(hipMemcpyAsync(ring_key, h->db.ring + i * gorio::kScRings, sizeof(double) * gorio::kScRings, hipMemcpyDeviceToHost, h->stream));
-  if (sector_key) SC_HIP(hipMemcpyAsync(sector_key, h->db.sector + i * gorio::kScSectors, sizeof(double) * gorio::kScSectors, hipMemcpyDeviceToHost, h->stream));
-  SC_HIP(hipStreamSynchronize(h->stream));
+  if (desc) GORIO_HIP_CHECK(sc_fail, hipMemcpyAsync(desc, h->db_desc + i * gorio::kScBins, sizeof(double) * gorio::kScBins, hipMemcpyDeviceToHost, h->stream));
+  if (ring_key) GORIO_HIP_CHECK(sc_fail, hipMemcpyAsync(ring_key, h->db_ring + i * gorio::kScRings, sizeof(double) * gorio::kScRings, hipMemcpyDeviceToHost, h->stream));
+  if (sector_key) GORIO_HIP_CHECK(sc_fail, hipMemcpyAsync(sector_key, h->db_sector + i * gorio::kScSectors, sizeof(double) * gorio::kScSectors, hipMemcpyDeviceToHost, h->stream));
+  GORIO_HIP_CHECK(sc_fail, hipStreamSynchronize(h->stream));
   return GORIO_OK;
 }
 
@@ -650,13 +624,13 @@ int gorio_sc_distance(gorio_sc_t* h, int i, int j, double* dist, int* shift) {
   o.qdb = i;
   o.kf[0] = j;
   o.kf[1] = o.kf[2] = -1;
-  SC_HIP(hipSetDevice(h->device));
-  if (sc_reserve(h->d_out, h->out_cap, 1)) return GORIO_ERR_NO_DEVICE;
-  SC_HIP(hipMemcpyAsync(h->d_out, &o, sizeof(o), hipMemcpyHostToDevice, h->stream));
-  hipLaunchKernelGGL(gorio::sc_pair_kernel, dim3(1), dim3(gorio::kScThreads), 0, h->stream, h->d_out, 1, h->db);
-  SC_HIP(hipGetLastError());
-  SC_HIP(hipMemcpyAsync(&o, h->d_out, sizeof(o), hipMemcpyDeviceToHost, h->stream));
-  SC_HIP(hipStreamSynchronize(h->stream));
+  GORIO_HIP_CHECK(sc_fail, hipSetDevice(h->device));
+  GORIO_HIP_CHECK(sc_fail, h->d_out.reserve(1));
+  GORIO_HIP_CHECK(sc_fail, hipMemcpyAsync(h->d_out, &o, sizeof(o), hipMemcpyHostToDevice, h->stream));
+  hipLaunchKernelGGL(gorio::sc_pair_kernel, dim3(1), dim3(gorio::kScThreads), 0, h->stream, h->d_out, 1, h->db());
+  GORIO_HIP_CHECK(sc_fail, hipGetLastError());
+  GORIO_HIP_CHECK(sc_fail, hipMemcpyAsync(&o, h->d_out, sizeof(o), hipMemcpyDeviceToHost, h->stream));
+  GORIO_HIP_CHECK(sc_fail, hipStreamSynchronize(h->stream));
   *dist = o.dist[0];
   *shift = o.shift[0];
   return GORIO_OK;
