@@ -228,6 +228,14 @@ class ApdGicp:
         _check(self._h, self._lib.gorio_apd_set_target_device(self._h, C.c_void_p(d_x), C.c_void_p(d_y), C.c_void_p(d_z), C.c_void_p(d_label or 0), int(n)))
         self._n_tgt = int(n)
 
+    def setInputSourceFromScan(self, scan):  # noqa: N802 -- gorio_apd_set_source_from_scan: the output of a prep.ScanPipeline, no host round trip
+        _check(self._h, self._lib.gorio_apd_set_source_from_scan(self._h, scan.h))
+        self._n_src = scan.last_result["n_out"]
+
+    def setInputTargetFromScan(self, scan):  # noqa: N802
+        _check(self._h, self._lib.gorio_apd_set_target_from_scan(self._h, scan.h))
+        self._n_tgt = scan.last_result["n_out"]
+
     def setInputTargetShared(self, owner):  # noqa: N802 -- gorio_apd_set_target_shared: one device copy of the map for many objects
         _check(self._h, self._lib.gorio_apd_set_target_shared(self._h, owner._h))
         self._n_tgt = owner._n_tgt

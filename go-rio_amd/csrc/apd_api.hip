@@ -689,6 +689,12 @@ bool shared_cov_mismatch(const gorio_apd* h) {
   return h->tgt.use_count() > 1 && t.cov_count == t.n && t.cov_k >= 0 && (t.cov_k != h->params.k_correspondences || t.cov_reg != h->params.regularization);
 }
 
+// the same for a source that other handles hold too (a scan output handed over by gorio_apd_set_source_from_scan, include/gorio_scan.h)
+bool shared_source_cov_mismatch(const gorio_apd* h) {
+  const DevCloud& s = *h->src;
+  return h->src.use_count() > 1 && s.cov_count == s.n && s.cov_k >= 0 && (s.cov_k != h->params.k_correspondences || s.cov_reg != h->params.regularization);
+}
+
 // ---- FastVGICP plumbing
 
 int voxel_offsets(int search) { return search == GORIO_VOXEL_DIRECT1 ? 1 : search == GORIO_VOXEL_DIRECT7 ? 7 : 27; }  // neighbor_offsets, VOX:16-43
@@ -812,6 +818,7 @@ int check_ready(gorio_apd* h) {
   if (!h->tgt->present) return fail(h, GORIO_ERR_STATE, "no input target set (setInputTarget)");
   const gorio_apd_params& p = h->params;
   if (shared_cov_mismatch(h)) return fail(h, GORIO_ERR_INVALID, "the shared target's covariances were estimated with another k_correspondences / regularization: give this handle a target of its own (setInputTarget)");
+  if (shared_source_cov_mismatch(h)) return fail(h, GORIO_ERR_INVALID, "the shared source's covariances were estimated with another k_correspondences / regularization: give this handle a source of its own (setInputSource)");
   if (shared_voxel_mismatch(h)) return fail(h, GORIO_ERR_INVALID, "the shared target's voxel map was built with another voxel_resolution / voxel_mode: give this handle a target of its own (setInputTarget)");
   if (h->method == GORIO_METHOD_VGICP && (h->comm || (h->shard_only && h->comm_world > 1)))
     return fail(h, GORIO_ERR_STATE, "FastVGICP has no sharded-source mode (gorio_apd_comm_init / gorio_apd_debug_set_shard): use an unsharded handle");
@@ -2072,3 +2079,4 @@ extern "C" int gorio_debug_search_stats(unsigned long long out[24], int reset) {
 // works through a private registration handle, hence down here
 #include "../../include/gorio_prep.h"
 #include "apd_prep.hip"
+#include "apd_scan.hip"

@@ -686,6 +686,25 @@ __global__ __launch_bounds__(256) void ground_final_fit_kernel(const GroundFrame
   if (threadIdx.x == 0) store_fit(s, out[blockIdx.x], m, it, term);
 }
 
+// ------------------------------------------------------------------------------------------------ a scan that is already on the device
+// The scan pipeline (include/gorio_scan.h) keeps its cloud as float columns on the device.  grid ceil(n / 256), block 256.
+__global__ __launch_bounds__(256) void ground_pack_kernel(const float* __restrict__ x, const float* __restrict__ y, const float* __restrict__ z, const float* __restrict__ inten, int n,
+                                                          float4* __restrict__ pts) {
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i < n) pts[i] = make_float4(x[i], y[i], z[i], inten[i]);
+}
+
+// PWP:872-884, the test only: below[i] = (normal . p_i + d < -1) in double on the float plane, the products summed left to right as the host
+// loop of ground_run sums them (the library is built with floating-point contraction off).  The erase order stays on the host.
+__global__ __launch_bounds__(256) void ground_below_kernel(const float4* __restrict__ pts, int n, const GroundFit* __restrict__ fit, unsigned char* __restrict__ below) {
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i >= n) return;
+  const float4 p = pts[i];
+  const double x = p.x, y = p.y, z = p.z;
+  const double dist = fit->normal[0] * x + fit->normal[1] * y + fit->normal[2] * z + fit->d;
+  below[i] = dist < -1.0 ? 1 : 0;
+}
+
 }  // namespace gorio
 
 // ================================================================================================ host side (include/gorio_ground.h)
@@ -929,9 +948,16 @@ void ground_decide(gorio_ground* h, const gorio::GroundPatch* rec, const int* pi
   h->fdiag.n_ground = (int)ground.size();
 }
 
+// one scan as float columns on the device (the scan pipeline): ground_run then reads no host point and uploads none
+struct GroundDeviceScan {
+  const float *x, *y, *z, *inten;
+};
+
+// dev != nullptr (count == 1): the scan is *dev, its coordinates finite by construction; xyz / inten / stride are not read
 int ground_run(gorio_ground* const* hs, int count, const float* const* xyz, const float* const* inten, const int* n, const int* stride, int id, int* const* order_out,
-               int* n_ground, int* n_out) {
-  if (!hs || count <= 0 || !xyz || !inten || !n || !stride || !order_out || !n_ground || !n_out) return ground_fail(GORIO_ERR_INVALID, "estimate: null argument");
+               int* n_ground, int* n_out, const GroundDeviceScan* dev = nullptr) {
+  if (dev && count != 1) return ground_fail(GORIO_ERR_INVALID, "estimate: a device scan is one scan");
+  if (!hs || count <= 0 || (!dev && (!xyz || !inten || !stride)) || !n || !order_out || !n_ground || !n_out) return ground_fail(GORIO_ERR_INVALID, "estimate: null argument");
   if (id != 0 && id != 1) return ground_fail(GORIO_ERR_INVALID, "estimate: id must be 0 (estimate_plane) or 1 (estimate_plane_cov)");
   gorio_ground* lead = hs[0];
   if (!lead) return ground_fail(GORIO_ERR_INVALID, "estimate: null handle at index 0");
@@ -942,9 +968,10 @@ int ground_run(gorio_ground* const* hs, int count, const float* const* xyz, cons
     if (!hs[q]) return ground_fail(GORIO_ERR_INVALID, "estimate: null handle" + at);
     if (hs[q]->device != lead->device) return ground_fail(GORIO_ERR_INVALID, "estimate: all handles of a batch must live on one device" + at);
     if (!distinct.insert(hs[q]).second) return ground_fail(GORIO_ERR_INVALID, "estimate: the same handle appears twice in a batch" + at);
-    if (!xyz[q] || !inten[q] || !order_out[q] || n[q] <= 0 || stride[q] < 12 || stride[q] % 4) return ground_fail(GORIO_ERR_INVALID, "estimate: bad cloud arguments" + at);
-    const size_t st = stride[q] / 4;
-    for (int i = 0; i < n[q]; ++i) {
+    if (dev ? (!order_out[q] || n[q] <= 0) : (!xyz[q] || !inten[q] || !order_out[q] || n[q] <= 0 || stride[q] < 12 || stride[q] % 4))
+      return ground_fail(GORIO_ERR_INVALID, "estimate: bad cloud arguments" + at);
+    const size_t st = dev ? 0 : stride[q] / 4;
+    for (int i = 0; !dev && i < n[q]; ++i) {
       const float* pt = xyz[q] + st * i;
       if (!std::isfinite(pt[0]) || !std::isfinite(pt[1]) || !std::isfinite(pt[2])) return ground_fail(GORIO_ERR_INVALID, "estimate: non-finite coordinate at point " + std::to_string(i) + at);
     }
@@ -960,15 +987,15 @@ int ground_run(gorio_ground* const* hs, int count, const float* const* xyz, cons
   }
   GORIO_HIP_CHECK(ground_fail, gorio::reserve_group(lead->rec_cap, ptot, ptot, lead->d_rec, ptot, lead->d_blk, ptot));
   GORIO_HIP_CHECK(ground_fail, gorio::reserve_group(lead->frame_cap, count, count, lead->d_frames, count, lead->d_final, count, lead->d_fit, count));
-  std::vector<float4> pts(ntot);
+  std::vector<float4> pts(dev ? 0 : ntot);
   std::vector<gorio::GroundFrame> fr(count);
   std::vector<int2> blk;
   blk.reserve(ptot);
   int pt_off = 0, patch_off = 0, max_n = 0;
   for (int q = 0; q < count; ++q) {
     const gorio_ground* h = hs[q];
-    const size_t st = stride[q] / 4, si = stride[q] / 4;
-    for (int i = 0; i < n[q]; ++i) {
+    const size_t st = dev ? 0 : stride[q] / 4, si = st;
+    for (int i = 0; !dev && i < n[q]; ++i) {
       const float* pt = xyz[q] + st * i;
       pts[pt_off + i] = make_float4(pt[0], pt[1], pt[2], inten[q][si * i]);
     }
@@ -1005,7 +1032,12 @@ int ground_run(gorio_ground* const* hs, int count, const float* const* xyz, cons
     max_n = std::max(max_n, n[q]);
   }
   hipStream_t st = lead->stream;
-  GORIO_HIP_CHECK(ground_fail, hipMemcpyAsync(lead->d_pts, pts.data(), sizeof(float4) * ntot, hipMemcpyHostToDevice, st));
+  if (dev) {
+    gorio::ground_pack_kernel<<<(n[0] + 255) / 256, 256, 0, st>>>(dev->x, dev->y, dev->z, dev->inten, n[0], lead->d_pts);
+    GORIO_HIP_CHECK(ground_fail, hipGetLastError());
+  } else {
+    GORIO_HIP_CHECK(ground_fail, hipMemcpyAsync(lead->d_pts, pts.data(), sizeof(float4) * ntot, hipMemcpyHostToDevice, st));
+  }
   GORIO_HIP_CHECK(ground_fail, hipMemcpyAsync(lead->d_frames, fr.data(), sizeof(gorio::GroundFrame) * count, hipMemcpyHostToDevice, st));
   GORIO_HIP_CHECK(ground_fail, hipMemcpyAsync(lead->d_blk, blk.data(), sizeof(int2) * ptot, hipMemcpyHostToDevice, st));
   gorio::ground_classify_kernel<<<dim3((max_n + 255) / 256, count), 256, 0, st>>>(lead->d_frames, lead->d_pts, lead->d_pid, lead->d_C6);
@@ -1048,6 +1080,13 @@ int ground_run(gorio_ground* const* hs, int count, const float* const* xyz, cons
   GORIO_HIP_CHECK(ground_fail, hipGetLastError());
   std::vector<gorio::GroundFit> fits(count);
   GORIO_HIP_CHECK(ground_fail, hipMemcpyAsync(fits.data(), lead->d_fit, sizeof(gorio::GroundFit) * count, hipMemcpyDeviceToHost, st));
+  std::vector<unsigned char> below;  // a device scan: the under-ground test of every point (d_mask is free again, its patch flags are on the host)
+  if (dev) {
+    below.resize(ntot);
+    gorio::ground_below_kernel<<<(n[0] + 255) / 256, 256, 0, st>>>(lead->d_pts, n[0], lead->d_fit, lead->d_mask);
+    GORIO_HIP_CHECK(ground_fail, hipGetLastError());
+    GORIO_HIP_CHECK(ground_fail, hipMemcpyAsync(below.data(), lead->d_mask, ntot, hipMemcpyDeviceToHost, st));
+  }
   GORIO_HIP_CHECK(ground_fail, hipStreamSynchronize(st));
   for (int q = 0; q < count; ++q) {
     gorio_ground* h = hs[q];
@@ -1066,9 +1105,11 @@ int ground_run(gorio_ground* const* hs, int count, const float* const* xyz, cons
     D.final_d = F.d;
     // PWP:872-884: erase(begin + i) while i still advances, so the point after an erased one is never tested
     std::vector<int>& ng = nongrounds[q];
-    const float* base = xyz[q];
-    const size_t sp = stride[q] / 4;
-    for (size_t i = 0; i < ng.size(); ++i) {
+    for (size_t i = 0; dev && i < ng.size(); ++i)
+      if (below[ng[i]]) ng.erase(ng.begin() + i);
+    const float* base = dev ? nullptr : xyz[q];
+    const size_t sp = dev ? 0 : stride[q] / 4;
+    for (size_t i = 0; !dev && i < ng.size(); ++i) {
       const float* pt = base + sp * ng[i];
       const double x = pt[0], y = pt[1], z = pt[2];
       const double dist = F.normal[0] * x + F.normal[1] * y + F.normal[2] * z + F.d;

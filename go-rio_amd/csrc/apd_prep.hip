@@ -188,6 +188,25 @@ __global__ __launch_bounds__(256) void sor_mean_distance_kernel(CloudView cloud,
   }
 }
 
+// PREP:539-548 for a cloud that lives on the device: the float coordinate sums of every cluster, its members added one after the other in
+// ascending index order exactly as the host loop of gorio_prep_dbscan_labels adds them.  One lane = one cluster (there are tens of them);
+// grid: ceil(nc / 64), block 64.
+__global__ __launch_bounds__(64) void cluster_sums_kernel(const float* __restrict__ x, const float* __restrict__ y, const float* __restrict__ z, const int* __restrict__ members,
+                                                          const int* __restrict__ offs, int nc, float* __restrict__ sums) {
+  const int c = blockIdx.x * 64 + threadIdx.x;
+  if (c >= nc) return;
+  float sx = 0.f, sy = 0.f, sz = 0.f;
+  for (int e = offs[c]; e < offs[c + 1]; ++e) {
+    const int idx = members[e];
+    sx += x[idx];
+    sy += y[idx];
+    sz += z[idx];
+  }
+  sums[3 * c] = sx;
+  sums[3 * c + 1] = sy;
+  sums[3 * c + 2] = sz;
+}
+
 }  // namespace gorio
 
 // ----------------------------------------------------------------------------------------------- REVE Doppler ego-velocity
@@ -204,11 +223,12 @@ struct ReveCfg {
 };
 
 // grid: ceil(n / 256).  f[i][4] = x/r, y/r, z/r, corrected doppler; valid[i]
-__global__ __launch_bounds__(256) void reve_features_kernel(const float* __restrict__ xyz, const float* __restrict__ inten, const float* __restrict__ dop, int stride, int n, ReveCfg c,
-                                                            double* __restrict__ f, unsigned char* __restrict__ valid) {
+// px / py / pz: first x, y, z; `stride` floats between targets (5 for the packed upload of gorio_prep_ego_velocity, 1 for device columns)
+__global__ __launch_bounds__(256) void reve_features_kernel(const float* __restrict__ px, const float* __restrict__ py, const float* __restrict__ pz, const float* __restrict__ inten,
+                                                            const float* __restrict__ dop, int stride, int n, ReveCfg c, double* __restrict__ f, unsigned char* __restrict__ valid) {
   const int i = blockIdx.x * 256 + threadIdx.x;
   if (i >= n) return;
-  const float x = xyz[(size_t)i * stride], y = xyz[(size_t)i * stride + 1], z = xyz[(size_t)i * stride + 2];
+  const float x = px[(size_t)i * stride], y = py[(size_t)i * stride], z = pz[(size_t)i * stride];
   const double r = sqrt((double)x * (double)x + (double)y * (double)y + (double)z * (double)z);  // Vector3(x, y, z).norm(), REVE:78
   const double azimuth = (double)(float)atan2((double)y, (double)x);                           // atan2(float, float), REVE:80
   float rxy2 = x * x;
@@ -291,9 +311,9 @@ struct PrepCtx {  // per thread: a private registration handle serves as the dev
 };
 thread_local PrepCtx g_prep;
 
-// the thread's context, ready for `device`; nullptr (and `rc`, the error recorded) when the device is not usable
-PrepCtx* prep_context(int device, const char* who, int& rc) {
-  PrepCtx& c = g_prep;
+// a context (the thread's, or the one a scan pipeline owns), ready for `device`; nullptr (and `rc`, the error recorded) when the device
+// is not usable
+PrepCtx* prep_context(PrepCtx& c, int device, const char* who, int& rc) {
   rc = GORIO_OK;
   if (!c.h || c.device != device) {
     c.reset();
@@ -306,6 +326,18 @@ PrepCtx* prep_context(int device, const char* who, int& rc) {
   }
   return &c;
 }
+PrepCtx* prep_context(int device, const char* who, int& rc) { return prep_context(g_prep, device, who, rc); }
+
+// the source of the context's handle gets its search index built and one d_cnt / d_offs slot per point
+int prep_index_source(PrepCtx& c, int n) {
+  gorio_apd* h = c.h;
+  std::vector<std::pair<gorio_apd*, DevCloud*>> one = {{h, h->src.get()}};
+  int rc = run_index_build(h, one);
+  if (rc) return prep_fail(rc, h->err);
+  const size_t cap = (size_t)n + n / 8;
+  GORIO_HIP_CHECK(prep_fail, reserve_group(c.pts_cap, n, cap, c.d_cnt, cap, c.d_offs, cap));
+  return GORIO_OK;
+}
 
 // the cloud becomes the source of the context's handle, with its search index built and one d_cnt / d_offs slot per point
 int prep_index_cloud(PrepCtx& c, const float* xyz, int n, int point_stride_bytes) {
@@ -313,29 +345,24 @@ int prep_index_cloud(PrepCtx& c, const float* xyz, int n, int point_stride_bytes
   h->params.search = GORIO_SEARCH_PRUNED;
   int rc = gorio_apd_set_source(h, xyz, nullptr, n, point_stride_bytes);
   if (rc) return prep_fail(rc, h->err);
-  std::vector<std::pair<gorio_apd*, DevCloud*>> one = {{h, h->src.get()}};
-  rc = run_index_build(h, one);
-  if (rc) return prep_fail(rc, h->err);
-  const size_t cap = (size_t)n + n / 8;
-  GORIO_HIP_CHECK(prep_fail, reserve_group(c.pts_cap, n, cap, c.d_cnt, cap, c.d_offs, cap));
-  return GORIO_OK;
+  return prep_index_source(c, n);
 }
-}  // namespace
 
-extern "C" {
+// the same for a cloud that already lives on the device as three columns (include/gorio_scan.h): no host copy is made
+int prep_index_cloud_device(PrepCtx& c, const float* dx, const float* dy, const float* dz, int n) {
+  gorio_apd* h = c.h;
+  h->params.search = GORIO_SEARCH_PRUNED;
+  int rc = gorio_apd_set_source_device(h, dx, dy, dz, nullptr, n);
+  if (rc) return prep_fail(rc, h->err);
+  return prep_index_source(c, n);
+}
 
-const char* gorio_prep_last_error(void) { return g_prep_err.c_str(); }
+// ---- the stages proper, on the indexed source of the context's handle.  The public entry points below and the scan pipeline
+// (apd_scan.hip) both run these; what differs is only where the cloud came from.
 
-int gorio_prep_dbscan_labels(int device, const float* xyz, int n, int point_stride_bytes, double eps, int core_min_pts, int min_cluster_size, int max_cluster_size,
-                             float* label_out, int label_stride_bytes, int* n_clusters) {
-  if (!xyz || !label_out || n <= 0 || point_stride_bytes < 12 || (point_stride_bytes % 4) || label_stride_bytes < 4 || (label_stride_bytes % 4))
-    return prep_fail(GORIO_ERR_INVALID, "dbscan_labels: bad arguments");
-  int rc = GORIO_OK;
-  PrepCtx* ctx = prep_context(device, "dbscan_labels", rc);
-  if (!ctx) return rc;
-  PrepCtx& c = *ctx;
-  rc = prep_index_cloud(c, xyz, n, point_stride_bytes);
-  if (rc) return rc;
+// DBS:28-100: the radius searches on the device, the queue replayed over their adjacency; clusters in the order the queue closes them,
+// members sorted (DBS:91)
+int prep_dbscan_clusters(PrepCtx& c, int n, double eps, int core_min_pts, int min_cluster_size, int max_cluster_size, std::vector<std::vector<int>>& clusters) {
   gorio_apd* h = c.h;
   const CloudView cv = h->src->view();
   const int grid = (roundup(n, 512) + 255) / 256;
@@ -362,7 +389,7 @@ int gorio_prep_dbscan_labels(int device, const float* xyz, int n, int point_stri
   enum : unsigned char { UN = 0, PROCESSING = 1, PROCESSED = 2 };
   std::vector<unsigned char> types((size_t)n, UN), noise((size_t)n, 0);
   std::vector<int> queue;
-  std::vector<std::vector<int>> clusters;
+  clusters.clear();
   auto seed_count = [&](int i) { return cnt[i]; };  // |N(i, seed radius)|, the point itself included
   auto exp_count = [&](int i) {
     int k = 0;
@@ -408,41 +435,27 @@ int gorio_prep_dbscan_labels(int device, const float* xyz, int n, int point_stri
     }
     if ((int)queue.size() >= min_cluster_size && (int)queue.size() <= max_cluster_size) clusters.push_back(queue);  // DBS:83-95
   }
-  // ---- preprocessing_nodelet_ntu.cpp:533-568: rank the clusters by the distance of their centroid, write rank + 1
-  const int st = point_stride_bytes / 4, lst = label_stride_bytes / 4;
-  for (int i = 0; i < n; ++i) label_out[(size_t)i * lst] = 0.0f;
+  for (std::vector<int>& m : clusters) std::sort(m.begin(), m.end());  // DBS:91
+  return GORIO_OK;
+}
+
+// PREP:550-568 from the float coordinate sums of the clusters (sums[c][3], PREP:539-548): rank[c] = position of cluster c when the
+// clusters are ordered by the distance of their centroid
+void prep_rank_clusters(const std::vector<std::vector<int>>& clusters, const float* sums, std::vector<int>& order) {
   const int nc = (int)clusters.size();
   std::vector<float> dist((size_t)nc);
-  std::vector<int> order((size_t)nc);
+  order.resize((size_t)nc);
   for (int cidx = 0; cidx < nc; ++cidx) {
-    std::vector<int>& m = clusters[cidx];
-    std::sort(m.begin(), m.end());  // DBS:91
-    float sx = 0.f, sy = 0.f, sz = 0.f;
-    for (int idx : m) {
-      const float* p = xyz + (size_t)idx * st;
-      sx += p[0]; sy += p[1]; sz += p[2];
-    }
-    const int num = (int)m.size();
-    const float cx = sx / num, cy = sy / num, cz = sz / num;
+    const int num = (int)clusters[cidx].size();
+    const float cx = sums[3 * cidx] / num, cy = sums[3 * cidx + 1] / num, cz = sums[3 * cidx + 2] / num;
     dist[cidx] = (float)std::sqrt((double)cx * cx + (double)cy * cy + (double)cz * cz);  // std::hypot(float, float, float)
     order[cidx] = cidx;
   }
   std::stable_sort(order.begin(), order.end(), [&](int a, int b) { return dist[a] < dist[b]; });
-  for (int r = 0; r < nc; ++r)
-    for (int idx : clusters[order[r]]) label_out[(size_t)idx * lst] = (float)(r + 1);
-  if (n_clusters) *n_clusters = nc;
-  return GORIO_OK;
 }
 
-int gorio_prep_radius_outlier_mask(int device, const float* xyz, int n, int point_stride_bytes, double radius, int min_neighbors, unsigned char* keep, int* n_kept) {
-  if (!xyz || !keep || n <= 0 || point_stride_bytes < 12 || (point_stride_bytes % 4) || !(radius > 0.0) || min_neighbors < 0)
-    return prep_fail(GORIO_ERR_INVALID, "radius_outlier_mask: bad arguments");
-  int rc = GORIO_OK;
-  PrepCtx* ctx = prep_context(device, "radius_outlier_mask", rc);
-  if (!ctx) return rc;
-  PrepCtx& c = *ctx;
-  rc = prep_index_cloud(c, xyz, n, point_stride_bytes);
-  if (rc) return rc;
+// pcl::RadiusOutlierRemoval: the neighbour counts of every point of the indexed source, then the mask
+int prep_radius_outlier_keep(PrepCtx& c, int n, double radius, int min_neighbors, unsigned char* keep, int* n_kept) {
   gorio_apd* h = c.h;
   const double r2d = radius * radius;
   float r2 = FLT_MAX;
@@ -464,17 +477,8 @@ int gorio_prep_radius_outlier_mask(int device, const float* xyz, int n, int poin
   return GORIO_OK;
 }
 
-int gorio_prep_statistical_outlier_mask(int device, const float* xyz, int n, int point_stride_bytes, int mean_k, double stddev_mul, unsigned char* keep, int* n_kept,
-                                        float* mean_dist_out) {
-  if (!xyz || !keep || n <= 0 || point_stride_bytes < 12 || (point_stride_bytes % 4) || mean_k < 1 || mean_k > 31)
-    return prep_fail(GORIO_ERR_INVALID, "statistical_outlier_mask: bad arguments (mean_k must lie in [1, 31])");
-  if (n < mean_k + 1) return prep_fail(GORIO_ERR_INVALID, "statistical_outlier_mask: fewer points than mean_k + 1 (PCL then sums distances nearestKSearch never set)");
-  int rc = GORIO_OK;
-  PrepCtx* ctx = prep_context(device, "statistical_outlier_mask", rc);
-  if (!ctx) return rc;
-  PrepCtx& c = *ctx;
-  rc = prep_index_cloud(c, xyz, n, point_stride_bytes);
-  if (rc) return rc;
+// pcl::StatisticalOutlierRemoval: the mean neighbour distance of every point of the indexed source, then threshold and mask
+int prep_statistical_outlier_keep(PrepCtx& c, int n, int mean_k, double stddev_mul, unsigned char* keep, int* n_kept, float* mean_dist_out) {
   gorio_apd* h = c.h;
   float* d_mean = reinterpret_cast<float*>(c.d_cnt.get());  // one 4-byte word per point, like the neighbour counts
   sor_mean_distance_kernel<<<(roundup(n, 512) + 255) / 256, 256, 0, h->stream>>>(h->src->view(), mean_k + 1, d_mean);
@@ -501,6 +505,73 @@ int gorio_prep_statistical_outlier_mask(int device, const float* xyz, int n, int
   }
   if (n_kept) *n_kept = kept;
   return GORIO_OK;
+}
+
+const char* const kSorTooFew = "statistical_outlier_mask: fewer points than mean_k + 1 (PCL then sums distances nearestKSearch never set)";
+}  // namespace
+
+extern "C" {
+
+const char* gorio_prep_last_error(void) { return g_prep_err.c_str(); }
+
+int gorio_prep_dbscan_labels(int device, const float* xyz, int n, int point_stride_bytes, double eps, int core_min_pts, int min_cluster_size, int max_cluster_size,
+                             float* label_out, int label_stride_bytes, int* n_clusters) {
+  if (!xyz || !label_out || n <= 0 || point_stride_bytes < 12 || (point_stride_bytes % 4) || label_stride_bytes < 4 || (label_stride_bytes % 4))
+    return prep_fail(GORIO_ERR_INVALID, "dbscan_labels: bad arguments");
+  int rc = GORIO_OK;
+  PrepCtx* ctx = prep_context(device, "dbscan_labels", rc);
+  if (!ctx) return rc;
+  PrepCtx& c = *ctx;
+  rc = prep_index_cloud(c, xyz, n, point_stride_bytes);
+  if (rc) return rc;
+  std::vector<std::vector<int>> clusters;
+  rc = prep_dbscan_clusters(c, n, eps, core_min_pts, min_cluster_size, max_cluster_size, clusters);
+  if (rc) return rc;
+  // ---- preprocessing_nodelet_ntu.cpp:533-568: rank the clusters by the distance of their centroid, write rank + 1
+  const int st = point_stride_bytes / 4, lst = label_stride_bytes / 4;
+  for (int i = 0; i < n; ++i) label_out[(size_t)i * lst] = 0.0f;
+  const int nc = (int)clusters.size();
+  std::vector<float> sums((size_t)nc * 3);
+  for (int cidx = 0; cidx < nc; ++cidx) {
+    float sx = 0.f, sy = 0.f, sz = 0.f;
+    for (int idx : clusters[cidx]) {
+      const float* p = xyz + (size_t)idx * st;
+      sx += p[0]; sy += p[1]; sz += p[2];
+    }
+    sums[3 * (size_t)cidx] = sx; sums[3 * (size_t)cidx + 1] = sy; sums[3 * (size_t)cidx + 2] = sz;
+  }
+  std::vector<int> order;
+  prep_rank_clusters(clusters, sums.data(), order);
+  for (int r = 0; r < nc; ++r)
+    for (int idx : clusters[order[r]]) label_out[(size_t)idx * lst] = (float)(r + 1);
+  if (n_clusters) *n_clusters = nc;
+  return GORIO_OK;
+}
+
+int gorio_prep_radius_outlier_mask(int device, const float* xyz, int n, int point_stride_bytes, double radius, int min_neighbors, unsigned char* keep, int* n_kept) {
+  if (!xyz || !keep || n <= 0 || point_stride_bytes < 12 || (point_stride_bytes % 4) || !(radius > 0.0) || min_neighbors < 0)
+    return prep_fail(GORIO_ERR_INVALID, "radius_outlier_mask: bad arguments");
+  int rc = GORIO_OK;
+  PrepCtx* ctx = prep_context(device, "radius_outlier_mask", rc);
+  if (!ctx) return rc;
+  PrepCtx& c = *ctx;
+  rc = prep_index_cloud(c, xyz, n, point_stride_bytes);
+  if (rc) return rc;
+  return prep_radius_outlier_keep(c, n, radius, min_neighbors, keep, n_kept);
+}
+
+int gorio_prep_statistical_outlier_mask(int device, const float* xyz, int n, int point_stride_bytes, int mean_k, double stddev_mul, unsigned char* keep, int* n_kept,
+                                        float* mean_dist_out) {
+  if (!xyz || !keep || n <= 0 || point_stride_bytes < 12 || (point_stride_bytes % 4) || mean_k < 1 || mean_k > 31)
+    return prep_fail(GORIO_ERR_INVALID, "statistical_outlier_mask: bad arguments (mean_k must lie in [1, 31])");
+  if (n < mean_k + 1) return prep_fail(GORIO_ERR_INVALID, kSorTooFew);
+  int rc = GORIO_OK;
+  PrepCtx* ctx = prep_context(device, "statistical_outlier_mask", rc);
+  if (!ctx) return rc;
+  PrepCtx& c = *ctx;
+  rc = prep_index_cloud(c, xyz, n, point_stride_bytes);
+  if (rc) return rc;
+  return prep_statistical_outlier_keep(c, n, mean_k, stddev_mul, keep, n_kept, mean_dist_out);
 }
 
 int gorio_prep_voxel_downsample(int device, const float* xyz, int n, int point_stride_bytes, double leaf, float* xyz_out, int out_stride_bytes, int out_capacity, int* n_out) {
@@ -585,33 +656,17 @@ struct ReveCtx {  // per thread; move-assigning a new one frees what the old one
 };
 thread_local ReveCtx g_reve;
 
-}  // namespace
+struct ReveFrame {  // what the gates of REVE:75-90 left of one scan: the rows of the valid targets, in input order
+  int n = 0, m = 0;
+  std::vector<int> vidx;    // [m] input index of each valid target
+  std::vector<double> fv;   // [m][4] x/r, y/r, z/r, corrected doppler
+};
 
-extern "C" {
-
-void gorio_prep_reve_default_config(gorio_reve_config* c) {  // radar_ego_velocity_estimator.h:30-60
-  if (!c) return;
-  std::memset(c, 0, sizeof(*c));
-  c->min_dist = 1; c->max_dist = 400; c->min_db = 0; c->elevation_thresh_deg = 22.5f; c->azimuth_thresh_deg = 56.5f; c->doppler_velocity_correction_factor = 1;
-  c->thresh_zero_velocity = 0.05f; c->allowed_outlier_percentage = 0.30f; c->sigma_zero_velocity_x = 1.0e-03f; c->sigma_zero_velocity_y = 3.2e-03f; c->sigma_zero_velocity_z = 1.0e-02f;
-  c->max_sigma_x = 0.2f; c->max_sigma_y = 0.2f; c->max_sigma_z = 0.2f; c->inlier_thresh = 0.5f; c->use_ransac = 1; c->n_ransac_points = 5;
-  c->outlier_prob = 0.05f; c->success_prob = 0.995f;
-}
-
-int gorio_prep_reve_ransac_iterations(const gorio_reve_config* c) {  // setRansacIter, radar_ego_velocity_estimator.h:138-141
-  if (!c) return 0;
-  return (int)(unsigned int)((std::log(1.0 - c->success_prob)) / std::log(1.0 - std::pow(1.0 - c->outlier_prob, (float)c->n_ransac_points)));
-}
-
-int gorio_prep_ego_velocity(int device, const float* xyz, const float* intensity, const float* doppler, int n, int stride_bytes, const gorio_reve_config* cfg,
-                            const unsigned int* sample_idx, int n_iter, double v_r[3], double sigma_v_r[3], unsigned char* inlier_mask, unsigned char* outlier_mask,
-                            int* n_valid, int* zero_velocity, int* success) {
-  if (!xyz || !intensity || !doppler || !cfg || !v_r || !sigma_v_r || n <= 0 || stride_bytes < 4 || (stride_bytes % 4) || n_iter < 0 || (n_iter > 0 && !sample_idx) || cfg->n_ransac_points < 3 || cfg->n_ransac_points > 64)
-    return prep_fail(GORIO_ERR_INVALID, "ego_velocity: bad arguments");
+// the context becomes this device's, with room for n targets
+int reve_prepare(ReveCtx& c, int device, int n) {
   int ndev = 0;
   if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return prep_fail(GORIO_ERR_NO_DEVICE, "ego_velocity: no usable HIP device (there is no CPU fallback)");
   if (device < 0 || device >= ndev) return prep_fail(GORIO_ERR_INVALID, "ego_velocity: bad device ordinal");
-  ReveCtx& c = g_reve;
   if (c.device >= 0 && c.device != device) {  // a context of another device: a plain reset, its buffers free on their own device
     hipSetDevice(c.device);
     c = ReveCtx();
@@ -623,42 +678,47 @@ int gorio_prep_ego_velocity(int device, const float* xyz, const float* intensity
     GORIO_HIP_CHECK(prep_fail, c.d_v.reserve(3 * 64));
     c.device = device;
   }
-  {
-    const size_t cap = (size_t)n + n / 8;
-    GORIO_HIP_CHECK(prep_fail, reserve_group(c.cap, n, cap, c.d_in, 5 * cap, c.d_f, 4 * cap, c.d_fv, 4 * cap, c.d_valid, cap, c.d_out, 10 * (cap / 256 + 2)));
-  }
-  // ---- per-target features on the device
-  const int st = stride_bytes / 4;
-  std::vector<float> in((size_t)n * 5);
-  for (int i = 0; i < n; ++i) {
-    in[5 * (size_t)i] = xyz[(size_t)i * st]; in[5 * (size_t)i + 1] = xyz[(size_t)i * st + 1]; in[5 * (size_t)i + 2] = xyz[(size_t)i * st + 2];
-    in[5 * (size_t)i + 3] = intensity[(size_t)i * st]; in[5 * (size_t)i + 4] = doppler[(size_t)i * st];
-  }
-  GORIO_HIP_CHECK(prep_fail, hipMemcpyAsync(c.d_in, in.data(), sizeof(float) * in.size(), hipMemcpyHostToDevice, c.stream));
+  const size_t cap = (size_t)n + n / 8;
+  GORIO_HIP_CHECK(prep_fail, reserve_group(c.cap, n, cap, c.d_in, 5 * cap, c.d_f, 4 * cap, c.d_fv, 4 * cap, c.d_valid, cap, c.d_out, 10 * (cap / 256 + 2)));
+  return GORIO_OK;
+}
+
+// REVE:75-90 for n targets on the device (px / py / pz / inten / dop with `stride` floats between targets): features and gates there,
+// the rows of the valid targets collected here
+int reve_features(ReveCtx& c, const float* px, const float* py, const float* pz, const float* inten, const float* dop, int stride, int n, const gorio_reve_config* cfg, ReveFrame& fr) {
   ReveCfg rc;
   rc.min_dist = cfg->min_dist; rc.max_dist = cfg->max_dist; rc.min_db = cfg->min_db;
   rc.az_lim = (double)cfg->azimuth_thresh_deg * M_PI / 180.0; rc.el_lim = (double)cfg->elevation_thresh_deg * M_PI / 180.0;  // angles::from_degrees
   rc.doppler_factor_unused = 0; rc.doppler_factor = cfg->doppler_velocity_correction_factor; rc.pad_ = 0;
-  reve_features_kernel<<<(n + 255) / 256, 256, 0, c.stream>>>(c.d_in, c.d_in + 3, c.d_in + 4, 5, n, rc, c.d_f, c.d_valid);
+  reve_features_kernel<<<(n + 255) / 256, 256, 0, c.stream>>>(px, py, pz, inten, dop, stride, n, rc, c.d_f, c.d_valid);
   GORIO_HIP_CHECK(prep_fail, hipGetLastError());
   std::vector<double> f((size_t)n * 4);
   std::vector<unsigned char> valid((size_t)n);
   GORIO_HIP_CHECK(prep_fail, hipMemcpyAsync(f.data(), c.d_f, sizeof(double) * f.size(), hipMemcpyDeviceToHost, c.stream));
   GORIO_HIP_CHECK(prep_fail, hipMemcpyAsync(valid.data(), c.d_valid, (size_t)n, hipMemcpyDeviceToHost, c.stream));
   GORIO_HIP_CHECK(prep_fail, hipStreamSynchronize(c.stream));
-  std::vector<int> vidx;
-  std::vector<double> fv;
+  fr.n = n;
+  fr.vidx.clear();
+  fr.fv.clear();
   for (int i = 0; i < n; ++i)
     if (valid[i]) {
-      vidx.push_back(i);
-      fv.insert(fv.end(), f.begin() + 4 * (size_t)i, f.begin() + 4 * (size_t)i + 4);
+      fr.vidx.push_back(i);
+      fr.fv.insert(fr.fv.end(), f.begin() + 4 * (size_t)i, f.begin() + 4 * (size_t)i + 4);
     }
-  const int m = (int)vidx.size();
+  fr.m = (int)fr.vidx.size();
+  return GORIO_OK;
+}
+
+// REVE:92-170 over the valid targets of `fr`: zero-velocity test, least squares, RANSAC
+int reve_solve(ReveCtx& c, const gorio_reve_config* cfg, const ReveFrame& fr, const unsigned int* sample_idx, int n_iter, double v_r[3], double sigma_v_r[3],
+               unsigned char* inlier_mask, unsigned char* outlier_mask, int* zero_velocity, int* success) {
+  const int n = fr.n, m = fr.m;
+  const std::vector<int>& vidx = fr.vidx;
+  const std::vector<double>& fv = fr.fv;
   if (inlier_mask) std::memset(inlier_mask, 0, (size_t)n);
   if (outlier_mask) std::memset(outlier_mask, 0, (size_t)n);
   v_r[0] = v_r[1] = v_r[2] = 0.0;
   sigma_v_r[0] = sigma_v_r[1] = sigma_v_r[2] = 0.0;
-  if (n_valid) *n_valid = m;
   if (zero_velocity) *zero_velocity = 0;
   int ok = 0;
   // solve3DFull (REVE:252-303) over the valid rows selected by `sel`: sums on the device, 3 x 3 algebra here
@@ -767,6 +827,47 @@ int gorio_prep_ego_velocity(int device, const float* xyz, const float* intensity
   }
   if (success) *success = ok;
   return GORIO_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+void gorio_prep_reve_default_config(gorio_reve_config* c) {  // radar_ego_velocity_estimator.h:30-60
+  if (!c) return;
+  std::memset(c, 0, sizeof(*c));
+  c->min_dist = 1; c->max_dist = 400; c->min_db = 0; c->elevation_thresh_deg = 22.5f; c->azimuth_thresh_deg = 56.5f; c->doppler_velocity_correction_factor = 1;
+  c->thresh_zero_velocity = 0.05f; c->allowed_outlier_percentage = 0.30f; c->sigma_zero_velocity_x = 1.0e-03f; c->sigma_zero_velocity_y = 3.2e-03f; c->sigma_zero_velocity_z = 1.0e-02f;
+  c->max_sigma_x = 0.2f; c->max_sigma_y = 0.2f; c->max_sigma_z = 0.2f; c->inlier_thresh = 0.5f; c->use_ransac = 1; c->n_ransac_points = 5;
+  c->outlier_prob = 0.05f; c->success_prob = 0.995f;
+}
+
+int gorio_prep_reve_ransac_iterations(const gorio_reve_config* c) {  // setRansacIter, radar_ego_velocity_estimator.h:138-141
+  if (!c) return 0;
+  return (int)(unsigned int)((std::log(1.0 - c->success_prob)) / std::log(1.0 - std::pow(1.0 - c->outlier_prob, (float)c->n_ransac_points)));
+}
+
+int gorio_prep_ego_velocity(int device, const float* xyz, const float* intensity, const float* doppler, int n, int stride_bytes, const gorio_reve_config* cfg,
+                            const unsigned int* sample_idx, int n_iter, double v_r[3], double sigma_v_r[3], unsigned char* inlier_mask, unsigned char* outlier_mask,
+                            int* n_valid, int* zero_velocity, int* success) {
+  if (!xyz || !intensity || !doppler || !cfg || !v_r || !sigma_v_r || n <= 0 || stride_bytes < 4 || (stride_bytes % 4) || n_iter < 0 || (n_iter > 0 && !sample_idx) || cfg->n_ransac_points < 3 || cfg->n_ransac_points > 64)
+    return prep_fail(GORIO_ERR_INVALID, "ego_velocity: bad arguments");
+  ReveCtx& c = g_reve;
+  int rc = reve_prepare(c, device, n);
+  if (rc) return rc;
+  // ---- per-target features on the device
+  const int st = stride_bytes / 4;
+  std::vector<float> in((size_t)n * 5);
+  for (int i = 0; i < n; ++i) {
+    in[5 * (size_t)i] = xyz[(size_t)i * st]; in[5 * (size_t)i + 1] = xyz[(size_t)i * st + 1]; in[5 * (size_t)i + 2] = xyz[(size_t)i * st + 2];
+    in[5 * (size_t)i + 3] = intensity[(size_t)i * st]; in[5 * (size_t)i + 4] = doppler[(size_t)i * st];
+  }
+  GORIO_HIP_CHECK(prep_fail, hipMemcpyAsync(c.d_in, in.data(), sizeof(float) * in.size(), hipMemcpyHostToDevice, c.stream));
+  ReveFrame fr;
+  rc = reve_features(c, c.d_in, c.d_in + 1, c.d_in + 2, c.d_in + 3, c.d_in + 4, 5, n, cfg, fr);
+  if (rc) return rc;
+  if (n_valid) *n_valid = fr.m;
+  return reve_solve(c, cfg, fr, sample_idx, n_iter, v_r, sigma_v_r, inlier_mask, outlier_mask, zero_velocity, success);
 }
 
 }  // extern "C"

@@ -32,6 +32,7 @@
 #include <fast_gicp/gicp/gicp_settings.hpp>
 
 #include <gorio_apd.h>
+#include <gorio_scan.h>
 
 namespace fast_gicp {
 
@@ -260,6 +261,27 @@ public:
     pcl::Registration<PointSource, PointTarget, Scalar>::setInputTarget(owner.target_);
     lazy_tree_->defer(owner.target_);
     check(gorio_apd_set_target_shared(handle_, owner.handle_));
+    target_covs_.clear();
+    target_covs_fresh_ = false;
+  }
+  // The frame a gorio::ScanPreprocessor just produced (radar_preprocessing/scan_preprocessor.hpp) as source / target (extra): the
+  // device keeps the cloud and the search index the preprocessing built -- no upload, no new index (gorio_apd_set_source_from_scan).
+  // The pcl cloud that process() returned becomes input_ / target_, which pcl::Registration::align() insists on.  Afterwards the object
+  // is in the state setInputSource / setInputTarget leave it in for that cloud.
+  template <typename Preprocessor>
+  void setInputSourceFromScan(Preprocessor& pre) {
+    if (!pre.last_scan()) throw std::runtime_error("FastAPDGICP::setInputSourceFromScan: the preprocessor's last process() produced no frame");
+    check(gorio_apd_set_source_from_scan(handle_, pre.handle()));
+    pcl::Registration<PointSource, PointTarget, Scalar>::setInputSource(pre.last_scan());
+    source_covs_.clear();
+    source_covs_fresh_ = false;
+  }
+  template <typename Preprocessor>
+  void setInputTargetFromScan(Preprocessor& pre) {
+    if (!pre.last_scan()) throw std::runtime_error("FastAPDGICP::setInputTargetFromScan: the preprocessor's last process() produced no frame");
+    check(gorio_apd_set_target_from_scan(handle_, pre.handle()));
+    pcl::Registration<PointSource, PointTarget, Scalar>::setInputTarget(pre.last_scan());
+    lazy_tree_->defer(pre.last_scan());
     target_covs_.clear();
     target_covs_fresh_ = false;
   }

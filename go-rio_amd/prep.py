@@ -120,3 +120,128 @@ def ego_velocity(targets, samples, cfg=None, device=0):
         msg = lib.gorio_prep_last_error()
         raise GorioError(rc, msg.decode() if msg else "")
     return dict(success=bool(ok.value), v_r=v, sigma_v_r=sg, inlier=inl.astype(bool), outlier=outl.astype(bool), n_valid=nv.value, zero_velocity=bool(zv.value))
+
+
+# ------------------------------------------------------------------------------------------------ include/gorio_scan.h
+SCAN_SYMBOLS = ["gorio_scan_default_params", "gorio_scan_create", "gorio_scan_destroy", "gorio_scan_load", "gorio_scan_run", "gorio_scan_get_output", "gorio_scan_get_stage",
+                "gorio_scan_get_stage_points", "gorio_scan_get_counters", "gorio_scan_last_error", "gorio_apd_set_source_from_scan", "gorio_apd_set_target_from_scan"]
+OUTLIER_NONE, OUTLIER_STATISTICAL, OUTLIER_RADIUS = 0, 1, 2
+SCAN_OK, SCAN_ZERO_VELOCITY, SCAN_EMPTY, SCAN_REFUSED = 0, 1, 2, 3
+SCAN_STATUS = {0: "ok", 1: "zero_velocity", 2: "empty", 3: "refused"}
+STAGES = {"gate": 0, "dynamic": 1, "deskew": 2, "distance": 3, "outlier": 4, "ground": 5}
+SCAN_STAGE_DBSCAN = 6  # only a value of a result's "stage": the label stage puts out no cloud of its own
+
+
+def _scan_params_type():
+    from .ground import GroundParams
+
+    class ScanParams(C.Structure):
+        """gorio_scan_params (include/gorio_scan.h)."""
+        _fields_ = [("power_threshold", C.c_float), ("rotation", C.c_double * 9), ("enable_dynamic_object_removal", C.c_int), ("deskew", C.c_int), ("scan_period", C.c_double),
+                    ("distance_near", C.c_double), ("distance_far", C.c_double), ("z_low", C.c_double), ("z_high", C.c_double), ("outlier_method", C.c_int), ("mean_k", C.c_int),
+                    ("stddev_mul", C.c_double), ("radius", C.c_double), ("min_neighbors", C.c_int), ("ground", C.c_int), ("ground_params", GroundParams),
+                    ("dbscan_core_min_pts", C.c_int), ("dbscan_eps", C.c_double), ("dbscan_min_cluster_size", C.c_int), ("dbscan_max_cluster_size", C.c_int), ("reve", ReveConfig)]
+
+    return ScanParams
+
+
+ScanParams = _scan_params_type()
+
+
+class ScanResult(C.Structure):
+    _fields_ = [("status", C.c_int), ("stage", C.c_int), ("reve_success", C.c_int), ("v_r", C.c_double * 3), ("sigma_v_r", C.c_double * 3), ("n_out", C.c_int),
+                ("n_ground", C.c_int), ("n_clusters", C.c_int)]
+
+
+def scan_default_params(**kw):
+    p = ScanParams()
+    load_library().gorio_scan_default_params(C.byref(p))
+    for k, v in kw.items():
+        if k == "rotation":
+            p.rotation[:] = [float(x) for x in np.asarray(v, np.float64).reshape(9)]
+        else:
+            setattr(p, k, v)
+    return p
+
+
+def _ptr(a):
+    return C.c_void_p(a.__array_interface__["data"][0])
+
+
+class ScanPipeline:
+    """gorio_scan_t: the preprocessing nodelet's cloud_callback (preprocessing_nodelet_ntu.cpp:370-581) with the scan resident on the GPU.
+    One frame is load(raw) -> (n_gated, n_valid), then run(samples, ang_vel) -> dict; output() / stage() read results back."""
+
+    def __init__(self, params=None, device=0, **overrides):
+        self.lib = load_library()
+        self.lib.gorio_scan_last_error.restype = C.c_char_p
+        self.params = params if params is not None else scan_default_params(**overrides)
+        self.h = C.c_void_p()
+        self._check(self.lib.gorio_scan_create(C.byref(self.h), int(device), C.byref(self.params)))
+
+    def _check(self, rc):
+        if rc < 0:
+            msg = self.lib.gorio_scan_last_error()
+            raise GorioError(rc, msg.decode() if msg else "")
+
+    def close(self):
+        if self.h:
+            self.lib.gorio_scan_destroy(self.h)
+            self.h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def load(self, raw):
+        """raw [n, 5] float32 = x y z power doppler (the message's points, channels[2] and channels[0])."""
+        t = np.ascontiguousarray(raw, np.float32).reshape(-1, 5)
+        base = t.__array_interface__["data"][0]
+        ng, nv = C.c_int(0), C.c_int(0)
+        n = t.shape[0]
+        self._check(self.lib.gorio_scan_load(self.h, C.c_void_p(base) if n else None, C.c_void_p(base + 12) if n else None, C.c_void_p(base + 16) if n else None, n, 20,
+                                             C.byref(ng), C.byref(nv)))
+        return ng.value, nv.value
+
+    def run(self, samples=(), ang_vel=None):
+        """samples [n_iter, n_ransac_points] uint32 into the valid targets; ang_vel: 3 numbers or None.  A refusal raises GorioError."""
+        k = self.params.reve.n_ransac_points
+        s = np.ascontiguousarray(samples, np.uint32).reshape(-1, k) if len(samples) else np.zeros((0, k), np.uint32)
+        w = None if ang_vel is None else (C.c_double * 3)(*[float(x) for x in ang_vel])
+        r = ScanResult()
+        rc = self.lib.gorio_scan_run(self.h, _ptr(s) if s.shape[0] else None, s.shape[0], w, C.byref(r))
+        self.last_result = dict(status=SCAN_STATUS.get(r.status, r.status), stage=r.stage, reve_success=bool(r.reve_success), v_r=np.array(r.v_r[:]), sigma_v_r=np.array(r.sigma_v_r[:]),
+                                n_out=r.n_out, n_ground=r.n_ground, n_clusters=r.n_clusters)
+        self._check(rc)
+        return self.last_result
+
+    def output(self):
+        """(xyz [n,3], intensity [n], doppler [n], label [n]) of the last OK run: what the nodelet publishes."""
+        n = self.last_result["n_out"]
+        buf = np.zeros((max(n, 1), 6), np.float32)
+        base = buf.__array_interface__["data"][0]
+        self._check(self.lib.gorio_scan_get_output(self.h, C.c_void_p(base), C.c_void_p(base + 12), C.c_void_p(base + 16), C.c_void_p(base + 20), 24, buf.shape[0]))
+        buf = buf[:n]
+        return buf[:, :3].copy(), buf[:, 3].copy(), buf[:, 4].copy(), buf[:, 5].copy()
+
+    def stage(self, stage, points=False):
+        """Indices (into the gated cloud; for "gate": into the raw message) of the points that survive `stage`, in order; with points=True
+        also their coordinates after that stage."""
+        st = STAGES[stage] if isinstance(stage, str) else int(stage)
+        cnt = C.c_int(0)
+        self._check(self.lib.gorio_scan_get_stage(self.h, st, None, 0, C.byref(cnt)))
+        idx = np.zeros(max(cnt.value, 1), np.int32)
+        self._check(self.lib.gorio_scan_get_stage(self.h, st, _ptr(idx), idx.shape[0], C.byref(cnt)))
+        idx = idx[:cnt.value]
+        if not points:
+            return idx
+        xyz = np.zeros((max(cnt.value, 1), 3), np.float32)
+        self._check(self.lib.gorio_scan_get_stage_points(self.h, st, _ptr(xyz), xyz.shape[0], C.byref(cnt)))
+        return idx, xyz[:cnt.value]
+
+    def counters(self):
+        u, b, d = C.c_longlong(0), C.c_longlong(0), C.c_longlong(0)
+        self._check(self.lib.gorio_scan_get_counters(self.h, C.byref(u), C.byref(b), C.byref(d)))
+        return dict(point_uploads=u.value, index_builds=b.value, point_downloads=d.value)
