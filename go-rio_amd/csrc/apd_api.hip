@@ -7,6 +7,7 @@
 #include <dlfcn.h>
 #include <rccl/rccl.h>
 
+#include <algorithm>
 #include <cfloat>
 #include <climits>
 #include <cmath>
@@ -462,11 +463,13 @@ void resolve_stage_events(gorio_apd* h) {
 }
 
 // Build the search accelerator of every listed cloud that lacks one (batched: every launch covers all clouds).  The launches, in order:
-//   bbox_morton_kernel                        bounding box + Morton keys (bbox_init / bbox / morton_kernel when a cloud exceeds kBboxFusedMax)
-//   bitonic_tile_sort_kernel, then per merge size above the sort tile bitonic_global_kernel per stride + bitonic_tile_merge_kernel
+//   bbox_morton_sort_kernel                   clouds of at most kLdsSortMax points: bounding box, Morton keys and their sort in one launch
+//   for the bigger clouds of the call, each routed by its own size (the jobs are ordered small first, the launches take their part):
+//     bbox_morton_kernel                      bounding box + Morton keys (bbox_init / bbox / morton_kernel when a cloud exceeds kBboxFusedMax)
+//     bitonic_tile_sort_kernel, then per merge size above the sort tile bitonic_global_kernel per stride + bitonic_tile_merge_kernel
 //   kd_refine_kernel                          gather in Morton order, median splits, sx / sy / sz / orig / s4, tile and super-tile boxes
 //   box_block_kernel                          block boxes
-// 9 launches for 16 384-point scans (14 before the gather and the two lower box levels moved into kd_refine_kernel).
+// 3 launches for 16 384-point scans (9 while their sort went through global memory between its stages).
 int run_index_build(gorio_apd* lead, std::vector<std::pair<gorio_apd*, DevCloud*>>& clouds) {
   std::vector<std::pair<gorio_apd*, DevCloud*>> todo;
   bool small_call = true;  // every cloud named in the call (built now or not) is a scan-sized one: kd chunks of 2048 points (kd_refine_kernel)
@@ -479,8 +482,10 @@ int run_index_build(gorio_apd* lead, std::vector<std::pair<gorio_apd*, DevCloud*
   }
   if (todo.empty()) return GORIO_OK;
   const int nj = (int)todo.size();
+  // clouds whose keys one workgroup sorts in LDS come first in the job list, the others behind them
+  const int ns = (int)(std::stable_partition(todo.begin(), todo.end(), [](const std::pair<gorio_apd*, DevCloud*>& c) { return c.second->n <= kLdsSortMax; }) - todo.begin());
   std::vector<IndexJob> jobs(nj);
-  int max_pow2 = kSortTile, max_spad = 512, max_n = 1;
+  int max_pow2 = kSortTile, max_spad = 512, max_n = 1;  // max_pow2 / max_n: over the clouds that take the tiled sort
   for (int q = 0; q < nj; ++q) {
     gorio_apd* h = todo[q].first;
     DevCloud& c = *todo[q].second;
@@ -496,26 +501,33 @@ int run_index_build(gorio_apd* lead, std::vector<std::pair<gorio_apd*, DevCloud*
     c.idx_spad = n_spad;
     IndexJob& j = jobs[q];
     j.x = c.x; j.y = c.y; j.z = c.z; j.n = c.n; j.npow2 = npow2; j.keys = c.keys; j.bb = c.bb; j.idx = c.index_view();
-    max_pow2 = std::max(max_pow2, npow2);
     max_spad = std::max(max_spad, n_spad);
-    max_n = std::max(max_n, c.n);
+    if (q >= ns) {
+      max_pow2 = std::max(max_pow2, npow2);
+      max_n = std::max(max_n, c.n);
+    }
   }
   HIP_TRY(lead, lead->d_ijobs.reserve(nj));
   if (int rc = upload_staged(lead, lead->pin_ijobs, lead->d_ijobs, jobs.data(), sizeof(IndexJob) * nj)) return rc;
   {
     StageTimer t(lead, 4);
     const IndexJob* dj = lead->d_ijobs;
-    if (max_n <= kBboxFusedMax) {
-      bbox_morton_kernel<<<nj, 1024, 0, lead->stream>>>(dj);
-    } else {
-      bbox_init_kernel<<<(nj + 63) / 64, 64, 0, lead->stream>>>(dj, nj);
-      bbox_kernel<<<dim3(std::min(64, (max_n + 255) / 256), nj), 256, 0, lead->stream>>>(dj);
-      morton_kernel<<<dim3((max_pow2 + 255) / 256, nj), 256, 0, lead->stream>>>(dj);
-    }
-    bitonic_tile_sort_kernel<<<dim3(max_pow2 / kSortTile, nj), 1024, 0, lead->stream>>>(dj);
-    for (int k = 2 * kSortTile; k <= max_pow2; k <<= 1) {
-      for (int j = k >> 1; j >= kSortTile; j >>= 1) bitonic_global_kernel<<<dim3((max_pow2 / 2 + 255) / 256, nj), 256, 0, lead->stream>>>(dj, k, j);
-      bitonic_tile_merge_kernel<<<dim3(max_pow2 / kSortTile, nj), 1024, 0, lead->stream>>>(dj, k);
+    if (ns > 0) bbox_morton_sort_kernel<<<ns, 1024, 0, lead->stream>>>(dj);
+    if (nj > ns) {
+      const IndexJob* bj = dj + ns;
+      const int nb = nj - ns;
+      if (max_n <= kBboxFusedMax) {
+        bbox_morton_kernel<<<nb, 1024, 0, lead->stream>>>(bj);
+      } else {
+        bbox_init_kernel<<<(nb + 63) / 64, 64, 0, lead->stream>>>(bj, nb);
+        bbox_kernel<<<dim3(std::min(64, (max_n + 255) / 256), nb), 256, 0, lead->stream>>>(bj);
+        morton_kernel<<<dim3((max_pow2 + 255) / 256, nb), 256, 0, lead->stream>>>(bj);
+      }
+      bitonic_tile_sort_kernel<<<dim3(max_pow2 / kSortTile, nb), 1024, 0, lead->stream>>>(bj);
+      for (int k = 2 * kSortTile; k <= max_pow2; k <<= 1) {
+        for (int j = k >> 1; j >= kSortTile; j >>= 1) bitonic_global_kernel<<<dim3((max_pow2 / 2 + 255) / 256, nb), 256, 0, lead->stream>>>(bj, k, j);
+        bitonic_tile_merge_kernel<<<dim3(max_pow2 / kSortTile, nb), 1024, 0, lead->stream>>>(bj, k);
+      }
     }
     if (small_call) kd_refine_kernel<2048><<<dim3((max_spad + 2047) / 2048, nj), 512, 0, lead->stream>>>(dj);
     else kd_refine_kernel<4096><<<dim3((max_spad + 4095) / 4096, nj), 1024, 0, lead->stream>>>(dj);

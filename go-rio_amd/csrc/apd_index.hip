@@ -4,6 +4,7 @@
 //   bbox_morton_kernel               bounding box + 3 x 11-bit Morton code per point in one launch (clouds up to kBboxFusedMax points);
 //   bbox_kernel / morton_kernel      the same as three launches for bigger clouds
 //   bitonic_*_kernel                 LDS-tiled bitonic sort of (code << 31 | index) keys
+//   bbox_morton_sort_kernel          box, keys and the whole sort in one launch, inside LDS (clouds up to kLdsSortMax points)
 //   kd_refine_kernel                 gathers the points in Morton order, median splits inside every chunk, tile / super-tile boxes
 //   box_block_kernel                 block boxes
 //   nn_search_pruned_kernel          1-NN correspondences (APD:164-180), same packed-key output as nn_search_kernel
@@ -227,6 +228,129 @@ __global__ __launch_bounds__(1024) void bitonic_tile_merge_kernel(const IndexJob
     __syncthreads();
   }
   for (int q = threadIdx.x; q < kSortTile; q += 1024) jb.keys[base + q] = s[q];
+}
+
+// bbox_morton_kernel + the whole bitonic sort as ONE launch for clouds whose padded keys fit in the LDS of one CU (npow2 <= kLdsSortMax:
+// every scan): one workgroup per cloud reduces the box, writes the keys into LDS instead of global memory, sorts them there and stores
+// the sorted keys once.  The keys are unique (the low 31 bits are the point's index; the padding keys are all ~0 and indistinguishable),
+// so ANY correct ascending sort leaves keys[] exactly as the six launches of the tiled sort do.
+//   * REGISTER BLOCKS: a compare-exchange stage per barrier would be 105 LDS round trips for 16 384 keys.  Here a thread takes the 16 keys
+//     whose indices differ in four address bits [b, b + 4) and runs the four stages with strides 2^(b+3) .. 2^b on them in registers
+//     (fewer bits when a merge has not a multiple of four stages: that group comes first, so b is always a multiple of four); merge sizes
+//     2 .. 16 are one such block.  29 round trips instead of 105.
+//   * PADDED SLOTS: key i sits in slot i + (i >> 4).  With b = 0 a lane's 16 keys are consecutive and lanes are 17 slots apart (34 dwords:
+//     32 lanes hit 32 different bank pairs); with b = 4, 8, 12 consecutive lanes read consecutive slots.  17 408 slots = 139 264 bytes.
+// The workgroup has a CU's LDS to itself while it runs: 128 clouds of a C4 batch take 128 of the 256 CUs for the length of one sort.
+// grid: (jobs), block 1024
+constexpr int kLdsSortMax = 16384;  // keys (npow2) per workgroup; 32 768 would need 278 528 bytes, a CU has 163 840
+constexpr int kLdsSortSlots = kLdsSortMax + kLdsSortMax / 16;
+__device__ __forceinline__ int lds_sort_slot(int i) { return i + (i >> 4); }
+
+// the stages with strides 2^(b+G-1) .. 2^b of merge size k (k > 2^(b+G-1): the direction is one per thread), 2^G keys per thread
+template <int G>
+__device__ __forceinline__ void lds_sort_block(unsigned long long* __restrict__ s, int n, int k, int b, int tid) {
+  constexpr int R = 1 << G;
+  for (int t = tid; t < (n >> G); t += 1024) {
+    const int lo = ((t >> b) << (b + G)) | (t & ((1 << b) - 1));
+    const bool up = (lo & k) == 0;
+    unsigned long long v[R];
+#pragma unroll
+    for (int r = 0; r < R; ++r) v[r] = s[lds_sort_slot(lo | (r << b))];
+#pragma unroll
+    for (int st = G - 1; st >= 0; --st) {
+#pragma unroll
+      for (int r = 0; r < R; ++r) {
+        if ((r & (1 << st)) == 0) cmpx(v[r], v[r | (1 << st)], up);
+      }
+    }
+#pragma unroll
+    for (int r = 0; r < R; ++r) s[lds_sort_slot(lo | (r << b))] = v[r];
+  }
+}
+
+__global__ __launch_bounds__(1024) void bbox_morton_sort_kernel(const IndexJob* __restrict__ jobs) {
+  const IndexJob& jb = jobs[blockIdx.x];
+  __shared__ unsigned long long s[kLdsSortSlots];
+  __shared__ unsigned int s_bb[16][6];
+  const int tid = threadIdx.x;
+  const int n = jb.npow2;  // keys to sort: a power of two, kSortTile <= n <= kLdsSortMax (run_index_build)
+  float flo[3] = {INFINITY, INFINITY, INFINITY}, fhi[3] = {-INFINITY, -INFINITY, -INFINITY};
+  for (int i = tid; i < jb.n; i += 1024) {
+    const float v[3] = {jb.x[i], jb.y[i], jb.z[i]};
+#pragma unroll
+    for (int a = 0; a < 3; ++a) {
+      flo[a] = fminf(flo[a], v[a]);
+      fhi[a] = fmaxf(fhi[a], v[a]);
+    }
+  }
+#pragma unroll
+  for (int a = 0; a < 3; ++a) {
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) {
+      flo[a] = fminf(flo[a], __shfl_xor(flo[a], off, 64));
+      fhi[a] = fmaxf(fhi[a], __shfl_xor(fhi[a], off, 64));
+    }
+    if ((tid & 63) == 0) {  // across waves on the order-preserving encoding, as bbox_morton_kernel
+      s_bb[tid >> 6][a] = f2ord(flo[a]);
+      s_bb[tid >> 6][3 + a] = f2ord(fhi[a]);
+    }
+  }
+  __syncthreads();
+  unsigned int bb[6];
+#pragma unroll
+  for (int a = 0; a < 3; ++a) {
+    bb[a] = 0xffffffffu;
+    bb[3 + a] = 0u;
+    for (int w = 0; w < 16; ++w) {
+      bb[a] = min(bb[a], s_bb[w][a]);
+      bb[3 + a] = max(bb[3 + a], s_bb[w][3 + a]);
+    }
+  }
+  if (tid == 0) {
+#pragma unroll
+    for (int a = 0; a < 6; ++a) jb.bb[a] = bb[a];
+  }
+  float ext = 1e-6f, lo[3];
+#pragma unroll
+  for (int a = 0; a < 3; ++a) {
+    lo[a] = ord2f(bb[a]);
+    ext = fmaxf(ext, ord2f(bb[3 + a]) - lo[a]);
+  }
+  for (int i = tid; i < n; i += 1024) s[lds_sort_slot(i)] = morton_key(jb, i, lo, ext);
+  __syncthreads();
+  // merge sizes 2 .. 16 on 16 consecutive keys per thread; the direction of a pair follows its own index here
+  for (int t = tid; t < (n >> 4); t += 1024) {
+    const int base = t << 4;
+    unsigned long long v[16];
+#pragma unroll
+    for (int r = 0; r < 16; ++r) v[r] = s[lds_sort_slot(base | r)];
+#pragma unroll
+    for (int lk = 1; lk <= 4; ++lk) {
+#pragma unroll
+      for (int st = lk - 1; st >= 0; --st) {
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+          if ((r & (1 << st)) == 0) cmpx(v[r], v[r | (1 << st)], ((base | r) & (1 << lk)) == 0);
+        }
+      }
+    }
+#pragma unroll
+    for (int r = 0; r < 16; ++r) s[lds_sort_slot(base | r)] = v[r];
+  }
+  __syncthreads();
+  for (int lk = 5; (1 << lk) <= n; ++lk) {
+    const int k = 1 << lk;
+    for (int hi = lk; hi > 0;) {  // address bits [0, hi) of this merge are still to do
+      const int g = (hi & 3) ? (hi & 3) : 4, b = hi - g;
+      if (g == 4) lds_sort_block<4>(s, n, k, b, tid);
+      else if (g == 3) lds_sort_block<3>(s, n, k, b, tid);
+      else if (g == 2) lds_sort_block<2>(s, n, k, b, tid);
+      else lds_sort_block<1>(s, n, k, b, tid);
+      hi = b;
+      __syncthreads();
+    }
+  }
+  for (int i = tid; i < n; i += 1024) jb.keys[i] = s[lds_sort_slot(i)];
 }
 
 // kd refinement of the Morton order: inside every chunk of 4096 sorted points (a compact region of space after the Morton sort)
