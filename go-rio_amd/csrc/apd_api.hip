@@ -79,7 +79,6 @@ struct DevCloud {
   DevBuf<unsigned long long> vm_keys;  // sort scratch: linear voxel id << 31 | point index
   DevBuf<int> vm_counts;               // voxel starts per 256 keys, scanned
   DevBuf<int> vm_bb;                   // [8] bounding box of the occupied coordinates + range flag
-  DevBuf<IndexJob> vm_job;             // descriptor the bitonic sort kernels read
   DevBuf<unsigned long long> vm_vkey;  // the map itself (VoxelMapView): these four hold vm_cap voxels
   DevBuf<double> vm_mean;
   DevBuf<double> vm_cov6;
@@ -89,6 +88,17 @@ struct DevCloud {
   double vm_res = 0.0;
   bool vm_mult = false;                   // MultiplicativeGaussianVoxel (ADDITIVE and ADDITIVE_WEIGHTED build the same voxels, VOX:138-141)
   bool vm_valid = false;
+  // What is derived from what: covariances, search index, voxel map and k-NN lists from the points; the voxel map and the k-NN lists from
+  // the covariances too.  New points leave all four stale, new covariances the last two.  These members are the ONLY code that writes
+  // present, cov_count, cov_k, cov_reg, idx_valid, idx_chunk, vm_valid and knn_valid; everybody else reads them.
+  void covs_dropped() { cov_count = 0; vm_valid = false; knn_valid = false; }
+  void points_replaced() { present = true; idx_valid = false; covs_dropped(); }
+  void cleared() { present = false; n = 0; idx_valid = false; covs_dropped(); }
+  void covs_estimated(int k, int reg, bool keep_knn) { cov_count = n; cov_k = k; cov_reg = reg; vm_valid = false; knn_valid = keep_knn; }
+  void covs_supplied() { covs_estimated(-1, -1, false); }  // not from a k-NN search of this library: no lists, no (k, reg) to compare
+  void index_built(int chunk) { idx_valid = true; idx_chunk = chunk; }
+  void voxelmap_dropped() { vm_valid = false; }
+  void voxelmap_built() { vm_valid = true; }
   VoxelMapView voxel_view() const { return VoxelMapView{vm_vkey, vm_mean, vm_cov6, vm_num, vm_nv, {vm_min[0], vm_min[1], vm_min[2]}, {vm_dim[0], vm_dim[1], vm_dim[2]}, vm_res}; }
   // the kernel-visible view of the search index (the buffers above own the memory)
   SearchIndex index_view() const { return SearchIndex{idx_sx, idx_sy, idx_sz, idx_orig, idx_s4, idx_tbox, idx_sbox, idx_bbox, idx_n, idx_spad, idx_spad / 32, idx_spad / 512}; }
@@ -147,7 +157,6 @@ struct gorio_apd {
   DevBuf<int> d_sub_counts;
   DevBuf<SubmapFrame> d_sub_frames;
   DevBuf<unsigned int> d_sub_bb;
-  DevBuf<IndexJob> d_sub_job;
   // sharded-source mode (gorio_apd_comm_init): RCCL communicator over the ranks that share one source cloud
   ncclComm_t comm = nullptr;
   int comm_world = 1, comm_rank = 0;
@@ -322,9 +331,7 @@ int upload_cloud(gorio_apd* h, DevCloud& c, const float* xyz, const float* label
   HIP_TRY(h, hipMemcpyAsync(c.label, bl, sizeof(float) * np, hipMemcpyHostToDevice, h->stream));
   HIP_TRY(h, hipMemcpyAsync(c.p4, b4, sizeof(float4) * np, hipMemcpyHostToDevice, h->stream));
   HIP_TRY(h, hipStreamSynchronize(h->stream));
-  c.present = true;
-  c.cov_count = 0; c.vm_valid = false;
-  c.idx_valid = false;
+  c.points_replaced();
   return GORIO_OK;
 }
 
@@ -349,9 +356,7 @@ int upload_cloud_device(gorio_apd* h, DevCloud& c, const float* dx, const float*
   if (rc) return rc;
   copy_cloud_kernel<<<(c.n_pad + 255) / 256, 256, 0, h->stream>>>(dx, dy, dz, dl, c.x, c.y, c.z, c.label, c.p4, n, c.n_pad);
   HIP_TRY(h, hipGetLastError());
-  c.present = true;
-  c.cov_count = 0; c.vm_valid = false;
-  c.idx_valid = false;
+  c.points_replaced();
   return GORIO_OK;
 }
 
@@ -466,7 +471,8 @@ void resolve_stage_events(gorio_apd* h) {
 //   bbox_morton_sort_kernel                   clouds of at most kLdsSortMax points: bounding box, Morton keys and their sort in one launch
 //   for the bigger clouds of the call, each routed by its own size (the jobs are ordered small first, the launches take their part):
 //     bbox_morton_kernel                      bounding box + Morton keys (bbox_init / bbox / morton_kernel when a cloud exceeds kBboxFusedMax)
-//     bitonic_tile_sort_kernel, then per merge size above the sort tile bitonic_global_kernel per stride + bitonic_tile_merge_kernel
+//     enqueue_tiled_sort                      bitonic_tile_sort_kernel, then per merge size above the sort tile bitonic_global_kernel per stride +
+//                                             bitonic_tile_merge_kernel (apd_index.hip; the voxel-map and submap sorts enqueue the same)
 //   kd_refine_kernel                          gather in Morton order, median splits, sx / sy / sz / orig / s4, tile and super-tile boxes
 //   box_block_kernel                          block boxes
 // 3 launches for 16 384-point scans (9 while their sort went through global memory between its stages).
@@ -490,8 +496,7 @@ int run_index_build(gorio_apd* lead, std::vector<std::pair<gorio_apd*, DevCloud*
     gorio_apd* h = todo[q].first;
     DevCloud& c = *todo[q].second;
     const int n_spad = roundup(c.n, 512);
-    int npow2 = kSortTile;
-    while (npow2 < c.n) npow2 <<= 1;
+    const int npow2 = sort_padded_size(c.n);
     const size_t cap = n_spad + roundup(n_spad / 8, 512);
     HIP_TRY(h, reserve_group(c.idx_cap, n_spad, cap, c.idx_sx, cap, c.idx_sy, cap, c.idx_sz, cap, c.idx_orig, cap, c.idx_s4, cap, c.idx_tbox, 8 * (cap / 32),
                              c.idx_sbox, 8 * (cap / 512), c.idx_bbox, 8 * (cap / 32768 + 1)));
@@ -523,21 +528,14 @@ int run_index_build(gorio_apd* lead, std::vector<std::pair<gorio_apd*, DevCloud*
         bbox_kernel<<<dim3(std::min(64, (max_n + 255) / 256), nb), 256, 0, lead->stream>>>(bj);
         morton_kernel<<<dim3((max_pow2 + 255) / 256, nb), 256, 0, lead->stream>>>(bj);
       }
-      bitonic_tile_sort_kernel<<<dim3(max_pow2 / kSortTile, nb), 1024, 0, lead->stream>>>(bj);
-      for (int k = 2 * kSortTile; k <= max_pow2; k <<= 1) {
-        for (int j = k >> 1; j >= kSortTile; j >>= 1) bitonic_global_kernel<<<dim3((max_pow2 / 2 + 255) / 256, nb), 256, 0, lead->stream>>>(bj, k, j);
-        bitonic_tile_merge_kernel<<<dim3(max_pow2 / kSortTile, nb), 1024, 0, lead->stream>>>(bj, k);
-      }
+      enqueue_tiled_sort(lead->stream, IndexJobKeys{bj}, nb, max_pow2);
     }
     if (small_call) kd_refine_kernel<2048><<<dim3((max_spad + 2047) / 2048, nj), 512, 0, lead->stream>>>(dj);
     else kd_refine_kernel<4096><<<dim3((max_spad + 4095) / 4096, nj), 1024, 0, lead->stream>>>(dj);
     box_block_kernel<<<dim3((max_spad / 32768 + 64) / 64, nj), 64, 0, lead->stream>>>(dj);
   }
   HIP_TRY(lead, hipGetLastError());
-  for (auto& t : todo) {
-    t.second->idx_valid = true;
-    t.second->idx_chunk = small_call ? 2048 : 4096;
-  }
+  for (auto& t : todo) t.second->index_built(small_call ? 2048 : 4096);
   return GORIO_OK;
 }
 
@@ -580,7 +578,6 @@ int run_covariances(gorio_apd* lead, std::vector<std::pair<gorio_apd*, DevCloud*
       HIP_TRY(h, c.knn.realloc((size_t)c.cap * k));
       c.knn_k = k;
     }
-    c.knn_valid = keep;
     if (select) {
       const size_t nw = roundup(c.n, 512) / 64, cap = nw + nw / 8;
       HIP_TRY(h, reserve_group(c.redo_cap, nw, cap, c.redo, cap, c.kth, 64 * cap));
@@ -636,11 +633,7 @@ int run_covariances(gorio_apd* lead, std::vector<std::pair<gorio_apd*, DevCloud*
     }
   }
   HIP_TRY(lead, hipGetLastError());
-  for (auto& t : todo) {
-    t.second->cov_count = t.second->n; t.second->vm_valid = false;
-    t.second->cov_k = k;
-    t.second->cov_reg = lead->params.regularization;
-  }
+  for (auto& t : todo) t.second->covs_estimated(k, lead->params.regularization, t.first->params.keep_knn_indices != 0);
   return GORIO_OK;
 }
 
@@ -724,10 +717,9 @@ bool shared_voxel_mismatch(const gorio_apd* h) {
 int build_voxelmap(gorio_apd* h, DevCloud& t, double res, int mode) {
   const bool mult = mode == GORIO_VOXEL_MULTIPLICATIVE;
   if (t.vm_valid && t.vm_res == res && t.vm_mult == mult) return GORIO_OK;
-  t.vm_valid = false;
+  t.voxelmap_dropped();
   const int n = t.n;
   HIP_TRY(h, t.vm_bb.reserve(8));
-  HIP_TRY(h, t.vm_job.reserve(1));
   vg_bbox_init_kernel<<<1, 64, 0, h->stream>>>(t.vm_bb);
   vg_coord_bbox_kernel<<<std::min(256, (n + 255) / 256), 256, 0, h->stream>>>(t.p4, n, res, t.vm_bb);
   int bb[8];
@@ -744,24 +736,12 @@ int build_voxelmap(gorio_apd* h, DevCloud& t, double res, int mode) {
   }
   g.res = res;
   if (cells >= 8589934592.0) return fail(h, GORIO_ERR_UNSUPPORTED, "voxel map: the bounding box of the occupied voxels has 2^33 cells or more (the voxel id is packed into 33 bits of the sort key)");
-  int npow2 = kSortTile;
-  while (npow2 < n) npow2 <<= 1;
+  const int npow2 = sort_padded_size(n);
   const int nblocks = (n + 255) / 256;
   HIP_TRY(h, t.vm_keys.reserve(npow2));
   HIP_TRY(h, t.vm_counts.reserve(nblocks + 1));
   vg_key_kernel<<<(npow2 + 255) / 256, 256, 0, h->stream>>>(t.p4, n, npow2, g, t.vm_keys);
-  IndexJob job;
-  std::memset(&job, 0, sizeof(job));
-  job.n = n;
-  job.npow2 = npow2;
-  job.keys = t.vm_keys;
-  HIP_TRY(h, hipMemcpyAsync(t.vm_job, &job, sizeof(job), hipMemcpyHostToDevice, h->stream));
-  HIP_TRY(h, hipStreamSynchronize(h->stream));  // `job` lives on this stack frame
-  bitonic_tile_sort_kernel<<<dim3(npow2 / kSortTile, 1), 1024, 0, h->stream>>>(t.vm_job);
-  for (int k = 2 * kSortTile; k <= npow2; k <<= 1) {
-    for (int j = k >> 1; j >= kSortTile; j >>= 1) bitonic_global_kernel<<<dim3((npow2 / 2 + 255) / 256, 1), 256, 0, h->stream>>>(t.vm_job, k, j);
-    bitonic_tile_merge_kernel<<<dim3(npow2 / kSortTile, 1), 1024, 0, h->stream>>>(t.vm_job, k);
-  }
+  enqueue_tiled_sort(h->stream, SortKeys{t.vm_keys, npow2}, 1, npow2);
   vox_count_kernel<<<nblocks, 256, 0, h->stream>>>(t.vm_keys, n, t.vm_counts);
   vox_scan_kernel<<<1, 1024, 0, h->stream>>>(t.vm_counts, nblocks);
   int nv = 0;
@@ -781,7 +761,7 @@ int build_voxelmap(gorio_apd* h, DevCloud& t, double res, int mode) {
   }
   t.vm_res = res;
   t.vm_mult = mult;
-  t.vm_valid = true;
+  t.voxelmap_built();
   return GORIO_OK;
 }
 
@@ -1396,9 +1376,7 @@ int gorio_apd_set_clouds_device_batch(gorio_apd_t** handles, int count, const go
       }
       jobs.push_back(CopyJob{in.x, in.y, in.z, in.label, c.x, c.y, c.z, c.label, c.p4, in.n, c.n_pad});
       max_pad = std::max(max_pad, c.n_pad);
-      c.present = true;
-      c.cov_count = 0; c.vm_valid = false;
-      c.idx_valid = false;
+      c.points_replaced();
       h->corr_valid = false;
     }
   }
@@ -1413,13 +1391,13 @@ int gorio_apd_set_clouds_device_batch(gorio_apd_t** handles, int count, const go
 int gorio_apd_clear_source(gorio_apd_t* h) {
   if (!h) return GORIO_ERR_INVALID;
   make_private(h, h->src);
-  h->src->present = false; h->src->n = 0; h->src->cov_count = 0; h->src->vm_valid = false; h->corr_valid = false;  // APD:101-105
+  h->src->cleared(); h->corr_valid = false;  // APD:101-105
   return GORIO_OK;
 }
 int gorio_apd_clear_target(gorio_apd_t* h) {
   if (!h) return GORIO_ERR_INVALID;
   make_private(h, h->tgt);
-  h->tgt->present = false; h->tgt->n = 0; h->tgt->cov_count = 0; h->tgt->vm_valid = false; h->corr_valid = false;  // APD:107-112
+  h->tgt->cleared(); h->corr_valid = false;  // APD:107-112
   return GORIO_OK;
 }
 int gorio_apd_set_target_shared(gorio_apd_t* h, gorio_apd_t* owner) {
@@ -1470,7 +1448,6 @@ int gorio_apd_set_target_submap(gorio_apd_t* h, const gorio_apd_keyframe* frames
   }
   HIP_TRY(h, h->d_sub_frames.reserve(count));
   HIP_TRY(h, h->d_sub_bb.reserve(8));
-  HIP_TRY(h, h->d_sub_job.reserve(1));
   HIP_TRY(h, hipMemcpyAsync(h->d_sub_in, stage.data(), sizeof(float4) * m, hipMemcpyHostToDevice, h->stream));
   HIP_TRY(h, hipMemcpyAsync(h->d_sub_frames, fr.data(), sizeof(SubmapFrame) * count, hipMemcpyHostToDevice, h->stream));
   submap_transform_kernel<<<dim3((max_frame + 255) / 256, count), 256, 0, h->stream>>>(h->d_sub_in, h->d_sub_frames, h->d_sub_out);
@@ -1502,25 +1479,12 @@ int gorio_apd_set_target_submap(gorio_apd_t* h, const gorio_apd_keyframe* frames
       }
       g.div0 = div_b[0];
       g.div01 = div_b[0] * div_b[1];
-      int npow2 = kSortTile;
-      while (npow2 < m) npow2 <<= 1;
+      const int npow2 = sort_padded_size(m);
       HIP_TRY(h, h->d_sub_keys.reserve(npow2));
       const int nblocks = (m + 255) / 256;
       HIP_TRY(h, h->d_sub_counts.reserve(nblocks + 1, nblocks + 1 + nblocks / 8));
-      IndexJob job;
-      std::memset(&job, 0, sizeof(job));
-      job.n = m;
-      job.npow2 = npow2;
-      job.keys = h->d_sub_keys;
-      HIP_TRY(h, hipMemcpyAsync(h->d_sub_job, &job, sizeof(job), hipMemcpyHostToDevice, h->stream));
-      HIP_TRY(h, hipStreamSynchronize(h->stream));  // `job` is a stack object
       vox_key_kernel<<<(npow2 + 255) / 256, 256, 0, h->stream>>>(h->d_sub_out, m, npow2, g, h->d_sub_keys);
-      const IndexJob* dj = h->d_sub_job;
-      bitonic_tile_sort_kernel<<<dim3(npow2 / kSortTile, 1), 1024, 0, h->stream>>>(dj);
-      for (int k = 2 * kSortTile; k <= npow2; k <<= 1) {
-        for (int j = k >> 1; j >= kSortTile; j >>= 1) bitonic_global_kernel<<<dim3((npow2 / 2 + 255) / 256, 1), 256, 0, h->stream>>>(dj, k, j);
-        bitonic_tile_merge_kernel<<<dim3(npow2 / kSortTile, 1), 1024, 0, h->stream>>>(dj, k);
-      }
+      enqueue_tiled_sort(h->stream, SortKeys{h->d_sub_keys, npow2}, 1, npow2);
       vox_count_kernel<<<nblocks, 256, 0, h->stream>>>(h->d_sub_keys, m, h->d_sub_counts);
       vox_scan_kernel<<<1, 1024, 0, h->stream>>>(h->d_sub_counts, nblocks);
       vox_centroid_kernel<<<nblocks, 256, 0, h->stream>>>(h->d_sub_keys, h->d_sub_out, m, h->d_sub_counts, h->d_sub_vox);
@@ -1537,10 +1501,7 @@ int gorio_apd_set_target_submap(gorio_apd_t* h, const gorio_apd_keyframe* frames
   submap_store_kernel<<<(c.n_pad + 255) / 256, 256, 0, h->stream>>>(result, n_out, c.n_pad, c.x, c.y, c.z, c.label, c.p4);
   HIP_TRY(h, hipGetLastError());
   HIP_TRY(h, hipStreamSynchronize(h->stream));  // the staging vectors die with this call
-  c.present = true;
-  c.cov_count = 0; c.vm_valid = false;
-  c.idx_valid = false;
-  c.knn_valid = false;
+  c.points_replaced();
   h->corr_valid = false;
   if (n_target) *n_target = n_out;
   return GORIO_OK;
@@ -1575,8 +1536,7 @@ static int set_covs(gorio_apd* h, DevCloud& c, const double* cov, int n) {
   if (!c.present || n != c.n) {
     // the reference stores the vector whatever its size (APD:138-145) and recomputes the covariances in computeTransformation when the
     // size does not match the cloud (APD:149-154): a mismatching set is therefore the same as none
-    c.cov_count = 0; c.vm_valid = false;
-    c.knn_valid = false;
+    c.covs_dropped();
     return GORIO_OK;
   }
   HIP_TRY(h, hipSetDevice(h->device));
@@ -1590,10 +1550,7 @@ static int set_covs(gorio_apd* h, DevCloud& c, const double* cov, int n) {
   geo_weight_kernel<<<(n + 255) / 256, 256, 0, h->stream>>>(c.cov6, c.geo_w, n);
   HIP_TRY(h, hipGetLastError());
   HIP_TRY(h, hipStreamSynchronize(h->stream));
-  c.cov_count = n;
-  c.vm_valid = false;
-  c.cov_k = c.cov_reg = -1;
-  c.knn_valid = false;  // these covariances did not come from a k-NN search of this library
+  c.covs_supplied();
   return GORIO_OK;
 }
 

@@ -3,7 +3,8 @@
 //
 //   bbox_morton_kernel               bounding box + 3 x 11-bit Morton code per point in one launch (clouds up to kBboxFusedMax points);
 //   bbox_kernel / morton_kernel      the same as three launches for bigger clouds
-//   bitonic_*_kernel                 LDS-tiled bitonic sort of (code << 31 | index) keys
+//   bitonic_*_kernel                 LDS-tiled bitonic sort of (code << 31 | index) keys, launched by enqueue_tiled_sort alone; templates on
+//                                    where the key array comes from (IndexJobKeys here, SortKeys for the voxel-map and submap sorts)
 //   bbox_morton_sort_kernel          box, keys and the whole sort in one launch, inside LDS (clouds up to kLdsSortMax points)
 //   kd_refine_kernel                 gathers the points in Morton order, median splits inside every chunk, tile / super-tile boxes
 //   box_block_kernel                 block boxes
@@ -159,6 +160,24 @@ __global__ __launch_bounds__(1024) void bbox_morton_kernel(const IndexJob* __res
 
 constexpr int kSortTile = 4096;  // u64 keys per LDS tile (32 KB), 1024 threads
 
+// the size the tiled sort pads n keys to: a power of two, at least one tile
+inline int sort_padded_size(int n) {
+  int npow2 = kSortTile;
+  while (npow2 < n) npow2 <<= 1;
+  return npow2;
+}
+
+// What the bitonic_*_kernel sort: the key array of blockIdx.y, from a key source that is passed BY VALUE as a kernel argument.
+struct SortKeys {  // a single array (voxel map, submap assembly): nothing to read from device memory but the keys themselves
+  unsigned long long* keys;  // [npow2]
+  int npow2;
+  __device__ SortKeys get() const { return *this; }
+};
+struct IndexJobKeys {  // the clouds of a batched index build (run_index_build)
+  const IndexJob* jobs;
+  __device__ SortKeys get() const { return SortKeys{jobs[blockIdx.y].keys, jobs[blockIdx.y].npow2}; }
+};
+
 __device__ __forceinline__ void cmpx(unsigned long long& a, unsigned long long& b, bool up) {
   if ((a > b) == up) {
     const unsigned long long t = a;
@@ -169,8 +188,9 @@ __device__ __forceinline__ void cmpx(unsigned long long& a, unsigned long long& 
 
 // full bitonic sort of every 4096-key tile in LDS; direction alternates with the tile index so that tiles pair into bitonic
 // sequences for the global stages.  grid: (max tiles, jobs), block 1024
-__global__ __launch_bounds__(1024) void bitonic_tile_sort_kernel(const IndexJob* __restrict__ jobs) {
-  const IndexJob& jb = jobs[blockIdx.y];
+template <class KeySource>
+__global__ __launch_bounds__(1024) void bitonic_tile_sort_kernel(const KeySource src) {
+  const SortKeys jb = src.get();
   const int base = blockIdx.x * kSortTile;
   if (base >= jb.npow2) return;
   __shared__ unsigned long long s[kSortTile];
@@ -193,8 +213,9 @@ __global__ __launch_bounds__(1024) void bitonic_tile_sort_kernel(const IndexJob*
 }
 
 // one global compare-exchange stage (stride j >= kSortTile) of merge size k.  grid: (max npow2 / 2 / 256, jobs), block 256
-__global__ __launch_bounds__(256) void bitonic_global_kernel(const IndexJob* __restrict__ jobs, int k, int j) {
-  const IndexJob& jb = jobs[blockIdx.y];
+template <class KeySource>
+__global__ __launch_bounds__(256) void bitonic_global_kernel(const KeySource src, int k, int j) {
+  const SortKeys jb = src.get();
   if (k > jb.npow2) return;
   const int t = blockIdx.x * 256 + threadIdx.x;
   if (t >= jb.npow2 / 2) return;
@@ -208,8 +229,9 @@ __global__ __launch_bounds__(256) void bitonic_global_kernel(const IndexJob* __r
 }
 
 // remaining stages (stride < kSortTile) of merge size k inside LDS.  grid: (max tiles, jobs), block 1024
-__global__ __launch_bounds__(1024) void bitonic_tile_merge_kernel(const IndexJob* __restrict__ jobs, int k) {
-  const IndexJob& jb = jobs[blockIdx.y];
+template <class KeySource>
+__global__ __launch_bounds__(1024) void bitonic_tile_merge_kernel(const KeySource src, int k) {
+  const SortKeys jb = src.get();
   if (k > jb.npow2) return;
   const int base = blockIdx.x * kSortTile;
   if (base >= jb.npow2) return;
@@ -228,6 +250,16 @@ __global__ __launch_bounds__(1024) void bitonic_tile_merge_kernel(const IndexJob
     __syncthreads();
   }
   for (int q = threadIdx.x; q < kSortTile; q += 1024) jb.keys[base + q] = s[q];
+}
+
+// THE launch sequence of the tiled sort, enqueued on `stream`: nb key arrays (blockIdx.y of `src`), the largest padded to max_pow2 keys
+template <class KeySource>
+void enqueue_tiled_sort(hipStream_t stream, const KeySource& src, int nb, int max_pow2) {
+  bitonic_tile_sort_kernel<<<dim3(max_pow2 / kSortTile, nb), 1024, 0, stream>>>(src);
+  for (int k = 2 * kSortTile; k <= max_pow2; k <<= 1) {
+    for (int j = k >> 1; j >= kSortTile; j >>= 1) bitonic_global_kernel<<<dim3((max_pow2 / 2 + 255) / 256, nb), 256, 0, stream>>>(src, k, j);
+    bitonic_tile_merge_kernel<<<dim3(max_pow2 / kSortTile, nb), 1024, 0, stream>>>(src, k);
+  }
 }
 
 // bbox_morton_kernel + the whole bitonic sort as ONE launch for clouds whose padded keys fit in the LDS of one CU (npow2 <= kLdsSortMax:
