@@ -38,6 +38,8 @@
 #include "apd_ground.hip"
 #include "../../include/gorio_sc.h"
 #include "apd_sc.hip"
+#include "../../include/gorio_ndt.h"
+#include "apd_ndt.hip"
 
 using namespace gorio;
 

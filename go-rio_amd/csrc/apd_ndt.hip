@@ -1,0 +1,1174 @@
+// apd_ndt.hip -- NDT_OMP registration (include/gorio_ndt.h): pclomp::NormalDistributionsTransform with the DIRECT1 / 7 / 26 searches.
+// Included by apd_api.hip after apd_sc.hip (it reuses the tiled bitonic sort, the voxel-start count / scan kernels, the fp64 Jacobi of
+// the covariance code and the 28-value wave reduction of linearize_kernel).
+//
+// NDT = ndt_omp_impl.hpp, NDTH = ndt_omp.h, VGC = voxel_grid_covariance_omp_impl.hpp under ndt_omp/include/pclomp of the Go-RIO sources.
+//   voxel map      ndt_bbox_kernel        bounding box of the finite target points (integer atomics on an order-preserving code)
+//                  ndt_key_kernel         leaf index in the float arithmetic of VGC:218-223, key = leaf index << 31 | point index
+//                  (enqueue_tiled_sort, vox_count_kernel, vox_scan_kernel)
+//                  ndt_leaf_kernel        one lane per leaf: sums in input order in fp64 (VGC:233-237), mean, covariance, Jacobi
+//                                         eigen-decomposition, inflation, inverse, the two disabling rules (VGC:293-364)
+//   derivatives    ndt_derivative_kernel  one lane per source point: float transform, <= 26 leaf lookups (binary search over the ascending
+//                                         leaf indices), computePointDerivatives / updateDerivatives in float (NDT:398-537) or
+//                                         updateHessian in double (NDT:613-645); 28 fp64 accumulators, wave_sum28, one partial per block
+//                  ndt_fold_kernel        the block partials in block order -> 28 doubles
+//   score          ndt_score_kernel       calculateScore (NDT:935-983), one double per block, ndt_fold_kernel
+//   align          host                   computeTransformation, computeStepLengthMT and its helpers (NDT:81-171, 648-932)
+// The only device loops are bounded: points of a leaf (<= n), neighbours (<= 26), binary-search steps (<= 32).  Every index that comes
+// from data is range-checked before it addresses memory: a source point outside the grid reads nothing.
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <cmath>
+#include <new>
+#include <vector>
+
+namespace gorio {
+
+constexpr int kNdtCoordLimit = 1 << 30;  // |cell coordinate| below this: offsets and differences stay inside int32
+
+struct NdtGrid {  // VGC:87-103
+  int min_b[3], max_b[3], div_b[3];
+  int mul1, mul2;  // divb_mul_ = (1, mul1, mul2)
+  float inv;       // inverse_leaf_size_
+  float leaf;      // leaf_size_
+};
+
+struct NdtMapView {
+  const int* lidx;     // [nl] ascending linear leaf index
+  const int* cnt;      // [nl] nr_points, -1 when disabled
+  const double* mean;  // [nl][3]
+  const double* icov;  // [nl][9]
+  int nl, min_points;
+  NdtGrid g;
+};
+
+struct NdtEval {  // one evaluation's constants, passed by value
+  float T[12];    // rows 0..2 of the float transform
+  double ja[24];  // j_ang, NDT:329-346, row-major [8][3]
+  double ha[45];  // h_ang with the double d1 row, NDT:351-371, [15][3]
+  double d1, d2, d3;
+  int n_off;      // 1, 7 or 26
+};
+
+// bb[0..2] min, bb[3..5] max (sc_code of the floats), bb[6] finite points, bb[7] flags
+__global__ void ndt_bbox_init_kernel(int* __restrict__ bb) {
+  if (threadIdx.x < 3) bb[threadIdx.x] = INT_MAX;
+  else if (threadIdx.x < 6) bb[threadIdx.x] = INT_MIN;
+  else if (threadIdx.x < 8) bb[threadIdx.x] = 0;
+}
+__device__ __forceinline__ bool ndt_finite3(float x, float y, float z) { return fabsf(x) <= FLT_MAX && fabsf(y) <= FLT_MAX && fabsf(z) <= FLT_MAX; }
+
+__global__ __launch_bounds__(256) void ndt_bbox_kernel(const float* __restrict__ x, const float* __restrict__ y, const float* __restrict__ z, int n, int* __restrict__ bb) {
+  int lo0 = INT_MAX, lo1 = INT_MAX, lo2 = INT_MAX, hi0 = INT_MIN, hi1 = INT_MIN, hi2 = INT_MIN, cnt = 0;
+  for (int i = blockIdx.x * 256 + threadIdx.x; i < n; i += gridDim.x * 256) {
+    const float px = x[i], py = y[i], pz = z[i];
+    if (!ndt_finite3(px, py, pz)) continue;  // VGC:213-215
+    const int c0 = sc_code(px), c1 = sc_code(py), c2 = sc_code(pz);
+    lo0 = min(lo0, c0); lo1 = min(lo1, c1); lo2 = min(lo2, c2);
+    hi0 = max(hi0, c0); hi1 = max(hi1, c1); hi2 = max(hi2, c2);
+    ++cnt;
+  }
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) {
+    lo0 = min(lo0, __shfl_down(lo0, off, 64)); lo1 = min(lo1, __shfl_down(lo1, off, 64)); lo2 = min(lo2, __shfl_down(lo2, off, 64));
+    hi0 = max(hi0, __shfl_down(hi0, off, 64)); hi1 = max(hi1, __shfl_down(hi1, off, 64)); hi2 = max(hi2, __shfl_down(hi2, off, 64));
+    cnt += __shfl_down(cnt, off, 64);
+  }
+  if ((threadIdx.x & 63) == 0) {
+    atomicMin(bb + 0, lo0); atomicMin(bb + 1, lo1); atomicMin(bb + 2, lo2);
+    atomicMax(bb + 3, hi0); atomicMax(bb + 4, hi1); atomicMax(bb + 5, hi2);
+    atomicAdd(bb + 6, cnt);
+  }
+}
+
+// flag[0] |= 1 when a point is not finite (the source check of gorio_ndt_set_source_device)
+__global__ __launch_bounds__(256) void ndt_finite_kernel(const float* __restrict__ x, const float* __restrict__ y, const float* __restrict__ z, int n, int* __restrict__ flag) {
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  const bool bad = i < n && !ndt_finite3(x[i], y[i], z[i]);
+  if (__ballot(bad) != 0ull && (threadIdx.x & 63) == 0) atomicOr(flag, 1);
+}
+
+// keys[i] = leaf index << 31 | i, VGC:218-223 in float; ~0 for the sort's padding and for non-finite points (they sort behind the rest).
+// A finite point outside the grid (impossible while floor is monotone; kept as the bounds check of what follows) raises bb[7].
+__global__ __launch_bounds__(256) void ndt_key_kernel(const float* __restrict__ x, const float* __restrict__ y, const float* __restrict__ z, int n, int npow2, NdtGrid g,
+                                                      unsigned long long* __restrict__ keys, int* __restrict__ bb) {
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i >= npow2) return;
+  unsigned long long key = ~0ull;
+  if (i < n) {
+    const float px = x[i], py = y[i], pz = z[i];
+    if (ndt_finite3(px, py, pz)) {
+      const float f0 = floorf(px * g.inv) - (float)g.min_b[0];
+      const float f1 = floorf(py * g.inv) - (float)g.min_b[1];
+      const float f2 = floorf(pz * g.inv) - (float)g.min_b[2];
+      const bool ok = f0 >= 0.0f && f0 < (float)g.div_b[0] && f1 >= 0.0f && f1 < (float)g.div_b[1] && f2 >= 0.0f && f2 < (float)g.div_b[2];
+      if (ok) {
+        const long long idx = (long long)(int)f0 + (long long)(int)f1 * g.mul1 + (long long)(int)f2 * g.mul2;  // < 2^31, checked on the host
+        key = ((unsigned long long)idx << 31) | (unsigned long long)i;
+      } else {
+        atomicOr(bb + 7, 1);
+      }
+    }
+  }
+  keys[i] = key;
+}
+
+// general 3 x 3 inverse by cofactors (Eigen's fixed-size inverse), row-major
+__device__ __forceinline__ void ndt_inv3(const double* __restrict__ a, double* __restrict__ r) {
+  const double c00 = a[4] * a[8] - a[5] * a[7], c01 = a[5] * a[6] - a[3] * a[8], c02 = a[3] * a[7] - a[4] * a[6];
+  const double det = a[0] * c00 + a[1] * c01 + a[2] * c02;
+  const double s = 1.0 / det;
+  r[0] = c00 * s; r[1] = (a[2] * a[7] - a[1] * a[8]) * s; r[2] = (a[1] * a[5] - a[2] * a[4]) * s;
+  r[3] = c01 * s; r[4] = (a[0] * a[8] - a[2] * a[6]) * s; r[5] = (a[2] * a[3] - a[0] * a[5]) * s;
+  r[6] = c02 * s; r[7] = (a[1] * a[6] - a[0] * a[7]) * s; r[8] = (a[0] * a[4] - a[1] * a[3]) * s;
+}
+
+// One lane per leaf start of the sorted keys (rank as in vg_accum_kernel): the second pass of applyFilter, VGC:282-367, on the sums of
+// VGC:233-237 taken in input order (the key's low bits ascend inside a leaf).  n = number of finite points = real keys.
+__global__ __launch_bounds__(256) void ndt_leaf_kernel(const unsigned long long* __restrict__ keys, const float* __restrict__ x, const float* __restrict__ y,
+                                                       const float* __restrict__ z, int n, int n_points, const int* __restrict__ offsets, int min_points, double eig_mult,
+                                                       int nl, int* __restrict__ lidx, int* __restrict__ lcnt, double* __restrict__ lmean, double* __restrict__ lraw,
+                                                       double* __restrict__ lcov, double* __restrict__ licov) {
+  const int p = blockIdx.x * 256 + threadIdx.x;
+  const bool start = p < n && (p == 0 || (keys[p] >> 31) != (keys[p - 1] >> 31));
+  const unsigned long long m = __ballot(start);
+  __shared__ int sw[4];
+  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+  if (lane == 0) sw[wv] = __builtin_popcountll(m);
+  __syncthreads();
+  if (!start) return;
+  int rank = offsets[blockIdx.x] + __builtin_popcountll(m & ((1ull << lane) - 1ull));
+  for (int q = 0; q < wv; ++q) rank += sw[q];
+  if (rank < 0 || rank >= nl) return;
+  const unsigned long long leaf = keys[p] >> 31;
+  double s0 = 0.0, s1 = 0.0, s2 = 0.0;
+  double c[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
+  int cnt = 0;
+  for (int j = p; j < n && (keys[j] >> 31) == leaf; ++j) {
+    const int i = (int)(keys[j] & 0x7fffffffull);
+    if (i >= n_points) break;
+    const double px = (double)x[i], py = (double)y[i], pz = (double)z[i];
+    s0 += px; s1 += py; s2 += pz;  // VGC:235
+    c[0] += px * px; c[1] += px * py; c[2] += px * pz;  // VGC:237
+    c[3] += py * px; c[4] += py * py; c[5] += py * pz;
+    c[6] += pz * px; c[7] += pz * py; c[8] += pz * pz;
+    ++cnt;
+  }
+  const double nd = (double)cnt;
+  const double m0 = s0 / nd, m1 = s1 / nd, m2 = s2 / nd;  // VGC:293
+  lidx[rank] = (int)leaf;
+  double* om = lmean + (size_t)rank * 3;
+  om[0] = m0; om[1] = m1; om[2] = m2;
+  double raw[9], cov[9], ic[9];
+#pragma unroll
+  for (int q = 0; q < 9; ++q) raw[q] = cov[q] = ic[q] = 0.0;
+  int out_cnt = cnt;
+  if (cnt >= min_points) {  // VGC:297
+    const double ps[3] = {s0, s1, s2}, mn[3] = {m0, m1, m2};
+    const double f = (nd - 1.0) / nd;
+#pragma unroll
+    for (int r = 0; r < 3; ++r)
+#pragma unroll
+      for (int q = 0; q < 3; ++q) {
+        double v = (c[3 * r + q] - 2.0 * (ps[r] * mn[q])) / nd;  // VGC:329
+        v = v + mn[r] * mn[q];
+        raw[3 * r + q] = v * f;                                  // VGC:330
+        cov[3 * r + q] = raw[3 * r + q];
+      }
+    // SelfAdjointEigenSolver reads the lower triangle (VGC:333); w0 >= w1 >= w2 here, the reference's order is ascending
+    const Eig3 e = sym3_eigen(raw[0], raw[3], raw[6], raw[4], raw[7], raw[8]);
+    double ev0 = e.w2, ev1 = e.w1;
+    const double ev2 = e.w0;
+    if (ev0 < 0 || ev1 < 0 || ev2 <= 0) {  // VGC:337-341
+      out_cnt = -1;
+    } else {
+      const double lo = eig_mult * ev2;  // VGC:345
+      if (ev0 < lo) {
+        ev0 = lo;
+        if (ev1 < lo) ev1 = lo;
+        // cov_ = evecs_ * eigen_val * evecs_.inverse(), VGC:355; columns in ascending order
+        const double V[9] = {e.v02, e.v01, e.v00, e.v12, e.v11, e.v10, e.v22, e.v21, e.v20};
+        double Vi[9];
+        ndt_inv3(V, Vi);
+        const double w[3] = {ev0, ev1, ev2};
+#pragma unroll
+        for (int r = 0; r < 3; ++r)
+#pragma unroll
+          for (int q = 0; q < 3; ++q) cov[3 * r + q] = (V[3 * r] * w[0] * Vi[q] + V[3 * r + 1] * w[1] * Vi[3 + q]) + V[3 * r + 2] * w[2] * Vi[6 + q];
+      }
+      ndt_inv3(cov, ic);  // VGC:359
+      double mx = ic[0], mi = ic[0];
+#pragma unroll
+      for (int q = 1; q < 9; ++q) {
+        mx = ic[q] > mx ? ic[q] : mx;
+        mi = ic[q] < mi ? ic[q] : mi;
+      }
+      if (mx == INFINITY || mi == -INFINITY) out_cnt = -1;  // VGC:360-364
+    }
+  }
+  lcnt[rank] = out_cnt;
+#pragma unroll
+  for (int q = 0; q < 9; ++q) {
+    lraw[(size_t)rank * 9 + q] = raw[q];
+    lcov[(size_t)rank * 9 + q] = cov[q];
+    licov[(size_t)rank * 9 + q] = out_cnt >= min_points ? ic[q] : 0.0;
+  }
+}
+
+// floor(x / leaf_size) of VGC:379-381 as an int; false when it does not fit (or is not finite)
+__device__ __forceinline__ bool ndt_cell(float v, float leaf, int& c) {
+  const float f = floorf(v / leaf);
+  const bool ok = f > -(float)kNdtCoordLimit && f < (float)kNdtCoordLimit;  // false for NaN
+  c = ok ? (int)f : 0;
+  return ok;
+}
+
+// displacement o of getNeighborhoodAtPoint1 / 7 / getAllNeighborCellIndices (VGC:406-442), without a table
+__device__ __forceinline__ void ndt_offset(int n_off, int o, int& d0, int& d1, int& d2) {
+  d0 = 0; d1 = 0; d2 = 0;
+  if (n_off == 7) {
+    if (o > 0) {  // centre, +x, -x, +y, -y, +z, -z (VGC:423-430)
+      const int axis = (o - 1) >> 1, sgn = (o & 1) ? 1 : -1;
+      d0 = axis == 0 ? sgn : 0;
+      d1 = axis == 1 ? sgn : 0;
+      d2 = axis == 2 ? sgn : 0;
+    }
+  } else if (n_off == 26) {  // 13 half cells, then their negatives
+    const int h = o < 13 ? o : o - 13, sgn = o < 13 ? 1 : -1;
+    if (h < 9) { d0 = h / 3 - 1; d1 = h % 3 - 1; d2 = -1; }
+    else if (h < 12) { d0 = h - 10; d1 = -1; d2 = 0; }
+    else { d0 = -1; d1 = 0; d2 = 0; }
+    d0 *= sgn; d1 *= sgn; d2 *= sgn;
+  }
+}
+
+// VGC:382-399: the leaf at cell (c + d), or -1.  The diff2min / diff2max test keeps the cell inside the grid BEFORE it becomes an index.
+__device__ __forceinline__ int ndt_lookup(const NdtMapView& vm, int c0, int c1, int c2, int d0, int d1, int d2) {
+  const NdtGrid& g = vm.g;
+  if (g.min_b[0] - c0 > d0 || g.min_b[1] - c1 > d1 || g.min_b[2] - c2 > d2) return -1;
+  if (g.max_b[0] - c0 < d0 || g.max_b[1] - c1 < d1 || g.max_b[2] - c2 < d2) return -1;
+  const long long lin = (long long)(c0 + d0 - g.min_b[0]) + (long long)(c1 + d1 - g.min_b[1]) * g.mul1 + (long long)(c2 + d2 - g.min_b[2]) * g.mul2;
+  int lo = 0, hi = vm.nl;  // first position whose index is >= lin
+  for (int step = 0; step < 32 && lo < hi; ++step) {
+    const int mid = (lo + hi) >> 1;
+    if ((long long)vm.lidx[mid] < lin) lo = mid + 1;
+    else hi = mid;
+  }
+  if (lo >= vm.nl || (long long)vm.lidx[lo] != lin) return -1;
+  return vm.cnt[lo] >= vm.min_points ? lo : -1;  // VGC:395
+}
+
+template <typename S>
+__device__ __forceinline__ S ndt_dot3(S a0, S a1, S a2, S b0, S b1, S b2) {
+  S r = a0 * b0;
+  r = r + a1 * b1;
+  r = r + a2 * b2;
+  return r;
+}
+
+// One (point, leaf) pair.  S = float: updateDerivatives (NDT:484-537) after computePointDerivatives (NDT:398-440), every float operation
+// in one written order, left to right; S = double: updateHessian (NDT:613-645), Hessian only.
+// acc: [0] score, [1..6] gradient, [7..27] upper triangle of the Hessian, row-major.
+template <typename S, bool HESS>
+__device__ __forceinline__ void ndt_pair(const NdtEval& ev, const S (&jx)[8], const S (&hx)[15], float qx, float qy, float qz, const double* __restrict__ mean,
+                                         const double* __restrict__ icov, double (&acc)[28]) {
+  constexpr bool kFloat = sizeof(S) == 4;
+  const S xt0 = (S)((double)qx - mean[0]), xt1 = (S)((double)qy - mean[1]), xt2 = (S)((double)qz - mean[2]);  // NDT:259-262, 492
+  S C[9];
+#pragma unroll
+  for (int q = 0; q < 9; ++q) C[q] = (S)icov[q];  // NDT:494
+  const S xC0 = ndt_dot3<S>(xt0, xt1, xt2, C[0], C[3], C[6]);  // x_trans4 * c_inv4
+  const S xC1 = ndt_dot3<S>(xt0, xt1, xt2, C[1], C[4], C[7]);
+  const S xC2 = ndt_dot3<S>(xt0, xt1, xt2, C[2], C[5], C[8]);
+  const S d2 = (S)ev.d2;
+  S e;
+  if constexpr (kFloat) {
+    const S arg = (-d2 * ndt_dot3<S>(xt0, xt1, xt2, xC0, xC1, xC2)) * 0.5f;
+    e = (S)exp((double)arg);                 // NDT:499, the correctly rounded float
+    const float inc = (float)(-ev.d1 * (double)e);  // NDT:501
+    e = d2 * e;
+    if (e > 1 || e < 0 || e != e) return;    // NDT:506
+    acc[0] += (double)inc;
+    e = (S)((double)e * ev.d1);              // NDT:510
+  } else {
+    e = d2 * exp(-d2 * ndt_dot3<S>(xt0, xt1, xt2, xC0, xC1, xC2) / 2);  // NDT:622
+    if (e > 1 || e < 0 || e != e) return;
+    e = e * ev.d1;
+  }
+  // point_gradient4 (NDT:223-224, 407-414), columns
+  const S G[6][3] = {{1, 0, 0}, {0, 1, 0}, {0, 0, 1}, {0, jx[0], jx[1]}, {jx[2], jx[3], jx[4]}, {jx[5], jx[6], jx[7]}};
+  S CG[6][3], xCG[6];
+#pragma unroll
+  for (int k = 0; k < 6; ++k) {
+#pragma unroll
+    for (int r = 0; r < 3; ++r) CG[k][r] = ndt_dot3<S>(C[3 * r], C[3 * r + 1], C[3 * r + 2], G[k][0], G[k][1], G[k][2]);  // NDT:512
+    xCG[k] = ndt_dot3<S>(xt0, xt1, xt2, CG[k][0], CG[k][1], CG[k][2]);                                                   // NDT:513
+    if constexpr (kFloat) acc[1 + k] += (double)(e * xCG[k]);                                                            // NDT:515
+  }
+  if constexpr (HESS) {
+    // blocks (i, j), 3 <= i <= j, of the point Hessian (NDT:421-438): a, b, c have no x component
+    const S Hv[6][3] = {{0, hx[0], hx[1]}, {0, hx[2], hx[3]}, {0, hx[4], hx[5]}, {hx[6], hx[7], hx[8]}, {hx[9], hx[10], hx[11]}, {hx[12], hx[13], hx[14]}};
+    int t = 7;
+#pragma unroll
+    for (int i = 0; i < 6; ++i) {
+#pragma unroll
+      for (int j = i; j < 6; ++j) {
+        S v = (-d2 * xCG[i]) * xCG[j];
+        if (i >= 3) {
+          const int b = i == 3 ? j - 3 : (i == 4 ? j - 1 : 5);
+          v = v + ndt_dot3<S>(xC0, xC1, xC2, Hv[b][0], Hv[b][1], Hv[b][2]);  // NDT:525
+        }
+        v = v + ndt_dot3<S>(G[j][0], G[j][1], G[j][2], CG[i][0], CG[i][1], CG[i][2]);  // NDT:519, element (j, i)
+        acc[t] += (double)(e * v);                                                     // NDT:529
+        ++t;
+      }
+    }
+  }
+}
+
+// grid: ceil(n / 256), block 256.  One 28-double partial per block.
+template <typename S, bool HESS>
+__global__ __launch_bounds__(256) void ndt_derivative_kernel(const float* __restrict__ sx, const float* __restrict__ sy, const float* __restrict__ sz, int n, NdtMapView vm,
+                                                             NdtEval ev, double* __restrict__ partials) {
+  double acc[28];
+#pragma unroll
+  for (int q = 0; q < 28; ++q) acc[q] = 0.0;
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i < n) {
+    const float x = sx[i], y = sy[i], z = sz[i];
+    float qx, qy, qz;
+    transform_f(ev.T, x, y, z, qx, qy, qz);
+    int c0, c1, c2;
+    bool ok = ndt_cell(qx, vm.g.leaf, c0);
+    ok = ndt_cell(qy, vm.g.leaf, c1) && ok;
+    ok = ndt_cell(qz, vm.g.leaf, c2) && ok;
+    if (ok) {
+      S jx[8], hx[15];
+      constexpr bool kFloat = sizeof(S) == 4;
+#pragma unroll
+      for (int r = 0; r < 8; ++r) jx[r] = ndt_dot3<S>((S)ev.ja[3 * r], (S)ev.ja[3 * r + 1], (S)ev.ja[3 * r + 2], (S)x, (S)y, (S)z);  // NDT:405
+#pragma unroll
+      for (int r = 0; r < 15; ++r) {
+        S h2 = (S)ev.ha[3 * r + 2];
+        if (kFloat && r == 6) h2 = -h2;  // NDT:383: the float table holds +sy, the double one -sy (NDT:361)
+        hx[r] = HESS ? ndt_dot3<S>((S)ev.ha[3 * r], (S)ev.ha[3 * r + 1], h2, (S)x, (S)y, (S)z) : (S)0;  // NDT:418
+      }
+#pragma unroll 1
+      for (int o = 0; o < ev.n_off; ++o) {
+        int d0, d1, d2;
+        ndt_offset(ev.n_off, o, d0, d1, d2);
+        const int leaf = ndt_lookup(vm, c0, c1, c2, d0, d1, d2);
+        if (leaf < 0) continue;
+        ndt_pair<S, HESS>(ev, jx, hx, qx, qy, qz, vm.mean + (size_t)leaf * 3, vm.icov + (size_t)leaf * 9, acc);
+      }
+    }
+  }
+  __shared__ double red[4][28];
+  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+  {
+    double ws[7];
+    wave_sum28(acc, ws);
+    if ((lane & 15) == 0) {
+#pragma unroll
+      for (int k = 0; k < 7; ++k) red[wv][7 * (lane >> 4) + k] = ws[k];
+    }
+  }
+  __syncthreads();
+  if (threadIdx.x < 28) partials[(size_t)blockIdx.x * 28 + threadIdx.x] = (red[0][threadIdx.x] + red[1][threadIdx.x]) + (red[2][threadIdx.x] + red[3][threadIdx.x]);
+}
+
+// calculateScore, NDT:935-983: per point sum of score_inc / neighborhood.size(); one double per block
+__global__ __launch_bounds__(256) void ndt_score_kernel(const float* __restrict__ sx, const float* __restrict__ sy, const float* __restrict__ sz, int n, NdtMapView vm, NdtEval ev,
+                                                        double* __restrict__ partials) {
+  double sum = 0.0;
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i < n) {
+    float qx, qy, qz;
+    transform_f(ev.T, sx[i], sy[i], sz[i], qx, qy, qz);
+    int c0, c1, c2;
+    bool ok = ndt_cell(qx, vm.g.leaf, c0);
+    ok = ndt_cell(qy, vm.g.leaf, c1) && ok;
+    ok = ndt_cell(qz, vm.g.leaf, c2) && ok;
+    if (ok) {
+      int nn = 0;
+      double s = 0.0;
+#pragma unroll 1
+      for (int o = 0; o < ev.n_off; ++o) {
+        int d0, d1, d2;
+        ndt_offset(ev.n_off, o, d0, d1, d2);
+        const int leaf = ndt_lookup(vm, c0, c1, c2, d0, d1, d2);
+        if (leaf < 0) continue;
+        const double* mean = vm.mean + (size_t)leaf * 3;
+        const double* C = vm.icov + (size_t)leaf * 9;
+        const double x0 = (double)qx - mean[0], x1 = (double)qy - mean[1], x2 = (double)qz - mean[2];
+        const double q = ndt_dot3<double>(x0, x1, x2, ndt_dot3<double>(C[0], C[1], C[2], x0, x1, x2), ndt_dot3<double>(C[3], C[4], C[5], x0, x1, x2),
+                                          ndt_dot3<double>(C[6], C[7], C[8], x0, x1, x2));
+        s += -ev.d1 * exp(-ev.d2 * q / 2) - ev.d3;  // NDT:975-977
+        ++nn;
+      }
+      if (nn) sum = s / (double)nn;  // NDT:979
+    }
+  }
+  sum = wave_sum(sum);
+  __shared__ double red[4];
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = sum;
+  __syncthreads();
+  if (threadIdx.x == 0) partials[blockIdx.x] = (red[0] + red[1]) + (red[2] + red[3]);
+}
+
+// out[k] = sum over the blocks, in block order, of partials[b * width + k]; width <= 64.  grid 1, block 64
+__global__ __launch_bounds__(64) void ndt_fold_kernel(const double* __restrict__ partials, int nblk, int width, double* __restrict__ out) {
+  if ((int)threadIdx.x >= width) return;
+  double s = 0.0;
+  for (int b = 0; b < nblk; ++b) s += partials[(size_t)b * width + threadIdx.x];
+  out[threadIdx.x] = s;
+}
+
+}  // namespace gorio
+
+// ================================================================================================= host (include/gorio_ndt.h)
+struct gorio_ndt {
+  int device = 0;
+  hipStream_t stream = nullptr;
+  gorio_ndt_params p;
+  // clouds, SoA
+  gorio::DevBuf<float> tx, ty, tz, sx, sy, sz;
+  size_t t_cap = 0, s_cap = 0;
+  int n_t = 0, n_s = 0;
+  bool has_target = false, has_source = false;
+  // voxel map (target_cells_): stale after a new target or a changed resolution / leaf rule, rebuilt by the next call that needs it
+  gorio::DevBuf<unsigned long long> keys;
+  gorio::DevBuf<int> counts, bb, flag;
+  gorio::DevBuf<int> lidx, lcnt;
+  gorio::DevBuf<double> lmean, lraw, lcov, licov;
+  size_t l_cap = 0;
+  int nl = 0;
+  gorio::NdtGrid grid{};
+  bool map_valid = false;
+  // evaluation scratch
+  gorio::DevBuf<double> partials, d_out;
+  gorio::PinnedBuf h_out;  // 28 doubles
+  gorio::NdtMapView map() const { return gorio::NdtMapView{lidx, lcnt, lmean, licov, nl, p.min_points_per_voxel, grid}; }
+};
+
+namespace {
+thread_local std::string g_ndt_err;
+int ndt_fail(int code, const std::string& m) {
+  g_ndt_err = m;
+  return code;
+}
+
+float ndt_decode(int k) {  // sc_decode on the host
+  const int i = k >= 0 ? k : k ^ 0x7fffffff;
+  float f;
+  std::memcpy(&f, &i, 4);
+  return f;
+}
+
+int ndt_n_off(int search) { return search == GORIO_NDT_DIRECT1 ? 1 : search == GORIO_NDT_DIRECT7 ? 7 : 26; }
+
+int ndt_check_params(const gorio_ndt_params& p) {
+  if (p.search == GORIO_NDT_KDTREE) return ndt_fail(GORIO_ERR_UNSUPPORTED, "set_params: KDTREE search is not built (a radius search over leaf centroids)");
+  if (p.search != GORIO_NDT_DIRECT26 && p.search != GORIO_NDT_DIRECT7 && p.search != GORIO_NDT_DIRECT1) return ndt_fail(GORIO_ERR_UNSUPPORTED, "set_params: unknown search method");
+  if (!(p.resolution > 0) || !std::isfinite(p.resolution)) return ndt_fail(GORIO_ERR_UNSUPPORTED, "set_params: resolution must be finite and > 0");
+  if (p.min_points_per_voxel < 1) return ndt_fail(GORIO_ERR_INVALID, "set_params: min_points_per_voxel < 1");
+  if (std::isnan(p.step_size) || std::isnan(p.outlier_ratio) || std::isnan(p.transformation_epsilon) || std::isnan(p.min_covar_eigvalue_mult))
+    return ndt_fail(GORIO_ERR_INVALID, "set_params: NaN parameter");
+  return GORIO_OK;
+}
+
+// SoA upload of a strided host cloud into (x, y, z) of one capacity
+int ndt_upload(gorio_ndt* h, const float* xyz, int n, int stride_bytes, gorio::DevBuf<float>& x, gorio::DevBuf<float>& y, gorio::DevBuf<float>& z, size_t& cap) {
+  std::vector<float> soa;
+  try {
+    soa.resize((size_t)3 * std::max(n, 1));
+  } catch (const std::bad_alloc&) {
+    return ndt_fail(GORIO_ERR_ALLOC, "out of host memory for the staging copy of the cloud");
+  }
+  const size_t st = stride_bytes / 4;
+  for (int i = 0; i < n; ++i) {
+    soa[i] = xyz[st * i];
+    soa[(size_t)n + i] = xyz[st * i + 1];
+    soa[(size_t)2 * n + i] = xyz[st * i + 2];
+  }
+  GORIO_HIP_CHECK(ndt_fail, hipSetDevice(h->device));
+  const size_t need = std::max(n, 1);
+  GORIO_HIP_CHECK(ndt_fail, gorio::reserve_group(cap, need, need + need / 8 + 64, x, need + need / 8 + 64, y, need + need / 8 + 64, z, need + need / 8 + 64));
+  if (n) {
+    GORIO_HIP_CHECK(ndt_fail, hipMemcpyAsync(x, soa.data(), sizeof(float) * n, hipMemcpyHostToDevice, h->stream));
+    GORIO_HIP_CHECK(ndt_fail, hipMemcpyAsync(y, soa.data() + n, sizeof(float) * n, hipMemcpyHostToDevice, h->stream));
+    GORIO_HIP_CHECK(ndt_fail, hipMemcpyAsync(z, soa.data() + (size_t)2 * n, sizeof(float) * n, hipMemcpyHostToDevice, h->stream));
+  }
+  GORIO_HIP_CHECK(ndt_fail, hipStreamSynchronize(h->stream));  // soa dies here
+  return GORIO_OK;
+}
+
+int ndt_copy_device(gorio_ndt* h, const float* x, const float* y, const float* z, int n, gorio::DevBuf<float>& dx, gorio::DevBuf<float>& dy, gorio::DevBuf<float>& dz, size_t& cap) {
+  GORIO_HIP_CHECK(ndt_fail, hipSetDevice(h->device));
+  const size_t need = std::max(n, 1);
+  GORIO_HIP_CHECK(ndt_fail, gorio::reserve_group(cap, need, need + need / 8 + 64, dx, need + need / 8 + 64, dy, need + need / 8 + 64, dz, need + need / 8 + 64));
+  if (n) {
+    GORIO_HIP_CHECK(ndt_fail, hipMemcpyAsync(dx, x, sizeof(float) * n, hipMemcpyDeviceToDevice, h->stream));
+    GORIO_HIP_CHECK(ndt_fail, hipMemcpyAsync(dy, y, sizeof(float) * n, hipMemcpyDeviceToDevice, h->stream));
+    GORIO_HIP_CHECK(ndt_fail, hipMemcpyAsync(dz, z, sizeof(float) * n, hipMemcpyDeviceToDevice, h->stream));
+  }
+  GORIO_HIP_CHECK(ndt_fail, hipStreamSynchronize(h->stream));
+  return GORIO_OK;
+}
+
+// init() (NDTH:276-283) -> VoxelGridCovariance::applyFilter (VGC:60-370) when the map is stale
+int ndt_ensure_map(gorio_ndt* h) {
+  using namespace gorio;
+  if (h->map_valid) return GORIO_OK;
+  if (!h->has_target) return ndt_fail(GORIO_ERR_STATE, "no target set");
+  GORIO_HIP_CHECK(ndt_fail, hipSetDevice(h->device));
+  const int n = h->n_t;
+  h->nl = 0;
+  h->grid = NdtGrid{};
+  h->grid.leaf = (float)h->p.resolution;
+  h->grid.inv = 1.0f / h->grid.leaf;
+  if (n == 0) {
+    h->map_valid = true;
+    return GORIO_OK;
+  }
+  GORIO_HIP_CHECK(ndt_fail, h->bb.reserve(8));
+  ndt_bbox_init_kernel<<<1, 64, 0, h->stream>>>(h->bb);
+  ndt_bbox_kernel<<<std::min(256, (n + 255) / 256), 256, 0, h->stream>>>(h->tx, h->ty, h->tz, n, h->bb);
+  int bb[8];
+  GORIO_HIP_CHECK(ndt_fail, hipMemcpyAsync(bb, h->bb, sizeof(int) * 8, hipMemcpyDeviceToHost, h->stream));
+  GORIO_HIP_CHECK(ndt_fail, hipStreamSynchronize(h->stream));
+  const int n_fin = bb[6];
+  if (n_fin < 0 || n_fin > n) return ndt_fail(GORIO_ERR_STATE, "voxel map: internal error, the finite-point count does not fit the cloud");
+  if (n_fin == 0) {
+    h->map_valid = true;
+    return GORIO_OK;
+  }
+  NdtGrid g = h->grid;
+  double cells_f = 1.0, cells_b = 1.0;
+  for (int a = 0; a < 3; ++a) {
+    const float lo = ndt_decode(bb[a]), hi = ndt_decode(bb[3 + a]);
+    const float d = (hi - lo) * g.inv;  // VGC:75-77
+    cells_f *= std::floor((double)d) + 1.0;
+    const float fl = std::floor(lo * g.inv), fh = std::floor(hi * g.inv);  // VGC:87-92
+    if (!(std::fabs(fl) < (float)kNdtCoordLimit) || !(std::fabs(fh) < (float)kNdtCoordLimit))
+      return ndt_fail(GORIO_ERR_UNSUPPORTED, "voxel map: a leaf coordinate of the target does not fit 31 bits");
+    g.min_b[a] = (int)fl;
+    g.max_b[a] = (int)fh;
+    g.div_b[a] = g.max_b[a] - g.min_b[a] + 1;  // VGC:95
+    cells_b *= (double)g.div_b[a];
+  }
+  if (cells_f > 2147483647.0 || cells_b > 2147483647.0)  // VGC:79-84
+    return ndt_fail(GORIO_ERR_UNSUPPORTED, "voxel map: leaf size is too small for the target, integer leaf indices would overflow");
+  g.mul1 = g.div_b[0];  // VGC:103
+  g.mul2 = g.div_b[0] * g.div_b[1];
+  const int npow2 = sort_padded_size(n);
+  const int nblocks = (n_fin + 255) / 256;
+  GORIO_HIP_CHECK(ndt_fail, h->keys.reserve(npow2));
+  GORIO_HIP_CHECK(ndt_fail, h->counts.reserve((size_t)(n + 255) / 256 + 1));
+  ndt_key_kernel<<<(npow2 + 255) / 256, 256, 0, h->stream>>>(h->tx, h->ty, h->tz, n, npow2, g, h->keys, h->bb);
+  enqueue_tiled_sort(h->stream, SortKeys{h->keys, npow2}, 1, npow2);
+  vox_count_kernel<<<nblocks, 256, 0, h->stream>>>(h->keys, n_fin, h->counts);
+  vox_scan_kernel<<<1, 1024, 0, h->stream>>>(h->counts, nblocks);
+  int nv = 0, flags = 0;
+  GORIO_HIP_CHECK(ndt_fail, hipMemcpyAsync(&nv, h->counts + nblocks, sizeof(int), hipMemcpyDeviceToHost, h->stream));
+  GORIO_HIP_CHECK(ndt_fail, hipMemcpyAsync(&flags, h->bb + 7, sizeof(int), hipMemcpyDeviceToHost, h->stream));
+  GORIO_HIP_CHECK(ndt_fail, hipStreamSynchronize(h->stream));
+  if (flags) return ndt_fail(GORIO_ERR_UNSUPPORTED, "voxel map: a target point falls outside the leaf grid (float leaf arithmetic out of range)");
+  if (nv <= 0 || nv > n_fin) return ndt_fail(GORIO_ERR_STATE, "voxel map: internal error, the leaf count does not fit the cloud");
+  {
+    const size_t cap = (size_t)nv + nv / 8 + 64;
+    GORIO_HIP_CHECK(ndt_fail, reserve_group(h->l_cap, nv, cap, h->lidx, cap, h->lcnt, cap, h->lmean, 3 * cap, h->lraw, 9 * cap, h->lcov, 9 * cap, h->licov, 9 * cap));
+  }
+  ndt_leaf_kernel<<<nblocks, 256, 0, h->stream>>>(h->keys, h->tx, h->ty, h->tz, n_fin, n, h->counts, h->p.min_points_per_voxel, h->p.min_covar_eigvalue_mult, nv, h->lidx, h->lcnt,
+                                                  h->lmean, h->lraw, h->lcov, h->licov);
+  GORIO_HIP_CHECK(ndt_fail, hipGetLastError());
+  GORIO_HIP_CHECK(ndt_fail, hipStreamSynchronize(h->stream));
+  h->nl = nv;
+  h->grid = g;
+  h->map_valid = true;
+  return GORIO_OK;
+}
+
+// ---- host arithmetic of the shell (plain C++, this file is built un-fused)
+
+float ndt_sinf(float a) { return (float)std::sin((double)a); }  // the correctly rounded float results, include/gorio_ndt.h
+float ndt_cosf(float a) { return (float)std::cos((double)a); }
+float ndt_atan2f(float a, float b) { return (float)std::atan2((double)a, (double)b); }
+
+// AngleAxis<float>(angle, unit axis).toRotationMatrix(), Eigen 3.3.7
+void ndt_angle_axis(float angle, int axis, float R[9]) {
+  float a[3] = {0, 0, 0};
+  a[axis] = 1.0f;
+  const float s = ndt_sinf(angle), c = ndt_cosf(angle);
+  const float sa[3] = {s * a[0], s * a[1], s * a[2]};
+  const float c1[3] = {(1.0f - c) * a[0], (1.0f - c) * a[1], (1.0f - c) * a[2]};
+  float t = c1[0] * a[1];
+  R[1] = t - sa[2]; R[3] = t + sa[2];
+  t = c1[0] * a[2];
+  R[2] = t + sa[1]; R[6] = t - sa[1];
+  t = c1[1] * a[2];
+  R[5] = t - sa[0]; R[7] = t + sa[0];
+  for (int k = 0; k < 3; ++k) R[4 * k] = c1[k] * a[k] + c;
+}
+void ndt_mul3f(const float* A, const float* B, float* C) {
+  for (int i = 0; i < 3; ++i)
+    for (int j = 0; j < 3; ++j) {
+      float v = A[3 * i] * B[j];
+      v = v + A[3 * i + 1] * B[3 + j];
+      v = v + A[3 * i + 2] * B[6 + j];
+      C[3 * i + j] = v;
+    }
+}
+// Translation * AngleAxis(X) * AngleAxis(Y) * AngleAxis(Z) in float, NDT:827-830; T row-major 4 x 4
+void ndt_pose_matrix(const double* p, float* T) {
+  float Rx[9], Ry[9], Rz[9], A[9], R[9];
+  ndt_angle_axis((float)p[3], 0, Rx);
+  ndt_angle_axis((float)p[4], 1, Ry);
+  ndt_angle_axis((float)p[5], 2, Rz);
+  ndt_mul3f(Rx, Ry, A);
+  ndt_mul3f(A, Rz, R);
+  for (int r = 0; r < 3; ++r) {
+    for (int c = 0; c < 3; ++c) T[4 * r + c] = R[3 * r + c];
+    T[4 * r + 3] = (float)p[r];
+  }
+  T[12] = T[13] = T[14] = 0.0f;
+  T[15] = 1.0f;
+}
+// eulerAngles(0, 1, 2) of the float rotation, Eigen 3.3.7 EulerAngles.h (NDT:109)
+void ndt_euler012(const float* T, float* out) {
+  auto R = [&](int r, int c) { return T[4 * r + c]; };
+  float r0 = ndt_atan2f(R(1, 2), R(2, 2)), r1;
+  const float c2 = std::sqrt(R(0, 0) * R(0, 0) + R(0, 1) * R(0, 1));
+  if (r0 > 0.0f) {
+    r0 = r0 - (float)M_PI;
+    r1 = ndt_atan2f(-R(0, 2), -c2);
+  } else {
+    r1 = ndt_atan2f(-R(0, 2), c2);
+  }
+  const float s1 = ndt_sinf(r0), c1 = ndt_cosf(r0);
+  const float r2 = ndt_atan2f(s1 * R(2, 0) - c1 * R(1, 0), c1 * R(1, 1) - s1 * R(2, 1));
+  out[0] = -r0; out[1] = -r1; out[2] = -r2;
+}
+
+// computeAngleDerivatives, NDT:288-395, in double (the kernel rounds to float where the reference does)
+void ndt_angle_tables(const double* p, double* ja, double* ha) {
+  double cx, cy, cz, sx, sy, sz;
+  if (std::fabs(p[3]) < 10e-5) { cx = 1.0; sx = 0.0; } else { cx = std::cos(p[3]); sx = std::sin(p[3]); }
+  if (std::fabs(p[4]) < 10e-5) { cy = 1.0; sy = 0.0; } else { cy = std::cos(p[4]); sy = std::sin(p[4]); }
+  if (std::fabs(p[5]) < 10e-5) { cz = 1.0; sz = 0.0; } else { cz = std::cos(p[5]); sz = std::sin(p[5]); }
+  const double j[24] = {(-sx * sz + cx * sy * cz), (-sx * cz - cx * sy * sz), (-cx * cy),
+                        (cx * sz + sx * sy * cz), (cx * cz - sx * sy * sz), (-sx * cy),
+                        (-sy * cz), sy * sz, cy,
+                        sx * cy * cz, (-sx * cy * sz), sx * sy,
+                        (-cx * cy * cz), cx * cy * sz, (-cx * sy),
+                        (-cy * sz), (-cy * cz), 0,
+                        (cx * cz - sx * sy * sz), (-cx * sz - sx * sy * cz), 0,
+                        (sx * cz + cx * sy * sz), (cx * sy * cz - sx * sz), 0};
+  const double hh[45] = {(-cx * sz - sx * sy * cz), (-cx * cz + sx * sy * sz), sx * cy,
+                         (-sx * sz + cx * sy * cz), (-cx * sy * sz - sx * cz), (-cx * cy),
+                         (cx * cy * cz), (-cx * cy * sz), (cx * sy),
+                         (sx * cy * cz), (-sx * cy * sz), (sx * sy),
+                         (-sx * cz - cx * sy * sz), (sx * sz - cx * sy * cz), 0,
+                         (cx * cz - sx * sy * sz), (-sx * sy * cz - cx * sz), 0,
+                         (-cy * cz), (cy * sz), (-sy),
+                         (-sx * sy * cz), (sx * sy * sz), (sx * cy),
+                         (cx * sy * cz), (-cx * sy * sz), (-cx * cy),
+                         (sy * sz), (sy * cz), 0,
+                         (-sx * cy * sz), (-sx * cy * cz), 0,
+                         (cx * cy * sz), (cx * cy * cz), 0,
+                         (-cy * cz), (cy * sz), 0,
+                         (-cx * sz - sx * sy * cz), (-cx * cz + sx * sy * sz), 0,
+                         (-sx * sz + cx * sy * cz), (-cx * sy * sz - sx * cz), 0};
+  std::copy(j, j + 24, ja);
+  std::copy(hh, hh + 45, ha);
+}
+
+gorio::NdtEval ndt_make_eval(const gorio_ndt* h, const double* p, const float* T) {
+  gorio::NdtEval ev{};
+  for (int q = 0; q < 12; ++q) ev.T[q] = T[q];
+  if (p) ndt_angle_tables(p, ev.ja, ev.ha);
+  // NDT:89-93; resolution_ is a float member
+  const double res = (double)(float)h->p.resolution;
+  const double c1 = 10 * (1 - h->p.outlier_ratio), c2 = h->p.outlier_ratio / std::pow(res, 3);
+  ev.d3 = -std::log(c2);
+  ev.d1 = -std::log(c1 + c2) - ev.d3;
+  ev.d2 = -2 * std::log((-std::log(c1 * std::exp(-0.5) + c2) - ev.d3) / ev.d1);
+  ev.n_off = ndt_n_off(h->p.search);
+  return ev;
+}
+
+// one evaluation: mode 0 computeDerivatives without the Hessian, 1 with it, 2 computeHessian, 3 calculateScore.  out: 28 doubles
+int ndt_evaluate(gorio_ndt* h, const gorio::NdtEval& ev, int mode, double* out) {
+  using namespace gorio;
+  const int n = h->n_s, nblk = (n + 255) / 256;
+  const int width = mode == 3 ? 1 : 28;
+  GORIO_HIP_CHECK(ndt_fail, h->partials.reserve((size_t)28 * nblk, (size_t)28 * (nblk + nblk / 8 + 4)));
+  GORIO_HIP_CHECK(ndt_fail, h->d_out.reserve(28));
+  if (!h->h_out.get()) GORIO_HIP_CHECK(ndt_fail, h->h_out.realloc(sizeof(double) * 28));
+  const NdtMapView vm = h->map();
+  if (mode == 0) ndt_derivative_kernel<float, false><<<nblk, 256, 0, h->stream>>>(h->sx, h->sy, h->sz, n, vm, ev, h->partials);
+  else if (mode == 1) ndt_derivative_kernel<float, true><<<nblk, 256, 0, h->stream>>>(h->sx, h->sy, h->sz, n, vm, ev, h->partials);
+  else if (mode == 2) ndt_derivative_kernel<double, true><<<nblk, 256, 0, h->stream>>>(h->sx, h->sy, h->sz, n, vm, ev, h->partials);
+  else ndt_score_kernel<<<nblk, 256, 0, h->stream>>>(h->sx, h->sy, h->sz, n, vm, ev, h->partials);
+  ndt_fold_kernel<<<1, 64, 0, h->stream>>>(h->partials, nblk, width, h->d_out);
+  GORIO_HIP_CHECK(ndt_fail, hipGetLastError());
+  GORIO_HIP_CHECK(ndt_fail, hipMemcpyAsync(h->h_out.get(), h->d_out, sizeof(double) * width, hipMemcpyDeviceToHost, h->stream));
+  GORIO_HIP_CHECK(ndt_fail, hipStreamSynchronize(h->stream));
+  std::memcpy(out, h->h_out.get(), sizeof(double) * width);
+  return GORIO_OK;
+}
+
+void ndt_unpack_hessian(const double* acc, double* H) {  // upper triangle, mirrored
+  int t = 7;
+  for (int i = 0; i < 6; ++i)
+    for (int j = i; j < 6; ++j, ++t) H[6 * i + j] = H[6 * j + i] = acc[t];
+}
+
+int ndt_ready(gorio_ndt* h, const char* what) {
+  if (!h) return ndt_fail(GORIO_ERR_INVALID, std::string(what) + ": null handle");
+  GORIO_HIP_CHECK(ndt_fail, hipSetDevice(h->device));  // the evaluation scratch below is allocated on the handle's device, whatever the caller left current
+  if (!h->has_target) return ndt_fail(GORIO_ERR_STATE, std::string(what) + ": no target set");
+  if (!h->has_source || h->n_s == 0) return ndt_fail(GORIO_ERR_STATE, std::string(what) + ": no source set (or an empty one)");
+  if (const int rc = ndt_ensure_map(h)) return rc;
+  if (h->nl == 0) return ndt_fail(GORIO_ERR_STATE, std::string(what) + ": the target has no finite point");
+  return GORIO_OK;
+}
+
+// JacobiSVD<6x6 double>(H).solve(b) for the symmetric H: cyclic Jacobi H = V L V^T, x = V L^+ V^T b, |L| <= 6 eps max|L| -> 0
+void ndt_svd_solve(const double* Hin, const double* b, double* x) {
+  double A[36], V[36];
+  for (int i = 0; i < 36; ++i) {
+    A[i] = Hin[i];
+    V[i] = (i % 7 == 0) ? 1.0 : 0.0;
+  }
+  for (int sweep = 0; sweep < 60; ++sweep) {
+    double off = 0.0;
+    for (int i = 0; i < 6; ++i)
+      for (int j = i + 1; j < 6; ++j) off += A[6 * i + j] * A[6 * i + j];
+    if (off == 0.0) break;
+    for (int pp = 0; pp < 6; ++pp)
+      for (int q = pp + 1; q < 6; ++q) {
+        const double apq = A[6 * pp + q];
+        if (apq == 0.0) continue;
+        const double g = 100.0 * std::fabs(apq);
+        if (sweep > 3 && std::fabs(A[7 * pp]) + g == std::fabs(A[7 * pp]) && std::fabs(A[7 * q]) + g == std::fabs(A[7 * q])) {
+          A[6 * pp + q] = A[6 * q + pp] = 0.0;
+          continue;
+        }
+        const double theta = (A[7 * q] - A[7 * pp]) / (2.0 * apq);
+        double t = 1.0 / (std::fabs(theta) + std::sqrt(theta * theta + 1.0));
+        if (theta < 0.0) t = -t;
+        const double c = 1.0 / std::sqrt(t * t + 1.0), s = t * c;
+        for (int k = 0; k < 6; ++k) {  // A <- A J
+          const double akp = A[6 * k + pp], akq = A[6 * k + q];
+          A[6 * k + pp] = c * akp - s * akq;
+          A[6 * k + q] = s * akp + c * akq;
+        }
+        for (int k = 0; k < 6; ++k) {  // A <- J^T A
+          const double apk = A[6 * pp + k], aqk = A[6 * q + k];
+          A[6 * pp + k] = c * apk - s * aqk;
+          A[6 * q + k] = s * apk + c * aqk;
+        }
+        A[6 * pp + q] = A[6 * q + pp] = 0.0;
+        for (int k = 0; k < 6; ++k) {
+          const double vkp = V[6 * k + pp], vkq = V[6 * k + q];
+          V[6 * k + pp] = c * vkp - s * vkq;
+          V[6 * k + q] = s * vkp + c * vkq;
+        }
+      }
+  }
+  double smax = 0.0;
+  for (int i = 0; i < 6; ++i) smax = std::max(smax, std::fabs(A[7 * i]));
+  const double thr = 6 * 2.220446049250313e-16 * smax;
+  for (int i = 0; i < 6; ++i) x[i] = 0.0;
+  for (int k = 0; k < 6; ++k) {
+    if (!(std::fabs(A[7 * k]) > thr)) continue;
+    double y = 0.0;
+    for (int i = 0; i < 6; ++i) y += V[6 * i + k] * b[i];
+    y /= A[7 * k];
+    for (int i = 0; i < 6; ++i) x[i] += V[6 * i + k] * y;
+  }
+}
+
+// trialValueSelectionMT, NDT:689-769
+double ndt_trial_value(double a_l, double f_l, double g_l, double a_u, double f_u, double g_u, double a_t, double f_t, double g_t) {
+  if (f_t > f_l) {
+    const double z = 3 * (f_t - f_l) / (a_t - a_l) - g_t - g_l;
+    const double w = std::sqrt(z * z - g_t * g_l);
+    const double a_c = a_l + (a_t - a_l) * (w - g_l - z) / (g_t - g_l + 2 * w);
+    const double a_q = a_l - 0.5 * (a_l - a_t) * g_l / (g_l - (f_l - f_t) / (a_l - a_t));
+    if (std::fabs(a_c - a_l) < std::fabs(a_q - a_l)) return a_c;
+    return 0.5 * (a_q + a_c);
+  } else if (g_t * g_l < 0) {
+    const double z = 3 * (f_t - f_l) / (a_t - a_l) - g_t - g_l;
+    const double w = std::sqrt(z * z - g_t * g_l);
+    const double a_c = a_l + (a_t - a_l) * (w - g_l - z) / (g_t - g_l + 2 * w);
+    const double a_s = a_l - (a_l - a_t) / (g_l - g_t) * g_l;
+    if (std::fabs(a_c - a_t) >= std::fabs(a_s - a_t)) return a_c;
+    return a_s;
+  } else if (std::fabs(g_t) <= std::fabs(g_l)) {
+    const double z = 3 * (f_t - f_l) / (a_t - a_l) - g_t - g_l;
+    const double w = std::sqrt(z * z - g_t * g_l);
+    const double a_c = a_l + (a_t - a_l) * (w - g_l - z) / (g_t - g_l + 2 * w);
+    const double a_s = a_l - (a_l - a_t) / (g_l - g_t) * g_l;
+    const double a_t_next = std::fabs(a_c - a_t) < std::fabs(a_s - a_t) ? a_c : a_s;
+    if (a_t > a_l) return std::min(a_t + 0.66 * (a_u - a_t), a_t_next);
+    return std::max(a_t + 0.66 * (a_u - a_t), a_t_next);
+  }
+  const double z = 3 * (f_t - f_u) / (a_t - a_u) - g_t - g_u;
+  const double w = std::sqrt(z * z - g_t * g_u);
+  return a_u + (a_t - a_u) * (w - g_u - z) / (g_t - g_u + 2 * w);
+}
+
+// updateIntervalMT, NDT:648-686
+bool ndt_update_interval(double& a_l, double& f_l, double& g_l, double& a_u, double& f_u, double& g_u, double a_t, double f_t, double g_t) {
+  if (f_t > f_l) {
+    a_u = a_t; f_u = f_t; g_u = g_t;
+    return false;
+  } else if (g_t * (a_l - a_t) > 0) {
+    a_l = a_t; f_l = f_t; g_l = g_t;
+    return false;
+  } else if (g_t * (a_l - a_t) < 0) {
+    a_u = a_l; f_u = f_l; g_u = g_l;
+    a_l = a_t; f_l = f_t; g_l = g_t;
+    return false;
+  }
+  return true;
+}
+
+struct NdtState {  // what computeTransformation carries between the calls
+  double score = 0.0, g[6], H[36];
+  float T[16];
+  gorio_ndt_diag diag{};
+};
+
+int ndt_derivs_at(gorio_ndt* h, NdtState& st, const double* p, const float* T, bool hessian) {
+  double acc[28];
+  const gorio::NdtEval ev = ndt_make_eval(h, p, T);
+  if (const int rc = ndt_evaluate(h, ev, hessian ? 1 : 0, acc)) return rc;
+  st.score = acc[0];
+  for (int k = 0; k < 6; ++k) st.g[k] = acc[1 + k];
+  if (hessian) ndt_unpack_hessian(acc, st.H);
+  st.diag.n_derivatives++;
+  return GORIO_OK;
+}
+
+// computeStepLengthMT, NDT:772-932
+int ndt_step_length(gorio_ndt* h, NdtState& st, const double* x, double* step_dir, double step_init, double step_max, double step_min, double* a_out) {
+  const double phi_0 = -st.score;
+  double d_phi_0 = 0.0;
+  for (int k = 0; k < 6; ++k) d_phi_0 += st.g[k] * step_dir[k];
+  d_phi_0 = -d_phi_0;
+  if (d_phi_0 >= 0) {
+    if (d_phi_0 == 0) {
+      *a_out = 0;
+      return GORIO_OK;
+    }
+    d_phi_0 *= -1;
+    for (int k = 0; k < 6; ++k) step_dir[k] *= -1;
+  }
+  const int max_step_iterations = 10;
+  int step_iterations = 0;
+  const double mu = 1.e-4, nu = 0.9;
+  double a_l = 0, a_u = 0;
+  double f_l = phi_0 - phi_0 - mu * d_phi_0 * a_l, g_l = d_phi_0 - mu * d_phi_0;  // auxiliaryFunction_PsiMT / _dPsiMT, NDTH:433, 446
+  double f_u = phi_0 - phi_0 - mu * d_phi_0 * a_u, g_u = d_phi_0 - mu * d_phi_0;
+  bool interval_converged = (step_max - step_min) < 0, open_interval = true;
+  double a_t = step_init;
+  a_t = std::min(a_t, step_max);
+  a_t = std::max(a_t, step_min);
+  double x_t[6];
+  for (int k = 0; k < 6; ++k) x_t[k] = x[k] + step_dir[k] * a_t;
+  ndt_pose_matrix(x_t, st.T);  // NDT:827-830
+  if (const int rc = ndt_derivs_at(h, st, x_t, st.T, true)) return rc;  // NDT:837
+  auto dir_dot = [&]() {
+    double s = 0.0;
+    for (int k = 0; k < 6; ++k) s += st.g[k] * step_dir[k];
+    return s;
+  };
+  double phi_t = -st.score, d_phi_t = -dir_dot();
+  double psi_t = phi_t - phi_0 - mu * d_phi_0 * a_t, d_psi_t = d_phi_t - mu * d_phi_0;
+  while (!interval_converged && step_iterations < max_step_iterations && !(psi_t <= 0 && d_phi_t <= -nu * d_phi_0)) {
+    if (open_interval) a_t = ndt_trial_value(a_l, f_l, g_l, a_u, f_u, g_u, a_t, psi_t, d_psi_t);
+    else a_t = ndt_trial_value(a_l, f_l, g_l, a_u, f_u, g_u, a_t, phi_t, d_phi_t);
+    a_t = std::min(a_t, step_max);
+    a_t = std::max(a_t, step_min);
+    for (int k = 0; k < 6; ++k) x_t[k] = x[k] + step_dir[k] * a_t;
+    ndt_pose_matrix(x_t, st.T);
+    if (const int rc = ndt_derivs_at(h, st, x_t, st.T, false)) return rc;  // NDT:881
+    phi_t = -st.score;
+    d_phi_t = -dir_dot();
+    psi_t = phi_t - phi_0 - mu * d_phi_0 * a_t;
+    d_psi_t = d_phi_t - mu * d_phi_0;
+    if (open_interval && (psi_t <= 0 && d_psi_t >= 0)) {
+      open_interval = false;
+      f_l = f_l + phi_0 - mu * d_phi_0 * a_l;
+      g_l = g_l + mu * d_phi_0;
+      f_u = f_u + phi_0 - mu * d_phi_0 * a_u;
+      g_u = g_u + mu * d_phi_0;
+    }
+    if (open_interval) interval_converged = ndt_update_interval(a_l, f_l, g_l, a_u, f_u, g_u, a_t, psi_t, d_psi_t);
+    else interval_converged = ndt_update_interval(a_l, f_l, g_l, a_u, f_u, g_u, a_t, phi_t, d_phi_t);
+    step_iterations++;
+  }
+  if (step_iterations) {  // NDT:928-929
+    double acc[28];
+    const gorio::NdtEval ev = ndt_make_eval(h, x_t, st.T);
+    if (const int rc = ndt_evaluate(h, ev, 2, acc)) return rc;
+    ndt_unpack_hessian(acc, st.H);
+    st.diag.n_hessians++;
+  }
+  st.diag.n_mt_iterations += step_iterations;
+  *a_out = a_t;
+  return GORIO_OK;
+}
+}  // namespace
+
+extern "C" {
+
+const char* gorio_ndt_last_error(void) { return g_ndt_err.c_str(); }
+
+void gorio_ndt_default_params(gorio_ndt_params* p) {  // NDT:47-76, VoxelGridCovariance's constructor
+  if (!p) return;
+  p->resolution = 1.0;
+  p->step_size = 0.1;
+  p->outlier_ratio = 0.55;
+  p->transformation_epsilon = 0.1;
+  p->max_iterations = 35;
+  p->search = GORIO_NDT_DIRECT7;
+  p->min_points_per_voxel = 6;
+  p->min_covar_eigvalue_mult = 0.01;
+}
+
+int gorio_ndt_create(gorio_ndt_t** out, int device) {  // NDT:47-76
+  if (!out) return ndt_fail(GORIO_ERR_INVALID, "create: null argument");
+  *out = nullptr;
+  int ndev = 0;
+  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return ndt_fail(GORIO_ERR_NO_DEVICE, "create: no usable HIP device (there is no CPU fallback)");
+  if (device < 0 || device >= ndev) return ndt_fail(GORIO_ERR_INVALID, "create: bad device ordinal");
+  GORIO_HIP_CHECK(ndt_fail, hipSetDevice(device));
+  gorio_ndt* h = new (std::nothrow) gorio_ndt();
+  if (!h) return ndt_fail(GORIO_ERR_ALLOC, "create: out of memory");
+  h->device = device;
+  gorio_ndt_default_params(&h->p);
+  if (hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking) != hipSuccess) {
+    delete h;
+    return ndt_fail(GORIO_ERR_NO_DEVICE, "create: no stream");
+  }
+  *out = h;
+  return GORIO_OK;
+}
+
+void gorio_ndt_destroy(gorio_ndt_t* h) {
+  if (!h) return;
+  hipSetDevice(h->device);
+  if (h->stream) {
+    hipStreamSynchronize(h->stream);
+    hipStreamDestroy(h->stream);
+  }
+  delete h;
+}
+
+// setResolution / setStepSize / setOutlierRatio / setNeighborhoodSearchMethod / setTransformationEpsilon / setMaximumIterations, NDTH:115-191
+int gorio_ndt_set_params(gorio_ndt_t* h, const gorio_ndt_params* p) {
+  if (!p) return ndt_fail(GORIO_ERR_INVALID, "set_params: null argument");
+  if (const int rc = ndt_check_params(*p)) return rc;  // before the handle: a refused value needs no device
+  if (!h) return ndt_fail(GORIO_ERR_INVALID, "set_params: null handle");
+  if ((float)p->resolution != (float)h->p.resolution || p->min_points_per_voxel != h->p.min_points_per_voxel || p->min_covar_eigvalue_mult != h->p.min_covar_eigvalue_mult)
+    h->map_valid = false;  // NDTH:136-141
+  h->p = *p;
+  return GORIO_OK;
+}
+
+int gorio_ndt_get_params(const gorio_ndt_t* h, gorio_ndt_params* p) {
+  if (!h || !p) return ndt_fail(GORIO_ERR_INVALID, "get_params: null argument");
+  *p = h->p;
+  return GORIO_OK;
+}
+
+// setInputTarget, NDTH:122-127 (init() runs at the next call that needs the map)
+int gorio_ndt_set_target(gorio_ndt_t* h, const float* xyz, int n, int stride_bytes) {
+  if (!h) return ndt_fail(GORIO_ERR_INVALID, "set_target: null handle");
+  if (n < 0 || (n > 0 && (!xyz || stride_bytes < 12 || stride_bytes % 4))) return ndt_fail(GORIO_ERR_INVALID, "set_target: bad cloud arguments");
+  if (n > INT_MAX / 2) return ndt_fail(GORIO_ERR_INVALID, "set_target: too many points");
+  h->map_valid = false;
+  h->has_target = false;
+  if (const int rc = ndt_upload(h, xyz, n, stride_bytes, h->tx, h->ty, h->tz, h->t_cap)) return rc;
+  h->n_t = n;
+  h->has_target = true;
+  return GORIO_OK;
+}
+
+// setInputSource (pcl::Registration)
+int gorio_ndt_set_source(gorio_ndt_t* h, const float* xyz, int n, int stride_bytes) {
+  if (!h) return ndt_fail(GORIO_ERR_INVALID, "set_source: null handle");
+  if (n < 0 || (n > 0 && (!xyz || stride_bytes < 12 || stride_bytes % 4))) return ndt_fail(GORIO_ERR_INVALID, "set_source: bad cloud arguments");
+  if (n > INT_MAX / 2) return ndt_fail(GORIO_ERR_INVALID, "set_source: too many points");
+  const size_t st = n ? stride_bytes / 4 : 0;
+  for (int i = 0; i < n; ++i)
+    if (!std::isfinite(xyz[st * i]) || !std::isfinite(xyz[st * i + 1]) || !std::isfinite(xyz[st * i + 2]))
+      return ndt_fail(GORIO_ERR_INVALID, "set_source: point " + std::to_string(i) + " is not finite (the reference's cell index of it is undefined)");
+  h->has_source = false;
+  if (const int rc = ndt_upload(h, xyz, n, stride_bytes, h->sx, h->sy, h->sz, h->s_cap)) return rc;
+  h->n_s = n;
+  h->has_source = true;
+  return GORIO_OK;
+}
+
+// setInputTarget from device arrays
+int gorio_ndt_set_target_device(gorio_ndt_t* h, const float* x, const float* y, const float* z, int n) {
+  if (!h) return ndt_fail(GORIO_ERR_INVALID, "set_target_device: null handle");
+  if (n < 0 || (n > 0 && (!x || !y || !z)) || n > INT_MAX / 2) return ndt_fail(GORIO_ERR_INVALID, "set_target_device: bad cloud arguments");
+  h->map_valid = false;
+  h->has_target = false;
+  if (const int rc = ndt_copy_device(h, x, y, z, n, h->tx, h->ty, h->tz, h->t_cap)) return rc;
+  h->n_t = n;
+  h->has_target = true;
+  return GORIO_OK;
+}
+
+// setInputSource from device arrays; the finiteness check runs on the device BEFORE the source held is replaced
+int gorio_ndt_set_source_device(gorio_ndt_t* h, const float* x, const float* y, const float* z, int n) {
+  if (!h) return ndt_fail(GORIO_ERR_INVALID, "set_source_device: null handle");
+  if (n < 0 || (n > 0 && (!x || !y || !z)) || n > INT_MAX / 2) return ndt_fail(GORIO_ERR_INVALID, "set_source_device: bad cloud arguments");
+  GORIO_HIP_CHECK(ndt_fail, hipSetDevice(h->device));
+  if (n) {
+    GORIO_HIP_CHECK(ndt_fail, h->flag.reserve(1));
+    int flag = 0;
+    GORIO_HIP_CHECK(ndt_fail, hipMemsetAsync(h->flag, 0, sizeof(int), h->stream));
+    gorio::ndt_finite_kernel<<<(n + 255) / 256, 256, 0, h->stream>>>(x, y, z, n, h->flag);
+    GORIO_HIP_CHECK(ndt_fail, hipGetLastError());
+    GORIO_HIP_CHECK(ndt_fail, hipMemcpyAsync(&flag, h->flag, sizeof(int), hipMemcpyDeviceToHost, h->stream));
+    GORIO_HIP_CHECK(ndt_fail, hipStreamSynchronize(h->stream));
+    if (flag) return ndt_fail(GORIO_ERR_INVALID, "set_source_device: a point is not finite (the reference's cell index of it is undefined)");
+  }
+  h->has_source = false;
+  if (const int rc = ndt_copy_device(h, x, y, z, n, h->sx, h->sy, h->sz, h->s_cap)) return rc;
+  h->n_s = n;
+  h->has_source = true;
+  return GORIO_OK;
+}
+
+// no reference member: how many elements the handle's device buffers hold (they grow, they are never shrunk or freed by a smaller cloud)
+int gorio_ndt_get_capacities(const gorio_ndt_t* h, long long* capacities) {
+  if (!h || !capacities) return ndt_fail(GORIO_ERR_INVALID, "get_capacities: null argument");
+  capacities[0] = (long long)h->t_cap;
+  capacities[1] = (long long)h->s_cap;
+  capacities[2] = (long long)h->l_cap;
+  capacities[3] = (long long)h->keys.cap();
+  return GORIO_OK;
+}
+
+// the leaves_ map of VoxelGridCovariance after applyFilter (VGC:60-370)
+int gorio_ndt_get_voxels(gorio_ndt_t* h, int capacity, int* n_leaves, int* leaf_index, int* nr_points, double* mean, double* cov_raw, double* cov, double* icov, int* min_b,
+                         int* div_b) {
+  if (!h || !n_leaves) return ndt_fail(GORIO_ERR_INVALID, "get_voxels: null argument");
+  if (!h->has_target) return ndt_fail(GORIO_ERR_STATE, "get_voxels: no target set");
+  GORIO_HIP_CHECK(ndt_fail, hipSetDevice(h->device));
+  if (const int rc = ndt_ensure_map(h)) return rc;
+  *n_leaves = h->nl;
+  for (int a = 0; a < 3; ++a) {
+    if (min_b) min_b[a] = h->grid.min_b[a];
+    if (div_b) div_b[a] = h->grid.div_b[a];
+  }
+  const bool any = leaf_index || nr_points || mean || cov_raw || cov || icov;
+  if (!any || h->nl == 0) return GORIO_OK;
+  if (capacity < h->nl) return ndt_fail(GORIO_ERR_INVALID, "get_voxels: capacity below the number of leaves");
+  const size_t nl = h->nl;
+  if (leaf_index) GORIO_HIP_CHECK(ndt_fail, hipMemcpyAsync(leaf_index, h->lidx, sizeof(int) * nl, hipMemcpyDeviceToHost, h->stream));
+  if (nr_points) GORIO_HIP_CHECK(ndt_fail, hipMemcpyAsync(nr_points, h->lcnt, sizeof(int) * nl, hipMemcpyDeviceToHost, h->stream));
+  if (mean) GORIO_HIP_CHECK(ndt_fail, hipMemcpyAsync(mean, h->lmean, sizeof(double) * 3 * nl, hipMemcpyDeviceToHost, h->stream));
+  if (cov_raw) GORIO_HIP_CHECK(ndt_fail, hipMemcpyAsync(cov_raw, h->lraw, sizeof(double) * 9 * nl, hipMemcpyDeviceToHost, h->stream));
+  if (cov) GORIO_HIP_CHECK(ndt_fail, hipMemcpyAsync(cov, h->lcov, sizeof(double) * 9 * nl, hipMemcpyDeviceToHost, h->stream));
+  if (icov) GORIO_HIP_CHECK(ndt_fail, hipMemcpyAsync(icov, h->licov, sizeof(double) * 9 * nl, hipMemcpyDeviceToHost, h->stream));
+  GORIO_HIP_CHECK(ndt_fail, hipStreamSynchronize(h->stream));
+  return GORIO_OK;
+}
+
+// computeDerivatives, NDT:180-285
+int gorio_ndt_derivatives(gorio_ndt_t* h, const double* p, int compute_hessian, double* score, double* gradient, double* hessian) {
+  if (const int rc = ndt_ready(h, "derivatives")) return rc;
+  if (!p || !score || !gradient || (compute_hessian && !hessian)) return ndt_fail(GORIO_ERR_INVALID, "derivatives: null argument");
+  NdtState st;
+  ndt_pose_matrix(p, st.T);
+  if (const int rc = ndt_derivs_at(h, st, p, st.T, compute_hessian != 0)) return rc;
+  *score = st.score;
+  std::copy(st.g, st.g + 6, gradient);
+  if (compute_hessian) std::copy(st.H, st.H + 36, hessian);
+  return GORIO_OK;
+}
+
+// computeHessian, NDT:540-645
+int gorio_ndt_hessian(gorio_ndt_t* h, const double* p, double* hessian) {
+  if (const int rc = ndt_ready(h, "hessian")) return rc;
+  if (!p || !hessian) return ndt_fail(GORIO_ERR_INVALID, "hessian: null argument");
+  float T[16];
+  double acc[28];
+  ndt_pose_matrix(p, T);
+  const gorio::NdtEval ev = ndt_make_eval(h, p, T);
+  if (const int rc = ndt_evaluate(h, ev, 2, acc)) return rc;
+  ndt_unpack_hessian(acc, hessian);
+  return GORIO_OK;
+}
+
+// calculateScore, NDT:935-983
+int gorio_ndt_calculate_score(gorio_ndt_t* h, const float* T, double* score) {
+  if (const int rc = ndt_ready(h, "calculate_score")) return rc;
+  if (!T || !score) return ndt_fail(GORIO_ERR_INVALID, "calculate_score: null argument");
+  double acc[28];
+  const gorio::NdtEval ev = ndt_make_eval(h, nullptr, T);
+  if (const int rc = ndt_evaluate(h, ev, 3, acc)) return rc;
+  *score = acc[0] / (double)h->n_s;  // NDT:982
+  return GORIO_OK;
+}
+
+// computeTransformation, NDT:81-171
+int gorio_ndt_align(gorio_ndt_t* h, const float* guess, float* T_out, int* converged, int* nr_iterations, double* trans_probability, gorio_ndt_diag* diag) {
+  if (const int rc = ndt_ready(h, "align")) return rc;
+  if (!T_out) return ndt_fail(GORIO_ERR_INVALID, "align: null argument");
+  NdtState st;
+  for (int i = 0; i < 16; ++i) st.T[i] = guess ? guess[i] : ((i % 5 == 0) ? 1.0f : 0.0f);  // NDT:95-104: final_transformation_ = guess
+  float ang[3];
+  ndt_euler012(st.T, ang);
+  double p[6] = {(double)st.T[3], (double)st.T[7], (double)st.T[11], (double)ang[0], (double)ang[1], (double)ang[2]};  // NDT:107-111
+  int nr = 0;
+  bool conv = false;
+  const double n_src = (double)h->n_s;
+  double prob = 0.0;
+  if (const int rc = ndt_derivs_at(h, st, p, st.T, true)) return rc;  // NDT:119: the cloud moved by the guess itself
+  while (!conv) {
+    double mg[6], delta[6];
+    for (int k = 0; k < 6; ++k) mg[k] = -st.g[k];
+    ndt_svd_solve(st.H, mg, delta);  // NDT:127-129
+    double nn = 0.0;
+    for (int k = 0; k < 6; ++k) nn += delta[k] * delta[k];
+    double delta_p_norm = std::sqrt(nn);
+    if (delta_p_norm == 0 || delta_p_norm != delta_p_norm) {  // NDT:134-139
+      prob = st.score / n_src;
+      conv = delta_p_norm == delta_p_norm;
+      goto done;
+    }
+    for (int k = 0; k < 6; ++k) delta[k] /= delta_p_norm;
+    if (const int rc = ndt_step_length(h, st, p, delta, delta_p_norm, h->p.step_size, h->p.transformation_epsilon / 2, &delta_p_norm)) return rc;
+    for (int k = 0; k < 6; ++k) {
+      delta[k] *= delta_p_norm;
+      p[k] = p[k] + delta[k];
+    }
+    if (nr > h->p.max_iterations || (nr && (std::fabs(delta_p_norm) < h->p.transformation_epsilon))) conv = true;  // NDT:158-162
+    nr++;
+  }
+  prob = st.score / n_src;  // NDT:170
+done:
+  std::copy(st.T, st.T + 16, T_out);
+  if (converged) *converged = conv ? 1 : 0;
+  if (nr_iterations) *nr_iterations = nr;
+  if (trans_probability) *trans_probability = prob;
+  if (diag) {
+    *diag = st.diag;
+    diag->score = st.score;
+  }
+  return GORIO_OK;
+}
+
+}  // extern "C"

@@ -1,0 +1,171 @@
+// Drop-in for ndt_omp/include/pclomp/ndt_omp.h of the Go-RIO sources (NDTH; NDT = ndt_omp_impl.hpp): pclomp::NormalDistributionsTransform
+// with the surface select_registration_method (registrations.cpp:117-134) and ndt_omp/apps/align.cpp use, on top of the C ABI of
+// include/gorio_ndt.h.  Every body is an ABI call; the voxel map, the derivative sums and the score run on the GPU.  KDTREE is refused
+// by the library (std::runtime_error here).  getFitnessScore, which the nodelets call after every match (scan_matching_odometry_nodelet.cpp:675,
+// loop_detector.cpp:229, 415), is computed on the GPU as the fast_gicp drop-ins do, through a registration handle of include/gorio_apd.h
+// that holds the same two clouds; through a pcl::Registration base pointer real PCL still runs its own CPU version.
+#pragma once
+#include <limits>
+#include <stdexcept>
+#include <string>
+
+#include <Eigen/Core>
+#include <pcl/point_cloud.h>
+#include <pcl/point_types.h>
+#include <pcl/registration/registration.h>
+
+#include "gorio_apd.h"
+#include "gorio_ndt.h"
+
+namespace pclomp {
+
+enum NeighborSearchMethod { KDTREE, DIRECT26, DIRECT7, DIRECT1 };  // NDTH:52-57
+
+template <typename PointSource, typename PointTarget>
+class NormalDistributionsTransform : public pcl::Registration<PointSource, PointTarget> {
+ protected:
+  using Base = pcl::Registration<PointSource, PointTarget>;
+  using PointCloudSource = typename Base::PointCloudSource;
+  using PointCloudSourceConstPtr = typename Base::PointCloudSourceConstPtr;
+  using PointCloudTargetConstPtr = typename Base::PointCloudTargetConstPtr;
+  using Base::converged_;
+  using Base::final_transformation_;
+  using Base::input_;
+  using Base::max_iterations_;
+  using Base::nr_iterations_;
+  using Base::reg_name_;
+  using Base::target_;
+  using Base::transformation_epsilon_;
+
+ public:
+  using Ptr = std::shared_ptr<NormalDistributionsTransform<PointSource, PointTarget>>;
+  using ConstPtr = std::shared_ptr<const NormalDistributionsTransform<PointSource, PointTarget>>;
+
+  NormalDistributionsTransform() {  // NDT:47-76
+    reg_name_ = "NormalDistributionsTransform";
+    check(gorio_ndt_create(&h_, 0), "NormalDistributionsTransform");
+    gorio_ndt_default_params(&p_);
+    transformation_epsilon_ = p_.transformation_epsilon;
+    max_iterations_ = p_.max_iterations;
+  }
+  virtual ~NormalDistributionsTransform() {
+    gorio_ndt_destroy(h_);
+    if (fit_) gorio_apd_destroy(fit_);
+  }
+  NormalDistributionsTransform(const NormalDistributionsTransform&) = delete;
+  NormalDistributionsTransform& operator=(const NormalDistributionsTransform&) = delete;
+
+  void setNumThreads(int) {}  // NDTH:115: accepted, ignored
+  void setInputTarget(const PointCloudTargetConstPtr& cloud) override {  // NDTH:122-127
+    Base::setInputTarget(cloud);
+    fit_target_stale_ = true;
+    const int n = (int)cloud->size();
+    check(gorio_ndt_set_target(h_, n ? &cloud->points[0].x : nullptr, n, (int)sizeof(PointTarget)), "setInputTarget");
+  }
+  void setInputSource(const PointCloudSourceConstPtr& cloud) override {
+    Base::setInputSource(cloud);
+    fit_source_stale_ = true;
+    const int n = (int)cloud->size();
+    check(gorio_ndt_set_source(h_, n ? &cloud->points[0].x : nullptr, n, (int)sizeof(PointSource)), "setInputSource");
+  }
+  void setResolution(float resolution) {  // NDTH:132-142
+    p_.resolution = resolution;
+    push("setResolution");
+  }
+  float getResolution() const { return (float)p_.resolution; }
+  double getStepSize() const { return p_.step_size; }
+  void setStepSize(double step_size) {
+    p_.step_size = step_size;
+    push("setStepSize");
+  }
+  double getOutlierRatio() const { return p_.outlier_ratio; }
+  void setOutlierRatio(double outlier_ratio) {
+    p_.outlier_ratio = outlier_ratio;
+    push("setOutlierRatio");
+  }
+  void setNeighborhoodSearchMethod(NeighborSearchMethod method) {  // NDTH:189-191
+    p_.search = (int)method;
+    push("setNeighborhoodSearchMethod");
+  }
+  double getTransformationProbability() const { return trans_probability_; }
+  int getFinalNumIteration() const { return nr_iterations_; }
+  const gorio_ndt_diag& getDiagnostics() const { return diag_; }
+
+  // calculateScore (NDT:935-983): the cloud as given (already transformed), scored against the target
+  double calculateScore(const PointCloudSource& cloud) const {
+    const int n = (int)cloud.size();
+    check(gorio_ndt_set_source(h_, n ? &cloud.points[0].x : nullptr, n, (int)sizeof(PointSource)), "calculateScore");
+    const float I[16] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1};
+    double score = 0.0;
+    const int rc = gorio_ndt_calculate_score(h_, I, &score);
+    if (input_) {  // the registration's own source comes back
+      const int m = (int)input_->size();
+      check(gorio_ndt_set_source(h_, m ? &input_->points[0].x : nullptr, m, (int)sizeof(PointSource)), "calculateScore");
+    }
+    check(rc, "calculateScore");
+    return score;
+  }
+
+  // pcl::Registration::getFitnessScore(max_range) as the nodelets call it: mean squared nearest-neighbour distance of the source moved by
+  // final_transformation_, computed on the GPU (gorio_apd_fitness_score).  The clouds go to that handle at the first call after they changed.
+  double getFitnessScore(double max_range = std::numeric_limits<double>::max()) {
+    if (!input_ || !target_) throw std::logic_error("pclomp::NormalDistributionsTransform::getFitnessScore: no source or no target");
+    if (!fit_) check_apd(gorio_apd_create(&fit_, 0), "getFitnessScore");
+    if (fit_target_stale_) {
+      const int n = (int)target_->size();
+      check_apd(gorio_apd_set_target(fit_, n ? &target_->points[0].x : nullptr, nullptr, n, (int)sizeof(PointTarget)), "getFitnessScore");
+      fit_target_stale_ = false;
+    }
+    if (fit_source_stale_) {
+      const int n = (int)input_->size();
+      check_apd(gorio_apd_set_source(fit_, n ? &input_->points[0].x : nullptr, nullptr, n, (int)sizeof(PointSource)), "getFitnessScore");
+      fit_source_stale_ = false;
+    }
+    float T[16];
+    for (int r = 0; r < 4; ++r)
+      for (int c = 0; c < 4; ++c) T[4 * r + c] = final_transformation_(r, c);
+    double score = 0.0;
+    check_apd(gorio_apd_fitness_score(fit_, T, max_range, 0.0, &score, nullptr), "getFitnessScore");
+    return score;
+  }
+
+ protected:
+  void computeTransformation(PointCloudSource& output, const Eigen::Matrix4f& guess) override {  // NDT:81-171
+    p_.transformation_epsilon = transformation_epsilon_;
+    p_.max_iterations = max_iterations_;
+    push("align");
+    float G[16], T[16];
+    for (int r = 0; r < 4; ++r)
+      for (int c = 0; c < 4; ++c) G[4 * r + c] = guess(r, c);
+    int conv = 0, nr = 0;
+    check(gorio_ndt_align(h_, G, T, &conv, &nr, &trans_probability_, &diag_), "align");
+    for (int r = 0; r < 4; ++r)
+      for (int c = 0; c < 4; ++c) final_transformation_(r, c) = T[4 * r + c];
+    converged_ = conv != 0;
+    nr_iterations_ = nr;
+    for (auto& p : output.points) {  // the cloud moved by the final transformation, as trans_cloud holds it (NDT:833)
+      const float x = p.x, y = p.y, z = p.z;
+      p.x = ((T[0] * x + T[1] * y) + T[2] * z) + T[3];
+      p.y = ((T[4] * x + T[5] * y) + T[6] * z) + T[7];
+      p.z = ((T[8] * x + T[9] * y) + T[10] * z) + T[11];
+    }
+  }
+
+ private:
+  gorio_ndt_t* h_ = nullptr;
+  gorio_ndt_params p_;
+  gorio_ndt_diag diag_ = {0, 0, 0, 0.0};
+  double trans_probability_ = 0.0;
+  gorio_apd_t* fit_ = nullptr;  // getFitnessScore only
+  bool fit_target_stale_ = true, fit_source_stale_ = true;
+
+  static void check(int rc, const char* what) {
+    if (rc < 0) throw std::runtime_error(std::string("pclomp::NormalDistributionsTransform::") + what + ": " + gorio_ndt_last_error());
+  }
+  void check_apd(int rc, const char* what) const {
+    if (rc < 0) throw std::runtime_error(std::string("pclomp::NormalDistributionsTransform::") + what + ": " + gorio_apd_last_error(fit_));
+  }
+  void push(const char* what) { check(gorio_ndt_set_params(h_, &p_), what); }
+};
+
+}  // namespace pclomp

@@ -1,0 +1,134 @@
+"""ctypes binding of include/gorio_ndt.h: NDT_OMP registration (pclomp::NormalDistributionsTransform, DIRECT1 / 7 / 26) on the GPU
+(no numerics here, no CPU fallback)."""
+import ctypes as C
+
+import numpy as np
+
+from .apd import GorioError, load_library
+
+NDT_SYMBOLS = ["gorio_ndt_align", "gorio_ndt_calculate_score", "gorio_ndt_create", "gorio_ndt_default_params", "gorio_ndt_derivatives", "gorio_ndt_destroy",
+               "gorio_ndt_get_capacities", "gorio_ndt_get_params", "gorio_ndt_get_voxels", "gorio_ndt_hessian", "gorio_ndt_last_error", "gorio_ndt_set_params", "gorio_ndt_set_source",
+               "gorio_ndt_set_source_device", "gorio_ndt_set_target", "gorio_ndt_set_target_device"]
+KDTREE, DIRECT26, DIRECT7, DIRECT1 = 0, 1, 2, 3  # pclomp::NeighborSearchMethod
+
+
+class NdtParams(C.Structure):
+    _fields_ = [("resolution", C.c_double), ("step_size", C.c_double), ("outlier_ratio", C.c_double), ("transformation_epsilon", C.c_double),
+                ("max_iterations", C.c_int), ("search", C.c_int), ("min_points_per_voxel", C.c_int), ("min_covar_eigvalue_mult", C.c_double)]
+
+
+class NdtDiag(C.Structure):
+    _fields_ = [("n_derivatives", C.c_int), ("n_hessians", C.c_int), ("n_mt_iterations", C.c_int), ("score", C.c_double)]
+
+
+def _ptr(a):
+    return C.c_void_p(a.__array_interface__["data"][0])
+
+
+def default_params():
+    lib = load_library()
+    p = NdtParams()
+    lib.gorio_ndt_default_params(C.byref(p))
+    return p
+
+
+class Ndt:
+    """pclomp::NormalDistributionsTransform on the GPU; keyword arguments are fields of gorio_ndt_params."""
+
+    def __init__(self, device=0, **params):
+        self.lib = load_library()
+        self.lib.gorio_ndt_last_error.restype = C.c_char_p
+        self.h = C.c_void_p()
+        self._check(self.lib.gorio_ndt_create(C.byref(self.h), int(device)))
+        if params:
+            self.set_params(**params)
+
+    def _check(self, rc):
+        if rc < 0:
+            msg = self.lib.gorio_ndt_last_error()
+            raise GorioError(rc, msg.decode() if msg else "")
+
+    def close(self):
+        if self.h:
+            self.lib.gorio_ndt_destroy(self.h)
+            self.h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def get_params(self):
+        p = NdtParams()
+        self._check(self.lib.gorio_ndt_get_params(self.h, C.byref(p)))
+        return p
+
+    def set_params(self, **params):
+        p = self.get_params()
+        for k, v in params.items():
+            setattr(p, k, v)
+        self._check(self.lib.gorio_ndt_set_params(self.h, C.byref(p)))
+
+    def set_target(self, xyz):
+        a = np.ascontiguousarray(xyz, np.float32).reshape(-1, 3)
+        self._check(self.lib.gorio_ndt_set_target(self.h, _ptr(a) if a.size else None, a.shape[0], 12))
+
+    def set_source(self, xyz):
+        a = np.ascontiguousarray(xyz, np.float32).reshape(-1, 3)
+        self._check(self.lib.gorio_ndt_set_source(self.h, _ptr(a) if a.size else None, a.shape[0], 12))
+
+    def set_target_device(self, x, y, z, n):
+        """x, y, z: device addresses (int) of float arrays of the handle's device."""
+        self._check(self.lib.gorio_ndt_set_target_device(self.h, C.c_void_p(x), C.c_void_p(y), C.c_void_p(z), int(n)))
+
+    def set_source_device(self, x, y, z, n):
+        self._check(self.lib.gorio_ndt_set_source_device(self.h, C.c_void_p(x), C.c_void_p(y), C.c_void_p(z), int(n)))
+
+    def capacities(self):
+        """Elements the device buffers hold: dict of target, source, leaves, keys."""
+        c = (C.c_longlong * 4)()
+        self._check(self.lib.gorio_ndt_get_capacities(self.h, c))
+        return {"target": c[0], "source": c[1], "leaves": c[2], "keys": c[3]}
+
+    def voxels(self):
+        """The leaves in ascending leaf index: dict of leaf_index, nr_points, mean [L, 3], cov_raw / cov / icov [L, 3, 3], min_b, div_b."""
+        n = C.c_int()
+        min_b, div_b = np.zeros(3, np.int32), np.zeros(3, np.int32)
+        self._check(self.lib.gorio_ndt_get_voxels(self.h, 0, C.byref(n), None, None, None, None, None, None, _ptr(min_b), _ptr(div_b)))
+        L = n.value
+        idx, cnt = np.zeros(max(L, 1), np.int32), np.zeros(max(L, 1), np.int32)
+        mean = np.zeros((max(L, 1), 3))
+        raw, cov, icov = (np.zeros((max(L, 1), 3, 3)) for _ in range(3))
+        self._check(self.lib.gorio_ndt_get_voxels(self.h, max(L, 1), C.byref(n), _ptr(idx), _ptr(cnt), _ptr(mean), _ptr(raw), _ptr(cov), _ptr(icov), None, None))
+        return {"leaf_index": idx[:L], "nr_points": cnt[:L], "mean": mean[:L], "cov_raw": raw[:L], "cov": cov[:L], "icov": icov[:L], "min_b": min_b, "div_b": div_b}
+
+    def derivatives(self, p, compute_hessian=True):
+        """computeDerivatives at pose vector p -> (score, gradient [6], hessian [6, 6] or None)."""
+        p = np.ascontiguousarray(p, np.float64).reshape(6)
+        s = C.c_double()
+        g, H = np.zeros(6), np.zeros((6, 6))
+        self._check(self.lib.gorio_ndt_derivatives(self.h, _ptr(p), int(bool(compute_hessian)), C.byref(s), _ptr(g), _ptr(H) if compute_hessian else None))
+        return s.value, g, (H if compute_hessian else None)
+
+    def hessian(self, p):
+        """computeHessian at pose vector p -> [6, 6]."""
+        p = np.ascontiguousarray(p, np.float64).reshape(6)
+        H = np.zeros((6, 6))
+        self._check(self.lib.gorio_ndt_hessian(self.h, _ptr(p), _ptr(H)))
+        return H
+
+    def calculate_score(self, T):
+        T = np.ascontiguousarray(T, np.float32).reshape(4, 4)
+        s = C.c_double()
+        self._check(self.lib.gorio_ndt_calculate_score(self.h, _ptr(T), C.byref(s)))
+        return s.value
+
+    def align(self, guess=None):
+        """computeTransformation -> dict: T (float32 4x4), converged, nr_iterations, trans_probability, n_derivatives, n_hessians, n_mt, score."""
+        g = None if guess is None else np.ascontiguousarray(guess, np.float32).reshape(4, 4)
+        T = np.zeros((4, 4), np.float32)
+        conv, nr, prob, d = C.c_int(), C.c_int(), C.c_double(), NdtDiag()
+        self._check(self.lib.gorio_ndt_align(self.h, None if g is None else _ptr(g), _ptr(T), C.byref(conv), C.byref(nr), C.byref(prob), C.byref(d)))
+        return {"T": T, "converged": bool(conv.value), "nr_iterations": nr.value, "trans_probability": prob.value, "n_derivatives": d.n_derivatives,
+                "n_hessians": d.n_hessians, "n_mt": d.n_mt_iterations, "score": d.score}

@@ -1,0 +1,123 @@
+/*
+ * gorio_ndt.h -- C ABI of NDT_OMP registration on the MI355X (libgorio_amd.so): pclomp::NormalDistributionsTransform, the default
+ * that select_registration_method hands out (REG:27, 102-135), with its DIRECT1 / DIRECT7 / DIRECT26 neighbourhoods.
+ *
+ * Paths relative to the Go-RIO sources:
+ *   NDT  = ndt_omp/include/pclomp/ndt_omp_impl.hpp       NDTH = ndt_omp/include/pclomp/ndt_omp.h
+ *   VGC  = ndt_omp/include/pclomp/voxel_grid_covariance_omp_impl.hpp
+ *   REG  = 4DRadarSLAM/src/radar_graph_slam/registrations.cpp
+ *
+ * Same conventions as include/gorio_sc.h: plain pointers, host pointers caller-owned and only read / written during the call, 0 on
+ * success or a negative gorio_status (include/gorio_apd.h), gorio_ndt_last_error() gives the text (thread-local).  No CPU fallback:
+ * without a HIP device gorio_ndt_create fails with GORIO_ERR_NO_DEVICE.  The handle is its own type: NDT shares no optimiser, search
+ * or per-point state with the GICP family of include/gorio_apd.h.  One handle must not be used from two threads at once.
+ *
+ * Where the work runs: the voxel map (VGC:60-370), the derivative sums (NDT:180-285, 540-645) and the score (NDT:935-983) on the device;
+ * the Newton / More-Thuente shell (NDT:81-171, 648-932) on the host in plain C++, one derivative evaluation per round trip (28 doubles
+ * down, one small kernel argument up).  Sums of a leaf run in input order in fp64; the derivative sums are reduced wave -> block ->
+ * block order without floating-point atomics, so two runs give the same bits.
+ *
+ * What is fixed here where the reference leaves it to a library (DESIGN.md section 2 lists the same definitions; parity is against a
+ * NumPy restatement of them, the reference cannot be compiled without PCL and Eigen):
+ *   - float sin / cos / atan2 / exp are the correctly rounded float results (computed in double, rounded once);
+ *   - 3-term float products sum left to right, un-fused; pcl::transformPointCloud is ((m0 x + m1 y) + m2 z) + m3 in float;
+ *   - Transform<float, 3, Affine>::rotation() (NDT:109) is taken as the linear part of the guess (exact for an orthonormal guess);
+ *   - DIRECT26 walks the 26 offsets of pcl::getAllNeighborCellIndices (PCL 1.10 voxel_grid.h) in its order: no centre cell;
+ *   - SelfAdjointEigenSolver of a leaf is the library's fp64 cyclic Jacobi on the lower triangle; cov_.inverse() the cofactor inverse;
+ *   - the Hessian of computeDerivatives is the upper triangle hessian(i, j), i <= j (NDT:529), mirrored (the reference's 36 float
+ *     terms are symmetric only up to rounding);
+ *   - JacobiSVD<6x6>::solve(-g): symmetric Jacobi eigen-decomposition H = V L V^T, x = V L^+ V^T (-g), singular values |L| not above
+ *     6 eps max|L| count as zero (Eigen's default threshold);
+ *   - non-finite target points are skipped (VGC:136-138, 213-215) and the bounding box is that of the finite points.
+ * Reference behaviour kept although it looks like a slip: the float table row d1 of computeAngleDerivatives holds +sy (NDT:383) where
+ * the double row used by computeHessian holds -sy (NDT:361).  So computeHessian (NDT:929, after a line search with inner iterations) is
+ * NOT computeDerivatives asked for the Hessian only: it is the same traversal and the same formula (NDT:639-641 = NDT:529-531) in
+ * double throughout with the double tables; the derivative kernel has both instantiations.
+ * A non-finite SOURCE point is refused at set time (GORIO_ERR_INVALID): the reference converts floor(x / leaf) of it to int, which is
+ * undefined.  A finite point whose cell coordinate does not fit 31 bits has no neighbour.
+ *
+ * Out of scope: KDTREE search (a radius search over leaf centroids: another structure; REG:127-133 selects it only on request, it
+ * is refused with GORIO_ERR_UNSUPPORTED), batched aligns, sharing a target between handles, the scan-pipeline hand-off
+ * (include/gorio_scan.h), RCCL sharding, and PCL's single-thread pcl::NormalDistributionsTransform (REG:111: the same algorithm with
+ * KDTREE only).
+ */
+#ifndef GORIO_NDT_H
+#define GORIO_NDT_H
+
+#ifdef __cplusplus
+extern "C" {
+#endif
+
+/* pclomp::NeighborSearchMethod, NDTH:52-57, in its order */
+enum gorio_ndt_search { GORIO_NDT_KDTREE = 0, GORIO_NDT_DIRECT26 = 1, GORIO_NDT_DIRECT7 = 2, GORIO_NDT_DIRECT1 = 3 };
+
+typedef struct {
+  double resolution;              /* setResolution, NDTH default 1.0 (a float member); REG:108 passes 0.5.  <= 0: GORIO_ERR_UNSUPPORTED */
+  double step_size;               /* setStepSize, 0.1 */
+  double outlier_ratio;           /* setOutlierRatio, 0.55 */
+  double transformation_epsilon;  /* 0.1 (NDT:71); REG:124 passes 0.01 */
+  int max_iterations;             /* 35 (NDT:72); REG:125 passes 64 */
+  int search;                     /* gorio_ndt_search, DIRECT7 (NDT:74) */
+  int min_points_per_voxel;       /* VoxelGridCovariance: 6 */
+  double min_covar_eigvalue_mult; /* VoxelGridCovariance: 0.01 */
+} gorio_ndt_params;
+
+/* What one align did. */
+typedef struct {
+  int n_derivatives;  /* computeDerivatives calls (NDT:119, 837, 881) */
+  int n_hessians;     /* computeHessian calls (NDT:929) */
+  int n_mt_iterations;/* More-Thuente inner iterations, summed over the outer iterations (NDT:850-923) */
+  double score;       /* the score of the last evaluation */
+} gorio_ndt_diag;
+
+typedef struct gorio_ndt gorio_ndt_t;
+
+/* The constructor's values, NDT:47-76. */
+void gorio_ndt_default_params(gorio_ndt_params* p);
+/* new pclomp::NormalDistributionsTransform (NDT:47-76) with the default parameters. */
+int gorio_ndt_create(gorio_ndt_t** out, int device);
+void gorio_ndt_destroy(gorio_ndt_t* h);
+/* The setters of NDTH:115-191 in one call.  A changed resolution (or leaf rule) marks the voxel map stale (NDTH:133-142).  KDTREE,
+ * unknown search values and resolution <= 0 are refused with GORIO_ERR_UNSUPPORTED and change nothing. */
+int gorio_ndt_set_params(gorio_ndt_t* h, const gorio_ndt_params* p);
+int gorio_ndt_get_params(const gorio_ndt_t* h, gorio_ndt_params* p);
+
+/* setInputTarget (NDTH:122-127): xyz points at the first x, stride_bytes between points (a multiple of 4, >= 12), n >= 0.  The map is
+ * built at the next call that needs it.  Non-finite points are accepted and skipped by the map. */
+int gorio_ndt_set_target(gorio_ndt_t* h, const float* xyz, int n, int stride_bytes);
+/* setInputSource.  A non-finite point is refused with GORIO_ERR_INVALID and the source held stays. */
+int gorio_ndt_set_source(gorio_ndt_t* h, const float* xyz, int n, int stride_bytes);
+/* The same from device arrays x[n], y[n], z[n] of the handle's device (copied on the handle's stream). */
+int gorio_ndt_set_target_device(gorio_ndt_t* h, const float* x, const float* y, const float* z, int n);
+int gorio_ndt_set_source_device(gorio_ndt_t* h, const float* x, const float* y, const float* z, int n);
+
+/* Parity hook: the leaves of VoxelGridCovariance::applyFilter (VGC:60-370) in ascending linear leaf index (the order of the reference's
+ * std::map).  *n_leaves is always set; the arrays (any may be NULL) need capacity >= *n_leaves leaves: leaf_index, nr_points (-1 for a
+ * leaf the reference disables, VGC:336-339, 360-363), mean [3], cov_raw [9] (VGC:329-330, before the inflation; zero below
+ * min_points_per_voxel), cov [9] (after VGC:341-357), icov [9] (zero for leaves that are not neighbours), row-major; min_b [3], div_b [3]. */
+int gorio_ndt_get_voxels(gorio_ndt_t* h, int capacity, int* n_leaves, int* leaf_index, int* nr_points, double* mean, double* cov_raw, double* cov, double* icov,
+                         int* min_b, int* div_b);
+
+/* No reference member: the elements the handle's device buffers hold, capacities[4] = target points, source points, leaves, sort keys.
+ * Buffers grow with the clouds and are kept when a smaller (or empty) cloud follows: equal capacities mean nothing was reallocated. */
+int gorio_ndt_get_capacities(const gorio_ndt_t* h, long long* capacities);
+
+/* computeDerivatives (NDT:180-285) at pose vector p = (x, y, z, roll, pitch, yaw): the source is moved by the float matrix NDT:827-830
+ * builds from p, the Gaussian constants are those of NDT:89-93 for the current parameters.  hessian is 6 x 6 row-major and may be NULL
+ * when compute_hessian == 0 (NDT:881: the 21 Hessian sums are then skipped). */
+int gorio_ndt_derivatives(gorio_ndt_t* h, const double* p, int compute_hessian, double* score, double* gradient, double* hessian);
+/* computeHessian (NDT:540-645) at p: double throughout, see above. */
+int gorio_ndt_hessian(gorio_ndt_t* h, const double* p, double* hessian);
+/* calculateScore (NDT:935-983) of the source moved by the float 4 x 4 row-major T, constants as for gorio_ndt_derivatives. */
+int gorio_ndt_calculate_score(gorio_ndt_t* h, const float* T, double* score);
+/* computeTransformation (NDT:81-171) from the 4 x 4 row-major float guess (NULL: identity): T_out = final_transformation_,
+ * converged, nr_iterations_, trans_probability_.  Any output but T_out may be NULL.  GORIO_ERR_STATE without a source or without a
+ * target that has at least one finite point. */
+int gorio_ndt_align(gorio_ndt_t* h, const float* guess, float* T_out, int* converged, int* nr_iterations, double* trans_probability, gorio_ndt_diag* diag);
+
+const char* gorio_ndt_last_error(void);
+
+#ifdef __cplusplus
+}
+#endif
+#endif /* GORIO_NDT_H */
