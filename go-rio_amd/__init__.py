@@ -35,5 +35,5 @@ from . import ground  # noqa: E402
 from . import scan_context  # noqa: E402
 from .scan_context import SC_SYMBOLS, ScanContext  # noqa: E402
 from . import ndt  # noqa: E402
-from .ndt import NDT_SYMBOLS, Ndt  # noqa: E402
+from .ndt import NDT_SYMBOLS, Ndt, NdtBatchStats  # noqa: E402
 from .ugpm import PreintOption, PreintPrior, UgpmBatch, VelPreintegration, ugpm_combine_preints, ugpm_preint_batch, ugpm_stage_times  # noqa: E402

@@ -12,15 +12,20 @@
 //                                         leaf indices), computePointDerivatives / updateDerivatives in float (NDT:398-537) or
 //                                         updateHessian in double (NDT:613-645); 28 fp64 accumulators, wave_sum28, one partial per block
 //                  ndt_fold_kernel        the block partials in block order -> 28 doubles
+//   batch          ndt_derivative_batch_kernel, ndt_fold_batch_kernel: the same two bodies (ndt_derivative_block, ndt_fold_sum) for the
+//                                         pending evaluations of many handles: a job table and a per-workgroup (job, local block) table
 //   score          ndt_score_kernel       calculateScore (NDT:935-983), one double per block, ndt_fold_kernel
-//   align          host                   computeTransformation, computeStepLengthMT and its helpers (NDT:81-171, 648-932)
+//   align          host                   computeTransformation, computeStepLengthMT and its helpers (NDT:81-171, 648-932) as ONE resumable
+//                                         machine (NdtMachine): gorio_ndt_align drives one, gorio_ndt_align_batch many in lock-step
 // The only device loops are bounded: points of a leaf (<= n), neighbours (<= 26), binary-search steps (<= 32).  Every index that comes
 // from data is range-checked before it addresses memory: a source point outside the grid reads nothing.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
 #include <cmath>
+#include <memory>
 #include <new>
+#include <string>
 #include <vector>
 
 namespace gorio {
@@ -327,14 +332,15 @@ __device__ __forceinline__ void ndt_pair(const NdtEval& ev, const S (&jx)[8], co
   }
 }
 
-// grid: ceil(n / 256), block 256.  One 28-double partial per block.
+// The work of ONE workgroup of 256 lanes, shared by the single and the batched kernel so that the two cannot drift apart: source points
+// [256 block, 256 block + 256) of the cloud -> out[0..27], the block's sums (wave_sum28, then the four waves in a fixed order).
 template <typename S, bool HESS>
-__global__ __launch_bounds__(256) void ndt_derivative_kernel(const float* __restrict__ sx, const float* __restrict__ sy, const float* __restrict__ sz, int n, NdtMapView vm,
-                                                             NdtEval ev, double* __restrict__ partials) {
+__device__ __forceinline__ void ndt_derivative_block(const float* __restrict__ sx, const float* __restrict__ sy, const float* __restrict__ sz, int n, const NdtMapView& vm,
+                                                     const NdtEval& ev, int block, double* __restrict__ out) {
   double acc[28];
 #pragma unroll
   for (int q = 0; q < 28; ++q) acc[q] = 0.0;
-  const int i = blockIdx.x * 256 + threadIdx.x;
+  const int i = block * 256 + threadIdx.x;
   if (i < n) {
     const float x = sx[i], y = sy[i], z = sz[i];
     float qx, qy, qz;
@@ -375,7 +381,35 @@ __global__ __launch_bounds__(256) void ndt_derivative_kernel(const float* __rest
     }
   }
   __syncthreads();
-  if (threadIdx.x < 28) partials[(size_t)blockIdx.x * 28 + threadIdx.x] = (red[0][threadIdx.x] + red[1][threadIdx.x]) + (red[2][threadIdx.x] + red[3][threadIdx.x]);
+  if (threadIdx.x < 28) out[threadIdx.x] = (red[0][threadIdx.x] + red[1][threadIdx.x]) + (red[2][threadIdx.x] + red[3][threadIdx.x]);
+}
+
+// grid: ceil(n / 256), block 256.  One 28-double partial per block.
+template <typename S, bool HESS>
+__global__ __launch_bounds__(256) void ndt_derivative_kernel(const float* __restrict__ sx, const float* __restrict__ sy, const float* __restrict__ sz, int n, NdtMapView vm,
+                                                             NdtEval ev, double* __restrict__ partials) {
+  ndt_derivative_block<S, HESS>(sx, sy, sz, n, vm, ev, (int)blockIdx.x, partials + (size_t)blockIdx.x * 28);
+}
+
+// One pending evaluation of gorio_ndt_align_batch.  Its workgroups write the partial slots [first, first + nblk).
+struct NdtJob {
+  const float *sx, *sy, *sz;
+  int n;
+  int mode;   // 0 <float, false>, 1 <float, true>, 2 <double, true>
+  int first;  // first partial-block slot
+  int nblk;   // ceil(n / 256)
+  NdtMapView vm;
+  NdtEval ev;
+};
+
+// grid: the sum over the launch's jobs of ceil(n_j / 256), block 256.  wg[blockIdx.x] = (job, job-local block), written by the host with
+// the job table; the index is uniform over the workgroup, so the job record comes in through scalar loads.  The host keeps
+// wg[].x < number of jobs and wg[].y < jobs[wg[].x].nblk; the partial buffer holds first + nblk slots for every job.
+template <typename S, bool HESS>
+__global__ __launch_bounds__(256) void ndt_derivative_batch_kernel(const NdtJob* __restrict__ jobs, const int2* __restrict__ wg, double* __restrict__ partials) {
+  const int2 w = wg[blockIdx.x];
+  const NdtJob& j = jobs[w.x];
+  ndt_derivative_block<S, HESS>(j.sx, j.sy, j.sz, j.n, j.vm, j.ev, w.y, partials + (size_t)(j.first + w.y) * 28);
 }
 
 // calculateScore, NDT:935-983: per point sum of score_inc / neighborhood.size(); one double per block
@@ -417,39 +451,77 @@ __global__ __launch_bounds__(256) void ndt_score_kernel(const float* __restrict_
   if (threadIdx.x == 0) partials[blockIdx.x] = (red[0] + red[1]) + (red[2] + red[3]);
 }
 
-// out[k] = sum over the blocks, in block order, of partials[b * width + k]; width <= 64.  grid 1, block 64
+// sum over the blocks, in block order, of partials[b * width + k]
+__device__ __forceinline__ double ndt_fold_sum(const double* __restrict__ partials, int nblk, int width, int k) {
+  double s = 0.0;
+  for (int b = 0; b < nblk; ++b) s += partials[(size_t)b * width + k];
+  return s;
+}
+
+// out[k] = ndt_fold_sum(k); width <= 64.  grid 1, block 64
 __global__ __launch_bounds__(64) void ndt_fold_kernel(const double* __restrict__ partials, int nblk, int width, double* __restrict__ out) {
   if ((int)threadIdx.x >= width) return;
-  double s = 0.0;
-  for (int b = 0; b < nblk; ++b) s += partials[(size_t)b * width + threadIdx.x];
-  out[threadIdx.x] = s;
+  out[threadIdx.x] = ndt_fold_sum(partials, nblk, width, (int)threadIdx.x);
+}
+
+// grid: one 64-lane workgroup per job.  out[28 job + k] = the job's 28 sums, its partials added in block order
+__global__ __launch_bounds__(64) void ndt_fold_batch_kernel(const NdtJob* __restrict__ jobs, const double* __restrict__ partials, double* __restrict__ out) {
+  if (threadIdx.x >= 28) return;
+  const NdtJob& j = jobs[blockIdx.x];
+  out[(size_t)blockIdx.x * 28 + threadIdx.x] = ndt_fold_sum(partials + (size_t)j.first * 28, j.nblk, 28, (int)threadIdx.x);
 }
 
 }  // namespace gorio
 
 // ================================================================================================= host (include/gorio_ndt.h)
+namespace gorio {
+// What setInputTarget leaves on the device: the cloud and the voxel map built from it (target_cells_).  Handles hold it through a
+// shared_ptr: gorio_ndt_set_target_shared makes two handles look at ONE state, which lives until the last of them lets go.
+struct NdtTarget {
+  int device = 0;
+  DevBuf<float> tx, ty, tz;
+  size_t t_cap = 0;
+  int n_t = 0;
+  bool has_target = false;
+  // voxel map: stale after a new target, or (with one holder) a changed resolution / leaf rule; rebuilt by the next call that needs it
+  DevBuf<unsigned long long> keys;
+  DevBuf<int> counts, bb;
+  DevBuf<int> lidx, lcnt;
+  DevBuf<double> lmean, lraw, lcov, licov;
+  size_t l_cap = 0;
+  int nl = 0;
+  NdtGrid grid{};
+  bool map_valid = false;
+  // the three parameters the valid map was built with
+  double resolution = 0.0, min_covar_eigvalue_mult = 0.0;
+  int min_points_per_voxel = 0;
+  NdtTarget() = default;
+  NdtTarget(const NdtTarget&) = delete;
+  NdtTarget& operator=(const NdtTarget&) = delete;
+  ~NdtTarget() { hipSetDevice(device); }  // the buffers free themselves as members, after this body: the device has to be current by then
+};
+}  // namespace gorio
+
 struct gorio_ndt {
   int device = 0;
   hipStream_t stream = nullptr;
   gorio_ndt_params p;
-  // clouds, SoA
-  gorio::DevBuf<float> tx, ty, tz, sx, sy, sz;
-  size_t t_cap = 0, s_cap = 0;
-  int n_t = 0, n_s = 0;
-  bool has_target = false, has_source = false;
-  // voxel map (target_cells_): stale after a new target or a changed resolution / leaf rule, rebuilt by the next call that needs it
-  gorio::DevBuf<unsigned long long> keys;
-  gorio::DevBuf<int> counts, bb, flag;
-  gorio::DevBuf<int> lidx, lcnt;
-  gorio::DevBuf<double> lmean, lraw, lcov, licov;
-  size_t l_cap = 0;
-  int nl = 0;
-  gorio::NdtGrid grid{};
-  bool map_valid = false;
+  std::shared_ptr<gorio::NdtTarget> tgt;  // never null; may be shared with other handles of the device
+  bool tgt_owned = true;                  // false after gorio_ndt_set_target_shared: the buffers were allocated through another handle
+  // source cloud, SoA
+  gorio::DevBuf<float> sx, sy, sz;
+  size_t s_cap = 0;
+  int n_s = 0;
+  bool has_source = false;
+  gorio::DevBuf<int> flag;
   // evaluation scratch
   gorio::DevBuf<double> partials, d_out;
   gorio::PinnedBuf h_out;  // 28 doubles
-  gorio::NdtMapView map() const { return gorio::NdtMapView{lidx, lcnt, lmean, licov, nl, p.min_points_per_voxel, grid}; }
+  // batch scratch (of the handle that leads a gorio_ndt_align_batch): job table + workgroup table, partials, sums
+  gorio::DevBuf<void> b_jobs;
+  gorio::DevBuf<double> b_partials, b_out;
+  gorio::PinnedBuf b_h_jobs, b_h_out;
+  gorio::NdtMapView map() const { return gorio::NdtMapView{tgt->lidx, tgt->lcnt, tgt->lmean, tgt->licov, tgt->nl, p.min_points_per_voxel, tgt->grid}; }
 };
 
 namespace {
@@ -517,34 +589,64 @@ int ndt_copy_device(gorio_ndt* h, const float* x, const float* y, const float* z
   return GORIO_OK;
 }
 
-// init() (NDTH:276-283) -> VoxelGridCovariance::applyFilter (VGC:60-370) when the map is stale
+// a target about to be overwritten must not be one other handles still look at (gorio_ndt_set_target_shared): detach first
+void ndt_make_private(gorio_ndt* h) {
+  if (h->tgt.use_count() > 1 || !h->tgt_owned) {
+    h->tgt = std::make_shared<gorio::NdtTarget>();
+    h->tgt->device = h->device;
+  }
+  h->tgt_owned = true;
+}
+
+// "" when the handle's three map parameters are those the valid map was built with, else a text that names the first one that differs
+std::string ndt_map_mismatch(const gorio_ndt* h) {
+  const gorio::NdtTarget& t = *h->tgt;
+  if ((float)h->p.resolution != (float)t.resolution) return "resolution " + std::to_string(h->p.resolution) + " differs from the shared map's " + std::to_string(t.resolution);
+  if (h->p.min_points_per_voxel != t.min_points_per_voxel)
+    return "min_points_per_voxel " + std::to_string(h->p.min_points_per_voxel) + " differs from the shared map's " + std::to_string(t.min_points_per_voxel);
+  if (h->p.min_covar_eigvalue_mult != t.min_covar_eigvalue_mult)
+    return "min_covar_eigvalue_mult " + std::to_string(h->p.min_covar_eigvalue_mult) + " differs from the shared map's " + std::to_string(t.min_covar_eigvalue_mult);
+  return std::string();
+}
+
+// init() (NDTH:276-283) -> VoxelGridCovariance::applyFilter (VGC:60-370) when the map is stale.  A valid map built with other parameters
+// is rebuilt when this handle is the state's only holder, and refused (GORIO_ERR_INVALID) when other handles look at it too.
 int ndt_ensure_map(gorio_ndt* h) {
   using namespace gorio;
-  if (h->map_valid) return GORIO_OK;
-  if (!h->has_target) return ndt_fail(GORIO_ERR_STATE, "no target set");
+  NdtTarget* t = h->tgt.get();
+  if (t->map_valid) {
+    const std::string bad = ndt_map_mismatch(h);
+    if (bad.empty()) return GORIO_OK;
+    if (h->tgt.use_count() > 1) return ndt_fail(GORIO_ERR_INVALID, "shared target: " + bad + " (set the owner's value, or give this handle a target of its own)");
+    t->map_valid = false;
+  }
+  if (!t->has_target) return ndt_fail(GORIO_ERR_STATE, "no target set");
   GORIO_HIP_CHECK(ndt_fail, hipSetDevice(h->device));
-  const int n = h->n_t;
-  h->nl = 0;
-  h->grid = NdtGrid{};
-  h->grid.leaf = (float)h->p.resolution;
-  h->grid.inv = 1.0f / h->grid.leaf;
+  const int n = t->n_t;
+  t->nl = 0;
+  t->grid = NdtGrid{};
+  t->grid.leaf = (float)h->p.resolution;
+  t->grid.inv = 1.0f / t->grid.leaf;
+  t->resolution = h->p.resolution;
+  t->min_points_per_voxel = h->p.min_points_per_voxel;
+  t->min_covar_eigvalue_mult = h->p.min_covar_eigvalue_mult;
   if (n == 0) {
-    h->map_valid = true;
+    t->map_valid = true;
     return GORIO_OK;
   }
-  GORIO_HIP_CHECK(ndt_fail, h->bb.reserve(8));
-  ndt_bbox_init_kernel<<<1, 64, 0, h->stream>>>(h->bb);
-  ndt_bbox_kernel<<<std::min(256, (n + 255) / 256), 256, 0, h->stream>>>(h->tx, h->ty, h->tz, n, h->bb);
+  GORIO_HIP_CHECK(ndt_fail, t->bb.reserve(8));
+  ndt_bbox_init_kernel<<<1, 64, 0, h->stream>>>(t->bb);
+  ndt_bbox_kernel<<<std::min(256, (n + 255) / 256), 256, 0, h->stream>>>(t->tx, t->ty, t->tz, n, t->bb);
   int bb[8];
-  GORIO_HIP_CHECK(ndt_fail, hipMemcpyAsync(bb, h->bb, sizeof(int) * 8, hipMemcpyDeviceToHost, h->stream));
+  GORIO_HIP_CHECK(ndt_fail, hipMemcpyAsync(bb, t->bb, sizeof(int) * 8, hipMemcpyDeviceToHost, h->stream));
   GORIO_HIP_CHECK(ndt_fail, hipStreamSynchronize(h->stream));
   const int n_fin = bb[6];
   if (n_fin < 0 || n_fin > n) return ndt_fail(GORIO_ERR_STATE, "voxel map: internal error, the finite-point count does not fit the cloud");
   if (n_fin == 0) {
-    h->map_valid = true;
+    t->map_valid = true;
     return GORIO_OK;
   }
-  NdtGrid g = h->grid;
+  NdtGrid g = t->grid;
   double cells_f = 1.0, cells_b = 1.0;
   for (int a = 0; a < 3; ++a) {
     const float lo = ndt_decode(bb[a]), hi = ndt_decode(bb[3 + a]);
@@ -564,29 +666,29 @@ int ndt_ensure_map(gorio_ndt* h) {
   g.mul2 = g.div_b[0] * g.div_b[1];
   const int npow2 = sort_padded_size(n);
   const int nblocks = (n_fin + 255) / 256;
-  GORIO_HIP_CHECK(ndt_fail, h->keys.reserve(npow2));
-  GORIO_HIP_CHECK(ndt_fail, h->counts.reserve((size_t)(n + 255) / 256 + 1));
-  ndt_key_kernel<<<(npow2 + 255) / 256, 256, 0, h->stream>>>(h->tx, h->ty, h->tz, n, npow2, g, h->keys, h->bb);
-  enqueue_tiled_sort(h->stream, SortKeys{h->keys, npow2}, 1, npow2);
-  vox_count_kernel<<<nblocks, 256, 0, h->stream>>>(h->keys, n_fin, h->counts);
-  vox_scan_kernel<<<1, 1024, 0, h->stream>>>(h->counts, nblocks);
+  GORIO_HIP_CHECK(ndt_fail, t->keys.reserve(npow2));
+  GORIO_HIP_CHECK(ndt_fail, t->counts.reserve((size_t)(n + 255) / 256 + 1));
+  ndt_key_kernel<<<(npow2 + 255) / 256, 256, 0, h->stream>>>(t->tx, t->ty, t->tz, n, npow2, g, t->keys, t->bb);
+  enqueue_tiled_sort(h->stream, SortKeys{t->keys, npow2}, 1, npow2);
+  vox_count_kernel<<<nblocks, 256, 0, h->stream>>>(t->keys, n_fin, t->counts);
+  vox_scan_kernel<<<1, 1024, 0, h->stream>>>(t->counts, nblocks);
   int nv = 0, flags = 0;
-  GORIO_HIP_CHECK(ndt_fail, hipMemcpyAsync(&nv, h->counts + nblocks, sizeof(int), hipMemcpyDeviceToHost, h->stream));
-  GORIO_HIP_CHECK(ndt_fail, hipMemcpyAsync(&flags, h->bb + 7, sizeof(int), hipMemcpyDeviceToHost, h->stream));
+  GORIO_HIP_CHECK(ndt_fail, hipMemcpyAsync(&nv, t->counts + nblocks, sizeof(int), hipMemcpyDeviceToHost, h->stream));
+  GORIO_HIP_CHECK(ndt_fail, hipMemcpyAsync(&flags, t->bb + 7, sizeof(int), hipMemcpyDeviceToHost, h->stream));
   GORIO_HIP_CHECK(ndt_fail, hipStreamSynchronize(h->stream));
   if (flags) return ndt_fail(GORIO_ERR_UNSUPPORTED, "voxel map: a target point falls outside the leaf grid (float leaf arithmetic out of range)");
   if (nv <= 0 || nv > n_fin) return ndt_fail(GORIO_ERR_STATE, "voxel map: internal error, the leaf count does not fit the cloud");
   {
     const size_t cap = (size_t)nv + nv / 8 + 64;
-    GORIO_HIP_CHECK(ndt_fail, reserve_group(h->l_cap, nv, cap, h->lidx, cap, h->lcnt, cap, h->lmean, 3 * cap, h->lraw, 9 * cap, h->lcov, 9 * cap, h->licov, 9 * cap));
+    GORIO_HIP_CHECK(ndt_fail, reserve_group(t->l_cap, nv, cap, t->lidx, cap, t->lcnt, cap, t->lmean, 3 * cap, t->lraw, 9 * cap, t->lcov, 9 * cap, t->licov, 9 * cap));
   }
-  ndt_leaf_kernel<<<nblocks, 256, 0, h->stream>>>(h->keys, h->tx, h->ty, h->tz, n_fin, n, h->counts, h->p.min_points_per_voxel, h->p.min_covar_eigvalue_mult, nv, h->lidx, h->lcnt,
-                                                  h->lmean, h->lraw, h->lcov, h->licov);
+  ndt_leaf_kernel<<<nblocks, 256, 0, h->stream>>>(t->keys, t->tx, t->ty, t->tz, n_fin, n, t->counts, h->p.min_points_per_voxel, h->p.min_covar_eigvalue_mult, nv, t->lidx, t->lcnt,
+                                                  t->lmean, t->lraw, t->lcov, t->licov);
   GORIO_HIP_CHECK(ndt_fail, hipGetLastError());
   GORIO_HIP_CHECK(ndt_fail, hipStreamSynchronize(h->stream));
-  h->nl = nv;
-  h->grid = g;
-  h->map_valid = true;
+  t->nl = nv;
+  t->grid = g;
+  t->map_valid = true;
   return GORIO_OK;
 }
 
@@ -725,13 +827,19 @@ void ndt_unpack_hessian(const double* acc, double* H) {  // upper triangle, mirr
     for (int j = i; j < 6; ++j, ++t) H[6 * i + j] = H[6 * j + i] = acc[t];
 }
 
-int ndt_ready(gorio_ndt* h, const char* what) {
-  if (!h) return ndt_fail(GORIO_ERR_INVALID, std::string(what) + ": null handle");
+// what a call that evaluates needs, without building anything: GORIO_OK or the refusal
+int ndt_check_ready(const gorio_ndt* h, const std::string& what) {
+  if (!h->tgt->has_target) return ndt_fail(GORIO_ERR_STATE, what + ": no target set");
+  if (!h->has_source || h->n_s == 0) return ndt_fail(GORIO_ERR_STATE, what + ": no source set (or an empty one)");
+  return GORIO_OK;
+}
+
+int ndt_ready(gorio_ndt* h, const std::string& what) {
+  if (!h) return ndt_fail(GORIO_ERR_INVALID, what + ": null handle");
   GORIO_HIP_CHECK(ndt_fail, hipSetDevice(h->device));  // the evaluation scratch below is allocated on the handle's device, whatever the caller left current
-  if (!h->has_target) return ndt_fail(GORIO_ERR_STATE, std::string(what) + ": no target set");
-  if (!h->has_source || h->n_s == 0) return ndt_fail(GORIO_ERR_STATE, std::string(what) + ": no source set (or an empty one)");
-  if (const int rc = ndt_ensure_map(h)) return rc;
-  if (h->nl == 0) return ndt_fail(GORIO_ERR_STATE, std::string(what) + ": the target has no finite point");
+  if (const int rc = ndt_check_ready(h, what)) return rc;
+  if (const int rc = ndt_ensure_map(h)) return ndt_fail(rc, what + ": " + g_ndt_err);
+  if (h->tgt->nl == 0) return ndt_fail(GORIO_ERR_STATE, what + ": the target has no finite point");
   return GORIO_OK;
 }
 
@@ -843,85 +951,224 @@ struct NdtState {  // what computeTransformation carries between the calls
   gorio_ndt_diag diag{};
 };
 
-int ndt_derivs_at(gorio_ndt* h, NdtState& st, const double* p, const float* T, bool hessian) {
-  double acc[28];
-  const gorio::NdtEval ev = ndt_make_eval(h, p, T);
-  if (const int rc = ndt_evaluate(h, ev, hessian ? 1 : 0, acc)) return rc;
+// the 28 sums of a computeDerivatives evaluation -> score, gradient and (asked for) Hessian
+void ndt_take_derivs(NdtState& st, const double* acc, bool hessian) {
   st.score = acc[0];
   for (int k = 0; k < 6; ++k) st.g[k] = acc[1 + k];
   if (hessian) ndt_unpack_hessian(acc, st.H);
   st.diag.n_derivatives++;
+}
+
+int ndt_derivs_at(gorio_ndt* h, NdtState& st, const double* p, const float* T, bool hessian) {
+  double acc[28];
+  const gorio::NdtEval ev = ndt_make_eval(h, p, T);
+  if (const int rc = ndt_evaluate(h, ev, hessian ? 1 : 0, acc)) return rc;
+  ndt_take_derivs(st, acc, hessian);
   return GORIO_OK;
 }
 
-// computeStepLengthMT, NDT:772-932
-int ndt_step_length(gorio_ndt* h, NdtState& st, const double* x, double* step_dir, double step_init, double step_max, double step_min, double* a_out) {
-  const double phi_0 = -st.score;
-  double d_phi_0 = 0.0;
-  for (int k = 0; k < 6; ++k) d_phi_0 += st.g[k] * step_dir[k];
-  d_phi_0 = -d_phi_0;
-  if (d_phi_0 >= 0) {
-    if (d_phi_0 == 0) {
-      *a_out = 0;
-      return GORIO_OK;
-    }
-    d_phi_0 *= -1;
-    for (int k = 0; k < 6; ++k) step_dir[k] *= -1;
+// computeTransformation (NDT:81-171) with computeStepLengthMT (NDT:772-932) inside, as a resumable machine: it stops wherever the
+// reference evaluates the derivative sums ("I need evaluation `mode` at pose `x_eval` / matrix st.T") and goes on when it is handed
+// the 28 sums.  gorio_ndt_align feeds one machine through ndt_evaluate; gorio_ndt_align_batch feeds many, one evaluation per round.
+struct NdtMachine {
+  enum Phase { kFirst, kStepFirst, kStepInner, kStepHessian, kDone };
+  const gorio_ndt* h = nullptr;
+  NdtState st;
+  Phase phase = kDone;
+  int mode = 1;        // of the pending evaluation: 0 computeDerivatives without the Hessian, 1 with it, 2 computeHessian
+  double x_eval[6];    // pose vector of the pending evaluation (its float matrix is st.T)
+  // computeTransformation's locals
+  double p[6], delta[6], delta_p_norm = 0.0, prob = 0.0;
+  int nr = 0;
+  bool conv = false;
+  // computeStepLengthMT's locals
+  double phi_0, d_phi_0, a_l, a_u, f_l, g_l, f_u, g_u, a_t, step_max, step_min, phi_t, d_phi_t, psi_t, d_psi_t;
+  bool interval_converged, open_interval;
+  int step_iterations;
+
+  static constexpr double mu = 1.e-4, nu = 0.9;
+  static constexpr int max_step_iterations = 10;
+
+  bool done() const { return phase == kDone; }
+
+  void begin(const gorio_ndt* handle, const float* guess) {
+    h = handle;
+    for (int i = 0; i < 16; ++i) st.T[i] = guess ? guess[i] : ((i % 5 == 0) ? 1.0f : 0.0f);  // NDT:95-104: final_transformation_ = guess
+    float ang[3];
+    ndt_euler012(st.T, ang);
+    const double p0[6] = {(double)st.T[3], (double)st.T[7], (double)st.T[11], (double)ang[0], (double)ang[1], (double)ang[2]};  // NDT:107-111
+    std::copy(p0, p0 + 6, p);
+    std::copy(p0, p0 + 6, x_eval);
+    mode = 1;  // NDT:119: the cloud moved by the guess itself
+    phase = kFirst;
   }
-  const int max_step_iterations = 10;
-  int step_iterations = 0;
-  const double mu = 1.e-4, nu = 0.9;
-  double a_l = 0, a_u = 0;
-  double f_l = phi_0 - phi_0 - mu * d_phi_0 * a_l, g_l = d_phi_0 - mu * d_phi_0;  // auxiliaryFunction_PsiMT / _dPsiMT, NDTH:433, 446
-  double f_u = phi_0 - phi_0 - mu * d_phi_0 * a_u, g_u = d_phi_0 - mu * d_phi_0;
-  bool interval_converged = (step_max - step_min) < 0, open_interval = true;
-  double a_t = step_init;
-  a_t = std::min(a_t, step_max);
-  a_t = std::max(a_t, step_min);
-  double x_t[6];
-  for (int k = 0; k < 6; ++k) x_t[k] = x[k] + step_dir[k] * a_t;
-  ndt_pose_matrix(x_t, st.T);  // NDT:827-830
-  if (const int rc = ndt_derivs_at(h, st, x_t, st.T, true)) return rc;  // NDT:837
-  auto dir_dot = [&]() {
+
+  // the 28 sums of the pending evaluation arrive; afterwards another evaluation is pending, or the machine is done
+  void resume(const double* acc) {
+    switch (phase) {
+      case kFirst:
+        ndt_take_derivs(st, acc, true);
+        newton();
+        break;
+      case kStepFirst:  // NDT:837
+        ndt_take_derivs(st, acc, true);
+        phi_t = -st.score;
+        d_phi_t = -dir_dot();
+        psi_t = phi_t - phi_0 - mu * d_phi_0 * a_t;
+        d_psi_t = d_phi_t - mu * d_phi_0;
+        step_loop();
+        break;
+      case kStepInner:  // NDT:881
+        ndt_take_derivs(st, acc, false);
+        phi_t = -st.score;
+        d_phi_t = -dir_dot();
+        psi_t = phi_t - phi_0 - mu * d_phi_0 * a_t;
+        d_psi_t = d_phi_t - mu * d_phi_0;
+        if (open_interval && (psi_t <= 0 && d_psi_t >= 0)) {
+          open_interval = false;
+          f_l = f_l + phi_0 - mu * d_phi_0 * a_l;
+          g_l = g_l + mu * d_phi_0;
+          f_u = f_u + phi_0 - mu * d_phi_0 * a_u;
+          g_u = g_u + mu * d_phi_0;
+        }
+        if (open_interval) interval_converged = ndt_update_interval(a_l, f_l, g_l, a_u, f_u, g_u, a_t, psi_t, d_psi_t);
+        else interval_converged = ndt_update_interval(a_l, f_l, g_l, a_u, f_u, g_u, a_t, phi_t, d_phi_t);
+        step_iterations++;
+        step_loop();
+        break;
+      case kStepHessian:  // NDT:928-929
+        ndt_unpack_hessian(acc, st.H);
+        st.diag.n_hessians++;
+        step_end();
+        break;
+      case kDone:
+        break;
+    }
+  }
+
+  void results(float* T_out, int* converged, int* nr_iterations, double* trans_probability, gorio_ndt_diag* diag) const {
+    std::copy(st.T, st.T + 16, T_out);
+    if (converged) *converged = conv ? 1 : 0;
+    if (nr_iterations) *nr_iterations = nr;
+    if (trans_probability) *trans_probability = prob;
+    if (diag) {
+      *diag = st.diag;
+      diag->score = st.score;
+    }
+  }
+
+ private:
+  double dir_dot() const {
     double s = 0.0;
-    for (int k = 0; k < 6; ++k) s += st.g[k] * step_dir[k];
+    for (int k = 0; k < 6; ++k) s += st.g[k] * delta[k];
     return s;
-  };
-  double phi_t = -st.score, d_phi_t = -dir_dot();
-  double psi_t = phi_t - phi_0 - mu * d_phi_0 * a_t, d_psi_t = d_phi_t - mu * d_phi_0;
-  while (!interval_converged && step_iterations < max_step_iterations && !(psi_t <= 0 && d_phi_t <= -nu * d_phi_0)) {
-    if (open_interval) a_t = ndt_trial_value(a_l, f_l, g_l, a_u, f_u, g_u, a_t, psi_t, d_psi_t);
-    else a_t = ndt_trial_value(a_l, f_l, g_l, a_u, f_u, g_u, a_t, phi_t, d_phi_t);
+  }
+  void ask(int m, Phase ph) {
+    mode = m;
+    phase = ph;
+  }
+  void trial_pose() {  // NDT:825-830
+    for (int k = 0; k < 6; ++k) x_eval[k] = p[k] + delta[k] * a_t;
+    ndt_pose_matrix(x_eval, st.T);
+  }
+
+  // the body of NDT:122-168 up to the line search's first evaluation; loops while a step needs no evaluation at all
+  void newton() {
+    const double n_src = (double)h->n_s;
+    while (!conv) {
+      double mg[6];
+      for (int k = 0; k < 6; ++k) mg[k] = -st.g[k];
+      ndt_svd_solve(st.H, mg, delta);  // NDT:127-129
+      double nn = 0.0;
+      for (int k = 0; k < 6; ++k) nn += delta[k] * delta[k];
+      delta_p_norm = std::sqrt(nn);
+      if (delta_p_norm == 0 || delta_p_norm != delta_p_norm) {  // NDT:134-139
+        prob = st.score / n_src;
+        conv = delta_p_norm == delta_p_norm;
+        phase = kDone;
+        return;
+      }
+      for (int k = 0; k < 6; ++k) delta[k] /= delta_p_norm;
+      if (step_begin(delta_p_norm, h->p.step_size, h->p.transformation_epsilon / 2)) return;  // an evaluation is pending
+      step_taken(0.0);  // NDT:787-789: no descent along the direction, a step of length 0
+    }
+    prob = st.score / n_src;  // NDT:170
+    phase = kDone;
+  }
+
+  // computeStepLengthMT up to NDT:837; false when it returns 0 without an evaluation (d_phi_0 == 0)
+  bool step_begin(double step_init, double smax, double smin) {
+    step_max = smax;
+    step_min = smin;
+    phi_0 = -st.score;
+    d_phi_0 = 0.0;
+    for (int k = 0; k < 6; ++k) d_phi_0 += st.g[k] * delta[k];
+    d_phi_0 = -d_phi_0;
+    if (d_phi_0 >= 0) {
+      if (d_phi_0 == 0) return false;
+      d_phi_0 *= -1;
+      for (int k = 0; k < 6; ++k) delta[k] *= -1;
+    }
+    step_iterations = 0;
+    a_l = 0;
+    a_u = 0;
+    f_l = phi_0 - phi_0 - mu * d_phi_0 * a_l;  // auxiliaryFunction_PsiMT / _dPsiMT, NDTH:433, 446
+    g_l = d_phi_0 - mu * d_phi_0;
+    f_u = phi_0 - phi_0 - mu * d_phi_0 * a_u;
+    g_u = d_phi_0 - mu * d_phi_0;
+    interval_converged = (step_max - step_min) < 0;
+    open_interval = true;
+    a_t = step_init;
     a_t = std::min(a_t, step_max);
     a_t = std::max(a_t, step_min);
-    for (int k = 0; k < 6; ++k) x_t[k] = x[k] + step_dir[k] * a_t;
-    ndt_pose_matrix(x_t, st.T);
-    if (const int rc = ndt_derivs_at(h, st, x_t, st.T, false)) return rc;  // NDT:881
-    phi_t = -st.score;
-    d_phi_t = -dir_dot();
-    psi_t = phi_t - phi_0 - mu * d_phi_0 * a_t;
-    d_psi_t = d_phi_t - mu * d_phi_0;
-    if (open_interval && (psi_t <= 0 && d_psi_t >= 0)) {
-      open_interval = false;
-      f_l = f_l + phi_0 - mu * d_phi_0 * a_l;
-      g_l = g_l + mu * d_phi_0;
-      f_u = f_u + phi_0 - mu * d_phi_0 * a_u;
-      g_u = g_u + mu * d_phi_0;
+    trial_pose();
+    ask(1, kStepFirst);
+    return true;
+  }
+
+  // the head of the loop NDT:850: another trial step, or the end of the search
+  void step_loop() {
+    if (!interval_converged && step_iterations < max_step_iterations && !(psi_t <= 0 && d_phi_t <= -nu * d_phi_0)) {
+      if (open_interval) a_t = ndt_trial_value(a_l, f_l, g_l, a_u, f_u, g_u, a_t, psi_t, d_psi_t);
+      else a_t = ndt_trial_value(a_l, f_l, g_l, a_u, f_u, g_u, a_t, phi_t, d_phi_t);
+      a_t = std::min(a_t, step_max);
+      a_t = std::max(a_t, step_min);
+      trial_pose();
+      ask(0, kStepInner);
+      return;
     }
-    if (open_interval) interval_converged = ndt_update_interval(a_l, f_l, g_l, a_u, f_u, g_u, a_t, psi_t, d_psi_t);
-    else interval_converged = ndt_update_interval(a_l, f_l, g_l, a_u, f_u, g_u, a_t, phi_t, d_phi_t);
-    step_iterations++;
+    if (step_iterations) {  // NDT:928-929: x_eval and st.T are those of the last trial
+      ask(2, kStepHessian);
+      return;
+    }
+    step_end();
   }
-  if (step_iterations) {  // NDT:928-929
-    double acc[28];
-    const gorio::NdtEval ev = ndt_make_eval(h, x_t, st.T);
-    if (const int rc = ndt_evaluate(h, ev, 2, acc)) return rc;
-    ndt_unpack_hessian(acc, st.H);
-    st.diag.n_hessians++;
+
+  void step_end() {
+    st.diag.n_mt_iterations += step_iterations;
+    step_taken(a_t);
+    newton();
   }
-  st.diag.n_mt_iterations += step_iterations;
-  *a_out = a_t;
-  return GORIO_OK;
+
+  // NDT:150-166
+  void step_taken(double a) {
+    delta_p_norm = a;
+    for (int k = 0; k < 6; ++k) {
+      delta[k] *= delta_p_norm;
+      p[k] = p[k] + delta[k];
+    }
+    if (nr > h->p.max_iterations || (nr && (std::fabs(delta_p_norm) < h->p.transformation_epsilon))) conv = true;  // NDT:158-162
+    nr++;
+  }
+};
+
+// the derivative launch of one evaluation mode
+template <typename... A>
+void ndt_launch_batch(int mode, int blocks, hipStream_t stream, A... a) {
+  using namespace gorio;
+  if (mode == 0) ndt_derivative_batch_kernel<float, false><<<blocks, 256, 0, stream>>>(a...);
+  else if (mode == 1) ndt_derivative_batch_kernel<float, true><<<blocks, 256, 0, stream>>>(a...);
+  else ndt_derivative_batch_kernel<double, true><<<blocks, 256, 0, stream>>>(a...);
 }
 }  // namespace
 
@@ -951,6 +1198,8 @@ int gorio_ndt_create(gorio_ndt_t** out, int device) {  // NDT:47-76
   gorio_ndt* h = new (std::nothrow) gorio_ndt();
   if (!h) return ndt_fail(GORIO_ERR_ALLOC, "create: out of memory");
   h->device = device;
+  h->tgt = std::make_shared<gorio::NdtTarget>();
+  h->tgt->device = device;
   gorio_ndt_default_params(&h->p);
   if (hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking) != hipSuccess) {
     delete h;
@@ -975,8 +1224,10 @@ int gorio_ndt_set_params(gorio_ndt_t* h, const gorio_ndt_params* p) {
   if (!p) return ndt_fail(GORIO_ERR_INVALID, "set_params: null argument");
   if (const int rc = ndt_check_params(*p)) return rc;  // before the handle: a refused value needs no device
   if (!h) return ndt_fail(GORIO_ERR_INVALID, "set_params: null handle");
-  if ((float)p->resolution != (float)h->p.resolution || p->min_points_per_voxel != h->p.min_points_per_voxel || p->min_covar_eigvalue_mult != h->p.min_covar_eigvalue_mult)
-    h->map_valid = false;  // NDTH:136-141
+  // NDTH:136-141.  A map other handles look at too is never dropped under them: ndt_ensure_map compares and refuses instead.
+  if (((float)p->resolution != (float)h->p.resolution || p->min_points_per_voxel != h->p.min_points_per_voxel || p->min_covar_eigvalue_mult != h->p.min_covar_eigvalue_mult) &&
+      h->tgt.use_count() == 1)
+    h->tgt->map_valid = false;
   h->p = *p;
   return GORIO_OK;
 }
@@ -992,11 +1243,13 @@ int gorio_ndt_set_target(gorio_ndt_t* h, const float* xyz, int n, int stride_byt
   if (!h) return ndt_fail(GORIO_ERR_INVALID, "set_target: null handle");
   if (n < 0 || (n > 0 && (!xyz || stride_bytes < 12 || stride_bytes % 4))) return ndt_fail(GORIO_ERR_INVALID, "set_target: bad cloud arguments");
   if (n > INT_MAX / 2) return ndt_fail(GORIO_ERR_INVALID, "set_target: too many points");
-  h->map_valid = false;
-  h->has_target = false;
-  if (const int rc = ndt_upload(h, xyz, n, stride_bytes, h->tx, h->ty, h->tz, h->t_cap)) return rc;
-  h->n_t = n;
-  h->has_target = true;
+  ndt_make_private(h);
+  gorio::NdtTarget& t = *h->tgt;
+  t.map_valid = false;
+  t.has_target = false;
+  if (const int rc = ndt_upload(h, xyz, n, stride_bytes, t.tx, t.ty, t.tz, t.t_cap)) return rc;
+  t.n_t = n;
+  t.has_target = true;
   return GORIO_OK;
 }
 
@@ -1020,11 +1273,13 @@ int gorio_ndt_set_source(gorio_ndt_t* h, const float* xyz, int n, int stride_byt
 int gorio_ndt_set_target_device(gorio_ndt_t* h, const float* x, const float* y, const float* z, int n) {
   if (!h) return ndt_fail(GORIO_ERR_INVALID, "set_target_device: null handle");
   if (n < 0 || (n > 0 && (!x || !y || !z)) || n > INT_MAX / 2) return ndt_fail(GORIO_ERR_INVALID, "set_target_device: bad cloud arguments");
-  h->map_valid = false;
-  h->has_target = false;
-  if (const int rc = ndt_copy_device(h, x, y, z, n, h->tx, h->ty, h->tz, h->t_cap)) return rc;
-  h->n_t = n;
-  h->has_target = true;
+  ndt_make_private(h);
+  gorio::NdtTarget& t = *h->tgt;
+  t.map_valid = false;
+  t.has_target = false;
+  if (const int rc = ndt_copy_device(h, x, y, z, n, t.tx, t.ty, t.tz, t.t_cap)) return rc;
+  t.n_t = n;
+  t.has_target = true;
   return GORIO_OK;
 }
 
@@ -1053,10 +1308,11 @@ int gorio_ndt_set_source_device(gorio_ndt_t* h, const float* x, const float* y, 
 // no reference member: how many elements the handle's device buffers hold (they grow, they are never shrunk or freed by a smaller cloud)
 int gorio_ndt_get_capacities(const gorio_ndt_t* h, long long* capacities) {
   if (!h || !capacities) return ndt_fail(GORIO_ERR_INVALID, "get_capacities: null argument");
-  capacities[0] = (long long)h->t_cap;
+  const bool own = h->tgt_owned;  // a sharer owns no target buffers
+  capacities[0] = own ? (long long)h->tgt->t_cap : 0;
   capacities[1] = (long long)h->s_cap;
-  capacities[2] = (long long)h->l_cap;
-  capacities[3] = (long long)h->keys.cap();
+  capacities[2] = own ? (long long)h->tgt->l_cap : 0;
+  capacities[3] = own ? (long long)h->tgt->keys.cap() : 0;
   return GORIO_OK;
 }
 
@@ -1064,24 +1320,25 @@ int gorio_ndt_get_capacities(const gorio_ndt_t* h, long long* capacities) {
 int gorio_ndt_get_voxels(gorio_ndt_t* h, int capacity, int* n_leaves, int* leaf_index, int* nr_points, double* mean, double* cov_raw, double* cov, double* icov, int* min_b,
                          int* div_b) {
   if (!h || !n_leaves) return ndt_fail(GORIO_ERR_INVALID, "get_voxels: null argument");
-  if (!h->has_target) return ndt_fail(GORIO_ERR_STATE, "get_voxels: no target set");
+  if (!h->tgt->has_target) return ndt_fail(GORIO_ERR_STATE, "get_voxels: no target set");
   GORIO_HIP_CHECK(ndt_fail, hipSetDevice(h->device));
-  if (const int rc = ndt_ensure_map(h)) return rc;
-  *n_leaves = h->nl;
+  if (const int rc = ndt_ensure_map(h)) return ndt_fail(rc, "get_voxels: " + g_ndt_err);
+  const gorio::NdtTarget& t = *h->tgt;
+  *n_leaves = t.nl;
   for (int a = 0; a < 3; ++a) {
-    if (min_b) min_b[a] = h->grid.min_b[a];
-    if (div_b) div_b[a] = h->grid.div_b[a];
+    if (min_b) min_b[a] = t.grid.min_b[a];
+    if (div_b) div_b[a] = t.grid.div_b[a];
   }
   const bool any = leaf_index || nr_points || mean || cov_raw || cov || icov;
-  if (!any || h->nl == 0) return GORIO_OK;
-  if (capacity < h->nl) return ndt_fail(GORIO_ERR_INVALID, "get_voxels: capacity below the number of leaves");
-  const size_t nl = h->nl;
-  if (leaf_index) GORIO_HIP_CHECK(ndt_fail, hipMemcpyAsync(leaf_index, h->lidx, sizeof(int) * nl, hipMemcpyDeviceToHost, h->stream));
-  if (nr_points) GORIO_HIP_CHECK(ndt_fail, hipMemcpyAsync(nr_points, h->lcnt, sizeof(int) * nl, hipMemcpyDeviceToHost, h->stream));
-  if (mean) GORIO_HIP_CHECK(ndt_fail, hipMemcpyAsync(mean, h->lmean, sizeof(double) * 3 * nl, hipMemcpyDeviceToHost, h->stream));
-  if (cov_raw) GORIO_HIP_CHECK(ndt_fail, hipMemcpyAsync(cov_raw, h->lraw, sizeof(double) * 9 * nl, hipMemcpyDeviceToHost, h->stream));
-  if (cov) GORIO_HIP_CHECK(ndt_fail, hipMemcpyAsync(cov, h->lcov, sizeof(double) * 9 * nl, hipMemcpyDeviceToHost, h->stream));
-  if (icov) GORIO_HIP_CHECK(ndt_fail, hipMemcpyAsync(icov, h->licov, sizeof(double) * 9 * nl, hipMemcpyDeviceToHost, h->stream));
+  if (!any || t.nl == 0) return GORIO_OK;
+  if (capacity < t.nl) return ndt_fail(GORIO_ERR_INVALID, "get_voxels: capacity below the number of leaves");
+  const size_t nl = t.nl;
+  if (leaf_index) GORIO_HIP_CHECK(ndt_fail, hipMemcpyAsync(leaf_index, t.lidx, sizeof(int) * nl, hipMemcpyDeviceToHost, h->stream));
+  if (nr_points) GORIO_HIP_CHECK(ndt_fail, hipMemcpyAsync(nr_points, t.lcnt, sizeof(int) * nl, hipMemcpyDeviceToHost, h->stream));
+  if (mean) GORIO_HIP_CHECK(ndt_fail, hipMemcpyAsync(mean, t.lmean, sizeof(double) * 3 * nl, hipMemcpyDeviceToHost, h->stream));
+  if (cov_raw) GORIO_HIP_CHECK(ndt_fail, hipMemcpyAsync(cov_raw, t.lraw, sizeof(double) * 9 * nl, hipMemcpyDeviceToHost, h->stream));
+  if (cov) GORIO_HIP_CHECK(ndt_fail, hipMemcpyAsync(cov, t.lcov, sizeof(double) * 9 * nl, hipMemcpyDeviceToHost, h->stream));
+  if (icov) GORIO_HIP_CHECK(ndt_fail, hipMemcpyAsync(icov, t.licov, sizeof(double) * 9 * nl, hipMemcpyDeviceToHost, h->stream));
   GORIO_HIP_CHECK(ndt_fail, hipStreamSynchronize(h->stream));
   return GORIO_OK;
 }
@@ -1127,47 +1384,145 @@ int gorio_ndt_calculate_score(gorio_ndt_t* h, const float* T, double* score) {
 int gorio_ndt_align(gorio_ndt_t* h, const float* guess, float* T_out, int* converged, int* nr_iterations, double* trans_probability, gorio_ndt_diag* diag) {
   if (const int rc = ndt_ready(h, "align")) return rc;
   if (!T_out) return ndt_fail(GORIO_ERR_INVALID, "align: null argument");
-  NdtState st;
-  for (int i = 0; i < 16; ++i) st.T[i] = guess ? guess[i] : ((i % 5 == 0) ? 1.0f : 0.0f);  // NDT:95-104: final_transformation_ = guess
-  float ang[3];
-  ndt_euler012(st.T, ang);
-  double p[6] = {(double)st.T[3], (double)st.T[7], (double)st.T[11], (double)ang[0], (double)ang[1], (double)ang[2]};  // NDT:107-111
-  int nr = 0;
-  bool conv = false;
-  const double n_src = (double)h->n_s;
-  double prob = 0.0;
-  if (const int rc = ndt_derivs_at(h, st, p, st.T, true)) return rc;  // NDT:119: the cloud moved by the guess itself
-  while (!conv) {
-    double mg[6], delta[6];
-    for (int k = 0; k < 6; ++k) mg[k] = -st.g[k];
-    ndt_svd_solve(st.H, mg, delta);  // NDT:127-129
-    double nn = 0.0;
-    for (int k = 0; k < 6; ++k) nn += delta[k] * delta[k];
-    double delta_p_norm = std::sqrt(nn);
-    if (delta_p_norm == 0 || delta_p_norm != delta_p_norm) {  // NDT:134-139
-      prob = st.score / n_src;
-      conv = delta_p_norm == delta_p_norm;
-      goto done;
-    }
-    for (int k = 0; k < 6; ++k) delta[k] /= delta_p_norm;
-    if (const int rc = ndt_step_length(h, st, p, delta, delta_p_norm, h->p.step_size, h->p.transformation_epsilon / 2, &delta_p_norm)) return rc;
-    for (int k = 0; k < 6; ++k) {
-      delta[k] *= delta_p_norm;
-      p[k] = p[k] + delta[k];
-    }
-    if (nr > h->p.max_iterations || (nr && (std::fabs(delta_p_norm) < h->p.transformation_epsilon))) conv = true;  // NDT:158-162
-    nr++;
+  NdtMachine m;
+  m.begin(h, guess);
+  while (!m.done()) {
+    double acc[28];
+    const gorio::NdtEval ev = ndt_make_eval(h, m.x_eval, m.st.T);
+    if (const int rc = ndt_evaluate(h, ev, m.mode, acc)) return rc;
+    m.resume(acc);
   }
-  prob = st.score / n_src;  // NDT:170
-done:
-  std::copy(st.T, st.T + 16, T_out);
-  if (converged) *converged = conv ? 1 : 0;
-  if (nr_iterations) *nr_iterations = nr;
-  if (trans_probability) *trans_probability = prob;
-  if (diag) {
-    *diag = st.diag;
-    diag->score = st.score;
+  m.results(T_out, converged, nr_iterations, trans_probability, diag);
+  return GORIO_OK;
+}
+
+// h looks at owner's target state from now on
+int gorio_ndt_set_target_shared(gorio_ndt_t* h, gorio_ndt_t* owner) {
+  if (!h || !owner) return ndt_fail(GORIO_ERR_INVALID, "set_target_shared: null handle");
+  if (h->device != owner->device) return ndt_fail(GORIO_ERR_INVALID, "set_target_shared: both handles must live on one device");
+  if (!owner->tgt->has_target) return ndt_fail(GORIO_ERR_STATE, "set_target_shared: the owner has no target");
+  if (h == owner || h->tgt == owner->tgt) return GORIO_OK;
+  GORIO_HIP_CHECK(ndt_fail, hipSetDevice(h->device));  // h's own state may die here
+  h->tgt = owner->tgt;  // points and voxel map: one copy on the device, alive until the last handle lets go of it
+  h->tgt_owned = false;
+  return GORIO_OK;
+}
+
+// computeTransformation for many handles, one evaluation of every unfinished handle per round
+int gorio_ndt_align_batch(gorio_ndt_t* const* handles, int count, const float* guesses, float* T_out, int* converged, int* nr_iterations, double* trans_probability,
+                          gorio_ndt_diag* diag, gorio_ndt_batch_stats* stats) {
+  using namespace gorio;
+  if (count == 0) {
+    if (stats) *stats = gorio_ndt_batch_stats{0, 0, 0};
+    return GORIO_OK;
   }
+  if (count < 0 || !handles || !T_out) return ndt_fail(GORIO_ERR_INVALID, "align_batch: bad arguments (count < 0, or no handles, or no T_out)");
+  // ---- validation: nothing is built, allocated or launched before every handle has passed
+  auto who = [](int i) { return "align_batch: handle " + std::to_string(i); };
+  for (int i = 0; i < count; ++i) {
+    if (!handles[i]) return ndt_fail(GORIO_ERR_INVALID, who(i) + ": null handle");
+    if (handles[i]->device != handles[0]->device) return ndt_fail(GORIO_ERR_INVALID, who(i) + ": on another device than handle 0");
+  }
+  {
+    std::vector<const gorio_ndt*> sorted(handles, handles + count);
+    std::sort(sorted.begin(), sorted.end());
+    if (std::adjacent_find(sorted.begin(), sorted.end()) != sorted.end()) {
+      for (int i = 0; i < count; ++i)
+        for (int k = 0; k < i; ++k)
+          if (handles[i] == handles[k]) return ndt_fail(GORIO_ERR_INVALID, who(i) + ": the same handle as handle " + std::to_string(k));
+    }
+  }
+  for (int i = 0; i < count; ++i) {
+    const gorio_ndt* h = handles[i];
+    if (const int rc = ndt_check_ready(h, who(i))) return rc;
+    if (h->tgt->map_valid && h->tgt.use_count() > 1) {
+      const std::string bad = ndt_map_mismatch(h);
+      if (!bad.empty()) return ndt_fail(GORIO_ERR_INVALID, who(i) + ": shared target: " + bad);
+    }
+  }
+  gorio_ndt* lead = handles[0];  // its stream carries the rounds, its scratch holds the tables and the sums
+  GORIO_HIP_CHECK(ndt_fail, hipSetDevice(lead->device));
+  // ---- stale maps, once per target state (each build ends with a synchronisation of the building handle's stream)
+  for (int i = 0; i < count; ++i) {
+    if (const int rc = ndt_ensure_map(handles[i])) return ndt_fail(rc, who(i) + ": " + g_ndt_err);
+    if (handles[i]->tgt->nl == 0) return ndt_fail(GORIO_ERR_STATE, who(i) + ": the target has no finite point");
+  }
+  // ---- scratch for the largest possible round: every handle pending
+  size_t max_blocks = 0;
+  for (int i = 0; i < count; ++i) max_blocks += (size_t)(handles[i]->n_s + 255) / 256;
+  const size_t jobs_bytes = sizeof(NdtJob) * (size_t)count, table_bytes = jobs_bytes + sizeof(int2) * max_blocks;
+  GORIO_HIP_CHECK(ndt_fail, lead->b_jobs.reserve(table_bytes, table_bytes + table_bytes / 4));
+  GORIO_HIP_CHECK(ndt_fail, lead->b_h_jobs.reserve(table_bytes, table_bytes + table_bytes / 4));
+  GORIO_HIP_CHECK(ndt_fail, lead->b_partials.reserve(28 * max_blocks, 28 * (max_blocks + max_blocks / 4)));
+  GORIO_HIP_CHECK(ndt_fail, lead->b_out.reserve((size_t)28 * count, (size_t)28 * (count + count / 4)));
+  GORIO_HIP_CHECK(ndt_fail, lead->b_h_out.reserve(sizeof(double) * 28 * count, sizeof(double) * 28 * (count + count / 4)));
+  std::vector<NdtMachine> m;
+  std::vector<int> order;
+  try {
+    m.resize(count);
+    order.reserve(count);
+  } catch (const std::bad_alloc&) {
+    return ndt_fail(GORIO_ERR_ALLOC, "align_batch: out of host memory");
+  }
+  for (int i = 0; i < count; ++i) m[i].begin(handles[i], guesses ? guesses + (size_t)16 * i : nullptr);
+  gorio_ndt_batch_stats bs{0, 0, 0};
+  NdtJob* const h_jobs = static_cast<NdtJob*>(lead->b_h_jobs.get());
+  for (;;) {
+    // the pending evaluations, grouped by mode: job k of the round belongs to handle order[k]
+    order.clear();
+    int mode_first_block[4] = {0, 0, 0, 0};
+    int blocks = 0;
+    for (int mode = 0; mode < 3; ++mode) {
+      mode_first_block[mode] = blocks;
+      for (int i = 0; i < count; ++i)
+        if (!m[i].done() && m[i].mode == mode) {
+          blocks += (handles[i]->n_s + 255) / 256;
+          order.push_back(i);
+        }
+    }
+    mode_first_block[3] = blocks;
+    const int njobs = (int)order.size();
+    if (njobs == 0) break;
+    int2* const h_wg = reinterpret_cast<int2*>(h_jobs + njobs);
+    int slot = 0;
+    for (int k = 0; k < njobs; ++k) {
+      const gorio_ndt* h = handles[order[k]];
+      const NdtMachine& mk = m[order[k]];
+      NdtJob& j = h_jobs[k];
+      j.sx = h->sx; j.sy = h->sy; j.sz = h->sz;
+      j.n = h->n_s;
+      j.mode = mk.mode;
+      j.first = slot;
+      j.nblk = (h->n_s + 255) / 256;
+      j.vm = h->map();
+      j.ev = ndt_make_eval(h, mk.x_eval, mk.st.T);
+      for (int b = 0; b < j.nblk; ++b) h_wg[slot + b] = make_int2(k, b);
+      slot += j.nblk;
+    }
+    const size_t bytes = sizeof(NdtJob) * (size_t)njobs + sizeof(int2) * (size_t)blocks;  // <= table_bytes
+    GORIO_HIP_CHECK(ndt_fail, hipMemcpyAsync(lead->b_jobs.get(), h_jobs, bytes, hipMemcpyHostToDevice, lead->stream));
+    const NdtJob* d_jobs = static_cast<const NdtJob*>(lead->b_jobs.get());
+    const int2* d_wg = reinterpret_cast<const int2*>(d_jobs + njobs);
+    for (int mode = 0; mode < 3; ++mode) {
+      const int nb = mode_first_block[mode + 1] - mode_first_block[mode];
+      if (nb == 0) continue;
+      ndt_launch_batch(mode, nb, lead->stream, d_jobs, d_wg + mode_first_block[mode], lead->b_partials.get());
+      bs.launches++;
+    }
+    ndt_fold_batch_kernel<<<njobs, 64, 0, lead->stream>>>(d_jobs, lead->b_partials, lead->b_out);
+    bs.launches++;
+    GORIO_HIP_CHECK(ndt_fail, hipGetLastError());
+    GORIO_HIP_CHECK(ndt_fail, hipMemcpyAsync(lead->b_h_out.get(), lead->b_out, sizeof(double) * 28 * njobs, hipMemcpyDeviceToHost, lead->stream));
+    GORIO_HIP_CHECK(ndt_fail, hipStreamSynchronize(lead->stream));  // the pinned tables are free again after it
+    const double* sums = static_cast<const double*>(lead->b_h_out.get());
+    for (int k = 0; k < njobs; ++k) m[order[k]].resume(sums + (size_t)28 * k);
+    bs.rounds++;
+    bs.evaluations += njobs;
+  }
+  for (int i = 0; i < count; ++i)
+    m[i].results(T_out + (size_t)16 * i, converged ? converged + i : nullptr, nr_iterations ? nr_iterations + i : nullptr, trans_probability ? trans_probability + i : nullptr,
+                 diag ? diag + i : nullptr);
+  if (stats) *stats = bs;
   return GORIO_OK;
 }
 

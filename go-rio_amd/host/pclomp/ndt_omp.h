@@ -4,10 +4,12 @@
 // by the library (std::runtime_error here).  getFitnessScore, which the nodelets call after every match (scan_matching_odometry_nodelet.cpp:675,
 // loop_detector.cpp:229, 415), is computed on the GPU as the fast_gicp drop-ins do, through a registration handle of include/gorio_apd.h
 // that holds the same two clouds; through a pcl::Registration base pointer real PCL still runs its own CPU version.
+// Extras without a counterpart in the reference: setInputTargetShared, alignBatch, getFitnessScoreBatch.
 #pragma once
 #include <limits>
 #include <stdexcept>
 #include <string>
+#include <vector>
 
 #include <Eigen/Core>
 #include <pcl/point_cloud.h>
@@ -25,6 +27,7 @@ template <typename PointSource, typename PointTarget>
 class NormalDistributionsTransform : public pcl::Registration<PointSource, PointTarget> {
  protected:
   using Base = pcl::Registration<PointSource, PointTarget>;
+  using Matrix4 = typename Base::Matrix4;
   using PointCloudSource = typename Base::PointCloudSource;
   using PointCloudSourceConstPtr = typename Base::PointCloudSourceConstPtr;
   using PointCloudTargetConstPtr = typename Base::PointCloudTargetConstPtr;
@@ -59,8 +62,17 @@ class NormalDistributionsTransform : public pcl::Registration<PointSource, Point
   void setInputTarget(const PointCloudTargetConstPtr& cloud) override {  // NDTH:122-127
     Base::setInputTarget(cloud);
     fit_target_stale_ = true;
+    fit_shared_with_ = nullptr;
     const int n = (int)cloud->size();
     check(gorio_ndt_set_target(h_, n ? &cloud->points[0].x : nullptr, n, (int)sizeof(PointTarget)), "setInputTarget");
+  }
+  // One map for many registrations (extra): reference the target another object already holds on the device -- its points and its voxel
+  // map -- instead of uploading a private copy and building the same map again.  The objects must agree in resolution.
+  void setInputTargetShared(NormalDistributionsTransform& owner) {
+    check(gorio_ndt_set_target_shared(h_, owner.h_), "setInputTargetShared");
+    Base::setInputTarget(owner.target_);
+    fit_target_stale_ = true;
+    fit_shared_with_ = &owner;
   }
   void setInputSource(const PointCloudSourceConstPtr& cloud) override {
     Base::setInputSource(cloud);
@@ -110,22 +122,87 @@ class NormalDistributionsTransform : public pcl::Registration<PointSource, Point
   // final_transformation_, computed on the GPU (gorio_apd_fitness_score).  The clouds go to that handle at the first call after they changed.
   double getFitnessScore(double max_range = std::numeric_limits<double>::max()) {
     if (!input_ || !target_) throw std::logic_error("pclomp::NormalDistributionsTransform::getFitnessScore: no source or no target");
-    if (!fit_) check_apd(gorio_apd_create(&fit_, 0), "getFitnessScore");
-    if (fit_target_stale_) {
-      const int n = (int)target_->size();
-      check_apd(gorio_apd_set_target(fit_, n ? &target_->points[0].x : nullptr, nullptr, n, (int)sizeof(PointTarget)), "getFitnessScore");
-      fit_target_stale_ = false;
-    }
-    if (fit_source_stale_) {
-      const int n = (int)input_->size();
-      check_apd(gorio_apd_set_source(fit_, n ? &input_->points[0].x : nullptr, nullptr, n, (int)sizeof(PointSource)), "getFitnessScore");
-      fit_source_stale_ = false;
-    }
+    fill_fitness_handle(nullptr, "getFitnessScore");
     float T[16];
     for (int r = 0; r < 4; ++r)
       for (int c = 0; c < 4; ++c) T[4 * r + c] = final_transformation_(r, c);
     double score = 0.0;
     check_apd(gorio_apd_fitness_score(fit_, T, max_range, 0.0, &score, nullptr), "getFitnessScore");
+    return score;
+  }
+
+  // ---- batch surface (extra; no counterpart in the reference).  Loop-closure verification (loop_detector.cpp:386-422) aligns N
+  // candidate sources against one target and scores each result: N x (align, getFitnessScore).  These members do the same for N objects
+  // -- typically sharing the target through setInputTargetShared -- with one device round trip per evaluation round.
+
+  // regs[i]->align(outputs[i], guesses[i]) for every i through ONE gorio_ndt_align_batch: afterwards every object is in the state the
+  // single align leaves (getFinalTransformation, hasConverged, getFinalNumIteration, getTransformationProbability, getDiagnostics),
+  // bit for bit; outputs (may be null) receives the moved sources.  The objects' settings may differ.  On an error std::runtime_error
+  // with the library's message, and no object is modified.
+  static void alignBatch(const std::vector<NormalDistributionsTransform*>& regs, const std::vector<Matrix4>& guesses, std::vector<PointCloudSource>* outputs = nullptr) {
+    if (regs.size() != guesses.size()) throw std::invalid_argument("pclomp::NormalDistributionsTransform::alignBatch: one guess per object");
+    const std::size_t count = regs.size();
+    for (std::size_t i = 0; i < count; ++i) {
+      if (!regs[i]) throw std::invalid_argument("pclomp::NormalDistributionsTransform::alignBatch: null object");
+      if (!regs[i]->input_ || !regs[i]->target_) throw std::runtime_error("pclomp::NormalDistributionsTransform::alignBatch: object " + std::to_string(i) + " has no source or no target");
+    }
+    if (outputs) outputs->resize(count);
+    if (count == 0) return;
+    std::vector<gorio_ndt_t*> hs(count);
+    std::vector<float> G(count * 16), T(count * 16);
+    std::vector<int> conv(count), nr(count);
+    std::vector<double> prob(count);
+    std::vector<gorio_ndt_diag> diag(count);
+    for (std::size_t i = 0; i < count; ++i) {
+      regs[i]->p_.transformation_epsilon = regs[i]->transformation_epsilon_;  // as computeTransformation does
+      regs[i]->p_.max_iterations = regs[i]->max_iterations_;
+      regs[i]->push("alignBatch");
+      hs[i] = regs[i]->h_;
+      for (int r = 0; r < 4; ++r)
+        for (int c = 0; c < 4; ++c) G[i * 16 + 4 * r + c] = guesses[i](r, c);
+    }
+    check(gorio_ndt_align_batch(hs.data(), (int)count, G.data(), T.data(), conv.data(), nr.data(), prob.data(), diag.data(), nullptr), "alignBatch");
+    for (std::size_t i = 0; i < count; ++i) {
+      NormalDistributionsTransform& o = *regs[i];
+      o.trans_probability_ = prob[i];
+      o.diag_ = diag[i];
+      PointCloudSource* out = nullptr;
+      if (outputs) {  // what pcl::Registration::align does to output before computeTransformation
+        out = &(*outputs)[i];
+        out->points = o.input_->points;
+        for (auto& p : out->points) p.data[3] = 1.0f;
+      }
+      o.finish_align(&T[i * 16], conv[i], nr[i], out);
+    }
+  }
+
+  // regs[i]->getFitnessScore(max_range) for every i through ONE gorio_apd_fitness_score_batch at the final transformations: the same
+  // values, bit for bit.  Objects that share an NDT target share the fitness target too (gorio_apd_set_target_shared).
+  static std::vector<double> getFitnessScoreBatch(const std::vector<NormalDistributionsTransform*>& regs, double max_range = std::numeric_limits<double>::max()) {
+    std::vector<double> score(regs.size());
+    if (regs.empty()) return score;
+    for (std::size_t i = 0; i < regs.size(); ++i) {
+      if (!regs[i]) throw std::invalid_argument("pclomp::NormalDistributionsTransform::getFitnessScoreBatch: null object");
+      if (!regs[i]->input_ || !regs[i]->target_) throw std::logic_error("pclomp::NormalDistributionsTransform::getFitnessScoreBatch: no source or no target");
+    }
+    std::vector<gorio_apd_t*> hs(regs.size());
+    std::vector<float> T(regs.size() * 16);
+    for (std::size_t i = 0; i < regs.size(); ++i) {  // owners first: a sharer links to a fitness handle that already holds the target
+      if (!regs[i]->fit_shared_with_) regs[i]->fill_fitness_handle(nullptr, "getFitnessScoreBatch");
+    }
+    for (std::size_t i = 0; i < regs.size(); ++i) {
+      NormalDistributionsTransform& o = *regs[i];
+      if (o.fit_shared_with_) {
+        NormalDistributionsTransform* owner = nullptr;  // only an owner that is in this batch and still on the shared cloud
+        for (std::size_t k = 0; k < regs.size() && !owner; ++k)
+          if (regs[k] == o.fit_shared_with_ && !regs[k]->fit_shared_with_ && regs[k]->target_ == o.target_) owner = regs[k];
+        o.fill_fitness_handle(owner, "getFitnessScoreBatch");
+      }
+      hs[i] = o.fit_;
+      for (int r = 0; r < 4; ++r)
+        for (int c = 0; c < 4; ++c) T[i * 16 + 4 * r + c] = o.final_transformation_(r, c);
+    }
+    regs[0]->check_apd(gorio_apd_fitness_score_batch(hs.data(), (int)regs.size(), T.data(), max_range, 0.0, score.data(), nullptr), "getFitnessScoreBatch");
     return score;
   }
 
@@ -139,16 +216,7 @@ class NormalDistributionsTransform : public pcl::Registration<PointSource, Point
       for (int c = 0; c < 4; ++c) G[4 * r + c] = guess(r, c);
     int conv = 0, nr = 0;
     check(gorio_ndt_align(h_, G, T, &conv, &nr, &trans_probability_, &diag_), "align");
-    for (int r = 0; r < 4; ++r)
-      for (int c = 0; c < 4; ++c) final_transformation_(r, c) = T[4 * r + c];
-    converged_ = conv != 0;
-    nr_iterations_ = nr;
-    for (auto& p : output.points) {  // the cloud moved by the final transformation, as trans_cloud holds it (NDT:833)
-      const float x = p.x, y = p.y, z = p.z;
-      p.x = ((T[0] * x + T[1] * y) + T[2] * z) + T[3];
-      p.y = ((T[4] * x + T[5] * y) + T[6] * z) + T[7];
-      p.z = ((T[8] * x + T[9] * y) + T[10] * z) + T[11];
-    }
+    finish_align(T, conv, nr, &output);
   }
 
  private:
@@ -158,6 +226,41 @@ class NormalDistributionsTransform : public pcl::Registration<PointSource, Point
   double trans_probability_ = 0.0;
   gorio_apd_t* fit_ = nullptr;  // getFitnessScore only
   bool fit_target_stale_ = true, fit_source_stale_ = true;
+  NormalDistributionsTransform* fit_shared_with_ = nullptr;  // the object setInputTargetShared named (not dereferenced: compared with batch members only)
+
+  // what computeTransformation leaves behind, from the ABI's outputs; output (may be null) holds the source on entry
+  void finish_align(const float* T, int conv, int nr, PointCloudSource* output) {
+    for (int r = 0; r < 4; ++r)
+      for (int c = 0; c < 4; ++c) final_transformation_(r, c) = T[4 * r + c];
+    converged_ = conv != 0;
+    nr_iterations_ = nr;
+    if (!output) return;
+    for (auto& p : output->points) {  // the cloud moved by the final transformation, as trans_cloud holds it (NDT:833)
+      const float x = p.x, y = p.y, z = p.z;
+      p.x = ((T[0] * x + T[1] * y) + T[2] * z) + T[3];
+      p.y = ((T[4] * x + T[5] * y) + T[6] * z) + T[7];
+      p.z = ((T[8] * x + T[9] * y) + T[10] * z) + T[11];
+    }
+  }
+  // the private registration handle of getFitnessScore holds the object's two clouds; with share_from the target is that object's
+  // fitness target (one copy on the device) instead of an upload of its own
+  void fill_fitness_handle(NormalDistributionsTransform* share_from, const char* what) {
+    if (!fit_) check_apd(gorio_apd_create(&fit_, 0), what);
+    if (fit_target_stale_) {
+      if (share_from && share_from->fit_ && !share_from->fit_target_stale_) {
+        check_apd(gorio_apd_set_target_shared(fit_, share_from->fit_), what);
+      } else {
+        const int n = (int)target_->size();
+        check_apd(gorio_apd_set_target(fit_, n ? &target_->points[0].x : nullptr, nullptr, n, (int)sizeof(PointTarget)), what);
+      }
+      fit_target_stale_ = false;
+    }
+    if (fit_source_stale_) {
+      const int n = (int)input_->size();
+      check_apd(gorio_apd_set_source(fit_, n ? &input_->points[0].x : nullptr, nullptr, n, (int)sizeof(PointSource)), what);
+      fit_source_stale_ = false;
+    }
+  }
 
   static void check(int rc, const char* what) {
     if (rc < 0) throw std::runtime_error(std::string("pclomp::NormalDistributionsTransform::") + what + ": " + gorio_ndt_last_error());

@@ -6,9 +6,9 @@ import numpy as np
 
 from .apd import GorioError, load_library
 
-NDT_SYMBOLS = ["gorio_ndt_align", "gorio_ndt_calculate_score", "gorio_ndt_create", "gorio_ndt_default_params", "gorio_ndt_derivatives", "gorio_ndt_destroy",
+NDT_SYMBOLS = ["gorio_ndt_align", "gorio_ndt_align_batch", "gorio_ndt_calculate_score", "gorio_ndt_create", "gorio_ndt_default_params", "gorio_ndt_derivatives", "gorio_ndt_destroy",
                "gorio_ndt_get_capacities", "gorio_ndt_get_params", "gorio_ndt_get_voxels", "gorio_ndt_hessian", "gorio_ndt_last_error", "gorio_ndt_set_params", "gorio_ndt_set_source",
-               "gorio_ndt_set_source_device", "gorio_ndt_set_target", "gorio_ndt_set_target_device"]
+               "gorio_ndt_set_source_device", "gorio_ndt_set_target", "gorio_ndt_set_target_device", "gorio_ndt_set_target_shared"]
 KDTREE, DIRECT26, DIRECT7, DIRECT1 = 0, 1, 2, 3  # pclomp::NeighborSearchMethod
 
 
@@ -19,6 +19,11 @@ class NdtParams(C.Structure):
 
 class NdtDiag(C.Structure):
     _fields_ = [("n_derivatives", C.c_int), ("n_hessians", C.c_int), ("n_mt_iterations", C.c_int), ("score", C.c_double)]
+
+
+class NdtBatchStats(C.Structure):
+    """What one align_batch did: lock-step rounds (device round trips), evaluations summed over the handles, kernel launches."""
+    _fields_ = [("rounds", C.c_int), ("evaluations", C.c_int), ("launches", C.c_int)]
 
 
 def _ptr(a):
@@ -78,6 +83,10 @@ class Ndt:
         a = np.ascontiguousarray(xyz, np.float32).reshape(-1, 3)
         self._check(self.lib.gorio_ndt_set_source(self.h, _ptr(a) if a.size else None, a.shape[0], 12))
 
+    def set_target_shared(self, owner):
+        """This handle's target becomes owner's current target: points and voxel map exist once on the device."""
+        self._check(self.lib.gorio_ndt_set_target_shared(self.h, owner.h))
+
     def set_target_device(self, x, y, z, n):
         """x, y, z: device addresses (int) of float arrays of the handle's device."""
         self._check(self.lib.gorio_ndt_set_target_device(self.h, C.c_void_p(x), C.c_void_p(y), C.c_void_p(z), int(n)))
@@ -130,5 +139,33 @@ class Ndt:
         T = np.zeros((4, 4), np.float32)
         conv, nr, prob, d = C.c_int(), C.c_int(), C.c_double(), NdtDiag()
         self._check(self.lib.gorio_ndt_align(self.h, None if g is None else _ptr(g), _ptr(T), C.byref(conv), C.byref(nr), C.byref(prob), C.byref(d)))
-        return {"T": T, "converged": bool(conv.value), "nr_iterations": nr.value, "trans_probability": prob.value, "n_derivatives": d.n_derivatives,
-                "n_hessians": d.n_hessians, "n_mt": d.n_mt_iterations, "score": d.score}
+        return _result(T, conv.value, nr.value, prob.value, d)
+
+
+def _result(T, conv, nr, prob, d):
+    return {"T": T, "converged": bool(conv), "nr_iterations": int(nr), "trans_probability": float(prob), "n_derivatives": d.n_derivatives,
+            "n_hessians": d.n_hessians, "n_mt": d.n_mt_iterations, "score": d.score}
+
+
+def align_batch(handles, guesses=None):
+    """computeTransformation for every handle (Ndt objects of one device) in lock-step through ONE gorio_ndt_align_batch.
+    guesses: None (identity for all) or one 4x4 per handle.  Returns (results, stats): results[i] is the dict Ndt.align returns for
+    handles[i], bit for bit; stats is an NdtBatchStats."""
+    handles = list(handles)
+    count = len(handles)
+    stats = NdtBatchStats()
+    if count == 0:
+        return [], stats
+    lib = handles[0].lib
+    g = None
+    if guesses is not None:
+        g = np.ascontiguousarray(np.stack([np.asarray(x, np.float32).reshape(4, 4) for x in guesses]), np.float32)
+        if g.shape[0] != count:
+            raise ValueError("align_batch: one guess per handle")
+    hs = (C.c_void_p * count)(*[h.h.value for h in handles])
+    T = np.zeros((count, 4, 4), np.float32)
+    conv, nr = np.zeros(count, np.int32), np.zeros(count, np.int32)
+    prob = np.zeros(count, np.float64)
+    diag = (NdtDiag * count)()
+    handles[0]._check(lib.gorio_ndt_align_batch(hs, count, None if g is None else _ptr(g), _ptr(T), _ptr(conv), _ptr(nr), _ptr(prob), diag, C.byref(stats)))
+    return [_result(T[i].copy(), conv[i], nr[i], prob[i], diag[i]) for i in range(count)], stats

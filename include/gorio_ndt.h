@@ -36,10 +36,16 @@
  * A non-finite SOURCE point is refused at set time (GORIO_ERR_INVALID): the reference converts floor(x / leaf) of it to int, which is
  * undefined.  A finite point whose cell coordinate does not fit 31 bits has no neighbour.
  *
+ * Many aligns at once: gorio_ndt_align_batch advances `count` handles in lock-step, one derivative evaluation of every unfinished handle
+ * per round, so a round costs the launches and the round trip of ONE evaluation whatever the count.  The host shell is the same
+ * resumable machine that gorio_ndt_align drives; the batched kernels run the single kernels' per-workgroup body over the same 256-point
+ * blocks and add the block partials in the same order.  The contract of the call: every output of handle i is BIT FOR BIT that of
+ * gorio_ndt_align(handles[i], guesses + 16 i, ...).  gorio_ndt_set_target_shared lets handles look at one target (points and voxel
+ * map exist once on the device), as the loop-closure flow wants it: N candidate sources against one keyframe.
+ *
  * Out of scope: KDTREE search (a radius search over leaf centroids: another structure; REG:127-133 selects it only on request, it
- * is refused with GORIO_ERR_UNSUPPORTED), batched aligns, sharing a target between handles, the scan-pipeline hand-off
- * (include/gorio_scan.h), RCCL sharding, and PCL's single-thread pcl::NormalDistributionsTransform (REG:111: the same algorithm with
- * KDTREE only).
+ * is refused with GORIO_ERR_UNSUPPORTED), gorio_ndt_calculate_score in batch form, the scan-pipeline hand-off (include/gorio_scan.h),
+ * RCCL sharding, and PCL's single-thread pcl::NormalDistributionsTransform (REG:111: the same algorithm with KDTREE only).
  */
 #ifndef GORIO_NDT_H
 #define GORIO_NDT_H
@@ -91,6 +97,17 @@ int gorio_ndt_set_source(gorio_ndt_t* h, const float* xyz, int n, int stride_byt
 int gorio_ndt_set_target_device(gorio_ndt_t* h, const float* x, const float* y, const float* z, int n);
 int gorio_ndt_set_source_device(gorio_ndt_t* h, const float* x, const float* y, const float* z, int n);
 
+/* h's target becomes owner's current target: points and voxel map exist once (no reference member; the semantics of
+ * gorio_apd_set_target_shared).  Both handles must live on one device (GORIO_ERR_INVALID) and the owner must have a target
+ * (GORIO_ERR_STATE).  The link is by value of the moment: a later gorio_ndt_set_target / _set_target_device on either handle detaches that
+ * handle only, and destroying the owner leaves the sharers working.
+ * Map parameters (resolution, min_points_per_voxel, min_covar_eigvalue_mult): while a target is held by ONE handle a changed value marks
+ * the map stale and the next use rebuilds it.  While it is held by several, a handle whose three values differ from those the valid map
+ * was built with gets GORIO_ERR_INVALID from every call that needs the map (the text names the parameter); when no valid map exists
+ * yet, the first handle that needs one builds it with its own values.  search, step_size, outlier_ratio, transformation_epsilon and
+ * max_iterations are per handle and may differ between sharers. */
+int gorio_ndt_set_target_shared(gorio_ndt_t* h, gorio_ndt_t* owner);
+
 /* Parity hook: the leaves of VoxelGridCovariance::applyFilter (VGC:60-370) in ascending linear leaf index (the order of the reference's
  * std::map).  *n_leaves is always set; the arrays (any may be NULL) need capacity >= *n_leaves leaves: leaf_index, nr_points (-1 for a
  * leaf the reference disables, VGC:336-339, 360-363), mean [3], cov_raw [9] (VGC:329-330, before the inflation; zero below
@@ -99,7 +116,8 @@ int gorio_ndt_get_voxels(gorio_ndt_t* h, int capacity, int* n_leaves, int* leaf_
                          int* min_b, int* div_b);
 
 /* No reference member: the elements the handle's device buffers hold, capacities[4] = target points, source points, leaves, sort keys.
- * Buffers grow with the clouds and are kept when a smaller (or empty) cloud follows: equal capacities mean nothing was reallocated. */
+ * Buffers grow with the clouds and are kept when a smaller (or empty) cloud follows: equal capacities mean nothing was reallocated.
+ * A handle whose target came through gorio_ndt_set_target_shared owns none of it and reports 0 for target points, leaves and sort keys. */
 int gorio_ndt_get_capacities(const gorio_ndt_t* h, long long* capacities);
 
 /* computeDerivatives (NDT:180-285) at pose vector p = (x, y, z, roll, pitch, yaw): the source is moved by the float matrix NDT:827-830
@@ -114,6 +132,28 @@ int gorio_ndt_calculate_score(gorio_ndt_t* h, const float* T, double* score);
  * converged, nr_iterations_, trans_probability_.  Any output but T_out may be NULL.  GORIO_ERR_STATE without a source or without a
  * target that has at least one finite point. */
 int gorio_ndt_align(gorio_ndt_t* h, const float* guess, float* T_out, int* converged, int* nr_iterations, double* trans_probability, gorio_ndt_diag* diag);
+
+typedef struct {
+  int rounds;       /* lock-step rounds = device round trips of the batch */
+  int evaluations;  /* derivative + Hessian evaluations summed over the handles */
+  int launches;     /* kernel launches of the rounds (map builds not counted) */
+} gorio_ndt_batch_stats;
+
+/* computeTransformation for `count` handles in lock-step.  guesses: count * 16 floats (handle i's at guesses + 16 i) or NULL (identity);
+ * T_out: count * 16 floats; converged / nr_iterations / trans_probability / diag: count entries or NULL; stats may be NULL.
+ * Every output of handle i is BIT FOR BIT that of gorio_ndt_align(handles[i], guesses + 16 i, ...): the same host shell, the same
+ * per-workgroup kernel body over source points [256 b, 256 b + 256) of block b, the block partials added in block order.
+ * A round collects the pending evaluation of every unfinished handle, sends one job table (one asynchronous copy from pinned memory),
+ * launches the derivative kernel once per evaluation mode present (score + gradient; + Hessian; computeHessian), folds all jobs in
+ * one launch, and ends with one copy of 28 doubles per job and one synchronisation: launches <= 4 * rounds, and
+ * rounds = max_i (n_derivatives_i + n_hessians_i).  Stale maps are built before the first round, once per target state; finished
+ * handles drop out of the later rounds.  The rounds run on handles[0]'s stream and scratch.
+ * count == 0 returns GORIO_OK and touches no device.  count < 0, NULL handles or T_out, a NULL entry, a handle that appears twice or
+ * handles on different devices: GORIO_ERR_INVALID.  A handle gorio_ndt_align would refuse (no target, no or an empty source, no finite
+ * target point, a sharer whose map parameters do not fit the shared map) gives that error with the handle's index in the text.  On a
+ * validation error no handle is changed and no evaluation runs.  Handles need not agree in any parameter. */
+int gorio_ndt_align_batch(gorio_ndt_t* const* handles, int count, const float* guesses, float* T_out, int* converged, int* nr_iterations, double* trans_probability,
+                          gorio_ndt_diag* diag, gorio_ndt_batch_stats* stats);
 
 const char* gorio_ndt_last_error(void);
 

@@ -7,6 +7,13 @@ tests/golden/real_lidar_pair.npz and on a 16 384 x 16 384 synthetic radar pair, 
 one host round trip by construction).  Prints one JSON line.
 
     python tools/ndt_bench.py [--reps 30] [--warmup 5]
+
+With --batch N: N handles on the same two workloads, the guesses perturbed per handle with a fixed seed (up to 0.1 m per axis and
+1 degree of yaw), and per search three timings of the same N aligns: N serial align calls on handles with private targets, N serial
+align calls on handles that share one target, and one align_batch on the sharing handles (with its stats).  The map builds are outside
+the timed region in all three (every handle has aligned once before).
+
+    python tools/ndt_bench.py --batch 16 [--reps 30] [--warmup 5]
 """
 import argparse
 import importlib
@@ -43,11 +50,62 @@ def workloads():
     yield "synthetic_16384", sx, tx
 
 
+def batch_guesses(count, seed=17):
+    rng = np.random.default_rng(seed)
+    out = []
+    for _ in range(count):
+        G = np.eye(4, dtype=np.float32)
+        a = np.deg2rad(rng.uniform(-1.0, 1.0))
+        G[:2, :2] = [[np.cos(a), -np.sin(a)], [np.sin(a), np.cos(a)]]
+        G[:3, 3] = rng.uniform(-0.1, 0.1, 3)
+        out.append(G)
+    return out
+
+
+def batch_main(a):
+    out = {"batch": a.batch, "reps": a.reps, "warmup": a.warmup, "workloads": {}}
+    guesses = batch_guesses(a.batch)
+    for name, src, tgt in workloads():
+        w = {"n_source": int(src.shape[0]), "n_target": int(tgt.shape[0])}
+        private, shared = [], []
+        for i in range(a.batch):
+            n = gorio.Ndt(transformation_epsilon=0.01, max_iterations=64)
+            n.set_target(tgt)
+            n.set_source(src)
+            private.append(n)
+            m = gorio.Ndt(transformation_epsilon=0.01, max_iterations=64)
+            if i == 0:
+                m.set_target(tgt)
+            else:
+                m.set_target_shared(shared[0])
+            m.set_source(src)
+            shared.append(m)
+        for sname, s in SEARCHES.items():
+            for n in private + shared:
+                n.set_params(search=s)
+            r = {}
+            r["serial_private_ms"] = median_ms(lambda: [n.align(g) for n, g in zip(private, guesses)], a.reps, a.warmup)
+            r["serial_shared_ms"] = median_ms(lambda: [n.align(g) for n, g in zip(shared, guesses)], a.reps, a.warmup)
+            r["batch_shared_ms"] = median_ms(lambda: gorio.ndt.align_batch(shared, guesses), a.reps, a.warmup)
+            res, st = gorio.ndt.align_batch(shared, guesses)
+            r["stats"] = {"rounds": st.rounds, "evaluations": st.evaluations, "launches": st.launches}
+            r["serial_over_batch"] = r["serial_private_ms"][0] / r["batch_shared_ms"][0]
+            r["equal_to_serial"] = all(np.array_equal(x["T"], n.align(g)["T"]) for x, n, g in zip(res, private, guesses))
+            w[sname] = r
+        for n in private + shared:
+            n.close()
+        out["workloads"][name] = w
+    print(json.dumps(out))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=30)
     ap.add_argument("--warmup", type=int, default=5)
+    ap.add_argument("--batch", type=int, default=0, help="N handles: N serial aligns (private / shared target) against one align_batch")
     a = ap.parse_args()
+    if a.batch > 0:
+        return batch_main(a)
     out = {"reps": a.reps, "warmup": a.warmup, "workloads": {}}
     p = np.array([0.12, -0.08, 0.03, 0.01, -0.02, 0.03])
     for name, src, tgt in workloads():
