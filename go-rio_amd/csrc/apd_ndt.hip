@@ -14,7 +14,10 @@
 //                  ndt_fold_kernel        the block partials in block order -> 28 doubles
 //   batch          ndt_derivative_batch_kernel, ndt_fold_batch_kernel: the same two bodies (ndt_derivative_block, ndt_fold_sum) for the
 //                                         pending evaluations of many handles: a job table and a per-workgroup (job, local block) table
-//   score          ndt_score_kernel       calculateScore (NDT:935-983), one double per block, ndt_fold_kernel
+//   score          ndt_score_kernel       calculateScore (NDT:935-983), one double per block, ndt_fold_kernel; ndt_score_batch_kernel runs
+//                                         the same body (ndt_score_block) over the job table of the batch for many handles
+//   device clouds  ndt_adopt_kernel       device arrays, the cloud of a scan pipeline or of a gorio_apd handle into the handle's own
+//                                         buffers: the copy and the finiteness check in one pass
 //   align          host                   computeTransformation, computeStepLengthMT and its helpers (NDT:81-171, 648-932) as ONE resumable
 //                                         machine (NdtMachine): gorio_ndt_align drives one, gorio_ndt_align_batch many in lock-step
 // The only device loops are bounded: points of a leaf (<= n), neighbours (<= 26), binary-search steps (<= 32).  Every index that comes
@@ -87,10 +90,18 @@ __global__ __launch_bounds__(256) void ndt_bbox_kernel(const float* __restrict__
   }
 }
 
-// flag[0] |= 1 when a point is not finite (the source check of gorio_ndt_set_source_device)
-__global__ __launch_bounds__(256) void ndt_finite_kernel(const float* __restrict__ x, const float* __restrict__ y, const float* __restrict__ z, int n, int* __restrict__ flag) {
+// Clouds that are already on the device (gorio_ndt_set_*_device, _set_*_from_scan, _set_target_from_apd): ONE pass copies x, y, z of
+// the first n points into (dx, dy, dz) -- each of at least n floats, reserved by the host -- and raises flag[0] for a non-finite
+// point (the source check: it must be known before the source held is replaced).  grid ceil(n / 256), block 256.
+__global__ __launch_bounds__(256) void ndt_adopt_kernel(const float* __restrict__ x, const float* __restrict__ y, const float* __restrict__ z, int n, float* __restrict__ dx,
+                                                        float* __restrict__ dy, float* __restrict__ dz, int* __restrict__ flag) {
   const int i = blockIdx.x * 256 + threadIdx.x;
-  const bool bad = i < n && !ndt_finite3(x[i], y[i], z[i]);
+  bool bad = false;
+  if (i < n) {
+    const float px = x[i], py = y[i], pz = z[i];
+    dx[i] = px; dy[i] = py; dz[i] = pz;
+    bad = !ndt_finite3(px, py, pz);
+  }
   if (__ballot(bad) != 0ull && (threadIdx.x & 63) == 0) atomicOr(flag, 1);
 }
 
@@ -395,7 +406,7 @@ __global__ __launch_bounds__(256) void ndt_derivative_kernel(const float* __rest
 struct NdtJob {
   const float *sx, *sy, *sz;
   int n;
-  int mode;   // 0 <float, false>, 1 <float, true>, 2 <double, true>
+  int mode;   // 0 <float, false>, 1 <float, true>, 2 <double, true>, 3 the score
   int first;  // first partial-block slot
   int nblk;   // ceil(n / 256)
   NdtMapView vm;
@@ -412,11 +423,13 @@ __global__ __launch_bounds__(256) void ndt_derivative_batch_kernel(const NdtJob*
   ndt_derivative_block<S, HESS>(j.sx, j.sy, j.sz, j.n, j.vm, j.ev, w.y, partials + (size_t)(j.first + w.y) * 28);
 }
 
-// calculateScore, NDT:935-983: per point sum of score_inc / neighborhood.size(); one double per block
-__global__ __launch_bounds__(256) void ndt_score_kernel(const float* __restrict__ sx, const float* __restrict__ sy, const float* __restrict__ sz, int n, NdtMapView vm, NdtEval ev,
-                                                        double* __restrict__ partials) {
+// calculateScore, NDT:935-983: per point sum of score_inc / neighborhood.size().  The work of ONE workgroup of 256 lanes, shared by the
+// single and the batched kernel as ndt_derivative_block is: source points [256 block, 256 block + 256) -> out[0], the block's sum
+// (wave_sum, then the four waves in a fixed order).
+__device__ __forceinline__ void ndt_score_block(const float* __restrict__ sx, const float* __restrict__ sy, const float* __restrict__ sz, int n, const NdtMapView& vm,
+                                                const NdtEval& ev, int block, double* __restrict__ out) {
   double sum = 0.0;
-  const int i = blockIdx.x * 256 + threadIdx.x;
+  const int i = block * 256 + threadIdx.x;
   if (i < n) {
     float qx, qy, qz;
     transform_f(ev.T, sx[i], sy[i], sz[i], qx, qy, qz);
@@ -448,7 +461,21 @@ __global__ __launch_bounds__(256) void ndt_score_kernel(const float* __restrict_
   __shared__ double red[4];
   if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = sum;
   __syncthreads();
-  if (threadIdx.x == 0) partials[blockIdx.x] = (red[0] + red[1]) + (red[2] + red[3]);
+  if (threadIdx.x == 0) out[0] = (red[0] + red[1]) + (red[2] + red[3]);
+}
+
+// grid: ceil(n / 256), block 256.  One double per block.
+__global__ __launch_bounds__(256) void ndt_score_kernel(const float* __restrict__ sx, const float* __restrict__ sy, const float* __restrict__ sz, int n, NdtMapView vm, NdtEval ev,
+                                                        double* __restrict__ partials) {
+  ndt_score_block(sx, sy, sz, n, vm, ev, (int)blockIdx.x, partials + blockIdx.x);
+}
+
+// gorio_ndt_calculate_score_batch: the grid and the (job, job-local block) table of ndt_derivative_batch_kernel, under the same host
+// guarantees; the partial buffer holds first + nblk doubles for every job.
+__global__ __launch_bounds__(256) void ndt_score_batch_kernel(const NdtJob* __restrict__ jobs, const int2* __restrict__ wg, double* __restrict__ partials) {
+  const int2 w = wg[blockIdx.x];
+  const NdtJob& j = jobs[w.x];
+  ndt_score_block(j.sx, j.sy, j.sz, j.n, j.vm, j.ev, w.y, partials + (size_t)(j.first + w.y));
 }
 
 // sum over the blocks, in block order, of partials[b * width + k]
@@ -464,11 +491,12 @@ __global__ __launch_bounds__(64) void ndt_fold_kernel(const double* __restrict__
   out[threadIdx.x] = ndt_fold_sum(partials, nblk, width, (int)threadIdx.x);
 }
 
-// grid: one 64-lane workgroup per job.  out[28 job + k] = the job's 28 sums, its partials added in block order
-__global__ __launch_bounds__(64) void ndt_fold_batch_kernel(const NdtJob* __restrict__ jobs, const double* __restrict__ partials, double* __restrict__ out) {
-  if (threadIdx.x >= 28) return;
+// grid: one 64-lane workgroup per job; width <= 64 (28 for the derivative sums, 1 for the score).  out[width job + k] = the job's sums,
+// its partials added in block order
+__global__ __launch_bounds__(64) void ndt_fold_batch_kernel(const NdtJob* __restrict__ jobs, const double* __restrict__ partials, int width, double* __restrict__ out) {
+  if ((int)threadIdx.x >= width) return;
   const NdtJob& j = jobs[blockIdx.x];
-  out[(size_t)blockIdx.x * 28 + threadIdx.x] = ndt_fold_sum(partials + (size_t)j.first * 28, j.nblk, 28, (int)threadIdx.x);
+  out[(size_t)blockIdx.x * width + threadIdx.x] = ndt_fold_sum(partials + (size_t)j.first * width, j.nblk, width, (int)threadIdx.x);
 }
 
 }  // namespace gorio
@@ -514,6 +542,10 @@ struct gorio_ndt {
   int n_s = 0;
   bool has_source = false;
   gorio::DevBuf<int> flag;
+  // staging of a source that comes from the device (ndt_adopt): filled first, swapped with sx, sy, sz only when every point is finite
+  gorio::DevBuf<float> ax, ay, az;
+  size_t a_cap = 0;
+  hipEvent_t adopt_ev = nullptr;  // orders a hand-off's copy behind the producer's stream; made by the first hand-off
   // evaluation scratch
   gorio::DevBuf<double> partials, d_out;
   gorio::PinnedBuf h_out;  // 28 doubles
@@ -576,19 +608,6 @@ int ndt_upload(gorio_ndt* h, const float* xyz, int n, int stride_bytes, gorio::D
   return GORIO_OK;
 }
 
-int ndt_copy_device(gorio_ndt* h, const float* x, const float* y, const float* z, int n, gorio::DevBuf<float>& dx, gorio::DevBuf<float>& dy, gorio::DevBuf<float>& dz, size_t& cap) {
-  GORIO_HIP_CHECK(ndt_fail, hipSetDevice(h->device));
-  const size_t need = std::max(n, 1);
-  GORIO_HIP_CHECK(ndt_fail, gorio::reserve_group(cap, need, need + need / 8 + 64, dx, need + need / 8 + 64, dy, need + need / 8 + 64, dz, need + need / 8 + 64));
-  if (n) {
-    GORIO_HIP_CHECK(ndt_fail, hipMemcpyAsync(dx, x, sizeof(float) * n, hipMemcpyDeviceToDevice, h->stream));
-    GORIO_HIP_CHECK(ndt_fail, hipMemcpyAsync(dy, y, sizeof(float) * n, hipMemcpyDeviceToDevice, h->stream));
-    GORIO_HIP_CHECK(ndt_fail, hipMemcpyAsync(dz, z, sizeof(float) * n, hipMemcpyDeviceToDevice, h->stream));
-  }
-  GORIO_HIP_CHECK(ndt_fail, hipStreamSynchronize(h->stream));
-  return GORIO_OK;
-}
-
 // a target about to be overwritten must not be one other handles still look at (gorio_ndt_set_target_shared): detach first
 void ndt_make_private(gorio_ndt* h) {
   if (h->tgt.use_count() > 1 || !h->tgt_owned) {
@@ -596,6 +615,58 @@ void ndt_make_private(gorio_ndt* h) {
     h->tgt->device = h->device;
   }
   h->tgt_owned = true;
+}
+
+// Every cloud that is already on the device comes in here: x, y, z [n] of the handle's device become the source or the target.  It is
+// the whole of gorio_ndt_set_source_device / _set_target_device (producer == nullptr: the caller orders its own writes, as before) and
+// the device half of gorio_ndt_set_source_from_scan / _set_target_from_scan / _set_target_from_apd, whose argument and state checks
+// come first, in csrc/apd_scan.hip, where the other handle types are complete; there `producer` is the stream the cloud was last
+// written on.  Ordering: that producer may still have work in flight (gorio_apd_set_target_device returns without a synchronisation),
+// so ONE event is recorded on its stream and this handle's stream waits for it on the device; nothing polls.  The copy is complete
+// when the call returns (the synchronisation that brings the flag down), so the producer may overwrite its cloud at once.
+// A source goes to the staging buffers and changes places with the held one only when no point is non-finite: a refusal leaves the
+// held source as it was.  A target is written in place: non-finite target points are accepted (the map skips them), nothing can refuse.
+int ndt_adopt(gorio_ndt* h, const float* x, const float* y, const float* z, int n, hipStream_t producer, bool source, const std::string& what) {
+  GORIO_HIP_CHECK(ndt_fail, hipSetDevice(h->device));
+  const size_t need = std::max(n, 1), grown = need + need / 8 + 64;
+  gorio::NdtTarget* t = nullptr;
+  if (source) {
+    GORIO_HIP_CHECK(ndt_fail, gorio::reserve_group(h->a_cap, need, grown, h->ax, grown, h->ay, grown, h->az, grown));
+  } else {
+    ndt_make_private(h);
+    t = h->tgt.get();
+    t->map_valid = false;
+    t->has_target = false;
+    GORIO_HIP_CHECK(ndt_fail, gorio::reserve_group(t->t_cap, need, grown, t->tx, grown, t->ty, grown, t->tz, grown));
+  }
+  if (n) {
+    GORIO_HIP_CHECK(ndt_fail, h->flag.reserve(1));
+    if (producer) {
+      if (!h->adopt_ev) GORIO_HIP_CHECK(ndt_fail, hipEventCreateWithFlags(&h->adopt_ev, hipEventDisableTiming));
+      GORIO_HIP_CHECK(ndt_fail, hipEventRecord(h->adopt_ev, producer));
+      GORIO_HIP_CHECK(ndt_fail, hipStreamWaitEvent(h->stream, h->adopt_ev, 0));
+    }
+    int flag = 0;
+    GORIO_HIP_CHECK(ndt_fail, hipMemsetAsync(h->flag, 0, sizeof(int), h->stream));
+    if (source) gorio::ndt_adopt_kernel<<<(n + 255) / 256, 256, 0, h->stream>>>(x, y, z, n, h->ax, h->ay, h->az, h->flag);
+    else gorio::ndt_adopt_kernel<<<(n + 255) / 256, 256, 0, h->stream>>>(x, y, z, n, t->tx, t->ty, t->tz, h->flag);
+    GORIO_HIP_CHECK(ndt_fail, hipGetLastError());
+    GORIO_HIP_CHECK(ndt_fail, hipMemcpyAsync(&flag, h->flag, sizeof(int), hipMemcpyDeviceToHost, h->stream));
+    GORIO_HIP_CHECK(ndt_fail, hipStreamSynchronize(h->stream));
+    if (source && flag) return ndt_fail(GORIO_ERR_INVALID, what + ": a point is not finite (the reference's cell index of it is undefined)");
+  }
+  if (source) {
+    std::swap(h->sx, h->ax);
+    std::swap(h->sy, h->ay);
+    std::swap(h->sz, h->az);
+    std::swap(h->s_cap, h->a_cap);
+    h->n_s = n;
+    h->has_source = true;
+  } else {
+    t->n_t = n;
+    t->has_target = true;
+  }
+  return GORIO_OK;
 }
 
 // "" when the handle's three map parameters are those the valid map was built with, else a text that names the first one that differs
@@ -1162,6 +1233,44 @@ struct NdtMachine {
   }
 };
 
+// What gorio_ndt_align_batch and gorio_ndt_calculate_score_batch ask of their handles before anything is built, allocated or launched;
+// `name` is the entry's name in the text.
+int ndt_batch_check(gorio_ndt* const* handles, int count, const std::string& name) {
+  auto who = [&](int i) { return name + ": handle " + std::to_string(i); };
+  for (int i = 0; i < count; ++i) {
+    if (!handles[i]) return ndt_fail(GORIO_ERR_INVALID, who(i) + ": null handle");
+    if (handles[i]->device != handles[0]->device) return ndt_fail(GORIO_ERR_INVALID, who(i) + ": on another device than handle 0");
+  }
+  {
+    std::vector<const gorio_ndt*> sorted(handles, handles + count);
+    std::sort(sorted.begin(), sorted.end());
+    if (std::adjacent_find(sorted.begin(), sorted.end()) != sorted.end()) {
+      for (int i = 0; i < count; ++i)
+        for (int k = 0; k < i; ++k)
+          if (handles[i] == handles[k]) return ndt_fail(GORIO_ERR_INVALID, who(i) + ": the same handle as handle " + std::to_string(k));
+    }
+  }
+  for (int i = 0; i < count; ++i) {
+    const gorio_ndt* h = handles[i];
+    if (const int rc = ndt_check_ready(h, who(i))) return rc;
+    if (h->tgt->map_valid && h->tgt.use_count() > 1) {
+      const std::string bad = ndt_map_mismatch(h);
+      if (!bad.empty()) return ndt_fail(GORIO_ERR_INVALID, who(i) + ": shared target: " + bad);
+    }
+  }
+  return GORIO_OK;
+}
+
+// stale maps, once per target state (each build ends with a synchronisation of the building handle's stream)
+int ndt_batch_maps(gorio_ndt* const* handles, int count, const std::string& name) {
+  for (int i = 0; i < count; ++i) {
+    const std::string who = name + ": handle " + std::to_string(i);
+    if (const int rc = ndt_ensure_map(handles[i])) return ndt_fail(rc, who + ": " + g_ndt_err);
+    if (handles[i]->tgt->nl == 0) return ndt_fail(GORIO_ERR_STATE, who + ": the target has no finite point");
+  }
+  return GORIO_OK;
+}
+
 // the derivative launch of one evaluation mode
 template <typename... A>
 void ndt_launch_batch(int mode, int blocks, hipStream_t stream, A... a) {
@@ -1216,6 +1325,7 @@ void gorio_ndt_destroy(gorio_ndt_t* h) {
     hipStreamSynchronize(h->stream);
     hipStreamDestroy(h->stream);
   }
+  if (h->adopt_ev) hipEventDestroy(h->adopt_ev);
   delete h;
 }
 
@@ -1273,36 +1383,14 @@ int gorio_ndt_set_source(gorio_ndt_t* h, const float* xyz, int n, int stride_byt
 int gorio_ndt_set_target_device(gorio_ndt_t* h, const float* x, const float* y, const float* z, int n) {
   if (!h) return ndt_fail(GORIO_ERR_INVALID, "set_target_device: null handle");
   if (n < 0 || (n > 0 && (!x || !y || !z)) || n > INT_MAX / 2) return ndt_fail(GORIO_ERR_INVALID, "set_target_device: bad cloud arguments");
-  ndt_make_private(h);
-  gorio::NdtTarget& t = *h->tgt;
-  t.map_valid = false;
-  t.has_target = false;
-  if (const int rc = ndt_copy_device(h, x, y, z, n, t.tx, t.ty, t.tz, t.t_cap)) return rc;
-  t.n_t = n;
-  t.has_target = true;
-  return GORIO_OK;
+  return ndt_adopt(h, x, y, z, n, nullptr, false, "set_target_device");
 }
 
-// setInputSource from device arrays; the finiteness check runs on the device BEFORE the source held is replaced
+// setInputSource from device arrays; the finiteness check runs on the device, in the pass that copies, BEFORE the source held is replaced
 int gorio_ndt_set_source_device(gorio_ndt_t* h, const float* x, const float* y, const float* z, int n) {
   if (!h) return ndt_fail(GORIO_ERR_INVALID, "set_source_device: null handle");
   if (n < 0 || (n > 0 && (!x || !y || !z)) || n > INT_MAX / 2) return ndt_fail(GORIO_ERR_INVALID, "set_source_device: bad cloud arguments");
-  GORIO_HIP_CHECK(ndt_fail, hipSetDevice(h->device));
-  if (n) {
-    GORIO_HIP_CHECK(ndt_fail, h->flag.reserve(1));
-    int flag = 0;
-    GORIO_HIP_CHECK(ndt_fail, hipMemsetAsync(h->flag, 0, sizeof(int), h->stream));
-    gorio::ndt_finite_kernel<<<(n + 255) / 256, 256, 0, h->stream>>>(x, y, z, n, h->flag);
-    GORIO_HIP_CHECK(ndt_fail, hipGetLastError());
-    GORIO_HIP_CHECK(ndt_fail, hipMemcpyAsync(&flag, h->flag, sizeof(int), hipMemcpyDeviceToHost, h->stream));
-    GORIO_HIP_CHECK(ndt_fail, hipStreamSynchronize(h->stream));
-    if (flag) return ndt_fail(GORIO_ERR_INVALID, "set_source_device: a point is not finite (the reference's cell index of it is undefined)");
-  }
-  h->has_source = false;
-  if (const int rc = ndt_copy_device(h, x, y, z, n, h->sx, h->sy, h->sz, h->s_cap)) return rc;
-  h->n_s = n;
-  h->has_source = true;
-  return GORIO_OK;
+  return ndt_adopt(h, x, y, z, n, nullptr, true, "set_source_device");
 }
 
 // no reference member: how many elements the handle's device buffers hold (they grow, they are never shrunk or freed by a smaller cloud)
@@ -1418,35 +1506,10 @@ int gorio_ndt_align_batch(gorio_ndt_t* const* handles, int count, const float* g
   }
   if (count < 0 || !handles || !T_out) return ndt_fail(GORIO_ERR_INVALID, "align_batch: bad arguments (count < 0, or no handles, or no T_out)");
   // ---- validation: nothing is built, allocated or launched before every handle has passed
-  auto who = [](int i) { return "align_batch: handle " + std::to_string(i); };
-  for (int i = 0; i < count; ++i) {
-    if (!handles[i]) return ndt_fail(GORIO_ERR_INVALID, who(i) + ": null handle");
-    if (handles[i]->device != handles[0]->device) return ndt_fail(GORIO_ERR_INVALID, who(i) + ": on another device than handle 0");
-  }
-  {
-    std::vector<const gorio_ndt*> sorted(handles, handles + count);
-    std::sort(sorted.begin(), sorted.end());
-    if (std::adjacent_find(sorted.begin(), sorted.end()) != sorted.end()) {
-      for (int i = 0; i < count; ++i)
-        for (int k = 0; k < i; ++k)
-          if (handles[i] == handles[k]) return ndt_fail(GORIO_ERR_INVALID, who(i) + ": the same handle as handle " + std::to_string(k));
-    }
-  }
-  for (int i = 0; i < count; ++i) {
-    const gorio_ndt* h = handles[i];
-    if (const int rc = ndt_check_ready(h, who(i))) return rc;
-    if (h->tgt->map_valid && h->tgt.use_count() > 1) {
-      const std::string bad = ndt_map_mismatch(h);
-      if (!bad.empty()) return ndt_fail(GORIO_ERR_INVALID, who(i) + ": shared target: " + bad);
-    }
-  }
+  if (const int rc = ndt_batch_check(handles, count, "align_batch")) return rc;
   gorio_ndt* lead = handles[0];  // its stream carries the rounds, its scratch holds the tables and the sums
   GORIO_HIP_CHECK(ndt_fail, hipSetDevice(lead->device));
-  // ---- stale maps, once per target state (each build ends with a synchronisation of the building handle's stream)
-  for (int i = 0; i < count; ++i) {
-    if (const int rc = ndt_ensure_map(handles[i])) return ndt_fail(rc, who(i) + ": " + g_ndt_err);
-    if (handles[i]->tgt->nl == 0) return ndt_fail(GORIO_ERR_STATE, who(i) + ": the target has no finite point");
-  }
+  if (const int rc = ndt_batch_maps(handles, count, "align_batch")) return rc;
   // ---- scratch for the largest possible round: every handle pending
   size_t max_blocks = 0;
   for (int i = 0; i < count; ++i) max_blocks += (size_t)(handles[i]->n_s + 255) / 256;
@@ -1509,7 +1572,7 @@ int gorio_ndt_align_batch(gorio_ndt_t* const* handles, int count, const float* g
       ndt_launch_batch(mode, nb, lead->stream, d_jobs, d_wg + mode_first_block[mode], lead->b_partials.get());
       bs.launches++;
     }
-    ndt_fold_batch_kernel<<<njobs, 64, 0, lead->stream>>>(d_jobs, lead->b_partials, lead->b_out);
+    ndt_fold_batch_kernel<<<njobs, 64, 0, lead->stream>>>(d_jobs, lead->b_partials, 28, lead->b_out);
     bs.launches++;
     GORIO_HIP_CHECK(ndt_fail, hipGetLastError());
     GORIO_HIP_CHECK(ndt_fail, hipMemcpyAsync(lead->b_h_out.get(), lead->b_out, sizeof(double) * 28 * njobs, hipMemcpyDeviceToHost, lead->stream));
@@ -1523,6 +1586,54 @@ int gorio_ndt_align_batch(gorio_ndt_t* const* handles, int count, const float* g
     m[i].results(T_out + (size_t)16 * i, converged ? converged + i : nullptr, nr_iterations ? nr_iterations + i : nullptr, trans_probability ? trans_probability + i : nullptr,
                  diag ? diag + i : nullptr);
   if (stats) *stats = bs;
+  return GORIO_OK;
+}
+
+// calculateScore, NDT:935-983, for many handles: one job table, one score launch, one fold launch, one copy, one synchronisation
+int gorio_ndt_calculate_score_batch(gorio_ndt_t* const* handles, int count, const float* T, double* score) {
+  using namespace gorio;
+  if (count == 0) return GORIO_OK;
+  if (count < 0 || !handles || !score) return ndt_fail(GORIO_ERR_INVALID, "calculate_score_batch: bad arguments (count < 0, or no handles, or no score)");
+  if (const int rc = ndt_batch_check(handles, count, "calculate_score_batch")) return rc;
+  gorio_ndt* lead = handles[0];  // its stream carries the launches, its batch scratch holds the table and the sums
+  GORIO_HIP_CHECK(ndt_fail, hipSetDevice(lead->device));
+  if (const int rc = ndt_batch_maps(handles, count, "calculate_score_batch")) return rc;
+  size_t blocks = 0;
+  for (int i = 0; i < count; ++i) blocks += (size_t)(handles[i]->n_s + 255) / 256;
+  if (blocks > (size_t)INT_MAX) return ndt_fail(GORIO_ERR_INVALID, "calculate_score_batch: too many source points in one batch");
+  const size_t bytes = sizeof(NdtJob) * (size_t)count + sizeof(int2) * blocks;
+  GORIO_HIP_CHECK(ndt_fail, lead->b_jobs.reserve(bytes, bytes + bytes / 4));
+  GORIO_HIP_CHECK(ndt_fail, lead->b_h_jobs.reserve(bytes, bytes + bytes / 4));
+  GORIO_HIP_CHECK(ndt_fail, lead->b_partials.reserve(blocks, blocks + blocks / 4));
+  GORIO_HIP_CHECK(ndt_fail, lead->b_out.reserve((size_t)count, (size_t)count + count / 4));
+  GORIO_HIP_CHECK(ndt_fail, lead->b_h_out.reserve(sizeof(double) * count, sizeof(double) * (count + count / 4)));
+  static const float kIdentity[16] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1};
+  NdtJob* const h_jobs = static_cast<NdtJob*>(lead->b_h_jobs.get());
+  int2* const h_wg = reinterpret_cast<int2*>(h_jobs + count);
+  int slot = 0;
+  for (int k = 0; k < count; ++k) {
+    const gorio_ndt* h = handles[k];
+    NdtJob& j = h_jobs[k];
+    j.sx = h->sx; j.sy = h->sy; j.sz = h->sz;
+    j.n = h->n_s;
+    j.mode = 3;
+    j.first = slot;
+    j.nblk = (h->n_s + 255) / 256;
+    j.vm = h->map();
+    j.ev = ndt_make_eval(h, nullptr, T ? T + (size_t)16 * k : kIdentity);
+    for (int b = 0; b < j.nblk; ++b) h_wg[slot + b] = make_int2(k, b);  // x < count, y < nblk: what the kernel relies on
+    slot += j.nblk;
+  }
+  GORIO_HIP_CHECK(ndt_fail, hipMemcpyAsync(lead->b_jobs.get(), h_jobs, bytes, hipMemcpyHostToDevice, lead->stream));
+  const NdtJob* d_jobs = static_cast<const NdtJob*>(lead->b_jobs.get());
+  const int2* d_wg = reinterpret_cast<const int2*>(d_jobs + count);
+  ndt_score_batch_kernel<<<(int)blocks, 256, 0, lead->stream>>>(d_jobs, d_wg, lead->b_partials.get());
+  ndt_fold_batch_kernel<<<count, 64, 0, lead->stream>>>(d_jobs, lead->b_partials, 1, lead->b_out);
+  GORIO_HIP_CHECK(ndt_fail, hipGetLastError());
+  GORIO_HIP_CHECK(ndt_fail, hipMemcpyAsync(lead->b_h_out.get(), lead->b_out, sizeof(double) * count, hipMemcpyDeviceToHost, lead->stream));
+  GORIO_HIP_CHECK(ndt_fail, hipStreamSynchronize(lead->stream));  // the pinned table is free again after it
+  const double* sums = static_cast<const double*>(lead->b_h_out.get());
+  for (int k = 0; k < count; ++k) score[k] = sums[k] / (double)handles[k]->n_s;  // NDT:982
   return GORIO_OK;
 }
 

@@ -633,6 +633,38 @@ static int scan_hand_off(gorio_apd* apd, gorio_scan* scan, bool source) {
 int gorio_apd_set_source_from_scan(gorio_apd_t* apd, gorio_scan_t* scan) { return scan_hand_off(apd, scan, true); }
 int gorio_apd_set_target_from_scan(gorio_apd_t* apd, gorio_scan_t* scan) { return scan_hand_off(apd, scan, false); }
 
+// ---- the hand-offs of include/gorio_ndt.h.  They live here because this is where gorio_scan, gorio_apd and gorio_ndt are all complete
+// types; the device half is ndt_adopt (csrc/apd_ndt.hip).  A hand-off is a COPY of x, y, z of the first n points -- NDT wants neither
+// labels nor a search index and keeps a SoA cloud of its own -- so it moves none of the pipeline's counters.
+// Order of the points: the pipeline's output is stage_cloud[GROUND], the columns gorio_scan_get_output downloads, written by
+// scan_permute_kernel / compact_scatter_kernel in output order.  A registration cloud keeps x[i], y[i], z[i] == p4[i] for i < n in the
+// order it was given (copy_cloud_kernel, copy_clouds_kernel, submap_store_kernel, upload_cloud); the search index sorts into arrays of
+// its own (idx_sx, idx_orig), never in place.  So neither side needs a permutation.
+// Streams: gorio_scan_run synchronises the pipeline's stream after the last kernel that writes the columns (the label upload, just
+// before have_output is set), but gorio_apd_set_target_device / _set_clouds_device_batch return with their copy kernel in flight, so
+// ndt_adopt orders its copy behind the producer's stream with one event in every case.
+static int ndt_scan_hand_off(gorio_ndt* ndt, gorio_scan* scan, bool source) {
+  const std::string what = source ? "set_source_from_scan" : "set_target_from_scan";
+  if (!ndt) return ndt_fail(GORIO_ERR_INVALID, what + ": null handle");
+  if (!scan) return ndt_fail(GORIO_ERR_INVALID, what + ": null pipeline");
+  if (!scan->have_output) return ndt_fail(GORIO_ERR_STATE, what + ": the pipeline's last run produced no frame");
+  if (ndt->device != scan->device) return ndt_fail(GORIO_ERR_INVALID, what + ": both handles must live on one device");
+  const ScanCloud& c = *scan->stage_cloud[GORIO_SCAN_STAGE_GROUND];
+  return ndt_adopt(ndt, c.col(0), c.col(1), c.col(2), scan->n_out, scan->stream, source, what);
+}
+int gorio_ndt_set_source_from_scan(gorio_ndt_t* ndt, gorio_scan_t* scan) { return ndt_scan_hand_off(ndt, scan, true); }
+int gorio_ndt_set_target_from_scan(gorio_ndt_t* ndt, gorio_scan_t* scan) { return ndt_scan_hand_off(ndt, scan, false); }
+
+int gorio_ndt_set_target_from_apd(gorio_ndt_t* ndt, gorio_apd_t* apd) {
+  const std::string what = "set_target_from_apd";
+  if (!ndt) return ndt_fail(GORIO_ERR_INVALID, what + ": null handle");
+  if (!apd) return ndt_fail(GORIO_ERR_INVALID, what + ": null registration handle");
+  if (ndt->device != apd->device) return ndt_fail(GORIO_ERR_INVALID, what + ": both handles must live on one device");
+  const DevCloud& t = *apd->tgt;
+  if (!t.present) return ndt_fail(GORIO_ERR_STATE, what + ": the registration handle has no input target");
+  return ndt_adopt(ndt, t.x, t.y, t.z, t.n, apd->stream, false, what);
+}
+
 int gorio_scan_get_counters(const gorio_scan_t* h, long long* point_uploads, long long* index_builds, long long* point_downloads) {
   if (!h) return scan_fail(GORIO_ERR_INVALID, "get_counters: null handle");
   if (point_uploads) *point_uploads = h->point_uploads;

@@ -4,7 +4,9 @@
 // by the library (std::runtime_error here).  getFitnessScore, which the nodelets call after every match (scan_matching_odometry_nodelet.cpp:675,
 // loop_detector.cpp:229, 415), is computed on the GPU as the fast_gicp drop-ins do, through a registration handle of include/gorio_apd.h
 // that holds the same two clouds; through a pcl::Registration base pointer real PCL still runs its own CPU version.
-// Extras without a counterpart in the reference: setInputTargetShared, alignBatch, getFitnessScoreBatch.
+// Extras without a counterpart in the reference (INTEGRATION.md sections 8, 11): setInputTargetShared, alignBatch, getFitnessScoreBatch,
+// calculateScoreBatch, and the inputs that are already on the device: setInputSourceFromScan / setInputTargetFromScan (the frame a
+// gorio::ScanPreprocessor just produced) and setInputTargetSubmap (scan-to-submap mode).
 #pragma once
 #include <limits>
 #include <stdexcept>
@@ -18,6 +20,7 @@
 
 #include "gorio_apd.h"
 #include "gorio_ndt.h"
+#include "gorio_scan.h"
 
 namespace pclomp {
 
@@ -30,6 +33,8 @@ class NormalDistributionsTransform : public pcl::Registration<PointSource, Point
   using Matrix4 = typename Base::Matrix4;
   using PointCloudSource = typename Base::PointCloudSource;
   using PointCloudSourceConstPtr = typename Base::PointCloudSourceConstPtr;
+  using PointCloudTarget = typename Base::PointCloudTarget;
+  using PointCloudTargetPtr = typename Base::PointCloudTargetPtr;
   using PointCloudTargetConstPtr = typename Base::PointCloudTargetConstPtr;
   using Base::converged_;
   using Base::final_transformation_;
@@ -79,6 +84,65 @@ class NormalDistributionsTransform : public pcl::Registration<PointSource, Point
     fit_source_stale_ = true;
     const int n = (int)cloud->size();
     check(gorio_ndt_set_source(h_, n ? &cloud->points[0].x : nullptr, n, (int)sizeof(PointSource)), "setInputSource");
+  }
+  // The frame a gorio::ScanPreprocessor just produced (radar_preprocessing/scan_preprocessor.hpp) as source / target (extra): one
+  // device-to-device copy into the NDT handle (gorio_ndt_set_source_from_scan) instead of an upload of the cloud process() downloaded.
+  // The pcl cloud that process() returned becomes input_ / target_.  The same call hands the frame to the private handle of
+  // getFitnessScore, with the search index the preprocessing built -- now, not at the first getFitnessScore: by then the preprocessor
+  // may hold the next frame.  So a getFitnessScore after the match uploads nothing and builds no index.
+  template <typename Preprocessor>
+  void setInputSourceFromScan(Preprocessor& pre) {
+    if (!pre.last_scan()) throw std::runtime_error("pclomp::NormalDistributionsTransform::setInputSourceFromScan: the preprocessor's last process() produced no frame");
+    check(gorio_ndt_set_source_from_scan(h_, pre.handle()), "setInputSourceFromScan");
+    Base::setInputSource(pre.last_scan());
+    fit_source_stale_ = true;  // until the hand-off below has succeeded
+    ensure_fitness_handle("setInputSourceFromScan");
+    check_apd(gorio_apd_set_source_from_scan(fit_, pre.handle()), "setInputSourceFromScan");
+    fit_source_stale_ = false;
+  }
+  template <typename Preprocessor>
+  void setInputTargetFromScan(Preprocessor& pre) {
+    if (!pre.last_scan()) throw std::runtime_error("pclomp::NormalDistributionsTransform::setInputTargetFromScan: the preprocessor's last process() produced no frame");
+    check(gorio_ndt_set_target_from_scan(h_, pre.handle()), "setInputTargetFromScan");
+    Base::setInputTarget(pre.last_scan());
+    fit_target_stale_ = true;
+    fit_shared_with_ = nullptr;
+    ensure_fitness_handle("setInputTargetFromScan");
+    check_apd(gorio_apd_set_target_from_scan(fit_, pre.handle()), "setInputTargetFromScan");
+    fit_target_stale_ = false;
+  }
+  // Scan-to-submap target assembly on the GPU (extra; the signature and the return value of FastAPDGICP::setInputTargetSubmap, in place of
+  // the CPU loop of scan_matching_odometry_nodelet.cpp:602-612): keyframe clouds moved by their relative poses, concatenated, downsampled
+  // (voxel_leaf <= 0: the launch files' NONE).  The fitness handle assembles it (gorio_apd_set_target_submap) and keeps it as its own
+  // target; the NDT handle takes a copy on the device (gorio_ndt_set_target_from_apd).  The assembled cloud is returned and kept as target_.
+  PointCloudTargetConstPtr setInputTargetSubmap(const std::vector<PointCloudTargetConstPtr>& clouds,
+                                                const std::vector<Eigen::Matrix4d, Eigen::aligned_allocator<Eigen::Matrix4d>>& rel_poses, double voxel_leaf = 0.0) {
+    if (clouds.empty() || clouds.size() != rel_poses.size()) throw std::invalid_argument("pclomp::NormalDistributionsTransform::setInputTargetSubmap: one relative pose per keyframe cloud");
+    std::vector<gorio_apd_keyframe> fr(clouds.size());
+    std::vector<double> poses(clouds.size() * 16);
+    for (std::size_t k = 0; k < clouds.size(); ++k) {
+      for (int r = 0; r < 4; ++r)
+        for (int c = 0; c < 4; ++c) poses[k * 16 + r * 4 + c] = rel_poses[k](r, c);
+      const bool any = clouds[k] && !clouds[k]->points.empty();
+      fr[k].xyz = any ? &clouds[k]->points[0].x : nullptr;
+      fr[k].label = nullptr;  // neither NDT nor the fitness score reads labels
+      fr[k].n = any ? static_cast<int>(clouds[k]->size()) : 0;
+      fr[k].point_stride_bytes = static_cast<int>(sizeof(PointTarget));
+      fr[k].rel_pose = &poses[k * 16];
+    }
+    ensure_fitness_handle("setInputTargetSubmap");
+    fit_target_stale_ = true;  // whatever happens below, the fitness handle's target is no longer target_
+    fit_shared_with_ = nullptr;
+    int n = 0;
+    check_apd(gorio_apd_set_target_submap(fit_, fr.data(), static_cast<int>(fr.size()), voxel_leaf, &n), "setInputTargetSubmap");
+    check(gorio_ndt_set_target_from_apd(h_, fit_), "setInputTargetSubmap");
+    PointCloudTargetPtr out(new PointCloudTarget());
+    out->resize(n);
+    if (n > 0) check_apd(gorio_apd_get_target_points(fit_, &out->points[0].x, nullptr, n, static_cast<int>(sizeof(PointTarget))), "setInputTargetSubmap");
+    for (auto& p : out->points) p.data[3] = 1.0f;
+    Base::setInputTarget(out);
+    fit_target_stale_ = false;
+    return out;
   }
   void setResolution(float resolution) {  // NDTH:132-142
     p_.resolution = resolution;
@@ -176,6 +240,28 @@ class NormalDistributionsTransform : public pcl::Registration<PointSource, Point
     }
   }
 
+  // regs[i]->calculateScore(regs[i]'s own source moved by transforms[i]) for every i through ONE gorio_ndt_calculate_score_batch: the
+  // values gorio_ndt_calculate_score gives one by one, bit for bit.  No object is modified.
+  static std::vector<double> calculateScoreBatch(const std::vector<NormalDistributionsTransform*>& regs, const std::vector<Matrix4>& transforms) {
+    if (regs.size() != transforms.size()) throw std::invalid_argument("pclomp::NormalDistributionsTransform::calculateScoreBatch: one transform per object");
+    const std::size_t count = regs.size();
+    for (std::size_t i = 0; i < count; ++i) {
+      if (!regs[i]) throw std::invalid_argument("pclomp::NormalDistributionsTransform::calculateScoreBatch: null object");
+      if (!regs[i]->input_ || !regs[i]->target_) throw std::runtime_error("pclomp::NormalDistributionsTransform::calculateScoreBatch: object " + std::to_string(i) + " has no source or no target");
+    }
+    std::vector<double> score(count);
+    if (count == 0) return score;
+    std::vector<gorio_ndt_t*> hs(count);
+    std::vector<float> T(count * 16);
+    for (std::size_t i = 0; i < count; ++i) {
+      hs[i] = regs[i]->h_;
+      for (int r = 0; r < 4; ++r)
+        for (int c = 0; c < 4; ++c) T[i * 16 + 4 * r + c] = transforms[i](r, c);
+    }
+    check(gorio_ndt_calculate_score_batch(hs.data(), (int)count, T.data(), score.data()), "calculateScoreBatch");
+    return score;
+  }
+
   // regs[i]->getFitnessScore(max_range) for every i through ONE gorio_apd_fitness_score_batch at the final transformations: the same
   // values, bit for bit.  Objects that share an NDT target share the fitness target too (gorio_apd_set_target_shared).
   static std::vector<double> getFitnessScoreBatch(const std::vector<NormalDistributionsTransform*>& regs, double max_range = std::numeric_limits<double>::max()) {
@@ -242,10 +328,14 @@ class NormalDistributionsTransform : public pcl::Registration<PointSource, Point
       p.z = ((T[8] * x + T[9] * y) + T[10] * z) + T[11];
     }
   }
-  // the private registration handle of getFitnessScore holds the object's two clouds; with share_from the target is that object's
-  // fitness target (one copy on the device) instead of an upload of its own
-  void fill_fitness_handle(NormalDistributionsTransform* share_from, const char* what) {
+  void ensure_fitness_handle(const char* what) {
     if (!fit_) check_apd(gorio_apd_create(&fit_, 0), what);
+  }
+  // the private registration handle of getFitnessScore holds the object's two clouds; with share_from the target is that object's
+  // fitness target (one copy on the device) instead of an upload of its own.  A side that is not stale is already there: uploaded by
+  // an earlier call, handed over by setInput*FromScan, or assembled by setInputTargetSubmap.
+  void fill_fitness_handle(NormalDistributionsTransform* share_from, const char* what) {
+    ensure_fitness_handle(what);
     if (fit_target_stale_) {
       if (share_from && share_from->fit_ && !share_from->fit_target_stale_) {
         check_apd(gorio_apd_set_target_shared(fit_, share_from->fit_), what);

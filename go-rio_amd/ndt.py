@@ -6,9 +6,10 @@ import numpy as np
 
 from .apd import GorioError, load_library
 
-NDT_SYMBOLS = ["gorio_ndt_align", "gorio_ndt_align_batch", "gorio_ndt_calculate_score", "gorio_ndt_create", "gorio_ndt_default_params", "gorio_ndt_derivatives", "gorio_ndt_destroy",
-               "gorio_ndt_get_capacities", "gorio_ndt_get_params", "gorio_ndt_get_voxels", "gorio_ndt_hessian", "gorio_ndt_last_error", "gorio_ndt_set_params", "gorio_ndt_set_source",
-               "gorio_ndt_set_source_device", "gorio_ndt_set_target", "gorio_ndt_set_target_device", "gorio_ndt_set_target_shared"]
+NDT_SYMBOLS = ["gorio_ndt_align", "gorio_ndt_align_batch", "gorio_ndt_calculate_score", "gorio_ndt_calculate_score_batch", "gorio_ndt_create", "gorio_ndt_default_params",
+               "gorio_ndt_derivatives", "gorio_ndt_destroy", "gorio_ndt_get_capacities", "gorio_ndt_get_params", "gorio_ndt_get_voxels", "gorio_ndt_hessian", "gorio_ndt_last_error",
+               "gorio_ndt_set_params", "gorio_ndt_set_source", "gorio_ndt_set_source_device", "gorio_ndt_set_source_from_scan", "gorio_ndt_set_target", "gorio_ndt_set_target_device",
+               "gorio_ndt_set_target_from_apd", "gorio_ndt_set_target_from_scan", "gorio_ndt_set_target_shared"]
 KDTREE, DIRECT26, DIRECT7, DIRECT1 = 0, 1, 2, 3  # pclomp::NeighborSearchMethod
 
 
@@ -94,6 +95,17 @@ class Ndt:
     def set_source_device(self, x, y, z, n):
         self._check(self.lib.gorio_ndt_set_source_device(self.h, C.c_void_p(x), C.c_void_p(y), C.c_void_p(z), int(n)))
 
+    def set_source_from_scan(self, scan):
+        """The output of a prep.ScanPipeline's last OK run becomes the source: one device-to-device copy, no host round trip."""
+        self._check(self.lib.gorio_ndt_set_source_from_scan(self.h, scan.h))
+
+    def set_target_from_scan(self, scan):
+        self._check(self.lib.gorio_ndt_set_target_from_scan(self.h, scan.h))
+
+    def set_target_from_apd(self, apd):
+        """The current target of a registration object (apd.ApdGicp: what setInputTargetSubmap assembled, say) becomes the target."""
+        self._check(self.lib.gorio_ndt_set_target_from_apd(self.h, apd._h))
+
     def capacities(self):
         """Elements the device buffers hold: dict of target, source, leaves, keys."""
         c = (C.c_longlong * 4)()
@@ -169,3 +181,22 @@ def align_batch(handles, guesses=None):
     diag = (NdtDiag * count)()
     handles[0]._check(lib.gorio_ndt_align_batch(hs, count, None if g is None else _ptr(g), _ptr(T), _ptr(conv), _ptr(nr), _ptr(prob), diag, C.byref(stats)))
     return [_result(T[i].copy(), conv[i], nr[i], prob[i], diag[i]) for i in range(count)], stats
+
+
+def calculate_score_batch(handles, Ts=None):
+    """calculateScore for every handle (Ndt objects of one device) through ONE gorio_ndt_calculate_score_batch.  Ts: None (identity for
+    all) or one 4x4 per handle.  Returns a float64 array: element i is what handles[i].calculate_score(Ts[i]) returns, bit for bit."""
+    handles = list(handles)
+    count = len(handles)
+    score = np.zeros(count, np.float64)
+    if count == 0:
+        return score
+    lib = handles[0].lib
+    t = None
+    if Ts is not None:
+        t = np.ascontiguousarray(np.stack([np.asarray(x, np.float32).reshape(4, 4) for x in Ts]), np.float32)
+        if t.shape[0] != count:
+            raise ValueError("calculate_score_batch: one transform per handle")
+    hs = (C.c_void_p * count)(*[h.h.value for h in handles])
+    handles[0]._check(lib.gorio_ndt_calculate_score_batch(hs, count, None if t is None else _ptr(t), _ptr(score)))
+    return score

@@ -43,9 +43,13 @@
  * gorio_ndt_align(handles[i], guesses + 16 i, ...).  gorio_ndt_set_target_shared lets handles look at one target (points and voxel
  * map exist once on the device), as the loop-closure flow wants it: N candidate sources against one keyframe.
  *
+ * Inputs that are already on the device: gorio_ndt_set_source_from_scan / _set_target_from_scan take the output of the scan pipeline
+ * (include/gorio_scan.h), gorio_ndt_set_target_from_apd the current target of a registration handle of include/gorio_apd.h (the
+ * scan-to-submap target, say), each as one device-to-device copy.  gorio_ndt_calculate_score_batch is the score's batch form.
+ *
  * Out of scope: KDTREE search (a radius search over leaf centroids: another structure; REG:127-133 selects it only on request, it
- * is refused with GORIO_ERR_UNSUPPORTED), gorio_ndt_calculate_score in batch form, the scan-pipeline hand-off (include/gorio_scan.h),
- * RCCL sharding, and PCL's single-thread pcl::NormalDistributionsTransform (REG:111: the same algorithm with KDTREE only).
+ * is refused with GORIO_ERR_UNSUPPORTED), RCCL sharding, and PCL's single-thread pcl::NormalDistributionsTransform (REG:111: the same
+ * algorithm with KDTREE only).
  */
 #ifndef GORIO_NDT_H
 #define GORIO_NDT_H
@@ -77,6 +81,8 @@ typedef struct {
 } gorio_ndt_diag;
 
 typedef struct gorio_ndt gorio_ndt_t;
+struct gorio_scan; /* gorio_scan_t of include/gorio_scan.h */
+struct gorio_apd;  /* gorio_apd_t of include/gorio_apd.h */
 
 /* The constructor's values, NDT:47-76. */
 void gorio_ndt_default_params(gorio_ndt_params* p);
@@ -115,9 +121,27 @@ int gorio_ndt_set_target_shared(gorio_ndt_t* h, gorio_ndt_t* owner);
 int gorio_ndt_get_voxels(gorio_ndt_t* h, int capacity, int* n_leaves, int* leaf_index, int* nr_points, double* mean, double* cov_raw, double* cov, double* icov,
                          int* min_b, int* div_b);
 
+/* setInputSource / setInputTarget with the output of the pipeline's last OK run (the points gorio_scan_get_output reports, in its
+ * order), without a host round trip: one device-to-device copy of x, y, z into the handle's own buffers, ordered behind the pipeline's
+ * stream by an event.  It is a copy, not a share: the pipeline may load its next frame at once, and none of its counters moves (no
+ * upload, no index build, no download).  Afterwards the handle is as gorio_ndt_set_source_device / _set_target_device leave it for the
+ * same points: a target detaches from its sharers and marks the map stale; a source is checked for non-finite points on the device
+ * in the pass that copies it, and a refusal (GORIO_ERR_INVALID) leaves the source held in place.
+ * Reported before any device call: a NULL handle of either kind or handles on different devices GORIO_ERR_INVALID, a pipeline whose
+ * last run produced no frame GORIO_ERR_STATE. */
+int gorio_ndt_set_source_from_scan(gorio_ndt_t* ndt, struct gorio_scan* scan);
+int gorio_ndt_set_target_from_scan(gorio_ndt_t* ndt, struct gorio_scan* scan);
+/* setInputTarget with the CURRENT target of a registration handle of gorio_apd.h (what gorio_apd_set_target_submap assembled, a scan
+ * handed over to it, a device or host cloud), in the order gorio_apd_get_target_points reports it: the scan-to-submap mode
+ * (SMO:602-618 of scan_matching_odometry_nodelet.cpp) for the default method.  The same copy, ordering and errors as above; a handle
+ * without a target gives GORIO_ERR_STATE.  The registration handle is not changed and may take its next target at once. */
+int gorio_ndt_set_target_from_apd(gorio_ndt_t* ndt, struct gorio_apd* apd);
+
 /* No reference member: the elements the handle's device buffers hold, capacities[4] = target points, source points, leaves, sort keys.
  * Buffers grow with the clouds and are kept when a smaller (or empty) cloud follows: equal capacities mean nothing was reallocated.
- * A handle whose target came through gorio_ndt_set_target_shared owns none of it and reports 0 for target points, leaves and sort keys. */
+ * A handle whose target came through gorio_ndt_set_target_shared owns none of it and reports 0 for target points, leaves and sort keys.
+ * A source that comes from the device (gorio_ndt_set_source_device, _set_source_from_scan) is checked while it is copied into a staging
+ * buffer, which then changes places with the buffer held: "source points" is the buffer held. */
 int gorio_ndt_get_capacities(const gorio_ndt_t* h, long long* capacities);
 
 /* computeDerivatives (NDT:180-285) at pose vector p = (x, y, z, roll, pitch, yaw): the source is moved by the float matrix NDT:827-830
@@ -154,6 +178,16 @@ typedef struct {
  * validation error no handle is changed and no evaluation runs.  Handles need not agree in any parameter. */
 int gorio_ndt_align_batch(gorio_ndt_t* const* handles, int count, const float* guesses, float* T_out, int* converged, int* nr_iterations, double* trans_probability,
                           gorio_ndt_diag* diag, gorio_ndt_batch_stats* stats);
+
+/* calculateScore (NDT:935-983) for `count` handles in one round trip.  T: count * 16 floats (handle i's at T + 16 i) or NULL (identity
+ * for all); score: count doubles.  score[i] is BIT FOR BIT what gorio_ndt_calculate_score(handles[i], T + 16 i, &s) returns: the same
+ * per-workgroup body over the same 256-point blocks, the block partials added in block order, the division by the source size on
+ * the host (NDT:982).  One job table goes up, one score launch runs over all handles, one fold launch, one copy of count doubles
+ * and one synchronisation follow, on handles[0]'s stream and scratch; stale maps are built before, once per target state.
+ * Validation as for gorio_ndt_align_batch: count == 0 returns GORIO_OK and touches no device; count < 0, NULL handles or score, a NULL
+ * entry, a handle that appears twice or handles on different devices: GORIO_ERR_INVALID; a handle the single call would refuse gives
+ * that error with the handle's index in the text.  On a validation error no handle is changed and nothing runs. */
+int gorio_ndt_calculate_score_batch(gorio_ndt_t* const* handles, int count, const float* T, double* score);
 
 const char* gorio_ndt_last_error(void);
 
