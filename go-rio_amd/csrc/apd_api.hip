@@ -1473,14 +1473,22 @@ int gorio_apd_set_target_submap(gorio_apd_t* h, const gorio_apd_keyframe* frames
     VoxGrid g;
     g.inv = 1.0f / (float)voxel_leaf;
     const long long dx = (long long)((mx[0] - mn[0]) * g.inv) + 1, dy = (long long)((mx[1] - mn[1]) * g.inv) + 1, dz = (long long)((mx[2] - mn[2]) * g.inv) + 1;
-    if (dx * dy * dz <= (long long)INT_MAX) {  // otherwise: "Leaf size is too small for the input dataset" -> PCL returns the input unchanged
-      int div_b[3];
+    // div_b = floor(max inv) - floor(min inv) + 1 can exceed d = (int64)((max - min) inv) + 1 by one per axis, so d's product can pass
+    // PCL's test while div_b's overflows the int PCL multiplies it in (undefined there).  Defined here: the
+    // product of div_b must fit int32 as well, as ndt_ensure_map requires of its grid; otherwise the input is returned unchanged.
+    long long div_b[3] = {1, 1, 1};
+    bool fits = dx * dy * dz <= (long long)INT_MAX;  // otherwise: "Leaf size is too small for the input dataset" -> PCL returns the input unchanged
+    if (fits) {
       for (int a = 0; a < 3; ++a) {
         g.min_b[a] = (int)std::floor(mn[a] * g.inv);
-        div_b[a] = (int)std::floor(mx[a] * g.inv) - g.min_b[a] + 1;
+        div_b[a] = (long long)(int)std::floor(mx[a] * g.inv) - (long long)g.min_b[a] + 1;
       }
-      g.div0 = div_b[0];
-      g.div01 = div_b[0] * div_b[1];
+      const long long div01 = div_b[0] * div_b[1];  // every factor is at most 2^31 + 1: each product is tested before the next is formed
+      fits = div01 <= (long long)INT_MAX && div01 * div_b[2] <= (long long)INT_MAX;
+    }
+    if (fits) {
+      g.div0 = (int)div_b[0];
+      g.div01 = (int)(div_b[0] * div_b[1]);
       const int npow2 = sort_padded_size(m);
       HIP_TRY(h, h->d_sub_keys.reserve(npow2));
       const int nblocks = (m + 255) / 256;

@@ -200,9 +200,10 @@ def align(guess, src_xyz, src_label, tgt_xyz, tgt_label, src_cov, tgt_cov, param
     return out
 
 
-def submap_assemble(frames, rel_poses, voxel_leaf=0.0):
+def submap_assemble(frames, rel_poses, voxel_leaf=0.0, with_counts=False):
     """SMO:602-618: transform the keyframe clouds by rel_poses (4x4 double), concatenate, downsample (voxel_leaf <= 0: the launch
-    files' NONE = PassThrough).  frames: list of (xyz [n,3] float32, label [n] float32).  Returns (xyz, label)."""
+    files' NONE = PassThrough).  frames: list of (xyz [n,3] float32, label [n] float32).  Returns (xyz, label), and with_counts the
+    number of input points behind every output point as a third array."""
     xyz = _f32(np.concatenate([f[0] for f in frames]))
     lab = _f32(np.concatenate([f[1] for f in frames]))
     cnt = np.ascontiguousarray([f[0].shape[0] for f in frames], np.int32)
@@ -210,10 +211,13 @@ def submap_assemble(frames, rel_poses, voxel_leaf=0.0):
     cap = xyz.shape[0]
     ox = np.empty((max(cap, 1), 3), np.float32)
     ol = np.empty(max(cap, 1), np.float32)
+    oc = np.zeros(max(cap, 1), np.int32)
     n = lib().apdo_submap_assemble(_p(xyz, C.c_float), _p(lab, C.c_float), _p(cnt, C.c_int), _p(T, C.c_double), len(frames), C.c_double(voxel_leaf),
-                                   _p(ox, C.c_float), _p(ol, C.c_float), cap)
+                                   _p(ox, C.c_float), _p(ol, C.c_float), _p(oc, C.c_int), cap)
     if n < 0:
         raise RuntimeError("apdo_submap_assemble failed")
+    if with_counts:
+        return ox[:n].copy(), ol[:n].copy(), oc[:n].copy()
     return ox[:n].copy(), ol[:n].copy()
 
 

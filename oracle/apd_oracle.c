@@ -1007,6 +1007,8 @@ void apdo_transform_point_f(const double* T, const float* p, float* q) {
  *        (AccumulatorNormal: Eigen 3.3 normalize() leaves a zero vector alone) -- so a voxel's label becomes sign(sum).
  *        PCL orders the points of one voxel by an unstable std::sort; here they are added in ascending input order.
  *        When the voxel count overflows int32 PCL warns and returns the input unchanged; so does this.
+ * The product of div_b must fit int32 as well (PCL multiplies it in an int and overflows: undefined there), otherwise the input is
+ * returned unchanged too.  out_count (or NULL): the number of input points behind every output point, 1 on a pass-through.
  * Returns the number of output points (<= cap), or -1 when cap is too small.
  */
 typedef struct {
@@ -1022,7 +1024,7 @@ static int vox_cmp(const void* a, const void* b) {
 }
 
 int apdo_submap_assemble(const float* xyz /* all frames, packed n x 3 */, const float* label, const int* frame_n, const double* rel_pose /* count x 16, row-major */,
-                         int count, double voxel_leaf, float* out_xyz, float* out_label, int cap) {
+                         int count, double voxel_leaf, float* out_xyz, float* out_label, int* out_count /* input points per output point, or NULL */, int cap) {
   int total = 0;
   for (int k = 0; k < count; k++) total += frame_n[k];
   float* tx = (float*)malloc(sizeof(float) * 3 * (size_t)(total > 0 ? total : 1));
@@ -1054,15 +1056,21 @@ int apdo_submap_assemble(const float* xyz /* all frames, packed n x 3 */, const 
         if (tx[3 * (size_t)i + a] > mx[a]) mx[a] = tx[3 * (size_t)i + a];
       }
     const int64_t dx = (int64_t)((mx[0] - mn[0]) * inv) + 1, dy = (int64_t)((mx[1] - mn[1]) * inv) + 1, dz = (int64_t)((mx[2] - mn[2]) * inv) + 1;
+    /* div_b can exceed d by one per axis, so d's product can pass PCL's test while div_b.x div_b.y (an int in PCL) overflows: undefined
+     * in the reference.  Defined here: the product of div_b must fit int32 too, otherwise output = input. */
+    int min_b[3] = {0, 0, 0};
+    int64_t div_b[3] = {1, 1, 1};
     if (dx * dy * dz > (int64_t)INT32_MAX) {
       passthrough = 1; /* "Leaf size is too small for the input dataset. Integer indices would overflow." -> output = input */
     } else {
-      int min_b[3], max_b[3], div_b[3];
       for (int a = 0; a < 3; a++) {
         min_b[a] = (int)floorf(mn[a] * inv);
-        max_b[a] = (int)floorf(mx[a] * inv);
-        div_b[a] = max_b[a] - min_b[a] + 1;
+        div_b[a] = (int64_t)(int)floorf(mx[a] * inv) - (int64_t)min_b[a] + 1;
       }
+      const int64_t div01 = div_b[0] * div_b[1]; /* factors <= 2^31 + 1: tested before the next product is formed */
+      if (div01 > (int64_t)INT32_MAX || div01 * div_b[2] > (int64_t)INT32_MAX) passthrough = 1;
+    }
+    if (!passthrough) {
       refs = (apdo_vox_ref*)malloc(sizeof(apdo_vox_ref) * (size_t)m);
       for (int i = 0; i < m; i++) {
         const int i0 = (int)floorf(tx[3 * (size_t)i] * inv) - min_b[0];
@@ -1095,6 +1103,7 @@ int apdo_submap_assemble(const float* xyz /* all frames, packed n x 3 */, const 
         out_xyz[3 * (size_t)n_out + 2] = sz / cnt;
         const float z2 = sn * sn;
         out_label[n_out] = z2 > 0.f ? sn / sqrtf(z2) : sn;
+        if (out_count) out_count[n_out] = j - i;
         n_out++;
         i = j;
       }
@@ -1106,6 +1115,8 @@ int apdo_submap_assemble(const float* xyz /* all frames, packed n x 3 */, const 
     } else {
       memcpy(out_xyz, tx, sizeof(float) * 3 * (size_t)m);
       memcpy(out_label, tl, sizeof(float) * (size_t)m);
+      if (out_count)
+        for (int i = 0; i < m; i++) out_count[i] = 1;
       n_out = m;
     }
   }

@@ -241,6 +241,76 @@ class VoxelMap:
         return np.where(inside & (self._codes[pos] == code), pos, -1).astype(np.int32)
 
 
+def _inverse_cofactor_rows(m):
+    """inverse_cofactor for a stack [n, 4, 4]: the same expressions element by element, so the same bits"""
+    a00, a01, a02, a11, a12, a22 = m[:, 0, 0], m[:, 0, 1], m[:, 0, 2], m[:, 1, 1], m[:, 1, 2], m[:, 2, 2]
+    c00 = a11 * a22 - a12 * a12
+    c01 = a02 * a12 - a01 * a22
+    c02 = a01 * a12 - a02 * a11
+    r = 1.0 / (a00 * c00 + a01 * c01 + a02 * c02)
+    out = np.zeros(m.shape)
+    out[:, 0, 0], out[:, 0, 1], out[:, 0, 2] = c00 * r, c01 * r, c02 * r
+    out[:, 1, 1], out[:, 1, 2], out[:, 2, 2] = (a00 * a22 - a02 * a02) * r, (a01 * a02 - a00 * a12) * r, (a00 * a11 - a01 * a01) * r
+    out[:, 1, 0], out[:, 2, 0], out[:, 2, 1] = out[:, 0, 1], out[:, 0, 2], out[:, 1, 2]
+    out[:, 3, 3] = 1.0 / m[:, 3, 3]
+    return out
+
+
+def _matvec_rows(m, v):
+    """_matvec for stacks [n, 4, 4] and [n, 4]"""
+    return ((m[:, :, 0] * v[:, 0:1] + m[:, :, 1] * v[:, 1:2]) + m[:, :, 2] * v[:, 2:3]) + m[:, :, 3] * v[:, 3:4]
+
+
+class VoxelMapVec(VoxelMap):
+    """VoxelMap without the loop over the points, for clouds of 1e5 points and more: the voxels are found by a stable sort of the
+    integer triples, and the k-th point of every voxel (in INPUT order) is added in step k -- the additions every voxel sees, and their
+    order, are those of VoxelMap, so every array is equal to the bit (tests/test_voxel_scenes.py holds the two together with
+    np.array_equal on every scene of at most 4097 points)."""
+
+    def __init__(self, xyz, covs, resolution, mode=ADDITIVE):
+        pts = np.concatenate([np.asarray(xyz, np.float32).astype(np.float64), np.ones((len(xyz), 1))], axis=1)
+        covs = np.asarray(covs, np.float64)
+        self.resolution = float(resolution)
+        self.mode = mode
+        additive = mode in (ADDITIVE, ADDITIVE_WEIGHTED)
+        coords = voxel_coord(pts, resolution)
+        n = pts.shape[0]
+        order = np.lexsort((coords[:, 2], coords[:, 1], coords[:, 0]))  # stable: input order inside a voxel
+        sc = coords[order]
+        first = np.ones(n, bool)
+        first[1:] = (sc[1:] != sc[:-1]).any(axis=1)
+        starts = np.nonzero(first)[0]
+        counts = np.diff(np.append(starts, n))
+        if additive:  # VOX:112-116
+            term_c, term_m = covs, pts
+        else:  # VOX:86-94
+            ci = covs.copy()
+            ci[:, 3, 3] = 1.0
+            term_c = _inverse_cofactor_rows(ci)
+            term_m = _matvec_rows(term_c, pts)
+        mean, cov = np.zeros((starts.size, 4)), np.zeros((starts.size, 4, 4))
+        for k in range(int(counts.max())):
+            m = counts > k
+            i = order[starts[m] + k]
+            mean[m] += term_m[i]
+            cov[m] += term_c[i]
+        if additive:  # VOX:118-121
+            mean = mean / counts[:, None]
+            cov = cov / counts[:, None, None]
+        else:  # VOX:96-102
+            cov[:, 3, 3] = 1.0
+            mean[:, 3] = 1.0
+            cov = _inverse_cofactor_rows(cov)
+            mean = _matvec_rows(cov, mean)
+        self.coord = sc[starts].reshape(-1, 3)
+        self.num_points = counts.astype(np.int64)
+        self.mean, self.cov = mean, cov
+        self._lo = self.coord.min(axis=0) - 1
+        self._dim = self.coord.max(axis=0) + 1 - self._lo + 1
+        self._codes = self._encode(self.coord)
+        assert np.all(np.diff(self._codes) > 0)
+
+
 # ------------------------------------------------------------------------------------------------ FastVGICP
 
 class Vgicp:

@@ -11,17 +11,13 @@ import pytest
 
 import gicp_restatement as gr
 import gicp_scenes as gs
+from map_checks import MAP_RTOL, check_map, rel  # noqa: F401 -- shared with tests/test_voxel_edges_gpu.py
 
 apd = importlib.import_module("go-rio_amd.apd")
 pytestmark = pytest.mark.gpu
 
 H_RTOL = 1e-9
-MAP_RTOL = 1e-12
 SHIPPED = dict(corr_dist_threshold=2.0, transformation_epsilon=0.1)  # launch/ntu_loop3.launch:85-96
-
-
-def rel(a, b):
-    return float(np.max(np.abs(np.asarray(a) - np.asarray(b))) / max(np.max(np.abs(b)), 1e-300))
 
 
 @pytest.fixture(scope="module")
@@ -141,15 +137,6 @@ def test_gicp_batch_equals_singles_and_mixed_batch_refused(gpu, gorio, covs):
 
 VG_CONFIGS = [(gr.DIRECT1, gr.ADDITIVE, 1.0), (gr.DIRECT7, gr.ADDITIVE, 1.0), (gr.DIRECT27, gr.ADDITIVE, 1.0), (gr.DIRECT1, gr.ADDITIVE, 0.5),
               (gr.DIRECT7, gr.ADDITIVE, 0.5), (gr.DIRECT27, gr.ADDITIVE, 0.5), (gr.DIRECT7, gr.MULTIPLICATIVE, 1.0), (gr.DIRECT7, gr.MULTIPLICATIVE, 0.5)]
-
-
-def check_map(vm, ref):
-    assert np.array_equal(vm["coord"], ref.coord)
-    assert np.array_equal(vm["num_points"], ref.num_points)
-    m = max(rel(vm["mean"][v], ref.mean[v]) for v in range(len(ref.mean)))
-    c = max(rel(vm["cov"][v], ref.cov[v]) for v in range(len(ref.cov)))
-    print("voxel map: %d voxels, mean %.2e cov %.2e (per-voxel relative)" % (len(ref.mean), m, c))
-    assert m < MAP_RTOL and c < MAP_RTOL
 
 
 @pytest.mark.parametrize("search,mode,res", VG_CONFIGS)

@@ -9,33 +9,11 @@ import pytest
 import ndt_restatement as R
 import ndt_scenes as S
 from conftest import rot_err
+from map_checks import check_ndt_map as _check_map
 
 pytestmark = pytest.mark.gpu
 SEARCHES = [R.DIRECT1, R.DIRECT7, R.DIRECT26]
 REL = 1e-9
-
-
-def _check_map(gorio, gpu, target, resolution=1.0):
-    ref = R.build_voxel_map(target, resolution)
-    n = gorio.Ndt(device=gpu, resolution=resolution)
-    n.set_target(target)
-    v = n.voxels()
-    n.close()
-    assert np.array_equal(v["leaf_index"], ref.idx)
-    assert np.array_equal(v["min_b"], ref.min_b) and np.array_equal(v["div_b"], ref.div_b)
-    raw_cnt = np.where(ref.count < 0, -1, ref.count)
-    assert np.array_equal(v["nr_points"], raw_cnt)  # the disabled flag (-1) of every leaf included
-    assert np.array_equal(v["mean"], ref.mean)
-    big = np.abs(ref.count) >= 6
-    big |= ref.count == -1
-    assert np.array_equal(v["cov_raw"][big], ref.cov_raw[big])
-    on = ref.count >= 6
-    if on.any():
-        scale = np.abs(ref.icov[on]).max(axis=(1, 2), keepdims=True)
-        assert (np.abs(v["icov"][on] - ref.icov[on]) / scale).max() < REL
-        cscale = np.abs(ref.cov[on]).max(axis=(1, 2), keepdims=True)
-        assert (np.abs(v["cov"][on] - ref.cov[on]) / cscale).max() < REL
-    return ref, v
 
 
 @pytest.fixture(scope="module")
