@@ -11,7 +11,9 @@ import pytest
 import gicp_scenes as gs
 import ground_scenes as grs
 import sc_scenes as ss
+import ugpm_shape_cases as ugpm_cases
 from test_prep_gpu import _radar_targets
+from test_ugpm_shapes_gpu import _DIAG, ERR_UNSUPPORTED, _batch, _records
 
 synth = importlib.import_module("go-rio_amd.synth")
 
@@ -161,6 +163,60 @@ def test_ego_velocity_context_across_sizes(gpu, gorio):
     for k, (t, s) in enumerate(cases):
         assert reused[k]["success"] and reused[k]["inlier"].sum() > 0
         assert _same(reused[k], _in_thread(lambda: prep.ego_velocity(t, s, cfg))), k
+
+
+def _ugpm_window(S, seed):
+    return dict(name=f"S{S}_{seed}", win=synth.window_for_states(S, seed=seed), kw={}, S=S)
+
+
+def _ugpm_lpm(seed):
+    w = synth.imu_window(seed=seed, duration=1.0, vel_hz=20.0)
+    return dict(name=f"lpm_{seed}", win=w, kw=dict(type=ugpm_cases.LPM, infer_t=[w["start_t"] + 0.4, w["end_t"]]), S=None)
+
+
+def _ugpm_run(gorio, cs):
+    """One batch call on this thread's context: (raw records, diagnostics, error code)."""
+    b, code = _batch(gorio, cs), 0
+    try:
+        b.run()
+    except gorio.GorioError as e:
+        code = e.code
+    return b.out.copy(), b.diagnostics(), code, b
+
+
+def test_ugpm_context_across_batches(gpu, gorio):
+    """One thread's UGPM context through five batches: small; every buffer grows and the LPM buffers appear; one window inside the kept
+    capacities with stale tails behind it; a refused window between two valid ones; the window arrays grow again.  Each batch equals the
+    same batch on a fresh thread (a fresh context, no iteration budget from an earlier batch) bit for bit, as
+    test_mixed_batch_equals_single_windows relies on batch = single."""
+    w = synth.imu_window(seed=7102, duration=2.0)
+    chunked = dict(name="chunked", win=w, kw=dict(quantum=0.7123, infer_t=[w["start_t"] + 0.6, w["start_t"] + 1.3, w["end_t"]]), S=None)
+    batches = [
+        [_ugpm_window(21, 7001), _ugpm_window(21, 7002)],
+        [_ugpm_window(17, 7011), _ugpm_window(21, 7012), _ugpm_window(66, 7013), _ugpm_lpm(7014), _ugpm_window(17, 7015), chunked, _ugpm_window(66, 7016),
+         _ugpm_lpm(7017), _ugpm_window(21, 7018)],
+        [_ugpm_window(21, 7021)],
+        [_ugpm_window(66, 7031), _ugpm_window(161, 7032), _ugpm_window(21, 7033)],
+        [_ugpm_window((17, 21, 33, 40, 41, 66)[k % 6], 7040 + k) for k in range(16)] + [_ugpm_lpm(7060)],
+    ]
+    reused = _in_thread(lambda: [_ugpm_run(gorio, cs)[:3] for cs in batches])
+    for step, cs in enumerate(batches):
+        out, diag, code = reused[step]
+        ref_out, ref_diag, ref_code, b = _in_thread(lambda: _ugpm_run(gorio, cs))
+        assert code == ref_code == (ERR_UNSUPPORTED if step == 3 else 0), step
+        for k, c in enumerate(cs):
+            refused = step == 3 and k == 1
+            assert diag[k]["status"] == (ERR_UNSUPPORTED if refused else 0), (step, k)
+            assert [diag[k][q] for q in _DIAG + ("status",)] == [ref_diag[k][q] for q in _DIAG + ("status",)], (step, c["name"])
+            o = sum(b.counts[:k])
+            got, ref = out[o:o + b.counts[k]], ref_out[o:o + b.counts[k]]
+            assert len(got) == len(c["kw"].get("infer_t", [0]))
+            if refused:
+                assert np.isnan(got).all() and np.isnan(ref).all()
+            else:
+                assert np.isfinite(got[:, :14]).all() and np.array_equal(got, ref), (step, c["name"])
+            if c["S"] is not None and not refused:
+                assert diag[k]["nb_state"] == c["S"] and diag[k]["iters_rot"] > 0 and diag[k]["iters_vel"] > 0
 
 
 def test_scan_context_handle_across_database_growth(gpu, gorio):
