@@ -9,8 +9,12 @@
 //   decisions, TGR, A-GLE  host                     O(patches) on the per-patch status values (PWP:745-850, 894-1018)
 //   final plane            ground_final_fit_kernel  one workgroup per scan over all of cloud_ground (PWP:866-867)
 //   under-ground pass      host                     PWP:872-884, with the point after every erased point left untested
-// The patches of a scan are independent inside the chain: the first fit of a patch is over its seeds, which are never empty, so
-// the stale pc_mean_ / cov_ that an empty fit inherits (see fit_plane) never crosses patches.  No workgroup waits for another.
+// The patches of a scan are independent inside the chain: the first fit of a patch is over its seeds, and with num_lpr >= 1 and
+// th_seeds > 0 (ground_check_params refuses anything else) the seeds are never empty -- the lowest point the LPR averages lies at or
+// below the LPR height, or no point is averaged, the height is 0 and every point lies below the zone-0 margin (margin x sensor
+// height, negative for a sensor above the ground).  So the stale
+// pc_mean_ / cov_ that an empty fit inherits (see fit_plane) never crosses patches.  No workgroup waits for another.  With num_lpr = 0
+// the reference's LPR height is 0 (PWP:646), a patch above th_seeds has no seeds and its first fit reads the previous patch's moments.
 //
 // One plane estimate (estimate_plane PWP:461-479, estimate_plane_cov PWP:497-580), fit_plane below:
 //   * pcl::computeMeanAndCovarianceMatrix: the nine float accumulators of PCL 1.10, summed by ONE lane in point order, un-fused
@@ -751,7 +755,12 @@ int ground_fail(int code, const std::string& m) {
 int ground_check_params(const gorio_ground_params& p) {
   if (p.enable_RVPF) return ground_fail(GORIO_ERR_INVALID, "enable_RVPF is not supported (off in the reference and in every caller)");
   if (p.num_iter < 1 || p.num_iter > GORIO_GROUND_MAX_FITS - 1) return ground_fail(GORIO_ERR_INVALID, "num_iter must be in [1, 8]");
-  if (p.num_lpr < 0 || p.num_min_pts < 1) return ground_fail(GORIO_ERR_INVALID, "num_lpr must be >= 0 and num_min_pts >= 1");
+  if (p.num_min_pts < 1) return ground_fail(GORIO_ERR_INVALID, "num_min_pts must be >= 1");
+  // PWP:646-653: with num_lpr = 0 the LPR height is 0, and with th_seeds <= 0 not even the lowest point lies below it + th_seeds
+  if (p.num_lpr < 1 || !(p.th_seeds > 0))
+    return ground_fail(GORIO_ERR_INVALID,
+                       "num_lpr must be >= 1 and th_seeds > 0: otherwise a patch can have no seeds, and its empty first fit would read the previous patch's "
+                       "pc_mean_ / cov_, which the per-patch kernels do not carry");
   if (!(p.min_range >= 0 && p.min_range < p.max_range)) return ground_fail(GORIO_ERR_INVALID, "need 0 <= min_range < max_range");
   if (p.max_flatness_storage < 0 || p.max_elevation_storage < 0) return ground_fail(GORIO_ERR_INVALID, "storage sizes must be >= 0");
   int np = 0;

@@ -1,7 +1,8 @@
 // Drop-in for include/patchworkpp/patchworkpp.hpp of the Go-RIO sources (PWP): Params and PatchWorkpp<PointT> with the reference's
 // constructor and estimate_ground signature, on top of the C ABI of include/gorio_ground.h.  The segmentation runs on the GPU; this
-// class only gathers whole points into cloud_ground / cloud_nonground in the order the library returns.  RVPF is refused
-// (std::invalid_argument), as the library refuses it; ego_vel is unused, as in the reference (PWP:761, 784).
+// class only gathers whole points into cloud_ground / cloud_nonground in the order the library returns.  What the library refuses
+// -- RVPF, num_lpr < 1 or th_seeds <= 0 (a patch could have no seeds), more than 512 patches -- the constructor throws as
+// std::runtime_error with the library's text; ego_vel is unused, as in the reference (PWP:761, 784).
 #pragma once
 #include <chrono>
 #include <stdexcept>

@@ -37,7 +37,10 @@ typedef struct {
 typedef struct gorio_ground gorio_ground_t;
 
 void gorio_ground_default_params(gorio_ground_params* p);
-/* Up to 512 patches (sum over zones of sectors x rings); min_range < max_range; num_iter in [1, 8]; num_min_pts >= 1. */
+/* Up to 512 patches (sum over zones of sectors x rings); min_range < max_range; num_iter in [1, 8]; num_min_pts >= 1.
+ * num_lpr >= 1 and th_seeds > 0: then every fitted patch has at least one seed.  With num_lpr = 0 the reference's LPR height is 0
+ * (PWP:646) and a patch above th_seeds has no seeds; its first plane fit then reads pc_mean_ / cov_ of the previous patch, which
+ * the per-patch kernels do not carry, so such parameters are refused (GORIO_ERR_INVALID). */
 int gorio_ground_create(gorio_ground_t** out, int device, const gorio_ground_params* p);
 void gorio_ground_destroy(gorio_ground_t* h);
 

@@ -244,6 +244,10 @@ class Patchworkpp:
         p.update(overrides)
         if p["enable_RVPF"]:
             raise ValueError("RVPF is not restated (off in the reference and every caller)")
+        if p["num_lpr"] < 1 or not p["th_seeds"] > 0:
+            # PWP:646-653: lpr_height is 0 with num_lpr = 0, so a patch above th_seeds has no seeds, and the reference's first fit of
+            # that patch reads pc_mean_ / cov_ of the previous patch.  patch_chain starts every patch from zeros, as the kernels do.
+            raise ValueError("num_lpr must be >= 1 and th_seeds > 0: a patch without seeds would inherit another patch's moments, which is not restated")
         self.p = p
         self.sensor_height = p["sensor_height"]
         self.elevation_thr = list(map(float, p["elevation_thr"]))

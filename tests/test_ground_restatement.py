@@ -140,6 +140,31 @@ def test_rvpf_refused_by_restatement():
         pr.Patchworkpp(enable_RVPF=True)
 
 
+def test_parameters_that_allow_an_empty_seed_set_are_refused():
+    for bad in (dict(num_lpr=0), dict(num_lpr=-1), dict(th_seeds=0.0), dict(th_seeds=-0.5), dict(th_seeds=float("nan"))):
+        with pytest.raises(ValueError, match="seeds"):
+            pr.Patchworkpp(**bad)
+    pr.Patchworkpp(num_lpr=1, th_seeds=1e-3)
+    # why: with num_lpr = 0 the LPR height is 0 (PWP:646), and a patch lifted above th_seeds has no seeds.  The reference would fit it
+    # with the previous patch's pc_mean_ / cov_; patch_chain (and the kernels) start every patch from zeros.
+    ref = pr.Patchworkpp()
+    ref.p["num_lpr"] = 0
+    xyz, _ = gs.scan(9, n_ground=400, extras=False)
+    P = xyz[np.argsort(xyz[:, 2], kind="stable")] + np.array([0, 0, 2.0], np.float32)
+    fits, _, _ = ref.patch_chain(1, P, pr.range_covariance(P), 0)
+    assert fits[0]["m"] == 0 and not fits[0]["mean"].any() and not fits[0]["cov"].any()
+    ref.p["num_lpr"] = 1  # the lowest point is its own LPR and lies below it + th_seeds
+    assert ref.patch_chain(1, P, pr.range_covariance(P), 0)[0][0]["m"] >= 1
+    assert ref.patch_chain(0, P - np.array([0, 0, 9.0], np.float32), pr.range_covariance(P), 0)[0][0]["m"] == len(P)  # all below the zone-0 margin
+
+
+def test_binding_refuses_empty_seed_parameters_before_it_looks_for_a_device(gorio):
+    for bad in (dict(num_lpr=0), dict(th_seeds=0.0), dict(th_seeds=-1.0)):
+        with pytest.raises(gorio.GorioError, match="no seeds") as e:
+            gorio.ground.GroundSegmenter(**bad)
+        assert "gorio error -1" in str(e.value)
+
+
 def test_binding_covers_header(gorio):
     txt = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "gorio_ground.h")).read(), flags=re.S)
     assert sorted(gorio.ground.GROUND_SYMBOLS) == sorted(set(re.findall(r"\b(gorio_[a-z0-9_]+)\s*\(", txt)))
