@@ -36,4 +36,6 @@ from . import scan_context  # noqa: E402
 from .scan_context import SC_SYMBOLS, ScanContext  # noqa: E402
 from . import ndt  # noqa: E402
 from .ndt import NDT_SYMBOLS, Ndt, NdtBatchStats  # noqa: E402
+from . import keyframes  # noqa: E402
+from .keyframes import KF_SYMBOLS, KeyframeStore  # noqa: E402
 from .ugpm import PreintOption, PreintPrior, UgpmBatch, VelPreintegration, ugpm_combine_preints, ugpm_preint_batch, ugpm_stage_times  # noqa: E402

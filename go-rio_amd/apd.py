@@ -261,6 +261,26 @@ class ApdGicp:
         self._n_tgt = cnt.value
         return cnt.value
 
+    def setInputSourceKeyframe(self, store, kid):  # noqa: N802 -- gorio_apd_set_source_from_keyframe: a keyframes.KeyframeStore entry, shared
+        _check(self._h, self._lib.gorio_apd_set_source_from_keyframe(self._h, store.h, int(kid)))
+        self._n_src = store.info(kid)["n"]
+
+    def setInputTargetKeyframe(self, store, kid):  # noqa: N802
+        _check(self._h, self._lib.gorio_apd_set_target_from_keyframe(self._h, store.h, int(kid)))
+        self._n_tgt = store.info(kid)["n"]
+
+    def setInputTargetSubmapKeyframes(self, store, ids, rel_poses, voxel_leaf=0.0):  # noqa: N802
+        """gorio_apd_set_target_submap_keyframes: setInputTargetSubmap from keyframes resident in a keyframes.KeyframeStore."""
+        ids = np.ascontiguousarray(ids, np.int32).reshape(-1)
+        T = np.ascontiguousarray(rel_poses, np.float64).reshape(-1, 16)
+        if T.shape[0] != ids.shape[0]:
+            raise ValueError("one 4x4 pose per keyframe id")
+        cnt = C.c_int(0)
+        _check(self._h, self._lib.gorio_apd_set_target_submap_keyframes(self._h, store.h, _p(ids, C.c_int) if ids.size else None, _p(T, C.c_double) if ids.size else None,
+                                                                          int(ids.shape[0]), C.c_double(voxel_leaf), C.byref(cnt)))
+        self._n_tgt = cnt.value
+        return cnt.value
+
     def getTargetPoints(self):  # noqa: N802
         buf = np.empty((self._n_tgt, 4), np.float32)
         _check(self._h, self._lib.gorio_apd_get_target_points(self._h, _p(buf, C.c_float), _p(buf[:, 3:], C.c_float), self._n_tgt, 16))

@@ -159,6 +159,8 @@ struct gorio_apd {
   DevBuf<int> d_sub_counts;
   DevBuf<SubmapFrame> d_sub_frames;
   DevBuf<unsigned int> d_sub_bb;
+  DevBuf<void> d_sub_kframes;  // gorio_apd_set_target_submap_keyframes (apd_keyframes.hip): frame table, and the finite points per 256-point block
+  DevBuf<int> d_sub_kcnt;
   // sharded-source mode (gorio_apd_comm_init): RCCL communicator over the ranks that share one source cloud
   ncclComm_t comm = nullptr;
   int comm_world = 1, comm_rank = 0;
@@ -1421,6 +1423,8 @@ int gorio_apd_set_target_shared(gorio_apd_t* h, gorio_apd_t* owner) {
   return GORIO_OK;
 }
 
+static int submap_finish(gorio_apd* h, int m, double voxel_leaf, int* n_target);
+
 int gorio_apd_set_target_submap(gorio_apd_t* h, const gorio_apd_keyframe* frames, int count, double voxel_leaf, int* n_target) {
   if (!h || !frames || count <= 0) return GORIO_ERR_INVALID;
   HIP_TRY(h, hipSetDevice(h->device));
@@ -1454,6 +1458,13 @@ int gorio_apd_set_target_submap(gorio_apd_t* h, const gorio_apd_keyframe* frames
   HIP_TRY(h, hipMemcpyAsync(h->d_sub_frames, fr.data(), sizeof(SubmapFrame) * count, hipMemcpyHostToDevice, h->stream));
   submap_transform_kernel<<<dim3((max_frame + 255) / 256, count), 256, 0, h->stream>>>(h->d_sub_in, h->d_sub_frames, h->d_sub_out);
   HIP_TRY(h, hipGetLastError());
+  return submap_finish(h, m, voxel_leaf, n_target);
+}
+
+// The second half of a submap assembly, shared by gorio_apd_set_target_submap and gorio_apd_set_target_submap_keyframes
+// (csrc/apd_keyframes.hip): the m transformed points in d_sub_out (enqueued on the handle's stream) pass through downsample()
+// (SMO:405-415) and become the target.  The stream is drained before a successful return: the callers' pageable tables may die then.
+static int submap_finish(gorio_apd* h, int m, double voxel_leaf, int* n_target) {
   const float4* result = h->d_sub_out;
   int n_out = m;
   if (voxel_leaf > 0.0) {  // pcl::VoxelGrid (SMO:145-149)
@@ -2059,3 +2070,5 @@ extern "C" int gorio_debug_search_stats(unsigned long long out[24], int reset) {
 #include "../../include/gorio_prep.h"
 #include "apd_prep.hip"
 #include "apd_scan.hip"
+#include "../../include/gorio_keyframes.h"
+#include "apd_keyframes.hip"

@@ -338,6 +338,7 @@ struct gorio_sc {
   gorio::DevBuf<void> d_in;
   gorio::DevBuf<gorio::ScHit> d_partial;
   gorio::DevBuf<gorio::ScOut> d_out;
+  gorio::DevBuf<void> d_kfjobs;  // gorio_sc_add_keyframes (apd_keyframes.hip): the pack kernel's job table
 };
 
 namespace {

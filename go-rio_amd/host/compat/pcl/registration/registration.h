@@ -36,6 +36,8 @@ class Registration {
     target_ = cloud;
     target_cloud_updated_ = true;
   }
+  PointCloudSourceConstPtr const getInputSource() { return input_; }  // PCL 1.10 registration.h
+  PointCloudTargetConstPtr const getInputTarget() { return target_; }
   // PCL 1.10 registration.h: a caller-provided tree; with force_no_recompute the tree is NOT rebuilt when the target changes
   void setSearchMethodTarget(const KdTreePtr& tree, bool force_no_recompute = false) {
     tree_ = tree;

@@ -33,6 +33,7 @@
 
 #include <gorio_apd.h>
 #include <gorio_scan.h>
+#include <gorio_keyframes.h>
 
 namespace fast_gicp {
 
@@ -284,6 +285,51 @@ public:
     lazy_tree_->defer(pre.last_scan());
     target_covs_.clear();
     target_covs_fresh_ = false;
+  }
+  // A keyframe resident in a gorio::KeyframeStore (radar_graph_slam/keyframe_store.hpp) as source / target (extra; in place of
+  // setInputSource / setInputTarget(keyframe->cloud) at scan_matching_odometry_nodelet.cpp:588 and loop_detector.cpp:222, 391): the
+  // object shares the keyframe's device cloud -- no upload -- with whatever it already carries.  Covariances, search index and voxel map
+  // that are valid on the device STAY valid: only the host copies are dropped and fetched again when asked for.  The store's host cloud
+  // becomes input_ / target_.  The settings are pushed first: the library compares k_correspondences / regularization with the ones
+  // the keyframe's covariances were estimated with.
+  template <typename Store>
+  void setInputSourceKeyframe(Store& store, int id) {
+    push_params();
+    check(gorio_apd_set_source_from_keyframe(handle_, store.handle(), id));
+    pcl::Registration<PointSource, PointTarget, Scalar>::setInputSource(store.cloud(id));
+    source_covs_.clear();
+    source_covs_fresh_ = false;
+  }
+  template <typename Store>
+  void setInputTargetKeyframe(Store& store, int id) {
+    push_params();
+    check(gorio_apd_set_target_from_keyframe(handle_, store.handle(), id));
+    pcl::Registration<PointSource, PointTarget, Scalar>::setInputTarget(store.cloud(id));
+    lazy_tree_->defer(store.cloud(id));
+    target_covs_.clear();
+    target_covs_fresh_ = false;
+  }
+  // setInputTargetSubmap from keyframes resident in a gorio::KeyframeStore (extra; scan_matching_odometry_nodelet.cpp:602-618): the
+  // same target, bit for bit, assembled on the device without staging or uploading the keyframe clouds again.
+  template <typename Store>
+  PointCloudTargetConstPtr setInputTargetSubmap(Store& store, const std::vector<int>& ids,
+                                                const std::vector<Eigen::Matrix4d, Eigen::aligned_allocator<Eigen::Matrix4d>>& rel_poses, double voxel_leaf = 0.0) {
+    if (ids.empty() || ids.size() != rel_poses.size()) throw std::invalid_argument("setInputTargetSubmap: one relative pose per keyframe id");
+    std::vector<double> poses(ids.size() * 16);
+    for (std::size_t k = 0; k < ids.size(); ++k)
+      for (int r = 0; r < 4; ++r)
+        for (int c = 0; c < 4; ++c) poses[k * 16 + r * 4 + c] = rel_poses[k](r, c);
+    int n = 0;
+    check(gorio_apd_set_target_submap_keyframes(handle_, store.handle(), ids.data(), poses.data(), static_cast<int>(ids.size()), voxel_leaf, &n));
+    PointCloudTargetPtr out(new PointCloudTarget());
+    out->resize(n);
+    if (n > 0) check(gorio_apd_get_target_points(handle_, out->points[0].data, &out->points[0].normal_x, n, static_cast<int>(sizeof(PointTarget))));
+    for (auto& p : out->points) p.data[3] = 1.0f;
+    pcl::Registration<PointSource, PointTarget, Scalar>::setInputTarget(out);  // bookkeeping only: the device already holds it
+    lazy_tree_->defer(out);
+    target_covs_.clear();
+    target_covs_fresh_ = false;
+    return out;
   }
   // extras (not in the reference): correspondences of the last linearisation, device handle
   void getCorrespondences(std::vector<int>& corr, std::vector<float>& sq_dist) {

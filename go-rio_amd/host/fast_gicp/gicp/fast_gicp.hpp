@@ -133,6 +133,31 @@ public:
     backend_->set_final(this->final_transformation_);
     return backend_->getInlierFraction(max_correspondence_dist);
   }
+  // A keyframe resident in a gorio::KeyframeStore as source / target, and the scan-to-submap target from resident keyframes (extras):
+  // FastAPDGICP::setInputSourceKeyframe / setInputTargetKeyframe / setInputTargetSubmap(store, ...) with this class' method selected first
+  // (the library compares a keyframe's voxel map with FastVGICP's voxel settings).
+  template <typename Store>
+  void setInputSourceKeyframe(Store& store, int id) {
+    push_settings();
+    backend_->setInputSourceKeyframe(store, id);
+    pcl::Registration<PointSource, PointTarget, Scalar>::setInputSource(store.cloud(id));
+  }
+  template <typename Store>
+  void setInputTargetKeyframe(Store& store, int id) {
+    push_settings();
+    backend_->setInputTargetKeyframe(store, id);
+    pcl::Registration<PointSource, PointTarget, Scalar>::setInputTarget(store.cloud(id));
+    lazy_tree_->defer(store.cloud(id));
+  }
+  template <typename Store>
+  PointCloudTargetConstPtr setInputTargetSubmap(Store& store, const std::vector<int>& ids,
+                                                const std::vector<Eigen::Matrix4d, Eigen::aligned_allocator<Eigen::Matrix4d>>& rel_poses, double voxel_leaf = 0.0) {
+    push_settings();
+    PointCloudTargetConstPtr out = backend_->setInputTargetSubmap(store, ids, rel_poses, voxel_leaf);
+    pcl::Registration<PointSource, PointTarget, Scalar>::setInputTarget(out);
+    lazy_tree_->defer(out);
+    return out;
+  }
   gorio_apd_t* handle() { return backend_->handle(); }
 
 protected:

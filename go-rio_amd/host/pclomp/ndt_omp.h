@@ -21,6 +21,7 @@
 #include "gorio_apd.h"
 #include "gorio_ndt.h"
 #include "gorio_scan.h"
+#include "gorio_keyframes.h"
 
 namespace pclomp {
 
@@ -110,6 +111,25 @@ class NormalDistributionsTransform : public pcl::Registration<PointSource, Point
     ensure_fitness_handle("setInputTargetFromScan");
     check_apd(gorio_apd_set_target_from_scan(fit_, pre.handle()), "setInputTargetFromScan");
     fit_target_stale_ = false;
+  }
+  // A keyframe resident in a gorio::KeyframeStore (radar_graph_slam/keyframe_store.hpp) as source / target (extra; loop_detector.cpp:222,
+  // 391 with NDT_OMP): one device-to-device copy into the NDT handle instead of an upload; the store's host cloud becomes input_ /
+  // target_.  The private handle of getFitnessScore shares the keyframe where its settings allow it (it estimates no covariances; a
+  // keyframe whose covariances carry another k_correspondences is uploaded from the host copy at the first getFitnessScore instead).
+  template <typename Store>
+  void setInputSourceKeyframe(Store& store, int id) {
+    check(gorio_ndt_set_source_from_keyframe(h_, store.handle(), id), "setInputSourceKeyframe");
+    Base::setInputSource(store.cloud(id));
+    ensure_fitness_handle("setInputSourceKeyframe");
+    fit_source_stale_ = gorio_apd_set_source_from_keyframe(fit_, store.handle(), id) < 0;
+  }
+  template <typename Store>
+  void setInputTargetKeyframe(Store& store, int id) {
+    check(gorio_ndt_set_target_from_keyframe(h_, store.handle(), id), "setInputTargetKeyframe");
+    Base::setInputTarget(store.cloud(id));
+    fit_shared_with_ = nullptr;
+    ensure_fitness_handle("setInputTargetKeyframe");
+    fit_target_stale_ = gorio_apd_set_target_from_keyframe(fit_, store.handle(), id) < 0;
   }
   // Scan-to-submap target assembly on the GPU (extra; the signature and the return value of FastAPDGICP::setInputTargetSubmap, in place of
   // the CPU loop of scan_matching_odometry_nodelet.cpp:602-612): keyframe clouds moved by their relative poses, concatenated, downsampled

@@ -19,6 +19,7 @@
 #include <radar_graph_slam/keyframe.hpp>
 
 #include "gorio_sc.h"
+#include "gorio_keyframes.h"
 
 using Eigen::MatrixXd;
 using SCPointType = pcl::PointXYZINormal;
@@ -141,6 +142,18 @@ class SCManager {
   // User-side API
   void makeAndSaveScancontextAndKeys(pcl::PointCloud<SCPointType>& _scan_down) {  // SC:255-269, the descriptor made on the GPU
     const int idx = add(h_, _scan_down);
+    MatrixXd sc(PC_NUM_RING, PC_NUM_SECTOR), ring(PC_NUM_RING, 1), sector(1, PC_NUM_SECTOR);
+    fetch(h_, idx, &sc, &ring, &sector);
+    polarcontexts_.push_back(sc);
+    polarcontext_invkeys_.push_back(ring);
+    polarcontext_vkeys_.push_back(sector);
+    polarcontext_invkeys_mat_.push_back(eig2stdvec(ring));
+  }
+  // the same for a keyframe resident in a gorio::KeyframeStore (extra; radar_graph_slam_nodelet.cpp:727-731): packed on the device, no upload
+  template <typename Store>
+  void makeAndSaveScancontextAndKeys(Store& store, int id) {
+    int idx = -1;
+    check(gorio_sc_add_keyframes(h_, store.handle(), &id, 1, &idx), "makeAndSaveScancontextAndKeys");
     MatrixXd sc(PC_NUM_RING, PC_NUM_SECTOR), ring(PC_NUM_RING, 1), sector(1, PC_NUM_SECTOR);
     fetch(h_, idx, &sc, &ring, &sector);
     polarcontexts_.push_back(sc);

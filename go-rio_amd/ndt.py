@@ -106,6 +106,13 @@ class Ndt:
         """The current target of a registration object (apd.ApdGicp: what setInputTargetSubmap assembled, say) becomes the target."""
         self._check(self.lib.gorio_ndt_set_target_from_apd(self.h, apd._h))
 
+    def set_source_from_keyframe(self, store, kid):
+        """A keyframes.KeyframeStore entry becomes the source: one device-to-device copy of x, y, z."""
+        self._check(self.lib.gorio_ndt_set_source_from_keyframe(self.h, store.h, int(kid)))
+
+    def set_target_from_keyframe(self, store, kid):
+        self._check(self.lib.gorio_ndt_set_target_from_keyframe(self.h, store.h, int(kid)))
+
     def capacities(self):
         """Elements the device buffers hold: dict of target, source, leaves, keys."""
         c = (C.c_longlong * 4)()

@@ -90,6 +90,14 @@ class ScanContext:
         self._check(self.lib.gorio_sc_add_scans(self.h, k, X, I, N, S, C.byref(first)))
         return first.value
 
+    def add_keyframes(self, store, ids):
+        """makeAndSaveScancontextAndKeys for the listed entries of a keyframes.KeyframeStore, in order, without a host copy; returns the
+        first index."""
+        ids = np.ascontiguousarray(ids, np.int32).reshape(-1)
+        first = C.c_int(-1)
+        self._check(self.lib.gorio_sc_add_keyframes(self.h, store.h, _ptr(ids) if ids.size else None, int(ids.size), C.byref(first)))
+        return first.value
+
     def add_scan(self, xyz, intensity):
         return self.add_scans([(xyz, intensity)])
 
