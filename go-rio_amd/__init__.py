@@ -38,4 +38,6 @@ from . import ndt  # noqa: E402
 from .ndt import NDT_SYMBOLS, Ndt, NdtBatchStats  # noqa: E402
 from . import keyframes  # noqa: E402
 from .keyframes import KF_SYMBOLS, KeyframeStore  # noqa: E402
+from . import map_cloud  # noqa: E402
+from .map_cloud import MAP_SYMBOLS, MapCloud  # noqa: E402
 from .ugpm import PreintOption, PreintPrior, UgpmBatch, VelPreintegration, ugpm_combine_preints, ugpm_preint_batch, ugpm_stage_times  # noqa: E402

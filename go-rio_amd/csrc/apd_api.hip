@@ -2072,3 +2072,5 @@ extern "C" int gorio_debug_search_stats(unsigned long long out[24], int reset) {
 #include "apd_scan.hip"
 #include "../../include/gorio_keyframes.h"
 #include "apd_keyframes.hip"
+#include "../../include/gorio_map.h"
+#include "apd_map.hip"

@@ -1,4 +1,5 @@
 #pragma once
+#include <cstdint>
 #include <memory>
 #include <vector>
 namespace pcl {
@@ -8,6 +9,8 @@ class PointCloud {
   using Ptr = std::shared_ptr<PointCloud<PointT>>;
   using ConstPtr = std::shared_ptr<const PointCloud<PointT>>;
   std::vector<PointT> points;
+  std::uint32_t width = 0, height = 0;  // as in PCL: the members are public and the caller keeps them in step with points
+  bool is_dense = true;
   std::size_t size() const { return points.size(); }
   bool empty() const { return points.empty(); }
   void resize(std::size_t n) { points.resize(n); }
