@@ -179,6 +179,7 @@ struct gorio_apd {
     }
   };
   Pinned pin_ijobs, pin_jobs, pin_desc, pin_states, pin_copy, pin_vox;
+  PinnedBuf pin_looks;  // where the align loop's looks at the pair states land (a download into pageable memory is staged by the runtime)
   std::string err;
   // profiling
   bool profiling = false;
@@ -1061,6 +1062,7 @@ int align_impl(gorio_apd** hs, int count, const float* guesses, float* T_out, do
   const bool fuse_gn = lead->params.optimizer != GORIO_OPT_LEVENBERG_MARQUARDT && lead->fuse_step && !vgicp;
   const dim3 g_vlin((unsigned int)(((size_t)max_n * max_off + 255) / 256), 1, count);
   const int max_it = lead->params.max_iterations;
+  HIP_TRY(lead, lead->pin_looks.reserve(sizeof(PairState) * count, sizeof(PairState) * (count + count / 2)));
   while (launched < max_it) {
     const int todo_it = std::min(chunk_iters, max_it - launched);
     StageChain chain(lead);
@@ -1087,8 +1089,9 @@ int align_impl(gorio_apd** hs, int count, const float* guesses, float* T_out, do
     chunk_iters = launched == todo_it && lead->align_budget > 0 ? 4 : std::min(16, chunk_iters * 2);  // after a budgeted first chunk: 4, 8, 16, ...
     HIP_TRY(lead, hipGetLastError());
     gather_states_kernel<<<count, 64, 0, lead->stream>>>(lead->d_desc, lead->d_states_batch);
-    HIP_TRY(lead, hipMemcpyAsync(states.data(), lead->d_states_batch, sizeof(PairState) * count, hipMemcpyDeviceToHost, lead->stream));
+    HIP_TRY(lead, hipMemcpyAsync(lead->pin_looks, lead->d_states_batch, sizeof(PairState) * count, hipMemcpyDeviceToHost, lead->stream));
     HIP_TRY(lead, hipStreamSynchronize(lead->stream));
+    std::memcpy(states.data(), lead->pin_looks, sizeof(PairState) * count);
     bool all_done = true;
     for (int q = 0; q < count; ++q) all_done = all_done && states[q].done;
     if (all_done) break;

@@ -35,6 +35,7 @@ thread_local std::string g_err;
 thread_local double g_stage_s[8] = {0, 0, 0, 0, 0, 0, 0, 0};
 thread_local int g_stage_n[8] = {0, 0, 0, 0, 0, 0, 0, 0};
 std::atomic<int> g_speculative_rot{1};  // gorio_ugpm_debug_set_schedule
+std::atomic<int> g_debug_path{0};       // gorio_ugpm_debug_set_path
 
 int ufail(int code, const std::string& msg) {
   g_err = msg;
@@ -82,8 +83,9 @@ struct Ctx {  // per-thread, per-device cached streams and buffers; every buffer
   DevBuf<int> d_ints;
   DevBuf<double> d_diag;
   size_t wins_cap = 0;
-  int lm_budget[2] = {0, 0};  // iterations the two fits of the PREVIOUS batch needed: that many are enqueued before the first look at the done flags
+  int lm_budget[2] = {0, 0};  // iterations the two fits of the PREVIOUS batch needed: that many are enqueued, without a look at the done flags (run_fit)
   PinnedBuf pin_in;  // pinned staging of the batch's input arrays (the H2D copy is then a DMA the call does not wait for)
+  PinnedBuf pin_out;  // where the results land: records, diagnostics, control words (a download into pageable memory is staged by the runtime)
   DevBuf<double> lpm_ws;  // opt.type = LPM windows (ugpm_lpm_out.hip)
   DevBuf<int> lpm_ints;
   DevBuf<ug::LpmOutWin> d_lpm_wins;
@@ -105,7 +107,7 @@ struct Ctx {  // per-thread, per-device cached streams and buffers; every buffer
     if (ev_up) hipEventDestroy(ev_up);
     ev_up = nullptr;
     drop_stage_events();
-    ws.reset(); d_wins.reset(); d_ints.reset(); d_diag.reset(); pin_in.reset(); lpm_ws.reset(); lpm_ints.reset(); d_lpm_wins.reset();
+    ws.reset(); d_wins.reset(); d_ints.reset(); d_diag.reset(); pin_in.reset(); pin_out.reset(); lpm_ws.reset(); lpm_ints.reset(); d_lpm_wins.reset();
     wins_cap = 0;
     lm_budget[0] = lm_budget[1] = 0;
     device = -1;
@@ -155,6 +157,10 @@ struct Batch {  // what the steps of one preint_batch_flat call share; the host 
   size_t total_doubles = 0, total_in = 0, total_out = 0;
   double* out_region = nullptr;  // the input region is the start of the workspace, the output region follows it
   int max_S = 0, max_G = 2, max_V = 2, max_infer = 0, n_lpm = 0;
+  bool rerun = false;             // this batch is the unfinished windows of another one
+  bool looks = false;             // every fit looks at the done flags (a re-run, or gorio_ugpm_debug_set_path bit 1)
+  bool enqueued_blind[2] = {false, false};  // fit p got the budgeted iterations and no look: collect() sorts out who finished
+  std::vector<int> final_status;  // per window, once collect() and the re-run are through
   int first_error = 0;
   std::string first_error_msg;
   void note_error(int i, int code, const std::string& m) {
@@ -217,6 +223,8 @@ int reserve_workspace(Ctx& c, const Batch& b) {
   UHIP(c.ws.reserve(b.total_doubles));
   UHIP(reserve_group(c.wins_cap, nw, nw, c.d_wins, nw, c.d_ints, kWinInts * nw, c.d_diag, 4 * nw));
   UHIP(c.pin_in.reserve(sizeof(double) * b.total_in, sizeof(double) * (b.total_in + b.total_in / 4 + 64)));
+  const size_t down = sizeof(double) * (b.total_out + 4 * nw) + sizeof(int) * kWinInts * nw;
+  UHIP(c.pin_out.reserve(down, down + down / 4 + 64));
   return 0;
 }
 
@@ -362,20 +370,21 @@ int open_groups(Ctx& c, Batch& b) {
 void launch_ata(Ctx& c, int max_S, const Run& r, int which, int decide = 0) {
   hipStream_t sq = which == 2 ? r.s2 : r.s;
   Stage st_ata(c, which == 2 ? 6 : 5, sq);
-  const int n = (which == 2 ? 6 : 3) * max_S, T = (n + 15) / 16, ntile = T * (T + 1) / 2;
+  const int n = (which == 2 ? 6 : 3) * max_S;
   const int tpg = which == 2 ? kAtaTilesCorr : kAtaTilesLm;
-  const int ng = (ntile + tpg - 1) / tpg;
+  const int dense = (g_debug_path.load() & 1) ? 1 : 0;
+  const int ng = ata_cut(n, which == 2 && !dense ? 3 * max_S : n, tpg).groups();  // of the largest window: no window has more (both kinds of group grow with S)
   const int npad = ((n + 15) / 32) * 32 + 16;
   const int grid = ((r.nw + 7) / 8) * ng * 8;  // 8 windows (one per XCD) x ng tile groups per slice of the grid
   // LDS as small as the staging needs (53 KB at n = 198): the scan matcher's kernels share the CUs with these workgroups
   auto lds = [&](int kc) { return sizeof(double) * 2 * kc * (npad + 1); };
   if (which == 2) {
-    if (npad <= 256) ug::ata_kernel<4, 16, kAtaTilesCorr><<<grid, 512, lds(16), sq>>>(r.wins, which, r.nw, ng, decide);
-    else if (npad <= 512) ug::ata_kernel<8, 16, kAtaTilesCorr><<<grid, 512, lds(16), sq>>>(r.wins, which, r.nw, ng, decide);
-    else ug::ata_kernel<16, 8, kAtaTilesCorr><<<grid, 512, lds(8), sq>>>(r.wins, which, r.nw, ng, decide);
+    if (npad <= 256) ug::ata_kernel<4, 16, kAtaTilesCorr><<<grid, 512, lds(16), sq>>>(r.wins, which, r.nw, ng, decide, dense);
+    else if (npad <= 512) ug::ata_kernel<8, 16, kAtaTilesCorr><<<grid, 512, lds(16), sq>>>(r.wins, which, r.nw, ng, decide, dense);
+    else ug::ata_kernel<16, 8, kAtaTilesCorr><<<grid, 512, lds(8), sq>>>(r.wins, which, r.nw, ng, decide, dense);
   } else {
-    if (npad <= 256) ug::ata_kernel<4, 16, kAtaTilesLm><<<grid, 512, lds(16), sq>>>(r.wins, which, r.nw, ng, decide);
-    else ug::ata_kernel<8, 16, kAtaTilesLm><<<grid, 512, lds(16), sq>>>(r.wins, which, r.nw, ng, decide);  // n = 3S <= 480
+    if (npad <= 256) ug::ata_kernel<4, 16, kAtaTilesLm><<<grid, 512, lds(16), sq>>>(r.wins, which, r.nw, ng, decide, dense);
+    else ug::ata_kernel<8, 16, kAtaTilesLm><<<grid, 512, lds(16), sq>>>(r.wins, which, r.nw, ng, decide, dense);  // n = 3S <= 480
   }
 }
 
@@ -420,8 +429,7 @@ int run_fit(Ctx& c, Batch& b, int problem) {
   const bool speculative = g_speculative_rot.load() != 0;
   std::vector<std::unique_ptr<Stage>> st_lm;
   for (Run& r : b.runs) {
-    st_lm.emplace_back(new Stage(c, 3, r.s));
-    ug::lm_begin_kernel<<<r.nw, 256, 0, r.s>>>(r.wins, problem);
+    st_lm.emplace_back(new Stage(c, 3, r.s));  // the fit was started by lpm_init_kernel (rotation) / lm_turn_kernel (velocity)
     if (problem == 0) ug::rot_eval_kernel<<<dim3(r.nw, kEvalSplit), 256, 0, r.s>>>(r.wins, 2);
     else ug::vel_eval_kernel<<<dim3(r.nw, kEvalSplit), 256, 0, r.s>>>(r.wins, 2);
     launch_ata(c, max_S, r, problem);
@@ -459,11 +467,18 @@ int run_fit(Ctx& c, Batch& b, int problem) {
       std::fprintf(stderr, "[ugpm lm] problem %d it %d: iter %d done %d term %d succ %d cost %.17g cost_new %.17g radius %.6g mcc %.17g step_norm2 %.6g x_norm %.17g initial %.17g\n", problem, it,
                    li[0], li[1], li[5], li[6], lc[0], lc[1], lc[2], lc[8], lc[11], lc[4], lc[7]);
     }
-    // When to look at the done flags (a look drains the stream: copy, synchronise, ~30 us of idle GPU).  A finished window's kernels
-    // return at once, so iterations enqueued beyond the need cost three empty launches each, far less than a look.  The first batch of a
-    // context looks every other iteration from the fourth on (no window of the C2 shape finishes in fewer than four); later batches
-    // enqueue as many iterations as the previous batch needed before the first look -- on like data that look is the only one.
+    // When to look at the done flags (a look drains the stream: copy, synchronise, ~30 us of idle GPU, and far more while the queue
+    // runs empty behind the scan matcher's launches).  A finished window's kernels return at once, so iterations enqueued beyond the
+    // need cost three empty launches each, far less than a look.  The first batch of a context looks every other iteration from the
+    // fourth on (no window of the C2 shape finishes in fewer than four).  Later batches enqueue as many iterations as the previous
+    // batch needed and go straight on, without a look: the kernel that ends the fit (lm_end_block) marks a window that is not done,
+    // nothing touches it after that, and collect() runs the marked windows again -- with looks, which then start at the budget.
     const int budget = c.lm_budget[problem];
+    if (budget > 0 && !b.looks) {
+      b.enqueued_blind[problem] = true;
+      if (it + 1 >= budget) break;
+      continue;
+    }
     const bool look = budget > 0 ? (it + 1 >= budget && ((it + 1 - budget) & 1) == 0) : (it >= 3 && (it & 1) == 1);
     if (look) {
       for (Run& r : b.runs)
@@ -484,14 +499,17 @@ int run_fit(Ctx& c, Batch& b, int problem) {
           if (f[16] != 0) continue;
           need = std::max(need, f[0] + (f[5] >= 3 ? 1 : 0));
         }
-        c.lm_budget[problem] = std::min(need, it + 1);
+        need = std::min(need, it + 1);
+        c.lm_budget[problem] = b.rerun ? std::max(c.lm_budget[problem], need) : need;  // a re-run is the rest of its batch: the slowest window of both counts
       }
     }
   }
   for (size_t g = 0; g < b.runs.size(); ++g) {
     const Run& r = b.runs[g];
-    if (problem == 0) UHIP(hipStreamWaitEvent(r.s, r.ev_jac, 0));  // corr_jac_kernel has read the initial states
-    ug::lm_end_kernel<<<r.nw, 256, 0, r.s>>>(r.wins, problem, c.d_diag + 4 * (size_t)r.g0);
+    if (problem == 0) {  // the rotation fit ends and the velocity fit starts in one launch; the velocity fit ends inside finish_kernel
+      UHIP(hipStreamWaitEvent(r.s, r.ev_jac, 0));  // corr_jac_kernel has read the initial states
+      ug::lm_turn_kernel<<<r.nw, 256, 0, r.s>>>(r.wins, c.d_diag + 4 * (size_t)r.g0);
+    }
     st_lm[g].reset();  // stage stop event behind the group's last launch of this problem
   }
   return 0;
@@ -502,7 +520,7 @@ int enqueue_finish_and_infer(Ctx& c, Batch& b) {
     UHIP(hipStreamWaitEvent(r.s, r.ev_corr, 0));  // join of the correlation chain (preint.h:1062-1065)
     {
       Stage st(c, 4, r.s);
-      ug::finish_kernel<<<r.nw, 256, 0, r.s>>>(r.wins);
+      ug::finish_kernel<<<r.nw, 256, 0, r.s>>>(r.wins, c.d_diag + 4 * (size_t)r.g0);
       ug::infer_kernel<<<dim3(std::max(1, b.max_infer), r.nw), 256, sizeof(double) * 17 * (6 * b.max_S + 16), r.s>>>(r.wins);
     }
     UHIP(hipEventRecord(r.ev_done, r.s));
@@ -512,14 +530,16 @@ int enqueue_finish_and_infer(Ctx& c, Batch& b) {
   return 0;
 }
 
-// ---- results: the downloads, the stage times, and per window its status, its diagnostics and NaN records where it failed
-int collect(Ctx& c, Batch& b, gorio_ugpm_meas* out, gorio_ugpm_diag* diag) {
-  std::vector<int> fin(kWinInts * (size_t)b.nw);
-  std::vector<double> dg(4 * (size_t)b.nw);
-  UHIP(hipMemcpyAsync(fin.data(), c.d_ints, sizeof(int) * fin.size(), hipMemcpyDeviceToHost, c.main.s));
-  UHIP(hipMemcpyAsync(dg.data(), c.d_diag, sizeof(double) * dg.size(), hipMemcpyDeviceToHost, c.main.s));
-  if (b.total_out) UHIP(hipMemcpyAsync(reinterpret_cast<double*>(out), b.out_region, sizeof(double) * b.total_out, hipMemcpyDeviceToHost, c.main.s));
+// ---- results: the downloads, the stage times, and per window its status and diagnostics; returns the windows whose fits were not done
+int collect(Ctx& c, Batch& b, gorio_ugpm_meas* out, gorio_ugpm_diag* diag, std::vector<int>& unfinished) {
+  double* const rec = static_cast<double*>(c.pin_out.get());  // [total_out] records, [4 nw] diagnostics, then the control words
+  double* const dg = rec + b.total_out;
+  int* const fin = reinterpret_cast<int*>(dg + 4 * (size_t)b.nw);
+  UHIP(hipMemcpyAsync(fin, c.d_ints, sizeof(int) * kWinInts * (size_t)b.nw, hipMemcpyDeviceToHost, c.main.s));
+  UHIP(hipMemcpyAsync(dg, c.d_diag, sizeof(double) * 4 * (size_t)b.nw, hipMemcpyDeviceToHost, c.main.s));
+  if (b.total_out) UHIP(hipMemcpyAsync(rec, b.out_region, sizeof(double) * b.total_out, hipMemcpyDeviceToHost, c.main.s));
   UHIP(hipStreamSynchronize(c.main.s));
+  if (b.total_out) std::memcpy(out, rec, sizeof(double) * b.total_out);
   for (const Ctx::StageEvents& e : c.ev) {
     float ms = 0.f;
     if (hipEventSynchronize(e.b) == hipSuccess && hipEventElapsedTime(&ms, e.a, e.b) == hipSuccess) {
@@ -528,16 +548,19 @@ int collect(Ctx& c, Batch& b, gorio_ugpm_meas* out, gorio_ugpm_diag* diag) {
     }
   }
   c.drop_stage_events();
+  if (b.enqueued_blind[0] || b.enqueued_blind[1]) {
+    // the budget of the next batch: what the slowest window of this one needed.  A fit that looked has set it already (run_fit);
+    // the re-run of the unfinished windows raises it to what they need.
+    FitOutcome o = fit_outcome(fin, b.hw);
+    for (int p = 0; p < 2; ++p)
+      if (b.enqueued_blind[p] && o.need[p] > 0) c.lm_budget[p] = o.need[p];
+    unfinished.swap(o.rerun);
+  }
+  b.final_status.assign(b.nw, 0);
   for (int i = 0; i < b.nw; ++i) {
     const HostWin& h = b.hw[i];
     const int st = h.status != 0 ? h.status : fin[kWinInts * (size_t)i + (h.is_lpm ? 17 : 16)];
-    // rejected on the host: its records were never written; the LPM kernels stop mid-way on a data-domain error: no partial records
-    if (h.status != 0 || (h.is_lpm && st != 0)) {
-      double* o = reinterpret_cast<double*>(out) + b.out_offs[i];
-      std::fill(o, o + (size_t)std::max(0, b.windows[i].n_infer) * 83, std::numeric_limits<double>::quiet_NaN());
-    }
-    if (st != 0 && h.status == 0)
-      b.note_error(i, st, st == GORIO_UGPM_ERR_NUMERIC ? "Cholesky factorisation met a non-positive pivot" : "LPM Partial: the start_time is not in the data domain");
+    b.final_status[i] = st;
     if (diag) {
       gorio_ugpm_diag& d = diag[i];
       d.nb_state = h.S; d.nb_gyr = h.G; d.nb_vel = h.V;
@@ -547,6 +570,89 @@ int collect(Ctx& c, Batch& b, gorio_ugpm_meas* out, gorio_ugpm_diag* diag) {
     }
   }
   return 0;
+}
+
+int preint_batch_flat(const gorio_ugpm_window* windows, int n_windows, gorio_ugpm_meas* out, gorio_ugpm_diag* diag, int device, bool rerun);
+
+// The windows a fit left unfinished (it had the budget of the previous batch and no look), as a batch of their own that looks: a
+// window's result does not depend on the batch it is in.  Their records, diagnostics and statuses replace the placeholders.
+int rerun_unfinished(Batch& b, const std::vector<int>& unfinished, gorio_ugpm_meas* out, gorio_ugpm_diag* diag, int device) {
+  std::vector<gorio_ugpm_window> sub;
+  size_t n_out = 0;
+  for (int i : unfinished) {
+    sub.push_back(b.windows[i]);
+    n_out += (size_t)b.windows[i].n_infer;
+  }
+  std::vector<gorio_ugpm_meas> sub_out(n_out);
+  std::vector<gorio_ugpm_diag> sub_diag(sub.size());
+  const int rc = preint_batch_flat(sub.data(), (int)sub.size(), sub_out.data(), sub_diag.data(), device, true);
+  bool per_window = false;  // as in gorio_ugpm_preint_batch: a per-window failure is reported through the diagnostics, anything else fails the call
+  for (const gorio_ugpm_diag& d : sub_diag) per_window = per_window || d.status != 0;
+  if (rc != 0 && !per_window) return rc;
+  size_t at = 0;
+  for (size_t k = 0; k < unfinished.size(); ++k) {
+    const int i = unfinished[k];
+    const size_t cnt = (size_t)b.windows[i].n_infer;
+    std::memcpy(reinterpret_cast<double*>(out) + b.out_offs[i], sub_out.data() + at, sizeof(gorio_ugpm_meas) * cnt);
+    at += cnt;
+    b.final_status[i] = sub_diag[k].status;
+    if (diag) diag[i] = sub_diag[k];
+  }
+  return 0;
+}
+
+// per window: NaN records where it failed, and the first failure as the error of the call
+void report(Batch& b, gorio_ugpm_meas* out) {
+  for (int i = 0; i < b.nw; ++i) {
+    const HostWin& h = b.hw[i];
+    const int st = b.final_status[i];
+    // rejected on the host: its records were never written; the LPM kernels stop mid-way on a data-domain error: no partial records
+    if (h.status != 0 || (h.is_lpm && st != 0)) {
+      double* o = reinterpret_cast<double*>(out) + b.out_offs[i];
+      std::fill(o, o + (size_t)std::max(0, b.windows[i].n_infer) * 83, std::numeric_limits<double>::quiet_NaN());
+    }
+    if (st != 0 && h.status == 0)
+      b.note_error(i, st, st == GORIO_UGPM_ERR_NUMERIC ? "Cholesky factorisation met a non-positive pivot" : "LPM Partial: the start_time is not in the data domain");
+  }
+}
+
+// every window non-chunked (quantum < 0): the device path
+int preint_batch_flat(const gorio_ugpm_window* windows, int n_windows, gorio_ugpm_meas* out, gorio_ugpm_diag* diag, int device, bool rerun) {
+  if (!windows || n_windows <= 0 || !out) return ufail(GORIO_UGPM_ERR_INVALID, "gorio_ugpm_preint_batch: bad arguments");
+  Ctx& c = g_ctx;
+  if (int rc = ensure_context(c, device)) return rc;
+  if (!rerun)
+    for (int i = 0; i < 8; ++i) { g_stage_s[i] = 0; g_stage_n[i] = 0; }  // a re-run adds to the stage times of its batch
+  std::vector<int> unfinished;
+  Batch b{windows, n_windows};
+  b.rerun = rerun;
+  b.looks = rerun || (g_debug_path.load() & 2) != 0;
+  {
+    StageEventsGuard guard{c};
+    auto tnow = [] { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
+    const double tt0 = tnow();
+    plan_windows(b);
+    if (int rc = reserve_workspace(c, b)) return rc;
+    if (int rc = stage_and_upload(c, b)) return rc;
+    const double tt1 = tnow();
+    if (int rc = run_lpm_windows(c, b)) return rc;
+    if (b.max_S > 0) {
+      b.flags.resize(kWinInts * (size_t)b.nw);
+      if (int rc = open_groups(c, b)) return rc;
+      if (int rc = enqueue_tables_and_correlation(c, b)) return rc;
+      for (int problem = 0; problem < 2; ++problem)
+        if (int rc = run_fit(c, b, problem)) return rc;
+      if (int rc = enqueue_finish_and_infer(c, b)) return rc;
+    }
+    const double tt3 = tnow();
+    if (int rc = collect(c, b, out, diag, unfinished)) return rc;
+    if (std::getenv("GORIO_UGPM_TRACE")) std::fprintf(stderr, "[ugpm trace] prep %.3f ms, kernels+polls %.3f ms, results %.3f ms, unfinished %d\n", (tt1 - tt0) * 1e3, (tt3 - tt1) * 1e3, (tnow() - tt3) * 1e3, (int)unfinished.size());
+  }
+  if (!unfinished.empty())  // the device buffers of the context are free again: every download above is complete
+    if (int rc = rerun_unfinished(b, unfinished, out, diag, device)) return rc;
+  report(b, out);
+  if (b.first_error) return ufail(b.first_error, b.first_error_msg);
+  return GORIO_UGPM_OK;
 }
 
 }  // namespace
@@ -570,6 +676,8 @@ const char* gorio_ugpm_last_error(void) { return g_err.c_str(); }
 
 void gorio_ugpm_debug_set_schedule(int speculative_rot) { g_speculative_rot.store(speculative_rot ? 1 : 0); }
 
+void gorio_ugpm_debug_set_path(int flags) { g_debug_path.store(flags); }
+
 int gorio_ugpm_get_stage_times(double seconds[8], int counts[8]) {
   for (int i = 0; i < 8; ++i) {
     if (seconds) seconds[i] = g_stage_s[i];
@@ -578,43 +686,13 @@ int gorio_ugpm_get_stage_times(double seconds[8], int counts[8]) {
   return 0;
 }
 
-// every window non-chunked (quantum < 0): the device path
-static int preint_batch_flat(const gorio_ugpm_window* windows, int n_windows, gorio_ugpm_meas* out, gorio_ugpm_diag* diag, int device) {
-  if (!windows || n_windows <= 0 || !out) return ufail(GORIO_UGPM_ERR_INVALID, "gorio_ugpm_preint_batch: bad arguments");
-  Ctx& c = g_ctx;
-  if (int rc = ensure_context(c, device)) return rc;
-  for (int i = 0; i < 8; ++i) { g_stage_s[i] = 0; g_stage_n[i] = 0; }
-  StageEventsGuard guard{c};
-  auto tnow = [] { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
-  const double tt0 = tnow();
-  Batch b{windows, n_windows};
-  plan_windows(b);
-  if (int rc = reserve_workspace(c, b)) return rc;
-  if (int rc = stage_and_upload(c, b)) return rc;
-  const double tt1 = tnow();
-  if (int rc = run_lpm_windows(c, b)) return rc;
-  if (b.max_S > 0) {
-    b.flags.resize(kWinInts * (size_t)b.nw);
-    if (int rc = open_groups(c, b)) return rc;
-    if (int rc = enqueue_tables_and_correlation(c, b)) return rc;
-    for (int problem = 0; problem < 2; ++problem)
-      if (int rc = run_fit(c, b, problem)) return rc;
-    if (int rc = enqueue_finish_and_infer(c, b)) return rc;
-  }
-  const double tt3 = tnow();
-  if (int rc = collect(c, b, out, diag)) return rc;
-  if (std::getenv("GORIO_UGPM_TRACE")) std::fprintf(stderr, "[ugpm trace] prep %.3f ms, kernels+polls %.3f ms, results %.3f ms\n", (tt1 - tt0) * 1e3, (tt3 - tt1) * 1e3, (tnow() - tt3) * 1e3);
-  if (b.first_error) return ufail(b.first_error, b.first_error_msg);
-  return GORIO_UGPM_OK;
-}
-
 // Requests with opt.quantum >= 0 (preint.h:1584-1702) are cut into chunk windows (ugpm_chunks.h); the chunk windows of ALL such
 // requests join the other windows of the call in one device batch, and their records are chained on the host afterwards.
 int gorio_ugpm_preint_batch(const gorio_ugpm_window* windows, int n_windows, gorio_ugpm_meas* out, gorio_ugpm_diag* diag, int device) {
   if (!windows || n_windows <= 0 || !out) return ufail(GORIO_UGPM_ERR_INVALID, "gorio_ugpm_preint_batch: bad arguments");
   bool any_chunked = false;
   for (int i = 0; i < n_windows; ++i) any_chunked = any_chunked || windows[i].quantum >= 0;
-  if (!any_chunked) return preint_batch_flat(windows, n_windows, out, diag, device);
+  if (!any_chunked) return preint_batch_flat(windows, n_windows, out, diag, device, false);
   struct Req { int first = 0, count = 0, status = 0; chunks::Plan plan; size_t out0 = 0; };  // first/count: its windows in the expanded batch
   std::vector<Req> reqs(n_windows);
   std::vector<gorio_ugpm_window> flat;
@@ -674,7 +752,7 @@ int gorio_ugpm_preint_batch(const gorio_ugpm_window* windows, int n_windows, gor
   std::vector<gorio_ugpm_diag> flat_diag(std::max<size_t>(1, flat.size()));
   int rc = 0;
   if (!flat.empty()) {
-    rc = preint_batch_flat(flat.data(), (int)flat.size(), flat_out.data(), flat_diag.data(), device);
+    rc = preint_batch_flat(flat.data(), (int)flat.size(), flat_out.data(), flat_diag.data(), device, false);
     bool per_window = false;  // a per-window failure leaves the other windows valid and is reported through the diagnostics; anything else fails the call
     for (const gorio_ugpm_diag& d : flat_diag) per_window = per_window || d.status != 0;
     if (rc != 0 && !per_window) return rc;

@@ -9,8 +9,40 @@
 namespace gorio {
 
 constexpr int kAtaTilesLm = 24, kAtaTilesCorr = 48;  // 16 x 16 output tiles per workgroup (8 waves x 4 / 6 accumulators)
-constexpr int kWinInts = 48;        // ints per window: lmi[16], status at 16
+constexpr int kWinInts = 48;        // ints per window: lmi[16], status at 16 (17: of an LPM window), kLmiNeed + problem: iterations fit `problem` needed
+constexpr int kLmiNeed = 18;
+constexpr int kStatusUnfinished = 2;  // internal, never reported: a fit had fewer iterations enqueued than the window needs; the host runs it again
 constexpr int kVelBlocks = 3;       // problem #2's normal matrix is block diagonal (one block per velocity channel): lm_step_kernel runs one workgroup per block
+
+#if defined(__HIPCC__)
+#define GORIO_HD __host__ __device__
+#else
+#define GORIO_HD
+#endif
+
+// How ata_kernel cuts the lower-triangular 16 x 16 tiling of an n x n J^T J (tiles numbered row by row, q = tr (tr + 1) / 2 + tc) into
+// workgroups of at most `tpg` tiles.  When the first rows of J are zero from column `zero_col` on (the gyro rows of the correlation
+// Jacobian: zero_col = 3S), every tile whose rows start at or behind zero_col gets nothing from them; those are the tiles from q_zero
+// on.  No group straddles q_zero: groups [0, ng_dense) share the tiles before it and stream every row of J, groups
+// [ng_dense, ng_dense + ng_skip) share the rest and start behind the zero rows.  zero_col = n: one kind of group, the plain cut.
+struct AtaCut {
+  int ntile, q_zero, ng_dense, ng_skip;
+  GORIO_HD int groups() const { return ng_dense + ng_skip; }
+  GORIO_HD bool skips(int grp) const { return grp >= ng_dense; }
+  GORIO_HD int q_lo(int grp) const {
+    return grp < ng_dense ? (int)((long)grp * q_zero / ng_dense) : q_zero + (int)((long)(grp - ng_dense) * (ntile - q_zero) / ng_skip);
+  }
+  GORIO_HD int q_hi(int grp) const { return grp + 1 == groups() ? ntile : q_lo(grp + 1); }
+};
+GORIO_HD inline AtaCut ata_cut(int n, int zero_col, int tpg) {
+  const int T = (n + 15) / 16, tz = zero_col >= n ? T : (zero_col + 15) / 16;
+  AtaCut c;
+  c.ntile = T * (T + 1) / 2;
+  c.q_zero = tz * (tz + 1) / 2;
+  c.ng_dense = (c.q_zero + tpg - 1) / tpg;
+  c.ng_skip = (c.ntile - c.q_zero + tpg - 1) / tpg;
+  return c;
+}
 
 struct UgpmWin {
   // ---- inputs

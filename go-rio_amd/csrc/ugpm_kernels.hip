@@ -633,8 +633,11 @@ __global__ __launch_bounds__(320) void lpm_rot_kernel(const UgpmWin* __restrict_
   (void)lane;
 }
 
+__device__ void lm_begin_block(const UgpmWin& w, int problem);  // Levenberg-Marquardt section below
+
 // LPM initialisation, part 2 (after all five integrations): GP state seeds, their finite-difference Jacobians, hyper-parameters.
-// grid: (windows), block 320.
+// Then the rotation fit is started on the seeds (lm_begin_block: the Gram and cross-kernel launches between this one and the fit's
+// first evaluation touch neither x nor the control block).  grid: (windows), block 320.
 __global__ __launch_bounds__(320) void lpm_init_kernel(const UgpmWin* __restrict__ wins) {
   const UgpmWin w = load_win(wins, blockIdx.x);
   if (*w.status != 0) return;
@@ -677,6 +680,8 @@ __global__ __launch_bounds__(320) void lpm_init_kernel(const UgpmWin* __restrict
     w.hyper[c * 4 + 3] = m;
     for (int i = 0; i < S; ++i) s[i] -= m;
   }
+  __syncthreads();  // s_dr is final
+  lm_begin_block(w, 0);
 }
 
 // =============================================================================================== block-wide dense helpers
@@ -1745,7 +1750,8 @@ __global__ __launch_bounds__(256) void corr_jac_kernel(const UgpmWin* __restrict
         const double* k1 = w.KsKinv + ((size_t)c * G + i) * S;
         for (int j = lane; j < S; j += 64) row[c * S + j] = f0 * k0[j] + f1 * k1[j];
       }
-      for (int j = lane; j < 3 * S; j += 64) row[3 * S + j] = 0.0;  // a rotation residual does not see the velocity channels
+      // a rotation residual does not see the velocity channels: columns 3S.. of these rows are zero, and ata_kernel, the only
+      // reader of J, takes them as zero without reading them -- they are not stored
     }
   }
   __syncthreads();
@@ -1817,7 +1823,7 @@ __device__ __forceinline__ int ata_npad(int n) { return ((n + 15) / 32) * 32 + 1
 // CMAX = 64-column groups of a staged row (npad <= 64 CMAX), KC = rows per staged chunk, TPG = output tiles per workgroup (8 waves x
 // TPG / 8 accumulators): 32 for the LM problems (n = 3S: more, shorter workgroups), 48 for the correlation (n = 6S).
 template <int CMAX, int KC, int TPG>
-__global__ __launch_bounds__(512) void ata_kernel(const UgpmWin* __restrict__ wins, int which, int n_windows, int groups_max, int decide) {
+__global__ __launch_bounds__(512) void ata_kernel(const UgpmWin* __restrict__ wins, int which, int n_windows, int groups_max, int decide, int dense) {
   // Consecutive workgroups of a launch go round-robin to the 8 XCDs, each with an L2 of its own: ALL tile groups of a window are given
   // workgroup numbers of one residue mod 8, 8 apart, so they start together on ONE XCD and stream the window's J through that L2 side
   // by side (one fetch from HBM / MALL serves the groups) instead of once per XCD.
@@ -1826,7 +1832,12 @@ __global__ __launch_bounds__(512) void ata_kernel(const UgpmWin* __restrict__ wi
 #ifdef GORIO_ATA_NO_XCD
   const int win = (slot * 8 + xcd) / groups_max, grp = (slot * 8 + xcd) % groups_max;
 #else
-  const int win = (slot / groups_max) * 8 + xcd, grp = slot % groups_max;
+  // Where the groups differ in length (the correlation with its zero blocks, see the cut below) the long ones of ALL windows get the
+  // lowest workgroup numbers: 448 workgroups at one per CU on 256 CUs, so the order decides the tail (measured with the groups of a
+  // window side by side instead: 0.61 ms per C4 launch, long groups first 0.47 ms).  A window's groups stay on one XCD either way.
+  const bool long_first = which == 2 && !dense;
+  const int nrow = (n_windows + 7) / 8;
+  const int win = (long_first ? slot % nrow : slot / groups_max) * 8 + xcd, grp = long_first ? slot / nrow : slot % groups_max;
 #endif
   if (win >= n_windows) return;
   const UgpmWin w = load_win(wins, win);
@@ -1836,9 +1847,11 @@ __global__ __launch_bounds__(512) void ata_kernel(const UgpmWin* __restrict__ wi
   double* C;
   const double* r = nullptr;
   double* g = nullptr;
+  int zrows = 0, zcol = 0;  // rows [0, zrows) of A are zero from column zcol on, and that part of them is never read (nor written)
   if (which == 2) {
     if (!w.correlate) return;
     m = 3 * w.G + 3 * w.V; n = 6 * w.S; A = w.Jc; C = w.Ac;
+    zrows = 3 * w.G; zcol = 3 * w.S;  // a rotation residual does not see the velocity channels (corr_jac_kernel)
   } else {
     if (w.lmi[1]) return;
     n = 3 * w.S;
@@ -1858,13 +1871,16 @@ __global__ __launch_bounds__(512) void ata_kernel(const UgpmWin* __restrict__ wi
       return;
     }
   }
-  const int T = (n + 15) / 16, ntile = T * (T + 1) / 2;
-  const int ng = (ntile + TPG - 1) / TPG;
+  // A group whose tiles all start at or behind zcol gets exactly zero from the rows before zrows (+-0 products added to a +0
+  // accumulator: no bit of the result depends on them), so it starts at the chunk that holds row zrows; the chunks themselves,
+  // and with them the order of every sum, are those of a group that streams all rows.  dense: the plain cut, every chunk (A/B runs).
+  const AtaCut cut = ata_cut(n, zrows > 0 && !dense ? zcol : n, TPG);
+  const int ng = cut.groups();
   if (grp >= ng) return;
-  const int q_lo = (int)((long)grp * ntile / ng), q_hi = (int)((long)(grp + 1) * ntile / ng);
+  const int q_lo = cut.q_lo(grp), q_hi = cut.q_hi(grp);
   const int npad = ata_npad(n);
   const int nck = (m + KC - 1) / KC;
-  const int c_lo = 0, c_hi = nck;
+  const int c_lo = cut.skips(grp) ? zrows / KC : 0, c_hi = nck;
   extern __shared__ double ata_lds[];  // [2][KC][npad] staged rows of A, then [2][KC] staged entries of r
   double* rl = ata_lds + (size_t)2 * KC * npad;
   const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -1904,10 +1920,11 @@ __global__ __launch_bounds__(512) void ata_kernel(const UgpmWin* __restrict__ wi
 #pragma unroll
     for (int rr = 0; rr < RMAX; ++rr) {
       const int k = ck * KC + wave + 8 * rr;
+      const int ncol = k < zrows ? zcol : n;
 #pragma unroll
       for (int cc = 0; cc < CMAX; ++cc) {
         const int col = lane + 64 * cc;
-        pre[rr][cc] = (k < m && col < n) ? A[(size_t)k * n + col] : 0.0;
+        pre[rr][cc] = (k < m && col < ncol) ? A[(size_t)k * n + col] : 0.0;
       }
     }
     if (r != nullptr && tid < KC) rpre = (ck * KC + tid < m) ? r[ck * KC + tid] : 0.0;
@@ -2025,10 +2042,9 @@ __global__ __launch_bounds__(256) void lm_relinearize_linear_kernel(const UgpmWi
 // lmc: 0 cost, 1 cost_new, 2 radius, 3 decrease_factor, 4 x_norm, 5 model_cost_change, 6 step_norm, 7 initial cost
 // lmi: 0 iter, 1 done, 2 reuse_diag, 3 need_J, 4 step_valid, 5 termination, 6 successful, 7 problem, 8 first
 
-// start a problem: load x, reset the control block.  grid: (windows), block 256.
-__global__ __launch_bounds__(256) void lm_begin_kernel(const UgpmWin* __restrict__ wins, int problem) {
-  const UgpmWin w = load_win(wins, blockIdx.x);
-  if (*w.status != 0) return;
+// start a problem: load x, reset the control block.  One workgroup per window (any block size); there is no launch of its own for
+// it: the rotation fit starts in the tail of lpm_init_kernel, the velocity fit in lm_turn_kernel.
+__device__ void lm_begin_block(const UgpmWin& w, int problem) {
   const int n = 3 * w.S;
   const double* src = problem == 0 ? w.s_dr : w.s_vel;
   for (int j = threadIdx.x; j < n; j += blockDim.x) w.lmv[5 * (size_t)n + j] = src[j];
@@ -2171,17 +2187,37 @@ __global__ __launch_bounds__(512) void lm_step_kernel(const UgpmWin* __restrict_
 }
 
 
-// write the solution back into the state.  grid: (windows), block 256.
-__global__ __launch_bounds__(256) void lm_end_kernel(const UgpmWin* __restrict__ wins, int problem, double* __restrict__ diag_out /* [windows][4] */) {
-  const UgpmWin w = load_win(wins, blockIdx.x);
-  if (*w.status != 0) return;
+// end a problem: write the solution back into the state, its iteration count and cost into diag_out[4] of the window, and into
+// lmi[kLmiNeed + problem] the iterations the fit needed (its step count, plus the step kernel that noticed a termination of its own:
+// gradient, iteration cap, radius).  One workgroup per window (any block size).  Returns false, and leaves everything else as it is,
+// for a window whose fit is NOT done: the host enqueued fewer iterations than this window needs (it enqueues what the previous batch
+// needed, without looking at the done flags).  Such a window is marked kStatusUnfinished -- every later kernel returns at once for a
+// window whose status is set -- and the host runs it again (ugpm_api.hip collect).  Uniform per workgroup.
+__device__ bool lm_end_block(const UgpmWin& w, int problem, double* __restrict__ diag_out) {
+  if (!w.lmi[1]) {
+    __syncthreads();  // every thread has read the flags before one of them changes the status word
+    if (threadIdx.x == 0) *w.status = kStatusUnfinished;
+    return false;
+  }
   const int n = 3 * w.S;
   double* dst = problem == 0 ? w.s_dr : w.s_vel;
   for (int j = threadIdx.x; j < n; j += blockDim.x) dst[j] = w.lmv[5 * (size_t)n + j];
   if (threadIdx.x == 0) {
-    diag_out[blockIdx.x * 4 + problem * 2 + 0] = (double)w.lmi[0];
-    diag_out[blockIdx.x * 4 + problem * 2 + 1] = w.lmc[0];
+    diag_out[problem * 2 + 0] = (double)w.lmi[0];
+    diag_out[problem * 2 + 1] = w.lmc[0];
+    w.lmi[kLmiNeed + problem] = w.lmi[0] + (w.lmi[5] >= 3 ? 1 : 0);
   }
+  return true;
+}
+
+// Between the two fits: end the rotation fit, start the velocity fit (thread j copies x[j] out before it loads the new x[j]; the
+// control block is reset behind a barrier).  grid: (windows), block 256.
+__global__ __launch_bounds__(256) void lm_turn_kernel(const UgpmWin* __restrict__ wins, double* __restrict__ diag_out /* [windows][4] */) {
+  const UgpmWin w = load_win(wins, blockIdx.x);
+  if (*w.status != 0) return;
+  if (!lm_end_block(w, 0, diag_out + 4 * (size_t)blockIdx.x)) return;
+  __syncthreads();  // every thread has read the done flag, and thread 0 the iteration count and cost, before thread 0 resets them
+  lm_begin_block(w, 1);
 }
 
 // =============================================================================================== state correlation
@@ -2228,10 +2264,13 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
 
 // =============================================================================================== inference tables + get(t)
 
-// preint.h:978-1060 and finishStateDiff (preint.h:1401-1441).  grid: (windows), block 256.
-__global__ __launch_bounds__(256) void finish_kernel(const UgpmWin* __restrict__ wins) {
+// The end of the velocity fit (lm_end_block), then preint.h:978-1060 and finishStateDiff (preint.h:1401-1441).
+// grid: (windows), block 256.
+__global__ __launch_bounds__(256) void finish_kernel(const UgpmWin* __restrict__ wins, double* __restrict__ diag_out /* [windows][4] */) {
   const UgpmWin w = load_win(wins, blockIdx.x);
   if (*w.status != 0) return;
+  if (!lm_end_block(w, 1, diag_out + 4 * (size_t)blockIdx.x)) return;
+  __syncthreads();  // s_vel is final
   const int S = w.S;
   for (int q = threadIdx.x; q < 6 * S; q += blockDim.x) {  // alpha = K^-1 s
     const int c = q / S, i = q % S;

@@ -143,6 +143,27 @@ void copy_noise_and_priors(const gorio_ugpm_window& w, Win& u) {
   u.vel_bias_std = w.vel_bias_std; u.gyr_bias_std = w.gyr_bias_std;
 }
 
+// ---- the fits of a batch that was enqueued without a look at the done flags (ugpm_api.hip run_fit): each fit got as many iterations
+// as the previous batch needed.  `ints` are the control words of the batch as they come back with the results, kWinInts per window:
+// the status word [16] is kStatusUnfinished where a fit was not done after those iterations (the kernels left that window alone from
+// there on), and [kLmiNeed + p] is the number of iterations fit p needed where it was done.
+struct FitOutcome {
+  std::vector<int> rerun;  // windows to run again, with looks, in the order of the batch
+  int need[2] = {0, 0};    // most iterations a finished window needed per fit; 0: no UGPM window finished that fit
+};
+
+inline FitOutcome fit_outcome(const int* ints, const std::vector<HostWin>& hw) {
+  FitOutcome o;
+  for (size_t i = 0; i < hw.size(); ++i) {
+    if (hw[i].status != 0 || hw[i].is_lpm) continue;  // refused on the host, or not a UGPM window: no fit ran
+    const int* f = ints + kWinInts * i;
+    if (f[16] == kStatusUnfinished) o.rerun.push_back((int)i);
+    if (f[16] != 0) continue;  // unfinished, or failed on the device
+    for (int p = 0; p < 2; ++p) o.need[p] = std::max(o.need[p], f[kLmiNeed + p]);
+  }
+  return o;
+}
+
 // ---- opt.type = LPM (preint.h:1567-1580): host bookkeeping of one IterativeIntegrator = the merged, sorted time line
 // (SortIndexTracker2, types.h:332-458) and the filler stamps of preint.h:228-237.  No numerics.
 struct LpmHost {

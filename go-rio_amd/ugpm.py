@@ -14,7 +14,7 @@ LPM, UGPM = 0, 1
 REC = 83
 
 UGPM_SYMBOLS = ["gorio_ugpm_default_window", "gorio_ugpm_preint_batch", "gorio_ugpm_last_error", "gorio_ugpm_get_stage_times", "gorio_ugpm_debug_set_schedule",
-                "gorio_ugpm_combine_preints"]
+                "gorio_ugpm_debug_set_path",                 "gorio_ugpm_combine_preints"]
 
 
 class UgpmWindow(C.Structure):
@@ -151,6 +151,15 @@ def ugpm_debug_set_schedule(speculative_rot=True):
     lib.gorio_ugpm_debug_set_schedule.argtypes = [C.c_int]
     lib.gorio_ugpm_debug_set_schedule.restype = None
     lib.gorio_ugpm_debug_set_schedule(1 if speculative_rot else 0)
+
+
+def ugpm_debug_set_path(dense_ata=False, draining_looks=False):
+    """gorio_ugpm_debug_set_path (test hook, process-wide): the correlation J^T J over every row in every workgroup, and the fits with a
+    look at the done flags (a stream drain) even when the iteration budget is known.  Both default to off; the results are the same bits."""
+    lib = load_library()
+    lib.gorio_ugpm_debug_set_path.argtypes = [C.c_int]
+    lib.gorio_ugpm_debug_set_path.restype = None
+    lib.gorio_ugpm_debug_set_path((1 if dense_ata else 0) | (2 if draining_looks else 0))
 
 
 def ugpm_stage_times():

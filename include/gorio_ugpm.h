@@ -126,6 +126,11 @@ int gorio_ugpm_get_stage_times(double seconds[8], int counts[8]);
  * schedules take the same steps; tests compare them.  Default 1. */
 void gorio_ugpm_debug_set_schedule(int speculative_rot);
 
+/* Test hook, process-wide, for A/B runs of the same library: bit 0 of `flags` selects the dense J^T J of the state correlation (the
+ * plain cut of the output tiles, every workgroup streams every row of the Jacobian) instead of the one that starts the workgroups
+ * whose tiles get nothing from the gyro rows behind those rows.  The two compute the same bits; tests compare them.  Default 0. */
+void gorio_ugpm_debug_set_path(int flags);
+
 #ifdef __cplusplus
 }
 #endif

@@ -4,6 +4,8 @@ import importlib, time
 import numpy as np
 gorio = importlib.import_module("go-rio_amd")
 n = int(sys.argv[1]) if len(sys.argv) > 1 else 64
+if len(sys.argv) > 2:  # A/B inside one library: "dense" (correlation J^T J over every row), "looks" (draining looks at the done flags), "dense,looks"
+    importlib.import_module("go-rio_amd.ugpm").ugpm_debug_set_path(dense_ata="dense" in sys.argv[2], draining_looks="looks" in sys.argv[2])
 wins = [gorio.synth.imu_window(seed=100 + q) for q in range(n)]
 gorio.ugpm_preint_batch(wins)
 t = time.perf_counter(); gorio.ugpm_preint_batch(wins); dt = time.perf_counter() - t
