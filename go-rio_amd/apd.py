@@ -53,10 +53,12 @@ APD_SYMBOLS = [
     "gorio_apd_get_mahalanobis", "gorio_apd_transform_source", "gorio_apd_fitness_score", "gorio_apd_fitness_score_batch", "gorio_apd_set_profiling",
     "gorio_apd_get_stage_times", "gorio_apd_set_target_shared", "gorio_comm_get_unique_id", "gorio_apd_comm_init", "gorio_apd_comm_destroy", "gorio_apd_comm_info", "gorio_apd_debug_set_shard", "gorio_apd_debug_set_schedule", "gorio_apd_debug_get_index", "gorio_apd_set_target_submap", "gorio_apd_get_target_points",
     "gorio_apd_set_method", "gorio_apd_get_method", "gorio_apd_get_voxelmap", "gorio_apd_get_voxel_correspondences",
+    "gorio_apd_set_gicp_omp_params", "gorio_apd_get_gicp_omp_params", "gorio_apd_gicp_omp_update", "gorio_apd_gicp_omp_evaluate", "gorio_apd_gicp_omp_diag",
 ]
 
 # gorio_method / gorio_voxel_search / gorio_voxel_mode of gorio_apd.h (the latter two in the order of gicp_settings.hpp)
-METHOD_APDGICP, METHOD_GICP, METHOD_VGICP = 0, 1, 2
+METHOD_APDGICP, METHOD_GICP, METHOD_VGICP, METHOD_GICP_OMP = 0, 1, 2, 3
+GICP_OMP_F, GICP_OMP_DF, GICP_OMP_FDF = 0, 1, 2  # modes of gorio_apd_gicp_omp_evaluate
 VOXEL_DIRECT27, VOXEL_DIRECT7, VOXEL_DIRECT1, VOXEL_DIRECT_RADIUS = 0, 1, 2, 3
 VOXEL_ADDITIVE, VOXEL_ADDITIVE_WEIGHTED, VOXEL_MULTIPLICATIVE = 0, 1, 2
 VOXEL_OFFSETS = {VOXEL_DIRECT27: 27, VOXEL_DIRECT7: 7, VOXEL_DIRECT1: 1}
@@ -127,6 +129,36 @@ class ApdGicp:
         m, s, a, r = C.c_int(0), C.c_int(0), C.c_int(0), C.c_double(0.0)
         _check(self._h, self._lib.gorio_apd_get_method(self._h, C.byref(m), C.byref(r), C.byref(s), C.byref(a)))
         return dict(method=m.value, voxel_resolution=r.value, voxel_search=s.value, voxel_mode=a.value)
+
+    # ---- GICP_OMP (METHOD_GICP_OMP): gicp_epsilon_ / setMaximumOptimizerIterations (gicp_omp.h:117-121, 255-260) and the three parity hooks
+    def setGicpOmpParams(self, gicp_epsilon=0.001, max_optimizer_iterations=20):  # noqa: N802
+        _check(self._h, self._lib.gorio_apd_set_gicp_omp_params(self._h, C.c_double(gicp_epsilon), int(max_optimizer_iterations)))
+
+    def getGicpOmpParams(self):  # noqa: N802
+        e, m = C.c_double(0.0), C.c_int(0)
+        _check(self._h, self._lib.gorio_apd_get_gicp_omp_params(self._h, C.byref(e), C.byref(m)))
+        return e.value, m.value
+
+    def setMaximumOptimizerIterations(self, n):  # noqa: N802
+        self.setGicpOmpParams(self.getGicpOmpParams()[0], int(n))
+
+    def gicpOmpUpdate(self, transformation, guess=None):  # noqa: N802 -- one pass of gicp_omp_impl.hpp:411-476; returns the number of pairs
+        t = np.ascontiguousarray(transformation, np.float32)
+        g = np.ascontiguousarray(np.eye(4) if guess is None else guess, np.float32)
+        m = C.c_int(0)
+        _check(self._h, self._lib.gorio_apd_gicp_omp_update(self._h, _p(t, C.c_float), _p(g, C.c_float), C.byref(m)))
+        return m.value
+
+    def gicpOmpEvaluate(self, x, mode=GICP_OMP_FDF):  # noqa: N802 -- the functor at x over the pairs held: (f or None, g or None)
+        x = np.ascontiguousarray(x, np.float64)
+        f, g = C.c_double(0.0), np.zeros(6, np.float64)
+        _check(self._h, self._lib.gorio_apd_gicp_omp_evaluate(self._h, _p(x, C.c_double), int(mode), C.byref(f), _p(g, C.c_double)))
+        return (None if mode == GICP_OMP_DF else f.value), (None if mode == GICP_OMP_F else g)
+
+    def gicpOmpDiag(self):  # noqa: N802
+        o, i, e, s = C.c_int(0), C.c_int(0), C.c_int(0), C.c_int(0)
+        _check(self._h, self._lib.gorio_apd_gicp_omp_diag(self._h, C.byref(o), C.byref(i), C.byref(e), C.byref(s)))
+        return dict(outer=o.value, inner_total=i.value, evaluations=e.value, last_status=s.value)
 
     def getVoxelMap(self):  # noqa: N802 -- parity hook: voxelmap_ (fast_vgicp.hpp:85), voxels in ascending (x, y, z) coordinate order
         nv = C.c_int(0)

@@ -66,6 +66,7 @@ struct DevCloud {
   bool present = false;
   int cov_count = 0;       // == source_covs_.size(): n when valid, 0 when stale
   int cov_k = -1, cov_reg = -1;  // k_correspondences / regularization the covariances were ESTIMATED with; -1: supplied by set_*_covariances
+  double cov_eps = 0.0;    // gicp_epsilon of covariances estimated by the GICP_OMP rule (cov_reg == kRegGicpOmp), 0 otherwise
   // exact search accelerator (GORIO_SEARCH_PRUNED)
   DevBuf<float> idx_sx, idx_sy, idx_sz, idx_tbox, idx_sbox, idx_bbox;  // the arrays behind index_view(): one group of capacity idx_cap
   DevBuf<int> idx_orig;
@@ -96,7 +97,7 @@ struct DevCloud {
   void covs_dropped() { cov_count = 0; vm_valid = false; knn_valid = false; }
   void points_replaced() { present = true; idx_valid = false; covs_dropped(); }
   void cleared() { present = false; n = 0; idx_valid = false; covs_dropped(); }
-  void covs_estimated(int k, int reg, bool keep_knn) { cov_count = n; cov_k = k; cov_reg = reg; vm_valid = false; knn_valid = keep_knn; }
+  void covs_estimated(int k, int reg, bool keep_knn, double eps = 0.0) { cov_count = n; cov_k = k; cov_reg = reg; cov_eps = eps; vm_valid = false; knn_valid = keep_knn; }
   void covs_supplied() { covs_estimated(-1, -1, false); }  // not from a k-NN search of this library: no lists, no (k, reg) to compare
   void index_built(int chunk) { idx_valid = true; idx_chunk = chunk; }
   void voxelmap_dropped() { vm_valid = false; }
@@ -144,6 +145,20 @@ struct gorio_apd {
   int v_n_off = 0;           // offsets per source point of the slot table held
   DevBuf<VoxPair> d_vox;     // batch array (owned by the handle that leads a batch)
   bool omega_valid = false;  // omega6 holds the Mahalanobis matrices of the last linearisation (not after a Gauss-Newton align)
+  // GICP_OMP (GORIO_METHOD_GICP_OMP, apd_gicp_omp.hip): gicp_epsilon_ / max_inner_iterations_ (GOH:117-121), the `output` cloud of GO:402 in
+  // original order (x, y, z) and in the source's search-index order, mahalanobis_ as 9 floats per source point, the functor's partials
+  double gomp_eps = 0.001;
+  int gomp_max_inner = 20;
+  DevBuf<float> gomp_out, gomp_maha;  // these five: one group of capacity gomp_cap (source points)
+  DevBuf<float4> gomp_s4;
+  DevBuf<double> gomp_part;
+  DevBuf<int> gomp_cnt;
+  int gomp_cap = 0;
+  DevBuf<double> gomp_res;            // [16] sums of the last functor evaluation
+  DevBuf<unsigned int> gomp_arrive;   // ticket counter of gomp_functor_kernel
+  float gomp_guess[16] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1};  // guess of the `output` cloud held
+  int gomp_pairs = -1;                // pairs of the last update (-1: none held)
+  int gomp_outer = 0, gomp_inner = 0, gomp_evals = 0, gomp_status = -1;  // gorio_apd_gicp_omp_diag
   DevBuf<PairState> d_state;
   DevBuf<PairDesc> d_desc;   // batch descriptor array and states (owned by the handle that leads a batch): one group of capacity desc_cap
   DevBuf<PairState> d_states_batch;
@@ -221,6 +236,16 @@ struct HandleFail {  // fail() bound to a handle, for GORIO_HIP_CHECK
 #define HIP_TRY(h, expr) GORIO_HIP_CHECK(HandleFail{h}, expr)
 
 int roundup(int v, int m) { return (v + m - 1) / m * m; }
+
+// GICP_OMP (apd_gicp_omp.hip, included at the end of this file)
+constexpr int kRegGicpOmp = 100;  // DevCloud::cov_reg of covariances estimated by the rule of GO:50-122: one more "regularization" for sharing
+int gomp_align(gorio_apd* h, const float* guess, float* T_out, double* H_out, int* converged, int* nr_iterations, int* n_linearize);
+int gomp_covariances(gorio_apd* lead, std::vector<std::pair<gorio_apd*, DevCloud*>>& todo);
+// the rule a handle estimates covariances by, and whether covariances estimated with (k, reg, eps) are the ones it would estimate
+int cov_rule(const gorio_apd* h) { return h->method == GORIO_METHOD_GICP_OMP ? kRegGicpOmp : h->params.regularization; }
+bool cov_rule_differs(const gorio_apd* h, const DevCloud& c) {
+  return c.cov_count == c.n && c.cov_k >= 0 && (c.cov_k != h->params.k_correspondences || c.cov_reg != cov_rule(h) || (c.cov_reg == kRegGicpOmp && c.cov_eps != h->gomp_eps));
+}
 
 // Upload `bytes` of a short-lived host array through the handle's pinned staging buffer `b`: no stream drain, the caller's array may die
 // right away.  A buffer that still feeds an earlier upload is waited for first (its event), never overwritten under it.
@@ -577,7 +602,7 @@ int run_covariances(gorio_apd* lead, std::vector<std::pair<gorio_apd*, DevCloud*
     if (s > max_splits) max_splits = s;
     const size_t need = pruned ? 0 : (size_t)s * K * c.n;
     HIP_TRY(h, reserve_group(c.part_cap, need, need, c.part_d, need, c.part_i, need));
-    const bool keep = h->params.keep_knn_indices != 0;
+    const bool keep = h->params.keep_knn_indices != 0 || lead->method == GORIO_METHOD_GICP_OMP;  // GICP_OMP estimates from the lists
     if (keep && (c.knn_k != k || !c.knn)) {
       c.knn_k = 0;
       HIP_TRY(h, c.knn.realloc((size_t)c.cap * k));
@@ -638,6 +663,11 @@ int run_covariances(gorio_apd* lead, std::vector<std::pair<gorio_apd*, DevCloud*
     }
   }
   HIP_TRY(lead, hipGetLastError());
+  if (lead->method == GORIO_METHOD_GICP_OMP) {
+    if (int rc = gomp_covariances(lead, todo)) return rc;
+    for (auto& t : todo) t.second->covs_estimated(k, kRegGicpOmp, true, lead->gomp_eps);
+    return GORIO_OK;
+  }
   for (auto& t : todo) t.second->covs_estimated(k, lead->params.regularization, t.first->params.keep_knn_indices != 0);
   return GORIO_OK;
 }
@@ -696,13 +726,13 @@ void launch_nn(gorio_apd* lead, const PairDesc* d_desc, dim3 g_nn, int max_src_s
 // they were estimated with would silently register with another object's covariances (the reference estimates them per object, APD:149-154)
 bool shared_cov_mismatch(const gorio_apd* h) {
   const DevCloud& t = *h->tgt;
-  return h->tgt.use_count() > 1 && t.cov_count == t.n && t.cov_k >= 0 && (t.cov_k != h->params.k_correspondences || t.cov_reg != h->params.regularization);
+  return h->tgt.use_count() > 1 && cov_rule_differs(h, t);
 }
 
 // the same for a source that other handles hold too (a scan output handed over by gorio_apd_set_source_from_scan, include/gorio_scan.h)
 bool shared_source_cov_mismatch(const gorio_apd* h) {
   const DevCloud& s = *h->src;
-  return h->src.use_count() > 1 && s.cov_count == s.n && s.cov_k >= 0 && (s.cov_k != h->params.k_correspondences || s.cov_reg != h->params.regularization);
+  return h->src.use_count() > 1 && cov_rule_differs(h, s);
 }
 
 // ---- FastVGICP plumbing
@@ -913,6 +943,8 @@ int align_impl(gorio_apd** hs, int count, const float* guesses, float* T_out, do
   HIP_TRY(lead, hipSetDevice(lead->device));
   for (int q = 0; q < count; ++q)
     if (hs[q] && hs[q]->comm && count != 1) return fail(lead, GORIO_ERR_INVALID, "a handle with a communicator (sharded source) cannot be part of a batch");
+  for (int q = 0; q < count; ++q)
+    if (hs[q] && hs[q]->method == GORIO_METHOD_GICP_OMP) return fail(lead, GORIO_ERR_UNSUPPORTED, "align_batch: GICP_OMP handles align one at a time (gorio_apd_align); a batched BFGS is not built");
   std::unordered_set<gorio_apd*> distinct;
   for (int q = 0; q < count; ++q) {
     gorio_apd* h = hs[q];
@@ -1240,12 +1272,21 @@ int gorio_apd_get_params(const gorio_apd_t* h, gorio_apd_params* p) {
 
 int gorio_apd_set_method(gorio_apd_t* h, int method, double voxel_resolution, int voxel_search, int voxel_mode) {
   if (!h) return GORIO_ERR_INVALID;
-  if (method != GORIO_METHOD_APDGICP && method != GORIO_METHOD_GICP && method != GORIO_METHOD_VGICP) return fail(h, GORIO_ERR_UNSUPPORTED, "set_method: unknown registration method");
+  if (method != GORIO_METHOD_APDGICP && method != GORIO_METHOD_GICP && method != GORIO_METHOD_VGICP && method != GORIO_METHOD_GICP_OMP) return fail(h, GORIO_ERR_UNSUPPORTED, "set_method: unknown registration method");
+  if (method == GORIO_METHOD_GICP_OMP) {  // the voxel arguments are ignored in this mode: the handle keeps the ones it has
+    if (h->comm) return fail(h, GORIO_ERR_STATE, "set_method: GICP_OMP has no sharded-source mode (the handle has a communicator)");
+    h->method = method;
+    h->corr_valid = false;
+    h->omega_valid = false;
+    h->gomp_pairs = -1;
+    return GORIO_OK;
+  }
   if (voxel_search == GORIO_VOXEL_DIRECT_RADIUS) return fail(h, GORIO_ERR_UNSUPPORTED, "set_method: DIRECT_RADIUS is not supported (the reference aborts there, VOX:13-15)");
   if (voxel_search != GORIO_VOXEL_DIRECT27 && voxel_search != GORIO_VOXEL_DIRECT7 && voxel_search != GORIO_VOXEL_DIRECT1) return fail(h, GORIO_ERR_UNSUPPORTED, "set_method: unknown neighbour search method");
   if (voxel_mode != GORIO_VOXEL_ADDITIVE && voxel_mode != GORIO_VOXEL_ADDITIVE_WEIGHTED && voxel_mode != GORIO_VOXEL_MULTIPLICATIVE) return fail(h, GORIO_ERR_UNSUPPORTED, "set_method: unknown voxel accumulation mode");
   if (!(voxel_resolution > 0.0) || !std::isfinite(voxel_resolution)) return fail(h, GORIO_ERR_UNSUPPORTED, "set_method: voxel_resolution must be positive");
   if (method == GORIO_METHOD_VGICP && h->comm) return fail(h, GORIO_ERR_STATE, "set_method: FastVGICP has no sharded-source mode (the handle has a communicator)");
+  h->gomp_pairs = -1;
   h->method = method;
   h->voxel_resolution = voxel_resolution;
   h->voxel_search = voxel_search;
@@ -1413,7 +1454,7 @@ int gorio_apd_set_target_shared(gorio_apd_t* h, gorio_apd_t* owner) {
   if (!owner->tgt->present) return fail(h, GORIO_ERR_STATE, "set_target_shared: the owner has no input target");
   {
     const DevCloud& t = *owner->tgt;
-    if (t.cov_count == t.n && t.cov_k >= 0 && (t.cov_k != h->params.k_correspondences || t.cov_reg != h->params.regularization))
+    if (cov_rule_differs(h, t))
       return fail(h, GORIO_ERR_INVALID, "set_target_shared: the owner's covariances were estimated with another k_correspondences / regularization than this handle's");
   }
   {
@@ -1641,6 +1682,7 @@ int gorio_apd_get_knn_indices(gorio_apd_t* h, int which, int* idx, int n_times_k
 
 int gorio_apd_align(gorio_apd_t* h, const float guess[16], float T_out[16], double* H_out, int* converged, int* nr_iterations, int* n_linearize) {
   if (!h) return GORIO_ERR_INVALID;
+  if (h->method == GORIO_METHOD_GICP_OMP) return gomp_align(h, guess, T_out, H_out, converged, nr_iterations, n_linearize);
   gorio_apd* hs[1] = {h};
   return align_impl(hs, 1, guess, T_out, H_out, converged, nr_iterations, n_linearize);
 }
@@ -1651,6 +1693,7 @@ int gorio_apd_align_batch(gorio_apd_t** handles, int count, const float* guesses
 
 int gorio_apd_linearize(gorio_apd_t* h, const double T[16], double* H, double* b, double* error) {
   if (!h || !T) return GORIO_ERR_INVALID;
+  if (h->method == GORIO_METHOD_GICP_OMP) return fail(h, GORIO_ERR_UNSUPPORTED, "linearize: GICP_OMP has no Gauss-Newton linearisation (gorio_apd_gicp_omp_update / _evaluate)");
   HIP_TRY(h, hipSetDevice(h->device));
   int rc = check_ready(h);
   if (rc) return rc;
@@ -1708,6 +1751,7 @@ int gorio_apd_linearize(gorio_apd_t* h, const double T[16], double* H, double* b
 
 int gorio_apd_compute_error(gorio_apd_t* h, const double T[16], double* error) {
   if (!h || !T || !error) return GORIO_ERR_INVALID;
+  if (h->method == GORIO_METHOD_GICP_OMP) return fail(h, GORIO_ERR_UNSUPPORTED, "compute_error: GICP_OMP evaluates its functor through gorio_apd_gicp_omp_evaluate");
   HIP_TRY(h, hipSetDevice(h->device));
   if (!h->corr_valid || !h->omega_valid) return fail(h, GORIO_ERR_STATE, "compute_error needs the correspondences and Mahalanobis matrices of a previous linearize (or LM align)");
   int rc = single_desc(h, true);
@@ -1751,6 +1795,22 @@ int gorio_apd_get_mahalanobis(gorio_apd_t* h, double* maha, int n) {
   if (!h->corr_valid || !h->omega_valid) return fail(h, GORIO_ERR_STATE, "no Mahalanobis matrices held (a Gauss-Newton align does not materialise them: call gorio_apd_linearize)");
   if (n != h->src->n) return fail(h, GORIO_ERR_INVALID, "get_mahalanobis: size mismatch");
   HIP_TRY(h, hipSetDevice(h->device));
+  if (h->method == GORIO_METHOD_GICP_OMP) {  // mahalanobis_ (GOH:304): the stored floats widened, zero for unpaired points
+    if (h->gomp_pairs < 0 || h->gomp_cap < n) return fail(h, GORIO_ERR_STATE, "no Mahalanobis matrices held");
+    std::vector<float> m9((size_t)n * 9);
+    std::vector<int> cr(n);
+    HIP_TRY(h, hipMemcpyAsync(m9.data(), h->gomp_maha, sizeof(float) * 9 * n, hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(h, hipMemcpyAsync(cr.data(), h->corr, sizeof(int) * n, hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    for (int i = 0; i < n; ++i) {
+      double* o = maha + (size_t)i * 16;
+      for (int q = 0; q < 16; ++q) o[q] = 0.0;
+      if (cr[i] < 0) continue;
+      for (int r = 0; r < 3; ++r)
+        for (int c = 0; c < 3; ++c) o[r * 4 + c] = (double)m9[(size_t)i * 9 + r * 3 + c];
+    }
+    return GORIO_OK;
+  }
   std::vector<double> o6((size_t)n * 6);
   HIP_TRY(h, hipMemcpyAsync(o6.data(), h->omega6, sizeof(double) * 6 * n, hipMemcpyDeviceToHost, h->stream));
   HIP_TRY(h, hipStreamSynchronize(h->stream));
@@ -2077,3 +2137,4 @@ extern "C" int gorio_debug_search_stats(unsigned long long out[24], int reset) {
 #include "apd_keyframes.hip"
 #include "../../include/gorio_map.h"
 #include "apd_map.hip"
+#include "apd_gicp_omp.hip"

@@ -1,0 +1,530 @@
+// apd_gicp_omp.hip -- GICP_OMP (pclomp::GeneralizedIterativeClosestPoint, REG:91-100) as method GORIO_METHOD_GICP_OMP of the registration
+// handle.  Included at the end of apd_api.hip: upload, search index, k-NN lists, 1-NN search, fitness score and hand-offs are the handle's.
+//   GOH = ndt_omp/include/pclomp/gicp_omp.h, GO = ndt_omp/include/pclomp/gicp_omp_impl.hpp
+//
+//   gomp_cov_kernel       covariances from the k-NN lists: float products summed in double, SVD rebuild with (1, 1, gicp_epsilon)   GO:82-120
+//   gomp_output_kernel    output = guess * p in float, once per align, in original and in search-index order                        GO:402
+//   gomp_update_kernel    gate, R C1 R^T + C2, cofactor inverse, float Mahalanobis matrix, pairs per block                         GO:441-460
+//   gomp_functor_kernel   <0> operator() float path, <1> df, <2> fdf: one launch each, wave -> block -> block order in fp64        GO:249-371
+// The 1-NN search is nn_search_kernel / nn_search_pruned_kernel run on a descriptor whose source view is the `output` copy: the kernels read
+// coordinates and nothing else of a source, so the index built for the stored source serves unchanged.
+// The BFGS shell (gicp_bfgs.h) and the outer loop of GO:409-516 run on the host, one device evaluation per round trip.
+#include "gicp_bfgs.h"
+
+namespace gorio {
+
+struct GompR {
+  double r[9];   // 3x3 of the double product transformation_ * guess (GO:417-423), row-major
+  double thr2;   // corr_dist_threshold_^2 (GO:401)
+};
+
+__global__ __launch_bounds__(256) void gomp_cov_kernel(CloudView c, const int* __restrict__ knn, int k, double eps) {
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i >= c.n) return;
+  double m0 = 0.0, m1 = 0.0, m2 = 0.0, c00 = 0.0, c10 = 0.0, c11 = 0.0, c20 = 0.0, c21 = 0.0, c22 = 0.0;
+  for (int t = 0; t < k; ++t) {
+    int j = knn[(size_t)i * k + t];
+    j = j < 0 ? 0 : (j >= c.n ? c.n - 1 : j);  // the lists hold indices of this cloud
+    const float4 p = c.p4[j];
+    m0 += (double)p.x; m1 += (double)p.y; m2 += (double)p.z;
+    c00 += (double)(p.x * p.x);  // GO:89-96: float products, double sums
+    c10 += (double)(p.y * p.x);
+    c11 += (double)(p.y * p.y);
+    c20 += (double)(p.z * p.x);
+    c21 += (double)(p.z * p.y);
+    c22 += (double)(p.z * p.z);
+  }
+  const double kd = (double)k;
+  m0 /= kd; m1 /= kd; m2 /= kd;
+  c00 = c00 / kd - m0 * m0;
+  c10 = c10 / kd - m1 * m0;
+  c11 = c11 / kd - m1 * m1;
+  c20 = c20 / kd - m2 * m0;
+  c21 = c21 / kd - m2 * m1;
+  c22 = c22 / kd - m2 * m2;
+  // JacobiSVD of a symmetric matrix: U = eigenvectors ordered by |eigenvalue| descending (the sign of a column cancels in u u^T)
+  Eig3 e = sym3_eigen(c00, c10, c20, c11, c21, c22);
+  if (fabs(e.w0) < fabs(e.w1)) swap_cols(e.w0, e.w1, e.v00, e.v10, e.v20, e.v01, e.v11, e.v21);
+  if (fabs(e.w1) < fabs(e.w2)) swap_cols(e.w1, e.w2, e.v01, e.v11, e.v21, e.v02, e.v12, e.v22);
+  if (fabs(e.w0) < fabs(e.w1)) swap_cols(e.w0, e.w1, e.v00, e.v10, e.v20, e.v01, e.v11, e.v21);
+  double* o = c.cov6 + (size_t)i * 6;
+  o[0] = (e.v00 * e.v00 + e.v01 * e.v01) + eps * e.v02 * e.v02;
+  o[1] = (e.v00 * e.v10 + e.v01 * e.v11) + eps * e.v02 * e.v12;
+  o[2] = (e.v00 * e.v20 + e.v01 * e.v21) + eps * e.v02 * e.v22;
+  o[3] = (e.v10 * e.v10 + e.v11 * e.v11) + eps * e.v12 * e.v12;
+  o[4] = (e.v10 * e.v20 + e.v11 * e.v21) + eps * e.v12 * e.v22;
+  o[5] = (e.v20 * e.v20 + e.v21 * e.v21) + eps * e.v22 * e.v22;
+  c.geo_w[i] = eps;  // sigma_3 / sigma_1 of the rebuilt matrix (read by no GICP_OMP code)
+}
+
+// s4_in / s4_out: the source's search-index copy (x, y, z, original index bits) by sorted position, or null (exhaustive search)
+__global__ __launch_bounds__(256) void gomp_output_kernel(const float* __restrict__ x, const float* __restrict__ y, const float* __restrict__ z, int n, TfArg g, float* __restrict__ ox,
+                                                          float* __restrict__ oy, float* __restrict__ oz, const float4* __restrict__ s4_in, float4* __restrict__ s4_out, int n_spad) {
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i < n) {
+    float a, b, c;
+    transform_f(g.m, x[i], y[i], z[i], a, b, c);
+    ox[i] = a; oy[i] = b; oz[i] = c;
+  }
+  if (s4_in && i < n_spad) {
+    float4 v = s4_in[i];
+    if (i < n) {  // positions >= n are padding
+      float a, b, c;
+      transform_f(g.m, v.x, v.y, v.z, a, b, c);
+      v.x = a; v.y = b; v.z = c;
+    }
+    s4_out[i] = v;
+  }
+}
+
+// Consumes (and re-arms) best_key; corr / sqd as linearize_kernel leaves them; maha[i][9] = the float cast of (R C1 R^T + C2)^-1, row-major;
+// cnt[block] = pairs of the block's 256 points.
+__global__ __launch_bounds__(256) void gomp_update_kernel(unsigned long long* __restrict__ best_key, int n, const double* __restrict__ c1, const double* __restrict__ c2, int n_tgt, GompR R,
+                                                          int* __restrict__ corr, float* __restrict__ sqd, float* __restrict__ maha, int* __restrict__ cnt) {
+  __shared__ int s_cnt[4];
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  bool pair = false;
+  if (i < n) {
+    const unsigned long long key = best_key[i];
+    best_key[i] = ~0ull;
+    const float d = __uint_as_float((unsigned int)(key >> 32));
+    int j = (int)(unsigned int)(key & 0xffffffffu);
+    const bool found = key != ~0ull && j >= 0 && j < n_tgt;
+    sqd[i] = found ? d : INFINITY;
+    pair = found && (double)d < R.thr2;  // GO:441
+    corr[i] = pair ? j : -1;
+    if (pair) {
+      const double* a = c1 + (size_t)i * 6;
+      const double* b = c2 + (size_t)j * 6;
+      const double C1[9] = {a[0], a[1], a[2], a[1], a[3], a[4], a[2], a[4], a[5]};
+      double M[9], T[9];
+#pragma unroll
+      for (int r = 0; r < 3; ++r)
+#pragma unroll
+        for (int c = 0; c < 3; ++c) M[r * 3 + c] = (R.r[r * 3] * C1[c] + R.r[r * 3 + 1] * C1[3 + c]) + R.r[r * 3 + 2] * C1[6 + c];  // M = R C1
+#pragma unroll
+      for (int r = 0; r < 3; ++r)
+#pragma unroll
+        for (int c = 0; c < 3; ++c) T[r * 3 + c] = (M[r * 3] * R.r[c * 3] + M[r * 3 + 1] * R.r[c * 3 + 1]) + M[r * 3 + 2] * R.r[c * 3 + 2];  // M R^T
+      T[0] += b[0]; T[1] += b[1]; T[2] += b[2]; T[3] += b[1]; T[4] += b[3]; T[5] += b[4]; T[6] += b[2]; T[7] += b[4]; T[8] += b[5];
+      // cofactor inverse: cof(i, j) = T(i+1, j+1) T(i+2, j+2) - T(i+1, j+2) T(i+2, j+1) (indices mod 3); inv(r, c) = cof(c, r) / det, det along column 0
+      double cof[9];
+#pragma unroll
+      for (int r = 0; r < 3; ++r)
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+          const int r1 = (r + 1) % 3, r2 = (r + 2) % 3, q1 = (c + 1) % 3, q2 = (c + 2) % 3;
+          cof[r * 3 + c] = T[r1 * 3 + q1] * T[r2 * 3 + q2] - T[r1 * 3 + q2] * T[r2 * 3 + q1];
+        }
+      const double det = (cof[0] * T[0] + cof[3] * T[3]) + cof[6] * T[6];
+      const double inv = 1.0 / det;
+      float* o = maha + (size_t)i * 9;
+#pragma unroll
+      for (int r = 0; r < 3; ++r)
+#pragma unroll
+        for (int c = 0; c < 3; ++c) o[r * 3 + c] = (float)(cof[c * 3 + r] * inv);  // GO:456
+    }
+  }
+  const unsigned long long bal = __ballot(pair);
+  if ((threadIdx.x & 63) == 0) s_cnt[threadIdx.x >> 6] = __popcll(bal);
+  __syncthreads();
+  if (threadIdx.x == 0) cnt[blockIdx.x] = (s_cnt[0] + s_cnt[1]) + (s_cnt[2] + s_cnt[3]);
+}
+
+// MODE 0: Sum res . (M res) over the pairs on the float path of operator() (GO:269-275), 1 value.
+// MODE 1: df (GO:305-320): Sum temp (3) and Sum p_src3 temp^T (9) on the double path, values [1..12].
+// MODE 2: fdf (GO:352-365): the same plus Sum res . temp in [0].
+// One launch: every workgroup reduces its 256 source points wave -> block (the four waves in a fixed order) and stores one partial; the
+// workgroup that draws the last ticket adds the partials in block order into out[0..12].  arrive is zeroed ahead of the launch.
+template <int MODE>
+__global__ __launch_bounds__(256) void gomp_functor_kernel(const float* __restrict__ ox, const float* __restrict__ oy, const float* __restrict__ oz, int n, const float4* __restrict__ tgt,
+                                                           const int* __restrict__ corr, const float* __restrict__ maha, TfArg tf, double* __restrict__ partials,
+                                                           unsigned int* __restrict__ arrive, double* __restrict__ out) {
+  constexpr int NV = 13;
+  constexpr int V0 = MODE == 1 ? 1 : 0, V1 = MODE == 0 ? 1 : NV;  // the values [V0, V1) this mode produces
+  __shared__ double s_red[4 * NV + 1];
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  double v[NV];
+#pragma unroll
+  for (int q = 0; q < NV; ++q) v[q] = 0.0;
+  const int j = i < n ? corr[i] : -1;
+  if (j >= 0) {
+    const float px = ox[i], py = oy[i], pz = oz[i];
+    const float4 t = tgt[j];
+    const float* m = maha + (size_t)i * 9;
+    float qx, qy, qz;
+    transform_f(tf.m, px, py, pz, qx, qy, qz);
+    if (MODE == 0) {
+      const float r0 = qx - t.x, r1 = qy - t.y, r2 = qz - t.z;
+      const float t0 = (m[0] * r0 + m[1] * r1) + m[2] * r2;
+      const float t1 = (m[3] * r0 + m[4] * r1) + m[5] * r2;
+      const float t2 = (m[6] * r0 + m[7] * r1) + m[8] * r2;
+      const float ret = (r0 * t0 + r1 * t1) + r2 * t2;
+      v[0] = (double)ret;
+    } else {
+      const double r0 = (double)(qx - t.x), r1 = (double)(qy - t.y), r2 = (double)(qz - t.z);  // pp[0] - p_tgt[0]: a float difference
+      const double t0 = ((double)m[0] * r0 + (double)m[1] * r1) + (double)m[2] * r2;
+      const double t1 = ((double)m[3] * r0 + (double)m[4] * r1) + (double)m[5] * r2;
+      const double t2 = ((double)m[6] * r0 + (double)m[7] * r1) + (double)m[8] * r2;
+      if (MODE == 2) v[0] = (r0 * t0 + r1 * t1) + r2 * t2;
+      v[1] = t0; v[2] = t1; v[3] = t2;
+      const double p0 = (double)px, p1 = (double)py, p2 = (double)pz;  // base_transformation_ is the identity (GO:398)
+      v[4] = p0 * t0; v[5] = p0 * t1; v[6] = p0 * t2;
+      v[7] = p1 * t0; v[8] = p1 * t1; v[9] = p1 * t2;
+      v[10] = p2 * t0; v[11] = p2 * t1; v[12] = p2 * t2;
+    }
+  }
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+#pragma unroll
+  for (int q = V0; q < V1; ++q) {
+    const double s = wave_sum(v[q]);
+    if (lane == 0) s_red[wave * NV + q] = s;
+  }
+  __syncthreads();
+  if ((int)threadIdx.x >= V0 && (int)threadIdx.x < V1) {
+    const int q = threadIdx.x;
+    partials[(size_t)blockIdx.x * NV + q] = ((s_red[q] + s_red[NV + q]) + s_red[2 * NV + q]) + s_red[3 * NV + q];
+  }
+  // hand-over to the last workgroup: stores drained, one agent-scope release ahead of the ticket, one acquire behind the last one
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    const unsigned int ticket = __hip_atomic_fetch_add(arrive, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    const bool last = ticket == gridDim.x - 1;
+    if (last) {
+      __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    }
+    s_red[4 * NV] = last ? 1.0 : 0.0;
+  }
+  __syncthreads();
+  if (s_red[4 * NV] == 0.0) return;
+  if ((int)threadIdx.x >= V0 && (int)threadIdx.x < V1) {
+    const int q = threadIdx.x;
+    double s = 0.0;
+    for (unsigned int b = 0; b < gridDim.x; ++b) s += partials[(size_t)b * NV + q];
+    out[q] = s;
+  }
+}
+
+}  // namespace gorio
+
+namespace {
+
+float gomp_round_sin(float a) { return (float)std::sin((double)a); }  // the correctly rounded float results
+float gomp_round_cos(float a) { return (float)std::cos((double)a); }
+
+// row-major 3x3 float product, every sum left to right
+void gomp_mul3f(const float* a, const float* b, float* c) {
+  for (int r = 0; r < 3; ++r)
+    for (int q = 0; q < 3; ++q) {
+      float s = a[r * 3] * b[q];
+      s = s + a[r * 3 + 1] * b[3 + q];
+      s = s + a[r * 3 + 2] * b[6 + q];
+      c[r * 3 + q] = s;
+    }
+}
+
+// applyState on an identity matrix (GO:522-533): float Rz Ry Rx, float translation; T = row-major 4x4
+void gomp_apply_state(const double* x, float* T) {
+  const float a = (float)x[3], b = (float)x[4], c = (float)x[5];
+  const float sa = gomp_round_sin(a), ca = gomp_round_cos(a), sb = gomp_round_sin(b), cb = gomp_round_cos(b), sc = gomp_round_sin(c), cc = gomp_round_cos(c);
+  const float Rx[9] = {1.f, 0.f, 0.f, 0.f, ca, -sa, 0.f, sa, ca};
+  const float Ry[9] = {cb, 0.f, sb, 0.f, 1.f, 0.f, -sb, 0.f, cb};
+  const float Rz[9] = {cc, -sc, 0.f, sc, cc, 0.f, 0.f, 0.f, 1.f};
+  float zy[9], R[9];
+  gomp_mul3f(Rz, Ry, zy);
+  gomp_mul3f(zy, Rx, R);
+  for (int r = 0; r < 3; ++r) {
+    for (int q = 0; q < 3; ++q) T[r * 4 + q] = R[r * 3 + q];
+    T[r * 4 + 3] = (float)x[r];
+  }
+  T[12] = 0.f; T[13] = 0.f; T[14] = 0.f; T[15] = 1.f;
+}
+
+// computeRDerivative (GO:125-177); R row-major 3x3
+void gomp_r_derivative(const double* x, const double* R, double* g) {
+  const double phi = x[3], theta = x[4], psi = x[5];
+  const double cphi = std::cos(phi), sphi = std::sin(phi), ctheta = std::cos(theta), stheta = std::sin(theta), cpsi = std::cos(psi), spsi = std::sin(psi);
+  const double dPhi[9] = {0., sphi * spsi + cphi * cpsi * stheta, cphi * spsi - cpsi * sphi * stheta,
+                          0., -cpsi * sphi + cphi * spsi * stheta, -cphi * cpsi - sphi * spsi * stheta,
+                          0., cphi * ctheta, -ctheta * sphi};
+  const double dTheta[9] = {-cpsi * stheta, cpsi * ctheta * sphi, cphi * cpsi * ctheta,
+                            -spsi * stheta, ctheta * sphi * spsi, cphi * ctheta * spsi,
+                            -ctheta, -sphi * stheta, -cphi * stheta};
+  const double dPsi[9] = {-ctheta * spsi, -cphi * cpsi - sphi * spsi * stheta, cpsi * sphi - cphi * spsi * stheta,
+                          cpsi * ctheta, -cphi * spsi + cpsi * sphi * stheta, sphi * spsi + cphi * cpsi * stheta,
+                          0., 0., 0.};
+  auto inner = [&](const double* m1) {  // matricesInnerProd, GOH:324-334: r += mat1(j, i) * mat2(i, j)
+    double r = 0.;
+    for (int i = 0; i < 3; ++i)
+      for (int j = 0; j < 3; ++j) r += m1[j * 3 + i] * R[i * 3 + j];
+    return r;
+  };
+  g[3] = inner(dPhi);
+  g[4] = inner(dTheta);
+  g[5] = inner(dPsi);
+}
+
+void gomp_mul4f(const float* a, const float* b, float* c) {  // row-major 4x4 float product, sums left to right
+  for (int r = 0; r < 4; ++r)
+    for (int q = 0; q < 4; ++q) {
+      float s = a[r * 4] * b[q];
+      for (int k = 1; k < 4; ++k) s = s + a[r * 4 + k] * b[k * 4 + q];
+      c[r * 4 + q] = s;
+    }
+}
+
+bool gomp_ready(const gorio_apd* h) { return h->gomp_pairs >= 0 && h->corr_valid; }
+
+int gomp_reserve(gorio_apd* h) {
+  const int n = h->src->n;
+  const size_t nblk = (size_t)(n + 255) / 256;
+  const size_t spad = (size_t)roundup(n, 512);
+  const size_t cap = n + n / 8 + 256;
+  HIP_TRY(h, reserve_group(h->gomp_cap, n, cap, h->gomp_out, 3 * cap, h->gomp_s4, cap + 1024, h->gomp_maha, 9 * cap, h->gomp_part, 13 * (cap / 256 + 2), h->gomp_cnt, cap / 256 + 2));
+  (void)nblk; (void)spad;
+  HIP_TRY(h, h->gomp_res.reserve(16));
+  HIP_TRY(h, h->gomp_arrive.reserve(1));
+  return GORIO_OK;
+}
+
+// everything an update needs: both clouds, their covariances by the GICP_OMP rule, the search index in pruned mode, the buffers
+int gomp_prepare(gorio_apd* h) {
+  int rc = check_ready(h);
+  if (rc) return rc;
+  if (h->comm || (h->shard_only && h->comm_world > 1)) return fail(h, GORIO_ERR_STATE, "GICP_OMP has no sharded-source mode");
+  rc = ensure_points(h, h->src->n);
+  if (rc) return rc;
+  rc = gorio_apd_calculate_covariances(h);
+  if (rc) return rc;
+  if (h->params.search == GORIO_SEARCH_PRUNED) {
+    std::vector<std::pair<gorio_apd*, DevCloud*>> all = {{h, h->src.get()}, {h, h->tgt.get()}};
+    rc = run_index_build(h, all);
+    if (rc) return rc;
+  }
+  return gomp_reserve(h);
+}
+
+// output = guess * input (GO:402), in both orders the searches read
+int gomp_set_guess(gorio_apd* h, const float* guess) {
+  const DevCloud& s = *h->src;
+  const int n = s.n;
+  const bool pruned = h->params.search == GORIO_SEARCH_PRUNED;
+  const int n_spad = pruned ? s.idx_spad : 0;
+  TfArg g;
+  for (int i = 0; i < 12; ++i) g.m[i] = guess[i];
+  float* o = h->gomp_out;
+  const size_t st = h->gomp_out.cap() / 3;
+  const int cover = std::max(n, n_spad);
+  gomp_output_kernel<<<(cover + 255) / 256, 256, 0, h->stream>>>(s.x, s.y, s.z, n, g, o, o + st, o + 2 * st, pruned ? s.idx_s4.get() : nullptr, h->gomp_s4, n_spad);
+  HIP_TRY(h, hipGetLastError());
+  for (int i = 0; i < 16; ++i) h->gomp_guess[i] = guess[i];
+  return GORIO_OK;
+}
+
+// one pass of GO:411-476 at transformation_ = Tr: search, gate, Mahalanobis matrices; *m = pairs
+int gomp_update(gorio_apd* h, const float* Tr, int* m) {
+  const int n = h->src->n;
+  const int nbx = (n + 255) / 256;
+  GompR R;
+  for (int i = 0; i < 3; ++i)
+    for (int j = 0; j < 3; ++j) {
+      double s = 0.0;
+      for (int k = 0; k < 4; ++k) s += (double)Tr[i * 4 + k] * (double)h->gomp_guess[k * 4 + j];
+      R.r[i * 3 + j] = s;
+    }
+  R.thr2 = h->params.corr_dist_threshold * h->params.corr_dist_threshold;
+  int rc = ensure_batch(h, 1);
+  if (rc) return rc;
+  PairDesc d;
+  fill_desc(h, d, h->d_state, (n + 63) / 64);
+  float* o = h->gomp_out;
+  const size_t st = h->gomp_out.cap() / 3;
+  d.src.x = o; d.src.y = o + st; d.src.z = o + 2 * st;  // the searches read the `output` copy
+  d.src.idx.s4 = h->gomp_s4;
+  PairState s;
+  double Td[16];
+  for (int i = 0; i < 16; ++i) Td[i] = (double)Tr[i];
+  init_state(s, Td);
+  for (int i = 0; i < 12; ++i) s.Tf[i] = Tr[i];
+  HIP_TRY(h, hipMemcpyAsync(h->d_desc, &d, sizeof(PairDesc), hipMemcpyHostToDevice, h->stream));
+  HIP_TRY(h, hipMemcpyAsync(h->d_state, &s, sizeof(s), hipMemcpyHostToDevice, h->stream));
+  HIP_TRY(h, hipStreamSynchronize(h->stream));  // d and s live on this frame
+  HIP_TRY(h, hipMemsetAsync(h->best_key, 0xff, sizeof(unsigned long long) * n, h->stream));
+  launch_nn(h, h->d_desc, dim3(nbx, d.nn_splits, 1), roundup(n, 512), 1, h->tgt->n);
+  gomp_update_kernel<<<nbx, 256, 0, h->stream>>>(h->best_key, n, h->src->cov6, h->tgt->cov6, h->tgt->n, R, h->corr, h->sqd, h->gomp_maha, h->gomp_cnt);
+  HIP_TRY(h, hipGetLastError());
+  std::vector<int> cnt(nbx);
+  HIP_TRY(h, hipMemcpyAsync(cnt.data(), h->gomp_cnt, sizeof(int) * nbx, hipMemcpyDeviceToHost, h->stream));
+  HIP_TRY(h, hipStreamSynchronize(h->stream));
+  int total = 0;
+  for (int b = 0; b < nbx; ++b) total += cnt[b];
+  h->gomp_pairs = total;
+  h->corr_valid = true;
+  h->omega_valid = true;
+  *m = total;
+  return GORIO_OK;
+}
+
+// one functor evaluation at x over the pairs held: mode 0 f, 1 df, 2 fdf
+int gomp_evaluate(gorio_apd* h, const double* x, int mode, double* f, double* g) {
+  const int n = h->src->n, m = h->gomp_pairs;
+  const int nbx = (n + 255) / 256;
+  float T[16];
+  gomp_apply_state(x, T);
+  TfArg tf;
+  for (int i = 0; i < 12; ++i) tf.m[i] = T[i];
+  const float* o = h->gomp_out;
+  const size_t st = h->gomp_out.cap() / 3;
+  HIP_TRY(h, hipMemsetAsync(h->gomp_arrive, 0, sizeof(unsigned int), h->stream));
+  if (mode == 0) gomp_functor_kernel<0><<<nbx, 256, 0, h->stream>>>(o, o + st, o + 2 * st, n, h->tgt->p4, h->corr, h->gomp_maha, tf, h->gomp_part, h->gomp_arrive, h->gomp_res);
+  else if (mode == 1) gomp_functor_kernel<1><<<nbx, 256, 0, h->stream>>>(o, o + st, o + 2 * st, n, h->tgt->p4, h->corr, h->gomp_maha, tf, h->gomp_part, h->gomp_arrive, h->gomp_res);
+  else gomp_functor_kernel<2><<<nbx, 256, 0, h->stream>>>(o, o + st, o + 2 * st, n, h->tgt->p4, h->corr, h->gomp_maha, tf, h->gomp_part, h->gomp_arrive, h->gomp_res);
+  HIP_TRY(h, hipGetLastError());
+  double r[13] = {0};
+  HIP_TRY(h, hipMemcpyAsync(r, h->gomp_res, sizeof(r), hipMemcpyDeviceToHost, h->stream));
+  HIP_TRY(h, hipStreamSynchronize(h->stream));
+  ++h->gomp_evals;
+  if (mode != 1 && f) *f = r[0] / (double)m;
+  if (mode != 0 && g) {
+    const double sc = 2.0 / (double)m;
+    double R[9];
+    for (int i = 0; i < 3; ++i) g[i] = r[1 + i] * sc;
+    for (int i = 0; i < 9; ++i) R[i] = r[4 + i] * sc;
+    gomp_r_derivative(x, R, g);
+  }
+  return GORIO_OK;
+}
+
+// computeTransformation, GO:375-520
+int gomp_align(gorio_apd* h, const float* guess, float* T_out, double* H_out, int* converged, int* nr_iterations, int* n_linearize) {
+  if (!guess || !T_out) return GORIO_ERR_INVALID;
+  HIP_TRY(h, hipSetDevice(h->device));
+  int rc = gomp_prepare(h);
+  if (rc) return rc;
+  rc = gomp_set_guess(h, guess);
+  if (rc) return rc;
+  h->gomp_outer = 0; h->gomp_inner = 0; h->gomp_evals = 0; h->gomp_status = gorio_bfgs::kRunning;
+  float Tr[16], prev[16];
+  for (int i = 0; i < 16; ++i) Tr[i] = prev[i] = (i % 5 == 0) ? 1.f : 0.f;  // align(): transformation_ = previous_transformation_ = identity
+  bool conv = false;
+  int nr = 0;
+  const gorio_apd_params& p = h->params;
+  int device_rc = GORIO_OK;
+  while (!conv) {
+    int m = 0;
+    rc = gomp_update(h, Tr, &m);
+    if (rc) return rc;
+    for (int i = 0; i < 16; ++i) prev[i] = Tr[i];  // GO:479
+    if (m < 4) {  // NotEnoughPointsException, GO:187-191 -> break, GO:499-503
+      h->err = "GICP_OMP: fewer than 4 correspondences";
+      break;
+    }
+    double x[6] = {(double)Tr[3], (double)Tr[7], (double)Tr[11], (double)(float)std::atan2((double)Tr[9], (double)Tr[10]), (double)(float)std::asin((double)-Tr[8]),
+                   (double)(float)std::atan2((double)Tr[4], (double)Tr[0])};  // GO:194-200, float results rounded once
+    gorio_bfgs::Callbacks cb;
+    cb.f = [&](const double* xx) { double f = NAN; if (!device_rc) device_rc = gomp_evaluate(h, xx, 0, &f, nullptr); return f; };
+    cb.df = [&](const double* xx, double* g) { for (int i = 0; i < 6; ++i) g[i] = NAN; if (!device_rc) device_rc = gomp_evaluate(h, xx, 1, nullptr, g); };
+    cb.fdf = [&](const double* xx, double* f, double* g) { *f = NAN; for (int i = 0; i < 6; ++i) g[i] = NAN; if (!device_rc) device_rc = gomp_evaluate(h, xx, 2, f, g); };
+    gorio_bfgs::Solver solver(cb);  // rho, sigma, tau1, tau2, tau3, order of GO:212-217 are the defaults of gorio_bfgs::Params
+    int inner = 0;
+    const int result = gorio_bfgs::minimize(solver, x, h->gomp_max_inner, 1e-2, &inner);
+    h->gomp_inner += inner;
+    h->gomp_status = result;
+    if (device_rc) return device_rc;
+    if (!(result == gorio_bfgs::kNoProgress || result == gorio_bfgs::kSuccess || inner == h->gomp_max_inner)) {  // SolverDidntConvergeException, GO:243-245
+      h->err = "GICP_OMP: BFGS solver didn't converge";
+      break;
+    }
+    gomp_apply_state(x, Tr);  // GO:240-241
+    double delta = 0.;  // GO:485-497
+    for (int k = 0; k < 4; ++k)
+      for (int l = 0; l < 4; ++l) {
+        const double ratio = (k < 3 && l < 3) ? 1. / p.rotation_epsilon : 1. / p.transformation_epsilon;
+        const double c_delta = ratio * (double)std::fabs(prev[k * 4 + l] - Tr[k * 4 + l]);
+        if (c_delta > delta) delta = c_delta;
+      }
+    ++nr;
+    ++h->gomp_outer;
+    if (nr >= p.max_iterations || delta < 1) {
+      conv = true;
+      for (int i = 0; i < 16; ++i) prev[i] = Tr[i];
+    }
+  }
+  gomp_mul4f(prev, guess, T_out);  // GO:516
+  if (H_out) std::memset(H_out, 0, sizeof(double) * 36);
+  if (converged) *converged = conv ? 1 : 0;
+  if (nr_iterations) *nr_iterations = nr;
+  if (n_linearize) *n_linearize = h->gomp_evals;
+  resolve_stage_events(h);
+  return GORIO_OK;
+}
+
+// the covariance rule of GO:50-122 over the lists run_covariances has just left in DevCloud::knn
+int gomp_covariances(gorio_apd* lead, std::vector<std::pair<gorio_apd*, DevCloud*>>& todo) {
+  for (auto& t : todo) {
+    DevCloud& c = *t.second;
+    gomp_cov_kernel<<<(c.n + 255) / 256, 256, 0, lead->stream>>>(c.view(), c.knn, c.knn_k, t.first->gomp_eps);
+  }
+  HIP_TRY(lead, hipGetLastError());
+  return GORIO_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int gorio_apd_set_gicp_omp_params(gorio_apd_t* h, double gicp_epsilon, int max_optimizer_iterations) {
+  if (!h) return GORIO_ERR_INVALID;
+  if (!(gicp_epsilon > 0.0) || !std::isfinite(gicp_epsilon)) return fail(h, GORIO_ERR_INVALID, "set_gicp_omp_params: gicp_epsilon must be positive");
+  if (max_optimizer_iterations < 1) return fail(h, GORIO_ERR_INVALID, "set_gicp_omp_params: max_optimizer_iterations must be at least 1");
+  if (gicp_epsilon != h->gomp_eps) {  // covariances estimated by the old epsilon are stale; a cloud other handles hold too is theirs (check_ready then refuses it)
+    for (auto* c : {&h->src, &h->tgt})
+      if ((*c)->cov_reg == kRegGicpOmp && (*c)->cov_count && c->use_count() == 1) (*c)->covs_dropped();
+  }
+  h->gomp_eps = gicp_epsilon;
+  h->gomp_max_inner = max_optimizer_iterations;
+  return GORIO_OK;
+}
+
+int gorio_apd_get_gicp_omp_params(const gorio_apd_t* h, double* gicp_epsilon, int* max_optimizer_iterations) {
+  if (!h) return GORIO_ERR_INVALID;
+  if (gicp_epsilon) *gicp_epsilon = h->gomp_eps;
+  if (max_optimizer_iterations) *max_optimizer_iterations = h->gomp_max_inner;
+  return GORIO_OK;
+}
+
+int gorio_apd_gicp_omp_update(gorio_apd_t* h, const float transformation[16], const float guess[16], int* m) {
+  if (!h || !transformation || !guess || !m) return GORIO_ERR_INVALID;
+  if (h->method != GORIO_METHOD_GICP_OMP) return fail(h, GORIO_ERR_STATE, "gicp_omp_update: the handle's method is not GORIO_METHOD_GICP_OMP");
+  HIP_TRY(h, hipSetDevice(h->device));
+  int rc = gomp_prepare(h);
+  if (rc) return rc;
+  rc = gomp_set_guess(h, guess);
+  if (rc) return rc;
+  return gomp_update(h, transformation, m);
+}
+
+int gorio_apd_gicp_omp_evaluate(gorio_apd_t* h, const double x[6], int mode, double* f, double* g) {
+  if (!h || !x || mode < 0 || mode > 2) return GORIO_ERR_INVALID;
+  if (h->method != GORIO_METHOD_GICP_OMP) return fail(h, GORIO_ERR_STATE, "gicp_omp_evaluate: the handle's method is not GORIO_METHOD_GICP_OMP");
+  if (!gomp_ready(h) || h->gomp_cap < h->src->n) return fail(h, GORIO_ERR_STATE, "gicp_omp_evaluate: no pairs held (gorio_apd_gicp_omp_update or an align first)");
+  if (h->gomp_pairs < 1) return fail(h, GORIO_ERR_STATE, "gicp_omp_evaluate: the last update found no pairs");
+  if ((mode != 1 && !f) || (mode != 0 && !g)) return GORIO_ERR_INVALID;
+  HIP_TRY(h, hipSetDevice(h->device));
+  return gomp_evaluate(h, x, mode, f, g);
+}
+
+int gorio_apd_gicp_omp_diag(const gorio_apd_t* h, int* outer, int* inner_total, int* evaluations, int* last_status) {
+  if (!h) return GORIO_ERR_INVALID;
+  if (outer) *outer = h->gomp_outer;
+  if (inner_total) *inner_total = h->gomp_inner;
+  if (evaluations) *evaluations = h->gomp_evals;
+  if (last_status) *last_status = h->gomp_status;
+  return GORIO_OK;
+}
+
+}  // extern "C"

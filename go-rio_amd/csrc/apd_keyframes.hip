@@ -353,7 +353,7 @@ static int kf_hand_off(gorio_apd* apd, gorio_kf* kf, int id, bool source) {
   if (!e) return fail(apd, rc, what + why);
   if (e->n <= 0) return fail(apd, GORIO_ERR_INVALID, what + "bad cloud arguments (the keyframe is empty)");
   const DevCloud& c = *e->cloud;
-  if (c.cov_count == c.n && c.cov_k >= 0 && (c.cov_k != apd->params.k_correspondences || c.cov_reg != apd->params.regularization))
+  if (cov_rule_differs(apd, c))
     return fail(apd, GORIO_ERR_INVALID, what + "the keyframe's covariances were estimated with another k_correspondences / regularization than this handle's");
   if (!source && apd->method == GORIO_METHOD_VGICP && c.vm_valid && (c.vm_res != apd->voxel_resolution || c.vm_mult != (apd->voxel_mode == GORIO_VOXEL_MULTIPLICATIVE)))
     return fail(apd, GORIO_ERR_INVALID, what + "the keyframe's voxel map was built with another voxel_resolution / voxel_mode than this handle's");

@@ -624,7 +624,7 @@ static int scan_hand_off(gorio_apd* apd, gorio_scan* scan, bool source) {
   if (apd->device != scan->device) return fail(apd, GORIO_ERR_INVALID, "set_input_from_scan: both handles must live on one device");
   if (!scan->have_output) return fail(apd, GORIO_ERR_STATE, "set_input_from_scan: the pipeline's last run produced no frame");
   const std::shared_ptr<DevCloud>& out = scan->prep.h->src;
-  if (out->cov_count == out->n && out->cov_k >= 0 && (out->cov_k != apd->params.k_correspondences || out->cov_reg != apd->params.regularization))
+  if (cov_rule_differs(apd, *out))
     return fail(apd, GORIO_ERR_INVALID, "set_input_from_scan: another handle estimated this cloud's covariances with another k_correspondences / regularization");
   (source ? apd->src : apd->tgt) = out;  // points, labels, search index: one copy on the device, alive until the last handle lets go of it
   apd->corr_valid = false;

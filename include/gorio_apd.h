@@ -45,7 +45,7 @@ typedef enum { GORIO_SEARCH_BRUTE_FORCE = 0, GORIO_SEARCH_PRUNED = 1 } gorio_sea
 
 /* which fast_gicp registration a handle stands for: the three classes select_registration_method hands out through one pcl::Registration
  * pointer (REG:28-37 FAST_APDGICP, REG:63-67 FAST_GICP, REG:68-71 FAST_VGICP) */
-typedef enum { GORIO_METHOD_APDGICP = 0, GORIO_METHOD_GICP = 1, GORIO_METHOD_VGICP = 2 } gorio_method;
+typedef enum { GORIO_METHOD_APDGICP = 0, GORIO_METHOD_GICP = 1, GORIO_METHOD_VGICP = 2, GORIO_METHOD_GICP_OMP = 3 /* pclomp GICP, REG:91-100; below */ } gorio_method;
 /* fast_gicp::NeighborSearchMethod, gicp_settings.hpp:8 (same order) */
 typedef enum { GORIO_VOXEL_DIRECT27 = 0, GORIO_VOXEL_DIRECT7 = 1, GORIO_VOXEL_DIRECT1 = 2, GORIO_VOXEL_DIRECT_RADIUS = 3 } gorio_voxel_search;
 /* fast_gicp::VoxelAccumulationMode, gicp_settings.hpp:10 (same order) */
@@ -108,6 +108,35 @@ int gorio_apd_get_params(const gorio_apd_t* h, gorio_apd_params* p);
  */
 int gorio_apd_set_method(gorio_apd_t* h, int method, double voxel_resolution, int voxel_search, int voxel_mode);
 int gorio_apd_get_method(const gorio_apd_t* h, int* method, double* voxel_resolution, int* voxel_search, int* voxel_mode);
+/*
+ * GORIO_METHOD_GICP_OMP: pclomp::GeneralizedIterativeClosestPoint (REG:91-100; GOH = ndt_omp/include/pclomp/gicp_omp.h, GO = its
+ * gicp_omp_impl.hpp).  gorio_apd_set_method(h, GORIO_METHOD_GICP_OMP, ...) ignores the voxel arguments.  In this mode
+ *   - covariances are estimated by GO:50-122 from the handle's k-NN lists (float products summed in double, cov / k - mean mean^T, SVD
+ *     rebuild with singular values 1, 1, gicp_epsilon); a cloud with fewer points than k_correspondences is refused (GORIO_ERR_INVALID; the
+ *     reference prints an error and goes on without covariances).  The rule counts as one more regularization for shared clouds: sharing
+ *     with a handle that estimates by another rule, k or gicp_epsilon gives GORIO_ERR_INVALID;
+ *   - gorio_apd_align runs computeTransformation GO:375-520: the exact 1-NN of transformation_ * (guess * p) per outer iteration, float
+ *     Mahalanobis matrices, the BFGS inner solve (GO:193-246) on the host with one device evaluation of the functor (GO:249-371) per round
+ *     trip.  H_out is zero-filled; n_linearize = functor evaluations.  max_iterations, transformation_epsilon, rotation_epsilon,
+ *     corr_dist_threshold, k_correspondences and search of gorio_apd_params are read, nothing else of it.  Fewer than 4 pairs, or a solver
+ *     status other than Success / NoProgress before the inner cap, ends the align unconverged with previous_transformation_ * guess;
+ *   - gorio_apd_linearize, gorio_apd_compute_error and gorio_apd_align_batch return GORIO_ERR_UNSUPPORTED (align_batch changes nothing);
+ *     the sharded-source calls return GORIO_ERR_STATE; everything else of this header works as in the other modes.
+ * gicp_epsilon = gicp_epsilon_ (default 0.001, GOH:118), max_optimizer_iterations = setMaximumOptimizerIterations (default 20, GOH:121;
+ * REG:99).  GORIO_ERR_INVALID for gicp_epsilon <= 0 and max_optimizer_iterations < 1.  Stored in every mode.
+ */
+int gorio_apd_set_gicp_omp_params(gorio_apd_t* h, double gicp_epsilon, int max_optimizer_iterations);
+int gorio_apd_get_gicp_omp_params(const gorio_apd_t* h, double* gicp_epsilon, int* max_optimizer_iterations);
+/* parity hooks (GICP_OMP mode).  _update: one pass of GO:411-476 with transformation_ = transformation16 and the given guess (both
+ * row-major float 4x4): m receives the number of pairs; gorio_apd_get_correspondences then gives the target index per source point (-1:
+ * none) and the float distances, gorio_apd_get_mahalanobis the stored float matrices widened to double (zero for unpaired points).
+ * _evaluate: the functor at x = (tx, ty, tz, roll, pitch, yaw) over those pairs -- mode 0: operator() (f), 1: df (g6), 2: fdf (both).
+ * _diag: outer iterations, minimizeOneStep calls and functor evaluations of the last align, and its last solver status (-1 running,
+ * 0 success, 1 no progress, 2 failed). */
+int gorio_apd_gicp_omp_update(gorio_apd_t* h, const float transformation16[16], const float guess16[16], int* m);
+int gorio_apd_gicp_omp_evaluate(gorio_apd_t* h, const double x6[6], int mode, double* f, double* g6);
+int gorio_apd_gicp_omp_diag(const gorio_apd_t* h, int* outer, int* inner_total, int* evaluations, int* last_status);
+
 /* parity hooks (VGICP mode; they build the map when it is stale): voxelmap_ (VGH:85) as arrays over the occupied voxels in ascending
  * lexicographic (x, y, z) coordinate order -- coord3: 3 ints, num_points, mean4: GaussianVoxel::mean, cov16: GaussianVoxel::cov row-major
  * (VOX:74-76).  n_voxels always receives the voxel count; the arrays (any may be NULL) are filled when capacity >= that count.
