@@ -54,6 +54,7 @@ APD_SYMBOLS = [
     "gorio_apd_get_stage_times", "gorio_apd_set_target_shared", "gorio_comm_get_unique_id", "gorio_apd_comm_init", "gorio_apd_comm_destroy", "gorio_apd_comm_info", "gorio_apd_debug_set_shard", "gorio_apd_debug_set_schedule", "gorio_apd_debug_get_index", "gorio_apd_set_target_submap", "gorio_apd_get_target_points",
     "gorio_apd_set_method", "gorio_apd_get_method", "gorio_apd_get_voxelmap", "gorio_apd_get_voxel_correspondences",
     "gorio_apd_set_gicp_omp_params", "gorio_apd_get_gicp_omp_params", "gorio_apd_gicp_omp_update", "gorio_apd_gicp_omp_evaluate", "gorio_apd_gicp_omp_diag",
+    "gorio_apd_gicp_omp_align_batch", "gorio_apd_gicp_omp_batch_diag",
 ]
 
 # gorio_method / gorio_voxel_search / gorio_voxel_mode of gorio_apd.h (the latter two in the order of gicp_settings.hpp)
@@ -530,6 +531,33 @@ def align_batch(objs, guesses=None):
         o._final = T[q]
         o._converged = bool(conv[q])
         out.append(dict(T=T[q], H=H[q], converged=bool(conv[q]), nr_iterations=int(nit[q]), n_linearize=int(nlin[q])))
+    return out
+
+
+def gicp_omp_align_batch(objs, guesses=None):
+    """gorio_apd_gicp_omp_align_batch over a list of ApdGicp objects in GICP_OMP mode (all on one device): their aligns in lock-step
+    rounds, every result bit for bit the one of the object's own align().  Returns the list of dicts align() returns, each with
+    batch_diag = dict(rounds, launches) of the whole batch.  An empty list makes no call."""
+    n = len(objs)
+    if n == 0:
+        return []
+    lib = load_library()
+    g = np.ascontiguousarray(np.tile(np.eye(4, dtype=np.float32), (n, 1, 1)) if guesses is None else guesses, np.float32).reshape(n, 16)
+    T = np.zeros((n, 4, 4), np.float32)
+    conv = np.zeros(n, np.int32)
+    nit = np.zeros(n, np.int32)
+    nev = np.zeros(n, np.int32)
+    arr = (C.c_void_p * n)(*[o._h for o in objs])
+    rc = lib.gorio_apd_gicp_omp_align_batch(arr, n, _p(g, C.c_float), _p(T, C.c_float), _p(conv, C.c_int), _p(nit, C.c_int), _p(nev, C.c_int))
+    _check(objs[0]._h, rc)
+    rounds, launches = C.c_int(0), C.c_int(0)
+    _check(objs[0]._h, lib.gorio_apd_gicp_omp_batch_diag(objs[0]._h, C.byref(rounds), C.byref(launches)))
+    diag = dict(rounds=rounds.value, launches=launches.value)
+    out = []
+    for q, o in enumerate(objs):
+        o._final = T[q]
+        o._converged = bool(conv[q])
+        out.append(dict(T=T[q], H=np.zeros((6, 6), np.float64), converged=bool(conv[q]), nr_iterations=int(nit[q]), n_linearize=int(nev[q]), batch_diag=dict(diag)))
     return out
 
 

@@ -159,6 +159,13 @@ struct gorio_apd {
   float gomp_guess[16] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1};  // guess of the `output` cloud held
   int gomp_pairs = -1;                // pairs of the last update (-1: none held)
   int gomp_outer = 0, gomp_inner = 0, gomp_evals = 0, gomp_status = -1;  // gorio_apd_gicp_omp_diag
+  // gorio_apd_gicp_omp_align_batch (owned by the handle that leads a batch): job and workgroup table, the partial slots of the round's
+  // evaluations and updates, the folded sums and pair counts on the device and pinned on the host
+  DevBuf<void> gomp_b_jobs, gomp_b_out;
+  DevBuf<double> gomp_b_part;
+  DevBuf<int> gomp_b_cnt;
+  PinnedBuf gomp_b_h_out;
+  int gomp_b_rounds = 0, gomp_b_launches = 0;  // gorio_apd_gicp_omp_batch_diag
   DevBuf<PairState> d_state;
   DevBuf<PairDesc> d_desc;   // batch descriptor array and states (owned by the handle that leads a batch): one group of capacity desc_cap
   DevBuf<PairState> d_states_batch;
@@ -193,7 +200,7 @@ struct gorio_apd {
       if (ev) hipEventDestroy(ev);
     }
   };
-  Pinned pin_ijobs, pin_jobs, pin_desc, pin_states, pin_copy, pin_vox;
+  Pinned pin_ijobs, pin_jobs, pin_desc, pin_states, pin_copy, pin_vox, pin_gomp_jobs;
   PinnedBuf pin_looks;  // where the align loop's looks at the pair states land (a download into pageable memory is staged by the runtime)
   std::string err;
   // profiling
@@ -944,7 +951,7 @@ int align_impl(gorio_apd** hs, int count, const float* guesses, float* T_out, do
   for (int q = 0; q < count; ++q)
     if (hs[q] && hs[q]->comm && count != 1) return fail(lead, GORIO_ERR_INVALID, "a handle with a communicator (sharded source) cannot be part of a batch");
   for (int q = 0; q < count; ++q)
-    if (hs[q] && hs[q]->method == GORIO_METHOD_GICP_OMP) return fail(lead, GORIO_ERR_UNSUPPORTED, "align_batch: GICP_OMP handles align one at a time (gorio_apd_align); a batched BFGS is not built");
+    if (hs[q] && hs[q]->method == GORIO_METHOD_GICP_OMP) return fail(lead, GORIO_ERR_UNSUPPORTED, "align_batch: GICP_OMP handles batch through gorio_apd_gicp_omp_align_batch (the BFGS shell is not the Gauss-Newton / LM one)");
   std::unordered_set<gorio_apd*> distinct;
   for (int q = 0; q < count; ++q) {
     gorio_apd* h = hs[q];

@@ -6,9 +6,13 @@
 //   gomp_output_kernel    output = guess * p in float, once per align, in original and in search-index order                        GO:402
 //   gomp_update_kernel    gate, R C1 R^T + C2, cofactor inverse, float Mahalanobis matrix, pairs per block                         GO:441-460
 //   gomp_functor_kernel   <0> operator() float path, <1> df, <2> fdf: one launch each, wave -> block -> block order in fp64        GO:249-371
+//   gomp_update_batch_kernel, gomp_functor_batch_kernel, gomp_fold_batch_kernel: the same per-workgroup bodies (gomp_update_block,
+//                         gomp_functor_block) over a job table -- one pending update or evaluation of one handle per job -- and the sums
+//                         of every job's blocks in block order                                          gorio_apd_gicp_omp_align_batch
 // The 1-NN search is nn_search_kernel / nn_search_pruned_kernel run on a descriptor whose source view is the `output` copy: the kernels read
 // coordinates and nothing else of a source, so the index built for the stored source serves unchanged.
-// The BFGS shell (gicp_bfgs.h) and the outer loop of GO:409-516 run on the host, one device evaluation per round trip.
+// The BFGS shell (gicp_bfgs.h) and the outer loop of GO:409-516 run on the host as one resumable machine per handle (GompMachine):
+// gorio_apd_align drives one, one device evaluation per round trip; gorio_apd_gicp_omp_align_batch drives many in lock-step.
 #include "gicp_bfgs.h"
 
 namespace gorio {
@@ -78,11 +82,12 @@ __global__ __launch_bounds__(256) void gomp_output_kernel(const float* __restric
 }
 
 // Consumes (and re-arms) best_key; corr / sqd as linearize_kernel leaves them; maha[i][9] = the float cast of (R C1 R^T + C2)^-1, row-major;
-// cnt[block] = pairs of the block's 256 points.
-__global__ __launch_bounds__(256) void gomp_update_kernel(unsigned long long* __restrict__ best_key, int n, const double* __restrict__ c1, const double* __restrict__ c2, int n_tgt, GompR R,
-                                                          int* __restrict__ corr, float* __restrict__ sqd, float* __restrict__ maha, int* __restrict__ cnt) {
+// cnt[0] = pairs of the block's 256 points.  The work of ONE workgroup of 256 lanes on source points [256 block, 256 block + 256) of one
+// handle, shared by the single and the batched kernel.
+__device__ __forceinline__ void gomp_update_block(unsigned long long* __restrict__ best_key, int n, const double* __restrict__ c1, const double* __restrict__ c2, int n_tgt, const GompR& R,
+                                                  int* __restrict__ corr, float* __restrict__ sqd, float* __restrict__ maha, int block, int* __restrict__ cnt) {
   __shared__ int s_cnt[4];
-  const int i = blockIdx.x * 256 + threadIdx.x;
+  const int i = block * 256 + threadIdx.x;
   bool pair = false;
   if (i < n) {
     const unsigned long long key = best_key[i];
@@ -128,22 +133,26 @@ __global__ __launch_bounds__(256) void gomp_update_kernel(unsigned long long* __
   const unsigned long long bal = __ballot(pair);
   if ((threadIdx.x & 63) == 0) s_cnt[threadIdx.x >> 6] = __popcll(bal);
   __syncthreads();
-  if (threadIdx.x == 0) cnt[blockIdx.x] = (s_cnt[0] + s_cnt[1]) + (s_cnt[2] + s_cnt[3]);
+  if (threadIdx.x == 0) cnt[0] = (s_cnt[0] + s_cnt[1]) + (s_cnt[2] + s_cnt[3]);
+}
+
+// grid: ceil(n / 256), block 256.  cnt[block] = pairs of the block
+__global__ __launch_bounds__(256) void gomp_update_kernel(unsigned long long* __restrict__ best_key, int n, const double* __restrict__ c1, const double* __restrict__ c2, int n_tgt, GompR R,
+                                                          int* __restrict__ corr, float* __restrict__ sqd, float* __restrict__ maha, int* __restrict__ cnt) {
+  gomp_update_block(best_key, n, c1, c2, n_tgt, R, corr, sqd, maha, (int)blockIdx.x, cnt + blockIdx.x);
 }
 
 // MODE 0: Sum res . (M res) over the pairs on the float path of operator() (GO:269-275), 1 value.
 // MODE 1: df (GO:305-320): Sum temp (3) and Sum p_src3 temp^T (9) on the double path, values [1..12].
 // MODE 2: fdf (GO:352-365): the same plus Sum res . temp in [0].
-// One launch: every workgroup reduces its 256 source points wave -> block (the four waves in a fixed order) and stores one partial; the
-// workgroup that draws the last ticket adds the partials in block order into out[0..12].  arrive is zeroed ahead of the launch.
+// The work of ONE workgroup of 256 lanes, shared by the single and the batched kernel: source points [256 block, 256 block + 256) of one
+// handle, reduced wave -> block (the four waves in a fixed order) into out[V0 .. V1) (13 slots).  s_red: 4 * 13 doubles of LDS.
 template <int MODE>
-__global__ __launch_bounds__(256) void gomp_functor_kernel(const float* __restrict__ ox, const float* __restrict__ oy, const float* __restrict__ oz, int n, const float4* __restrict__ tgt,
-                                                           const int* __restrict__ corr, const float* __restrict__ maha, TfArg tf, double* __restrict__ partials,
-                                                           unsigned int* __restrict__ arrive, double* __restrict__ out) {
+__device__ __forceinline__ void gomp_functor_block(const float* __restrict__ ox, const float* __restrict__ oy, const float* __restrict__ oz, int n, const float4* __restrict__ tgt,
+                                                   const int* __restrict__ corr, const float* __restrict__ maha, const TfArg& tf, int block, double* s_red, double* __restrict__ out) {
   constexpr int NV = 13;
   constexpr int V0 = MODE == 1 ? 1 : 0, V1 = MODE == 0 ? 1 : NV;  // the values [V0, V1) this mode produces
-  __shared__ double s_red[4 * NV + 1];
-  const int i = blockIdx.x * 256 + threadIdx.x;
+  const int i = block * 256 + threadIdx.x;
   double v[NV];
 #pragma unroll
   for (int q = 0; q < NV; ++q) v[q] = 0.0;
@@ -183,8 +192,20 @@ __global__ __launch_bounds__(256) void gomp_functor_kernel(const float* __restri
   __syncthreads();
   if ((int)threadIdx.x >= V0 && (int)threadIdx.x < V1) {
     const int q = threadIdx.x;
-    partials[(size_t)blockIdx.x * NV + q] = ((s_red[q] + s_red[NV + q]) + s_red[2 * NV + q]) + s_red[3 * NV + q];
+    out[q] = ((s_red[q] + s_red[NV + q]) + s_red[2 * NV + q]) + s_red[3 * NV + q];
   }
+}
+
+// One launch: every workgroup reduces its 256 source points and stores one partial; the workgroup that draws the last ticket adds the
+// partials in block order into out[0..12].  arrive is zeroed ahead of the launch.
+template <int MODE>
+__global__ __launch_bounds__(256) void gomp_functor_kernel(const float* __restrict__ ox, const float* __restrict__ oy, const float* __restrict__ oz, int n, const float4* __restrict__ tgt,
+                                                           const int* __restrict__ corr, const float* __restrict__ maha, TfArg tf, double* __restrict__ partials,
+                                                           unsigned int* __restrict__ arrive, double* __restrict__ out) {
+  constexpr int NV = 13;
+  constexpr int V0 = MODE == 1 ? 1 : 0, V1 = MODE == 0 ? 1 : NV;
+  __shared__ double s_red[4 * NV + 1];
+  gomp_functor_block<MODE>(ox, oy, oz, n, tgt, corr, maha, tf, (int)blockIdx.x, s_red, partials + (size_t)blockIdx.x * NV);
   // hand-over to the last workgroup: stores drained, one agent-scope release ahead of the ticket, one acquire behind the last one
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   __syncthreads();
@@ -207,6 +228,69 @@ __global__ __launch_bounds__(256) void gomp_functor_kernel(const float* __restri
     for (unsigned int b = 0; b < gridDim.x; ++b) s += partials[(size_t)b * NV + q];
     out[q] = s;
   }
+}
+
+// One pending request of gorio_apd_gicp_omp_align_batch: an evaluation of the functor (mode 0, 1, 2) or an update (mode 3) of one handle.
+// Its workgroups write the partial slots (13 doubles each; one int each for an update) [first, first + nblk).
+struct GompJob {
+  const float *ox, *oy, *oz;  // the `output` cloud
+  const float4* tgt;
+  int* corr;
+  float* maha;
+  // an update only
+  unsigned long long* best_key;
+  const double *c1, *c2;
+  float* sqd;
+  GompR R;
+  TfArg tf;   // the transform of the request (an evaluation only)
+  int n, n_tgt;
+  int mode;
+  int first;  // first partial slot
+  int nblk;   // ceil(n / 256)
+  int pad0_;
+};
+
+// grid: the sum over the launch's jobs of ceil(n_j / 256), block 256.  wg[blockIdx.x] = (job, job-local block), written by the host with the
+// job table; the index is uniform over the workgroup, so the job record comes in through scalar loads.  The host keeps wg[].x < number of
+// jobs and wg[].y < jobs[wg[].x].nblk; the partial buffers hold first + nblk slots for every job.
+__global__ __launch_bounds__(256) void gomp_functor_batch_kernel(const GompJob* __restrict__ jobs, const int2* __restrict__ wg, double* __restrict__ partials) {
+  __shared__ double s_red[4 * 13];
+  const int2 w = wg[blockIdx.x];
+  const GompJob& j = jobs[w.x];
+  double* out = partials + (size_t)(j.first + w.y) * 13;
+  if (j.mode == 0) gomp_functor_block<0>(j.ox, j.oy, j.oz, j.n, j.tgt, j.corr, j.maha, j.tf, w.y, s_red, out);
+  else if (j.mode == 1) gomp_functor_block<1>(j.ox, j.oy, j.oz, j.n, j.tgt, j.corr, j.maha, j.tf, w.y, s_red, out);
+  else gomp_functor_block<2>(j.ox, j.oy, j.oz, j.n, j.tgt, j.corr, j.maha, j.tf, w.y, s_red, out);
+}
+
+__global__ __launch_bounds__(256) void gomp_update_batch_kernel(const GompJob* __restrict__ jobs, const int2* __restrict__ wg, int* __restrict__ cnt) {
+  const int2 w = wg[blockIdx.x];
+  const GompJob& j = jobs[w.x];
+  gomp_update_block(j.best_key, j.n, j.c1, j.c2, j.n_tgt, j.R, j.corr, j.sqd, j.maha, w.y, cnt + j.first + w.y);
+}
+
+// grid: the round's jobs, block 64.  An evaluation: lane q adds the job's partials of value q in block order, as the last workgroup of
+// gomp_functor_kernel does, into out[13 job + q] (the values the mode produces).  An update: the pairs of the job's blocks into pairs[job].
+__global__ __launch_bounds__(64) void gomp_fold_batch_kernel(const GompJob* __restrict__ jobs, const double* __restrict__ partials, const int* __restrict__ cnt, double* __restrict__ out,
+                                                             int* __restrict__ pairs) {
+  const GompJob& j = jobs[blockIdx.x];
+  const int q = threadIdx.x;
+  if (j.mode == 3) {
+    if (q == 0) {
+      int total = 0;
+      for (int b = 0; b < j.nblk; ++b) total += cnt[j.first + b];
+      pairs[blockIdx.x] = total;
+    }
+    return;
+  }
+  const int v0 = j.mode == 1 ? 1 : 0, v1 = j.mode == 0 ? 1 : 13;
+  if (q >= v0 && q < v1) {
+    double s = 0.0;
+    for (int b = 0; b < j.nblk; ++b) s += partials[(size_t)(j.first + b) * 13 + q];
+    out[(size_t)blockIdx.x * 13 + q] = s;
+  }
+  if (q < 13 && (q < v0 || q >= v1)) out[(size_t)blockIdx.x * 13 + q] = 0.0;
+  if (q == 0) pairs[blockIdx.x] = 0;
 }
 
 }  // namespace gorio
@@ -325,10 +409,8 @@ int gomp_set_guess(gorio_apd* h, const float* guess) {
   return GORIO_OK;
 }
 
-// one pass of GO:411-476 at transformation_ = Tr: search, gate, Mahalanobis matrices; *m = pairs
-int gomp_update(gorio_apd* h, const float* Tr, int* m) {
-  const int n = h->src->n;
-  const int nbx = (n + 255) / 256;
+// the rotation of transformation_ * guess in double (GO:417-423) and the squared gate of an update at transformation_ = Tr
+GompR gomp_make_r(const gorio_apd* h, const float* Tr) {
   GompR R;
   for (int i = 0; i < 3; ++i)
     for (int j = 0; j < 3; ++j) {
@@ -337,6 +419,14 @@ int gomp_update(gorio_apd* h, const float* Tr, int* m) {
       R.r[i * 3 + j] = s;
     }
   R.thr2 = h->params.corr_dist_threshold * h->params.corr_dist_threshold;
+  return R;
+}
+
+// one pass of GO:411-476 at transformation_ = Tr: search, gate, Mahalanobis matrices; *m = pairs
+int gomp_update(gorio_apd* h, const float* Tr, int* m) {
+  const int n = h->src->n;
+  const int nbx = (n + 255) / 256;
+  const GompR R = gomp_make_r(h, Tr);
   int rc = ensure_batch(h, 1);
   if (rc) return rc;
   PairDesc d;
@@ -369,9 +459,23 @@ int gomp_update(gorio_apd* h, const float* Tr, int* m) {
   return GORIO_OK;
 }
 
+// the functor's value and gradient from the 13 sums of an evaluation at x over the m pairs held (GO:275, 321-327, 366-370)
+void gomp_finish_evaluation(gorio_apd* h, const double* x, int mode, const double* r, double* f, double* g) {
+  const int m = h->gomp_pairs;
+  ++h->gomp_evals;
+  if (mode != 1 && f) *f = r[0] / (double)m;
+  if (mode != 0 && g) {
+    const double sc = 2.0 / (double)m;
+    double R[9];
+    for (int i = 0; i < 3; ++i) g[i] = r[1 + i] * sc;
+    for (int i = 0; i < 9; ++i) R[i] = r[4 + i] * sc;
+    gomp_r_derivative(x, R, g);
+  }
+}
+
 // one functor evaluation at x over the pairs held: mode 0 f, 1 df, 2 fdf
 int gomp_evaluate(gorio_apd* h, const double* x, int mode, double* f, double* g) {
-  const int n = h->src->n, m = h->gomp_pairs;
+  const int n = h->src->n;
   const int nbx = (n + 255) / 256;
   float T[16];
   gomp_apply_state(x, T);
@@ -387,59 +491,75 @@ int gomp_evaluate(gorio_apd* h, const double* x, int mode, double* f, double* g)
   double r[13] = {0};
   HIP_TRY(h, hipMemcpyAsync(r, h->gomp_res, sizeof(r), hipMemcpyDeviceToHost, h->stream));
   HIP_TRY(h, hipStreamSynchronize(h->stream));
-  ++h->gomp_evals;
-  if (mode != 1 && f) *f = r[0] / (double)m;
-  if (mode != 0 && g) {
-    const double sc = 2.0 / (double)m;
-    double R[9];
-    for (int i = 0; i < 3; ++i) g[i] = r[1 + i] * sc;
-    for (int i = 0; i < 9; ++i) R[i] = r[4 + i] * sc;
-    gomp_r_derivative(x, R, g);
-  }
+  gomp_finish_evaluation(h, x, mode, r, f, g);
   return GORIO_OK;
 }
 
-// computeTransformation, GO:375-520
-int gomp_align(gorio_apd* h, const float* guess, float* T_out, double* H_out, int* converged, int* nr_iterations, int* n_linearize) {
-  if (!guess || !T_out) return GORIO_ERR_INVALID;
-  HIP_TRY(h, hipSetDevice(h->device));
-  int rc = gomp_prepare(h);
-  if (rc) return rc;
-  rc = gomp_set_guess(h, guess);
-  if (rc) return rc;
-  h->gomp_outer = 0; h->gomp_inner = 0; h->gomp_evals = 0; h->gomp_status = gorio_bfgs::kRunning;
-  float Tr[16], prev[16];
-  for (int i = 0; i < 16; ++i) Tr[i] = prev[i] = (i % 5 == 0) ? 1.f : 0.f;  // align(): transformation_ = previous_transformation_ = identity
+// computeTransformation, GO:375-520, as a machine that stops wherever it needs the device: for one pass of GO:411-476 at transformation_
+// (kUpdate), or for one functor evaluation of the BFGS inner solve (kEvaluate).  The caller answers with update_done() / evaluation_done().
+struct GompMachine {
+  enum State { kUpdate, kEvaluate, kFinished };
+  gorio_apd* h = nullptr;
+  State state = kFinished;
+  float guess[16], Tr[16], prev[16];
   bool conv = false;
   int nr = 0;
-  const gorio_apd_params& p = h->params;
-  int device_rc = GORIO_OK;
-  while (!conv) {
-    int m = 0;
-    rc = gomp_update(h, Tr, &m);
-    if (rc) return rc;
+  int mode = 0;  // of the evaluation wanted: 0 f, 1 df, 2 fdf
+  double x[6];   // where
+  gorio_bfgs::Machine bfgs;  // rho, sigma, tau1, tau2, tau3, order of GO:212-217 are the defaults of gorio_bfgs::Params
+
+  void begin(gorio_apd* handle, const float* g) {
+    h = handle;
+    for (int i = 0; i < 16; ++i) guess[i] = g[i];
+    h->gomp_outer = 0; h->gomp_inner = 0; h->gomp_evals = 0; h->gomp_status = gorio_bfgs::kRunning;
+    for (int i = 0; i < 16; ++i) Tr[i] = prev[i] = (i % 5 == 0) ? 1.f : 0.f;  // align(): transformation_ = previous_transformation_ = identity
+    conv = false;
+    nr = 0;
+    state = kUpdate;
+  }
+  bool done() const { return state == kFinished; }
+  // m = pairs of the update at Tr
+  void update_done(int m) {
     for (int i = 0; i < 16; ++i) prev[i] = Tr[i];  // GO:479
     if (m < 4) {  // NotEnoughPointsException, GO:187-191 -> break, GO:499-503
       h->err = "GICP_OMP: fewer than 4 correspondences";
-      break;
+      state = kFinished;
+      return;
     }
-    double x[6] = {(double)Tr[3], (double)Tr[7], (double)Tr[11], (double)(float)std::atan2((double)Tr[9], (double)Tr[10]), (double)(float)std::asin((double)-Tr[8]),
-                   (double)(float)std::atan2((double)Tr[4], (double)Tr[0])};  // GO:194-200, float results rounded once
-    gorio_bfgs::Callbacks cb;
-    cb.f = [&](const double* xx) { double f = NAN; if (!device_rc) device_rc = gomp_evaluate(h, xx, 0, &f, nullptr); return f; };
-    cb.df = [&](const double* xx, double* g) { for (int i = 0; i < 6; ++i) g[i] = NAN; if (!device_rc) device_rc = gomp_evaluate(h, xx, 1, nullptr, g); };
-    cb.fdf = [&](const double* xx, double* f, double* g) { *f = NAN; for (int i = 0; i < 6; ++i) g[i] = NAN; if (!device_rc) device_rc = gomp_evaluate(h, xx, 2, f, g); };
-    gorio_bfgs::Solver solver(cb);  // rho, sigma, tau1, tau2, tau3, order of GO:212-217 are the defaults of gorio_bfgs::Params
-    int inner = 0;
-    const int result = gorio_bfgs::minimize(solver, x, h->gomp_max_inner, 1e-2, &inner);
+    const double x0[6] = {(double)Tr[3], (double)Tr[7], (double)Tr[11], (double)(float)std::atan2((double)Tr[9], (double)Tr[10]), (double)(float)std::asin((double)-Tr[8]),
+                          (double)(float)std::atan2((double)Tr[4], (double)Tr[0])};  // GO:194-200, float results rounded once
+    bfgs.start(x0, h->gomp_max_inner, 1e-2);
+    next_request();
+  }
+  // f, g: the functor at x (what gomp_finish_evaluation makes of the sums)
+  void evaluation_done(double f, const double* g) {
+    bfgs.resume(f, g);
+    next_request();
+  }
+  void results(float* T_out, int* converged, int* nr_iterations, int* n_linearize) const {
+    gomp_mul4f(prev, guess, T_out);  // GO:516
+    if (converged) *converged = conv ? 1 : 0;
+    if (nr_iterations) *nr_iterations = nr;
+    if (n_linearize) *n_linearize = h->gomp_evals;
+  }
+
+ private:
+  void next_request() {
+    mode = bfgs.request(x);
+    if (mode != gorio_bfgs::Machine::kFinished) {
+      state = kEvaluate;
+      return;
+    }
+    const gorio_apd_params& p = h->params;
+    const int inner = bfgs.inner(), result = bfgs.status();
     h->gomp_inner += inner;
     h->gomp_status = result;
-    if (device_rc) return device_rc;
     if (!(result == gorio_bfgs::kNoProgress || result == gorio_bfgs::kSuccess || inner == h->gomp_max_inner)) {  // SolverDidntConvergeException, GO:243-245
       h->err = "GICP_OMP: BFGS solver didn't converge";
-      break;
+      state = kFinished;
+      return;
     }
-    gomp_apply_state(x, Tr);  // GO:240-241
+    gomp_apply_state(bfgs.x(), Tr);  // GO:240-241
     double delta = 0.;  // GO:485-497
     for (int k = 0; k < 4; ++k)
       for (int l = 0; l < 4; ++l) {
@@ -452,14 +572,221 @@ int gomp_align(gorio_apd* h, const float* guess, float* T_out, double* H_out, in
     if (nr >= p.max_iterations || delta < 1) {
       conv = true;
       for (int i = 0; i < 16; ++i) prev[i] = Tr[i];
+      state = kFinished;
+      return;
+    }
+    state = kUpdate;
+  }
+};
+
+int gomp_align(gorio_apd* h, const float* guess, float* T_out, double* H_out, int* converged, int* nr_iterations, int* n_linearize) {
+  if (!guess || !T_out) return GORIO_ERR_INVALID;
+  HIP_TRY(h, hipSetDevice(h->device));
+  int rc = gomp_prepare(h);
+  if (rc) return rc;
+  rc = gomp_set_guess(h, guess);
+  if (rc) return rc;
+  GompMachine mc;
+  mc.begin(h, guess);
+  while (!mc.done()) {
+    if (mc.state == GompMachine::kUpdate) {
+      int m = 0;
+      rc = gomp_update(h, mc.Tr, &m);
+      if (rc) return rc;
+      mc.update_done(m);
+    } else {
+      double f = NAN, g[6] = {NAN, NAN, NAN, NAN, NAN, NAN};
+      rc = gomp_evaluate(h, mc.x, mc.mode, &f, g);
+      if (rc) return rc;
+      mc.evaluation_done(f, g);
     }
   }
-  gomp_mul4f(prev, guess, T_out);  // GO:516
+  mc.results(T_out, converged, nr_iterations, n_linearize);
   if (H_out) std::memset(H_out, 0, sizeof(double) * 36);
-  if (converged) *converged = conv ? 1 : 0;
-  if (nr_iterations) *nr_iterations = nr;
-  if (n_linearize) *n_linearize = h->gomp_evals;
   resolve_stage_events(h);
+  return GORIO_OK;
+}
+
+// gorio_apd_gicp_omp_align_batch: N machines in lock-step.  Every round each unfinished handle has exactly one request pending; the
+// updates of a round share one search launch and one update launch, the evaluations one functor launch, everything one fold launch, one
+// copy back and one synchronisation.  The tables and the sums live in the lead handle (hs[0]), whose stream carries the rounds.
+int gomp_align_batch(gorio_apd** hs, int count, const float* guesses, float* T_out, int* converged, int* nr_iterations, int* n_evaluations) {
+  gorio_apd* lead = hs[0];
+  const bool pruned = lead->params.search == GORIO_SEARCH_PRUNED;
+  // ---- covariances and search indices: a cloud several handles hold is made once
+  int rc = GORIO_OK;
+  for (int q = 0; q < count; ++q) {
+    rc = ensure_points(hs[q], hs[q]->src->n);
+    if (rc) {
+      if (hs[q] != lead) lead->err = hs[q]->err;
+      return rc;
+    }
+  }
+  if (pruned) {  // the indices of ALL clouds of the batch in one call, as align_impl builds them
+    std::vector<std::pair<gorio_apd*, DevCloud*>> all;
+    for (int q = 0; q < count; ++q) {
+      all.emplace_back(hs[q], hs[q]->src.get());
+      all.emplace_back(hs[q], hs[q]->tgt.get());
+    }
+    rc = run_index_build(lead, all);
+    if (rc) return rc;
+  }
+  {
+    std::unordered_set<DevCloud*> seen;
+    std::vector<std::pair<gorio_apd*, DevCloud*>> stale;
+    for (int q = 0; q < count; ++q)
+      for (DevCloud* c : {hs[q]->src.get(), hs[q]->tgt.get()})
+        if (c->cov_count != c->n && seen.insert(c).second) stale.emplace_back(hs[q], c);
+    while (!stale.empty()) {  // run_covariances estimates with ONE gicp_epsilon, its lead's: one call per value
+      gorio_apd* first = stale.front().first;
+      std::vector<std::pair<gorio_apd*, DevCloud*>> todo, rest;
+      for (auto& t : stale) (t.first->gomp_eps == first->gomp_eps ? todo : rest).push_back(t);
+      rc = run_covariances(first, todo);
+      if (rc) {
+        if (first != lead) lead->err = first->err;
+        return rc;
+      }
+      stale.swap(rest);
+    }
+  }
+  size_t max_blocks = 0;
+  for (int q = 0; q < count; ++q) {
+    gorio_apd* h = hs[q];
+    rc = gomp_reserve(h);
+    if (!rc) rc = gomp_set_guess(h, guesses + (size_t)16 * q);
+    if (rc) {
+      if (h != lead) lead->err = h->err;
+      return rc;
+    }
+    HIP_TRY(lead, hipMemsetAsync(h->best_key, 0xff, sizeof(unsigned long long) * h->src->n, lead->stream));  // gomp_update_block re-arms it
+    max_blocks += (size_t)(h->src->n + 255) / 256;
+  }
+  if (max_blocks > (size_t)INT_MAX / 16) return fail(lead, GORIO_ERR_INVALID, "gicp_omp_align_batch: too many source points in one batch");
+  // ---- scratch for the largest possible round: every handle pending
+  rc = ensure_batch(lead, count);
+  if (rc) return rc;
+  const size_t table_bytes = sizeof(GompJob) * (size_t)count + sizeof(int2) * max_blocks;
+  const size_t out_bytes = (sizeof(double) * 13 + sizeof(int)) * (size_t)count;
+  HIP_TRY(lead, lead->gomp_b_jobs.reserve(table_bytes, table_bytes + table_bytes / 4));
+  HIP_TRY(lead, lead->gomp_b_part.reserve(13 * max_blocks, 13 * (max_blocks + max_blocks / 4)));
+  HIP_TRY(lead, lead->gomp_b_cnt.reserve(max_blocks, max_blocks + max_blocks / 4));
+  HIP_TRY(lead, lead->gomp_b_out.reserve(out_bytes, out_bytes + out_bytes / 4));
+  HIP_TRY(lead, lead->gomp_b_h_out.reserve(out_bytes, out_bytes + out_bytes / 4));
+  std::vector<GompMachine> mc(count);
+  for (int q = 0; q < count; ++q) mc[q].begin(hs[q], guesses + (size_t)16 * q);
+  std::vector<unsigned char> table(table_bytes);
+  std::vector<PairDesc> descs(count);
+  std::vector<PairState> states(count);
+  std::vector<int> order;
+  order.reserve(count);
+  int rounds = 0, launches = count;  // one gomp_output_kernel launch per handle so far
+  for (;;) {
+    // job k of the round belongs to handle order[k]: the updates first, then the evaluations
+    order.clear();
+    for (int q = 0; q < count; ++q)
+      if (mc[q].state == GompMachine::kUpdate) order.push_back(q);
+    const int n_upd = (int)order.size();
+    for (int q = 0; q < count; ++q)
+      if (mc[q].state == GompMachine::kEvaluate) order.push_back(q);
+    const int njobs = (int)order.size();
+    if (njobs == 0) break;
+    GompJob* const jobs = reinterpret_cast<GompJob*>(table.data());
+    int2* const wg = reinterpret_cast<int2*>(jobs + njobs);
+    long upd_waves = 0;
+    int upd_max_n = 0, upd_max_m = 0;
+    for (int k = 0; k < n_upd; ++k) {
+      upd_waves += (hs[order[k]]->src->n + 63) / 64;
+      upd_max_n = std::max(upd_max_n, hs[order[k]]->src->n);
+      upd_max_m = std::max(upd_max_m, hs[order[k]]->tgt->n);
+    }
+    int slot = 0, upd_blocks = 0, max_splits = 1;
+    for (int k = 0; k < njobs; ++k) {
+      gorio_apd* h = hs[order[k]];
+      const GompMachine& m = mc[order[k]];
+      const int n = h->src->n;
+      float* o = h->gomp_out;
+      const size_t st = h->gomp_out.cap() / 3;
+      GompJob& j = jobs[k];
+      std::memset(&j, 0, sizeof(j));
+      j.ox = o; j.oy = o + st; j.oz = o + 2 * st;
+      j.tgt = h->tgt->p4;
+      j.corr = h->corr;
+      j.maha = h->gomp_maha;
+      j.n = n;
+      j.n_tgt = h->tgt->n;
+      j.first = slot;
+      j.nblk = (n + 255) / 256;
+      if (k < n_upd) {
+        j.mode = 3;
+        j.best_key = h->best_key;
+        j.c1 = h->src->cov6;
+        j.c2 = h->tgt->cov6;
+        j.sqd = h->sqd;
+        j.R = gomp_make_r(h, m.Tr);
+        PairDesc& d = descs[k];
+        fill_desc(h, d, lead->d_states_batch + k, upd_waves);
+        d.src.x = o; d.src.y = o + st; d.src.z = o + 2 * st;  // the searches read the `output` copy
+        d.src.idx.s4 = h->gomp_s4;
+        max_splits = std::max(max_splits, d.nn_splits);
+        double Td[16];
+        for (int i = 0; i < 16; ++i) Td[i] = (double)m.Tr[i];
+        init_state(states[k], Td);
+        for (int i = 0; i < 12; ++i) states[k].Tf[i] = m.Tr[i];
+        upd_blocks += j.nblk;
+      } else {
+        j.mode = m.mode;
+        float T[16];
+        gomp_apply_state(m.x, T);
+        for (int i = 0; i < 12; ++i) j.tf.m[i] = T[i];
+      }
+      for (int b = 0; b < j.nblk; ++b) wg[slot + b] = make_int2(k, b);  // x < njobs, y < nblk: what the kernels rely on
+      slot += j.nblk;
+    }
+    const size_t bytes = sizeof(GompJob) * (size_t)njobs + sizeof(int2) * (size_t)slot;  // <= table_bytes
+    if (int rc2 = upload_staged(lead, lead->pin_gomp_jobs, lead->gomp_b_jobs, table.data(), bytes)) return rc2;
+    const GompJob* d_jobs = static_cast<const GompJob*>(lead->gomp_b_jobs.get());
+    const int2* d_wg = reinterpret_cast<const int2*>(d_jobs + njobs);
+    if (n_upd > 0) {
+      if (int rc2 = upload_staged(lead, lead->pin_desc, lead->d_desc, descs.data(), sizeof(PairDesc) * n_upd)) return rc2;
+      if (int rc2 = upload_staged(lead, lead->pin_states, lead->d_states_batch, states.data(), sizeof(PairState) * n_upd)) return rc2;
+      launch_nn(lead, lead->d_desc, dim3((upd_max_n + 255) / 256, max_splits, n_upd), roundup(upd_max_n, 512), n_upd, upd_max_m);
+      gomp_update_batch_kernel<<<upd_blocks, 256, 0, lead->stream>>>(d_jobs, d_wg, lead->gomp_b_cnt);
+      launches += 2;
+    }
+    if (slot > upd_blocks) {
+      gomp_functor_batch_kernel<<<slot - upd_blocks, 256, 0, lead->stream>>>(d_jobs, d_wg + upd_blocks, lead->gomp_b_part);
+      ++launches;
+    }
+    double* d_out = static_cast<double*>(lead->gomp_b_out.get());
+    int* d_pairs = reinterpret_cast<int*>(d_out + (size_t)13 * njobs);
+    gomp_fold_batch_kernel<<<njobs, 64, 0, lead->stream>>>(d_jobs, lead->gomp_b_part, lead->gomp_b_cnt, d_out, d_pairs);
+    ++launches;
+    HIP_TRY(lead, hipGetLastError());
+    HIP_TRY(lead, hipMemcpyAsync(lead->gomp_b_h_out.get(), d_out, (sizeof(double) * 13 + sizeof(int)) * (size_t)njobs, hipMemcpyDeviceToHost, lead->stream));
+    HIP_TRY(lead, hipStreamSynchronize(lead->stream));
+    const double* sums = static_cast<const double*>(lead->gomp_b_h_out.get());
+    const int* pairs = reinterpret_cast<const int*>(sums + (size_t)13 * njobs);
+    for (int k = 0; k < njobs; ++k) {
+      gorio_apd* h = hs[order[k]];
+      GompMachine& m = mc[order[k]];
+      if (k < n_upd) {
+        h->gomp_pairs = pairs[k];
+        h->corr_valid = true;
+        h->omega_valid = true;
+        m.update_done(pairs[k]);
+      } else {
+        double f = NAN, g[6] = {NAN, NAN, NAN, NAN, NAN, NAN};
+        gomp_finish_evaluation(h, m.x, m.mode, sums + (size_t)13 * k, &f, g);
+        m.evaluation_done(f, g);
+      }
+    }
+    ++rounds;
+  }
+  for (int q = 0; q < count; ++q)
+    mc[q].results(T_out + (size_t)16 * q, converged ? converged + q : nullptr, nr_iterations ? nr_iterations + q : nullptr, n_evaluations ? n_evaluations + q : nullptr);
+  lead->gomp_b_rounds = rounds;
+  lead->gomp_b_launches = launches;
+  resolve_stage_events(lead);
   return GORIO_OK;
 }
 
@@ -524,6 +851,46 @@ int gorio_apd_gicp_omp_diag(const gorio_apd_t* h, int* outer, int* inner_total, 
   if (inner_total) *inner_total = h->gomp_inner;
   if (evaluations) *evaluations = h->gomp_evals;
   if (last_status) *last_status = h->gomp_status;
+  return GORIO_OK;
+}
+
+int gorio_apd_gicp_omp_align_batch(gorio_apd_t** handles, int count, const float* guesses, float* T_out, int* converged, int* nr_iterations, int* n_evaluations) {
+  if (count == 0) return GORIO_OK;
+  if (count < 0 || !handles || !guesses || !T_out) return GORIO_ERR_INVALID;
+  for (int q = 0; q < count; ++q)
+    if (!handles[q]) return handles[0] ? fail(handles[0], GORIO_ERR_INVALID, "gicp_omp_align_batch: handle " + std::to_string(q) + " is null") : GORIO_ERR_INVALID;
+  gorio_apd* lead = handles[0];
+  // ---- validation: nothing is built, allocated or launched before every handle has passed
+  auto refuse = [&](int q, int code, const std::string& why) { return fail(lead, code, "gicp_omp_align_batch: handle " + std::to_string(q) + ": " + why); };
+  std::unordered_set<gorio_apd*> distinct;
+  for (int q = 0; q < count; ++q) {
+    gorio_apd* h = handles[q];
+    if (h->device != lead->device) return refuse(q, GORIO_ERR_INVALID, "all handles of a batch must live on one device");
+    if (!distinct.insert(h).second) return refuse(q, GORIO_ERR_INVALID, "the same handle appears twice in a batch (its buffers would be raced on)");
+    if (h->comm || (h->shard_only && h->comm_world > 1)) return refuse(q, GORIO_ERR_INVALID, "a handle with a communicator (sharded source) cannot be part of a batch");
+    if (h->method != GORIO_METHOD_GICP_OMP) return refuse(q, GORIO_ERR_STATE, "the handle's method is not GORIO_METHOD_GICP_OMP");
+    gorio_apd_params a = h->params, b = lead->params;
+    a.cl_weight_points = b.cl_weight_points = 0;
+    if (std::memcmp(&a, &b, sizeof(a)) != 0) return refuse(q, GORIO_ERR_INVALID, "all handles of a batch must carry the same parameters (cl_weight_points excepted)");
+  }
+  for (int q = 0; q < count; ++q) {
+    gorio_apd* h = handles[q];
+    const std::string kept = h->err;
+    const int rc = check_ready(h);
+    if (rc) {
+      const std::string why = h->err;
+      if (h != lead) h->err = kept;
+      return refuse(q, rc, why);
+    }
+  }
+  HIP_TRY(lead, hipSetDevice(lead->device));
+  return gomp_align_batch(handles, count, guesses, T_out, converged, nr_iterations, n_evaluations);
+}
+
+int gorio_apd_gicp_omp_batch_diag(const gorio_apd_t* lead, int* rounds, int* launches) {
+  if (!lead) return GORIO_ERR_INVALID;
+  if (rounds) *rounds = lead->gomp_b_rounds;
+  if (launches) *launches = lead->gomp_b_launches;
   return GORIO_OK;
 }
 

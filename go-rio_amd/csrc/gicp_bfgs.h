@@ -112,99 +112,63 @@ inline double interpolate(double a, double fa, double fpa, double b, double fb, 
   return a + z * (b - a);
 }
 
-class Solver {
+// The minimiser as a resumable machine: minimizeInit, then the loop of GO:219-235 (minimizeOneStep, testGradient, the iteration cap), suspended
+// wherever it needs the objective.  start() runs up to the first evaluation; request() names the evaluation wanted (kF, kDf, kFdf: the
+// modes of the device functor) and the point, or kFinished; resume() feeds the answer and runs on to the next evaluation or to the end.
+// The body is ONE function whose position is kept in pc_ (a switch with a case behind every suspension), so every local of the step and
+// of the line search is a member.  Solver / minimize() below answer the requests through callbacks; apd_gicp_omp.hip answers them from the
+// device, one handle at a time or many in lock-step.
+class Machine {
  public:
+  enum Request { kF = 0, kDf = 1, kFdf = 2, kFinished = 3 };
   Params parameters;
-  int evaluations = 0;  // callbacks made so far (each of f, df, fdf counts one)
 
-  explicit Solver(Callbacks cb) : cb_(std::move(cb)) {}
-
-  // minimizeInit (rule S)
-  int init(const double* x) {
-    iter_ = 0;
-    delta_f_ = 0.0;
-    for (int i = 0; i < N; ++i) dx_[i] = 0.0;
-    eval_fdf(x, &f_, g_);
-    for (int i = 0; i < N; ++i) { x0_[i] = x[i]; g0_[i] = g_[i]; x_[i] = x[i]; }
-    g0norm_ = norm6(g0_);
-    for (int i = 0; i < N; ++i) p_[i] = g_[i] * (-1.0 / g0norm_);
-    pnorm_ = norm6(p_);
-    fp0_ = -g0norm_;
-    change_direction();
-    return kSuccess;
+  void start(const double* x, int max_inner_iterations, double gradient_tol) {
+    for (int i = 0; i < N; ++i) { x_[i] = x[i]; xa_[i] = x[i]; }
+    max_inner_ = max_inner_iterations;
+    tol_ = gradient_tol;
+    pc_ = 0;
+    req_ = kFinished;
+    n_ = 0;
+    result_ = kRunning;
+    advance();
   }
-
-  // minimizeOneStep (rule T); x is read and, on kSuccess, replaced by the new iterate
-  int step(double* x) {
-    double alpha = 0.0, alpha1;
-    const double f0 = f_;
-    // (a NaN here -- a zero gradient at the start makes p = 0 / 0 -- is "no progress" too: every comparison below would be false)
-    if (pnorm_ == 0.0 || g0norm_ == 0.0 || fp0_ == 0.0 || std::isnan(pnorm_) || std::isnan(fp0_)) {
-      for (int i = 0; i < N; ++i) dx_[i] = 0.0;
-      return kNoProgress;
-    }
-    if (delta_f_ < 0.0) {
-      const double del = std::fmax(-delta_f_, 10.0 * DBL_EPSILON * std::fabs(f0));
-      alpha1 = std::fmin(1.0, 2.0 * del / (-fp0_));
-    } else {
-      alpha1 = std::fabs(parameters.step_size);
-    }
-    const int status = line_search(alpha1, &alpha);
-    if (status != kSuccess) return status;
-    // updatePosition: x, f, g at the accepted alpha (from the cache when the line search ended on a full evaluation)
-    {
-      double fa, dfa;
-      wrap_fdf(alpha, &fa, &dfa);
-      f_ = fa;
-      for (int i = 0; i < N; ++i) { x_[i] = xa_[i]; g_[i] = ga_[i]; x[i] = xa_[i]; }
-    }
-    if (!std::isfinite(f_)) return kFailed;
-    delta_f_ = f_ - f0;
-    {  // memoryless BFGS direction: p = g - A dx - B dg
-      double dx0[N], dg0[N];
-      for (int i = 0; i < N; ++i) { dx0[i] = x_[i] - x0_[i]; dx_[i] = dx0[i]; dg0[i] = g_[i] - g0_[i]; }
-      const double dxg = dot6(dx0, g_), dgg = dot6(dg0, g_), dxdg = dot6(dx0, dg0), dgnorm = norm6(dg0);
-      double A = 0.0, B = 0.0;
-      if (dxdg != 0.0) {
-        B = dxg / dxdg;
-        A = -(1.0 + dgnorm * dgnorm / dxdg) * B + dgg / dxdg;
-      }
-      for (int i = 0; i < N; ++i) p_[i] = g_[i] - A * dx0[i] - B * dg0[i];
-    }
-    for (int i = 0; i < N; ++i) { g0_[i] = g_[i]; x0_[i] = x_[i]; }
-    g0norm_ = norm6(g0_);
-    pnorm_ = norm6(p_);
-    const double pg = dot6(p_, g_);
-    const double dir = pg >= 0.0 ? -1.0 : 1.0;
-    for (int i = 0; i < N; ++i) p_[i] *= dir / pnorm_;
-    pnorm_ = norm6(p_);
-    fp0_ = dot6(p_, g0_);
-    change_direction();
-    ++iter_;
-    return kSuccess;
+  // the evaluation wanted: its mode, and the point in x (untouched when finished)
+  int request(double* x) const {
+    if (req_ != kFinished)
+      for (int i = 0; i < N; ++i) x[i] = xa_[i];
+    return req_;
   }
-
-  // testGradient (rule G)
-  int test_gradient(double epsilon) const {
-    if (epsilon < 0.0) return kFailed;
-    return norm6(g_) < epsilon ? kSuccess : kRunning;
+  // f is read for kF and kFdf, g (6 values) for kDf and kFdf
+  void resume(double f, const double* g) {
+    if (req_ == kFinished) return;
+    if (req_ != kDf) ans_f_ = f;
+    if (req_ != kF)
+      for (int i = 0; i < N; ++i) ans_g_[i] = g[i];
+    advance();
   }
-
+  bool finished() const { return req_ == kFinished; }
+  int status() const { return result_; }  // the last status of the loop of GO:219-235
+  int inner() const { return n_; }        // minimizeOneStep calls made
+  const double* x() const { return x_; }  // the iterate: the start until a step succeeds
   double value() const { return f_; }
   const double* gradient() const { return g_; }
 
  private:
-  Callbacks cb_;
+  int pc_ = 0, req_ = kFinished, max_inner_ = 0, n_ = 0, result_ = kRunning;
+  double tol_ = 0.0, ans_f_ = 0.0, ans_g_[N] = {0, 0, 0, 0, 0, 0};
   int iter_ = 0;
   double f_ = 0.0, delta_f_ = 0.0, fp0_ = 0.0, g0norm_ = 0.0, pnorm_ = 0.0;
   double x_[N], g_[N], x0_[N], g0_[N], p_[N], dx_[N];
   // the evaluation cache along x_ + alpha p_ (rule C)
   double xa_[N], ga_[N], f_alpha_ = 0.0, df_alpha_ = 0.0;
   double x_key_ = 0.0, f_key_ = 0.0, g_key_ = 0.0, df_key_ = 0.0;
-
-  double eval_f(const double* x) { ++evaluations; return cb_.f(x); }
-  void eval_df(const double* x, double* g) { ++evaluations; cb_.df(x, g); }
-  void eval_fdf(const double* x, double* f, double* g) { ++evaluations; cb_.fdf(x, f, g); }
+  // locals of minimizeOneStep (s_) and of the line search (l_)
+  double s_alpha_ = 0.0, s_alpha1_ = 0.0, s_f0_ = 0.0, s_fa_ = 0.0, s_dfa_ = 0.0;
+  int s_status_ = kSuccess;
+  double l_f0_ = 0.0, l_fp0_ = 0.0, l_falpha_ = 0.0, l_falpha_prev_ = 0.0, l_fpalpha_ = 0.0, l_fpalpha_prev_ = 0.0, l_delta_ = 0.0, l_alpha_next_ = 0.0;
+  double l_alpha_ = 0.0, l_alpha_prev_ = 0.0, l_a_ = 0.0, l_b_ = 0.0, l_fa_ = 0.0, l_fb_ = 0.0, l_fpa_ = 0.0, l_fpb_ = 0.0;
+  int l_i_ = 0;
 
   void change_direction() {
     for (int i = 0; i < N; ++i) { xa_[i] = x_[i]; ga_[i] = g_[i]; }
@@ -217,119 +181,254 @@ class Solver {
     for (int i = 0; i < N; ++i) xa_[i] = x_[i] + alpha * p_[i];
     x_key_ = alpha;
   }
-  double wrap_f(double alpha) {
-    if (alpha == f_key_) return f_alpha_;
-    move_to(alpha);
-    f_alpha_ = eval_f(xa_);
-    f_key_ = alpha;
-    return f_alpha_;
-  }
-  double wrap_df(double alpha) {
-    if (alpha == df_key_) return df_alpha_;
-    move_to(alpha);
-    if (alpha != g_key_) {
-      eval_df(xa_, ga_);
-      g_key_ = alpha;
-    }
-    df_alpha_ = dot6(ga_, p_);
-    df_key_ = alpha;
-    return df_alpha_;
-  }
-  void wrap_fdf(double alpha, double* f, double* df) {
-    if (alpha == f_key_ && alpha == df_key_) {
-      *f = f_alpha_;
-      *df = df_alpha_;
-      return;
-    }
-    if (alpha == f_key_ || alpha == df_key_) {
-      *f = wrap_f(alpha);
-      *df = wrap_df(alpha);
-      return;
-    }
-    move_to(alpha);
-    eval_fdf(xa_, &f_alpha_, ga_);
-    f_key_ = g_key_ = alpha;
-    df_alpha_ = dot6(ga_, p_);
-    df_key_ = alpha;
-    *f = f_alpha_;
-    *df = df_alpha_;
+  int test_gradient(double epsilon) const {  // testGradient (rule G)
+    if (epsilon < 0.0) return kFailed;
+    return norm6(g_) < epsilon ? kSuccess : kRunning;
   }
 
-  // Fletcher's bracketing and sectioning (rule L)
-  int line_search(double alpha1, double* alpha_new) {
+// suspend with a request for MODE at xa_; execution continues behind the case label with the answer in ans_f_ / ans_g_
+#define GORIO_BFGS_EVAL(MODE, LABEL) \
+  do {                               \
+    req_ = MODE;                     \
+    pc_ = LABEL;                     \
+    return;                          \
+    case LABEL:;                     \
+  } while (0)
+// the cached evaluations of rule C: OUT = f(A), OUT = f'(A), (F, DF) = both
+#define GORIO_BFGS_WRAP_F(A, OUT, LABEL) \
+  do {                                   \
+    if ((A) == f_key_) {                 \
+      OUT = f_alpha_;                    \
+    } else {                             \
+      move_to(A);                        \
+      GORIO_BFGS_EVAL(kF, LABEL);        \
+      f_alpha_ = ans_f_;                 \
+      f_key_ = (A);                      \
+      OUT = f_alpha_;                    \
+    }                                    \
+  } while (0)
+#define GORIO_BFGS_WRAP_DF(A, OUT, LABEL)                 \
+  do {                                                    \
+    if ((A) == df_key_) {                                 \
+      OUT = df_alpha_;                                    \
+    } else {                                              \
+      move_to(A);                                         \
+      if ((A) != g_key_) {                                \
+        GORIO_BFGS_EVAL(kDf, LABEL);                      \
+        for (int i = 0; i < N; ++i) ga_[i] = ans_g_[i];   \
+        g_key_ = (A);                                     \
+      }                                                   \
+      df_alpha_ = dot6(ga_, p_);                          \
+      df_key_ = (A);                                      \
+      OUT = df_alpha_;                                    \
+    }                                                     \
+  } while (0)
+#define GORIO_BFGS_WRAP_FDF(A, F, DF, L1, L2, L3)         \
+  do {                                                    \
+    if ((A) == f_key_ && (A) == df_key_) {                \
+      F = f_alpha_;                                       \
+      DF = df_alpha_;                                     \
+    } else if ((A) == f_key_ || (A) == df_key_) {         \
+      GORIO_BFGS_WRAP_F(A, F, L1);                        \
+      GORIO_BFGS_WRAP_DF(A, DF, L2);                      \
+    } else {                                              \
+      move_to(A);                                         \
+      GORIO_BFGS_EVAL(kFdf, L3);                          \
+      f_alpha_ = ans_f_;                                  \
+      for (int i = 0; i < N; ++i) ga_[i] = ans_g_[i];     \
+      f_key_ = g_key_ = (A);                              \
+      df_alpha_ = dot6(ga_, p_);                          \
+      df_key_ = (A);                                      \
+      F = f_alpha_;                                       \
+      DF = df_alpha_;                                     \
+    }                                                     \
+  } while (0)
+
+  void advance() {
     const double rho = parameters.rho, sigma = parameters.sigma, tau1 = parameters.tau1, tau2 = parameters.tau2, tau3 = parameters.tau3;
     const int order = parameters.order;
-    double f0, fp0, falpha, falpha_prev, fpalpha = 0.0, fpalpha_prev, delta, alpha_next;
-    double alpha = alpha1, alpha_prev = 0.0;
-    double a, b, fa, fb, fpa, fpb;
-    int i = 0;
-    wrap_fdf(0.0, &f0, &fp0);
-    falpha_prev = f0;
-    fpalpha_prev = fp0;
-    a = 0.0; b = alpha; fa = f0; fb = 0.0; fpa = fp0; fpb = 0.0;
-    while (i++ < parameters.bracket_iters) {
-      if (!std::isfinite(alpha)) return kFailed;
-      falpha = wrap_f(alpha);
-      if (std::isnan(falpha)) return kFailed;
-      if (falpha > f0 + alpha * rho * fp0 || falpha >= falpha_prev) {
-        a = alpha_prev; fa = falpha_prev; fpa = fpalpha_prev;
-        b = alpha; fb = falpha; fpb = NAN;
-        break;
-      }
-      fpalpha = wrap_df(alpha);
-      if (std::fabs(fpalpha) <= -sigma * fp0) {
-        *alpha_new = alpha;
-        return kSuccess;
-      }
-      if (fpalpha >= 0.0) {
-        a = alpha; fa = falpha; fpa = fpalpha;
-        b = alpha_prev; fb = falpha_prev; fpb = fpalpha_prev;
-        break;
-      }
-      delta = alpha - alpha_prev;
-      alpha_next = interpolate(alpha_prev, falpha_prev, fpalpha_prev, alpha, falpha, fpalpha, alpha + delta, alpha + tau1 * delta, order);
-      alpha_prev = alpha; falpha_prev = falpha; fpalpha_prev = fpalpha;
-      alpha = alpha_next;
+    switch (pc_) {
+      case 0:
+        // minimizeInit (rule S); start() has put the start into x_ and xa_
+        iter_ = 0;
+        delta_f_ = 0.0;
+        for (int i = 0; i < N; ++i) dx_[i] = 0.0;
+        GORIO_BFGS_EVAL(kFdf, 1);
+        f_ = ans_f_;
+        for (int i = 0; i < N; ++i) { g_[i] = ans_g_[i]; x0_[i] = x_[i]; g0_[i] = g_[i]; }
+        g0norm_ = norm6(g0_);
+        for (int i = 0; i < N; ++i) p_[i] = g_[i] * (-1.0 / g0norm_);
+        pnorm_ = norm6(p_);
+        fp0_ = -g0norm_;
+        change_direction();
+        // the loop of GO:219-235
+        n_ = 0;
+        result_ = kRunning;
+        do {
+          ++n_;
+          // minimizeOneStep (rule T)
+          s_alpha_ = 0.0;
+          s_f0_ = f_;
+          // (a NaN here -- a zero gradient at the start makes p = 0 / 0 -- is "no progress" too: every comparison below would be false)
+          if (pnorm_ == 0.0 || g0norm_ == 0.0 || fp0_ == 0.0 || std::isnan(pnorm_) || std::isnan(fp0_)) {
+            for (int i = 0; i < N; ++i) dx_[i] = 0.0;
+            result_ = kNoProgress;
+            break;
+          }
+          if (delta_f_ < 0.0) {
+            const double del = std::fmax(-delta_f_, 10.0 * DBL_EPSILON * std::fabs(s_f0_));
+            s_alpha1_ = std::fmin(1.0, 2.0 * del / (-fp0_));
+          } else {
+            s_alpha1_ = std::fabs(parameters.step_size);
+          }
+          // Fletcher's bracketing and sectioning (rule L): s_status_, and s_alpha_ where it accepts a point
+          l_fpalpha_ = 0.0;
+          l_alpha_ = s_alpha1_;
+          l_alpha_prev_ = 0.0;
+          l_i_ = 0;
+          GORIO_BFGS_WRAP_FDF(0.0, l_f0_, l_fp0_, 2, 3, 4);
+          l_falpha_prev_ = l_f0_;
+          l_fpalpha_prev_ = l_fp0_;
+          l_a_ = 0.0; l_b_ = l_alpha_; l_fa_ = l_f0_; l_fb_ = 0.0; l_fpa_ = l_fp0_; l_fpb_ = 0.0;
+          while (l_i_++ < parameters.bracket_iters) {
+            if (!std::isfinite(l_alpha_)) { s_status_ = kFailed; goto line_search_done; }
+            GORIO_BFGS_WRAP_F(l_alpha_, l_falpha_, 5);
+            if (std::isnan(l_falpha_)) { s_status_ = kFailed; goto line_search_done; }
+            if (l_falpha_ > l_f0_ + l_alpha_ * rho * l_fp0_ || l_falpha_ >= l_falpha_prev_) {
+              l_a_ = l_alpha_prev_; l_fa_ = l_falpha_prev_; l_fpa_ = l_fpalpha_prev_;
+              l_b_ = l_alpha_; l_fb_ = l_falpha_; l_fpb_ = NAN;
+              break;
+            }
+            GORIO_BFGS_WRAP_DF(l_alpha_, l_fpalpha_, 6);
+            if (std::fabs(l_fpalpha_) <= -sigma * l_fp0_) {
+              s_alpha_ = l_alpha_;
+              s_status_ = kSuccess;
+              goto line_search_done;
+            }
+            if (l_fpalpha_ >= 0.0) {
+              l_a_ = l_alpha_; l_fa_ = l_falpha_; l_fpa_ = l_fpalpha_;
+              l_b_ = l_alpha_prev_; l_fb_ = l_falpha_prev_; l_fpb_ = l_fpalpha_prev_;
+              break;
+            }
+            l_delta_ = l_alpha_ - l_alpha_prev_;
+            l_alpha_next_ = interpolate(l_alpha_prev_, l_falpha_prev_, l_fpalpha_prev_, l_alpha_, l_falpha_, l_fpalpha_, l_alpha_ + l_delta_, l_alpha_ + tau1 * l_delta_, order);
+            l_alpha_prev_ = l_alpha_; l_falpha_prev_ = l_falpha_; l_fpalpha_prev_ = l_fpalpha_;
+            l_alpha_ = l_alpha_next_;
+          }
+          while (l_i_++ < parameters.section_iters) {
+            l_delta_ = l_b_ - l_a_;
+            l_alpha_ = interpolate(l_a_, l_fa_, l_fpa_, l_b_, l_fb_, l_fpb_, l_a_ + tau2 * l_delta_, l_b_ - tau3 * l_delta_, order);
+            if (!std::isfinite(l_alpha_)) { s_status_ = kFailed; goto line_search_done; }
+            GORIO_BFGS_WRAP_F(l_alpha_, l_falpha_, 7);
+            if (std::isnan(l_falpha_)) { s_status_ = kFailed; goto line_search_done; }
+            if ((l_a_ - l_alpha_) * l_fpa_ <= DBL_EPSILON) { s_status_ = kNoProgress; goto line_search_done; }  // roundoff prevents progress
+            if (l_falpha_ > l_f0_ + rho * l_alpha_ * l_fp0_ || l_falpha_ >= l_fa_) {
+              l_b_ = l_alpha_; l_fb_ = l_falpha_; l_fpb_ = NAN;
+            } else {
+              GORIO_BFGS_WRAP_DF(l_alpha_, l_fpalpha_, 8);
+              if (std::fabs(l_fpalpha_) <= -sigma * l_fp0_) {
+                s_alpha_ = l_alpha_;
+                s_status_ = kSuccess;
+                goto line_search_done;
+              }
+              if (((l_b_ - l_a_) >= 0.0 && l_fpalpha_ >= 0.0) || ((l_b_ - l_a_) <= 0.0 && l_fpalpha_ <= 0.0)) {
+                l_b_ = l_a_; l_fb_ = l_fa_; l_fpb_ = l_fpa_;
+                l_a_ = l_alpha_; l_fa_ = l_falpha_; l_fpa_ = l_fpalpha_;
+              } else {
+                l_a_ = l_alpha_; l_fa_ = l_falpha_; l_fpa_ = l_fpalpha_;
+              }
+            }
+          }
+          s_status_ = kSuccess;  // iteration budget spent: s_alpha_ keeps its 0, the step re-evaluates at x and restarts along -g (rule L5)
+        line_search_done:
+          if (s_status_ != kSuccess) {
+            result_ = s_status_;
+            break;
+          }
+          // updatePosition: x, f, g at the accepted alpha (from the cache when the line search ended on a full evaluation)
+          GORIO_BFGS_WRAP_FDF(s_alpha_, s_fa_, s_dfa_, 9, 10, 11);
+          f_ = s_fa_;
+          for (int i = 0; i < N; ++i) { x_[i] = xa_[i]; g_[i] = ga_[i]; }
+          if (!std::isfinite(f_)) {
+            result_ = kFailed;
+            break;
+          }
+          delta_f_ = f_ - s_f0_;
+          {  // memoryless BFGS direction: p = g - A dx - B dg
+            double dx0[N], dg0[N];
+            for (int i = 0; i < N; ++i) { dx0[i] = x_[i] - x0_[i]; dx_[i] = dx0[i]; dg0[i] = g_[i] - g0_[i]; }
+            const double dxg = dot6(dx0, g_), dgg = dot6(dg0, g_), dxdg = dot6(dx0, dg0), dgnorm = norm6(dg0);
+            double A = 0.0, B = 0.0;
+            if (dxdg != 0.0) {
+              B = dxg / dxdg;
+              A = -(1.0 + dgnorm * dgnorm / dxdg) * B + dgg / dxdg;
+            }
+            for (int i = 0; i < N; ++i) p_[i] = g_[i] - A * dx0[i] - B * dg0[i];
+            for (int i = 0; i < N; ++i) { g0_[i] = g_[i]; x0_[i] = x_[i]; }
+            g0norm_ = norm6(g0_);
+            pnorm_ = norm6(p_);
+            const double pg = dot6(p_, g_);
+            const double dir = pg >= 0.0 ? -1.0 : 1.0;
+            for (int i = 0; i < N; ++i) p_[i] *= dir / pnorm_;
+            pnorm_ = norm6(p_);
+            fp0_ = dot6(p_, g0_);
+          }
+          change_direction();
+          ++iter_;
+          result_ = test_gradient(tol_);
+        } while (result_ == kRunning && n_ < max_inner_);
+        req_ = kFinished;
+        pc_ = 12;
+        return;
+      case 12:
+      default:
+        req_ = kFinished;
+        return;
     }
-    while (i++ < parameters.section_iters) {
-      delta = b - a;
-      alpha = interpolate(a, fa, fpa, b, fb, fpb, a + tau2 * delta, b - tau3 * delta, order);
-      if (!std::isfinite(alpha)) return kFailed;
-      falpha = wrap_f(alpha);
-      if (std::isnan(falpha)) return kFailed;
-      if ((a - alpha) * fpa <= DBL_EPSILON) return kNoProgress;  // roundoff prevents progress
-      if (falpha > f0 + rho * alpha * fp0 || falpha >= fa) {
-        b = alpha; fb = falpha; fpb = NAN;
-      } else {
-        fpalpha = wrap_df(alpha);
-        if (std::fabs(fpalpha) <= -sigma * fp0) {
-          *alpha_new = alpha;
-          return kSuccess;
-        }
-        if (((b - a) >= 0.0 && fpalpha >= 0.0) || ((b - a) <= 0.0 && fpalpha <= 0.0)) {
-          b = a; fb = fa; fpb = fpa;
-          a = alpha; fa = falpha; fpa = fpalpha;
-        } else {
-          a = alpha; fa = falpha; fpa = fpalpha;
-        }
-      }
-    }
-    return kSuccess;  // iteration budget spent: *alpha_new keeps the caller's 0, the step re-evaluates at x and restarts along -g (rule L5)
   }
+#undef GORIO_BFGS_WRAP_FDF
+#undef GORIO_BFGS_WRAP_DF
+#undef GORIO_BFGS_WRAP_F
+#undef GORIO_BFGS_EVAL
+};
+
+// The machine answered through callbacks.  `evaluations` counts the callbacks made (each of f, df, fdf counts one).
+class Solver {
+ public:
+  Params parameters;
+  int evaluations = 0;
+
+  explicit Solver(Callbacks cb) : cb_(std::move(cb)) {}
+
+  double value() const { return m_.value(); }
+  const double* gradient() const { return m_.gradient(); }
+
+  // runs the machine from x to its end; x becomes the final iterate
+  int run(double* x, int max_inner_iterations, double gradient_tol, int* inner) {
+    m_.parameters = parameters;
+    m_.start(x, max_inner_iterations, gradient_tol);
+    double xe[N], f, g[N];
+    for (;;) {
+      const int mode = m_.request(xe);
+      if (mode == Machine::kFinished) break;
+      ++evaluations;
+      f = 0.0;
+      if (mode == Machine::kF) f = cb_.f(xe);
+      else if (mode == Machine::kDf) cb_.df(xe, g);
+      else cb_.fdf(xe, &f, g);
+      m_.resume(f, g);
+    }
+    for (int i = 0; i < N; ++i) x[i] = m_.x()[i];
+    *inner = m_.inner();
+    return m_.status();
+  }
+
+ private:
+  Callbacks cb_;
+  Machine m_;
 };
 
 // The loop of GO:219-235 around the solver: returns the last status, `inner` = minimizeOneStep calls made.
-inline int minimize(Solver& s, double* x, int max_inner_iterations, double gradient_tol, int* inner) {
-  s.init(x);
-  int n = 0, result = kRunning;
-  do {
-    ++n;
-    result = s.step(x);
-    if (result) break;
-    result = s.test_gradient(gradient_tol);
-  } while (result == kRunning && n < max_inner_iterations);
-  *inner = n;
-  return result;
-}
+inline int minimize(Solver& s, double* x, int max_inner_iterations, double gradient_tol, int* inner) { return s.run(x, max_inner_iterations, gradient_tol, inner); }
 
 }  // namespace gorio_bfgs

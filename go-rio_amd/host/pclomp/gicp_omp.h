@@ -7,7 +7,9 @@
 // Mahalanobis matrices, so it only works from inside computeTransformation: a direct call is refused (std::logic_error).  setUseReciprocalCorrespondences
 // (registrations.cpp:96) is accepted and unused, as GO never reads it.  getFitnessScore runs on the GPU as in the fast_gicp drop-ins.
 // Extras without a counterpart in the reference: setInputSourceFromScan / setInputTargetFromScan, setInputSourceKeyframe /
-// setInputTargetKeyframe, handle().
+// setInputTargetKeyframe, handle(), and the batch surface in the shape of pclomp/ndt_omp.h: setInputTargetShared, alignBatch
+// (gorio_apd_gicp_omp_align_batch: the aligns of many objects in lock-step rounds, every result bit for bit the single align's),
+// getFitnessScoreBatch.
 #pragma once
 #include <cfloat>
 #include <cmath>
@@ -88,6 +90,16 @@ class GeneralizedIterativeClosestPoint : public pcl::Registration<PointSource, P
     pairs_valid_ = false;
   }
   void setTargetCovariances(const MatricesVectorPtr& covariances) { target_covariances_ = covariances; }  // GOH:185-189
+  // The target of `owner` as this object's target (extra): the device cloud, its covariances and its search index are shared, nothing is
+  // uploaded or estimated twice.  The loop-closure shape: N candidate objects on one keyframe's target, then alignBatch.
+  void setInputTargetShared(GeneralizedIterativeClosestPoint& owner) {
+    push_params();
+    owner.push_params();
+    check(gorio_apd_set_target_shared(h_, owner.h_), "setInputTargetShared");
+    Base::setInputTarget(owner.target_);
+    target_covariances_.reset();
+    pairs_valid_ = false;
+  }
 
   // The frame a gorio::ScanPreprocessor just produced / a keyframe resident in a gorio::KeyframeStore as source or target (extras): the
   // handle shares the device cloud and its search index, nothing is uploaded; the host cloud becomes input_ / target_.
@@ -188,6 +200,64 @@ class GeneralizedIterativeClosestPoint : public pcl::Registration<PointSource, P
     double score = 0.0;
     check(gorio_apd_fitness_score(h_, T, max_range, 0.0, &score, nullptr), "getFitnessScore");
     pairs_valid_ = false;  // the score's search replaced the correspondences held
+    return score;
+  }
+  // regs[i]->align(outputs[i], guesses[i]) for every i through ONE gorio_apd_gicp_omp_align_batch (extra): afterwards every object is in
+  // the state its own align leaves (hasConverged, getFinalTransformation, getIterationCounts, mahalanobis), bit for bit.  The objects must
+  // carry the same pcl::Registration settings, rotation epsilon and correspondence randomness; the optimizer iterations may differ.
+  static void alignBatch(const std::vector<GeneralizedIterativeClosestPoint*>& regs, const std::vector<typename Base::Matrix4>& guesses, std::vector<PointCloudSource>* outputs = nullptr) {
+    if (regs.size() != guesses.size()) throw std::invalid_argument("pclomp::GeneralizedIterativeClosestPoint::alignBatch: one guess per object");
+    const std::size_t count = regs.size();
+    for (std::size_t i = 0; i < count; ++i) {
+      if (!regs[i]) throw std::invalid_argument("pclomp::GeneralizedIterativeClosestPoint::alignBatch: null object");
+      if (!regs[i]->input_ || !regs[i]->target_) throw std::runtime_error("pclomp::GeneralizedIterativeClosestPoint::alignBatch: object " + std::to_string(i) + " has no source or no target");
+    }
+    if (outputs) outputs->resize(count);
+    if (count == 0) return;
+    std::vector<gorio_apd_t*> hs(count);
+    std::vector<float> G(count * 16), T(count * 16);
+    std::vector<int> conv(count), nr(count);
+    for (std::size_t i = 0; i < count; ++i) {
+      GeneralizedIterativeClosestPoint& o = *regs[i];
+      o.push_params();
+      o.upload_covariances(o.input_covariances_, true);
+      o.upload_covariances(o.target_covariances_, false);
+      hs[i] = o.h_;
+      for (int r = 0; r < 4; ++r)
+        for (int c = 0; c < 4; ++c) G[i * 16 + 4 * r + c] = guesses[i](r, c);
+    }
+    regs[0]->check(gorio_apd_gicp_omp_align_batch(hs.data(), (int)count, G.data(), T.data(), conv.data(), nr.data(), nullptr), "alignBatch");
+    for (std::size_t i = 0; i < count; ++i) {
+      GeneralizedIterativeClosestPoint& o = *regs[i];
+      o.mahalanobis_.clear();
+      for (int r = 0; r < 4; ++r)
+        for (int c = 0; c < 4; ++c) o.final_transformation_(r, c) = T[i * 16 + 4 * r + c];
+      o.converged_ = conv[i] != 0;
+      o.nr_iterations_ = nr[i];
+      o.pairs_valid_ = true;
+      if (outputs) {
+        PointCloudSource& out = (*outputs)[i];
+        const int n = (int)o.input_->size();
+        if ((int)out.size() != n) out.points = o.input_->points;
+        if (n > 0) o.check(gorio_apd_transform_source(o.h_, &T[i * 16], out.points[0].data, n, (int)sizeof(PointSource)), "alignBatch");
+      }
+    }
+  }
+  // getFitnessScore of every object at its own final transformation through ONE gorio_apd_fitness_score_batch (extra)
+  static std::vector<double> getFitnessScoreBatch(const std::vector<GeneralizedIterativeClosestPoint*>& regs, double max_range = std::numeric_limits<double>::max()) {
+    std::vector<double> score(regs.size());
+    if (regs.empty()) return score;
+    std::vector<gorio_apd_t*> hs(regs.size());
+    std::vector<float> T(regs.size() * 16);
+    for (std::size_t i = 0; i < regs.size(); ++i) {
+      if (!regs[i]) throw std::invalid_argument("pclomp::GeneralizedIterativeClosestPoint::getFitnessScoreBatch: null object");
+      if (!regs[i]->input_ || !regs[i]->target_) throw std::logic_error("pclomp::GeneralizedIterativeClosestPoint::getFitnessScoreBatch: no source or no target");
+      hs[i] = regs[i]->h_;
+      for (int r = 0; r < 4; ++r)
+        for (int c = 0; c < 4; ++c) T[i * 16 + 4 * r + c] = regs[i]->final_transformation_(r, c);
+    }
+    regs[0]->check(gorio_apd_fitness_score_batch(hs.data(), (int)regs.size(), T.data(), max_range, 0.0, score.data(), nullptr), "getFitnessScoreBatch");
+    for (std::size_t i = 0; i < regs.size(); ++i) regs[i]->pairs_valid_ = false;  // the score's search replaced the correspondences held
     return score;
   }
   // outer iterations, minimizeOneStep calls and functor evaluations of the last align (extra: gorio_apd_gicp_omp_diag)

@@ -120,7 +120,8 @@ int gorio_apd_get_method(const gorio_apd_t* h, int* method, double* voxel_resolu
  *     trip.  H_out is zero-filled; n_linearize = functor evaluations.  max_iterations, transformation_epsilon, rotation_epsilon,
  *     corr_dist_threshold, k_correspondences and search of gorio_apd_params are read, nothing else of it.  Fewer than 4 pairs, or a solver
  *     status other than Success / NoProgress before the inner cap, ends the align unconverged with previous_transformation_ * guess;
- *   - gorio_apd_linearize, gorio_apd_compute_error and gorio_apd_align_batch return GORIO_ERR_UNSUPPORTED (align_batch changes nothing);
+ *   - gorio_apd_linearize, gorio_apd_compute_error and gorio_apd_align_batch return GORIO_ERR_UNSUPPORTED (align_batch changes nothing;
+ *     gorio_apd_gicp_omp_align_batch below is the batched form);
  *     the sharded-source calls return GORIO_ERR_STATE; everything else of this header works as in the other modes.
  * gicp_epsilon = gicp_epsilon_ (default 0.001, GOH:118), max_optimizer_iterations = setMaximumOptimizerIterations (default 20, GOH:121;
  * REG:99).  GORIO_ERR_INVALID for gicp_epsilon <= 0 and max_optimizer_iterations < 1.  Stored in every mode.
@@ -136,6 +137,36 @@ int gorio_apd_get_gicp_omp_params(const gorio_apd_t* h, double* gicp_epsilon, in
 int gorio_apd_gicp_omp_update(gorio_apd_t* h, const float transformation16[16], const float guess16[16], int* m);
 int gorio_apd_gicp_omp_evaluate(gorio_apd_t* h, const double x6[6], int mode, double* f, double* g6);
 int gorio_apd_gicp_omp_diag(const gorio_apd_t* h, int* outer, int* inner_total, int* evaluations, int* last_status);
+/*
+ * Batched GICP_OMP aligns: the aligns of `count` handles in lock-step rounds.  Every handle runs the machine its own gorio_apd_align runs
+ * (one pass of GO:411-476, then the BFGS inner solve, suspended at every functor evaluation); in every round each unfinished handle has
+ * exactly one request pending, an update or an evaluation.  Per round: one search launch and one update launch when any update is pending,
+ * one functor launch when any evaluation is pending, one launch that adds every request's block sums in block order, one copy back, one
+ * synchronisation -- on the stream and with the tables of handles[0].  guesses / T_out: count x 16 row-major floats; converged,
+ * nr_iterations, n_evaluations: count ints each, any may be NULL.
+ *   - gorio_apd_align_batch is unchanged: it keeps returning GORIO_ERR_UNSUPPORTED for these handles.  The batched BFGS has an entry
+ *     point of its own because its shell is not the Gauss-Newton / LM one.
+ *   - count == 0 returns GORIO_OK.  count < 0, a null array or a null entry: GORIO_ERR_INVALID.  The same handle twice, handles on two
+ *     devices, a handle with a communicator, gorio_apd_params that differ between handles (cl_weight_points excepted, as for
+ *     gorio_apd_align_batch): GORIO_ERR_INVALID.  A handle whose method is not GORIO_METHOD_GICP_OMP: GORIO_ERR_STATE.  A handle that is
+ *     not ready (no source or target, a cloud smaller than k_correspondences, a shared cloud estimated by another rule / k / epsilon):
+ *     that handle's own code.  All of it is checked before anything is built or launched; the message on handles[0] names the offending
+ *     index ("handle <q>: ..."), and no handle is changed.
+ *   - gicp_epsilon and max_optimizer_iterations are per handle and may differ within a batch.
+ *   - targets and sources may be shared between the handles (gorio_apd_set_target_shared, keyframe and scan hand-offs): a shared cloud's
+ *     index and covariances are made once per batch.
+ *   - an align that ends early is not a failed call: "fewer than 4 correspondences" and "BFGS solver didn't converge" end that handle alone
+ *     with converged[q] = 0 and its own error string, as gorio_apd_align does; the call still returns GORIO_OK.
+ *   - after the call every handle holds what its own gorio_apd_align would have left: correspondences, squared distances, Mahalanobis
+ *     matrices, the pairs, and the four gorio_apd_gicp_omp_diag values; the parity hooks work on that state.
+ *   - T_out, converged, nr_iterations and n_evaluations are bit for bit those of gorio_apd_align on the same handle, in both search modes:
+ *     the per-workgroup bodies of the kernels and the order of every sum are the single align's.
+ * gorio_apd_gicp_omp_batch_diag, of the last batch led by `lead` (its handles[0]): rounds = lock-step rounds (the longest member's updates
+ * plus evaluations), launches = kernel launches of the batch (one `output` launch per handle, then at most four per round).
+ */
+int gorio_apd_gicp_omp_align_batch(gorio_apd_t** handles, int count, const float* guesses /* count x 16 */, float* T_out /* count x 16 */,
+                                   int* converged, int* nr_iterations, int* n_evaluations /* each count, may be NULL */);
+int gorio_apd_gicp_omp_batch_diag(const gorio_apd_t* lead, int* rounds, int* launches);
 
 /* parity hooks (VGICP mode; they build the map when it is stale): voxelmap_ (VGH:85) as arrays over the occupied voxels in ascending
  * lexicographic (x, y, z) coordinate order -- coord3: 3 ints, num_points, mean4: GaussianVoxel::mean, cov16: GaussianVoxel::cov row-major
