@@ -40,4 +40,6 @@ from . import keyframes  # noqa: E402
 from .keyframes import KF_SYMBOLS, KeyframeStore  # noqa: E402
 from . import map_cloud  # noqa: E402
 from .map_cloud import MAP_SYMBOLS, MapCloud  # noqa: E402
+from . import search  # noqa: E402
+from .search import SEARCH_SYMBOLS, Search  # noqa: E402
 from .ugpm import PreintOption, PreintPrior, UgpmBatch, VelPreintegration, ugpm_combine_preints, ugpm_preint_batch, ugpm_stage_times  # noqa: E402

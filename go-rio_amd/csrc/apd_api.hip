@@ -2145,3 +2145,5 @@ extern "C" int gorio_debug_search_stats(unsigned long long out[24], int reset) {
 #include "../../include/gorio_map.h"
 #include "apd_map.hip"
 #include "apd_gicp_omp.hip"
+#include "../../include/gorio_search.h"
+#include "apd_search.hip"

@@ -49,7 +49,8 @@
  *
  * Out of scope: KDTREE search (a radius search over leaf centroids: another structure; REG:127-133 selects it only on request, it
  * is refused with GORIO_ERR_UNSUPPORTED), RCCL sharding, and PCL's single-thread pcl::NormalDistributionsTransform (REG:111: the same
- * algorithm with KDTREE only).
+ * algorithm with KDTREE only).  The structure a KDTREE mode needs exists now -- exact radius queries of arbitrary points against a
+ * device-resident cloud, include/gorio_search.h -- but nothing here is wired to it: KDTREE stays refused.
  */
 #ifndef GORIO_NDT_H
 #define GORIO_NDT_H
