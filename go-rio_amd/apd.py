@@ -55,10 +55,11 @@ APD_SYMBOLS = [
     "gorio_apd_set_method", "gorio_apd_get_method", "gorio_apd_get_voxelmap", "gorio_apd_get_voxel_correspondences",
     "gorio_apd_set_gicp_omp_params", "gorio_apd_get_gicp_omp_params", "gorio_apd_gicp_omp_update", "gorio_apd_gicp_omp_evaluate", "gorio_apd_gicp_omp_diag",
     "gorio_apd_gicp_omp_align_batch", "gorio_apd_gicp_omp_batch_diag",
+    "gorio_apd_set_icp_params", "gorio_apd_get_icp_params", "gorio_apd_icp_diag", "gorio_apd_icp_step", "gorio_apd_icp_align_batch", "gorio_apd_icp_batch_diag",
 ]
 
 # gorio_method / gorio_voxel_search / gorio_voxel_mode of gorio_apd.h (the latter two in the order of gicp_settings.hpp)
-METHOD_APDGICP, METHOD_GICP, METHOD_VGICP, METHOD_GICP_OMP = 0, 1, 2, 3
+METHOD_APDGICP, METHOD_GICP, METHOD_VGICP, METHOD_GICP_OMP, METHOD_ICP = 0, 1, 2, 3, 4
 GICP_OMP_F, GICP_OMP_DF, GICP_OMP_FDF = 0, 1, 2  # modes of gorio_apd_gicp_omp_evaluate
 VOXEL_DIRECT27, VOXEL_DIRECT7, VOXEL_DIRECT1, VOXEL_DIRECT_RADIUS = 0, 1, 2, 3
 VOXEL_ADDITIVE, VOXEL_ADDITIVE_WEIGHTED, VOXEL_MULTIPLICATIVE = 0, 1, 2
@@ -160,6 +161,28 @@ class ApdGicp:
         o, i, e, s = C.c_int(0), C.c_int(0), C.c_int(0), C.c_int(0)
         _check(self._h, self._lib.gorio_apd_gicp_omp_diag(self._h, C.byref(o), C.byref(i), C.byref(e), C.byref(s)))
         return dict(outer=o.value, inner_total=i.value, evaluations=e.value, last_status=s.value)
+
+    # ---- ICP (METHOD_ICP): the setters of pcl::IterativeClosestPoint that gorio_apd_params does not carry, and the parity hooks
+    def set_icp_params(self, use_reciprocal=False, euclidean_fitness_epsilon=-np.finfo(np.float64).max, transformation_rotation_epsilon=0.0):
+        _check(self._h, self._lib.gorio_apd_set_icp_params(self._h, int(bool(use_reciprocal)), C.c_double(euclidean_fitness_epsilon), C.c_double(transformation_rotation_epsilon)))
+
+    def get_icp_params(self):
+        r, f, t = C.c_int(0), C.c_double(0.0), C.c_double(0.0)
+        _check(self._h, self._lib.gorio_apd_get_icp_params(self._h, C.byref(r), C.byref(f), C.byref(t)))
+        return dict(use_reciprocal=bool(r.value), euclidean_fitness_epsilon=f.value, transformation_rotation_epsilon=t.value)
+
+    def icp_step(self, T=None):
+        """gorio_apd_icp_step: one correspondence pass on T * source -> dict(pairs, sums [17], T_est [4, 4]); getCorrespondences() gives the pairs."""
+        T = np.ascontiguousarray(np.eye(4) if T is None else T, np.float32)
+        m, sums, est = C.c_int(0), np.zeros(17, np.float64), np.zeros((4, 4), np.float32)
+        _check(self._h, self._lib.gorio_apd_icp_step(self._h, _p(T, C.c_float), C.byref(m), _p(sums, C.c_double), _p(est, C.c_float)))
+        return dict(pairs=m.value, sums=sums, T_est=est)
+
+    def icp_diag(self):
+        """gorio_apd_icp_diag of the last align: iterations, ConvergenceState, mean squared pair distance, pairs of the last pass."""
+        i, s, p, e = C.c_int(0), C.c_int(0), C.c_int(0), C.c_double(0.0)
+        _check(self._h, self._lib.gorio_apd_icp_diag(self._h, C.byref(i), C.byref(s), C.byref(e), C.byref(p)))
+        return dict(iterations=i.value, state=s.value, mse=e.value, pairs=p.value)
 
     def getVoxelMap(self):  # noqa: N802 -- parity hook: voxelmap_ (fast_vgicp.hpp:85), voxels in ascending (x, y, z) coordinate order
         nv = C.c_int(0)
@@ -558,6 +581,34 @@ def gicp_omp_align_batch(objs, guesses=None):
         o._final = T[q]
         o._converged = bool(conv[q])
         out.append(dict(T=T[q], H=np.zeros((6, 6), np.float64), converged=bool(conv[q]), nr_iterations=int(nit[q]), n_linearize=int(nev[q]), batch_diag=dict(diag)))
+    return out
+
+
+def icp_align_batch(objs, guesses=None):
+    """gorio_apd_icp_align_batch over a list of ApdGicp objects in ICP mode (all on one device): their aligns in lock-step rounds, every
+    result bit for bit the one of the object's own align().  Returns the list of dicts align() returns (n_linearize = the object's
+    correspondence passes), each with batch_diag = dict(rounds, launches) of the whole batch.  An empty list makes no call."""
+    n = len(objs)
+    if n == 0:
+        return []
+    lib = load_library()
+    g = np.ascontiguousarray(np.tile(np.eye(4, dtype=np.float32), (n, 1, 1)) if guesses is None else guesses, np.float32).reshape(n, 16)
+    T = np.zeros((n, 4, 4), np.float32)
+    conv = np.zeros(n, np.int32)
+    nit = np.zeros(n, np.int32)
+    arr = (C.c_void_p * n)(*[o._h for o in objs])
+    rc = lib.gorio_apd_icp_align_batch(arr, n, _p(g, C.c_float), _p(T, C.c_float), _p(conv, C.c_int), _p(nit, C.c_int))
+    _check(objs[0]._h, rc)
+    rounds, launches = C.c_int(0), C.c_int(0)
+    _check(objs[0]._h, lib.gorio_apd_icp_batch_diag(objs[0]._h, C.byref(rounds), C.byref(launches)))
+    diag = dict(rounds=rounds.value, launches=launches.value)
+    out = []
+    for q, o in enumerate(objs):
+        o._final = T[q]
+        o._converged = bool(conv[q])
+        d = o.icp_diag()  # passes = iterations, plus the pass that found fewer than 3 pairs (state 5) when the align ended there
+        out.append(dict(T=T[q], H=np.zeros((6, 6), np.float64), converged=bool(conv[q]), nr_iterations=int(nit[q]), n_linearize=d["iterations"] + (d["state"] == 5),
+                        batch_diag=dict(diag)))
     return out
 
 

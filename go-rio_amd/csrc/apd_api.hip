@@ -166,6 +166,21 @@ struct gorio_apd {
   DevBuf<int> gomp_b_cnt;
   PinnedBuf gomp_b_h_out;
   int gomp_b_rounds = 0, gomp_b_launches = 0;  // gorio_apd_gicp_omp_batch_diag
+  // ICP (GORIO_METHOD_ICP, apd_icp.hip): use_reciprocal_correspondences_, euclidean_fitness_epsilon_ and transformation_rotation_epsilon_ of
+  // pcl::IterativeClosestPoint, the moved working copy in original order (x, y, z) and in the source's search-index order, the reciprocal flags
+  int icp_reciprocal = 0;
+  double icp_fit_eps = -DBL_MAX, icp_rot_eps = 0.0;
+  DevBuf<float> icp_w;                // these three: one group of capacity icp_cap (source points)
+  DevBuf<float4> icp_s4;
+  DevBuf<int> icp_rflag;
+  int icp_cap = 0;
+  int icp_iterations = 0, icp_state = 0, icp_pairs = -1, icp_passes = 0;  // gorio_apd_icp_diag
+  double icp_mse = 0.0;
+  // owned by the handle that leads the rounds: job and workgroup table, block partials, the folded sums on the device and pinned on the host
+  DevBuf<void> icp_b_jobs, icp_b_out;
+  DevBuf<double> icp_b_part;
+  PinnedBuf icp_b_h_out;
+  int icp_b_rounds = 0, icp_b_launches = 0;  // gorio_apd_icp_batch_diag
   DevBuf<PairState> d_state;
   DevBuf<PairDesc> d_desc;   // batch descriptor array and states (owned by the handle that leads a batch): one group of capacity desc_cap
   DevBuf<PairState> d_states_batch;
@@ -200,7 +215,7 @@ struct gorio_apd {
       if (ev) hipEventDestroy(ev);
     }
   };
-  Pinned pin_ijobs, pin_jobs, pin_desc, pin_states, pin_copy, pin_vox, pin_gomp_jobs;
+  Pinned pin_ijobs, pin_jobs, pin_desc, pin_states, pin_copy, pin_vox, pin_gomp_jobs, pin_icp_jobs;
   PinnedBuf pin_looks;  // where the align loop's looks at the pair states land (a download into pageable memory is staged by the runtime)
   std::string err;
   // profiling
@@ -248,6 +263,8 @@ int roundup(int v, int m) { return (v + m - 1) / m * m; }
 constexpr int kRegGicpOmp = 100;  // DevCloud::cov_reg of covariances estimated by the rule of GO:50-122: one more "regularization" for sharing
 int gomp_align(gorio_apd* h, const float* guess, float* T_out, double* H_out, int* converged, int* nr_iterations, int* n_linearize);
 int gomp_covariances(gorio_apd* lead, std::vector<std::pair<gorio_apd*, DevCloud*>>& todo);
+// ICP (apd_icp.hip, included at the end of this file)
+int icp_align(gorio_apd* h, const float* guess, float* T_out, double* H_out, int* converged, int* nr_iterations, int* n_linearize);
 // the rule a handle estimates covariances by, and whether covariances estimated with (k, reg, eps) are the ones it would estimate
 int cov_rule(const gorio_apd* h) { return h->method == GORIO_METHOD_GICP_OMP ? kRegGicpOmp : h->params.regularization; }
 bool cov_rule_differs(const gorio_apd* h, const DevCloud& c) {
@@ -679,11 +696,12 @@ int run_covariances(gorio_apd* lead, std::vector<std::pair<gorio_apd*, DevCloud*
   return GORIO_OK;
 }
 
-// largest float f with (double)f < thr2: candidates beyond it can never pass the gate of APD:183
-float gate_bound(double thr2) {
+// largest float f with (double)f < thr2: candidates beyond it can never pass the gate of APD:183.  inclusive: with (double)f <= thr2, for
+// the gate of pcl::CorrespondenceEstimation (a pair is dropped when its distance is GREATER than the threshold)
+float gate_bound(double thr2, bool inclusive = false) {
   if (!(thr2 < (double)FLT_MAX)) return FLT_MAX;
   float f = (float)thr2;
-  while (!((double)f < thr2)) f = std::nextafterf(f, 0.0f);
+  while (!(inclusive ? (double)f <= thr2 : (double)f < thr2)) f = std::nextafterf(f, 0.0f);
   return f;
 }
 
@@ -695,7 +713,7 @@ void launch_pruned(dim3 grid, hipStream_t stream, const PairDesc* d_desc, float 
 // launch_index: position of this search inside its align (0 = the unseeded one), or -1 for a search outside an align loop.  From the third
 // search of an align on, the work measured in the second one (the first seeded one) decides which query waves are cut into parts and
 // which run first (nn_plan_kernel); the first two use the grid position, with the groups of every wave dealt over `splits` workgroups.
-void launch_nn(gorio_apd* lead, const PairDesc* d_desc, dim3 g_nn, int max_src_spad, int count, int max_tgt_n, int launch_index = -1) {
+void launch_nn(gorio_apd* lead, const PairDesc* d_desc, dim3 g_nn, int max_src_spad, int count, int max_tgt_n, int launch_index = -1, bool inclusive_gate = false) {
   if (lead->params.search == GORIO_SEARCH_PRUNED) {
     const double thr = lead->params.corr_dist_threshold;
     const long waves = (long)count * ((max_src_spad + 63) / 64);
@@ -711,7 +729,7 @@ void launch_nn(gorio_apd* lead, const PairDesc* d_desc, dim3 g_nn, int max_src_s
     const int capmul = big ? 4 : 2, plan_div = big ? 20480 : 10240;
     const int plan_cap = std::min(16 * nw_max, std::max(capmul * nw_max, 8192 / std::max(1, count)));
     if (planned) {
-      launch_pruned(dim3((plan_cap + 3) / 4, 1, count), lead->stream, d_desc, gate_bound(thr * thr), 2 | (launch_index & 1));
+      launch_pruned(dim3((plan_cap + 3) / 4, 1, count), lead->stream, d_desc, gate_bound(thr * thr, inclusive_gate), 2 | (launch_index & 1));
       return;
     }
     int splits = (int)(4096 / (waves > 0 ? waves : 1));  // a lone 16k scan has 256 query waves: deal the tile groups over more workgroups
@@ -722,7 +740,7 @@ void launch_nn(gorio_apd* lead, const PairDesc* d_desc, dim3 g_nn, int max_src_s
     // shortens that tail until the plan takes over.
     if (max_tgt_n >= 131072 && splits < 8) splits = 8;
     while (splits & (splits - 1)) splits &= splits - 1;  // the kernel deals groups by their low bits: a power of two
-    launch_pruned(dim3((max_src_spad + 255) / 256, splits, count), lead->stream, d_desc, gate_bound(thr * thr), launch_index >= 0 ? (launch_index & 1) : 0);
+    launch_pruned(dim3((max_src_spad + 255) / 256, splits, count), lead->stream, d_desc, gate_bound(thr * thr, inclusive_gate), launch_index >= 0 ? (launch_index & 1) : 0);
     if (launch_index == 1 && !lead->comm && !lead->shard_only && !no_plan) nn_plan_kernel<<<count, 256, 0, lead->stream>>>(d_desc, 1, count, plan_cap, plan_div);
   } else {
     nn_search_kernel<<<g_nn, 256, 0, lead->stream>>>(d_desc);
@@ -952,6 +970,8 @@ int align_impl(gorio_apd** hs, int count, const float* guesses, float* T_out, do
     if (hs[q] && hs[q]->comm && count != 1) return fail(lead, GORIO_ERR_INVALID, "a handle with a communicator (sharded source) cannot be part of a batch");
   for (int q = 0; q < count; ++q)
     if (hs[q] && hs[q]->method == GORIO_METHOD_GICP_OMP) return fail(lead, GORIO_ERR_UNSUPPORTED, "align_batch: GICP_OMP handles batch through gorio_apd_gicp_omp_align_batch (the BFGS shell is not the Gauss-Newton / LM one)");
+  for (int q = 0; q < count; ++q)
+    if (hs[q] && hs[q]->method == GORIO_METHOD_ICP) return fail(lead, GORIO_ERR_UNSUPPORTED, "align_batch: ICP handles batch through gorio_apd_icp_align_batch");
   std::unordered_set<gorio_apd*> distinct;
   for (int q = 0; q < count; ++q) {
     gorio_apd* h = hs[q];
@@ -1279,9 +1299,11 @@ int gorio_apd_get_params(const gorio_apd_t* h, gorio_apd_params* p) {
 
 int gorio_apd_set_method(gorio_apd_t* h, int method, double voxel_resolution, int voxel_search, int voxel_mode) {
   if (!h) return GORIO_ERR_INVALID;
-  if (method != GORIO_METHOD_APDGICP && method != GORIO_METHOD_GICP && method != GORIO_METHOD_VGICP && method != GORIO_METHOD_GICP_OMP) return fail(h, GORIO_ERR_UNSUPPORTED, "set_method: unknown registration method");
-  if (method == GORIO_METHOD_GICP_OMP) {  // the voxel arguments are ignored in this mode: the handle keeps the ones it has
-    if (h->comm) return fail(h, GORIO_ERR_STATE, "set_method: GICP_OMP has no sharded-source mode (the handle has a communicator)");
+  if (method != GORIO_METHOD_APDGICP && method != GORIO_METHOD_GICP && method != GORIO_METHOD_VGICP && method != GORIO_METHOD_GICP_OMP && method != GORIO_METHOD_ICP) return fail(h, GORIO_ERR_UNSUPPORTED, "set_method: unknown registration method");
+  if (method == GORIO_METHOD_GICP_OMP || method == GORIO_METHOD_ICP) {  // the voxel arguments are ignored in these modes: the handle keeps the ones it has
+    if (h->comm) return fail(h, GORIO_ERR_STATE, "set_method: GICP_OMP and ICP have no sharded-source mode (the handle has a communicator)");
+    if (method == GORIO_METHOD_ICP && h->shard_only && h->comm_world > 1) return fail(h, GORIO_ERR_STATE, "set_method: ICP has no sharded-source mode (gorio_apd_debug_set_shard is on)");
+    h->icp_pairs = -1;
     h->method = method;
     h->corr_valid = false;
     h->omega_valid = false;
@@ -1294,6 +1316,7 @@ int gorio_apd_set_method(gorio_apd_t* h, int method, double voxel_resolution, in
   if (!(voxel_resolution > 0.0) || !std::isfinite(voxel_resolution)) return fail(h, GORIO_ERR_UNSUPPORTED, "set_method: voxel_resolution must be positive");
   if (method == GORIO_METHOD_VGICP && h->comm) return fail(h, GORIO_ERR_STATE, "set_method: FastVGICP has no sharded-source mode (the handle has a communicator)");
   h->gomp_pairs = -1;
+  h->icp_pairs = -1;
   h->method = method;
   h->voxel_resolution = voxel_resolution;
   h->voxel_search = voxel_search;
@@ -1690,6 +1713,7 @@ int gorio_apd_get_knn_indices(gorio_apd_t* h, int which, int* idx, int n_times_k
 int gorio_apd_align(gorio_apd_t* h, const float guess[16], float T_out[16], double* H_out, int* converged, int* nr_iterations, int* n_linearize) {
   if (!h) return GORIO_ERR_INVALID;
   if (h->method == GORIO_METHOD_GICP_OMP) return gomp_align(h, guess, T_out, H_out, converged, nr_iterations, n_linearize);
+  if (h->method == GORIO_METHOD_ICP) return icp_align(h, guess, T_out, H_out, converged, nr_iterations, n_linearize);
   gorio_apd* hs[1] = {h};
   return align_impl(hs, 1, guess, T_out, H_out, converged, nr_iterations, n_linearize);
 }
@@ -1701,6 +1725,7 @@ int gorio_apd_align_batch(gorio_apd_t** handles, int count, const float* guesses
 int gorio_apd_linearize(gorio_apd_t* h, const double T[16], double* H, double* b, double* error) {
   if (!h || !T) return GORIO_ERR_INVALID;
   if (h->method == GORIO_METHOD_GICP_OMP) return fail(h, GORIO_ERR_UNSUPPORTED, "linearize: GICP_OMP has no Gauss-Newton linearisation (gorio_apd_gicp_omp_update / _evaluate)");
+  if (h->method == GORIO_METHOD_ICP) return fail(h, GORIO_ERR_UNSUPPORTED, "linearize: ICP has no Gauss-Newton linearisation (gorio_apd_icp_step)");
   HIP_TRY(h, hipSetDevice(h->device));
   int rc = check_ready(h);
   if (rc) return rc;
@@ -1759,6 +1784,7 @@ int gorio_apd_linearize(gorio_apd_t* h, const double T[16], double* H, double* b
 int gorio_apd_compute_error(gorio_apd_t* h, const double T[16], double* error) {
   if (!h || !T || !error) return GORIO_ERR_INVALID;
   if (h->method == GORIO_METHOD_GICP_OMP) return fail(h, GORIO_ERR_UNSUPPORTED, "compute_error: GICP_OMP evaluates its functor through gorio_apd_gicp_omp_evaluate");
+  if (h->method == GORIO_METHOD_ICP) return fail(h, GORIO_ERR_UNSUPPORTED, "compute_error: ICP has no weighted error (gorio_apd_icp_diag gives the mean squared distance)");
   HIP_TRY(h, hipSetDevice(h->device));
   if (!h->corr_valid || !h->omega_valid) return fail(h, GORIO_ERR_STATE, "compute_error needs the correspondences and Mahalanobis matrices of a previous linearize (or LM align)");
   int rc = single_desc(h, true);
@@ -1799,6 +1825,7 @@ int gorio_apd_get_correspondences(gorio_apd_t* h, int* corr, float* sq_dist, int
 int gorio_apd_get_mahalanobis(gorio_apd_t* h, double* maha, int n) {
   if (!h || !maha) return GORIO_ERR_INVALID;
   if (h->method == GORIO_METHOD_VGICP) return fail(h, GORIO_ERR_STATE, "get_mahalanobis: FastVGICP holds one matrix per (point, voxel) pair, not per point");
+  if (h->method == GORIO_METHOD_ICP) return fail(h, GORIO_ERR_STATE, "get_mahalanobis: ICP holds no Mahalanobis matrices");
   if (!h->corr_valid || !h->omega_valid) return fail(h, GORIO_ERR_STATE, "no Mahalanobis matrices held (a Gauss-Newton align does not materialise them: call gorio_apd_linearize)");
   if (n != h->src->n) return fail(h, GORIO_ERR_INVALID, "get_mahalanobis: size mismatch");
   HIP_TRY(h, hipSetDevice(h->device));
@@ -2015,6 +2042,7 @@ int gorio_comm_get_unique_id(char id[128]) {
 int gorio_apd_comm_init(gorio_apd_t* h, int world_size, int rank, const char id[128]) {
   if (!h || !id || world_size < 1 || rank < 0 || rank >= world_size) return GORIO_ERR_INVALID;
   if (h->method == GORIO_METHOD_VGICP) return fail(h, GORIO_ERR_STATE, "comm_init: FastVGICP has no sharded-source mode");
+  if (h->method == GORIO_METHOD_ICP) return fail(h, GORIO_ERR_STATE, "comm_init: ICP has no sharded-source mode");
   Rccl& R = rccl();
   if (!R.ok) return fail(h, GORIO_ERR_NO_DEVICE, "librccl could not be loaded");
   HIP_TRY(h, hipSetDevice(h->device));
@@ -2050,6 +2078,7 @@ int gorio_apd_comm_info(gorio_apd_t* h, int* world_size, int* rank, long long* a
 int gorio_apd_debug_set_shard(gorio_apd_t* h, int world_size, int rank) {
   if (!h || world_size < 1 || rank < 0 || rank >= world_size) return GORIO_ERR_INVALID;
   if (h->comm) return fail(h, GORIO_ERR_STATE, "debug_set_shard: the handle has a communicator");
+  if (h->method == GORIO_METHOD_ICP && world_size > 1) return fail(h, GORIO_ERR_STATE, "debug_set_shard: ICP has no sharded-source mode");
   h->comm_world = world_size;
   h->comm_rank = rank;
   h->shard_only = world_size > 1;
@@ -2145,5 +2174,6 @@ extern "C" int gorio_debug_search_stats(unsigned long long out[24], int reset) {
 #include "../../include/gorio_map.h"
 #include "apd_map.hip"
 #include "apd_gicp_omp.hip"
+#include "apd_icp.hip"
 #include "../../include/gorio_search.h"
 #include "apd_search.hip"

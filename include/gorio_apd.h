@@ -46,6 +46,9 @@ typedef enum { GORIO_SEARCH_BRUTE_FORCE = 0, GORIO_SEARCH_PRUNED = 1 } gorio_sea
 /* which fast_gicp registration a handle stands for: the three classes select_registration_method hands out through one pcl::Registration
  * pointer (REG:28-37 FAST_APDGICP, REG:63-67 FAST_GICP, REG:68-71 FAST_VGICP) */
 typedef enum { GORIO_METHOD_APDGICP = 0, GORIO_METHOD_GICP = 1, GORIO_METHOD_VGICP = 2, GORIO_METHOD_GICP_OMP = 3 /* pclomp GICP, REG:91-100; below */ } gorio_method;
+/* the methods that stand for classes of PCL itself, values of the same `method` argument of gorio_apd_set_method (gorio_method keeps the
+ * GICP family: classes of the reference tree) */
+typedef enum { GORIO_METHOD_ICP = 4 /* pcl::IterativeClosestPoint, REG:72-79; below */ } gorio_method_pcl;
 /* fast_gicp::NeighborSearchMethod, gicp_settings.hpp:8 (same order) */
 typedef enum { GORIO_VOXEL_DIRECT27 = 0, GORIO_VOXEL_DIRECT7 = 1, GORIO_VOXEL_DIRECT1 = 2, GORIO_VOXEL_DIRECT_RADIUS = 3 } gorio_voxel_search;
 /* fast_gicp::VoxelAccumulationMode, gicp_settings.hpp:10 (same order) */
@@ -167,6 +170,76 @@ int gorio_apd_gicp_omp_diag(const gorio_apd_t* h, int* outer, int* inner_total, 
 int gorio_apd_gicp_omp_align_batch(gorio_apd_t** handles, int count, const float* guesses /* count x 16 */, float* T_out /* count x 16 */,
                                    int* converged, int* nr_iterations, int* n_evaluations /* each count, may be NULL */);
 int gorio_apd_gicp_omp_batch_diag(const gorio_apd_t* lead, int* rounds, int* launches);
+
+/*
+ * GORIO_METHOD_ICP: pcl::IterativeClosestPoint (REG:72-79).  gorio_apd_set_method(h, GORIO_METHOD_ICP, ...) ignores the voxel arguments.
+ * The algorithm below is PCL 1.10's IterativeClosestPoint::computeTransformation with CorrespondenceEstimation, TransformationEstimationSVD
+ * and DefaultConvergenceCriteria, RECALLED from the published sources (they are not part of the reference tree) and FIXED HERE: this text
+ * is the specification, tests/icp_restatement.py restates it.
+ *   start   final = guess; the working copy W = guess * source in float by the ((m0 x + m1 y) + m2 z) + m3 rule; transformation = I,
+ *           nr_iterations = 0, prev_mse = DBL_MAX, similar = 0.  translation_thr = transformation_epsilon, rotation_thr =
+ *           transformation_rotation_epsilon > 0 ? that : 1 - transformation_epsilon, rel_mse_thr = euclidean_fitness_epsilon,
+ *           abs_mse_thr = 1e-12, max_similar = 0.
+ *   loop    1. the exact 1-NN of every point of W in the target (float L2_Simple, ties to the lowest index);
+ *           2. the pair is kept unless (double)sqd > corr_dist_threshold^2;
+ *           3. with use_reciprocal, only if the exact 1-NN of the matched target point among the points of W (ties to the lowest index) is
+ *              that source point (a brute-force pass over W);
+ *           4. fewer than 3 pairs: state 5, converged = false, stop;
+ *           5. transformation = the rigid transform of the pairs: with n pairs (q in W, t in the target), means q_m, t_m and
+ *              Sigma = sum(t q^T) / n - t_m q_m^T in double, Sigma = U D V^T by fp64 Jacobi, R = U diag(1, 1, det(U) det(V)) V^T (Umeyama's
+ *              rule without scale: sign(det Sigma) at full rank, the rank-2 rule otherwise), t = t_m - R q_m, rounded ONCE to float.  PCL
+ *              evaluates this in float with Eigen's summation order; the double evaluation rounded once is this library's definition;
+ *           6. W <- transformation * W in float: the copy is moved incrementally and accumulates rounding, as PCL's does;
+ *           7. final = transformation * final, a float 4x4 product summed left to right;   8. ++nr_iterations;
+ *           9. (a) nr_iterations >= max_iterations: state 1, converged.  (b) cos = 0.5 (trace R - 1), t2 = |t|^2 of transformation in double
+ *              from its float entries; cos >= rotation_thr && t2 <= translation_thr: state 2, converged when similar >= max_similar, else
+ *              the step is marked similar.  (c) mse = mean of the pairs' float squared distances summed in double;
+ *              |mse - prev_mse| < abs_mse_thr: the same rule with state 3; |mse - prev_mse| / prev_mse < rel_mse_thr: with state 4.
+ *              (d) similar is incremented when the step was marked and reset otherwise; prev_mse = mse; continue.
+ *   end     T_out = final, converged and nr_iterations as the loop left them.
+ * In this mode
+ *   - gorio_apd_align runs the loop; H_out is zero-filled, n_linearize = correspondence passes.  Of gorio_apd_params only max_iterations,
+ *     transformation_epsilon, corr_dist_threshold and search are read.  No k-NN lists and no covariances are computed: a cloud with fewer
+ *     points than k_correspondences is accepted.  In pruned mode the target index is built, and the source index to order the query waves;
+ *   - gorio_apd_linearize, gorio_apd_compute_error and gorio_apd_align_batch return GORIO_ERR_UNSUPPORTED and change nothing;
+ *     gorio_apd_get_mahalanobis, the sharded-source calls (gorio_apd_comm_init, gorio_apd_debug_set_shard with more than one rank) and the
+ *     gorio_apd_gicp_omp_* entry points that compute return GORIO_ERR_STATE; the gorio_apd_icp_* calls return GORIO_ERR_STATE on a handle of
+ *     another method;
+ *   - setters, hand-offs (host, device, scan, keyframe, submap, shared target), gorio_apd_transform_source and the fitness scores work as
+ *     in the other modes; gorio_apd_get_correspondences gives the pairs of the last pass: the target index and the float squared distance
+ *     of a pair, -1 and +infinity for a point without one (no neighbour inside the gate, or not reciprocal).
+ * use_reciprocal = setUseReciprocalCorrespondences (0 / 1, default 0), euclidean_fitness_epsilon = setEuclideanFitnessEpsilon (default
+ * -DBL_MAX), transformation_rotation_epsilon = setTransformationRotationEpsilon (default 0).  GORIO_ERR_INVALID for another
+ * use_reciprocal and for NaN.  Stored in every mode, read in ICP mode.
+ */
+int gorio_apd_set_icp_params(gorio_apd_t* h, int use_reciprocal, double euclidean_fitness_epsilon, double transformation_rotation_epsilon);
+int gorio_apd_get_icp_params(const gorio_apd_t* h, int* use_reciprocal, double* euclidean_fitness_epsilon, double* transformation_rotation_epsilon);
+/* Of the last align (any output may be NULL): nr_iterations, pcl::registration::DefaultConvergenceCriteria::ConvergenceState (0 not
+ * converged, 1 iterations, 2 transform, 3 abs MSE, 4 rel MSE, 5 no correspondences, 6 failure after max iterations -- never produced),
+ * the mean squared pair distance and the pair count of the last pass (-1: none held). */
+int gorio_apd_icp_diag(const gorio_apd_t* h, int* iterations, int* state, double* mse, int* pairs);
+/* Parity hook: ONE correspondence pass on the copy T16 * source (row-major float 4x4).  pairs = the pair count; sums17 = count, sum d^2,
+ * sum q (3), sum t (3), sum t q^T (9, row-major: t along the rows) over the pairs, block partials of 256 source points added in block
+ * order; T_est16 = the rigid transform of step 5 (the identity when fewer than 3 pairs).  Any output may be NULL.
+ * gorio_apd_get_correspondences then gives the pairs. */
+int gorio_apd_icp_step(gorio_apd_t* h, const float T16[16], int* pairs, double sums17[17], float T_est16[16]);
+/*
+ * Batched ICP aligns in lock-step rounds: every round each unfinished handle has one correspondence pass pending.  Per round: one search
+ * launch, one launch that commits the moved copies, gates and reduces the pairs, one launch that adds every handle's block sums in block
+ * order (three launches; a round with a reciprocal handle pending adds one), one copy back, one synchronisation -- on the stream and with
+ * the tables of handles[0].  rounds = the largest nr_iterations of the batch (a handle that ends with fewer than 3 pairs counts that pass).
+ *   - validation is that of gorio_apd_gicp_omp_align_batch: count == 0 is GORIO_OK; count < 0, a null array or entry, the same handle
+ *     twice, handles on two devices, differing gorio_apd_params: GORIO_ERR_INVALID; a handle of another method, or without its clouds:
+ *     GORIO_ERR_STATE.  Checked before anything is built or launched; the message on handles[0] names the index ("handle <q>: ...").
+ *   - the ICP parameters are per handle and may differ; targets and sources may be shared.
+ *   - "fewer than 3 correspondences" ends that handle alone with converged[q] = 0; the call still returns GORIO_OK.
+ *   - every output of handle q, its correspondences and its gorio_apd_icp_diag values are bit for bit those of its own gorio_apd_align:
+ *     the single align runs the same rounds with count = 1.
+ * gorio_apd_icp_batch_diag, of the last batch led by `lead`: lock-step rounds and kernel launches.
+ */
+int gorio_apd_icp_align_batch(gorio_apd_t** handles, int count, const float* guesses /* count x 16 */, float* T_out /* count x 16 */,
+                              int* converged, int* nr_iterations /* each count, may be NULL */);
+int gorio_apd_icp_batch_diag(const gorio_apd_t* lead, int* rounds, int* launches);
 
 /* parity hooks (VGICP mode; they build the map when it is stale): voxelmap_ (VGH:85) as arrays over the occupied voxels in ascending
  * lexicographic (x, y, z) coordinate order -- coord3: 3 ints, num_points, mean4: GaussianVoxel::mean, cov16: GaussianVoxel::cov row-major
