@@ -56,10 +56,13 @@ APD_SYMBOLS = [
     "gorio_apd_set_gicp_omp_params", "gorio_apd_get_gicp_omp_params", "gorio_apd_gicp_omp_update", "gorio_apd_gicp_omp_evaluate", "gorio_apd_gicp_omp_diag",
     "gorio_apd_gicp_omp_align_batch", "gorio_apd_gicp_omp_batch_diag",
     "gorio_apd_set_icp_params", "gorio_apd_get_icp_params", "gorio_apd_icp_diag", "gorio_apd_icp_step", "gorio_apd_icp_align_batch", "gorio_apd_icp_batch_diag",
+    "gorio_apd_set_ndt_cuda_params", "gorio_apd_get_ndt_cuda_params", "gorio_apd_ndt_cuda_get_voxels", "gorio_apd_ndt_cuda_get_pairs",
 ]
 
 # gorio_method / gorio_voxel_search / gorio_voxel_mode of gorio_apd.h (the latter two in the order of gicp_settings.hpp)
 METHOD_APDGICP, METHOD_GICP, METHOD_VGICP, METHOD_GICP_OMP, METHOD_ICP = 0, 1, 2, 3, 4
+METHOD_NDT_CUDA = 5  # gorio_method_fast_ndt: fast_gicp::NDTCuda
+NDT_CUDA_P2D, NDT_CUDA_D2D = 0, 1  # gorio_ndt_cuda_distance (ndt_settings.hpp:6)
 GICP_OMP_F, GICP_OMP_DF, GICP_OMP_FDF = 0, 1, 2  # modes of gorio_apd_gicp_omp_evaluate
 VOXEL_DIRECT27, VOXEL_DIRECT7, VOXEL_DIRECT1, VOXEL_DIRECT_RADIUS = 0, 1, 2, 3
 VOXEL_ADDITIVE, VOXEL_ADDITIVE_WEIGHTED, VOXEL_MULTIPLICATIVE = 0, 1, 2
@@ -183,6 +186,36 @@ class ApdGicp:
         i, s, p, e = C.c_int(0), C.c_int(0), C.c_int(0), C.c_double(0.0)
         _check(self._h, self._lib.gorio_apd_icp_diag(self._h, C.byref(i), C.byref(s), C.byref(e), C.byref(p)))
         return dict(iterations=i.value, state=s.value, mse=e.value, pairs=p.value)
+
+    # ---- NDTCuda (METHOD_NDT_CUDA): setDistanceMode and the radius of setNeighborSearchMethod (ndt_cuda.hpp:53-55), and the parity hooks
+    def set_ndt_cuda_params(self, distance_mode=NDT_CUDA_D2D, radius=-1.0):
+        _check(self._h, self._lib.gorio_apd_set_ndt_cuda_params(self._h, int(distance_mode), C.c_double(radius)))
+
+    def get_ndt_cuda_params(self):
+        m, r = C.c_int(0), C.c_double(0.0)
+        _check(self._h, self._lib.gorio_apd_get_ndt_cuda_params(self._h, C.byref(m), C.byref(r)))
+        return dict(distance_mode=m.value, radius=r.value)
+
+    def ndt_cuda_voxels(self, which):
+        """gorio_apd_ndt_cuda_get_voxels: the float voxel map of the source (0) / target (1), voxels in ascending (x, y, z) coordinate order."""
+        nv = C.c_int(0)
+        _check(self._h, self._lib.gorio_apd_ndt_cuda_get_voxels(self._h, int(which), 0, C.byref(nv), None, None, None, None, None))
+        n = nv.value
+        coord, num = np.empty((n, 3), np.int32), np.empty(n, np.int32)
+        mean, raw, cov = np.empty((n, 3), np.float32), np.empty((n, 3, 3), np.float32), np.empty((n, 3, 3), np.float32)
+        if n:
+            _check(self._h, self._lib.gorio_apd_ndt_cuda_get_voxels(self._h, int(which), n, C.byref(nv), _p(coord, C.c_int), _p(num, C.c_int), _p(mean, C.c_float),
+                                                                     _p(raw, C.c_float), _p(cov, C.c_float)))
+        return dict(coord=coord, num_points=num, mean=mean, cov_raw=raw, cov=cov)
+
+    def ndt_cuda_pairs(self):
+        """gorio_apd_ndt_cuda_get_pairs: the (item, voxel) pairs of the last linearise, offset-major then item order, as an [n, 2] array."""
+        m = C.c_int(0)
+        _check(self._h, self._lib.gorio_apd_ndt_cuda_get_pairs(self._h, 0, C.byref(m), None, None))
+        item, vox = np.empty(m.value, np.int32), np.empty(m.value, np.int32)
+        if m.value:
+            _check(self._h, self._lib.gorio_apd_ndt_cuda_get_pairs(self._h, m.value, C.byref(m), _p(item, C.c_int), _p(vox, C.c_int)))
+        return np.stack([item, vox], axis=1)
 
     def getVoxelMap(self):  # noqa: N802 -- parity hook: voxelmap_ (fast_vgicp.hpp:85), voxels in ascending (x, y, z) coordinate order
         nv = C.c_int(0)

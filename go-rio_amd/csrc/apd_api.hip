@@ -35,6 +35,7 @@
 #include "apd_index.hip"
 #include "apd_submap.hip"
 #include "apd_voxel.hip"
+#include "apd_ndt_cuda.hip"
 #include "apd_ground.hip"
 #include "../../include/gorio_sc.h"
 #include "apd_sc.hip"
@@ -91,12 +92,25 @@ struct DevCloud {
   double vm_res = 0.0;
   bool vm_mult = false;                   // MultiplicativeGaussianVoxel (ADDITIVE and ADDITIVE_WEIGHTED build the same voxels, VOX:138-141)
   bool vm_valid = false;
+  // float Gaussian voxel map of this cloud for fast_gicp::NDTCuda (apd_ndt_cuda.hip; source_voxelmap / target_voxelmap, ndt_cuda.cu:120-140):
+  // lives with the cloud, so a swap moves it and the sharers of a target share it.  Built from the points alone; vm_keys / vm_counts / vm_bb
+  // above are its sort scratch too.  Valid for nc_res until the points change.
+  DevBuf<unsigned long long> nc_vkey;  // these five hold nc_cap voxels
+  DevBuf<float> nc_mean, nc_raw, nc_cov6;
+  DevBuf<int> nc_num;
+  int nc_cap = 0, nc_nv = 0;
+  int nc_min[3] = {0, 0, 0}, nc_dim[3] = {0, 0, 0};
+  float nc_res = 0.0f;
+  bool nc_valid = false;
+  NdtcMapView ndtc_view() const { return NdtcMapView{nc_vkey, nc_mean, nc_cov6, nc_num, nc_nv, {nc_min[0], nc_min[1], nc_min[2]}, {nc_dim[0], nc_dim[1], nc_dim[2]}, nc_res}; }
   // What is derived from what: covariances, search index, voxel map and k-NN lists from the points; the voxel map and the k-NN lists from
   // the covariances too.  New points leave all four stale, new covariances the last two.  These members are the ONLY code that writes
-  // present, cov_count, cov_k, cov_reg, idx_valid, idx_chunk, vm_valid and knn_valid; everybody else reads them.
+  // present, cov_count, cov_k, cov_reg, idx_valid, idx_chunk, vm_valid, nc_valid and knn_valid; everybody else reads them.
   void covs_dropped() { cov_count = 0; vm_valid = false; knn_valid = false; }
-  void points_replaced() { present = true; idx_valid = false; covs_dropped(); }
-  void cleared() { present = false; n = 0; idx_valid = false; covs_dropped(); }
+  void points_replaced() { present = true; idx_valid = false; nc_valid = false; covs_dropped(); }
+  void cleared() { present = false; n = 0; idx_valid = false; nc_valid = false; covs_dropped(); }
+  void ndtc_map_dropped() { nc_valid = false; }
+  void ndtc_map_built() { nc_valid = true; }
   void covs_estimated(int k, int reg, bool keep_knn, double eps = 0.0) { cov_count = n; cov_k = k; cov_reg = reg; cov_eps = eps; vm_valid = false; knn_valid = keep_knn; }
   void covs_supplied() { covs_estimated(-1, -1, false); }  // not from a k-NN search of this library: no lists, no (k, reg) to compare
   void index_built(int chunk) { idx_valid = true; idx_chunk = chunk; }
@@ -181,6 +195,20 @@ struct gorio_apd {
   DevBuf<double> icp_b_part;
   PinnedBuf icp_b_h_out;
   int icp_b_rounds = 0, icp_b_launches = 0;  // gorio_apd_icp_batch_diag
+  // fast_gicp::NDTCuda (GORIO_METHOD_NDT_CUDA, apd_ndt_cuda.hip): distance_mode and the DIRECT_RADIUS radius (ndt_cuda.cu:21-35), the offset
+  // table on the device and the (search, radius) it was made for, the slot table, linearized_x and the block partials
+  int ndtc_mode = GORIO_NDT_CUDA_D2D;
+  double ndtc_radius = -1.0;
+  DevBuf<int> ndtc_off;
+  int ndtc_n_off = 0, ndtc_off_search = -1;
+  double ndtc_off_radius = 0.0;
+  std::vector<int> ndtc_off_host;
+  DevBuf<int> ndtc_slots;      // these two: one group of capacity ndtc_cap (slots)
+  DevBuf<double> ndtc_partials;
+  size_t ndtc_cap = 0;
+  DevBuf<float> ndtc_tlin;     // [12]
+  int ndtc_items = 0, ndtc_slot_off = 0, ndtc_slot_d2d = 0;  // shape of the slot table held (items, offsets, distance mode)
+  DevBuf<NdtcPair> d_ndtc;     // batch array (owned by the handle that leads a batch)
   DevBuf<PairState> d_state;
   DevBuf<PairDesc> d_desc;   // batch descriptor array and states (owned by the handle that leads a batch): one group of capacity desc_cap
   DevBuf<PairState> d_states_batch;
@@ -215,7 +243,7 @@ struct gorio_apd {
       if (ev) hipEventDestroy(ev);
     }
   };
-  Pinned pin_ijobs, pin_jobs, pin_desc, pin_states, pin_copy, pin_vox, pin_gomp_jobs, pin_icp_jobs;
+  Pinned pin_ijobs, pin_jobs, pin_desc, pin_states, pin_copy, pin_vox, pin_ndtc, pin_gomp_jobs, pin_icp_jobs;
   PinnedBuf pin_looks;  // where the align loop's looks at the pair states land (a download into pageable memory is staged by the runtime)
   std::string err;
   // profiling
@@ -850,6 +878,170 @@ int ensure_vox_batch(gorio_apd* lead, int count) {
   return GORIO_OK;
 }
 
+// ---- fast_gicp::NDTCuda plumbing (apd_ndt_cuda.hip)
+
+bool is_ndtc(const gorio_apd* h) { return h->method == GORIO_METHOD_NDT_CUDA; }
+
+// 0 < radius <= 3 (at most 123 offsets); ndt_cuda.cu:70-84 would build an empty table for radius <= 0
+int ndtc_check_radius(gorio_apd* h, double radius) {
+  if (!(radius > 0.0) || !std::isfinite(radius)) return fail(h, GORIO_ERR_INVALID, "NDTCuda: the DIRECT_RADIUS radius must be positive and finite (gorio_apd_set_ndt_cuda_params)");
+  if (radius > 3.0) return fail(h, GORIO_ERR_UNSUPPORTED, "NDTCuda: a DIRECT_RADIUS radius above 3 voxels is not supported");
+  return GORIO_OK;
+}
+
+// set_neighbor_search_method, ndt_cuda.cu:35-88, in table order
+std::vector<int> ndtc_offset_table(int search, double radius) {
+  std::vector<int> o;
+  auto push = [&o](int i, int j, int k) { o.push_back(i); o.push_back(j); o.push_back(k); };
+  if (search == GORIO_VOXEL_DIRECT1) {
+    push(0, 0, 0);
+  } else if (search == GORIO_VOXEL_DIRECT7) {
+    push(0, 0, 0); push(1, 0, 0); push(-1, 0, 0); push(0, 1, 0); push(0, -1, 0); push(0, 0, 1); push(0, 0, -1);
+  } else if (search == GORIO_VOXEL_DIRECT27) {
+    for (int i = -1; i <= 1; ++i)
+      for (int j = -1; j <= 1; ++j)
+        for (int k = -1; k <= 1; ++k) push(i, j, k);
+  } else {
+    const int range = (int)std::ceil(radius);
+    for (int i = -range; i <= range; ++i)
+      for (int j = -range; j <= range; ++j)
+        for (int k = -range; k <= range; ++k)
+          if (std::sqrt((double)(i * i + j * j + k * k)) <= radius + 1e-3) push(i, j, k);
+  }
+  return o;
+}
+
+bool ndtc_same_settings(const gorio_apd* a, const gorio_apd* b) {
+  return a->voxel_resolution == b->voxel_resolution && a->voxel_search == b->voxel_search && a->ndtc_mode == b->ndtc_mode &&
+         (a->voxel_search != GORIO_VOXEL_DIRECT_RADIUS || a->ndtc_radius == b->ndtc_radius);
+}
+
+// a cloud shared with other handles carries ONE map: a sharer with another resolution would rebuild it under the others
+bool ndtc_shared_mismatch(const gorio_apd* h, const std::shared_ptr<DevCloud>& c) {
+  return c.use_count() > 1 && c->nc_valid && c->nc_res != (float)h->voxel_resolution;
+}
+
+int ndtc_ready(gorio_apd* h) {
+  if (!h->src->present) return fail(h, GORIO_ERR_STATE, "no input source set (setInputSource)");
+  if (!h->tgt->present) return fail(h, GORIO_ERR_STATE, "no input target set (setInputTarget)");
+  if (h->comm || (h->shard_only && h->comm_world > 1)) return fail(h, GORIO_ERR_STATE, "NDTCuda has no sharded-source mode (gorio_apd_comm_init / gorio_apd_debug_set_shard): use an unsharded handle");
+  if (ndtc_shared_mismatch(h, h->tgt)) return fail(h, GORIO_ERR_INVALID, "the shared target's NDTCuda voxel map was built with another resolution: give this handle a target of its own (setInputTarget)");
+  if (h->ndtc_mode == GORIO_NDT_CUDA_D2D && ndtc_shared_mismatch(h, h->src)) return fail(h, GORIO_ERR_INVALID, "the shared source's NDTCuda voxel map was built with another resolution: give this handle a source of its own (setInputSource)");
+  if (h->voxel_search == GORIO_VOXEL_DIRECT_RADIUS) return ndtc_check_radius(h, h->ndtc_radius);
+  return GORIO_OK;
+}
+
+// create_voxelmap + covariance_regularization (ndt_cuda.cu:120-140) of cloud c: coordinates + bounding box, keys, sort, voxel starts, one
+// accumulation pass.  Two small read-backs (the box, the voxel count); nothing to do when the map held matches.  Deviation from the
+// reference: a changed resolution rebuilds the map (ndt_cuda.cu:122, 133 keep the old one).
+int build_ndtc_map(gorio_apd* h, DevCloud& c, double resolution) {
+  const float res = (float)resolution;
+  if (c.nc_valid && c.nc_res == res) return GORIO_OK;
+  c.ndtc_map_dropped();
+  const int n = c.n;
+  HIP_TRY(h, c.vm_bb.reserve(8));
+  vg_bbox_init_kernel<<<1, 64, 0, h->stream>>>(c.vm_bb);
+  ndtc_coord_bbox_kernel<<<std::min(256, (n + 255) / 256), 256, 0, h->stream>>>(c.p4, n, res, c.vm_bb);
+  int bb[8];
+  HIP_TRY(h, hipMemcpyAsync(bb, c.vm_bb, sizeof(int) * 7, hipMemcpyDeviceToHost, h->stream));
+  HIP_TRY(h, hipStreamSynchronize(h->stream));
+  if (bb[6]) return fail(h, GORIO_ERR_UNSUPPORTED, "NDTCuda voxel map: a coordinate is not finite or its voxel coordinate does not fit 31 bits");
+  NdtcBox g;
+  double cells = 1.0;
+  for (int a = 0; a < 3; ++a) {
+    g.min_c[a] = bb[a];
+    const long long d = (long long)bb[3 + a] - (long long)bb[a] + 1;
+    g.dim[a] = (int)d;
+    cells *= (double)d;
+  }
+  g.res = res;
+  if (cells >= 8589934592.0) return fail(h, GORIO_ERR_UNSUPPORTED, "NDTCuda voxel map: the bounding box of the occupied voxels has 2^33 cells or more (the voxel id is packed into 33 bits of the sort key)");
+  const int npow2 = sort_padded_size(n);
+  const int nblocks = (n + 255) / 256;
+  HIP_TRY(h, c.vm_keys.reserve(npow2));
+  HIP_TRY(h, c.vm_counts.reserve(nblocks + 1));
+  ndtc_key_kernel<<<(npow2 + 255) / 256, 256, 0, h->stream>>>(c.p4, n, npow2, g, c.vm_keys);
+  enqueue_tiled_sort(h->stream, SortKeys{c.vm_keys, npow2}, 1, npow2);
+  vox_count_kernel<<<nblocks, 256, 0, h->stream>>>(c.vm_keys, n, c.vm_counts);
+  vox_scan_kernel<<<1, 1024, 0, h->stream>>>(c.vm_counts, nblocks);
+  int nv = 0;
+  HIP_TRY(h, hipMemcpyAsync(&nv, c.vm_counts + nblocks, sizeof(int), hipMemcpyDeviceToHost, h->stream));
+  HIP_TRY(h, hipStreamSynchronize(h->stream));
+  if (nv <= 0 || nv > n) return fail(h, GORIO_ERR_NO_DEVICE, "NDTCuda voxel map: inconsistent voxel count");
+  {
+    const size_t cap = nv + nv / 8 + 64;
+    HIP_TRY(h, reserve_group(c.nc_cap, nv, cap, c.nc_vkey, cap, c.nc_mean, 3 * cap, c.nc_raw, 9 * cap, c.nc_cov6, 6 * cap, c.nc_num, cap));
+  }
+  ndtc_accum_kernel<<<nblocks, 256, 0, h->stream>>>(c.vm_keys, c.p4, n, c.vm_counts, c.nc_vkey, c.nc_mean, c.nc_raw, c.nc_cov6, c.nc_num);
+  HIP_TRY(h, hipGetLastError());
+  c.nc_nv = nv;
+  for (int a = 0; a < 3; ++a) {
+    c.nc_min[a] = g.min_c[a];
+    c.nc_dim[a] = g.dim[a];
+  }
+  c.nc_res = res;
+  c.ndtc_map_built();
+  return GORIO_OK;
+}
+
+// the maps a linearisation needs (create_voxelmaps, ndt_cuda.cu:115-140: P2D builds no source map), the offset table, the slot table and
+// the block partials of this handle's (offset, item) slots
+int ensure_ndtc_pair(gorio_apd* h) {
+  int rc = build_ndtc_map(h, *h->tgt, h->voxel_resolution);
+  if (rc) return rc;
+  const bool d2d = h->ndtc_mode == GORIO_NDT_CUDA_D2D;
+  if (d2d) {
+    rc = build_ndtc_map(h, *h->src, h->voxel_resolution);
+    if (rc) return rc;
+  }
+  if (h->ndtc_off_search != h->voxel_search || (h->voxel_search == GORIO_VOXEL_DIRECT_RADIUS && h->ndtc_off_radius != h->ndtc_radius)) {
+    h->ndtc_off_host = ndtc_offset_table(h->voxel_search, h->ndtc_radius);
+    HIP_TRY(h, h->ndtc_off.reserve(h->ndtc_off_host.size()));
+    HIP_TRY(h, hipMemcpyAsync(h->ndtc_off, h->ndtc_off_host.data(), sizeof(int) * h->ndtc_off_host.size(), hipMemcpyHostToDevice, h->stream));
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    h->ndtc_n_off = (int)(h->ndtc_off_host.size() / 3);
+    h->ndtc_off_search = h->voxel_search;
+    h->ndtc_off_radius = h->ndtc_radius;
+  }
+  const int items = d2d ? h->src->nc_nv : h->src->n;
+  const size_t total = (size_t)items * h->ndtc_n_off;
+  if (total >= (size_t)INT_MAX) return fail(h, GORIO_ERR_UNSUPPORTED, "NDTCuda: items x offsets does not fit 31 bits");
+  const size_t cap = total + total / 8 + 256;
+  HIP_TRY(h, reserve_group(h->ndtc_cap, total, cap, h->ndtc_slots, cap, h->ndtc_partials, 28 * (cap / 256 + 2)));
+  HIP_TRY(h, h->ndtc_tlin.reserve(12));
+  h->ndtc_items = items;
+  h->ndtc_slot_off = h->ndtc_n_off;
+  h->ndtc_slot_d2d = d2d ? 1 : 0;
+  return GORIO_OK;
+}
+
+// over the slot table HELD (compute_error reads the stale pairs of the last linearise, ndt_cuda.cu:162-177)
+NdtcPair make_ndtc_pair(const gorio_apd* h) {
+  NdtcPair p;
+  p.map = h->tgt->ndtc_view();
+  const bool d2d = h->ndtc_slot_d2d != 0;
+  p.item = d2d ? h->src->nc_mean.get() : reinterpret_cast<const float*>(h->src->p4.get());
+  p.item_cov6 = d2d ? h->src->nc_cov6.get() : nullptr;
+  p.offsets = h->ndtc_off;
+  p.slots = h->ndtc_slots;
+  p.tlin = h->ndtc_tlin;
+  p.item_stride = d2d ? 3 : 4;
+  p.n_items = h->ndtc_items;
+  p.n_off = h->ndtc_slot_off;
+  p.d2d = d2d ? 1 : 0;
+  return p;
+}
+
+void ndtc_desc(const gorio_apd* h, PairDesc& d) {
+  d.partials = h->ndtc_partials;
+  d.nblk = (int)(((size_t)h->ndtc_items * h->ndtc_slot_off + 255) / 256);
+}
+
+void launch_ndtc_linearize(bool d2d, dim3 grid, hipStream_t stream, const PairDesc* d_desc, const NdtcPair* d_pairs) {
+  if (d2d) ndtc_linearize_kernel<true><<<grid, 256, 0, stream>>>(d_desc, d_pairs);
+  else ndtc_linearize_kernel<false><<<grid, 256, 0, stream>>>(d_desc, d_pairs);
+}
+
 // the compile-time variants behind one call (kMethodApd stays the instantiation every APD-GICP caller runs)
 void launch_linearize(int method, dim3 grid, hipStream_t stream, const PairDesc* d_desc, const ApdConsts& cst, int fuse) {
   if (method == GORIO_METHOD_GICP) linearize_kernel<kMethodGicp><<<grid, 256, 0, stream>>>(d_desc, cst, fuse);
@@ -985,18 +1177,21 @@ int align_impl(gorio_apd** hs, int count, const float* guesses, float* T_out, do
       if (h->method != lead->method) return fail(lead, GORIO_ERR_INVALID, "all handles of a batch must use the same registration method (gorio_apd_set_method)");
       if (h->method == GORIO_METHOD_VGICP && (h->voxel_resolution != lead->voxel_resolution || h->voxel_search != lead->voxel_search || h->voxel_mode != lead->voxel_mode))
         return fail(lead, GORIO_ERR_INVALID, "all FastVGICP handles of a batch must carry the same voxel_resolution / voxel_search / voxel_mode");
+      if (is_ndtc(h) && !ndtc_same_settings(h, lead))
+        return fail(lead, GORIO_ERR_INVALID, "all NDTCuda handles of a batch must carry the same resolution / neighbour offsets / distance mode");
     }
-    int rc = check_ready(h);
+    int rc = is_ndtc(h) ? ndtc_ready(h) : check_ready(h);
     if (rc) {
       if (h != lead) lead->err = h->err;
       return rc;
     }
-    rc = ensure_points(h, h->src->n);
+    if (!is_ndtc(h)) rc = ensure_points(h, h->src->n);  // NDTCuda holds no per-point search state
     if (rc) return rc;
   }
-  // APD:149-154: covariances of whichever cloud is stale
+  const bool ndtc = is_ndtc(lead);
+  // APD:149-154: covariances of whichever cloud is stale (NDTCuda: none, and no search index)
   std::vector<std::pair<gorio_apd*, DevCloud*>> todo;
-  {
+  if (!ndtc) {
     std::unordered_set<DevCloud*> seen;  // a target shared by many handles of the batch is estimated once
     for (int q = 0; q < count; ++q) {
       gorio_apd* h = hs[q];
@@ -1005,7 +1200,7 @@ int align_impl(gorio_apd** hs, int count, const float* guesses, float* T_out, do
     }
   }
   int rc = GORIO_OK;
-  if (lead->params.search == GORIO_SEARCH_PRUNED) {  // the search indices first, for ALL clouds of the batch in one call: the kd chunk size is chosen by the whole set (run_index_build)
+  if (lead->params.search == GORIO_SEARCH_PRUNED && !ndtc) {  // the search indices first, for ALL clouds of the batch in one call: the kd chunk size is chosen by the whole set (run_index_build)
     std::vector<std::pair<gorio_apd*, DevCloud*>> all;
     for (int q = 0; q < count; ++q) {
       all.emplace_back(hs[q], hs[q]->src.get());
@@ -1031,6 +1226,16 @@ int align_impl(gorio_apd** hs, int count, const float* guesses, float* T_out, do
     rc = ensure_vox_batch(lead, count);
     if (rc) return rc;
   }
+  if (ndtc) {  // create_voxelmaps (NI:76-79): a shared cloud's map once, the second sharer finds it valid
+    for (int q = 0; q < count; ++q) {
+      rc = ensure_ndtc_pair(hs[q]);
+      if (rc) {
+        if (hs[q] != lead) lead->err = hs[q]->err;
+        return rc;
+      }
+    }
+    HIP_TRY(lead, lead->d_ndtc.reserve(count));
+  }
 
   rc = ensure_batch(lead, count);
   if (rc) return rc;
@@ -1050,6 +1255,7 @@ int align_impl(gorio_apd** hs, int count, const float* guesses, float* T_out, do
     init_state(states[q], T);
     fill_desc(hs[q], descs[q], hs[q]->d_state, total_src_waves);
     if (vgicp) vgicp_desc(hs[q], descs[q]);
+    if (ndtc) ndtc_desc(hs[q], descs[q]);
     // Gauss-Newton never reads the Mahalanobis matrices back (only LM error trials and the parity hooks do): do not store them
     descs[q].write_omega = lead->params.optimizer == GORIO_OPT_LEVENBERG_MARQUARDT ? 1 : 0;
     hs[q]->omega_valid = descs[q].write_omega != 0;
@@ -1065,8 +1271,17 @@ int align_impl(gorio_apd** hs, int count, const float* guesses, float* T_out, do
     max_off = lead->v_n_off;
     if (int rc2 = upload_staged(lead, lead->pin_vox, lead->d_vox, voxs.data(), sizeof(VoxPair) * count)) return rc2;
   }
+  size_t ndtc_max_slots = 1;
+  if (ndtc) {
+    std::vector<NdtcPair> prs(count);
+    for (int q = 0; q < count; ++q) {
+      prs[q] = make_ndtc_pair(hs[q]);
+      ndtc_max_slots = std::max(ndtc_max_slots, (size_t)prs[q].n_items * prs[q].n_off);
+    }
+    if (int rc2 = upload_staged(lead, lead->pin_ndtc, lead->d_ndtc, prs.data(), sizeof(NdtcPair) * count)) return rc2;
+  }
   scatter_states_kernel<<<count, 64, 0, lead->stream>>>(lead->d_desc, lead->d_states_batch);
-  if (!vgicp) arm_keys_kernel<<<dim3(std::min(64, (max_n + 255) / 256), count), 256, 0, lead->stream>>>(lead->d_desc);  // the search's key buffers
+  if (!vgicp && !ndtc) arm_keys_kernel<<<dim3(std::min(64, (max_n + 255) / 256), count), 256, 0, lead->stream>>>(lead->d_desc);  // the search's key buffers
 
   const ApdConsts cst = make_consts(lead->params);
   const dim3 g_nn((max_n + 255) / 256, max_splits, count), g_lin((max_n + 255) / 256, 1, count), g_lm(count);
@@ -1118,7 +1333,8 @@ int align_impl(gorio_apd** hs, int count, const float* guesses, float* T_out, do
   // batches first enqueue as many iterations as the previous batch needed -- on like data that look is the only one.  A finished pair's
   // kernels return at once, so the schedule of the looks never changes a result.
   int chunk_iters = lead->align_budget > 0 ? lead->align_budget : 4;
-  const bool fuse_gn = lead->params.optimizer != GORIO_OPT_LEVENBERG_MARQUARDT && lead->fuse_step && !vgicp;
+  const bool fuse_gn = lead->params.optimizer != GORIO_OPT_LEVENBERG_MARQUARDT && lead->fuse_step && !vgicp && !ndtc;
+  const dim3 g_nlin((unsigned int)((ndtc_max_slots + 255) / 256), 1, count);
   const dim3 g_vlin((unsigned int)(((size_t)max_n * max_off + 255) / 256), 1, count);
   const int max_it = lead->params.max_iterations;
   HIP_TRY(lead, lead->pin_looks.reserve(sizeof(PairState) * count, sizeof(PairState) * (count + count / 2)));
@@ -1130,6 +1346,13 @@ int align_impl(gorio_apd** hs, int count, const float* guesses, float* T_out, do
         vgicp_linearize_kernel<<<g_vlin, 256, 0, lead->stream>>>(lead->d_desc, lead->d_vox);
         chain.mark(2);
         launch_lm_solve(method, g_lm, lead->stream, lead->d_desc, lead->d_vox, cst, 0);
+        chain.mark(3);
+        continue;
+      }
+      if (ndtc) {  // update_correspondences + compute_error (NI:82-85) in one launch, then the shell
+        launch_ndtc_linearize(lead->ndtc_mode == GORIO_NDT_CUDA_D2D, g_nlin, lead->stream, lead->d_desc, lead->d_ndtc);
+        chain.mark(2);
+        lm_solve_ndtc_kernel<<<g_lm, 1024, 0, lead->stream>>>(lead->d_desc, lead->d_ndtc, cst, 0);
         chain.mark(3);
         continue;
       }
@@ -1199,7 +1422,15 @@ int single_desc(gorio_apd* h, bool solver = false) {
   PairDesc d;
   fill_desc(h, d, h->d_state, (h->src->n + 63) / 64);
   if (solver && h->method == GORIO_METHOD_VGICP) vgicp_desc(h, d);
+  if (solver && is_ndtc(h)) ndtc_desc(h, d);
   HIP_TRY(h, hipMemcpyAsync(h->d_desc, &d, sizeof(PairDesc), hipMemcpyHostToDevice, h->stream));
+  if (solver && is_ndtc(h)) {
+    HIP_TRY(h, h->d_ndtc.reserve(1));
+    const NdtcPair p = make_ndtc_pair(h);
+    HIP_TRY(h, hipMemcpyAsync(h->d_ndtc, &p, sizeof(NdtcPair), hipMemcpyHostToDevice, h->stream));
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    return GORIO_OK;
+  }
   if (solver && h->method == GORIO_METHOD_VGICP) {
     rc = ensure_vox_batch(h, 1);
     if (rc) return rc;
@@ -1299,7 +1530,22 @@ int gorio_apd_get_params(const gorio_apd_t* h, gorio_apd_params* p) {
 
 int gorio_apd_set_method(gorio_apd_t* h, int method, double voxel_resolution, int voxel_search, int voxel_mode) {
   if (!h) return GORIO_ERR_INVALID;
-  if (method != GORIO_METHOD_APDGICP && method != GORIO_METHOD_GICP && method != GORIO_METHOD_VGICP && method != GORIO_METHOD_GICP_OMP && method != GORIO_METHOD_ICP) return fail(h, GORIO_ERR_UNSUPPORTED, "set_method: unknown registration method");
+  if (method != GORIO_METHOD_APDGICP && method != GORIO_METHOD_GICP && method != GORIO_METHOD_VGICP && method != GORIO_METHOD_GICP_OMP && method != GORIO_METHOD_ICP && method != GORIO_METHOD_NDT_CUDA) return fail(h, GORIO_ERR_UNSUPPORTED, "set_method: unknown registration method");
+  if (method == GORIO_METHOD_NDT_CUDA) {  // voxel_resolution = setResolution, voxel_search = setNeighborSearchMethod (DIRECT_RADIUS with the radius of gorio_apd_set_ndt_cuda_params); voxel_mode is ignored
+    if (voxel_search != GORIO_VOXEL_DIRECT27 && voxel_search != GORIO_VOXEL_DIRECT7 && voxel_search != GORIO_VOXEL_DIRECT1 && voxel_search != GORIO_VOXEL_DIRECT_RADIUS) return fail(h, GORIO_ERR_UNSUPPORTED, "set_method: unknown neighbour search method");
+    if (!(voxel_resolution > 0.0) || !std::isfinite(voxel_resolution)) return fail(h, GORIO_ERR_UNSUPPORTED, "set_method: voxel_resolution must be positive");
+    if (h->comm || (h->shard_only && h->comm_world > 1)) return fail(h, GORIO_ERR_STATE, "set_method: NDTCuda has no sharded-source mode");
+    if (voxel_search == GORIO_VOXEL_DIRECT_RADIUS)
+      if (int rc = ndtc_check_radius(h, h->ndtc_radius)) return rc;
+    h->gomp_pairs = -1;
+    h->icp_pairs = -1;
+    h->method = method;
+    h->voxel_resolution = voxel_resolution;
+    h->voxel_search = voxel_search;
+    h->corr_valid = false;
+    h->omega_valid = false;
+    return GORIO_OK;
+  }
   if (method == GORIO_METHOD_GICP_OMP || method == GORIO_METHOD_ICP) {  // the voxel arguments are ignored in these modes: the handle keeps the ones it has
     if (h->comm) return fail(h, GORIO_ERR_STATE, "set_method: GICP_OMP and ICP have no sharded-source mode (the handle has a communicator)");
     if (method == GORIO_METHOD_ICP && h->shard_only && h->comm_world > 1) return fail(h, GORIO_ERR_STATE, "set_method: ICP has no sharded-source mode (gorio_apd_debug_set_shard is on)");
@@ -1403,6 +1649,94 @@ int gorio_apd_get_voxel_correspondences(gorio_apd_t* h, int* voxel_idx, int n_so
   return GORIO_OK;
 }
 
+int gorio_apd_set_ndt_cuda_params(gorio_apd_t* h, int distance_mode, double radius) {
+  if (!h) return GORIO_ERR_INVALID;
+  if (distance_mode != GORIO_NDT_CUDA_P2D && distance_mode != GORIO_NDT_CUDA_D2D) return fail(h, GORIO_ERR_INVALID, "set_ndt_cuda_params: distance_mode must be P2D (0) or D2D (1)");
+  if (std::isnan(radius)) return fail(h, GORIO_ERR_INVALID, "set_ndt_cuda_params: radius is NaN");
+  if (is_ndtc(h) && h->voxel_search == GORIO_VOXEL_DIRECT_RADIUS)  // the radius is in use: it must be a usable one
+    if (int rc = ndtc_check_radius(h, radius)) return rc;
+  h->ndtc_mode = distance_mode;
+  h->ndtc_radius = radius;
+  if (is_ndtc(h)) h->corr_valid = false;  // pairs of another item set or neighbourhood
+  return GORIO_OK;
+}
+
+int gorio_apd_get_ndt_cuda_params(const gorio_apd_t* h, int* distance_mode, double* radius) {
+  if (!h) return GORIO_ERR_INVALID;
+  if (distance_mode) *distance_mode = h->ndtc_mode;
+  if (radius) *radius = h->ndtc_radius;
+  return GORIO_OK;
+}
+
+int gorio_apd_ndt_cuda_get_voxels(gorio_apd_t* h, int which, int capacity, int* n_voxels, int* coords, int* num_points, float* mean, float* cov_raw, float* cov) {
+  if (!h || !n_voxels || (which != 0 && which != 1)) return GORIO_ERR_INVALID;
+  if (!is_ndtc(h)) return fail(h, GORIO_ERR_STATE, "ndt_cuda_get_voxels: the handle is not in NDTCuda mode (gorio_apd_set_method)");
+  HIP_TRY(h, hipSetDevice(h->device));
+  const std::shared_ptr<DevCloud>& cp = which == 0 ? h->src : h->tgt;
+  DevCloud& c = *cp;
+  if (!c.present) return fail(h, GORIO_ERR_STATE, "ndt_cuda_get_voxels: that cloud is not set");
+  if (ndtc_shared_mismatch(h, cp)) return fail(h, GORIO_ERR_INVALID, "ndt_cuda_get_voxels: the shared cloud's map was built with another resolution");
+  if (which == 0 && h->ndtc_mode == GORIO_NDT_CUDA_P2D) {  // P2D builds no source map (NC:122): report the one held, if any
+    if (!c.nc_valid || c.nc_res != (float)h->voxel_resolution) {
+      *n_voxels = 0;
+      return GORIO_OK;
+    }
+  } else if (int rc = build_ndtc_map(h, c, h->voxel_resolution)) {
+    return rc;
+  }
+  const int nv = c.nc_nv;
+  *n_voxels = nv;
+  if (capacity < nv || (!coords && !num_points && !mean && !cov_raw && !cov)) return GORIO_OK;
+  std::vector<unsigned long long> vkey(nv);
+  std::vector<float> c6((size_t)nv * 6);
+  HIP_TRY(h, hipMemcpyAsync(vkey.data(), c.nc_vkey, sizeof(unsigned long long) * nv, hipMemcpyDeviceToHost, h->stream));
+  HIP_TRY(h, hipMemcpyAsync(c6.data(), c.nc_cov6, sizeof(float) * 6 * nv, hipMemcpyDeviceToHost, h->stream));
+  if (num_points) HIP_TRY(h, hipMemcpyAsync(num_points, c.nc_num, sizeof(int) * nv, hipMemcpyDeviceToHost, h->stream));
+  if (mean) HIP_TRY(h, hipMemcpyAsync(mean, c.nc_mean, sizeof(float) * 3 * nv, hipMemcpyDeviceToHost, h->stream));
+  if (cov_raw) HIP_TRY(h, hipMemcpyAsync(cov_raw, c.nc_raw, sizeof(float) * 9 * nv, hipMemcpyDeviceToHost, h->stream));
+  HIP_TRY(h, hipStreamSynchronize(h->stream));
+  for (int v = 0; v < nv; ++v) {
+    if (coords) {
+      const unsigned long long id = vkey[v];
+      const unsigned long long d1 = (unsigned long long)c.nc_dim[1], d2 = (unsigned long long)c.nc_dim[2];
+      coords[3 * (size_t)v + 2] = (int)(id % d2) + c.nc_min[2];
+      coords[3 * (size_t)v + 1] = (int)((id / d2) % d1) + c.nc_min[1];
+      coords[3 * (size_t)v] = (int)(id / (d2 * d1)) + c.nc_min[0];
+    }
+    if (cov) {
+      const float* q = c6.data() + 6 * (size_t)v;
+      float* o = cov + 9 * (size_t)v;
+      o[0] = q[0]; o[1] = q[1]; o[2] = q[2];
+      o[3] = q[1]; o[4] = q[3]; o[5] = q[4];
+      o[6] = q[2]; o[7] = q[4]; o[8] = q[5];
+    }
+  }
+  return GORIO_OK;
+}
+
+int gorio_apd_ndt_cuda_get_pairs(gorio_apd_t* h, int capacity, int* n_pairs, int* item, int* voxel) {
+  if (!h || !n_pairs) return GORIO_ERR_INVALID;
+  if (!is_ndtc(h)) return fail(h, GORIO_ERR_STATE, "ndt_cuda_get_pairs: the handle is not in NDTCuda mode (gorio_apd_set_method)");
+  if (!h->corr_valid || !h->ndtc_slots) return fail(h, GORIO_ERR_STATE, "ndt_cuda_get_pairs: no pairs held (gorio_apd_linearize or an align first)");
+  HIP_TRY(h, hipSetDevice(h->device));
+  const size_t total = (size_t)h->ndtc_items * h->ndtc_slot_off;
+  std::vector<int> slots(total);
+  HIP_TRY(h, hipMemcpyAsync(slots.data(), h->ndtc_slots, sizeof(int) * total, hipMemcpyDeviceToHost, h->stream));
+  HIP_TRY(h, hipStreamSynchronize(h->stream));
+  int np = 0;
+  for (size_t t = 0; t < total; ++t) np += slots[t] >= 0;
+  *n_pairs = np;
+  if (capacity < np || (!item && !voxel)) return GORIO_OK;
+  int w = 0;
+  for (size_t t = 0; t < total; ++t) {  // offset-major, then item order
+    if (slots[t] < 0) continue;
+    if (item) item[w] = (int)(t % (size_t)h->ndtc_items);
+    if (voxel) voxel[w] = slots[t];
+    ++w;
+  }
+  return GORIO_OK;
+}
+
 int gorio_apd_set_source(gorio_apd_t* h, const float* xyz, const float* label, int n, int stride) {
   if (!h) return GORIO_ERR_INVALID;
   h->corr_valid = false;
@@ -1492,6 +1826,8 @@ int gorio_apd_set_target_shared(gorio_apd_t* h, gorio_apd_t* owner) {
     if (h->method == GORIO_METHOD_VGICP && t.vm_valid && (t.vm_res != h->voxel_resolution || t.vm_mult != (h->voxel_mode == GORIO_VOXEL_MULTIPLICATIVE)))
       return fail(h, GORIO_ERR_INVALID, "set_target_shared: the owner's voxel map was built with another voxel_resolution / voxel_mode than this handle's");
   }
+  if (is_ndtc(h) && owner->tgt->nc_valid && owner->tgt->nc_res != (float)h->voxel_resolution)
+    return fail(h, GORIO_ERR_INVALID, "set_target_shared: the owner's NDTCuda voxel map was built with another resolution than this handle's");
   h->tgt = owner->tgt;  // points, covariances, search index, voxel map: one copy on the device, alive until the last handle lets go of it
   h->corr_valid = false;
   return GORIO_OK;
@@ -1627,6 +1963,7 @@ int gorio_apd_swap_source_and_target(gorio_apd_t* h) {
 }
 
 static int set_covs(gorio_apd* h, DevCloud& c, const double* cov, int n) {
+  if (is_ndtc(h)) return fail(h, GORIO_ERR_STATE, "set_covariances: NDTCuda has no per-point covariances");
   if (n < 0 || (n > 0 && !cov)) return fail(h, GORIO_ERR_INVALID, "set_covariances: bad arguments");
   if (!c.present || n != c.n) {
     // the reference stores the vector whatever its size (APD:138-145) and recomputes the covariances in computeTransformation when the
@@ -1653,6 +1990,7 @@ int gorio_apd_set_source_covariances(gorio_apd_t* h, const double* cov, int n) {
 int gorio_apd_set_target_covariances(gorio_apd_t* h, const double* cov, int n) { return h ? set_covs(h, *h->tgt, cov, n) : GORIO_ERR_INVALID; }
 
 static int get_covs(gorio_apd* h, DevCloud& c, double* cov, int n) {
+  if (is_ndtc(h)) return fail(h, GORIO_ERR_STATE, "get_covariances: NDTCuda has no per-point covariances");
   const int cnt = c.present ? c.cov_count : 0;
   if (!cov || cnt == 0) return cnt;
   const int m = n < cnt ? n : cnt;
@@ -1675,6 +2013,7 @@ int gorio_apd_get_target_covariances(gorio_apd_t* h, double* cov, int n) { retur
 
 int gorio_apd_calculate_covariances(gorio_apd_t* h) {
   if (!h) return GORIO_ERR_INVALID;
+  if (is_ndtc(h)) return fail(h, GORIO_ERR_STATE, "calculate_covariances: NDTCuda has no per-point covariances");
   HIP_TRY(h, hipSetDevice(h->device));
   const gorio_apd_params& p = h->params;
   std::vector<std::pair<gorio_apd*, DevCloud*>> todo;
@@ -1727,6 +2066,30 @@ int gorio_apd_linearize(gorio_apd_t* h, const double T[16], double* H, double* b
   if (h->method == GORIO_METHOD_GICP_OMP) return fail(h, GORIO_ERR_UNSUPPORTED, "linearize: GICP_OMP has no Gauss-Newton linearisation (gorio_apd_gicp_omp_update / _evaluate)");
   if (h->method == GORIO_METHOD_ICP) return fail(h, GORIO_ERR_UNSUPPORTED, "linearize: ICP has no Gauss-Newton linearisation (gorio_apd_icp_step)");
   HIP_TRY(h, hipSetDevice(h->device));
+  if (is_ndtc(h)) {  // NI:82-85: update_correspondences(trans), then compute_error(trans, H, b) over the fresh pairs
+    int rc = ndtc_ready(h);
+    if (!rc) rc = ensure_ndtc_pair(h);
+    if (!rc) rc = single_desc(h, true);
+    if (rc) return rc;
+    PairState s;
+    init_state(s, T);
+    HIP_TRY(h, hipMemcpyAsync(h->d_state, &s, sizeof(s), hipMemcpyHostToDevice, h->stream));
+    const ApdConsts cst = make_consts(h->params);
+    const unsigned int nblk = (unsigned int)(((size_t)h->ndtc_items * h->ndtc_slot_off + 255) / 256);
+    launch_ndtc_linearize(h->ndtc_slot_d2d != 0, dim3(nblk, 1, 1), h->stream, h->d_desc, h->d_ndtc);
+    lm_solve_ndtc_kernel<<<1, 1024, 0, h->stream>>>(h->d_desc, h->d_ndtc, cst, 1);
+    HIP_TRY(h, hipGetLastError());
+    HIP_TRY(h, hipMemcpyAsync(&s, h->d_state, sizeof(s), hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    h->corr_valid = true;
+    h->omega_valid = false;
+    if (H && b) {
+      std::memcpy(H, s.H, sizeof(double) * 36);
+      std::memcpy(b, s.b, sizeof(double) * 6);
+    }
+    if (error) *error = s.y0;
+    return GORIO_OK;
+  }
   int rc = check_ready(h);
   if (rc) return rc;
   rc = ensure_points(h, h->src->n);
@@ -1786,7 +2149,7 @@ int gorio_apd_compute_error(gorio_apd_t* h, const double T[16], double* error) {
   if (h->method == GORIO_METHOD_GICP_OMP) return fail(h, GORIO_ERR_UNSUPPORTED, "compute_error: GICP_OMP evaluates its functor through gorio_apd_gicp_omp_evaluate");
   if (h->method == GORIO_METHOD_ICP) return fail(h, GORIO_ERR_UNSUPPORTED, "compute_error: ICP has no weighted error (gorio_apd_icp_diag gives the mean squared distance)");
   HIP_TRY(h, hipSetDevice(h->device));
-  if (!h->corr_valid || !h->omega_valid) return fail(h, GORIO_ERR_STATE, "compute_error needs the correspondences and Mahalanobis matrices of a previous linearize (or LM align)");
+  if (is_ndtc(h) ? !h->corr_valid : (!h->corr_valid || !h->omega_valid)) return fail(h, GORIO_ERR_STATE, "compute_error needs the correspondences and Mahalanobis matrices of a previous linearize (or LM align)");
   int rc = single_desc(h, true);
   if (rc) return rc;
   double xi[16];
@@ -1794,6 +2157,14 @@ int gorio_apd_compute_error(gorio_apd_t* h, const double T[16], double* error) {
   HIP_TRY(h, hipMemcpyAsync(reinterpret_cast<char*>(h->d_state.get()) + offsetof(PairState, xi), xi, sizeof(xi), hipMemcpyHostToDevice, h->stream));
   const ApdConsts cst = make_consts(h->params);
   double yi = 0.0;
+  if (is_ndtc(h)) {  // NC:162-177 over the stale pairs, R_lin of the last linearise
+    lm_solve_ndtc_kernel<<<1, 1024, 0, h->stream>>>(h->d_desc, h->d_ndtc, cst, 2);
+    HIP_TRY(h, hipGetLastError());
+    HIP_TRY(h, hipMemcpyAsync(&yi, reinterpret_cast<char*>(h->d_state.get()) + offsetof(PairState, yi), sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    *error = yi;
+    return GORIO_OK;
+  }
   if (h->comm) {
     launch_shard_trial_error(h->method, h->stream, h->d_desc, h->d_red + 28, cst, 2);
     NCCL_TRY(h, rccl().AllReduce(h->d_red + 28, h->d_red + 28, 1, ncclDouble, ncclSum, h->comm, h->stream));
@@ -1813,6 +2184,7 @@ int gorio_apd_compute_error(gorio_apd_t* h, const double T[16], double* error) {
 int gorio_apd_get_correspondences(gorio_apd_t* h, int* corr, float* sq_dist, int n) {
   if (!h) return GORIO_ERR_INVALID;
   if (h->method == GORIO_METHOD_VGICP) return fail(h, GORIO_ERR_STATE, "get_correspondences: FastVGICP pairs points with voxels, not with target points (gorio_apd_get_voxel_correspondences)");
+  if (is_ndtc(h)) return fail(h, GORIO_ERR_STATE, "get_correspondences: NDTCuda pairs items with voxels, not with target points (gorio_apd_ndt_cuda_get_pairs)");
   if (!h->corr_valid) return fail(h, GORIO_ERR_STATE, "no correspondences held");
   if (n != h->src->n) return fail(h, GORIO_ERR_INVALID, "get_correspondences: size mismatch");
   HIP_TRY(h, hipSetDevice(h->device));
@@ -1826,6 +2198,7 @@ int gorio_apd_get_mahalanobis(gorio_apd_t* h, double* maha, int n) {
   if (!h || !maha) return GORIO_ERR_INVALID;
   if (h->method == GORIO_METHOD_VGICP) return fail(h, GORIO_ERR_STATE, "get_mahalanobis: FastVGICP holds one matrix per (point, voxel) pair, not per point");
   if (h->method == GORIO_METHOD_ICP) return fail(h, GORIO_ERR_STATE, "get_mahalanobis: ICP holds no Mahalanobis matrices");
+  if (is_ndtc(h)) return fail(h, GORIO_ERR_STATE, "get_mahalanobis: NDTCuda holds no Mahalanobis matrices (they are recomputed per pair)");
   if (!h->corr_valid || !h->omega_valid) return fail(h, GORIO_ERR_STATE, "no Mahalanobis matrices held (a Gauss-Newton align does not materialise them: call gorio_apd_linearize)");
   if (n != h->src->n) return fail(h, GORIO_ERR_INVALID, "get_mahalanobis: size mismatch");
   HIP_TRY(h, hipSetDevice(h->device));
@@ -2043,6 +2416,7 @@ int gorio_apd_comm_init(gorio_apd_t* h, int world_size, int rank, const char id[
   if (!h || !id || world_size < 1 || rank < 0 || rank >= world_size) return GORIO_ERR_INVALID;
   if (h->method == GORIO_METHOD_VGICP) return fail(h, GORIO_ERR_STATE, "comm_init: FastVGICP has no sharded-source mode");
   if (h->method == GORIO_METHOD_ICP) return fail(h, GORIO_ERR_STATE, "comm_init: ICP has no sharded-source mode");
+  if (is_ndtc(h)) return fail(h, GORIO_ERR_STATE, "comm_init: NDTCuda has no sharded-source mode");
   Rccl& R = rccl();
   if (!R.ok) return fail(h, GORIO_ERR_NO_DEVICE, "librccl could not be loaded");
   HIP_TRY(h, hipSetDevice(h->device));
@@ -2079,6 +2453,7 @@ int gorio_apd_debug_set_shard(gorio_apd_t* h, int world_size, int rank) {
   if (!h || world_size < 1 || rank < 0 || rank >= world_size) return GORIO_ERR_INVALID;
   if (h->comm) return fail(h, GORIO_ERR_STATE, "debug_set_shard: the handle has a communicator");
   if (h->method == GORIO_METHOD_ICP && world_size > 1) return fail(h, GORIO_ERR_STATE, "debug_set_shard: ICP has no sharded-source mode");
+  if (is_ndtc(h) && world_size > 1) return fail(h, GORIO_ERR_STATE, "debug_set_shard: NDTCuda has no sharded-source mode");
   h->comm_world = world_size;
   h->comm_rank = rank;
   h->shard_only = world_size > 1;

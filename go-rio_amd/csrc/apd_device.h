@@ -108,6 +108,7 @@ struct PairDesc {
 constexpr int kMethodApd = 0;    // fast_gicp::FastAPDGICP
 constexpr int kMethodGicp = 1;   // fast_gicp::FastGICP
 constexpr int kMethodVgicp = 2;  // fast_gicp::FastVGICP
+constexpr int kMethodNdtCuda = 3;  // fast_gicp::NDTCuda (lm_solve_body only: its linearisation is ndtc_linearize_kernel)
 
 // Gaussian voxel map of a target cloud (GaussianVoxelMap, fast_vgicp_voxel.hpp:124-182): the occupied voxels in ASCENDING order of their
 // linear id ((cx - min.x) * dim.y + (cy - min.y)) * dim.z + (cz - min.z) inside the bounding box of the occupied coordinates, i.e. in
@@ -131,6 +132,34 @@ struct VoxPair {
   double* omega6;  // [n_source][n_off][6] sqrt(num_points) * Mahalanobis 3x3 block of the pair (the weight of VG:149 folded in)
   int n_off;       // 1, 7 or 27
   int write_omega;
+};
+
+// fast_gicp::NDTCuda (apd_ndt_cuda.hip): the float Gaussian voxel map of a cloud (GaussianVoxelMap of gaussian_voxelmap.cu after
+// covariance_regularization), voxels in ascending linear id like VoxelMapView
+struct NdtcMapView {
+  const unsigned long long* vkey;  // [nv] linear voxel id
+  const float* mean;               // [nv][3]
+  const float* cov6;               // [nv][6] upper triangle of the regularised covariance
+  const int* num;                  // [nv]
+  int nv;
+  int min_c[3];
+  int dim[3];
+  float res;                       // (float)resolution
+};
+
+// per scan pair of an NDTCuda linearisation: the items (P2D: source points, D2D: means of the source's own voxel map), the offset table
+// and the slot table [n_off][n_items] (offset-major, the order of find_voxel_correspondences.cu:83-111)
+struct NdtcPair {
+  NdtcMapView map;         // of the target
+  const float* item;       // item i at item[i * item_stride .. + 2]
+  const float* item_cov6;  // D2D: [n_items][6] regularised covariance of the source voxel; null for P2D
+  const int* offsets;      // [n_off][3], global memory
+  int* slots;              // [n_off][n_items] voxel index or -1
+  float* tlin;             // [12] (float)x of the last linearise (linearized_x, ndt_cuda.cu:149)
+  int item_stride;
+  int n_items;
+  int n_off;
+  int d2d;
 };
 
 // XCD-aware placement of a (x, y, units) launch whose third grid dimension counts independent units (scan pairs, clouds): the hardware

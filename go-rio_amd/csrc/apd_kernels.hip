@@ -481,6 +481,7 @@ __device__ __forceinline__ double residual_terms(const double* __restrict__ T, f
 __device__ void gn_step_tail(const PairDesc& pd, const ApdConsts& cst);
 // this thread's part of FastVGICP::compute_error over the pairs of the last linearise (apd_voxel.hip)
 __device__ double vgicp_error_part(const PairDesc& pd, const VoxPair& vp, const double* __restrict__ T);
+__device__ double ndtc_error_part(const PairDesc& pd, const NdtcPair& np, const double* __restrict__ T);  // apd_ndt_cuda.hip
 
 __device__ __forceinline__ float sumsq2_f(float a, float b) {  // x^2 + y^2 in float, un-fused (APD:198 squares floats)
   float r = a * a;
@@ -802,13 +803,16 @@ __device__ bool is_converged(const double* __restrict__ delta, double inv_rot_ep
 }
 
 // compute_error (APD:310-346) over all source points of one pair by one workgroup; result valid on every thread
-// (kMethodGicp: GICP:234-257, no weight; kMethodVgicp: VG:183-204 over the slot table of the last linearise, apd_voxel.hip)
-template <int METHOD>
-__device__ double block_error(const PairDesc& pd, const VoxPair* __restrict__ vp, const double* __restrict__ T, const ApdConsts& cst, double* __restrict__ sred) {
+// (kMethodGicp: GICP:234-257, no weight; kMethodVgicp: VG:183-204 over the slot table of the last linearise, apd_voxel.hip;
+// kMethodNdtCuda: NC:162-177 over the slot table of the last linearise, apd_ndt_cuda.hip).  AUX: VoxPair, or NdtcPair for kMethodNdtCuda
+template <int METHOD, typename AUX>
+__device__ double block_error(const PairDesc& pd, const AUX* __restrict__ vp, const double* __restrict__ T, const ApdConsts& cst, double* __restrict__ sred) {
   const int n = pd.src.n;
   double sum = 0.0;
   if constexpr (METHOD == kMethodVgicp) {
     sum = vgicp_error_part(pd, *vp, T);
+  } else if constexpr (METHOD == kMethodNdtCuda) {
+    sum = ndtc_error_part(pd, *vp, T);
   } else {
     for (int i = threadIdx.x; i < n; i += blockDim.x) {
       const int j = pd.corr[i];
@@ -839,8 +843,8 @@ __device__ double block_error(const PairDesc& pd, const VoxPair* __restrict__ vp
 
 // grid: (pairs), block 1024.  mode 0: full optimiser step (LSQ:67-76 body).  mode 1: only publish H, b, y0 (linearize API).
 // mode 2: only evaluate the error at st->xi with the stored correspondences (compute_error API).
-template <int METHOD>
-__device__ void lm_solve_body(const PairDesc& pd, const VoxPair* __restrict__ vp, const ApdConsts& cst, int mode) {
+template <int METHOD, typename AUX>
+__device__ void lm_solve_body(const PairDesc& pd, const AUX* __restrict__ vp, const ApdConsts& cst, int mode) {
   PairState* __restrict__ st = pd.state;
   __shared__ double sH[36], sb[6], sxi[16], sdelta[16], sd[6], sws[56], sHl[36], snb[6];
   __shared__ double sy0, sred[16];
@@ -976,11 +980,15 @@ __device__ void lm_solve_body(const PairDesc& pd, const VoxPair* __restrict__ vp
 
 template <int METHOD>
 __global__ __launch_bounds__(1024) void lm_solve_kernel(const PairDesc* __restrict__ descs, ApdConsts cst, int mode) {
-  lm_solve_body<METHOD>(descs[blockIdx.x], nullptr, cst, mode);
+  lm_solve_body<METHOD>(descs[blockIdx.x], static_cast<const VoxPair*>(nullptr), cst, mode);
 }
 // FastVGICP: the same shell over the (point, voxel) pairs; vox[pair] carries the voxel map and the slot table (apd_voxel.hip)
 __global__ __launch_bounds__(1024) void lm_solve_vgicp_kernel(const PairDesc* __restrict__ descs, const VoxPair* __restrict__ vox, ApdConsts cst, int mode) {
   lm_solve_body<kMethodVgicp>(descs[blockIdx.x], vox + blockIdx.x, cst, mode);
+}
+// fast_gicp::NDTCuda: the same shell over the (item, voxel) pairs of apd_ndt_cuda.hip
+__global__ __launch_bounds__(1024) void lm_solve_ndtc_kernel(const PairDesc* __restrict__ descs, const NdtcPair* __restrict__ pairs, ApdConsts cst, int mode) {
+  lm_solve_body<kMethodNdtCuda>(descs[blockIdx.x], pairs + blockIdx.x, cst, mode);
 }
 
 // The Gauss-Newton case of lm_solve_body (mode 0, optimizer 0) for the last workgroup of linearize_kernel: the same sums in the same
@@ -1162,7 +1170,7 @@ __global__ __launch_bounds__(1024) void shard_trial_error_kernel(const PairDesc*
   }
   if (threadIdx.x < 16) sxi[threadIdx.x] = st->xi[threadIdx.x];
   __syncthreads();
-  const double yi = block_error<METHOD>(pd, nullptr, sxi, cst, sred);
+  const double yi = block_error<METHOD>(pd, static_cast<const VoxPair*>(nullptr), sxi, cst, sred);
   if (threadIdx.x == 0) ered[0] = yi;
 }
 

@@ -166,7 +166,8 @@ __global__ __launch_bounds__(256) void vg_accum_kernel(const unsigned long long*
 
 // lookup_voxel (VOX:167-174): position of voxel (c0, c1, c2) in the ascending order, or -1.  A coordinate outside the bounding box of
 // the occupied voxels cannot be occupied.
-__device__ __forceinline__ int voxel_lookup(const VoxelMapView& vm, int c0, int c1, int c2) {
+template <typename MapView>  // VoxelMapView, or the float map of apd_ndt_cuda.hip
+__device__ __forceinline__ int voxel_lookup(const MapView& vm, int c0, int c1, int c2) {
   const int r0 = c0 - vm.min_c[0], r1 = c1 - vm.min_c[1], r2 = c2 - vm.min_c[2];
   if (r0 < 0 || r1 < 0 || r2 < 0 || r0 >= vm.dim[0] || r1 >= vm.dim[1] || r2 >= vm.dim[2]) return -1;
   const unsigned long long id = ((unsigned long long)r0 * (unsigned long long)vm.dim[1] + (unsigned long long)r1) * (unsigned long long)vm.dim[2] + (unsigned long long)r2;

@@ -49,6 +49,10 @@ typedef enum { GORIO_METHOD_APDGICP = 0, GORIO_METHOD_GICP = 1, GORIO_METHOD_VGI
 /* the methods that stand for classes of PCL itself, values of the same `method` argument of gorio_apd_set_method (gorio_method keeps the
  * GICP family: classes of the reference tree) */
 typedef enum { GORIO_METHOD_ICP = 4 /* pcl::IterativeClosestPoint, REG:72-79; below */ } gorio_method_pcl;
+/* a third enumeration feeding the same `method` argument: the algorithm of fast_gicp's CUDA back end (fast_gicp::NDTCuda; below) */
+typedef enum { GORIO_METHOD_NDT_CUDA = 5 } gorio_method_fast_ndt;
+/* fast_gicp::NDTDistanceMode in the order of ndt/ndt_settings.hpp:6 */
+typedef enum { GORIO_NDT_CUDA_P2D = 0, GORIO_NDT_CUDA_D2D = 1 } gorio_ndt_cuda_distance;
 /* fast_gicp::NeighborSearchMethod, gicp_settings.hpp:8 (same order) */
 typedef enum { GORIO_VOXEL_DIRECT27 = 0, GORIO_VOXEL_DIRECT7 = 1, GORIO_VOXEL_DIRECT1 = 2, GORIO_VOXEL_DIRECT_RADIUS = 3 } gorio_voxel_search;
 /* fast_gicp::VoxelAccumulationMode, gicp_settings.hpp:10 (same order) */
@@ -240,6 +244,66 @@ int gorio_apd_icp_step(gorio_apd_t* h, const float T16[16], int* pairs, double s
 int gorio_apd_icp_align_batch(gorio_apd_t** handles, int count, const float* guesses /* count x 16 */, float* T_out /* count x 16 */,
                               int* converged, int* nr_iterations /* each count, may be NULL */);
 int gorio_apd_icp_batch_diag(const gorio_apd_t* lead, int* rounds, int* launches);
+
+/*
+ * GORIO_METHOD_NDT_CUDA: fast_gicp::NDTCuda, the point-to-distribution (P2D) and distribution-to-distribution (D2D) NDT of the reference's
+ * CUDA back end under the LsqRegistration shell of the GICP family.  Reference lines: NC = src/fast_gicp/cuda/ndt_cuda.cu, ND =
+ * src/fast_gicp/cuda/ndt_compute_derivatives.cu, GV = src/fast_gicp/cuda/gaussian_voxelmap.cu, FV = src/fast_gicp/cuda/
+ * find_voxel_correspondences.cu, CR = src/fast_gicp/cuda/covariance_regularization.cu, NH / NI = include/fast_gicp/ndt/ndt_cuda.hpp and
+ * its impl, NS = ndt/ndt_settings.hpp.  The reference sums with float atomics and a tree reduction (its results are not reproducible) and
+ * its hash table may drop voxels; THIS TEXT is the definition, tests/ndt_cuda_restatement.py restates it.
+ *   map      (replaces GaussianVoxelMap::create_voxelmap, GV:205-227, and covariance_regularization, NC:128 / 139)  res = (float)resolution;
+ *            per axis coord = (int)floorf(x / res - 0.5f) IN FLOAT (GV:118-121; not the double rule of the FastVGICP map).  Per occupied
+ *            voxel, in input order, in float: n, s += p, S += p p^T (each product rounded, then added).  mean = s / (float)n, cov_raw =
+ *            (S - mean s^T) / (float)n (GV:185-188; 9 floats, mean s^T is not symmetric in float).  cov = sum_i max(1e-3, lambda_i) v_i v_i^T
+ *            with (lambda, v) from this library's fp64 cyclic Jacobi on the UPPER triangle of cov_raw widened to double, summed in double,
+ *            rounded to float once (the reference: Eigen's float closed form and V diag V^-1, CR:73-87 -- a library detail replaced here).
+ *            Voxels of any size are regularised.  Voxels are numbered in ascending packed id, i.e. lexicographic (x, y, z) coordinate order
+ *            (the reference's numbering is its insertion race); no voxel is ever dropped (GV:254-285 tolerates 1 % unassigned points).
+ *   offsets  (replaces set_neighbor_search_method, NC:35-88) in table order: DIRECT1 (0,0,0); DIRECT7 the centre, +x, -x, +y, -y, +z, -z;
+ *            DIRECT27 i, j, k nested, k fastest, each -1..1; DIRECT_RADIUS every integer offset with norm <= radius + 1e-3 from the same
+ *            triple loop over -ceil(radius)..ceil(radius).  0 < radius <= 3; larger: GORIO_ERR_UNSUPPORTED; <= 0 or not finite:
+ *            GORIO_ERR_INVALID (the reference would build an empty table).
+ *   pairs    (replaces update_correspondences, NC:142-160, FV:32-60, 83-111)  items: P2D the source points, D2D the means of the source
+ *            cloud's own map in voxel order.  At linearize(x): Tf = (float)x, q = R p + t per row, left to right, un-fused, in float; for
+ *            every offset in table order and every item there is a pair when voxel coord(q) + offset exists.  The list is offset-major,
+ *            then item order; x is remembered as x_lin.
+ *   terms    (replaces the functors of ND:50-91 and ND:120-163) per pair, all in float; a pair is skipped when the TARGET voxel has
+ *            num_points <= 6.  a' = R a + t at the evaluation pose; e = mean_B - a'; Q = cov_B (P2D) or cov_B + (R_lin cov_A) R_lin^T (D2D);
+ *            C = adj(Q) / det(Q), adj by the nine 2x2 cofactors (minuend first: c00 = q11 q22 - q12 q21, c01 = q02 q21 - q01 q22, c02 = q01 q12
+ *            - q02 q11, c10 = q12 q20 - q10 q22, c11 = q00 q22 - q02 q20, c12 = q02 q10 - q00 q12, c20 = q10 q21 - q11 q20, c21 = q01 q20 - q00
+ *            q21, c22 = q00 q11 - q01 q10), det = (q00 c00 + q01 c10) + q02 c20; w = k^2 / (k^2 + n n), k = res, n = sqrtf((e0 e0 + e1 e1) + e2
+ *            e2) (the Cauchy kernel, ND:15-18); J = [skew(a') | -I]; A = w J^T, B = A C, H = B J, b = B e, err = ((w e)^T C) e; every
+ *            3-term sum left to right.  The upper triangle of H is taken.
+ *   sums     the float terms are widened and added in fp64: wave, then block, then blocks in block order.  No floating-point atomics: two
+ *            runs give the same bits.
+ *   shell    LsqRegistration unchanged (LSQ:55-173): linearize = pairs + terms + sums; compute_error(x) = terms + sums over the STALE pairs
+ *            with R_lin (NC:162-177).  corr_dist_threshold is not read.
+ *   maps     built lazily at the first linearise / align (NI:76-79) and reused while the cloud and the resolution stay the same; P2D builds
+ *            no source map; gorio_apd_swap_source_and_target swaps clouds and maps (NC:90-93).  DEVIATION: a changed resolution rebuilds the
+ *            maps (the reference keeps the old ones, NC:120-140).
+ * gorio_apd_set_method(h, GORIO_METHOD_NDT_CUDA, voxel_resolution, voxel_search, voxel_mode): voxel_resolution = setResolution,
+ * voxel_search = setNeighborSearchMethod (DIRECT_RADIUS is accepted in this method only and uses the radius stored by
+ * gorio_apd_set_ndt_cuda_params, checked as above); voxel_mode is ignored; voxel_resolution <= 0: GORIO_ERR_UNSUPPORTED.  In this mode
+ *   - gorio_apd_linearize, gorio_apd_compute_error, gorio_apd_align, gorio_apd_align_batch (all handles must agree in method, resolution,
+ *     offsets and distance mode: GORIO_ERR_INVALID otherwise; results bit for bit the single aligns'), the fitness scores,
+ *     gorio_apd_transform_source, shared targets (the sharers share the map; a sharer with another resolution gets GORIO_ERR_INVALID) and
+ *     the scan / keyframe / submap hand-offs work;
+ *   - gorio_apd_get_correspondences, gorio_apd_get_mahalanobis, the covariance getters, setters and gorio_apd_calculate_covariances, and the
+ *     sharded-source calls return GORIO_ERR_STATE;
+ *   - no k-NN, covariance estimate or search index is made for an align.
+ * gorio_apd_set_ndt_cuda_params: distance_mode = setDistanceMode (NS:6: P2D = 0, D2D = 1; default D2D, NC:21), radius = the second argument
+ * of setNeighborSearchMethod (default -1, NH:55).  Stored in every mode; another distance_mode or a NaN radius: GORIO_ERR_INVALID; while the
+ * handle is in this method with DIRECT_RADIUS the radius is checked as above.
+ * Parity hooks: gorio_apd_ndt_cuda_get_voxels gives the map of the source (which = 0) or target (1), building it when stale -- except the
+ * source's in P2D mode, where the map held (or 0 voxels) is reported: coords 3 ints, num_points, mean 3 floats, cov_raw and cov 9 floats
+ * row-major per voxel.  n_voxels always receives the count; the arrays (any may be NULL) are filled when capacity >= it.
+ * gorio_apd_ndt_cuda_get_pairs gives the pair list of the last linearise (item index, target voxel index), GORIO_ERR_STATE when none is held.
+ */
+int gorio_apd_set_ndt_cuda_params(gorio_apd_t* h, int distance_mode, double radius);
+int gorio_apd_get_ndt_cuda_params(const gorio_apd_t* h, int* distance_mode, double* radius);
+int gorio_apd_ndt_cuda_get_voxels(gorio_apd_t* h, int which, int capacity, int* n_voxels, int* coords, int* num_points, float* mean, float* cov_raw, float* cov);
+int gorio_apd_ndt_cuda_get_pairs(gorio_apd_t* h, int capacity, int* n_pairs, int* item, int* voxel);
 
 /* parity hooks (VGICP mode; they build the map when it is stale): voxelmap_ (VGH:85) as arrays over the occupied voxels in ascending
  * lexicographic (x, y, z) coordinate order -- coord3: 3 ints, num_points, mean4: GaussianVoxel::mean, cov16: GaussianVoxel::cov row-major
