@@ -57,12 +57,15 @@ APD_SYMBOLS = [
     "gorio_apd_gicp_omp_align_batch", "gorio_apd_gicp_omp_batch_diag",
     "gorio_apd_set_icp_params", "gorio_apd_get_icp_params", "gorio_apd_icp_diag", "gorio_apd_icp_step", "gorio_apd_icp_align_batch", "gorio_apd_icp_batch_diag",
     "gorio_apd_set_ndt_cuda_params", "gorio_apd_get_ndt_cuda_params", "gorio_apd_ndt_cuda_get_voxels", "gorio_apd_ndt_cuda_get_pairs",
+    "gorio_apd_set_vgicp_cuda_params", "gorio_apd_get_vgicp_cuda_params", "gorio_apd_vgicp_cuda_get_points", "gorio_apd_vgicp_cuda_get_voxels", "gorio_apd_vgicp_cuda_get_pairs",
 ]
 
 # gorio_method / gorio_voxel_search / gorio_voxel_mode of gorio_apd.h (the latter two in the order of gicp_settings.hpp)
 METHOD_APDGICP, METHOD_GICP, METHOD_VGICP, METHOD_GICP_OMP, METHOD_ICP = 0, 1, 2, 3, 4
 METHOD_NDT_CUDA = 5  # gorio_method_fast_ndt: fast_gicp::NDTCuda
 NDT_CUDA_P2D, NDT_CUDA_D2D = 0, 1  # gorio_ndt_cuda_distance (ndt_settings.hpp:6)
+METHOD_VGICP_CUDA = 6  # gorio_method_fast_vgicp_cuda: fast_gicp::FastVGICPCuda
+NN_CPU_PARALLEL_KDTREE, NN_GPU_BRUTEFORCE, NN_GPU_RBF_KERNEL = 0, 1, 2  # gorio_vgicp_cuda_nn (fast_vgicp_cuda.hpp:21)
 GICP_OMP_F, GICP_OMP_DF, GICP_OMP_FDF = 0, 1, 2  # modes of gorio_apd_gicp_omp_evaluate
 VOXEL_DIRECT27, VOXEL_DIRECT7, VOXEL_DIRECT1, VOXEL_DIRECT_RADIUS = 0, 1, 2, 3
 VOXEL_ADDITIVE, VOXEL_ADDITIVE_WEIGHTED, VOXEL_MULTIPLICATIVE = 0, 1, 2
@@ -215,6 +218,44 @@ class ApdGicp:
         item, vox = np.empty(m.value, np.int32), np.empty(m.value, np.int32)
         if m.value:
             _check(self._h, self._lib.gorio_apd_ndt_cuda_get_pairs(self._h, m.value, C.byref(m), _p(item, C.c_int), _p(vox, C.c_int)))
+        return np.stack([item, vox], axis=1)
+
+    # ---- FastVGICPCuda (METHOD_VGICP_CUDA): setNearestNeighborSearchMethod and setKernelWidth (fast_vgicp_cuda.hpp:55-59), and the parity hooks
+    def set_vgicp_cuda_params(self, nn_method=NN_CPU_PARALLEL_KDTREE, kernel_width=0.5, kernel_max_dist=3.0):
+        _check(self._h, self._lib.gorio_apd_set_vgicp_cuda_params(self._h, int(nn_method), C.c_double(kernel_width), C.c_double(kernel_max_dist)))
+
+    def get_vgicp_cuda_params(self):
+        m, w, d = C.c_int(0), C.c_double(0.0), C.c_double(0.0)
+        _check(self._h, self._lib.gorio_apd_get_vgicp_cuda_params(self._h, C.byref(m), C.byref(w), C.byref(d)))
+        return dict(nn_method=m.value, kernel_width=w.value, kernel_max_dist=d.value)
+
+    def vgicp_cuda_points(self, which):
+        """gorio_apd_vgicp_cuda_get_points: of the source (0) / target (1) the raw covariance of every point, the input indices of the
+        points the regularisation keeps, and their regularised covariances (six floats each: 00 01 02 11 12 22)."""
+        n, nk = C.c_int(0), C.c_int(0)
+        _check(self._h, self._lib.gorio_apd_vgicp_cuda_get_points(self._h, int(which), 0, C.byref(n), None, C.byref(nk), None, None))
+        raw, idx, cov = np.empty((n.value, 6), np.float32), np.empty(nk.value, np.int32), np.empty((nk.value, 6), np.float32)
+        if n.value:
+            _check(self._h, self._lib.gorio_apd_vgicp_cuda_get_points(self._h, int(which), n.value, C.byref(n), _p(raw, C.c_float), C.byref(nk), _p(idx, C.c_int), _p(cov, C.c_float)))
+        return dict(cov_raw=raw, kept_index=idx, cov=cov)
+
+    def vgicp_cuda_voxels(self):
+        """gorio_apd_vgicp_cuda_get_voxels: the voxel map of the kept target points, voxels in ascending (x, y, z) coordinate order."""
+        nv = C.c_int(0)
+        _check(self._h, self._lib.gorio_apd_vgicp_cuda_get_voxels(self._h, 0, C.byref(nv), None, None, None, None))
+        n = nv.value
+        coord, num, mean, cov = np.empty((n, 3), np.int32), np.empty(n, np.int32), np.empty((n, 3), np.float32), np.empty((n, 6), np.float32)
+        if n:
+            _check(self._h, self._lib.gorio_apd_vgicp_cuda_get_voxels(self._h, n, C.byref(nv), _p(coord, C.c_int), _p(num, C.c_int), _p(mean, C.c_float), _p(cov, C.c_float)))
+        return dict(coord=coord, num_points=num, mean=mean, cov=cov)
+
+    def vgicp_cuda_pairs(self):
+        """gorio_apd_vgicp_cuda_get_pairs: the (kept item, voxel) pairs of the last linearise, offset-major then item order, as an [n, 2] array."""
+        m = C.c_int(0)
+        _check(self._h, self._lib.gorio_apd_vgicp_cuda_get_pairs(self._h, 0, C.byref(m), None, None))
+        item, vox = np.empty(m.value, np.int32), np.empty(m.value, np.int32)
+        if m.value:
+            _check(self._h, self._lib.gorio_apd_vgicp_cuda_get_pairs(self._h, m.value, C.byref(m), _p(item, C.c_int), _p(vox, C.c_int)))
         return np.stack([item, vox], axis=1)
 
     def getVoxelMap(self):  # noqa: N802 -- parity hook: voxelmap_ (fast_vgicp.hpp:85), voxels in ascending (x, y, z) coordinate order

@@ -36,6 +36,7 @@
 #include "apd_submap.hip"
 #include "apd_voxel.hip"
 #include "apd_ndt_cuda.hip"
+#include "apd_vgicp_cuda.hip"
 #include "apd_ground.hip"
 #include "../../include/gorio_sc.h"
 #include "apd_sc.hip"
@@ -103,12 +104,42 @@ struct DevCloud {
   float nc_res = 0.0f;
   bool nc_valid = false;
   NdtcMapView ndtc_view() const { return NdtcMapView{nc_vkey, nc_mean, nc_cov6, nc_num, nc_nv, {nc_min[0], nc_min[1], nc_min[2]}, {nc_dim[0], nc_dim[1], nc_dim[2]}, nc_res}; }
+  // fast_gicp::FastVGICPCuda (apd_vgicp_cuda.hip): three stages, each valid for the settings recorded beside it until the points change.
+  //   raw   float covariances of ALL points (source_covariances / target_covariances, VC:183-219) from the k-NN lists (vc_knn) or the RBF pass
+  //   kept  the points the regularisation keeps, in input order, with their regularised covariances (CR:91-117)
+  //   map   the voxel map of the kept points that averages their covariances (GV:229-252); built for a target only
+  // They live with the cloud: a swap moves them, the sharers of a cloud share them.
+  DevBuf<float> vc_raw6, vc_reg6;      // the point group of this method: these, vc_keep, vc_p4, vc_cov6, vc_index hold vc_cap points
+  DevBuf<unsigned char> vc_keep;
+  DevBuf<float4> vc_p4;                // kept points
+  DevBuf<float> vc_cov6;               // [vc_nkept][6]
+  DevBuf<int> vc_index;                // [vc_nkept] input index of a kept point
+  int vc_cap = 0, vc_nkept = 0;
+  DevBuf<int> vc_knn, vc_bcnt;         // [n][k] lists; kept points per 256, scanned
+  DevBuf<double> vc_scratch;           // [n][7] the double covariances and weights the k-NN kernels make on their way to the lists
+  DevBuf<float> vc_part;               // RBF block partials [blocks][10][n]
+  bool vc_raw_valid = false, vc_kept_valid = false, vc_map_valid = false;
+  int vc_rbf = 0, vc_k = 0, vc_reg = -1;  // what raw / kept were made with: RBF or lists, k (lists), kernel_width and max_dist (RBF), regularization
+  double vc_width = 0.0, vc_maxd = 0.0;
+  DevBuf<unsigned long long> vc_vkey;  // the map: these four hold vc_mcap voxels
+  DevBuf<float> vc_mean, vc_mcov6;
+  DevBuf<int> vc_num;
+  int vc_mcap = 0, vc_nv = 0;
+  int vc_min[3] = {0, 0, 0}, vc_dim[3] = {0, 0, 0};
+  float vc_res = 0.0f;
+  NdtcMapView vgc_view() const { return NdtcMapView{vc_vkey, vc_mean, vc_mcov6, vc_num, vc_nv, {vc_min[0], vc_min[1], vc_min[2]}, {vc_dim[0], vc_dim[1], vc_dim[2]}, vc_res}; }
   // What is derived from what: covariances, search index, voxel map and k-NN lists from the points; the voxel map and the k-NN lists from
   // the covariances too.  New points leave all four stale, new covariances the last two.  These members are the ONLY code that writes
-  // present, cov_count, cov_k, cov_reg, idx_valid, idx_chunk, vm_valid, nc_valid and knn_valid; everybody else reads them.
+  // present, cov_count, cov_k, cov_reg, idx_valid, idx_chunk, vm_valid, nc_valid, knn_valid and the three vc_*_valid; everybody else reads them.
   void covs_dropped() { cov_count = 0; vm_valid = false; knn_valid = false; }
-  void points_replaced() { present = true; idx_valid = false; nc_valid = false; covs_dropped(); }
-  void cleared() { present = false; n = 0; idx_valid = false; nc_valid = false; covs_dropped(); }
+  void points_replaced() { present = true; idx_valid = false; nc_valid = false; vgc_raw_dropped(); covs_dropped(); }
+  void cleared() { present = false; n = 0; idx_valid = false; nc_valid = false; vgc_raw_dropped(); covs_dropped(); }
+  void vgc_raw_dropped() { vc_raw_valid = false; vgc_kept_dropped(); }
+  void vgc_kept_dropped() { vc_kept_valid = false; vc_map_valid = false; }
+  void vgc_map_dropped() { vc_map_valid = false; }
+  void vgc_raw_built(bool rbf, int k, double width, double maxd) { vc_raw_valid = true; vc_rbf = rbf ? 1 : 0; vc_k = k; vc_width = width; vc_maxd = maxd; }
+  void vgc_kept_built(int reg, int nkept) { vc_kept_valid = true; vc_reg = reg; vc_nkept = nkept; }
+  void vgc_map_built() { vc_map_valid = true; }
   void ndtc_map_dropped() { nc_valid = false; }
   void ndtc_map_built() { nc_valid = true; }
   void covs_estimated(int k, int reg, bool keep_knn, double eps = 0.0) { cov_count = n; cov_k = k; cov_reg = reg; cov_eps = eps; vm_valid = false; knn_valid = keep_knn; }
@@ -209,6 +240,10 @@ struct gorio_apd {
   DevBuf<float> ndtc_tlin;     // [12]
   int ndtc_items = 0, ndtc_slot_off = 0, ndtc_slot_d2d = 0;  // shape of the slot table held (items, offsets, distance mode)
   DevBuf<NdtcPair> d_ndtc;     // batch array (owned by the handle that leads a batch)
+  // fast_gicp::FastVGICPCuda (GORIO_METHOD_VGICP_CUDA, apd_vgicp_cuda.hip): neighbor_method_, kernel_width_, kernel_max_dist_ (VI:27-31).  Its
+  // offset table, slot table, linearized_x and partials are the NDTCuda members above (ndtc_slot_d2d == 2).
+  int vgc_nn = GORIO_VGICP_CUDA_NN_CPU_PARALLEL_KDTREE;
+  double vgc_width = 0.5, vgc_maxd = 3.0;
   DevBuf<PairState> d_state;
   DevBuf<PairDesc> d_desc;   // batch descriptor array and states (owned by the handle that leads a batch): one group of capacity desc_cap
   DevBuf<PairState> d_states_batch;
@@ -621,8 +656,17 @@ int run_index_build(gorio_apd* lead, std::vector<std::pair<gorio_apd*, DevCloud*
   return GORIO_OK;
 }
 
+// run_covariances for its k-NN lists alone (FastVGICPCuda's float covariances are made from them, apd_vgicp_cuda.hip): the lists go to
+// knn_out, the double covariances and weights the kernels make on the way go to scratch, and the clouds' own covariances, lists and state
+// stay as they are
+struct KnnListsOnly {
+  int* knn_out;    // [n][k]
+  double* cov6;    // [n][6] scratch
+  double* geo_w;   // [n] scratch
+};
+
 // covariance estimation for a list of clouds on lead's stream
-int run_covariances(gorio_apd* lead, std::vector<std::pair<gorio_apd*, DevCloud*>>& todo) {
+int run_covariances(gorio_apd* lead, std::vector<std::pair<gorio_apd*, DevCloud*>>& todo, const KnnListsOnly* only = nullptr) {
   if (todo.empty()) return GORIO_OK;
   const int njobs = (int)todo.size();
   const int k = lead->params.k_correspondences;
@@ -655,7 +699,7 @@ int run_covariances(gorio_apd* lead, std::vector<std::pair<gorio_apd*, DevCloud*
     const size_t need = pruned ? 0 : (size_t)s * K * c.n;
     HIP_TRY(h, reserve_group(c.part_cap, need, need, c.part_d, need, c.part_i, need));
     const bool keep = h->params.keep_knn_indices != 0 || lead->method == GORIO_METHOD_GICP_OMP;  // GICP_OMP estimates from the lists
-    if (keep && (c.knn_k != k || !c.knn)) {
+    if (!only && keep && (c.knn_k != k || !c.knn)) {
       c.knn_k = 0;
       HIP_TRY(h, c.knn.realloc((size_t)c.cap * k));
       c.knn_k = k;
@@ -666,9 +710,13 @@ int run_covariances(gorio_apd* lead, std::vector<std::pair<gorio_apd*, DevCloud*
     }
     KnnJob& j = jobs[q];
     j.cloud = c.view();
+    if (only) {
+      j.cloud.cov6 = only->cov6;
+      j.cloud.geo_w = only->geo_w;
+    }
     j.part_d = c.part_d;
     j.part_i = c.part_i;
-    j.knn_out = keep ? c.knn.get() : nullptr;
+    j.knn_out = only ? only->knn_out : keep ? c.knn.get() : nullptr;
     j.redo = select ? c.redo.get() : nullptr;
     j.kth = select ? c.kth.get() : nullptr;
     j.k = k;
@@ -715,6 +763,7 @@ int run_covariances(gorio_apd* lead, std::vector<std::pair<gorio_apd*, DevCloud*
     }
   }
   HIP_TRY(lead, hipGetLastError());
+  if (only) return GORIO_OK;
   if (lead->method == GORIO_METHOD_GICP_OMP) {
     if (int rc = gomp_covariances(lead, todo)) return rc;
     for (auto& t : todo) t.second->covs_estimated(k, kRegGicpOmp, true, lead->gomp_eps);
@@ -931,22 +980,16 @@ int ndtc_ready(gorio_apd* h) {
   return GORIO_OK;
 }
 
-// create_voxelmap + covariance_regularization (ndt_cuda.cu:120-140) of cloud c: coordinates + bounding box, keys, sort, voxel starts, one
-// accumulation pass.  Two small read-backs (the box, the voxel count); nothing to do when the map held matches.  Deviation from the
-// reference: a changed resolution rebuilds the map (ndt_cuda.cu:122, 133 keep the old one).
-int build_ndtc_map(gorio_apd* h, DevCloud& c, double resolution) {
-  const float res = (float)resolution;
-  if (c.nc_valid && c.nc_res == res) return GORIO_OK;
-  c.ndtc_map_dropped();
-  const int n = c.n;
+// the first half of a float map build: the voxel starts of `n` points `pts` of cloud c (whose vm_keys / vm_counts / vm_bb are the
+// scratch), the box g and the voxel count nv.  Two small read-backs.
+int ndtc_voxel_starts(gorio_apd* h, DevCloud& c, const float4* pts, int n, float res, NdtcBox& g, int& nv) {
   HIP_TRY(h, c.vm_bb.reserve(8));
   vg_bbox_init_kernel<<<1, 64, 0, h->stream>>>(c.vm_bb);
-  ndtc_coord_bbox_kernel<<<std::min(256, (n + 255) / 256), 256, 0, h->stream>>>(c.p4, n, res, c.vm_bb);
+  ndtc_coord_bbox_kernel<<<std::min(256, (n + 255) / 256), 256, 0, h->stream>>>(pts, n, res, c.vm_bb);
   int bb[8];
   HIP_TRY(h, hipMemcpyAsync(bb, c.vm_bb, sizeof(int) * 7, hipMemcpyDeviceToHost, h->stream));
   HIP_TRY(h, hipStreamSynchronize(h->stream));
   if (bb[6]) return fail(h, GORIO_ERR_UNSUPPORTED, "NDTCuda voxel map: a coordinate is not finite or its voxel coordinate does not fit 31 bits");
-  NdtcBox g;
   double cells = 1.0;
   for (int a = 0; a < 3; ++a) {
     g.min_c[a] = bb[a];
@@ -960,14 +1003,29 @@ int build_ndtc_map(gorio_apd* h, DevCloud& c, double resolution) {
   const int nblocks = (n + 255) / 256;
   HIP_TRY(h, c.vm_keys.reserve(npow2));
   HIP_TRY(h, c.vm_counts.reserve(nblocks + 1));
-  ndtc_key_kernel<<<(npow2 + 255) / 256, 256, 0, h->stream>>>(c.p4, n, npow2, g, c.vm_keys);
+  ndtc_key_kernel<<<(npow2 + 255) / 256, 256, 0, h->stream>>>(pts, n, npow2, g, c.vm_keys);
   enqueue_tiled_sort(h->stream, SortKeys{c.vm_keys, npow2}, 1, npow2);
   vox_count_kernel<<<nblocks, 256, 0, h->stream>>>(c.vm_keys, n, c.vm_counts);
   vox_scan_kernel<<<1, 1024, 0, h->stream>>>(c.vm_counts, nblocks);
-  int nv = 0;
+  nv = 0;
   HIP_TRY(h, hipMemcpyAsync(&nv, c.vm_counts + nblocks, sizeof(int), hipMemcpyDeviceToHost, h->stream));
   HIP_TRY(h, hipStreamSynchronize(h->stream));
   if (nv <= 0 || nv > n) return fail(h, GORIO_ERR_NO_DEVICE, "NDTCuda voxel map: inconsistent voxel count");
+  return GORIO_OK;
+}
+
+// create_voxelmap + covariance_regularization (ndt_cuda.cu:120-140) of cloud c: coordinates + bounding box, keys, sort, voxel starts, one
+// accumulation pass.  Two small read-backs (the box, the voxel count); nothing to do when the map held matches.  Deviation from the
+// reference: a changed resolution rebuilds the map (ndt_cuda.cu:122, 133 keep the old one).
+int build_ndtc_map(gorio_apd* h, DevCloud& c, double resolution) {
+  const float res = (float)resolution;
+  if (c.nc_valid && c.nc_res == res) return GORIO_OK;
+  c.ndtc_map_dropped();
+  const int n = c.n;
+  const int nblocks = (n + 255) / 256;
+  NdtcBox g;
+  int nv = 0;
+  if (int rc = ndtc_voxel_starts(h, c, c.p4, n, res, g, nv)) return rc;
   {
     const size_t cap = nv + nv / 8 + 64;
     HIP_TRY(h, reserve_group(c.nc_cap, nv, cap, c.nc_vkey, cap, c.nc_mean, 3 * cap, c.nc_raw, 9 * cap, c.nc_cov6, 6 * cap, c.nc_num, cap));
@@ -984,6 +1042,7 @@ int build_ndtc_map(gorio_apd* h, DevCloud& c, double resolution) {
   return GORIO_OK;
 }
 
+int ensure_ndtc_slots(gorio_apd* h, int items, int mode);
 // the maps a linearisation needs (create_voxelmaps, ndt_cuda.cu:115-140: P2D builds no source map), the offset table, the slot table and
 // the block partials of this handle's (offset, item) slots
 int ensure_ndtc_pair(gorio_apd* h) {
@@ -994,6 +1053,11 @@ int ensure_ndtc_pair(gorio_apd* h) {
     rc = build_ndtc_map(h, *h->src, h->voxel_resolution);
     if (rc) return rc;
   }
+  return ensure_ndtc_slots(h, d2d ? h->src->nc_nv : h->src->n, d2d ? 1 : 0);
+}
+
+// the offset table on the device, and the slot table and block partials of `items` items (mode: NdtcPair::d2d)
+int ensure_ndtc_slots(gorio_apd* h, int items, int mode) {
   if (h->ndtc_off_search != h->voxel_search || (h->voxel_search == GORIO_VOXEL_DIRECT_RADIUS && h->ndtc_off_radius != h->ndtc_radius)) {
     h->ndtc_off_host = ndtc_offset_table(h->voxel_search, h->ndtc_radius);
     HIP_TRY(h, h->ndtc_off.reserve(h->ndtc_off_host.size()));
@@ -1003,7 +1067,6 @@ int ensure_ndtc_pair(gorio_apd* h) {
     h->ndtc_off_search = h->voxel_search;
     h->ndtc_off_radius = h->ndtc_radius;
   }
-  const int items = d2d ? h->src->nc_nv : h->src->n;
   const size_t total = (size_t)items * h->ndtc_n_off;
   if (total >= (size_t)INT_MAX) return fail(h, GORIO_ERR_UNSUPPORTED, "NDTCuda: items x offsets does not fit 31 bits");
   const size_t cap = total + total / 8 + 256;
@@ -1011,13 +1074,26 @@ int ensure_ndtc_pair(gorio_apd* h) {
   HIP_TRY(h, h->ndtc_tlin.reserve(12));
   h->ndtc_items = items;
   h->ndtc_slot_off = h->ndtc_n_off;
-  h->ndtc_slot_d2d = d2d ? 1 : 0;
+  h->ndtc_slot_d2d = mode;
   return GORIO_OK;
 }
 
 // over the slot table HELD (compute_error reads the stale pairs of the last linearise, ndt_cuda.cu:162-177)
 NdtcPair make_ndtc_pair(const gorio_apd* h) {
   NdtcPair p;
+  if (h->ndtc_slot_d2d == 2) {  // FastVGICPCuda: the kept source points and their covariances against the map of the kept target points
+    p.map = h->tgt->vgc_view();
+    p.item = reinterpret_cast<const float*>(h->src->vc_p4.get());
+    p.item_cov6 = h->src->vc_cov6;
+    p.offsets = h->ndtc_off;
+    p.slots = h->ndtc_slots;
+    p.tlin = h->ndtc_tlin;
+    p.item_stride = 4;
+    p.n_items = h->ndtc_items;
+    p.n_off = h->ndtc_slot_off;
+    p.d2d = 2;
+    return p;
+  }
   p.map = h->tgt->ndtc_view();
   const bool d2d = h->ndtc_slot_d2d != 0;
   p.item = d2d ? h->src->nc_mean.get() : reinterpret_cast<const float*>(h->src->p4.get());
@@ -1040,6 +1116,170 @@ void ndtc_desc(const gorio_apd* h, PairDesc& d) {
 void launch_ndtc_linearize(bool d2d, dim3 grid, hipStream_t stream, const PairDesc* d_desc, const NdtcPair* d_pairs) {
   if (d2d) ndtc_linearize_kernel<true><<<grid, 256, 0, stream>>>(d_desc, d_pairs);
   else ndtc_linearize_kernel<false><<<grid, 256, 0, stream>>>(d_desc, d_pairs);
+}
+
+// ---- fast_gicp::FastVGICPCuda plumbing (apd_vgicp_cuda.hip)
+
+bool is_vgc(const gorio_apd* h) { return h->method == GORIO_METHOD_VGICP_CUDA; }
+bool is_voxf(const gorio_apd* h) { return is_ndtc(h) || is_vgc(h); }  // the two methods of the reference's CUDA back end: float voxel maps, no per-point search state
+std::string voxf_name(const gorio_apd* h) { return is_vgc(h) ? "FastVGICPCuda" : "NDTCuda"; }
+
+bool vgc_rbf(const gorio_apd* h) { return h->vgc_nn == GORIO_VGICP_CUDA_NN_GPU_RBF_KERNEL; }
+double vgc_max_dist(const gorio_apd* h) { return h->vgc_maxd > 0.0 ? h->vgc_maxd : 5.0 * h->vgc_width; }  // VI:46-50
+
+// does the stage held by cloud c equal the one this handle would make (each stage rests on the one before it)
+bool vgc_raw_matches(const gorio_apd* h, const DevCloud& c) {
+  if (!c.vc_raw_valid) return false;
+  if (vgc_rbf(h)) return c.vc_rbf && c.vc_width == h->vgc_width && c.vc_maxd == vgc_max_dist(h);
+  return !c.vc_rbf && c.vc_k == h->params.k_correspondences;  // CPU_PARALLEL_KDTREE and GPU_BRUTEFORCE are one path
+}
+bool vgc_kept_matches(const gorio_apd* h, const DevCloud& c) { return vgc_raw_matches(h, c) && c.vc_kept_valid && c.vc_reg == h->params.regularization; }
+bool vgc_map_matches(const gorio_apd* h, const DevCloud& c) { return vgc_kept_matches(h, c) && c.vc_map_valid && c.vc_res == (float)h->voxel_resolution; }
+
+// a cloud other handles hold too carries ONE set of covariances, kept points and map: a sharer that would make any stage HELD
+// differently would rebuild it under the others
+bool vgc_shared_mismatch(const gorio_apd* h, const std::shared_ptr<DevCloud>& cp, bool with_map) {
+  const DevCloud& c = *cp;
+  if (cp.use_count() <= 1) return false;
+  if (c.vc_raw_valid && !vgc_raw_matches(h, c)) return true;
+  if (c.vc_kept_valid && c.vc_reg != h->params.regularization) return true;
+  return with_map && c.vc_map_valid && c.vc_res != (float)h->voxel_resolution;
+}
+
+int vgc_cloud_ready(gorio_apd* h, const DevCloud& c, const char* side) {
+  const gorio_apd_params& p = h->params;
+  if (p.regularization < 0 || p.regularization > 4) return fail(h, GORIO_ERR_UNSUPPORTED, "unknown regularization method");
+  if (vgc_rbf(h) || vgc_raw_matches(h, c)) return GORIO_OK;
+  if (p.k_correspondences < 1 || p.k_correspondences > 32) return fail(h, GORIO_ERR_UNSUPPORTED, "k_correspondences must be in [1, 32]");
+  if (c.n < p.k_correspondences) return fail(h, GORIO_ERR_INVALID, std::string(side) + " cloud has fewer points than k_correspondences (the k-NN list would hold padding)");
+  return GORIO_OK;
+}
+
+int vgc_ready(gorio_apd* h) {
+  if (!h->src->present) return fail(h, GORIO_ERR_STATE, "no input source set (setInputSource)");
+  if (!h->tgt->present) return fail(h, GORIO_ERR_STATE, "no input target set (setInputTarget)");
+  if (h->comm || (h->shard_only && h->comm_world > 1)) return fail(h, GORIO_ERR_STATE, "FastVGICPCuda has no sharded-source mode (gorio_apd_comm_init / gorio_apd_debug_set_shard): use an unsharded handle");
+  if (vgc_shared_mismatch(h, h->tgt, true)) return fail(h, GORIO_ERR_INVALID, "the shared target's FastVGICPCuda covariances / kept points / voxel map were made with other settings: give this handle a target of its own (setInputTarget)");
+  if (vgc_shared_mismatch(h, h->src, false)) return fail(h, GORIO_ERR_INVALID, "the shared source's FastVGICPCuda covariances / kept points were made with other settings: give this handle a source of its own (setInputSource)");
+  if (int rc = vgc_cloud_ready(h, *h->src, "source")) return rc;
+  if (int rc = vgc_cloud_ready(h, *h->tgt, "target")) return rc;
+  if (h->voxel_search == GORIO_VOXEL_DIRECT_RADIUS) return ndtc_check_radius(h, h->ndtc_radius);
+  return GORIO_OK;
+}
+
+// stage 1: the float covariance of every point (VC:183-219)
+int vgc_covariances(gorio_apd* h, DevCloud& c) {
+  if (vgc_raw_matches(h, c)) return GORIO_OK;
+  c.vgc_raw_dropped();
+  const int n = c.n;
+  {
+    const size_t cap = (size_t)n + n / 8 + 64;
+    HIP_TRY(h, reserve_group(c.vc_cap, n, cap, c.vc_raw6, 6 * cap, c.vc_reg6, 6 * cap, c.vc_keep, cap, c.vc_p4, cap, c.vc_cov6, 6 * cap, c.vc_index, cap));
+  }
+  const unsigned int nblk = (unsigned int)((n + 255) / 256);
+  if (vgc_rbf(h)) {  // no list, no search index: every point against every block of 512 (RB:116-151)
+    const int nb = (n + kRbfBlock - 1) / kRbfBlock;
+    // the partials of at most 64 M floats' worth of blocks at a time; the running sums wait in the first chunk's tail between chunks
+    const int per = std::max(1, (int)std::min<size_t>((size_t)nb, ((size_t)64 << 20) / ((size_t)kRbfTerms * n)));
+    HIP_TRY(h, c.vc_part.reserve((size_t)(per + 1) * kRbfTerms * n));
+    float* acc = c.vc_part + (size_t)per * kRbfTerms * n;
+    const float g = (float)h->vgc_width, md = (float)vgc_max_dist(h);
+    for (int b0 = 0; b0 < nb; b0 += per) {
+      const int cnt = std::min(per, nb - b0);
+      vgc_cov_rbf_kernel<<<dim3(nblk, (unsigned int)cnt), 256, 0, h->stream>>>(c.p4, n, b0, g, md * md, c.vc_part);
+      vgc_cov_rbf_fold_kernel<<<nblk, 256, 0, h->stream>>>(c.vc_part, n, cnt, acc, b0 == 0 ? 1 : 0, b0 + cnt == nb ? 1 : 0, c.vc_raw6);
+    }
+    HIP_TRY(h, hipGetLastError());
+    c.vgc_raw_built(true, 0, h->vgc_width, vgc_max_dist(h));
+    return GORIO_OK;
+  }
+  const int k = h->params.k_correspondences;
+  HIP_TRY(h, c.vc_knn.reserve((size_t)n * k));
+  HIP_TRY(h, c.vc_scratch.reserve((size_t)7 * n));
+  {  // the handle's exact k-NN kernels, by params.search (pruned: the search index is built when stale)
+    std::vector<std::pair<gorio_apd*, DevCloud*>> one = {{h, &c}};
+    const KnnListsOnly only = {c.vc_knn, c.vc_scratch, c.vc_scratch + (size_t)6 * n};
+    if (int rc = run_covariances(h, one, &only)) return rc;
+  }
+  vgc_cov_knn_kernel<<<nblk, 256, 0, h->stream>>>(c.p4, c.vc_knn, n, k, c.vc_raw6);
+  HIP_TRY(h, hipGetLastError());
+  c.vgc_raw_built(false, k, 0.0, 0.0);
+  return GORIO_OK;
+}
+
+// stage 2: covariance_regularization (CR:91-117) and the ordered compaction of the points it keeps.  One small read-back (the count).
+int vgc_filter(gorio_apd* h, DevCloud& c) {
+  if (int rc = vgc_covariances(h, c)) return rc;
+  if (vgc_kept_matches(h, c)) return GORIO_OK;
+  c.vgc_kept_dropped();
+  const int n = c.n;
+  const int nblk = (n + 255) / 256;
+  HIP_TRY(h, c.vc_bcnt.reserve(nblk + 1));
+  vgc_regularize_kernel<<<nblk, 256, 0, h->stream>>>(c.vc_raw6, n, h->params.regularization, c.vc_keep, c.vc_reg6);
+  compact_count_kernel<<<nblk, 256, 0, h->stream>>>(c.vc_keep, n, c.vc_bcnt);
+  compact_scan_kernel<<<1, 1024, 0, h->stream>>>(c.vc_bcnt, nblk);
+  vgc_scatter_kernel<<<nblk, 256, 0, h->stream>>>(c.p4, c.vc_reg6, c.vc_keep, n, c.vc_bcnt, c.vc_p4, c.vc_cov6, c.vc_index);
+  HIP_TRY(h, hipGetLastError());
+  int nkept = 0;
+  HIP_TRY(h, hipMemcpyAsync(&nkept, c.vc_bcnt + nblk, sizeof(int), hipMemcpyDeviceToHost, h->stream));
+  HIP_TRY(h, hipStreamSynchronize(h->stream));
+  if (nkept < 0 || nkept > n) return fail(h, GORIO_ERR_NO_DEVICE, "FastVGICPCuda: inconsistent kept-point count");
+  c.vgc_kept_built(h->params.regularization, nkept);
+  return GORIO_OK;
+}
+
+// stage 3: the voxel map of the kept points (GV:229-252).  No kept point: an empty map, in which every lookup misses.  Deviation from
+// the reference: a changed resolution rebuilds the map (VI:41-43, 145; VC:257-263).
+int build_vgc_map(gorio_apd* h, DevCloud& c) {
+  if (int rc = vgc_filter(h, c)) return rc;
+  if (vgc_map_matches(h, c)) return GORIO_OK;
+  c.vgc_map_dropped();
+  const float res = (float)h->voxel_resolution;
+  const int n = c.vc_nkept;
+  NdtcBox g = {{0, 0, 0}, {0, 0, 0}, res};
+  int nv = 0;
+  if (n > 0) {
+    if (int rc = ndtc_voxel_starts(h, c, c.vc_p4, n, res, g, nv)) return rc;
+    const size_t cap = nv + nv / 8 + 64;
+    HIP_TRY(h, reserve_group(c.vc_mcap, nv, cap, c.vc_vkey, cap, c.vc_mean, 3 * cap, c.vc_mcov6, 6 * cap, c.vc_num, cap));
+    vgc_accum_kernel<<<(n + 255) / 256, 256, 0, h->stream>>>(c.vm_keys, c.vc_p4, c.vc_cov6, n, c.vm_counts, c.vc_vkey, c.vc_mean, c.vc_mcov6, c.vc_num);
+    HIP_TRY(h, hipGetLastError());
+  }
+  c.vc_nv = nv;
+  for (int a = 0; a < 3; ++a) {
+    c.vc_min[a] = g.min_c[a];
+    c.vc_dim[a] = g.dim[a];
+  }
+  c.vc_res = res;
+  c.vgc_map_built();
+  return GORIO_OK;
+}
+
+// everything a linearisation needs: both clouds filtered, the target's map, the offset and slot tables over the kept source points
+int ensure_vgc_pair(gorio_apd* h) {
+  int rc = vgc_filter(h, *h->src);
+  if (!rc) rc = build_vgc_map(h, *h->tgt);
+  if (rc) return rc;
+  return ensure_ndtc_slots(h, h->src->vc_nkept, 2);
+}
+
+bool vgc_same_settings(const gorio_apd* a, const gorio_apd* b) {
+  return a->voxel_resolution == b->voxel_resolution && a->voxel_search == b->voxel_search &&
+         (a->voxel_search != GORIO_VOXEL_DIRECT_RADIUS || a->ndtc_radius == b->ndtc_radius) && a->vgc_nn == b->vgc_nn && a->vgc_width == b->vgc_width &&
+         a->vgc_maxd == b->vgc_maxd;
+}
+
+int voxf_ready(gorio_apd* h) { return is_vgc(h) ? vgc_ready(h) : ndtc_ready(h); }
+int ensure_voxf_pair(gorio_apd* h) { return is_vgc(h) ? ensure_vgc_pair(h) : ensure_ndtc_pair(h); }
+
+// the linearisation launch and the shell launch of the slot table HELD (ndtc_slot_d2d of the lead in a batch: the settings agree)
+void launch_voxf_linearize(const gorio_apd* h, dim3 grid, const PairDesc* d_desc, const NdtcPair* d_pairs) {
+  if (h->ndtc_slot_d2d == 2) vgc_linearize_kernel<<<grid, 256, 0, h->stream>>>(d_desc, d_pairs);
+  else launch_ndtc_linearize(h->ndtc_slot_d2d != 0, grid, h->stream, d_desc, d_pairs);
+}
+void launch_voxf_solve(const gorio_apd* h, dim3 grid, const PairDesc* d_desc, const NdtcPair* d_pairs, const ApdConsts& cst, int mode) {
+  if (is_vgc(h)) lm_solve_vgc_kernel<<<grid, 1024, 0, h->stream>>>(d_desc, d_pairs, cst, mode);
+  else lm_solve_ndtc_kernel<<<grid, 1024, 0, h->stream>>>(d_desc, d_pairs, cst, mode);
 }
 
 // the compile-time variants behind one call (kMethodApd stays the instantiation every APD-GICP caller runs)
@@ -1179,17 +1419,19 @@ int align_impl(gorio_apd** hs, int count, const float* guesses, float* T_out, do
         return fail(lead, GORIO_ERR_INVALID, "all FastVGICP handles of a batch must carry the same voxel_resolution / voxel_search / voxel_mode");
       if (is_ndtc(h) && !ndtc_same_settings(h, lead))
         return fail(lead, GORIO_ERR_INVALID, "all NDTCuda handles of a batch must carry the same resolution / neighbour offsets / distance mode");
+      if (is_vgc(h) && !vgc_same_settings(h, lead))
+        return fail(lead, GORIO_ERR_INVALID, "all FastVGICPCuda handles of a batch must carry the same resolution / neighbour offsets / neighbour method / kernel parameters");
     }
-    int rc = is_ndtc(h) ? ndtc_ready(h) : check_ready(h);
+    int rc = is_voxf(h) ? voxf_ready(h) : check_ready(h);
     if (rc) {
       if (h != lead) lead->err = h->err;
       return rc;
     }
-    if (!is_ndtc(h)) rc = ensure_points(h, h->src->n);  // NDTCuda holds no per-point search state
+    if (!is_voxf(h)) rc = ensure_points(h, h->src->n);  // NDTCuda and FastVGICPCuda hold no per-point search state
     if (rc) return rc;
   }
-  const bool ndtc = is_ndtc(lead);
-  // APD:149-154: covariances of whichever cloud is stale (NDTCuda: none, and no search index)
+  const bool ndtc = is_voxf(lead);  // the float voxel back end: NDTCuda or FastVGICPCuda
+  // APD:149-154: covariances of whichever cloud is stale (NDTCuda: none, and no search index; FastVGICPCuda: its own, ensure_vgc_pair)
   std::vector<std::pair<gorio_apd*, DevCloud*>> todo;
   if (!ndtc) {
     std::unordered_set<DevCloud*> seen;  // a target shared by many handles of the batch is estimated once
@@ -1228,7 +1470,7 @@ int align_impl(gorio_apd** hs, int count, const float* guesses, float* T_out, do
   }
   if (ndtc) {  // create_voxelmaps (NI:76-79): a shared cloud's map once, the second sharer finds it valid
     for (int q = 0; q < count; ++q) {
-      rc = ensure_ndtc_pair(hs[q]);
+      rc = ensure_voxf_pair(hs[q]);
       if (rc) {
         if (hs[q] != lead) lead->err = hs[q]->err;
         return rc;
@@ -1350,9 +1592,9 @@ int align_impl(gorio_apd** hs, int count, const float* guesses, float* T_out, do
         continue;
       }
       if (ndtc) {  // update_correspondences + compute_error (NI:82-85) in one launch, then the shell
-        launch_ndtc_linearize(lead->ndtc_mode == GORIO_NDT_CUDA_D2D, g_nlin, lead->stream, lead->d_desc, lead->d_ndtc);
+        launch_voxf_linearize(lead, g_nlin, lead->d_desc, lead->d_ndtc);
         chain.mark(2);
-        lm_solve_ndtc_kernel<<<g_lm, 1024, 0, lead->stream>>>(lead->d_desc, lead->d_ndtc, cst, 0);
+        launch_voxf_solve(lead, g_lm, lead->d_desc, lead->d_ndtc, cst, 0);
         chain.mark(3);
         continue;
       }
@@ -1422,9 +1664,9 @@ int single_desc(gorio_apd* h, bool solver = false) {
   PairDesc d;
   fill_desc(h, d, h->d_state, (h->src->n + 63) / 64);
   if (solver && h->method == GORIO_METHOD_VGICP) vgicp_desc(h, d);
-  if (solver && is_ndtc(h)) ndtc_desc(h, d);
+  if (solver && is_voxf(h)) ndtc_desc(h, d);
   HIP_TRY(h, hipMemcpyAsync(h->d_desc, &d, sizeof(PairDesc), hipMemcpyHostToDevice, h->stream));
-  if (solver && is_ndtc(h)) {
+  if (solver && is_voxf(h)) {
     HIP_TRY(h, h->d_ndtc.reserve(1));
     const NdtcPair p = make_ndtc_pair(h);
     HIP_TRY(h, hipMemcpyAsync(h->d_ndtc, &p, sizeof(NdtcPair), hipMemcpyHostToDevice, h->stream));
@@ -1530,11 +1772,11 @@ int gorio_apd_get_params(const gorio_apd_t* h, gorio_apd_params* p) {
 
 int gorio_apd_set_method(gorio_apd_t* h, int method, double voxel_resolution, int voxel_search, int voxel_mode) {
   if (!h) return GORIO_ERR_INVALID;
-  if (method != GORIO_METHOD_APDGICP && method != GORIO_METHOD_GICP && method != GORIO_METHOD_VGICP && method != GORIO_METHOD_GICP_OMP && method != GORIO_METHOD_ICP && method != GORIO_METHOD_NDT_CUDA) return fail(h, GORIO_ERR_UNSUPPORTED, "set_method: unknown registration method");
-  if (method == GORIO_METHOD_NDT_CUDA) {  // voxel_resolution = setResolution, voxel_search = setNeighborSearchMethod (DIRECT_RADIUS with the radius of gorio_apd_set_ndt_cuda_params); voxel_mode is ignored
+  if (method != GORIO_METHOD_APDGICP && method != GORIO_METHOD_GICP && method != GORIO_METHOD_VGICP && method != GORIO_METHOD_GICP_OMP && method != GORIO_METHOD_ICP && method != GORIO_METHOD_NDT_CUDA && method != GORIO_METHOD_VGICP_CUDA) return fail(h, GORIO_ERR_UNSUPPORTED, "set_method: unknown registration method");
+  if (method == GORIO_METHOD_NDT_CUDA || method == GORIO_METHOD_VGICP_CUDA) {  // voxel_resolution = setResolution, voxel_search = setNeighborSearchMethod (DIRECT_RADIUS with the radius of gorio_apd_set_ndt_cuda_params); voxel_mode is ignored
     if (voxel_search != GORIO_VOXEL_DIRECT27 && voxel_search != GORIO_VOXEL_DIRECT7 && voxel_search != GORIO_VOXEL_DIRECT1 && voxel_search != GORIO_VOXEL_DIRECT_RADIUS) return fail(h, GORIO_ERR_UNSUPPORTED, "set_method: unknown neighbour search method");
     if (!(voxel_resolution > 0.0) || !std::isfinite(voxel_resolution)) return fail(h, GORIO_ERR_UNSUPPORTED, "set_method: voxel_resolution must be positive");
-    if (h->comm || (h->shard_only && h->comm_world > 1)) return fail(h, GORIO_ERR_STATE, "set_method: NDTCuda has no sharded-source mode");
+    if (h->comm || (h->shard_only && h->comm_world > 1)) return fail(h, GORIO_ERR_STATE, "set_method: NDTCuda and FastVGICPCuda have no sharded-source mode");
     if (voxel_search == GORIO_VOXEL_DIRECT_RADIUS)
       if (int rc = ndtc_check_radius(h, h->ndtc_radius)) return rc;
     h->gomp_pairs = -1;
@@ -1653,11 +1895,11 @@ int gorio_apd_set_ndt_cuda_params(gorio_apd_t* h, int distance_mode, double radi
   if (!h) return GORIO_ERR_INVALID;
   if (distance_mode != GORIO_NDT_CUDA_P2D && distance_mode != GORIO_NDT_CUDA_D2D) return fail(h, GORIO_ERR_INVALID, "set_ndt_cuda_params: distance_mode must be P2D (0) or D2D (1)");
   if (std::isnan(radius)) return fail(h, GORIO_ERR_INVALID, "set_ndt_cuda_params: radius is NaN");
-  if (is_ndtc(h) && h->voxel_search == GORIO_VOXEL_DIRECT_RADIUS)  // the radius is in use: it must be a usable one
+  if (is_voxf(h) && h->voxel_search == GORIO_VOXEL_DIRECT_RADIUS)  // the radius is in use: it must be a usable one
     if (int rc = ndtc_check_radius(h, radius)) return rc;
   h->ndtc_mode = distance_mode;
   h->ndtc_radius = radius;
-  if (is_ndtc(h)) h->corr_valid = false;  // pairs of another item set or neighbourhood
+  if (is_voxf(h)) h->corr_valid = false;  // pairs of another item set or neighbourhood
   return GORIO_OK;
 }
 
@@ -1714,15 +1956,16 @@ int gorio_apd_ndt_cuda_get_voxels(gorio_apd_t* h, int which, int capacity, int* 
   return GORIO_OK;
 }
 
-int gorio_apd_ndt_cuda_get_pairs(gorio_apd_t* h, int capacity, int* n_pairs, int* item, int* voxel) {
-  if (!h || !n_pairs) return GORIO_ERR_INVALID;
-  if (!is_ndtc(h)) return fail(h, GORIO_ERR_STATE, "ndt_cuda_get_pairs: the handle is not in NDTCuda mode (gorio_apd_set_method)");
-  if (!h->corr_valid || !h->ndtc_slots) return fail(h, GORIO_ERR_STATE, "ndt_cuda_get_pairs: no pairs held (gorio_apd_linearize or an align first)");
+// the pair list of the slot table held, offset-major then item order (both float voxel methods)
+static int voxf_get_pairs(gorio_apd* h, int capacity, int* n_pairs, int* item, int* voxel) {
+  const size_t total = (size_t)h->ndtc_items * h->ndtc_slot_off;  // 0 when FastVGICPCuda's filter kept no source point: an empty list, no slot table
+  if (!h->corr_valid || (total && !h->ndtc_slots)) return fail(h, GORIO_ERR_STATE, "get_pairs: no pairs held (gorio_apd_linearize or an align first)");
   HIP_TRY(h, hipSetDevice(h->device));
-  const size_t total = (size_t)h->ndtc_items * h->ndtc_slot_off;
   std::vector<int> slots(total);
-  HIP_TRY(h, hipMemcpyAsync(slots.data(), h->ndtc_slots, sizeof(int) * total, hipMemcpyDeviceToHost, h->stream));
-  HIP_TRY(h, hipStreamSynchronize(h->stream));
+  if (total) {
+    HIP_TRY(h, hipMemcpyAsync(slots.data(), h->ndtc_slots, sizeof(int) * total, hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+  }
   int np = 0;
   for (size_t t = 0; t < total; ++t) np += slots[t] >= 0;
   *n_pairs = np;
@@ -1735,6 +1978,89 @@ int gorio_apd_ndt_cuda_get_pairs(gorio_apd_t* h, int capacity, int* n_pairs, int
     ++w;
   }
   return GORIO_OK;
+}
+
+int gorio_apd_ndt_cuda_get_pairs(gorio_apd_t* h, int capacity, int* n_pairs, int* item, int* voxel) {
+  if (!h || !n_pairs) return GORIO_ERR_INVALID;
+  if (!is_ndtc(h)) return fail(h, GORIO_ERR_STATE, "ndt_cuda_get_pairs: the handle is not in NDTCuda mode (gorio_apd_set_method)");
+  return voxf_get_pairs(h, capacity, n_pairs, item, voxel);
+}
+
+int gorio_apd_set_vgicp_cuda_params(gorio_apd_t* h, int nn_method, double kernel_width, double kernel_max_dist) {
+  if (!h) return GORIO_ERR_INVALID;
+  if (nn_method != GORIO_VGICP_CUDA_NN_CPU_PARALLEL_KDTREE && nn_method != GORIO_VGICP_CUDA_NN_GPU_BRUTEFORCE && nn_method != GORIO_VGICP_CUDA_NN_GPU_RBF_KERNEL)
+    return fail(h, GORIO_ERR_INVALID, "set_vgicp_cuda_params: nn_method must be CPU_PARALLEL_KDTREE (0), GPU_BRUTEFORCE (1) or GPU_RBF_KERNEL (2)");
+  if (!std::isfinite(kernel_width) || !std::isfinite(kernel_max_dist)) return fail(h, GORIO_ERR_INVALID, "set_vgicp_cuda_params: kernel_width and kernel_max_dist must be finite");
+  if (!(kernel_width > 0.0)) return fail(h, GORIO_ERR_INVALID, "set_vgicp_cuda_params: kernel_width must be positive");
+  h->vgc_nn = nn_method;
+  h->vgc_width = kernel_width;
+  h->vgc_maxd = kernel_max_dist;
+  if (is_vgc(h)) h->corr_valid = false;  // pairs of other kept points
+  return GORIO_OK;
+}
+
+int gorio_apd_get_vgicp_cuda_params(const gorio_apd_t* h, int* nn_method, double* kernel_width, double* kernel_max_dist) {
+  if (!h) return GORIO_ERR_INVALID;
+  if (nn_method) *nn_method = h->vgc_nn;
+  if (kernel_width) *kernel_width = h->vgc_width;
+  if (kernel_max_dist) *kernel_max_dist = h->vgc_maxd;
+  return GORIO_OK;
+}
+
+int gorio_apd_vgicp_cuda_get_points(gorio_apd_t* h, int which, int capacity, int* n, float* cov_raw, int* n_kept, int* kept_index, float* cov) {
+  if (!h || !n || !n_kept || (which != 0 && which != 1)) return GORIO_ERR_INVALID;
+  if (!is_vgc(h)) return fail(h, GORIO_ERR_STATE, "vgicp_cuda_get_points: the handle is not in FastVGICPCuda mode (gorio_apd_set_method)");
+  HIP_TRY(h, hipSetDevice(h->device));
+  const std::shared_ptr<DevCloud>& cp = which == 0 ? h->src : h->tgt;
+  DevCloud& c = *cp;
+  if (!c.present) return fail(h, GORIO_ERR_STATE, "vgicp_cuda_get_points: that cloud is not set");
+  if (vgc_shared_mismatch(h, cp, false)) return fail(h, GORIO_ERR_INVALID, "vgicp_cuda_get_points: the shared cloud's covariances / kept points were made with other settings");
+  if (int rc = vgc_cloud_ready(h, c, which == 0 ? "source" : "target")) return rc;
+  if (int rc = vgc_filter(h, c)) return rc;
+  *n = c.n;
+  *n_kept = c.vc_nkept;
+  if (capacity < c.n) return GORIO_OK;
+  if (cov_raw) HIP_TRY(h, hipMemcpyAsync(cov_raw, c.vc_raw6, sizeof(float) * 6 * c.n, hipMemcpyDeviceToHost, h->stream));
+  if (kept_index && c.vc_nkept) HIP_TRY(h, hipMemcpyAsync(kept_index, c.vc_index, sizeof(int) * c.vc_nkept, hipMemcpyDeviceToHost, h->stream));
+  if (cov && c.vc_nkept) HIP_TRY(h, hipMemcpyAsync(cov, c.vc_cov6, sizeof(float) * 6 * c.vc_nkept, hipMemcpyDeviceToHost, h->stream));
+  HIP_TRY(h, hipStreamSynchronize(h->stream));
+  return GORIO_OK;
+}
+
+int gorio_apd_vgicp_cuda_get_voxels(gorio_apd_t* h, int capacity, int* n_voxels, int* coords, int* num_points, float* mean, float* cov) {
+  if (!h || !n_voxels) return GORIO_ERR_INVALID;
+  if (!is_vgc(h)) return fail(h, GORIO_ERR_STATE, "vgicp_cuda_get_voxels: the handle is not in FastVGICPCuda mode (gorio_apd_set_method)");
+  HIP_TRY(h, hipSetDevice(h->device));
+  DevCloud& c = *h->tgt;  // there is no source map (VC:257-263)
+  if (!c.present) return fail(h, GORIO_ERR_STATE, "vgicp_cuda_get_voxels: no input target set (setInputTarget)");
+  if (vgc_shared_mismatch(h, h->tgt, true)) return fail(h, GORIO_ERR_INVALID, "vgicp_cuda_get_voxels: the shared target's covariances / kept points / voxel map were made with other settings");
+  if (int rc = vgc_cloud_ready(h, c, "target")) return rc;
+  if (int rc = build_vgc_map(h, c)) return rc;
+  const int nv = c.vc_nv;
+  *n_voxels = nv;
+  if (capacity < nv || nv == 0 || (!coords && !num_points && !mean && !cov)) return GORIO_OK;
+  std::vector<unsigned long long> vkey(nv);
+  HIP_TRY(h, hipMemcpyAsync(vkey.data(), c.vc_vkey, sizeof(unsigned long long) * nv, hipMemcpyDeviceToHost, h->stream));
+  if (num_points) HIP_TRY(h, hipMemcpyAsync(num_points, c.vc_num, sizeof(int) * nv, hipMemcpyDeviceToHost, h->stream));
+  if (mean) HIP_TRY(h, hipMemcpyAsync(mean, c.vc_mean, sizeof(float) * 3 * nv, hipMemcpyDeviceToHost, h->stream));
+  if (cov) HIP_TRY(h, hipMemcpyAsync(cov, c.vc_mcov6, sizeof(float) * 6 * nv, hipMemcpyDeviceToHost, h->stream));
+  HIP_TRY(h, hipStreamSynchronize(h->stream));
+  if (coords) {
+    const unsigned long long d1 = (unsigned long long)c.vc_dim[1], d2 = (unsigned long long)c.vc_dim[2];
+    for (int v = 0; v < nv; ++v) {
+      const unsigned long long id = vkey[v];
+      coords[3 * (size_t)v + 2] = (int)(id % d2) + c.vc_min[2];
+      coords[3 * (size_t)v + 1] = (int)((id / d2) % d1) + c.vc_min[1];
+      coords[3 * (size_t)v] = (int)(id / (d2 * d1)) + c.vc_min[0];
+    }
+  }
+  return GORIO_OK;
+}
+
+int gorio_apd_vgicp_cuda_get_pairs(gorio_apd_t* h, int capacity, int* n_pairs, int* item, int* voxel) {
+  if (!h || !n_pairs) return GORIO_ERR_INVALID;
+  if (!is_vgc(h)) return fail(h, GORIO_ERR_STATE, "vgicp_cuda_get_pairs: the handle is not in FastVGICPCuda mode (gorio_apd_set_method)");
+  return voxf_get_pairs(h, capacity, n_pairs, item, voxel);
 }
 
 int gorio_apd_set_source(gorio_apd_t* h, const float* xyz, const float* label, int n, int stride) {
@@ -1828,6 +2154,11 @@ int gorio_apd_set_target_shared(gorio_apd_t* h, gorio_apd_t* owner) {
   }
   if (is_ndtc(h) && owner->tgt->nc_valid && owner->tgt->nc_res != (float)h->voxel_resolution)
     return fail(h, GORIO_ERR_INVALID, "set_target_shared: the owner's NDTCuda voxel map was built with another resolution than this handle's");
+  if (is_vgc(h)) {
+    const DevCloud& t = *owner->tgt;
+    if ((t.vc_raw_valid && !vgc_raw_matches(h, t)) || (t.vc_kept_valid && t.vc_reg != h->params.regularization) || (t.vc_map_valid && t.vc_res != (float)h->voxel_resolution))
+      return fail(h, GORIO_ERR_INVALID, "set_target_shared: the owner's FastVGICPCuda covariances / kept points / voxel map were made with other settings than this handle's");
+  }
   h->tgt = owner->tgt;  // points, covariances, search index, voxel map: one copy on the device, alive until the last handle lets go of it
   h->corr_valid = false;
   return GORIO_OK;
@@ -1963,7 +2294,7 @@ int gorio_apd_swap_source_and_target(gorio_apd_t* h) {
 }
 
 static int set_covs(gorio_apd* h, DevCloud& c, const double* cov, int n) {
-  if (is_ndtc(h)) return fail(h, GORIO_ERR_STATE, "set_covariances: NDTCuda has no per-point covariances");
+  if (is_voxf(h)) return fail(h, GORIO_ERR_STATE, "set_covariances: " + voxf_name(h) + " takes no per-point double covariances");
   if (n < 0 || (n > 0 && !cov)) return fail(h, GORIO_ERR_INVALID, "set_covariances: bad arguments");
   if (!c.present || n != c.n) {
     // the reference stores the vector whatever its size (APD:138-145) and recomputes the covariances in computeTransformation when the
@@ -1990,7 +2321,7 @@ int gorio_apd_set_source_covariances(gorio_apd_t* h, const double* cov, int n) {
 int gorio_apd_set_target_covariances(gorio_apd_t* h, const double* cov, int n) { return h ? set_covs(h, *h->tgt, cov, n) : GORIO_ERR_INVALID; }
 
 static int get_covs(gorio_apd* h, DevCloud& c, double* cov, int n) {
-  if (is_ndtc(h)) return fail(h, GORIO_ERR_STATE, "get_covariances: NDTCuda has no per-point covariances");
+  if (is_voxf(h)) return fail(h, GORIO_ERR_STATE, "get_covariances: " + voxf_name(h) + " holds no per-point double covariances");
   const int cnt = c.present ? c.cov_count : 0;
   if (!cov || cnt == 0) return cnt;
   const int m = n < cnt ? n : cnt;
@@ -2013,7 +2344,7 @@ int gorio_apd_get_target_covariances(gorio_apd_t* h, double* cov, int n) { retur
 
 int gorio_apd_calculate_covariances(gorio_apd_t* h) {
   if (!h) return GORIO_ERR_INVALID;
-  if (is_ndtc(h)) return fail(h, GORIO_ERR_STATE, "calculate_covariances: NDTCuda has no per-point covariances");
+  if (is_voxf(h)) return fail(h, GORIO_ERR_STATE, "calculate_covariances: " + voxf_name(h) + " has no per-point double covariances");
   HIP_TRY(h, hipSetDevice(h->device));
   const gorio_apd_params& p = h->params;
   std::vector<std::pair<gorio_apd*, DevCloud*>> todo;
@@ -2066,9 +2397,9 @@ int gorio_apd_linearize(gorio_apd_t* h, const double T[16], double* H, double* b
   if (h->method == GORIO_METHOD_GICP_OMP) return fail(h, GORIO_ERR_UNSUPPORTED, "linearize: GICP_OMP has no Gauss-Newton linearisation (gorio_apd_gicp_omp_update / _evaluate)");
   if (h->method == GORIO_METHOD_ICP) return fail(h, GORIO_ERR_UNSUPPORTED, "linearize: ICP has no Gauss-Newton linearisation (gorio_apd_icp_step)");
   HIP_TRY(h, hipSetDevice(h->device));
-  if (is_ndtc(h)) {  // NI:82-85: update_correspondences(trans), then compute_error(trans, H, b) over the fresh pairs
-    int rc = ndtc_ready(h);
-    if (!rc) rc = ensure_ndtc_pair(h);
+  if (is_voxf(h)) {  // NI:82-85, VI:170-173: update_correspondences(trans), then compute_error(trans, H, b) over the fresh pairs
+    int rc = voxf_ready(h);
+    if (!rc) rc = ensure_voxf_pair(h);
     if (!rc) rc = single_desc(h, true);
     if (rc) return rc;
     PairState s;
@@ -2076,8 +2407,8 @@ int gorio_apd_linearize(gorio_apd_t* h, const double T[16], double* H, double* b
     HIP_TRY(h, hipMemcpyAsync(h->d_state, &s, sizeof(s), hipMemcpyHostToDevice, h->stream));
     const ApdConsts cst = make_consts(h->params);
     const unsigned int nblk = (unsigned int)(((size_t)h->ndtc_items * h->ndtc_slot_off + 255) / 256);
-    launch_ndtc_linearize(h->ndtc_slot_d2d != 0, dim3(nblk, 1, 1), h->stream, h->d_desc, h->d_ndtc);
-    lm_solve_ndtc_kernel<<<1, 1024, 0, h->stream>>>(h->d_desc, h->d_ndtc, cst, 1);
+    if (nblk) launch_voxf_linearize(h, dim3(nblk, 1, 1), h->d_desc, h->d_ndtc);  // no kept source point: no slot, zero sums
+    launch_voxf_solve(h, dim3(1), h->d_desc, h->d_ndtc, cst, 1);
     HIP_TRY(h, hipGetLastError());
     HIP_TRY(h, hipMemcpyAsync(&s, h->d_state, sizeof(s), hipMemcpyDeviceToHost, h->stream));
     HIP_TRY(h, hipStreamSynchronize(h->stream));
@@ -2149,7 +2480,7 @@ int gorio_apd_compute_error(gorio_apd_t* h, const double T[16], double* error) {
   if (h->method == GORIO_METHOD_GICP_OMP) return fail(h, GORIO_ERR_UNSUPPORTED, "compute_error: GICP_OMP evaluates its functor through gorio_apd_gicp_omp_evaluate");
   if (h->method == GORIO_METHOD_ICP) return fail(h, GORIO_ERR_UNSUPPORTED, "compute_error: ICP has no weighted error (gorio_apd_icp_diag gives the mean squared distance)");
   HIP_TRY(h, hipSetDevice(h->device));
-  if (is_ndtc(h) ? !h->corr_valid : (!h->corr_valid || !h->omega_valid)) return fail(h, GORIO_ERR_STATE, "compute_error needs the correspondences and Mahalanobis matrices of a previous linearize (or LM align)");
+  if (is_voxf(h) ? !h->corr_valid : (!h->corr_valid || !h->omega_valid)) return fail(h, GORIO_ERR_STATE, "compute_error needs the correspondences and Mahalanobis matrices of a previous linearize (or LM align)");
   int rc = single_desc(h, true);
   if (rc) return rc;
   double xi[16];
@@ -2157,8 +2488,8 @@ int gorio_apd_compute_error(gorio_apd_t* h, const double T[16], double* error) {
   HIP_TRY(h, hipMemcpyAsync(reinterpret_cast<char*>(h->d_state.get()) + offsetof(PairState, xi), xi, sizeof(xi), hipMemcpyHostToDevice, h->stream));
   const ApdConsts cst = make_consts(h->params);
   double yi = 0.0;
-  if (is_ndtc(h)) {  // NC:162-177 over the stale pairs, R_lin of the last linearise
-    lm_solve_ndtc_kernel<<<1, 1024, 0, h->stream>>>(h->d_desc, h->d_ndtc, cst, 2);
+  if (is_voxf(h)) {  // NC:162-177, VC:276-284 over the stale pairs, R_lin of the last linearise
+    launch_voxf_solve(h, dim3(1), h->d_desc, h->d_ndtc, cst, 2);
     HIP_TRY(h, hipGetLastError());
     HIP_TRY(h, hipMemcpyAsync(&yi, reinterpret_cast<char*>(h->d_state.get()) + offsetof(PairState, yi), sizeof(double), hipMemcpyDeviceToHost, h->stream));
     HIP_TRY(h, hipStreamSynchronize(h->stream));
@@ -2184,7 +2515,7 @@ int gorio_apd_compute_error(gorio_apd_t* h, const double T[16], double* error) {
 int gorio_apd_get_correspondences(gorio_apd_t* h, int* corr, float* sq_dist, int n) {
   if (!h) return GORIO_ERR_INVALID;
   if (h->method == GORIO_METHOD_VGICP) return fail(h, GORIO_ERR_STATE, "get_correspondences: FastVGICP pairs points with voxels, not with target points (gorio_apd_get_voxel_correspondences)");
-  if (is_ndtc(h)) return fail(h, GORIO_ERR_STATE, "get_correspondences: NDTCuda pairs items with voxels, not with target points (gorio_apd_ndt_cuda_get_pairs)");
+  if (is_voxf(h)) return fail(h, GORIO_ERR_STATE, "get_correspondences: " + voxf_name(h) + " pairs items with voxels, not with target points (gorio_apd_ndt_cuda_get_pairs / gorio_apd_vgicp_cuda_get_pairs)");
   if (!h->corr_valid) return fail(h, GORIO_ERR_STATE, "no correspondences held");
   if (n != h->src->n) return fail(h, GORIO_ERR_INVALID, "get_correspondences: size mismatch");
   HIP_TRY(h, hipSetDevice(h->device));
@@ -2198,7 +2529,7 @@ int gorio_apd_get_mahalanobis(gorio_apd_t* h, double* maha, int n) {
   if (!h || !maha) return GORIO_ERR_INVALID;
   if (h->method == GORIO_METHOD_VGICP) return fail(h, GORIO_ERR_STATE, "get_mahalanobis: FastVGICP holds one matrix per (point, voxel) pair, not per point");
   if (h->method == GORIO_METHOD_ICP) return fail(h, GORIO_ERR_STATE, "get_mahalanobis: ICP holds no Mahalanobis matrices");
-  if (is_ndtc(h)) return fail(h, GORIO_ERR_STATE, "get_mahalanobis: NDTCuda holds no Mahalanobis matrices (they are recomputed per pair)");
+  if (is_voxf(h)) return fail(h, GORIO_ERR_STATE, "get_mahalanobis: " + voxf_name(h) + " holds no Mahalanobis matrices (they are recomputed per pair)");
   if (!h->corr_valid || !h->omega_valid) return fail(h, GORIO_ERR_STATE, "no Mahalanobis matrices held (a Gauss-Newton align does not materialise them: call gorio_apd_linearize)");
   if (n != h->src->n) return fail(h, GORIO_ERR_INVALID, "get_mahalanobis: size mismatch");
   HIP_TRY(h, hipSetDevice(h->device));
@@ -2416,7 +2747,7 @@ int gorio_apd_comm_init(gorio_apd_t* h, int world_size, int rank, const char id[
   if (!h || !id || world_size < 1 || rank < 0 || rank >= world_size) return GORIO_ERR_INVALID;
   if (h->method == GORIO_METHOD_VGICP) return fail(h, GORIO_ERR_STATE, "comm_init: FastVGICP has no sharded-source mode");
   if (h->method == GORIO_METHOD_ICP) return fail(h, GORIO_ERR_STATE, "comm_init: ICP has no sharded-source mode");
-  if (is_ndtc(h)) return fail(h, GORIO_ERR_STATE, "comm_init: NDTCuda has no sharded-source mode");
+  if (is_voxf(h)) return fail(h, GORIO_ERR_STATE, "comm_init: " + voxf_name(h) + " has no sharded-source mode");
   Rccl& R = rccl();
   if (!R.ok) return fail(h, GORIO_ERR_NO_DEVICE, "librccl could not be loaded");
   HIP_TRY(h, hipSetDevice(h->device));
@@ -2453,7 +2784,7 @@ int gorio_apd_debug_set_shard(gorio_apd_t* h, int world_size, int rank) {
   if (!h || world_size < 1 || rank < 0 || rank >= world_size) return GORIO_ERR_INVALID;
   if (h->comm) return fail(h, GORIO_ERR_STATE, "debug_set_shard: the handle has a communicator");
   if (h->method == GORIO_METHOD_ICP && world_size > 1) return fail(h, GORIO_ERR_STATE, "debug_set_shard: ICP has no sharded-source mode");
-  if (is_ndtc(h) && world_size > 1) return fail(h, GORIO_ERR_STATE, "debug_set_shard: NDTCuda has no sharded-source mode");
+  if (is_voxf(h) && world_size > 1) return fail(h, GORIO_ERR_STATE, "debug_set_shard: " + voxf_name(h) + " has no sharded-source mode");
   h->comm_world = world_size;
   h->comm_rank = rank;
   h->shard_only = world_size > 1;

@@ -109,6 +109,7 @@ constexpr int kMethodApd = 0;    // fast_gicp::FastAPDGICP
 constexpr int kMethodGicp = 1;   // fast_gicp::FastGICP
 constexpr int kMethodVgicp = 2;  // fast_gicp::FastVGICP
 constexpr int kMethodNdtCuda = 3;  // fast_gicp::NDTCuda (lm_solve_body only: its linearisation is ndtc_linearize_kernel)
+constexpr int kMethodVgicpCuda = 4;  // fast_gicp::FastVGICPCuda (lm_solve_body only: its linearisation is vgc_linearize_kernel)
 
 // Gaussian voxel map of a target cloud (GaussianVoxelMap, fast_vgicp_voxel.hpp:124-182): the occupied voxels in ASCENDING order of their
 // linear id ((cx - min.x) * dim.y + (cy - min.y)) * dim.z + (cz - min.z) inside the bounding box of the occupied coordinates, i.e. in
@@ -159,7 +160,7 @@ struct NdtcPair {
   int item_stride;
   int n_items;
   int n_off;
-  int d2d;
+  int d2d;                 // 0 P2D, 1 D2D; 2: the items are FastVGICPCuda's kept source points with their covariances (apd_vgicp_cuda.hip)
 };
 
 // XCD-aware placement of a (x, y, units) launch whose third grid dimension counts independent units (scan pairs, clouds): the hardware

@@ -481,7 +481,8 @@ __device__ __forceinline__ double residual_terms(const double* __restrict__ T, f
 __device__ void gn_step_tail(const PairDesc& pd, const ApdConsts& cst);
 // this thread's part of FastVGICP::compute_error over the pairs of the last linearise (apd_voxel.hip)
 __device__ double vgicp_error_part(const PairDesc& pd, const VoxPair& vp, const double* __restrict__ T);
-__device__ double ndtc_error_part(const PairDesc& pd, const NdtcPair& np, const double* __restrict__ T);  // apd_ndt_cuda.hip
+template <bool VGICP>  // apd_ndt_cuda.hip; VGICP: the pair term of fast_gicp::FastVGICPCuda (apd_vgicp_cuda.hip)
+__device__ double ndtc_error_part(const PairDesc& pd, const NdtcPair& np, const double* __restrict__ T);
 
 __device__ __forceinline__ float sumsq2_f(float a, float b) {  // x^2 + y^2 in float, un-fused (APD:198 squares floats)
   float r = a * a;
@@ -804,7 +805,8 @@ __device__ bool is_converged(const double* __restrict__ delta, double inv_rot_ep
 
 // compute_error (APD:310-346) over all source points of one pair by one workgroup; result valid on every thread
 // (kMethodGicp: GICP:234-257, no weight; kMethodVgicp: VG:183-204 over the slot table of the last linearise, apd_voxel.hip;
-// kMethodNdtCuda: NC:162-177 over the slot table of the last linearise, apd_ndt_cuda.hip).  AUX: VoxPair, or NdtcPair for kMethodNdtCuda
+// kMethodNdtCuda: NC:162-177 over the slot table of the last linearise, apd_ndt_cuda.hip; kMethodVgicpCuda: CD:106-135 likewise,
+// apd_vgicp_cuda.hip).  AUX: VoxPair, or NdtcPair for kMethodNdtCuda and kMethodVgicpCuda
 template <int METHOD, typename AUX>
 __device__ double block_error(const PairDesc& pd, const AUX* __restrict__ vp, const double* __restrict__ T, const ApdConsts& cst, double* __restrict__ sred) {
   const int n = pd.src.n;
@@ -812,7 +814,9 @@ __device__ double block_error(const PairDesc& pd, const AUX* __restrict__ vp, co
   if constexpr (METHOD == kMethodVgicp) {
     sum = vgicp_error_part(pd, *vp, T);
   } else if constexpr (METHOD == kMethodNdtCuda) {
-    sum = ndtc_error_part(pd, *vp, T);
+    sum = ndtc_error_part<false>(pd, *vp, T);
+  } else if constexpr (METHOD == kMethodVgicpCuda) {
+    sum = ndtc_error_part<true>(pd, *vp, T);
   } else {
     for (int i = threadIdx.x; i < n; i += blockDim.x) {
       const int j = pd.corr[i];
@@ -989,6 +993,10 @@ __global__ __launch_bounds__(1024) void lm_solve_vgicp_kernel(const PairDesc* __
 // fast_gicp::NDTCuda: the same shell over the (item, voxel) pairs of apd_ndt_cuda.hip
 __global__ __launch_bounds__(1024) void lm_solve_ndtc_kernel(const PairDesc* __restrict__ descs, const NdtcPair* __restrict__ pairs, ApdConsts cst, int mode) {
   lm_solve_body<kMethodNdtCuda>(descs[blockIdx.x], pairs + blockIdx.x, cst, mode);
+}
+// fast_gicp::FastVGICPCuda: the same shell over the (kept point, voxel) pairs of apd_vgicp_cuda.hip
+__global__ __launch_bounds__(1024) void lm_solve_vgc_kernel(const PairDesc* __restrict__ descs, const NdtcPair* __restrict__ pairs, ApdConsts cst, int mode) {
+  lm_solve_body<kMethodVgicpCuda>(descs[blockIdx.x], pairs + blockIdx.x, cst, mode);
 }
 
 // The Gauss-Newton case of lm_solve_body (mode 0, optimizer 0) for the last workgroup of linearize_kernel: the same sums in the same

@@ -150,7 +150,8 @@ __device__ __forceinline__ void ndtc_transform(const float* __restrict__ T, floa
 // Order (the restatement's pair_terms): a' = R a + t; e = mean_B - a'; Q = cov_B (+ (R_l cov_A) R_l^T); C = adj(Q) / det(Q) with
 // adj as written below and det = (q00 c00 + q01 c10) + q02 c20; w = k^2 / (k^2 + n n), n = sqrtf((e0 e0 + e1 e1) + e2 e2);
 // J = [skew(a') | -I]; A = w J^T; B = A C; H = B J; b = B e; err = ((w e)^T C) e; every 3-term sum left to right, zeros included.
-template <bool D2D, bool ERR_ONLY>
+// VGICP (fast_gicp::FastVGICPCuda, apd_vgicp_cuda.hip; CD:50-92): the same terms with w = sqrtf((float)num_points) instead of the Cauchy kernel.
+template <bool D2D, bool ERR_ONLY, bool VGICP = false>
 __device__ __forceinline__ void ndtc_pair_terms(const NdtcPair& np, int item, int v, const float* __restrict__ Te, const float* __restrict__ Tl, float ax, float ay, float az,
                                                 float (&out)[28]) {
   float a[3];
@@ -192,9 +193,14 @@ __device__ __forceinline__ void ndtc_pair_terms(const NdtcPair& np, int item, in
   for (int i = 0; i < 3; ++i)
 #pragma unroll
     for (int j = 0; j < 3; ++j) c[i][j] = c[i][j] / det;
-  const float k2 = np.map.res * np.map.res;
-  const float nrm = sqrtf((e[0] * e[0] + e[1] * e[1]) + e[2] * e[2]);
-  const float w = k2 / (k2 + nrm * nrm);
+  float w;
+  if constexpr (VGICP) {
+    w = sqrtf((float)np.map.num[v]);
+  } else {
+    const float k2 = np.map.res * np.map.res;
+    const float nrm = sqrtf((e[0] * e[0] + e[1] * e[1]) + e[2] * e[2]);
+    w = k2 / (k2 + nrm * nrm);
+  }
   {
     const float we0 = w * e[0], we1 = w * e[1], we2 = w * e[2];
     const float u0 = (we0 * c[0][0] + we1 * c[1][0]) + we2 * c[2][0];
@@ -227,8 +233,8 @@ __device__ __forceinline__ void ndtc_item(const NdtcPair& np, int i, float& x, f
 }
 
 // The linearisation of one pair's slots by one workgroup: called by the single and the batched launch alike (grid z = pair), so a batch
-// returns the single align's bits.  Slot t = o * n_items + i (offset-major, FV:83-111).
-template <bool D2D>
+// returns the single align's bits.  Slot t = o * n_items + i (offset-major, FV:83-111).  VGICP: no num_points gate (CD:50-92).
+template <bool D2D, bool VGICP = false>
 __device__ __forceinline__ void ndtc_linearize_body(const PairDesc& pd, const NdtcPair& np, unsigned int bx) {
   const PairState* __restrict__ st = pd.state;
   if (st->done) return;
@@ -255,9 +261,9 @@ __device__ __forceinline__ void ndtc_linearize_body(const PairDesc& pd, const Nd
     const int* off = np.offsets + 3 * o;
     const int v = ok ? voxel_lookup(np.map, c0 + off[0], c1 + off[1], c2 + off[2]) : -1;
     np.slots[t] = v;
-    if (v >= 0 && np.map.num[v] > 6) {  // ND:61, ND:132
+    if (v >= 0 && (VGICP || np.map.num[v] > 6)) {  // ND:61, ND:132
       float out[28];
-      ndtc_pair_terms<D2D, false>(np, i, v, Tf, Tf, ax, ay, az, out);
+      ndtc_pair_terms<D2D, false, VGICP>(np, i, v, Tf, Tf, ax, ay, az, out);
 #pragma unroll
       for (int q = 0; q < 28; ++q) acc[q] = (double)out[q];
     }
@@ -283,7 +289,9 @@ __global__ __launch_bounds__(256) void ndtc_linearize_kernel(const PairDesc* __r
   ndtc_linearize_body<D2D>(descs[gp.z], pairs[gp.z], gp.x);
 }
 
-// compute_error (NC:162-177): the slots of the last linearise at pose T, R_lin from tlin; this thread's strided share
+// compute_error (NC:162-177; VGICP: CD:106-135, no num_points gate): the slots of the last linearise at pose T, R_lin from tlin; this
+// thread's strided share
+template <bool VGICP>
 __device__ double ndtc_error_part(const PairDesc& pd, const NdtcPair& np, const double* __restrict__ T) {
   const long long total = (long long)np.n_items * np.n_off;
   float Te[12], Tl[12];
@@ -295,12 +303,13 @@ __device__ double ndtc_error_part(const PairDesc& pd, const NdtcPair& np, const 
   double sum = 0.0;
   for (long long t = threadIdx.x; t < total; t += blockDim.x) {
     const int v = np.slots[t];
-    if (v < 0 || np.map.num[v] <= 6) continue;
+    if (v < 0 || (!VGICP && np.map.num[v] <= 6)) continue;
     const int i = (int)(t % np.n_items);
     float ax, ay, az;
     ndtc_item(np, i, ax, ay, az);
     float out[28];
-    if (np.d2d) ndtc_pair_terms<true, true>(np, i, v, Te, Tl, ax, ay, az, out);
+    if constexpr (VGICP) ndtc_pair_terms<true, true, true>(np, i, v, Te, Tl, ax, ay, az, out);
+    else if (np.d2d) ndtc_pair_terms<true, true>(np, i, v, Te, Tl, ax, ay, az, out);
     else ndtc_pair_terms<false, true>(np, i, v, Te, Tl, ax, ay, az, out);
     sum += (double)out[27];
   }

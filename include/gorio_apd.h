@@ -53,6 +53,10 @@ typedef enum { GORIO_METHOD_ICP = 4 /* pcl::IterativeClosestPoint, REG:72-79; be
 typedef enum { GORIO_METHOD_NDT_CUDA = 5 } gorio_method_fast_ndt;
 /* fast_gicp::NDTDistanceMode in the order of ndt/ndt_settings.hpp:6 */
 typedef enum { GORIO_NDT_CUDA_P2D = 0, GORIO_NDT_CUDA_D2D = 1 } gorio_ndt_cuda_distance;
+/* a fourth enumeration feeding the same `method` argument: the other class of that back end (fast_gicp::FastVGICPCuda; below) */
+typedef enum { GORIO_METHOD_VGICP_CUDA = 6 } gorio_method_fast_vgicp_cuda;
+/* fast_gicp::NearestNeighborMethod in the order of gicp/fast_vgicp_cuda.hpp:21 */
+typedef enum { GORIO_VGICP_CUDA_NN_CPU_PARALLEL_KDTREE = 0, GORIO_VGICP_CUDA_NN_GPU_BRUTEFORCE = 1, GORIO_VGICP_CUDA_NN_GPU_RBF_KERNEL = 2 } gorio_vgicp_cuda_nn;
 /* fast_gicp::NeighborSearchMethod, gicp_settings.hpp:8 (same order) */
 typedef enum { GORIO_VOXEL_DIRECT27 = 0, GORIO_VOXEL_DIRECT7 = 1, GORIO_VOXEL_DIRECT1 = 2, GORIO_VOXEL_DIRECT_RADIUS = 3 } gorio_voxel_search;
 /* fast_gicp::VoxelAccumulationMode, gicp_settings.hpp:10 (same order) */
@@ -304,6 +308,75 @@ int gorio_apd_set_ndt_cuda_params(gorio_apd_t* h, int distance_mode, double radi
 int gorio_apd_get_ndt_cuda_params(const gorio_apd_t* h, int* distance_mode, double* radius);
 int gorio_apd_ndt_cuda_get_voxels(gorio_apd_t* h, int which, int capacity, int* n_voxels, int* coords, int* num_points, float* mean, float* cov_raw, float* cov);
 int gorio_apd_ndt_cuda_get_pairs(gorio_apd_t* h, int capacity, int* n_pairs, int* item, int* voxel);
+
+/*
+ * GORIO_METHOD_VGICP_CUDA: fast_gicp::FastVGICPCuda, the voxelised GICP of the reference's CUDA back end (FAST_VGICP_CUDA of
+ * select_registration_method, REG:52-61) under the LsqRegistration shell.  Reference lines (paths relative to the reference's
+ * fast_apdgicp/): VH / VI = include/fast_gicp/gicp/fast_vgicp_cuda.hpp and impl/fast_vgicp_cuda_impl.hpp, VC = src/fast_gicp/cuda/
+ * fast_vgicp_cuda.cu, CE = covariance_estimation.cu, RB = covariance_estimation_rbf.cu, CR = covariance_regularization.cu, GV =
+ * gaussian_voxelmap.cu, FV = find_voxel_correspondences.cu, CD = compute_derivatives.cu (all in src/fast_gicp/cuda/).  As with NDTCuda the
+ * reference is not reproducible (float atomics in the voxel sums, a thrust tree over the derivatives, an insertion race for the voxel
+ * numbering, an unspecified heap order in the brute-force k-NN); THIS TEXT is the definition, tests/vgicp_cuda_restatement.py restates it.
+ * Every float expression is un-fused and evaluated in the one order written here.
+ *   neighbours  (VH:21; default CPU_PARALLEL_KDTREE, VI:27)  CPU_PARALLEL_KDTREE (0) and GPU_BRUTEFORCE (1) are ONE path: the exact k-NN list of
+ *            every point in its own cloud, k = params.k_correspondences, in ascending (float squared distance ((dx dx + dy dy) + dz dz),
+ *            index) order, the point itself included.  GPU_RBF_KERNEL (2) uses no list and builds no search index.
+ *   k-NN covariance  (CE:26-34) in float, in list order: mean += p, S_ab += p_a p_b for a <= b; then mean /= (float)k and cov_ab = S_ab /
+ *            (float)k - mean_a mean_b.  Six floats per point (00 01 02 11 12 22).
+ *   RBF covariance  (RB:67-85, 98-108, 116-151)  g = (float)kernel_width is the exponent factor itself, not its reciprocal (RB:120, 80); m2
+ *            = (float)max_dist squared, max_dist = kernel_max_dist, or 5 kernel_width when that is <= 0 (VI:46-50).  The cloud is extended
+ *            to a multiple of 512 points with points at the origin, which take part like any other (RB:127-129).  Per point x and per
+ *            block of 512 consecutive points, in index order, from zero: d2 = (dx dx + dy dy) + dz dz with d = x - p; skipped when d2 > m2;
+ *            w = expf(-g d2); sw += w; s_a += w p_a; S_ab += (w p_a) p_b for a <= b.  The block partials are added in block order to a
+ *            total that starts at zero.  mean = s / sw; cov_ab = (S_ab - mean_a s_b) / sw.  DEVIATION: the reference keeps nine sums, this
+ *            library the upper triangle.  QUIRK (replicated): a cloud whose size is no multiple of 512 gives every point within max_dist of
+ *            the origin up to 511 phantom neighbours at the origin.
+ *   regularisation  (CR:91-117; params.regularization) on the six floats widened to double, eigenvalues w0 <= w1 <= w2 with vectors v0, v1, v2
+ *            from this library's fp64 cyclic Jacobi; every rebuilt matrix is summed in double and rounded to float once.  PLANE: a point
+ *            is KEPT when w1 > w2 * 0.1 (CR:29) and dropped otherwise, cov = 1e-3 v0 v0^T + v1 v1^T + v2 v2^T.  MIN_EIG: sum_i max(1e-3, w_i)
+ *            v_i v_i^T.  FROBENIUS: C = cov + 1e-3 I, result ||C^-1||_F C.  NONE and NORMALIZED_MIN_EIG leave the raw covariance (the
+ *            reference prints "unimplemented" and does the same, CR:114-116).  Only PLANE drops points.  The kept points keep their input
+ *            order; source and target are both filtered and the dropped points take no further part.
+ *   map      (GV:229-252, VC:257-263) of the kept TARGET points and their regularised covariances: coordinates by the float rule of the
+ *            NDTCuda map, voxels in ascending packed id; per voxel, in the kept points' order, in float: n, s += p, Csum += cov; mean = s /
+ *            (float)n, cov = Csum / (float)n.  No voxel is dropped.  There is no source map.  No kept point: an empty map.
+ *   pairs    (VC:265-274, FV) the NDTCuda rule with items = the kept source points: offset-major, float transform, x remembered as x_lin.
+ *   terms    (CD:50-92, 106-135) per pair, all in float: a' = R a + t at the evaluation pose; e = mean_B - a'; Q = cov_B + (R_lin cov_A)
+ *            R_lin^T; C = adj(Q) / det(Q) as written out for NDTCuda above; w = sqrtf((float)num_points) -- no Cauchy kernel and no
+ *            num_points > 6 gate; J = [skew(a') | -I]; A = w J^T, B = A C, H = B J, b = B e, err = ((w e)^T C) e.
+ *   sums     the float terms are widened and added in fp64: wave, then block, then blocks in block order.  Two runs give the same bits.
+ *   shell    LsqRegistration unchanged; compute_error runs over the STALE slots with R_lin; corr_dist_threshold is not read.
+ *   lifecycle  covariances, kept points and map are made lazily at the first linearise / align and reused while the cloud, k, the neighbour
+ *            method, the kernel parameters, the regularisation and the resolution stay the same; a change rebuilds what depends on it.
+ *            gorio_apd_swap_source_and_target swaps clouds with their covariances and kept points and builds the new target's map
+ *            (VC:97-107).  DEVIATION, as for NDTCuda: a changed resolution rebuilds the map (in the reference setResolution reaches only the
+ *            first map ever built and computeTransformation resets the core to 1.0: VI:41-43, 145; VC:257-263).
+ *            gorio_apd_transform_source and the fitness scores work on the whole uploaded cloud, filter or not, as PCL does with input_.
+ * gorio_apd_set_method(h, GORIO_METHOD_VGICP_CUDA, voxel_resolution, voxel_search, voxel_mode): as for GORIO_METHOD_NDT_CUDA -- DIRECT_RADIUS is
+ * accepted with the radius of gorio_apd_set_ndt_cuda_params and its checks, voxel_mode is ignored, voxel_resolution <= 0:
+ * GORIO_ERR_UNSUPPORTED.  In this mode
+ *   - gorio_apd_linearize, gorio_apd_compute_error, gorio_apd_align, gorio_apd_align_batch (all handles must agree in method, resolution,
+ *     offsets, neighbour method, kernel parameters and regularisation: GORIO_ERR_INVALID otherwise; results bit for bit the single aligns'),
+ *     the fitness scores, gorio_apd_transform_source, shared targets (the sharers share covariances, kept points and map; a sharer that
+ *     disagrees in a setting that shapes a stage held gets GORIO_ERR_INVALID) and the scan / keyframe / submap hand-offs work (they deliver
+ *     points: covariances stored with a keyframe are not used);
+ *   - gorio_apd_get_correspondences, gorio_apd_get_mahalanobis, the double covariance getters and setters,
+ *     gorio_apd_calculate_covariances and the sharded-source calls return GORIO_ERR_STATE;
+ *   - in the k-NN modes a cloud with fewer than k points is refused with GORIO_ERR_INVALID, as the handle's covariance estimate refuses it;
+ *   - when the filter keeps no source point linearize returns zero sums and an align behaves as the shell does on an empty pair list.
+ * gorio_apd_set_vgicp_cuda_params: nn_method = setNearestNeighborSearchMethod, kernel_width / kernel_max_dist = setKernelWidth (defaults 0, 0.5,
+ * 3.0: VI:27, 31).  Stored in every method; another nn_method, a non-finite value or kernel_width <= 0: GORIO_ERR_INVALID.
+ * Parity hooks (this method only; they build what is stale; a count always arrives, the arrays -- any may be NULL -- are filled when
+ * capacity >= the count): gorio_apd_vgicp_cuda_get_points gives for the source (which = 0) or target (1) n, cov_raw [n][6], n_kept,
+ * kept_index [n_kept] and the regularised cov [n_kept][6] (capacity counts points: >= n fills all three); gorio_apd_vgicp_cuda_get_voxels
+ * gives the target map: coords 3 ints, num_points, mean 3 floats, cov 6 floats per voxel; gorio_apd_vgicp_cuda_get_pairs gives the pair
+ * list of the last linearise (kept-item index, voxel index), GORIO_ERR_STATE when none is held.
+ */
+int gorio_apd_set_vgicp_cuda_params(gorio_apd_t* h, int nn_method, double kernel_width, double kernel_max_dist);
+int gorio_apd_get_vgicp_cuda_params(const gorio_apd_t* h, int* nn_method, double* kernel_width, double* kernel_max_dist);
+int gorio_apd_vgicp_cuda_get_points(gorio_apd_t* h, int which, int capacity, int* n, float* cov_raw, int* n_kept, int* kept_index, float* cov);
+int gorio_apd_vgicp_cuda_get_voxels(gorio_apd_t* h, int capacity, int* n_voxels, int* coords, int* num_points, float* mean, float* cov);
+int gorio_apd_vgicp_cuda_get_pairs(gorio_apd_t* h, int capacity, int* n_pairs, int* item, int* voxel);
 
 /* parity hooks (VGICP mode; they build the map when it is stale): voxelmap_ (VGH:85) as arrays over the occupied voxels in ascending
  * lexicographic (x, y, z) coordinate order -- coord3: 3 ints, num_points, mean4: GaussianVoxel::mean, cov16: GaussianVoxel::cov row-major
