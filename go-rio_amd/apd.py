@@ -58,6 +58,8 @@ APD_SYMBOLS = [
     "gorio_apd_set_icp_params", "gorio_apd_get_icp_params", "gorio_apd_icp_diag", "gorio_apd_icp_step", "gorio_apd_icp_align_batch", "gorio_apd_icp_batch_diag",
     "gorio_apd_set_ndt_cuda_params", "gorio_apd_get_ndt_cuda_params", "gorio_apd_ndt_cuda_get_voxels", "gorio_apd_ndt_cuda_get_pairs",
     "gorio_apd_set_vgicp_cuda_params", "gorio_apd_get_vgicp_cuda_params", "gorio_apd_vgicp_cuda_get_points", "gorio_apd_vgicp_cuda_get_voxels", "gorio_apd_vgicp_cuda_get_pairs",
+    "gorio_apd_set_gicp_mp_params", "gorio_apd_get_gicp_mp_params", "gorio_apd_gicp_mp_get_covariances", "gorio_apd_gicp_mp_pass", "gorio_apd_gicp_mp_get_neighbors", "gorio_apd_gicp_mp_get_merged",
+    "gorio_apd_gicp_mp_diag",
 ]
 
 # gorio_method / gorio_voxel_search / gorio_voxel_mode of gorio_apd.h (the latter two in the order of gicp_settings.hpp)
@@ -66,6 +68,7 @@ METHOD_NDT_CUDA = 5  # gorio_method_fast_ndt: fast_gicp::NDTCuda
 NDT_CUDA_P2D, NDT_CUDA_D2D = 0, 1  # gorio_ndt_cuda_distance (ndt_settings.hpp:6)
 METHOD_VGICP_CUDA = 6  # gorio_method_fast_vgicp_cuda: fast_gicp::FastVGICPCuda
 NN_CPU_PARALLEL_KDTREE, NN_GPU_BRUTEFORCE, NN_GPU_RBF_KERNEL = 0, 1, 2  # gorio_vgicp_cuda_nn (fast_vgicp_cuda.hpp:21)
+METHOD_GICP_MP = 8  # gorio_method_fast_gicp_mp: fast_gicp::FastGICPMultiPoints (7 stays unused and refused)
 GICP_OMP_F, GICP_OMP_DF, GICP_OMP_FDF = 0, 1, 2  # modes of gorio_apd_gicp_omp_evaluate
 VOXEL_DIRECT27, VOXEL_DIRECT7, VOXEL_DIRECT1, VOXEL_DIRECT_RADIUS = 0, 1, 2, 3
 VOXEL_ADDITIVE, VOXEL_ADDITIVE_WEIGHTED, VOXEL_MULTIPLICATIVE = 0, 1, 2
@@ -257,6 +260,55 @@ class ApdGicp:
         if m.value:
             _check(self._h, self._lib.gorio_apd_vgicp_cuda_get_pairs(self._h, m.value, C.byref(m), _p(item, C.c_int), _p(vox, C.c_int)))
         return np.stack([item, vox], axis=1)
+
+    # ---- FastGICPMultiPoints (METHOD_GICP_MP): neighbor_search_radius_ (fast_gicp_mp_impl.hpp:35; the reference has no setter) and the parity hooks
+    def set_gicp_mp_params(self, neighbor_search_radius=0.5):
+        _check(self._h, self._lib.gorio_apd_set_gicp_mp_params(self._h, C.c_double(neighbor_search_radius)))
+
+    def get_gicp_mp_params(self):
+        r = C.c_double(0.0)
+        _check(self._h, self._lib.gorio_apd_get_gicp_mp_params(self._h, C.byref(r)))
+        return dict(neighbor_search_radius=r.value)
+
+    def gicp_mp_covariances(self, which):
+        """gorio_apd_gicp_mp_get_covariances: the float covariances of the source (0) / target (1), six floats per point (00 01 02 11 12 22)."""
+        n = C.c_int(0)
+        _check(self._h, self._lib.gorio_apd_gicp_mp_get_covariances(self._h, int(which), 0, C.byref(n), None))
+        cov = np.empty((n.value, 6), np.float32)
+        if n.value:
+            _check(self._h, self._lib.gorio_apd_gicp_mp_get_covariances(self._h, int(which), n.value, C.byref(n), _p(cov, C.c_float)))
+        return cov
+
+    def gicp_mp_pass(self, T=None):
+        """gorio_apd_gicp_mp_pass: one pass (neighbourhoods, merge, linearisation) at the float pose T -> dict(used, total, H [6, 6], g [6])."""
+        T = np.ascontiguousarray(np.eye(4) if T is None else T, np.float32)
+        used, total = C.c_int(0), C.c_longlong(0)
+        H, g = np.zeros((6, 6), np.float64), np.zeros(6, np.float64)
+        _check(self._h, self._lib.gorio_apd_gicp_mp_pass(self._h, _p(T, C.c_float), C.byref(used), C.byref(total), _p(H, C.c_double), _p(g, C.c_double)))
+        return dict(used=used.value, total=total.value, H=H, g=g)
+
+    def gicp_mp_neighbors(self):
+        """gorio_apd_gicp_mp_get_neighbors: the CSR of the last pass -> (offsets [n + 1] int64, idx [total] int32, sqd [total] float32)."""
+        nq, total = C.c_int(0), C.c_longlong(0)
+        _check(self._h, self._lib.gorio_apd_gicp_mp_get_neighbors(self._h, C.c_longlong(-1), C.byref(nq), C.byref(total), None, None, None))
+        offs, idx, sqd = np.zeros(nq.value + 1, np.int64), np.empty(total.value, np.int32), np.empty(total.value, np.float32)
+        _check(self._h, self._lib.gorio_apd_gicp_mp_get_neighbors(self._h, C.c_longlong(total.value), C.byref(nq), C.byref(total), _p(offs, C.c_longlong), _p(idx, C.c_int), _p(sqd, C.c_float)))
+        return offs, idx, sqd
+
+    def gicp_mp_merged(self):
+        """gorio_apd_gicp_mp_get_merged: of the last gicp_mp_pass per source point mean_B [n, 3], cov_B [n, 6] and the used flag [n]."""
+        n = C.c_int(0)
+        _check(self._h, self._lib.gorio_apd_gicp_mp_get_merged(self._h, 0, C.byref(n), None, None, None))
+        mean, cov, used = np.empty((n.value, 3), np.float32), np.empty((n.value, 6), np.float32), np.empty(n.value, np.int32)
+        if n.value:
+            _check(self._h, self._lib.gorio_apd_gicp_mp_get_merged(self._h, n.value, C.byref(n), _p(mean, C.c_float), _p(cov, C.c_float), _p(used, C.c_int)))
+        return dict(mean_B=mean, cov_B=cov, used=used.astype(bool))
+
+    def gicp_mp_diag(self):
+        p, u, t = C.c_int(0), C.c_int(0), C.c_longlong(0)
+        s = (C.c_double * 4)()
+        _check(self._h, self._lib.gorio_apd_gicp_mp_diag(self._h, C.byref(p), C.byref(u), C.byref(t), s))
+        return dict(passes=p.value, used=u.value, total=t.value, stage_seconds=dict(zip(("query", "search", "linearize", "shell"), list(s))))
 
     def getVoxelMap(self):  # noqa: N802 -- parity hook: voxelmap_ (fast_vgicp.hpp:85), voxels in ascending (x, y, z) coordinate order
         nv = C.c_int(0)

@@ -128,12 +128,22 @@ struct DevCloud {
   int vc_min[3] = {0, 0, 0}, vc_dim[3] = {0, 0, 0};
   float vc_res = 0.0f;
   NdtcMapView vgc_view() const { return NdtcMapView{vc_vkey, vc_mean, vc_mcov6, vc_num, vc_nv, {vc_min[0], vc_min[1], vc_min[2]}, {vc_dim[0], vc_dim[1], vc_dim[2]}, vc_res}; }
+  // fast_gicp::FastGICPMultiPoints (apd_gicp_mp.hip): every point with its float covariance as a record of three float4, made from the k-NN
+  // lists mp_knn (mp_scratch: what the k-NN kernels write on their way to the lists).  Valid for (mp_k, mp_reg) until the points change;
+  // lives with the cloud, so a swap moves it and the sharers of a cloud share it.
+  DevBuf<float4> mp_rec;               // [n][3]
+  DevBuf<int> mp_knn;                  // [n][k]
+  DevBuf<double> mp_scratch;           // [n][7]
+  bool mp_valid = false;
+  int mp_k = 0, mp_reg = -1;
   // What is derived from what: covariances, search index, voxel map and k-NN lists from the points; the voxel map and the k-NN lists from
   // the covariances too.  New points leave all four stale, new covariances the last two.  These members are the ONLY code that writes
-  // present, cov_count, cov_k, cov_reg, idx_valid, idx_chunk, vm_valid, nc_valid, knn_valid and the three vc_*_valid; everybody else reads them.
+  // present, cov_count, cov_k, cov_reg, idx_valid, idx_chunk, vm_valid, nc_valid, knn_valid, the three vc_*_valid and mp_valid; everybody else reads them.
   void covs_dropped() { cov_count = 0; vm_valid = false; knn_valid = false; }
-  void points_replaced() { present = true; idx_valid = false; nc_valid = false; vgc_raw_dropped(); covs_dropped(); }
-  void cleared() { present = false; n = 0; idx_valid = false; nc_valid = false; vgc_raw_dropped(); covs_dropped(); }
+  void points_replaced() { present = true; idx_valid = false; nc_valid = false; vgc_raw_dropped(); mp_dropped(); covs_dropped(); }
+  void cleared() { present = false; n = 0; idx_valid = false; nc_valid = false; vgc_raw_dropped(); mp_dropped(); covs_dropped(); }
+  void mp_dropped() { mp_valid = false; }
+  void mp_built(int k, int reg) { mp_valid = true; mp_k = k; mp_reg = reg; }
   void vgc_raw_dropped() { vc_raw_valid = false; vgc_kept_dropped(); }
   void vgc_kept_dropped() { vc_kept_valid = false; vc_map_valid = false; }
   void vgc_map_dropped() { vc_map_valid = false; }
@@ -160,6 +170,8 @@ struct DevCloud {
 };
 
 }  // namespace
+
+struct GicpMpState;  // apd_gicp_mp.hip
 
 struct gorio_apd {
   int device = 0;
@@ -244,6 +256,11 @@ struct gorio_apd {
   // offset table, slot table, linearized_x and partials are the NDTCuda members above (ndtc_slot_d2d == 2).
   int vgc_nn = GORIO_VGICP_CUDA_NN_CPU_PARALLEL_KDTREE;
   double vgc_width = 0.5, vgc_maxd = 3.0;
+  // fast_gicp::FastGICPMultiPoints (GORIO_METHOD_GICP_MP, apd_gicp_mp.hip): neighbor_search_radius_ (MPI:35), the per-pass state (the radius
+  // search's buffers and CSR, the transformed source, the merged distributions, the partials) and whether it holds a pass
+  double mp_radius = 0.5;
+  std::shared_ptr<GicpMpState> mp;
+  bool mp_pass_valid = false;
   DevBuf<PairState> d_state;
   DevBuf<PairDesc> d_desc;   // batch descriptor array and states (owned by the handle that leads a batch): one group of capacity desc_cap
   DevBuf<PairState> d_states_batch;
@@ -324,10 +341,14 @@ int roundup(int v, int m) { return (v + m - 1) / m * m; }
 
 // GICP_OMP (apd_gicp_omp.hip, included at the end of this file)
 constexpr int kRegGicpOmp = 100;  // DevCloud::cov_reg of covariances estimated by the rule of GO:50-122: one more "regularization" for sharing
+constexpr int kRegMpBase = 200;   // DevCloud::mp_reg = kRegMpBase + regularization: the covariance rule of FastGICPMultiPoints is one more "regularization" for sharing
 int gomp_align(gorio_apd* h, const float* guess, float* T_out, double* H_out, int* converged, int* nr_iterations, int* n_linearize);
 int gomp_covariances(gorio_apd* lead, std::vector<std::pair<gorio_apd*, DevCloud*>>& todo);
 // ICP (apd_icp.hip, included at the end of this file)
 int icp_align(gorio_apd* h, const float* guess, float* T_out, double* H_out, int* converged, int* nr_iterations, int* n_linearize);
+// FastGICPMultiPoints (apd_gicp_mp.hip, included at the end of this file)
+int mp_align(gorio_apd* h, const float* guess, float* T_out, double* H_out, int* converged, int* nr_iterations, int* n_linearize);
+bool is_mp(const gorio_apd* h) { return h->method == GORIO_METHOD_GICP_MP; }
 // the rule a handle estimates covariances by, and whether covariances estimated with (k, reg, eps) are the ones it would estimate
 int cov_rule(const gorio_apd* h) { return h->method == GORIO_METHOD_GICP_OMP ? kRegGicpOmp : h->params.regularization; }
 bool cov_rule_differs(const gorio_apd* h, const DevCloud& c) {
@@ -1404,6 +1425,8 @@ int align_impl(gorio_apd** hs, int count, const float* guesses, float* T_out, do
     if (hs[q] && hs[q]->method == GORIO_METHOD_GICP_OMP) return fail(lead, GORIO_ERR_UNSUPPORTED, "align_batch: GICP_OMP handles batch through gorio_apd_gicp_omp_align_batch (the BFGS shell is not the Gauss-Newton / LM one)");
   for (int q = 0; q < count; ++q)
     if (hs[q] && hs[q]->method == GORIO_METHOD_ICP) return fail(lead, GORIO_ERR_UNSUPPORTED, "align_batch: ICP handles batch through gorio_apd_icp_align_batch");
+  for (int q = 0; q < count; ++q)
+    if (hs[q] && is_mp(hs[q])) return fail(lead, GORIO_ERR_UNSUPPORTED, "align_batch: FastGICPMultiPoints has no batched form (its radius search serves one cloud per call)");
   std::unordered_set<gorio_apd*> distinct;
   for (int q = 0; q < count; ++q) {
     gorio_apd* h = hs[q];
@@ -1772,7 +1795,7 @@ int gorio_apd_get_params(const gorio_apd_t* h, gorio_apd_params* p) {
 
 int gorio_apd_set_method(gorio_apd_t* h, int method, double voxel_resolution, int voxel_search, int voxel_mode) {
   if (!h) return GORIO_ERR_INVALID;
-  if (method != GORIO_METHOD_APDGICP && method != GORIO_METHOD_GICP && method != GORIO_METHOD_VGICP && method != GORIO_METHOD_GICP_OMP && method != GORIO_METHOD_ICP && method != GORIO_METHOD_NDT_CUDA && method != GORIO_METHOD_VGICP_CUDA) return fail(h, GORIO_ERR_UNSUPPORTED, "set_method: unknown registration method");
+  if (method != GORIO_METHOD_APDGICP && method != GORIO_METHOD_GICP && method != GORIO_METHOD_VGICP && method != GORIO_METHOD_GICP_OMP && method != GORIO_METHOD_ICP && method != GORIO_METHOD_NDT_CUDA && method != GORIO_METHOD_VGICP_CUDA && method != GORIO_METHOD_GICP_MP) return fail(h, GORIO_ERR_UNSUPPORTED, "set_method: unknown registration method");
   if (method == GORIO_METHOD_NDT_CUDA || method == GORIO_METHOD_VGICP_CUDA) {  // voxel_resolution = setResolution, voxel_search = setNeighborSearchMethod (DIRECT_RADIUS with the radius of gorio_apd_set_ndt_cuda_params); voxel_mode is ignored
     if (voxel_search != GORIO_VOXEL_DIRECT27 && voxel_search != GORIO_VOXEL_DIRECT7 && voxel_search != GORIO_VOXEL_DIRECT1 && voxel_search != GORIO_VOXEL_DIRECT_RADIUS) return fail(h, GORIO_ERR_UNSUPPORTED, "set_method: unknown neighbour search method");
     if (!(voxel_resolution > 0.0) || !std::isfinite(voxel_resolution)) return fail(h, GORIO_ERR_UNSUPPORTED, "set_method: voxel_resolution must be positive");
@@ -1782,17 +1805,19 @@ int gorio_apd_set_method(gorio_apd_t* h, int method, double voxel_resolution, in
     h->gomp_pairs = -1;
     h->icp_pairs = -1;
     h->method = method;
+    h->mp_pass_valid = false;  // the pass FastGICPMultiPoints held means nothing after a switch
     h->voxel_resolution = voxel_resolution;
     h->voxel_search = voxel_search;
     h->corr_valid = false;
     h->omega_valid = false;
     return GORIO_OK;
   }
-  if (method == GORIO_METHOD_GICP_OMP || method == GORIO_METHOD_ICP) {  // the voxel arguments are ignored in these modes: the handle keeps the ones it has
-    if (h->comm) return fail(h, GORIO_ERR_STATE, "set_method: GICP_OMP and ICP have no sharded-source mode (the handle has a communicator)");
-    if (method == GORIO_METHOD_ICP && h->shard_only && h->comm_world > 1) return fail(h, GORIO_ERR_STATE, "set_method: ICP has no sharded-source mode (gorio_apd_debug_set_shard is on)");
+  if (method == GORIO_METHOD_GICP_OMP || method == GORIO_METHOD_ICP || method == GORIO_METHOD_GICP_MP) {  // the voxel arguments are ignored in these modes: the handle keeps the ones it has
+    if (h->comm) return fail(h, GORIO_ERR_STATE, "set_method: GICP_OMP, ICP and FastGICPMultiPoints have no sharded-source mode (the handle has a communicator)");
+    if (method != GORIO_METHOD_GICP_OMP && h->shard_only && h->comm_world > 1) return fail(h, GORIO_ERR_STATE, "set_method: ICP and FastGICPMultiPoints have no sharded-source mode (gorio_apd_debug_set_shard is on)");
     h->icp_pairs = -1;
     h->method = method;
+    h->mp_pass_valid = false;  // the pass FastGICPMultiPoints held means nothing after a switch
     h->corr_valid = false;
     h->omega_valid = false;
     h->gomp_pairs = -1;
@@ -1806,6 +1831,7 @@ int gorio_apd_set_method(gorio_apd_t* h, int method, double voxel_resolution, in
   h->gomp_pairs = -1;
   h->icp_pairs = -1;
   h->method = method;
+  h->mp_pass_valid = false;
   h->voxel_resolution = voxel_resolution;
   h->voxel_search = voxel_search;
   h->voxel_mode = voxel_mode;
@@ -2159,6 +2185,8 @@ int gorio_apd_set_target_shared(gorio_apd_t* h, gorio_apd_t* owner) {
     if ((t.vc_raw_valid && !vgc_raw_matches(h, t)) || (t.vc_kept_valid && t.vc_reg != h->params.regularization) || (t.vc_map_valid && t.vc_res != (float)h->voxel_resolution))
       return fail(h, GORIO_ERR_INVALID, "set_target_shared: the owner's FastVGICPCuda covariances / kept points / voxel map were made with other settings than this handle's");
   }
+  if (is_mp(h) && owner->tgt->mp_valid && (owner->tgt->mp_k != h->params.k_correspondences || owner->tgt->mp_reg != kRegMpBase + h->params.regularization))
+    return fail(h, GORIO_ERR_INVALID, "set_target_shared: the owner's FastGICPMultiPoints covariances were made with another k_correspondences or regularization than this handle's");
   h->tgt = owner->tgt;  // points, covariances, search index, voxel map: one copy on the device, alive until the last handle lets go of it
   h->corr_valid = false;
   return GORIO_OK;
@@ -2295,6 +2323,7 @@ int gorio_apd_swap_source_and_target(gorio_apd_t* h) {
 
 static int set_covs(gorio_apd* h, DevCloud& c, const double* cov, int n) {
   if (is_voxf(h)) return fail(h, GORIO_ERR_STATE, "set_covariances: " + voxf_name(h) + " takes no per-point double covariances");
+  if (is_mp(h)) return fail(h, GORIO_ERR_STATE, "set_covariances: FastGICPMultiPoints takes no per-point double covariances");
   if (n < 0 || (n > 0 && !cov)) return fail(h, GORIO_ERR_INVALID, "set_covariances: bad arguments");
   if (!c.present || n != c.n) {
     // the reference stores the vector whatever its size (APD:138-145) and recomputes the covariances in computeTransformation when the
@@ -2322,6 +2351,7 @@ int gorio_apd_set_target_covariances(gorio_apd_t* h, const double* cov, int n) {
 
 static int get_covs(gorio_apd* h, DevCloud& c, double* cov, int n) {
   if (is_voxf(h)) return fail(h, GORIO_ERR_STATE, "get_covariances: " + voxf_name(h) + " holds no per-point double covariances");
+  if (is_mp(h)) return fail(h, GORIO_ERR_STATE, "get_covariances: FastGICPMultiPoints holds float covariances (gorio_apd_gicp_mp_get_covariances)");
   const int cnt = c.present ? c.cov_count : 0;
   if (!cov || cnt == 0) return cnt;
   const int m = n < cnt ? n : cnt;
@@ -2345,6 +2375,7 @@ int gorio_apd_get_target_covariances(gorio_apd_t* h, double* cov, int n) { retur
 int gorio_apd_calculate_covariances(gorio_apd_t* h) {
   if (!h) return GORIO_ERR_INVALID;
   if (is_voxf(h)) return fail(h, GORIO_ERR_STATE, "calculate_covariances: " + voxf_name(h) + " has no per-point double covariances");
+  if (is_mp(h)) return fail(h, GORIO_ERR_STATE, "calculate_covariances: FastGICPMultiPoints has no per-point double covariances (gorio_apd_gicp_mp_get_covariances makes its float ones)");
   HIP_TRY(h, hipSetDevice(h->device));
   const gorio_apd_params& p = h->params;
   std::vector<std::pair<gorio_apd*, DevCloud*>> todo;
@@ -2384,6 +2415,7 @@ int gorio_apd_align(gorio_apd_t* h, const float guess[16], float T_out[16], doub
   if (!h) return GORIO_ERR_INVALID;
   if (h->method == GORIO_METHOD_GICP_OMP) return gomp_align(h, guess, T_out, H_out, converged, nr_iterations, n_linearize);
   if (h->method == GORIO_METHOD_ICP) return icp_align(h, guess, T_out, H_out, converged, nr_iterations, n_linearize);
+  if (is_mp(h)) return mp_align(h, guess, T_out, H_out, converged, nr_iterations, n_linearize);
   gorio_apd* hs[1] = {h};
   return align_impl(hs, 1, guess, T_out, H_out, converged, nr_iterations, n_linearize);
 }
@@ -2396,6 +2428,7 @@ int gorio_apd_linearize(gorio_apd_t* h, const double T[16], double* H, double* b
   if (!h || !T) return GORIO_ERR_INVALID;
   if (h->method == GORIO_METHOD_GICP_OMP) return fail(h, GORIO_ERR_UNSUPPORTED, "linearize: GICP_OMP has no Gauss-Newton linearisation (gorio_apd_gicp_omp_update / _evaluate)");
   if (h->method == GORIO_METHOD_ICP) return fail(h, GORIO_ERR_UNSUPPORTED, "linearize: ICP has no Gauss-Newton linearisation (gorio_apd_icp_step)");
+  if (is_mp(h)) return fail(h, GORIO_ERR_UNSUPPORTED, "linearize: FastGICPMultiPoints linearises at a float pose through gorio_apd_gicp_mp_pass");
   HIP_TRY(h, hipSetDevice(h->device));
   if (is_voxf(h)) {  // NI:82-85, VI:170-173: update_correspondences(trans), then compute_error(trans, H, b) over the fresh pairs
     int rc = voxf_ready(h);
@@ -2479,6 +2512,7 @@ int gorio_apd_compute_error(gorio_apd_t* h, const double T[16], double* error) {
   if (!h || !T || !error) return GORIO_ERR_INVALID;
   if (h->method == GORIO_METHOD_GICP_OMP) return fail(h, GORIO_ERR_UNSUPPORTED, "compute_error: GICP_OMP evaluates its functor through gorio_apd_gicp_omp_evaluate");
   if (h->method == GORIO_METHOD_ICP) return fail(h, GORIO_ERR_UNSUPPORTED, "compute_error: ICP has no weighted error (gorio_apd_icp_diag gives the mean squared distance)");
+  if (is_mp(h)) return fail(h, GORIO_ERR_UNSUPPORTED, "compute_error: FastGICPMultiPoints has no error function (its solver takes full Gauss-Newton steps)");
   HIP_TRY(h, hipSetDevice(h->device));
   if (is_voxf(h) ? !h->corr_valid : (!h->corr_valid || !h->omega_valid)) return fail(h, GORIO_ERR_STATE, "compute_error needs the correspondences and Mahalanobis matrices of a previous linearize (or LM align)");
   int rc = single_desc(h, true);
@@ -2516,6 +2550,7 @@ int gorio_apd_get_correspondences(gorio_apd_t* h, int* corr, float* sq_dist, int
   if (!h) return GORIO_ERR_INVALID;
   if (h->method == GORIO_METHOD_VGICP) return fail(h, GORIO_ERR_STATE, "get_correspondences: FastVGICP pairs points with voxels, not with target points (gorio_apd_get_voxel_correspondences)");
   if (is_voxf(h)) return fail(h, GORIO_ERR_STATE, "get_correspondences: " + voxf_name(h) + " pairs items with voxels, not with target points (gorio_apd_ndt_cuda_get_pairs / gorio_apd_vgicp_cuda_get_pairs)");
+  if (is_mp(h)) return fail(h, GORIO_ERR_UNSUPPORTED, "get_correspondences: FastGICPMultiPoints pairs a point with a neighbourhood, not with one target point (gorio_apd_gicp_mp_get_neighbors)");
   if (!h->corr_valid) return fail(h, GORIO_ERR_STATE, "no correspondences held");
   if (n != h->src->n) return fail(h, GORIO_ERR_INVALID, "get_correspondences: size mismatch");
   HIP_TRY(h, hipSetDevice(h->device));
@@ -2529,6 +2564,7 @@ int gorio_apd_get_mahalanobis(gorio_apd_t* h, double* maha, int n) {
   if (!h || !maha) return GORIO_ERR_INVALID;
   if (h->method == GORIO_METHOD_VGICP) return fail(h, GORIO_ERR_STATE, "get_mahalanobis: FastVGICP holds one matrix per (point, voxel) pair, not per point");
   if (h->method == GORIO_METHOD_ICP) return fail(h, GORIO_ERR_STATE, "get_mahalanobis: ICP holds no Mahalanobis matrices");
+  if (is_mp(h)) return fail(h, GORIO_ERR_UNSUPPORTED, "get_mahalanobis: FastGICPMultiPoints holds no Mahalanobis matrices (they are recomputed per point and pass)");
   if (is_voxf(h)) return fail(h, GORIO_ERR_STATE, "get_mahalanobis: " + voxf_name(h) + " holds no Mahalanobis matrices (they are recomputed per pair)");
   if (!h->corr_valid || !h->omega_valid) return fail(h, GORIO_ERR_STATE, "no Mahalanobis matrices held (a Gauss-Newton align does not materialise them: call gorio_apd_linearize)");
   if (n != h->src->n) return fail(h, GORIO_ERR_INVALID, "get_mahalanobis: size mismatch");
@@ -2747,6 +2783,7 @@ int gorio_apd_comm_init(gorio_apd_t* h, int world_size, int rank, const char id[
   if (!h || !id || world_size < 1 || rank < 0 || rank >= world_size) return GORIO_ERR_INVALID;
   if (h->method == GORIO_METHOD_VGICP) return fail(h, GORIO_ERR_STATE, "comm_init: FastVGICP has no sharded-source mode");
   if (h->method == GORIO_METHOD_ICP) return fail(h, GORIO_ERR_STATE, "comm_init: ICP has no sharded-source mode");
+  if (is_mp(h)) return fail(h, GORIO_ERR_STATE, "comm_init: FastGICPMultiPoints has no sharded-source mode");
   if (is_voxf(h)) return fail(h, GORIO_ERR_STATE, "comm_init: " + voxf_name(h) + " has no sharded-source mode");
   Rccl& R = rccl();
   if (!R.ok) return fail(h, GORIO_ERR_NO_DEVICE, "librccl could not be loaded");
@@ -2784,6 +2821,7 @@ int gorio_apd_debug_set_shard(gorio_apd_t* h, int world_size, int rank) {
   if (!h || world_size < 1 || rank < 0 || rank >= world_size) return GORIO_ERR_INVALID;
   if (h->comm) return fail(h, GORIO_ERR_STATE, "debug_set_shard: the handle has a communicator");
   if (h->method == GORIO_METHOD_ICP && world_size > 1) return fail(h, GORIO_ERR_STATE, "debug_set_shard: ICP has no sharded-source mode");
+  if (is_mp(h) && world_size > 1) return fail(h, GORIO_ERR_STATE, "debug_set_shard: FastGICPMultiPoints has no sharded-source mode");
   if (is_voxf(h) && world_size > 1) return fail(h, GORIO_ERR_STATE, "debug_set_shard: " + voxf_name(h) + " has no sharded-source mode");
   h->comm_world = world_size;
   h->comm_rank = rank;
@@ -2883,3 +2921,4 @@ extern "C" int gorio_debug_search_stats(unsigned long long out[24], int reset) {
 #include "apd_icp.hip"
 #include "../../include/gorio_search.h"
 #include "apd_search.hip"
+#include "apd_gicp_mp.hip"

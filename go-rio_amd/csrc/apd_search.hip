@@ -364,6 +364,7 @@ __global__ __launch_bounds__(256) void search_long_emit_kernel(const search_plan
 struct gorio_search_handle {
   int device = 0;
   gorio_apd* up = nullptr;  // a private registration handle: its SOURCE is the cloud held (own or shared), its stream the device's launch stream
+  DevCloud* cloud = nullptr;  // set only by a search state that lives INSIDE a registration handle (apd_gicp_mp.hip): the cloud searched instead of up's source
   long long point_uploads = 0, index_builds = 0, result_downloads = 0;
   DevBuf<int> d_flag;
   // queries and k-NN results of the host forms
@@ -412,8 +413,11 @@ int search_check_radius(const char* who, const gorio_search_handle* s, int nq, i
   return search_check_queries(who, s, nq, stride_bytes);
 }
 
-DevCloud& search_cloud(gorio_search_handle* s) { return *s->up->src; }
-int search_cloud_n(const gorio_search_handle* s) { return s->up->src->present ? s->up->src->n : 0; }
+DevCloud& search_cloud(gorio_search_handle* s) { return s->cloud ? *s->cloud : *s->up->src; }
+int search_cloud_n(const gorio_search_handle* s) {
+  const DevCloud& c = s->cloud ? *s->cloud : *s->up->src;
+  return c.present ? c.n : 0;
+}
 
 // the index of `cloud` through `owner` (the handle whose launches and scratch build it), unless it is built already
 int search_build_index(gorio_apd* owner, DevCloud* cloud, bool* built) {

@@ -57,6 +57,8 @@ typedef enum { GORIO_NDT_CUDA_P2D = 0, GORIO_NDT_CUDA_D2D = 1 } gorio_ndt_cuda_d
 typedef enum { GORIO_METHOD_VGICP_CUDA = 6 } gorio_method_fast_vgicp_cuda;
 /* fast_gicp::NearestNeighborMethod in the order of gicp/fast_vgicp_cuda.hpp:21 */
 typedef enum { GORIO_VGICP_CUDA_NN_CPU_PARALLEL_KDTREE = 0, GORIO_VGICP_CUDA_NN_GPU_BRUTEFORCE = 1, GORIO_VGICP_CUDA_NN_GPU_RBF_KERNEL = 2 } gorio_vgicp_cuda_nn;
+/* a fifth enumeration feeding the same `method` argument: fast_gicp::FastGICPMultiPoints (below).  The value 7 stays unused and refused. */
+typedef enum { GORIO_METHOD_GICP_MP = 8 } gorio_method_fast_gicp_mp;
 /* fast_gicp::NeighborSearchMethod, gicp_settings.hpp:8 (same order) */
 typedef enum { GORIO_VOXEL_DIRECT27 = 0, GORIO_VOXEL_DIRECT7 = 1, GORIO_VOXEL_DIRECT1 = 2, GORIO_VOXEL_DIRECT_RADIUS = 3 } gorio_voxel_search;
 /* fast_gicp::VoxelAccumulationMode, gicp_settings.hpp:10 (same order) */
@@ -377,6 +379,74 @@ int gorio_apd_get_vgicp_cuda_params(const gorio_apd_t* h, int* nn_method, double
 int gorio_apd_vgicp_cuda_get_points(gorio_apd_t* h, int which, int capacity, int* n, float* cov_raw, int* n_kept, int* kept_index, float* cov);
 int gorio_apd_vgicp_cuda_get_voxels(gorio_apd_t* h, int capacity, int* n_voxels, int* coords, int* num_points, float* mean, float* cov);
 int gorio_apd_vgicp_cuda_get_pairs(gorio_apd_t* h, int capacity, int* n_pairs, int* item, int* voxel);
+
+/*
+ * GORIO_METHOD_GICP_MP: fast_gicp::FastGICPMultiPoints, the multi-point GICP of the reference's experimental directory.  Reference lines (paths
+ * relative to the reference's fast_apdgicp/): MPH / MPI = include/fast_gicp/gicp/experimental/fast_gicp_mp.hpp and fast_gicp_mp_impl.hpp
+ * (instantiated in src/fast_gicp/gicp/experimental/fast_gicp_mp.cpp).  Every source point is matched against a distribution MERGED from all target
+ * points within neighbor_search_radius of its transformed position, distance-weighted and redone at every Gauss-Newton pass.  What MPI leaves
+ * open -- fast_gicp/opt/gauss_newton.hpp and Sophus are not in the reference tree, FLANN's result order is not specified -- is fixed HERE: this text
+ * is the definition, tests/gicp_mp_restatement.py restates it.  Every float expression is un-fused and evaluated in the one order written.
+ *   covariances  (MPI:225-276; made lazily, reused while the cloud, k and the regularisation stay) per point of either cloud from its exact k-NN
+ *            list in its own cloud, k = params.k_correspondences, in ascending (float squared distance, index) order, the point itself
+ *            included.  In float, in list order: s += p; mean = s / (float)k; then with d = p - mean, cov_ab += d_a d_b for a <= b -- NOT divided
+ *            by k (MPI:242).  FROBENIUS, in double: C = cov + 1e-3 I; X = C^-1 (cofactors times 1 / det, det expanded along the first row); f =
+ *            sqrt of the sum of the nine squared entries of X, row by row; result = (X / f)^-1, rounded to float.  PLANE / MIN_EIG /
+ *            NORMALIZED_MIN_EIG: the reference takes JacobiSVD<Matrix3f>; the matrix is symmetric positive semi-definite, so this library's
+ *            fp64 symmetric 3 x 3 eigen-solver STANDS IN for it: eigenvalues w0 >= w1 >= w2 with vectors v0, v1, v2 of the six floats widened
+ *            to double, s_i = |(float)w_i|, values (1, 1, 1e-3f) / max(s_i, 1e-3f) / max(s_i / max(s), 1e-3f), result = sum_i value_i v_i v_i^T
+ *            summed in double in that order and rounded to float once.  NONE: GORIO_ERR_UNSUPPORTED (the reference aborts, MPI:255-257).  A
+ *            cloud with fewer than k points: GORIO_ERR_INVALID (the reference reads uninitialised columns there).
+ *   exp / log  Rodrigues and its inverse in double from float inputs, rounded to float wherever the reference holds a float (x0, delta,
+ *            trans).  exp(w) = I + A K + B K^2, K = skew(w), K^2 = w w^T - t2 I, t2 = (w0 w0 + w1 w1) + w2 w2; t2 < 1e-12: A = 1 - t2 / 6, B = 1 / 2
+ *            - t2 / 24; otherwise A = sin(t) / t, B = 2 sin^2(t / 2) / t2.  log(R): v = (R21 - R12, R02 - R20, R10 - R01) / 2, c = ((R00 + R11) + R22 -
+ *            1) / 2, s = |v|, t = atan2(s, c), w = (t / s) v, or (1 + t^2 / 6) v when s < 1e-6.  Rotations near pi are outside its domain.
+ *   loop     (MPI:80-115) x0 = [float(log(R_guess)), t_guess].  Pass i = 0 .. max_iterations - 1 sets iterations = i: trans = [float(exp(
+ *            x0.head)) | x0.tail]; queries q = trans p by the float transform of the GICP family (((m0 x + m1 y) + m2 z) + m3); neighbours of
+ *            q in the target by the rule and order of include/gorio_search.h: d < (float)(r r) strictly, ascending (d, original index); an
+ *            empty neighbourhood stays empty.  Then the terms, H = sum J^T J, g = sum J^T r, delta = float(LDLT6(H) \ g) with this library's
+ *            pivoted 6 x 6 LDLT in double, x0.head = float(log(exp(-delta.head) exp(x0.head))) (the product in double), x0.tail -= delta.tail
+ *            (float), and the float test max(|float(exp(delta.head)) - I| (float)(1 / rotation_epsilon), |delta.tail| (float)(1 /
+ *            transformation_epsilon)) < 1 ends the align converged.  The final transformation is trans of the last x0.
+ *   term     (MPI:170-213) of source point i with neighbours j (skipped without one): w_j = max(1e-3, min(1, 1 - (double)sqrtf(d_j) / r)) in
+ *            double (the square root is the float one of MPI:184); sw += w_j, sm += w_j b_j, sC += w_j C_j (six entries) in double in the
+ *            neighbours' order; mean_B = float(sm / sw), cov_B = float(sC / sw).  In float: a' = q_i; d = mean_B - a'; M = R C_a (each entry (R_r0
+ *            A_0c + R_r1 A_1c) + R_r2 A_2c); Q = cov_B + M R^T (likewise); C = adj(Q) / det(Q), the cofactor form of FastVGICPCuda above (RCR(3,
+ *            3) = 1 decouples the fourth row); residual r = C d and Jacobian J = C [skew(a') | -I], each entry of C skew(a') the three-term sum
+ *            left to right with its zeros, the last three columns -C.
+ *   sums     per point the 21 + 6 entries (J_0a J_0b + J_1a J_1b) + J_2a J_2b and (J_0a r_0 + J_1a r_1) + J_2a r_2 in double from the widened
+ *            floats; per block of 256 consecutive source points the halving tree of a wave (lanes l and l + 32, 16, 8, 4, 2, 1) and (w0 + w1) +
+ *            (w2 + w3) over its four waves; the blocks added in block order.  No atomics: two runs give the same bits.
+ *   DEVIATIONS  the reference's solver is not in its tree; as recalled it factors with LLT and substitutes a random step for a non-finite one.
+ *            Here a non-finite delta, or a pass in which no source point has a neighbour, ENDS the align unconverged with the current x0.
+ * gorio_apd_set_method(h, GORIO_METHOD_GICP_MP, ...): the voxel arguments are ignored, as for ICP.  Read from gorio_apd_params:
+ * k_correspondences, regularization, max_iterations, rotation_epsilon, transformation_epsilon, search (of the k-NN lists); nothing else.  The
+ * class's own defaults (MPI:20-36: k 20, 64 iterations, both epsilons 1e-5, PLANE) are the caller's to set.  In this mode
+ *   - gorio_apd_align runs the loop: nr_iterations = the index of the last pass, n_linearize = the passes run, H_out = the last H;
+ *   - gorio_apd_linearize, gorio_apd_compute_error, gorio_apd_get_correspondences, gorio_apd_get_mahalanobis and gorio_apd_align_batch return
+ *     GORIO_ERR_UNSUPPORTED and change nothing; the other methods' batch calls refuse such a handle as they refuse any foreign one; the double
+ *     covariance getters / setters, gorio_apd_calculate_covariances and the sharded-source calls return GORIO_ERR_STATE;
+ *   - fitness and inlier scores, gorio_apd_transform_source, shared targets (the sharers share the float covariances: a sharer with another k
+ *     or regularisation gets GORIO_ERR_INVALID) and the scan / keyframe hand-offs work; the target's search index is the one every method
+ *     builds, its points are uploaded once.  A neighbour total above 2^31 - 1 returns the search's GORIO_ERR_UNSUPPORTED.
+ * gorio_apd_set_gicp_mp_params: neighbor_search_radius (default 0.5, MPI:35; the reference has no setter).  Stored in every method; not finite
+ * or <= 0: GORIO_ERR_INVALID.  Changing the method, the radius or either cloud drops the pass held.
+ * Parity hooks (this method only; GORIO_ERR_STATE otherwise): gorio_apd_gicp_mp_get_covariances gives the float covariances of the source
+ * (which = 0) or target (1), six floats per point (00 01 02 11 12 22), filled when capacity >= n.  gorio_apd_gicp_mp_pass runs ONE pass at the
+ * float pose T16 (its 12 leading floats are trans) and returns the points used, the neighbour total, H (36) and g (6) (any may be NULL); it
+ * leaves on the device the CSR and the merged distributions, which gorio_apd_gicp_mp_get_neighbors (offsets [n + 1], idx / sqd [total], filled
+ * when capacity >= total) and gorio_apd_gicp_mp_get_merged (mean_B 3 floats, cov_B 6 floats, used flag per source point; capacity >= n) deliver.
+ * An align leaves the CSR of its last pass but no merged distributions.  gorio_apd_gicp_mp_diag: passes of the last align, points used and
+ * neighbour total of the last pass, and the seconds spent per stage (query transform, radius search, merge + linearise, shell) while
+ * gorio_apd profiling was on.
+ */
+int gorio_apd_set_gicp_mp_params(gorio_apd_t* h, double neighbor_search_radius);
+int gorio_apd_get_gicp_mp_params(const gorio_apd_t* h, double* neighbor_search_radius);
+int gorio_apd_gicp_mp_get_covariances(gorio_apd_t* h, int which, int capacity, int* n, float* cov);
+int gorio_apd_gicp_mp_pass(gorio_apd_t* h, const float T16[16], int* used, long long* total, double* H, double* g);
+int gorio_apd_gicp_mp_get_neighbors(gorio_apd_t* h, long long capacity, int* n_queries, long long* total, long long* offsets, int* idx, float* sqd);
+int gorio_apd_gicp_mp_get_merged(gorio_apd_t* h, int capacity, int* n, float* mean_B, float* cov_B, int* used);
+int gorio_apd_gicp_mp_diag(const gorio_apd_t* h, int* passes, int* used, long long* total, double* stage_seconds);
 
 /* parity hooks (VGICP mode; they build the map when it is stale): voxelmap_ (VGH:85) as arrays over the occupied voxels in ascending
  * lexicographic (x, y, z) coordinate order -- coord3: 3 ints, num_points, mean4: GaussianVoxel::mean, cov16: GaussianVoxel::cov row-major
