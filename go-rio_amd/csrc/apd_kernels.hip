@@ -523,8 +523,6 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(6, 6))) voi
     typedef const __attribute__((address_space(1))) float* g_f32p;
     const unsigned long long key = ((g_u64p)pd.best_key)[i];
     const float ax = ((g_f32p)pd.src.x)[i], ay = ((g_f32p)pd.src.y)[i], az = ((g_f32p)pd.src.z)[i];
-    const float src_label = ((g_f32p)pd.src.label)[i];
-    const double src_geo_w = ((g_f64p)pd.src.geo_w)[i];
     double cA[6];
 #pragma unroll
     for (int t = 0; t < 6; ++t) cA[t] = ((g_f64p)pd.src.cov6)[(size_t)i * 6 + t];
@@ -545,7 +543,6 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(6, 6))) voi
       const v4f_lin t4 = ((const __attribute__((address_space(1))) v4f_lin*)pd.tgt.p4)[jj];
       tb = make_float4(t4.x, t4.y, t4.z, t4.w);
     }
-    double* om = pd.omega6 + (size_t)i * 6;
     if (j >= 0) {
       // fp64 from here on is tolerance arithmetic (H, b, error agree with the host restatement to 1e-9): let the compiler fuse
       // multiply-adds in THIS block (the build is -ffp-contract=off for the float search arithmetic, which lives in functions of its own)
@@ -621,7 +618,17 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(6, 6))) voi
       const double q22 = cB[5] + (M20 * R20 + M21 * R21 + M22 * R22);
       PointTerms p;
       inv_sym3(q00, q01, q02, q11, q12, q22, p.o00, p.o01, p.o02, p.o11, p.o12, p.o22);  // APD:217
+      // the geometric weight and the cluster label are wanted only for the error weight below: requested here, behind the register peak
+      // of the covariance block (held from the top of the kernel they were the values that did not fit: stored to scratch, the weight
+      // behind a wait for its own load)
+      double src_geo_w = 0.0;
+      float src_label = 0.0f;
+      if constexpr (METHOD == kMethodApd) {
+        src_geo_w = ((g_f64p)pd.src.geo_w)[i];
+        src_label = ((g_f32p)pd.src.label)[i];
+      }
       if (pd.write_omega) {
+        double* om = pd.omega6 + (size_t)i * 6;
         om[0] = p.o00; om[1] = p.o01; om[2] = p.o02; om[3] = p.o11; om[4] = p.o12; om[5] = p.o22;
       }
 
@@ -658,6 +665,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(6, 6))) voi
       acc[24] = -oe0; acc[25] = -oe1; acc[26] = -oe2;
     } else {
       if (pd.write_omega) {
+        double* om = pd.omega6 + (size_t)i * 6;
         om[0] = 0; om[1] = 0; om[2] = 0; om[3] = 0; om[4] = 0; om[5] = 0;
       }
     }

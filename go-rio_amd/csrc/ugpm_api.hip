@@ -180,8 +180,10 @@ int ensure_context(Ctx& c, int device) {
   if (c.device == device) return 0;
   if (int rc = make_stream_pair(c.main)) return rc;
   // ata_kernel stages J through up to ~128 KB of dynamic LDS (the default limit is 64 KB)
-  UHIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&ug::corr_diag_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 140 * 1024));
-  UHIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&ug::infer_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 17 * (6 * 160 + 16) * 8) /* S = 160: with the 31 KB of static LDS this is just inside the 160 KB of a CU */);
+  UHIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&ug::corr_diag_kernel<kSolveKmaxSmall>), hipFuncAttributeMaxDynamicSharedMemorySize, 140 * 1024));
+  UHIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&ug::corr_diag_kernel<kSolveKmaxFull>), hipFuncAttributeMaxDynamicSharedMemorySize, 140 * 1024));
+  UHIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&ug::infer_kernel<kSolveKmaxSmall>), hipFuncAttributeMaxDynamicSharedMemorySize, 17 * (6 * 160 + 16) * 8));
+  UHIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&ug::infer_kernel<kSolveKmaxFull>), hipFuncAttributeMaxDynamicSharedMemorySize, 17 * (6 * 160 + 16) * 8) /* S = 160: with the 31 KB of static LDS this is just inside the 160 KB of a CU */);
   const void* fns[] = {reinterpret_cast<const void*>(&ug::ata_kernel<4, 16, kAtaTilesCorr>), reinterpret_cast<const void*>(&ug::ata_kernel<8, 16, kAtaTilesCorr>),
                        reinterpret_cast<const void*>(&ug::ata_kernel<16, 8, kAtaTilesCorr>), reinterpret_cast<const void*>(&ug::ata_kernel<4, 16, kAtaTilesLm>),
                        reinterpret_cast<const void*>(&ug::ata_kernel<8, 16, kAtaTilesLm>)};
@@ -388,8 +390,41 @@ void launch_ata(Ctx& c, int max_S, const Run& r, int which, int decide = 0) {
   }
 }
 
+// The solver kernels in the instantiation solver_sizes (ugpm_windows.h) picks for the largest window of the batch.  Each switch names every
+// value solver_sizes can return for that kernel; a smaller instantiation runs the same instructions on the same data as the full one
+// (the conditions are written down with solver_sizes), so which one runs never shows in the results.
+SolverSizes batch_sizes(const Batch& b) { return solver_sizes(b.max_S, (g_debug_path.load() & 4) != 0); }
+
+void launch_gram(const Run& r, const SolverSizes& z) {
+  const dim3 grid(6, r.nw);
+  if (z.gram_rows == kGramRowsSmall) ug::gram_kernel<kGramRowsSmall, kGramKmax><<<grid, 256, 0, r.s>>>(r.wins);
+  else if (z.gram_rows == kGramRows) ug::gram_kernel<kGramRows, kGramKmax><<<grid, 256, 0, r.s>>>(r.wins);
+  else ug::gram_kernel<kCholRowsFull, kSolveKmaxFull><<<grid, 256, 0, r.s>>>(r.wins);
+}
+
+void launch_lm_step(const Run& r, const SolverSizes& z, int problem) {
+  const dim3 grid(r.nw, problem == 1 ? kVelBlocks : 1);
+  if (z.lm_rows == kLmRowsSmall) ug::lm_step_kernel<kLmRowsSmall><<<grid, 512, 0, r.s>>>(r.wins);
+  else ug::lm_step_kernel<kCholRowsFull><<<grid, 512, 0, r.s>>>(r.wins);
+}
+
+void launch_corr_diag(const Run& r, const SolverSizes& z, int max_S) {
+  const dim3 grid((6 * max_S + 15) / 16, r.nw);
+  const size_t lds = sizeof(double) * 17 * (6 * max_S + 16);
+  if (z.solve_kmax == kSolveKmaxSmall) ug::corr_diag_kernel<kSolveKmaxSmall><<<grid, 256, lds, r.s2>>>(r.wins);
+  else ug::corr_diag_kernel<kSolveKmaxFull><<<grid, 256, lds, r.s2>>>(r.wins);
+}
+
+void launch_infer(const Run& r, const SolverSizes& z, int max_S, int max_infer) {
+  const dim3 grid(std::max(1, max_infer), r.nw);
+  const size_t lds = sizeof(double) * 17 * (6 * max_S + 16);
+  if (z.solve_kmax == kSolveKmaxSmall) ug::infer_kernel<kSolveKmaxSmall><<<grid, 256, lds, r.s>>>(r.wins);
+  else ug::infer_kernel<kSolveKmaxFull><<<grid, 256, lds, r.s>>>(r.wins);
+}
+
 int enqueue_tables_and_correlation(Ctx& c, Batch& b) {
   const int max_S = b.max_S;
+  const SolverSizes sizes = batch_sizes(b);
   for (const Run& r : b.runs) {
     {
       Stage st(c, 0, r.s);
@@ -398,7 +433,7 @@ int enqueue_tables_and_correlation(Ctx& c, Batch& b) {
     }
     {
       Stage st(c, 1, r.s);
-      ug::gram_kernel<<<dim3(6, r.nw), 256, 0, r.s>>>(r.wins);
+      launch_gram(r, sizes);
       ug::cross_kernel<<<dim3(12, r.nw, (std::max(b.max_G, b.max_V) + ug::kCrossRows - 1) / ug::kCrossRows), 256, sizeof(double) * ug::kCrossRows * (((max_S + 31) / 32) * 32 + 4), r.s>>>(r.wins);
     }
     // State correlation at the LPM-initialised state.  The reference assembles the Jacobian synchronously (preint.h:887-937) and
@@ -414,7 +449,7 @@ int enqueue_tables_and_correlation(Ctx& c, Batch& b) {
       UHIP(hipEventRecord(r.ev_jac, r.s2));
       launch_ata(c, max_S, r, 2);
       ug::corr_factor_kernel<<<r.nw, 512, 0, r.s2>>>(r.wins);
-      ug::corr_diag_kernel<<<dim3((6 * max_S + 15) / 16, r.nw), 256, sizeof(double) * 17 * (6 * max_S + 16), r.s2>>>(r.wins);
+      launch_corr_diag(r, sizes, max_S);
     }
     UHIP(hipEventRecord(r.ev_corr, r.s2));
   }
@@ -424,6 +459,7 @@ int enqueue_tables_and_correlation(Ctx& c, Batch& b) {
 // ceres::Solve #1 (problem 0, rotation) or #2 (problem 1, velocity), preint.h:943-967
 int run_fit(Ctx& c, Batch& b, int problem) {
   const int max_S = b.max_S;
+  const SolverSizes sizes = batch_sizes(b);
   std::vector<int>& flags = b.flags;
   const bool lmtrace = std::getenv("GORIO_UGPM_LMTRACE") != nullptr;
   const bool speculative = g_speculative_rot.load() != 0;
@@ -440,7 +476,7 @@ int run_fit(Ctx& c, Batch& b, int problem) {
     for (Run& r : b.runs) {
       if (!r.active) continue;
       any = true;
-      ug::lm_step_kernel<<<dim3(r.nw, problem == 1 ? kVelBlocks : 1), 512, 0, r.s>>>(r.wins);
+      launch_lm_step(r, sizes, problem);
       if (problem == 0 && speculative) {
         // three launches per iteration: the candidate residual AND the Jacobian at the candidate in one evaluation, the
         // acceptance test inside the J^T J launch (rot_eval_kernel mode 3, ata_kernel decide)
@@ -516,12 +552,13 @@ int run_fit(Ctx& c, Batch& b, int problem) {
 }
 
 int enqueue_finish_and_infer(Ctx& c, Batch& b) {
+  const SolverSizes sizes = batch_sizes(b);
   for (const Run& r : b.runs) {
     UHIP(hipStreamWaitEvent(r.s, r.ev_corr, 0));  // join of the correlation chain (preint.h:1062-1065)
     {
       Stage st(c, 4, r.s);
       ug::finish_kernel<<<r.nw, 256, 0, r.s>>>(r.wins, c.d_diag + 4 * (size_t)r.g0);
-      ug::infer_kernel<<<dim3(std::max(1, b.max_infer), r.nw), 256, sizeof(double) * 17 * (6 * b.max_S + 16), r.s>>>(r.wins);
+      launch_infer(r, sizes, b.max_S, b.max_infer);
     }
     UHIP(hipEventRecord(r.ev_done, r.s));
   }

@@ -12,6 +12,7 @@ constexpr int kAtaTilesLm = 24, kAtaTilesCorr = 48;  // 16 x 16 output tiles per
 constexpr int kWinInts = 48;        // ints per window: lmi[16], status at 16 (17: of an LPM window), kLmiNeed + problem: iterations fit `problem` needed
 constexpr int kLmiNeed = 18;
 constexpr int kStatusUnfinished = 2;  // internal, never reported: a fit had fewer iterations enqueued than the window needs; the host runs it again
+constexpr int kCholRowsFull = 384;  // panel rows of the largest workgroup Cholesky (ugpm_kernels.hip CholLds; ugpm_windows.h solver_sizes picks smaller ones)
 constexpr int kVelBlocks = 3;       // problem #2's normal matrix is block diagonal (one block per velocity channel): lm_step_kernel runs one workgroup per block
 
 #if defined(__HIPCC__)

@@ -717,13 +717,17 @@ __device__ long long g_chol_t[12];
 #define CHOL_T_VMWAIT do { } while (0)
 #endif
 typedef double f64x4 __attribute__((ext_vector_type(4)));
+// ROWS: panel rows kept in LDS.  kCholRowsFull = 384 (ugpm_device.h) holds every system of the library; a kernel whose systems are smaller takes a smaller
+// capacity under the conditions of ugpm_windows.h (solver_sizes): ROWS also decides the look-ahead, the row ownership and the number of
+// panel passes below, and a smaller instantiation is only used where all of them come out as with 384.
+template <int ROWS>
 struct CholLds {
   double D[2][kCholNB][kCholNB + 1];   // factored diagonal block (double buffered for the look-ahead)
   double Dinv[2][kCholNB];
   double Dt[kCholNB][kCholNB + 1];      // next diagonal block after its trailing update, on its way from MFMA layout to one row per lane
-  double dinv_n[384];        // 1 / L[i][i] of every row, kept for block_backward (filled when a right-hand side is carried)
+  double dinv_n[ROWS + kCholNB < kCholRowsFull ? ROWS + kCholNB : kCholRowsFull];  // 1 / L[i][i] of every row, kept for block_backward (filled when a right-hand side is carried: n < 384 and n <= ROWS + 16)
   unsigned short tile[328];  // q -> (tile row << 8 | tile column) of the lower-triangular 16 x 16 tiling, q = tr (tr + 1) / 2 + tc, tr < 25
-  double P[kCholMaxN > 384 ? 384 : kCholMaxN][kCholNB + 1];  // panel rows of the current block column (n - kb - NB <= 384 rows handled per pass)
+  double P[ROWS][kCholNB + 1];  // panel rows of the current block column (n - kb - NB <= ROWS rows handled per pass)
 };
 
 __device__ __forceinline__ double readlane_f64(double v, int lane) {
@@ -745,7 +749,8 @@ __device__ __forceinline__ double rsqrt_newton(double a) {
   return y;
 }
 
-__device__ __forceinline__ bool block_cholesky(double* __restrict__ A, int n, int lda, CholLds& L, int* __restrict__ sflag, double* __restrict__ rhs = nullptr) {
+template <int ROWS>
+__device__ __forceinline__ bool block_cholesky(double* __restrict__ A, int n, int lda, CholLds<ROWS>& L, int* __restrict__ sflag, double* __restrict__ rhs = nullptr) {
   constexpr int NB = kCholNB;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, nwave = (int)(blockDim.x >> 6);
   if (tid == 0) *sflag = 0;
@@ -760,7 +765,7 @@ __device__ __forceinline__ bool block_cholesky(double* __restrict__ A, int n, in
   // LOOK-AHEAD (matrices that fit one panel pass): the serial factorisation of the NEXT diagonal block runs on wave 0 while the
   // other waves do the trailing update of the current panel -- wave 0 first updates that one 16 x 16 tile, stages it in LDS,
   // re-reads it one row per lane and factors it in registers.  The diagonal block buffers are double buffered.
-  const bool la = n - min(NB, n) + (rhs != nullptr ? 1 : 0) <= 384 && nwave >= 2;  // the first panel (the longest) fits one pass
+  const bool la = n - min(NB, n) + (rhs != nullptr ? 1 : 0) <= ROWS && nwave >= 2;  // the first panel (the longest) fits one pass
   int cur = 0;
   // factor the 16 x 16 block held one row per lane in a[] (lane r = row r, identity rows pad a short block), publish it in
   // L.D[buf] / L.Dinv[buf] and in A
@@ -800,7 +805,7 @@ __device__ __forceinline__ bool block_cholesky(double* __restrict__ A, int n, in
     const int me = m + (rhs != nullptr ? 1 : 0);
     auto panel_row = [&](int i) -> double* { return (rhs != nullptr && i == m) ? rhs + kb : A + (size_t)(kb + nb + i) * lda + kb; };
     double x[NB];
-    const bool own = tid < min(me, 384);
+    const bool own = tid < min(me, ROWS);
     auto load_row = [&](const double* arow) {
 #pragma unroll
       for (int c = 0; c < NB; ++c) x[c] = c < nb ? arow[c] : 0.0;
@@ -824,8 +829,8 @@ __device__ __forceinline__ bool block_cholesky(double* __restrict__ A, int n, in
     }
     if (*sflag) return false;
     if (me <= 0) break;
-    for (int p0 = 0; p0 < me; p0 += 384) {  // panel passes (one pass unless n > 400)
-      const int mp = min(384, me - p0);
+    for (int p0 = 0; p0 < me; p0 += ROWS) {  // panel passes (one pass unless n > ROWS + 16)
+      const int mp = min(ROWS, me - p0);
       for (int i = tid; i < mp; i += blockDim.x) {  // panel solve: row i of L21 = A21 L11^-T (all 16 columns; padding solves to 0)
         double* arow = panel_row(p0 + i);
         if (!(p0 == 0 && i == tid)) load_row(arow);
@@ -941,7 +946,7 @@ __device__ __forceinline__ bool block_cholesky(double* __restrict__ A, int n, in
           }
         }
       }
-      if (p0 != 0 || me > 384) {  // generic (slow) path for matrices larger than one panel pass: element-wise from global memory
+      if (p0 != 0 || me > ROWS) {  // generic (slow) path for matrices larger than one panel pass: element-wise from global memory
         for (long q = tid; q < (long)mp * m; q += blockDim.x) {
           const int i = p0 + (int)(q / m), k = (int)(q % m);
           if (k > i || (p0 == 0 && k < mp)) continue;
@@ -1014,7 +1019,9 @@ __device__ __forceinline__ void wave_backward(const double* __restrict__ L, int 
 // used).  Per block the 16 owners publish their entries and the 16 x 16 diagonal block in LDS (double buffered: ONE barrier per
 // block), every wave then solves the small transposed system redundantly in registers (v_readlane broadcasts) and each thread
 // to the left removes the 16 new unknowns from its own entry.
-__device__ __forceinline__ void block_backward(const double* __restrict__ Lm, int n, int lda, double* __restrict__ x, CholLds& C) {
+template <int ROWS>
+__device__ __forceinline__ void block_backward(const double* __restrict__ Lm, int n, int lda, double* __restrict__ x, CholLds<ROWS>& C) {
+  static_assert(ROWS >= 2 * (kCholNB + 1), "two staging buffers of 17 panel rows");
   constexpr int NB = kCholNB;
   const int tid = threadIdx.x, lane = tid & 63;
   double cur[NB], nxt[NB];
@@ -1094,13 +1101,16 @@ struct Solve16Lds {
   double Pt[4][16][17];  // partial update tiles of the 4 waves
   double Dl[16][17];     // L_ii
 };
+// KMAX: blocks of one block row a wave holds in registers.  Wave v owns k = jb + v + 4 t, so KMAX >= ceil((ceil(n / 16) - 1 - jb) / 4)
+// is needed; 16 holds every system of the library (n <= 1024), a caller with smaller systems takes less (ugpm_windows.h solver_sizes):
+// the iterations t >= KMAX it drops are those whose k < i test fails for every block row.
+template <int KMAX>
 __device__ __forceinline__ void blocked_lower_solve16(const double* __restrict__ Lm, int n, int jb, double* __restrict__ Xc, Solve16Lds& sh) {
   const int nblk = (n + 15) / 16;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int lr = lane & 15, lk = lane >> 4;
   // operand prefetch: for block row i, wave v owns k = jb + v, jb + v + 4, ...; element (row i*16 + lr, col k*16 + k0 + lk), k0 = 0,4,8,12
-  constexpr int KMAX = 16;  // blocks per wave per row: supports nblk - jb <= 64 (n <= 1024)
-  double la[KMAX][4];       // one buffer: the next block row is requested right after the matrix cores consumed the current one
+  double la[KMAX][4];  // one buffer: the next block row is requested right after the matrix cores consumed the current one
   auto fetch = [&](int i) {
 #pragma unroll
     for (int t = 0; t < KMAX; ++t) {
@@ -1219,6 +1229,8 @@ __device__ __forceinline__ void small_gemm_nn(const double* __restrict__ A, cons
 
 // grid: (6 channels, windows), block 256.  preint.h:832-866 for one channel: K + sz2 I = L L^T (block_cholesky), L^-1 by the
 // blocked 16-column forward substitution, K^-1 = L^-T L^-1, K K^-1 and K_int K^-1 on the matrix cores.
+// ROWS >= ceil16(S) panel rows (the factorisation needs ceil16(S - 16), the solve's X the rest), KMAX >= ceil((ceil(S / 16) - 1) / 4).
+template <int ROWS, int KMAX>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) void gram_kernel(const UgpmWin* __restrict__ wins) {
   const WinPart wp = xcd_win_part();
   const UgpmWin w = load_win(wins, wp.win);
@@ -1230,7 +1242,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
   double* Kc = w.JtJ + (size_t)c * S * S;    // scratch: the Gram matrix itself (JtJ / lhs are idle until the LM stage, 9 S^2 each)
   const double* st = w.state_t;
   __shared__ int sflag;
-  __shared__ CholLds chol;
+  __shared__ CholLds<ROWS> chol;
   __shared__ Solve16Lds sh;
   const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63, nwave = (int)(blockDim.x >> 6);
   for (int i = wave; i < S; i += nwave)
@@ -1244,14 +1256,14 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
     if (threadIdx.x == 0) *w.status = -6;
     return;
   }
-  // L^-1, 16 columns at a time (the panel buffer of the factorisation is free: S + 16 <= 384 rows of 17)
+  // L^-1, 16 columns at a time (the panel buffer of the factorisation is free: ceil16(S) <= ROWS rows of 17)
   {
     double* Xc = &chol.P[0][0];
     const int nblk = (S + 15) / 16;
     for (int jb = 0; jb < nblk; ++jb) {
       const int rows = (nblk - jb) * 16;
       for (int q = threadIdx.x; q < rows * 16; q += blockDim.x) Xc[(size_t)(q >> 4) * 17 + (q & 15)] = (q >> 4) == (q & 15) ? 1.0 : 0.0;
-      blocked_lower_solve16(A, S, jb, Xc, sh);
+      blocked_lower_solve16<KMAX>(A, S, jb, Xc, sh);
       for (int i = wave; i < S; i += nwave) {  // column block jb of L^-1: zeros above the diagonal block
         if (lane < 16 && jb * 16 + lane < S) B[(size_t)i * S + jb * 16 + lane] = i >= jb * 16 ? Xc[(size_t)(i - jb * 16) * 17 + lane] : 0.0;
       }
@@ -2067,6 +2079,7 @@ __device__ void lm_begin_block(const UgpmWin& w, int problem) {
 // Every workgroup evaluates the (cheap, deterministic) global quantities for itself -- cost, gradient maximum, |x| -- and writes
 // identical values; the words a step consumes or counts are updated by the evaluation kernel that follows (lm_step_bookkeeping), so no
 // workgroup reads a control word another one writes in the same launch.
+template <int ROWS>
 __global__ __launch_bounds__(512) void lm_step_kernel(const UgpmWin* __restrict__ wins) {
   const UgpmWin w = load_win(wins, blockIdx.x);
   if (*w.status != 0 || w.lmi[1]) return;
@@ -2084,7 +2097,7 @@ __global__ __launch_bounds__(512) void lm_step_kernel(const UgpmWin* __restrict_
   double* xn = w.lmv + 6 * (size_t)n;
   __shared__ double sred[8];
   __shared__ int sflag;
-  __shared__ CholLds chol;
+  __shared__ CholLds<ROWS> chol;
   if (w.lmi[3]) {  // a fresh linearisation arrived
     double c = 0.0;
     for (int k = threadIdx.x; k < m; k += blockDim.x) c += w.res[k] * w.res[k];
@@ -2124,7 +2137,7 @@ __global__ __launch_bounds__(512) void lm_step_kernel(const UgpmWin* __restrict_
   __syncthreads();
   double* L = w.lhs + (size_t)j0 * n + j0;  // this workgroup's diagonal block inside the n x n buffer (row stride n)
   __shared__ double xs[kCholMaxN / 2];
-  const bool fused = ns < 384 && ns <= (int)blockDim.x && ns <= kCholMaxN / 2;  // rhs rides through the factorisation, blocked back-substitution
+  const bool fused = ns < kCholRowsFull && ns <= (int)blockDim.x && ns <= kCholMaxN / 2;  // rhs rides through the factorisation, blocked back-substitution
   for (int i = threadIdx.x >> 6; i < ns; i += (int)(blockDim.x >> 6)) {  // lower triangle of D J^T J D + diag / radius, one row per wave
     const double si = scale[j0 + i];
     for (int j = threadIdx.x & 63; j <= i; j += 64)
@@ -2228,7 +2241,7 @@ __global__ __launch_bounds__(512) void corr_factor_kernel(const UgpmWin* __restr
   if (*w.status != 0 || !w.correlate) return;
   const int n = 6 * w.S;
   __shared__ int sflag;
-  __shared__ CholLds chol;
+  __shared__ CholLds<kCholRowsFull> chol;  // n = 6 S: already 381 rows at S = 66
   for (int i = threadIdx.x; i < n; i += blockDim.x) w.Ac[(size_t)i * n + i] += 0.00001;
   __syncthreads();
   if (!block_cholesky(w.Ac, n, n, chol, &sflag)) {
@@ -2239,6 +2252,7 @@ __global__ __launch_bounds__(512) void corr_factor_kernel(const UgpmWin* __restr
 
 // diag(A^-1) = squared column norms of L^-1, 16 columns per workgroup; then dsc = state_std / sqrt(diag(A^-1)) (preint.h:1487-1489).
 // grid: (ceil(6S / 16), windows), block 256.  Dynamic LDS: (rows + 16) * 17 doubles for X, rows = 6 max_S.
+template <int KMAX>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) void corr_diag_kernel(const UgpmWin* __restrict__ wins) {
   const WinPart wp = xcd_win_part();
   const UgpmWin w = load_win(wins, wp.win);
@@ -2252,7 +2266,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
     const int rows = ((n + 15) / 16 - jb) * 16;
     for (int q = threadIdx.x; q < rows * 16; q += blockDim.x) Xc[(size_t)(q >> 4) * 17 + (q & 15)] = (q >> 4) == (q & 15) ? 1.0 : 0.0;  // E_j
   }
-  blocked_lower_solve16(w.Ac, n, jb, Xc, sh);
+  blocked_lower_solve16<KMAX>(w.Ac, n, jb, Xc, sh);
   if (threadIdx.x < 16) {
     const int c = threadIdx.x, col = j0 + c;
     const int rows = ((n + 15) / 16 - jb) * 16;
@@ -2336,6 +2350,7 @@ __global__ __launch_bounds__(256) void finish_kernel(const UgpmWin* __restrict__
 
 // Se3Integrator::get(t) (preint.h:1069-1153) + cov inflation of VelPreintegration::get (preint.h:1744-1757).
 // grid: (max n_infer, windows), block 256.
+template <int KMAX>
 __global__ __launch_bounds__(256) void infer_kernel(const UgpmWin* __restrict__ wins) {
   const WinPart wp = xcd_win_part();
   const UgpmWin w = load_win(wins, wp.win);
@@ -2419,7 +2434,7 @@ __global__ __launch_bounds__(256) void infer_kernel(const UgpmWin* __restrict__ 
       const int c = row / S;
       Xc[(size_t)row * 17 + c] = w.dsc[row] * ksK[c][row - c * S];
     }
-    blocked_lower_solve16(w.Ac, n, 0, Xc, sh);
+    blocked_lower_solve16<KMAX>(w.Ac, n, 0, Xc, sh);
     for (int pair = 0; pair < 21; ++pair) {
       int a2 = 0, b2 = pair;
       while (b2 >= 6 - a2) { b2 -= 6 - a2; ++a2; }

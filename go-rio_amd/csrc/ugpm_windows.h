@@ -15,6 +15,8 @@
 namespace gorio {
 namespace windows {
 
+constexpr int kMaxStates = 160;  // plan_window refuses larger windows; the solver kernels' capacities (solver_sizes below) are sized for it
+
 struct HostWin {
   int g0 = 0, G = 0, v0 = 0, V = 0, S = 0;
   double state_freq = 0;
@@ -105,7 +107,7 @@ inline int plan_window(const gorio_ugpm_window& w, HostWin& h, std::string& err)
   sf = std::min(sf, std::min(vel_freq, gyr_freq));
   h.state_freq = sf;
   h.S = (int)(std::ceil(duration * sf) + (2 * w.overlap));  // preint.h:775
-  if (h.S < 2 * w.overlap + 1 || h.S > 160) return fail(GORIO_UGPM_ERR_UNSUPPORTED, "number of GP states outside [2 overlap + 1, 160]");
+  if (h.S < 2 * w.overlap + 1 || h.S > kMaxStates) return fail(GORIO_UGPM_ERR_UNSUPPORTED, "number of GP states outside [2 overlap + 1, 160]");
   h.state_t.resize(h.S);
   const double t0 = w.start_t - (((double)w.overlap) / sf);
   for (int k = 0; k < h.S; ++k) h.state_t[k] = t0 + ((double)k) / sf;  // preint.h:777-783
@@ -163,6 +165,59 @@ inline FitOutcome fit_outcome(const int* ints, const std::vector<HostWin>& hw) {
   }
   return o;
 }
+
+// ---- which instantiations of the solver kernels a batch runs (ugpm_kernels.hip: CholLds<ROWS>, block_cholesky, blocked_lower_solve16<KMAX>).
+// ROWS is the number of 16-column panel rows block_cholesky keeps in LDS, KMAX the number of 16 x 16 blocks of one block row a wave of
+// blocked_lower_solve16 prefetches into registers.  The kernels were built for the largest system of the library (ROWS = 384, KMAX = 16);
+// a window of S <= 160 states needs far less, and registers and LDS that hold nothing cost scratch traffic, waves per SIMD and room on the
+// CU the scan matcher's kernels share (profiles/r21/gp_footprint.md).  A smaller instantiation runs the SAME instructions on the same data as the full one, under these conditions:
+//   block_cholesky of an n x n system (+ 1 row where a right-hand side rides along): ROWS decides the look-ahead (`la`), which threads own
+//   a panel row (`own`), the number of panel passes and the element-wise fall-back.  With me0 = n - min(16, n) + rhs, the rows of the first
+//   (longest) panel, every one of them comes out as with 384 exactly when me0 <= ROWS (chol_same_path).  What is stored: the panel rows up
+//   to the end of the last 16-row tile, the right-hand-side row behind the matrix rows (chol_rows_needed), and n <= ROWS + 16 inverse pivots;
+//   blocked_lower_solve16 of n rows from block row jb: wave v multiplies blocks k = jb + v + 4 t < i <= ceil(n / 16) - 1, so every t >=
+//   ceil((ceil(n / 16) - 1) / 4) fails the k < i test for every wave and block row (solve16_blocks_needed): those iterations load
+//   predicated zeros and multiply nothing.
+// The largest window of a batch decides for all of its windows: the needs grow with S, so a smaller window fits what the largest one fits.
+constexpr int kSolveKmaxFull = 16;  // with kCholRowsFull (ugpm_device.h) the capacities every kernel had before they were sized; gorio_ugpm_debug_set_path bit 2 brings them back
+constexpr int kGramRowsSmall = 96, kGramRows = 160;  // gram_kernel: n = S, and ceil16(S) rows of the solve's X in the same buffer
+constexpr int kGramKmax = 3;                         // gram_kernel's solve: n = S <= 160, 10 block rows
+constexpr int kLmRowsSmall = 192;                    // lm_step_kernel: n <= 3 S with the right-hand side, block_backward's 34 staging rows
+constexpr int kSolveKmaxSmall = 8;                   // corr_diag_kernel, infer_kernel: n = 6 S
+
+constexpr int ceil16(int v) { return (v + 15) / 16 * 16; }
+// rows of the first panel of block_cholesky: what `la`, `own`, the pass count and the fall-back compare with ROWS
+constexpr int chol_first_panel(int n, bool rhs) { return n - (n < 16 ? n : 16) + (rhs ? 1 : 0); }
+constexpr bool chol_same_path(int rows, int n, bool rhs) { return chol_first_panel(n, rhs) <= rows; }
+// panel rows written in one pass: the matrix rows padded to whole 16-row tiles, and with a right-hand side its row behind the m matrix rows
+constexpr int chol_rows_needed(int n, bool rhs) {
+  const int m = n - (n < 16 ? n : 16);
+  return rhs ? (ceil16(m) > m + 1 ? ceil16(m) : m + 1) : ceil16(m);
+}
+constexpr int solve16_blocks_needed(int n) { return (ceil16(n) / 16 - 1 + 3) / 4; }
+constexpr int gram_rows_needed(int S) { return chol_rows_needed(S, false) > ceil16(S) ? chol_rows_needed(S, false) : ceil16(S); }
+constexpr int lm_rows_needed(int S) { return chol_rows_needed(3 * S, true) > 34 ? chol_rows_needed(3 * S, true) : 34; }
+constexpr bool gram_fits(int rows, int S) { return gram_rows_needed(S) <= rows && chol_same_path(rows, S, false); }
+// a fit's step factors 3 S unknowns (rotation) or S (one velocity channel); the right-hand side rides along below 384 unknowns
+constexpr bool lm_fits(int rows, int S) { return 3 * S < kCholRowsFull && lm_rows_needed(S) <= rows && 3 * S <= rows + 16 && chol_same_path(rows, 3 * S, true) && chol_same_path(rows, S, true); }
+
+struct SolverSizes {
+  int gram_rows, gram_kmax;  // gram_kernel<ROWS, KMAX>
+  int lm_rows;               // lm_step_kernel<ROWS>
+  int solve_kmax;            // corr_diag_kernel<KMAX>, infer_kernel<KMAX>
+};
+
+// the instantiations for a batch whose largest window has max_S states; `full`: the capacities from before the sizing, for comparisons.
+// Every branch ends in an instantiation that holds max_S <= kMaxStates (the static_asserts below); nothing is left to check at run time.
+constexpr SolverSizes solver_sizes(int max_S, bool full) {
+  if (full) return SolverSizes{kCholRowsFull, kSolveKmaxFull, kCholRowsFull, kSolveKmaxFull};
+  return SolverSizes{gram_fits(kGramRowsSmall, max_S) ? kGramRowsSmall : kGramRows, kGramKmax, lm_fits(kLmRowsSmall, max_S) ? kLmRowsSmall : kCholRowsFull,
+                     solve16_blocks_needed(6 * max_S) <= kSolveKmaxSmall ? kSolveKmaxSmall : kSolveKmaxFull};
+}
+static_assert(gram_fits(kGramRows, kMaxStates) && solve16_blocks_needed(kMaxStates) <= kGramKmax, "gram_kernel's capacities hold the largest window");
+static_assert(solve16_blocks_needed(6 * kMaxStates) <= kSolveKmaxFull, "the full solve holds the largest correlation system");
+static_assert(solver_sizes(66, false).gram_rows == kGramRowsSmall && solver_sizes(66, false).lm_rows == kLmRowsSmall && solver_sizes(66, false).solve_kmax == kSolveKmaxSmall,
+              "the 66-state window of the scan-to-scan step runs the small instantiations");
 
 // ---- opt.type = LPM (preint.h:1567-1580): host bookkeeping of one IterativeIntegrator = the merged, sorted time line
 // (SortIndexTracker2, types.h:332-458) and the filler stamps of preint.h:228-237.  No numerics.

@@ -153,13 +153,14 @@ def ugpm_debug_set_schedule(speculative_rot=True):
     lib.gorio_ugpm_debug_set_schedule(1 if speculative_rot else 0)
 
 
-def ugpm_debug_set_path(dense_ata=False, draining_looks=False):
-    """gorio_ugpm_debug_set_path (test hook, process-wide): the correlation J^T J over every row in every workgroup, and the fits with a
-    look at the done flags (a stream drain) even when the iteration budget is known.  Both default to off; the results are the same bits."""
+def ugpm_debug_set_path(dense_ata=False, draining_looks=False, full_capacity=False):
+    """gorio_ugpm_debug_set_path (test hook, process-wide): the correlation J^T J over every row in every workgroup, the fits with a
+    look at the done flags (a stream drain) even when the iteration budget is known, and the solver kernels with the register and LDS
+    capacities of the largest system of the library instead of those sized to the batch.  All default to off; the results are the same bits."""
     lib = load_library()
     lib.gorio_ugpm_debug_set_path.argtypes = [C.c_int]
     lib.gorio_ugpm_debug_set_path.restype = None
-    lib.gorio_ugpm_debug_set_path((1 if dense_ata else 0) | (2 if draining_looks else 0))
+    lib.gorio_ugpm_debug_set_path((1 if dense_ata else 0) | (2 if draining_looks else 0) | (4 if full_capacity else 0))
 
 
 def ugpm_stage_times():

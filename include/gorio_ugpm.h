@@ -128,7 +128,9 @@ void gorio_ugpm_debug_set_schedule(int speculative_rot);
 
 /* Test hook, process-wide, for A/B runs of the same library: bit 0 of `flags` selects the dense J^T J of the state correlation (the
  * plain cut of the output tiles, every workgroup streams every row of the Jacobian) instead of the one that starts the workgroups
- * whose tiles get nothing from the gyro rows behind those rows.  The two compute the same bits; tests compare them.  Default 0. */
+ * whose tiles get nothing from the gyro rows behind those rows.  Bit 1 makes every fit look at the done flags.  Bit 2 runs the solver kernels
+ * (Gram, trust-region step, correlation diagonal, inference) with the register and LDS capacities of the largest system of the library
+ * instead of those sized to the batch's largest window.  Each pair computes the same bits; tests compare them.  Default 0. */
 void gorio_ugpm_debug_set_path(int flags);
 
 #ifdef __cplusplus

@@ -11,7 +11,7 @@ using namespace gorio;
 using namespace gorio::ug;
 
 __global__ __launch_bounds__(512) void chol_bench_kernel(double* mats, int n, int reps, int with_rhs, double* xout, double* rhs_all) {
-  __shared__ CholLds chol;
+  __shared__ CholLds<kCholRowsFull> chol;
   __shared__ int sflag;
   __shared__ double xs[480];
   double* orig = mats + (size_t)blockIdx.x * 2 * n * n;
