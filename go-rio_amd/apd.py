@@ -60,6 +60,7 @@ APD_SYMBOLS = [
     "gorio_apd_set_vgicp_cuda_params", "gorio_apd_get_vgicp_cuda_params", "gorio_apd_vgicp_cuda_get_points", "gorio_apd_vgicp_cuda_get_voxels", "gorio_apd_vgicp_cuda_get_pairs",
     "gorio_apd_set_gicp_mp_params", "gorio_apd_get_gicp_mp_params", "gorio_apd_gicp_mp_get_covariances", "gorio_apd_gicp_mp_pass", "gorio_apd_gicp_mp_get_neighbors", "gorio_apd_gicp_mp_get_merged",
     "gorio_apd_gicp_mp_diag",
+    "gorio_apd_set_submap_downsample", "gorio_apd_get_submap_downsample",
 ]
 
 # gorio_method / gorio_voxel_search / gorio_voxel_mode of gorio_apd.h (the latter two in the order of gicp_settings.hpp)
@@ -72,6 +73,7 @@ METHOD_GICP_MP = 8  # gorio_method_fast_gicp_mp: fast_gicp::FastGICPMultiPoints 
 GICP_OMP_F, GICP_OMP_DF, GICP_OMP_FDF = 0, 1, 2  # modes of gorio_apd_gicp_omp_evaluate
 VOXEL_DIRECT27, VOXEL_DIRECT7, VOXEL_DIRECT1, VOXEL_DIRECT_RADIUS = 0, 1, 2, 3
 VOXEL_ADDITIVE, VOXEL_ADDITIVE_WEIGHTED, VOXEL_MULTIPLICATIVE = 0, 1, 2
+DOWNSAMPLE_VOXELGRID, DOWNSAMPLE_APPROX_VOXELGRID = 0, 1  # gorio_downsample_method: what a submap call's voxel_leaf > 0 runs
 VOXEL_OFFSETS = {VOXEL_DIRECT27: 27, VOXEL_DIRECT7: 7, VOXEL_DIRECT1: 1}
 
 _lib = None
@@ -462,6 +464,14 @@ class ApdGicp:
                                                                           int(ids.shape[0]), C.c_double(voxel_leaf), C.byref(cnt)))
         self._n_tgt = cnt.value
         return cnt.value
+
+    def setSubmapDownsample(self, method):  # noqa: N802 -- gorio_apd_set_submap_downsample: DOWNSAMPLE_VOXELGRID (default) or DOWNSAMPLE_APPROX_VOXELGRID
+        _check(self._h, self._lib.gorio_apd_set_submap_downsample(self._h, int(method)))
+
+    def getSubmapDownsample(self):  # noqa: N802
+        m = C.c_int(0)
+        _check(self._h, self._lib.gorio_apd_get_submap_downsample(self._h, C.byref(m)))
+        return m.value
 
     def getTargetPoints(self):  # noqa: N802
         buf = np.empty((self._n_tgt, 4), np.float32)

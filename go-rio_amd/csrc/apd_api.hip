@@ -34,6 +34,7 @@
 #include "apd_kernels.hip"
 #include "apd_index.hip"
 #include "apd_submap.hip"
+#include "apd_approx_voxel.hip"
 #include "apd_voxel.hip"
 #include "apd_ndt_cuda.hip"
 #include "apd_vgicp_cuda.hip"
@@ -278,6 +279,8 @@ struct gorio_apd {
   DevBuf<unsigned int> d_sub_bb;
   DevBuf<void> d_sub_kframes;  // gorio_apd_set_target_submap_keyframes (apd_keyframes.hip): frame table, and the finite points per 256-point block
   DevBuf<int> d_sub_kcnt;
+  int sub_downsample = GORIO_DOWNSAMPLE_VOXELGRID;  // gorio_apd_set_submap_downsample: what a voxel_leaf > 0 runs (SMO:140-154)
+  AvgScratch avg;  // pcl::ApproximateVoxelGrid (apd_approx_voxel.hip): the submap mode above and gorio_prep_approx_voxel_downsample
   // sharded-source mode (gorio_apd_comm_init): RCCL communicator over the ranks that share one source cloud
   ncclComm_t comm = nullptr;
   int comm_world = 1, comm_rank = 0;
@@ -2236,7 +2239,23 @@ int gorio_apd_set_target_submap(gorio_apd_t* h, const gorio_apd_keyframe* frames
 static int submap_finish(gorio_apd* h, int m, double voxel_leaf, int* n_target) {
   const float4* result = h->d_sub_out;
   int n_out = m;
-  if (voxel_leaf > 0.0) {  // pcl::VoxelGrid (SMO:145-149)
+  if (voxel_leaf > 0.0 && h->sub_downsample == GORIO_DOWNSAMPLE_APPROX_VOXELGRID) {  // pcl::ApproximateVoxelGrid (SMO:150-154), cubic, over (x, y, z, label)
+    if (m > kAvgMaxPoints) return fail(h, GORIO_ERR_INVALID, "set_target_submap: too many points for the approximate voxel grid");
+    const float* base = reinterpret_cast<const float*>(h->d_sub_out.get());
+    float* obase = reinterpret_cast<float*>(h->d_sub_vox.get());
+    AvgCols in{};
+    AvgColsOut out{};
+    for (int f = 0; f < 4; ++f) in.c[f] = base + f, out.c[f] = obase + f;
+    in.stride = out.stride = 4;
+    const float lf = (float)voxel_leaf;
+    const float leaf3[3] = {lf, lf, lf};
+    const int* d_n_out = nullptr;
+    HIP_TRY(h, avg_enqueue(h->stream, h->avg, in, m, 4, leaf3, out, m, &d_n_out));
+    HIP_TRY(h, hipMemcpyAsync(&n_out, d_n_out, sizeof(int), hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(h, hipStreamSynchronize(h->stream));  // also covers the pageable staging vectors above
+    if (n_out < 0) return fail(h, GORIO_ERR_INVALID, "set_target_submap: a cell coordinate of the approximate voxel grid leaves (-2^30, 2^30); the target is unchanged");
+    result = h->d_sub_vox;
+  } else if (voxel_leaf > 0.0) {  // pcl::VoxelGrid (SMO:145-149)
     unsigned int bb[6];
     vox_bbox_init_kernel<<<1, 64, 0, h->stream>>>(h->d_sub_bb);
     vox_bbox_kernel<<<std::min(256, (m + 255) / 256), 256, 0, h->stream>>>(h->d_sub_out, m, h->d_sub_bb);
@@ -2311,6 +2330,18 @@ int gorio_apd_get_target_points(gorio_apd_t* h, float* xyz_out, float* label_out
     o[0] = tmp[i].x; o[1] = tmp[i].y; o[2] = tmp[i].z;
     if (label_out) label_out[(size_t)i * st] = tmp[i].w;
   }
+  return GORIO_OK;
+}
+
+int gorio_apd_set_submap_downsample(gorio_apd_t* h, int method) {
+  if (!h) return GORIO_ERR_INVALID;
+  if (method != GORIO_DOWNSAMPLE_VOXELGRID && method != GORIO_DOWNSAMPLE_APPROX_VOXELGRID) return fail(h, GORIO_ERR_INVALID, "set_submap_downsample: unknown method");
+  h->sub_downsample = method;
+  return GORIO_OK;
+}
+int gorio_apd_get_submap_downsample(const gorio_apd_t* h, int* method) {
+  if (!h || !method) return GORIO_ERR_INVALID;
+  *method = h->sub_downsample;
   return GORIO_OK;
 }
 

@@ -600,6 +600,100 @@ int gorio_prep_voxel_downsample(int device, const float* xyz, int n, int point_s
   return GORIO_OK;
 }
 
+// ---- pcl::ApproximateVoxelGrid (apd_approx_voxel.hip)
+static int avg_check_common(int n, int n_fields, const double* leaf, float leaf_f[3], const int* n_out) {
+  if (!n_out || !leaf || n < 0 || n > kAvgMaxPoints || n_fields < 3 || n_fields > kAvgMaxFields) return GORIO_ERR_INVALID;
+  for (int a = 0; a < 3; ++a) {
+    leaf_f[a] = (float)leaf[a];  // setLeafSize takes floats
+    if (!std::isfinite(leaf[a]) || !(leaf_f[a] > 0.0f) || !std::isfinite(leaf_f[a])) return GORIO_ERR_INVALID;
+  }
+  return GORIO_OK;
+}
+
+// the launches, the 4-byte read-back and what it says; the context's handle holds the scratch
+static int avg_run(PrepCtx& c, hipStream_t stream, const AvgCols& in, int n, int n_fields, const float leaf_f[3], const AvgColsOut& out, int capacity, int* n_out) {
+  const int* d_n_out = nullptr;
+  int m = 0;
+  GORIO_HIP_CHECK(prep_fail, avg_enqueue(stream, c.h->avg, in, n, n_fields, leaf_f, out, capacity, &d_n_out));
+  GORIO_HIP_CHECK(prep_fail, hipMemcpyAsync(&m, d_n_out, sizeof(int), hipMemcpyDeviceToHost, stream));
+  GORIO_HIP_CHECK(prep_fail, hipStreamSynchronize(stream));
+  if (m < 0) {
+    *n_out = 0;
+    return prep_fail(GORIO_ERR_INVALID, "approx_voxel_downsample: refused: a coordinate is not finite or a cell coordinate leaves (-2^30, 2^30)");
+  }
+  *n_out = m;
+  if (m > capacity) return prep_fail(GORIO_ERR_INVALID, "approx_voxel_downsample: output capacity too small (n_out holds the size needed)");
+  return GORIO_OK;
+}
+
+int gorio_prep_approx_voxel_downsample(int device, const float* pts, int n, int stride_bytes, const int* field_offsets, int n_fields, const double leaf[3], float* out,
+                                       int out_stride_bytes, int out_capacity, int* n_out) {
+  float leaf_f[3];
+  if (avg_check_common(n, n_fields, leaf, leaf_f, n_out) || !field_offsets || stride_bytes <= 0 || (stride_bytes % 4) || out_stride_bytes <= 0 || (out_stride_bytes % 4) ||
+      out_capacity < 0 || (out_capacity > 0 && !out) || (n > 0 && !pts))
+    return prep_fail(GORIO_ERR_INVALID, "approx_voxel_downsample: bad arguments");
+  const int st = stride_bytes / 4, ost = out_stride_bytes / 4;
+  for (int f = 0; f < n_fields; ++f)
+    if (field_offsets[f] < 0 || field_offsets[f] >= st || field_offsets[f] >= ost) return prep_fail(GORIO_ERR_INVALID, "approx_voxel_downsample: a field offset lies outside the point");
+  *n_out = 0;
+  if (n == 0) return GORIO_OK;
+  int rc = GORIO_OK;
+  PrepCtx* ctx = prep_context(device, "approx_voxel_downsample", rc);
+  if (!ctx) return rc;
+  PrepCtx& c = *ctx;
+  gorio_apd* h = c.h;
+  GORIO_HIP_CHECK(prep_fail, hipSetDevice(device));
+  AvgScratch& w = h->avg;
+  const size_t need = (size_t)n * n_fields, grown = ((size_t)n + (size_t)n / 8) * kAvgMaxFields;
+  GORIO_HIP_CHECK(prep_fail, w.stage_in.reserve(need, grown));
+  GORIO_HIP_CHECK(prep_fail, w.stage_out.reserve(need, grown));
+  std::vector<float> cols(need);  // columns [n_fields][n]
+  for (int f = 0; f < n_fields; ++f) {
+    const float* src = pts + field_offsets[f];
+    float* dst = cols.data() + (size_t)f * n;
+    for (int i = 0; i < n; ++i) dst[i] = src[(size_t)i * st];
+  }
+  GORIO_HIP_CHECK(prep_fail, hipMemcpyAsync(w.stage_in, cols.data(), sizeof(float) * need, hipMemcpyHostToDevice, h->stream));
+  AvgCols in{};
+  AvgColsOut oc{};
+  for (int f = 0; f < n_fields; ++f) in.c[f] = w.stage_in + (size_t)f * n, oc.c[f] = w.stage_out + (size_t)f * n;
+  in.stride = oc.stride = 1;
+  rc = avg_run(c, h->stream, in, n, n_fields, leaf_f, oc, std::min(out_capacity, n), n_out);
+  if (rc) return rc;
+  const int m = *n_out;
+  for (int f = 0; f < n_fields; ++f)
+    GORIO_HIP_CHECK(prep_fail, hipMemcpyAsync(cols.data() + (size_t)f * n, oc.c[f], sizeof(float) * m, hipMemcpyDeviceToHost, h->stream));
+  GORIO_HIP_CHECK(prep_fail, hipStreamSynchronize(h->stream));
+  for (int f = 0; f < n_fields; ++f) {
+    const float* src = cols.data() + (size_t)f * n;
+    float* dst = out + field_offsets[f];
+    for (int i = 0; i < m; ++i) dst[(size_t)i * ost] = src[i];
+  }
+  return GORIO_OK;
+}
+
+int gorio_prep_approx_voxel_downsample_device(int device, const float* const* cols, int n_fields, int n, const double leaf[3], float* const* cols_out, int capacity, int* n_out,
+                                              void* stream) {
+  float leaf_f[3];
+  if (avg_check_common(n, n_fields, leaf, leaf_f, n_out) || capacity < 0 || (n > 0 && !cols) || (capacity > 0 && !cols_out))
+    return prep_fail(GORIO_ERR_INVALID, "approx_voxel_downsample_device: bad arguments");
+  AvgCols in{};
+  AvgColsOut oc{};
+  for (int f = 0; f < n_fields; ++f) {
+    if ((n > 0 && !cols[f]) || (capacity > 0 && !cols_out[f])) return prep_fail(GORIO_ERR_INVALID, "approx_voxel_downsample_device: a column pointer is NULL");
+    in.c[f] = n > 0 ? cols[f] : nullptr;
+    oc.c[f] = capacity > 0 ? cols_out[f] : nullptr;
+  }
+  in.stride = oc.stride = 1;
+  *n_out = 0;
+  if (n == 0) return GORIO_OK;
+  int rc = GORIO_OK;
+  PrepCtx* ctx = prep_context(device, "approx_voxel_downsample_device", rc);
+  if (!ctx) return rc;
+  GORIO_HIP_CHECK(prep_fail, hipSetDevice(device));
+  return avg_run(*ctx, static_cast<hipStream_t>(stream), in, n, n_fields, leaf_f, oc, capacity, n_out);
+}
+
 }  // extern "C"
 
 // ----------------------------------------------------------------------------------------------- REVE (include/gorio_prep.h)

@@ -226,6 +226,14 @@ public:
     }
     return out;
   }
+  // downsample_method of the nodelets (scan_matching_odometry_nodelet.cpp:140-154) for the voxel_leaf > 0 branch of setInputTargetSubmap:
+  // GORIO_DOWNSAMPLE_VOXELGRID (default) or GORIO_DOWNSAMPLE_APPROX_VOXELGRID (gorio_apd_set_submap_downsample); it stays until set again
+  void setSubmapDownsampleMethod(int method) { check(gorio_apd_set_submap_downsample(handle_, method)); }
+  int getSubmapDownsampleMethod() const {
+    int m = 0;
+    gorio_apd_get_submap_downsample(handle_, &m);
+    return m;
+  }
   // Scan-to-submap target assembly on the GPU (extra; replaces the CPU loop of scan_matching_odometry_nodelet.cpp:602-612): keyframe
   // clouds moved by their relative poses, concatenated, downsampled (voxel_leaf <= 0: the launch files' NONE), set as the target.  The
   // assembled cloud is also returned as a pcl cloud and kept as target_, because pcl::Registration::align() insists on one.

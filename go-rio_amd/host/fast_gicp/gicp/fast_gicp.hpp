@@ -158,6 +158,17 @@ public:
     lazy_tree_->defer(out);
     return out;
   }
+  // the host-cloud form of the same assembly, and which filter its voxel_leaf > 0 runs (FastAPDGICP::setSubmapDownsampleMethod)
+  PointCloudTargetConstPtr setInputTargetSubmap(const std::vector<PointCloudTargetConstPtr>& clouds,
+                                                const std::vector<Eigen::Matrix4d, Eigen::aligned_allocator<Eigen::Matrix4d>>& rel_poses, double voxel_leaf = 0.0) {
+    push_settings();
+    PointCloudTargetConstPtr out = backend_->setInputTargetSubmap(clouds, rel_poses, voxel_leaf);
+    pcl::Registration<PointSource, PointTarget, Scalar>::setInputTarget(out);
+    lazy_tree_->defer(out);
+    return out;
+  }
+  void setSubmapDownsampleMethod(int method) { backend_->setSubmapDownsampleMethod(method); }
+  int getSubmapDownsampleMethod() const { return backend_->getSubmapDownsampleMethod(); }
   gorio_apd_t* handle() { return backend_->handle(); }
 
 protected:

@@ -164,6 +164,12 @@ class NormalDistributionsTransform : public pcl::Registration<PointSource, Point
     fit_target_stale_ = false;
     return out;
   }
+  // which filter the voxel_leaf > 0 branch of setInputTargetSubmap runs: GORIO_DOWNSAMPLE_VOXELGRID (default) or
+  // GORIO_DOWNSAMPLE_APPROX_VOXELGRID, on the fitness handle that assembles the submap (gorio_apd_set_submap_downsample)
+  void setSubmapDownsampleMethod(int method) {
+    ensure_fitness_handle("setSubmapDownsampleMethod");
+    check_apd(gorio_apd_set_submap_downsample(fit_, method), "setSubmapDownsampleMethod");
+  }
   void setResolution(float resolution) {  // NDTH:132-142
     p_.resolution = resolution;
     push("setResolution");

@@ -5,7 +5,7 @@ import numpy as np
 
 from .apd import GorioError, load_library
 
-PREP_SYMBOLS = ["gorio_prep_dbscan_labels", "gorio_prep_radius_outlier_mask", "gorio_prep_statistical_outlier_mask", "gorio_prep_voxel_downsample", "gorio_prep_last_error", "gorio_prep_reve_default_config", "gorio_prep_reve_ransac_iterations", "gorio_prep_ego_velocity"]
+PREP_SYMBOLS = ["gorio_prep_dbscan_labels", "gorio_prep_radius_outlier_mask", "gorio_prep_statistical_outlier_mask", "gorio_prep_voxel_downsample", "gorio_prep_approx_voxel_downsample", "gorio_prep_approx_voxel_downsample_device", "gorio_prep_last_error", "gorio_prep_reve_default_config", "gorio_prep_reve_ransac_iterations", "gorio_prep_ego_velocity"]
 
 
 def dbscan_labels(xyz, eps=0.9, core_min_pts=10, min_cluster_size=20, max_cluster_size=25000, device=0):
@@ -35,6 +35,26 @@ def voxel_downsample(xyz, leaf=0.1, device=0):
     out = np.zeros((n, 3), np.float32)
     m = C.c_int(0)
     rc = lib.gorio_prep_voxel_downsample(int(device), C.c_void_p(xyz.__array_interface__["data"][0]), n, 12, C.c_double(leaf), C.c_void_p(out.__array_interface__["data"][0]), 12, n, C.byref(m))
+    if rc < 0:
+        msg = lib.gorio_prep_last_error()
+        raise GorioError(rc, msg.decode() if msg else "")
+    return out[:m.value].copy()
+
+
+def approx_voxel_downsample(points, leaf, device=0):
+    """pcl::ApproximateVoxelGrid (include/gorio_prep.h): points [n, F] float32, 3 <= F <= 8, columns 0..2 = x y z, every column averaged;
+    leaf a scalar or three values.  Returns the filtered [m, F] array in the filter's flush order.  A refused cloud raises GorioError(-1)."""
+    lib = load_library()
+    lib.gorio_prep_last_error.restype = C.c_char_p
+    pts = np.ascontiguousarray(points, np.float32)
+    if pts.ndim != 2:
+        raise ValueError("points must be [n, F]")
+    n, nf = pts.shape
+    lf = np.ascontiguousarray(np.broadcast_to(np.asarray(leaf, np.float64).reshape(-1), (3,)), np.float64)
+    offs = np.arange(nf, dtype=np.int32)
+    out = np.zeros((max(n, 1), max(nf, 1)), np.float32)
+    m = C.c_int(0)
+    rc = lib.gorio_prep_approx_voxel_downsample(int(device), _ptr(pts) if n else None, n, 4 * nf, _ptr(offs), nf, _ptr(lf), _ptr(out), 4 * nf, n, C.byref(m))
     if rc < 0:
         msg = lib.gorio_prep_last_error()
         raise GorioError(rc, msg.decode() if msg else "")

@@ -515,6 +515,19 @@ typedef struct {
 int gorio_apd_set_target_submap(gorio_apd_t* h, const gorio_apd_keyframe* frames, int count, double voxel_leaf, int* n_target);
 int gorio_apd_get_target_points(gorio_apd_t* h, float* xyz_out, float* label_out, int n, int point_stride_bytes);
 
+/*
+ * downsample_method of the nodelets (SMO:140-154): which filter the voxel_leaf > 0 branch of gorio_apd_set_target_submap and
+ * gorio_apd_set_target_submap_keyframes runs.  VOXELGRID is the default and today's behaviour, bit for bit.  APPROX_VOXELGRID runs
+ * pcl::ApproximateVoxelGrid (definition: include/gorio_prep.h, gorio_prep_approx_voxel_downsample) with the cubic leaf (float)voxel_leaf
+ * over the assembled (x, y, z, label) points, all four fields averaged alike: the label is the plain float mean, not VoxelGrid's
+ * normalised sign, and the output is in the filter's flush order.  A cloud the filter refuses (a cell coordinate outside
+ * (-2^30, 2^30)) gives GORIO_ERR_INVALID and leaves the previous target in place.  voxel_leaf <= 0 is the same in both modes.
+ * The method stays until it is set again.  A value other than the two is GORIO_ERR_INVALID.
+ */
+typedef enum { GORIO_DOWNSAMPLE_VOXELGRID = 0, GORIO_DOWNSAMPLE_APPROX_VOXELGRID = 1 } gorio_downsample_method;
+int gorio_apd_set_submap_downsample(gorio_apd_t* h, int method);
+int gorio_apd_get_submap_downsample(const gorio_apd_t* h, int* method);
+
 /* clearSource APD:101-105, clearTarget APD:107-112, swapSourceAndTarget APD:89-98 */
 int gorio_apd_clear_source(gorio_apd_t* h);
 int gorio_apd_clear_target(gorio_apd_t* h);

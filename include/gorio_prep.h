@@ -58,6 +58,38 @@ int gorio_prep_statistical_outlier_mask(int device, const float* xyz, int n, int
 int gorio_prep_voxel_downsample(int device, const float* xyz, int n, int point_stride_bytes, double leaf, float* xyz_out, int out_stride_bytes, int out_capacity, int* n_out);
 
 /*
+ * pcl::ApproximateVoxelGrid: downsample_method APPROX_VOXELGRID of both nodelets (preprocessing_nodelet_ntu.cpp:140-145,
+ * scan_matching_odometry_nodelet.cpp:150-154) and the downsample() of fast_apdgicp's pygicp (src/python/main.cpp:46-62).
+ * PCL is not in the image: the definition is RECALLED from PCL 1.10 filters/impl/approximate_voxel_grid.hpp -- parity as recalled,
+ * unpinned -- and it is what tests/approx_voxel_restatement.py restates.
+ *   A point is a row of F float fields, 3 <= F <= 8, the first three x, y, z.  With downsample_all_data_ (PCL's default) all fields are
+ *   averaged alike; F = 3 is downsample_all_data_ = false.
+ *   inv[a] = 1.0f / (float)leaf[a] (float division; one leaf per axis);  cell c[a] = (int)floorf(p[a] * inv[a]) (float product);
+ *   bucket h = (uint32)(c0 * 7171 + c1 * 3079 + c2 * 4231) & 511 (the sum wraps in 32 bits, as the reference's signed overflow does in
+ *   practice; histsize_ = 512).
+ *   History: 512 entries (count, cell, float sum[F]), all empty at the start.  For each point in input order: if its bucket holds a
+ *   DIFFERENT cell, that entry is flushed -- sum[f] / (float)count is appended to the output -- and emptied; then the point is added:
+ *   count++, sum[f] = sum[f] + p[f] in float.  After the last point every non-empty entry is flushed in ascending bucket order.
+ * Deviation: the reference has no finite test (it converts NaN to int).  Here a cloud that holds a point with a non-finite coordinate,
+ * or a cell coordinate outside (-2^30, 2^30), is refused with GORIO_ERR_INVALID and nothing is written (*n_out = 0).  Non-finite values
+ * in the other fields are averaged as given.  The device runs the parallel form of DESIGN.md section 4: the same bits in the same order.
+ *
+ * pts: first x of the cloud; stride_bytes between points (a multiple of 4); field_offsets[n_fields]: float offsets of the averaged
+ * fields inside a point, the first three being x, y, z (pcl::PointXYZINormal with all data: 0,1,2,4,5,6,8,9).  out has the same layout
+ * with out_stride_bytes; fields not listed are not written.  *n_out is the number of output points even when out_capacity is too small
+ * (then nothing is written and the call returns GORIO_ERR_INVALID, like gorio_prep_voxel_downsample).  out may be NULL with
+ * out_capacity 0.  Argument errors (n < 0 or above 2^28, a leaf <= 0 or not finite as a float, n_fields outside 3..8, a stride that is
+ * no multiple of 4 or does not hold the offsets, NULL pointers with n > 0) are GORIO_ERR_INVALID before any device call; n == 0 is
+ * GORIO_OK with *n_out = 0.
+ */
+int gorio_prep_approx_voxel_downsample(int device, const float* pts, int n, int stride_bytes, const int* field_offsets, int n_fields,
+                                       const double leaf[3], float* out, int out_stride_bytes, int out_capacity, int* n_out);
+/* The same on device memory: cols[n_fields][n] in, cols_out[n_fields][capacity] out (host arrays of device pointers), on `stream` (a
+ * hipStream_t or NULL).  The call returns after the 4-byte read-back of n_out; the columns are then written. */
+int gorio_prep_approx_voxel_downsample_device(int device, const float* const* cols, int n_fields, int n, const double leaf[3],
+                                              float* const* cols_out, int capacity, int* n_out, void* stream);
+
+/*
  * REVE Doppler ego-velocity (REVE = src/radar_ego_velocity_estimator.cpp, REVEH = include/radar_ego_velocity_estimator.h):
  * RadarEgoVelocityEstimator::estimate (REVE:60-170) -- per-target gates, zero-velocity test, 3-D least squares with RANSAC
  * (REVE:172-250, 252-303).  The velocities it produces are the `vel` samples of the GP pre-integration windows
