@@ -33,6 +33,7 @@
 
 #include "apd_kernels.hip"
 #include "apd_index.hip"
+#include "apd_voxel_group.hip"
 #include "apd_submap.hip"
 #include "apd_approx_voxel.hip"
 #include "apd_voxel.hip"
@@ -50,6 +51,48 @@ namespace {
 
 constexpr int kPad = 16;
 constexpr float kFar = 1e30f;
+
+// One Gaussian voxel map on the device (VoxMapView<Real> is its kernel-visible view): the occupied voxels in ascending id order, and the
+// box of occupied coordinates that the ids are linear in.  What it is valid FOR (settings, the state of the cloud) is its owner's business.
+template <typename Real>
+struct VoxMap {
+  DevBuf<unsigned long long> vkey;  // these four hold `cap` voxels
+  DevBuf<Real> mean, cov6;
+  DevBuf<int> num;
+  int cap = 0, nv = 0;
+  int min[3] = {0, 0, 0}, dim[3] = {0, 0, 0};
+  Real res = 0;
+  hipError_t reserve(int n_voxels) {
+    const size_t c = n_voxels + n_voxels / 8 + 64;
+    return reserve_group(cap, n_voxels, c, vkey, c, mean, 3 * c, cov6, 6 * c, num, c);
+  }
+  void set_geometry(const CellBox<Real>& g, int n_voxels) {
+    nv = n_voxels;
+    for (int a = 0; a < 3; ++a) {
+      min[a] = g.min_c[a];
+      dim[a] = g.dim[a];
+    }
+    res = g.res;
+  }
+  VoxMapView<Real> view() const { return VoxMapView<Real>{vkey, mean, cov6, num, nv, {min[0], min[1], min[2]}, {dim[0], dim[1], dim[2]}, res}; }
+  // host: (cx, cy, cz) of the nv linear ids `ids` (a download of vkey) -> coords [nv][3]
+  void decode_coords(const unsigned long long* ids, int* coords) const {
+    const unsigned long long d1 = (unsigned long long)dim[1], d2 = (unsigned long long)dim[2];
+    for (int v = 0; v < nv; ++v) {
+      const unsigned long long id = ids[v];
+      coords[3 * (size_t)v + 2] = (int)(id % d2) + min[2];
+      coords[3 * (size_t)v + 1] = (int)((id / d2) % d1) + min[1];
+      coords[3 * (size_t)v] = (int)(id / (d2 * d1)) + min[0];
+    }
+  }
+};
+
+// scratch of a cell grouping (voxel_cell_starts): the three maps of a cloud are built one after the other on one stream and share it
+struct VoxScratch {
+  DevBuf<unsigned long long> keys;  // linear voxel id << 31 | point index, sorted
+  DevBuf<int> counts;               // voxel starts per 256 keys, scanned; [blocks] is the voxel count
+  DevBuf<int> bb;                   // [8] bounding box of the occupied coordinates + range flag
+};
 
 struct DevCloud {
   int device = 0;          // first member: ~DevCloud selects it before the buffers below free themselves
@@ -81,30 +124,16 @@ struct DevCloud {
   bool idx_valid = false;
   int idx_chunk = 0;       // kd chunk size the index was built with (gorio_apd_debug_get_index)
   // Gaussian voxel map of this cloud as a FastVGICP target (voxelmap_, fast_vgicp.hpp:85): lives with the cloud, so the handles that share a
-  // target share its map.  Valid for (vm_res, vm_mult) until the points or the covariances change.
-  DevBuf<unsigned long long> vm_keys;  // sort scratch: linear voxel id << 31 | point index
-  DevBuf<int> vm_counts;               // voxel starts per 256 keys, scanned
-  DevBuf<int> vm_bb;                   // [8] bounding box of the occupied coordinates + range flag
-  DevBuf<unsigned long long> vm_vkey;  // the map itself (VoxelMapView): these four hold vm_cap voxels
-  DevBuf<double> vm_mean;
-  DevBuf<double> vm_cov6;
-  DevBuf<int> vm_num;
-  int vm_cap = 0, vm_nv = 0;
-  int vm_min[3] = {0, 0, 0}, vm_dim[3] = {0, 0, 0};
-  double vm_res = 0.0;
+  // target share its map.  Valid for (vm.res, vm_mult) until the points or the covariances change.
+  VoxScratch vox_scratch;
+  VoxMap<double> vm;
   bool vm_mult = false;                   // MultiplicativeGaussianVoxel (ADDITIVE and ADDITIVE_WEIGHTED build the same voxels, VOX:138-141)
   bool vm_valid = false;
   // float Gaussian voxel map of this cloud for fast_gicp::NDTCuda (apd_ndt_cuda.hip; source_voxelmap / target_voxelmap, ndt_cuda.cu:120-140):
-  // lives with the cloud, so a swap moves it and the sharers of a target share it.  Built from the points alone; vm_keys / vm_counts / vm_bb
-  // above are its sort scratch too.  Valid for nc_res until the points change.
-  DevBuf<unsigned long long> nc_vkey;  // these five hold nc_cap voxels
-  DevBuf<float> nc_mean, nc_raw, nc_cov6;
-  DevBuf<int> nc_num;
-  int nc_cap = 0, nc_nv = 0;
-  int nc_min[3] = {0, 0, 0}, nc_dim[3] = {0, 0, 0};
-  float nc_res = 0.0f;
+  // lives with the cloud, so a swap moves it and the sharers of a target share it.  Built from the points alone; valid for nc.res until the points change.
+  VoxMap<float> nc;                    // cov6: the regularised covariance
+  DevBuf<float> nc_raw;                // [nc.cap][9] the covariance before the regularisation (GV:188), row-major
   bool nc_valid = false;
-  NdtcMapView ndtc_view() const { return NdtcMapView{nc_vkey, nc_mean, nc_cov6, nc_num, nc_nv, {nc_min[0], nc_min[1], nc_min[2]}, {nc_dim[0], nc_dim[1], nc_dim[2]}, nc_res}; }
   // fast_gicp::FastVGICPCuda (apd_vgicp_cuda.hip): three stages, each valid for the settings recorded beside it until the points change.
   //   raw   float covariances of ALL points (source_covariances / target_covariances, VC:183-219) from the k-NN lists (vc_knn) or the RBF pass
   //   kept  the points the regularisation keeps, in input order, with their regularised covariances (CR:91-117)
@@ -122,13 +151,7 @@ struct DevCloud {
   bool vc_raw_valid = false, vc_kept_valid = false, vc_map_valid = false;
   int vc_rbf = 0, vc_k = 0, vc_reg = -1;  // what raw / kept were made with: RBF or lists, k (lists), kernel_width and max_dist (RBF), regularization
   double vc_width = 0.0, vc_maxd = 0.0;
-  DevBuf<unsigned long long> vc_vkey;  // the map: these four hold vc_mcap voxels
-  DevBuf<float> vc_mean, vc_mcov6;
-  DevBuf<int> vc_num;
-  int vc_mcap = 0, vc_nv = 0;
-  int vc_min[3] = {0, 0, 0}, vc_dim[3] = {0, 0, 0};
-  float vc_res = 0.0f;
-  NdtcMapView vgc_view() const { return NdtcMapView{vc_vkey, vc_mean, vc_mcov6, vc_num, vc_nv, {vc_min[0], vc_min[1], vc_min[2]}, {vc_dim[0], vc_dim[1], vc_dim[2]}, vc_res}; }
+  VoxMap<float> vc_map;                // the map
   // fast_gicp::FastGICPMultiPoints (apd_gicp_mp.hip): every point with its float covariance as a record of three float4, made from the k-NN
   // lists mp_knn (mp_scratch: what the k-NN kernels write on their way to the lists).  Valid for (mp_k, mp_reg) until the points change;
   // lives with the cloud, so a swap moves it and the sharers of a cloud share it.
@@ -158,7 +181,6 @@ struct DevCloud {
   void index_built(int chunk) { idx_valid = true; idx_chunk = chunk; }
   void voxelmap_dropped() { vm_valid = false; }
   void voxelmap_built() { vm_valid = true; }
-  VoxelMapView voxel_view() const { return VoxelMapView{vm_vkey, vm_mean, vm_cov6, vm_num, vm_nv, {vm_min[0], vm_min[1], vm_min[2]}, {vm_dim[0], vm_dim[1], vm_dim[2]}, vm_res}; }
   // the kernel-visible view of the search index (the buffers above own the memory)
   SearchIndex index_view() const { return SearchIndex{idx_sx, idx_sy, idx_sz, idx_orig, idx_s4, idx_tbox, idx_sbox, idx_bbox, idx_n, idx_spad, idx_spad / 32, idx_spad / 512}; }
   CloudView view() const { return CloudView{x, y, z, label, p4, cov6, geo_w, n, n_pad, index_view()}; }
@@ -870,24 +892,21 @@ int voxel_offsets(int search) { return search == GORIO_VOXEL_DIRECT1 ? 1 : searc
 bool shared_voxel_mismatch(const gorio_apd* h) {
   const DevCloud& t = *h->tgt;
   return h->method == GORIO_METHOD_VGICP && h->tgt.use_count() > 1 && t.vm_valid &&
-         (t.vm_res != h->voxel_resolution || t.vm_mult != (h->voxel_mode == GORIO_VOXEL_MULTIPLICATIVE));
+         (t.vm.res != h->voxel_resolution || t.vm_mult != (h->voxel_mode == GORIO_VOXEL_MULTIPLICATIVE));
 }
 
-// create_voxelmap (VOX:129-156) of target cloud t, whose covariances are valid: coordinates + bounding box, keys, sort, voxel starts, one
-// accumulation pass.  Two small read-backs (the box, the voxel count); nothing to do when the map held matches.
-int build_voxelmap(gorio_apd* h, DevCloud& t, double res, int mode) {
-  const bool mult = mode == GORIO_VOXEL_MULTIPLICATIVE;
-  if (t.vm_valid && t.vm_res == res && t.vm_mult == mult) return GORIO_OK;
-  t.voxelmap_dropped();
-  const int n = t.n;
-  HIP_TRY(h, t.vm_bb.reserve(8));
-  vg_bbox_init_kernel<<<1, 64, 0, h->stream>>>(t.vm_bb);
-  vg_coord_bbox_kernel<<<std::min(256, (n + 255) / 256), 256, 0, h->stream>>>(t.p4, n, res, t.vm_bb);
+// The first half of every map build with the floor(x / res - 0.5) rule (apd_voxel_group.hip), in double or in float: the voxel starts of
+// the `n` points `pts` in scratch s (sorted keys, scanned block counts), the box g of the occupied coordinates and the voxel count nv.
+// Two small read-backs (the box, the count).  what / whose: the caller's words in the error texts.
+template <typename Real>
+int voxel_cell_starts(gorio_apd* h, VoxScratch& s, const float4* pts, int n, Real res, const std::string& what, const char* whose, CellBox<Real>& g, int& nv) {
+  HIP_TRY(h, s.bb.reserve(8));
+  cell_bbox_init_kernel<<<1, 64, 0, h->stream>>>(s.bb);
+  cell_coord_bbox_kernel<Real><<<std::min(256, (n + 255) / 256), 256, 0, h->stream>>>(pts, n, res, s.bb);
   int bb[8];
-  HIP_TRY(h, hipMemcpyAsync(bb, t.vm_bb, sizeof(int) * 7, hipMemcpyDeviceToHost, h->stream));
+  HIP_TRY(h, hipMemcpyAsync(bb, s.bb, sizeof(int) * 7, hipMemcpyDeviceToHost, h->stream));
   HIP_TRY(h, hipStreamSynchronize(h->stream));
-  if (bb[6]) return fail(h, GORIO_ERR_UNSUPPORTED, "voxel map: a target coordinate is not finite or its voxel coordinate does not fit 31 bits");
-  VoxBox g;
+  if (bb[6]) return fail(h, GORIO_ERR_UNSUPPORTED, what + ": " + whose + " is not finite or its voxel coordinate does not fit 31 bits");
   double cells = 1.0;
   for (int a = 0; a < 3; ++a) {
     g.min_c[a] = bb[a];
@@ -896,31 +915,37 @@ int build_voxelmap(gorio_apd* h, DevCloud& t, double res, int mode) {
     cells *= (double)d;
   }
   g.res = res;
-  if (cells >= 8589934592.0) return fail(h, GORIO_ERR_UNSUPPORTED, "voxel map: the bounding box of the occupied voxels has 2^33 cells or more (the voxel id is packed into 33 bits of the sort key)");
+  if (cells >= 8589934592.0) return fail(h, GORIO_ERR_UNSUPPORTED, what + ": the bounding box of the occupied voxels has 2^33 cells or more (the voxel id is packed into 33 bits of the sort key)");
   const int npow2 = sort_padded_size(n);
   const int nblocks = (n + 255) / 256;
-  HIP_TRY(h, t.vm_keys.reserve(npow2));
-  HIP_TRY(h, t.vm_counts.reserve(nblocks + 1));
-  vg_key_kernel<<<(npow2 + 255) / 256, 256, 0, h->stream>>>(t.p4, n, npow2, g, t.vm_keys);
-  enqueue_tiled_sort(h->stream, SortKeys{t.vm_keys, npow2}, 1, npow2);
-  vox_count_kernel<<<nblocks, 256, 0, h->stream>>>(t.vm_keys, n, t.vm_counts);
-  vox_scan_kernel<<<1, 1024, 0, h->stream>>>(t.vm_counts, nblocks);
-  int nv = 0;
-  HIP_TRY(h, hipMemcpyAsync(&nv, t.vm_counts + nblocks, sizeof(int), hipMemcpyDeviceToHost, h->stream));
+  HIP_TRY(h, s.keys.reserve(npow2));
+  HIP_TRY(h, s.counts.reserve(nblocks + 1));
+  cell_key_kernel<Real><<<(npow2 + 255) / 256, 256, 0, h->stream>>>(pts, n, npow2, g, s.keys);
+  enqueue_tiled_sort(h->stream, SortKeys{s.keys, npow2}, 1, npow2);
+  cell_count_kernel<31><<<nblocks, 256, 0, h->stream>>>(s.keys, n, s.counts);
+  block_scan_kernel<<<1, 1024, 0, h->stream>>>(s.counts, nblocks);
+  nv = 0;
+  HIP_TRY(h, hipMemcpyAsync(&nv, s.counts + nblocks, sizeof(int), hipMemcpyDeviceToHost, h->stream));
   HIP_TRY(h, hipStreamSynchronize(h->stream));
-  if (nv <= 0 || nv > n) return fail(h, GORIO_ERR_NO_DEVICE, "voxel map: inconsistent voxel count");
-  {
-    const size_t cap = nv + nv / 8 + 64;
-    HIP_TRY(h, reserve_group(t.vm_cap, nv, cap, t.vm_vkey, cap, t.vm_mean, 3 * cap, t.vm_cov6, 6 * cap, t.vm_num, cap));
-  }
-  vg_accum_kernel<<<nblocks, 256, 0, h->stream>>>(t.vm_keys, t.p4, t.cov6, n, t.vm_counts, mult ? 2 : 0, t.vm_vkey, t.vm_mean, t.vm_cov6, t.vm_num);
+  if (nv <= 0 || nv > n) return fail(h, GORIO_ERR_NO_DEVICE, what + ": inconsistent voxel count");
+  return GORIO_OK;
+}
+
+// create_voxelmap (VOX:129-156) of target cloud t, whose covariances are valid: the voxel starts, one accumulation pass; nothing to do when
+// the map held matches.
+int build_voxelmap(gorio_apd* h, DevCloud& t, double res, int mode) {
+  const bool mult = mode == GORIO_VOXEL_MULTIPLICATIVE;
+  if (t.vm_valid && t.vm.res == res && t.vm_mult == mult) return GORIO_OK;
+  t.voxelmap_dropped();
+  const int n = t.n;
+  VoxScratch& s = t.vox_scratch;
+  VoxBox g;
+  int nv = 0;
+  if (int rc = voxel_cell_starts(h, s, t.p4, n, res, "voxel map", "a target coordinate", g, nv)) return rc;
+  HIP_TRY(h, t.vm.reserve(nv));
+  vg_accum_kernel<<<(n + 255) / 256, 256, 0, h->stream>>>(s.keys, t.p4, t.cov6, n, s.counts, mult ? 2 : 0, t.vm.vkey, t.vm.mean, t.vm.cov6, t.vm.num);
   HIP_TRY(h, hipGetLastError());
-  t.vm_nv = nv;
-  for (int a = 0; a < 3; ++a) {
-    t.vm_min[a] = g.min_c[a];
-    t.vm_dim[a] = g.dim[a];
-  }
-  t.vm_res = res;
+  t.vm.set_geometry(g, nv);
   t.vm_mult = mult;
   t.voxelmap_built();
   return GORIO_OK;
@@ -938,7 +963,7 @@ int ensure_voxel_pair(gorio_apd* h) {
 
 VoxPair make_vox_pair(const gorio_apd* h, int write_omega) {
   VoxPair v;
-  v.map = h->tgt->voxel_view();
+  v.map = h->tgt->vm.view();
   v.slots = h->v_slots;
   v.omega6 = h->v_omega6;
   v.n_off = h->v_n_off;
@@ -991,7 +1016,7 @@ bool ndtc_same_settings(const gorio_apd* a, const gorio_apd* b) {
 
 // a cloud shared with other handles carries ONE map: a sharer with another resolution would rebuild it under the others
 bool ndtc_shared_mismatch(const gorio_apd* h, const std::shared_ptr<DevCloud>& c) {
-  return c.use_count() > 1 && c->nc_valid && c->nc_res != (float)h->voxel_resolution;
+  return c.use_count() > 1 && c->nc_valid && c->nc.res != (float)h->voxel_resolution;
 }
 
 int ndtc_ready(gorio_apd* h) {
@@ -1004,64 +1029,22 @@ int ndtc_ready(gorio_apd* h) {
   return GORIO_OK;
 }
 
-// the first half of a float map build: the voxel starts of `n` points `pts` of cloud c (whose vm_keys / vm_counts / vm_bb are the
-// scratch), the box g and the voxel count nv.  Two small read-backs.
-int ndtc_voxel_starts(gorio_apd* h, DevCloud& c, const float4* pts, int n, float res, NdtcBox& g, int& nv) {
-  HIP_TRY(h, c.vm_bb.reserve(8));
-  vg_bbox_init_kernel<<<1, 64, 0, h->stream>>>(c.vm_bb);
-  ndtc_coord_bbox_kernel<<<std::min(256, (n + 255) / 256), 256, 0, h->stream>>>(pts, n, res, c.vm_bb);
-  int bb[8];
-  HIP_TRY(h, hipMemcpyAsync(bb, c.vm_bb, sizeof(int) * 7, hipMemcpyDeviceToHost, h->stream));
-  HIP_TRY(h, hipStreamSynchronize(h->stream));
-  if (bb[6]) return fail(h, GORIO_ERR_UNSUPPORTED, "NDTCuda voxel map: a coordinate is not finite or its voxel coordinate does not fit 31 bits");
-  double cells = 1.0;
-  for (int a = 0; a < 3; ++a) {
-    g.min_c[a] = bb[a];
-    const long long d = (long long)bb[3 + a] - (long long)bb[a] + 1;
-    g.dim[a] = (int)d;
-    cells *= (double)d;
-  }
-  g.res = res;
-  if (cells >= 8589934592.0) return fail(h, GORIO_ERR_UNSUPPORTED, "NDTCuda voxel map: the bounding box of the occupied voxels has 2^33 cells or more (the voxel id is packed into 33 bits of the sort key)");
-  const int npow2 = sort_padded_size(n);
-  const int nblocks = (n + 255) / 256;
-  HIP_TRY(h, c.vm_keys.reserve(npow2));
-  HIP_TRY(h, c.vm_counts.reserve(nblocks + 1));
-  ndtc_key_kernel<<<(npow2 + 255) / 256, 256, 0, h->stream>>>(pts, n, npow2, g, c.vm_keys);
-  enqueue_tiled_sort(h->stream, SortKeys{c.vm_keys, npow2}, 1, npow2);
-  vox_count_kernel<<<nblocks, 256, 0, h->stream>>>(c.vm_keys, n, c.vm_counts);
-  vox_scan_kernel<<<1, 1024, 0, h->stream>>>(c.vm_counts, nblocks);
-  nv = 0;
-  HIP_TRY(h, hipMemcpyAsync(&nv, c.vm_counts + nblocks, sizeof(int), hipMemcpyDeviceToHost, h->stream));
-  HIP_TRY(h, hipStreamSynchronize(h->stream));
-  if (nv <= 0 || nv > n) return fail(h, GORIO_ERR_NO_DEVICE, "NDTCuda voxel map: inconsistent voxel count");
-  return GORIO_OK;
-}
-
-// create_voxelmap + covariance_regularization (ndt_cuda.cu:120-140) of cloud c: coordinates + bounding box, keys, sort, voxel starts, one
-// accumulation pass.  Two small read-backs (the box, the voxel count); nothing to do when the map held matches.  Deviation from the
-// reference: a changed resolution rebuilds the map (ndt_cuda.cu:122, 133 keep the old one).
+// create_voxelmap + covariance_regularization (ndt_cuda.cu:120-140) of cloud c: the voxel starts, one accumulation pass; nothing to do
+// when the map held matches.  Deviation from the reference: a changed resolution rebuilds the map (ndt_cuda.cu:122, 133 keep the old one).
 int build_ndtc_map(gorio_apd* h, DevCloud& c, double resolution) {
   const float res = (float)resolution;
-  if (c.nc_valid && c.nc_res == res) return GORIO_OK;
+  if (c.nc_valid && c.nc.res == res) return GORIO_OK;
   c.ndtc_map_dropped();
   const int n = c.n;
-  const int nblocks = (n + 255) / 256;
+  VoxScratch& s = c.vox_scratch;
   NdtcBox g;
   int nv = 0;
-  if (int rc = ndtc_voxel_starts(h, c, c.p4, n, res, g, nv)) return rc;
-  {
-    const size_t cap = nv + nv / 8 + 64;
-    HIP_TRY(h, reserve_group(c.nc_cap, nv, cap, c.nc_vkey, cap, c.nc_mean, 3 * cap, c.nc_raw, 9 * cap, c.nc_cov6, 6 * cap, c.nc_num, cap));
-  }
-  ndtc_accum_kernel<<<nblocks, 256, 0, h->stream>>>(c.vm_keys, c.p4, n, c.vm_counts, c.nc_vkey, c.nc_mean, c.nc_raw, c.nc_cov6, c.nc_num);
+  if (int rc = voxel_cell_starts(h, s, c.p4, n, res, "NDTCuda voxel map", "a coordinate", g, nv)) return rc;
+  HIP_TRY(h, c.nc.reserve(nv));
+  HIP_TRY(h, c.nc_raw.reserve(9 * (size_t)nv, 9 * (size_t)c.nc.cap));
+  ndtc_accum_kernel<<<(n + 255) / 256, 256, 0, h->stream>>>(s.keys, c.p4, n, s.counts, c.nc.vkey, c.nc.mean, c.nc_raw, c.nc.cov6, c.nc.num);
   HIP_TRY(h, hipGetLastError());
-  c.nc_nv = nv;
-  for (int a = 0; a < 3; ++a) {
-    c.nc_min[a] = g.min_c[a];
-    c.nc_dim[a] = g.dim[a];
-  }
-  c.nc_res = res;
+  c.nc.set_geometry(g, nv);
   c.ndtc_map_built();
   return GORIO_OK;
 }
@@ -1077,7 +1060,7 @@ int ensure_ndtc_pair(gorio_apd* h) {
     rc = build_ndtc_map(h, *h->src, h->voxel_resolution);
     if (rc) return rc;
   }
-  return ensure_ndtc_slots(h, d2d ? h->src->nc_nv : h->src->n, d2d ? 1 : 0);
+  return ensure_ndtc_slots(h, d2d ? h->src->nc.nv : h->src->n, d2d ? 1 : 0);
 }
 
 // the offset table on the device, and the slot table and block partials of `items` items (mode: NdtcPair::d2d)
@@ -1106,7 +1089,7 @@ int ensure_ndtc_slots(gorio_apd* h, int items, int mode) {
 NdtcPair make_ndtc_pair(const gorio_apd* h) {
   NdtcPair p;
   if (h->ndtc_slot_d2d == 2) {  // FastVGICPCuda: the kept source points and their covariances against the map of the kept target points
-    p.map = h->tgt->vgc_view();
+    p.map = h->tgt->vc_map.view();
     p.item = reinterpret_cast<const float*>(h->src->vc_p4.get());
     p.item_cov6 = h->src->vc_cov6;
     p.offsets = h->ndtc_off;
@@ -1118,10 +1101,10 @@ NdtcPair make_ndtc_pair(const gorio_apd* h) {
     p.d2d = 2;
     return p;
   }
-  p.map = h->tgt->ndtc_view();
+  p.map = h->tgt->nc.view();
   const bool d2d = h->ndtc_slot_d2d != 0;
-  p.item = d2d ? h->src->nc_mean.get() : reinterpret_cast<const float*>(h->src->p4.get());
-  p.item_cov6 = d2d ? h->src->nc_cov6.get() : nullptr;
+  p.item = d2d ? h->src->nc.mean.get() : reinterpret_cast<const float*>(h->src->p4.get());
+  p.item_cov6 = d2d ? h->src->nc.cov6.get() : nullptr;
   p.offsets = h->ndtc_off;
   p.slots = h->ndtc_slots;
   p.tlin = h->ndtc_tlin;
@@ -1158,7 +1141,7 @@ bool vgc_raw_matches(const gorio_apd* h, const DevCloud& c) {
   return !c.vc_rbf && c.vc_k == h->params.k_correspondences;  // CPU_PARALLEL_KDTREE and GPU_BRUTEFORCE are one path
 }
 bool vgc_kept_matches(const gorio_apd* h, const DevCloud& c) { return vgc_raw_matches(h, c) && c.vc_kept_valid && c.vc_reg == h->params.regularization; }
-bool vgc_map_matches(const gorio_apd* h, const DevCloud& c) { return vgc_kept_matches(h, c) && c.vc_map_valid && c.vc_res == (float)h->voxel_resolution; }
+bool vgc_map_matches(const gorio_apd* h, const DevCloud& c) { return vgc_kept_matches(h, c) && c.vc_map_valid && c.vc_map.res == (float)h->voxel_resolution; }
 
 // a cloud other handles hold too carries ONE set of covariances, kept points and map: a sharer that would make any stage HELD
 // differently would rebuild it under the others
@@ -1167,7 +1150,7 @@ bool vgc_shared_mismatch(const gorio_apd* h, const std::shared_ptr<DevCloud>& cp
   if (cp.use_count() <= 1) return false;
   if (c.vc_raw_valid && !vgc_raw_matches(h, c)) return true;
   if (c.vc_kept_valid && c.vc_reg != h->params.regularization) return true;
-  return with_map && c.vc_map_valid && c.vc_res != (float)h->voxel_resolution;
+  return with_map && c.vc_map_valid && c.vc_map.res != (float)h->voxel_resolution;
 }
 
 int vgc_cloud_ready(gorio_apd* h, const DevCloud& c, const char* side) {
@@ -1241,7 +1224,7 @@ int vgc_filter(gorio_apd* h, DevCloud& c) {
   HIP_TRY(h, c.vc_bcnt.reserve(nblk + 1));
   vgc_regularize_kernel<<<nblk, 256, 0, h->stream>>>(c.vc_raw6, n, h->params.regularization, c.vc_keep, c.vc_reg6);
   compact_count_kernel<<<nblk, 256, 0, h->stream>>>(c.vc_keep, n, c.vc_bcnt);
-  compact_scan_kernel<<<1, 1024, 0, h->stream>>>(c.vc_bcnt, nblk);
+  block_scan_kernel<<<1, 1024, 0, h->stream>>>(c.vc_bcnt, nblk);
   vgc_scatter_kernel<<<nblk, 256, 0, h->stream>>>(c.p4, c.vc_reg6, c.vc_keep, n, c.vc_bcnt, c.vc_p4, c.vc_cov6, c.vc_index);
   HIP_TRY(h, hipGetLastError());
   int nkept = 0;
@@ -1260,21 +1243,16 @@ int build_vgc_map(gorio_apd* h, DevCloud& c) {
   c.vgc_map_dropped();
   const float res = (float)h->voxel_resolution;
   const int n = c.vc_nkept;
+  VoxScratch& s = c.vox_scratch;
   NdtcBox g = {{0, 0, 0}, {0, 0, 0}, res};
   int nv = 0;
   if (n > 0) {
-    if (int rc = ndtc_voxel_starts(h, c, c.vc_p4, n, res, g, nv)) return rc;
-    const size_t cap = nv + nv / 8 + 64;
-    HIP_TRY(h, reserve_group(c.vc_mcap, nv, cap, c.vc_vkey, cap, c.vc_mean, 3 * cap, c.vc_mcov6, 6 * cap, c.vc_num, cap));
-    vgc_accum_kernel<<<(n + 255) / 256, 256, 0, h->stream>>>(c.vm_keys, c.vc_p4, c.vc_cov6, n, c.vm_counts, c.vc_vkey, c.vc_mean, c.vc_mcov6, c.vc_num);
+    if (int rc = voxel_cell_starts(h, s, c.vc_p4, n, res, "NDTCuda voxel map", "a coordinate", g, nv)) return rc;
+    HIP_TRY(h, c.vc_map.reserve(nv));
+    vgc_accum_kernel<<<(n + 255) / 256, 256, 0, h->stream>>>(s.keys, c.vc_p4, c.vc_cov6, n, s.counts, c.vc_map.vkey, c.vc_map.mean, c.vc_map.cov6, c.vc_map.num);
     HIP_TRY(h, hipGetLastError());
   }
-  c.vc_nv = nv;
-  for (int a = 0; a < 3; ++a) {
-    c.vc_min[a] = g.min_c[a];
-    c.vc_dim[a] = g.dim[a];
-  }
-  c.vc_res = res;
+  c.vc_map.set_geometry(g, nv);
   c.vgc_map_built();
   return GORIO_OK;
 }
@@ -1872,26 +1850,20 @@ int gorio_apd_get_voxelmap(gorio_apd_t* h, int* coord3, int* num_points, double*
   }
   rc = build_voxelmap(h, t, h->voxel_resolution, h->voxel_mode);
   if (rc) return rc;
-  const int nv = t.vm_nv;
+  const int nv = t.vm.nv;
   *n_voxels = nv;
   if (capacity < nv || (!coord3 && !num_points && !mean4 && !cov16)) return GORIO_OK;
   std::vector<unsigned long long> vkey(nv);
   std::vector<double> mean((size_t)nv * 3), c6((size_t)nv * 6);
   std::vector<int> num(nv);
-  HIP_TRY(h, hipMemcpyAsync(vkey.data(), t.vm_vkey, sizeof(unsigned long long) * nv, hipMemcpyDeviceToHost, h->stream));
-  HIP_TRY(h, hipMemcpyAsync(mean.data(), t.vm_mean, sizeof(double) * 3 * nv, hipMemcpyDeviceToHost, h->stream));
-  HIP_TRY(h, hipMemcpyAsync(c6.data(), t.vm_cov6, sizeof(double) * 6 * nv, hipMemcpyDeviceToHost, h->stream));
-  HIP_TRY(h, hipMemcpyAsync(num.data(), t.vm_num, sizeof(int) * nv, hipMemcpyDeviceToHost, h->stream));
+  HIP_TRY(h, hipMemcpyAsync(vkey.data(), t.vm.vkey, sizeof(unsigned long long) * nv, hipMemcpyDeviceToHost, h->stream));
+  HIP_TRY(h, hipMemcpyAsync(mean.data(), t.vm.mean, sizeof(double) * 3 * nv, hipMemcpyDeviceToHost, h->stream));
+  HIP_TRY(h, hipMemcpyAsync(c6.data(), t.vm.cov6, sizeof(double) * 6 * nv, hipMemcpyDeviceToHost, h->stream));
+  HIP_TRY(h, hipMemcpyAsync(num.data(), t.vm.num, sizeof(int) * nv, hipMemcpyDeviceToHost, h->stream));
   HIP_TRY(h, hipStreamSynchronize(h->stream));
   const double c33 = t.vm_mult ? 1.0 : 0.0;  // finalize(): the multiplicative voxel inverts a matrix whose (3,3) is 1 (VOX:97-100), the additive one divides a 0
+  if (coord3) t.vm.decode_coords(vkey.data(), coord3);
   for (int v = 0; v < nv; ++v) {
-    if (coord3) {
-      const unsigned long long id = vkey[v];
-      const unsigned long long d1 = (unsigned long long)t.vm_dim[1], d2 = (unsigned long long)t.vm_dim[2];
-      coord3[3 * (size_t)v + 2] = (int)(id % d2) + t.vm_min[2];
-      coord3[3 * (size_t)v + 1] = (int)((id / d2) % d1) + t.vm_min[1];
-      coord3[3 * (size_t)v] = (int)(id / (d2 * d1)) + t.vm_min[0];
-    }
     if (num_points) num_points[v] = num[v];
     if (mean4) {
       double* o = mean4 + 4 * (size_t)v;
@@ -1948,32 +1920,26 @@ int gorio_apd_ndt_cuda_get_voxels(gorio_apd_t* h, int which, int capacity, int* 
   if (!c.present) return fail(h, GORIO_ERR_STATE, "ndt_cuda_get_voxels: that cloud is not set");
   if (ndtc_shared_mismatch(h, cp)) return fail(h, GORIO_ERR_INVALID, "ndt_cuda_get_voxels: the shared cloud's map was built with another resolution");
   if (which == 0 && h->ndtc_mode == GORIO_NDT_CUDA_P2D) {  // P2D builds no source map (NC:122): report the one held, if any
-    if (!c.nc_valid || c.nc_res != (float)h->voxel_resolution) {
+    if (!c.nc_valid || c.nc.res != (float)h->voxel_resolution) {
       *n_voxels = 0;
       return GORIO_OK;
     }
   } else if (int rc = build_ndtc_map(h, c, h->voxel_resolution)) {
     return rc;
   }
-  const int nv = c.nc_nv;
+  const int nv = c.nc.nv;
   *n_voxels = nv;
   if (capacity < nv || (!coords && !num_points && !mean && !cov_raw && !cov)) return GORIO_OK;
   std::vector<unsigned long long> vkey(nv);
   std::vector<float> c6((size_t)nv * 6);
-  HIP_TRY(h, hipMemcpyAsync(vkey.data(), c.nc_vkey, sizeof(unsigned long long) * nv, hipMemcpyDeviceToHost, h->stream));
-  HIP_TRY(h, hipMemcpyAsync(c6.data(), c.nc_cov6, sizeof(float) * 6 * nv, hipMemcpyDeviceToHost, h->stream));
-  if (num_points) HIP_TRY(h, hipMemcpyAsync(num_points, c.nc_num, sizeof(int) * nv, hipMemcpyDeviceToHost, h->stream));
-  if (mean) HIP_TRY(h, hipMemcpyAsync(mean, c.nc_mean, sizeof(float) * 3 * nv, hipMemcpyDeviceToHost, h->stream));
+  HIP_TRY(h, hipMemcpyAsync(vkey.data(), c.nc.vkey, sizeof(unsigned long long) * nv, hipMemcpyDeviceToHost, h->stream));
+  HIP_TRY(h, hipMemcpyAsync(c6.data(), c.nc.cov6, sizeof(float) * 6 * nv, hipMemcpyDeviceToHost, h->stream));
+  if (num_points) HIP_TRY(h, hipMemcpyAsync(num_points, c.nc.num, sizeof(int) * nv, hipMemcpyDeviceToHost, h->stream));
+  if (mean) HIP_TRY(h, hipMemcpyAsync(mean, c.nc.mean, sizeof(float) * 3 * nv, hipMemcpyDeviceToHost, h->stream));
   if (cov_raw) HIP_TRY(h, hipMemcpyAsync(cov_raw, c.nc_raw, sizeof(float) * 9 * nv, hipMemcpyDeviceToHost, h->stream));
   HIP_TRY(h, hipStreamSynchronize(h->stream));
+  if (coords) c.nc.decode_coords(vkey.data(), coords);
   for (int v = 0; v < nv; ++v) {
-    if (coords) {
-      const unsigned long long id = vkey[v];
-      const unsigned long long d1 = (unsigned long long)c.nc_dim[1], d2 = (unsigned long long)c.nc_dim[2];
-      coords[3 * (size_t)v + 2] = (int)(id % d2) + c.nc_min[2];
-      coords[3 * (size_t)v + 1] = (int)((id / d2) % d1) + c.nc_min[1];
-      coords[3 * (size_t)v] = (int)(id / (d2 * d1)) + c.nc_min[0];
-    }
     if (cov) {
       const float* q = c6.data() + 6 * (size_t)v;
       float* o = cov + 9 * (size_t)v;
@@ -2065,24 +2031,16 @@ int gorio_apd_vgicp_cuda_get_voxels(gorio_apd_t* h, int capacity, int* n_voxels,
   if (vgc_shared_mismatch(h, h->tgt, true)) return fail(h, GORIO_ERR_INVALID, "vgicp_cuda_get_voxels: the shared target's covariances / kept points / voxel map were made with other settings");
   if (int rc = vgc_cloud_ready(h, c, "target")) return rc;
   if (int rc = build_vgc_map(h, c)) return rc;
-  const int nv = c.vc_nv;
+  const int nv = c.vc_map.nv;
   *n_voxels = nv;
   if (capacity < nv || nv == 0 || (!coords && !num_points && !mean && !cov)) return GORIO_OK;
   std::vector<unsigned long long> vkey(nv);
-  HIP_TRY(h, hipMemcpyAsync(vkey.data(), c.vc_vkey, sizeof(unsigned long long) * nv, hipMemcpyDeviceToHost, h->stream));
-  if (num_points) HIP_TRY(h, hipMemcpyAsync(num_points, c.vc_num, sizeof(int) * nv, hipMemcpyDeviceToHost, h->stream));
-  if (mean) HIP_TRY(h, hipMemcpyAsync(mean, c.vc_mean, sizeof(float) * 3 * nv, hipMemcpyDeviceToHost, h->stream));
-  if (cov) HIP_TRY(h, hipMemcpyAsync(cov, c.vc_mcov6, sizeof(float) * 6 * nv, hipMemcpyDeviceToHost, h->stream));
+  HIP_TRY(h, hipMemcpyAsync(vkey.data(), c.vc_map.vkey, sizeof(unsigned long long) * nv, hipMemcpyDeviceToHost, h->stream));
+  if (num_points) HIP_TRY(h, hipMemcpyAsync(num_points, c.vc_map.num, sizeof(int) * nv, hipMemcpyDeviceToHost, h->stream));
+  if (mean) HIP_TRY(h, hipMemcpyAsync(mean, c.vc_map.mean, sizeof(float) * 3 * nv, hipMemcpyDeviceToHost, h->stream));
+  if (cov) HIP_TRY(h, hipMemcpyAsync(cov, c.vc_map.cov6, sizeof(float) * 6 * nv, hipMemcpyDeviceToHost, h->stream));
   HIP_TRY(h, hipStreamSynchronize(h->stream));
-  if (coords) {
-    const unsigned long long d1 = (unsigned long long)c.vc_dim[1], d2 = (unsigned long long)c.vc_dim[2];
-    for (int v = 0; v < nv; ++v) {
-      const unsigned long long id = vkey[v];
-      coords[3 * (size_t)v + 2] = (int)(id % d2) + c.vc_min[2];
-      coords[3 * (size_t)v + 1] = (int)((id / d2) % d1) + c.vc_min[1];
-      coords[3 * (size_t)v] = (int)(id / (d2 * d1)) + c.vc_min[0];
-    }
-  }
+  if (coords) c.vc_map.decode_coords(vkey.data(), coords);
   return GORIO_OK;
 }
 
@@ -2178,14 +2136,14 @@ int gorio_apd_set_target_shared(gorio_apd_t* h, gorio_apd_t* owner) {
   }
   {
     const DevCloud& t = *owner->tgt;
-    if (h->method == GORIO_METHOD_VGICP && t.vm_valid && (t.vm_res != h->voxel_resolution || t.vm_mult != (h->voxel_mode == GORIO_VOXEL_MULTIPLICATIVE)))
+    if (h->method == GORIO_METHOD_VGICP && t.vm_valid && (t.vm.res != h->voxel_resolution || t.vm_mult != (h->voxel_mode == GORIO_VOXEL_MULTIPLICATIVE)))
       return fail(h, GORIO_ERR_INVALID, "set_target_shared: the owner's voxel map was built with another voxel_resolution / voxel_mode than this handle's");
   }
-  if (is_ndtc(h) && owner->tgt->nc_valid && owner->tgt->nc_res != (float)h->voxel_resolution)
+  if (is_ndtc(h) && owner->tgt->nc_valid && owner->tgt->nc.res != (float)h->voxel_resolution)
     return fail(h, GORIO_ERR_INVALID, "set_target_shared: the owner's NDTCuda voxel map was built with another resolution than this handle's");
   if (is_vgc(h)) {
     const DevCloud& t = *owner->tgt;
-    if ((t.vc_raw_valid && !vgc_raw_matches(h, t)) || (t.vc_kept_valid && t.vc_reg != h->params.regularization) || (t.vc_map_valid && t.vc_res != (float)h->voxel_resolution))
+    if ((t.vc_raw_valid && !vgc_raw_matches(h, t)) || (t.vc_kept_valid && t.vc_reg != h->params.regularization) || (t.vc_map_valid && t.vc_map.res != (float)h->voxel_resolution))
       return fail(h, GORIO_ERR_INVALID, "set_target_shared: the owner's FastVGICPCuda covariances / kept points / voxel map were made with other settings than this handle's");
   }
   if (is_mp(h) && owner->tgt->mp_valid && (owner->tgt->mp_k != h->params.k_correspondences || owner->tgt->mp_reg != kRegMpBase + h->params.regularization))
@@ -2294,8 +2252,8 @@ static int submap_finish(gorio_apd* h, int m, double voxel_leaf, int* n_target) 
       HIP_TRY(h, h->d_sub_counts.reserve(nblocks + 1, nblocks + 1 + nblocks / 8));
       vox_key_kernel<<<(npow2 + 255) / 256, 256, 0, h->stream>>>(h->d_sub_out, m, npow2, g, h->d_sub_keys);
       enqueue_tiled_sort(h->stream, SortKeys{h->d_sub_keys, npow2}, 1, npow2);
-      vox_count_kernel<<<nblocks, 256, 0, h->stream>>>(h->d_sub_keys, m, h->d_sub_counts);
-      vox_scan_kernel<<<1, 1024, 0, h->stream>>>(h->d_sub_counts, nblocks);
+      cell_count_kernel<31><<<nblocks, 256, 0, h->stream>>>(h->d_sub_keys, m, h->d_sub_counts);
+      block_scan_kernel<<<1, 1024, 0, h->stream>>>(h->d_sub_counts, nblocks);
       vox_centroid_kernel<<<nblocks, 256, 0, h->stream>>>(h->d_sub_keys, h->d_sub_out, m, h->d_sub_counts, h->d_sub_vox);
       HIP_TRY(h, hipGetLastError());
       HIP_TRY(h, hipMemcpyAsync(&n_out, h->d_sub_counts + nblocks, sizeof(int), hipMemcpyDeviceToHost, h->stream));

@@ -1,4 +1,5 @@
-// apd_approx_voxel.hip -- pcl::ApproximateVoxelGrid on the device.  Included by apd_api.hip after apd_submap.hip (it reuses vox_scan_kernel).
+// apd_approx_voxel.hip -- pcl::ApproximateVoxelGrid on the device.  Included by apd_api.hip after apd_submap.hip (it reuses block_scan_kernel of
+// apd_voxel_group.hip).
 //
 // PCL is not in the image: the definition below is RECALLED from PCL 1.10 filters/impl/approximate_voxel_grid.hpp (parity: as recalled,
 // unpinned), and it is what tests/approx_voxel_restatement.py restates.
@@ -22,7 +23,7 @@
 //   2. inside a bucket a RUN starts where the cell differs from its predecessor's; a run is one output point
 //        avg_flag_kernel         0 = inside a run, 1 = first run of its bucket, 2 = a later run: its first point EVICTS the run before it
 //   3. an evicted run is put out when its evictor arrives: its position is the number of evicting points with a smaller input index
-//        avg_count_kernel + vox_scan_kernel + avg_rank_kernel   exclusive prefix sum of the evictor flags in input order; n_out
+//        avg_count_kernel + block_scan_kernel + avg_rank_kernel   exclusive prefix sum of the evictor flags in input order; n_out
 //      the last run of every bucket follows all evicted runs, in ascending bucket order
 //   4. avg_accumulate_kernel     float sums strictly in input order, the division, the store at the run's position
 // Eight launches whatever n is; the host reads back n_out (4 bytes) and nothing else.
@@ -325,7 +326,7 @@ inline hipError_t avg_enqueue(hipStream_t stream, AvgScratch& w, const AvgCols& 
   avg_scatter_kernel<<<kAvgWaves / 4, 256, 0, stream>>>(in, n, chunk, g, hist, bstart, meta, w.scell);
   avg_flag_kernel<<<nblocks, 256, 0, stream>>>(w.scell, n, meta, w.sflag, w.evflag);
   avg_count_kernel<<<nblocks, 256, 0, stream>>>(w.evflag, n, w.counts);
-  vox_scan_kernel<<<1, 1024, 0, stream>>>(w.counts, nblocks);
+  block_scan_kernel<<<1, 1024, 0, stream>>>(w.counts, nblocks);
   avg_rank_kernel<<<nblocks, 256, 0, stream>>>(w.evflag, n, w.counts, nblocks, meta);
   switch (n_fields) {
 #define GORIO_AVG_CASE(F) \

@@ -111,19 +111,25 @@ constexpr int kMethodVgicp = 2;  // fast_gicp::FastVGICP
 constexpr int kMethodNdtCuda = 3;  // fast_gicp::NDTCuda (lm_solve_body only: its linearisation is ndtc_linearize_kernel)
 constexpr int kMethodVgicpCuda = 4;  // fast_gicp::FastVGICPCuda (lm_solve_body only: its linearisation is vgc_linearize_kernel)
 
-// Gaussian voxel map of a target cloud (GaussianVoxelMap, fast_vgicp_voxel.hpp:124-182): the occupied voxels in ASCENDING order of their
-// linear id ((cx - min.x) * dim.y + (cy - min.y)) * dim.z + (cz - min.z) inside the bounding box of the occupied coordinates, i.e. in
-// lexicographic (cx, cy, cz) order.  lookup_voxel (VOX:167-174) is a binary search over vkey.
-struct VoxelMapView {
+// Gaussian voxel map of a cloud: the occupied voxels in ASCENDING order of their linear id
+// ((cx - min.x) * dim.y + (cy - min.y)) * dim.z + (cz - min.z) inside the bounding box of the occupied coordinates, i.e. in lexicographic
+// (cx, cy, cz) order.  lookup_voxel (VOX:167-174) is a binary search over vkey.
+template <typename Real>
+struct VoxMapView {
   const unsigned long long* vkey;  // [nv] linear voxel id
-  const double* mean;              // [nv][3]  GaussianVoxel::mean (component 3 is 1)
-  const double* cov6;              // [nv][6]  upper triangle of the 3x3 block of GaussianVoxel::cov
+  const Real* mean;                // [nv][3]  GaussianVoxel::mean (component 3 is 1)
+  const Real* cov6;                // [nv][6]  upper triangle of the 3x3 block of GaussianVoxel::cov
   const int* num;                  // [nv]     GaussianVoxel::num_points
   int nv;
   int min_c[3];
   int dim[3];
-  double res;                      // voxel_resolution_
+  Real res;                        // voxel_resolution_
 };
+using VoxelMapView = VoxMapView<double>;  // FastVGICP: GaussianVoxelMap, fast_vgicp_voxel.hpp:124-182
+// fast_gicp::NDTCuda (apd_ndt_cuda.hip) and FastVGICPCuda (apd_vgicp_cuda.hip): the float GaussianVoxelMap of gaussian_voxelmap.cu (NDTCuda:
+// after covariance_regularization); res = (float)resolution
+using NdtcMapView = VoxMapView<float>;
+static_assert(sizeof(VoxelMapView) == 72 && sizeof(NdtcMapView) == 64, "VoxPair and NdtcPair are uploaded as they are");
 
 // per scan pair of a FastVGICP linearisation: voxel_correspondences_ / voxel_mahalanobis_ (fast_vgicp.hpp:86-87) in a FIXED layout, one
 // slot per (source point, neighbour offset) in the offset order of VOX:16-43
@@ -133,19 +139,6 @@ struct VoxPair {
   double* omega6;  // [n_source][n_off][6] sqrt(num_points) * Mahalanobis 3x3 block of the pair (the weight of VG:149 folded in)
   int n_off;       // 1, 7 or 27
   int write_omega;
-};
-
-// fast_gicp::NDTCuda (apd_ndt_cuda.hip): the float Gaussian voxel map of a cloud (GaussianVoxelMap of gaussian_voxelmap.cu after
-// covariance_regularization), voxels in ascending linear id like VoxelMapView
-struct NdtcMapView {
-  const unsigned long long* vkey;  // [nv] linear voxel id
-  const float* mean;               // [nv][3]
-  const float* cov6;               // [nv][6] upper triangle of the regularised covariance
-  const int* num;                  // [nv]
-  int nv;
-  int min_c[3];
-  int dim[3];
-  float res;                       // (float)resolution
 };
 
 // per scan pair of an NDTCuda linearisation: the items (P2D: source points, D2D: means of the source's own voxel map), the offset table

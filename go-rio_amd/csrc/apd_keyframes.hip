@@ -1,6 +1,6 @@
 // apd_keyframes.hip -- the keyframe store and its consumers: include/gorio_keyframes.h.  Kernels first, the host side below them.
 // Included at the end of apd_api.hip, after apd_scan.hip: this is where gorio_apd, gorio_scan, gorio_ndt and gorio_sc are all complete
-// types, and the ordered compaction's block scan (compact_scan_kernel, apd_scan.hip) is reused from there.
+// types, and the ordered compaction's block scan (block_scan_kernel, apd_voxel_group.hip) is reused from there.
 //
 // SMO = apps/scan_matching_odometry_nodelet.cpp, RGS = apps/radar_graph_slam_nodelet.cpp, LD = src/radar_graph_slam/loop_detector.cpp
 // of the Go-RIO sources.
@@ -20,7 +20,7 @@ namespace gorio {
 // What the host loop of gorio_apd_set_target_submap does serially (skip non-finite points, pack the frames one behind the other, then
 // submap_transform_kernel) in three launches, none of which waits for another workgroup:
 //   kf_submap_count_kernel     per 256-point block of every frame: the finite points, one ballot + popcount per wave
-//   compact_scan_kernel        ONE workgroup scans all block counts (exclusive, in place; any number of blocks) and leaves the total behind
+//   block_scan_kernel          ONE workgroup scans all block counts (exclusive, in place; any number of blocks) and leaves the total behind
 //   kf_submap_scatter_kernel   every block repeats its ballots and writes each finite point, transformed, at its rank
 // Blocks are numbered frame by frame (KfFrame::blk0), so ranks ascend in frame order and, inside a frame, in point order.
 // grid: (max blocks of one frame, frames), block 256; a block beyond its frame's last one leaves at once (uniform per block).
@@ -355,7 +355,7 @@ static int kf_hand_off(gorio_apd* apd, gorio_kf* kf, int id, bool source) {
   const DevCloud& c = *e->cloud;
   if (cov_rule_differs(apd, c))
     return fail(apd, GORIO_ERR_INVALID, what + "the keyframe's covariances were estimated with another k_correspondences / regularization than this handle's");
-  if (!source && apd->method == GORIO_METHOD_VGICP && c.vm_valid && (c.vm_res != apd->voxel_resolution || c.vm_mult != (apd->voxel_mode == GORIO_VOXEL_MULTIPLICATIVE)))
+  if (!source && apd->method == GORIO_METHOD_VGICP && c.vm_valid && (c.vm.res != apd->voxel_resolution || c.vm_mult != (apd->voxel_mode == GORIO_VOXEL_MULTIPLICATIVE)))
     return fail(apd, GORIO_ERR_INVALID, what + "the keyframe's voxel map was built with another voxel_resolution / voxel_mode than this handle's");
   (source ? apd->src : apd->tgt) = e->cloud;  // points, covariances, search index, voxel map: one copy on the device, alive until the last holder lets go of it
   apd->corr_valid = false;
@@ -420,7 +420,7 @@ int gorio_apd_set_target_submap_keyframes(gorio_apd_t* h, gorio_kf_t* kf, const 
   HIP_TRY(h, hipMemcpyAsync(h->d_sub_kframes, fr.data(), fbytes, hipMemcpyHostToDevice, h->stream));
   const dim3 grid(max_blocks, count);
   gorio::kf_submap_count_kernel<<<grid, 256, 0, h->stream>>>(d_fr, h->d_sub_kcnt);
-  gorio::compact_scan_kernel<<<1, 1024, 0, h->stream>>>(h->d_sub_kcnt, (int)nblocks);
+  gorio::block_scan_kernel<<<1, 1024, 0, h->stream>>>(h->d_sub_kcnt, (int)nblocks);
   gorio::kf_submap_scatter_kernel<<<grid, 256, 0, h->stream>>>(d_fr, h->d_sub_kcnt, h->d_sub_out);
   HIP_TRY(h, hipGetLastError());
   int m = 0;

@@ -1,6 +1,6 @@
 // apd_map.hip -- the back end's map cloud from resident keyframes: include/gorio_map.h.  Kernels first, the host side below them.
 // Included at the end of apd_api.hip, after apd_keyframes.hip: gorio_kf and KfEntry are complete there, and the ordered compaction's block
-// scan (compact_scan_kernel, apd_scan.hip) and the tiled key sort (enqueue_tiled_sort, apd_index.hip) are reused from there.
+// scan (block_scan_kernel, apd_voxel_group.hip) and the tiled key sort (enqueue_tiled_sort, apd_index.hip) are reused from there.
 //
 // MCG = src/radar_graph_slam/map_cloud_generator.cpp, RGS = apps/radar_graph_slam_nodelet.cpp of the Go-RIO sources.
 //
@@ -19,7 +19,7 @@ namespace gorio {
 // ---------------------------------------------------------------------------------------------------------------- stage A (MCG:22-32)
 // Three launches, as the submap assembly from keyframes (apd_keyframes.hip), none of which waits for another workgroup:
 //   map_gate_count_kernel   per 256-point block of every frame: the points that pass the range gate, one ballot + popcount per wave
-//   compact_scan_kernel     ONE workgroup scans all block counts (exclusive, in place) and leaves the total behind
+//   block_scan_kernel       ONE workgroup scans all block counts (exclusive, in place) and leaves the total behind
 //   map_scatter_kernel      every block repeats its ballots and writes each kept point, transformed by the float pose, with its intensity,
 //                           at its rank; with `anchor` it also takes the smallest rank whose transformed point is finite
 // Blocks are numbered frame by frame (MapFrame::blk0), so ranks ascend in frame order and, inside a frame, in point order.
@@ -102,7 +102,7 @@ __global__ __launch_bounds__(256) void map_scatter_kernel(const MapFrame* __rest
 //   -- one copy of MapRecord to the host, where the limits are checked --
 //   map_key_kernel            key = (kx - min) << 42 | (ky - min) << 21 | (kz - min); non-finite points and the padding get ~0
 //   enqueue_tiled_sort        (apd_index.hip)
-//   map_voxel_count_kernel    first occurrences of a key per 256-key block; compact_scan_kernel scans them
+//   cell_count_kernel<0, true>  first occurrences of a key per 256-key block (apd_voxel_group.hip); block_scan_kernel scans them
 //   map_centre_kernel         one centre per first occurrence at its rank, computed from the key: no gather of points
 struct MapLattice {
   double a[3];   // (double)q0 - res / 2
@@ -181,33 +181,15 @@ __global__ __launch_bounds__(256) void map_key_kernel(const float4* __restrict__
   keys[i] = key;
 }
 
-__device__ __forceinline__ bool map_voxel_start(const unsigned long long* __restrict__ keys, int p, int n) {
-  return p < n && keys[p] != ~0ull && (p == 0 || keys[p] != keys[p - 1]);
-}
-
-// grid: ceil(n / 256) over the sorted keys of the kept points (the padding lies behind them)
-__global__ __launch_bounds__(256) void map_voxel_count_kernel(const unsigned long long* __restrict__ keys, int n, int* __restrict__ counts) {
-  const unsigned long long m = __ballot(map_voxel_start(keys, blockIdx.x * 256 + threadIdx.x, n));
-  __shared__ int sw[4];
-  if ((threadIdx.x & 63) == 0) sw[threadIdx.x >> 6] = __popcll(m);
-  __syncthreads();
-  if (threadIdx.x == 0) counts[blockIdx.x] = (sw[0] + sw[1]) + (sw[2] + sw[3]);
-}
-
+// grid: ceil(n / 256) over the sorted keys of the kept points (the padding lies behind them).  A cell is a whole key, and the all-ones
+// key of a non-finite point starts none: cell_run_start<0, true>.
 __global__ __launch_bounds__(256) void map_centre_kernel(const unsigned long long* __restrict__ keys, int n, const int* __restrict__ offsets, MapLattice g, float4* __restrict__ out,
                                                          int cap) {
-  const int p = blockIdx.x * 256 + threadIdx.x;
-  const bool start = map_voxel_start(keys, p, n);
-  const unsigned long long m = __ballot(start);
-  __shared__ int sw[4];
-  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-  if (lane == 0) sw[wv] = __popcll(m);
-  __syncthreads();
-  if (!start) return;
-  int rank = offsets[blockIdx.x] + __popcll(m & ((1ull << lane) - 1ull));
-  for (int q = 0; q < wv; ++q) rank += sw[q];
+  const RunStart rs = cell_run_start<0, true>(keys, n);
+  if (!rs.start) return;
+  const int rank = offsets[blockIdx.x] + rs.local;
   if (rank < 0 || rank >= cap) return;
-  const unsigned long long key = keys[p];
+  const unsigned long long key = keys[blockIdx.x * 256 + threadIdx.x];
   const double k0 = (double)((long long)(key >> 42) + (long long)g.min_k[0]);
   const double k1 = (double)((long long)((key >> 21) & 0x1fffffull) + (long long)g.min_k[1]);
   const double k2 = (double)((long long)(key & 0x1fffffull) + (long long)g.min_k[2]);
@@ -335,7 +317,7 @@ int gorio_map_generate(gorio_map_t* m, gorio_kf_t* kf, const int* ids, const dou
     }
     const dim3 grid(max_blocks, count);
     gorio::map_gate_count_kernel<<<grid, 256, 0, st>>>(d_fr, m->d_bcnt);
-    gorio::compact_scan_kernel<<<1, 1024, 0, st>>>(m->d_bcnt, (int)nblocks);
+    gorio::block_scan_kernel<<<1, 1024, 0, st>>>(m->d_bcnt, (int)nblocks);
     gorio::map_scatter_kernel<<<grid, 256, 0, st>>>(d_fr, m->d_bcnt, m->d_stage, cap, voxels ? d_rec : nullptr);
     if (voxels) {
       gorio::map_cells_kernel<<<(int)std::min<long long>(gorio::kMapCellBlocks, (total + 255) / 256), 256, 0, st>>>(m->d_stage, m->d_bcnt.get() + nblocks, cap, resolution, d_rec);
@@ -375,8 +357,8 @@ int gorio_map_generate(gorio_map_t* m, gorio_kf_t* kf, const int* ids, const dou
       GORIO_HIP_CHECK(map_fail, m->d_keys.reserve((size_t)npow2));
       gorio::map_key_kernel<<<npow2 / 256, 256, 0, st>>>(m->d_stage, kept, npow2, lat, m->d_keys);
       enqueue_tiled_sort(st, SortKeys{m->d_keys, npow2}, 1, npow2);
-      gorio::map_voxel_count_kernel<<<vblocks, 256, 0, st>>>(m->d_keys, kept, m->d_bcnt);
-      gorio::compact_scan_kernel<<<1, 1024, 0, st>>>(m->d_bcnt, vblocks);
+      gorio::cell_count_kernel<0, true><<<vblocks, 256, 0, st>>>(m->d_keys, kept, m->d_bcnt);
+      gorio::block_scan_kernel<<<1, 1024, 0, st>>>(m->d_bcnt, vblocks);
       GORIO_HIP_CHECK(map_fail, hipGetLastError());
       GORIO_HIP_CHECK(map_fail, hipMemcpyAsync(&n_out, m->d_bcnt.get() + vblocks, sizeof(int), hipMemcpyDeviceToHost, st));  // the voxel count
       GORIO_HIP_CHECK(map_fail, hipStreamSynchronize(st));

@@ -5,7 +5,7 @@
 // NDT = ndt_omp_impl.hpp, NDTH = ndt_omp.h, VGC = voxel_grid_covariance_omp_impl.hpp under ndt_omp/include/pclomp of the Go-RIO sources.
 //   voxel map      ndt_bbox_kernel        bounding box of the finite target points (integer atomics on an order-preserving code)
 //                  ndt_key_kernel         leaf index in the float arithmetic of VGC:218-223, key = leaf index << 31 | point index
-//                  (enqueue_tiled_sort, vox_count_kernel, vox_scan_kernel)
+//                  (enqueue_tiled_sort; cell_count_kernel, block_scan_kernel of apd_voxel_group.hip)
 //                  ndt_leaf_kernel        one lane per leaf: sums in input order in fp64 (VGC:233-237), mean, covariance, Jacobi
 //                                         eigen-decomposition, inflation, inverse, the two disabling rules (VGC:293-364)
 //   derivatives    ndt_derivative_kernel  one lane per source point: float transform, <= 26 leaf lookups (binary search over the ascending
@@ -59,12 +59,7 @@ struct NdtEval {  // one evaluation's constants, passed by value
   int n_off;      // 1, 7 or 26
 };
 
-// bb[0..2] min, bb[3..5] max (sc_code of the floats), bb[6] finite points, bb[7] flags
-__global__ void ndt_bbox_init_kernel(int* __restrict__ bb) {
-  if (threadIdx.x < 3) bb[threadIdx.x] = INT_MAX;
-  else if (threadIdx.x < 6) bb[threadIdx.x] = INT_MIN;
-  else if (threadIdx.x < 8) bb[threadIdx.x] = 0;
-}
+// bb (cell_bbox_init_kernel): bb[0..2] min, bb[3..5] max (sc_code of the floats), bb[6] finite points, bb[7] flags
 __device__ __forceinline__ bool ndt_finite3(float x, float y, float z) { return fabsf(x) <= FLT_MAX && fabsf(y) <= FLT_MAX && fabsf(z) <= FLT_MAX; }
 
 __global__ __launch_bounds__(256) void ndt_bbox_kernel(const float* __restrict__ x, const float* __restrict__ y, const float* __restrict__ z, int n, int* __restrict__ bb) {
@@ -146,16 +141,9 @@ __global__ __launch_bounds__(256) void ndt_leaf_kernel(const unsigned long long*
                                                        const float* __restrict__ z, int n, int n_points, const int* __restrict__ offsets, int min_points, double eig_mult,
                                                        int nl, int* __restrict__ lidx, int* __restrict__ lcnt, double* __restrict__ lmean, double* __restrict__ lraw,
                                                        double* __restrict__ lcov, double* __restrict__ licov) {
-  const int p = blockIdx.x * 256 + threadIdx.x;
-  const bool start = p < n && (p == 0 || (keys[p] >> 31) != (keys[p - 1] >> 31));
-  const unsigned long long m = __ballot(start);
-  __shared__ int sw[4];
-  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-  if (lane == 0) sw[wv] = __builtin_popcountll(m);
-  __syncthreads();
-  if (!start) return;
-  int rank = offsets[blockIdx.x] + __builtin_popcountll(m & ((1ull << lane) - 1ull));
-  for (int q = 0; q < wv; ++q) rank += sw[q];
+  const RunStart rs = cell_run_start<31>(keys, n);
+  if (!rs.start) return;
+  const int p = blockIdx.x * 256 + threadIdx.x, rank = offsets[blockIdx.x] + rs.local;
   if (rank < 0 || rank >= nl) return;
   const unsigned long long leaf = keys[p] >> 31;
   double s0 = 0.0, s1 = 0.0, s2 = 0.0;
@@ -706,7 +694,7 @@ int ndt_ensure_map(gorio_ndt* h) {
     return GORIO_OK;
   }
   GORIO_HIP_CHECK(ndt_fail, t->bb.reserve(8));
-  ndt_bbox_init_kernel<<<1, 64, 0, h->stream>>>(t->bb);
+  cell_bbox_init_kernel<<<1, 64, 0, h->stream>>>(t->bb);
   ndt_bbox_kernel<<<std::min(256, (n + 255) / 256), 256, 0, h->stream>>>(t->tx, t->ty, t->tz, n, t->bb);
   int bb[8];
   GORIO_HIP_CHECK(ndt_fail, hipMemcpyAsync(bb, t->bb, sizeof(int) * 8, hipMemcpyDeviceToHost, h->stream));
@@ -741,8 +729,8 @@ int ndt_ensure_map(gorio_ndt* h) {
   GORIO_HIP_CHECK(ndt_fail, t->counts.reserve((size_t)(n + 255) / 256 + 1));
   ndt_key_kernel<<<(npow2 + 255) / 256, 256, 0, h->stream>>>(t->tx, t->ty, t->tz, n, npow2, g, t->keys, t->bb);
   enqueue_tiled_sort(h->stream, SortKeys{t->keys, npow2}, 1, npow2);
-  vox_count_kernel<<<nblocks, 256, 0, h->stream>>>(t->keys, n_fin, t->counts);
-  vox_scan_kernel<<<1, 1024, 0, h->stream>>>(t->counts, nblocks);
+  cell_count_kernel<31><<<nblocks, 256, 0, h->stream>>>(t->keys, n_fin, t->counts);
+  block_scan_kernel<<<1, 1024, 0, h->stream>>>(t->counts, nblocks);
   int nv = 0, flags = 0;
   GORIO_HIP_CHECK(ndt_fail, hipMemcpyAsync(&nv, t->counts + nblocks, sizeof(int), hipMemcpyDeviceToHost, h->stream));
   GORIO_HIP_CHECK(ndt_fail, hipMemcpyAsync(&flags, t->bb + 7, sizeof(int), hipMemcpyDeviceToHost, h->stream));

@@ -1,6 +1,6 @@
 // apd_ndt_cuda.hip -- fast_gicp::NDTCuda on the device: point-to-distribution (P2D) and distribution-to-distribution (D2D) NDT with a Cauchy
-// kernel under the LsqRegistration shell.  Included by apd_api.hip after apd_voxel.hip: it reuses the key sort, the voxel-start count / scan
-// and the binary-search lookup of the FastVGICP map, the 21 + 6 + 1 partial layout and lm_solve_body.
+// kernel under the LsqRegistration shell.  Included by apd_api.hip after apd_voxel.hip: it reuses the cell grouping of apd_voxel_group.hip
+// (voxel_axis, the bounding-box and key kernels in float), the binary-search lookup of the FastVGICP map, the 21 + 6 + 1 partial layout and lm_solve_body.
 //
 // Reference lines (paths relative to the reference's fast_apdgicp/):
 //   NC = src/fast_gicp/cuda/ndt_cuda.cu                 ND = src/fast_gicp/cuda/ndt_compute_derivatives.cu
@@ -8,8 +8,7 @@
 //   CR = src/fast_gicp/cuda/covariance_regularization.cu
 // The definition this file implements is the one of include/gorio_apd.h ("GORIO_METHOD_NDT_CUDA"); tests/ndt_cuda_restatement.py restates it.
 //
-//   ndtc_coord_bbox_kernel  calc_voxel_coord (GV:118-121) of every point IN FLOAT, bounding box of the occupied coordinates, range flag
-//   ndtc_key_kernel         keys[i] = linear voxel id << 31 | i: the sort puts a voxel's points in input order behind its first key
+//   cell_coord_bbox_kernel<float>, cell_key_kernel<float> (apd_voxel_group.hip)   calc_voxel_coord (GV:118-121) of every point IN FLOAT
 //   ndtc_accum_kernel       one lane per voxel: n, s += p, S += p p^T in float in input order (GV:133-141 without the atomics), the finalise
 //                           of GV:185-188, and the MIN_EIG rebuild (CR:73-87) by the fp64 Jacobi of this library
 //   ndtc_linearize_kernel   one lane per (offset, item) slot, offset-major: q = Tf * item in float, lookup (FV:32-60), the pair terms of
@@ -21,82 +20,15 @@
 
 namespace gorio {
 
-// one axis of calc_voxel_coord: (int)floorf(x / res - 0.5f), in float; false when the value does not fit (or is not finite)
-__device__ __forceinline__ bool ndtc_axis(float v, float res, int& c) {
-  float q = v / res;
-  q = q - 0.5f;
-  q = floorf(q);
-  const bool ok = q > -(float)kVoxCoordLimit && q < (float)kVoxCoordLimit;  // false for NaN
-  c = ok ? (int)q : 0;
-  return ok;
-}
-
-__global__ __launch_bounds__(256) void ndtc_coord_bbox_kernel(const float4* __restrict__ pts, int n, float res, int* __restrict__ bb) {
-  int lo0 = INT_MAX, lo1 = INT_MAX, lo2 = INT_MAX, hi0 = INT_MIN, hi1 = INT_MIN, hi2 = INT_MIN, bad = 0;
-  for (int i = blockIdx.x * 256 + threadIdx.x; i < n; i += gridDim.x * 256) {
-    const float4 p = pts[i];
-    int c0, c1, c2;
-    bool ok = ndtc_axis(p.x, res, c0);
-    ok = ndtc_axis(p.y, res, c1) && ok;
-    ok = ndtc_axis(p.z, res, c2) && ok;
-    if (!ok) {
-      bad = 1;
-      continue;
-    }
-    lo0 = min(lo0, c0); lo1 = min(lo1, c1); lo2 = min(lo2, c2);
-    hi0 = max(hi0, c0); hi1 = max(hi1, c1); hi2 = max(hi2, c2);
-  }
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) {
-    lo0 = min(lo0, __shfl_down(lo0, off, 64)); lo1 = min(lo1, __shfl_down(lo1, off, 64)); lo2 = min(lo2, __shfl_down(lo2, off, 64));
-    hi0 = max(hi0, __shfl_down(hi0, off, 64)); hi1 = max(hi1, __shfl_down(hi1, off, 64)); hi2 = max(hi2, __shfl_down(hi2, off, 64));
-    bad |= __shfl_down(bad, off, 64);
-  }
-  if ((threadIdx.x & 63) == 0) {
-    atomicMin(bb + 0, lo0); atomicMin(bb + 1, lo1); atomicMin(bb + 2, lo2);
-    atomicMax(bb + 3, hi0); atomicMax(bb + 4, hi1); atomicMax(bb + 5, hi2);
-    if (bad) atomicOr(bb + 6, 1);
-  }
-}
-
-struct NdtcBox {
-  int min_c[3];
-  int dim[3];
-  float res;
-};
-
-__global__ __launch_bounds__(256) void ndtc_key_kernel(const float4* __restrict__ pts, int n, int npow2, NdtcBox g, unsigned long long* __restrict__ keys) {
-  const int i = blockIdx.x * 256 + threadIdx.x;
-  if (i >= npow2) return;
-  unsigned long long key = ~0ull;
-  if (i < n) {
-    const float4 p = pts[i];
-    int c0, c1, c2;
-    ndtc_axis(p.x, g.res, c0);
-    ndtc_axis(p.y, g.res, c1);
-    ndtc_axis(p.z, g.res, c2);
-    const unsigned long long id = ((unsigned long long)(c0 - g.min_c[0]) * (unsigned long long)g.dim[1] + (unsigned long long)(c1 - g.min_c[1])) * (unsigned long long)g.dim[2] + (unsigned long long)(c2 - g.min_c[2]);
-    key = (id << 31) | (unsigned long long)i;
-  }
-  keys[i] = key;
-}
-
 // one lane per voxel start of the sorted keys (rank as in vg_accum_kernel).  cov_raw: the 9 floats of GV:188, row-major (mean s^T is not
 // symmetric in float); cov6: upper triangle of sum_i max(1e-3, lambda_i) v_i v_i^T, (lambda, v) of the UPPER triangle of cov_raw widened to
 // double, summed in double and rounded once (the reference: Eigen's float closed form and V diag V^-1, CR:73-87)
 __global__ __launch_bounds__(256) void ndtc_accum_kernel(const unsigned long long* __restrict__ keys, const float4* __restrict__ pts, int n, const int* __restrict__ offsets,
                                                          unsigned long long* __restrict__ vkey, float* __restrict__ vmean, float* __restrict__ vraw, float* __restrict__ vcov6,
                                                          int* __restrict__ vnum) {
-  const int p = blockIdx.x * 256 + threadIdx.x;
-  const bool start = p < n && (p == 0 || (keys[p] >> 31) != (keys[p - 1] >> 31));
-  const unsigned long long m = __ballot(start);
-  __shared__ int sw[4];
-  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-  if (lane == 0) sw[wv] = __builtin_popcountll(m);
-  __syncthreads();
-  if (!start) return;
-  int rank = offsets[blockIdx.x] + __builtin_popcountll(m & ((1ull << lane) - 1ull));
-  for (int q = 0; q < wv; ++q) rank += sw[q];
+  const RunStart rs = cell_run_start<31>(keys, n);
+  if (!rs.start) return;
+  const int p = blockIdx.x * 256 + threadIdx.x, rank = offsets[blockIdx.x] + rs.local;
   const unsigned long long vox = keys[p] >> 31;
   float s0 = 0.f, s1 = 0.f, s2 = 0.f;
   float S00 = 0.f, S01 = 0.f, S02 = 0.f, S11 = 0.f, S12 = 0.f, S22 = 0.f;
@@ -255,9 +187,9 @@ __device__ __forceinline__ void ndtc_linearize_body(const PairDesc& pd, const Nd
     ndtc_item(np, i, ax, ay, az);
     ndtc_transform(Tf, ax, ay, az, qx, qy, qz);
     int c0, c1, c2;
-    bool ok = ndtc_axis(qx, np.map.res, c0);
-    ok = ndtc_axis(qy, np.map.res, c1) && ok;
-    ok = ndtc_axis(qz, np.map.res, c2) && ok;
+    bool ok = voxel_axis(qx, np.map.res, c0);
+    ok = voxel_axis(qy, np.map.res, c1) && ok;
+    ok = voxel_axis(qz, np.map.res, c2) && ok;
     const int* off = np.offsets + 3 * o;
     const int v = ok ? voxel_lookup(np.map, c0 + off[0], c1 + off[1], c2 + off[2]) : -1;
     np.slots[t] = v;

@@ -105,35 +105,7 @@ __global__ __launch_bounds__(256) void compact_count_kernel(const unsigned char*
   if (threadIdx.x == 0) bcnt[blockIdx.x] = (w[0] + w[1]) + (w[2] + w[3]);
 }
 
-// grid 1, block 1024.  bcnt[0 .. nb) becomes its exclusive prefix sum, bcnt[nb] the total.  nb is uniform, so every thread makes the
-// same number of trips round the loop and meets every barrier.
-__global__ __launch_bounds__(1024) void compact_scan_kernel(int* __restrict__ bcnt, int nb) {
-  __shared__ int wsum[16];
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  int carry = 0;
-  for (int base = 0; base < nb; base += 1024) {
-    const int i = base + threadIdx.x;
-    const int v = i < nb ? bcnt[i] : 0;
-    int s = v;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-      const int t = __shfl_up(s, d);
-      if (lane >= d) s += t;
-    }
-    if (lane == 63) wsum[wave] = s;
-    __syncthreads();
-    int woff = 0, tot = 0;
-#pragma unroll
-    for (int k = 0; k < 16; ++k) {
-      if (k < wave) woff += wsum[k];
-      tot += wsum[k];
-    }
-    if (i < nb) bcnt[i] = carry + woff + (s - v);
-    carry += tot;
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) bcnt[nb] = carry;
-}
+// (2) is block_scan_kernel of apd_voxel_group.hip, which the cell groupings share.
 
 __global__ __launch_bounds__(256) void compact_scatter_kernel(ScanColumns c, const unsigned char* __restrict__ keep, int n, const int* __restrict__ boffs) {
   const int i = blockIdx.x * 256 + threadIdx.x;
@@ -240,7 +212,7 @@ gorio::ScanColumns scan_columns(const ScanCloud& src, ScanCloud& dst) {
 int scan_compact(gorio_scan* h, const ScanCloud& src, ScanCloud& dst) {
   const int n = src.n, nb = (n + 255) / 256;
   gorio::compact_count_kernel<<<nb, 256, 0, h->stream>>>(h->d_keep, n, h->d_bcnt);
-  gorio::compact_scan_kernel<<<1, 1024, 0, h->stream>>>(h->d_bcnt, nb);
+  gorio::block_scan_kernel<<<1, 1024, 0, h->stream>>>(h->d_bcnt, nb);
   gorio::compact_scatter_kernel<<<nb, 256, 0, h->stream>>>(scan_columns(src, dst), h->d_keep, n, h->d_bcnt);
   GORIO_HIP_CHECK(scan_fail, hipGetLastError());
   int total = 0;

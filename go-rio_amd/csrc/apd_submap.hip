@@ -1,5 +1,6 @@
 // apd_submap.hip -- scan-to-submap target assembly on the device.  Included by apd_api.hip after apd_index.hip
-// (it reuses the LDS bitonic sort kernels of the search-index build).
+// and apd_voxel_group.hip (it reuses the LDS bitonic sort kernels of the search-index build and the run starts, the count and the scan
+// of the cell grouping).
 //
 // SMO = /root/reference/4DRadarSLAM/apps/scan_matching_odometry_nodelet.cpp.  SMO:602-618: the last keyframe clouds are moved into the
 // newest keyframe's frame (pcl::transformPointCloud with a double 4x4), concatenated, passed through downsample() (SMO:405-415: NONE =
@@ -95,53 +96,12 @@ __global__ __launch_bounds__(256) void vox_key_kernel(const float4* __restrict__
   keys[i] = key;
 }
 
-// number of voxel starts per 256-key block -> counts[block]
-__global__ __launch_bounds__(256) void vox_count_kernel(const unsigned long long* __restrict__ keys, int n, int* __restrict__ counts) {
-  const int p = blockIdx.x * 256 + threadIdx.x;
-  const bool start = p < n && (p == 0 || (keys[p] >> 31) != (keys[p - 1] >> 31));
-  const unsigned long long m = __ballot(start);
-  __shared__ int sw[4];
-  if ((threadIdx.x & 63) == 0) sw[threadIdx.x >> 6] = __builtin_popcountll(m);
-  __syncthreads();
-  if (threadIdx.x == 0) counts[blockIdx.x] = sw[0] + sw[1] + sw[2] + sw[3];
-}
-// exclusive scan of the block counts by ONE workgroup (<= a few thousand blocks); total -> counts[nblocks]
-__global__ __launch_bounds__(1024) void vox_scan_kernel(int* __restrict__ counts, int nblocks) {
-  __shared__ int s[1024];
-  __shared__ int carry;
-  if (threadIdx.x == 0) carry = 0;
-  __syncthreads();
-  for (int base = 0; base < nblocks; base += 1024) {
-    const int i = base + threadIdx.x;
-    const int v = i < nblocks ? counts[i] : 0;
-    s[threadIdx.x] = v;
-    __syncthreads();
-    for (int off = 1; off < 1024; off <<= 1) {
-      const int t = threadIdx.x >= off ? s[threadIdx.x - off] : 0;
-      __syncthreads();
-      s[threadIdx.x] += t;
-      __syncthreads();
-    }
-    if (i < nblocks) counts[i] = carry + s[threadIdx.x] - v;
-    __syncthreads();
-    if (threadIdx.x == 1023) carry += s[1023];
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) counts[nblocks] = carry;
-}
 // one lane per voxel start: the centroid of its run of keys, written at its rank in ascending voxel order
 __global__ __launch_bounds__(256) void vox_centroid_kernel(const unsigned long long* __restrict__ keys, const float4* __restrict__ pts, int n, const int* __restrict__ offsets,
                                                            float4* __restrict__ out) {
-  const int p = blockIdx.x * 256 + threadIdx.x;
-  const bool start = p < n && (p == 0 || (keys[p] >> 31) != (keys[p - 1] >> 31));
-  const unsigned long long m = __ballot(start);
-  __shared__ int sw[4];
-  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-  if (lane == 0) sw[wv] = __builtin_popcountll(m);
-  __syncthreads();
-  if (!start) return;
-  int rank = offsets[blockIdx.x] + __builtin_popcountll(m & ((1ull << lane) - 1ull));
-  for (int q = 0; q < wv; ++q) rank += sw[q];
+  const RunStart rs = cell_run_start<31>(keys, n);
+  if (!rs.start) return;
+  const int p = blockIdx.x * 256 + threadIdx.x, rank = offsets[blockIdx.x] + rs.local;
   const unsigned long long vox = keys[p] >> 31;
   float sx = 0.f, sy = 0.f, sz = 0.f, sn = 0.f;
   int cnt = 0;

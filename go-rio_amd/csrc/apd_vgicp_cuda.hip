@@ -1,8 +1,8 @@
 // apd_vgicp_cuda.hip -- fast_gicp::FastVGICPCuda on the device: float per-point covariances (from the k-NN lists, or by an RBF kernel over
 // the whole cloud), their regularisation with the point-dropping PLANE filter, a voxel map that averages point covariances, and the GICP
 // pair term with the sqrt(num_points) weight under the LsqRegistration shell.  Included by apd_api.hip after apd_ndt_cuda.hip: the float
-// coordinate and key kernels, the key sort, the lookup, the slot table, the pair arithmetic (ndtc_pair_terms, third mode) and the fp64
-// sums are the ones of NDTCuda.
+// instances of the coordinate and key kernels (apd_voxel_group.hip), the key sort, the lookup, the slot table, the pair arithmetic
+// (ndtc_pair_terms, third mode) and the fp64 sums are the ones of NDTCuda.
 //
 // Reference lines (paths relative to the reference's fast_apdgicp/):
 //   VH / VI = include/fast_gicp/gicp/fast_vgicp_cuda.hpp and impl/fast_vgicp_cuda_impl.hpp   VC = src/fast_gicp/cuda/fast_vgicp_cuda.cu
@@ -17,7 +17,7 @@
 //                           order (RB:116-151); grid (point tiles, blocks), so a 16 k cloud is 2048 workgroups, not 64
 //   vgc_cov_rbf_fold_kernel one lane per point: the block partials added in block order, then the finalise of RB:98-108
 //   vgc_regularize_kernel   fp64 Jacobi on the six floats, the keep flag of the PLANE filter (CR:29) and the rebuilt covariance (CR:91-117)
-//   vgc_scatter_kernel      the scatter of the ordered compaction (compact_count_kernel / compact_scan_kernel of apd_scan.hip before it)
+//   vgc_scatter_kernel      the scatter of the ordered compaction (compact_count_kernel of apd_scan.hip and block_scan_kernel before it)
 //   vgc_accum_kernel        one lane per voxel: n, s += p, Csum += cov in kept order, in float (GV:229-252 without the atomics)
 //   vgc_linearize_kernel    ndtc_linearize_body with the GICP term (CD:50-92): Q = cov_B + R_lin cov_A R_lin^T, w = sqrtf(num_points)
 //   (compute_error, CD:106-135, over the slots of the last linearise is ndtc_error_part<true> of apd_ndt_cuda.hip, inside lm_solve_vgc_kernel)
@@ -27,9 +27,8 @@
 
 namespace gorio {
 
-// the ordered compaction's count and scan (apd_scan.hip, included at the end of apd_api.hip)
+// the ordered compaction's count (apd_scan.hip, included at the end of apd_api.hip)
 __global__ __launch_bounds__(256) void compact_count_kernel(const unsigned char* __restrict__ keep, int n, int* __restrict__ bcnt);
-__global__ __launch_bounds__(1024) void compact_scan_kernel(int* __restrict__ bcnt, int nb);
 
 constexpr int kRbfBlock = 512;  // RB:116: the reference's tile of the pairwise pass; part of the summation order
 constexpr int kRbfTerms = 10;   // sw, s[3], S[6] (upper triangle: the reference keeps nine sums)
@@ -179,16 +178,9 @@ __global__ __launch_bounds__(256) void vgc_scatter_kernel(const float4* __restri
 __global__ __launch_bounds__(256) void vgc_accum_kernel(const unsigned long long* __restrict__ keys, const float4* __restrict__ pts, const float* __restrict__ cov6, int n,
                                                         const int* __restrict__ offsets, unsigned long long* __restrict__ vkey, float* __restrict__ vmean,
                                                         float* __restrict__ vcov6, int* __restrict__ vnum) {
-  const int p = blockIdx.x * 256 + threadIdx.x;
-  const bool start = p < n && (p == 0 || (keys[p] >> 31) != (keys[p - 1] >> 31));
-  const unsigned long long m = __ballot(start);
-  __shared__ int sw[4];
-  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-  if (lane == 0) sw[wv] = __builtin_popcountll(m);
-  __syncthreads();
-  if (!start) return;
-  int rank = offsets[blockIdx.x] + __builtin_popcountll(m & ((1ull << lane) - 1ull));
-  for (int q = 0; q < wv; ++q) rank += sw[q];
+  const RunStart rs = cell_run_start<31>(keys, n);
+  if (!rs.start) return;
+  const int p = blockIdx.x * 256 + threadIdx.x, rank = offsets[blockIdx.x] + rs.local;
   const unsigned long long vox = keys[p] >> 31;
   float s0 = 0.f, s1 = 0.f, s2 = 0.f;
   float c[6] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f};

@@ -1,12 +1,11 @@
 // apd_voxel.hip -- FastVGICP on the device: Gaussian voxel map of the target, pose-dependent voxel lookups, linearisation over the
 // (source point, voxel) pairs.  Included by apd_api.hip after apd_submap.hip (it reuses the LDS bitonic sort of the search-index build and
-// the count / scan kernels of the submap voxel grid).
+// the cell grouping of apd_voxel_group.hip: voxel_axis, the bounding-box and key kernels in double, the run starts, the count and the scan).
 //
 // Reference lines (paths relative to /root/reference/fast_apdgicp/include/fast_gicp/gicp):
 //   VG  = impl/fast_vgicp_impl.hpp     VOX = fast_vgicp_voxel.hpp
 //
-//   vg_coord_bbox_kernel   voxel_coord (VOX:158-160) of every target point, bounding box of the occupied coordinates, range flag
-//   vg_key_kernel          keys[i] = linear voxel id << 31 | i; the sort puts a voxel's points in INPUT order behind its first key
+//   cell_coord_bbox_kernel<double>, cell_key_kernel<double> (apd_voxel_group.hip)   voxel_coord (VOX:158-160) of every target point
 //   vg_accum_kernel        one lane per voxel: append() in input order and finalize() (VOX:79-122), fp64 -- the order of the sums is the
 //                          reference's (create_voxelmap walks the cloud once, VOX:131-151), so the map does not depend on scheduling
 //   vgicp_linearize_kernel one lane per (source point, offset) slot: T * mean_A in double, un-fused, column order (VG:84-86), voxel_coord,
@@ -20,8 +19,6 @@
 #include <hip/hip_runtime.h>
 
 namespace gorio {
-
-constexpr int kVoxCoordLimit = 1 << 30;  // |coordinate| below this: +-1 neighbours and the box arithmetic stay inside int32
 
 // Eigen Isometry3d * Vector4d (VG:85): ((m0 x + m1 y) + m2 z) + m3 * 1 per row, double, NO fused multiply-add: the voxel a point
 // falls into must not depend on how a compiler contracts the sum (this file is built with -ffp-contract=off)
@@ -40,90 +37,16 @@ __device__ __forceinline__ void transform_d(const double* __restrict__ T, double
   qz = a + T[11];
 }
 
-// one axis of voxel_coord, VOX:158-160: floor(x / resolution - 0.5); false when the value does not fit (or is not finite)
-__device__ __forceinline__ bool voxel_axis(double v, double res, int& c) {
-  double q = v / res;
-  q = q - 0.5;
-  q = floor(q);
-  const bool ok = q > -(double)kVoxCoordLimit && q < (double)kVoxCoordLimit;  // false for NaN
-  c = ok ? (int)q : 0;
-  return ok;
-}
-
-// bb[0..2] min, bb[3..5] max of the occupied coordinates, bb[6] != 0: a point whose coordinate does not fit
-__global__ void vg_bbox_init_kernel(int* __restrict__ bb) {
-  if (threadIdx.x < 3) bb[threadIdx.x] = INT_MAX;
-  else if (threadIdx.x < 6) bb[threadIdx.x] = INT_MIN;
-  else if (threadIdx.x == 6) bb[6] = 0;
-}
-__global__ __launch_bounds__(256) void vg_coord_bbox_kernel(const float4* __restrict__ pts, int n, double res, int* __restrict__ bb) {
-  int lo0 = INT_MAX, lo1 = INT_MAX, lo2 = INT_MAX, hi0 = INT_MIN, hi1 = INT_MIN, hi2 = INT_MIN, bad = 0;
-  for (int i = blockIdx.x * 256 + threadIdx.x; i < n; i += gridDim.x * 256) {
-    const float4 p = pts[i];
-    int c0, c1, c2;
-    bool ok = voxel_axis((double)p.x, res, c0);
-    ok = voxel_axis((double)p.y, res, c1) && ok;
-    ok = voxel_axis((double)p.z, res, c2) && ok;
-    if (!ok) {
-      bad = 1;
-      continue;
-    }
-    lo0 = min(lo0, c0); lo1 = min(lo1, c1); lo2 = min(lo2, c2);
-    hi0 = max(hi0, c0); hi1 = max(hi1, c1); hi2 = max(hi2, c2);
-  }
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) {
-    lo0 = min(lo0, __shfl_down(lo0, off, 64)); lo1 = min(lo1, __shfl_down(lo1, off, 64)); lo2 = min(lo2, __shfl_down(lo2, off, 64));
-    hi0 = max(hi0, __shfl_down(hi0, off, 64)); hi1 = max(hi1, __shfl_down(hi1, off, 64)); hi2 = max(hi2, __shfl_down(hi2, off, 64));
-    bad |= __shfl_down(bad, off, 64);
-  }
-  if ((threadIdx.x & 63) == 0) {
-    atomicMin(bb + 0, lo0); atomicMin(bb + 1, lo1); atomicMin(bb + 2, lo2);
-    atomicMax(bb + 3, hi0); atomicMax(bb + 4, hi1); atomicMax(bb + 5, hi2);
-    if (bad) atomicOr(bb + 6, 1);
-  }
-}
-
-struct VoxBox {
-  int min_c[3];
-  int dim[3];
-  double res;
-};
-
-// keys[i] = linear voxel id << 31 | i (id < 2^33, checked on the host); ~0 for the sort's padding
-__global__ __launch_bounds__(256) void vg_key_kernel(const float4* __restrict__ pts, int n, int npow2, VoxBox g, unsigned long long* __restrict__ keys) {
-  const int i = blockIdx.x * 256 + threadIdx.x;
-  if (i >= npow2) return;
-  unsigned long long key = ~0ull;
-  if (i < n) {
-    const float4 p = pts[i];
-    int c0, c1, c2;
-    voxel_axis((double)p.x, g.res, c0);
-    voxel_axis((double)p.y, g.res, c1);
-    voxel_axis((double)p.z, g.res, c2);
-    const unsigned long long id = ((unsigned long long)(c0 - g.min_c[0]) * (unsigned long long)g.dim[1] + (unsigned long long)(c1 - g.min_c[1])) * (unsigned long long)g.dim[2] + (unsigned long long)(c2 - g.min_c[2]);
-    key = (id << 31) | (unsigned long long)i;
-  }
-  keys[i] = key;
-}
-
-// one lane per voxel start of the sorted keys (rank = position in ascending id order, as vox_centroid_kernel computes it): the
+// one lane per voxel start of the sorted keys (rank = position in ascending id order, cell_run_start): the
 // voxel's points in input order.  mode 0 / 1: AdditiveGaussianVoxel (VOX:105-122; ADDITIVE_WEIGHTED builds the same voxel, VOX:138-141),
 // mode 2: MultiplicativeGaussianVoxel (VOX:79-103).  The 4x4 matrices of the reference decouple: row / column 3 of a covariance are zero
 // (with (3,3) set to 1 before every inverse), so the 3x3 block is inverted and component 3 of the mean is 1.
 __global__ __launch_bounds__(256) void vg_accum_kernel(const unsigned long long* __restrict__ keys, const float4* __restrict__ pts, const double* __restrict__ cov6, int n,
                                                        const int* __restrict__ offsets, int mode, unsigned long long* __restrict__ vkey, double* __restrict__ vmean,
                                                        double* __restrict__ vcov6, int* __restrict__ vnum) {
-  const int p = blockIdx.x * 256 + threadIdx.x;
-  const bool start = p < n && (p == 0 || (keys[p] >> 31) != (keys[p - 1] >> 31));
-  const unsigned long long m = __ballot(start);
-  __shared__ int sw[4];
-  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-  if (lane == 0) sw[wv] = __builtin_popcountll(m);
-  __syncthreads();
-  if (!start) return;
-  int rank = offsets[blockIdx.x] + __builtin_popcountll(m & ((1ull << lane) - 1ull));
-  for (int q = 0; q < wv; ++q) rank += sw[q];
+  const RunStart rs = cell_run_start<31>(keys, n);
+  if (!rs.start) return;
+  const int p = blockIdx.x * 256 + threadIdx.x, rank = offsets[blockIdx.x] + rs.local;
   const unsigned long long vox = keys[p] >> 31;
   double m0 = 0.0, m1 = 0.0, m2 = 0.0;
   double s00 = 0.0, s01 = 0.0, s02 = 0.0, s11 = 0.0, s12 = 0.0, s22 = 0.0;

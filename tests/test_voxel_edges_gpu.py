@@ -1,14 +1,19 @@
-"""The three device voxel structures at the size and geometry edges of tests/voxel_scenes.py, against the CPU restatements that
+"""The device voxel structures at the size and geometry edges of tests/voxel_scenes.py, against the CPU restatements that
 tests/test_voxel_scenes.py pins on the same scenes.
 
-All three go through one pipeline (keys = cell id << 31 | input index, the tiled key sort, vox_count_kernel per 256-key block,
-vox_scan_kernel over the block counts 1024 at a time, one lane per cell start), so every regime x size runs on each of them:
+All of them go through one pipeline (keys = cell id << 31 | input index, the tiled key sort, cell_count_kernel per 256-key block,
+block_scan_kernel over the block counts 1024 at a time, one lane per cell start), so every regime x size runs on the first three:
   pcl::VoxelGrid     setInputTargetSubmap + getTargetPoints and prep.voxel_downsample against oracle.apd.submap_assemble: np.array_equal
                      on points and labels, equal counts
   FastVGICP map      getVoxelMap() against gicp_restatement.VoxelMap (VoxelMapVec at 262 k points) with the gates of
                      map_checks.check_map; voxel slots of linearize() equal to the restatement's table
   NDT grid           Ndt.voxels() against ndt_restatement.build_voxel_map with the gates of map_checks.check_ndt_map
 The 262 k inputs and their references are built once per module.
+The two float maps run the sizes on the wave and 256-key block boundaries of the shared preamble (the 1024 / 1025-block scan edge is
+the same scan kernel's, exercised above):
+  NDTCuda map        ndt_cuda_voxels(1) against ndt_cuda_restatement.build_map with the table comparison of tests/test_ndt_cuda_gpu.py
+  FastVGICPCuda map  vgicp_cuda_voxels() against vgicp_cuda_restatement.build_map fed the device's own per-point covariances, with the
+                     comparison of tests/test_vgicp_cuda_gpu.py (bit-exact)
 """
 import importlib
 
@@ -16,7 +21,11 @@ import numpy as np
 import pytest
 
 import gicp_restatement as gr
+import ndt_cuda_restatement as ncr
 import ndt_restatement as nr
+import test_ndt_cuda_gpu as ndtc
+import test_vgicp_cuda_gpu as vgc
+import vgicp_cuda_restatement as vr
 import voxel_scenes as S
 from map_checks import check_map, check_ndt_map
 
@@ -200,3 +209,34 @@ def test_ndt_limits(gpu, gorio, ndt_case):
     v = n.voxels()
     n.close()
     assert np.array_equal(v["leaf_index"], ref.idx) and np.array_equal(v["mean"], ref.mean)
+
+
+# ------------------------------------------------------------------------------------------------ the float maps: NDTCuda, FastVGICPCuda
+
+FLOAT_CASES = [(r, m) for r in ("own_cell", "mixed") for m in (1, 63, 64, 65, 255, 256, 257, 4097)] + [("one_cell", 4097)]
+FLOAT_IDS = ["%s-%d" % c for c in FLOAT_CASES]
+
+
+@pytest.mark.parametrize("regime,m", FLOAT_CASES, ids=FLOAT_IDS)
+def test_ndt_cuda_map(gpu, gorio, regime, m):
+    xyz = S.vgicp_target((regime, m))  # points in the middle half of their voxels: the float and the double rule agree
+    g = ndtc.make(gorio, gpu, mode=ncr.P2D)
+    g.setInputTarget(xyz)
+    ref = ncr.build_map(xyz, 1.0)
+    assert ref["num_points"].sum() == m
+    ndtc.check_table(g.ndt_cuda_voxels(1), ref)
+
+
+@pytest.mark.parametrize("regime,m", FLOAT_CASES, ids=FLOAT_IDS)
+def test_vgicp_cuda_map(gpu, gorio, regime, m):
+    """covariances by the RBF kernel (no k-NN list, so one point is a cloud) and no regularisation: every point is kept, the map is
+    built from exactly m keys"""
+    xyz = S.vgicp_target((regime, m))
+    g = vgc.make(gorio, gpu, nn=vr.GPU_RBF_KERNEL, regularization=vr.NONE)
+    g.setInputTarget(xyz)
+    pts, tab = g.vgicp_cuda_points(1), g.vgicp_cuda_voxels()
+    assert np.array_equal(pts["kept_index"], np.arange(m)) and np.isfinite(pts["cov"]).all()
+    ref = vr.build_map(xyz, pts["cov"], 1.0)
+    assert np.array_equal(tab["coord"], ref["coord"]) and np.array_equal(tab["num_points"], ref["num_points"])
+    assert vgc.same_bits(tab["mean"], ref["mean"]) and vgc.same_bits(tab["cov"], ref["cov6"])
+    assert ref["num_points"].sum() == m
