@@ -29,7 +29,7 @@ def build(force: bool = False) -> str:
 
 
 from . import synth  # noqa: E402  (pure-numpy synthetic inputs, no GPU)
-from .apd import ApdGicp, ApdParams, DeviceInputs, GorioError, align_batch, fitness_score_batch, gicp_omp_align_batch, icp_align_batch, load_library  # noqa: E402
+from .apd import ApdGicp, ApdParams, DeviceInputs, GorioError, align_batch, fitness_score_batch, gicp_mp_align_batch, gicp_omp_align_batch, icp_align_batch, load_library  # noqa: E402
 from . import prep  # noqa: E402
 from . import ground  # noqa: E402
 from . import scan_context  # noqa: E402

@@ -59,7 +59,7 @@ APD_SYMBOLS = [
     "gorio_apd_set_ndt_cuda_params", "gorio_apd_get_ndt_cuda_params", "gorio_apd_ndt_cuda_get_voxels", "gorio_apd_ndt_cuda_get_pairs",
     "gorio_apd_set_vgicp_cuda_params", "gorio_apd_get_vgicp_cuda_params", "gorio_apd_vgicp_cuda_get_points", "gorio_apd_vgicp_cuda_get_voxels", "gorio_apd_vgicp_cuda_get_pairs",
     "gorio_apd_set_gicp_mp_params", "gorio_apd_get_gicp_mp_params", "gorio_apd_gicp_mp_get_covariances", "gorio_apd_gicp_mp_pass", "gorio_apd_gicp_mp_get_neighbors", "gorio_apd_gicp_mp_get_merged",
-    "gorio_apd_gicp_mp_diag",
+    "gorio_apd_gicp_mp_diag", "gorio_apd_gicp_mp_align_batch", "gorio_apd_gicp_mp_batch_diag", "gorio_apd_gicp_mp_last_hessian",
     "gorio_apd_set_submap_downsample", "gorio_apd_get_submap_downsample",
 ]
 
@@ -745,6 +745,35 @@ def icp_align_batch(objs, guesses=None):
         d = o.icp_diag()  # passes = iterations, plus the pass that found fewer than 3 pairs (state 5) when the align ended there
         out.append(dict(T=T[q], H=np.zeros((6, 6), np.float64), converged=bool(conv[q]), nr_iterations=int(nit[q]), n_linearize=d["iterations"] + (d["state"] == 5),
                         batch_diag=dict(diag)))
+    return out
+
+
+def gicp_mp_align_batch(objs, guesses=None):
+    """gorio_apd_gicp_mp_align_batch over a list of ApdGicp objects in GICP_MP mode (all on one device; parameters and radii may
+    differ): their aligns in lock-step rounds over one batched radius search per round, every result bit for bit the one of the
+    object's own align().  Returns the list of dicts align() returns (H = the last pass's, n_linearize = the object's passes); the
+    first carries batch_diag = dict(rounds, launches, syncs, max_round_launches) of the whole batch.  An empty list makes no call."""
+    n = len(objs)
+    if n == 0:
+        return []
+    lib = load_library()
+    g = np.ascontiguousarray(np.tile(np.eye(4, dtype=np.float32), (n, 1, 1)) if guesses is None else guesses, np.float32).reshape(n, 16)
+    T = np.zeros((n, 4, 4), np.float32)
+    conv = np.zeros(n, np.int32)
+    nit = np.zeros(n, np.int32)
+    arr = (C.c_void_p * n)(*[o._h for o in objs])
+    rc = lib.gorio_apd_gicp_mp_align_batch(arr, n, _p(g, C.c_float), _p(T, C.c_float), _p(conv, C.c_int), _p(nit, C.c_int))
+    _check(objs[0]._h, rc)
+    r, l, sy, m = C.c_int(0), C.c_int(0), C.c_int(0), C.c_int(0)
+    _check(objs[0]._h, lib.gorio_apd_gicp_mp_batch_diag(objs[0]._h, C.byref(r), C.byref(l), C.byref(sy), C.byref(m)))
+    out = []
+    for q, o in enumerate(objs):
+        o._final = T[q]
+        o._converged = bool(conv[q])
+        H = np.zeros((6, 6), np.float64)
+        _check(o._h, lib.gorio_apd_gicp_mp_last_hessian(o._h, _p(H, C.c_double)))
+        out.append(dict(T=T[q], H=H, converged=bool(conv[q]), nr_iterations=int(nit[q]), n_linearize=o.gicp_mp_diag()["passes"]))
+    out[0]["batch_diag"] = dict(rounds=r.value, launches=l.value, syncs=sy.value, max_round_launches=m.value)
     return out
 
 

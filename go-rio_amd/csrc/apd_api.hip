@@ -17,6 +17,7 @@
 #include <memory>
 #include <mutex>
 #include <string>
+#include <unordered_map>
 #include <unordered_set>
 #include <vector>
 
@@ -1407,7 +1408,7 @@ int align_impl(gorio_apd** hs, int count, const float* guesses, float* T_out, do
   for (int q = 0; q < count; ++q)
     if (hs[q] && hs[q]->method == GORIO_METHOD_ICP) return fail(lead, GORIO_ERR_UNSUPPORTED, "align_batch: ICP handles batch through gorio_apd_icp_align_batch");
   for (int q = 0; q < count; ++q)
-    if (hs[q] && is_mp(hs[q])) return fail(lead, GORIO_ERR_UNSUPPORTED, "align_batch: FastGICPMultiPoints has no batched form (its radius search serves one cloud per call)");
+    if (hs[q] && is_mp(hs[q])) return fail(lead, GORIO_ERR_UNSUPPORTED, "align_batch: FastGICPMultiPoints handles are batched by gorio_apd_gicp_mp_align_batch (their rounds run a batched radius search, not this call's pair searches)");
   std::unordered_set<gorio_apd*> distinct;
   for (int q = 0; q < count; ++q) {
     gorio_apd* h = hs[q];

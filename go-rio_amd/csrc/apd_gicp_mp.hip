@@ -16,11 +16,16 @@
 //                         (profiles/r20/gicp_mp.md).  No LDS but the 4 x 28 reduction cells, no scratch, no atomics.
 //   mp_fold_kernel        the block partials added in block order
 //
+//   mp_*_batch_kernel     query, linearise and fold over the (job, block) entries of a batch round, calling the bodies of the three above
+//
 // The shell (6 x 6 LDLT, exp / log, update, convergence) runs on the host between passes: the radius search synchronises once per pass
-// for its total anyway, and the pass ends with one copy back of 28 doubles.
+// for its total anyway, and the pass ends with one copy back of 28 doubles.  It is the resumable MpMachine of gicp_mp_machine.h, which
+// gorio_apd_align drives for one handle and gorio_apd_gicp_mp_align_batch for many in lock-step rounds (mp_run_batch).
 #include <hip/hip_runtime.h>
 
 #include <chrono>
+
+#include "gicp_mp_machine.h"
 
 namespace gorio {
 
@@ -95,23 +100,27 @@ __global__ __launch_bounds__(256) void mp_cov_kernel(const float4* __restrict__ 
 }
 
 // grid ceil(n / 256), block 256
-__global__ __launch_bounds__(256) void mp_query_kernel(const float4* __restrict__ pts, int n, MpPose T, float4* __restrict__ q) {
-  const int i = blockIdx.x * 256 + threadIdx.x;
+__device__ __forceinline__ void mp_query_point(const float4* __restrict__ pts, int n, const MpPose& T, float4* __restrict__ q, int i) {
   if (i >= n) return;
   const float4 p = pts[i];
   float x, y, z;
   transform_f(T.m, p.x, p.y, p.z, x, y, z);
   q[i] = make_float4(x, y, z, 0.f);
 }
+__global__ __launch_bounds__(256) void mp_query_kernel(const float4* __restrict__ pts, int n, MpPose T, float4* __restrict__ q) {
+  mp_query_point(pts, n, T, q, blockIdx.x * 256 + threadIdx.x);
+}
 
 // grid ceil(n / 256), block 256.  src_rec / tgt_rec: the records of mp_cov_kernel; q: the transformed source of THIS pose; offs / idx /
 // sqd: the CSR of the radius search (idx and sqd may be null when it is empty).  merged (may be null): per source point mean_B, cov_B
 // and the used flag as three float4 (m0 m1 m2 c00 | c01 c02 c11 c12 | c22 used 0 0).  partials: [blocks][28] = 21 H (upper triangle,
 // row-major), 6 g, the points used.
-__global__ __launch_bounds__(256) void mp_linearize_kernel(const float4* __restrict__ src_rec, const float4* __restrict__ q, int n, const long long* __restrict__ offs,
-                                                           const int* __restrict__ idx, const float* __restrict__ sqd, const float4* __restrict__ tgt_rec, int n_tgt, MpPose T,
-                                                           double radius, float4* __restrict__ merged, double* __restrict__ partials) {
-  const int i = blockIdx.x * 256 + threadIdx.x;
+// The work of ONE workgroup: source points [256 blk, 256 blk + 256), their 28 sums to block_out[0..27].  mp_linearize_kernel runs it for one
+// handle, mp_linearize_batch_kernel for a (job, block) entry of a batch: one body, one summation order, the same bits.
+__device__ __forceinline__ void mp_linearize_block(const float4* __restrict__ src_rec, const float4* __restrict__ q, int n, const long long* __restrict__ offs,
+                                                   const int* __restrict__ idx, const float* __restrict__ sqd, const float4* __restrict__ tgt_rec, int n_tgt, const MpPose& T,
+                                                   double radius, float4* __restrict__ merged, int blk, double* __restrict__ block_out) {
+  const int i = blk * 256 + threadIdx.x;
   double acc[28];
 #pragma unroll
   for (int t = 0; t < 28; ++t) acc[t] = 0.0;
@@ -211,16 +220,58 @@ __global__ __launch_bounds__(256) void mp_linearize_kernel(const float4* __restr
     }
   }
   __syncthreads();
-  if (threadIdx.x < 28) partials[(size_t)blockIdx.x * 28 + threadIdx.x] = (red[0][threadIdx.x] + red[1][threadIdx.x]) + (red[2][threadIdx.x] + red[3][threadIdx.x]);
+  if (threadIdx.x < 28) block_out[threadIdx.x] = (red[0][threadIdx.x] + red[1][threadIdx.x]) + (red[2][threadIdx.x] + red[3][threadIdx.x]);
+}
+__global__ __launch_bounds__(256) void mp_linearize_kernel(const float4* __restrict__ src_rec, const float4* __restrict__ q, int n, const long long* __restrict__ offs,
+                                                           const int* __restrict__ idx, const float* __restrict__ sqd, const float4* __restrict__ tgt_rec, int n_tgt, MpPose T,
+                                                           double radius, float4* __restrict__ merged, double* __restrict__ partials) {
+  mp_linearize_block(src_rec, q, n, offs, idx, sqd, tgt_rec, n_tgt, T, radius, merged, blockIdx.x, partials + (size_t)blockIdx.x * 28);
 }
 
-// grid 1, block 64: out[t] = the partials of term t added in block order
-__global__ __launch_bounds__(64) void mp_fold_kernel(const double* __restrict__ partials, int nblk, double* __restrict__ out) {
+// out[t] = the nblk partials of term t added in block order, lane t of one wave
+__device__ __forceinline__ void mp_fold_wave(const double* __restrict__ partials, int nblk, double* __restrict__ out) {
   const int t = threadIdx.x;
   if (t >= 28) return;
   double s = 0.0;
   for (int b = 0; b < nblk; ++b) s += partials[(size_t)b * 28 + t];
   out[t] = s;
+}
+// grid 1, block 64
+__global__ __launch_bounds__(64) void mp_fold_kernel(const double* __restrict__ partials, int nblk, double* __restrict__ out) { mp_fold_wave(partials, nblk, out); }
+
+// ---- the batched align (gorio_apd_gicp_mp_align_batch): the three launches above once more, each over the pending handles of a round.
+// One handle's pass of a round.  Workgroups [first, first + nblk) of the query and the linearise launch belong to it, and so do the
+// partial slots of the same numbers.
+struct MpJob {
+  const float4* src_p4;
+  const float4* src_rec;
+  float4* q;
+  const long long* offs;  // the CSR of the handle's own search state (set after the search of the round)
+  const int* idx;
+  const float* sqd;
+  const float4* tgt_rec;
+  double radius;
+  MpPose T;
+  int n, n_tgt, first, nblk;
+};
+struct MpBlockRef {
+  int job, blk;
+};
+// grid: the jobs' blocks added up, block 256
+__global__ __launch_bounds__(256) void mp_query_batch_kernel(const MpJob* __restrict__ jobs, const MpBlockRef* __restrict__ blocks) {
+  const MpBlockRef w = load_uniform(blocks + blockIdx.x);
+  const MpJob j = load_uniform(jobs + w.job);
+  mp_query_point(j.src_p4, j.n, j.T, j.q, w.blk * 256 + (int)threadIdx.x);
+}
+__global__ __launch_bounds__(256) void mp_linearize_batch_kernel(const MpJob* __restrict__ jobs, const MpBlockRef* __restrict__ blocks, double* __restrict__ partials) {
+  const MpBlockRef w = load_uniform(blocks + blockIdx.x);
+  const MpJob j = load_uniform(jobs + w.job);
+  mp_linearize_block(j.src_rec, j.q, j.n, j.offs, j.idx, j.sqd, j.tgt_rec, j.n_tgt, j.T, j.radius, nullptr, w.blk, partials + (size_t)(j.first + w.blk) * 28);
+}
+// grid: the round's jobs, block 64
+__global__ __launch_bounds__(64) void mp_fold_batch_kernel(const MpJob* __restrict__ jobs, const double* __restrict__ partials, double* __restrict__ out) {
+  const MpJob j = load_uniform(jobs + blockIdx.x);
+  mp_fold_wave(partials + (size_t)j.first * 28, j.nblk, out + (size_t)blockIdx.x * 28);
 }
 
 }  // namespace gorio
@@ -239,7 +290,14 @@ struct GicpMpState {
   bool merged_valid = false;
   long long total = 0;           // neighbours of the last pass
   int used = 0, passes = 0;      // of the last pass / of the last align
+  double last_H[36] = {};        // H of the last pass of the last align, single or batched (gorio_apd_gicp_mp_last_hessian)
   double stage_s[4] = {0, 0, 0, 0};  // query transform, radius search, merge + linearise (with fold and copy back), shell: filled while profiling
+  // a batch this handle LEADS (gorio_apd_gicp_mp_align_batch): job records and block table, block partials, the jobs' sums
+  DevBuf<unsigned char> b_tab;
+  DevBuf<double> b_part, b_out;
+  PinnedBuf b_h_out;
+  gorio_apd::Pinned pin_tab;
+  int b_rounds = 0, b_launches = 0, b_syncs = 0, b_max_round_launches = 0;  // gorio_apd_gicp_mp_batch_diag
 };
 
 namespace {
@@ -361,106 +419,9 @@ int mp_pass(gorio_apd* h, const float* T12, bool keep_merged, double* sums) {
   return GORIO_OK;
 }
 
-// Eigen::LDLT<6x6>(A).solve(rhs): ldlt6_solve of apd_kernels.hip on the host
-void mp_ldlt6_solve(const double* A_in, const double* rhs, double* x) {
-  double A[36], y[6], col[6];
-  int perm[6];
-  for (int i = 0; i < 36; ++i) A[i] = A_in[i];
-  for (int i = 0; i < 6; ++i) perm[i] = i;
-  for (int k = 0; k < 6; ++k) {
-    int piv = k;
-    double best = std::fabs(A[k * 6 + k]);
-    for (int i = k + 1; i < 6; ++i)
-      if (std::fabs(A[i * 6 + i]) > best) {
-        best = std::fabs(A[i * 6 + i]);
-        piv = i;
-      }
-    if (piv != k) {
-      for (int c = 0; c < 6; ++c) std::swap(A[k * 6 + c], A[piv * 6 + c]);
-      for (int r = 0; r < 6; ++r) std::swap(A[r * 6 + k], A[r * 6 + piv]);
-      std::swap(perm[k], perm[piv]);
-    }
-    const double d = A[k * 6 + k];
-    if (d == 0.0) continue;
-    for (int i = k + 1; i < 6; ++i) col[i] = A[i * 6 + k];
-    for (int i = k + 1; i < 6; ++i) {
-      const double l = col[i] / d;
-      for (int j = k + 1; j <= i; ++j) A[i * 6 + j] -= l * col[j];
-      A[i * 6 + k] = l;
-    }
-    for (int i = k + 1; i < 6; ++i)
-      for (int j = i + 1; j < 6; ++j) A[i * 6 + j] = A[j * 6 + i];
-  }
-  for (int i = 0; i < 6; ++i) y[i] = rhs[perm[i]];
-  for (int i = 0; i < 6; ++i)
-    for (int j = 0; j < i; ++j) y[i] -= A[i * 6 + j] * y[j];
-  for (int i = 0; i < 6; ++i) y[i] = (A[i * 6 + i] != 0.0) ? y[i] / A[i * 6 + i] : 0.0;
-  for (int i = 5; i >= 0; --i)
-    for (int j = i + 1; j < 6; ++j) y[i] -= A[j * 6 + i] * y[j];
-  for (int i = 0; i < 6; ++i) x[perm[i]] = y[i];
-}
-
-// exp: Rodrigues in double, R = I + A K + B K^2 with K = skew(w), K^2 = w w^T - theta^2 I.  theta^2 < 1e-12: A = 1 - theta^2 / 6, B = 1 / 2 -
-// theta^2 / 24; otherwise A = sin(theta) / theta, B = 2 sin^2(theta / 2) / theta^2.  R row-major 3 x 3.
-void mp_exp(const double* w, double* R) {
-  const double th2 = (w[0] * w[0] + w[1] * w[1]) + w[2] * w[2];
-  double A, B;
-  if (th2 < 1e-12) {
-    A = 1.0 - th2 / 6.0;
-    B = 0.5 - th2 / 24.0;
-  } else {
-    const double th = std::sqrt(th2), sh = std::sin(0.5 * th);
-    A = std::sin(th) / th;
-    B = 2.0 * sh * sh / th2;
-  }
-  const double K[9] = {0.0, -w[2], w[1], w[2], 0.0, -w[0], -w[1], w[0], 0.0};
-  for (int r = 0; r < 3; ++r)
-    for (int c = 0; c < 3; ++c) R[r * 3 + c] = ((r == c ? 1.0 : 0.0) + A * K[r * 3 + c]) + B * (w[r] * w[c] - (r == c ? th2 : 0.0));
-}
-
-// log: v = (R32 - R23, R13 - R31, R21 - R12) / 2 = sin(theta) axis, c = (trace - 1) / 2, theta = atan2(|v|, c), w = f v with f = theta /
-// |v|, or 1 + theta^2 / 6 when |v| < 1e-6.  Rotations near pi (|v| small with c < 0) are outside the domain of this class's steps.
-void mp_log(const double* R, double* w) {
-  const double v[3] = {0.5 * (R[7] - R[5]), 0.5 * (R[2] - R[6]), 0.5 * (R[3] - R[1])};
-  const double c = 0.5 * (((R[0] + R[4]) + R[8]) - 1.0);
-  const double s = std::sqrt((v[0] * v[0] + v[1] * v[1]) + v[2] * v[2]);
-  const double th = std::atan2(s, c);
-  const double f = s < 1e-6 ? 1.0 + th * th / 6.0 : th / s;
-  for (int a = 0; a < 3; ++a) w[a] = f * v[a];
-}
-
-// trans of MPI:131-133, 158-160: [float(exp(x.head)) | x.tail], 12 floats
-void mp_trans(const float* x, float* T12) {
-  const double w[3] = {(double)x[0], (double)x[1], (double)x[2]};
-  double R[9];
-  mp_exp(w, R);
-  for (int r = 0; r < 3; ++r) {
-    for (int c = 0; c < 3; ++c) T12[r * 4 + c] = (float)R[r * 3 + c];
-    T12[r * 4 + 3] = x[3 + r];
-  }
-}
-
-// is_converged (MPI:118-127) in float: the scale 1 / epsilon is rounded to float before it multiplies
-bool mp_converged(const float* delta, double rot_eps, double trans_eps) {
-  const double w[3] = {(double)delta[0], (double)delta[1], (double)delta[2]};
-  double R[9];
-  mp_exp(w, R);
-  const float ri = (float)(1.0 / rot_eps), ti = (float)(1.0 / trans_eps);
-  float worst = 0.f;
-  for (int r = 0; r < 3; ++r)
-    for (int c = 0; c < 3; ++c) worst = std::max(worst, ri * std::fabs((float)R[r * 3 + c] - (r == c ? 1.f : 0.f)));
-  for (int a = 0; a < 3; ++a) worst = std::max(worst, ti * std::fabs(delta[3 + a]));
-  return worst < 1.f;
-}
-
-void mp_unpack_H(const double* sums, double* H) {
-  int t = 0;
-  for (int r = 0; r < 6; ++r)
-    for (int c = r; c < 6; ++c) {
-      H[r * 6 + c] = sums[t];
-      H[c * 6 + r] = sums[t++];
-    }
-}
+// the shell -- 6 x 6 LDLT, exp / log, update, convergence, the two deviations -- is the resumable machine of gicp_mp_machine.h
+using gorio_mp::MpMachine;
+using gorio_mp::mp_unpack_H;
 
 int mp_align(gorio_apd* h, const float* guess, float* T_out, double* H_out, int* converged, int* nr_iterations, int* n_linearize) {
   if (!guess || !T_out) return GORIO_ERR_INVALID;
@@ -470,70 +431,137 @@ int mp_align(gorio_apd* h, const float* guess, float* T_out, double* H_out, int*
   if (rc) return rc;
   GicpMpState* m = mp_state(h);
   const gorio_apd_params& p = h->params;
-  float x0[6];
-  {
-    double R[9], w[3];
-    for (int r = 0; r < 3; ++r)
-      for (int c = 0; c < 3; ++c) R[r * 3 + c] = (double)guess[r * 4 + c];
-    mp_log(R, w);
-    for (int a = 0; a < 3; ++a) {
-      x0[a] = (float)w[a];
-      x0[3 + a] = guess[a * 4 + 3];
-    }
-  }
-  bool conv = false;
-  int nr = 0, passes = 0;
-  double H[36];
-  std::memset(H, 0, sizeof(H));
-  for (int i = 0; i < p.max_iterations; ++i) {
-    nr = i;
+  MpMachine mc;  // a batch of one: the machine the rounds of mp_run_batch drive, here over the single kernels
+  mc.begin(guess, p.max_iterations, p.rotation_epsilon, p.transformation_epsilon);
+  while (!mc.done()) {
     float T12[12];
-    mp_trans(x0, T12);
+    mc.next_pose(T12);
     double sums[28];
     rc = mp_pass(h, T12, false, sums);
     if (rc) return rc;
-    ++passes;
     MpClock clock(h);
-    mp_unpack_H(sums, H);
-    if (sums[27] < 1.0) break;  // no source point has a neighbour: nothing to solve (deviation, gorio_apd.h)
-    double dd[6];
-    mp_ldlt6_solve(H, sums + 21, dd);
-    float delta[6];
-    bool finite = true;
-    for (int a = 0; a < 6; ++a) {
-      delta[a] = (float)dd[a];
-      finite = finite && std::isfinite(delta[a]);
-    }
-    if (!finite) break;  // deviation: the reference's solver substitutes a random step
-    {
-      const double nd[3] = {-(double)delta[0], -(double)delta[1], -(double)delta[2]}, xw[3] = {(double)x0[0], (double)x0[1], (double)x0[2]};
-      double Rd[9], Rx[9], Rn[9], w[3];
-      mp_exp(nd, Rd);
-      mp_exp(xw, Rx);
-      for (int r = 0; r < 3; ++r)
-        for (int c = 0; c < 3; ++c) Rn[r * 3 + c] = (Rd[r * 3] * Rx[c] + Rd[r * 3 + 1] * Rx[3 + c]) + Rd[r * 3 + 2] * Rx[6 + c];
-      mp_log(Rn, w);
-      for (int a = 0; a < 3; ++a) {
-        x0[a] = (float)w[a];
-        x0[3 + a] = x0[3 + a] - delta[3 + a];
-      }
-    }
-    const bool done = mp_converged(delta, p.rotation_epsilon, p.transformation_epsilon);
+    mc.consume(sums);
     clock.lap(m->stage_s[3]);
-    if (done) {
-      conv = true;
-      break;
+  }
+  m->passes = mc.pass;
+  mc.results(T_out, m->last_H, converged, nr_iterations, n_linearize);
+  if (H_out) std::memcpy(H_out, m->last_H, sizeof(m->last_H));
+  return GORIO_OK;
+}
+
+// The lock-step rounds of gorio_apd_gicp_mp_align_batch.  Every unfinished handle has one pass pending at its own pose; a round is one
+// query-transform launch over (job, block) entries, the batched radius search (each handle's target through the search state inside the
+// handle, its own radius), one merge-and-linearise launch, one fold launch, one copy back of 28 doubles per pending handle and one
+// synchronisation -- on the stream and with the tables of hs[0].  Two synchronisations per round: the found offsets and the sums.
+int mp_run_batch(gorio_apd** hs, int count, const float* guesses, float* T_out, int* converged, int* nr_iterations) {
+  gorio_apd* lead = hs[0];
+  for (int q = 0; q < count; ++q) {  // preparation is per handle, not per pass
+    gorio_apd* h = hs[q];
+    const int rc = mp_prepare(h);
+    if (rc) {
+      if (h != lead) lead->err = h->err;
+      return rc;
+    }
+    if (h->stream != lead->stream) HIP_TRY(lead, hipStreamSynchronize(h->stream));
+  }
+  GicpMpState* lm = mp_state(lead);
+  size_t max_blk = 0;
+  for (int q = 0; q < count; ++q) max_blk += (size_t)(hs[q]->src->n + 255) / 256;
+  if (max_blk > (size_t)INT_MAX / 32) return fail(lead, GORIO_ERR_INVALID, "gicp_mp_align_batch: too many source points in one batch");
+  const size_t o_blk = sizeof(MpJob) * (size_t)count, tab_bytes = o_blk + sizeof(MpBlockRef) * max_blk, out_bytes = sizeof(double) * 28 * (size_t)count;
+  HIP_TRY(lead, lm->b_tab.reserve(tab_bytes, tab_bytes + tab_bytes / 4));
+  HIP_TRY(lead, lm->b_part.reserve(28 * max_blk, 28 * (max_blk + max_blk / 4)));
+  HIP_TRY(lead, lm->b_out.reserve(28 * (size_t)count, 28 * ((size_t)count + (size_t)count / 4)));
+  HIP_TRY(lead, lm->b_h_out.reserve(out_bytes, out_bytes + out_bytes / 4));
+  std::vector<MpMachine> mc((size_t)count);
+  for (int q = 0; q < count; ++q) {
+    const gorio_apd_params& p = hs[q]->params;
+    mc[q].begin(guesses + (size_t)16 * q, p.max_iterations, p.rotation_epsilon, p.transformation_epsilon);
+  }
+  std::vector<unsigned char> table(tab_bytes);
+  std::vector<SearchBatchJob> sj((size_t)count);
+  std::vector<int> order;
+  order.reserve(count);
+  int rounds = 0, launches = 0, syncs = 0, max_round = 0;
+  for (;;) {
+    order.clear();
+    for (int q = 0; q < count; ++q)
+      if (!mc[q].done()) order.push_back(q);
+    const int njobs = (int)order.size();
+    if (njobs == 0) break;
+    MpJob* const jobs = reinterpret_cast<MpJob*>(table.data());
+    MpBlockRef* const blocks = reinterpret_cast<MpBlockRef*>(table.data() + sizeof(MpJob) * (size_t)njobs);
+    int slot = 0;
+    for (int k = 0; k < njobs; ++k) {
+      gorio_apd* h = hs[order[k]];
+      GicpMpState* m = mp_state(h);
+      const DevCloud& s = *h->src;
+      MpJob& j = jobs[k];
+      std::memset(&j, 0, sizeof(j));
+      j.src_p4 = s.p4;
+      j.src_rec = s.mp_rec;
+      j.q = m->q;
+      j.tgt_rec = h->tgt->mp_rec;
+      j.radius = h->mp_radius;
+      mc[order[k]].next_pose(j.T.m);
+      j.n = s.n;
+      j.n_tgt = h->tgt->n;
+      j.first = slot;
+      j.nblk = (s.n + 255) / 256;
+      for (int b = 0; b < j.nblk; ++b) blocks[slot + b] = MpBlockRef{k, b};  // job < njobs, blk < nblk: what the kernels rely on
+      slot += j.nblk;
+      h->mp_pass_valid = false;
+      h->corr_valid = false;
+      m->merged_valid = false;
+      sj[k] = SearchBatchJob{&m->s, reinterpret_cast<const float*>(m->q.get()), s.n, 16, h->mp_radius, 0, nullptr, 0};
+    }
+    const size_t bytes = sizeof(MpJob) * (size_t)njobs + sizeof(MpBlockRef) * (size_t)slot;  // <= tab_bytes
+    if (int rc = upload_staged(lead, lm->pin_tab, lm->b_tab, table.data(), bytes)) return rc;
+    const MpJob* d_jobs = reinterpret_cast<const MpJob*>(lm->b_tab.get());
+    const MpBlockRef* d_blocks = reinterpret_cast<const MpBlockRef*>(lm->b_tab.get() + sizeof(MpJob) * (size_t)njobs);
+    mp_query_batch_kernel<<<slot, 256, 0, lead->stream>>>(d_jobs, d_blocks);
+    HIP_TRY(lead, hipGetLastError());
+    SearchBatchStats st;
+    if (int rc = search_radius_batch_core(sj.data(), njobs, &st)) return fail(lead, rc, "FastGICPMultiPoints: " + g_search_err);
+    for (int k = 0; k < njobs; ++k) {  // the CSR every handle's search state now holds (the search may have moved its buffers)
+      GicpMpState* m = hs[order[k]]->mp.get();
+      jobs[k].offs = m->s.d_kept_offs;
+      jobs[k].idx = m->s.d_ridx;
+      jobs[k].sqd = m->s.d_rsqd;
+    }
+    if (int rc = upload_staged(lead, lm->pin_tab, lm->b_tab, table.data(), sizeof(MpJob) * (size_t)njobs)) return rc;
+    mp_linearize_batch_kernel<<<slot, 256, 0, lead->stream>>>(d_jobs, d_blocks, lm->b_part);
+    mp_fold_batch_kernel<<<njobs, 64, 0, lead->stream>>>(d_jobs, lm->b_part, lm->b_out);
+    HIP_TRY(lead, hipGetLastError());
+    HIP_TRY(lead, hipMemcpyAsync(lm->b_h_out.get(), lm->b_out, sizeof(double) * 28 * (size_t)njobs, hipMemcpyDeviceToHost, lead->stream));
+    HIP_TRY(lead, hipStreamSynchronize(lead->stream));
+    const int round_launches = 3 + st.launches;
+    launches += round_launches;
+    max_round = std::max(max_round, round_launches);
+    syncs += 1 + st.syncs;
+    ++rounds;
+    const double* sums = static_cast<const double*>(lm->b_h_out.get());
+    for (int k = 0; k < njobs; ++k) {
+      gorio_apd* h = hs[order[k]];
+      GicpMpState* m = h->mp.get();
+      const double* sk = sums + (size_t)28 * k;
+      m->pass_n = h->src->n;
+      m->total = sj[k].total;
+      m->used = (int)sk[27];
+      h->mp_pass_valid = true;
+      h->corr_valid = true;
+      h->omega_valid = false;
+      mc[order[k]].consume(sk);
     }
   }
-  m->passes = passes;
-  float T12[12];
-  mp_trans(x0, T12);
-  for (int i = 0; i < 12; ++i) T_out[i] = T12[i];
-  T_out[12] = 0.f; T_out[13] = 0.f; T_out[14] = 0.f; T_out[15] = 1.f;
-  if (H_out) std::memcpy(H_out, H, sizeof(H));
-  if (converged) *converged = conv ? 1 : 0;
-  if (nr_iterations) *nr_iterations = nr;
-  if (n_linearize) *n_linearize = passes;
+  for (int q = 0; q < count; ++q) {
+    mp_state(hs[q])->passes = mc[q].pass;
+    mc[q].results(T_out + (size_t)16 * q, mp_state(hs[q])->last_H, converged ? converged + q : nullptr, nr_iterations ? nr_iterations + q : nullptr, nullptr);
+  }
+  lm->b_rounds = rounds;
+  lm->b_launches = launches;
+  lm->b_syncs = syncs;
+  lm->b_max_round_launches = max_round;
   return GORIO_OK;
 }
 
@@ -627,6 +655,71 @@ int gorio_apd_gicp_mp_get_merged(gorio_apd_t* h, int capacity, int* n, float* me
       for (int t = 0; t < 6; ++t) cov_B[6 * (size_t)i + t] = r[3 + t];
     if (used) used[i] = r[9] != 0.f ? 1 : 0;
   }
+  return GORIO_OK;
+}
+
+int gorio_apd_gicp_mp_align_batch(gorio_apd_t** handles, int count, const float* guesses, float* T_out, int* converged, int* nr_iterations) {
+  if (count == 0) return GORIO_OK;
+  if (count < 0 || !handles || !guesses || !T_out) return GORIO_ERR_INVALID;
+  for (int q = 0; q < count; ++q)
+    if (!handles[q]) return handles[0] ? fail(handles[0], GORIO_ERR_INVALID, "gicp_mp_align_batch: handle " + std::to_string(q) + " is null") : GORIO_ERR_INVALID;
+  gorio_apd* lead = handles[0];
+  // ---- validation: nothing is built, allocated or launched before every handle has passed
+  auto refuse = [&](int q, int code, const std::string& why) { return fail(lead, code, "gicp_mp_align_batch: handle " + std::to_string(q) + ": " + why); };
+  std::unordered_set<gorio_apd*> distinct;
+  for (int q = 0; q < count; ++q) {
+    gorio_apd* h = handles[q];
+    if (h->device != lead->device) return refuse(q, GORIO_ERR_INVALID, "all handles of a batch must live on one device");
+    if (!distinct.insert(h).second) return refuse(q, GORIO_ERR_INVALID, "the same handle appears twice in a batch (its buffers would be raced on)");
+    if (!is_mp(h)) return refuse(q, GORIO_ERR_STATE, "the handle is not in FastGICPMultiPoints mode (gorio_apd_set_method)");
+  }
+  for (int q = 0; q < count; ++q) {
+    gorio_apd* h = handles[q];
+    const std::string kept = h->err;
+    const int rc = mp_ready(h);
+    if (rc) {
+      const std::string why = h->err;
+      if (h != lead) h->err = kept;
+      return refuse(q, rc, why);
+    }
+  }
+  // members that share a cloud must make its covariances by one rule: the single align refuses the second of them by the cloud's state, which
+  // inside a batch the first member's preparation would only set after this check
+  std::unordered_map<const DevCloud*, int> owner;
+  for (int q = 0; q < count; ++q) {
+    gorio_apd* h = handles[q];
+    for (const DevCloud* c : {h->src.get(), h->tgt.get()}) {
+      const auto it = owner.find(c);
+      if (it == owner.end()) {
+        owner.emplace(c, q);
+        continue;
+      }
+      const gorio_apd_params &a = handles[it->second]->params, &b = h->params;
+      if (a.k_correspondences != b.k_correspondences || a.regularization != b.regularization)
+        return refuse(q, GORIO_ERR_INVALID, "it shares a cloud with handle " + std::to_string(it->second) + " but has another k_correspondences or regularization");
+    }
+  }
+  HIP_TRY(lead, hipSetDevice(lead->device));
+  return mp_run_batch(handles, count, guesses, T_out, converged, nr_iterations);
+}
+
+int gorio_apd_gicp_mp_batch_diag(const gorio_apd_t* lead, int* rounds, int* launches, int* syncs, int* max_round_launches) {
+  if (!lead) return GORIO_ERR_INVALID;
+  if (!is_mp(lead)) return fail(const_cast<gorio_apd_t*>(lead), GORIO_ERR_STATE, "gicp_mp_batch_diag: the handle is not in FastGICPMultiPoints mode (gorio_apd_set_method)");
+  const GicpMpState* m = lead->mp.get();
+  if (rounds) *rounds = m ? m->b_rounds : 0;
+  if (launches) *launches = m ? m->b_launches : 0;
+  if (syncs) *syncs = m ? m->b_syncs : 0;
+  if (max_round_launches) *max_round_launches = m ? m->b_max_round_launches : 0;
+  return GORIO_OK;
+}
+
+int gorio_apd_gicp_mp_last_hessian(const gorio_apd_t* h, double* H36) {
+  if (!h || !H36) return GORIO_ERR_INVALID;
+  if (!is_mp(h)) return fail(const_cast<gorio_apd_t*>(h), GORIO_ERR_STATE, "gicp_mp_last_hessian: the handle is not in FastGICPMultiPoints mode (gorio_apd_set_method)");
+  const GicpMpState* m = h->mp.get();
+  if (m) std::memcpy(H36, m->last_H, sizeof(double) * 36);
+  else std::memset(H36, 0, sizeof(double) * 36);
   return GORIO_OK;
 }
 

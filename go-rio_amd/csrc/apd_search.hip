@@ -11,6 +11,8 @@
 //   search_scan_kernel           exclusive scans of the found and the kept counts, one workgroup
 //   search_segment_sort_kernel   sorts every segment of at most kSegLdsMax keys inside LDS and emits its kept part
 //   search_long_*_kernel         long segments: into padded slots, enqueue_tiled_sort over all of them at once, emit
+//   search_*_batch_kernel        the radius kernels once more over a JOB TABLE (search_radius_batch_core, gorio_search_radius_batch): every
+//                                kernel above keeps its body in a __device__ per-workgroup function that its batched twin calls too
 //
 // Exactness is the argument of apd_index.hip: the lower bound of a box is evaluated with the float expression of a point distance, so
 // bound <= distance holds in float arithmetic and a tile is skipped only when no point of it can enter the result.  The k-NN list holds
@@ -41,9 +43,8 @@ __global__ __launch_bounds__(256) void search_finite_kernel(const float* __restr
 
 // grid: ceil(npow2 / 256), block 256.  bb: the cloud's bounding box as run_index_build left it (ordered encodings, IndexJob::bb).
 // A non-finite query takes the largest code: such queries gather at the tail of the order, before the padding keys (~0).
-__global__ __launch_bounds__(256) void search_query_keys_kernel(const float* __restrict__ q, int stride_f, int nq, int npow2, const unsigned int* __restrict__ bb,
-                                                                unsigned long long* __restrict__ keys) {
-  const int i = blockIdx.x * 256 + threadIdx.x;
+__device__ __forceinline__ void search_query_key(const float* __restrict__ q, int stride_f, int nq, int npow2, const unsigned int* __restrict__ bb,
+                                                 unsigned long long* __restrict__ keys, int i) {
   if (i >= npow2) return;
   if (i >= nq) {
     keys[i] = ~0ull;
@@ -69,6 +70,10 @@ __global__ __launch_bounds__(256) void search_query_keys_kernel(const float* __r
     code = spread11(c[0]) | (spread11(c[1]) << 1) | (spread11(c[2]) << 2);
   }
   keys[i] = (code << 31) | (unsigned long long)i;
+}
+__global__ __launch_bounds__(256) void search_query_keys_kernel(const float* __restrict__ q, int stride_f, int nq, int npow2, const unsigned int* __restrict__ bb,
+                                                                unsigned long long* __restrict__ keys) {
+  search_query_key(q, stride_f, nq, npow2, bb, keys, blockIdx.x * 256 + threadIdx.x);
 }
 
 // the query of sorted position p.  exists: p is a query of the call; live: it is one with finite coordinates (the cloud's own points
@@ -215,11 +220,13 @@ __global__ __launch_bounds__(256) void search_knn_empty_kernel(int nq, int k, in
 
 // ---- radius.  MODE 0: found[query] = neighbours with d < r2; MODE 1: their keys to keys_out[found_offs[query] ...] in the order met.
 // grid: ceil(queries / 64), block 64.
+// The work of ONE wave (= one workgroup): queries [64 wave, 64 wave + 64) of the call.  search_radius_kernel runs it for a single call,
+// search_radius_batch_kernel for a job of a batch: one body, one arithmetic, the same bits.
 template <int MODE>
-__global__ __launch_bounds__(64) void search_radius_kernel(SearchIndex si, SearchQueries sq, float r2, int* __restrict__ found, const long long* __restrict__ found_offs,
-                                                           unsigned long long* __restrict__ keys_out) {
+__device__ __forceinline__ void search_radius_wave(const SearchIndex& si, const SearchQueries& sq, float r2, int wave, int* __restrict__ found,
+                                                   const long long* __restrict__ found_offs, unsigned long long* __restrict__ keys_out) {
   const int lane = threadIdx.x;
-  const int p = blockIdx.x * 64 + lane;
+  const int p = wave * 64 + lane;
   const LaneQuery q = load_query(si, sq, p);
   float qlo[3], qhi[3];
   wave_query_box(q, qlo, qhi);
@@ -260,11 +267,16 @@ __global__ __launch_bounds__(64) void search_radius_kernel(SearchIndex si, Searc
   }
   if (MODE == 0 && q.exists) found[q.qi] = cnt;
 }
+template <int MODE>
+__global__ __launch_bounds__(64) void search_radius_kernel(SearchIndex si, SearchQueries sq, float r2, int* __restrict__ found, const long long* __restrict__ found_offs,
+                                                           unsigned long long* __restrict__ keys_out) {
+  search_radius_wave<MODE>(si, sq, r2, blockIdx.x, found, found_offs, keys_out);
+}
 
 // Exclusive scans of found[] and of kept[] = min(found, max_nn) (max_nn > 0), nq + 1 entries each; what
 // search_plan::offsets_from_counts computes on the host.  ONE workgroup: a thread sums a contiguous share of the queries, the 1024 sums
 // are scanned in LDS, the thread then writes its share.  grid: 1, block 1024.
-__global__ __launch_bounds__(1024) void search_scan_kernel(const int* __restrict__ found, int nq, int max_nn, long long* __restrict__ found_offs, long long* __restrict__ kept_offs) {
+__device__ __forceinline__ void search_scan_block(const int* __restrict__ found, int nq, int max_nn, long long* __restrict__ found_offs, long long* __restrict__ kept_offs) {
   __shared__ long long sf[2][1024], sk[2][1024];
   const int tid = threadIdx.x;
   const int share = (nq + 1023) / 1024;
@@ -299,13 +311,16 @@ __global__ __launch_bounds__(1024) void search_scan_kernel(const int* __restrict
     kept_offs[nq] = sk[cur][1023];
   }
 }
+__global__ __launch_bounds__(1024) void search_scan_kernel(const int* __restrict__ found, int nq, int max_nn, long long* __restrict__ found_offs, long long* __restrict__ kept_offs) {
+  search_scan_block(found, nq, max_nn, found_offs, kept_offs);
+}
 
 // One workgroup per query: a segment of 1 .. kSegLdsMax found keys is sorted ascending in LDS (bitonic, padded to a power of two with
 // ~0) and its first kept keys are emitted as (index, distance).  Longer segments are left to the long path.  grid: nq, block 256.
-__global__ __launch_bounds__(256) void search_segment_sort_kernel(const unsigned long long* __restrict__ keys, const long long* __restrict__ found_offs,
-                                                                  const long long* __restrict__ kept_offs, int* __restrict__ idx_out, float* __restrict__ sqd_out) {
+__device__ __forceinline__ void search_segment_sort_block(const unsigned long long* __restrict__ keys, const long long* __restrict__ found_offs,
+                                                          const long long* __restrict__ kept_offs, int* __restrict__ idx_out, float* __restrict__ sqd_out, int q) {
   __shared__ unsigned long long s[search_plan::kSegLdsMax];
-  const int q = blockIdx.x, tid = threadIdx.x;
+  const int tid = threadIdx.x;
   const long long b = found_offs[q];
   const long long len64 = found_offs[q + 1] - b;
   if (len64 <= 0 || len64 > search_plan::kSegLdsMax) return;  // workgroup-uniform
@@ -333,12 +348,19 @@ __global__ __launch_bounds__(256) void search_segment_sort_kernel(const unsigned
     sqd_out[ob + i] = __uint_as_float((unsigned int)(s[i] >> 32));
   }
 }
+__global__ __launch_bounds__(256) void search_segment_sort_kernel(const unsigned long long* __restrict__ keys, const long long* __restrict__ found_offs,
+                                                                  const long long* __restrict__ kept_offs, int* __restrict__ idx_out, float* __restrict__ sqd_out) {
+  search_segment_sort_block(keys, found_offs, kept_offs, idx_out, sqd_out, blockIdx.x);
+}
 
 // long segments (search_plan::LongSeg): into their slots, padded with ~0.  grid: (blocks, segments), block 256
+__device__ __forceinline__ void search_long_pad_seg(const search_plan::LongSeg& sg, const unsigned long long* __restrict__ keys, unsigned long long* __restrict__ slots) {
+  for (int i = blockIdx.x * 256 + threadIdx.x; i < sg.npow2; i += gridDim.x * 256) slots[sg.slot + i] = i < sg.len ? keys[sg.src + i] : ~0ull;
+}
 __global__ __launch_bounds__(256) void search_long_pad_kernel(const search_plan::LongSeg* __restrict__ segs, const unsigned long long* __restrict__ keys,
                                                               unsigned long long* __restrict__ slots) {
   const search_plan::LongSeg sg = segs[blockIdx.y];
-  for (int i = blockIdx.x * 256 + threadIdx.x; i < sg.npow2; i += gridDim.x * 256) slots[sg.slot + i] = i < sg.len ? keys[sg.src + i] : ~0ull;
+  search_long_pad_seg(sg, keys, slots);
 }
 // the key arrays enqueue_tiled_sort sorts: the slot of segment blockIdx.y
 struct LongSegKeys {
@@ -347,14 +369,108 @@ struct LongSegKeys {
   __device__ SortKeys get() const { return SortKeys{slots + segs[blockIdx.y].slot, segs[blockIdx.y].npow2}; }
 };
 // grid: (blocks, segments), block 256
-__global__ __launch_bounds__(256) void search_long_emit_kernel(const search_plan::LongSeg* __restrict__ segs, const unsigned long long* __restrict__ slots, int* __restrict__ idx_out,
-                                                               float* __restrict__ sqd_out) {
-  const search_plan::LongSeg sg = segs[blockIdx.y];
+__device__ __forceinline__ void search_long_emit_seg(const search_plan::LongSeg& sg, const unsigned long long* __restrict__ slots, int* __restrict__ idx_out,
+                                                     float* __restrict__ sqd_out) {
   for (int i = blockIdx.x * 256 + threadIdx.x; i < sg.kept; i += gridDim.x * 256) {
     const unsigned long long key = slots[sg.slot + i];
     idx_out[sg.out + i] = (int)(unsigned int)(key & 0xffffffffull);
     sqd_out[sg.out + i] = __uint_as_float((unsigned int)(key >> 32));
   }
+}
+__global__ __launch_bounds__(256) void search_long_emit_kernel(const search_plan::LongSeg* __restrict__ segs, const unsigned long long* __restrict__ slots, int* __restrict__ idx_out,
+                                                               float* __restrict__ sqd_out) {
+  const search_plan::LongSeg sg = segs[blockIdx.y];
+  search_long_emit_seg(sg, slots, idx_out, sqd_out);
+}
+
+// ---- the batched radius search (search_radius_batch_core): the launches above once more, each over the jobs of a table.  A workgroup
+// finds its job through tables that every lane reads at the same address, read through the scalar data path (load_uniform, scalar_ip): the
+// job's record lands in SGPRs as the arguments of the single kernels do, and the bodies are the single kernels' bodies.
+struct SearchJob {
+  SearchIndex si;
+  SearchQueries sq;
+  const unsigned int* bb;      // the cloud's bounding box (query keys)
+  unsigned long long* qkeys;   // [npow2] the job's own query keys (= sq.keys); null for self queries
+  int* found;                  // [nq]
+  long long* found_offs;       // [nq + 1] the job's part of the batch's shared found offsets
+  long long* kept_offs;        // [nq + 1] the job's own
+  unsigned long long* keys;    // the found keys, the job's own (set after the plan)
+  int* ridx;                   // the result, the job's own (set after the plan)
+  float* rsqd;
+  float r2;
+  int max_nn;
+  int npow2;                   // size of the query-key segment (0: self queries)
+  int nq;                      // 0: the job takes part in no launch (no query, or an empty cloud)
+};
+static_assert(sizeof(SearchJob) % 8 == 0, "the tables behind the job records are 8-byte aligned");
+
+// *p through scalar loads: p must be the same in every lane of the wave
+template <class T>
+__device__ __forceinline__ T load_uniform(const T* p) {
+  static_assert(sizeof(T) % 4 == 0 && std::is_trivially_copyable<T>::value, "words of a plain record");
+  union U {
+    T v;
+    int w[sizeof(T) / 4];
+    __device__ U() {}
+  } u;
+  const scalar_ip s = (scalar_ip) reinterpret_cast<const int*>(p);
+#pragma unroll
+  for (int i = 0; i < (int)(sizeof(T) / 4); ++i) u.w[i] = s[i];
+  return u.v;
+}
+
+// grid: the key segments' 256-key blocks added up (BatchLayout::key_items), block 256
+__global__ __launch_bounds__(256) void search_query_keys_batch_kernel(const SearchJob* __restrict__ jobs, const int* __restrict__ key_first, const int* __restrict__ key_jobs,
+                                                                      int nsegs) {
+  const scalar_ip kf = (scalar_ip)key_first;
+  const int sg = search_plan::job_of(kf, nsegs, (int)blockIdx.x);
+  const SearchJob j = load_uniform(jobs + ((scalar_ip)key_jobs)[sg]);
+  search_query_key(j.sq.q, j.sq.stride_f, j.sq.nq, j.npow2, j.bb, j.qkeys, (int)(blockIdx.x - kf[sg]) * 256 + (int)threadIdx.x);
+}
+// the key arrays of the one tiled sort over all jobs' query keys: segment blockIdx.y
+struct BatchQueryKeys {
+  const SearchJob* jobs;
+  const int* key_jobs;
+  __device__ SortKeys get() const {
+    const SearchJob* j = jobs + ((scalar_ip)key_jobs)[blockIdx.y];
+    return SortKeys{j->qkeys, j->npow2};
+  }
+};
+// grid: the jobs' waves added up, block 64
+template <int MODE>
+__global__ __launch_bounds__(64) void search_radius_batch_kernel(const SearchJob* __restrict__ jobs, const search_plan::WaveRef* __restrict__ wave_tab) {
+  const search_plan::WaveRef w = load_uniform(wave_tab + blockIdx.x);
+  const SearchJob j = load_uniform(jobs + w.job);
+  search_radius_wave<MODE>(j.si, j.sq, j.r2, w.wave, j.found, j.found_offs, j.keys);
+}
+// grid: the jobs, block 1024
+__global__ __launch_bounds__(1024) void search_scan_batch_kernel(const SearchJob* __restrict__ jobs) {
+  const SearchJob j = load_uniform(jobs + blockIdx.x);
+  if (j.nq == 0) return;  // workgroup-uniform
+  search_scan_block(j.found, j.nq, j.max_nn, j.found_offs, j.kept_offs);
+}
+// grid: the jobs' queries added up, block 256
+__global__ __launch_bounds__(256) void search_segment_sort_batch_kernel(const SearchJob* __restrict__ jobs, const int* __restrict__ query_first, int count) {
+  const scalar_ip qf = (scalar_ip)query_first;
+  const int k = search_plan::job_of(qf, count, (int)blockIdx.x);
+  const SearchJob j = load_uniform(jobs + k);
+  search_segment_sort_block(j.keys, j.found_offs, j.kept_offs, j.ridx, j.rsqd, (int)blockIdx.x - qf[k]);
+}
+// grid: (blocks, segments), block 256
+__global__ __launch_bounds__(256) void search_long_pad_batch_kernel(const SearchJob* __restrict__ jobs, const search_plan::BatchLongSeg* __restrict__ segs,
+                                                                    unsigned long long* __restrict__ slots) {
+  const search_plan::BatchLongSeg sg = load_uniform(segs + blockIdx.y);
+  search_long_pad_seg(sg.seg, jobs[sg.job].keys, slots);
+}
+struct BatchLongSegKeys {
+  const search_plan::BatchLongSeg* segs;
+  unsigned long long* slots;
+  __device__ SortKeys get() const { return SortKeys{slots + segs[blockIdx.y].seg.slot, segs[blockIdx.y].seg.npow2}; }
+};
+__global__ __launch_bounds__(256) void search_long_emit_batch_kernel(const SearchJob* __restrict__ jobs, const search_plan::BatchLongSeg* __restrict__ segs,
+                                                                     const unsigned long long* __restrict__ slots) {
+  const search_plan::BatchLongSeg sg = load_uniform(segs + blockIdx.y);
+  search_long_emit_seg(sg.seg, slots, jobs[sg.job].ridx, jobs[sg.job].rsqd);
 }
 
 }  // namespace gorio
@@ -384,6 +500,13 @@ struct gorio_search_handle {
   bool r_valid = false;
   int r_nq = 0;
   std::vector<long long> r_offs;  // kept offsets of the result held, nq + 1
+  // a batch this state LEADS (search_radius_batch_core): the job records and tables, the found offsets of all jobs, the merged long segments
+  // (their slots are d_slots)
+  DevBuf<unsigned char> b_tab;
+  DevBuf<long long> b_found_offs;
+  DevBuf<search_plan::BatchLongSeg> b_segs;
+  gorio_apd::Pinned pin_tab, pin_segs;
+  PinnedBuf b_h_offs;
 };
 
 namespace {
@@ -573,6 +696,193 @@ int search_radius_core(gorio_search_handle* s, const float* d_q, int nq, int str
   return GORIO_OK;
 }
 
+// ---- the batched radius search: `count` calls of search_radius_core, each against its own state, run by ONE set of launches on the stream
+// of job 0.  Launches and synchronisations do not grow with count: query keys (one launch + one tiled sort over the jobs' segments), count,
+// scan, ONE copy back of all found offsets + one synchronisation, fill, segment sort, and for the long segments of all jobs one table, one
+// pad launch, one tiled sort, one emit launch.  Every job's result is bit for bit that of search_radius_core for it alone: the kernels run
+// the single kernels' bodies over the job's own buffers.
+struct SearchBatchJob {
+  gorio_search_handle* s;
+  const float* d_q;  // device; null = the cloud's own points
+  int nq, stride_bytes;
+  double radius;
+  int max_nn;
+  int* count_out;    // host, may be null
+  long long total;   // out
+};
+struct SearchBatchStats {
+  int launches = 0, syncs = 0;
+};
+
+int tiled_sort_launches(int max_pow2) {
+  int n = 1;
+  for (int k = 2 * kSortTile; k <= max_pow2; k <<= 1) {
+    for (int j = k >> 1; j >= kSortTile; j >>= 1) ++n;
+    ++n;
+  }
+  return n;
+}
+
+int search_upload_staged(hipStream_t stream, gorio_apd::Pinned& b, void* dst, const void* src, size_t bytes) {
+  if (b.pending) {
+    GORIO_HIP_CHECK(search_fail, hipEventSynchronize(b.ev));
+    b.pending = false;
+  }
+  GORIO_HIP_CHECK(search_fail, b.buf.reserve(bytes, bytes + bytes / 2 + 256));
+  if (!b.ev) GORIO_HIP_CHECK(search_fail, hipEventCreateWithFlags(&b.ev, hipEventDisableTiming));
+  std::memcpy(b.buf, src, bytes);
+  GORIO_HIP_CHECK(search_fail, hipMemcpyAsync(dst, b.buf, bytes, hipMemcpyHostToDevice, stream));
+  GORIO_HIP_CHECK(search_fail, hipEventRecord(b.ev, stream));
+  b.pending = true;
+  return GORIO_OK;
+}
+
+int search_radius_batch_core(SearchBatchJob* jobs, int count, SearchBatchStats* stats) {
+  SearchBatchStats st;
+  for (int j = 0; j < count; ++j) jobs[j].total = 0;
+  if (count <= 0) return GORIO_OK;
+  gorio_search_handle* lead = jobs[0].s;
+  hipStream_t stream = lead->up->stream;
+  // ---- the layout: which job owns which wave, query, offset and key segment
+  std::vector<search_plan::BatchJobShape> shapes((size_t)count);
+  for (int j = 0; j < count; ++j) shapes[j] = search_plan::BatchJobShape{jobs[j].nq, jobs[j].d_q == nullptr, jobs[j].nq > 0 && search_cloud_n(jobs[j].s) > 0};
+  search_plan::BatchLayout lay;
+  if (!search_plan::make_batch_layout(shapes.data(), count, lay)) return search_fail(GORIO_ERR_INVALID, "radius_batch: too many queries in one batch");
+  const int n_waves = lay.wave_first[count], n_queries = lay.query_first[count], n_segs = (int)lay.key_jobs.size();
+  const size_t n_offs = (size_t)lay.offs_first[count];
+  std::vector<search_plan::Plan> plans((size_t)count);
+  std::vector<std::vector<long long>> koffs((size_t)count);
+  if (n_waves > 0) {
+    // ---- the table: job records, wave table, query_first, key_first, key_jobs
+    const size_t o_wave = sizeof(SearchJob) * (size_t)count, o_qf = o_wave + sizeof(search_plan::WaveRef) * (size_t)n_waves, o_kf = o_qf + sizeof(int) * ((size_t)count + 1),
+                 o_kj = o_kf + sizeof(int) * ((size_t)n_segs + 1), tab_bytes = o_kj + sizeof(int) * (size_t)n_segs;
+    GORIO_HIP_CHECK(search_fail, lead->b_tab.reserve(tab_bytes, tab_bytes + tab_bytes / 4 + 256));
+    GORIO_HIP_CHECK(search_fail, lead->b_found_offs.reserve(n_offs, search_plan::grown(n_offs)));
+    GORIO_HIP_CHECK(search_fail, lead->b_h_offs.reserve(sizeof(long long) * n_offs, sizeof(long long) * search_plan::grown(n_offs)));
+    std::vector<unsigned char> tab(tab_bytes);
+    SearchJob* const rec = reinterpret_cast<SearchJob*>(tab.data());
+    std::memset(tab.data(), 0, tab_bytes);
+    for (int j = 0; j < count; ++j) {
+      if (!shapes[j].active) continue;
+      gorio_search_handle* s = jobs[j].s;
+      const int nq = jobs[j].nq;
+      const DevCloud& c = search_cloud(s);
+      SearchJob& r = rec[j];
+      r.si = c.index_view();
+      if (shapes[j].self) {
+        r.sq = SearchQueries{nullptr, nullptr, 0, c.n};
+      } else {
+        r.npow2 = search_plan::key_pow2(nq);
+        GORIO_HIP_CHECK(search_fail, s->d_qkeys.reserve((size_t)r.npow2));
+        r.sq = SearchQueries{jobs[j].d_q, s->d_qkeys, jobs[j].stride_bytes / 4, nq};
+        r.qkeys = s->d_qkeys;
+      }
+      const size_t qcap = search_plan::grown((size_t)nq + 1);
+      GORIO_HIP_CHECK(search_fail, reserve_group(s->rq_cap, (size_t)nq + 1, qcap, s->d_found, qcap, s->d_found_offs, qcap, s->d_kept_offs, qcap));
+      r.bb = c.bb;
+      r.found = s->d_found;
+      r.found_offs = lead->b_found_offs + lay.offs_first[j];
+      r.kept_offs = s->d_kept_offs;
+      r.r2 = (float)(jobs[j].radius * jobs[j].radius);
+      r.max_nn = jobs[j].max_nn;
+      r.nq = nq;
+    }
+    std::memcpy(tab.data() + o_wave, lay.wave_tab.data(), sizeof(search_plan::WaveRef) * (size_t)n_waves);
+    std::memcpy(tab.data() + o_qf, lay.query_first.data(), sizeof(int) * ((size_t)count + 1));
+    std::memcpy(tab.data() + o_kf, lay.key_first.data(), sizeof(int) * ((size_t)n_segs + 1));
+    if (n_segs > 0) std::memcpy(tab.data() + o_kj, lay.key_jobs.data(), sizeof(int) * (size_t)n_segs);
+    if (int rc = search_upload_staged(stream, lead->pin_tab, lead->b_tab, tab.data(), tab_bytes)) return rc;
+    const unsigned char* d_tab = lead->b_tab;
+    const SearchJob* d_jobs = reinterpret_cast<const SearchJob*>(d_tab);
+    const search_plan::WaveRef* d_wave = reinterpret_cast<const search_plan::WaveRef*>(d_tab + o_wave);
+    const int* d_qf = reinterpret_cast<const int*>(d_tab + o_qf);
+    const int* d_kf = reinterpret_cast<const int*>(d_tab + o_kf);
+    const int* d_kj = reinterpret_cast<const int*>(d_tab + o_kj);
+    if (n_segs > 0) {
+      search_query_keys_batch_kernel<<<(unsigned)lay.key_items, 256, 0, stream>>>(d_jobs, d_kf, d_kj, n_segs);
+      enqueue_tiled_sort(stream, BatchQueryKeys{d_jobs, d_kj}, n_segs, lay.max_key_pow2);
+      st.launches += 1 + tiled_sort_launches(lay.max_key_pow2);
+    }
+    search_radius_batch_kernel<0><<<n_waves, 64, 0, stream>>>(d_jobs, d_wave);
+    search_scan_batch_kernel<<<count, 1024, 0, stream>>>(d_jobs);
+    st.launches += 2;
+    GORIO_HIP_CHECK(search_fail, hipGetLastError());
+    long long* const foffs = static_cast<long long*>(lead->b_h_offs.get());
+    GORIO_HIP_CHECK(search_fail, hipMemcpyAsync(foffs, lead->b_found_offs, sizeof(long long) * n_offs, hipMemcpyDeviceToHost, stream));
+    GORIO_HIP_CHECK(search_fail, hipStreamSynchronize(stream));
+    ++st.syncs;
+    // ---- the plans.  Nothing of any job's held result is replaced before every job has passed.
+    for (int j = 0; j < count; ++j) {
+      if (!shapes[j].active) continue;
+      const long long* fo = foffs + lay.offs_first[j];
+      const int nq = jobs[j].nq;
+      if (fo[nq] > search_plan::kMaxTotal) return search_fail(GORIO_ERR_UNSUPPORTED, "radius_batch: job " + std::to_string(j) + ": more than 2^31 - 1 neighbours found");
+      if (!search_plan::make_plan(fo, nq, jobs[j].max_nn, plans[j]))
+        return search_fail(GORIO_ERR_UNSUPPORTED, "radius_batch: job " + std::to_string(j) + ": the neighbours found cannot be planned (more than 2^31 - 1, or a segment too long to sort)");
+    }
+    search_plan::BatchLongPlan lp;
+    search_plan::merge_long_segs(plans.data(), count, lp);
+    bool any_found = false;
+    for (int j = 0; j < count; ++j) {
+      if (!shapes[j].active) continue;
+      gorio_search_handle* s = jobs[j].s;
+      const long long* fo = foffs + lay.offs_first[j];
+      const int nq = jobs[j].nq;
+      std::vector<int> cnt((size_t)nq);
+      std::vector<long long> f2((size_t)nq + 1);
+      koffs[j].resize((size_t)nq + 1);
+      for (int q = 0; q < nq; ++q) cnt[q] = (int)(fo[q + 1] - fo[q]);
+      search_plan::offsets_from_counts(cnt.data(), nq, jobs[j].max_nn, f2.data(), koffs[j].data());
+      const size_t found = (size_t)plans[j].found_total, kept = (size_t)plans[j].kept_total;
+      if (found == 0) continue;
+      any_found = true;
+      GORIO_HIP_CHECK(search_fail, s->d_keys.reserve(found, search_plan::grown(found)));
+      s->r_valid = false;  // from here on this job's held result is being replaced
+      GORIO_HIP_CHECK(search_fail, reserve_group(s->r_cap, kept, search_plan::grown(kept), s->d_ridx, search_plan::grown(kept), s->d_rsqd, search_plan::grown(kept)));
+      rec[j].keys = s->d_keys;
+      rec[j].ridx = s->d_ridx;
+      rec[j].rsqd = s->d_rsqd;
+    }
+    if (any_found) {
+      // the job records once more, now with the buffers the totals sized
+      if (int rc = search_upload_staged(stream, lead->pin_tab, lead->b_tab, tab.data(), o_wave)) return rc;
+      search_radius_batch_kernel<1><<<n_waves, 64, 0, stream>>>(d_jobs, d_wave);
+      search_segment_sort_batch_kernel<<<n_queries, 256, 0, stream>>>(d_jobs, d_qf, count);
+      st.launches += 2;
+      GORIO_HIP_CHECK(search_fail, hipGetLastError());
+      if (!lp.segs.empty()) {
+        const int nl = (int)lp.segs.size();
+        GORIO_HIP_CHECK(search_fail, lead->b_segs.reserve((size_t)nl, search_plan::grown((size_t)nl)));
+        GORIO_HIP_CHECK(search_fail, lead->d_slots.reserve((size_t)lp.slot_keys, search_plan::grown((size_t)lp.slot_keys)));
+        if (int rc = search_upload_staged(stream, lead->pin_segs, lead->b_segs, lp.segs.data(), sizeof(search_plan::BatchLongSeg) * (size_t)nl)) return rc;
+        const dim3 grid((unsigned)std::min(64, (lp.max_pow2 + 255) / 256), (unsigned)nl);
+        search_long_pad_batch_kernel<<<grid, 256, 0, stream>>>(d_jobs, lead->b_segs, lead->d_slots);
+        enqueue_tiled_sort(stream, BatchLongSegKeys{lead->b_segs, lead->d_slots}, nl, lp.max_pow2);
+        search_long_emit_batch_kernel<<<grid, 256, 0, stream>>>(d_jobs, lead->b_segs, lead->d_slots);
+        st.launches += 2 + tiled_sort_launches(lp.max_pow2);
+        GORIO_HIP_CHECK(search_fail, hipGetLastError());
+      }
+    }
+  }
+  // ---- every job's result becomes the one its state holds
+  for (int j = 0; j < count; ++j) {
+    gorio_search_handle* s = jobs[j].s;
+    const int nq = jobs[j].nq;
+    if (!shapes[j].active) koffs[j].assign((size_t)nq + 1, 0);
+    if (jobs[j].count_out)
+      for (int q = 0; q < nq; ++q) jobs[j].count_out[q] = (int)(koffs[j][q + 1] - koffs[j][q]);
+    s->r_offs.swap(koffs[j]);
+    s->r_nq = nq;
+    s->r_valid = true;
+    jobs[j].total = plans[j].kept_total;
+  }
+  if (stats) {
+    stats->launches += st.launches;
+    stats->syncs += st.syncs;
+  }
+  return GORIO_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -728,6 +1038,48 @@ int gorio_search_radius(gorio_search_t* s, const float* q_xyz, int nq, int strid
     if (int rc = search_upload_queries(s, q_xyz, nq, stride_bytes)) return rc;
   }
   return search_radius_core(s, (q_xyz && nq > 0) ? s->d_q.get() : nullptr, nq, 12, radius, max_nn, count_out, total);
+}
+
+int gorio_search_radius_batch(gorio_search_t** handles, int count, const float* const* q_xyz, const int* nq, const int* stride_bytes, const double* radius, const int* max_nn,
+                              int* const* count_out, long long* totals) {
+  if (count == 0) return GORIO_OK;
+  if (count < 0) return search_fail(GORIO_ERR_INVALID, "radius_batch: count must not be negative");
+  if (!handles || !q_xyz || !nq || !stride_bytes || !radius || !max_nn || !totals) return search_fail(GORIO_ERR_INVALID, "radius_batch: null array");
+  // ---- every job's arguments, before any device call and before any state changes
+  std::unordered_set<const gorio_search_handle*> distinct;
+  for (int j = 0; j < count; ++j) {
+    const std::string who = "radius_batch: job " + std::to_string(j);
+    if (!handles[j]) return search_fail(GORIO_ERR_INVALID, who + ": null handle");
+    if (handles[j]->device != handles[0]->device) return search_fail(GORIO_ERR_INVALID, who + ": all handles of a batch must live on one device");
+    if (!distinct.insert(handles[j]).second) return search_fail(GORIO_ERR_INVALID, who + ": the same handle appears twice in a batch (it holds one result)");
+    if (int rc = search_check_radius(who.c_str(), handles[j], nq[j], stride_bytes[j], radius[j], max_nn[j], totals)) return rc;
+    if (int rc = search_self_nq(who.c_str(), handles[j], q_xyz[j], nq[j])) return rc;
+  }
+  GORIO_HIP_CHECK(search_fail, hipSetDevice(handles[0]->device));
+  hipStream_t stream = handles[0]->up->stream;
+  // ---- the queries: packed on the host, every job into the buffer of its own state, one synchronisation for all of them
+  std::vector<std::vector<float>> packed((size_t)count);
+  std::vector<SearchBatchJob> jobs((size_t)count);
+  for (int j = 0; j < count; ++j) {
+    gorio_search_handle* s = handles[j];
+    const bool cross = q_xyz[j] && nq[j] > 0;
+    if (cross) {
+      std::vector<float>& buf = packed[j];
+      buf.resize((size_t)nq[j] * 3);
+      const size_t st = stride_bytes[j] / 4;
+      for (int i = 0; i < nq[j]; ++i) {
+        const float* p = q_xyz[j] + (size_t)i * st;
+        buf[3 * (size_t)i] = p[0], buf[3 * (size_t)i + 1] = p[1], buf[3 * (size_t)i + 2] = p[2];
+      }
+      GORIO_HIP_CHECK(search_fail, s->d_q.reserve(buf.size(), search_plan::grown(buf.size())));
+      GORIO_HIP_CHECK(search_fail, hipMemcpyAsync(s->d_q, buf.data(), sizeof(float) * buf.size(), hipMemcpyHostToDevice, stream));
+    }
+    jobs[j] = SearchBatchJob{s, cross ? s->d_q.get() : nullptr, nq[j], 12, radius[j], max_nn[j], count_out ? count_out[j] : nullptr, 0};
+  }
+  GORIO_HIP_CHECK(search_fail, hipStreamSynchronize(stream));  // the packed queries are pageable
+  if (int rc = search_radius_batch_core(jobs.data(), count, nullptr)) return rc;
+  for (int j = 0; j < count; ++j) totals[j] = jobs[j].total;
+  return GORIO_OK;
 }
 
 int gorio_search_radius_get(gorio_search_t* s, long long* offsets_out, int* idx_out, float* sqd_out, long long capacity) {

@@ -96,6 +96,118 @@ inline bool make_plan(const long long* found_offs, int nq, int max_nn, Plan& p) 
   return true;
 }
 
+// ---- a BATCH of radius calls (search_radius_batch_core of apd_search.hip): several jobs, each a call of its own against a cloud of its
+// own, run by one set of launches.  Every job keeps the buffers of its own search state (found counts, keys, result), so its offsets stay
+// 64-bit counts of its own neighbours; what the jobs share is the launch grids, the found offsets the host reads back in one copy, the
+// query-key segments of one tiled sort and the table and slots of the long segments.
+//   count / fill     one wave per 64 queries, the jobs' waves one after the other: wave w of the launch is wave_tab[w] = (job, wave in job)
+//   segment sort     one workgroup per query, the jobs' queries one after the other: workgroup g belongs to job_of(query_first, count, g)
+//   found offsets    job j's nq + 1 offsets at offs_first[j] of the shared buffer
+//   query keys       job j's segment (a power of two, >= one sort tile) is segment key_seg[j] of the one tiled sort, or -1: a job with
+//                    self queries needs no keys.  The sort takes the passes of the largest segment (max_key_pow2).
+// A job that is not `active` (no query, or an empty cloud) takes part in none of it.
+struct BatchJobShape {
+  int nq;      // queries (self queries: the size of the cloud)
+  bool self;   // the queries are the cloud's own points
+  bool active;
+};
+struct WaveRef {
+  int job, wave;
+};
+struct BatchLayout {
+  std::vector<WaveRef> wave_tab;
+  std::vector<int> wave_first, query_first, key_seg;  // count + 1, count + 1, count
+  std::vector<long long> offs_first;                  // count + 1
+  std::vector<int> key_jobs;                          // the jobs of the key segments, in segment order
+  std::vector<int> key_first;                         // segments + 1: the first 256-key block of every segment in the key launch
+  int max_key_pow2 = 0;                               // 0: no job has cross queries
+  long long key_items = 0;                            // workgroups of 256 threads the key launch takes: the segments' sizes / 256 added up
+};
+
+inline int key_pow2(int nq) {
+  int p = kSortTileKeys;
+  while (p < nq) p <<= 1;
+  return p;
+}
+
+// false when the batch does not fit the int grids of its launches
+inline bool make_batch_layout(const BatchJobShape* jobs, int count, BatchLayout& b) {
+  b = BatchLayout();
+  b.wave_first.assign((size_t)count + 1, 0);
+  b.query_first.assign((size_t)count + 1, 0);
+  b.offs_first.assign((size_t)count + 1, 0);
+  b.key_seg.assign((size_t)count, -1);
+  long long waves = 0, queries = 0, offs = 0;
+  for (int j = 0; j < count; ++j) {
+    b.wave_first[j] = (int)waves;
+    b.query_first[j] = (int)queries;
+    b.offs_first[j] = offs;
+    if (!jobs[j].active || jobs[j].nq <= 0) continue;
+    const int nw = (jobs[j].nq + 63) / 64;
+    waves += nw;
+    queries += jobs[j].nq;
+    offs += (long long)jobs[j].nq + 1;
+    if (waves > kMaxTotal || queries > kMaxTotal) return false;
+    for (int w = 0; w < nw; ++w) b.wave_tab.push_back(WaveRef{j, w});
+    if (!jobs[j].self) {
+      const int p = key_pow2(jobs[j].nq);
+      b.key_seg[j] = (int)b.key_jobs.size();
+      b.key_jobs.push_back(j);
+      b.key_first.push_back((int)b.key_items);
+      b.key_items += p / 256;
+      if (b.key_items > kMaxTotal) return false;
+      if (p > b.max_key_pow2) b.max_key_pow2 = p;
+    }
+  }
+  b.wave_first[count] = (int)waves;
+  b.query_first[count] = (int)queries;
+  b.offs_first[count] = offs;
+  b.key_first.push_back((int)b.key_items);
+  return true;
+}
+
+// the job of item x of a launch whose jobs own [first[j], first[j + 1]): the last j with first[j] <= x (jobs without items share their
+// successor's start and are never the answer).  count >= 1, 0 <= x < first[count].  Plain integer code: the kernels of apd_search.hip run
+// the same function over the device copy of `first` (IntPtr: their scalar-load pointer).
+template <class IntPtr>
+#ifdef __HIPCC__
+__host__ __device__
+#endif
+inline int job_of(IntPtr first, int count, int x) {
+  int lo = 0, hi = count;  // first[lo] <= x < first[hi]
+  while (hi - lo > 1) {
+    const int mid = lo + (hi - lo) / 2;
+    if (first[mid] <= x) lo = mid;
+    else hi = mid;
+  }
+  return lo;
+}
+
+// One long segment of a batch: the segment as its job's plan has it (src / out count inside the job's own buffers), the slot moved into
+// the ONE padded buffer all jobs share.
+struct BatchLongSeg {
+  LongSeg seg;
+  int job;
+  int pad_;
+};
+struct BatchLongPlan {
+  std::vector<BatchLongSeg> segs;
+  long long slot_keys = 0;
+  int max_pow2 = 0;
+};
+inline void merge_long_segs(const Plan* plans, int count, BatchLongPlan& m) {
+  m = BatchLongPlan();
+  for (int j = 0; j < count; ++j) {
+    for (const LongSeg& s : plans[j].long_segs) {
+      BatchLongSeg b{s, j, 0};
+      b.seg.slot += m.slot_keys;
+      m.segs.push_back(b);
+    }
+    m.slot_keys += plans[j].slot_keys;
+    if (plans[j].max_pow2 > m.max_pow2) m.max_pow2 = plans[j].max_pow2;
+  }
+}
+
 // elements to allocate for a buffer that must hold `need`: an eighth more, so that calls of slowly growing size do not reallocate
 inline size_t grown(size_t need) { return need + need / 8 + 16; }
 

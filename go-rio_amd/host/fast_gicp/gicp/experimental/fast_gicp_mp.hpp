@@ -11,7 +11,9 @@
 //     with the old ones).
 //   - ADDITION: setNeighborSearchRadius (the reference fixes 0.5 in its constructor and has no setter).
 //   - Extras in the shape of the other drop-ins: setInputTargetShared, setInputSourceFromScan / setInputTargetFromScan,
-//     setInputSourceKeyframe / setInputTargetKeyframe, getFitnessScore on the GPU, handle().
+//     setInputSourceKeyframe / setInputTargetKeyframe, getFitnessScore on the GPU, handle(), and the loop-closure shape: static alignBatch
+//     (gorio_apd_gicp_mp_align_batch: N objects, usually on one shared target, in lock-step rounds over one batched radius search per
+//     round; every result bit for bit the object's own align) with getFitnessScoreBatch and getBatchCounts.
 #ifndef FAST_GICP_FAST_GICP_MP_HPP
 #define FAST_GICP_FAST_GICP_MP_HPP
 
@@ -19,6 +21,7 @@
 #include <memory>
 #include <stdexcept>
 #include <string>
+#include <vector>
 
 #include <Eigen/Core>
 #include <pcl/point_cloud.h>
@@ -158,6 +161,55 @@ class FastGICPMultiPoints : public pcl::Registration<PointSource, PointTarget, f
   }
   // passes of the last align, source points used and neighbours found in its last pass
   void getPassCounts(int& passes, int& used, long long& neighbours) const { check(gorio_apd_gicp_mp_diag(h_, &passes, &used, &neighbours, nullptr), "getPassCounts"); }
+  // align() of every object from its own guess in ONE gorio_apd_gicp_mp_align_batch.  Parameters and radii may differ per object.  A null
+  // object or a guess count that does not match throws std::invalid_argument, an object without source or target and whatever the
+  // library refuses std::runtime_error, before any object has changed.
+  static void alignBatch(const std::vector<FastGICPMultiPoints*>& regs, const std::vector<Matrix4>& guesses, std::vector<PointCloudSource>* outputs = nullptr) {
+    if (regs.size() != guesses.size()) throw std::invalid_argument("fast_gicp::FastGICPMultiPoints::alignBatch: one guess per object");
+    const std::size_t count = regs.size();
+    for (std::size_t i = 0; i < count; ++i) {
+      if (!regs[i]) throw std::invalid_argument("fast_gicp::FastGICPMultiPoints::alignBatch: null object");
+      if (!regs[i]->input_ || !regs[i]->target_) throw std::runtime_error("fast_gicp::FastGICPMultiPoints::alignBatch: object " + std::to_string(i) + " has no source or no target");
+    }
+    if (outputs) outputs->resize(count);
+    if (count == 0) return;
+    std::vector<gorio_apd_t*> hs(count);
+    std::vector<float> G(count * 16), T(count * 16);
+    std::vector<int> conv(count), nr(count);
+    for (std::size_t i = 0; i < count; ++i) {
+      regs[i]->push_params();
+      hs[i] = regs[i]->h_;
+      for (int r = 0; r < 4; ++r)
+        for (int c = 0; c < 4; ++c) G[i * 16 + 4 * r + c] = guesses[i](r, c);
+    }
+    regs[0]->check(gorio_apd_gicp_mp_align_batch(hs.data(), (int)count, G.data(), T.data(), conv.data(), nr.data()), "alignBatch");
+    for (std::size_t i = 0; i < count; ++i) {
+      FastGICPMultiPoints& o = *regs[i];
+      o.take_results(&T[i * 16], conv[i], nr[i]);
+      if (outputs) o.move_source(&T[i * 16], (*outputs)[i], "alignBatch");
+    }
+  }
+  // getFitnessScore of every object at its own final transformation through ONE gorio_apd_fitness_score_batch
+  static std::vector<double> getFitnessScoreBatch(const std::vector<FastGICPMultiPoints*>& regs, double max_range = std::numeric_limits<double>::max()) {
+    std::vector<double> score(regs.size());
+    if (regs.empty()) return score;
+    std::vector<gorio_apd_t*> hs(regs.size());
+    std::vector<float> T(regs.size() * 16);
+    for (std::size_t i = 0; i < regs.size(); ++i) {
+      if (!regs[i]) throw std::invalid_argument("fast_gicp::FastGICPMultiPoints::getFitnessScoreBatch: null object");
+      if (!regs[i]->input_ || !regs[i]->target_) throw std::logic_error("fast_gicp::FastGICPMultiPoints::getFitnessScoreBatch: no source or no target");
+      hs[i] = regs[i]->h_;
+      for (int r = 0; r < 4; ++r)
+        for (int c = 0; c < 4; ++c) T[i * 16 + 4 * r + c] = regs[i]->final_transformation_(r, c);
+    }
+    regs[0]->check(gorio_apd_fitness_score_batch(hs.data(), (int)regs.size(), T.data(), max_range, 0.0, score.data(), nullptr), "getFitnessScoreBatch");
+    return score;
+  }
+  // of the last alignBatch this object led (regs[0]): lock-step rounds, kernel launches and synchronisations of all rounds, and the
+  // launches of its most expensive round
+  void getBatchCounts(int& rounds, int& launches, int& syncs, int& max_round_launches) const {
+    check(gorio_apd_gicp_mp_batch_diag(h_, &rounds, &launches, &syncs, &max_round_launches), "getBatchCounts");
+  }
   gorio_apd_t* handle() { return h_; }
 
  protected:
@@ -168,13 +220,8 @@ class FastGICPMultiPoints : public pcl::Registration<PointSource, PointTarget, f
       for (int c = 0; c < 4; ++c) g[r * 4 + c] = guess(r, c);
     int conv = 0, nit = 0;
     check(gorio_apd_align(h_, g, T, nullptr, &conv, &nit, nullptr), "align");
-    for (int r = 0; r < 4; ++r)
-      for (int c = 0; c < 4; ++c) final_transformation_(r, c) = T[r * 4 + c];
-    converged_ = conv != 0;
-    nr_iterations_ = nit;
-    const int n = (int)input_->size();  // pcl::transformPointCloud(*input_, output, final_transformation_), fast_gicp_mp_impl.hpp:114
-    if ((int)output.size() != n) output.points = input_->points;
-    if (n > 0) check(gorio_apd_transform_source(h_, T, output.points[0].data, n, (int)sizeof(PointSource)), "align");
+    take_results(T, conv, nit);
+    move_source(T, output, "align");
   }
 
  private:
@@ -184,6 +231,17 @@ class FastGICPMultiPoints : public pcl::Registration<PointSource, PointTarget, f
   RegularizationMethod regularization_method_;
   gorio_apd_t* h_ = nullptr;
 
+  void take_results(const float* T, int conv, int nit) {
+    for (int r = 0; r < 4; ++r)
+      for (int c = 0; c < 4; ++c) final_transformation_(r, c) = T[r * 4 + c];
+    converged_ = conv != 0;
+    nr_iterations_ = nit;
+  }
+  void move_source(const float* T, PointCloudSource& output, const char* what) {  // pcl::transformPointCloud(*input_, output, final_transformation_), fast_gicp_mp_impl.hpp:114
+    const int n = (int)input_->size();
+    if ((int)output.size() != n) output.points = input_->points;
+    if (n > 0) check(gorio_apd_transform_source(h_, T, output.points[0].data, n, (int)sizeof(PointSource)), what);
+  }
   void check(int rc, const char* what) const {
     if (rc < 0) throw std::runtime_error(std::string("fast_gicp::FastGICPMultiPoints::") + what + " (gorio_amd): " + gorio_apd_last_error(h_) + " [code " + std::to_string(rc) + "]");
   }

@@ -8,7 +8,7 @@ from .apd import GorioError, load_library
 
 SEARCH_SYMBOLS = ["gorio_search_create", "gorio_search_destroy", "gorio_search_set_cloud", "gorio_search_set_cloud_device", "gorio_search_set_cloud_from_apd",
                   "gorio_search_set_cloud_from_keyframe", "gorio_search_cloud_size", "gorio_search_get_counters", "gorio_search_knn", "gorio_search_knn_device",
-                  "gorio_search_radius", "gorio_search_radius_device", "gorio_search_radius_get", "gorio_search_last_error"]
+                  "gorio_search_radius", "gorio_search_radius_device", "gorio_search_radius_batch", "gorio_search_radius_get", "gorio_search_last_error"]
 MAX_K = 32
 
 
@@ -118,3 +118,29 @@ class Search:
         sqd = np.zeros(max(cap, 1), np.float32)
         self._check(self.lib.gorio_search_radius_get(self.h, _ptr(offs), _ptr(idx), _ptr(sqd), C.c_longlong(cap)))
         return offs, idx[:total], sqd[:total]
+
+    @staticmethod
+    def radius_batch(searches, queries, radius, max_nn=0):
+        """gorio_search_radius_batch: job j = searches[j].radius(queries[j], radius[j], max_nn[j]) followed by radius_get, all jobs in one
+        set of launches.  queries: one array (or None: the cloud's own points) per job; radius / max_nn: one value per job, or a scalar
+        for all.  Returns per job (count [nq] int32, total, offsets [nq + 1] int64, idx [total] int32, sqd [total] float32)."""
+        n = len(searches)
+        if n == 0:
+            return []
+        lib = searches[0].lib
+        radius = [float(radius)] * n if np.isscalar(radius) else [float(r) for r in radius]
+        max_nn = [int(max_nn)] * n if np.isscalar(max_nn) else [int(m) for m in max_nn]
+        qs = [_queries(q) for q in queries]
+        nq = [s.cloud_size() if q is None else q.shape[0] for s, (q, _) in zip(searches, qs)]
+        cnt = [np.zeros(max(k, 1), np.int32) for k in nq]
+        hs = (C.c_void_p * n)(*[s.h for s in searches])
+        qp = (C.c_void_p * n)(*[None if q is None else _ptr(buf) for q, buf in qs])
+        cp = (C.c_void_p * n)(*[_ptr(c) for c in cnt])
+        totals = (C.c_longlong * n)(*([-1] * n))
+        rc = lib.gorio_search_radius_batch(hs, n, qp, (C.c_int * n)(*nq), (C.c_int * n)(*([12] * n)), (C.c_double * n)(*radius), (C.c_int * n)(*max_nn), cp, totals)
+        searches[0]._check(rc)
+        out = []
+        for j, s in enumerate(searches):
+            s._r_nq = nq[j]
+            out.append((cnt[j][:nq[j]], int(totals[j])) + s.radius_get(int(totals[j])))
+        return out

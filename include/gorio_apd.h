@@ -424,7 +424,8 @@ int gorio_apd_vgicp_cuda_get_pairs(gorio_apd_t* h, int capacity, int* n_pairs, i
  * class's own defaults (MPI:20-36: k 20, 64 iterations, both epsilons 1e-5, PLANE) are the caller's to set.  In this mode
  *   - gorio_apd_align runs the loop: nr_iterations = the index of the last pass, n_linearize = the passes run, H_out = the last H;
  *   - gorio_apd_linearize, gorio_apd_compute_error, gorio_apd_get_correspondences, gorio_apd_get_mahalanobis and gorio_apd_align_batch return
- *     GORIO_ERR_UNSUPPORTED and change nothing; the other methods' batch calls refuse such a handle as they refuse any foreign one; the double
+ *     GORIO_ERR_UNSUPPORTED and change nothing (the batched form of this method is gorio_apd_gicp_mp_align_batch below); the other methods'
+ *     batch calls refuse such a handle as they refuse any foreign one; the double
  *     covariance getters / setters, gorio_apd_calculate_covariances and the sharded-source calls return GORIO_ERR_STATE;
  *   - fitness and inlier scores, gorio_apd_transform_source, shared targets (the sharers share the float covariances: a sharer with another k
  *     or regularisation gets GORIO_ERR_INVALID) and the scan / keyframe hand-offs work; the target's search index is the one every method
@@ -438,8 +439,27 @@ int gorio_apd_vgicp_cuda_get_pairs(gorio_apd_t* h, int capacity, int* n_pairs, i
  * when capacity >= total) and gorio_apd_gicp_mp_get_merged (mean_B 3 floats, cov_B 6 floats, used flag per source point; capacity >= n) deliver.
  * An align leaves the CSR of its last pass but no merged distributions.  gorio_apd_gicp_mp_diag: passes of the last align, points used and
  * neighbour total of the last pass, and the seconds spent per stage (query transform, radius search, merge + linearise, shell) while
- * gorio_apd profiling was on.
+ * gorio_apd profiling was on.  gorio_apd_gicp_mp_last_hessian: the 36 doubles gorio_apd_align gave as H_out, held for the last align of the
+ * handle, single or batched (zeros before any).
+ *
+ * gorio_apd_gicp_mp_align_batch: `count` aligns in lock step, handle q from guesses + 16 q to T_out + 16 q (converged / nr_iterations: count
+ * entries each, may be NULL).  Every unfinished handle has one pass pending at its own pose; a ROUND is one query-transform launch over all of
+ * them, ONE batched radius search (include/gorio_search.h: gorio_search_radius_batch's core, every handle against its own target with its own
+ * radius), one merge-and-linearise launch, one fold launch and one copy back of 28 doubles per pending handle -- two synchronisations per
+ * round whatever the count, on the stream of handles[0].  The kernels run the single align's per-workgroup bodies, so afterwards every
+ * handle's T_out, converged, nr_iterations, gorio_apd_gicp_mp_diag, gorio_apd_gicp_mp_last_hessian and gorio_apd_gicp_mp_get_neighbors are
+ * bit for bit those of its own gorio_apd_align.  A handle that ends early (converged, no neighbour at all, a non-finite step) ends alone.
+ * gorio_apd_params and the radius are per handle and MAY differ; targets and sources may be shared by the rules of the single align (sharers
+ * of one cloud: one k_correspondences and regularization).  count == 0: GORIO_OK.  count < 0, a null array or entry, the same handle twice,
+ * handles on two devices: GORIO_ERR_INVALID; a handle of another method or without its clouds: GORIO_ERR_STATE; whatever else the single align
+ * refuses for a member, with that member's code -- all checked before anything is built or launched, the text on handles[0] naming the index
+ * ("handle <q>: ...").  Preparation (covariances, the target's index, buffers) runs handle by handle before the first round.
+ * gorio_apd_gicp_mp_batch_diag (of the lead, handles[0]): rounds = the most passes any member ran, launches and synchronisations of all
+ * rounds, and the launches of the most expensive round.
  */
+int gorio_apd_gicp_mp_align_batch(gorio_apd_t** handles, int count, const float* guesses, float* T_out, int* converged, int* nr_iterations);
+int gorio_apd_gicp_mp_batch_diag(const gorio_apd_t* lead, int* rounds, int* launches, int* syncs, int* max_round_launches);
+int gorio_apd_gicp_mp_last_hessian(const gorio_apd_t* h, double* H36);
 int gorio_apd_set_gicp_mp_params(gorio_apd_t* h, double neighbor_search_radius);
 int gorio_apd_get_gicp_mp_params(const gorio_apd_t* h, double* neighbor_search_radius);
 int gorio_apd_gicp_mp_get_covariances(gorio_apd_t* h, int which, int capacity, int* n, float* cov);

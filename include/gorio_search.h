@@ -83,6 +83,21 @@ int gorio_search_knn_device(gorio_search_t* s, const float* q_xyz, int nq, int s
 int gorio_search_radius(gorio_search_t* s, const float* q_xyz, int nq, int stride_bytes, double radius, int max_nn, int* count_out, long long* total);
 /* The same with a DEVICE pointer for the queries; count_out stays a host array. */
 int gorio_search_radius_device(gorio_search_t* s, const float* q_xyz, int nq, int stride_bytes, double radius, int max_nn, int* count_out, long long* total);
+/*
+ * `count` radius calls in one: job j is gorio_search_radius(handles[j], q_xyz[j], nq[j], stride_bytes[j], radius[j], max_nn[j],
+ * count_out[j], &totals[j]), and its result -- counts, total and the CSR handles[j] then holds for gorio_search_radius_get -- is bit for
+ * bit that call's.  What differs is the cost: the jobs share ONE set of launches and ONE synchronisation for the neighbours found (query
+ * keys and their sort over all jobs, count, scan, fill, segment sort, the long segments of all jobs in one table), on the launch stream of
+ * handles[0], so neither grows with count.  Queries are host pointers; q_xyz[j] == NULL means the cloud's own points (nq[j] must then be
+ * its size).  count_out may be NULL and so may any entry of it; totals holds count entries.  nq[j] == 0 and an empty cloud are legal jobs
+ * (no neighbour), and two handles may SHARE one cloud (gorio_search_set_cloud_from_apd / _from_keyframe of one owner).  count == 0 is
+ * GORIO_OK and touches nothing.  GORIO_ERR_INVALID ("job <j>: ..."): count < 0, a null array or handle, the same handle twice, handles on
+ * two devices, or a radius, max_nn, stride or nq the single call refuses -- checked for every job before any device call and before any
+ * state changes.  When ANY job finds more than 2^31 - 1 neighbours the whole call returns GORIO_ERR_UNSUPPORTED ("job <j>: ...") after
+ * the count pass, and every handle still holds the result it held before.
+ */
+int gorio_search_radius_batch(gorio_search_t** handles, int count, const float* const* q_xyz, const int* nq, const int* stride_bytes, const double* radius, const int* max_nn,
+                              int* const* count_out, long long* totals);
 /* Downloads the CSR of the last radius call: offsets_out[nq + 1], idx_out / sqd_out[total] (each may be NULL).  capacity (entries of
  * idx_out / sqd_out) < total returns GORIO_ERR_INVALID and writes nothing, whichever outputs are asked for; GORIO_ERR_STATE without
  * a radius result. */
