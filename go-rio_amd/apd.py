@@ -672,76 +672,62 @@ class DeviceInputs:
                 o._n_tgt = self._nt[i]
 
 
+def _run_align_batch(objs, guesses, call):
+    """What the batched aligns share: the guesses (identity by default), the result arrays and the handle array.  call(handles, n, g, T,
+    conv, nit) makes the C call; its code is checked against objs[0].  Stores every object's _final / _converged, returns (T, conv, nit)."""
+    n = len(objs)
+    g = np.ascontiguousarray(np.tile(np.eye(4, dtype=np.float32), (n, 1, 1)) if guesses is None else guesses, np.float32).reshape(n, 16)
+    T = np.zeros((n, 4, 4), np.float32)
+    conv = np.zeros(n, np.int32)
+    nit = np.zeros(n, np.int32)
+    arr = (C.c_void_p * n)(*[o._h for o in objs])
+    _check(objs[0]._h, call(arr, n, _p(g, C.c_float), _p(T, C.c_float), _p(conv, C.c_int), _p(nit, C.c_int)))
+    for q, o in enumerate(objs):
+        o._final = T[q]
+        o._converged = bool(conv[q])
+    return T, conv, nit
+
+
+def _batch_diag(fn, lead, names):
+    vals = [C.c_int(0) for _ in names]
+    _check(lead._h, fn(lead._h, *[C.byref(v) for v in vals]))
+    return {k: v.value for k, v in zip(names, vals)}
+
+
 def align_batch(objs, guesses=None):
     """gorio_apd_align_batch over a list of ApdGicp objects (all on one device).  Returns a list of result dicts."""
     lib = load_library()
     n = len(objs)
-    g = np.ascontiguousarray(np.tile(np.eye(4, dtype=np.float32), (n, 1, 1)) if guesses is None else guesses, np.float32).reshape(n, 16)
-    T = np.zeros((n, 4, 4), np.float32)
     H = np.zeros((n, 6, 6), np.float64)
-    conv = np.zeros(n, np.int32)
-    nit = np.zeros(n, np.int32)
     nlin = np.zeros(n, np.int32)
-    arr = (C.c_void_p * n)(*[o._h for o in objs])
-    rc = lib.gorio_apd_align_batch(arr, n, _p(g, C.c_float), _p(T, C.c_float), _p(H, C.c_double), _p(conv, C.c_int), _p(nit, C.c_int), _p(nlin, C.c_int))
-    _check(objs[0]._h, rc)
-    out = []
-    for q, o in enumerate(objs):
-        o._final = T[q]
-        o._converged = bool(conv[q])
-        out.append(dict(T=T[q], H=H[q], converged=bool(conv[q]), nr_iterations=int(nit[q]), n_linearize=int(nlin[q])))
-    return out
+    T, conv, nit = _run_align_batch(objs, guesses, lambda arr, n, g, T, conv, nit: lib.gorio_apd_align_batch(arr, n, g, T, _p(H, C.c_double), conv, nit, _p(nlin, C.c_int)))
+    return [dict(T=T[q], H=H[q], converged=bool(conv[q]), nr_iterations=int(nit[q]), n_linearize=int(nlin[q])) for q in range(n)]
 
 
 def gicp_omp_align_batch(objs, guesses=None):
     """gorio_apd_gicp_omp_align_batch over a list of ApdGicp objects in GICP_OMP mode (all on one device): their aligns in lock-step
     rounds, every result bit for bit the one of the object's own align().  Returns the list of dicts align() returns, each with
     batch_diag = dict(rounds, launches) of the whole batch.  An empty list makes no call."""
-    n = len(objs)
-    if n == 0:
+    if len(objs) == 0:
         return []
     lib = load_library()
-    g = np.ascontiguousarray(np.tile(np.eye(4, dtype=np.float32), (n, 1, 1)) if guesses is None else guesses, np.float32).reshape(n, 16)
-    T = np.zeros((n, 4, 4), np.float32)
-    conv = np.zeros(n, np.int32)
-    nit = np.zeros(n, np.int32)
-    nev = np.zeros(n, np.int32)
-    arr = (C.c_void_p * n)(*[o._h for o in objs])
-    rc = lib.gorio_apd_gicp_omp_align_batch(arr, n, _p(g, C.c_float), _p(T, C.c_float), _p(conv, C.c_int), _p(nit, C.c_int), _p(nev, C.c_int))
-    _check(objs[0]._h, rc)
-    rounds, launches = C.c_int(0), C.c_int(0)
-    _check(objs[0]._h, lib.gorio_apd_gicp_omp_batch_diag(objs[0]._h, C.byref(rounds), C.byref(launches)))
-    diag = dict(rounds=rounds.value, launches=launches.value)
-    out = []
-    for q, o in enumerate(objs):
-        o._final = T[q]
-        o._converged = bool(conv[q])
-        out.append(dict(T=T[q], H=np.zeros((6, 6), np.float64), converged=bool(conv[q]), nr_iterations=int(nit[q]), n_linearize=int(nev[q]), batch_diag=dict(diag)))
-    return out
+    nev = np.zeros(len(objs), np.int32)
+    T, conv, nit = _run_align_batch(objs, guesses, lambda arr, n, g, T, conv, nit: lib.gorio_apd_gicp_omp_align_batch(arr, n, g, T, conv, nit, _p(nev, C.c_int)))
+    diag = _batch_diag(lib.gorio_apd_gicp_omp_batch_diag, objs[0], ("rounds", "launches"))
+    return [dict(T=T[q], H=np.zeros((6, 6), np.float64), converged=bool(conv[q]), nr_iterations=int(nit[q]), n_linearize=int(nev[q]), batch_diag=dict(diag)) for q in range(len(objs))]
 
 
 def icp_align_batch(objs, guesses=None):
     """gorio_apd_icp_align_batch over a list of ApdGicp objects in ICP mode (all on one device): their aligns in lock-step rounds, every
     result bit for bit the one of the object's own align().  Returns the list of dicts align() returns (n_linearize = the object's
     correspondence passes), each with batch_diag = dict(rounds, launches) of the whole batch.  An empty list makes no call."""
-    n = len(objs)
-    if n == 0:
+    if len(objs) == 0:
         return []
     lib = load_library()
-    g = np.ascontiguousarray(np.tile(np.eye(4, dtype=np.float32), (n, 1, 1)) if guesses is None else guesses, np.float32).reshape(n, 16)
-    T = np.zeros((n, 4, 4), np.float32)
-    conv = np.zeros(n, np.int32)
-    nit = np.zeros(n, np.int32)
-    arr = (C.c_void_p * n)(*[o._h for o in objs])
-    rc = lib.gorio_apd_icp_align_batch(arr, n, _p(g, C.c_float), _p(T, C.c_float), _p(conv, C.c_int), _p(nit, C.c_int))
-    _check(objs[0]._h, rc)
-    rounds, launches = C.c_int(0), C.c_int(0)
-    _check(objs[0]._h, lib.gorio_apd_icp_batch_diag(objs[0]._h, C.byref(rounds), C.byref(launches)))
-    diag = dict(rounds=rounds.value, launches=launches.value)
+    T, conv, nit = _run_align_batch(objs, guesses, lib.gorio_apd_icp_align_batch)
+    diag = _batch_diag(lib.gorio_apd_icp_batch_diag, objs[0], ("rounds", "launches"))
     out = []
     for q, o in enumerate(objs):
-        o._final = T[q]
-        o._converged = bool(conv[q])
         d = o.icp_diag()  # passes = iterations, plus the pass that found fewer than 3 pairs (state 5) when the align ended there
         out.append(dict(T=T[q], H=np.zeros((6, 6), np.float64), converged=bool(conv[q]), nr_iterations=int(nit[q]), n_linearize=d["iterations"] + (d["state"] == 5),
                         batch_diag=dict(diag)))
@@ -753,27 +739,17 @@ def gicp_mp_align_batch(objs, guesses=None):
     differ): their aligns in lock-step rounds over one batched radius search per round, every result bit for bit the one of the
     object's own align().  Returns the list of dicts align() returns (H = the last pass's, n_linearize = the object's passes); the
     first carries batch_diag = dict(rounds, launches, syncs, max_round_launches) of the whole batch.  An empty list makes no call."""
-    n = len(objs)
-    if n == 0:
+    if len(objs) == 0:
         return []
     lib = load_library()
-    g = np.ascontiguousarray(np.tile(np.eye(4, dtype=np.float32), (n, 1, 1)) if guesses is None else guesses, np.float32).reshape(n, 16)
-    T = np.zeros((n, 4, 4), np.float32)
-    conv = np.zeros(n, np.int32)
-    nit = np.zeros(n, np.int32)
-    arr = (C.c_void_p * n)(*[o._h for o in objs])
-    rc = lib.gorio_apd_gicp_mp_align_batch(arr, n, _p(g, C.c_float), _p(T, C.c_float), _p(conv, C.c_int), _p(nit, C.c_int))
-    _check(objs[0]._h, rc)
-    r, l, sy, m = C.c_int(0), C.c_int(0), C.c_int(0), C.c_int(0)
-    _check(objs[0]._h, lib.gorio_apd_gicp_mp_batch_diag(objs[0]._h, C.byref(r), C.byref(l), C.byref(sy), C.byref(m)))
+    T, conv, nit = _run_align_batch(objs, guesses, lib.gorio_apd_gicp_mp_align_batch)
+    diag = _batch_diag(lib.gorio_apd_gicp_mp_batch_diag, objs[0], ("rounds", "launches", "syncs", "max_round_launches"))
     out = []
     for q, o in enumerate(objs):
-        o._final = T[q]
-        o._converged = bool(conv[q])
         H = np.zeros((6, 6), np.float64)
         _check(o._h, lib.gorio_apd_gicp_mp_last_hessian(o._h, _p(H, C.c_double)))
         out.append(dict(T=T[q], H=H, converged=bool(conv[q]), nr_iterations=int(nit[q]), n_linearize=o.gicp_mp_diag()["passes"]))
-    out[0]["batch_diag"] = dict(rounds=r.value, launches=l.value, syncs=sy.value, max_round_launches=m.value)
+    out[0]["batch_diag"] = diag
     return out
 
 

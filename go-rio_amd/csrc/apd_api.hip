@@ -240,13 +240,7 @@ struct gorio_apd {
   float gomp_guess[16] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1};  // guess of the `output` cloud held
   int gomp_pairs = -1;                // pairs of the last update (-1: none held)
   int gomp_outer = 0, gomp_inner = 0, gomp_evals = 0, gomp_status = -1;  // gorio_apd_gicp_omp_diag
-  // gorio_apd_gicp_omp_align_batch (owned by the handle that leads a batch): job and workgroup table, the partial slots of the round's
-  // evaluations and updates, the folded sums and pair counts on the device and pinned on the host
-  DevBuf<void> gomp_b_jobs, gomp_b_out;
-  DevBuf<double> gomp_b_part;
-  DevBuf<int> gomp_b_cnt;
-  PinnedBuf gomp_b_h_out;
-  int gomp_b_rounds = 0, gomp_b_launches = 0;  // gorio_apd_gicp_omp_batch_diag
+  int gomp_b_rounds = 0, gomp_b_launches = 0;  // gorio_apd_gicp_omp_batch_diag: of the last batch this handle led
   // ICP (GORIO_METHOD_ICP, apd_icp.hip): use_reciprocal_correspondences_, euclidean_fitness_epsilon_ and transformation_rotation_epsilon_ of
   // pcl::IterativeClosestPoint, the moved working copy in original order (x, y, z) and in the source's search-index order, the reciprocal flags
   int icp_reciprocal = 0;
@@ -257,11 +251,7 @@ struct gorio_apd {
   int icp_cap = 0;
   int icp_iterations = 0, icp_state = 0, icp_pairs = -1, icp_passes = 0;  // gorio_apd_icp_diag
   double icp_mse = 0.0;
-  // owned by the handle that leads the rounds: job and workgroup table, block partials, the folded sums on the device and pinned on the host
-  DevBuf<void> icp_b_jobs, icp_b_out;
-  DevBuf<double> icp_b_part;
-  PinnedBuf icp_b_h_out;
-  int icp_b_rounds = 0, icp_b_launches = 0;  // gorio_apd_icp_batch_diag
+  int icp_b_rounds = 0, icp_b_launches = 0;  // gorio_apd_icp_batch_diag: of the last batch this handle led
   // fast_gicp::NDTCuda (GORIO_METHOD_NDT_CUDA, apd_ndt_cuda.hip): distance_mode and the DIRECT_RADIUS radius (ndt_cuda.cu:21-35), the offset
   // table on the device and the (search, radius) it was made for, the slot table, linearized_x and the block partials
   int ndtc_mode = GORIO_NDT_CUDA_D2D;
@@ -321,7 +311,19 @@ struct gorio_apd {
       if (ev) hipEventDestroy(ev);
     }
   };
-  Pinned pin_ijobs, pin_jobs, pin_desc, pin_states, pin_copy, pin_vox, pin_ndtc, pin_gomp_jobs, pin_icp_jobs;
+  Pinned pin_ijobs, pin_jobs, pin_desc, pin_states, pin_copy, pin_vox, pin_ndtc;
+  // The lock-step batched aligns (run_rounds, apd_batch_rounds.hip), used by the handle that leads the rounds: job records and round table,
+  // block partials and block counts, the jobs' folded sums on the device and pinned on the host, the staging of the table.  One set for
+  // all methods: a handle leads one batch at a time and every call reserves what it needs; pin's event guards the staging's reuse.
+  struct RoundScratch {
+    DevBuf<unsigned char> tab;
+    DevBuf<double> part;
+    DevBuf<int> cnt;
+    DevBuf<void> out;  // sums (and counts) of the jobs, h_out the same on the host
+    PinnedBuf h_out;
+    Pinned pin;
+  };
+  RoundScratch round;
   PinnedBuf pin_looks;  // where the align loop's looks at the pair states land (a download into pageable memory is staged by the runtime)
   std::string err;
   // profiling
@@ -2907,6 +2909,7 @@ extern "C" int gorio_debug_search_stats(unsigned long long out[24], int reset) {
 #include "apd_keyframes.hip"
 #include "../../include/gorio_map.h"
 #include "apd_map.hip"
+#include "apd_batch_rounds.hip"
 #include "apd_gicp_omp.hip"
 #include "apd_icp.hip"
 #include "../../include/gorio_search.h"

@@ -228,16 +228,8 @@ __global__ __launch_bounds__(256) void mp_linearize_kernel(const float4* __restr
   mp_linearize_block(src_rec, q, n, offs, idx, sqd, tgt_rec, n_tgt, T, radius, merged, blockIdx.x, partials + (size_t)blockIdx.x * 28);
 }
 
-// out[t] = the nblk partials of term t added in block order, lane t of one wave
-__device__ __forceinline__ void mp_fold_wave(const double* __restrict__ partials, int nblk, double* __restrict__ out) {
-  const int t = threadIdx.x;
-  if (t >= 28) return;
-  double s = 0.0;
-  for (int b = 0; b < nblk; ++b) s += partials[(size_t)b * 28 + t];
-  out[t] = s;
-}
-// grid 1, block 64
-__global__ __launch_bounds__(64) void mp_fold_kernel(const double* __restrict__ partials, int nblk, double* __restrict__ out) { mp_fold_wave(partials, nblk, out); }
+// grid 1, block 64: out[t] = the nblk partials of term t added in block order, lane t of one wave
+__global__ __launch_bounds__(64) void mp_fold_kernel(const double* __restrict__ partials, int nblk, double* __restrict__ out) { fold_wave<28>(partials, nblk, out); }
 
 // ---- the batched align (gorio_apd_gicp_mp_align_batch): the three launches above once more, each over the pending handles of a round.
 // One handle's pass of a round.  Workgroups [first, first + nblk) of the query and the linearise launch belong to it, and so do the
@@ -254,24 +246,21 @@ struct MpJob {
   MpPose T;
   int n, n_tgt, first, nblk;
 };
-struct MpBlockRef {
-  int job, blk;
-};
-// grid: the jobs' blocks added up, block 256
-__global__ __launch_bounds__(256) void mp_query_batch_kernel(const MpJob* __restrict__ jobs, const MpBlockRef* __restrict__ blocks) {
-  const MpBlockRef w = load_uniform(blocks + blockIdx.x);
+// grid: the jobs' blocks added up, block 256.  blocks: the round table (batch_rounds.h), job < number of jobs, blk < jobs[job].nblk
+__global__ __launch_bounds__(256) void mp_query_batch_kernel(const MpJob* __restrict__ jobs, const BlockRef* __restrict__ blocks) {
+  const BlockRef w = load_uniform(blocks + blockIdx.x);
   const MpJob j = load_uniform(jobs + w.job);
   mp_query_point(j.src_p4, j.n, j.T, j.q, w.blk * 256 + (int)threadIdx.x);
 }
-__global__ __launch_bounds__(256) void mp_linearize_batch_kernel(const MpJob* __restrict__ jobs, const MpBlockRef* __restrict__ blocks, double* __restrict__ partials) {
-  const MpBlockRef w = load_uniform(blocks + blockIdx.x);
+__global__ __launch_bounds__(256) void mp_linearize_batch_kernel(const MpJob* __restrict__ jobs, const BlockRef* __restrict__ blocks, double* __restrict__ partials) {
+  const BlockRef w = load_uniform(blocks + blockIdx.x);
   const MpJob j = load_uniform(jobs + w.job);
   mp_linearize_block(j.src_rec, j.q, j.n, j.offs, j.idx, j.sqd, j.tgt_rec, j.n_tgt, j.T, j.radius, nullptr, w.blk, partials + (size_t)(j.first + w.blk) * 28);
 }
 // grid: the round's jobs, block 64
 __global__ __launch_bounds__(64) void mp_fold_batch_kernel(const MpJob* __restrict__ jobs, const double* __restrict__ partials, double* __restrict__ out) {
   const MpJob j = load_uniform(jobs + blockIdx.x);
-  mp_fold_wave(partials + (size_t)j.first * 28, j.nblk, out + (size_t)blockIdx.x * 28);
+  fold_wave<28>(partials + (size_t)j.first * 28, j.nblk, out + (size_t)blockIdx.x * 28);
 }
 
 }  // namespace gorio
@@ -292,11 +281,7 @@ struct GicpMpState {
   int used = 0, passes = 0;      // of the last pass / of the last align
   double last_H[36] = {};        // H of the last pass of the last align, single or batched (gorio_apd_gicp_mp_last_hessian)
   double stage_s[4] = {0, 0, 0, 0};  // query transform, radius search, merge + linearise (with fold and copy back), shell: filled while profiling
-  // a batch this handle LEADS (gorio_apd_gicp_mp_align_batch): job records and block table, block partials, the jobs' sums
-  DevBuf<unsigned char> b_tab;
-  DevBuf<double> b_part, b_out;
-  PinnedBuf b_h_out;
-  gorio_apd::Pinned pin_tab;
+  // the last batch this handle LED (gorio_apd_gicp_mp_align_batch)
   int b_rounds = 0, b_launches = 0, b_syncs = 0, b_max_round_launches = 0;  // gorio_apd_gicp_mp_batch_diag
 };
 
@@ -449,6 +434,13 @@ int mp_align(gorio_apd* h, const float* guess, float* T_out, double* H_out, int*
   return GORIO_OK;
 }
 
+struct MpRounds {  // the round table of run_rounds
+  using Job = MpJob;
+  static constexpr int kSums = 28;
+  static constexpr bool kCounts = false, kSecondList = false;
+  static void fold(int njobs, hipStream_t stream, const MpJob* jobs, const double* part, const int*, double* out, int*) { mp_fold_batch_kernel<<<njobs, 64, 0, stream>>>(jobs, part, out); }
+};
+
 // The lock-step rounds of gorio_apd_gicp_mp_align_batch.  Every unfinished handle has one pass pending at its own pose; a round is one
 // query-transform launch over (job, block) entries, the batched radius search (each handle's target through the search state inside the
 // handle, its own radius), one merge-and-linearise launch, one fold launch, one copy back of 28 doubles per pending handle and one
@@ -457,109 +449,79 @@ int mp_run_batch(gorio_apd** hs, int count, const float* guesses, float* T_out, 
   gorio_apd* lead = hs[0];
   for (int q = 0; q < count; ++q) {  // preparation is per handle, not per pass
     gorio_apd* h = hs[q];
-    const int rc = mp_prepare(h);
-    if (rc) {
-      if (h != lead) lead->err = h->err;
-      return rc;
-    }
+    if (int rc = hand_over(lead, h, mp_prepare(h))) return rc;
     if (h->stream != lead->stream) HIP_TRY(lead, hipStreamSynchronize(h->stream));
   }
   GicpMpState* lm = mp_state(lead);
   size_t max_blk = 0;
   for (int q = 0; q < count; ++q) max_blk += (size_t)(hs[q]->src->n + 255) / 256;
-  if (max_blk > (size_t)INT_MAX / 32) return fail(lead, GORIO_ERR_INVALID, "gicp_mp_align_batch: too many source points in one batch");
-  const size_t o_blk = sizeof(MpJob) * (size_t)count, tab_bytes = o_blk + sizeof(MpBlockRef) * max_blk, out_bytes = sizeof(double) * 28 * (size_t)count;
-  HIP_TRY(lead, lm->b_tab.reserve(tab_bytes, tab_bytes + tab_bytes / 4));
-  HIP_TRY(lead, lm->b_part.reserve(28 * max_blk, 28 * (max_blk + max_blk / 4)));
-  HIP_TRY(lead, lm->b_out.reserve(28 * (size_t)count, 28 * ((size_t)count + (size_t)count / 4)));
-  HIP_TRY(lead, lm->b_h_out.reserve(out_bytes, out_bytes + out_bytes / 4));
+  if (batch_rounds::too_many_wg(max_blk, 32)) return fail(lead, GORIO_ERR_INVALID, "gicp_mp_align_batch: too many source points in one batch");
   std::vector<MpMachine> mc((size_t)count);
   for (int q = 0; q < count; ++q) {
     const gorio_apd_params& p = hs[q]->params;
     mc[q].begin(guesses + (size_t)16 * q, p.max_iterations, p.rotation_epsilon, p.transformation_epsilon);
   }
-  std::vector<unsigned char> table(tab_bytes);
   std::vector<SearchBatchJob> sj((size_t)count);
-  std::vector<int> order;
-  order.reserve(count);
-  int rounds = 0, launches = 0, syncs = 0, max_round = 0;
-  for (;;) {
-    order.clear();
-    for (int q = 0; q < count; ++q)
-      if (!mc[q].done()) order.push_back(q);
-    const int njobs = (int)order.size();
-    if (njobs == 0) break;
-    MpJob* const jobs = reinterpret_cast<MpJob*>(table.data());
-    MpBlockRef* const blocks = reinterpret_cast<MpBlockRef*>(table.data() + sizeof(MpJob) * (size_t)njobs);
-    int slot = 0;
-    for (int k = 0; k < njobs; ++k) {
-      gorio_apd* h = hs[order[k]];
-      GicpMpState* m = mp_state(h);
-      const DevCloud& s = *h->src;
-      MpJob& j = jobs[k];
-      std::memset(&j, 0, sizeof(j));
-      j.src_p4 = s.p4;
-      j.src_rec = s.mp_rec;
-      j.q = m->q;
-      j.tgt_rec = h->tgt->mp_rec;
-      j.radius = h->mp_radius;
-      mc[order[k]].next_pose(j.T.m);
-      j.n = s.n;
-      j.n_tgt = h->tgt->n;
-      j.first = slot;
-      j.nblk = (s.n + 255) / 256;
-      for (int b = 0; b < j.nblk; ++b) blocks[slot + b] = MpBlockRef{k, b};  // job < njobs, blk < nblk: what the kernels rely on
-      slot += j.nblk;
-      h->mp_pass_valid = false;
-      h->corr_valid = false;
-      m->merged_valid = false;
-      sj[k] = SearchBatchJob{&m->s, reinterpret_cast<const float*>(m->q.get()), s.n, 16, h->mp_radius, 0, nullptr, 0};
-    }
-    const size_t bytes = sizeof(MpJob) * (size_t)njobs + sizeof(MpBlockRef) * (size_t)slot;  // <= tab_bytes
-    if (int rc = upload_staged(lead, lm->pin_tab, lm->b_tab, table.data(), bytes)) return rc;
-    const MpJob* d_jobs = reinterpret_cast<const MpJob*>(lm->b_tab.get());
-    const MpBlockRef* d_blocks = reinterpret_cast<const MpBlockRef*>(lm->b_tab.get() + sizeof(MpJob) * (size_t)njobs);
-    mp_query_batch_kernel<<<slot, 256, 0, lead->stream>>>(d_jobs, d_blocks);
+  RoundCounters ctr;
+  int syncs = 0, max_round = 0;
+  auto pending = [&](int q) { return mc[q].done() ? -1 : 0; };
+  auto fill = [&](int k, int q, MpJob& j) {
+    gorio_apd* h = hs[q];
+    GicpMpState* m = mp_state(h);
+    const DevCloud& s = *h->src;
+    j.src_p4 = s.p4;
+    j.src_rec = s.mp_rec;
+    j.q = m->q;
+    j.tgt_rec = h->tgt->mp_rec;
+    j.radius = h->mp_radius;
+    mc[q].next_pose(j.T.m);
+    j.n = s.n;
+    j.n_tgt = h->tgt->n;
+    h->mp_pass_valid = false;
+    h->corr_valid = false;
+    m->merged_valid = false;
+    sj[k] = SearchBatchJob{&m->s, reinterpret_cast<const float*>(m->q.get()), s.n, 16, h->mp_radius, 0, nullptr, 0};
+    const int nblk = (s.n + 255) / 256;
+    return batch_rounds::JobShape{nblk, nblk, false};
+  };
+  // the search in the middle of the round: the job records go up a second time, with the CSR every handle's search state then holds
+  auto launch = [&](const RoundView<MpJob>& v, int& launches) {
+    const int njobs = v.plan.njobs;
+    mp_query_batch_kernel<<<v.plan.wg, 256, 0, lead->stream>>>(v.d_jobs, v.d_refs);
     HIP_TRY(lead, hipGetLastError());
     SearchBatchStats st;
     if (int rc = search_radius_batch_core(sj.data(), njobs, &st)) return fail(lead, rc, "FastGICPMultiPoints: " + g_search_err);
-    for (int k = 0; k < njobs; ++k) {  // the CSR every handle's search state now holds (the search may have moved its buffers)
-      GicpMpState* m = hs[order[k]]->mp.get();
-      jobs[k].offs = m->s.d_kept_offs;
-      jobs[k].idx = m->s.d_ridx;
-      jobs[k].sqd = m->s.d_rsqd;
+    for (int k = 0; k < njobs; ++k) {  // the search may have moved its buffers
+      GicpMpState* m = hs[v.order[k]]->mp.get();
+      v.jobs[k].offs = m->s.d_kept_offs;
+      v.jobs[k].idx = m->s.d_ridx;
+      v.jobs[k].sqd = m->s.d_rsqd;
     }
-    if (int rc = upload_staged(lead, lm->pin_tab, lm->b_tab, table.data(), sizeof(MpJob) * (size_t)njobs)) return rc;
-    mp_linearize_batch_kernel<<<slot, 256, 0, lead->stream>>>(d_jobs, d_blocks, lm->b_part);
-    mp_fold_batch_kernel<<<njobs, 64, 0, lead->stream>>>(d_jobs, lm->b_part, lm->b_out);
-    HIP_TRY(lead, hipGetLastError());
-    HIP_TRY(lead, hipMemcpyAsync(lm->b_h_out.get(), lm->b_out, sizeof(double) * 28 * (size_t)njobs, hipMemcpyDeviceToHost, lead->stream));
-    HIP_TRY(lead, hipStreamSynchronize(lead->stream));
-    const int round_launches = 3 + st.launches;
-    launches += round_launches;
-    max_round = std::max(max_round, round_launches);
+    if (int rc = upload_staged(lead, lead->round.pin, lead->round.tab, v.jobs, sizeof(MpJob) * (size_t)njobs)) return rc;
+    mp_linearize_batch_kernel<<<v.plan.wg, 256, 0, lead->stream>>>(v.d_jobs, v.d_refs, lead->round.part);
+    launches += 2 + st.launches;
+    max_round = std::max(max_round, launches);
     syncs += 1 + st.syncs;
-    ++rounds;
-    const double* sums = static_cast<const double*>(lm->b_h_out.get());
-    for (int k = 0; k < njobs; ++k) {
-      gorio_apd* h = hs[order[k]];
-      GicpMpState* m = h->mp.get();
-      const double* sk = sums + (size_t)28 * k;
-      m->pass_n = h->src->n;
-      m->total = sj[k].total;
-      m->used = (int)sk[27];
-      h->mp_pass_valid = true;
-      h->corr_valid = true;
-      h->omega_valid = false;
-      mc[order[k]].consume(sk);
-    }
-  }
+    return (int)GORIO_OK;
+  };
+  auto consume = [&](int k, int q, const double* sk, int) {
+    gorio_apd* h = hs[q];
+    GicpMpState* m = h->mp.get();
+    m->pass_n = h->src->n;
+    m->total = sj[k].total;
+    m->used = (int)sk[27];
+    h->mp_pass_valid = true;
+    h->corr_valid = true;
+    h->omega_valid = false;
+    mc[q].consume(sk);
+  };
+  if (int rc = run_rounds<MpRounds>(lead, count, max_blk, ctr, pending, fill, launch, consume)) return rc;
   for (int q = 0; q < count; ++q) {
     mp_state(hs[q])->passes = mc[q].pass;
     mc[q].results(T_out + (size_t)16 * q, mp_state(hs[q])->last_H, converged ? converged + q : nullptr, nr_iterations ? nr_iterations + q : nullptr, nullptr);
   }
-  lm->b_rounds = rounds;
-  lm->b_launches = launches;
+  lm->b_rounds = ctr.rounds;
+  lm->b_launches = ctr.launches;
   lm->b_syncs = syncs;
   lm->b_max_round_launches = max_round;
   return GORIO_OK;
@@ -660,29 +622,8 @@ int gorio_apd_gicp_mp_get_merged(gorio_apd_t* h, int capacity, int* n, float* me
 
 int gorio_apd_gicp_mp_align_batch(gorio_apd_t** handles, int count, const float* guesses, float* T_out, int* converged, int* nr_iterations) {
   if (count == 0) return GORIO_OK;
-  if (count < 0 || !handles || !guesses || !T_out) return GORIO_ERR_INVALID;
-  for (int q = 0; q < count; ++q)
-    if (!handles[q]) return handles[0] ? fail(handles[0], GORIO_ERR_INVALID, "gicp_mp_align_batch: handle " + std::to_string(q) + " is null") : GORIO_ERR_INVALID;
+  if (int rc = batch_front_door("gicp_mp_align_batch", handles, count, guesses, T_out, false, is_mp, "the handle is not in FastGICPMultiPoints mode (gorio_apd_set_method)", mp_ready)) return rc;
   gorio_apd* lead = handles[0];
-  // ---- validation: nothing is built, allocated or launched before every handle has passed
-  auto refuse = [&](int q, int code, const std::string& why) { return fail(lead, code, "gicp_mp_align_batch: handle " + std::to_string(q) + ": " + why); };
-  std::unordered_set<gorio_apd*> distinct;
-  for (int q = 0; q < count; ++q) {
-    gorio_apd* h = handles[q];
-    if (h->device != lead->device) return refuse(q, GORIO_ERR_INVALID, "all handles of a batch must live on one device");
-    if (!distinct.insert(h).second) return refuse(q, GORIO_ERR_INVALID, "the same handle appears twice in a batch (its buffers would be raced on)");
-    if (!is_mp(h)) return refuse(q, GORIO_ERR_STATE, "the handle is not in FastGICPMultiPoints mode (gorio_apd_set_method)");
-  }
-  for (int q = 0; q < count; ++q) {
-    gorio_apd* h = handles[q];
-    const std::string kept = h->err;
-    const int rc = mp_ready(h);
-    if (rc) {
-      const std::string why = h->err;
-      if (h != lead) h->err = kept;
-      return refuse(q, rc, why);
-    }
-  }
   // members that share a cloud must make its covariances by one rule: the single align refuses the second of them by the cloud's state, which
   // inside a batch the first member's preparation would only set after this check
   std::unordered_map<const DevCloud*, int> owner;
@@ -696,7 +637,7 @@ int gorio_apd_gicp_mp_align_batch(gorio_apd_t** handles, int count, const float*
       }
       const gorio_apd_params &a = handles[it->second]->params, &b = h->params;
       if (a.k_correspondences != b.k_correspondences || a.regularization != b.regularization)
-        return refuse(q, GORIO_ERR_INVALID, "it shares a cloud with handle " + std::to_string(it->second) + " but has another k_correspondences or regularization");
+        return fail(lead, GORIO_ERR_INVALID, "gicp_mp_align_batch: handle " + std::to_string(q) + ": it shares a cloud with handle " + std::to_string(it->second) + " but has another k_correspondences or regularization");
     }
   }
   HIP_TRY(lead, hipSetDevice(lead->device));

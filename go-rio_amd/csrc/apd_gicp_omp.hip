@@ -250,23 +250,23 @@ struct GompJob {
   int pad0_;
 };
 
-// grid: the sum over the launch's jobs of ceil(n_j / 256), block 256.  wg[blockIdx.x] = (job, job-local block), written by the host with the
-// job table; the index is uniform over the workgroup, so the job record comes in through scalar loads.  The host keeps wg[].x < number of
-// jobs and wg[].y < jobs[wg[].x].nblk; the partial buffers hold first + nblk slots for every job.
-__global__ __launch_bounds__(256) void gomp_functor_batch_kernel(const GompJob* __restrict__ jobs, const int2* __restrict__ wg, double* __restrict__ partials) {
+// grid: the sum over the launch's jobs of ceil(n_j / 256), block 256.  wg[blockIdx.x] = (job, job-local block) of the round table
+// (batch_rounds.h); the index is uniform over the workgroup, so the job record comes in through scalar loads.  job < number of jobs and
+// blk < jobs[job].nblk; the partial buffers hold first + nblk slots for every job.
+__global__ __launch_bounds__(256) void gomp_functor_batch_kernel(const GompJob* __restrict__ jobs, const BlockRef* __restrict__ wg, double* __restrict__ partials) {
   __shared__ double s_red[4 * 13];
-  const int2 w = wg[blockIdx.x];
-  const GompJob& j = jobs[w.x];
-  double* out = partials + (size_t)(j.first + w.y) * 13;
-  if (j.mode == 0) gomp_functor_block<0>(j.ox, j.oy, j.oz, j.n, j.tgt, j.corr, j.maha, j.tf, w.y, s_red, out);
-  else if (j.mode == 1) gomp_functor_block<1>(j.ox, j.oy, j.oz, j.n, j.tgt, j.corr, j.maha, j.tf, w.y, s_red, out);
-  else gomp_functor_block<2>(j.ox, j.oy, j.oz, j.n, j.tgt, j.corr, j.maha, j.tf, w.y, s_red, out);
+  const BlockRef w = wg[blockIdx.x];
+  const GompJob& j = jobs[w.job];
+  double* out = partials + (size_t)(j.first + w.blk) * 13;
+  if (j.mode == 0) gomp_functor_block<0>(j.ox, j.oy, j.oz, j.n, j.tgt, j.corr, j.maha, j.tf, w.blk, s_red, out);
+  else if (j.mode == 1) gomp_functor_block<1>(j.ox, j.oy, j.oz, j.n, j.tgt, j.corr, j.maha, j.tf, w.blk, s_red, out);
+  else gomp_functor_block<2>(j.ox, j.oy, j.oz, j.n, j.tgt, j.corr, j.maha, j.tf, w.blk, s_red, out);
 }
 
-__global__ __launch_bounds__(256) void gomp_update_batch_kernel(const GompJob* __restrict__ jobs, const int2* __restrict__ wg, int* __restrict__ cnt) {
-  const int2 w = wg[blockIdx.x];
-  const GompJob& j = jobs[w.x];
-  gomp_update_block(j.best_key, j.n, j.c1, j.c2, j.n_tgt, j.R, j.corr, j.sqd, j.maha, w.y, cnt + j.first + w.y);
+__global__ __launch_bounds__(256) void gomp_update_batch_kernel(const GompJob* __restrict__ jobs, const BlockRef* __restrict__ wg, int* __restrict__ cnt) {
+  const BlockRef w = wg[blockIdx.x];
+  const GompJob& j = jobs[w.job];
+  gomp_update_block(j.best_key, j.n, j.c1, j.c2, j.n_tgt, j.R, j.corr, j.sqd, j.maha, w.blk, cnt + j.first + w.blk);
 }
 
 // grid: the round's jobs, block 64.  An evaluation: lane q adds the job's partials of value q in block order, as the last workgroup of
@@ -284,11 +284,7 @@ __global__ __launch_bounds__(64) void gomp_fold_batch_kernel(const GompJob* __re
     return;
   }
   const int v0 = j.mode == 1 ? 1 : 0, v1 = j.mode == 0 ? 1 : 13;
-  if (q >= v0 && q < v1) {
-    double s = 0.0;
-    for (int b = 0; b < j.nblk; ++b) s += partials[(size_t)(j.first + b) * 13 + q];
-    out[(size_t)blockIdx.x * 13 + q] = s;
-  }
+  if (q >= v0 && q < v1) fold_wave<13>(partials + (size_t)j.first * 13, j.nblk, out + (size_t)blockIdx.x * 13);
   if (q < 13 && (q < v0 || q >= v1)) out[(size_t)blockIdx.x * 13 + q] = 0.0;
   if (q == 0) pairs[blockIdx.x] = 0;
 }
@@ -430,16 +426,10 @@ int gomp_update(gorio_apd* h, const float* Tr, int* m) {
   int rc = ensure_batch(h, 1);
   if (rc) return rc;
   PairDesc d;
-  fill_desc(h, d, h->d_state, (n + 63) / 64);
-  float* o = h->gomp_out;
-  const size_t st = h->gomp_out.cap() / 3;
-  d.src.x = o; d.src.y = o + st; d.src.z = o + 2 * st;  // the searches read the `output` copy
-  d.src.idx.s4 = h->gomp_s4;
   PairState s;
-  double Td[16];
-  for (int i = 0; i < 16; ++i) Td[i] = (double)Tr[i];
-  init_state(s, Td);
-  for (int i = 0; i < 12; ++i) s.Tf[i] = Tr[i];
+  const float* o = h->gomp_out;
+  const size_t st = h->gomp_out.cap() / 3;
+  fill_moved_search(h, d, s, h->d_state, (n + 63) / 64, o, o + st, o + 2 * st, h->gomp_s4, Tr);  // the searches read the `output` copy
   HIP_TRY(h, hipMemcpyAsync(h->d_desc, &d, sizeof(PairDesc), hipMemcpyHostToDevice, h->stream));
   HIP_TRY(h, hipMemcpyAsync(h->d_state, &s, sizeof(s), hipMemcpyHostToDevice, h->stream));
   HIP_TRY(h, hipStreamSynchronize(h->stream));  // d and s live on this frame
@@ -607,30 +597,21 @@ int gomp_align(gorio_apd* h, const float* guess, float* T_out, double* H_out, in
   return GORIO_OK;
 }
 
+struct GompRounds {  // the round table of run_rounds
+  using Job = GompJob;
+  static constexpr int kSums = 13;
+  static constexpr bool kCounts = true, kSecondList = false;  // an update's pairs: an int per block, folded to an int per job
+  static void fold(int njobs, hipStream_t stream, const GompJob* jobs, const double* part, const int* cnt, double* out, int* pairs) { gomp_fold_batch_kernel<<<njobs, 64, 0, stream>>>(jobs, part, cnt, out, pairs); }
+};
+
 // gorio_apd_gicp_omp_align_batch: N machines in lock-step.  Every round each unfinished handle has exactly one request pending; the
 // updates of a round share one search launch and one update launch, the evaluations one functor launch, everything one fold launch, one
 // copy back and one synchronisation.  The tables and the sums live in the lead handle (hs[0]), whose stream carries the rounds.
 int gomp_align_batch(gorio_apd** hs, int count, const float* guesses, float* T_out, int* converged, int* nr_iterations, int* n_evaluations) {
   gorio_apd* lead = hs[0];
-  const bool pruned = lead->params.search == GORIO_SEARCH_PRUNED;
-  // ---- covariances and search indices: a cloud several handles hold is made once
-  int rc = GORIO_OK;
-  for (int q = 0; q < count; ++q) {
-    rc = ensure_points(hs[q], hs[q]->src->n);
-    if (rc) {
-      if (hs[q] != lead) lead->err = hs[q]->err;
-      return rc;
-    }
-  }
-  if (pruned) {  // the indices of ALL clouds of the batch in one call, as align_impl builds them
-    std::vector<std::pair<gorio_apd*, DevCloud*>> all;
-    for (int q = 0; q < count; ++q) {
-      all.emplace_back(hs[q], hs[q]->src.get());
-      all.emplace_back(hs[q], hs[q]->tgt.get());
-    }
-    rc = run_index_build(lead, all);
-    if (rc) return rc;
-  }
+  // ---- search indices and covariances: a cloud several handles hold is made once
+  int rc = batch_prepare_search(hs, count);
+  if (rc) return rc;
   {
     std::unordered_set<DevCloud*> seen;
     std::vector<std::pair<gorio_apd*, DevCloud*>> stale;
@@ -641,151 +622,101 @@ int gomp_align_batch(gorio_apd** hs, int count, const float* guesses, float* T_o
       gorio_apd* first = stale.front().first;
       std::vector<std::pair<gorio_apd*, DevCloud*>> todo, rest;
       for (auto& t : stale) (t.first->gomp_eps == first->gomp_eps ? todo : rest).push_back(t);
-      rc = run_covariances(first, todo);
-      if (rc) {
-        if (first != lead) lead->err = first->err;
-        return rc;
-      }
+      rc = hand_over(lead, first, run_covariances(first, todo));
+      if (rc) return rc;
       stale.swap(rest);
     }
   }
   size_t max_blocks = 0;
-  for (int q = 0; q < count; ++q) {
-    gorio_apd* h = hs[q];
-    rc = gomp_reserve(h);
-    if (!rc) rc = gomp_set_guess(h, guesses + (size_t)16 * q);
-    if (rc) {
-      if (h != lead) lead->err = h->err;
-      return rc;
-    }
-    HIP_TRY(lead, hipMemsetAsync(h->best_key, 0xff, sizeof(unsigned long long) * h->src->n, lead->stream));  // gomp_update_block re-arms it
-    max_blocks += (size_t)(h->src->n + 255) / 256;
-  }
-  if (max_blocks > (size_t)INT_MAX / 16) return fail(lead, GORIO_ERR_INVALID, "gicp_omp_align_batch: too many source points in one batch");
-  // ---- scratch for the largest possible round: every handle pending
-  rc = ensure_batch(lead, count);
+  rc = batch_arm_handles(hs, count, [&](int q) {
+    max_blocks += (size_t)(hs[q]->src->n + 255) / 256;
+    const int rc2 = gomp_reserve(hs[q]);
+    return rc2 ? rc2 : gomp_set_guess(hs[q], guesses + (size_t)16 * q);
+  });
   if (rc) return rc;
-  const size_t table_bytes = sizeof(GompJob) * (size_t)count + sizeof(int2) * max_blocks;
-  const size_t out_bytes = (sizeof(double) * 13 + sizeof(int)) * (size_t)count;
-  HIP_TRY(lead, lead->gomp_b_jobs.reserve(table_bytes, table_bytes + table_bytes / 4));
-  HIP_TRY(lead, lead->gomp_b_part.reserve(13 * max_blocks, 13 * (max_blocks + max_blocks / 4)));
-  HIP_TRY(lead, lead->gomp_b_cnt.reserve(max_blocks, max_blocks + max_blocks / 4));
-  HIP_TRY(lead, lead->gomp_b_out.reserve(out_bytes, out_bytes + out_bytes / 4));
-  HIP_TRY(lead, lead->gomp_b_h_out.reserve(out_bytes, out_bytes + out_bytes / 4));
+  if (batch_rounds::too_many_wg(max_blocks, 16)) return fail(lead, GORIO_ERR_INVALID, "gicp_omp_align_batch: too many source points in one batch");
+  if ((rc = ensure_batch(lead, count))) return rc;
   std::vector<GompMachine> mc(count);
   for (int q = 0; q < count; ++q) mc[q].begin(hs[q], guesses + (size_t)16 * q);
-  std::vector<unsigned char> table(table_bytes);
   std::vector<PairDesc> descs(count);
   std::vector<PairState> states(count);
-  std::vector<int> order;
-  order.reserve(count);
-  int rounds = 0, launches = count;  // one gomp_output_kernel launch per handle so far
-  for (;;) {
-    // job k of the round belongs to handle order[k]: the updates first, then the evaluations
-    order.clear();
-    for (int q = 0; q < count; ++q)
-      if (mc[q].state == GompMachine::kUpdate) order.push_back(q);
-    const int n_upd = (int)order.size();
-    for (int q = 0; q < count; ++q)
-      if (mc[q].state == GompMachine::kEvaluate) order.push_back(q);
-    const int njobs = (int)order.size();
-    if (njobs == 0) break;
-    GompJob* const jobs = reinterpret_cast<GompJob*>(table.data());
-    int2* const wg = reinterpret_cast<int2*>(jobs + njobs);
-    long upd_waves = 0;
-    int upd_max_n = 0, upd_max_m = 0;
-    for (int k = 0; k < n_upd; ++k) {
-      upd_waves += (hs[order[k]]->src->n + 63) / 64;
-      upd_max_n = std::max(upd_max_n, hs[order[k]]->src->n);
-      upd_max_m = std::max(upd_max_m, hs[order[k]]->tgt->n);
+  RoundCounters ctr;
+  ctr.launches = count;  // one gomp_output_kernel launch per handle so far
+  // job k of the round belongs to handle order[k]: the updates (the leading class) first, then the evaluations
+  auto pending = [&](int q) { return mc[q].state == GompMachine::kUpdate ? 0 : mc[q].state == GompMachine::kEvaluate ? 1 : -1; };
+  auto fill = [&](int, int q, GompJob& j) {
+    gorio_apd* h = hs[q];
+    const GompMachine& m = mc[q];
+    float* o = h->gomp_out;
+    const size_t st = h->gomp_out.cap() / 3;
+    j.ox = o; j.oy = o + st; j.oz = o + 2 * st;
+    j.tgt = h->tgt->p4;
+    j.corr = h->corr;
+    j.maha = h->gomp_maha;
+    j.n = h->src->n;
+    j.n_tgt = h->tgt->n;
+    if (m.state == GompMachine::kUpdate) {
+      j.mode = 3;
+      j.best_key = h->best_key;
+      j.c1 = h->src->cov6;
+      j.c2 = h->tgt->cov6;
+      j.sqd = h->sqd;
+      j.R = gomp_make_r(h, m.Tr);
+    } else {
+      j.mode = m.mode;
+      float T[16];
+      gomp_apply_state(m.x, T);
+      for (int i = 0; i < 12; ++i) j.tf.m[i] = T[i];
     }
-    int slot = 0, upd_blocks = 0, max_splits = 1;
-    for (int k = 0; k < njobs; ++k) {
-      gorio_apd* h = hs[order[k]];
-      const GompMachine& m = mc[order[k]];
-      const int n = h->src->n;
-      float* o = h->gomp_out;
-      const size_t st = h->gomp_out.cap() / 3;
-      GompJob& j = jobs[k];
-      std::memset(&j, 0, sizeof(j));
-      j.ox = o; j.oy = o + st; j.oz = o + 2 * st;
-      j.tgt = h->tgt->p4;
-      j.corr = h->corr;
-      j.maha = h->gomp_maha;
-      j.n = n;
-      j.n_tgt = h->tgt->n;
-      j.first = slot;
-      j.nblk = (n + 255) / 256;
-      if (k < n_upd) {
-        j.mode = 3;
-        j.best_key = h->best_key;
-        j.c1 = h->src->cov6;
-        j.c2 = h->tgt->cov6;
-        j.sqd = h->sqd;
-        j.R = gomp_make_r(h, m.Tr);
-        PairDesc& d = descs[k];
-        fill_desc(h, d, lead->d_states_batch + k, upd_waves);
-        d.src.x = o; d.src.y = o + st; d.src.z = o + 2 * st;  // the searches read the `output` copy
-        d.src.idx.s4 = h->gomp_s4;
-        max_splits = std::max(max_splits, d.nn_splits);
-        double Td[16];
-        for (int i = 0; i < 16; ++i) Td[i] = (double)m.Tr[i];
-        init_state(states[k], Td);
-        for (int i = 0; i < 12; ++i) states[k].Tf[i] = m.Tr[i];
-        upd_blocks += j.nblk;
-      } else {
-        j.mode = m.mode;
-        float T[16];
-        gomp_apply_state(m.x, T);
-        for (int i = 0; i < 12; ++i) j.tf.m[i] = T[i];
-      }
-      for (int b = 0; b < j.nblk; ++b) wg[slot + b] = make_int2(k, b);  // x < njobs, y < nblk: what the kernels rely on
-      slot += j.nblk;
-    }
-    const size_t bytes = sizeof(GompJob) * (size_t)njobs + sizeof(int2) * (size_t)slot;  // <= table_bytes
-    if (int rc2 = upload_staged(lead, lead->pin_gomp_jobs, lead->gomp_b_jobs, table.data(), bytes)) return rc2;
-    const GompJob* d_jobs = static_cast<const GompJob*>(lead->gomp_b_jobs.get());
-    const int2* d_wg = reinterpret_cast<const int2*>(d_jobs + njobs);
+    const int nblk = (j.n + 255) / 256;
+    return batch_rounds::JobShape{nblk, nblk, false};
+  };
+  auto launch = [&](const RoundView<GompJob>& v, int& launches) {
+    const int n_upd = v.plan.n_leading;
     if (n_upd > 0) {
+      long upd_waves = 0;
+      int upd_max_n = 0, upd_max_m = 0, max_splits = 1;
+      for (int k = 0; k < n_upd; ++k) {
+        upd_waves += (hs[v.order[k]]->src->n + 63) / 64;
+        upd_max_n = std::max(upd_max_n, hs[v.order[k]]->src->n);
+        upd_max_m = std::max(upd_max_m, hs[v.order[k]]->tgt->n);
+      }
+      for (int k = 0; k < n_upd; ++k) {  // the searches read the `output` copy
+        gorio_apd* h = hs[v.order[k]];
+        fill_moved_search(h, descs[k], states[k], lead->d_states_batch + k, upd_waves, v.jobs[k].ox, v.jobs[k].oy, v.jobs[k].oz, h->gomp_s4, mc[v.order[k]].Tr);
+        max_splits = std::max(max_splits, descs[k].nn_splits);
+      }
       if (int rc2 = upload_staged(lead, lead->pin_desc, lead->d_desc, descs.data(), sizeof(PairDesc) * n_upd)) return rc2;
       if (int rc2 = upload_staged(lead, lead->pin_states, lead->d_states_batch, states.data(), sizeof(PairState) * n_upd)) return rc2;
       launch_nn(lead, lead->d_desc, dim3((upd_max_n + 255) / 256, max_splits, n_upd), roundup(upd_max_n, 512), n_upd, upd_max_m);
-      gomp_update_batch_kernel<<<upd_blocks, 256, 0, lead->stream>>>(d_jobs, d_wg, lead->gomp_b_cnt);
+      gomp_update_batch_kernel<<<v.plan.lead_wg, 256, 0, lead->stream>>>(v.d_jobs, v.d_refs, lead->round.cnt);
       launches += 2;
     }
-    if (slot > upd_blocks) {
-      gomp_functor_batch_kernel<<<slot - upd_blocks, 256, 0, lead->stream>>>(d_jobs, d_wg + upd_blocks, lead->gomp_b_part);
+    if (v.plan.wg > v.plan.lead_wg) {
+      gomp_functor_batch_kernel<<<v.plan.wg - v.plan.lead_wg, 256, 0, lead->stream>>>(v.d_jobs, v.d_refs + v.plan.lead_wg, lead->round.part);
       ++launches;
     }
-    double* d_out = static_cast<double*>(lead->gomp_b_out.get());
-    int* d_pairs = reinterpret_cast<int*>(d_out + (size_t)13 * njobs);
-    gomp_fold_batch_kernel<<<njobs, 64, 0, lead->stream>>>(d_jobs, lead->gomp_b_part, lead->gomp_b_cnt, d_out, d_pairs);
-    ++launches;
-    HIP_TRY(lead, hipGetLastError());
-    HIP_TRY(lead, hipMemcpyAsync(lead->gomp_b_h_out.get(), d_out, (sizeof(double) * 13 + sizeof(int)) * (size_t)njobs, hipMemcpyDeviceToHost, lead->stream));
-    HIP_TRY(lead, hipStreamSynchronize(lead->stream));
-    const double* sums = static_cast<const double*>(lead->gomp_b_h_out.get());
-    const int* pairs = reinterpret_cast<const int*>(sums + (size_t)13 * njobs);
-    for (int k = 0; k < njobs; ++k) {
-      gorio_apd* h = hs[order[k]];
-      GompMachine& m = mc[order[k]];
-      if (k < n_upd) {
-        h->gomp_pairs = pairs[k];
-        h->corr_valid = true;
-        h->omega_valid = true;
-        m.update_done(pairs[k]);
-      } else {
-        double f = NAN, g[6] = {NAN, NAN, NAN, NAN, NAN, NAN};
-        gomp_finish_evaluation(h, m.x, m.mode, sums + (size_t)13 * k, &f, g);
-        m.evaluation_done(f, g);
-      }
+    return (int)GORIO_OK;
+  };
+  auto consume = [&](int, int q, const double* sums, int pairs) {
+    gorio_apd* h = hs[q];
+    GompMachine& m = mc[q];
+    if (m.state == GompMachine::kUpdate) {
+      h->gomp_pairs = pairs;
+      h->corr_valid = true;
+      h->omega_valid = true;
+      m.update_done(pairs);
+    } else {
+      double f = NAN, g[6] = {NAN, NAN, NAN, NAN, NAN, NAN};
+      gomp_finish_evaluation(h, m.x, m.mode, sums, &f, g);
+      m.evaluation_done(f, g);
     }
-    ++rounds;
-  }
+  };
+  if ((rc = run_rounds<GompRounds>(lead, count, max_blocks, ctr, pending, fill, launch, consume))) return rc;
   for (int q = 0; q < count; ++q)
     mc[q].results(T_out + (size_t)16 * q, converged ? converged + q : nullptr, nr_iterations ? nr_iterations + q : nullptr, n_evaluations ? n_evaluations + q : nullptr);
-  lead->gomp_b_rounds = rounds;
-  lead->gomp_b_launches = launches;
+  lead->gomp_b_rounds = ctr.rounds;
+  lead->gomp_b_launches = ctr.launches;
   resolve_stage_events(lead);
   return GORIO_OK;
 }
@@ -856,33 +787,11 @@ int gorio_apd_gicp_omp_diag(const gorio_apd_t* h, int* outer, int* inner_total, 
 
 int gorio_apd_gicp_omp_align_batch(gorio_apd_t** handles, int count, const float* guesses, float* T_out, int* converged, int* nr_iterations, int* n_evaluations) {
   if (count == 0) return GORIO_OK;
-  if (count < 0 || !handles || !guesses || !T_out) return GORIO_ERR_INVALID;
-  for (int q = 0; q < count; ++q)
-    if (!handles[q]) return handles[0] ? fail(handles[0], GORIO_ERR_INVALID, "gicp_omp_align_batch: handle " + std::to_string(q) + " is null") : GORIO_ERR_INVALID;
+  if (int rc = batch_front_door("gicp_omp_align_batch", handles, count, guesses, T_out, true, [](const gorio_apd* h) { return h->method == GORIO_METHOD_GICP_OMP; }, "the handle's method is not GORIO_METHOD_GICP_OMP", check_ready)) return rc;
   gorio_apd* lead = handles[0];
-  // ---- validation: nothing is built, allocated or launched before every handle has passed
-  auto refuse = [&](int q, int code, const std::string& why) { return fail(lead, code, "gicp_omp_align_batch: handle " + std::to_string(q) + ": " + why); };
-  std::unordered_set<gorio_apd*> distinct;
-  for (int q = 0; q < count; ++q) {
-    gorio_apd* h = handles[q];
-    if (h->device != lead->device) return refuse(q, GORIO_ERR_INVALID, "all handles of a batch must live on one device");
-    if (!distinct.insert(h).second) return refuse(q, GORIO_ERR_INVALID, "the same handle appears twice in a batch (its buffers would be raced on)");
-    if (h->comm || (h->shard_only && h->comm_world > 1)) return refuse(q, GORIO_ERR_INVALID, "a handle with a communicator (sharded source) cannot be part of a batch");
-    if (h->method != GORIO_METHOD_GICP_OMP) return refuse(q, GORIO_ERR_STATE, "the handle's method is not GORIO_METHOD_GICP_OMP");
-    gorio_apd_params a = h->params, b = lead->params;
-    a.cl_weight_points = b.cl_weight_points = 0;
-    if (std::memcmp(&a, &b, sizeof(a)) != 0) return refuse(q, GORIO_ERR_INVALID, "all handles of a batch must carry the same parameters (cl_weight_points excepted)");
-  }
-  for (int q = 0; q < count; ++q) {
-    gorio_apd* h = handles[q];
-    const std::string kept = h->err;
-    const int rc = check_ready(h);
-    if (rc) {
-      const std::string why = h->err;
-      if (h != lead) h->err = kept;
-      return refuse(q, rc, why);
-    }
-  }
+  for (int q = 0; q < count; ++q)
+    if (handles[q]->comm || (handles[q]->shard_only && handles[q]->comm_world > 1))
+      return fail(lead, GORIO_ERR_INVALID, "gicp_omp_align_batch: handle " + std::to_string(q) + ": a handle with a communicator (sharded source) cannot be part of a batch");
   HIP_TRY(lead, hipSetDevice(lead->device));
   return gomp_align_batch(handles, count, guesses, T_out, converged, nr_iterations, n_evaluations);
 }

@@ -39,12 +39,12 @@ constexpr int kIcpSums = 17;
 
 // grid: the reciprocal jobs' source blocks, block 256.  Lane = source point i with search winner j: the lowest-index nearest point of
 // target j among q_k = tf * p_k, k < n (the distances are those of the forward search: sqdist3 is even in its difference).
-__global__ __launch_bounds__(256) void icp_recip_batch_kernel(const IcpJob* __restrict__ jobs, const int2* __restrict__ wg) {
+__global__ __launch_bounds__(256) void icp_recip_batch_kernel(const IcpJob* __restrict__ jobs, const BlockRef* __restrict__ wg) {
   __shared__ float s_x[256], s_y[256], s_z[256];
-  const int2 w = wg[blockIdx.x];
-  const IcpJob& j = jobs[w.x];
+  const BlockRef w = wg[blockIdx.x];
+  const IcpJob& j = jobs[w.job];
   const int n = j.n;
-  const int i = w.y * 256 + threadIdx.x;
+  const int i = w.blk * 256 + threadIdx.x;
   bool live = false;
   float tx = 0.f, ty = 0.f, tz = 0.f;
   if (i < n) {
@@ -131,23 +131,19 @@ __device__ __forceinline__ void icp_pairs_block(const IcpJob& j, int block, doub
   }
 }
 
-// grid: the sum over the round's jobs of nwg, block 256.  wg[blockIdx.x] = (job, job-local block), written by the host with the job
-// table: wg[].x < number of jobs, wg[].y < jobs[wg[].x].nwg; the partial buffer holds a slot for every workgroup of the launch.
-__global__ __launch_bounds__(256) void icp_pairs_batch_kernel(const IcpJob* __restrict__ jobs, const int2* __restrict__ wg, double* __restrict__ partials) {
+// grid: the sum over the round's jobs of nwg, block 256.  wg[blockIdx.x] = (job, job-local block) of the round table (batch_rounds.h):
+// job < number of jobs, blk < jobs[job].nwg; the partial buffer holds a slot for every workgroup of the launch.
+__global__ __launch_bounds__(256) void icp_pairs_batch_kernel(const IcpJob* __restrict__ jobs, const BlockRef* __restrict__ wg, double* __restrict__ partials) {
   __shared__ double s_red[4 * kIcpSums];
-  const int2 w = wg[blockIdx.x];
-  const IcpJob& j = jobs[w.x];
-  icp_pairs_block(j, w.y, s_red, partials + (size_t)(j.first + w.y) * kIcpSums);
+  const BlockRef w = wg[blockIdx.x];
+  const IcpJob& j = jobs[w.job];
+  icp_pairs_block(j, w.blk, s_red, partials + (size_t)(j.first + w.blk) * kIcpSums);
 }
 
 // grid: the round's jobs, block 64.  Lane q adds the job's partials of value q in block order into out[17 job + q].
 __global__ __launch_bounds__(64) void icp_fold_batch_kernel(const IcpJob* __restrict__ jobs, const double* __restrict__ partials, double* __restrict__ out) {
   const IcpJob& j = jobs[blockIdx.x];
-  const int q = threadIdx.x;
-  if (q >= kIcpSums) return;
-  double s = 0.0;
-  for (int b = 0; b < j.nblk; ++b) s += partials[(size_t)(j.first + b) * kIcpSums + q];
-  out[(size_t)blockIdx.x * kIcpSums + q] = s;
+  fold_wave<kIcpSums>(partials + (size_t)j.first * kIcpSums, j.nblk, out + (size_t)blockIdx.x * kIcpSums);
 }
 
 }  // namespace gorio
@@ -335,152 +331,99 @@ int icp_reserve(gorio_apd* h) {
   return GORIO_OK;
 }
 
+struct IcpRounds {  // the round table of run_rounds
+  using Job = IcpJob;
+  static constexpr int kSums = kIcpSums;
+  static constexpr bool kCounts = false, kSecondList = true;  // the second list: the source blocks of the reciprocal jobs
+  static void fold(int njobs, hipStream_t stream, const IcpJob* jobs, const double* part, const int*, double* out, int*) { icp_fold_batch_kernel<<<njobs, 64, 0, stream>>>(jobs, part, out); }
+};
+
 // The lock-step rounds behind gorio_apd_align (count 1), gorio_apd_icp_align_batch and gorio_apd_icp_step (step_T != null: one pass of
 // hs[0] on step_T * source, no machine).  Per round: one search launch, one reciprocal launch when a pending handle asks for it, one pairs
-// launch, one fold launch, one copy back, one synchronisation -- on the stream and with the tables of hs[0].
-int icp_run(gorio_apd** hs, int count, const float* guesses, float* T_out, int* converged, int* nr_iterations, int* n_linearize, const float* step_T, double* step_sums) {
+// launch, one fold launch, one copy back, one synchronisation -- on the stream and with the tables of hs[0].  ctr: the rounds and launches.
+int icp_run(gorio_apd** hs, int count, const float* guesses, float* T_out, int* converged, int* nr_iterations, int* n_linearize, const float* step_T, double* step_sums,
+            RoundCounters& ctr) {
   gorio_apd* lead = hs[0];
   const bool pruned = lead->params.search == GORIO_SEARCH_PRUNED;
-  int rc = GORIO_OK;
+  if (int rc = batch_prepare_search(hs, count)) return rc;
   size_t max_wg = 0;
-  for (int q = 0; q < count; ++q) {
-    gorio_apd* h = hs[q];
-    rc = ensure_points(h, h->src->n);
-    if (!rc) rc = icp_reserve(h);
-    if (rc) {
-      if (h != lead) lead->err = h->err;
-      return rc;
-    }
-  }
-  if (pruned) {  // the indices of ALL clouds of the batch in one call, as align_impl builds them
-    std::vector<std::pair<gorio_apd*, DevCloud*>> all;
-    for (int q = 0; q < count; ++q) {
-      all.emplace_back(hs[q], hs[q]->src.get());
-      all.emplace_back(hs[q], hs[q]->tgt.get());
-    }
-    rc = run_index_build(lead, all);
-    if (rc) return rc;
-  }
-  for (int q = 0; q < count; ++q) {
-    gorio_apd* h = hs[q];
-    HIP_TRY(lead, hipMemsetAsync(h->best_key, 0xff, sizeof(unsigned long long) * h->src->n, lead->stream));  // icp_pairs_block re-arms it
-    const int cover = std::max(h->src->n, pruned ? h->src->idx_spad : 0);
+  const int armed = batch_arm_handles(hs, count, [&](int q) {
+    const int cover = std::max(hs[q]->src->n, pruned ? hs[q]->src->idx_spad : 0);
     max_wg += (size_t)(cover + 255) / 256;
-  }
-  if (max_wg > (size_t)INT_MAX / 32) return fail(lead, GORIO_ERR_INVALID, "icp_align_batch: too many source points in one batch");
-  rc = ensure_batch(lead, count);
-  if (rc) return rc;
-  const size_t table_bytes = sizeof(IcpJob) * (size_t)count + sizeof(int2) * 2 * max_wg;
-  const size_t out_bytes = sizeof(double) * kIcpSums * (size_t)count;
-  HIP_TRY(lead, lead->icp_b_jobs.reserve(table_bytes, table_bytes + table_bytes / 4));
-  HIP_TRY(lead, lead->icp_b_part.reserve(kIcpSums * max_wg, kIcpSums * (max_wg + max_wg / 4)));
-  HIP_TRY(lead, lead->icp_b_out.reserve(out_bytes, out_bytes + out_bytes / 4));
-  HIP_TRY(lead, lead->icp_b_h_out.reserve(out_bytes, out_bytes + out_bytes / 4));
+    return icp_reserve(hs[q]);
+  });
+  if (armed) return armed;
+  if (batch_rounds::too_many_wg(max_wg, 32)) return fail(lead, GORIO_ERR_INVALID, "icp_align_batch: too many source points in one batch");
+  if (int rc = ensure_batch(lead, count)) return rc;
   std::vector<IcpMachine> mc(count);
   if (!step_T)
     for (int q = 0; q < count; ++q) mc[q].begin(hs[q], guesses + (size_t)16 * q);
   std::vector<char> first_pass(count, 1);
-  std::vector<unsigned char> table(table_bytes);
   std::vector<PairDesc> descs(count);
   std::vector<PairState> states(count);
-  std::vector<int> order;
-  order.reserve(count);
-  int rounds = 0, launches = 0;
-  for (;;) {
-    order.clear();
-    for (int q = 0; q < count; ++q)
-      if (step_T ? rounds == 0 : !mc[q].done()) order.push_back(q);
-    const int njobs = (int)order.size();
-    if (njobs == 0) break;
-    IcpJob* const jobs = reinterpret_cast<IcpJob*>(table.data());
-    int2* const wg = reinterpret_cast<int2*>(jobs + njobs);
+  bool stepped = false;
+  auto tr_of = [&](int q) { return step_T ? step_T : mc[q].Tr; };
+  auto pending = [&](int q) { return (step_T ? !stepped : !mc[q].done()) ? 0 : -1; };
+  auto fill = [&](int, int q, IcpJob& j) {
+    gorio_apd* h = hs[q];
+    const DevCloud& s = *h->src;
+    const int n = s.n;
+    float* o = h->icp_w;
+    const size_t st = h->icp_w.cap() / 3;
+    const bool first = first_pass[q] != 0;
+    first_pass[q] = 0;
+    j.ix = first ? s.x.get() : o; j.iy = first ? s.y.get() : o + st; j.iz = first ? s.z.get() : o + 2 * st;
+    j.ox = o; j.oy = o + st; j.oz = o + 2 * st;
+    j.s4_in = pruned ? (first ? s.idx_s4.get() : h->icp_s4.get()) : nullptr;
+    j.s4_out = h->icp_s4;
+    j.tgt = h->tgt->p4;
+    j.best_key = h->best_key;
+    j.corr = h->corr;
+    j.sqd = h->sqd;
+    j.rflag = h->icp_rflag;
+    for (int i = 0; i < 12; ++i) j.tf.m[i] = tr_of(q)[i];
+    j.thr2 = h->params.corr_dist_threshold * h->params.corr_dist_threshold;
+    j.n = n;
+    j.n_tgt = h->tgt->n;
+    j.n_spad = pruned ? s.idx_spad : 0;
+    j.recip = h->icp_reciprocal;
+    j.nwg = (std::max(n, j.n_spad) + 255) / 256;
+    return batch_rounds::JobShape{(n + 255) / 256, j.nwg, j.recip != 0};
+  };
+  auto launch = [&](const RoundView<IcpJob>& v, int& launches) {
+    const int njobs = v.plan.njobs;
     long waves = 0;
-    int max_n = 0, max_m = 0, max_splits = 1, slot = 0, n_recip_wg = 0;
-    for (int k = 0; k < njobs; ++k) {
-      waves += (hs[order[k]]->src->n + 63) / 64;
-      max_n = std::max(max_n, hs[order[k]]->src->n);
-      max_m = std::max(max_m, hs[order[k]]->tgt->n);
+    int max_n = 0, max_m = 0, max_splits = 1;
+    for (int q : v.order) {
+      waves += (hs[q]->src->n + 63) / 64;
+      max_n = std::max(max_n, hs[q]->src->n);
+      max_m = std::max(max_m, hs[q]->tgt->n);
     }
-    for (int k = 0; k < njobs; ++k) {
-      gorio_apd* h = hs[order[k]];
-      const DevCloud& s = *h->src;
-      const int n = s.n;
-      const float* Tr = step_T ? step_T : mc[order[k]].Tr;
-      float* o = h->icp_w;
-      const size_t st = h->icp_w.cap() / 3;
-      const bool first = first_pass[order[k]] != 0;
-      IcpJob& j = jobs[k];
-      std::memset(&j, 0, sizeof(j));
-      j.ix = first ? s.x.get() : o; j.iy = first ? s.y.get() : o + st; j.iz = first ? s.z.get() : o + 2 * st;
-      j.ox = o; j.oy = o + st; j.oz = o + 2 * st;
-      j.s4_in = pruned ? (first ? s.idx_s4.get() : h->icp_s4.get()) : nullptr;
-      j.s4_out = h->icp_s4;
-      j.tgt = h->tgt->p4;
-      j.best_key = h->best_key;
-      j.corr = h->corr;
-      j.sqd = h->sqd;
-      j.rflag = h->icp_rflag;
-      for (int i = 0; i < 12; ++i) j.tf.m[i] = Tr[i];
-      j.thr2 = h->params.corr_dist_threshold * h->params.corr_dist_threshold;
-      j.n = n;
-      j.n_tgt = h->tgt->n;
-      j.n_spad = pruned ? s.idx_spad : 0;
-      j.recip = h->icp_reciprocal;
-      j.first = slot;
-      j.nblk = (n + 255) / 256;
-      j.nwg = (std::max(n, j.n_spad) + 255) / 256;
-      for (int b = 0; b < j.nwg; ++b) wg[slot + b] = make_int2(k, b);  // x < njobs, y < nwg: what the kernels rely on
-      slot += j.nwg;
-      PairDesc& d = descs[k];
-      fill_desc(h, d, lead->d_states_batch + k, waves);
-      d.src.x = const_cast<float*>(j.ix); d.src.y = const_cast<float*>(j.iy); d.src.z = const_cast<float*>(j.iz);  // the searches read the copy
-      d.src.idx.s4 = const_cast<float4*>(j.s4_in);
-      max_splits = std::max(max_splits, d.nn_splits);
-      double Td[16];
-      for (int i = 0; i < 16; ++i) Td[i] = (double)Tr[i];
-      init_state(states[k], Td);
-      for (int i = 0; i < 12; ++i) states[k].Tf[i] = Tr[i];
-      first_pass[order[k]] = 0;
+    for (int k = 0; k < njobs; ++k) {  // the searches read the copy the job reads
+      const IcpJob& j = v.jobs[k];
+      fill_moved_search(hs[v.order[k]], descs[k], states[k], lead->d_states_batch + k, waves, j.ix, j.iy, j.iz, j.s4_in, tr_of(v.order[k]));
+      max_splits = std::max(max_splits, descs[k].nn_splits);
     }
-    int2* const rwg = wg + slot;  // the source blocks of the reciprocal jobs
-    for (int k = 0; k < njobs; ++k)
-      if (jobs[k].recip)
-        for (int b = 0; b < jobs[k].nblk; ++b) rwg[n_recip_wg++] = make_int2(k, b);
-    const size_t bytes = sizeof(IcpJob) * (size_t)njobs + sizeof(int2) * (size_t)(slot + n_recip_wg);  // <= table_bytes
-    if (int rc2 = upload_staged(lead, lead->pin_icp_jobs, lead->icp_b_jobs, table.data(), bytes)) return rc2;
     if (int rc2 = upload_staged(lead, lead->pin_desc, lead->d_desc, descs.data(), sizeof(PairDesc) * njobs)) return rc2;
     if (int rc2 = upload_staged(lead, lead->pin_states, lead->d_states_batch, states.data(), sizeof(PairState) * njobs)) return rc2;
-    const IcpJob* d_jobs = static_cast<const IcpJob*>(lead->icp_b_jobs.get());
-    const int2* d_wg = reinterpret_cast<const int2*>(d_jobs + njobs);
     launch_nn(lead, lead->d_desc, dim3((max_n + 255) / 256, max_splits, njobs), roundup(max_n, 512), njobs, max_m, -1, true);
-    ++launches;
-    if (n_recip_wg > 0) {
-      icp_recip_batch_kernel<<<n_recip_wg, 256, 0, lead->stream>>>(d_jobs, d_wg + slot);
-      ++launches;
-    }
-    icp_pairs_batch_kernel<<<slot, 256, 0, lead->stream>>>(d_jobs, d_wg, lead->icp_b_part);
-    double* d_out = static_cast<double*>(lead->icp_b_out.get());
-    icp_fold_batch_kernel<<<njobs, 64, 0, lead->stream>>>(d_jobs, lead->icp_b_part, d_out);
-    launches += 2;
-    HIP_TRY(lead, hipGetLastError());
-    HIP_TRY(lead, hipMemcpyAsync(lead->icp_b_h_out.get(), d_out, sizeof(double) * kIcpSums * (size_t)njobs, hipMemcpyDeviceToHost, lead->stream));
-    HIP_TRY(lead, hipStreamSynchronize(lead->stream));
-    const double* sums = static_cast<const double*>(lead->icp_b_h_out.get());
-    ++rounds;
-    if (step_T) {
-      std::memcpy(step_sums, sums, sizeof(double) * kIcpSums);
-      lead->icp_pairs = (int)sums[0];
-      lead->corr_valid = true;
-      lead->omega_valid = false;
-      break;
-    }
-    for (int k = 0; k < njobs; ++k) mc[order[k]].pass_done(sums + (size_t)kIcpSums * k);
-  }
+    if (v.plan.second > 0) icp_recip_batch_kernel<<<v.plan.second, 256, 0, lead->stream>>>(v.d_jobs, v.d_refs + v.plan.wg);
+    icp_pairs_batch_kernel<<<v.plan.wg, 256, 0, lead->stream>>>(v.d_jobs, v.d_refs, lead->round.part);
+    launches += v.plan.second > 0 ? 3 : 2;
+    return (int)GORIO_OK;
+  };
+  auto consume = [&](int, int q, const double* sums, int) {
+    if (!step_T) return mc[q].pass_done(sums);
+    std::memcpy(step_sums, sums, sizeof(double) * kIcpSums);
+    lead->icp_pairs = (int)sums[0];
+    lead->corr_valid = true;
+    lead->omega_valid = false;
+    stepped = true;
+  };
+  if (int rc = run_rounds<IcpRounds>(lead, count, max_wg, ctr, pending, fill, launch, consume)) return rc;
   if (!step_T)
     for (int q = 0; q < count; ++q)
       mc[q].results(T_out + (size_t)16 * q, converged ? converged + q : nullptr, nr_iterations ? nr_iterations + q : nullptr, n_linearize ? n_linearize + q : nullptr);
-  lead->icp_b_rounds = rounds;
-  lead->icp_b_launches = launches;
   resolve_stage_events(lead);
   return GORIO_OK;
 }
@@ -491,10 +434,8 @@ int icp_align(gorio_apd* h, const float* guess, float* T_out, double* H_out, int
   int rc = icp_check_ready(h);
   if (rc) return rc;
   gorio_apd* hs[1] = {h};
-  const int kept_rounds = h->icp_b_rounds, kept_launches = h->icp_b_launches;  // gorio_apd_icp_batch_diag speaks of batches only
-  rc = icp_run(hs, 1, guess, T_out, converged, nr_iterations, n_linearize, nullptr, nullptr);
-  h->icp_b_rounds = kept_rounds;
-  h->icp_b_launches = kept_launches;
+  RoundCounters ctr;  // dropped: gorio_apd_icp_batch_diag speaks of batches only
+  rc = icp_run(hs, 1, guess, T_out, converged, nr_iterations, n_linearize, nullptr, nullptr, ctr);
   if (rc) return rc;
   if (H_out) std::memset(H_out, 0, sizeof(double) * 36);
   return GORIO_OK;
@@ -540,10 +481,8 @@ int gorio_apd_icp_step(gorio_apd_t* h, const float T16[16], int* pairs, double s
   if (rc) return rc;
   gorio_apd* hs[1] = {h};
   double s[kIcpSums];
-  const int kept_rounds = h->icp_b_rounds, kept_launches = h->icp_b_launches;
-  rc = icp_run(hs, 1, nullptr, nullptr, nullptr, nullptr, nullptr, T16, s);
-  h->icp_b_rounds = kept_rounds;
-  h->icp_b_launches = kept_launches;
+  RoundCounters ctr;
+  rc = icp_run(hs, 1, nullptr, nullptr, nullptr, nullptr, nullptr, T16, s, ctr);
   if (rc) return rc;
   if (pairs) *pairs = (int)s[0];
   if (sums17) std::memcpy(sums17, s, sizeof(s));
@@ -557,34 +496,15 @@ int gorio_apd_icp_step(gorio_apd_t* h, const float T16[16], int* pairs, double s
 
 int gorio_apd_icp_align_batch(gorio_apd_t** handles, int count, const float* guesses, float* T_out, int* converged, int* nr_iterations) {
   if (count == 0) return GORIO_OK;
-  if (count < 0 || !handles || !guesses || !T_out) return GORIO_ERR_INVALID;
-  for (int q = 0; q < count; ++q)
-    if (!handles[q]) return handles[0] ? fail(handles[0], GORIO_ERR_INVALID, "icp_align_batch: handle " + std::to_string(q) + " is null") : GORIO_ERR_INVALID;
+  if (int rc = batch_front_door("icp_align_batch", handles, count, guesses, T_out, true, [](const gorio_apd* h) { return h->method == GORIO_METHOD_ICP; }, "the handle's method is not GORIO_METHOD_ICP", icp_check_ready)) return rc;
   gorio_apd* lead = handles[0];
-  // ---- validation: nothing is built, allocated or launched before every handle has passed
-  auto refuse = [&](int q, int code, const std::string& why) { return fail(lead, code, "icp_align_batch: handle " + std::to_string(q) + ": " + why); };
-  std::unordered_set<gorio_apd*> distinct;
-  for (int q = 0; q < count; ++q) {
-    gorio_apd* h = handles[q];
-    if (h->device != lead->device) return refuse(q, GORIO_ERR_INVALID, "all handles of a batch must live on one device");
-    if (!distinct.insert(h).second) return refuse(q, GORIO_ERR_INVALID, "the same handle appears twice in a batch (its buffers would be raced on)");
-    if (h->method != GORIO_METHOD_ICP) return refuse(q, GORIO_ERR_STATE, "the handle's method is not GORIO_METHOD_ICP");
-    gorio_apd_params a = h->params, b = lead->params;
-    a.cl_weight_points = b.cl_weight_points = 0;
-    if (std::memcmp(&a, &b, sizeof(a)) != 0) return refuse(q, GORIO_ERR_INVALID, "all handles of a batch must carry the same parameters (cl_weight_points excepted)");
-  }
-  for (int q = 0; q < count; ++q) {
-    gorio_apd* h = handles[q];
-    const std::string kept = h->err;
-    const int rc = icp_check_ready(h);
-    if (rc) {
-      const std::string why = h->err;
-      if (h != lead) h->err = kept;
-      return refuse(q, rc, why);
-    }
-  }
   HIP_TRY(lead, hipSetDevice(lead->device));
-  return icp_run(handles, count, guesses, T_out, converged, nr_iterations, nullptr, nullptr, nullptr);
+  RoundCounters ctr;
+  const int rc = icp_run(handles, count, guesses, T_out, converged, nr_iterations, nullptr, nullptr, nullptr, ctr);
+  if (rc) return rc;
+  lead->icp_b_rounds = ctr.rounds;
+  lead->icp_b_launches = ctr.launches;
+  return GORIO_OK;
 }
 
 int gorio_apd_icp_batch_diag(const gorio_apd_t* lead, int* rounds, int* launches) {
