@@ -2914,4 +2914,5 @@ extern "C" int gorio_debug_search_stats(unsigned long long out[24], int reset) {
 #include "apd_icp.hip"
 #include "../../include/gorio_search.h"
 #include "apd_search.hip"
+#include "apd_ndt_radius.hip"
 #include "apd_gicp_mp.hip"

@@ -1,4 +1,5 @@
-// apd_ndt.hip -- NDT_OMP registration (include/gorio_ndt.h): pclomp::NormalDistributionsTransform with the DIRECT1 / 7 / 26 searches.
+// apd_ndt.hip -- NDT_OMP registration (include/gorio_ndt.h): pclomp::NormalDistributionsTransform with the DIRECT1 / 7 / 26 searches, and
+// the radius neighbourhood of pcl::NormalDistributionsTransform / pclomp's KDTREE (gorio_ndt_set_radius_search).
 // Included by apd_api.hip after apd_sc.hip (it reuses the tiled bitonic sort, the voxel-start count / scan kernels, the fp64 Jacobi of
 // the covariance code and the 28-value wave reduction of linearize_kernel).
 //
@@ -16,13 +17,23 @@
 //                                         pending evaluations of many handles: a job table and a per-workgroup (job, local block) table
 //   score          ndt_score_kernel       calculateScore (NDT:935-983), one double per block, ndt_fold_kernel; ndt_score_batch_kernel runs
 //                                         the same body (ndt_score_block) over the job table of the batch for many handles
+//   radius mode    ndt_centroid_count_kernel, ndt_centroid_compact_kernel: once per map, the ordered compaction of the eligible leaves' float
+//                                         centroids (VGC:282-326) into SoA columns + a centroid -> leaf table; their search index is the library's
+//                  ndt_query_kernel       the float-transformed source, the queries of the radius search of apd_search.hip (a CSR)
+//                  ndt_derivative_csr_kernel, ndt_score_csr_kernel: one lane per source point walks its CSR segment through ndt_pair; the
+//                                         same wave_sum28 and block fold.  Batched: ndt_query_batch_kernel, ndt_derivative_csr_batch_kernel,
+//                                         ndt_score_csr_batch_kernel run the same bodies over the job table.  The host half that needs the
+//                                         search handle's type is apd_ndt_radius.hip
 //   device clouds  ndt_adopt_kernel       device arrays, the cloud of a scan pipeline or of a gorio_apd handle into the handle's own
 //                                         buffers: the copy and the finiteness check in one pass
 //   align          host                   computeTransformation, computeStepLengthMT and its helpers (NDT:81-171, 648-932) as ONE resumable
 //                                         machine (NdtMachine): gorio_ndt_align drives one, gorio_ndt_align_batch many in lock-step
-// The only device loops are bounded: points of a leaf (<= n), neighbours (<= 26), binary-search steps (<= 32).  Every index that comes
-// from data is range-checked before it addresses memory: a source point outside the grid reads nothing.
+// The only device loops are bounded: points of a leaf (<= n), neighbours (<= 26, or a CSR segment of the radius search: <= 27 centroids),
+// binary-search steps (<= 32).  Every index that comes from data is range-checked before it addresses memory: a source point outside the
+// grid reads nothing, a centroid index or leaf position outside its table is skipped.
 #include <hip/hip_runtime.h>
+
+#include "../../include/gorio_search.h"  // the centroid index of the radius mode is a search handle
 
 #include <algorithm>
 #include <cmath>
@@ -140,7 +151,7 @@ __device__ __forceinline__ void ndt_inv3(const double* __restrict__ a, double* _
 __global__ __launch_bounds__(256) void ndt_leaf_kernel(const unsigned long long* __restrict__ keys, const float* __restrict__ x, const float* __restrict__ y,
                                                        const float* __restrict__ z, int n, int n_points, const int* __restrict__ offsets, int min_points, double eig_mult,
                                                        int nl, int* __restrict__ lidx, int* __restrict__ lcnt, double* __restrict__ lmean, double* __restrict__ lraw,
-                                                       double* __restrict__ lcov, double* __restrict__ licov) {
+                                                       double* __restrict__ lcov, double* __restrict__ licov, float* __restrict__ lcent) {
   const RunStart rs = cell_run_start<31>(keys, n);
   if (!rs.start) return;
   const int p = blockIdx.x * 256 + threadIdx.x, rank = offsets[blockIdx.x] + rs.local;
@@ -148,12 +159,14 @@ __global__ __launch_bounds__(256) void ndt_leaf_kernel(const unsigned long long*
   const unsigned long long leaf = keys[p] >> 31;
   double s0 = 0.0, s1 = 0.0, s2 = 0.0;
   double c[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
+  float f0 = 0.0f, f1 = 0.0f, f2 = 0.0f;  // the centroid cloud's sums: float, in input order (VGC:242-243)
   int cnt = 0;
   for (int j = p; j < n && (keys[j] >> 31) == leaf; ++j) {
     const int i = (int)(keys[j] & 0x7fffffffull);
     if (i >= n_points) break;
     const double px = (double)x[i], py = (double)y[i], pz = (double)z[i];
     s0 += px; s1 += py; s2 += pz;  // VGC:235
+    f0 += x[i]; f1 += y[i]; f2 += z[i];
     c[0] += px * px; c[1] += px * py; c[2] += px * pz;  // VGC:237
     c[3] += py * px; c[4] += py * py; c[5] += py * pz;
     c[6] += pz * px; c[7] += pz * py; c[8] += pz * pz;
@@ -164,6 +177,11 @@ __global__ __launch_bounds__(256) void ndt_leaf_kernel(const unsigned long long*
   lidx[rank] = (int)leaf;
   double* om = lmean + (size_t)rank * 3;
   om[0] = m0; om[1] = m1; om[2] = m2;
+  {
+    const float nf = (float)cnt;  // VGC:289: a true division per element
+    float* oc = lcent + (size_t)rank * 3;
+    oc[0] = f0 / nf; oc[1] = f1 / nf; oc[2] = f2 / nf;
+  }
   double raw[9], cov[9], ic[9];
 #pragma unroll
   for (int q = 0; q < 9; ++q) raw[q] = cov[q] = ic[q] = 0.0;
@@ -218,6 +236,42 @@ __global__ __launch_bounds__(256) void ndt_leaf_kernel(const unsigned long long*
     lcov[(size_t)rank * 9 + q] = cov[q];
     licov[(size_t)rank * 9 + q] = out_cnt >= min_points ? ic[q] : 0.0;
   }
+}
+
+// ---- the centroid cloud of the radius mode (VGC:282-326): one point per leaf with nr_points >= min_points_per_voxel, in ascending leaf
+// index.  A leaf the eigenvalue or the infinity rule disabled afterwards (lcnt == -1: it had the points) stays in the cloud.
+__device__ __forceinline__ bool ndt_in_centroid_cloud(int cnt, int min_points) { return cnt == -1 || cnt >= min_points; }
+
+// counts[b] = leaves of block b that are in the cloud.  grid ceil(nl / 256), block 256; block_scan_kernel turns counts into offsets.
+__global__ __launch_bounds__(256) void ndt_centroid_count_kernel(const int* __restrict__ lcnt, int nl, int min_points, int* __restrict__ counts) {
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  const bool in = i < nl && ndt_in_centroid_cloud(lcnt[i], min_points);
+  __shared__ int wcnt[4];
+  const unsigned long long b = __ballot(in);
+  if ((threadIdx.x & 63) == 0) wcnt[threadIdx.x >> 6] = __popcll(b);
+  __syncthreads();
+  if (threadIdx.x == 0) counts[blockIdx.x] = (wcnt[0] + wcnt[1]) + (wcnt[2] + wcnt[3]);
+}
+
+// The ordered compaction: leaf i of the cloud goes to position offsets[block] + (leaves of the cloud before it in the block).  The
+// position is checked against nc (the scanned total the buffers were sized for) before it addresses memory.
+__global__ __launch_bounds__(256) void ndt_centroid_compact_kernel(const int* __restrict__ lcnt, const float* __restrict__ lcent, int nl, int min_points,
+                                                                   const int* __restrict__ offsets, int nc, float* __restrict__ cx, float* __restrict__ cy, float* __restrict__ cz,
+                                                                   int* __restrict__ c2l) {
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  const bool in = i < nl && ndt_in_centroid_cloud(lcnt[i], min_points);
+  __shared__ int wcnt[4];
+  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+  const unsigned long long b = __ballot(in);
+  if (lane == 0) wcnt[wv] = __popcll(b);
+  __syncthreads();
+  int pos = offsets[blockIdx.x] + __popcll(b & ((1ull << lane) - 1ull));
+  for (int w = 0; w < wv; ++w) pos += wcnt[w];
+  if (!in || pos < 0 || pos >= nc) return;
+  cx[pos] = lcent[(size_t)i * 3];
+  cy[pos] = lcent[(size_t)i * 3 + 1];
+  cz[pos] = lcent[(size_t)i * 3 + 2];
+  c2l[pos] = i;
 }
 
 // floor(x / leaf_size) of VGC:379-381 as an int; false when it does not fit (or is not finite)
@@ -331,6 +385,36 @@ __device__ __forceinline__ void ndt_pair(const NdtEval& ev, const S (&jx)[8], co
   }
 }
 
+// x_j_ang (NDT:405) and x_h_ang (NDT:418) of one source point, shared by the DIRECT and the radius body
+template <typename S, bool HESS>
+__device__ __forceinline__ void ndt_point_tables(const NdtEval& ev, float x, float y, float z, S (&jx)[8], S (&hx)[15]) {
+  constexpr bool kFloat = sizeof(S) == 4;
+#pragma unroll
+  for (int r = 0; r < 8; ++r) jx[r] = ndt_dot3<S>((S)ev.ja[3 * r], (S)ev.ja[3 * r + 1], (S)ev.ja[3 * r + 2], (S)x, (S)y, (S)z);  // NDT:405
+#pragma unroll
+  for (int r = 0; r < 15; ++r) {
+    S h2 = (S)ev.ha[3 * r + 2];
+    if (kFloat && r == 6) h2 = -h2;  // NDT:383: the float table holds +sy, the double one -sy (NDT:361)
+    hx[r] = HESS ? ndt_dot3<S>((S)ev.ha[3 * r], (S)ev.ha[3 * r + 1], h2, (S)x, (S)y, (S)z) : (S)0;  // NDT:418
+  }
+}
+
+// the 28 sums of a 256-lane workgroup: wave_sum28, then the four waves in a fixed order -> out[0..27]
+__device__ __forceinline__ void ndt_block_sum28(const double (&acc)[28], double* __restrict__ out) {
+  __shared__ double red[4][28];
+  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+  {
+    double ws[7];
+    wave_sum28(acc, ws);
+    if ((lane & 15) == 0) {
+#pragma unroll
+      for (int k = 0; k < 7; ++k) red[wv][7 * (lane >> 4) + k] = ws[k];
+    }
+  }
+  __syncthreads();
+  if (threadIdx.x < 28) out[threadIdx.x] = (red[0][threadIdx.x] + red[1][threadIdx.x]) + (red[2][threadIdx.x] + red[3][threadIdx.x]);
+}
+
 // The work of ONE workgroup of 256 lanes, shared by the single and the batched kernel so that the two cannot drift apart: source points
 // [256 block, 256 block + 256) of the cloud -> out[0..27], the block's sums (wave_sum28, then the four waves in a fixed order).
 template <typename S, bool HESS>
@@ -350,15 +434,7 @@ __device__ __forceinline__ void ndt_derivative_block(const float* __restrict__ s
     ok = ndt_cell(qz, vm.g.leaf, c2) && ok;
     if (ok) {
       S jx[8], hx[15];
-      constexpr bool kFloat = sizeof(S) == 4;
-#pragma unroll
-      for (int r = 0; r < 8; ++r) jx[r] = ndt_dot3<S>((S)ev.ja[3 * r], (S)ev.ja[3 * r + 1], (S)ev.ja[3 * r + 2], (S)x, (S)y, (S)z);  // NDT:405
-#pragma unroll
-      for (int r = 0; r < 15; ++r) {
-        S h2 = (S)ev.ha[3 * r + 2];
-        if (kFloat && r == 6) h2 = -h2;  // NDT:383: the float table holds +sy, the double one -sy (NDT:361)
-        hx[r] = HESS ? ndt_dot3<S>((S)ev.ha[3 * r], (S)ev.ha[3 * r + 1], h2, (S)x, (S)y, (S)z) : (S)0;  // NDT:418
-      }
+      ndt_point_tables<S, HESS>(ev, x, y, z, jx, hx);
 #pragma unroll 1
       for (int o = 0; o < ev.n_off; ++o) {
         int d0, d1, d2;
@@ -369,18 +445,69 @@ __device__ __forceinline__ void ndt_derivative_block(const float* __restrict__ s
       }
     }
   }
-  __shared__ double red[4][28];
-  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-  {
-    double ws[7];
-    wave_sum28(acc, ws);
-    if ((lane & 15) == 0) {
+  ndt_block_sum28(acc, out);
+}
+
+// ---- the radius mode (gorio_ndt_set_radius_search): the neighbourhood of a point is target_cells_.radiusSearch(x_trans_pt, resolution_)
+// (NDT:234-235, 573-574, 948-949) over the centroid cloud.  One query launch writes the float-transformed source, the exact radius
+// search of apd_search.hip turns it into a CSR in ascending (distance, centroid index), one launch walks each point's segment.
+struct NdtNeighbours {   // the CSR of one evaluation; offs == nullptr: no point has a neighbour (a map without an eligible leaf)
+  float4* q;             // [n] the transformed source, written by ndt_query_block
+  const long long* offs; // [n + 1]
+  const int* idx;        // [offs[n]] centroid indices
+  const int* c2l;        // [nc] centroid -> leaf position
+  int nc;
+};
+
+// q[i] = T * source[i] in the float arithmetic of pcl::transformPointCloud: the bits the search sees are the bits the pair arithmetic reads
+__device__ __forceinline__ void ndt_query_block(const float* __restrict__ sx, const float* __restrict__ sy, const float* __restrict__ sz, int n, const float* __restrict__ T,
+                                                int block, float4* __restrict__ q) {
+  const int i = block * 256 + threadIdx.x;
+  if (i >= n) return;
+  float qx, qy, qz;
+  transform_f(T, sx[i], sy[i], sz[i], qx, qy, qz);
+  q[i] = make_float4(qx, qy, qz, 0.0f);
+}
+
+// grid: ceil(n / 256), block 256
+__global__ __launch_bounds__(256) void ndt_query_kernel(const float* __restrict__ sx, const float* __restrict__ sy, const float* __restrict__ sz, int n, NdtEval ev,
+                                                        float4* __restrict__ q) {
+  ndt_query_block(sx, sy, sz, n, ev.T, (int)blockIdx.x, q);
+}
+
+// ndt_derivative_block with the neighbours taken from the CSR: the pair terms of a point are added in the order of its segment.  Every
+// centroid index and leaf position read from memory is range-checked before it addresses the map.  There is no ndt_cell test here.
+template <typename S, bool HESS>
+__device__ __forceinline__ void ndt_derivative_csr_block(const float* __restrict__ sx, const float* __restrict__ sy, const float* __restrict__ sz, int n, const NdtMapView& vm,
+                                                         const NdtEval& ev, const NdtNeighbours& nb, int block, double* __restrict__ out) {
+  double acc[28];
 #pragma unroll
-      for (int k = 0; k < 7; ++k) red[wv][7 * (lane >> 4) + k] = ws[k];
+  for (int q = 0; q < 28; ++q) acc[q] = 0.0;
+  const int i = block * 256 + threadIdx.x;
+  if (i < n && nb.offs) {
+    const long long b = nb.offs[i], e = nb.offs[i + 1];
+    if (e > b) {
+      const float4 qt = nb.q[i];
+      S jx[8], hx[15];
+      ndt_point_tables<S, HESS>(ev, sx[i], sy[i], sz[i], jx, hx);
+#pragma unroll 1
+      for (long long k = b; k < e; ++k) {
+        const int c = nb.idx[k];
+        if (c < 0 || c >= nb.nc) continue;
+        const int leaf = nb.c2l[c];
+        if (leaf < 0 || leaf >= vm.nl) continue;
+        ndt_pair<S, HESS>(ev, jx, hx, qt.x, qt.y, qt.z, vm.mean + (size_t)leaf * 3, vm.icov + (size_t)leaf * 9, acc);
+      }
     }
   }
-  __syncthreads();
-  if (threadIdx.x < 28) out[threadIdx.x] = (red[0][threadIdx.x] + red[1][threadIdx.x]) + (red[2][threadIdx.x] + red[3][threadIdx.x]);
+  ndt_block_sum28(acc, out);
+}
+
+// grid: ceil(n / 256), block 256.  One 28-double partial per block.
+template <typename S, bool HESS>
+__global__ __launch_bounds__(256) void ndt_derivative_csr_kernel(const float* __restrict__ sx, const float* __restrict__ sy, const float* __restrict__ sz, int n, NdtMapView vm,
+                                                                 NdtEval ev, NdtNeighbours nb, double* __restrict__ partials) {
+  ndt_derivative_csr_block<S, HESS>(sx, sy, sz, n, vm, ev, nb, (int)blockIdx.x, partials + (size_t)blockIdx.x * 28);
 }
 
 // grid: ceil(n / 256), block 256.  One 28-double partial per block.
@@ -399,6 +526,7 @@ struct NdtJob {
   int nblk;   // ceil(n / 256)
   NdtMapView vm;
   NdtEval ev;
+  NdtNeighbours nb;  // radius jobs only: q from the start, the CSR once the round's search has run
 };
 
 // grid: the sum over the launch's jobs of ceil(n_j / 256), block 256.  wg[blockIdx.x] = (job, job-local block), written by the host with
@@ -409,6 +537,40 @@ __global__ __launch_bounds__(256) void ndt_derivative_batch_kernel(const NdtJob*
   const int2 w = wg[blockIdx.x];
   const NdtJob& j = jobs[w.x];
   ndt_derivative_block<S, HESS>(j.sx, j.sy, j.sz, j.n, j.vm, j.ev, w.y, partials + (size_t)(j.first + w.y) * 28);
+}
+
+// The radius jobs of a round, under the same grid, table and host guarantees: the query launch, then (after the batched search has
+// filled every job's CSR) the walk.
+__global__ __launch_bounds__(256) void ndt_query_batch_kernel(const NdtJob* __restrict__ jobs, const int2* __restrict__ wg) {
+  const int2 w = wg[blockIdx.x];
+  const NdtJob& j = jobs[w.x];
+  ndt_query_block(j.sx, j.sy, j.sz, j.n, j.ev.T, w.y, j.nb.q);
+}
+
+template <typename S, bool HESS>
+__global__ __launch_bounds__(256) void ndt_derivative_csr_batch_kernel(const NdtJob* __restrict__ jobs, const int2* __restrict__ wg, double* __restrict__ partials) {
+  const int2 w = wg[blockIdx.x];
+  const NdtJob& j = jobs[w.x];
+  ndt_derivative_csr_block<S, HESS>(j.sx, j.sy, j.sz, j.n, j.vm, j.ev, j.nb, w.y, partials + (size_t)(j.first + w.y) * 28);
+}
+
+// score_inc of one (point, leaf) pair, NDT:975-977, in double
+__device__ __forceinline__ double ndt_score_pair(const NdtMapView& vm, const NdtEval& ev, int leaf, float qx, float qy, float qz) {
+  const double* mean = vm.mean + (size_t)leaf * 3;
+  const double* C = vm.icov + (size_t)leaf * 9;
+  const double x0 = (double)qx - mean[0], x1 = (double)qy - mean[1], x2 = (double)qz - mean[2];
+  const double q = ndt_dot3<double>(x0, x1, x2, ndt_dot3<double>(C[0], C[1], C[2], x0, x1, x2), ndt_dot3<double>(C[3], C[4], C[5], x0, x1, x2),
+                                    ndt_dot3<double>(C[6], C[7], C[8], x0, x1, x2));
+  return -ev.d1 * exp(-ev.d2 * q / 2) - ev.d3;
+}
+
+// one sum of a 256-lane workgroup: wave_sum, then the four waves in a fixed order -> out[0]
+__device__ __forceinline__ void ndt_block_sum1(double sum, double* __restrict__ out) {
+  sum = wave_sum(sum);
+  __shared__ double red[4];
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = sum;
+  __syncthreads();
+  if (threadIdx.x == 0) out[0] = (red[0] + red[1]) + (red[2] + red[3]);
 }
 
 // calculateScore, NDT:935-983: per point sum of score_inc / neighborhood.size().  The work of ONE workgroup of 256 lanes, shared by the
@@ -434,22 +596,47 @@ __device__ __forceinline__ void ndt_score_block(const float* __restrict__ sx, co
         ndt_offset(ev.n_off, o, d0, d1, d2);
         const int leaf = ndt_lookup(vm, c0, c1, c2, d0, d1, d2);
         if (leaf < 0) continue;
-        const double* mean = vm.mean + (size_t)leaf * 3;
-        const double* C = vm.icov + (size_t)leaf * 9;
-        const double x0 = (double)qx - mean[0], x1 = (double)qy - mean[1], x2 = (double)qz - mean[2];
-        const double q = ndt_dot3<double>(x0, x1, x2, ndt_dot3<double>(C[0], C[1], C[2], x0, x1, x2), ndt_dot3<double>(C[3], C[4], C[5], x0, x1, x2),
-                                          ndt_dot3<double>(C[6], C[7], C[8], x0, x1, x2));
-        s += -ev.d1 * exp(-ev.d2 * q / 2) - ev.d3;  // NDT:975-977
+        s += ndt_score_pair(vm, ev, leaf, qx, qy, qz);
         ++nn;
       }
       if (nn) sum = s / (double)nn;  // NDT:979
     }
   }
-  sum = wave_sum(sum);
-  __shared__ double red[4];
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = sum;
-  __syncthreads();
-  if (threadIdx.x == 0) out[0] = (red[0] + red[1]) + (red[2] + red[3]);
+  ndt_block_sum1(sum, out);
+}
+
+// ndt_score_block with the neighbours taken from the CSR (NDT:948-949); the divisor is neighborhood.size(), the whole segment
+__device__ __forceinline__ void ndt_score_csr_block(int n, const NdtMapView& vm, const NdtEval& ev, const NdtNeighbours& nb, int block, double* __restrict__ out) {
+  double sum = 0.0;
+  const int i = block * 256 + threadIdx.x;
+  if (i < n && nb.offs) {
+    const long long b = nb.offs[i], e = nb.offs[i + 1];
+    if (e > b) {
+      const float4 qt = nb.q[i];
+      double s = 0.0;
+#pragma unroll 1
+      for (long long k = b; k < e; ++k) {
+        const int c = nb.idx[k];
+        if (c < 0 || c >= nb.nc) continue;
+        const int leaf = nb.c2l[c];
+        if (leaf < 0 || leaf >= vm.nl) continue;
+        s += ndt_score_pair(vm, ev, leaf, qt.x, qt.y, qt.z);
+      }
+      sum = s / (double)(e - b);  // NDT:979
+    }
+  }
+  ndt_block_sum1(sum, out);
+}
+
+// grid: ceil(n / 256), block 256.  One double per block.
+__global__ __launch_bounds__(256) void ndt_score_csr_kernel(int n, NdtMapView vm, NdtEval ev, NdtNeighbours nb, double* __restrict__ partials) {
+  ndt_score_csr_block(n, vm, ev, nb, (int)blockIdx.x, partials + blockIdx.x);
+}
+
+__global__ __launch_bounds__(256) void ndt_score_csr_batch_kernel(const NdtJob* __restrict__ jobs, const int2* __restrict__ wg, double* __restrict__ partials) {
+  const int2 w = wg[blockIdx.x];
+  const NdtJob& j = jobs[w.x];
+  ndt_score_csr_block(j.n, j.vm, j.ev, j.nb, w.y, partials + (size_t)(j.first + w.y));
 }
 
 // grid: ceil(n / 256), block 256.  One double per block.
@@ -504,6 +691,7 @@ struct NdtTarget {
   DevBuf<int> counts, bb;
   DevBuf<int> lidx, lcnt;
   DevBuf<double> lmean, lraw, lcov, licov;
+  DevBuf<float> lcent;  // [nl][3] the float centroid of every leaf (VGC:242-243, 289)
   size_t l_cap = 0;
   int nl = 0;
   NdtGrid grid{};
@@ -511,10 +699,21 @@ struct NdtTarget {
   // the three parameters the valid map was built with
   double resolution = 0.0, min_covar_eigvalue_mult = 0.0;
   int min_points_per_voxel = 0;
+  // radius mode: the centroid cloud (SoA, ascending leaf index), centroid -> leaf position, and the search handle that holds the indexed
+  // copy of the cloud.  Part of the map, so sharers see ONE index; built by the first evaluation that needs it, stale with the map.
+  DevBuf<float> cx, cy, cz;
+  DevBuf<int> c2l;
+  size_t c_cap = 0;
+  int nc = 0;
+  bool cent_valid = false;
+  gorio_search_handle* cent = nullptr;
   NdtTarget() = default;
   NdtTarget(const NdtTarget&) = delete;
   NdtTarget& operator=(const NdtTarget&) = delete;
-  ~NdtTarget() { hipSetDevice(device); }  // the buffers free themselves as members, after this body: the device has to be current by then
+  ~NdtTarget() {
+    hipSetDevice(device);
+    if (cent) gorio_search_destroy(cent);
+  }  // the buffers free themselves as members, after this body: the device has to be current by then
 };
 }  // namespace gorio
 
@@ -541,6 +740,13 @@ struct gorio_ndt {
   gorio::DevBuf<void> b_jobs;
   gorio::DevBuf<double> b_partials, b_out;
   gorio::PinnedBuf b_h_jobs, b_h_out;
+  // radius mode (gorio_ndt_set_radius_search): the switch, the transformed source of the last evaluation, this handle's search state
+  // (scratch and the CSR of its last search; the cloud searched is the target state's) and whether that CSR is still the last evaluation's
+  bool radius = false;
+  gorio::DevBuf<float4> rq;
+  gorio_search_handle* rs = nullptr;
+  bool nb_valid = false, nb_empty = false;
+  int nb_n = 0;
   gorio::NdtMapView map() const { return gorio::NdtMapView{tgt->lidx, tgt->lcnt, tgt->lmean, tgt->licov, tgt->nl, p.min_points_per_voxel, tgt->grid}; }
 };
 
@@ -558,10 +764,35 @@ float ndt_decode(int k) {  // sc_decode on the host
   return f;
 }
 
+// ---- the search half of the radius mode.  The exact radius search lives in apd_search.hip, which is included after this file (its handle
+// type is complete only there): these five are defined in apd_ndt_radius.hip, behind it.  `cloud` is the search handle that holds the
+// indexed centroid cloud (NdtTarget::cent); `s` a per-handle search state (scratch and the CSR of its last search).
+struct NdtCsr {  // device pointers into a search state, valid until its next search
+  const long long* offs = nullptr;
+  const int* idx = nullptr;
+  const float* sqd = nullptr;
+  long long total = 0;
+};
+struct NdtRadiusJob {
+  gorio_search_handle* s;
+  gorio_search_handle* cloud;
+  const float4* q;
+  int n;
+  double radius;
+  NdtCsr csr;  // out
+};
+gorio_search_handle* ndt_rs_new(int device);
+void ndt_rs_free(gorio_search_handle* s);
+hipStream_t ndt_rs_stream(gorio_search_handle* cloud);  // the device's launch stream: every radius evaluation runs on it
+int ndt_rs_radius(NdtRadiusJob* job);                   // one search_radius_core; errors through ndt_fail
+int ndt_rs_radius_batch(NdtRadiusJob* jobs, int count, int* launches, int* syncs);  // one search_radius_batch_core
+const std::vector<long long>& ndt_rs_host_offsets(const gorio_search_handle* s);    // host copy of the last CSR's offsets, nq + 1
+void ndt_rs_csr(NdtRadiusJob* job);                     // job->csr = the CSR job->s holds
+
 int ndt_n_off(int search) { return search == GORIO_NDT_DIRECT1 ? 1 : search == GORIO_NDT_DIRECT7 ? 7 : 26; }
 
 int ndt_check_params(const gorio_ndt_params& p) {
-  if (p.search == GORIO_NDT_KDTREE) return ndt_fail(GORIO_ERR_UNSUPPORTED, "set_params: KDTREE search is not built (a radius search over leaf centroids)");
+  if (p.search == GORIO_NDT_KDTREE) return ndt_fail(GORIO_ERR_UNSUPPORTED, "set_params: KDTREE is not a value of params.search; gorio_ndt_set_radius_search(h, 1) selects the radius search over leaf centroids");
   if (p.search != GORIO_NDT_DIRECT26 && p.search != GORIO_NDT_DIRECT7 && p.search != GORIO_NDT_DIRECT1) return ndt_fail(GORIO_ERR_UNSUPPORTED, "set_params: unknown search method");
   if (!(p.resolution > 0) || !std::isfinite(p.resolution)) return ndt_fail(GORIO_ERR_UNSUPPORTED, "set_params: resolution must be finite and > 0");
   if (p.min_points_per_voxel < 1) return ndt_fail(GORIO_ERR_INVALID, "set_params: min_points_per_voxel < 1");
@@ -618,6 +849,7 @@ int ndt_adopt(gorio_ndt* h, const float* x, const float* y, const float* z, int 
   GORIO_HIP_CHECK(ndt_fail, hipSetDevice(h->device));
   const size_t need = std::max(n, 1), grown = need + need / 8 + 64;
   gorio::NdtTarget* t = nullptr;
+  h->nb_valid = false;
   if (source) {
     GORIO_HIP_CHECK(ndt_fail, gorio::reserve_group(h->a_cap, need, grown, h->ax, grown, h->ay, grown, h->az, grown));
   } else {
@@ -683,6 +915,9 @@ int ndt_ensure_map(gorio_ndt* h) {
   GORIO_HIP_CHECK(ndt_fail, hipSetDevice(h->device));
   const int n = t->n_t;
   t->nl = 0;
+  t->nc = 0;
+  t->cent_valid = false;
+  h->nb_valid = false;
   t->grid = NdtGrid{};
   t->grid.leaf = (float)h->p.resolution;
   t->grid.inv = 1.0f / t->grid.leaf;
@@ -739,15 +974,49 @@ int ndt_ensure_map(gorio_ndt* h) {
   if (nv <= 0 || nv > n_fin) return ndt_fail(GORIO_ERR_STATE, "voxel map: internal error, the leaf count does not fit the cloud");
   {
     const size_t cap = (size_t)nv + nv / 8 + 64;
-    GORIO_HIP_CHECK(ndt_fail, reserve_group(t->l_cap, nv, cap, t->lidx, cap, t->lcnt, cap, t->lmean, 3 * cap, t->lraw, 9 * cap, t->lcov, 9 * cap, t->licov, 9 * cap));
+    GORIO_HIP_CHECK(ndt_fail, reserve_group(t->l_cap, nv, cap, t->lidx, cap, t->lcnt, cap, t->lmean, 3 * cap, t->lraw, 9 * cap, t->lcov, 9 * cap, t->licov, 9 * cap, t->lcent, 3 * cap));
   }
   ndt_leaf_kernel<<<nblocks, 256, 0, h->stream>>>(t->keys, t->tx, t->ty, t->tz, n_fin, n, t->counts, h->p.min_points_per_voxel, h->p.min_covar_eigvalue_mult, nv, t->lidx, t->lcnt,
-                                                  t->lmean, t->lraw, t->lcov, t->licov);
+                                                  t->lmean, t->lraw, t->lcov, t->licov, t->lcent);
   GORIO_HIP_CHECK(ndt_fail, hipGetLastError());
   GORIO_HIP_CHECK(ndt_fail, hipStreamSynchronize(h->stream));
   t->nl = nv;
   t->grid = g;
   t->map_valid = true;
+  return GORIO_OK;
+}
+
+// The centroid cloud of the valid map and its search index (VGC:282-326: cloud of leaf centroids + kdtree_.setInputCloud), built once per
+// map by the first call that needs them: count, scan, ordered compaction, then the index through the library's one index build.
+int ndt_ensure_centroids(gorio_ndt* h) {
+  using namespace gorio;
+  NdtTarget* t = h->tgt.get();
+  if (t->cent_valid) return GORIO_OK;
+  GORIO_HIP_CHECK(ndt_fail, hipSetDevice(h->device));
+  const int nl = t->nl, nblk = (nl + 255) / 256;
+  int nc = 0;
+  if (nl > 0) {
+    GORIO_HIP_CHECK(ndt_fail, t->counts.reserve((size_t)nblk + 1));
+    ndt_centroid_count_kernel<<<nblk, 256, 0, h->stream>>>(t->lcnt, nl, t->min_points_per_voxel, t->counts);
+    block_scan_kernel<<<1, 1024, 0, h->stream>>>(t->counts, nblk);
+    GORIO_HIP_CHECK(ndt_fail, hipGetLastError());
+    GORIO_HIP_CHECK(ndt_fail, hipMemcpyAsync(&nc, t->counts + nblk, sizeof(int), hipMemcpyDeviceToHost, h->stream));
+    GORIO_HIP_CHECK(ndt_fail, hipStreamSynchronize(h->stream));
+    if (nc < 0 || nc > nl) return ndt_fail(GORIO_ERR_STATE, "centroid cloud: internal error, the count does not fit the leaves");
+  }
+  if (nc > 0) {
+    const size_t cap = (size_t)nc + nc / 8 + 64;
+    GORIO_HIP_CHECK(ndt_fail, reserve_group(t->c_cap, nc, cap, t->cx, cap, t->cy, cap, t->cz, cap, t->c2l, cap));
+    ndt_centroid_compact_kernel<<<nblk, 256, 0, h->stream>>>(t->lcnt, t->lcent, nl, t->min_points_per_voxel, t->counts, nc, t->cx, t->cy, t->cz, t->c2l);
+    GORIO_HIP_CHECK(ndt_fail, hipGetLastError());
+    GORIO_HIP_CHECK(ndt_fail, hipStreamSynchronize(h->stream));  // the index build below runs on the device's launch stream
+  }
+  if (!t->cent && gorio_search_create(&t->cent, t->device)) return ndt_fail(GORIO_ERR_NO_DEVICE, std::string("centroid index: ") + gorio_search_last_error());
+  if (const int rc = gorio_search_set_cloud_device(t->cent, t->cx, t->cy, t->cz, nc))  // a float sum that overflowed is refused here
+    return ndt_fail(rc, std::string("centroid index: ") + gorio_search_last_error());
+  GORIO_HIP_CHECK(ndt_fail, hipStreamSynchronize(ndt_rs_stream(t->cent)));  // the columns are free again (a rebuild writes them on h->stream)
+  t->nc = nc;
+  t->cent_valid = true;
   return GORIO_OK;
 }
 
@@ -859,9 +1128,59 @@ gorio::NdtEval ndt_make_eval(const gorio_ndt* h, const double* p, const float* T
   return ev;
 }
 
+double ndt_radius_of(const gorio_ndt* h) { return (double)(float)h->p.resolution; }  // resolution_, the float member (NDT:234)
+
+// what a radius evaluation needs beside the map: the centroid index, this handle's search state and its query buffer
+int ndt_radius_prepare(gorio_ndt* h) {
+  if (const int rc = ndt_ensure_centroids(h)) return rc;
+  if (!h->rs && !(h->rs = ndt_rs_new(h->device))) return ndt_fail(GORIO_ERR_ALLOC, "radius search: out of memory");
+  const size_t n = (size_t)h->n_s;
+  GORIO_HIP_CHECK(ndt_fail, h->rq.reserve(n, n + n / 8 + 64));
+  return GORIO_OK;
+}
+
+// ndt_evaluate for a handle with the radius switch on: query launch, radius search, walk, fold -- all on the device's launch stream, where
+// the search runs.  (Uploads and map builds end with a synchronisation of the handle's own stream, so nothing is in flight there.)
+int ndt_evaluate_radius(gorio_ndt* h, const gorio::NdtEval& ev, int mode, double* out) {
+  using namespace gorio;
+  const int n = h->n_s, nblk = (n + 255) / 256;
+  const int width = mode == 3 ? 1 : 28;
+  if (const int rc = ndt_radius_prepare(h)) return rc;
+  NdtTarget* t = h->tgt.get();
+  hipStream_t stream = ndt_rs_stream(t->cent);
+  GORIO_HIP_CHECK(ndt_fail, h->partials.reserve((size_t)28 * nblk, (size_t)28 * (nblk + nblk / 8 + 4)));
+  GORIO_HIP_CHECK(ndt_fail, h->d_out.reserve(28));
+  if (!h->h_out.get()) GORIO_HIP_CHECK(ndt_fail, h->h_out.realloc(sizeof(double) * 28));
+  h->nb_valid = false;
+  NdtNeighbours nb{h->rq, nullptr, nullptr, t->c2l, t->nc};
+  if (t->nc > 0) {
+    ndt_query_kernel<<<nblk, 256, 0, stream>>>(h->sx, h->sy, h->sz, n, ev, h->rq);
+    GORIO_HIP_CHECK(ndt_fail, hipGetLastError());
+    NdtRadiusJob job{h->rs, t->cent, h->rq, n, ndt_radius_of(h), NdtCsr{}};
+    if (const int rc = ndt_rs_radius(&job)) return rc;
+    nb.offs = job.csr.offs;
+    nb.idx = job.csr.idx;
+  }
+  const NdtMapView vm = h->map();
+  if (mode == 0) ndt_derivative_csr_kernel<float, false><<<nblk, 256, 0, stream>>>(h->sx, h->sy, h->sz, n, vm, ev, nb, h->partials);
+  else if (mode == 1) ndt_derivative_csr_kernel<float, true><<<nblk, 256, 0, stream>>>(h->sx, h->sy, h->sz, n, vm, ev, nb, h->partials);
+  else if (mode == 2) ndt_derivative_csr_kernel<double, true><<<nblk, 256, 0, stream>>>(h->sx, h->sy, h->sz, n, vm, ev, nb, h->partials);
+  else ndt_score_csr_kernel<<<nblk, 256, 0, stream>>>(n, vm, ev, nb, h->partials);
+  ndt_fold_kernel<<<1, 64, 0, stream>>>(h->partials, nblk, width, h->d_out);
+  GORIO_HIP_CHECK(ndt_fail, hipGetLastError());
+  GORIO_HIP_CHECK(ndt_fail, hipMemcpyAsync(h->h_out.get(), h->d_out, sizeof(double) * width, hipMemcpyDeviceToHost, stream));
+  GORIO_HIP_CHECK(ndt_fail, hipStreamSynchronize(stream));
+  std::memcpy(out, h->h_out.get(), sizeof(double) * width);
+  h->nb_valid = true;
+  h->nb_empty = t->nc == 0;
+  h->nb_n = n;
+  return GORIO_OK;
+}
+
 // one evaluation: mode 0 computeDerivatives without the Hessian, 1 with it, 2 computeHessian, 3 calculateScore.  out: 28 doubles
 int ndt_evaluate(gorio_ndt* h, const gorio::NdtEval& ev, int mode, double* out) {
   using namespace gorio;
+  if (h->radius) return ndt_evaluate_radius(h, ev, mode, out);
   const int n = h->n_s, nblk = (n + 255) / 256;
   const int width = mode == 3 ? 1 : 28;
   GORIO_HIP_CHECK(ndt_fail, h->partials.reserve((size_t)28 * nblk, (size_t)28 * (nblk + nblk / 8 + 4)));
@@ -1259,13 +1578,94 @@ int ndt_batch_maps(gorio_ndt* const* handles, int count, const std::string& name
   return GORIO_OK;
 }
 
-// the derivative launch of one evaluation mode
+// the derivative launch of one evaluation mode, over DIRECT jobs or over radius jobs (whose CSR the round's search has filled)
 template <typename... A>
-void ndt_launch_batch(int mode, int blocks, hipStream_t stream, A... a) {
+void ndt_launch_batch(int mode, bool radius, int blocks, hipStream_t stream, A... a) {
   using namespace gorio;
-  if (mode == 0) ndt_derivative_batch_kernel<float, false><<<blocks, 256, 0, stream>>>(a...);
-  else if (mode == 1) ndt_derivative_batch_kernel<float, true><<<blocks, 256, 0, stream>>>(a...);
-  else ndt_derivative_batch_kernel<double, true><<<blocks, 256, 0, stream>>>(a...);
+  if (radius) {
+    if (mode == 0) ndt_derivative_csr_batch_kernel<float, false><<<blocks, 256, 0, stream>>>(a...);
+    else if (mode == 1) ndt_derivative_csr_batch_kernel<float, true><<<blocks, 256, 0, stream>>>(a...);
+    else ndt_derivative_csr_batch_kernel<double, true><<<blocks, 256, 0, stream>>>(a...);
+  } else {
+    if (mode == 0) ndt_derivative_batch_kernel<float, false><<<blocks, 256, 0, stream>>>(a...);
+    else if (mode == 1) ndt_derivative_batch_kernel<float, true><<<blocks, 256, 0, stream>>>(a...);
+    else ndt_derivative_batch_kernel<double, true><<<blocks, 256, 0, stream>>>(a...);
+  }
+}
+
+// what a batch prepares per radius handle before its rounds: centroid index, search state, query buffer
+int ndt_batch_radius_prepare(gorio_ndt* const* handles, int count, const std::string& name) {
+  for (int i = 0; i < count; ++i)
+    if (handles[i]->radius)
+      if (const int rc = ndt_radius_prepare(handles[i])) return ndt_fail(rc, name + ": handle " + std::to_string(i) + ": " + g_ndt_err);
+  return GORIO_OK;
+}
+
+// The stream the launches of a batch run on: handles[0]'s own while every handle is DIRECT; the device's launch stream, where the search
+// runs, as soon as one handle has the radius switch on.
+hipStream_t ndt_batch_stream(gorio_ndt* const* handles, int count) {
+  for (int i = 0; i < count; ++i)
+    if (handles[i]->radius) return ndt_rs_stream(handles[i]->tgt->cent);
+  return handles[0]->stream;
+}
+
+// job record of one pending evaluation; the partial slots [first, first + nblk) are its own
+void ndt_fill_job(gorio::NdtJob& j, gorio_ndt* h, int mode, int first, const gorio::NdtEval& ev) {
+  j.sx = h->sx; j.sy = h->sy; j.sz = h->sz;
+  j.n = h->n_s;
+  j.mode = mode;
+  j.first = first;
+  j.nblk = (h->n_s + 255) / 256;
+  j.vm = h->map();
+  j.ev = ev;
+  j.nb = gorio::NdtNeighbours{nullptr, nullptr, nullptr, nullptr, 0};
+  if (h->radius) {
+    j.nb = gorio::NdtNeighbours{h->rq, nullptr, nullptr, h->tgt->c2l, h->tgt->nc};
+    h->nb_valid = false;
+  }
+}
+
+// The neighbours of a round's radius jobs rk (indices into the job table; job k belongs to handles[order[k]]): ONE query launch over their
+// (job, block) entries d_wg[0 .. blocks), ONE search_radius_batch_core over those whose map has a centroid, then the job records go up
+// once more with the CSR every search state now holds.  The table is already on its way to the device when this is called.
+int ndt_batch_neighbours(gorio_ndt* const* handles, const std::vector<int>& order, const std::vector<int>& rk, gorio::NdtJob* h_jobs, gorio::NdtJob* d_jobs, const int2* d_wg, int blocks,
+                         hipStream_t stream, std::vector<NdtRadiusJob>& rjobs, int* launches) {
+  using namespace gorio;
+  rjobs.clear();
+  std::vector<int> searched;
+  for (const int k : rk) {
+    gorio_ndt* h = handles[order[k]];
+    if (h->tgt->nc == 0) continue;  // no centroid: the job keeps offs == nullptr, no point has a neighbour
+    rjobs.push_back(NdtRadiusJob{h->rs, h->tgt->cent, h->rq, h->n_s, ndt_radius_of(h), NdtCsr{}});
+    searched.push_back(k);
+  }
+  if (rjobs.empty()) return GORIO_OK;
+  ndt_query_batch_kernel<<<blocks, 256, 0, stream>>>(d_jobs, d_wg);
+  GORIO_HIP_CHECK(ndt_fail, hipGetLastError());
+  int search_launches = 0, syncs = 0;
+  if (const int rc = ndt_rs_radius_batch(rjobs.data(), (int)rjobs.size(), &search_launches, &syncs)) return rc;
+  if (syncs == 0) GORIO_HIP_CHECK(ndt_fail, hipStreamSynchronize(stream));  // the pinned table is read by the first copy until then
+  int lo = INT_MAX, hi = -1;
+  for (size_t r = 0; r < searched.size(); ++r) {
+    NdtJob& j = h_jobs[searched[r]];
+    j.nb.offs = rjobs[r].csr.offs;
+    j.nb.idx = rjobs[r].csr.idx;
+    lo = std::min(lo, searched[r]);
+    hi = std::max(hi, searched[r]);
+  }
+  GORIO_HIP_CHECK(ndt_fail, hipMemcpyAsync(d_jobs + lo, h_jobs + lo, sizeof(NdtJob) * (size_t)(hi - lo + 1), hipMemcpyHostToDevice, stream));
+  *launches += 1 + search_launches;
+  return GORIO_OK;
+}
+
+// after the round's synchronisation: every radius job's CSR is the last evaluation of its handle
+void ndt_batch_neighbours_done(gorio_ndt* const* handles, const std::vector<int>& order, const std::vector<int>& rk) {
+  for (const int k : rk) {
+    gorio_ndt* h = handles[order[k]];
+    h->nb_valid = true;
+    h->nb_empty = h->tgt->nc == 0;
+    h->nb_n = h->n_s;
+  }
 }
 }  // namespace
 
@@ -1314,6 +1714,7 @@ void gorio_ndt_destroy(gorio_ndt_t* h) {
     hipStreamDestroy(h->stream);
   }
   if (h->adopt_ev) hipEventDestroy(h->adopt_ev);
+  if (h->rs) ndt_rs_free(h->rs);
   delete h;
 }
 
@@ -1345,6 +1746,7 @@ int gorio_ndt_set_target(gorio_ndt_t* h, const float* xyz, int n, int stride_byt
   gorio::NdtTarget& t = *h->tgt;
   t.map_valid = false;
   t.has_target = false;
+  h->nb_valid = false;
   if (const int rc = ndt_upload(h, xyz, n, stride_bytes, t.tx, t.ty, t.tz, t.t_cap)) return rc;
   t.n_t = n;
   t.has_target = true;
@@ -1361,6 +1763,7 @@ int gorio_ndt_set_source(gorio_ndt_t* h, const float* xyz, int n, int stride_byt
     if (!std::isfinite(xyz[st * i]) || !std::isfinite(xyz[st * i + 1]) || !std::isfinite(xyz[st * i + 2]))
       return ndt_fail(GORIO_ERR_INVALID, "set_source: point " + std::to_string(i) + " is not finite (the reference's cell index of it is undefined)");
   h->has_source = false;
+  h->nb_valid = false;
   if (const int rc = ndt_upload(h, xyz, n, stride_bytes, h->sx, h->sy, h->sz, h->s_cap)) return rc;
   h->n_s = n;
   h->has_source = true;
@@ -1416,6 +1819,92 @@ int gorio_ndt_get_voxels(gorio_ndt_t* h, int capacity, int* n_leaves, int* leaf_
   if (cov) GORIO_HIP_CHECK(ndt_fail, hipMemcpyAsync(cov, t.lcov, sizeof(double) * 9 * nl, hipMemcpyDeviceToHost, h->stream));
   if (icov) GORIO_HIP_CHECK(ndt_fail, hipMemcpyAsync(icov, t.licov, sizeof(double) * 9 * nl, hipMemcpyDeviceToHost, h->stream));
   GORIO_HIP_CHECK(ndt_fail, hipStreamSynchronize(h->stream));
+  return GORIO_OK;
+}
+
+// pcl::NormalDistributionsTransform / pclomp's KDTREE: every neighbourhood is target_cells_.radiusSearch(x_trans_pt, resolution_)
+int gorio_ndt_set_radius_search(gorio_ndt_t* h, int enable) {
+  if (!h) return ndt_fail(GORIO_ERR_INVALID, "set_radius_search: null handle");
+  const bool on = enable != 0;
+  if (on != h->radius) h->nb_valid = false;  // the map stays; the neighbour lists held belong to the other mode's past
+  h->radius = on;
+  return GORIO_OK;
+}
+
+int gorio_ndt_get_radius_search(const gorio_ndt_t* h, int* enabled) {
+  if (!h || !enabled) return ndt_fail(GORIO_ERR_INVALID, "get_radius_search: null argument");
+  *enabled = h->radius ? 1 : 0;
+  return GORIO_OK;
+}
+
+// the centroid cloud of VGC:282-326 and the leaf position of every centroid
+int gorio_ndt_get_centroids(gorio_ndt_t* h, int capacity, int* n_centroids, float* xyz, int* leaf_pos) {
+  if (!h || !n_centroids) return ndt_fail(GORIO_ERR_INVALID, "get_centroids: null argument");
+  if (!h->tgt->has_target) return ndt_fail(GORIO_ERR_STATE, "get_centroids: no target set");
+  GORIO_HIP_CHECK(ndt_fail, hipSetDevice(h->device));
+  if (const int rc = ndt_ensure_map(h)) return ndt_fail(rc, "get_centroids: " + g_ndt_err);
+  if (const int rc = ndt_ensure_centroids(h)) return ndt_fail(rc, "get_centroids: " + g_ndt_err);
+  const gorio::NdtTarget& t = *h->tgt;
+  *n_centroids = t.nc;
+  if ((!xyz && !leaf_pos) || t.nc == 0) return GORIO_OK;
+  if (capacity < t.nc) return ndt_fail(GORIO_ERR_INVALID, "get_centroids: capacity below the number of centroids");
+  const size_t nc = (size_t)t.nc;
+  std::vector<float> soa;
+  try {
+    soa.resize(3 * nc);
+  } catch (const std::bad_alloc&) {
+    return ndt_fail(GORIO_ERR_ALLOC, "get_centroids: out of host memory");
+  }
+  if (xyz) {
+    GORIO_HIP_CHECK(ndt_fail, hipMemcpyAsync(soa.data(), t.cx, sizeof(float) * nc, hipMemcpyDeviceToHost, h->stream));
+    GORIO_HIP_CHECK(ndt_fail, hipMemcpyAsync(soa.data() + nc, t.cy, sizeof(float) * nc, hipMemcpyDeviceToHost, h->stream));
+    GORIO_HIP_CHECK(ndt_fail, hipMemcpyAsync(soa.data() + 2 * nc, t.cz, sizeof(float) * nc, hipMemcpyDeviceToHost, h->stream));
+  }
+  if (leaf_pos) GORIO_HIP_CHECK(ndt_fail, hipMemcpyAsync(leaf_pos, t.c2l, sizeof(int) * nc, hipMemcpyDeviceToHost, h->stream));
+  GORIO_HIP_CHECK(ndt_fail, hipStreamSynchronize(h->stream));
+  if (xyz)
+    for (size_t i = 0; i < nc; ++i) {
+      xyz[3 * i] = soa[i];
+      xyz[3 * i + 1] = soa[nc + i];
+      xyz[3 * i + 2] = soa[2 * nc + i];
+    }
+  return GORIO_OK;
+}
+
+// the CSR of the handle's last radius evaluation: offsets [source size + 1], then per neighbour the leaf position and the squared distance
+int gorio_ndt_get_neighbours(gorio_ndt_t* h, long long* offsets, int* leaf_pos, float* sqd, long long capacity) {
+  if (!h) return ndt_fail(GORIO_ERR_INVALID, "get_neighbours: null handle");
+  if (!h->nb_valid || !h->rs) return ndt_fail(GORIO_ERR_STATE, "get_neighbours: no radius evaluation to report (none yet, or the source, the target or the switch changed since)");
+  GORIO_HIP_CHECK(ndt_fail, hipSetDevice(h->device));
+  const size_t n = (size_t)h->nb_n;
+  if (h->nb_empty) {
+    if (offsets) std::fill(offsets, offsets + n + 1, 0LL);
+    return GORIO_OK;
+  }
+  const std::vector<long long>& offs = ndt_rs_host_offsets(h->rs);
+  if (offs.size() != n + 1) return ndt_fail(GORIO_ERR_STATE, "get_neighbours: internal error, the result held does not fit the source");
+  const long long total = offs[n];
+  if ((leaf_pos || sqd) && capacity < total) return ndt_fail(GORIO_ERR_INVALID, "get_neighbours: capacity below the number of neighbours");
+  if (offsets) std::copy(offs.begin(), offs.end(), offsets);
+  if (total == 0 || (!leaf_pos && !sqd)) return GORIO_OK;
+  const gorio::NdtTarget& t = *h->tgt;
+  NdtRadiusJob job{h->rs, t.cent, nullptr, 0, 0.0, NdtCsr{}};
+  ndt_rs_csr(&job);
+  hipStream_t stream = ndt_rs_stream(t.cent);
+  std::vector<int> c2l;
+  try {
+    c2l.resize((size_t)t.nc);
+  } catch (const std::bad_alloc&) {
+    return ndt_fail(GORIO_ERR_ALLOC, "get_neighbours: out of host memory");
+  }
+  if (leaf_pos) {
+    GORIO_HIP_CHECK(ndt_fail, hipMemcpyAsync(leaf_pos, job.csr.idx, sizeof(int) * (size_t)total, hipMemcpyDeviceToHost, stream));
+    GORIO_HIP_CHECK(ndt_fail, hipMemcpyAsync(c2l.data(), t.c2l, sizeof(int) * (size_t)t.nc, hipMemcpyDeviceToHost, stream));
+  }
+  if (sqd) GORIO_HIP_CHECK(ndt_fail, hipMemcpyAsync(sqd, job.csr.sqd, sizeof(float) * (size_t)total, hipMemcpyDeviceToHost, stream));
+  GORIO_HIP_CHECK(ndt_fail, hipStreamSynchronize(stream));
+  if (leaf_pos)
+    for (long long k = 0; k < total; ++k) leaf_pos[k] = (leaf_pos[k] >= 0 && leaf_pos[k] < t.nc) ? c2l[(size_t)leaf_pos[k]] : -1;
   return GORIO_OK;
 }
 
@@ -1479,6 +1968,7 @@ int gorio_ndt_set_target_shared(gorio_ndt_t* h, gorio_ndt_t* owner) {
   if (!owner->tgt->has_target) return ndt_fail(GORIO_ERR_STATE, "set_target_shared: the owner has no target");
   if (h == owner || h->tgt == owner->tgt) return GORIO_OK;
   GORIO_HIP_CHECK(ndt_fail, hipSetDevice(h->device));  // h's own state may die here
+  h->nb_valid = false;
   h->tgt = owner->tgt;  // points and voxel map: one copy on the device, alive until the last handle lets go of it
   h->tgt_owned = false;
   return GORIO_OK;
@@ -1498,6 +1988,7 @@ int gorio_ndt_align_batch(gorio_ndt_t* const* handles, int count, const float* g
   gorio_ndt* lead = handles[0];  // its stream carries the rounds, its scratch holds the tables and the sums
   GORIO_HIP_CHECK(ndt_fail, hipSetDevice(lead->device));
   if (const int rc = ndt_batch_maps(handles, count, "align_batch")) return rc;
+  if (const int rc = ndt_batch_radius_prepare(handles, count, "align_batch")) return rc;
   // ---- scratch for the largest possible round: every handle pending
   size_t max_blocks = 0;
   for (int i = 0; i < count; ++i) max_blocks += (size_t)(handles[i]->n_s + 255) / 256;
@@ -1508,63 +1999,66 @@ int gorio_ndt_align_batch(gorio_ndt_t* const* handles, int count, const float* g
   GORIO_HIP_CHECK(ndt_fail, lead->b_out.reserve((size_t)28 * count, (size_t)28 * (count + count / 4)));
   GORIO_HIP_CHECK(ndt_fail, lead->b_h_out.reserve(sizeof(double) * 28 * count, sizeof(double) * 28 * (count + count / 4)));
   std::vector<NdtMachine> m;
-  std::vector<int> order;
+  std::vector<int> order, rk;
   try {
     m.resize(count);
     order.reserve(count);
+    rk.reserve(count);
   } catch (const std::bad_alloc&) {
     return ndt_fail(GORIO_ERR_ALLOC, "align_batch: out of host memory");
   }
   for (int i = 0; i < count; ++i) m[i].begin(handles[i], guesses ? guesses + (size_t)16 * i : nullptr);
   gorio_ndt_batch_stats bs{0, 0, 0};
   NdtJob* const h_jobs = static_cast<NdtJob*>(lead->b_h_jobs.get());
+  std::vector<NdtRadiusJob> rjobs;
+  const hipStream_t stream = ndt_batch_stream(handles, count);
   for (;;) {
-    // the pending evaluations, grouped by mode: job k of the round belongs to handle order[k]
+    // the pending evaluations, grouped by neighbourhood source and mode (DIRECT 0, 1, 2, then radius 0, 1, 2): job k of the round belongs
+    // to handle order[k]
     order.clear();
-    int mode_first_block[4] = {0, 0, 0, 0};
+    int group_first_block[7] = {0, 0, 0, 0, 0, 0, 0};
     int blocks = 0;
-    for (int mode = 0; mode < 3; ++mode) {
-      mode_first_block[mode] = blocks;
+    rk.clear();
+    for (int group = 0; group < 6; ++group) {
+      group_first_block[group] = blocks;
       for (int i = 0; i < count; ++i)
-        if (!m[i].done() && m[i].mode == mode) {
+        if (!m[i].done() && m[i].mode == group % 3 && handles[i]->radius == (group >= 3)) {
           blocks += (handles[i]->n_s + 255) / 256;
+          if (group >= 3) rk.push_back((int)order.size());
           order.push_back(i);
         }
     }
-    mode_first_block[3] = blocks;
+    group_first_block[6] = blocks;
     const int njobs = (int)order.size();
     if (njobs == 0) break;
     int2* const h_wg = reinterpret_cast<int2*>(h_jobs + njobs);
     int slot = 0;
     for (int k = 0; k < njobs; ++k) {
-      const gorio_ndt* h = handles[order[k]];
+      gorio_ndt* h = handles[order[k]];
       const NdtMachine& mk = m[order[k]];
-      NdtJob& j = h_jobs[k];
-      j.sx = h->sx; j.sy = h->sy; j.sz = h->sz;
-      j.n = h->n_s;
-      j.mode = mk.mode;
-      j.first = slot;
-      j.nblk = (h->n_s + 255) / 256;
-      j.vm = h->map();
-      j.ev = ndt_make_eval(h, mk.x_eval, mk.st.T);
-      for (int b = 0; b < j.nblk; ++b) h_wg[slot + b] = make_int2(k, b);
-      slot += j.nblk;
+      ndt_fill_job(h_jobs[k], h, mk.mode, slot, ndt_make_eval(h, mk.x_eval, mk.st.T));
+      for (int b = 0; b < h_jobs[k].nblk; ++b) h_wg[slot + b] = make_int2(k, b);
+      slot += h_jobs[k].nblk;
     }
     const size_t bytes = sizeof(NdtJob) * (size_t)njobs + sizeof(int2) * (size_t)blocks;  // <= table_bytes
-    GORIO_HIP_CHECK(ndt_fail, hipMemcpyAsync(lead->b_jobs.get(), h_jobs, bytes, hipMemcpyHostToDevice, lead->stream));
-    const NdtJob* d_jobs = static_cast<const NdtJob*>(lead->b_jobs.get());
+    GORIO_HIP_CHECK(ndt_fail, hipMemcpyAsync(lead->b_jobs.get(), h_jobs, bytes, hipMemcpyHostToDevice, stream));
+    NdtJob* d_jobs = static_cast<NdtJob*>(lead->b_jobs.get());
     const int2* d_wg = reinterpret_cast<const int2*>(d_jobs + njobs);
-    for (int mode = 0; mode < 3; ++mode) {
-      const int nb = mode_first_block[mode + 1] - mode_first_block[mode];
+    if (const int rc = ndt_batch_neighbours(handles, order, rk, h_jobs, d_jobs, d_wg + group_first_block[3], group_first_block[6] - group_first_block[3], stream, rjobs,
+                                            &bs.launches))
+      return rc;
+    for (int group = 0; group < 6; ++group) {
+      const int nb = group_first_block[group + 1] - group_first_block[group];
       if (nb == 0) continue;
-      ndt_launch_batch(mode, nb, lead->stream, d_jobs, d_wg + mode_first_block[mode], lead->b_partials.get());
+      ndt_launch_batch(group % 3, group >= 3, nb, stream, d_jobs, d_wg + group_first_block[group], lead->b_partials.get());
       bs.launches++;
     }
-    ndt_fold_batch_kernel<<<njobs, 64, 0, lead->stream>>>(d_jobs, lead->b_partials, 28, lead->b_out);
+    ndt_fold_batch_kernel<<<njobs, 64, 0, stream>>>(d_jobs, lead->b_partials, 28, lead->b_out);
     bs.launches++;
     GORIO_HIP_CHECK(ndt_fail, hipGetLastError());
-    GORIO_HIP_CHECK(ndt_fail, hipMemcpyAsync(lead->b_h_out.get(), lead->b_out, sizeof(double) * 28 * njobs, hipMemcpyDeviceToHost, lead->stream));
-    GORIO_HIP_CHECK(ndt_fail, hipStreamSynchronize(lead->stream));  // the pinned tables are free again after it
+    GORIO_HIP_CHECK(ndt_fail, hipMemcpyAsync(lead->b_h_out.get(), lead->b_out, sizeof(double) * 28 * njobs, hipMemcpyDeviceToHost, stream));
+    GORIO_HIP_CHECK(ndt_fail, hipStreamSynchronize(stream));  // the pinned tables are free again after it
+    ndt_batch_neighbours_done(handles, order, rk);
     const double* sums = static_cast<const double*>(lead->b_h_out.get());
     for (int k = 0; k < njobs; ++k) m[order[k]].resume(sums + (size_t)28 * k);
     bs.rounds++;
@@ -1586,6 +2080,7 @@ int gorio_ndt_calculate_score_batch(gorio_ndt_t* const* handles, int count, cons
   gorio_ndt* lead = handles[0];  // its stream carries the launches, its batch scratch holds the table and the sums
   GORIO_HIP_CHECK(ndt_fail, hipSetDevice(lead->device));
   if (const int rc = ndt_batch_maps(handles, count, "calculate_score_batch")) return rc;
+  if (const int rc = ndt_batch_radius_prepare(handles, count, "calculate_score_batch")) return rc;
   size_t blocks = 0;
   for (int i = 0; i < count; ++i) blocks += (size_t)(handles[i]->n_s + 255) / 256;
   if (blocks > (size_t)INT_MAX) return ndt_fail(GORIO_ERR_INVALID, "calculate_score_batch: too many source points in one batch");
@@ -1598,28 +2093,38 @@ int gorio_ndt_calculate_score_batch(gorio_ndt_t* const* handles, int count, cons
   static const float kIdentity[16] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1};
   NdtJob* const h_jobs = static_cast<NdtJob*>(lead->b_h_jobs.get());
   int2* const h_wg = reinterpret_cast<int2*>(h_jobs + count);
+  const hipStream_t stream = ndt_batch_stream(handles, count);
+  std::vector<int> order((size_t)count), rk;
   int slot = 0;
-  for (int k = 0; k < count; ++k) {
-    const gorio_ndt* h = handles[k];
-    NdtJob& j = h_jobs[k];
-    j.sx = h->sx; j.sy = h->sy; j.sz = h->sz;
-    j.n = h->n_s;
-    j.mode = 3;
-    j.first = slot;
-    j.nblk = (h->n_s + 255) / 256;
-    j.vm = h->map();
-    j.ev = ndt_make_eval(h, nullptr, T ? T + (size_t)16 * k : kIdentity);
-    for (int b = 0; b < j.nblk; ++b) h_wg[slot + b] = make_int2(k, b);  // x < count, y < nblk: what the kernel relies on
-    slot += j.nblk;
+  for (int k = 0; k < count; ++k) {  // job k is handle k; its partial slots follow handle order
+    order[k] = k;
+    ndt_fill_job(h_jobs[k], handles[k], 3, slot, ndt_make_eval(handles[k], nullptr, T ? T + (size_t)16 * k : kIdentity));
+    slot += h_jobs[k].nblk;
   }
-  GORIO_HIP_CHECK(ndt_fail, hipMemcpyAsync(lead->b_jobs.get(), h_jobs, bytes, hipMemcpyHostToDevice, lead->stream));
-  const NdtJob* d_jobs = static_cast<const NdtJob*>(lead->b_jobs.get());
+  // the (job, block) table: the DIRECT jobs' workgroups first, then the radius jobs'.  x < count, y < nblk: what the kernels rely on
+  int w = 0, direct_blocks = 0;
+  for (int pass = 0; pass < 2; ++pass) {
+    if (pass == 1) direct_blocks = w;
+    for (int k = 0; k < count; ++k) {
+      if (handles[k]->radius != (pass == 1)) continue;
+      if (pass == 1) rk.push_back(k);
+      for (int b = 0; b < h_jobs[k].nblk; ++b) h_wg[w++] = make_int2(k, b);
+    }
+  }
+  const int radius_blocks = (int)blocks - direct_blocks;
+  GORIO_HIP_CHECK(ndt_fail, hipMemcpyAsync(lead->b_jobs.get(), h_jobs, bytes, hipMemcpyHostToDevice, stream));
+  NdtJob* d_jobs = static_cast<NdtJob*>(lead->b_jobs.get());
   const int2* d_wg = reinterpret_cast<const int2*>(d_jobs + count);
-  ndt_score_batch_kernel<<<(int)blocks, 256, 0, lead->stream>>>(d_jobs, d_wg, lead->b_partials.get());
-  ndt_fold_batch_kernel<<<count, 64, 0, lead->stream>>>(d_jobs, lead->b_partials, 1, lead->b_out);
+  std::vector<NdtRadiusJob> rjobs;
+  int launches = 0;
+  if (const int rc = ndt_batch_neighbours(handles, order, rk, h_jobs, d_jobs, d_wg + direct_blocks, radius_blocks, stream, rjobs, &launches)) return rc;
+  if (direct_blocks) ndt_score_batch_kernel<<<direct_blocks, 256, 0, stream>>>(d_jobs, d_wg, lead->b_partials.get());
+  if (radius_blocks) ndt_score_csr_batch_kernel<<<radius_blocks, 256, 0, stream>>>(d_jobs, d_wg + direct_blocks, lead->b_partials.get());
+  ndt_fold_batch_kernel<<<count, 64, 0, stream>>>(d_jobs, lead->b_partials, 1, lead->b_out);
   GORIO_HIP_CHECK(ndt_fail, hipGetLastError());
-  GORIO_HIP_CHECK(ndt_fail, hipMemcpyAsync(lead->b_h_out.get(), lead->b_out, sizeof(double) * count, hipMemcpyDeviceToHost, lead->stream));
-  GORIO_HIP_CHECK(ndt_fail, hipStreamSynchronize(lead->stream));  // the pinned table is free again after it
+  GORIO_HIP_CHECK(ndt_fail, hipMemcpyAsync(lead->b_h_out.get(), lead->b_out, sizeof(double) * count, hipMemcpyDeviceToHost, stream));
+  GORIO_HIP_CHECK(ndt_fail, hipStreamSynchronize(stream));  // the pinned table is free again after it
+  ndt_batch_neighbours_done(handles, order, rk);
   const double* sums = static_cast<const double*>(lead->b_h_out.get());
   for (int k = 0; k < count; ++k) score[k] = sums[k] / (double)handles[k]->n_s;  // NDT:982
   return GORIO_OK;

@@ -1,8 +1,8 @@
 // Drop-in for ndt_omp/include/pclomp/ndt_omp.h of the Go-RIO sources (NDTH; NDT = ndt_omp_impl.hpp): pclomp::NormalDistributionsTransform
 // with the surface select_registration_method (registrations.cpp:117-134) and ndt_omp/apps/align.cpp use, on top of the C ABI of
 // include/gorio_ndt.h.  Every body is an ABI call; the voxel map, the derivative sums and the score run on the GPU.  KDTREE is refused
-// by the library (std::runtime_error here).  getFitnessScore, which the nodelets call after every match (scan_matching_odometry_nodelet.cpp:675,
-// loop_detector.cpp:229, 415), is computed on the GPU as the fast_gicp drop-ins do, through a registration handle of include/gorio_apd.h
+// by the library (std::runtime_error here); its neighbourhood -- pcl::NormalDistributionsTransform -- is the class of gorio/ndt.hpp.
+// getFitnessScore, which the nodelets call after every match (scan_matching_odometry_nodelet.cpp:675, loop_detector.cpp:229, 415), is computed on the GPU as the fast_gicp drop-ins do, through a registration handle of include/gorio_apd.h
 // that holds the same two clouds; through a pcl::Registration base pointer real PCL still runs its own CPU version.
 // Extras without a counterpart in the reference (INTEGRATION.md sections 8, 11): setInputTargetShared, alignBatch, getFitnessScoreBatch,
 // calculateScoreBatch, and the inputs that are already on the device: setInputSourceFromScan / setInputTargetFromScan (the frame a
@@ -319,6 +319,8 @@ class NormalDistributionsTransform : public pcl::Registration<PointSource, Point
   }
 
  protected:
+  gorio_ndt_t* handle() const { return h_; }  // for gorio::NormalDistributionsTransform (gorio/ndt.hpp), which switches the radius search on
+
   void computeTransformation(PointCloudSource& output, const Eigen::Matrix4f& guess) override {  // NDT:81-171
     p_.transformation_epsilon = transformation_epsilon_;
     p_.max_iterations = max_iterations_;

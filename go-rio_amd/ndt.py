@@ -1,5 +1,5 @@
-"""ctypes binding of include/gorio_ndt.h: NDT_OMP registration (pclomp::NormalDistributionsTransform, DIRECT1 / 7 / 26) on the GPU
-(no numerics here, no CPU fallback)."""
+"""ctypes binding of include/gorio_ndt.h: NDT_OMP registration (pclomp::NormalDistributionsTransform, DIRECT1 / 7 / 26) and the radius
+neighbourhood of pcl::NormalDistributionsTransform / pclomp's KDTREE on the GPU (no numerics here, no CPU fallback)."""
 import ctypes as C
 
 import numpy as np
@@ -7,8 +7,8 @@ import numpy as np
 from .apd import GorioError, load_library
 
 NDT_SYMBOLS = ["gorio_ndt_align", "gorio_ndt_align_batch", "gorio_ndt_calculate_score", "gorio_ndt_calculate_score_batch", "gorio_ndt_create", "gorio_ndt_default_params",
-               "gorio_ndt_derivatives", "gorio_ndt_destroy", "gorio_ndt_get_capacities", "gorio_ndt_get_params", "gorio_ndt_get_voxels", "gorio_ndt_hessian", "gorio_ndt_last_error",
-               "gorio_ndt_set_params", "gorio_ndt_set_source", "gorio_ndt_set_source_device", "gorio_ndt_set_source_from_scan", "gorio_ndt_set_target", "gorio_ndt_set_target_device",
+               "gorio_ndt_derivatives", "gorio_ndt_destroy", "gorio_ndt_get_capacities", "gorio_ndt_get_centroids", "gorio_ndt_get_neighbours", "gorio_ndt_get_params",
+               "gorio_ndt_get_radius_search", "gorio_ndt_get_voxels", "gorio_ndt_hessian", "gorio_ndt_last_error", "gorio_ndt_set_params", "gorio_ndt_set_radius_search", "gorio_ndt_set_source", "gorio_ndt_set_source_device", "gorio_ndt_set_source_from_scan", "gorio_ndt_set_target", "gorio_ndt_set_target_device",
                "gorio_ndt_set_target_from_apd", "gorio_ndt_set_target_from_scan", "gorio_ndt_set_target_shared"]
 KDTREE, DIRECT26, DIRECT7, DIRECT1 = 0, 1, 2, 3  # pclomp::NeighborSearchMethod
 
@@ -38,16 +38,29 @@ def default_params():
     return p
 
 
-class Ndt:
-    """pclomp::NormalDistributionsTransform on the GPU; keyword arguments are fields of gorio_ndt_params."""
+def radius_round_launch_bound(max_radius_source):
+    """Launches one round of align_batch may take when handles with the radius switch on take part (include/gorio_ndt.h): 14 + s,
+    s = 0 up to 4096 points in the largest such source, m (m + 3) / 2 for 4096 * 2^m."""
+    m = 0
+    while 4096 << m < int(max_radius_source):
+        m += 1
+    return 14 + m * (m + 3) // 2
 
-    def __init__(self, device=0, **params):
+
+class Ndt:
+    """pclomp::NormalDistributionsTransform on the GPU; keyword arguments are fields of gorio_ndt_params.  radius_search=True makes it
+    pcl::NormalDistributionsTransform (pclomp's KDTREE): every neighbourhood is the radius search over the leaf centroids."""
+
+    def __init__(self, device=0, radius_search=False, **params):
         self.lib = load_library()
         self.lib.gorio_ndt_last_error.restype = C.c_char_p
         self.h = C.c_void_p()
+        self._n_source = None  # known for sources set from the host or from device arrays
         self._check(self.lib.gorio_ndt_create(C.byref(self.h), int(device)))
         if params:
             self.set_params(**params)
+        if radius_search:
+            self.set_radius_search(True)
 
     def _check(self, rc):
         if rc < 0:
@@ -76,6 +89,37 @@ class Ndt:
             setattr(p, k, v)
         self._check(self.lib.gorio_ndt_set_params(self.h, C.byref(p)))
 
+    def set_radius_search(self, enable):
+        """Switch the radius neighbourhood on or off; params.search is kept and rules again when it is off."""
+        self._check(self.lib.gorio_ndt_set_radius_search(self.h, int(bool(enable))))
+
+    def get_radius_search(self):
+        e = C.c_int()
+        self._check(self.lib.gorio_ndt_get_radius_search(self.h, C.byref(e)))
+        return bool(e.value)
+
+    def centroids(self):
+        """The centroid cloud of the radius mode: (xyz float32 [C, 3], leaf_pos int32 [C]: the centroid's leaf in voxels() order)."""
+        n = C.c_int()
+        self._check(self.lib.gorio_ndt_get_centroids(self.h, 0, C.byref(n), None, None))
+        c = n.value
+        xyz, pos = np.zeros((max(c, 1), 3), np.float32), np.zeros(max(c, 1), np.int32)
+        self._check(self.lib.gorio_ndt_get_centroids(self.h, max(c, 1), C.byref(n), _ptr(xyz), _ptr(pos)))
+        return xyz[:c], pos[:c]
+
+    def neighbours(self, n_source=None):
+        """The CSR of the last radius evaluation: (offsets int64 [source size + 1], leaf_pos int32 [total], sqd float32 [total]).
+        n_source: the source's size, needed when the source came from a scan pipeline or a keyframe store."""
+        n_source = self._n_source if n_source is None else int(n_source)
+        if n_source is None:
+            raise ValueError("neighbours: pass n_source for a source that was handed over on the device")
+        offs = np.zeros(n_source + 1, np.int64)
+        self._check(self.lib.gorio_ndt_get_neighbours(self.h, _ptr(offs), None, None, 0))
+        total = int(offs[-1])
+        pos, sqd = np.zeros(max(total, 1), np.int32), np.zeros(max(total, 1), np.float32)
+        self._check(self.lib.gorio_ndt_get_neighbours(self.h, _ptr(offs), _ptr(pos), _ptr(sqd), max(total, 1)))
+        return offs, pos[:total], sqd[:total]
+
     def set_target(self, xyz):
         a = np.ascontiguousarray(xyz, np.float32).reshape(-1, 3)
         self._check(self.lib.gorio_ndt_set_target(self.h, _ptr(a) if a.size else None, a.shape[0], 12))
@@ -83,6 +127,7 @@ class Ndt:
     def set_source(self, xyz):
         a = np.ascontiguousarray(xyz, np.float32).reshape(-1, 3)
         self._check(self.lib.gorio_ndt_set_source(self.h, _ptr(a) if a.size else None, a.shape[0], 12))
+        self._n_source = a.shape[0]
 
     def set_target_shared(self, owner):
         """This handle's target becomes owner's current target: points and voxel map exist once on the device."""
@@ -94,10 +139,12 @@ class Ndt:
 
     def set_source_device(self, x, y, z, n):
         self._check(self.lib.gorio_ndt_set_source_device(self.h, C.c_void_p(x), C.c_void_p(y), C.c_void_p(z), int(n)))
+        self._n_source = int(n)
 
     def set_source_from_scan(self, scan):
         """The output of a prep.ScanPipeline's last OK run becomes the source: one device-to-device copy, no host round trip."""
         self._check(self.lib.gorio_ndt_set_source_from_scan(self.h, scan.h))
+        self._n_source = None
 
     def set_target_from_scan(self, scan):
         self._check(self.lib.gorio_ndt_set_target_from_scan(self.h, scan.h))
@@ -109,6 +156,7 @@ class Ndt:
     def set_source_from_keyframe(self, store, kid):
         """A keyframes.KeyframeStore entry becomes the source: one device-to-device copy of x, y, z."""
         self._check(self.lib.gorio_ndt_set_source_from_keyframe(self.h, store.h, int(kid)))
+        self._n_source = None
 
     def set_target_from_keyframe(self, store, kid):
         self._check(self.lib.gorio_ndt_set_target_from_keyframe(self.h, store.h, int(kid)))

@@ -47,10 +47,30 @@
  * (include/gorio_scan.h), gorio_ndt_set_target_from_apd the current target of a registration handle of include/gorio_apd.h (the
  * scan-to-submap target, say), each as one device-to-device copy.  gorio_ndt_calculate_score_batch is the score's batch form.
  *
- * Out of scope: KDTREE search (a radius search over leaf centroids: another structure; REG:127-133 selects it only on request, it
- * is refused with GORIO_ERR_UNSUPPORTED), RCCL sharding, and PCL's single-thread pcl::NormalDistributionsTransform (REG:111: the same
- * algorithm with KDTREE only).  The structure a KDTREE mode needs exists now -- exact radius queries of arbitrary points against a
- * device-resident cloud, include/gorio_search.h -- but nothing here is wired to it: KDTREE stays refused.
+ * The radius neighbourhood: pcl::NormalDistributionsTransform (REG:109-115, plain "NDT") and pclomp's KDTREE (NDT:234-235, 573-574,
+ * 948-949) take every neighbourhood from target_cells_.radiusSearch(x_trans_pt, resolution_, ...) over the cloud of leaf centroids.
+ * gorio_ndt_set_radius_search(h, 1) selects it, whatever params.search holds; params.search = GORIO_NDT_KDTREE itself stays refused
+ * by gorio_ndt_set_params (GORIO_ERR_UNSUPPORTED; the text names gorio_ndt_set_radius_search).  What is fixed here for that mode:
+ *   - CENTROID CLOUD (VGC:282-326): one point per leaf with nr_points >= min_points_per_voxel, in ascending leaf index.  A leaf that
+ *     VGC:337-341 or VGC:360-364 disables afterwards stays in the cloud (it is pushed before the `continue`) and is a neighbour with
+ *     a ZERO inverse covariance: the constructor's value (VGCH:108) for the first rule; for the second the reference would carry
+ *     the infinities, here the leaf's icov is zero as gorio_ndt_get_voxels reports it;
+ *   - CENTROID COORDINATES are float: the running float sum of the leaf's points in input order (VGC:242-243) divided per element
+ *     by (float) nr_points (VGC:289, a true division).  The search index is over these floats; cell->getMean() in the pair
+ *     arithmetic stays the double mean.  A float sum that overflows makes the cloud non-finite: the evaluation is refused
+ *     (GORIO_ERR_INVALID);
+ *   - SEARCH: radius resolution_ (the float member), max_nn = 0, the rule of include/gorio_search.h: un-fused float L2_Simple,
+ *     strictly below (float)((double) r * (double) r), results in ascending (distance, centroid index) -- the order a point's pair
+ *     terms are added in.  A query without a centroid in range has no neighbour; there is no cell-range test on this path; a map
+ *     without an eligible leaf gives zero sums;
+ *   - PAIR ARITHMETIC is unchanged (the float path, the float path with the Hessian, the double computeHessian); calculateScore
+ *     divides a point's sum by neighborhood.size().
+ * An evaluation is one query launch (the float-transformed source: the bits the search sees are the bits the pair arithmetic reads),
+ * one radius search (a CSR) and one launch that walks each point's segment; they run on the device's launch stream, where the search
+ * runs.  The centroid cloud and its index belong to the target state (sharers of gorio_ndt_set_target_shared see ONE index) and are
+ * built by the first call that needs them.
+ *
+ * Out of scope: RCCL sharding; params.search = GORIO_NDT_KDTREE as a spelling of the radius mode (it stays refused, see above).
  */
 #ifndef GORIO_NDT_H
 #define GORIO_NDT_H
@@ -90,10 +110,18 @@ void gorio_ndt_default_params(gorio_ndt_params* p);
 /* new pclomp::NormalDistributionsTransform (NDT:47-76) with the default parameters. */
 int gorio_ndt_create(gorio_ndt_t** out, int device);
 void gorio_ndt_destroy(gorio_ndt_t* h);
-/* The setters of NDTH:115-191 in one call.  A changed resolution (or leaf rule) marks the voxel map stale (NDTH:133-142).  KDTREE,
- * unknown search values and resolution <= 0 are refused with GORIO_ERR_UNSUPPORTED and change nothing. */
+/* The setters of NDTH:115-191 in one call.  A changed resolution (or leaf rule) marks the voxel map stale (NDTH:133-142).  KDTREE
+ * (its neighbourhood is selected by gorio_ndt_set_radius_search instead), unknown search values and resolution <= 0 are refused with
+ * GORIO_ERR_UNSUPPORTED and change nothing. */
 int gorio_ndt_set_params(gorio_ndt_t* h, const gorio_ndt_params* p);
 int gorio_ndt_get_params(const gorio_ndt_t* h, gorio_ndt_params* p);
+
+/* The radius neighbourhood of pcl::NormalDistributionsTransform / pclomp::KDTREE (see the head of this file): 0 by default.  While it
+ * is on, every neighbourhood of computeDerivatives, computeHessian and calculateScore is the radius search over the leaf centroids,
+ * whatever params.search holds; params.search is kept and rules again when the switch goes off.  A changed value keeps the map and
+ * invalidates the neighbour lists gorio_ndt_get_neighbours reports.  NULL arguments: GORIO_ERR_INVALID. */
+int gorio_ndt_set_radius_search(gorio_ndt_t* h, int enable);
+int gorio_ndt_get_radius_search(const gorio_ndt_t* h, int* enabled);
 
 /* setInputTarget (NDTH:122-127): xyz points at the first x, stride_bytes between points (a multiple of 4, >= 12), n >= 0.  The map is
  * built at the next call that needs it.  Non-finite points are accepted and skipped by the map. */
@@ -122,6 +150,16 @@ int gorio_ndt_set_target_shared(gorio_ndt_t* h, gorio_ndt_t* owner);
 int gorio_ndt_get_voxels(gorio_ndt_t* h, int capacity, int* n_leaves, int* leaf_index, int* nr_points, double* mean, double* cov_raw, double* cov, double* icov,
                          int* min_b, int* div_b);
 
+/* Parity hooks of the radius mode.  gorio_ndt_get_centroids: the centroid cloud (built now when it is stale, switch on or off);
+ * *n_centroids is always set, xyz [3 per centroid] and leaf_pos [position of the centroid's leaf in gorio_ndt_get_voxels' order] may be
+ * NULL and need capacity >= *n_centroids.  gorio_ndt_get_neighbours: the CSR of this handle's LAST radius evaluation (derivatives,
+ * Hessian, score, or the last evaluation of an align, single or batched): offsets [source size + 1], then per neighbour its leaf
+ * position and float squared distance, in the order the pair terms were added; capacity (entries of leaf_pos / sqd) below the total
+ * gives GORIO_ERR_INVALID and writes nothing.  GORIO_ERR_STATE when there is no such evaluation, or the source, the target or the
+ * switch changed since. */
+int gorio_ndt_get_centroids(gorio_ndt_t* h, int capacity, int* n_centroids, float* xyz, int* leaf_pos);
+int gorio_ndt_get_neighbours(gorio_ndt_t* h, long long* offsets, int* leaf_pos, float* sqd, long long capacity);
+
 /* setInputSource / setInputTarget with the output of the pipeline's last OK run (the points gorio_scan_get_output reports, in its
  * order), without a host round trip: one device-to-device copy of x, y, z into the handle's own buffers, ordered behind the pipeline's
  * stream by an event.  It is a copy, not a share: the pipeline may load its next frame at once, and none of its counters moves (no
@@ -138,7 +176,8 @@ int gorio_ndt_set_target_from_scan(gorio_ndt_t* ndt, struct gorio_scan* scan);
  * without a target gives GORIO_ERR_STATE.  The registration handle is not changed and may take its next target at once. */
 int gorio_ndt_set_target_from_apd(gorio_ndt_t* ndt, struct gorio_apd* apd);
 
-/* No reference member: the elements the handle's device buffers hold, capacities[4] = target points, source points, leaves, sort keys.
+/* No reference member: the elements the handle's device buffers hold, capacities[4] = target points, source points, leaves, sort keys
+ * (the centroid cloud of the radius mode is at most one point per leaf and is not listed).
  * Buffers grow with the clouds and are kept when a smaller (or empty) cloud follows: equal capacities mean nothing was reallocated.
  * A handle whose target came through gorio_ndt_set_target_shared owns none of it and reports 0 for target points, leaves and sort keys.
  * A source that comes from the device (gorio_ndt_set_source_device, _set_source_from_scan) is checked while it is copied into a staging
@@ -170,8 +209,12 @@ typedef struct {
  * per-workgroup kernel body over source points [256 b, 256 b + 256) of block b, the block partials added in block order.
  * A round collects the pending evaluation of every unfinished handle, sends one job table (one asynchronous copy from pinned memory),
  * launches the derivative kernel once per evaluation mode present (score + gradient; + Hessian; computeHessian), folds all jobs in
- * one launch, and ends with one copy of 28 doubles per job and one synchronisation: launches <= 4 * rounds, and
- * rounds = max_i (n_derivatives_i + n_hessians_i).  Stale maps are built before the first round, once per target state; finished
+ * one launch, and ends with one copy of 28 doubles per job and one synchronisation: launches <= 4 * rounds while every handle is DIRECT,
+ * and rounds = max_i (n_derivatives_i + n_hessians_i).  Handles with the radius switch on may be mixed with DIRECT ones.  A round with
+ * radius jobs adds ONE query launch over those jobs, ONE batched radius search over them (include/gorio_search.h: query keys and their
+ * tiled sort, count, scan, fill, segment sort = 6 + s launches, s = 0 while the largest radius source has at most 4096 points and
+ * m (m + 3) / 2 for 4096 * 2^m; segments hold at most 27 centroids, so the search's long-segment path never runs) and one walk launch
+ * per evaluation mode present among them, and it runs on the device's launch stream: launches <= (14 + s) * rounds.  Stale maps are built before the first round, once per target state; finished
  * handles drop out of the later rounds.  The rounds run on handles[0]'s stream and scratch.
  * count == 0 returns GORIO_OK and touches no device.  count < 0, NULL handles or T_out, a NULL entry, a handle that appears twice or
  * handles on different devices: GORIO_ERR_INVALID.  A handle gorio_ndt_align would refuse (no target, no or an empty source, no finite
@@ -183,7 +226,8 @@ int gorio_ndt_align_batch(gorio_ndt_t* const* handles, int count, const float* g
 /* calculateScore (NDT:935-983) for `count` handles in one round trip.  T: count * 16 floats (handle i's at T + 16 i) or NULL (identity
  * for all); score: count doubles.  score[i] is BIT FOR BIT what gorio_ndt_calculate_score(handles[i], T + 16 i, &s) returns: the same
  * per-workgroup body over the same 256-point blocks, the block partials added in block order, the division by the source size on
- * the host (NDT:982).  One job table goes up, one score launch runs over all handles, one fold launch, one copy of count doubles
+ * the host (NDT:982).  One job table goes up, one score launch runs over all DIRECT handles (and, for handles with the radius switch
+ * on, one query launch, one batched radius search and one walk launch), one fold launch, one copy of count doubles
  * and one synchronisation follow, on handles[0]'s stream and scratch; stale maps are built before, once per target state.
  * Validation as for gorio_ndt_align_batch: count == 0 returns GORIO_OK and touches no device; count < 0, NULL handles or score, a NULL
  * entry, a handle that appears twice or handles on different devices: GORIO_ERR_INVALID; a handle the single call would refuse gives
