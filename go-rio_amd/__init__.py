@@ -37,7 +37,7 @@ from .scan_context import SC_SYMBOLS, ScanContext  # noqa: E402
 from . import ndt  # noqa: E402
 from .ndt import NDT_SYMBOLS, Ndt, NdtBatchStats  # noqa: E402
 from . import keyframes  # noqa: E402
-from .keyframes import KF_SYMBOLS, KeyframeStore  # noqa: E402
+from .keyframes import KF_EDGE_SYMBOLS, KF_SYMBOLS, KeyframeStore  # noqa: E402
 from . import map_cloud  # noqa: E402
 from .map_cloud import MAP_SYMBOLS, MapCloud  # noqa: E402
 from . import search  # noqa: E402

@@ -11,6 +11,7 @@
 #include <hip/hip_runtime.h>
 
 #include "../../include/gorio_keyframes.h"
+#include "edge_information.h"
 
 #pragma clang fp contract(off)
 
@@ -90,6 +91,40 @@ __global__ __launch_bounds__(256) void kf_sc_pack_kernel(const KfScJob* __restri
   pts[j.off + i] = make_float4(p.x, p.y, j.intensity[i], 0.0f);
 }
 
+// ---------------------------------------------------------------------------------------------- pose-graph edges between keyframes
+// The reduction of gorio_kf_edge_fitness (include/gorio_kf_edges.h) over the packed keys the pruned search left: per 256 source points
+// of every edge the sum of the squared distances within max_range_sq and their number.  The partition, the wave_sum tree and the
+// combination of the four wave sums are those of fitness_kernel (apd_kernels.hip), so an edge's partials are bit for bit the ones a
+// single gorio_apd_fitness_score computes.  Edges differ in size by orders of magnitude, so the partials are not a [edges][max blocks]
+// rectangle: every edge's descriptor names its own slice (PairDesc::partials = out + 2 * first block of the edge) and the host reads
+// back exactly the blocks that exist.  grid: (max blocks of one edge, edges), block 256; a block past its edge's last one leaves at once.
+__global__ __launch_bounds__(256) void kf_edge_reduce_kernel(const PairDesc* __restrict__ descs, double max_range_sq) {
+  const PairDesc& pd = descs[blockIdx.y];
+  const int n = pd.src.n;
+  if ((int)blockIdx.x * 256 >= n) return;  // uniform over the block
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  double s = 0.0, c = 0.0;
+  if (i < n) {
+    const unsigned long long key = pd.best_key[i];
+    if (key != ~0ull) {
+      const double d = (double)__uint_as_float((unsigned int)(key >> 32));
+      if (d <= max_range_sq) {
+        s = d;
+        c = 1.0;
+      }
+    }
+  }
+  s = wave_sum(s);
+  c = wave_sum(c);
+  __shared__ double sw[4][2];
+  if ((threadIdx.x & 63) == 0) {
+    sw[threadIdx.x >> 6][0] = s;
+    sw[threadIdx.x >> 6][1] = c;
+  }
+  __syncthreads();
+  if (threadIdx.x < 2) pd.partials[(size_t)blockIdx.x * 2 + threadIdx.x] = (sw[0][threadIdx.x] + sw[1][threadIdx.x]) + (sw[2][threadIdx.x] + sw[3][threadIdx.x]);
+}
+
 }  // namespace gorio
 
 // ================================================================================================= host (include/gorio_keyframes.h)
@@ -113,6 +148,16 @@ struct gorio_kf {
   gorio_apd* up = nullptr;  // made by the first call that needs the device: its stream (the device's launch stream) and upload_cloud run through it
   std::vector<KfEntry> kfs;
   long long point_uploads = 0, point_downloads = 0, device_copies = 0;
+  // gorio_kf_edge_fitness (include/gorio_kf_edges.h).  The search scratch of ALL edges of a call, one slice per edge: packed keys by
+  // source point, seeds by sorted source position, the measured work and the plan of the query waves.  A registration handle keeps
+  // these per handle, which is why two of its pairs cannot share a source; here they belong to the edge.  They grow, never shrink.
+  DevBuf<unsigned long long> e_keys;
+  DevBuf<int> e_seed;
+  DevBuf<unsigned int> e_work, e_plan;
+  DevBuf<void> e_tab;    // the edge table: [edges] PairDesc, then [edges] PairState; staged in e_pin (free again once a call has synchronised)
+  DevBuf<double> e_fit;  // [blocks of all edges][2] partial sums and counts, read back into e_out
+  PinnedBuf e_pin, e_out;
+  long long edge_calls = 0, edge_edges = 0, edge_index_builds = 0, edge_syncs = 0;
 };
 
 namespace {
@@ -469,6 +514,203 @@ int gorio_sc_add_keyframes(gorio_sc_t* h, gorio_kf_t* kf, const int* ids, int co
   if (first_index_out) *first_index_out = h->n;
   h->n += count;
   ++kf->device_copies;
+  return GORIO_OK;
+}
+
+// ------------------------------------------------------------------------------------------------- pose-graph edges (include/gorio_kf_edges.h)
+
+// IMC:55-86 for `count` edges.  who: the entry point's name for the error text.
+static int kf_edge_fitness_impl(gorio_kf* kf, const char* who, const gorio_kf_edge* edges, int count, double max_range, double* score, long long* n_in_range) {
+  const std::string what = std::string(who) + ": ";
+  if (count > 65535) return kf_fail(GORIO_ERR_UNSUPPORTED, what + std::to_string(count) + " edges in one call (at most 65535: one edge is one grid row)");
+  if (std::isnan(max_range)) return kf_fail(GORIO_ERR_INVALID, what + "max_range is NaN");
+  // every check, then the sizes: nothing below this block can refuse an argument
+  struct Slice {
+    int e;  // index into edges[]
+    size_t key_off, seed_off, work_off, plan_off, blk0;
+  };
+  std::vector<Slice> live;  // the edges with points on both sides, in the caller's order
+  std::vector<std::pair<gorio_apd*, DevCloud*>> clouds;
+  size_t n_keys = 0, n_seed = 0, n_work = 0, n_plan = 0, n_blk = 0;
+  long long total_src = 0, total_waves = 0;
+  int max_n = 1, max_nbx = 1, max_spad = 512;
+  try {
+    for (int e = 0; e < count; ++e) {
+      const std::string at = what + "edges[" + std::to_string(e) + "]: ";
+      int rc = GORIO_OK;
+      std::string why;
+      const KfEntry* t = kf_entry(kf, edges[e].target_id, &rc, &why);
+      if (!t) return kf_fail(rc, at + "target: " + why);
+      const KfEntry* s = kf_entry(kf, edges[e].source_id, &rc, &why);
+      if (!s) return kf_fail(rc, at + "source: " + why);
+      for (int q = 0; q < 16; ++q)
+        if (!std::isfinite(edges[e].relpose[q])) return kf_fail(GORIO_ERR_INVALID, at + "relpose[" + std::to_string(q) + "] is not finite");
+      total_src += s->n;
+      if (total_src > (long long)INT_MAX) return kf_fail(GORIO_ERR_UNSUPPORTED, at + "more than 2^31 - 1 source points over the edges of one call");
+      if (s->n <= 0 || t->n <= 0) continue;  // scores DBL_MAX below, takes no part in the launches
+      const int spad = roundup(s->n, 512), wcap = spad / 64;
+      live.push_back(Slice{e, n_keys, n_seed, n_work, n_plan, n_blk});
+      n_keys += (size_t)s->n;
+      n_seed += (size_t)spad;
+      n_work += 2 * (size_t)wcap;
+      n_plan += 1 + 16 * (size_t)wcap;
+      n_blk += (size_t)((s->n + 255) / 256);
+      total_waves += (s->n + 63) / 64;
+      max_n = std::max(max_n, s->n);
+      max_nbx = std::max(max_nbx, (s->n + 255) / 256);
+      max_spad = std::max(max_spad, spad);
+      clouds.emplace_back(kf->up, s->cloud.get());
+      clouds.emplace_back(kf->up, t->cloud.get());
+    }
+  } catch (const std::bad_alloc&) {
+    return kf_fail(GORIO_ERR_ALLOC, what + "out of memory");
+  }
+  int rc = kf_ensure_device(kf, who);  // (a store that holds a keyframe has its device side already)
+  if (rc) return rc;
+  for (int e = 0; e < count; ++e) {
+    score[e] = DBL_MAX;  // IMC:85
+    if (n_in_range) n_in_range[e] = 0;
+  }
+  const int m = (int)live.size();
+  if (m == 0) {  // nothing but empty keyframes: nothing to launch, nothing to wait for
+    ++kf->edge_calls;
+    kf->edge_edges += count;
+    return GORIO_OK;
+  }
+  GORIO_HIP_CHECK(kf_fail, hipSetDevice(kf->device));
+  gorio_apd* up = kf->up;
+  hipStream_t st = up->stream;
+  {  // ONE index build for the keyframes that lack one; a keyframe named by many edges is one cloud
+    std::unordered_set<DevCloud*> lacking;
+    for (auto& c : clouds)
+      if (!c.second->idx_valid) lacking.insert(c.second);
+    rc = run_index_build(up, clouds);
+    if (rc) return kf_fail(rc, what + up->err);
+    kf->edge_index_builds += (long long)lacking.size();
+  }
+  const size_t b_desc = sizeof(PairDesc) * (size_t)m, b_tab = b_desc + sizeof(PairState) * (size_t)m, b_out = sizeof(double) * 2 * n_blk;
+  GORIO_HIP_CHECK(kf_fail, kf->e_keys.reserve(n_keys, n_keys + n_keys / 8));
+  GORIO_HIP_CHECK(kf_fail, kf->e_seed.reserve(n_seed, n_seed + n_seed / 8));
+  GORIO_HIP_CHECK(kf_fail, kf->e_work.reserve(n_work, n_work + n_work / 8));
+  GORIO_HIP_CHECK(kf_fail, kf->e_plan.reserve(n_plan, n_plan + n_plan / 8));
+  GORIO_HIP_CHECK(kf_fail, kf->e_fit.reserve(2 * n_blk, 2 * n_blk + n_blk / 4));
+  GORIO_HIP_CHECK(kf_fail, kf->e_tab.reserve(b_tab, b_tab + b_tab / 2));
+  GORIO_HIP_CHECK(kf_fail, kf->e_pin.reserve(b_tab, b_tab + b_tab / 2));
+  GORIO_HIP_CHECK(kf_fail, kf->e_out.reserve(b_out, b_out + b_out / 2));
+  static_assert(sizeof(PairDesc) % 8 == 0, "the states follow the descriptors in one table");
+  PairDesc* h_desc = static_cast<PairDesc*>(kf->e_pin.get());
+  PairState* h_state = reinterpret_cast<PairState*>(static_cast<char*>(kf->e_pin.get()) + b_desc);
+  PairDesc* d_desc = static_cast<PairDesc*>(kf->e_tab.get());
+  PairState* d_state = reinterpret_cast<PairState*>(static_cast<char*>(kf->e_tab.get()) + b_desc);
+  for (int k = 0; k < m; ++k) {
+    const Slice& sl = live[k];
+    const gorio_kf_edge& ed = edges[sl.e];
+    const DevCloud& src = *kf->kfs[ed.source_id].cloud;
+    const DevCloud& tgt = *kf->kfs[ed.target_id].cloud;
+    PairDesc& d = h_desc[k];
+    std::memset(&d, 0, sizeof(d));
+    d.src = src.view();
+    d.tgt = tgt.view();
+    d.best_key = kf->e_keys.get() + sl.key_off;
+    d.seed = kf->e_seed.get() + sl.seed_off;
+    d.nn_work = kf->e_work.get() + sl.work_off;
+    d.nn_plan = kf->e_plan.get() + sl.plan_off;
+    d.nn_wcap = roundup(src.n, 512) / 64;
+    d.partials = kf->e_fit.get() + 2 * sl.blk0;  // this edge's slice of the block partials (kf_edge_reduce_kernel)
+    d.state = d_state + k;
+    d.nblk = (src.n + 255) / 256;
+    d.nn_splits = 1;  // (the exhaustive search's split of the target: not launched here)
+    d.nn_chunk = std::max(512, roundup(tgt.n_pad, kPad));
+    d.shard_lo = 0;
+    d.shard_hi = INT_MAX;
+    // relpose.cast<float>() (IMC:63), then exactly what gorio_apd_fitness_score makes of a float pose
+    float Tf[16];
+    double Td[16];
+    for (int q = 0; q < 16; ++q) {
+      Tf[q] = (float)ed.relpose[q];
+      Td[q] = (double)Tf[q];
+    }
+    init_state(h_state[k], Td);
+    for (int q = 0; q < 12; ++q) h_state[k].Tf[q] = Tf[q];
+  }
+  GORIO_HIP_CHECK(kf_fail, hipMemcpyAsync(kf->e_tab.get(), kf->e_pin.get(), b_tab, hipMemcpyHostToDevice, st));
+  arm_keys_kernel<<<dim3(std::min(64, (max_n + 255) / 256), m), 256, 0, st>>>(d_desc);
+  launch_pruned(dim3(max_spad / 256, fitness_splits((long)total_waves), m), st, d_desc, fitness_bound(max_range, 0.0), 0);
+  gorio::kf_edge_reduce_kernel<<<dim3(max_nbx, m), 256, 0, st>>>(d_desc, max_range);
+  GORIO_HIP_CHECK(kf_fail, hipGetLastError());
+  GORIO_HIP_CHECK(kf_fail, hipMemcpyAsync(kf->e_out.get(), kf->e_fit.get(), b_out, hipMemcpyDeviceToHost, st));
+  GORIO_HIP_CHECK(kf_fail, hipStreamSynchronize(st));
+  ++kf->edge_syncs;
+  ++kf->edge_calls;
+  kf->edge_edges += count;
+  const double* part = static_cast<const double*>(kf->e_out.get());
+  for (int k = 0; k < m; ++k) {
+    const Slice& sl = live[k];
+    const int nbx = h_desc[k].nblk;
+    double sum = 0.0, cnt = 0.0;
+    for (int bk = 0; bk < nbx; ++bk) {  // block order, as gorio_apd_fitness_score adds them
+      sum += part[2 * (sl.blk0 + bk)];
+      cnt += part[2 * (sl.blk0 + bk) + 1];
+    }
+    score[sl.e] = cnt > 0 ? sum / cnt : DBL_MAX;
+    if (n_in_range) n_in_range[sl.e] = (long long)cnt;
+  }
+  return GORIO_OK;
+}
+
+int gorio_kf_edge_fitness(gorio_kf_t* kf, const gorio_kf_edge* edges, int count, double max_range, double* score, long long* n_in_range) {
+  if (!kf) return kf_fail(GORIO_ERR_INVALID, "edge_fitness: null handle");
+  if (count < 0) return kf_fail(GORIO_ERR_INVALID, "edge_fitness: count < 0");
+  if (count == 0) return GORIO_OK;
+  if (!edges || !score) return kf_fail(GORIO_ERR_INVALID, "edge_fitness: null argument");
+  return kf_edge_fitness_impl(kf, "edge_fitness", edges, count, max_range, score, n_in_range);
+}
+
+void gorio_kf_default_inf_params(gorio_inf_params* p) {
+  if (!p) return;
+  p->use_const_inf_matrix = 0;  // IMC:15-24
+  p->const_stddev_x = 0.5;
+  p->const_stddev_q = 0.1;
+  p->var_gain_a = 20.0;
+  p->min_stddev_x = 0.1;
+  p->max_stddev_x = 5.0;
+  p->min_stddev_q = 0.05;
+  p->max_stddev_q = 0.2;
+  p->fitness_score_thresh = 0.5;
+}
+
+int gorio_kf_edge_information(gorio_kf_t* kf, const gorio_inf_params* p, const gorio_kf_edge* edges, int count, double* inf_diag, double* score) {
+  if (!kf) return kf_fail(GORIO_ERR_INVALID, "edge_information: null handle");
+  if (!p) return kf_fail(GORIO_ERR_INVALID, "edge_information: null parameters");
+  if (count < 0) return kf_fail(GORIO_ERR_INVALID, "edge_information: count < 0");
+  if (count == 0) return GORIO_OK;
+  if (!inf_diag) return kf_fail(GORIO_ERR_INVALID, "edge_information: null argument");
+  if (p->use_const_inf_matrix) {  // IMC:30-35: neither cloud is looked at
+    for (int e = 0; e < count; ++e) gorio::edge_information_from_score(*p, 0.0, inf_diag + 2 * (size_t)e);
+    return GORIO_OK;
+  }
+  if (!edges) return kf_fail(GORIO_ERR_INVALID, "edge_information: null argument");
+  std::vector<double> own;
+  if (!score) {
+    try {
+      own.resize((size_t)count);
+    } catch (const std::bad_alloc&) {
+      return kf_fail(GORIO_ERR_ALLOC, "edge_information: out of memory");
+    }
+    score = own.data();
+  }
+  const int rc = kf_edge_fitness_impl(kf, "edge_information", edges, count, DBL_MAX, score, nullptr);  // IMC:37: max_range at its default
+  if (rc) return rc;
+  for (int e = 0; e < count; ++e) gorio::edge_information_from_score(*p, score[e], inf_diag + 2 * (size_t)e);
+  return GORIO_OK;
+}
+
+int gorio_kf_edge_counters(const gorio_kf_t* kf, long long* calls, long long* edges_scored, long long* index_builds, long long* synchronisations) {
+  if (!kf) return kf_fail(GORIO_ERR_INVALID, "edge_counters: null handle");
+  if (calls) *calls = kf->edge_calls;
+  if (edges_scored) *edges_scored = kf->edge_edges;
+  if (index_builds) *index_builds = kf->edge_index_builds;
+  if (synchronisations) *synchronisations = kf->edge_syncs;
   return GORIO_OK;
 }
 

@@ -155,4 +155,9 @@ int gorio_sc_add_keyframes(gorio_sc_t* sc, gorio_kf_t* kf, const int* ids, int c
 #ifdef __cplusplus
 }
 #endif
+
+/* Pose-graph edges between resident keyframes (InformationMatrixCalculator of the back end): fitness score and information matrix of
+ * any number of edges in one pass.  Part of this ABI, kept in a file of its own. */
+#include "gorio_kf_edges.h"
+
 #endif /* GORIO_KEYFRAMES_H */
