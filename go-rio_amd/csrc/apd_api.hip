@@ -298,6 +298,7 @@ struct gorio_apd {
   ncclComm_t comm = nullptr;
   int comm_world = 1, comm_rank = 0;
   bool shard_only = false;  // gorio_apd_debug_set_shard: the source partition of a rank without the collectives (test hook)
+  bool fuse_supported = false;  // gorio_apd_create: the device is one the fence-free hand-over of the fused step was validated on
   bool fuse_step = true, plan_search = true;  // gorio_apd_debug_set_schedule
   DevBuf<double> d_red;     // [32] all-reduce buffer: 28 sums of a linearisation, [28] trial error, [29] scratch
   long long allreduce_count = 0;  // ncclAllReduce calls enqueued through this handle's communicator (gorio_apd_comm_info)
@@ -333,6 +334,9 @@ struct gorio_apd {
   struct EvPair { hipEvent_t start, stop; int stage; int prev; };  // prev >= 0: the span starts at ev_pool[prev].stop (StageChain)
   std::vector<EvPair> ev_pool;
   size_t ev_used = 0;
+  // gorio_apd_set_method: correspondences, Mahalanobis matrices, pair counts and passes of another method (or another neighbourhood) mean
+  // nothing to the new one
+  void method_switched() { corr_valid = false; omega_valid = false; gomp_pairs = -1; icp_pairs = -1; mp_pass_valid = false; }
   // gorio_apd_destroy makes the device current and drains the stream first; the buffers then free themselves as members
   ~gorio_apd() {
     for (auto& e : ev_pool) { hipEventDestroy(e.start); hipEventDestroy(e.stop); }
@@ -974,11 +978,6 @@ VoxPair make_vox_pair(const gorio_apd* h, int write_omega) {
   return v;
 }
 
-int ensure_vox_batch(gorio_apd* lead, int count) {
-  HIP_TRY(lead, lead->d_vox.reserve(count));
-  return GORIO_OK;
-}
-
 // ---- fast_gicp::NDTCuda plumbing (apd_ndt_cuda.hip)
 
 bool is_ndtc(const gorio_apd* h) { return h->method == GORIO_METHOD_NDT_CUDA; }
@@ -1116,11 +1115,6 @@ NdtcPair make_ndtc_pair(const gorio_apd* h) {
   p.n_off = h->ndtc_slot_off;
   p.d2d = d2d ? 1 : 0;
   return p;
-}
-
-void ndtc_desc(const gorio_apd* h, PairDesc& d) {
-  d.partials = h->ndtc_partials;
-  d.nblk = (int)(((size_t)h->ndtc_items * h->ndtc_slot_off + 255) / 256);
 }
 
 void launch_ndtc_linearize(bool d2d, dim3 grid, hipStream_t stream, const PairDesc* d_desc, const NdtcPair* d_pairs) {
@@ -1274,34 +1268,6 @@ bool vgc_same_settings(const gorio_apd* a, const gorio_apd* b) {
          a->vgc_maxd == b->vgc_maxd;
 }
 
-int voxf_ready(gorio_apd* h) { return is_vgc(h) ? vgc_ready(h) : ndtc_ready(h); }
-int ensure_voxf_pair(gorio_apd* h) { return is_vgc(h) ? ensure_vgc_pair(h) : ensure_ndtc_pair(h); }
-
-// the linearisation launch and the shell launch of the slot table HELD (ndtc_slot_d2d of the lead in a batch: the settings agree)
-void launch_voxf_linearize(const gorio_apd* h, dim3 grid, const PairDesc* d_desc, const NdtcPair* d_pairs) {
-  if (h->ndtc_slot_d2d == 2) vgc_linearize_kernel<<<grid, 256, 0, h->stream>>>(d_desc, d_pairs);
-  else launch_ndtc_linearize(h->ndtc_slot_d2d != 0, grid, h->stream, d_desc, d_pairs);
-}
-void launch_voxf_solve(const gorio_apd* h, dim3 grid, const PairDesc* d_desc, const NdtcPair* d_pairs, const ApdConsts& cst, int mode) {
-  if (is_vgc(h)) lm_solve_vgc_kernel<<<grid, 1024, 0, h->stream>>>(d_desc, d_pairs, cst, mode);
-  else lm_solve_ndtc_kernel<<<grid, 1024, 0, h->stream>>>(d_desc, d_pairs, cst, mode);
-}
-
-// the compile-time variants behind one call (kMethodApd stays the instantiation every APD-GICP caller runs)
-void launch_linearize(int method, dim3 grid, hipStream_t stream, const PairDesc* d_desc, const ApdConsts& cst, int fuse) {
-  if (method == GORIO_METHOD_GICP) linearize_kernel<kMethodGicp><<<grid, 256, 0, stream>>>(d_desc, cst, fuse);
-  else linearize_kernel<kMethodApd><<<grid, 256, 0, stream>>>(d_desc, cst, fuse);
-}
-void launch_lm_solve(int method, dim3 grid, hipStream_t stream, const PairDesc* d_desc, const VoxPair* d_vox, const ApdConsts& cst, int mode) {
-  if (method == GORIO_METHOD_VGICP) lm_solve_vgicp_kernel<<<grid, 1024, 0, stream>>>(d_desc, d_vox, cst, mode);
-  else if (method == GORIO_METHOD_GICP) lm_solve_kernel<kMethodGicp><<<grid, 1024, 0, stream>>>(d_desc, cst, mode);
-  else lm_solve_kernel<kMethodApd><<<grid, 1024, 0, stream>>>(d_desc, cst, mode);
-}
-void launch_shard_trial_error(int method, hipStream_t stream, const PairDesc* d_desc, double* ered, const ApdConsts& cst, int mode) {
-  if (method == GORIO_METHOD_GICP) shard_trial_error_kernel<kMethodGicp><<<1, 1024, 0, stream>>>(d_desc, ered, cst, mode);
-  else shard_trial_error_kernel<kMethodApd><<<1, 1024, 0, stream>>>(d_desc, ered, cst, mode);
-}
-
 int check_ready(gorio_apd* h) {
   if (!h->src->present) return fail(h, GORIO_ERR_STATE, "no input source set (setInputSource)");
   if (!h->tgt->present) return fail(h, GORIO_ERR_STATE, "no input target set (setInputTarget)");
@@ -1355,12 +1321,6 @@ void fill_desc(gorio_apd* h, PairDesc& d, PairState* state, long total_src_waves
   }
 }
 
-// FastVGICP linearisations reduce one partial per 256 (point, offset) slots (vgicp_linearize_kernel), not per 256 points
-void vgicp_desc(const gorio_apd* h, PairDesc& d) {
-  d.partials = h->v_partials;
-  d.nblk = (int)(((size_t)h->src->n * h->v_n_off + 255) / 256);
-}
-
 void init_state(PairState& s, const double* T16) {
   std::memset(&s, 0, sizeof(s));
   for (int i = 0; i < 16; ++i) s.x0[i] = T16[i];
@@ -1397,254 +1357,13 @@ int ensure_batch(gorio_apd* lead, int count) {
   return GORIO_OK;
 }
 
-// Shared body of align / align_batch.
-int align_impl(gorio_apd** hs, int count, const float* guesses, float* T_out, double* H_out, int* converged, int* nr_iterations, int* n_linearize) {
-  if (!hs || count <= 0 || !guesses || !T_out) return GORIO_ERR_INVALID;
-  gorio_apd* lead = hs[0];
-  if (!lead) return GORIO_ERR_INVALID;
-  HIP_TRY(lead, hipSetDevice(lead->device));
-  for (int q = 0; q < count; ++q)
-    if (hs[q] && hs[q]->comm && count != 1) return fail(lead, GORIO_ERR_INVALID, "a handle with a communicator (sharded source) cannot be part of a batch");
-  for (int q = 0; q < count; ++q)
-    if (hs[q] && hs[q]->method == GORIO_METHOD_GICP_OMP) return fail(lead, GORIO_ERR_UNSUPPORTED, "align_batch: GICP_OMP handles batch through gorio_apd_gicp_omp_align_batch (the BFGS shell is not the Gauss-Newton / LM one)");
-  for (int q = 0; q < count; ++q)
-    if (hs[q] && hs[q]->method == GORIO_METHOD_ICP) return fail(lead, GORIO_ERR_UNSUPPORTED, "align_batch: ICP handles batch through gorio_apd_icp_align_batch");
-  for (int q = 0; q < count; ++q)
-    if (hs[q] && is_mp(hs[q])) return fail(lead, GORIO_ERR_UNSUPPORTED, "align_batch: FastGICPMultiPoints handles are batched by gorio_apd_gicp_mp_align_batch (their rounds run a batched radius search, not this call's pair searches)");
-  std::unordered_set<gorio_apd*> distinct;
-  for (int q = 0; q < count; ++q) {
-    gorio_apd* h = hs[q];
-    if (!h) return fail(lead, GORIO_ERR_INVALID, "null handle in batch");
-    if (h->device != lead->device) return fail(lead, GORIO_ERR_INVALID, "all handles of a batch must live on one device");
-    if (!distinct.insert(h).second) return fail(lead, GORIO_ERR_INVALID, "the same handle appears twice in a batch (its buffers would be raced on)");
-    {  // one launch set advances all pairs: everything but cl_weight_points (per handle) must agree with the first handle
-      gorio_apd_params a = h->params, b = lead->params;
-      a.cl_weight_points = b.cl_weight_points = 0;
-      if (std::memcmp(&a, &b, sizeof(a)) != 0) return fail(lead, GORIO_ERR_INVALID, "all handles of a batch must carry the same parameters (cl_weight_points excepted)");
-      if (h->method != lead->method) return fail(lead, GORIO_ERR_INVALID, "all handles of a batch must use the same registration method (gorio_apd_set_method)");
-      if (h->method == GORIO_METHOD_VGICP && (h->voxel_resolution != lead->voxel_resolution || h->voxel_search != lead->voxel_search || h->voxel_mode != lead->voxel_mode))
-        return fail(lead, GORIO_ERR_INVALID, "all FastVGICP handles of a batch must carry the same voxel_resolution / voxel_search / voxel_mode");
-      if (is_ndtc(h) && !ndtc_same_settings(h, lead))
-        return fail(lead, GORIO_ERR_INVALID, "all NDTCuda handles of a batch must carry the same resolution / neighbour offsets / distance mode");
-      if (is_vgc(h) && !vgc_same_settings(h, lead))
-        return fail(lead, GORIO_ERR_INVALID, "all FastVGICPCuda handles of a batch must carry the same resolution / neighbour offsets / neighbour method / kernel parameters");
-    }
-    int rc = is_voxf(h) ? voxf_ready(h) : check_ready(h);
-    if (rc) {
-      if (h != lead) lead->err = h->err;
-      return rc;
-    }
-    if (!is_voxf(h)) rc = ensure_points(h, h->src->n);  // NDTCuda and FastVGICPCuda hold no per-point search state
-    if (rc) return rc;
-  }
-  const bool ndtc = is_voxf(lead);  // the float voxel back end: NDTCuda or FastVGICPCuda
-  // APD:149-154: covariances of whichever cloud is stale (NDTCuda: none, and no search index; FastVGICPCuda: its own, ensure_vgc_pair)
-  std::vector<std::pair<gorio_apd*, DevCloud*>> todo;
-  if (!ndtc) {
-    std::unordered_set<DevCloud*> seen;  // a target shared by many handles of the batch is estimated once
-    for (int q = 0; q < count; ++q) {
-      gorio_apd* h = hs[q];
-      if (h->src->cov_count != h->src->n && seen.insert(h->src.get()).second) todo.emplace_back(h, h->src.get());
-      if (h->tgt->cov_count != h->tgt->n && seen.insert(h->tgt.get()).second) todo.emplace_back(h, h->tgt.get());
-    }
-  }
-  int rc = GORIO_OK;
-  if (lead->params.search == GORIO_SEARCH_PRUNED && !ndtc) {  // the search indices first, for ALL clouds of the batch in one call: the kd chunk size is chosen by the whole set (run_index_build)
-    std::vector<std::pair<gorio_apd*, DevCloud*>> all;
-    for (int q = 0; q < count; ++q) {
-      all.emplace_back(hs[q], hs[q]->src.get());
-      all.emplace_back(hs[q], hs[q]->tgt.get());
-    }
-    if (lead->method == GORIO_METHOD_VGICP) all = todo;  // no nearest-neighbour search in this mode: only the k-NN covariance stage of the stale clouds reads an index
-    rc = run_index_build(lead, all);
-    if (rc) return rc;
-  }
-  rc = run_covariances(lead, todo);
-  if (rc) return rc;
-  const int method = lead->method;
-  const bool vgicp = method == GORIO_METHOD_VGICP;
-  if (vgicp) {  // VG:120-123: the voxel map of every target (a shared target's once: the second sharer finds it valid)
-    for (int q = 0; q < count; ++q) {
-      rc = build_voxelmap(hs[q], *hs[q]->tgt, hs[q]->voxel_resolution, hs[q]->voxel_mode);
-      if (!rc) rc = ensure_voxel_pair(hs[q]);
-      if (rc) {
-        if (hs[q] != lead) lead->err = hs[q]->err;
-        return rc;
-      }
-    }
-    rc = ensure_vox_batch(lead, count);
-    if (rc) return rc;
-  }
-  if (ndtc) {  // create_voxelmaps (NI:76-79): a shared cloud's map once, the second sharer finds it valid
-    for (int q = 0; q < count; ++q) {
-      rc = ensure_voxf_pair(hs[q]);
-      if (rc) {
-        if (hs[q] != lead) lead->err = hs[q]->err;
-        return rc;
-      }
-    }
-    HIP_TRY(lead, lead->d_ndtc.reserve(count));
-  }
-
-  rc = ensure_batch(lead, count);
-  if (rc) return rc;
-  long total_src_waves = 0;
-  int max_n = 0, max_m = 0;
-  for (int q = 0; q < count; ++q) {
-    total_src_waves += (hs[q]->src->n + 63) / 64;
-    if (hs[q]->src->n > max_n) max_n = hs[q]->src->n;
-    if (hs[q]->tgt->n > max_m) max_m = hs[q]->tgt->n;
-  }
-  std::vector<PairDesc> descs(count);
-  std::vector<PairState> states(count);
-  int max_splits = 1;
-  for (int q = 0; q < count; ++q) {
-    double T[16];
-    for (int i = 0; i < 16; ++i) T[i] = (double)guesses[(size_t)q * 16 + i];  // LSQ:56
-    init_state(states[q], T);
-    fill_desc(hs[q], descs[q], hs[q]->d_state, total_src_waves);
-    if (vgicp) vgicp_desc(hs[q], descs[q]);
-    if (ndtc) ndtc_desc(hs[q], descs[q]);
-    // Gauss-Newton never reads the Mahalanobis matrices back (only LM error trials and the parity hooks do): do not store them
-    descs[q].write_omega = lead->params.optimizer == GORIO_OPT_LEVENBERG_MARQUARDT ? 1 : 0;
-    hs[q]->omega_valid = descs[q].write_omega != 0;
-    if (descs[q].nn_splits > max_splits) max_splits = descs[q].nn_splits;
-    hs[q]->corr_valid = true;
-  }
-  if (int rc2 = upload_staged(lead, lead->pin_desc, lead->d_desc, descs.data(), sizeof(PairDesc) * count)) return rc2;
-  if (int rc2 = upload_staged(lead, lead->pin_states, lead->d_states_batch, states.data(), sizeof(PairState) * count)) return rc2;
-  int max_off = 1;
-  if (vgicp) {
-    std::vector<VoxPair> voxs(count);
-    for (int q = 0; q < count; ++q) voxs[q] = make_vox_pair(hs[q], descs[q].write_omega);
-    max_off = lead->v_n_off;
-    if (int rc2 = upload_staged(lead, lead->pin_vox, lead->d_vox, voxs.data(), sizeof(VoxPair) * count)) return rc2;
-  }
-  size_t ndtc_max_slots = 1;
-  if (ndtc) {
-    std::vector<NdtcPair> prs(count);
-    for (int q = 0; q < count; ++q) {
-      prs[q] = make_ndtc_pair(hs[q]);
-      ndtc_max_slots = std::max(ndtc_max_slots, (size_t)prs[q].n_items * prs[q].n_off);
-    }
-    if (int rc2 = upload_staged(lead, lead->pin_ndtc, lead->d_ndtc, prs.data(), sizeof(NdtcPair) * count)) return rc2;
-  }
-  scatter_states_kernel<<<count, 64, 0, lead->stream>>>(lead->d_desc, lead->d_states_batch);
-  if (!vgicp && !ndtc) arm_keys_kernel<<<dim3(std::min(64, (max_n + 255) / 256), count), 256, 0, lead->stream>>>(lead->d_desc);  // the search's key buffers
-
-  const ApdConsts cst = make_consts(lead->params);
-  const dim3 g_nn((max_n + 255) / 256, max_splits, count), g_lin((max_n + 255) / 256, 1, count), g_lm(count);
-  if (lead->comm) {  // sharded source: the same loop, cut at the two all-reduces (count == 1, checked above)
-    Rccl& R = rccl();
-    const int max_it = lead->params.max_iterations;
-    const bool lm = lead->params.optimizer == GORIO_OPT_LEVENBERG_MARQUARDT;
-    for (int it = 0; it < max_it; ++it) {
-      launch_nn(lead, lead->d_desc, g_nn, roundup(max_n, 512), 1, max_m);
-      launch_linearize(method, g_lin, lead->stream, lead->d_desc, cst, 0);
-      shard_reduce_partials_kernel<<<1, 64, 0, lead->stream>>>(lead->d_desc, lead->d_red);
-      NCCL_TRY(lead, R.AllReduce(lead->d_red, lead->d_red, 28, ncclDouble, ncclSum, lead->comm, lead->stream));  // THE collective: H, b, error
-      ++lead->allreduce_count;
-      shard_begin_kernel<<<1, 64, 0, lead->stream>>>(lead->d_desc, lead->d_red, cst, 0);
-      int trials = 0;
-      bool active = lm;
-      while (active) {
-        // two trial slots per round trip: a Levenberg-Marquardt step is almost always decided by the first or second trial; every rank
-        // reads the same flags, so every rank enqueues the same sequence of collectives
-        for (int t = 0; t < 2 && trials < lead->params.lm_max_iterations; ++t, ++trials) {
-          launch_shard_trial_error(method, lead->stream, lead->d_desc, lead->d_red + 28, cst, 0);
-          NCCL_TRY(lead, R.AllReduce(lead->d_red + 28, lead->d_red + 28, 1, ncclDouble, ncclSum, lead->comm, lead->stream));
-          ++lead->allreduce_count;
-          shard_trial_decide_kernel<<<1, 64, 0, lead->stream>>>(lead->d_desc, lead->d_red + 28, cst, 0);
-        }
-        HIP_TRY(lead, hipMemcpyAsync(&states[0], lead->d_state, sizeof(PairState), hipMemcpyDeviceToHost, lead->stream));
-        HIP_TRY(lead, hipStreamSynchronize(lead->stream));
-        active = states[0].trial_active != 0 && trials < lead->params.lm_max_iterations;
-      }
-      if (lm) shard_trial_decide_kernel<<<1, 64, 0, lead->stream>>>(lead->d_desc, lead->d_red + 28, cst, 1);  // end-of-iteration bookkeeping
-      HIP_TRY(lead, hipGetLastError());
-      HIP_TRY(lead, hipMemcpyAsync(&states[0], lead->d_state, sizeof(PairState), hipMemcpyDeviceToHost, lead->stream));
-      HIP_TRY(lead, hipStreamSynchronize(lead->stream));
-      if (states[0].done) break;
-    }
-    const PairState& s0 = states[0];
-    for (int i = 0; i < 12; ++i) T_out[i] = (float)s0.x0[i];
-    T_out[12] = 0.f; T_out[13] = 0.f; T_out[14] = 0.f; T_out[15] = 1.f;
-    if (H_out) std::memcpy(H_out, s0.Hfin, sizeof(double) * 36);
-    if (converged) converged[0] = s0.converged;
-    if (nr_iterations) nr_iterations[0] = s0.nr_iterations;
-    if (n_linearize) n_linearize[0] = s0.n_linearize;
-    if (s0.lm_failed) lead->err = "lm not converged!!";
-    resolve_stage_events(lead);
-    return GORIO_OK;
-  }
-  int launched = 0;
-  // Iterations between looks at the done flags (a look drains the stream): 4, 8, 16, 16, ... for the first batch of a handle; later
-  // batches first enqueue as many iterations as the previous batch needed -- on like data that look is the only one.  A finished pair's
-  // kernels return at once, so the schedule of the looks never changes a result.
-  int chunk_iters = lead->align_budget > 0 ? lead->align_budget : 4;
-  const bool fuse_gn = lead->params.optimizer != GORIO_OPT_LEVENBERG_MARQUARDT && lead->fuse_step && !vgicp && !ndtc;
-  const dim3 g_nlin((unsigned int)((ndtc_max_slots + 255) / 256), 1, count);
-  const dim3 g_vlin((unsigned int)(((size_t)max_n * max_off + 255) / 256), 1, count);
-  const int max_it = lead->params.max_iterations;
-  HIP_TRY(lead, lead->pin_looks.reserve(sizeof(PairState) * count, sizeof(PairState) * (count + count / 2)));
-  while (launched < max_it) {
-    const int todo_it = std::min(chunk_iters, max_it - launched);
-    StageChain chain(lead);
-    for (int it = 0; it < todo_it; ++it) {
-      if (vgicp) {  // no nearest-neighbour search: the lookups are part of the linearisation (VG:73-116)
-        vgicp_linearize_kernel<<<g_vlin, 256, 0, lead->stream>>>(lead->d_desc, lead->d_vox);
-        chain.mark(2);
-        launch_lm_solve(method, g_lm, lead->stream, lead->d_desc, lead->d_vox, cst, 0);
-        chain.mark(3);
-        continue;
-      }
-      if (ndtc) {  // update_correspondences + compute_error (NI:82-85) in one launch, then the shell
-        launch_voxf_linearize(lead, g_nlin, lead->d_desc, lead->d_ndtc);
-        chain.mark(2);
-        launch_voxf_solve(lead, g_lm, lead->d_desc, lead->d_ndtc, cst, 0);
-        chain.mark(3);
-        continue;
-      }
-      launch_nn(lead, lead->d_desc, g_nn, roundup(max_n, 512), count, max_m, launched + it);
-      chain.mark(1);
-      // Gauss-Newton needs no error trials: the optimiser step rides on the linearisation launch (its last workgroup per pair).
-      // Levenberg-Marquardt keeps its own launch: an error trial wants the 1024 threads of lm_solve_kernel.
-      launch_linearize(method, g_lin, lead->stream, lead->d_desc, cst, fuse_gn ? 1 : 0);
-      chain.mark(2);
-      if (!fuse_gn) {
-        launch_lm_solve(method, g_lm, lead->stream, lead->d_desc, nullptr, cst, 0);
-        chain.mark(3);
-      }
-    }
-    launched += todo_it;
-    chunk_iters = launched == todo_it && lead->align_budget > 0 ? 4 : std::min(16, chunk_iters * 2);  // after a budgeted first chunk: 4, 8, 16, ...
-    HIP_TRY(lead, hipGetLastError());
-    gather_states_kernel<<<count, 64, 0, lead->stream>>>(lead->d_desc, lead->d_states_batch);
-    HIP_TRY(lead, hipMemcpyAsync(lead->pin_looks, lead->d_states_batch, sizeof(PairState) * count, hipMemcpyDeviceToHost, lead->stream));
-    HIP_TRY(lead, hipStreamSynchronize(lead->stream));
-    std::memcpy(states.data(), lead->pin_looks, sizeof(PairState) * count);
-    bool all_done = true;
-    for (int q = 0; q < count; ++q) all_done = all_done && states[q].done;
-    if (all_done) break;
-  }
-  {
-    int need = 1;  // loop iterations the slowest pair used = its linearisations
-    for (int q = 0; q < count; ++q) need = std::max(need, states[q].n_linearize);
-    lead->align_budget = std::min(need, max_it);
-  }
-  for (int q = 0; q < count; ++q) {
-    const PairState& s = states[q];
-    for (int i = 0; i < 12; ++i) T_out[(size_t)q * 16 + i] = (float)s.x0[i];  // LSQ:78
-    T_out[(size_t)q * 16 + 12] = 0.f; T_out[(size_t)q * 16 + 13] = 0.f; T_out[(size_t)q * 16 + 14] = 0.f; T_out[(size_t)q * 16 + 15] = 1.f;
-    if (H_out) std::memcpy(H_out + (size_t)q * 36, s.Hfin, sizeof(double) * 36);
-    if (converged) converged[q] = s.converged;
-    if (nr_iterations) nr_iterations[q] = s.nr_iterations;
-    if (n_linearize) n_linearize[q] = s.n_linearize;
-    if (s.lm_failed) hs[q]->err = "lm not converged!!";  // LSQ:72 prints this to stderr
-  }
-  resolve_stage_events(lead);
-  return GORIO_OK;
+// A batch member's failure is reported on the handle that leads the batch
+int hand_over(gorio_apd* lead, gorio_apd* h, int rc) {
+  if (rc && h != lead) lead->err = h->err;
+  return rc;
 }
+
+#include "apd_lsq.hip"
 
 // Search bound of a fitness score: nothing farther than max(max_range, inlier_dist^2) is counted by either statistic (rounded up to a float).
 float fitness_bound(double max_range, double inlier_sq) {
@@ -1664,30 +1383,13 @@ int fitness_splits(long waves) {
   return splits;
 }
 
-// solver: the descriptor feeds linearize / compute_error (in FastVGICP mode with the slot table behind it), not a fitness search
-int single_desc(gorio_apd* h, bool solver = false) {
+// the descriptor of a fitness score's search
+int single_desc(gorio_apd* h) {
   int rc = ensure_batch(h, 1);
   if (rc) return rc;
   PairDesc d;
   fill_desc(h, d, h->d_state, (h->src->n + 63) / 64);
-  if (solver && h->method == GORIO_METHOD_VGICP) vgicp_desc(h, d);
-  if (solver && is_voxf(h)) ndtc_desc(h, d);
   HIP_TRY(h, hipMemcpyAsync(h->d_desc, &d, sizeof(PairDesc), hipMemcpyHostToDevice, h->stream));
-  if (solver && is_voxf(h)) {
-    HIP_TRY(h, h->d_ndtc.reserve(1));
-    const NdtcPair p = make_ndtc_pair(h);
-    HIP_TRY(h, hipMemcpyAsync(h->d_ndtc, &p, sizeof(NdtcPair), hipMemcpyHostToDevice, h->stream));
-    HIP_TRY(h, hipStreamSynchronize(h->stream));
-    return GORIO_OK;
-  }
-  if (solver && h->method == GORIO_METHOD_VGICP) {
-    rc = ensure_vox_batch(h, 1);
-    if (rc) return rc;
-    const VoxPair v = make_vox_pair(h, 1);
-    HIP_TRY(h, hipMemcpyAsync(h->d_vox, &v, sizeof(VoxPair), hipMemcpyHostToDevice, h->stream));
-    HIP_TRY(h, hipStreamSynchronize(h->stream));
-    return GORIO_OK;
-  }
   HIP_TRY(h, hipStreamSynchronize(h->stream));
   return GORIO_OK;
 }
@@ -1736,7 +1438,8 @@ int gorio_apd_create(gorio_apd_t** out, int device) {
   {  // the fence-free "last workgroup runs the optimiser step" hand-over relies on how gfx950 writes through and acknowledges sc1 stores across
      // its XCD L2s: it was validated there and is switched off on anything else (the step then takes its own launch)
     hipDeviceProp_t prop;
-    h->fuse_step = hipGetDeviceProperties(&prop, device) == hipSuccess && std::strncmp(prop.gcnArchName, "gfx950", 6) == 0;
+    h->fuse_supported = hipGetDeviceProperties(&prop, device) == hipSuccess && std::strncmp(prop.gcnArchName, "gfx950", 6) == 0;
+    h->fuse_step = h->fuse_supported;
   }
   if (!h->stream || h->d_state.reserve(1) != hipSuccess || h->d_red.reserve(32) != hipSuccess) {  // d_fit grows with its first fitness score
     delete h;
@@ -1780,47 +1483,31 @@ int gorio_apd_get_params(const gorio_apd_t* h, gorio_apd_params* p) {
 int gorio_apd_set_method(gorio_apd_t* h, int method, double voxel_resolution, int voxel_search, int voxel_mode) {
   if (!h) return GORIO_ERR_INVALID;
   if (method != GORIO_METHOD_APDGICP && method != GORIO_METHOD_GICP && method != GORIO_METHOD_VGICP && method != GORIO_METHOD_GICP_OMP && method != GORIO_METHOD_ICP && method != GORIO_METHOD_NDT_CUDA && method != GORIO_METHOD_VGICP_CUDA && method != GORIO_METHOD_GICP_MP) return fail(h, GORIO_ERR_UNSUPPORTED, "set_method: unknown registration method");
-  if (method == GORIO_METHOD_NDT_CUDA || method == GORIO_METHOD_VGICP_CUDA) {  // voxel_resolution = setResolution, voxel_search = setNeighborSearchMethod (DIRECT_RADIUS with the radius of gorio_apd_set_ndt_cuda_params); voxel_mode is ignored
+  if (method == GORIO_METHOD_NDT_CUDA || method == GORIO_METHOD_VGICP_CUDA) {  // voxel_resolution = setResolution, voxel_search = setNeighborSearchMethod (DIRECT_RADIUS with the radius of gorio_apd_set_ndt_cuda_params); voxel_mode is ignored: the handle keeps the one it has
     if (voxel_search != GORIO_VOXEL_DIRECT27 && voxel_search != GORIO_VOXEL_DIRECT7 && voxel_search != GORIO_VOXEL_DIRECT1 && voxel_search != GORIO_VOXEL_DIRECT_RADIUS) return fail(h, GORIO_ERR_UNSUPPORTED, "set_method: unknown neighbour search method");
     if (!(voxel_resolution > 0.0) || !std::isfinite(voxel_resolution)) return fail(h, GORIO_ERR_UNSUPPORTED, "set_method: voxel_resolution must be positive");
     if (h->comm || (h->shard_only && h->comm_world > 1)) return fail(h, GORIO_ERR_STATE, "set_method: NDTCuda and FastVGICPCuda have no sharded-source mode");
     if (voxel_search == GORIO_VOXEL_DIRECT_RADIUS)
       if (int rc = ndtc_check_radius(h, h->ndtc_radius)) return rc;
-    h->gomp_pairs = -1;
-    h->icp_pairs = -1;
-    h->method = method;
-    h->mp_pass_valid = false;  // the pass FastGICPMultiPoints held means nothing after a switch
-    h->voxel_resolution = voxel_resolution;
-    h->voxel_search = voxel_search;
-    h->corr_valid = false;
-    h->omega_valid = false;
-    return GORIO_OK;
-  }
-  if (method == GORIO_METHOD_GICP_OMP || method == GORIO_METHOD_ICP || method == GORIO_METHOD_GICP_MP) {  // the voxel arguments are ignored in these modes: the handle keeps the ones it has
+    voxel_mode = h->voxel_mode;
+  } else if (method == GORIO_METHOD_GICP_OMP || method == GORIO_METHOD_ICP || method == GORIO_METHOD_GICP_MP) {  // the voxel arguments are ignored in these modes: the handle keeps the ones it has
     if (h->comm) return fail(h, GORIO_ERR_STATE, "set_method: GICP_OMP, ICP and FastGICPMultiPoints have no sharded-source mode (the handle has a communicator)");
     if (method != GORIO_METHOD_GICP_OMP && h->shard_only && h->comm_world > 1) return fail(h, GORIO_ERR_STATE, "set_method: ICP and FastGICPMultiPoints have no sharded-source mode (gorio_apd_debug_set_shard is on)");
-    h->icp_pairs = -1;
-    h->method = method;
-    h->mp_pass_valid = false;  // the pass FastGICPMultiPoints held means nothing after a switch
-    h->corr_valid = false;
-    h->omega_valid = false;
-    h->gomp_pairs = -1;
-    return GORIO_OK;
+    voxel_resolution = h->voxel_resolution;
+    voxel_search = h->voxel_search;
+    voxel_mode = h->voxel_mode;
+  } else {
+    if (voxel_search == GORIO_VOXEL_DIRECT_RADIUS) return fail(h, GORIO_ERR_UNSUPPORTED, "set_method: DIRECT_RADIUS is not supported (the reference aborts there, VOX:13-15)");
+    if (voxel_search != GORIO_VOXEL_DIRECT27 && voxel_search != GORIO_VOXEL_DIRECT7 && voxel_search != GORIO_VOXEL_DIRECT1) return fail(h, GORIO_ERR_UNSUPPORTED, "set_method: unknown neighbour search method");
+    if (voxel_mode != GORIO_VOXEL_ADDITIVE && voxel_mode != GORIO_VOXEL_ADDITIVE_WEIGHTED && voxel_mode != GORIO_VOXEL_MULTIPLICATIVE) return fail(h, GORIO_ERR_UNSUPPORTED, "set_method: unknown voxel accumulation mode");
+    if (!(voxel_resolution > 0.0) || !std::isfinite(voxel_resolution)) return fail(h, GORIO_ERR_UNSUPPORTED, "set_method: voxel_resolution must be positive");
+    if (method == GORIO_METHOD_VGICP && h->comm) return fail(h, GORIO_ERR_STATE, "set_method: FastVGICP has no sharded-source mode (the handle has a communicator)");
   }
-  if (voxel_search == GORIO_VOXEL_DIRECT_RADIUS) return fail(h, GORIO_ERR_UNSUPPORTED, "set_method: DIRECT_RADIUS is not supported (the reference aborts there, VOX:13-15)");
-  if (voxel_search != GORIO_VOXEL_DIRECT27 && voxel_search != GORIO_VOXEL_DIRECT7 && voxel_search != GORIO_VOXEL_DIRECT1) return fail(h, GORIO_ERR_UNSUPPORTED, "set_method: unknown neighbour search method");
-  if (voxel_mode != GORIO_VOXEL_ADDITIVE && voxel_mode != GORIO_VOXEL_ADDITIVE_WEIGHTED && voxel_mode != GORIO_VOXEL_MULTIPLICATIVE) return fail(h, GORIO_ERR_UNSUPPORTED, "set_method: unknown voxel accumulation mode");
-  if (!(voxel_resolution > 0.0) || !std::isfinite(voxel_resolution)) return fail(h, GORIO_ERR_UNSUPPORTED, "set_method: voxel_resolution must be positive");
-  if (method == GORIO_METHOD_VGICP && h->comm) return fail(h, GORIO_ERR_STATE, "set_method: FastVGICP has no sharded-source mode (the handle has a communicator)");
-  h->gomp_pairs = -1;
-  h->icp_pairs = -1;
   h->method = method;
-  h->mp_pass_valid = false;
   h->voxel_resolution = voxel_resolution;
   h->voxel_search = voxel_search;
   h->voxel_mode = voxel_mode;
-  h->corr_valid = false;  // correspondences of another method (or another neighbourhood) mean nothing to this one
-  h->omega_valid = false;
+  h->method_switched();
   return GORIO_OK;
 }
 
@@ -2421,83 +2108,7 @@ int gorio_apd_linearize(gorio_apd_t* h, const double T[16], double* H, double* b
   if (h->method == GORIO_METHOD_GICP_OMP) return fail(h, GORIO_ERR_UNSUPPORTED, "linearize: GICP_OMP has no Gauss-Newton linearisation (gorio_apd_gicp_omp_update / _evaluate)");
   if (h->method == GORIO_METHOD_ICP) return fail(h, GORIO_ERR_UNSUPPORTED, "linearize: ICP has no Gauss-Newton linearisation (gorio_apd_icp_step)");
   if (is_mp(h)) return fail(h, GORIO_ERR_UNSUPPORTED, "linearize: FastGICPMultiPoints linearises at a float pose through gorio_apd_gicp_mp_pass");
-  HIP_TRY(h, hipSetDevice(h->device));
-  if (is_voxf(h)) {  // NI:82-85, VI:170-173: update_correspondences(trans), then compute_error(trans, H, b) over the fresh pairs
-    int rc = voxf_ready(h);
-    if (!rc) rc = ensure_voxf_pair(h);
-    if (!rc) rc = single_desc(h, true);
-    if (rc) return rc;
-    PairState s;
-    init_state(s, T);
-    HIP_TRY(h, hipMemcpyAsync(h->d_state, &s, sizeof(s), hipMemcpyHostToDevice, h->stream));
-    const ApdConsts cst = make_consts(h->params);
-    const unsigned int nblk = (unsigned int)(((size_t)h->ndtc_items * h->ndtc_slot_off + 255) / 256);
-    if (nblk) launch_voxf_linearize(h, dim3(nblk, 1, 1), h->d_desc, h->d_ndtc);  // no kept source point: no slot, zero sums
-    launch_voxf_solve(h, dim3(1), h->d_desc, h->d_ndtc, cst, 1);
-    HIP_TRY(h, hipGetLastError());
-    HIP_TRY(h, hipMemcpyAsync(&s, h->d_state, sizeof(s), hipMemcpyDeviceToHost, h->stream));
-    HIP_TRY(h, hipStreamSynchronize(h->stream));
-    h->corr_valid = true;
-    h->omega_valid = false;
-    if (H && b) {
-      std::memcpy(H, s.H, sizeof(double) * 36);
-      std::memcpy(b, s.b, sizeof(double) * 6);
-    }
-    if (error) *error = s.y0;
-    return GORIO_OK;
-  }
-  int rc = check_ready(h);
-  if (rc) return rc;
-  rc = ensure_points(h, h->src->n);
-  if (rc) return rc;
-  rc = gorio_apd_calculate_covariances(h);
-  if (rc) return rc;
-  if (h->params.search == GORIO_SEARCH_PRUNED) {
-    std::vector<std::pair<gorio_apd*, DevCloud*>> all = {{h, h->src.get()}, {h, h->tgt.get()}};
-    rc = run_index_build(h, all);
-    if (rc) return rc;
-  }
-  const bool vgicp = h->method == GORIO_METHOD_VGICP;
-  if (vgicp) {  // VG:120-123
-    rc = build_voxelmap(h, *h->tgt, h->voxel_resolution, h->voxel_mode);
-    if (!rc) rc = ensure_voxel_pair(h);
-    if (rc) return rc;
-  }
-  rc = single_desc(h, true);
-  if (rc) return rc;
-  PairState s;
-  init_state(s, T);
-  HIP_TRY(h, hipMemcpyAsync(h->d_state, &s, sizeof(s), hipMemcpyHostToDevice, h->stream));
-  HIP_TRY(h, hipMemsetAsync(h->best_key, 0xff, sizeof(unsigned long long) * h->src->n, h->stream));
-  const ApdConsts cst = make_consts(h->params);
-  PairDesc d;
-  fill_desc(h, d, h->d_state, (h->src->n + 63) / 64);
-  if (vgicp) vgicp_desc(h, d);
-  const int nbx = (h->src->n + 255) / 256;
-  if (vgicp) {
-    vgicp_linearize_kernel<<<dim3(d.nblk, 1, 1), 256, 0, h->stream>>>(h->d_desc, h->d_vox);
-  } else {
-    launch_nn(h, h->d_desc, dim3(nbx, d.nn_splits, 1), roundup(h->src->n, 512), 1, h->tgt->n);
-    launch_linearize(h->method, dim3(nbx, 1, 1), h->stream, h->d_desc, cst, 0);
-  }
-  if (h->comm) {  // every rank of the communicator makes this call; H, b and the error come back summed over all of them
-    shard_reduce_partials_kernel<<<1, 64, 0, h->stream>>>(h->d_desc, h->d_red);
-    NCCL_TRY(h, rccl().AllReduce(h->d_red, h->d_red, 28, ncclDouble, ncclSum, h->comm, h->stream));
-    shard_begin_kernel<<<1, 64, 0, h->stream>>>(h->d_desc, h->d_red, cst, 1);
-  } else {
-    launch_lm_solve(h->method, dim3(1), h->stream, h->d_desc, h->d_vox, cst, 1);
-  }
-  HIP_TRY(h, hipGetLastError());
-  HIP_TRY(h, hipMemcpyAsync(&s, h->d_state, sizeof(s), hipMemcpyDeviceToHost, h->stream));
-  HIP_TRY(h, hipStreamSynchronize(h->stream));
-  h->corr_valid = true;
-  h->omega_valid = true;
-  if (H && b) {
-    std::memcpy(H, s.H, sizeof(double) * 36);
-    std::memcpy(b, s.b, sizeof(double) * 6);
-  }
-  if (error) *error = s.y0;
-  return GORIO_OK;
+  return lsq_linearize(h, T, H, b, error);
 }
 
 int gorio_apd_compute_error(gorio_apd_t* h, const double T[16], double* error) {
@@ -2505,37 +2116,7 @@ int gorio_apd_compute_error(gorio_apd_t* h, const double T[16], double* error) {
   if (h->method == GORIO_METHOD_GICP_OMP) return fail(h, GORIO_ERR_UNSUPPORTED, "compute_error: GICP_OMP evaluates its functor through gorio_apd_gicp_omp_evaluate");
   if (h->method == GORIO_METHOD_ICP) return fail(h, GORIO_ERR_UNSUPPORTED, "compute_error: ICP has no weighted error (gorio_apd_icp_diag gives the mean squared distance)");
   if (is_mp(h)) return fail(h, GORIO_ERR_UNSUPPORTED, "compute_error: FastGICPMultiPoints has no error function (its solver takes full Gauss-Newton steps)");
-  HIP_TRY(h, hipSetDevice(h->device));
-  if (is_voxf(h) ? !h->corr_valid : (!h->corr_valid || !h->omega_valid)) return fail(h, GORIO_ERR_STATE, "compute_error needs the correspondences and Mahalanobis matrices of a previous linearize (or LM align)");
-  int rc = single_desc(h, true);
-  if (rc) return rc;
-  double xi[16];
-  for (int i = 0; i < 16; ++i) xi[i] = T[i];
-  HIP_TRY(h, hipMemcpyAsync(reinterpret_cast<char*>(h->d_state.get()) + offsetof(PairState, xi), xi, sizeof(xi), hipMemcpyHostToDevice, h->stream));
-  const ApdConsts cst = make_consts(h->params);
-  double yi = 0.0;
-  if (is_voxf(h)) {  // NC:162-177, VC:276-284 over the stale pairs, R_lin of the last linearise
-    launch_voxf_solve(h, dim3(1), h->d_desc, h->d_ndtc, cst, 2);
-    HIP_TRY(h, hipGetLastError());
-    HIP_TRY(h, hipMemcpyAsync(&yi, reinterpret_cast<char*>(h->d_state.get()) + offsetof(PairState, yi), sizeof(double), hipMemcpyDeviceToHost, h->stream));
-    HIP_TRY(h, hipStreamSynchronize(h->stream));
-    *error = yi;
-    return GORIO_OK;
-  }
-  if (h->comm) {
-    launch_shard_trial_error(h->method, h->stream, h->d_desc, h->d_red + 28, cst, 2);
-    NCCL_TRY(h, rccl().AllReduce(h->d_red + 28, h->d_red + 28, 1, ncclDouble, ncclSum, h->comm, h->stream));
-    HIP_TRY(h, hipMemcpyAsync(&yi, h->d_red + 28, sizeof(double), hipMemcpyDeviceToHost, h->stream));
-    HIP_TRY(h, hipStreamSynchronize(h->stream));
-    *error = yi;
-    return GORIO_OK;
-  }
-  launch_lm_solve(h->method, dim3(1), h->stream, h->d_desc, h->d_vox, cst, 2);
-  HIP_TRY(h, hipGetLastError());
-  HIP_TRY(h, hipMemcpyAsync(&yi, reinterpret_cast<char*>(h->d_state.get()) + offsetof(PairState, yi), sizeof(double), hipMemcpyDeviceToHost, h->stream));
-  HIP_TRY(h, hipStreamSynchronize(h->stream));
-  *error = yi;
-  return GORIO_OK;
+  return lsq_compute_error(h, T, error);
 }
 
 int gorio_apd_get_correspondences(gorio_apd_t* h, int* corr, float* sq_dist, int n) {
@@ -2824,7 +2405,7 @@ int gorio_apd_debug_set_shard(gorio_apd_t* h, int world_size, int rank) {
 
 int gorio_apd_debug_set_schedule(gorio_apd_t* h, int fuse_step, int plan_search) {
   if (!h) return GORIO_ERR_INVALID;
-  h->fuse_step = fuse_step != 0;
+  h->fuse_step = h->fuse_supported && fuse_step != 0;
   h->plan_search = plan_search != 0;
   return GORIO_OK;
 }

@@ -59,14 +59,8 @@ int batch_front_door(const std::string& name, gorio_apd** handles, int count, co
   return GORIO_OK;
 }
 
-// A batch member's failure is reported on the handle that leads the batch
-int hand_over(gorio_apd* lead, gorio_apd* h, int rc) {
-  if (rc && h != lead) lead->err = h->err;
-  return rc;
-}
-
 // The per-source-point buffers of every handle, and in pruned mode the search indices of ALL clouds of the batch in one call, as
-// align_impl builds them.
+// LsqBatch::prepare builds them.
 int batch_prepare_search(gorio_apd** hs, int count) {
   gorio_apd* lead = hs[0];
   for (int q = 0; q < count; ++q)
