@@ -51,7 +51,7 @@ APD_SYMBOLS = [
     "gorio_apd_get_target_covariances", "gorio_apd_calculate_covariances", "gorio_apd_get_knn_indices", "gorio_apd_align",
     "gorio_apd_align_batch", "gorio_apd_linearize", "gorio_apd_compute_error", "gorio_apd_get_correspondences",
     "gorio_apd_get_mahalanobis", "gorio_apd_transform_source", "gorio_apd_fitness_score", "gorio_apd_fitness_score_batch", "gorio_apd_set_profiling",
-    "gorio_apd_get_stage_times", "gorio_apd_set_target_shared", "gorio_comm_get_unique_id", "gorio_apd_comm_init", "gorio_apd_comm_destroy", "gorio_apd_comm_info", "gorio_apd_debug_set_shard", "gorio_apd_debug_set_schedule", "gorio_apd_debug_get_index", "gorio_apd_set_target_submap", "gorio_apd_get_target_points",
+    "gorio_apd_get_stage_times", "gorio_apd_set_target_shared", "gorio_comm_get_unique_id", "gorio_apd_comm_init", "gorio_apd_comm_destroy", "gorio_apd_comm_info", "gorio_apd_debug_set_shard", "gorio_apd_debug_set_schedule", "gorio_apd_debug_get_index", "gorio_apd_debug_knn_redo_groups", "gorio_apd_set_target_submap", "gorio_apd_get_target_points",
     "gorio_apd_set_method", "gorio_apd_get_method", "gorio_apd_get_voxelmap", "gorio_apd_get_voxel_correspondences",
     "gorio_apd_set_gicp_omp_params", "gorio_apd_get_gicp_omp_params", "gorio_apd_gicp_omp_update", "gorio_apd_gicp_omp_evaluate", "gorio_apd_gicp_omp_diag",
     "gorio_apd_gicp_omp_align_batch", "gorio_apd_gicp_omp_batch_diag",
@@ -540,6 +540,11 @@ class ApdGicp:
 
     def calculateCovariances(self):  # noqa: N802
         _check(self._h, self._lib.gorio_apd_calculate_covariances(self._h))
+
+    def debugKnnRedoGroups(self):  # noqa: N802 -- test hook: 64-point groups the redo pass of the last k-NN covariance estimation did
+        groups = C.c_int(0)
+        _check(self._h, self._lib.gorio_apd_debug_knn_redo_groups(self._h, C.byref(groups)))
+        return groups.value
 
     def debugGetIndex(self, which):  # noqa: N802 -- test hook: the search index of the source (0) / target (1) as the pruned searches see it
         sizes = (C.c_int * 6)()

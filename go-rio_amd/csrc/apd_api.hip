@@ -280,6 +280,7 @@ struct gorio_apd {
   DevBuf<PairState> d_states_batch;
   int desc_cap = 0;
   DevBuf<KnnJob> d_jobs;
+  DevBuf<unsigned int> d_redo_list;  // run_covariances: [0] count, then (job, group) of the 64-position groups knn_collect_kernel gave up on
   DevBuf<void> d_copy_jobs;  // gorio_apd_set_clouds_device_batch
   DevBuf<IndexJob> d_ijobs;
   DevBuf<double> d_fit;      // block partials of a fitness score
@@ -793,6 +794,11 @@ int run_covariances(gorio_apd* lead, std::vector<std::pair<gorio_apd*, DevCloud*
   }
   HIP_TRY(lead, lead->d_jobs.reserve(njobs));
   if (int rc = upload_staged(lead, lead->pin_jobs, lead->d_jobs, jobs.data(), sizeof(KnnJob) * njobs)) return rc;
+  if (select) {  // the call's redo list: room for every 64-position group that has a query
+    size_t groups = 0;
+    for (auto& t : todo) groups += ((size_t)t.second->n + 63) / 64;
+    HIP_TRY(lead, lead->d_redo_list.reserve(2 + 2 * groups, 2 + 2 * (groups + groups / 8)));
+  }
   {
     StageTimer t(lead, 0);
     dim3 g1((max_n + 255) / 256, max_splits, njobs), g2((max_n + 255) / 256, 1, njobs);
@@ -800,9 +806,10 @@ int run_covariances(gorio_apd* lead, std::vector<std::pair<gorio_apd*, DevCloud*
     if (K == 20) {
       if (pruned) {
         const dim3 gs(gp.x * (256 / qpw), 1, njobs);
+        HIP_TRY(lead, hipMemsetAsync(lead->d_redo_list, 0, sizeof(unsigned int), lead->stream));
         knn_kth_kernel<20><<<gs, kKnnBlock, 0, lead->stream>>>(lead->d_jobs);
-        knn_collect_kernel<20><<<gs, kKnnBlock, 0, lead->stream>>>(lead->d_jobs);
-        knn_pruned_kernel<20><<<gp, 256, 0, lead->stream>>>(lead->d_jobs);  // only the waves knn_collect_kernel flagged (massive ties) do anything
+        knn_collect_kernel<20><<<gs, kKnnBlock, 0, lead->stream>>>(lead->d_jobs, lead->d_redo_list);
+        knn_redo_kernel<20><<<kKnnRedoBlocks, 256, 0, lead->stream>>>(lead->d_jobs, lead->d_redo_list);  // the groups knn_collect_kernel listed (massive ties)
       } else {
         knn_partial_kernel<20><<<g1, 256, 0, lead->stream>>>(lead->d_jobs);
         cov_finalize_kernel<20><<<g2, 256, 0, lead->stream>>>(lead->d_jobs);
@@ -2407,6 +2414,17 @@ int gorio_apd_debug_set_schedule(gorio_apd_t* h, int fuse_step, int plan_search)
   if (!h) return GORIO_ERR_INVALID;
   h->fuse_step = h->fuse_supported && fuse_step != 0;
   h->plan_search = plan_search != 0;
+  return GORIO_OK;
+}
+
+int gorio_apd_debug_knn_redo_groups(gorio_apd_t* h, int* groups) {
+  if (!h || !groups) return GORIO_ERR_INVALID;
+  if (!h->d_redo_list) return fail(h, GORIO_ERR_STATE, "debug_knn_redo_groups: this handle has led no k-NN covariance estimation by selection (pruned search, k <= 20)");
+  HIP_TRY(h, hipSetDevice(h->device));
+  HIP_TRY(h, hipStreamSynchronize(h->stream));
+  unsigned int count = 0;
+  HIP_TRY(h, hipMemcpy(&count, h->d_redo_list, sizeof(count), hipMemcpyDeviceToHost));
+  *groups = (int)count;
   return GORIO_OK;
 }
 

@@ -189,8 +189,8 @@ struct KnnJob {
   float* part_d;  // [splits][K][n]
   int* part_i;
   int* knn_out;   // [n][k] or null (parity hook: only kept when gorio_apd_params.keep_knn_indices is set)
-  int* redo;      // [ceil(n_spad / 64)] per query wave: 1 = knn_collect_kernel gave up (more ties than its buffer holds), the
-                  // insertion kernel knn_pruned_kernel redoes that wave; null = knn_pruned_kernel does every wave
+  int* redo;      // [ceil(n_spad / 64)] per 64-position group that has a query (the others are never written or read): 1 = knn_collect_kernel
+                  // gave up (more ties than its buffer holds) and listed the group for knn_redo_kernel; null outside the selection path
   float* kth;     // [n_spad] k-th smallest distance of every query by SORTED position (knn_kth_kernel -> knn_collect_kernel)
   int k;
   int regularization;

@@ -18,6 +18,8 @@
 // beat or tie the final answer; ties are broken on the ORIGINAL index, so the result equals the exhaustive search bit for bit.
 #include <hip/hip_runtime.h>
 
+#include "knn_sort_network.h"
+
 namespace gorio {
 
 __device__ __forceinline__ unsigned int f2ord(float f) {  // order-preserving float -> uint
@@ -699,6 +701,7 @@ __device__ unsigned long long g_search_stats[1024][24];
 #define STAT_MAX(k, v) do { if ((threadIdx.x & 63) == 0) atomicMax(&STAT_ROW()[k], (unsigned long long)(v)); } while (0)
 #define STAT_DECL(name) int name = 0
 #define STAT_INC(name) ++name
+#define STAT_INC_IF(name, cond) do { if (cond) ++name; } while (0)
 // wave-local counters and phase clocks of nn_search_pruned_kernel: accumulated in registers, ONE set of atomics per wave at the end
 #define STAT_CLOCK_DECL() unsigned long long st_acc_[8] = {0, 0, 0, 0, 0, 0, 0, 0}; unsigned int st_cnt_[8] = {0, 0, 0, 0, 0, 0, 0, 0}; unsigned long long st_t_ = __builtin_amdgcn_s_memtime()
 #define STAT_PHASE(k) do { const unsigned long long now_ = __builtin_amdgcn_s_memtime(); st_acc_[k] += now_ - st_t_; st_t_ = now_; } while (0)
@@ -713,6 +716,7 @@ __device__ unsigned long long g_search_stats[1024][24];
 #define STAT_MAX(k, v) do { } while (0)
 #define STAT_DECL(name) do { } while (0)
 #define STAT_INC(name) do { } while (0)
+#define STAT_INC_IF(name, cond) do { } while (0)
 #endif
 
 // ----------------------------------------------------------------------------------------------- 1-NN correspondences, pruned
@@ -1276,17 +1280,14 @@ __device__ __forceinline__ void topk_insert_key(unsigned long long (&L)[K], unsi
   }
 }
 
-// self k-NN, pruned, fused with the covariance estimation of APD:366-407 (covariance_from_list).
-// grid: (ceil(n_spad / 256), 1, clouds), block 256.
+// The body of one wave of knn_pruned_kernel: the 64 sorted positions from wave_base (a multiple of 64, below n) on; positions past n - 1 repeat the last
+// query and store nothing.  s_d is a distance column per thread of the 256-thread block; the waves of a block never cooperate.
 template <int K>
-__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(5, 5))) void knn_pruned_kernel(const KnnJob* __restrict__ jobs) {
-  const KnnJob& job = jobs[blockIdx.z];
+__device__ __forceinline__ void knn_pruned_wave(const KnnJob& job, int wave_base, float (&s_d)[32][256]) {
   const SearchIndex& si = job.cloud.idx;
   const int n = si.n;
-  const int p = blockIdx.x * 256 + threadIdx.x;
-  if (blockIdx.x * 256 >= n) return;
   const int lane = threadIdx.x & 63;
-  if (job.redo && job.redo[(blockIdx.x * 256 + threadIdx.x) >> 6] == 0) return;  // this wave was done by knn_select_kernel
+  const int p = wave_base + lane;
   const int pq = p < n ? p : n - 1;
   const float qx = si.sx[pq], qy = si.sy[pq], qz = si.sz[pq];
   const float qlo[3] = {wave_min(qx), wave_min(qy), wave_min(qz)};
@@ -1296,7 +1297,6 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(5, 5))) voi
   const scalar_fp tz = as_scalar(si.sz);
   const scalar_ip to = (scalar_ip)si.orig;
   const float4* __restrict__ tb4 = reinterpret_cast<const float4*>(si.tbox);
-  __shared__ float s_d[32][256];  // distances of the current tile, one column per lane
   STAT_ADD(0, 1);
   const __attribute__((address_space(1))) int* og = (const __attribute__((address_space(1))) int*)si.orig;
   unsigned long long L[K];  // ascending (distance, original index) keys
@@ -1304,7 +1304,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(5, 5))) voi
   for (int t = 0; t < K; ++t) L[t] = 0x7f8000007fffffffull;  // (+inf, int max)
   auto kth = [&]() -> float { return __uint_as_float((unsigned int)(L[K - 1] >> 32)); };
   const int ng = (si.n_tiles + 63) / 64;
-  const int own_tile = __builtin_amdgcn_readfirstlane((blockIdx.x * 256 + (threadIdx.x & ~63)) / 32);
+  const int own_tile = __builtin_amdgcn_readfirstlane(wave_base / 32);
   const int g0 = own_tile / 64;
   for (int v = 0; v < 2 * ng; ++v) {
     const int off = (v + 1) >> 1;
@@ -1319,7 +1319,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(5, 5))) voi
     // in the own group take the own tiles first (they fill the list with true neighbours), then the rest
     for (int phase = (g == g0 ? 0 : 1); phase < 2; ++phase) {
       const float wb = wave_max(kth());
-      unsigned long long mask = __ballot(box_box_bound(qlo, qhi, lo, hi) <= wb);
+      unsigned long long mask = __ballot(tl < si.n_tiles && box_box_bound(qlo, qhi, lo, hi) <= wb);  // wb = +inf (fewer points than K) admits every box
       STAT_ADD(1, __builtin_popcountll(mask));
       if (g == g0) {
         const int ol = own_tile - g * 64;
@@ -1377,6 +1377,31 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(5, 5))) voi
   }  // lists never leave the registers: no partial lists, no second kernel
 }
 
+// self k-NN, pruned, fused with the covariance estimation of APD:366-407 (covariance_from_list).
+// grid: (ceil(n_spad / 256), 1, clouds), block 256.
+template <int K>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(5, 5))) void knn_pruned_kernel(const KnnJob* __restrict__ jobs) {
+  const KnnJob& job = jobs[blockIdx.z];
+  if (blockIdx.x * 256 >= job.cloud.idx.n) return;
+  __shared__ float s_d[32][256];  // distances of the current tile, one column per lane
+  knn_pruned_wave<K>(job, blockIdx.x * 256 + (threadIdx.x & ~63), s_d);
+}
+
+// The redo pass of the selection kernels below: knn_pruned_kernel's body for exactly the 64-position groups knn_collect_kernel listed,
+// so the same lists and covariances bit for bit.  list[0] = number of entries (zeroed on the stream ahead of knn_collect_kernel),
+// entry e = (list[2 + 2 e] = job, list[3 + 2 e] = group).  Fixed grid (kKnnRedoBlocks, block 256), the waves stride over the list: with
+// nothing listed -- every cloud without massive ties -- each wave reads the count and returns.
+constexpr int kKnnRedoBlocks = 512;
+template <int K>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(5, 5))) void knn_redo_kernel(const KnnJob* __restrict__ jobs, const unsigned int* __restrict__ list) {
+  const unsigned int count = list[0];
+  __shared__ float s_d[32][256];
+  for (unsigned int e = blockIdx.x * 4u + (threadIdx.x >> 6); e < count; e += gridDim.x * 4u) {
+    const unsigned int q = __builtin_amdgcn_readfirstlane(list[2 + 2 * e]), group = __builtin_amdgcn_readfirstlane(list[3 + 2 * e]);
+    knn_pruned_wave<K>(jobs[q], (int)(group * 64u), s_d);
+  }
+}
+
 // ----------------------------------------------------------------------------------------------- self k-NN by SELECTION
 //
 // knn_pruned_kernel above keeps a sorted (distance, index) list per lane and pays a 20-slot 64-bit insertion (~105 VALU instructions)
@@ -1390,11 +1415,12 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(5, 5))) voi
 //                       costs 5 half-rate instructions per slot where this costs one.)
 //   knn_collect_kernel  walks the tiles again with the now exact bound d_k; every candidate with d <= d_k (at most K - 1 below d_k plus
 //                       the ties at d_k) is appended to a lane-private LDS column as a packed (distance, original index) key; the
-//                       <= CAP buffered keys are then sorted into the register list with the 64-bit insertion (dense: every lane has
-//                       ~K of them), which also resolves ties on the original index, and the covariance is formed from the list
-//                       (covariance_from_list) as before.
+//                       <= CAP buffered keys are then sorted in registers by a fixed comparator network (knn_sort_network.h: 126
+//                       compare-exchanges where K insertion rounds took 400), which also resolves ties on the original index, and
+//                       the covariance is formed from the list (covariance_from_list) as before.
 // A wave in which some lane meets more than CAP candidates at or below its d_k (only with many exactly equal distances: lattices,
-// duplicated points) flags itself in job.redo and is redone by knn_pruned_kernel, so the result is exact for every input.
+// duplicated points) puts its 64-position group on the call's redo list and knn_redo_kernel redoes it with knn_pruned_kernel's body,
+// so the result is exact for every input.
 // grid of both: (ceil(n_spad / qpw), 1, clouds), block kKnnBlock (one wave: the waves never cooperate, see nn_search_pruned_kernel).
 // qpw = KnnJob::qpw queries per wave (64, 32, 16 or 8; the other lanes idle).  A wave walks the UNION of the tiles its queries need, and
 // its life grows with that union; when the call has fewer 64-query waves than the chip has SIMDs (a lone pair of scans) smaller groups
@@ -1404,6 +1430,23 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(5, 5))) voi
 #define GORIO_KNN_BLOCK 64
 #endif
 constexpr int kKnnBlock = GORIO_KNN_BLOCK;
+
+// Insertion of c into the ascending distance list, slots TO - 1 down to FROM: the new slot t is the median of (old D[t-1], c, old D[t])
+// -- every slot from OLD values, so the operations are independent (no carry chain); descending t keeps D[t-1] old when slot t is
+// written, also from one call to the next one below it.  The instruction is written out so that it updates D[t] IN PLACE: left to
+// the register allocator, the branches between the tiers of knn_kth_kernel put the list into other registers on each path and copy
+// it back where they meet (20 to 40 v_mov per insertion, measured: the stage 0.2 ms slower than without tiers).
+template <int K, int FROM, int TO>
+__device__ __forceinline__ void kth_insert_slots(float (&D)[K], float c) {
+#pragma unroll
+  for (int t = TO - 1; t >= FROM; --t) {
+    if (t > 0) asm("v_med3_f32 %0, %1, %2, %0" : "+v"(D[t]) : "v"(D[t - 1]), "v"(c));
+    else D[0] = __builtin_amdgcn_fmed3f(D[0], c, -INFINITY);  // min(D[0], c) without the canonicalisation fminf would add
+  }
+}
+// where knn_kth_kernel's chain may stop on its way down (counted on the C4 clouds, profiles/r26/knn_stage.md: no lane takes 23 % of the
+// executed insertions below D[9] and 41 % below D[4])
+constexpr int kKthCutLo = 5, kKthCutHi = 10;
 
 template <int K>
 __global__ __launch_bounds__(kKnnBlock) void knn_kth_kernel(const KnnJob* __restrict__ jobs) {
@@ -1432,6 +1475,10 @@ __global__ __launch_bounds__(kKnnBlock) void knn_kth_kernel(const KnnJob* __rest
   float D[K];  // the K smallest distances met so far, ascending.  An idle lane holds -inf throughout: it needs no tile, accepts no candidate
 #pragma unroll
   for (int t = 0; t < K; ++t) D[t] = live ? INFINITY : -INFINITY;
+  STAT_DECL(st_ins);  // executed insertions, and those among them that no lane takes below D[4] / D[9] / D[14] (tools/knn_list_work.py)
+  STAT_DECL(st_above4);
+  STAT_DECL(st_above9);
+  STAT_DECL(st_above14);
   for (int v = 0; v < 2 * ng; ++v) {
     const int off = (v + 1) >> 1;
     const int g = (v & 1) ? g0 - off : g0 + off;
@@ -1465,21 +1512,33 @@ __global__ __launch_bounds__(kKnnBlock) void knn_kth_kernel(const KnnJob* __rest
           for (int u = 0; u < 8; ++u) {
             const float c = d[u];
             if (__ballot(c < D[K - 1]) == 0) continue;  // no lane's list changes: skip the insertion for the whole wave
-            // insertion from the back: the new slot t is the median of (old D[t-1], c, old D[t]) -- every slot from OLD values, so the
-            // K operations are independent (no carry chain); descending t keeps D[t-1] old when slot t is written
-#pragma unroll
-            for (int t = K - 1; t > 0; --t) D[t] = __builtin_amdgcn_fmed3f(D[t - 1], c, D[t]);
-            D[0] = __builtin_amdgcn_fmed3f(D[0], c, -INFINITY);  // min(D[0], c) without the canonicalisation fminf would add
+            STAT_INC(st_ins);
+            STAT_INC_IF(st_above4, __ballot(c < D[4]) == 0);
+            STAT_INC_IF(st_above9, __ballot(c < D[9]) == 0);
+            STAT_INC_IF(st_above14, __ballot(c < D[14]) == 0);
+            // insertion from the back, in tiers: with c >= D[h] on every lane the slots 0 .. h would come out of their med3 as they are
+            // (c >= D[t] >= D[t-1] gives D[t], equality included), so the chain, which runs downwards, stops above them.  Own and near
+            // tiles come first and settle the low slots early.  Each test reads a slot the chain has not reached yet: an old value.
+            kth_insert_slots<K, kKthCutHi, K>(D, c);
+            if (__ballot(c < D[kKthCutHi - 1]) != 0) {
+              kth_insert_slots<K, kKthCutLo, kKthCutHi>(D, c);
+              if (__ballot(c < D[kKthCutLo - 1]) != 0) kth_insert_slots<K, 0, kKthCutLo>(D, c);
+            }
           }
         }
       }
     }
   }
+  STAT_ADD(4, 1);
+  STAT_ADD(5, st_ins);
+  STAT_ADD(6, st_above4);
+  STAT_ADD(7, st_above9);
+  STAT_ADD(8, st_above14);
   if (live) job.kth[p] = D[K - 1];  // indexed by SORTED position (n_spad entries)
 }
 
 template <int K>
-__global__ __launch_bounds__(kKnnBlock) void knn_collect_kernel(const KnnJob* __restrict__ jobs) {
+__global__ __launch_bounds__(kKnnBlock) void knn_collect_kernel(const KnnJob* __restrict__ jobs, unsigned int* __restrict__ redo_list) {
   const GridPos gp = xcd_grid_pos();  // cloud -> XCD (apd_device.h)
   const KnnJob& job = jobs[gp.z];
   const SearchIndex& si = job.cloud.idx;
@@ -1514,7 +1573,7 @@ __global__ __launch_bounds__(kKnnBlock) void knn_collect_kernel(const KnnJob* __
         lo = tb4[2 * (size_t)tl];
         hi = tb4[2 * (size_t)tl + 1];
       }
-      unsigned long long mask = __ballot(box_box_bound(qlo, qhi, lo, hi) <= wb);
+      unsigned long long mask = __ballot(tl < si.n_tiles && box_box_bound(qlo, qhi, lo, hi) <= wb);  // wb = +inf (fewer points than K) admits every box
       while (mask) {
         const int tlane = __builtin_ctzll(mask);
         mask &= mask - 1;
@@ -1542,19 +1601,38 @@ __global__ __launch_bounds__(kKnnBlock) void knn_collect_kernel(const KnnJob* __
   }
   const bool redo = __ballot(cnt > CAP) != 0ull;
   if (redo) {
-    if (lane == 0) job.redo[base >> 6] = 1;  // cleared by knn_kth_kernel; knn_pruned_kernel redoes the 64 sorted positions of the flag
+    STAT_ADD(10, 1);
+    // job.redo (cleared by knn_kth_kernel for every group that has a wave) marks the group: with qpw < 64 several waves share one and
+    // the first to raise the mark lists it.  knn_redo_kernel redoes the 64 sorted positions of every listed group.
+    if (lane == 0 && atomicExch(&job.redo[base >> 6], 1) == 0) {
+      const unsigned int e = atomicAdd(&redo_list[0], 1u);
+      redo_list[2 + 2 * e] = gp.z;
+      redo_list[3 + 2 * e] = (unsigned int)(base >> 6);
+    }
     return;
   }
   // sort the buffered keys (ties fall to the lower original index, surplus ties beyond K drop off the end)
-  unsigned long long L[K];
+  // by the fixed comparator network of knn_sort_network.h: real keys are distinct (the low word is the original index) and below the
+  // padding (+inf, int max) the rows from cnt on count as, so the first K outputs are the list an insertion of the keys would leave
+  static_assert(CAP == kKnnSortWidth && K == kKnnSortKeep, "knn_sort_network.h sorts the CAP = 24 buffered keys of K = 20");
+#ifdef GORIO_STATS
+  {
+    int rounds = cnt;
 #pragma unroll
-  for (int t = 0; t < K; ++t) L[t] = 0x7f8000007fffffffull;  // (+inf, int max)
-  int rounds = cnt;
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) rounds = max(rounds, __shfl_xor(rounds, o, 64));
-  for (int r = 0; r < rounds; ++r) {
-    if (r < cnt) topk_insert_key<K>(L, s_buf[r][threadIdx.x]);
+    for (int o = 32; o > 0; o >>= 1) rounds = max(rounds, __shfl_xor(rounds, o, 64));
+    STAT_ADD(9, rounds);
+    STAT_ADD(12 + min(max(rounds, K), CAP) - K, 1);  // [12..16]: waves by the longest column, K .. CAP
   }
+#endif
+  unsigned long long L[CAP];
+#pragma unroll
+  for (int r = 0; r < CAP; ++r) L[r] = r < cnt ? s_buf[r][threadIdx.x] : 0x7f8000007fffffffull;
+  knn_sort_network(L, [](unsigned long long& lo, unsigned long long& hi) {
+    const bool swap = hi < lo;
+    const unsigned long long a = swap ? hi : lo, b = swap ? lo : hi;
+    lo = a;
+    hi = b;
+  });
   if (live && p < n) {
     float bd[K];
     int bi[K];

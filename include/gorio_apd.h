@@ -659,6 +659,10 @@ int gorio_apd_debug_set_schedule(gorio_apd_t* h, int fuse_step, int plan_search)
  *   tbox [n_tiles * 8], sbox [n_super * 8], bbox [n_blocks * 8]   lo.x lo.y lo.z 0 hi.x hi.y hi.z 0
  * GORIO_ERR_STATE when the handle holds no valid index for that cloud. */
 int gorio_apd_debug_get_index(gorio_apd_t* h, int which, int sizes[6], float* sxyz, int* orig, float* tbox, float* sbox, float* bbox);
+/* Test hook: how many 64-point groups the redo pass of the last k-NN covariance estimation this handle led did (pruned search, k <= 20:
+ * the groups in which some point has more than 24 neighbours at or below its k-th distance, i.e. massive ties; 0 on ordinary clouds).
+ * Waits for the handle's stream.  GORIO_ERR_STATE when the handle has led no such estimation. */
+int gorio_apd_debug_knn_redo_groups(gorio_apd_t* h, int* groups);
 
 /* seconds spent inside device kernels of the last align / align_batch, by stage (HIP events on the launch stream):
  * [0] k-NN + covariance estimation, [1] correspondence search, [2] linearize, [3] LM/GN solve + error trials, [4] search-index build
