@@ -43,6 +43,7 @@
 #include "apd_ground.hip"
 #include "../../include/gorio_sc.h"
 #include "apd_sc.hip"
+#include "apd_sc_pairs.hip"
 #include "../../include/gorio_ndt.h"
 #include "apd_ndt.hip"
 

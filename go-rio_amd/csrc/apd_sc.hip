@@ -10,7 +10,8 @@
 //                        sc_knn_merge_kernel   one wave per query: merges the chunks' top 3s, maps the positions through the
 //                                              query's CURRENT candidate list (SC:330-338)
 //   SC distance          sc_pair_kernel        one wave per (query, candidate): 20-shift sector-key alignment, then 3 shifts x 20
-//                                              columns of double cosines (SC:80-160)
+//                                              columns of double cosines (SC:80-160); its body is sc_pair_eval, which the kernels of
+//                                              apd_sc_pairs.hip (include/gorio_sc_pairs.h) call too
 //   counter, snapshots   host                  which snapshot each query sees follows from the inputs alone (SC:284-306)
 //   final decision       host                  strict minimum over <= 3 distances, threshold, yaw (SC:341-371)
 // Every sum runs in index order (Eigen's reduction order is not pinned by the reference), un-fused (-ffp-contract=off), so the
@@ -229,13 +230,96 @@ __global__ __launch_bounds__(64) void sc_knn_merge_kernel(const ScQuery* __restr
   }
 }
 
+// Per-wave LDS scratch of sc_pair_eval.
+struct ScPairScratch {
+  double vnorm[kScSectors];
+  double sim[3][kScSectors];
+  double sdist[3];
+  int eff[3][kScSectors];
+  int shifts[3];
+  int pad;
+};
+
+// distanceBtnScanContext(q, c) (SC:127-160) by one wave; every kernel that needs the distance calls this one function, which is what
+// makes the batched forms (apd_sc_pairs.hip) bit-identical to gorio_sc_distance.  vq / vc: sector keys, nq / nc: column norms, dq / dc:
+// descriptors, ring-major as in the database; global memory or LDS.  EVERY thread of the workgroup must call it
+// (it synchronises the workgroup between its stages), waves without a pair with live = false.  Lane 0 of a live wave returns the result.
+__device__ __forceinline__ void sc_pair_eval(bool live, int lane, ScPairScratch& S, const double* vq, const double* vc, const double* nq, const double* nc,
+                                             const double* dq0, const double* dc0, double& dist, int& shift) {
+  // fastAlignUsingVkey (SC:104-122): ||vkey_q - circshift(vkey_c, s)||, circshift moving column j to (j + s) mod 20 (SC:42-62)
+  if (live && lane < kScSectors) {
+    double sq = 0.0;
+    for (int j = 0; j < kScSectors; ++j) {
+      const double diff = vq[j] - vc[(j - lane + kScSectors) % kScSectors];
+      sq += diff * diff;
+    }
+    S.vnorm[lane] = sqrt(sq);
+  }
+  __syncthreads();
+  if (live && lane == 0) {
+    int a = 0;
+    double m = 10000000.0;
+    for (int s = 0; s < kScSectors; ++s)
+      if (S.vnorm[s] < m) {
+        a = s;
+        m = S.vnorm[s];
+      }
+    // SEARCH_RADIUS = round(0.5 * 0.1 * 20) = 1: {a, a + 1, a - 1} mod 20, sorted ascending (SC:134-141)
+    int s0 = a, s1 = (a + 1) % kScSectors, s2 = (a - 1 + kScSectors) % kScSectors, tmp;
+    if (s1 < s0) { tmp = s0; s0 = s1; s1 = tmp; }
+    if (s2 < s1) { tmp = s1; s1 = s2; s2 = tmp; }
+    if (s1 < s0) { tmp = s0; s0 = s1; s1 = tmp; }
+    S.shifts[0] = s0;
+    S.shifts[1] = s1;
+    S.shifts[2] = s2;
+  }
+  __syncthreads();
+  // distDirectSC (SC:80-101) column terms: lane = 20 k + j, column j of the query against column j of the shifted candidate
+  if (live && lane < 3 * kScSectors) {
+    const int k = lane / kScSectors, j = lane % kScSectors;
+    const int cj = (j - S.shifts[k] + kScSectors) % kScSectors;
+    const double n1 = nq[j], n2 = nc[cj];
+    int ok = 0;
+    double sv = 0.0;
+    if (!((n1 == 0) | (n2 == 0))) {
+      const double* dq = dq0 + j;
+      const double* dc = dc0 + cj;
+      double dot = 0.0;
+      for (int r = 0; r < kScRings; ++r) dot += dq[r * kScSectors] * dc[r * kScSectors];
+      sv = dot / (n1 * n2);
+      ok = 1;
+    }
+    S.sim[k][j] = sv;
+    S.eff[k][j] = ok;
+  }
+  __syncthreads();
+  if (live && lane < 3) {
+    double sum = 0.0;
+    int n_eff = 0;
+    for (int j = 0; j < kScSectors; ++j)
+      if (S.eff[lane][j]) {
+        sum = sum + S.sim[lane][j];
+        n_eff = n_eff + 1;
+      }
+    S.sdist[lane] = 1.0 - sum / (double)n_eff;  // no effective column: 0 / 0 = NaN
+  }
+  __syncthreads();
+  if (live && lane == 0) {
+    int arg = 0;
+    double m = 10000000.0;
+    for (int k = 0; k < 3; ++k)
+      if (S.sdist[k] < m) {  // strict, a NaN never wins (SC:144-157)
+        arg = S.shifts[k];
+        m = S.sdist[k];
+      }
+    dist = m;
+    shift = arg;
+  }
+}
+
 // distanceBtnScanContext(desc[qdb], desc[kf]) (SC:127-160) for pair k of out[i], pair index = 3 i + k; one wave per pair.
 __global__ __launch_bounds__(kScThreads) void sc_pair_kernel(ScOut* __restrict__ out, int n_pairs, ScDb db) {
-  __shared__ double vnorm[kScThreads / 64][kScSectors];
-  __shared__ double sim[kScThreads / 64][3][kScSectors];
-  __shared__ int eff[kScThreads / 64][3][kScSectors];
-  __shared__ double sdist[kScThreads / 64][3];
-  __shared__ int shifts[kScThreads / 64][3];
+  __shared__ ScPairScratch scratch[kScThreads / 64];
   const int t = threadIdx.x, lane = t & 63, w = t >> 6;
   const int pair = blockIdx.x * (kScThreads / 64) + w;
   const bool active = pair < n_pairs;
@@ -245,74 +329,12 @@ __global__ __launch_bounds__(kScThreads) void sc_pair_kernel(ScOut* __restrict__
     c = out[pair / 3].kf[pair % 3];
   }
   const bool live = active && c >= 0;
-  // fastAlignUsingVkey (SC:104-122): ||vkey_q - circshift(vkey_c, s)||, circshift moving column j to (j + s) mod 20 (SC:42-62)
-  if (live && lane < kScSectors) {
-    const double* vq = db.sector + (size_t)q * kScSectors;
-    const double* vc = db.sector + (size_t)c * kScSectors;
-    double sq = 0.0;
-    for (int j = 0; j < kScSectors; ++j) {
-      const double diff = vq[j] - vc[(j - lane + kScSectors) % kScSectors];
-      sq += diff * diff;
-    }
-    vnorm[w][lane] = sqrt(sq);
-  }
-  __syncthreads();
+  const size_t qq = live ? q : 0, cc = live ? c : 0;
+  double m = 0.0;
+  int arg = 0;
+  sc_pair_eval(live, lane, scratch[w], db.sector + qq * kScSectors, db.sector + cc * kScSectors, db.colnorm + qq * kScSectors, db.colnorm + cc * kScSectors,
+                           db.desc + qq * kScBins, db.desc + cc * kScBins, m, arg);
   if (live && lane == 0) {
-    int a = 0;
-    double m = 10000000.0;
-    for (int s = 0; s < kScSectors; ++s)
-      if (vnorm[w][s] < m) {
-        a = s;
-        m = vnorm[w][s];
-      }
-    // SEARCH_RADIUS = round(0.5 * 0.1 * 20) = 1: {a, a + 1, a - 1} mod 20, sorted ascending (SC:134-141)
-    int s0 = a, s1 = (a + 1) % kScSectors, s2 = (a - 1 + kScSectors) % kScSectors, tmp;
-    if (s1 < s0) { tmp = s0; s0 = s1; s1 = tmp; }
-    if (s2 < s1) { tmp = s1; s1 = s2; s2 = tmp; }
-    if (s1 < s0) { tmp = s0; s0 = s1; s1 = tmp; }
-    shifts[w][0] = s0;
-    shifts[w][1] = s1;
-    shifts[w][2] = s2;
-  }
-  __syncthreads();
-  // distDirectSC (SC:80-101) column terms: lane = 20 k + j, column j of the query against column j of the shifted candidate
-  if (live && lane < 3 * kScSectors) {
-    const int k = lane / kScSectors, j = lane % kScSectors;
-    const int cj = (j - shifts[w][k] + kScSectors) % kScSectors;
-    const double n1 = db.colnorm[(size_t)q * kScSectors + j], n2 = db.colnorm[(size_t)c * kScSectors + cj];
-    int ok = 0;
-    double sv = 0.0;
-    if (!((n1 == 0) | (n2 == 0))) {
-      const double* dq = db.desc + (size_t)q * kScBins + j;
-      const double* dc = db.desc + (size_t)c * kScBins + cj;
-      double dot = 0.0;
-      for (int r = 0; r < kScRings; ++r) dot += dq[r * kScSectors] * dc[r * kScSectors];
-      sv = dot / (n1 * n2);
-      ok = 1;
-    }
-    sim[w][k][j] = sv;
-    eff[w][k][j] = ok;
-  }
-  __syncthreads();
-  if (live && lane < 3) {
-    double sum = 0.0;
-    int n_eff = 0;
-    for (int j = 0; j < kScSectors; ++j)
-      if (eff[w][lane][j]) {
-        sum = sum + sim[w][lane][j];
-        n_eff = n_eff + 1;
-      }
-    sdist[w][lane] = 1.0 - sum / (double)n_eff;  // no effective column: 0 / 0 = NaN
-  }
-  __syncthreads();
-  if (live && lane == 0) {
-    int arg = 0;
-    double m = 10000000.0;
-    for (int k = 0; k < 3; ++k)
-      if (sdist[w][k] < m) {  // strict, a NaN never wins (SC:144-157)
-        arg = shifts[w][k];
-        m = sdist[w][k];
-      }
     out[pair / 3].dist[pair % 3] = m;
     out[pair / 3].shift[pair % 3] = arg;
   }
@@ -339,6 +361,9 @@ struct gorio_sc {
   gorio::DevBuf<gorio::ScHit> d_partial;
   gorio::DevBuf<gorio::ScOut> d_out;
   gorio::DevBuf<void> d_kfjobs;  // gorio_sc_add_keyframes (apd_keyframes.hip): the pack kernel's job table
+  // include/gorio_sc_pairs.h (apd_sc_pairs.hip): the upload, the device results, and the cumulative counters
+  gorio::DevBuf<void> d_px_in, d_px_out;
+  long long px_calls = 0, px_pairs = 0, px_launches = 0, px_syncs = 0;
 };
 
 namespace {

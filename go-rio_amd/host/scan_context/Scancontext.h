@@ -4,6 +4,7 @@
 // callers that read them.  makeScancontext(cloud) goes through a second, private database.  The helpers that take caller-given
 // matrices (make*Key, fastAlignUsingVkey, distDirectSC, distanceBtnScanContext) are O(800) and run here in the library's index
 // order.  Without nanoflann there is no InvKeyTree: the snapshot lives in the library, polarcontext_invkeys_to_search_ mirrors it.
+// distanceBtnScanContextBatch, distanceMatrix, bestMatches and detectLoopClosureIDExhaustive are extensions (include/gorio_sc_pairs.h).
 #pragma once
 #include <algorithm>
 #include <cmath>
@@ -177,6 +178,57 @@ class SCManager {
     return {loop_id, yaw};
   }
 
+  // ---- Exhaustive matching (include/gorio_sc_pairs.h).  An EXTENSION: the reference has none of these members.  Each keeps the
+  // reference's distance (distanceBtnScanContext of two stored keyframes, the first unshifted); the detect also keeps the early
+  // return, the recent-keyframe filter, the strict minimum in list order, the threshold and the yaw, and drops the tree, its counter
+  // and its snapshot (tree_making_period_conter and polarcontext_invkeys_to_search_ are left alone).
+  struct BestMatch {
+    int index;    // -1: no candidate, or none below 1e7
+    double dist;  // 1e7 then
+    int shift;
+  };
+  // distanceBtnScanContext(polarcontexts_[first], polarcontexts_[second]) for every listed pair, in one launch
+  std::vector<std::pair<double, int>> distanceBtnScanContextBatch(const std::vector<std::pair<int, int>>& pairs) {
+    std::vector<int> q, c;
+    for (auto& p : pairs) q.push_back(p.first), c.push_back(p.second);
+    std::vector<double> d(pairs.size());
+    std::vector<int> s(pairs.size());
+    check(gorio_sc_distance_pairs(h_, q.data(), c.data(), (int)pairs.size(), d.data(), s.data()), "distanceBtnScanContextBatch");
+    std::vector<std::pair<double, int>> out;
+    for (size_t k = 0; k < pairs.size(); ++k) out.emplace_back(d[k], s[k]);
+    return out;
+  }
+  // every (row, column) pair, row-major: dist / shift [rows.size() * cols.size()]
+  void distanceMatrix(const std::vector<int>& rows, const std::vector<int>& cols, std::vector<double>& dist, std::vector<int>& shift) {
+    dist.assign(rows.size() * cols.size(), 0.0);
+    shift.assign(rows.size() * cols.size(), 0);
+    check(gorio_sc_distance_matrix(h_, rows.data(), (int)rows.size(), cols.data(), (int)cols.size(), dist.data(), shift.data()), "distanceMatrix");
+  }
+  // the whole database against itself
+  void distanceMatrix(std::vector<double>& dist, std::vector<int>& shift) {
+    const size_t n = polarcontexts_.size();
+    dist.assign(n * n, 0.0);
+    shift.assign(n * n, 0);
+    check(gorio_sc_distance_matrix(h_, nullptr, (int)n, nullptr, (int)n, dist.data(), shift.data()), "distanceMatrix");
+  }
+  // per listed keyframe r the best of the keyframes 0 .. r - min_gap (ties to the lower index), the matrix never materialised
+  std::vector<BestMatch> bestMatches(const std::vector<int>& rows, int min_gap) { return best(rows.data(), (int)rows.size(), min_gap); }
+  std::vector<BestMatch> bestMatches(int min_gap) { return best(nullptr, (int)polarcontexts_.size(), min_gap); }
+  // detectLoopClosureID with every candidate scored instead of the tree's 3
+  std::pair<int, float> detectLoopClosureIDExhaustive(const std::vector<radar_graph_slam::KeyFrame::Ptr>& candidate_keyframes, const radar_graph_slam::KeyFrame::Ptr& new_keyframe,
+                                                      double* min_dist_out = nullptr) {
+    std::vector<int> cand;
+    for (auto& k : candidate_keyframes) cand.push_back((int)k->index);
+    const int query = (int)new_keyframe->index, n = (int)cand.size();
+    const int* list = cand.data();
+    int loop_id = -1;
+    float yaw = 0.0f;
+    double min_dist = 0.0;
+    check(gorio_sc_detect_exhaustive(h_, 1, &query, &list, &n, &loop_id, &yaw, &min_dist), "detectLoopClosureIDExhaustive");
+    if (min_dist_out) *min_dist_out = min_dist;
+    return {loop_id, yaw};
+  }
+
   const Eigen::MatrixXd& getConstRefRecentSCD(void) { return polarcontexts_.back(); }
 
  public:
@@ -210,6 +262,14 @@ class SCManager {
 
   static void check(int rc, const char* what) {
     if (rc < 0) throw std::runtime_error(std::string("SCManager::") + what + ": " + gorio_sc_last_error());
+  }
+  std::vector<BestMatch> best(const int* rows, int n_rows, int min_gap) {
+    std::vector<int> idx(n_rows), shift(n_rows);
+    std::vector<double> dist(n_rows);
+    check(gorio_sc_best_matches(h_, rows, n_rows, min_gap, idx.data(), dist.data(), shift.data()), "bestMatches");
+    std::vector<BestMatch> out(n_rows);
+    for (int i = 0; i < n_rows; ++i) out[i] = BestMatch{idx[i], dist[i], shift[i]};
+    return out;
   }
   static void open(gorio_sc_t*& h, const gorio_sc_params& p) { check(gorio_sc_create(&h, 0, &p), "SCManager"); }
   void reopen() {

@@ -8,7 +8,11 @@ from .apd import GorioError, load_library
 
 SC_SYMBOLS = ["gorio_sc_add_scans", "gorio_sc_create", "gorio_sc_default_params", "gorio_sc_destroy", "gorio_sc_detect", "gorio_sc_detect_batch",
               "gorio_sc_distance", "gorio_sc_get_descriptor", "gorio_sc_get_state", "gorio_sc_last_error"]
+# include/gorio_sc_pairs.h, the exhaustive section (an extension: listed pairs, matrices, best matches, detect without the tree)
+SC_PAIRS_SYMBOLS = ["gorio_sc_best_matches", "gorio_sc_detect_exhaustive", "gorio_sc_distance_matrix", "gorio_sc_distance_pairs", "gorio_sc_pairs_counters"]
 RINGS, SECTORS = 40, 20
+EXCLUDE_RECENT = 10  # GORIO_SC_EXCLUDE_RECENT
+TILE_ROWS, TILE_COLS, PAIRS_PER_GROUP = 8, 8, 4  # GORIO_SC_TILE_ROWS, GORIO_SC_TILE_COLS, GORIO_SC_PAIRS_PER_GROUP
 
 
 class ScParams(C.Structure):
@@ -142,3 +146,58 @@ class ScanContext:
         d = (ScDiag * k)()
         self._check(self.lib.gorio_sc_detect_batch(self.h, k, Q, P, N, lid, yaw, md, d))
         return [(lid[i], np.float32(yaw[i]), md[i], diag_dict(d[i])) for i in range(k)]
+
+    # ---- include/gorio_sc_pairs.h: every value is, bit for bit, what distance() gives for the pair
+    def _indices(self, a):
+        if a is None:
+            return None, self.state()["n_scans"]
+        a = np.ascontiguousarray(a, np.int32).reshape(-1)
+        return a, int(a.size)
+
+    def distance_pairs(self, q, c):
+        """d(q[k], c[k]) for listed pairs in one launch -> (dist [count] float64, shift [count] int32)."""
+        q = np.ascontiguousarray(q, np.int32).reshape(-1)
+        c = np.ascontiguousarray(c, np.int32).reshape(-1)
+        if q.size != c.size:
+            raise ValueError("distance_pairs: q and c differ in length")
+        dist, shift = np.zeros(q.size, np.float64), np.zeros(q.size, np.int32)
+        self._check(self.lib.gorio_sc_distance_pairs(self.h, _ptr(q), _ptr(c), int(q.size), _ptr(dist), _ptr(shift)))
+        return dist, shift
+
+    def distance_matrix(self, rows=None, cols=None, want_dist=True, want_shift=True):
+        """d(rows[i], cols[j]) for every pair -> (dist [n_rows, n_cols] float64, shift int32); None for rows / cols means every scan,
+        an output not wanted comes back as None."""
+        r, nr = self._indices(rows)
+        c, nc = self._indices(cols)
+        dist = np.zeros((nr, nc), np.float64) if want_dist else None
+        shift = np.zeros((nr, nc), np.int32) if want_shift else None
+        self._check(self.lib.gorio_sc_distance_matrix(self.h, None if r is None else _ptr(r), nr, None if c is None else _ptr(c), nc,
+                                                      None if dist is None else _ptr(dist), None if shift is None else _ptr(shift)))
+        return dist, shift
+
+    def best_matches(self, rows=None, min_gap=EXCLUDE_RECENT):
+        """Per row r the minimum of d(r, c) over 0 <= c <= r - min_gap, ties to the lower c -> (index [n] int32, dist [n] float64,
+        shift [n] int32); (-1, 1e7, 0) where there is no candidate or none scores below 1e7."""
+        r, nr = self._indices(rows)
+        idx, dist, shift = np.zeros(nr, np.int32), np.zeros(nr, np.float64), np.zeros(nr, np.int32)
+        self._check(self.lib.gorio_sc_best_matches(self.h, None if r is None else _ptr(r), nr, int(min_gap), _ptr(idx), _ptr(dist), _ptr(shift)))
+        return idx, dist, shift
+
+    def detect_exhaustive(self, query_indices, candidate_lists):
+        """detectLoopClosureID with the tree stage replaced by all candidates, for every query in one pass -> list of (loop_id, yaw_rad
+        (float32), min_dist).  Stateless: counter and snapshot are untouched."""
+        k = len(query_indices)
+        cands = [np.ascontiguousarray(c, np.int32).reshape(-1) for c in candidate_lists]
+        if len(cands) != k:
+            raise ValueError("detect_exhaustive: one candidate list per query")
+        Q = (C.c_int * k)(*[int(q) for q in query_indices])
+        P = (C.c_void_p * k)(*[c.__array_interface__["data"][0] if c.size else None for c in cands])
+        N = (C.c_int * k)(*[c.size for c in cands])
+        lid, yaw, md = (C.c_int * k)(), (C.c_float * k)(), (C.c_double * k)()
+        self._check(self.lib.gorio_sc_detect_exhaustive(self.h, k, Q, P, N, lid, yaw, md))
+        return [(lid[i], np.float32(yaw[i]), md[i]) for i in range(k)]
+
+    def pairs_counters(self):
+        v = [C.c_longlong() for _ in range(4)]
+        self._check(self.lib.gorio_sc_pairs_counters(self.h, *[C.byref(x) for x in v]))
+        return dict(zip(("calls", "pairs", "launches", "synchronisations"), [x.value for x in v]))

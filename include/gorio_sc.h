@@ -112,4 +112,8 @@ const char* gorio_sc_last_error(void);
 #ifdef __cplusplus
 }
 #endif
+
+/* the exhaustive section: listed pairs, matrices, best matches and the detect without the tree (an extension, not in the reference) */
+#include "gorio_sc_pairs.h"
+
 #endif /* GORIO_SC_H */
