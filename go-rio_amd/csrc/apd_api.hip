@@ -648,7 +648,9 @@ void resolve_stage_events(gorio_apd* h) {
 //   kd_refine_kernel                          gather in Morton order, median splits, sx / sy / sz / orig / s4, tile and super-tile boxes
 //   box_block_kernel                          block boxes
 // 3 launches for 16 384-point scans (9 while their sort went through global memory between its stages).
+thread_local int g_index_build_launches = 0;  // kernel launches of this thread's last run_index_build (the scan batch's diagnostics add them up)
 int run_index_build(gorio_apd* lead, std::vector<std::pair<gorio_apd*, DevCloud*>>& clouds) {
+  g_index_build_launches = 0;
   std::vector<std::pair<gorio_apd*, DevCloud*>> todo;
   bool small_call = true;  // every cloud named in the call (built now or not) is a scan-sized one: kd chunks of 2048 points (kd_refine_kernel)
   {
@@ -707,6 +709,14 @@ int run_index_build(gorio_apd* lead, std::vector<std::pair<gorio_apd*, DevCloud*
     box_block_kernel<<<dim3((max_spad / 32768 + 64) / 64, nj), 64, 0, lead->stream>>>(dj);
   }
   HIP_TRY(lead, hipGetLastError());
+  g_index_build_launches = (ns > 0 ? 1 : 0) + 2;
+  if (nj > ns) {
+    g_index_build_launches += (max_n <= kBboxFusedMax ? 1 : 3) + 1;
+    for (int k = 2 * kSortTile; k <= max_pow2; k <<= 1) {
+      for (int j = k >> 1; j >= kSortTile; j >>= 1) ++g_index_build_launches;
+      ++g_index_build_launches;
+    }
+  }
   for (auto& t : todo) t.second->index_built(small_call ? 2048 : 4096);
   return GORIO_OK;
 }

@@ -709,7 +709,34 @@ __global__ __launch_bounds__(256) void ground_below_kernel(const float4* __restr
   below[i] = dist < -1.0 ? 1 : 0;
 }
 
+
+// one scan as float columns on the device (the scan pipeline): ground_run then reads no host point and uploads none
+struct GroundDeviceScan {
+  const float *x, *y, *z, *inten;
+};
+
+// ground_pack_kernel / ground_below_kernel for the frames of a batch of device scans: grid (ceil(max n / 256), frames), block 256; frame
+// blockIdx.y packs into / tests its own stretch of pts and tests against its own fit.  The arithmetic is that of the single kernels.
+__global__ __launch_bounds__(256) void ground_pack_frames_kernel(const GroundFrame* __restrict__ frames, const GroundDeviceScan* __restrict__ scans, float4* __restrict__ pts) {
+  const GroundFrame& f = frames[blockIdx.y];
+  const GroundDeviceScan s = scans[blockIdx.y];
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i < f.n) pts[f.pt_off + i] = make_float4(s.x[i], s.y[i], s.z[i], s.inten[i]);
+}
+__global__ __launch_bounds__(256) void ground_below_frames_kernel(const GroundFrame* __restrict__ frames, const float4* __restrict__ pts, const GroundFit* __restrict__ fits,
+                                                                  unsigned char* __restrict__ below) {
+  const GroundFrame& f = frames[blockIdx.y];
+  const GroundFit* fit = fits + blockIdx.y;
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i >= f.n) return;
+  const float4 p = pts[f.pt_off + i];
+  const double x = p.x, y = p.y, z = p.z;
+  const double dist = fit->normal[0] * x + fit->normal[1] * y + fit->normal[2] * z + fit->d;
+  below[f.pt_off + i] = dist < -1.0 ? 1 : 0;
+}
+
 }  // namespace gorio
+using gorio::GroundDeviceScan;
 
 // ================================================================================================ host side (include/gorio_ground.h)
 #include "../../include/gorio_ground.h"
@@ -738,6 +765,7 @@ struct gorio_ground {
   gorio::DevBuf<gorio::GroundFrame> d_frames;  // per frame of a batch: one group of capacity frame_cap
   gorio::DevBuf<gorio::GroundFinal> d_final;
   gorio::DevBuf<gorio::GroundFit> d_fit;
+  gorio::DevBuf<gorio::GroundDeviceScan> d_scans;  // a batch of device scans: the column pointers of every frame
   size_t frame_cap = 0;
   // diagnostics of the last estimate
   gorio_ground_frame_diag fdiag;
@@ -957,15 +985,10 @@ void ground_decide(gorio_ground* h, const gorio::GroundPatch* rec, const int* pi
   h->fdiag.n_ground = (int)ground.size();
 }
 
-// one scan as float columns on the device (the scan pipeline): ground_run then reads no host point and uploads none
-struct GroundDeviceScan {
-  const float *x, *y, *z, *inten;
-};
-
-// dev != nullptr (count == 1): the scan is *dev, its coordinates finite by construction; xyz / inten / stride are not read
+// dev != nullptr: scan q is dev[q], its coordinates finite by construction; xyz / inten / stride are not read.  One device scan takes the
+// single pack and under-ground kernels, several take their per-frame forms: one launch each, whatever the count.
 int ground_run(gorio_ground* const* hs, int count, const float* const* xyz, const float* const* inten, const int* n, const int* stride, int id, int* const* order_out,
                int* n_ground, int* n_out, const GroundDeviceScan* dev = nullptr) {
-  if (dev && count != 1) return ground_fail(GORIO_ERR_INVALID, "estimate: a device scan is one scan");
   if (!hs || count <= 0 || (!dev && (!xyz || !inten || !stride)) || !n || !order_out || !n_ground || !n_out) return ground_fail(GORIO_ERR_INVALID, "estimate: null argument");
   if (id != 0 && id != 1) return ground_fail(GORIO_ERR_INVALID, "estimate: id must be 0 (estimate_plane) or 1 (estimate_plane_cov)");
   gorio_ground* lead = hs[0];
@@ -995,7 +1018,7 @@ int ground_run(gorio_ground* const* hs, int count, const float* const* xyz, cons
                                     lead->d_keys, 2 * cap));
   }
   GORIO_HIP_CHECK(ground_fail, gorio::reserve_group(lead->rec_cap, ptot, ptot, lead->d_rec, ptot, lead->d_blk, ptot));
-  GORIO_HIP_CHECK(ground_fail, gorio::reserve_group(lead->frame_cap, count, count, lead->d_frames, count, lead->d_final, count, lead->d_fit, count));
+  GORIO_HIP_CHECK(ground_fail, gorio::reserve_group(lead->frame_cap, count, count, lead->d_frames, count, lead->d_final, count, lead->d_fit, count, lead->d_scans, count));
   std::vector<float4> pts(dev ? 0 : ntot);
   std::vector<gorio::GroundFrame> fr(count);
   std::vector<int2> blk;
@@ -1041,13 +1064,17 @@ int ground_run(gorio_ground* const* hs, int count, const float* const* xyz, cons
     max_n = std::max(max_n, n[q]);
   }
   hipStream_t st = lead->stream;
-  if (dev) {
+  GORIO_HIP_CHECK(ground_fail, hipMemcpyAsync(lead->d_frames, fr.data(), sizeof(gorio::GroundFrame) * count, hipMemcpyHostToDevice, st));
+  if (dev && count == 1) {
     gorio::ground_pack_kernel<<<(n[0] + 255) / 256, 256, 0, st>>>(dev->x, dev->y, dev->z, dev->inten, n[0], lead->d_pts);
+    GORIO_HIP_CHECK(ground_fail, hipGetLastError());
+  } else if (dev) {
+    GORIO_HIP_CHECK(ground_fail, hipMemcpyAsync(lead->d_scans, dev, sizeof(GroundDeviceScan) * count, hipMemcpyHostToDevice, st));
+    gorio::ground_pack_frames_kernel<<<dim3((max_n + 255) / 256, count), 256, 0, st>>>(lead->d_frames, lead->d_scans, lead->d_pts);
     GORIO_HIP_CHECK(ground_fail, hipGetLastError());
   } else {
     GORIO_HIP_CHECK(ground_fail, hipMemcpyAsync(lead->d_pts, pts.data(), sizeof(float4) * ntot, hipMemcpyHostToDevice, st));
   }
-  GORIO_HIP_CHECK(ground_fail, hipMemcpyAsync(lead->d_frames, fr.data(), sizeof(gorio::GroundFrame) * count, hipMemcpyHostToDevice, st));
   GORIO_HIP_CHECK(ground_fail, hipMemcpyAsync(lead->d_blk, blk.data(), sizeof(int2) * ptot, hipMemcpyHostToDevice, st));
   gorio::ground_classify_kernel<<<dim3((max_n + 255) / 256, count), 256, 0, st>>>(lead->d_frames, lead->d_pts, lead->d_pid, lead->d_C6);
   GORIO_HIP_CHECK(ground_fail, hipGetLastError());
@@ -1092,7 +1119,8 @@ int ground_run(gorio_ground* const* hs, int count, const float* const* xyz, cons
   std::vector<unsigned char> below;  // a device scan: the under-ground test of every point (d_mask is free again, its patch flags are on the host)
   if (dev) {
     below.resize(ntot);
-    gorio::ground_below_kernel<<<(n[0] + 255) / 256, 256, 0, st>>>(lead->d_pts, n[0], lead->d_fit, lead->d_mask);
+    if (count == 1) gorio::ground_below_kernel<<<(n[0] + 255) / 256, 256, 0, st>>>(lead->d_pts, n[0], lead->d_fit, lead->d_mask);
+    else gorio::ground_below_frames_kernel<<<dim3((max_n + 255) / 256, count), 256, 0, st>>>(lead->d_frames, lead->d_pts, lead->d_fit, lead->d_mask);
     GORIO_HIP_CHECK(ground_fail, hipGetLastError());
     GORIO_HIP_CHECK(ground_fail, hipMemcpyAsync(below.data(), lead->d_mask, ntot, hipMemcpyDeviceToHost, st));
   }
@@ -1115,7 +1143,7 @@ int ground_run(gorio_ground* const* hs, int count, const float* const* xyz, cons
     // PWP:872-884: erase(begin + i) while i still advances, so the point after an erased one is never tested
     std::vector<int>& ng = nongrounds[q];
     for (size_t i = 0; dev && i < ng.size(); ++i)
-      if (below[ng[i]]) ng.erase(ng.begin() + i);
+      if (below[fr[q].pt_off + ng[i]]) ng.erase(ng.begin() + i);
     const float* base = dev ? nullptr : xyz[q];
     const size_t sp = dev ? 0 : stride[q] / 4;
     for (size_t i = 0; !dev && i < ng.size(); ++i) {

@@ -23,12 +23,14 @@ struct RadiusArgs {
 };
 
 // mode 0: count; mode 1: fill.  grid: ceil(n_spad / 256), block 256.  One lane = one query in sorted order.
+// The search kernels of this file are per-workgroup bodies, `block` the 256-query block, and a __global__ that hands them blockIdx.x; the
+// job-table kernels of apd_scan_batch.hip hand the same bodies the block of a (job, block) entry.
 template <int MODE>
-__global__ __launch_bounds__(256) void radius_neighbours_kernel(CloudView cloud, RadiusArgs a) {
+__device__ __forceinline__ void radius_neighbours_body(const CloudView& cloud, const RadiusArgs& a, int block) {
   const SearchIndex& si = cloud.idx;
   const int n = si.n;
-  const int p = blockIdx.x * 256 + threadIdx.x;
-  if (blockIdx.x * 256 >= n) return;
+  const int p = block * 256 + threadIdx.x;
+  if (block * 256 >= n) return;
   const int lane = threadIdx.x & 63;
   const int pq = p < n ? p : n - 1;
   const float qx = si.sx[pq], qy = si.sy[pq], qz = si.sz[pq];
@@ -80,16 +82,20 @@ __global__ __launch_bounds__(256) void radius_neighbours_kernel(CloudView cloud,
   }
   if (MODE == 0 && p < n) a.cnt[me] = cnt;
 }
+template <int MODE>
+__global__ __launch_bounds__(256) void radius_neighbours_kernel(CloudView cloud, RadiusArgs a) {
+  radius_neighbours_body<MODE>(cloud, a, blockIdx.x);
+}
 
 // pcl::RadiusOutlierRemoval as the preprocessing nodelet configures it (preprocessing_nodelet_ntu.cpp:163-171, 626-634; launch files:
 // radius 2 m, 1 - 5 neighbours): number of points of the SAME cloud, the query included, whose float squared distance is at most the
 // squared radius.  r2 = largest float whose double value is <= radius * radius (the comparison PCL makes is in double on float
 // distances).  grid: ceil(n_spad / 256), block 256; cnt[] by ORIGINAL index.
-__global__ __launch_bounds__(256) void radius_count_kernel(CloudView cloud, float r2, int* __restrict__ cnt_out) {
+__device__ __forceinline__ void radius_count_body(const CloudView& cloud, float r2, int* __restrict__ cnt_out, int block) {
   const SearchIndex& si = cloud.idx;
   const int n = si.n;
-  const int p = blockIdx.x * 256 + threadIdx.x;
-  if (blockIdx.x * 256 >= n) return;
+  const int p = block * 256 + threadIdx.x;
+  if (block * 256 >= n) return;
   const int lane = threadIdx.x & 63;
   const int pq = p < n ? p : n - 1;
   const float qx = si.sx[pq], qy = si.sy[pq], qz = si.sz[pq];
@@ -121,6 +127,7 @@ __global__ __launch_bounds__(256) void radius_count_kernel(CloudView cloud, floa
   }
   if (p < n) cnt_out[si.orig[p]] = cnt;
 }
+__global__ __launch_bounds__(256) void radius_count_kernel(CloudView cloud, float r2, int* __restrict__ cnt_out) { radius_count_body(cloud, r2, cnt_out, blockIdx.x); }
 
 
 // pcl::StatisticalOutlierRemoval, first half (PCL 1.10 filters/impl/statistical_outlier_removal.hpp, as preprocessing_nodelet_ntu.cpp:
@@ -131,12 +138,12 @@ __global__ __launch_bounds__(256) void radius_count_kernel(CloudView cloud, floa
 // candidate moves, so D[31] is the k-th smallest throughout.  The sum runs over the sorted distances 1 .. k-1 in double, on double
 // square roots of the float values, and is divided by mean_k and rounded to float as PCL does.
 // grid: ceil(n_spad / 256), block 256; mean_out[] by ORIGINAL index.
-__global__ __launch_bounds__(256) void sor_mean_distance_kernel(CloudView cloud, int k, float* __restrict__ mean_out) {
+__device__ __forceinline__ void sor_mean_distance_body(const CloudView& cloud, int k, float* __restrict__ mean_out, int block) {
   constexpr int K = 32;
   const SearchIndex& si = cloud.idx;
   const int n = si.n;
-  const int p = blockIdx.x * 256 + threadIdx.x;
-  if (blockIdx.x * 256 >= n) return;
+  const int p = block * 256 + threadIdx.x;
+  if (block * 256 >= n) return;
   const int lane = threadIdx.x & 63;
   const int pq = p < n ? p : n - 1;
   const float qx = si.sx[pq], qy = si.sy[pq], qz = si.sz[pq];
@@ -147,7 +154,7 @@ __global__ __launch_bounds__(256) void sor_mean_distance_kernel(CloudView cloud,
   const scalar_fp tz = as_scalar(si.sz);
   const float4* __restrict__ tb4 = reinterpret_cast<const float4*>(si.tbox);
   const int ng = (si.n_tiles + 63) / 64;
-  const int g0 = (blockIdx.x * 256 + (threadIdx.x & ~63)) / 32 / 64;  // the group of this wave's own tiles: visited first, it tightens the bounds
+  const int g0 = (block * 256 + (threadIdx.x & ~63)) / 32 / 64;  // the group of this wave's own tiles: visited first, it tightens the bounds
   float D[K];
 #pragma unroll
   for (int t = 0; t < K; ++t) D[t] = t < K - k ? -INFINITY : INFINITY;
@@ -187,13 +194,14 @@ __global__ __launch_bounds__(256) void sor_mean_distance_kernel(CloudView cloud,
     mean_out[si.orig[p]] = (float)(sum / (double)(k - 1));
   }
 }
+__global__ __launch_bounds__(256) void sor_mean_distance_kernel(CloudView cloud, int k, float* __restrict__ mean_out) { sor_mean_distance_body(cloud, k, mean_out, blockIdx.x); }
 
 // PREP:539-548 for a cloud that lives on the device: the float coordinate sums of every cluster, its members added one after the other in
 // ascending index order exactly as the host loop of gorio_prep_dbscan_labels adds them.  One lane = one cluster (there are tens of them);
 // grid: ceil(nc / 64), block 64.
-__global__ __launch_bounds__(64) void cluster_sums_kernel(const float* __restrict__ x, const float* __restrict__ y, const float* __restrict__ z, const int* __restrict__ members,
-                                                          const int* __restrict__ offs, int nc, float* __restrict__ sums) {
-  const int c = blockIdx.x * 64 + threadIdx.x;
+__device__ __forceinline__ void cluster_sums_body(const float* __restrict__ x, const float* __restrict__ y, const float* __restrict__ z, const int* __restrict__ members,
+                                                  const int* __restrict__ offs, int nc, float* __restrict__ sums, int block) {
+  const int c = block * 64 + threadIdx.x;
   if (c >= nc) return;
   float sx = 0.f, sy = 0.f, sz = 0.f;
   for (int e = offs[c]; e < offs[c + 1]; ++e) {
@@ -205,6 +213,10 @@ __global__ __launch_bounds__(64) void cluster_sums_kernel(const float* __restric
   sums[3 * c] = sx;
   sums[3 * c + 1] = sy;
   sums[3 * c + 2] = sz;
+}
+__global__ __launch_bounds__(64) void cluster_sums_kernel(const float* __restrict__ x, const float* __restrict__ y, const float* __restrict__ z, const int* __restrict__ members,
+                                                          const int* __restrict__ offs, int nc, float* __restrict__ sums) {
+  cluster_sums_body(x, y, z, members, offs, nc, sums, blockIdx.x);
 }
 
 }  // namespace gorio
@@ -224,9 +236,9 @@ struct ReveCfg {
 
 // grid: ceil(n / 256).  f[i][4] = x/r, y/r, z/r, corrected doppler; valid[i]
 // px / py / pz: first x, y, z; `stride` floats between targets (5 for the packed upload of gorio_prep_ego_velocity, 1 for device columns)
-__global__ __launch_bounds__(256) void reve_features_kernel(const float* __restrict__ px, const float* __restrict__ py, const float* __restrict__ pz, const float* __restrict__ inten,
-                                                            const float* __restrict__ dop, int stride, int n, ReveCfg c, double* __restrict__ f, unsigned char* __restrict__ valid) {
-  const int i = blockIdx.x * 256 + threadIdx.x;
+__device__ __forceinline__ void reve_features_body(const float* __restrict__ px, const float* __restrict__ py, const float* __restrict__ pz, const float* __restrict__ inten,
+                                                   const float* __restrict__ dop, int stride, int n, const ReveCfg& c, double* __restrict__ f, unsigned char* __restrict__ valid, int block) {
+  const int i = block * 256 + threadIdx.x;
   if (i >= n) return;
   const float x = px[(size_t)i * stride], y = py[(size_t)i * stride], z = pz[(size_t)i * stride];
   const double r = sqrt((double)x * (double)x + (double)y * (double)y + (double)z * (double)z);  // Vector3(x, y, z).norm(), REVE:78
@@ -243,19 +255,27 @@ __global__ __launch_bounds__(256) void reve_features_kernel(const float* __restr
   f[4 * (size_t)i + 2] = z / r;
   f[4 * (size_t)i + 3] = (double)d;
 }
+__global__ __launch_bounds__(256) void reve_features_kernel(const float* __restrict__ px, const float* __restrict__ py, const float* __restrict__ pz, const float* __restrict__ inten,
+                                                            const float* __restrict__ dop, int stride, int n, ReveCfg c, double* __restrict__ f, unsigned char* __restrict__ valid) {
+  reve_features_body(px, py, pz, inten, dop, stride, n, c, f, valid, blockIdx.x);
+}
 
 // grid: (ceil(m / 256), hypotheses).  flags[k][j] = |y_j - h_j . v_k| < thresh (REVE:203-214) over the VALID targets
-__global__ __launch_bounds__(256) void reve_eval_kernel(const double* __restrict__ f, int m, const double* __restrict__ v /* [K][3] */, double thresh, unsigned char* __restrict__ flags) {
-  const int j = blockIdx.x * 256 + threadIdx.x, k = blockIdx.y;
+__device__ __forceinline__ void reve_eval_body(const double* __restrict__ f, int m, const double* __restrict__ v /* [K][3] */, double thresh, unsigned char* __restrict__ flags, int block,
+                                               int k) {
+  const int j = block * 256 + threadIdx.x;
   if (j >= m) return;
   const double* r = f + 4 * (size_t)j;
   const double err = fabs(r[3] - (r[0] * v[3 * k] + r[1] * v[3 * k + 1] + r[2] * v[3 * k + 2]));
   flags[(size_t)k * m + j] = err < thresh ? 1 : 0;
 }
+__global__ __launch_bounds__(256) void reve_eval_kernel(const double* __restrict__ f, int m, const double* __restrict__ v /* [K][3] */, double thresh, unsigned char* __restrict__ flags) {
+  reve_eval_body(f, m, v, thresh, flags, blockIdx.x, blockIdx.y);
+}
 
 // grid: ceil(m / 256).  per block: 10 sums over the selected rows -- H^T H (6 unique), H^T y (3), and, with v, e^T e of e = H v - y
-__global__ __launch_bounds__(256) void reve_sums_kernel(const double* __restrict__ f, int m, const unsigned char* __restrict__ sel, const double* __restrict__ v, double* __restrict__ out) {
-  const int j = blockIdx.x * 256 + threadIdx.x;
+__device__ __forceinline__ void reve_sums_body(const double* __restrict__ f, int m, const unsigned char* __restrict__ sel, const double* __restrict__ v, double* __restrict__ out, int block) {
+  const int j = block * 256 + threadIdx.x;
   double a[10];
 #pragma unroll
   for (int q = 0; q < 10; ++q) a[q] = 0.0;
@@ -276,7 +296,10 @@ __global__ __launch_bounds__(256) void reve_sums_kernel(const double* __restrict
     if (lane == 0) red[wv][q] = s;
   }
   __syncthreads();
-  if (threadIdx.x < 10) out[(size_t)blockIdx.x * 10 + threadIdx.x] = (red[0][threadIdx.x] + red[1][threadIdx.x]) + (red[2][threadIdx.x] + red[3][threadIdx.x]);
+  if (threadIdx.x < 10) out[(size_t)block * 10 + threadIdx.x] = (red[0][threadIdx.x] + red[1][threadIdx.x]) + (red[2][threadIdx.x] + red[3][threadIdx.x]);
+}
+__global__ __launch_bounds__(256) void reve_sums_kernel(const double* __restrict__ f, int m, const unsigned char* __restrict__ sel, const double* __restrict__ v, double* __restrict__ out) {
+  reve_sums_body(f, m, sel, v, out, blockIdx.x);
 }
 
 }  // namespace gorio
@@ -360,6 +383,9 @@ int prep_index_cloud_device(PrepCtx& c, const float* dx, const float* dy, const 
 // ---- the stages proper, on the indexed source of the context's handle.  The public entry points below and the scan pipeline
 // (apd_scan.hip) both run these; what differs is only where the cloud came from.
 
+void prep_dbscan_replay(const std::vector<int>& cnt, const std::vector<long long>& offs, const std::vector<int>& adj, int n, int core_min_pts, int min_cluster_size, int max_cluster_size,
+                        std::vector<std::vector<int>>& clusters);
+
 // DBS:28-100: the radius searches on the device, the queue replayed over their adjacency; clusters in the order the queue closes them,
 // members sorted (DBS:91)
 int prep_dbscan_clusters(PrepCtx& c, int n, double eps, int core_min_pts, int min_cluster_size, int max_cluster_size, std::vector<std::vector<int>>& clusters) {
@@ -384,8 +410,13 @@ int prep_dbscan_clusters(PrepCtx& c, int n, double eps, int core_min_pts, int mi
   std::vector<int> adj((size_t)E);
   if (E > 0) GORIO_HIP_CHECK(prep_fail, hipMemcpyAsync(adj.data(), c.d_adj, sizeof(int) * (size_t)E, hipMemcpyDeviceToHost, h->stream));
   GORIO_HIP_CHECK(prep_fail, hipStreamSynchronize(h->stream));
+  prep_dbscan_replay(cnt, offs, adj, n, core_min_pts, min_cluster_size, max_cluster_size, clusters);
+  return GORIO_OK;
+}
 
-  // ---- the queue of DBSCAN_simple.h:28-100, statement for statement, over the adjacency (the radius searches are done)
+// the queue of DBSCAN_simple.h:28-100, statement for statement, over the adjacency (the radius searches are done)
+void prep_dbscan_replay(const std::vector<int>& cnt, const std::vector<long long>& offs, const std::vector<int>& adj, int n, int core_min_pts, int min_cluster_size, int max_cluster_size,
+                        std::vector<std::vector<int>>& clusters) {
   enum : unsigned char { UN = 0, PROCESSING = 1, PROCESSED = 2 };
   std::vector<unsigned char> types((size_t)n, UN), noise((size_t)n, 0);
   std::vector<int> queue;
@@ -436,7 +467,6 @@ int prep_dbscan_clusters(PrepCtx& c, int n, double eps, int core_min_pts, int mi
     if ((int)queue.size() >= min_cluster_size && (int)queue.size() <= max_cluster_size) clusters.push_back(queue);  // DBS:83-95
   }
   for (std::vector<int>& m : clusters) std::sort(m.begin(), m.end());  // DBS:91
-  return GORIO_OK;
 }
 
 // PREP:550-568 from the float coordinate sums of the clusters (sums[c][3], PREP:539-548): rank[c] = position of cluster c when the
@@ -455,39 +485,39 @@ void prep_rank_clusters(const std::vector<std::vector<int>>& clusters, const flo
 }
 
 // pcl::RadiusOutlierRemoval: the neighbour counts of every point of the indexed source, then the mask
-int prep_radius_outlier_keep(PrepCtx& c, int n, double radius, int min_neighbors, unsigned char* keep, int* n_kept) {
-  gorio_apd* h = c.h;
+float prep_radius_r2(double radius) {
   const double r2d = radius * radius;
   float r2 = FLT_MAX;
   if (r2d < (double)FLT_MAX) {  // largest float whose double value is <= r^2: (double)d <= r^2  <=>  d <= r2 for every float d
     r2 = (float)r2d;
     while ((double)r2 > r2d) r2 = std::nextafterf(r2, 0.0f);
   }
-  radius_count_kernel<<<(roundup(n, 512) + 255) / 256, 256, 0, h->stream>>>(h->src->view(), r2, c.d_cnt);
-  GORIO_HIP_CHECK(prep_fail, hipGetLastError());
-  std::vector<int> cnt((size_t)n);
-  GORIO_HIP_CHECK(prep_fail, hipMemcpyAsync(cnt.data(), c.d_cnt, sizeof(int) * (size_t)n, hipMemcpyDeviceToHost, h->stream));
-  GORIO_HIP_CHECK(prep_fail, hipStreamSynchronize(h->stream));
+  return r2;
+}
+// the mask from the neighbour counts
+void prep_radius_keep_from_counts(const int* cnt, int n, int min_neighbors, unsigned char* keep, int* n_kept) {
   int kept = 0;
   for (int i = 0; i < n; ++i) {
     keep[i] = cnt[i] > min_neighbors ? 1 : 0;  // the query itself is one of the counted points
     kept += keep[i];
   }
   if (n_kept) *n_kept = kept;
+}
+int prep_radius_outlier_keep(PrepCtx& c, int n, double radius, int min_neighbors, unsigned char* keep, int* n_kept) {
+  gorio_apd* h = c.h;
+  const float r2 = prep_radius_r2(radius);
+  radius_count_kernel<<<(roundup(n, 512) + 255) / 256, 256, 0, h->stream>>>(h->src->view(), r2, c.d_cnt);
+  GORIO_HIP_CHECK(prep_fail, hipGetLastError());
+  std::vector<int> cnt((size_t)n);
+  GORIO_HIP_CHECK(prep_fail, hipMemcpyAsync(cnt.data(), c.d_cnt, sizeof(int) * (size_t)n, hipMemcpyDeviceToHost, h->stream));
+  GORIO_HIP_CHECK(prep_fail, hipStreamSynchronize(h->stream));
+  prep_radius_keep_from_counts(cnt.data(), n, min_neighbors, keep, n_kept);
   return GORIO_OK;
 }
 
-// pcl::StatisticalOutlierRemoval: the mean neighbour distance of every point of the indexed source, then threshold and mask
-int prep_statistical_outlier_keep(PrepCtx& c, int n, int mean_k, double stddev_mul, unsigned char* keep, int* n_kept, float* mean_dist_out) {
-  gorio_apd* h = c.h;
-  float* d_mean = reinterpret_cast<float*>(c.d_cnt.get());  // one 4-byte word per point, like the neighbour counts
-  sor_mean_distance_kernel<<<(roundup(n, 512) + 255) / 256, 256, 0, h->stream>>>(h->src->view(), mean_k + 1, d_mean);
-  GORIO_HIP_CHECK(prep_fail, hipGetLastError());
-  std::vector<float> dist((size_t)n);
-  GORIO_HIP_CHECK(prep_fail, hipMemcpyAsync(dist.data(), d_mean, sizeof(float) * (size_t)n, hipMemcpyDeviceToHost, h->stream));
-  GORIO_HIP_CHECK(prep_fail, hipStreamSynchronize(h->stream));
-  // mean and standard deviation of the per-point values and the threshold, in PCL's order and types (statistical_outlier_removal.hpp:
-  // double sums over the float distances in point order, the n - 1 form of the variance); N numbers: done on the host
+// mean and standard deviation of the per-point values and the threshold, in PCL's order and types (statistical_outlier_removal.hpp:
+// double sums over the float distances in point order, the n - 1 form of the variance); N numbers: done on the host
+void prep_sor_keep_from_distances(const float* dist, int n, double stddev_mul, unsigned char* keep, int* n_kept, float* mean_dist_out) {
   double sum = 0.0, sq_sum = 0.0;
   for (int i = 0; i < n; ++i) {
     sum += dist[i];
@@ -504,6 +534,18 @@ int prep_statistical_outlier_keep(PrepCtx& c, int n, int mean_k, double stddev_m
     if (mean_dist_out) mean_dist_out[i] = dist[i];
   }
   if (n_kept) *n_kept = kept;
+}
+
+// pcl::StatisticalOutlierRemoval: the mean neighbour distance of every point of the indexed source, then threshold and mask
+int prep_statistical_outlier_keep(PrepCtx& c, int n, int mean_k, double stddev_mul, unsigned char* keep, int* n_kept, float* mean_dist_out) {
+  gorio_apd* h = c.h;
+  float* d_mean = reinterpret_cast<float*>(c.d_cnt.get());  // one 4-byte word per point, like the neighbour counts
+  sor_mean_distance_kernel<<<(roundup(n, 512) + 255) / 256, 256, 0, h->stream>>>(h->src->view(), mean_k + 1, d_mean);
+  GORIO_HIP_CHECK(prep_fail, hipGetLastError());
+  std::vector<float> dist((size_t)n);
+  GORIO_HIP_CHECK(prep_fail, hipMemcpyAsync(dist.data(), d_mean, sizeof(float) * (size_t)n, hipMemcpyDeviceToHost, h->stream));
+  GORIO_HIP_CHECK(prep_fail, hipStreamSynchronize(h->stream));
+  prep_sor_keep_from_distances(dist.data(), n, stddev_mul, keep, n_kept, mean_dist_out);
   return GORIO_OK;
 }
 
@@ -779,18 +821,15 @@ int reve_prepare(ReveCtx& c, int device, int n) {
 
 // REVE:75-90 for n targets on the device (px / py / pz / inten / dop with `stride` floats between targets): features and gates there,
 // the rows of the valid targets collected here
-int reve_features(ReveCtx& c, const float* px, const float* py, const float* pz, const float* inten, const float* dop, int stride, int n, const gorio_reve_config* cfg, ReveFrame& fr) {
+ReveCfg reve_device_cfg(const gorio_reve_config* cfg) {
   ReveCfg rc;
   rc.min_dist = cfg->min_dist; rc.max_dist = cfg->max_dist; rc.min_db = cfg->min_db;
   rc.az_lim = (double)cfg->azimuth_thresh_deg * M_PI / 180.0; rc.el_lim = (double)cfg->elevation_thresh_deg * M_PI / 180.0;  // angles::from_degrees
   rc.doppler_factor_unused = 0; rc.doppler_factor = cfg->doppler_velocity_correction_factor; rc.pad_ = 0;
-  reve_features_kernel<<<(n + 255) / 256, 256, 0, c.stream>>>(px, py, pz, inten, dop, stride, n, rc, c.d_f, c.d_valid);
-  GORIO_HIP_CHECK(prep_fail, hipGetLastError());
-  std::vector<double> f((size_t)n * 4);
-  std::vector<unsigned char> valid((size_t)n);
-  GORIO_HIP_CHECK(prep_fail, hipMemcpyAsync(f.data(), c.d_f, sizeof(double) * f.size(), hipMemcpyDeviceToHost, c.stream));
-  GORIO_HIP_CHECK(prep_fail, hipMemcpyAsync(valid.data(), c.d_valid, (size_t)n, hipMemcpyDeviceToHost, c.stream));
-  GORIO_HIP_CHECK(prep_fail, hipStreamSynchronize(c.stream));
+  return rc;
+}
+// the rows of the valid targets, in input order, from what the features kernel left (f[n][4], valid[n])
+void reve_collect(ReveFrame& fr, const std::vector<double>& f, const std::vector<unsigned char>& valid, int n) {
   fr.n = n;
   fr.vidx.clear();
   fr.fv.clear();
@@ -800,44 +839,202 @@ int reve_features(ReveCtx& c, const float* px, const float* py, const float* pz,
       fr.fv.insert(fr.fv.end(), f.begin() + 4 * (size_t)i, f.begin() + 4 * (size_t)i + 4);
     }
   fr.m = (int)fr.vidx.size();
+}
+int reve_features(ReveCtx& c, const float* px, const float* py, const float* pz, const float* inten, const float* dop, int stride, int n, const gorio_reve_config* cfg, ReveFrame& fr) {
+  const ReveCfg rc = reve_device_cfg(cfg);
+  reve_features_kernel<<<(n + 255) / 256, 256, 0, c.stream>>>(px, py, pz, inten, dop, stride, n, rc, c.d_f, c.d_valid);
+  GORIO_HIP_CHECK(prep_fail, hipGetLastError());
+  std::vector<double> f((size_t)n * 4);
+  std::vector<unsigned char> valid((size_t)n);
+  GORIO_HIP_CHECK(prep_fail, hipMemcpyAsync(f.data(), c.d_f, sizeof(double) * f.size(), hipMemcpyDeviceToHost, c.stream));
+  GORIO_HIP_CHECK(prep_fail, hipMemcpyAsync(valid.data(), c.d_valid, (size_t)n, hipMemcpyDeviceToHost, c.stream));
+  GORIO_HIP_CHECK(prep_fail, hipStreamSynchronize(c.stream));
+  reve_collect(fr, f, valid, n);
   return GORIO_OK;
 }
 
-// REVE:92-170 over the valid targets of `fr`: zero-velocity test, least squares, RANSAC
-int reve_solve(ReveCtx& c, const gorio_reve_config* cfg, const ReveFrame& fr, const unsigned int* sample_idx, int n_iter, double v_r[3], double sigma_v_r[3],
-               unsigned char* inlier_mask, unsigned char* outlier_mask, int* zero_velocity, int* success) {
-  const int n = fr.n, m = fr.m;
-  const std::vector<int>& vidx = fr.vidx;
-  const std::vector<double>& fv = fr.fv;
-  if (inlier_mask) std::memset(inlier_mask, 0, (size_t)n);
-  if (outlier_mask) std::memset(outlier_mask, 0, (size_t)n);
+// REVE:92-170 over the valid targets of `fr`: zero-velocity test, least squares, RANSAC.  One solve is advanced in phases, so that a batch
+// (apd_scan_batch.hip) can put the launches of many solves into one: a phase does its host part, enqueues its uploads on the context's
+// stream and names the launch it wants (`want`); after that launch, reve_solve_download and a synchronisation, reve_solve_advance does
+// the next host part.  reve_solve below drives one solve with the single kernels.
+struct ReveSolve {
+  ReveCtx* c = nullptr;
+  const gorio_reve_config* cfg = nullptr;
+  const ReveFrame* fr = nullptr;
+  const unsigned int* sample_idx = nullptr;
+  int n_iter = 0;
+  double *v_r = nullptr, *sigma_v_r = nullptr;
+  unsigned char *inlier_mask = nullptr, *outlier_mask = nullptr;
+  int* zero_velocity = nullptr;
+  int ok = 0;
+  enum Want { DONE = 0, EVAL = 1, SUMS = 2 };
+  int want = DONE;
+  int K = 0;     // EVAL: hypotheses; flags[K][m] come back
+  int pass = 0;  // SUMS: 0 = H^T H and H^T y of the selected rows, 1 = the same with e^T e for v_r
+  int rows = 0;  // SUMS: selected rows
+  bool ransac = false;
+  std::vector<double> vs, part;
+  std::vector<unsigned char> flags, sel, best_out;
+  size_t nbo = 0;
+};
+
+// solve3DFull (REVE:252-303) over the valid rows selected by S.sel: sums on the device (two SUMS launches), 3 x 3 algebra on the host
+int reve_solve_start_sums(ReveSolve& S) {
+  ReveCtx& c = *S.c;
+  const int m = S.fr->m, nb = (m + 255) / 256;
+  if (hipMemcpyAsync(c.d_valid, S.sel.data(), (size_t)m, hipMemcpyHostToDevice, c.stream) != hipSuccess) return prep_fail(GORIO_ERR_NO_DEVICE, "ego_velocity: device error");
+  S.part.assign((size_t)nb * 10, 0.0);
+  S.pass = 0;
+  S.want = ReveSolve::SUMS;
+  return GORIO_OK;
+}
+
+void reve_solve_finish(ReveSolve& S, bool solved) {
+  const int m = S.fr->m;
+  const std::vector<int>& vidx = S.fr->vidx;
+  if (solved) {
+    S.ok = 1;  // REVE:301: true whatever the sigma test said
+    if (S.inlier_mask)
+      for (int j = 0; j < m; ++j)
+        if (S.sel[j]) S.inlier_mask[vidx[j]] = 1;
+  }
+  if (S.ransac && S.outlier_mask && S.nbo > 0)
+    for (int j = 0; j < m; ++j)
+      if (S.best_out[j]) S.outlier_mask[vidx[j]] = 1;
+  S.want = ReveSolve::DONE;
+}
+
+int reve_solve_begin(ReveSolve& S) {
+  ReveCtx& c = *S.c;
+  const gorio_reve_config* cfg = S.cfg;
+  const int n = S.fr->n, m = S.fr->m;
+  const std::vector<int>& vidx = S.fr->vidx;
+  const std::vector<double>& fv = S.fr->fv;
+  double *v_r = S.v_r, *sigma_v_r = S.sigma_v_r;
+  if (S.inlier_mask) std::memset(S.inlier_mask, 0, (size_t)n);
+  if (S.outlier_mask) std::memset(S.outlier_mask, 0, (size_t)n);
   v_r[0] = v_r[1] = v_r[2] = 0.0;
   sigma_v_r[0] = sigma_v_r[1] = sigma_v_r[2] = 0.0;
-  if (zero_velocity) *zero_velocity = 0;
-  int ok = 0;
-  // solve3DFull (REVE:252-303) over the valid rows selected by `sel`: sums on the device, 3 x 3 algebra here
-  auto solve = [&](const std::vector<unsigned char>& sel, int rows, bool estimate_sigma, double* v, double* sigma) -> int {
-    const int nb = (m + 255) / 256;
-    if (hipMemcpyAsync(c.d_valid, sel.data(), (size_t)m, hipMemcpyHostToDevice, c.stream) != hipSuccess) return -1;
-    std::vector<double> part((size_t)nb * 10);
-    double s[10];
-    for (int pass = 0; pass < (estimate_sigma ? 2 : 1); ++pass) {
-      if (pass == 1 && hipMemcpyAsync(c.d_v, v, sizeof(double) * 3, hipMemcpyHostToDevice, c.stream) != hipSuccess) return -1;
-      reve_sums_kernel<<<nb, 256, 0, c.stream>>>(c.d_fv, m, c.d_valid, pass == 1 ? c.d_v.get() : nullptr, c.d_out);
-      if (hipMemcpyAsync(part.data(), c.d_out, sizeof(double) * part.size(), hipMemcpyDeviceToHost, c.stream) != hipSuccess || hipStreamSynchronize(c.stream) != hipSuccess) return -1;
-      for (int q = 0; q < 10; ++q) s[q] = 0.0;
-      for (int b = 0; b < nb; ++b)
-        for (int q = 0; q < 10; ++q) s[q] += part[(size_t)b * 10 + q];
-      if (pass == 0) {
-        const double HTH[9] = {s[0], s[1], s[2], s[1], s[3], s[4], s[2], s[4], s[5]}, HTy[3] = {s[6], s[7], s[8]};
-        host_ldlt3_solve(HTH, HTy, v);  // use_cholesky_instead_of_bdcsvd = true: (HTH).ldlt().solve(H^T y), REVE:272
+  if (S.zero_velocity) *S.zero_velocity = 0;
+  S.ok = 0;
+  S.want = ReveSolve::DONE;
+  if (m <= 2) return GORIO_OK;
+  GORIO_HIP_CHECK(prep_fail, hipMemcpyAsync(c.d_fv, fv.data(), sizeof(double) * fv.size(), hipMemcpyHostToDevice, c.stream));
+  std::vector<double> vd((size_t)m);
+  for (int k = 0; k < m; ++k) vd[k] = std::fabs(fv[4 * (size_t)k + 3]);
+  const size_t nth = std::min((size_t)((double)m * (1.0 - (double)cfg->allowed_outlier_percentage)), (size_t)m - 1);
+  std::nth_element(vd.begin(), vd.begin() + nth, vd.end());  // REVE:105-108
+  if (vd[nth] < cfg->thresh_zero_velocity) {                 // REVE:110-121
+    if (S.zero_velocity) *S.zero_velocity = 1;
+    sigma_v_r[0] = cfg->sigma_zero_velocity_x; sigma_v_r[1] = cfg->sigma_zero_velocity_y; sigma_v_r[2] = cfg->sigma_zero_velocity_z;
+    if (S.inlier_mask)
+      for (int k = 0; k < m; ++k)
+        if (std::fabs(fv[4 * (size_t)k + 3]) < cfg->thresh_zero_velocity) S.inlier_mask[vidx[k]] = 1;
+    S.ok = 1;
+    return GORIO_OK;
+  }
+  if (!cfg->use_ransac) {
+    S.sel.assign((size_t)m, 1);
+    S.rows = m;
+    return reve_solve_start_sums(S);
+  }
+  // solve3DFullRansac, REVE:172-250
+  S.ransac = true;
+  S.nbo = 0;
+  const int K = m >= cfg->n_ransac_points ? S.n_iter : 0;
+  S.K = K;
+  if (K <= 0) {
+    reve_solve_finish(S, false);
+    return GORIO_OK;
+  }
+  if (K > 64) return prep_fail(GORIO_ERR_INVALID, "ego_velocity: more than 64 RANSAC iterations");
+  std::vector<double>& vs = S.vs;
+  vs.assign((size_t)K * 3, 0.0);
+  for (int k = 0; k < K; ++k) {  // the sample systems are N_ransac_points rows: solved here (3 x 3)
+    double HTH[9] = {0}, HTy[3] = {0};
+    for (int q = 0; q < cfg->n_ransac_points; ++q) {
+      const unsigned int row = S.sample_idx[(size_t)k * cfg->n_ransac_points + q];
+      if (row >= (unsigned int)m) return prep_fail(GORIO_ERR_INVALID, "ego_velocity: sample index outside the valid targets");
+      const double* r = fv.data() + 4 * (size_t)row;
+      for (int a = 0; a < 3; ++a) {
+        for (int b = 0; b < 3; ++b) HTH[a * 3 + b] += r[a] * r[b];
+        HTy[a] += r[a] * r[3];
       }
     }
-    if (estimate_sigma) {  // REVE:278-290
+    host_ldlt3_solve(HTH, HTy, vs.data() + 3 * (size_t)k);
+  }
+  GORIO_HIP_CHECK(prep_fail, c.d_flags.reserve((size_t)K * m, (size_t)K * m + 1024));
+  GORIO_HIP_CHECK(prep_fail, hipMemcpyAsync(c.d_v, vs.data(), sizeof(double) * vs.size(), hipMemcpyHostToDevice, c.stream));
+  S.flags.assign((size_t)K * m, 0);
+  S.want = ReveSolve::EVAL;
+  return GORIO_OK;
+}
+
+// what the launch named by S.want left, on its way to the host; the caller synchronises the stream before reve_solve_advance
+int reve_solve_download(ReveSolve& S) {
+  ReveCtx& c = *S.c;
+  if (S.want == ReveSolve::EVAL) {
+    GORIO_HIP_CHECK(prep_fail, hipMemcpyAsync(S.flags.data(), c.d_flags, S.flags.size(), hipMemcpyDeviceToHost, c.stream));
+  } else if (S.want == ReveSolve::SUMS) {
+    if (hipMemcpyAsync(S.part.data(), c.d_out, sizeof(double) * S.part.size(), hipMemcpyDeviceToHost, c.stream) != hipSuccess)
+      return prep_fail(GORIO_ERR_NO_DEVICE, "ego_velocity: device error");
+  }
+  return GORIO_OK;
+}
+
+int reve_solve_advance(ReveSolve& S) {
+  ReveCtx& c = *S.c;
+  const gorio_reve_config* cfg = S.cfg;
+  const int m = S.fr->m;
+  double *v_r = S.v_r, *sigma = S.sigma_v_r;
+  if (S.want == ReveSolve::EVAL) {
+    const int K = S.K;
+    const std::vector<double>& vs = S.vs;
+    std::vector<unsigned char> best_in;
+    size_t nbi = 0;
+    for (int k = 0; k < K; ++k) {
+      const unsigned char* fl = S.flags.data() + (size_t)k * m;
+      size_t ni = 0;
+      for (int j = 0; j < m; ++j) ni += fl[j];
+      size_t no = (size_t)m - ni;
+      std::vector<unsigned char> cur_in(fl, fl + m), cur_out((size_t)m);
+      for (int j = 0; j < m; ++j) cur_out[j] = !fl[j];
+      if ((float)no / (float)(ni + no) > 0.05) {  // REVE:215-220
+        std::fill(cur_in.begin(), cur_in.end(), 1);
+        std::fill(cur_out.begin(), cur_out.end(), 0);
+        ni = (size_t)m;
+        no = 0;
+      }
+      if (ni > nbi) { best_in = cur_in; nbi = ni; }
+      if (no > S.nbo) { S.best_out = cur_out; S.nbo = no; }
+      v_r[0] = vs[3 * (size_t)k]; v_r[1] = vs[3 * (size_t)k + 1]; v_r[2] = vs[3 * (size_t)k + 2];
+    }
+    if (nbi == 0) {
+      reve_solve_finish(S, false);
+      return GORIO_OK;
+    }
+    S.sel = best_in;
+    S.rows = (int)nbi;
+    return reve_solve_start_sums(S);
+  }
+  if (S.want == ReveSolve::SUMS) {
+    const int nb = (m + 255) / 256;
+    double s[10];
+    for (int q = 0; q < 10; ++q) s[q] = 0.0;
+    for (int b = 0; b < nb; ++b)
+      for (int q = 0; q < 10; ++q) s[q] += S.part[(size_t)b * 10 + q];
+    if (S.pass == 0) {
+      const double HTH[9] = {s[0], s[1], s[2], s[1], s[3], s[4], s[2], s[4], s[5]}, HTy[3] = {s[6], s[7], s[8]};
+      host_ldlt3_solve(HTH, HTy, v_r);  // use_cholesky_instead_of_bdcsvd = true: (HTH).ldlt().solve(H^T y), REVE:272
+      if (hipMemcpyAsync(c.d_v, v_r, sizeof(double) * 3, hipMemcpyHostToDevice, c.stream) != hipSuccess) return prep_fail(GORIO_ERR_NO_DEVICE, "ego_velocity: device error");
+      S.pass = 1;
+      return GORIO_OK;  // want stays SUMS
+    }
+    {  // REVE:278-290
       const double H0 = s[0], H1 = s[1], H2 = s[2], H4 = s[3], H5 = s[4], H8 = s[5];
       const double c00 = H4 * H8 - H5 * H5, c01 = H5 * H2 - H1 * H8, c02 = H1 * H5 - H4 * H2;
       const double det = H0 * c00 + H1 * c01 + H2 * c02;
-      const double sc = s[9] / (double)(rows - 3);
+      const double sc = s[9] / (double)(S.rows - 3);
       double sg[3] = {sc * (c00 / det), sc * ((H0 * H8 - H2 * H2) / det), sc * ((H0 * H4 - H1 * H1) / det)};
       sigma[0] = sg[0]; sigma[1] = sg[1]; sigma[2] = sg[2];
       if (sg[0] >= 0.0 && sg[1] >= 0.0 && sg[2] >= 0.0) {
@@ -846,80 +1043,33 @@ int reve_solve(ReveCtx& c, const gorio_reve_config* cfg, const ReveFrame& fr, co
         sigma[2] = std::sqrt(sg[2]) + cfg->sigma_offset_radar_z;
       }
     }
-    return 0;
-  };
-  if (m > 2) {
-    GORIO_HIP_CHECK(prep_fail, hipMemcpyAsync(c.d_fv, fv.data(), sizeof(double) * fv.size(), hipMemcpyHostToDevice, c.stream));
-    std::vector<double> vd((size_t)m);
-    for (int k = 0; k < m; ++k) vd[k] = std::fabs(fv[4 * (size_t)k + 3]);
-    const size_t nth = std::min((size_t)((double)m * (1.0 - (double)cfg->allowed_outlier_percentage)), (size_t)m - 1);
-    std::nth_element(vd.begin(), vd.begin() + nth, vd.end());  // REVE:105-108
-    if (vd[nth] < cfg->thresh_zero_velocity) {                 // REVE:110-121
-      if (zero_velocity) *zero_velocity = 1;
-      sigma_v_r[0] = cfg->sigma_zero_velocity_x; sigma_v_r[1] = cfg->sigma_zero_velocity_y; sigma_v_r[2] = cfg->sigma_zero_velocity_z;
-      if (inlier_mask)
-        for (int k = 0; k < m; ++k)
-          if (std::fabs(fv[4 * (size_t)k + 3]) < cfg->thresh_zero_velocity) inlier_mask[vidx[k]] = 1;
-      ok = 1;
-    } else if (!cfg->use_ransac) {
-      std::vector<unsigned char> all((size_t)m, 1);
-      if (solve(all, m, true, v_r, sigma_v_r)) return prep_fail(GORIO_ERR_NO_DEVICE, "ego_velocity: device error");
-      if (inlier_mask) for (int k = 0; k < m; ++k) inlier_mask[vidx[k]] = 1;
-      ok = 1;
-    } else {  // solve3DFullRansac, REVE:172-250
-      std::vector<unsigned char> best_in, best_out;
-      size_t nbi = 0, nbo = 0;
-      const int K = m >= cfg->n_ransac_points ? n_iter : 0;
-      if (K > 0) {
-        if (K > 64) return prep_fail(GORIO_ERR_INVALID, "ego_velocity: more than 64 RANSAC iterations");
-        std::vector<double> vs((size_t)K * 3);
-        for (int k = 0; k < K; ++k) {  // the sample systems are N_ransac_points rows: solved here (3 x 3)
-          double HTH[9] = {0}, HTy[3] = {0};
-          for (int q = 0; q < cfg->n_ransac_points; ++q) {
-            const unsigned int row = sample_idx[(size_t)k * cfg->n_ransac_points + q];
-            if (row >= (unsigned int)m) return prep_fail(GORIO_ERR_INVALID, "ego_velocity: sample index outside the valid targets");
-            const double* r = fv.data() + 4 * (size_t)row;
-            for (int a = 0; a < 3; ++a) {
-              for (int b = 0; b < 3; ++b) HTH[a * 3 + b] += r[a] * r[b];
-              HTy[a] += r[a] * r[3];
-            }
-          }
-          host_ldlt3_solve(HTH, HTy, vs.data() + 3 * (size_t)k);
-        }
-        GORIO_HIP_CHECK(prep_fail, c.d_flags.reserve((size_t)K * m, (size_t)K * m + 1024));
-        GORIO_HIP_CHECK(prep_fail, hipMemcpyAsync(c.d_v, vs.data(), sizeof(double) * vs.size(), hipMemcpyHostToDevice, c.stream));
-        reve_eval_kernel<<<dim3((m + 255) / 256, K), 256, 0, c.stream>>>(c.d_fv, m, c.d_v, (double)cfg->inlier_thresh, c.d_flags);
-        GORIO_HIP_CHECK(prep_fail, hipGetLastError());
-        std::vector<unsigned char> flags((size_t)K * m);
-        GORIO_HIP_CHECK(prep_fail, hipMemcpyAsync(flags.data(), c.d_flags, flags.size(), hipMemcpyDeviceToHost, c.stream));
-        GORIO_HIP_CHECK(prep_fail, hipStreamSynchronize(c.stream));
-        for (int k = 0; k < K; ++k) {
-          const unsigned char* fl = flags.data() + (size_t)k * m;
-          size_t ni = 0;
-          for (int j = 0; j < m; ++j) ni += fl[j];
-          size_t no = (size_t)m - ni;
-          std::vector<unsigned char> cur_in(fl, fl + m), cur_out((size_t)m);
-          for (int j = 0; j < m; ++j) cur_out[j] = !fl[j];
-          if ((float)no / (float)(ni + no) > 0.05) {  // REVE:215-220
-            std::fill(cur_in.begin(), cur_in.end(), 1);
-            std::fill(cur_out.begin(), cur_out.end(), 0);
-            ni = (size_t)m;
-            no = 0;
-          }
-          if (ni > nbi) { best_in = cur_in; nbi = ni; }
-          if (no > nbo) { best_out = cur_out; nbo = no; }
-          v_r[0] = vs[3 * (size_t)k]; v_r[1] = vs[3 * (size_t)k + 1]; v_r[2] = vs[3 * (size_t)k + 2];
-        }
-      }
-      if (nbi > 0) {
-        if (solve(best_in, (int)nbi, true, v_r, sigma_v_r)) return prep_fail(GORIO_ERR_NO_DEVICE, "ego_velocity: device error");
-        ok = 1;  // REVE:301: true whatever the sigma test said
-        if (inlier_mask) for (int j = 0; j < m; ++j) if (best_in[j]) inlier_mask[vidx[j]] = 1;
-      }
-      if (outlier_mask && nbo > 0) for (int j = 0; j < m; ++j) if (best_out[j]) outlier_mask[vidx[j]] = 1;
-    }
+    reve_solve_finish(S, true);
   }
-  if (success) *success = ok;
+  return GORIO_OK;
+}
+
+int reve_solve(ReveCtx& c, const gorio_reve_config* cfg, const ReveFrame& fr, const unsigned int* sample_idx, int n_iter, double v_r[3], double sigma_v_r[3],
+               unsigned char* inlier_mask, unsigned char* outlier_mask, int* zero_velocity, int* success) {
+  ReveSolve S;
+  S.c = &c; S.cfg = cfg; S.fr = &fr; S.sample_idx = sample_idx; S.n_iter = n_iter; S.v_r = v_r; S.sigma_v_r = sigma_v_r;
+  S.inlier_mask = inlier_mask; S.outlier_mask = outlier_mask; S.zero_velocity = zero_velocity;
+  int rc = reve_solve_begin(S);
+  if (rc) return rc;
+  const int m = fr.m, nb = (m + 255) / 256;
+  while (S.want != ReveSolve::DONE) {
+    if (S.want == ReveSolve::EVAL) {
+      reve_eval_kernel<<<dim3(nb, S.K), 256, 0, c.stream>>>(c.d_fv, m, c.d_v, (double)cfg->inlier_thresh, c.d_flags);
+      GORIO_HIP_CHECK(prep_fail, hipGetLastError());
+    } else {
+      reve_sums_kernel<<<nb, 256, 0, c.stream>>>(c.d_fv, m, c.d_valid, S.pass == 1 ? c.d_v.get() : nullptr, c.d_out);
+    }
+    rc = reve_solve_download(S);
+    if (rc) return rc;
+    if (hipStreamSynchronize(c.stream) != hipSuccess) return prep_fail(GORIO_ERR_NO_DEVICE, "ego_velocity: device error");
+    rc = reve_solve_advance(S);
+    if (rc) return rc;
+  }
+  if (success) *success = S.ok;
   return GORIO_OK;
 }
 

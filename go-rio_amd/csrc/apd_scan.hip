@@ -32,9 +32,11 @@ struct GateArgs {
   double R[9];
   float power_threshold;
 };
-__global__ __launch_bounds__(256) void scan_gate_rotate_kernel(float* __restrict__ x, float* __restrict__ y, float* __restrict__ z, const float* __restrict__ power, int n, GateArgs a,
-                                                               unsigned char* __restrict__ keep) {
-  const int i = blockIdx.x * 256 + threadIdx.x;
+// Every kernel of this file is a per-workgroup body, `block` its 256-point block, and a __global__ that hands it blockIdx.x; the job-table
+// kernels of apd_scan_batch.hip hand the same bodies the block of a (job, block) entry.
+__device__ __forceinline__ void scan_gate_rotate_body(float* __restrict__ x, float* __restrict__ y, float* __restrict__ z, const float* __restrict__ power, int n, const GateArgs& a,
+                                                      unsigned char* __restrict__ keep, int block) {
+  const int i = block * 256 + threadIdx.x;
   if (i >= n) return;
   const float fx = x[i], fy = y[i], fz = z[i];
   const bool ok = power[i] > a.power_threshold && isfinite(fx) && isfinite(fy) && isfinite(fz);
@@ -44,6 +46,10 @@ __global__ __launch_bounds__(256) void scan_gate_rotate_kernel(float* __restrict
   x[i] = (float)((a.R[0] * dx + a.R[1] * dy) + a.R[2] * dz);
   y[i] = (float)((a.R[3] * dx + a.R[4] * dy) + a.R[5] * dz);
   z[i] = (float)((a.R[6] * dx + a.R[7] * dy) + a.R[8] * dz);
+}
+__global__ __launch_bounds__(256) void scan_gate_rotate_kernel(float* __restrict__ x, float* __restrict__ y, float* __restrict__ z, const float* __restrict__ power, int n, GateArgs a,
+                                                               unsigned char* __restrict__ keep) {
+  scan_gate_rotate_body(x, y, z, power, n, a, keep, blockIdx.x);
 }
 
 // ---------------------------------------------------------------------------------------------- deskew (PREP:705-716)
@@ -55,8 +61,8 @@ __global__ __launch_bounds__(256) void scan_gate_rotate_kernel(float* __restrict
 //   uv = i.vec x v   (cross: a.y b.z - a.z b.y, a.z b.x - a.x b.z, a.x b.y - a.y b.x);  uv = uv + uv
 //   out = (v + iw * uv) + i.vec x uv                                            Eigen's QuaternionBase::_transformVector
 // intensity, doppler and map pass through.  grid ceil(n / 256), block 256.
-__global__ __launch_bounds__(256) void scan_deskew_kernel(ScanColumns c, int n, double scan_period, float wx, float wy, float wz) {
-  const int i = blockIdx.x * 256 + threadIdx.x;
+__device__ __forceinline__ void scan_deskew_body(const ScanColumns& c, int n, double scan_period, float wx, float wy, float wz, int block) {
+  const int i = block * 256 + threadIdx.x;
   if (i >= n) return;
   const double delta_t = scan_period * (double)i / (double)n;
   const double half = delta_t / 2.0;
@@ -76,39 +82,51 @@ __global__ __launch_bounds__(256) void scan_deskew_kernel(ScanColumns c, int n, 
   c.d[4][i] = c.s[4][i];
   c.dmap[i] = c.smap ? c.smap[i] : i;
 }
+__global__ __launch_bounds__(256) void scan_deskew_kernel(ScanColumns c, int n, double scan_period, float wx, float wy, float wz) {
+  scan_deskew_body(c, n, scan_period, wx, wy, wz, blockIdx.x);
+}
 
 // ---------------------------------------------------------------------------------------------- distance filter (PREP:643-647)
 // d = double(sqrtf((x x + y y) + z z)) (getVector3fMap().norm()), z widened to double; all four inequalities strict.
 struct DistanceArgs {
   double near_, far_, z_low, z_high;
 };
-__global__ __launch_bounds__(256) void scan_distance_kernel(const float* __restrict__ x, const float* __restrict__ y, const float* __restrict__ z, int n, DistanceArgs a,
-                                                            unsigned char* __restrict__ keep) {
-  const int i = blockIdx.x * 256 + threadIdx.x;
+__device__ __forceinline__ void scan_distance_body(const float* __restrict__ x, const float* __restrict__ y, const float* __restrict__ z, int n, const DistanceArgs& a,
+                                                   unsigned char* __restrict__ keep, int block) {
+  const int i = block * 256 + threadIdx.x;
   if (i >= n) return;
   const float fx = x[i], fy = y[i], fz = z[i];
   const double d = (double)sqrtf((fx * fx + fy * fy) + fz * fz), zd = (double)fz;
   keep[i] = (d > a.near_ && d < a.far_ && zd < a.z_high && zd > a.z_low) ? 1 : 0;
+}
+__global__ __launch_bounds__(256) void scan_distance_kernel(const float* __restrict__ x, const float* __restrict__ y, const float* __restrict__ z, int n, DistanceArgs a,
+                                                            unsigned char* __restrict__ keep) {
+  scan_distance_body(x, y, z, n, a, keep, blockIdx.x);
 }
 
 // ---------------------------------------------------------------------------------------------- order-preserving compaction
 // Three launches, no workgroup ever waits for another: (1) per workgroup the number of kept points, from one ballot + popcount per wave;
 // (2) ONE workgroup scans the workgroup counts (exclusive, in place) and leaves the total behind them; (3) every workgroup repeats its
 // ballots and scatters: position = workgroup offset + kept points of the lower waves + kept lanes below this one.
-__global__ __launch_bounds__(256) void compact_count_kernel(const unsigned char* __restrict__ keep, int n, int* __restrict__ bcnt) {
-  const int i = blockIdx.x * 256 + threadIdx.x;
+// `out`: where this workgroup's count goes
+__device__ __forceinline__ void compact_count_body(const unsigned char* __restrict__ keep, int n, int* __restrict__ out, int block) {
+  const int i = block * 256 + threadIdx.x;
   const bool k = i < n && keep[i];
   const unsigned long long b = __ballot(k);
   __shared__ int w[4];
   if ((threadIdx.x & 63) == 0) w[threadIdx.x >> 6] = __popcll(b);
   __syncthreads();
-  if (threadIdx.x == 0) bcnt[blockIdx.x] = (w[0] + w[1]) + (w[2] + w[3]);
+  if (threadIdx.x == 0) *out = (w[0] + w[1]) + (w[2] + w[3]);
+}
+__global__ __launch_bounds__(256) void compact_count_kernel(const unsigned char* __restrict__ keep, int n, int* __restrict__ bcnt) {
+  compact_count_body(keep, n, bcnt + blockIdx.x, blockIdx.x);
 }
 
 // (2) is block_scan_kernel of apd_voxel_group.hip, which the cell groupings share.
 
-__global__ __launch_bounds__(256) void compact_scatter_kernel(ScanColumns c, const unsigned char* __restrict__ keep, int n, const int* __restrict__ boffs) {
-  const int i = blockIdx.x * 256 + threadIdx.x;
+// `boff`: the position of this workgroup's first kept point in the output
+__device__ __forceinline__ void compact_scatter_body(const ScanColumns& c, const unsigned char* __restrict__ keep, int n, int boff, int block) {
+  const int i = block * 256 + threadIdx.x;
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const bool k = i < n && keep[i];
   const unsigned long long b = __ballot(k);
@@ -116,30 +134,37 @@ __global__ __launch_bounds__(256) void compact_scatter_kernel(ScanColumns c, con
   if (lane == 0) w[wave] = __popcll(b);
   __syncthreads();
   if (!k) return;
-  int pos = boffs[blockIdx.x] + __popcll(b & ((1ull << lane) - 1ull));
+  int pos = boff + __popcll(b & ((1ull << lane) - 1ull));
   for (int q = 0; q < wave; ++q) pos += w[q];
 #pragma unroll
   for (int q = 0; q < 5; ++q) c.d[q][pos] = c.s[q][i];
   c.dmap[pos] = c.smap ? c.smap[i] : i;
 }
+__global__ __launch_bounds__(256) void compact_scatter_kernel(ScanColumns c, const unsigned char* __restrict__ keep, int n, const int* __restrict__ boffs) {
+  compact_scatter_body(c, keep, n, boffs[blockIdx.x], blockIdx.x);
+}
 
 // ---------------------------------------------------------------------------------------------- ground + nonground order (PREP:518)
 // out[j] = in[order[j]], every column.  grid ceil(m / 256), block 256; order[j] < the source size (checked on the host before the upload).
-__global__ __launch_bounds__(256) void scan_permute_kernel(ScanColumns c, const int* __restrict__ order, int m) {
-  const int j = blockIdx.x * 256 + threadIdx.x;
+__device__ __forceinline__ void scan_permute_body(const ScanColumns& c, const int* __restrict__ order, int m, int block) {
+  const int j = block * 256 + threadIdx.x;
   if (j >= m) return;
   const int i = order[j];
 #pragma unroll
   for (int q = 0; q < 5; ++q) c.d[q][j] = c.s[q][i];
   c.dmap[j] = c.smap ? c.smap[i] : i;
 }
+__global__ __launch_bounds__(256) void scan_permute_kernel(ScanColumns c, const int* __restrict__ order, int m) { scan_permute_body(c, order, m, blockIdx.x); }
 
 // the labels of the DBSCAN stage into the registration cloud the stage indexed (label column and the w of the packed points)
-__global__ __launch_bounds__(256) void scan_set_labels_kernel(const float* __restrict__ lab, int n, float* __restrict__ label, float4* __restrict__ p4) {
-  const int i = blockIdx.x * 256 + threadIdx.x;
+__device__ __forceinline__ void scan_set_labels_body(const float* __restrict__ lab, int n, float* __restrict__ label, float4* __restrict__ p4, int block) {
+  const int i = block * 256 + threadIdx.x;
   if (i >= n) return;
   label[i] = lab[i];
   p4[i].w = lab[i];
+}
+__global__ __launch_bounds__(256) void scan_set_labels_kernel(const float* __restrict__ lab, int n, float* __restrict__ label, float4* __restrict__ p4) {
+  scan_set_labels_body(lab, n, label, p4, blockIdx.x);
 }
 
 }  // namespace gorio
@@ -163,6 +188,7 @@ struct ScanCloud {
 };
 
 enum { kScanRaw = 0, kScanClouds = 1 + GORIO_SCAN_STAGE_COUNT };  // cloud 0: the upload, gated in place; cloud 1 + s: what stage s put out
+struct ScanBatchLead;  // apd_scan_batch.hip: what the lead handle of a batch holds for it
 }  // namespace
 
 struct gorio_scan {
@@ -186,6 +212,8 @@ struct gorio_scan {
   bool loaded = false, have_output = false;
   int n_out = 0;
   long long point_uploads = 0, index_builds = 0, point_downloads = 0;
+  std::string run_err;                  // the text of the last run when it ended REFUSED, "" otherwise (gorio_scan_handle_error)
+  std::shared_ptr<ScanBatchLead> batch;  // made by the first batch call that names this handle first
 };
 
 namespace {
@@ -377,12 +405,21 @@ int gorio_scan_load(gorio_scan_t* h, const float* xyz, const float* power, const
   return GORIO_OK;
 }
 
+static int scan_run_stages(gorio_scan_t* h, const unsigned int* sample_idx, int n_iter, const double* ang_vel, gorio_scan_result* result);
+
 int gorio_scan_run(gorio_scan_t* h, const unsigned int* sample_idx, int n_iter, const double* ang_vel, gorio_scan_result* result) {
   if (!h || !result) return scan_fail(GORIO_ERR_INVALID, "run: null argument");
   std::memset(result, 0, sizeof(*result));
   result->stage = -1;
   if (n_iter < 0 || (n_iter > 0 && !sample_idx)) return scan_fail(GORIO_ERR_INVALID, "run: bad sample arguments");
   if (!h->loaded) return scan_fail(GORIO_ERR_STATE, "run: no scan loaded (gorio_scan_load comes first, once per run)");
+  h->run_err.clear();
+  const int rc = scan_run_stages(h, sample_idx, n_iter, ang_vel, result);
+  if (result->status == GORIO_SCAN_REFUSED) h->run_err = g_scan_err;
+  return rc;
+}
+
+static int scan_run_stages(gorio_scan_t* h, const unsigned int* sample_idx, int n_iter, const double* ang_vel, gorio_scan_result* result) {
   h->loaded = false;
   h->have_output = false;
   GORIO_HIP_CHECK(scan_fail, hipSetDevice(h->device));
@@ -646,3 +683,5 @@ int gorio_scan_get_counters(const gorio_scan_t* h, long long* point_uploads, lon
 }
 
 }  // extern "C"
+
+#include "apd_scan_batch.hip"

@@ -120,6 +120,64 @@ class ScanPreprocessor {
     return o;
   }
 
+  // process_packed for many sensors (or many recorded messages, one object each) in lock-step rounds on the GPU (include/gorio_scan_batch.h):
+  // message i goes through pre[i].  The RANSAC samples are drawn in member order from the one rng, so the results, last_scan() included,
+  // equal the same process_packed calls made one after another with the same generator.  ang_vel[i] may be null, and so may raw5[i] when
+  // n[i] is 0.  The exception rules are process_packed's: a refused member is a Result with `message` and does not throw.
+  static std::vector<Result> processBatch(const std::vector<ScanPreprocessor*>& pre, const std::vector<const float*>& raw5, const std::vector<int>& n,
+                                          const std::vector<const double*>& ang_vel, std::mt19937& rng) {
+    const std::size_t count = pre.size();
+    if (raw5.size() != count || n.size() != count || ang_vel.size() != count) throw std::invalid_argument("ScanPreprocessor::processBatch: one message, size and angular velocity per object");
+    std::vector<Result> out(count);
+    if (count == 0) return out;
+    std::vector<gorio_scan_t*> hs(count);
+    std::vector<const float*> power(count), doppler(count);
+    std::vector<int> stride(count, 20), n_gated(count, 0), n_valid(count, 0);
+    for (std::size_t i = 0; i < count; ++i) {
+      if (!pre[i]) throw std::invalid_argument("ScanPreprocessor::processBatch: null object");
+      pre[i]->last_.reset();
+      hs[i] = pre[i]->h_;
+      power[i] = raw5[i] ? raw5[i] + 3 : nullptr;
+      doppler[i] = raw5[i] ? raw5[i] + 4 : nullptr;
+    }
+    batch_check(gorio_scan_load_batch(hs.data(), static_cast<int>(count), raw5.data(), power.data(), doppler.data(), n.data(), stride.data(), n_gated.data(), n_valid.data()));
+    std::vector<std::vector<unsigned int>> samples(count);
+    std::vector<const unsigned int*> sample_ptr(count);
+    std::vector<int> n_iter(count);
+    for (std::size_t i = 0; i < count; ++i) {
+      const gorio_scan_params& P = pre[i]->params_;
+      samples[i] = draw_ransac_samples(P.reve, n_valid[i], rng);
+      sample_ptr[i] = samples[i].empty() ? nullptr : samples[i].data();
+      n_iter[i] = static_cast<int>(samples[i].size()) / std::max(P.reve.n_ransac_points, 1);
+    }
+    std::vector<gorio_scan_result> res(count);
+    std::vector<int> codes(count, 0);
+    batch_check(gorio_scan_run_batch(hs.data(), static_cast<int>(count), sample_ptr.data(), n_iter.data(), ang_vel.data(), res.data(), codes.data()));
+    for (std::size_t i = 0; i < count; ++i) {
+      const gorio_scan_result& r = res[i];
+      Result& o = out[i];
+      if (codes[i] < 0 && r.status == GORIO_SCAN_REFUSED) o.message = gorio_scan_handle_error(hs[i]);
+      else if (codes[i] < 0) throw std::runtime_error(std::string("ScanPreprocessor (gorio_amd): member ") + std::to_string(i) + ": " + gorio_scan_handle_error(hs[i]) + " [code " + std::to_string(codes[i]) + "]");
+      o.status = r.status;
+      for (int q = 0; q < 3; ++q) {
+        o.v_r[q] = r.v_r[q];
+        o.sigma_v_r[q] = r.sigma_v_r[q];
+      }
+      o.n_ground = r.n_ground;
+      o.n_clusters = r.n_clusters;
+      if (r.status != GORIO_SCAN_OK) continue;
+      CloudPtr cloud(new Cloud());
+      cloud->resize(r.n_out);
+      if (r.n_out > 0) {
+        PointT& p0 = cloud->points[0];
+        pre[i]->check(gorio_scan_get_output(hs[i], &p0.x, &p0.intensity, &p0.curvature, &p0.normal_x, static_cast<int>(sizeof(PointT)), r.n_out));
+      }
+      o.full_scan = cloud;
+      pre[i]->last_ = cloud;
+    }
+    return out;
+  }
+
   // the cloud of the last process() that produced a frame (null otherwise): what FastAPDGICP::setInputSourceFromScan keeps as input_
   CloudConstPtr last_scan() const { return last_; }
   gorio_scan_t* handle() { return h_; }
@@ -127,6 +185,9 @@ class ScanPreprocessor {
 
  private:
   void check(int rc) const {
+    if (rc < 0) throw std::runtime_error(std::string("ScanPreprocessor (gorio_amd): ") + gorio_scan_last_error() + " [code " + std::to_string(rc) + "]");
+  }
+  static void batch_check(int rc) {
     if (rc < 0) throw std::runtime_error(std::string("ScanPreprocessor (gorio_amd): ") + gorio_scan_last_error() + " [code " + std::to_string(rc) + "]");
   }
   gorio_scan_params params_;

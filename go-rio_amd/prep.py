@@ -145,6 +145,8 @@ def ego_velocity(targets, samples, cfg=None, device=0):
 # ------------------------------------------------------------------------------------------------ include/gorio_scan.h
 SCAN_SYMBOLS = ["gorio_scan_default_params", "gorio_scan_create", "gorio_scan_destroy", "gorio_scan_load", "gorio_scan_run", "gorio_scan_get_output", "gorio_scan_get_stage",
                 "gorio_scan_get_stage_points", "gorio_scan_get_counters", "gorio_scan_last_error", "gorio_apd_set_source_from_scan", "gorio_apd_set_target_from_scan"]
+SCAN_BATCH_SYMBOLS = ["gorio_scan_load_batch", "gorio_scan_run_batch", "gorio_scan_handle_error", "gorio_scan_batch_diag"]  # include/gorio_scan_batch.h
+SCAN_BATCH_MAX = 1024
 OUTLIER_NONE, OUTLIER_STATISTICAL, OUTLIER_RADIUS = 0, 1, 2
 SCAN_OK, SCAN_ZERO_VELOCITY, SCAN_EMPTY, SCAN_REFUSED = 0, 1, 2, 3
 SCAN_STATUS = {0: "ok", 1: "zero_velocity", 2: "empty", 3: "refused"}
@@ -265,3 +267,74 @@ class ScanPipeline:
         u, b, d = C.c_longlong(0), C.c_longlong(0), C.c_longlong(0)
         self._check(self.lib.gorio_scan_get_counters(self.h, C.byref(u), C.byref(b), C.byref(d)))
         return dict(point_uploads=u.value, index_builds=b.value, point_downloads=d.value)
+
+
+# ------------------------------------------------------------------------------------------------ include/gorio_scan_batch.h
+def _result_dict(r, code=0, error=""):
+    return dict(status=SCAN_STATUS.get(r.status, r.status), stage=r.stage, reve_success=bool(r.reve_success), v_r=np.array(r.v_r[:]), sigma_v_r=np.array(r.sigma_v_r[:]),
+                n_out=r.n_out, n_ground=r.n_ground, n_clusters=r.n_clusters, code=code, error=error)
+
+
+def _batch_check(lib, rc):
+    if rc < 0:
+        lib.gorio_scan_last_error.restype = C.c_char_p
+        msg = lib.gorio_scan_last_error()
+        raise GorioError(rc, msg.decode() if msg else "")
+
+
+def scan_load_batch(pipes, raws):
+    """gorio_scan_load_batch: pipes[i].load(raws[i]) for every member in two rounds.  Returns (n_gated [count], n_valid [count])."""
+    if len(pipes) != len(raws):
+        raise ValueError("one raw scan per pipeline")
+    count = len(pipes)
+    if count == 0:
+        return np.zeros(0, np.int32), np.zeros(0, np.int32)
+    lib = pipes[0].lib
+    ts = [np.ascontiguousarray(r, np.float32).reshape(-1, 5) for r in raws]
+    base = [t.__array_interface__["data"][0] for t in ts]
+    hs = (C.c_void_p * count)(*[p.h for p in pipes])
+    xyz = (C.c_void_p * count)(*[b if len(t) else None for b, t in zip(base, ts)])
+    pw = (C.c_void_p * count)(*[b + 12 if len(t) else None for b, t in zip(base, ts)])
+    dop = (C.c_void_p * count)(*[b + 16 if len(t) else None for b, t in zip(base, ts)])
+    n = (C.c_int * count)(*[len(t) for t in ts])
+    st = (C.c_int * count)(*([20] * count))
+    ng, nv = (C.c_int * count)(), (C.c_int * count)()
+    _batch_check(lib, lib.gorio_scan_load_batch(hs, count, xyz, pw, dop, n, st, ng, nv))
+    return np.array(ng[:], np.int32), np.array(nv[:], np.int32)
+
+
+def scan_run_batch(pipes, samples, ang_vels):
+    """gorio_scan_run_batch: pipes[i].run(samples[i], ang_vels[i]) for every member in lock-step rounds.  A member's refusal does not raise:
+    its dict carries `code` (what the single run would have returned) and `error` (its text).  Sets every pipe.last_result."""
+    if len(pipes) != len(samples) or len(pipes) != len(ang_vels):
+        raise ValueError("one sample set and one angular velocity (or None) per pipeline")
+    count = len(pipes)
+    if count == 0:
+        return []
+    lib = pipes[0].lib
+    lib.gorio_scan_handle_error.restype = C.c_char_p
+    ss = []
+    for p, s in zip(pipes, samples):
+        k = p.params.reve.n_ransac_points
+        ss.append(np.ascontiguousarray(s, np.uint32).reshape(-1, k) if len(s) else np.zeros((0, k), np.uint32))
+    ws = [None if w is None else (C.c_double * 3)(*[float(x) for x in w]) for w in ang_vels]
+    hs = (C.c_void_p * count)(*[p.h for p in pipes])
+    sp = (C.c_void_p * count)(*[s.__array_interface__["data"][0] if s.shape[0] else None for s in ss])
+    ni = (C.c_int * count)(*[s.shape[0] for s in ss])
+    wp = (C.c_void_p * count)(*[None if w is None else C.addressof(w) for w in ws])
+    res = (ScanResult * count)()
+    codes = (C.c_int * count)()
+    _batch_check(lib, lib.gorio_scan_run_batch(hs, count, sp, ni, wp, res, codes))
+    out = []
+    for i, p in enumerate(pipes):
+        msg = lib.gorio_scan_handle_error(p.h)
+        p.last_result = _result_dict(res[i], codes[i], msg.decode() if msg else "")
+        out.append(p.last_result)
+    return out
+
+
+def scan_batch_diag(lead):
+    """Shape of the last batch call whose first pipeline was `lead`: dict(rounds, launches, synchronisations)."""
+    r, l, s = C.c_int(0), C.c_int(0), C.c_int(0)
+    _batch_check(lead.lib, lead.lib.gorio_scan_batch_diag(lead.h, C.byref(r), C.byref(l), C.byref(s)))
+    return dict(rounds=r.value, launches=l.value, synchronisations=s.value)

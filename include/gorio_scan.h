@@ -160,4 +160,8 @@ const char* gorio_scan_last_error(void);
 #ifdef __cplusplus
 }
 #endif
+
+/* the batched section: N scans through the same stages in lock-step rounds (an extension, not in the reference) */
+#include "gorio_scan_batch.h"
+
 #endif /* GORIO_SCAN_H */
