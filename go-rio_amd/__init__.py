@@ -33,7 +33,7 @@ from .apd import ApdGicp, ApdParams, DeviceInputs, GorioError, align_batch, fitn
 from . import prep  # noqa: E402
 from . import ground  # noqa: E402
 from . import scan_context  # noqa: E402
-from .scan_context import SC_PAIRS_SYMBOLS, SC_SYMBOLS, ScanContext  # noqa: E402
+from .scan_context import SC_CROSS_SYMBOLS, SC_PAIRS_SYMBOLS, SC_SYMBOLS, ScanContext  # noqa: E402
 from . import ndt  # noqa: E402
 from .ndt import NDT_SYMBOLS, Ndt, NdtBatchStats  # noqa: E402
 from . import keyframes  # noqa: E402

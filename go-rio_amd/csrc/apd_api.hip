@@ -44,6 +44,7 @@
 #include "../../include/gorio_sc.h"
 #include "apd_sc.hip"
 #include "apd_sc_pairs.hip"
+#include "apd_sc_cross.hip"
 #include "../../include/gorio_ndt.h"
 #include "apd_ndt.hip"
 

@@ -364,6 +364,8 @@ struct gorio_sc {
   // include/gorio_sc_pairs.h (apd_sc_pairs.hip): the upload, the device results, and the cumulative counters
   gorio::DevBuf<void> d_px_in, d_px_out;
   long long px_calls = 0, px_pairs = 0, px_launches = 0, px_syncs = 0;
+  // include/gorio_sc_cross.h (apd_sc_cross.hip): the counters of the calls this handle made as the query handle; they share d_px_in / d_px_out
+  long long cx_calls = 0, cx_pairs = 0, cx_launches = 0, cx_syncs = 0;
 };
 
 namespace {

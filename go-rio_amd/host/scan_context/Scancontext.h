@@ -4,7 +4,8 @@
 // callers that read them.  makeScancontext(cloud) goes through a second, private database.  The helpers that take caller-given
 // matrices (make*Key, fastAlignUsingVkey, distDirectSC, distanceBtnScanContext) are O(800) and run here in the library's index
 // order.  Without nanoflann there is no InvKeyTree: the snapshot lives in the library, polarcontext_invkeys_to_search_ mirrors it.
-// distanceBtnScanContextBatch, distanceMatrix, bestMatches and detectLoopClosureIDExhaustive are extensions (include/gorio_sc_pairs.h).
+// distanceBtnScanContextBatch, distanceMatrix, bestMatches and detectLoopClosureIDExhaustive are extensions (include/gorio_sc_pairs.h),
+// as are their forms that take a second SCManager, topMatches and detectLoopClosureIDAgainst (include/gorio_sc_cross.h).
 #pragma once
 #include <algorithm>
 #include <cmath>
@@ -229,6 +230,52 @@ class SCManager {
     return {loop_id, yaw};
   }
 
+  // ---- Matching against ANOTHER SCManager, and the K best per keyframe (include/gorio_sc_cross.h).  An EXTENSION as well: the
+  // reference holds one SCManager per run.  This manager is the query side (the first, unshifted argument of distanceBtnScanContext),
+  // `db` the database side, which is only read (`db` may be *this); SC_DIST_THRES is this manager's.  Both need the same azimuth range.
+  // distanceBtnScanContext(polarcontexts_[first], db.polarcontexts_[second]) for every listed pair, in one launch
+  std::vector<std::pair<double, int>> distanceBtnScanContextBatch(const SCManager& db, const std::vector<std::pair<int, int>>& pairs) {
+    std::vector<int> q, c;
+    for (auto& p : pairs) q.push_back(p.first), c.push_back(p.second);
+    std::vector<double> d(pairs.size());
+    std::vector<int> s(pairs.size());
+    check(gorio_sc_cross_distance_pairs(h_, db.h_, q.data(), c.data(), (int)pairs.size(), d.data(), s.data()), "distanceBtnScanContextBatch");
+    std::vector<std::pair<double, int>> out;
+    for (size_t k = 0; k < pairs.size(); ++k) out.emplace_back(d[k], s[k]);
+    return out;
+  }
+  // every (row of this manager, column of db) pair, row-major: dist / shift [rows.size() * cols.size()]
+  void distanceMatrix(const SCManager& db, const std::vector<int>& rows, const std::vector<int>& cols, std::vector<double>& dist, std::vector<int>& shift) {
+    dist.assign(rows.size() * cols.size(), 0.0);
+    shift.assign(rows.size() * cols.size(), 0);
+    check(gorio_sc_cross_distance_matrix(h_, rows.data(), (int)rows.size(), db.h_, cols.data(), (int)cols.size(), dist.data(), shift.data()), "distanceMatrix");
+  }
+  // per listed keyframe rows[i] its (up to) k best among db's keyframes 0 .. col_end[i] - 1 (col_end empty: all of db), ascending in
+  // (dist, index), the matrix never materialised; fewer than k entries where fewer score below 1e7
+  std::vector<std::vector<BestMatch>> topMatches(const SCManager& db, const std::vector<int>& rows, const std::vector<int>& col_end, int k) {
+    if (!col_end.empty() && col_end.size() != rows.size()) throw std::logic_error("SCManager::topMatches: one col_end per row");
+    return top(db, rows.data(), (int)rows.size(), col_end.empty() ? nullptr : col_end.data(), k);
+  }
+  // the same-database triangle: every keyframe r against the keyframes 0 .. r - min_gap
+  std::vector<std::vector<BestMatch>> topMatches(int k, int min_gap) {
+    if (min_gap < 1) throw std::logic_error("SCManager::topMatches: min_gap must be >= 1");
+    std::vector<int> col_end(polarcontexts_.size());
+    for (size_t r = 0; r < col_end.size(); ++r) col_end[r] = std::max(0, (int)r - min_gap + 1);
+    return top(*this, nullptr, (int)col_end.size(), col_end.data(), k);
+  }
+  // detectLoopClosureID's decision over the listed keyframes of db, every one scored, in list order: (loop id or -1, yaw).  No early
+  // return and no recent-keyframe filter: the indices of two sessions are unrelated.
+  std::pair<int, float> detectLoopClosureIDAgainst(const SCManager& db, const std::vector<int>& candidate_indices, int query_index, double* min_dist_out = nullptr) {
+    const int n = (int)candidate_indices.size();
+    const int* list = candidate_indices.data();
+    int loop_id = -1;
+    float yaw = 0.0f;
+    double min_dist = 0.0;
+    check(gorio_sc_cross_detect(h_, db.h_, 1, &query_index, &list, &n, &loop_id, &yaw, &min_dist), "detectLoopClosureIDAgainst");
+    if (min_dist_out) *min_dist_out = min_dist;
+    return {loop_id, yaw};
+  }
+
   const Eigen::MatrixXd& getConstRefRecentSCD(void) { return polarcontexts_.back(); }
 
  public:
@@ -269,6 +316,16 @@ class SCManager {
     check(gorio_sc_best_matches(h_, rows, n_rows, min_gap, idx.data(), dist.data(), shift.data()), "bestMatches");
     std::vector<BestMatch> out(n_rows);
     for (int i = 0; i < n_rows; ++i) out[i] = BestMatch{idx[i], dist[i], shift[i]};
+    return out;
+  }
+  std::vector<std::vector<BestMatch>> top(const SCManager& db, const int* rows, int n_rows, const int* col_end, int k) {
+    const size_t slots = (size_t)n_rows * (size_t)std::max(k, 0);
+    std::vector<int> idx(slots), shift(slots);
+    std::vector<double> dist(slots);
+    check(gorio_sc_cross_top_matches(h_, rows, n_rows, db.h_, col_end, k, idx.data(), dist.data(), shift.data()), "topMatches");
+    std::vector<std::vector<BestMatch>> out(n_rows);
+    for (int i = 0; i < n_rows; ++i)
+      for (int j = 0; j < k && idx[(size_t)i * k + j] >= 0; ++j) out[i].push_back(BestMatch{idx[(size_t)i * k + j], dist[(size_t)i * k + j], shift[(size_t)i * k + j]});
     return out;
   }
   static void open(gorio_sc_t*& h, const gorio_sc_params& p) { check(gorio_sc_create(&h, 0, &p), "SCManager"); }

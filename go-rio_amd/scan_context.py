@@ -10,6 +10,9 @@ SC_SYMBOLS = ["gorio_sc_add_scans", "gorio_sc_create", "gorio_sc_default_params"
               "gorio_sc_distance", "gorio_sc_get_descriptor", "gorio_sc_get_state", "gorio_sc_last_error"]
 # include/gorio_sc_pairs.h, the exhaustive section (an extension: listed pairs, matrices, best matches, detect without the tree)
 SC_PAIRS_SYMBOLS = ["gorio_sc_best_matches", "gorio_sc_detect_exhaustive", "gorio_sc_distance_matrix", "gorio_sc_distance_pairs", "gorio_sc_pairs_counters"]
+# include/gorio_sc_cross.h, the cross-database section (an extension as well: the same calls between two handles, the K best per keyframe)
+SC_CROSS_SYMBOLS = ["gorio_sc_cross_counters", "gorio_sc_cross_detect", "gorio_sc_cross_distance_matrix", "gorio_sc_cross_distance_pairs", "gorio_sc_cross_top_matches"]
+TOP_MAX = 8  # GORIO_SC_TOP_MAX
 RINGS, SECTORS = 40, 20
 EXCLUDE_RECENT = 10  # GORIO_SC_EXCLUDE_RECENT
 TILE_ROWS, TILE_COLS, PAIRS_PER_GROUP = 8, 8, 4  # GORIO_SC_TILE_ROWS, GORIO_SC_TILE_COLS, GORIO_SC_PAIRS_PER_GROUP
@@ -200,4 +203,62 @@ class ScanContext:
     def pairs_counters(self):
         v = [C.c_longlong() for _ in range(4)]
         self._check(self.lib.gorio_sc_pairs_counters(self.h, *[C.byref(x) for x in v]))
+        return dict(zip(("calls", "pairs", "launches", "synchronisations"), [x.value for x in v]))
+
+    # ---- include/gorio_sc_cross.h: this handle is the query side, `other` the database side (only read); every value has the bits
+    # distance() gives on a handle that holds both descriptors
+    def cross_distance_pairs(self, other, q, c):
+        """d(self[q[k]], other[c[k]]) for listed pairs in one launch -> (dist [count] float64, shift [count] int32)."""
+        q = np.ascontiguousarray(q, np.int32).reshape(-1)
+        c = np.ascontiguousarray(c, np.int32).reshape(-1)
+        if q.size != c.size:
+            raise ValueError("cross_distance_pairs: q and c differ in length")
+        dist, shift = np.zeros(q.size, np.float64), np.zeros(q.size, np.int32)
+        self._check(self.lib.gorio_sc_cross_distance_pairs(self.h, other.h, _ptr(q), _ptr(c), int(q.size), _ptr(dist), _ptr(shift)))
+        return dist, shift
+
+    def cross_distance_matrix(self, other, rows=None, cols=None, want_dist=True, want_shift=True):
+        """d(self[rows[i]], other[cols[j]]) for every pair -> (dist [n_rows, n_cols] float64, shift int32); None for rows means every scan
+        of this handle, for cols every scan of `other`; an output not wanted comes back as None."""
+        r, nr = self._indices(rows)
+        c, nc = other._indices(cols)
+        dist = np.zeros((nr, nc), np.float64) if want_dist else None
+        shift = np.zeros((nr, nc), np.int32) if want_shift else None
+        self._check(self.lib.gorio_sc_cross_distance_matrix(self.h, None if r is None else _ptr(r), nr, other.h, None if c is None else _ptr(c), nc,
+                                                            None if dist is None else _ptr(dist), None if shift is None else _ptr(shift)))
+        return dist, shift
+
+    def top_matches(self, other=None, rows=None, col_end=None, k=3):
+        """Per row r of this handle the k best of d(r, c) over the scans 0 <= c < col_end[i] of `other` (None: this handle itself; col_end
+        None: every scan), ascending in (dist, index) -> (index [n, k] int32, dist [n, k] float64, shift [n, k] int32); slots beyond what
+        scores below 1e7 hold (-1, 1e7, 0)."""
+        other = self if other is None else other
+        r, nr = self._indices(rows)
+        e = None if col_end is None else np.ascontiguousarray(col_end, np.int32).reshape(-1)
+        if e is not None and e.size != nr:
+            raise ValueError("top_matches: one col_end per row")
+        k = int(k)
+        kk = max(k, 0)
+        idx, dist, shift = np.zeros((nr, kk), np.int32), np.zeros((nr, kk), np.float64), np.zeros((nr, kk), np.int32)
+        self._check(self.lib.gorio_sc_cross_top_matches(self.h, None if r is None else _ptr(r), nr, other.h, None if e is None else _ptr(e), k, _ptr(idx), _ptr(dist),
+                                                        _ptr(shift)))
+        return idx, dist, shift
+
+    def cross_detect(self, other, query_indices, candidate_lists):
+        """For every query of this handle the strict minimum of d(query, c) over its list of `other`'s scans, in list order, with this
+        handle's threshold -> list of (loop_id, yaw_rad (float32), min_dist).  No early return, no recent-keyframe filter."""
+        k = len(query_indices)
+        cands = [np.ascontiguousarray(c, np.int32).reshape(-1) for c in candidate_lists]
+        if len(cands) != k:
+            raise ValueError("cross_detect: one candidate list per query")
+        Q = (C.c_int * k)(*[int(q) for q in query_indices])
+        P = (C.c_void_p * k)(*[c.__array_interface__["data"][0] if c.size else None for c in cands])
+        N = (C.c_int * k)(*[c.size for c in cands])
+        lid, yaw, md = (C.c_int * k)(), (C.c_float * k)(), (C.c_double * k)()
+        self._check(self.lib.gorio_sc_cross_detect(self.h, other.h, k, Q, P, N, lid, yaw, md))
+        return [(lid[i], np.float32(yaw[i]), md[i]) for i in range(k)]
+
+    def cross_counters(self):
+        v = [C.c_longlong() for _ in range(4)]
+        self._check(self.lib.gorio_sc_cross_counters(self.h, *[C.byref(x) for x in v]))
         return dict(zip(("calls", "pairs", "launches", "synchronisations"), [x.value for x in v]))

@@ -115,5 +115,7 @@ const char* gorio_sc_last_error(void);
 
 /* the exhaustive section: listed pairs, matrices, best matches and the detect without the tree (an extension, not in the reference) */
 #include "gorio_sc_pairs.h"
+/* the cross-database section: the same calls between two handles, and the K best matches per keyframe (an extension as well) */
+#include "gorio_sc_cross.h"
 
 #endif /* GORIO_SC_H */
