@@ -361,11 +361,12 @@ struct gorio_sc {
   gorio::DevBuf<gorio::ScHit> d_partial;
   gorio::DevBuf<gorio::ScOut> d_out;
   gorio::DevBuf<void> d_kfjobs;  // gorio_sc_add_keyframes (apd_keyframes.hip): the pack kernel's job table
-  // include/gorio_sc_pairs.h (apd_sc_pairs.hip): the upload, the device results, and the cumulative counters
+  // include/gorio_sc_pairs.h and include/gorio_sc_cross.h (apd_sc_pairs.hip, apd_sc_cross.hip): the upload and the device results of
+  // either header's calls, and one group of cumulative counters each (cx: the calls this handle made as the query handle)
   gorio::DevBuf<void> d_px_in, d_px_out;
-  long long px_calls = 0, px_pairs = 0, px_launches = 0, px_syncs = 0;
-  // include/gorio_sc_cross.h (apd_sc_cross.hip): the counters of the calls this handle made as the query handle; they share d_px_in / d_px_out
-  long long cx_calls = 0, cx_pairs = 0, cx_launches = 0, cx_syncs = 0;
+  struct Counters {
+    long long calls = 0, pairs = 0, launches = 0, syncs = 0;
+  } px, cx;
 };
 
 namespace {

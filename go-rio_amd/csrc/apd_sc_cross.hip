@@ -1,12 +1,9 @@
-// apd_sc_cross.hip -- Scan Context matching between two databases (include/gorio_sc_cross.h): listed pairs, whole matrices, the K best
-// matches per row and a detect over lists, each with the query side read from one handle and the database side from another.  Included by
-// apd_api.hip after apd_sc_pairs.hip, whose records, staging, row minimum and host helpers it uses.  An extension, like apd_sc_pairs.hip.
+// apd_sc_cross.hip -- what Scan Context matching between two databases (include/gorio_sc_cross.h) has of its own: the K best matches
+// per row, the check on a pair of handles, and the header's entry points.  Its listed pairs, matrices and detect are the two-handle
+// forms of apd_sc_pairs.hip's host paths and run that file's kernels.  Included by apd_api.hip after apd_sc_pairs.hip, whose records,
+// staging, tile shape and host helpers it uses.  An extension, like apd_sc_pairs.hip.
 //
-//   listed pairs     sc_xpairs_kernel   sc_pairs_kernel with the two sides in two databases (gorio_sc_cross_distance_pairs,
-//                                       gorio_sc_cross_detect, the latter followed by sc_rowmin_kernel)
-//   matrix tiles     sc_xtile_kernel    the matrix form of sc_tile_kernel, row records staged from Q and column records from D
-//                                       (gorio_sc_cross_distance_matrix)
-//   K-best tiles     sc_top_kernel      the folding form of its own: a workgroup walks a run of column tiles and every wave keeps the k
+//   K-best tiles     sc_top_kernel      the folding walk with a list: a workgroup walks a run of column tiles and every wave keeps the k
 //                                       best (dist, column) of its row across its lanes 0 .. k - 1 (gorio_sc_cross_top_matches)
 //   K row minimum    sc_rowtop_kernel   one wave per row: the k smallest (dist, column) keys of the runs' partial lists
 // Every distance comes out of sc_pair_eval, so it has the bits gorio_sc_distance gives.  No floating-point atomics, no waits between
@@ -20,58 +17,6 @@ namespace gorio {
 constexpr int kScTopMax = GORIO_SC_TOP_MAX;
 static_assert(kScTopMax <= 64 && kScTopMax * 2 == 16, "a wave keeps its list in its first lanes; the merge of a row's two lists indexes 16 slots");
 
-// sc_pairs_kernel with the query side in dq and the candidate side in dd.
-__global__ __launch_bounds__(kScThreads) void sc_xpairs_kernel(const ScPairRef* __restrict__ pairs, int n_pairs, ScDb dq, ScDb dd, ScBest* __restrict__ out) {
-  __shared__ ScPairScratch scratch[kScThreads / 64];
-  const int t = threadIdx.x, lane = t & 63, w = t >> 6;
-  const long long pair = (long long)blockIdx.x * (kScThreads / 64) + w;
-  const bool live = pair < n_pairs;
-  const ScPairRef P = live ? pairs[pair] : ScPairRef{0, 0};
-  const size_t q = P.q, c = P.c;
-  double m = 0.0;
-  int arg = 0;
-  sc_pair_eval(live, lane, scratch[w], dq.sector + q * kScSectors, dd.sector + c * kScSectors, dq.colnorm + q * kScSectors, dd.colnorm + c * kScSectors,
-               dq.desc + q * kScBins, dd.desc + c * kScBins, m, arg);
-  if (live && lane == 0) out[pair] = ScBest{m, P.c, arg};
-}
-
-// The matrix form of sc_tile_kernel (its shape, its staging, its wave-to-pair map) with the row records staged from dq and the column
-// records from dd; one column tile per workgroup (A.run_tiles, A.min_gap and A.partial are not read).
-//   LDS 122,304 B static, 65 VGPRs, scratch 0, no spills, 4 waves per SIMD (hipcc -Rpass-analysis=kernel-resource-usage); LDS traffic is
-//   ds_read / ds_write only.  One column tile per workgroup, so both index lists are filled before one barrier and both record sets
-//   staged before the next.
-__global__ __launch_bounds__(kScTileThreads) void sc_xtile_kernel(ScTileArgs A, ScDb dq, ScDb dd) {
-  __shared__ __attribute__((aligned(16))) double rec[(kScTileR + kScTileC) * kScRecord];
-  __shared__ ScPairScratch scratch[kScTileWaves];
-  __shared__ int ridx[kScTileR], cidx[kScTileC];
-  const int t = threadIdx.x, lane = t & 63, w = t >> 6;
-  const int tr = blockIdx.x / A.n_ctiles, tc = blockIdx.x % A.n_ctiles;
-  const int r0 = tr * kScTileR, nr = min(kScTileR, A.n_rows - r0);
-  const int c0 = tc * kScTileC, nc = min(kScTileC, A.n_cols - c0);
-  if (t < nr) ridx[t] = A.rows ? A.rows[r0 + t] : r0 + t;
-  if (t >= 64 && t - 64 < nc) cidx[t - 64] = A.cols ? A.cols[c0 + t - 64] : c0 + t - 64;
-  __syncthreads();
-  sc_stage_records(rec, ridx, nr, dq, t);
-  sc_stage_records(rec + kScTileR * kScRecord, cidx, nc, dd, t);
-  __syncthreads();
-  const int ri = w >> 1, cbase = (w & 1) * kScPairsPerWave;
-  const double* R = rec + ri * kScRecord;
-#pragma unroll 1
-  for (int i = 0; i < kScPairsPerWave; ++i) {
-    const int ci = cbase + i;
-    const bool live = ri < nr && ci < nc;
-    const double* C = rec + (kScTileR + ci) * kScRecord;
-    double m = 0.0;
-    int arg = 0;
-    sc_pair_eval(live, lane, scratch[w], R + kScBins, C + kScBins, R + kScBins + kScSectors, C + kScBins + kScSectors, R, C, m, arg);
-    if (live && lane == 0) {
-      const size_t o = (size_t)(r0 + ri) * A.n_cols + (c0 + ci);
-      if (A.dist) A.dist[o] = m;
-      if (A.shift) A.shift[o] = arg;
-    }
-  }
-}
-
 struct ScTopArgs {
   const int* rows;     // query index of row i, or null: i
   const int* col_end;  // row i takes the columns 0 .. col_end[i] - 1, or null: n_cols for every row
@@ -83,8 +28,8 @@ struct ScTopArgs {
   ScBest* partial;     // [n_rows][n_runs][k], each list ascending in (d, c), unused slots {1e7, -1, 0}
 };
 
-// The K-best form of the tile kernel: sc_tile_kernel<true>'s walk over a run of column tiles, with a list of the k best instead of one
-// running best.  The list of a wave lies ACROSS its lanes, lane j < k holding the j-th smallest (d, c) key of the wave's row so far in
+// The K-best form of the folding kernel: sc_tile_kernel's walk over a run of column tiles, between two databases and with a list of the
+// k best instead of one running best.  The list of a wave lies ACROSS its lanes, lane j < k holding the j-th smallest (d, c) key of the wave's row so far in
 // three scalars of its own (kd, kc, ks; c = -1: unused, and unused slots come last).  A new pair (m, c) is inserted by ballot: its
 // position is the number of lanes whose key is smaller, the lanes behind it take their left neighbour's entry (one __shfl_up each for
 // d, c and s) and the lane at the position takes the pair; what falls off lane k - 1 lands in lanes that are never read.  Nothing is
@@ -92,7 +37,7 @@ struct ScTopArgs {
 // so the order in which pairs arrive does not matter.
 // At the end every wave writes its list to LDS, and the 16 slots of a row's two waves (which saw interleaved column groups) are merged
 // by rank: a slot's position in the output is the number of the row's keys below its own.
-//   LDS 124,384 B static (the matrix form's 122,304 B + 16 lists of 8 x 16 B + the rows' col_end), 100 VGPRs, scratch 0, no spills,
+//   LDS 124,384 B static (the matrix kernel's 122,304 B + 16 lists of 8 x 16 B + the rows' col_end), 100 VGPRs, scratch 0, no spills,
 //   4 waves per SIMD (hipcc -Rpass-analysis=kernel-resource-usage); no flat access to LDS.  The two outer loops stay rolled, as in
 //   sc_tile_kernel.
 __global__ __launch_bounds__(kScTileThreads) void sc_top_kernel(ScTopArgs A, ScDb dq, ScDb dd) {
@@ -227,11 +172,12 @@ __global__ __launch_bounds__(kScThreads) void sc_rowtop_kernel(const ScBest* __r
 
 }  // namespace gorio
 
+
 // ================================================================================================= host (include/gorio_sc_cross.h)
 namespace {
 
 // The checks on the pair of handles that every call of the header starts with.
-int scc_check_handles(const gorio_sc* Q, const gorio_sc* D, const char* fn) {
+int sc_check_handles(const gorio_sc* Q, const gorio_sc* D, const char* fn) {
   if (!Q || !D) return sc_fail(GORIO_ERR_INVALID, std::string(fn) + ": null " + (!Q ? "query" : "database") + " handle");
   if (Q->device != D->device)
     return sc_fail(GORIO_ERR_INVALID, std::string(fn) + ": the query handle is on device " + std::to_string(Q->device) + ", the database handle on device " + std::to_string(D->device));
@@ -241,114 +187,35 @@ int scc_check_handles(const gorio_sc* Q, const gorio_sc* D, const char* fn) {
   return GORIO_OK;
 }
 
-int scc_not_added(const char* fn, const std::string& what, int value, bool query_side, int n) {
-  return sc_fail(GORIO_ERR_INVALID, std::string(fn) + ": " + what + " = " + std::to_string(value) + " has not been added to the " + (query_side ? "query" : "database") + " handle (" +
-                                        std::to_string(n) + " scans)");
-}
-
-// rows / cols of the matrix calls on one side: null means 0 .. n - 1 of that side's handle, so the extent must be its scan count.
-int scc_check_indices(const gorio_sc* h, bool query_side, const char* fn, const char* what, const int* idx, int n) {
-  if (!idx) {
-    if (n != h->n)
-      return sc_fail(GORIO_ERR_INVALID, std::string(fn) + ": null " + what + " means all " + std::to_string(h->n) + " scans of the " + (query_side ? "query" : "database") +
-                                            " handle, but the extent is " + std::to_string(n));
-    return GORIO_OK;
-  }
-  for (int i = 0; i < n; ++i)
-    if (idx[i] < 0 || idx[i] >= h->n) return scc_not_added(fn, std::string(what) + "[" + std::to_string(i) + "]", idx[i], query_side, h->n);
-  return GORIO_OK;
-}
-
-void scc_count(gorio_sc* Q, long long pairs, int launches) {
-  Q->cx_calls += 1;
-  Q->cx_pairs += pairs;
-  Q->cx_launches += launches;
-  Q->cx_syncs += 1;
-}
-
 }  // namespace
 
 extern "C" {
 
 int gorio_sc_cross_distance_pairs(gorio_sc_t* Q, gorio_sc_t* D, const int* q, const int* c, int count, double* dist, int* shift) {
-  if (scc_check_handles(Q, D, "cross_distance_pairs")) return GORIO_ERR_INVALID;
-  if (count < 0) return sc_fail(GORIO_ERR_INVALID, "cross_distance_pairs: count < 0");
-  if (count == 0) return GORIO_OK;
-  if (!q || !c || !dist || !shift) return sc_fail(GORIO_ERR_INVALID, "cross_distance_pairs: null argument");
-  for (int k = 0; k < count; ++k) {
-    if (q[k] < 0 || q[k] >= Q->n) return scc_not_added("cross_distance_pairs", "q[" + std::to_string(k) + "]", q[k], true, Q->n);
-    if (c[k] < 0 || c[k] >= D->n) return scc_not_added("cross_distance_pairs", "c[" + std::to_string(k) + "]", c[k], false, D->n);
-  }
-  std::vector<gorio::ScPairRef> tab(count);
-  for (int k = 0; k < count; ++k) tab[k] = gorio::ScPairRef{q[k], c[k]};
-  std::vector<gorio::ScBest> res(count);
-  GORIO_HIP_CHECK(sc_fail, hipSetDevice(Q->device));
-  if (scx_reserve(Q, sizeof(gorio::ScPairRef) * tab.size(), sizeof(gorio::ScBest) * res.size())) return GORIO_ERR_ALLOC;
-  GORIO_HIP_CHECK(sc_fail, hipMemcpyAsync(Q->d_px_in, tab.data(), sizeof(gorio::ScPairRef) * tab.size(), hipMemcpyHostToDevice, Q->stream));
-  hipLaunchKernelGGL(gorio::sc_xpairs_kernel, dim3((unsigned)(((long long)count + 3) / 4)), dim3(gorio::kScThreads), 0, Q->stream, (const gorio::ScPairRef*)Q->d_px_in.get(), count, Q->db(),
-                     D->db(), (gorio::ScBest*)Q->d_px_out.get());
-  GORIO_HIP_CHECK(sc_fail, hipGetLastError());
-  GORIO_HIP_CHECK(sc_fail, hipMemcpyAsync(res.data(), Q->d_px_out, sizeof(gorio::ScBest) * res.size(), hipMemcpyDeviceToHost, Q->stream));
-  GORIO_HIP_CHECK(sc_fail, hipStreamSynchronize(Q->stream));
-  scc_count(Q, count, 1);
-  for (int k = 0; k < count; ++k) {
-    dist[k] = res[k].d;
-    shift[k] = res[k].s;
-  }
-  return GORIO_OK;
+  if (sc_check_handles(Q, D, "cross_distance_pairs")) return GORIO_ERR_INVALID;
+  return sc_distance_pairs(sc_two_handles(Q, D, "cross_distance_pairs"), q, c, count, dist, shift);
 }
 
 int gorio_sc_cross_distance_matrix(gorio_sc_t* Q, const int* rows, int n_rows, gorio_sc_t* D, const int* cols, int n_cols, double* dist, int* shift) {
-  if (scc_check_handles(Q, D, "cross_distance_matrix")) return GORIO_ERR_INVALID;
-  if (n_rows < 0 || n_cols < 0) return sc_fail(GORIO_ERR_INVALID, "cross_distance_matrix: negative extent");
-  if (n_rows == 0 || n_cols == 0) return GORIO_OK;
-  if (!dist && !shift) return sc_fail(GORIO_ERR_INVALID, "cross_distance_matrix: both outputs are null");
-  if (scc_check_indices(Q, true, "cross_distance_matrix", "rows", rows, n_rows) || scc_check_indices(D, false, "cross_distance_matrix", "cols", cols, n_cols)) return GORIO_ERR_INVALID;
-  const long long total = (long long)n_rows * n_cols;
-  if (total > (long long)INT_MAX)
-    return sc_fail(GORIO_ERR_UNSUPPORTED, "cross_distance_matrix: " + std::to_string(n_rows) + " x " + std::to_string(n_cols) + " pairs exceed 2^31 - 1");
-  const size_t b_rows = rows ? scx_align16(sizeof(int) * n_rows) : 0, b_cols = cols ? scx_align16(sizeof(int) * n_cols) : 0;
-  const size_t b_dist = dist ? scx_align16(sizeof(double) * total) : 0, b_shift = shift ? sizeof(int) * total : 0;
-  std::vector<char> blob(b_rows + b_cols);
-  if (rows) std::memcpy(blob.data(), rows, sizeof(int) * n_rows);
-  if (cols) std::memcpy(blob.data() + b_rows, cols, sizeof(int) * n_cols);
-  GORIO_HIP_CHECK(sc_fail, hipSetDevice(Q->device));
-  if (scx_reserve(Q, blob.size(), b_dist + b_shift)) return GORIO_ERR_ALLOC;
-  if (!blob.empty()) GORIO_HIP_CHECK(sc_fail, hipMemcpyAsync(Q->d_px_in, blob.data(), blob.size(), hipMemcpyHostToDevice, Q->stream));
-  gorio::ScTileArgs A{};
-  A.rows = rows ? (const int*)Q->d_px_in.get() : nullptr;
-  A.cols = cols ? (const int*)((const char*)Q->d_px_in.get() + b_rows) : nullptr;
-  A.n_rows = n_rows, A.n_cols = n_cols;
-  A.n_ctiles = (n_cols + gorio::kScTileC - 1) / gorio::kScTileC;
-  A.run_tiles = 1, A.n_runs = A.n_ctiles;
-  A.dist = dist ? (double*)Q->d_px_out.get() : nullptr;
-  A.shift = shift ? (int*)((char*)Q->d_px_out.get() + b_dist) : nullptr;
-  const long long n_groups = (long long)((n_rows + gorio::kScTileR - 1) / gorio::kScTileR) * A.n_ctiles;  // <= 2^31 / 8 + n_rows + n_cols
-  hipLaunchKernelGGL(gorio::sc_xtile_kernel, dim3((unsigned)n_groups), dim3(gorio::kScTileThreads), 0, Q->stream, A, Q->db(), D->db());
-  GORIO_HIP_CHECK(sc_fail, hipGetLastError());
-  if (dist) GORIO_HIP_CHECK(sc_fail, hipMemcpyAsync(dist, A.dist, sizeof(double) * total, hipMemcpyDeviceToHost, Q->stream));
-  if (shift) GORIO_HIP_CHECK(sc_fail, hipMemcpyAsync(shift, A.shift, sizeof(int) * total, hipMemcpyDeviceToHost, Q->stream));
-  GORIO_HIP_CHECK(sc_fail, hipStreamSynchronize(Q->stream));
-  scc_count(Q, total, 1);
-  return GORIO_OK;
+  if (sc_check_handles(Q, D, "cross_distance_matrix")) return GORIO_ERR_INVALID;
+  return sc_distance_matrix(sc_two_handles(Q, D, "cross_distance_matrix"), rows, n_rows, cols, n_cols, dist, shift);
 }
 
 int gorio_sc_cross_top_matches(gorio_sc_t* Q, const int* rows, int n_rows, gorio_sc_t* D, const int* col_end, int k, int* index, double* dist, int* shift) {
-  if (scc_check_handles(Q, D, "cross_top_matches")) return GORIO_ERR_INVALID;
-  if (n_rows < 0) return sc_fail(GORIO_ERR_INVALID, "cross_top_matches: negative extent");
+  if (sc_check_handles(Q, D, "cross_top_matches")) return GORIO_ERR_INVALID;
+  const ScSides S = sc_two_handles(Q, D, "cross_top_matches");
+  if (n_rows < 0) return sc_refuse(S, GORIO_ERR_INVALID, "negative extent");
   if (n_rows == 0) return GORIO_OK;
-  if (!index || !dist) return sc_fail(GORIO_ERR_INVALID, "cross_top_matches: null output");
-  if (k < 1) return sc_fail(GORIO_ERR_INVALID, "cross_top_matches: k = " + std::to_string(k) + " must be >= 1");
-  if (k > GORIO_SC_TOP_MAX)
-    return sc_fail(GORIO_ERR_UNSUPPORTED, "cross_top_matches: k = " + std::to_string(k) + " exceeds GORIO_SC_TOP_MAX = " + std::to_string(GORIO_SC_TOP_MAX));
-  if (scc_check_indices(Q, true, "cross_top_matches", "rows", rows, n_rows)) return GORIO_ERR_INVALID;
+  if (!index || !dist) return sc_refuse(S, GORIO_ERR_INVALID, "null output");
+  if (k < 1) return sc_refuse(S, GORIO_ERR_INVALID, "k = " + std::to_string(k) + " must be >= 1");
+  if (k > GORIO_SC_TOP_MAX) return sc_refuse(S, GORIO_ERR_UNSUPPORTED, "k = " + std::to_string(k) + " exceeds GORIO_SC_TOP_MAX = " + std::to_string(GORIO_SC_TOP_MAX));
+  if (sc_check_indices(S, true, "rows", rows, n_rows)) return GORIO_ERR_INVALID;
   int n_cols = col_end ? 0 : D->n;  // the largest col_end
   long long pairs = col_end ? 0 : (long long)n_rows * D->n;
   if (col_end)
     for (int i = 0; i < n_rows; ++i) {
       if (col_end[i] < 0 || col_end[i] > D->n)
-        return sc_fail(GORIO_ERR_INVALID, "cross_top_matches: col_end[" + std::to_string(i) + "] = " + std::to_string(col_end[i]) + " is outside 0 .. " + std::to_string(D->n) +
-                                              ", the scan count of the database handle");
+        return sc_refuse(S, GORIO_ERR_INVALID, "col_end[" + std::to_string(i) + "] = " + std::to_string(col_end[i]) + " is outside 0 .. " + std::to_string(D->n) + ", the scan count of the database handle");
       n_cols = std::max(n_cols, col_end[i]);
       pairs += col_end[i];
     }
@@ -359,19 +226,16 @@ int gorio_sc_cross_top_matches(gorio_sc_t* Q, const int* rows, int n_rows, gorio
     gorio::ScTopArgs A{};
     A.n_rows = n_rows, A.n_cols = n_cols, A.k = k;
     A.n_ctiles = (n_cols + gorio::kScTileC - 1) / gorio::kScTileC;
-    // enough column runs for about 2048 workgroups, as in gorio_sc_best_matches: the partial lists stay O(k * (n_rows + 8 * 2048))
-    const int want_runs = std::min(A.n_ctiles, std::max(1, 2048 / n_rtiles));
-    A.run_tiles = (A.n_ctiles + want_runs - 1) / want_runs;
-    A.n_runs = (A.n_ctiles + A.run_tiles - 1) / A.run_tiles;
+    sc_size_runs(n_rtiles, A.n_ctiles, &A.run_tiles, &A.n_runs);
     const size_t n_partial = (size_t)n_rows * A.n_runs * k;
-    if (n_partial > (size_t)INT_MAX) return sc_fail(GORIO_ERR_UNSUPPORTED, "cross_top_matches: too many rows");
+    if (n_partial > (size_t)INT_MAX) return sc_refuse(S, GORIO_ERR_UNSUPPORTED, "too many rows");
     // upload: rows | col_end
-    const size_t b_rows = rows ? scx_align16(sizeof(int) * (size_t)n_rows) : 0, b_end = col_end ? sizeof(int) * (size_t)n_rows : 0;
+    const size_t b_rows = rows ? sc_align16(sizeof(int) * (size_t)n_rows) : 0, b_end = col_end ? sizeof(int) * (size_t)n_rows : 0;
     std::vector<char> blob(b_rows + b_end);
     if (rows) std::memcpy(blob.data(), rows, sizeof(int) * (size_t)n_rows);
     if (col_end) std::memcpy(blob.data() + b_rows, col_end, b_end);
     GORIO_HIP_CHECK(sc_fail, hipSetDevice(Q->device));
-    if (scx_reserve(Q, blob.size(), sizeof(gorio::ScBest) * (n_partial + n_out))) return GORIO_ERR_ALLOC;
+    if (sc_reserve(Q, blob.size(), sizeof(gorio::ScBest) * (n_partial + n_out))) return GORIO_ERR_ALLOC;
     if (!blob.empty()) GORIO_HIP_CHECK(sc_fail, hipMemcpyAsync(Q->d_px_in, blob.data(), blob.size(), hipMemcpyHostToDevice, Q->stream));
     A.rows = rows ? (const int*)Q->d_px_in.get() : nullptr;
     A.col_end = col_end ? (const int*)((const char*)Q->d_px_in.get() + b_rows) : nullptr;
@@ -382,7 +246,7 @@ int gorio_sc_cross_top_matches(gorio_sc_t* Q, const int* rows, int n_rows, gorio
     GORIO_HIP_CHECK(sc_fail, hipGetLastError());
     GORIO_HIP_CHECK(sc_fail, hipMemcpyAsync(res.data(), d_res, sizeof(gorio::ScBest) * n_out, hipMemcpyDeviceToHost, Q->stream));
     GORIO_HIP_CHECK(sc_fail, hipStreamSynchronize(Q->stream));
-    scc_count(Q, pairs, 2);
+    sc_charge(S, pairs, 2);
   }
   for (size_t i = 0; i < n_out; ++i) {
     index[i] = res[i].c;
@@ -393,69 +257,14 @@ int gorio_sc_cross_top_matches(gorio_sc_t* Q, const int* rows, int n_rows, gorio
 }
 
 int gorio_sc_cross_detect(gorio_sc_t* Q, gorio_sc_t* D, int count, const int* qidx, const int* const* cands, const int* ncand, int* loop_id, float* yaw_rad, double* min_dist) {
-  if (scc_check_handles(Q, D, "cross_detect")) return GORIO_ERR_INVALID;
-  if (count < 0) return sc_fail(GORIO_ERR_INVALID, "cross_detect: count < 0");
-  if (count == 0) return GORIO_OK;
-  if (!qidx || !cands || !ncand || !loop_id || !yaw_rad || !min_dist) return sc_fail(GORIO_ERR_INVALID, "cross_detect: null argument");
-  size_t total = 0;
-  for (int i = 0; i < count; ++i) {
-    const std::string at = " (query " + std::to_string(i) + ")";
-    if (qidx[i] < 0 || qidx[i] >= Q->n)
-      return sc_fail(GORIO_ERR_INVALID, "cross_detect: query index " + std::to_string(qidx[i]) + " has not been added to the query handle (" + std::to_string(Q->n) + " scans)" + at);
-    if (ncand[i] <= 0 || !cands[i]) return sc_fail(GORIO_ERR_INVALID, "cross_detect: empty candidate list" + at);
-    for (int j = 0; j < ncand[i]; ++j)
-      if (cands[i][j] < 0 || cands[i][j] >= D->n)
-        return sc_fail(GORIO_ERR_INVALID, "cross_detect: candidate " + std::to_string(j) + " = " + std::to_string(cands[i][j]) + " has not been added to the database handle (" +
-                                              std::to_string(D->n) + " scans)" + at);
-    total += ncand[i];
-  }
-  if (total > (size_t)INT_MAX) return sc_fail(GORIO_ERR_UNSUPPORTED, "cross_detect: more than 2^31 - 1 candidates in all");
-  // CSR of the lists as they are: one segment per query, no early return and no recent-keyframe filter
-  std::vector<gorio::ScPairRef> tab;
-  tab.reserve(total);
-  std::vector<int> off(1, 0);
-  for (int i = 0; i < count; ++i) {
-    for (int j = 0; j < ncand[i]; ++j) tab.push_back(gorio::ScPairRef{qidx[i], cands[i][j]});
-    off.push_back((int)tab.size());
-  }
-  const int n_pairs = (int)tab.size();
-  std::vector<gorio::ScBest> res(count);
-  const size_t b_tab = scx_align16(sizeof(gorio::ScPairRef) * tab.size()), b_off = sizeof(int) * off.size();
-  std::vector<char> blob(b_tab + b_off);
-  std::memcpy(blob.data(), tab.data(), sizeof(gorio::ScPairRef) * tab.size());
-  std::memcpy(blob.data() + b_tab, off.data(), b_off);
-  GORIO_HIP_CHECK(sc_fail, hipSetDevice(Q->device));
-  if (scx_reserve(Q, blob.size(), sizeof(gorio::ScBest) * (tab.size() + count))) return GORIO_ERR_ALLOC;
-  GORIO_HIP_CHECK(sc_fail, hipMemcpyAsync(Q->d_px_in, blob.data(), blob.size(), hipMemcpyHostToDevice, Q->stream));
-  gorio::ScBest* items = (gorio::ScBest*)Q->d_px_out.get();
-  gorio::ScBest* d_res = items + tab.size();
-  hipLaunchKernelGGL(gorio::sc_xpairs_kernel, dim3((unsigned)(((long long)n_pairs + 3) / 4)), dim3(gorio::kScThreads), 0, Q->stream, (const gorio::ScPairRef*)Q->d_px_in.get(), n_pairs,
-                     Q->db(), D->db(), items);
-  hipLaunchKernelGGL(gorio::sc_rowmin_kernel, dim3((unsigned)((count + 3) / 4)), dim3(gorio::kScThreads), 0, Q->stream, (const gorio::ScBest*)items,
-                     (const int*)((const char*)Q->d_px_in.get() + b_tab), count, d_res);
-  GORIO_HIP_CHECK(sc_fail, hipGetLastError());
-  GORIO_HIP_CHECK(sc_fail, hipMemcpyAsync(res.data(), d_res, sizeof(gorio::ScBest) * count, hipMemcpyDeviceToHost, Q->stream));
-  GORIO_HIP_CHECK(sc_fail, hipStreamSynchronize(Q->stream));
-  scc_count(Q, n_pairs, 2);
-  const double unit = (Q->p.azimuth_range - (-Q->p.azimuth_range)) / double(GORIO_SC_SECTORS);  // PC_UNIT_SECTOR_ANGLE (SC:72)
-  for (int i = 0; i < count; ++i) {
-    const gorio::ScBest& o = res[i];
-    const int nn_idx = o.c < 0 ? 0 : o.c, nn_align = o.c < 0 ? 0 : o.s;  // SC:312-314: the values the loop starts from
-    loop_id[i] = o.d < Q->p.sc_dist_thresh ? nn_idx : -1;                // SC:354-356
-    const float deg = (float)(nn_align * unit);                          // deg2rad(float degrees) (SC:18-21, 369)
-    yaw_rad[i] = (float)((double)deg * M_PI / 180.0);
-    min_dist[i] = o.d;
-  }
-  return GORIO_OK;
+  if (sc_check_handles(Q, D, "cross_detect")) return GORIO_ERR_INVALID;
+  // no early return and no recent-keyframe filter: the indices of two sessions are unrelated
+  return sc_detect_lists(sc_two_handles(Q, D, "cross_detect"), false, count, qidx, cands, ncand, loop_id, yaw_rad, min_dist);
 }
 
 int gorio_sc_cross_counters(const gorio_sc_t* Q, long long* calls, long long* pairs, long long* launches, long long* synchronisations) {
   if (!Q) return sc_fail(GORIO_ERR_INVALID, "cross_counters: null handle");
-  if (calls) *calls = Q->cx_calls;
-  if (pairs) *pairs = Q->cx_pairs;
-  if (launches) *launches = Q->cx_launches;
-  if (synchronisations) *synchronisations = Q->cx_syncs;
-  return GORIO_OK;
+  return sc_read_counters(Q->cx, calls, pairs, launches, synchronisations);
 }
 
 }  // extern "C"

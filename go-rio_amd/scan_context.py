@@ -157,26 +157,51 @@ class ScanContext:
         a = np.ascontiguousarray(a, np.int32).reshape(-1)
         return a, int(a.size)
 
-    def distance_pairs(self, q, c):
-        """d(q[k], c[k]) for listed pairs in one launch -> (dist [count] float64, shift [count] int32)."""
+    def _pairs(self, name, fn, handles, q, c):
         q = np.ascontiguousarray(q, np.int32).reshape(-1)
         c = np.ascontiguousarray(c, np.int32).reshape(-1)
         if q.size != c.size:
-            raise ValueError("distance_pairs: q and c differ in length")
+            raise ValueError(f"{name}: q and c differ in length")
         dist, shift = np.zeros(q.size, np.float64), np.zeros(q.size, np.int32)
-        self._check(self.lib.gorio_sc_distance_pairs(self.h, _ptr(q), _ptr(c), int(q.size), _ptr(dist), _ptr(shift)))
+        self._check(fn(*handles, _ptr(q), _ptr(c), int(q.size), _ptr(dist), _ptr(shift)))
         return dist, shift
+
+    def _matrix(self, fn, other, rows, cols, want_dist, want_shift):
+        """other None: the one-handle call, whose columns are this handle's and which takes no second handle before them."""
+        r, nr = self._indices(rows)
+        c, nc = (self if other is None else other)._indices(cols)
+        dist = np.zeros((nr, nc), np.float64) if want_dist else None
+        shift = np.zeros((nr, nc), np.int32) if want_shift else None
+        col_handle = [] if other is None else [other.h]
+        self._check(fn(self.h, None if r is None else _ptr(r), nr, *col_handle, None if c is None else _ptr(c), nc,
+                       None if dist is None else _ptr(dist), None if shift is None else _ptr(shift)))
+        return dist, shift
+
+    def _detect_lists(self, name, fn, handles, query_indices, candidate_lists):
+        k = len(query_indices)
+        cands = [np.ascontiguousarray(c, np.int32).reshape(-1) for c in candidate_lists]
+        if len(cands) != k:
+            raise ValueError(f"{name}: one candidate list per query")
+        Q = (C.c_int * k)(*[int(q) for q in query_indices])
+        P = (C.c_void_p * k)(*[c.__array_interface__["data"][0] if c.size else None for c in cands])
+        N = (C.c_int * k)(*[c.size for c in cands])
+        lid, yaw, md = (C.c_int * k)(), (C.c_float * k)(), (C.c_double * k)()
+        self._check(fn(*handles, k, Q, P, N, lid, yaw, md))
+        return [(lid[i], np.float32(yaw[i]), md[i]) for i in range(k)]
+
+    def _counters(self, fn):
+        v = [C.c_longlong() for _ in range(4)]
+        self._check(fn(self.h, *[C.byref(x) for x in v]))
+        return dict(zip(("calls", "pairs", "launches", "synchronisations"), [x.value for x in v]))
+
+    def distance_pairs(self, q, c):
+        """d(q[k], c[k]) for listed pairs in one launch -> (dist [count] float64, shift [count] int32)."""
+        return self._pairs("distance_pairs", self.lib.gorio_sc_distance_pairs, (self.h,), q, c)
 
     def distance_matrix(self, rows=None, cols=None, want_dist=True, want_shift=True):
         """d(rows[i], cols[j]) for every pair -> (dist [n_rows, n_cols] float64, shift int32); None for rows / cols means every scan,
         an output not wanted comes back as None."""
-        r, nr = self._indices(rows)
-        c, nc = self._indices(cols)
-        dist = np.zeros((nr, nc), np.float64) if want_dist else None
-        shift = np.zeros((nr, nc), np.int32) if want_shift else None
-        self._check(self.lib.gorio_sc_distance_matrix(self.h, None if r is None else _ptr(r), nr, None if c is None else _ptr(c), nc,
-                                                      None if dist is None else _ptr(dist), None if shift is None else _ptr(shift)))
-        return dist, shift
+        return self._matrix(self.lib.gorio_sc_distance_matrix, None, rows, cols, want_dist, want_shift)
 
     def best_matches(self, rows=None, min_gap=EXCLUDE_RECENT):
         """Per row r the minimum of d(r, c) over 0 <= c <= r - min_gap, ties to the lower c -> (index [n] int32, dist [n] float64,
@@ -189,44 +214,21 @@ class ScanContext:
     def detect_exhaustive(self, query_indices, candidate_lists):
         """detectLoopClosureID with the tree stage replaced by all candidates, for every query in one pass -> list of (loop_id, yaw_rad
         (float32), min_dist).  Stateless: counter and snapshot are untouched."""
-        k = len(query_indices)
-        cands = [np.ascontiguousarray(c, np.int32).reshape(-1) for c in candidate_lists]
-        if len(cands) != k:
-            raise ValueError("detect_exhaustive: one candidate list per query")
-        Q = (C.c_int * k)(*[int(q) for q in query_indices])
-        P = (C.c_void_p * k)(*[c.__array_interface__["data"][0] if c.size else None for c in cands])
-        N = (C.c_int * k)(*[c.size for c in cands])
-        lid, yaw, md = (C.c_int * k)(), (C.c_float * k)(), (C.c_double * k)()
-        self._check(self.lib.gorio_sc_detect_exhaustive(self.h, k, Q, P, N, lid, yaw, md))
-        return [(lid[i], np.float32(yaw[i]), md[i]) for i in range(k)]
+        return self._detect_lists("detect_exhaustive", self.lib.gorio_sc_detect_exhaustive, (self.h,), query_indices, candidate_lists)
 
     def pairs_counters(self):
-        v = [C.c_longlong() for _ in range(4)]
-        self._check(self.lib.gorio_sc_pairs_counters(self.h, *[C.byref(x) for x in v]))
-        return dict(zip(("calls", "pairs", "launches", "synchronisations"), [x.value for x in v]))
+        return self._counters(self.lib.gorio_sc_pairs_counters)
 
     # ---- include/gorio_sc_cross.h: this handle is the query side, `other` the database side (only read); every value has the bits
     # distance() gives on a handle that holds both descriptors
     def cross_distance_pairs(self, other, q, c):
         """d(self[q[k]], other[c[k]]) for listed pairs in one launch -> (dist [count] float64, shift [count] int32)."""
-        q = np.ascontiguousarray(q, np.int32).reshape(-1)
-        c = np.ascontiguousarray(c, np.int32).reshape(-1)
-        if q.size != c.size:
-            raise ValueError("cross_distance_pairs: q and c differ in length")
-        dist, shift = np.zeros(q.size, np.float64), np.zeros(q.size, np.int32)
-        self._check(self.lib.gorio_sc_cross_distance_pairs(self.h, other.h, _ptr(q), _ptr(c), int(q.size), _ptr(dist), _ptr(shift)))
-        return dist, shift
+        return self._pairs("cross_distance_pairs", self.lib.gorio_sc_cross_distance_pairs, (self.h, other.h), q, c)
 
     def cross_distance_matrix(self, other, rows=None, cols=None, want_dist=True, want_shift=True):
         """d(self[rows[i]], other[cols[j]]) for every pair -> (dist [n_rows, n_cols] float64, shift int32); None for rows means every scan
         of this handle, for cols every scan of `other`; an output not wanted comes back as None."""
-        r, nr = self._indices(rows)
-        c, nc = other._indices(cols)
-        dist = np.zeros((nr, nc), np.float64) if want_dist else None
-        shift = np.zeros((nr, nc), np.int32) if want_shift else None
-        self._check(self.lib.gorio_sc_cross_distance_matrix(self.h, None if r is None else _ptr(r), nr, other.h, None if c is None else _ptr(c), nc,
-                                                            None if dist is None else _ptr(dist), None if shift is None else _ptr(shift)))
-        return dist, shift
+        return self._matrix(self.lib.gorio_sc_cross_distance_matrix, other, rows, cols, want_dist, want_shift)
 
     def top_matches(self, other=None, rows=None, col_end=None, k=3):
         """Per row r of this handle the k best of d(r, c) over the scans 0 <= c < col_end[i] of `other` (None: this handle itself; col_end
@@ -247,18 +249,7 @@ class ScanContext:
     def cross_detect(self, other, query_indices, candidate_lists):
         """For every query of this handle the strict minimum of d(query, c) over its list of `other`'s scans, in list order, with this
         handle's threshold -> list of (loop_id, yaw_rad (float32), min_dist).  No early return, no recent-keyframe filter."""
-        k = len(query_indices)
-        cands = [np.ascontiguousarray(c, np.int32).reshape(-1) for c in candidate_lists]
-        if len(cands) != k:
-            raise ValueError("cross_detect: one candidate list per query")
-        Q = (C.c_int * k)(*[int(q) for q in query_indices])
-        P = (C.c_void_p * k)(*[c.__array_interface__["data"][0] if c.size else None for c in cands])
-        N = (C.c_int * k)(*[c.size for c in cands])
-        lid, yaw, md = (C.c_int * k)(), (C.c_float * k)(), (C.c_double * k)()
-        self._check(self.lib.gorio_sc_cross_detect(self.h, other.h, k, Q, P, N, lid, yaw, md))
-        return [(lid[i], np.float32(yaw[i]), md[i]) for i in range(k)]
+        return self._detect_lists("cross_detect", self.lib.gorio_sc_cross_detect, (self.h, other.h), query_indices, candidate_lists)
 
     def cross_counters(self):
-        v = [C.c_longlong() for _ in range(4)]
-        self._check(self.lib.gorio_sc_cross_counters(self.h, *[C.byref(x) for x in v]))
-        return dict(zip(("calls", "pairs", "launches", "synchronisations"), [x.value for x in v]))
+        return self._counters(self.lib.gorio_sc_cross_counters)

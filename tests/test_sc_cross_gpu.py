@@ -1,8 +1,8 @@
 """The cross-database Scan Context calls (include/gorio_sc_cross.h) on the MI355X, over the two databases of tests/sc_cross_scenes.py
 (A: 29 keyframes, the query side unless said otherwise; B: 19 keyframes): every distance bit for bit what the restatement
 (tests/sc_cross_restatement.py) and a merged handle give, the K best per row against a plain stable sort of the matrix, the detect over
-lists, statelessness of both handles against twins, a database that grows between calls, the launch structure through the counters and
-the refusals."""
+lists, statelessness of both handles against twins, a database that grows between calls, the launch structure through the counters,
+the calls of both headers in two orders on one pair of handles, and the refusals."""
 import ctypes as C
 
 import numpy as np
@@ -312,6 +312,63 @@ def test_counters_pin_the_launch_structure(fresh):
     assert step(all_zero) == ZERO and (idx == -1).all() and (best == sr.BIG).all() and (arg == 0).all()
     assert step(lambda: a.cross_detect(b, [], [])) == ZERO
     assert a.pairs_counters() == ZERO and b.pairs_counters() == ZERO and b.cross_counters() == ZERO
+
+
+def _int_columns(result):
+    """A call's result as integer arrays: a detect's list of (loop_id, yaw_rad, min_dist) by column, float64 viewed as int64 and float32
+    as int32."""
+    if isinstance(result, list):
+        result = (np.array([r[0] for r in result]), np.array([r[1] for r in result], F), np.array([r[2] for r in result], np.float64))
+    return [a.view(np.int64) if a.dtype == np.float64 else a.view(np.int32) if a.dtype == F else a for a in map(np.asarray, result)]
+
+
+def test_call_order_does_not_matter(gorio, world):
+    """The eight calls of the two headers share two runners and one pair of scratch buffers on the query handle.  Each call's result on
+    a fresh pair of handles is the reference; all eight then run on one pair of handles in two interleavings, one ending each family with
+    its largest request (the whole matrix) and one with its smallest (a few listed pairs), top_matches before a matrix and a detect after
+    best_matches, so partial tables and segment offsets lie in the buffers the next call uses.  Every result has the reference's bits,
+    and each counter group advances by its own family's four calls."""
+    lists = _lists()
+    cq = [1, 5, 7, 28, 14]
+    eq = [28, 3, 20, 12]  # 3 returns early; 25 lies after its query 20 and is kept (SC:300); 3 is too recent for 12
+    el = [np.arange(28), [0, 1], [5, 15, 25, 10], [0, 1, 2, 3]]
+    kept = sum(1 for q, cand in zip(eq, el) if q >= 10 for c in cand if c > q or q - c >= 10)
+    assert kept == 19 + 3 + 3
+    calls = {  # name: (family, pairs, launches, the call)
+        "distance_pairs": ("pairs", 5, 1, lambda a, b: a.distance_pairs([3, cs.A_EMPTY, 27, 0, 13], [27, 4, cs.A_NARROW, 0, 2])),
+        "distance_matrix": ("pairs", 29 * 29, 1, lambda a, b: a.distance_matrix()),
+        "best_matches": ("pairs", 29 * 28 // 2, 2, lambda a, b: a.best_matches(None, 1)),
+        "detect_exhaustive": ("pairs", kept, 2, lambda a, b: a.detect_exhaustive(eq, el)),
+        "cross_distance_pairs": ("cross", 7, 1, lambda a, b: a.cross_distance_pairs(b, [cs.A_EMPTY, 3, cs.A_NARROW, 28, 0, 9, 9], [3, cs.B_EMPTY, cs.B_TIED[1], 18, 0, 7, 7])),
+        "cross_distance_matrix": ("cross", 29 * 19, 1, lambda a, b: a.cross_distance_matrix(b)),
+        "top_matches": ("cross", int(MIXED.sum()), 2, lambda a, b: a.top_matches(b, None, MIXED, 3)),
+        "cross_detect": ("cross", sum(len(lists[q]) for q in cq), 2, lambda a, b: a.cross_detect(b, cq, [lists[q] for q in cq])),
+    }
+
+    def pair_of_handles():
+        a, b = gorio.ScanContext(), gorio.ScanContext()
+        a.add_scans(world["scans_a"]), b.add_scans(world["scans_b"])
+        return a, b
+
+    want = {}
+    for name, (_, _, _, fn) in calls.items():
+        a, b = pair_of_handles()
+        want[name] = _int_columns(fn(a, b))
+        a.close(), b.close()
+    assert (want["detect_exhaustive"][0] >= 0).any() and (want["cross_detect"][0] >= 0).any() and (want["best_matches"][0] >= 0).any()
+    largest_last = ["cross_distance_pairs", "top_matches", "distance_pairs", "best_matches", "cross_detect", "detect_exhaustive", "cross_distance_matrix", "distance_matrix"]
+    smallest_last = ["top_matches", "cross_distance_matrix", "best_matches", "detect_exhaustive", "distance_matrix", "cross_detect", "distance_pairs", "cross_distance_pairs"]
+    for order in (largest_last, smallest_last):
+        assert sorted(order) == sorted(calls)
+        a, b = pair_of_handles()
+        for name in order:
+            got = _int_columns(calls[name][3](a, b))
+            assert len(got) == len(want[name]) and all(np.array_equal(g, w) for g, w in zip(got, want[name])), (order[-1], name)
+        for family, counters in (("pairs", a.pairs_counters()), ("cross", a.cross_counters())):
+            mine = [c for c in calls.values() if c[0] == family]
+            assert counters == dict(calls=4, pairs=sum(c[1] for c in mine), launches=sum(c[2] for c in mine), synchronisations=4), family
+        assert b.pairs_counters() == ZERO and b.cross_counters() == ZERO
+        a.close(), b.close()
 
 
 def test_errors_change_nothing(gorio, world, fresh):
